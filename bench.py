@@ -2,6 +2,7 @@
 """bench.py — headline benchmark of the antialiased resample hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json metric / configs[1]): uint8 channels_last [B,3,438,906] -> [196,320] bilinear antialias,
 Pillow-exact arithmetic, B images per GPU resident in HBM before the timed region (B=1024 -> 1.22 GB in, far beyond
@@ -9,10 +10,15 @@ the 256 MB Infinity Cache).  A "step" is one pass of the hot path over one such 
 (weak scaling: fixed per-GPU batch); the only collective is the broadcast of the packed weight tables, outside
 the timed region.  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times the K steps, writes the last step's output if --dump-outputs is given, and prints the
+line.  Everything else it can measure or check runs with --full only: the parity spot-check against the CPU oracle
+(max_abs_err_vs_oracle), the committed counter traffic and the live copy ceiling of the roofline, the short timings of the
+other BASELINE configs (secondary) and the CPU baseline.
+
 roofline: dominant kernel's ALGORITHMIC bytes per launch (read input once + write output once = 1,378,644 B/image
 for this config) ÷ its average duration measured here with HIP events on the launch stream.
-cpu_baseline: the reference's own step_three separable C++ (oracle/_ref/ref_s3sep.so, built from /root/reference in
-the build container) timed on this box's host cores on a bounded sample; falls back to our C port (kind "port").
+cpu_baseline: the reference's own step_three separable C++ (oracle/_ref/ref_s3sep.so, built by oracle/Makefile where the
+reference checkout exists) timed on the host cores on a bounded sample; falls back to our C port (kind "port").
 """
 import argparse
 import json
@@ -31,6 +37,7 @@ import torch.distributed as dist  # noqa: E402
 H_IN, W_IN, H_OUT, W_OUT, CH = 438, 906, 196, 320, 3
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, which also quotes a 6.29 TB/s float4-copy ceiling)
 GUIDE_COPY_CEILING_GBS = 6290.0
+DUMP_IMAGES = 64  # --dump-outputs: at most 64 output images x 188,160 values x 4 B = 48 MB
 PMC_SUMMARIES = {  # dominant kernel -> committed rocprofv3 --pmc summary (separate FETCH_SIZE / WRITE_SIZE passes), newest first
     "fused_u8_nhwc_pil_v3": ("r03_pmc_fused_v3.json", "r02_pmc_fused_v3.json", "r01_pmc_fused_v3.json"),
     "fused_u8_nhwc_pil": ("r01_pmc_fused_v1.json",),
@@ -63,6 +70,16 @@ def pmc_traffic_bytes(variant: str, batch: int):
         stale = stamped is None or now is None or stamped != now
         return int((2.0 * fetch + write) * 1024 * batch / pmc_batch), f"profiles/{name} (batch {pmc_batch}, sources {stamped})", stale
     return None, None, None
+
+
+def dump_outputs(out_dir: str, y: torch.Tensor) -> None:
+    """--dump-outputs: the timed path's output `y` (uint8 [B,3,H,W]) as float32 NCHW in out_dir/output.npy — every image when
+    B <= DUMP_IMAGES, else DUMP_IMAGES images chosen by a fixed seed (the same ones for the same --batch), in batch order."""
+    B = y.shape[0]
+    idx = np.arange(B) if B <= DUMP_IMAGES else np.sort(np.random.default_rng(0).choice(B, DUMP_IMAGES, replace=False))
+    sample = y[torch.from_numpy(idx).to(y.device)].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "output.npy"), np.ascontiguousarray(sample))
 
 
 def measure_copy_ceiling(dev, nbytes=2 << 30, reps=10):
@@ -305,10 +322,16 @@ def parse_args(argv=None):
                     help="untimed spin-up before the W warm-up steps: the GPU needs ~20 ms of work to reach its sustained clock "
                          "(a 5-step warm-up under-reports the steady state by 8 %%, see DESIGN.md section 5)")
     ap.add_argument("--batch", type=int, default=1024, help="images per GPU per step")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short timings of the other BASELINE configs")
-    ap.add_argument("--with-atomics", action="store_true", help="secondary: also time the scatter-add atomics form of the backward (API parity path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the oracle spot-check, the roofline's traffic and copy ceiling, the secondary "
+                         "configs and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help=f"write the last timed step's output (rank 0) to DIR/output.npy as float32 [k,3,{H_OUT},{W_OUT}] NCHW: all "
+                         f"images of the batch, or {DUMP_IMAGES} picked with a fixed seed when the batch is larger")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the short timings of the other BASELINE configs")
+    ap.add_argument("--with-atomics", action="store_true", help="--full, secondary: also time the scatter-add atomics form of the backward (API parity path)")
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="exercise the rank launcher only: every rank prints its rendezvous environment and exits before any "
                          "GPU call; rank 0 also prints the bench line's skeleton (n_gpus, global_batch).  Runs without a GPU.")
@@ -398,6 +421,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.force_launcher):
         raise SystemExit(launch_ranks(args, argv))
 
@@ -479,21 +504,26 @@ def main(argv=None):
     total_images = sharding.reduce_sum_int(B * args.steps, dev)
 
     if rank == 0:
-        # parity spot-check of what was just timed (image 0 of rank 0) against the oracle
-        import oracle
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, y)
+        max_abs_e, traffic, traffic_src, traffic_stale, ceiling, ceiling_forms = None, None, None, None, None, {}
+        if args.full:
+            # parity spot-check of what was just timed (image 0 of rank 0) against the oracle
+            import oracle
 
-        max_abs_e = 0
-        for i in sorted({0, B // 2, B - 1}):  # first, middle and last image of the batch that was timed
-            exp = oracle.pil_resize_u8("linear", x[i:i + 1].cpu().numpy(), (H_OUT, W_OUT))
-            max_abs_e = max(max_abs_e, int(np.abs(y[i:i + 1].cpu().numpy().astype(int) - exp.astype(int)).max()))
+            max_abs_e = 0
+            for i in sorted({0, B // 2, B - 1}):  # first, middle and last image of the batch that was timed
+                exp = oracle.pil_resize_u8("linear", x[i:i + 1].cpu().numpy(), (H_OUT, W_OUT))
+                max_abs_e = max(max_abs_e, int(np.abs(y[i:i + 1].cpu().numpy().astype(int) - exp.astype(int)).max()))
+            traffic, traffic_src, traffic_stale = pmc_traffic_bytes(variant, B)
         mpix_s = total_images * H_IN * W_IN / wall / 1e6
         alg_bytes_img = CH * H_IN * W_IN + CH * H_OUT * W_OUT  # 1,378,644
         kern_ms = ev_ms / args.steps  # one hot-path pass per step
         achieved = alg_bytes_img * B / (kern_ms * 1e-3) / 1e9
-        traffic, traffic_src, traffic_stale = pmc_traffic_bytes(variant, B)
         in_bytes_img = CH * H_IN * W_IN
         del y
-        ceiling, ceiling_forms = measure_copy_ceiling(dev) if world == 1 else (None, {})  # (after the timed region; N = 1 only)
+        if args.full and world == 1:  # (after the timed region; N = 1 only)
+            ceiling, ceiling_forms = measure_copy_ceiling(dev)
         out = {
             "metric": "Mpix/s (input pixels) antialiased bilinear 438x906->196x320, uint8 channels_last, PIL-exact",
             "value": round(mpix_s, 1), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -518,8 +548,11 @@ def main(argv=None):
                          "frac_of_guide_copy_ceiling_6290": round(achieved / GUIDE_COPY_CEILING_GBS, 4)},
         }
         # secondary workloads, the copy ceiling and the CPU baseline are rank-0-at-N=1 measurements (the contract): an N > 1 line says
-        # so explicitly instead of dropping the keys
-        if world > 1:
+        # so explicitly instead of dropping the keys; so does a plain run, which measures the headline only
+        if not args.full:
+            out["secondary"], out["cpu_baseline"] = None, None
+            out["full_only"] = "max_abs_err_vs_oracle, roofline traffic and copy ceiling, secondary and cpu_baseline are measured with --full only"
+        elif world > 1:
             out["secondary"], out["cpu_baseline"] = None, None
             out["n1_only"] = "secondary, cpu_baseline and the copy ceiling are measured at --gpus 1 only"
         else:

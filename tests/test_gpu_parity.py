@@ -1693,10 +1693,35 @@ def test_bench_rank_path_through_the_launcher():
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-launcher", "--batch", "8", "--steps", "3",
-                          "--warmup", "1", "--prewarm-seconds", "0", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True,
-                         timeout=900, env=env)
+                          "--warmup", "1", "--prewarm-seconds", "0", "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True,
+                         text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["process_group"] == "nccl" and line["max_abs_err_vs_oracle"] == 0
     assert line["value"] > 0 and line["secondary"] is None and line["cpu_baseline"] is None
     assert line["roofline"]["read_frac"] < line["roofline"]["frac"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_what_it_timed(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps, reports ms_per_step and leaves the --full measurements out; --dump-outputs
+    writes the last timed step's output, which is the oracle's result on the seeded input batch."""
+    import json
+    import subprocess
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "8", "--steps", "3", "--warmup", "1",
+                          "--prewarm-seconds", "0", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "Mpix/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["max_abs_err_vs_oracle"] is None and line["secondary"] is None and line["cpu_baseline"] is None
+    assert line["roofline"]["copy_ceiling_measured_GBs"] is None
+    got = np.load(tmp_path / "output.npy")
+    assert got.dtype == np.float32 and got.shape == (8, 3, 196, 320)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0)  # bench.py's input of rank 0
+    x = torch.randint(0, 256, (8, 438, 906, 3), dtype=torch.uint8, device="cuda", generator=gen).permute(0, 3, 1, 2)
+    exp = oracle.pil_resize_u8("linear", x.cpu().numpy(), (196, 320), nthreads=8)
+    assert np.array_equal(got, exp.astype(np.float32))

@@ -236,6 +236,25 @@ def test_bench_launcher_survives_chatty_and_failing_ranks():
     assert out.returncode != 0 and "rank 1 exited with 3" in out.stderr and time.time() - t0 < 120, (out.returncode, out.stderr[-500:])
 
 
+def test_bench_dump_outputs_sample(tmp_path):
+    """--dump-outputs writes float32 NCHW images of the timed output: all of a small batch; of a large one the same seeded
+    sample of bench.DUMP_IMAGES images on every run, in batch order, which at the headline shape stays under 64 MB."""
+    import bench
+
+    assert bench.DUMP_IMAGES * 3 * bench.H_OUT * bench.W_OUT * 4 <= 64 << 20
+    small = torch.randint(0, 256, (5, 4, 6, 3), dtype=torch.uint8).permute(0, 3, 1, 2)  # channels_last, as the bench's output
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(tmp_path / "a" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.float().numpy())
+    big = torch.arange(200, dtype=torch.uint8).view(200, 1, 1, 1).expand(200, 3, 2, 2).contiguous()  # image i holds the value i
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    b, c = np.load(tmp_path / "b" / "output.npy"), np.load(tmp_path / "c" / "output.npy")
+    assert b.shape == (bench.DUMP_IMAGES, 3, 2, 2) and np.array_equal(b, c)
+    picked = b[:, 0, 0, 0]
+    assert np.all(np.diff(picked) > 0) and np.all(b == picked[:, None, None, None])
+
+
 def test_headline_kernel_keeps_six_waves_per_simd(tmp_path):
     """Occupancy regression guard (no GPU needed: read from the built code object).  The headline kernel — uint8 channels_last,
     3 channels, 6-tap windows, 2 open output rows, non-negative weights, periodic slot phases — must stay within 80 VGPRs

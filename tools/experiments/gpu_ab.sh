@@ -7,7 +7,7 @@ for rep in 1 2; do
   for n in "$@"; do
     lib=$PWD/interpolate_antialiasing_amd/csrc/libaa_interp_$n.so
     [ "$n" = "stock" ] && lib=$PWD/interpolate_antialiasing_amd/csrc/libaa_interp.so
-    AA_INTERP_LIB=$lib timeout -k 10 200 python bench.py --steps 100 --warmup 20 --no-secondary --no-cpu-baseline > $OUT/${n}_$rep.json 2> $OUT/${n}_$rep.err || echo "$n failed"
+    AA_INTERP_LIB=$lib timeout -k 10 200 python bench.py --steps 100 --warmup 20 --full --no-secondary --no-cpu-baseline > $OUT/${n}_$rep.json 2> $OUT/${n}_$rep.err || echo "$n failed"
   done
 done
 python - "$OUT" <<'PY'
