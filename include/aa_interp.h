@@ -46,8 +46,12 @@ enum aa_status {
 };
 
 /* Filters: s2.2/aa_interpolation_impl.h:292-300 (triangle), :410-424 (Keys cubic a=-0.5), :367-372 (box;
- * the reference binds it as "nearest_forward": "it's not nearest but box", extension_interpolate.cpp:48). */
-enum aa_filter { AA_FILTER_LINEAR = 0, AA_FILTER_CUBIC = 1, AA_FILTER_BOX = 2 };
+ * the reference binds it as "nearest_forward": "it's not nearest but box", extension_interpolate.cpp:48), and Pillow's other two
+ * antialiasing filters (src/libImaging/Resample.c): Hamming-windowed sinc (support 1) and Lanczos-3 (support 3, negative lobes).
+ * The float table kinds size their windows from interp_size = 2 x support, as the reference does for its three filters.
+ * Hamming and Lanczos were added without an ABI version change (the change is additive): a caller detects a library that predates
+ * them because aa_table_ksize() returns AA_ERR_BAD_FILTER for ids 3 and 4. */
+enum aa_filter { AA_FILTER_LINEAR = 0, AA_FILTER_CUBIC = 1, AA_FILTER_BOX = 2, AA_FILTER_HAMMING = 3, AA_FILTER_LANCZOS = 4 };
 
 /* Element type of the image tensors. */
 enum aa_dtype { AA_U8 = 0, AA_F32 = 1, AA_F64 = 2, AA_F16 = 3, AA_BF16 = 4 };

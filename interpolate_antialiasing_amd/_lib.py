@@ -16,7 +16,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "aa_interp.h")
 
 # enums (include/aa_interp.h)
 AA_OK = 0
-FILTER_LINEAR, FILTER_CUBIC, FILTER_BOX = 0, 1, 2
+FILTER_LINEAR, FILTER_CUBIC, FILTER_BOX, FILTER_HAMMING, FILTER_LANCZOS = 0, 1, 2, 3, 4
 U8, F32, F64, F16, BF16 = 0, 1, 2, 3, 4
 NCHW, NHWC = 0, 1
 TABLE_PIL, TABLE_F32, TABLE_F64 = 0, 1, 2

@@ -14,14 +14,8 @@ namespace {
 thread_local const char *g_last_variant = "none";
 int g_fused_enabled = 1;
 
-int interp_size_of(int filter) {
-  switch (filter) {
-    case AA_FILTER_LINEAR: return 2;  // s2.2/aa_interpolation_impl.h:287
-    case AA_FILTER_CUBIC: return 4;   // :377
-    case AA_FILTER_BOX: return 1;     // :333
-    default: return -1;
-  }
-}
+// (s2.2/aa_interpolation_impl.h:287, :377, :333 for the reference's three filters; aa_common.h's table for all of them)
+int interp_size_of(int filter) { return aa_filter_valid(filter) ? aa_filter_info(filter).interp_size : -1; }
 
 // ATen area_pixel_compute_scale<scalar_t> (UpSample.h; call site s2.2:314-315). scale<=0: not given.
 double scale_for(int kind, int64_t in_size, int64_t out_size, int align_corners, double scale_opt) {
@@ -39,7 +33,7 @@ int ksize_for(int filter, int kind, double scale) {
   const int interp_size = interp_size_of(filter);
   if (kind == AA_TABLE_PIL) {
     // Pillow precompute_coeffs: support = filter.support * max(scale,1); ksize = (int)ceil(support)*2+1
-    const double fs = filter == AA_FILTER_LINEAR ? 1.0 : (filter == AA_FILTER_CUBIC ? 2.0 : 0.5);
+    const double fs = aa_filter_info(filter).support;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
     return (int)ceil(fs * filterscale) * 2 + 1;
   }

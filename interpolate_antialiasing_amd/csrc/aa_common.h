@@ -9,6 +9,32 @@
 #define AA_TABLE_MAGIC 0x42544141
 #define AA_MAX_KSIZE 4096  // generic kernels loop over taps, so this only bounds sanity
 
+// ---- filter properties: the one place host and device read them from -------------------------------------------------
+// support in Pillow's units (Resample.c's filter structs); interp_size = 2 x support is what the float table kinds size windows by
+// (the reference's interp_size for its three filters: 2 / 4 / 1); nonneg: no weight is ever negative, so the fused uint8 kernel's
+// horizontal clip may be a plain shift (aa_fused_u8_v3_impl.h, NONNEG).  Hamming is non-negative on its support: sinc > 0 and
+// 0.54 + 0.46 cos(pi x) >= 0.08 for |x| < 1; Keys cubic and Lanczos have negative lobes.
+struct AAFilterInfo {
+  double support;
+  int interp_size;
+  bool nonneg;
+};
+__host__ __device__ inline bool aa_filter_valid(int filter) { return filter >= AA_FILTER_LINEAR && filter <= AA_FILTER_LANCZOS; }
+__host__ __device__ inline AAFilterInfo aa_filter_info(int filter) {
+  switch (filter) {
+    case AA_FILTER_LINEAR: return {1.0, 2, true};
+    case AA_FILTER_CUBIC: return {2.0, 4, false};
+    case AA_FILTER_BOX: return {0.5, 1, true};
+    case AA_FILTER_HAMMING: return {1.0, 2, true};
+    case AA_FILTER_LANCZOS: return {3.0, 6, false};
+    default: return {0.0, -1, false};  // (callers check aa_filter_valid first)
+  }
+}
+// both axes' filters non-negative: the fused uint8 kernel's NONNEG instantiations apply
+__host__ __device__ inline bool aa_filters_nonneg(int filter_a, int filter_b) {
+  return aa_filter_info(filter_a).nonneg && aa_filter_info(filter_b).nonneg;
+}
+
 // ---- packed table views --------------------------------------------------------------------------------
 __host__ __device__ inline size_t aa_align16(size_t x) { return (x + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t aa_weight_elem_bytes(int kind) { return kind == AA_TABLE_F64 ? 8 : 4; }

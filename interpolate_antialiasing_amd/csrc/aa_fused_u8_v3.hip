@@ -3,6 +3,9 @@
 
 #include "aa_fused_u8_v3_impl.h"
 
+// filters whose shrinking heights may take the narrow-window MAXC-6 instantiations (5-6 open output rows with <= 16 taps)
+static bool v3_six_narrow_filter(int filter) { return filter == AA_FILTER_LANCZOS || filter == AA_FILTER_HAMMING; }
+
 // Everything the kernel needs that can be known without the pointers (aa_workspace_bytes asks before they exist).
 static bool v3_shape_ok(int dtype, int layout, int64_t N, int64_t Cin, int64_t H, int64_t W, const aa_axis &ah, const aa_axis &aw, bool *flt_out,
                         bool *planar_out, int *tw_out, int out_f32 = 0, int out_layout = AA_NCHW, bool *up_out = nullptr,
@@ -28,11 +31,15 @@ static bool v3_shape_ok(int dtype, int layout, int64_t N, int64_t Cin, int64_t H
     if (planar && oW > 256) return false;
   } else {  // the in-register scatter pass needs the H table's scatter section and at most 4 open output rows
     if (ah.scatter_off <= 0 || ah.scatter_max <= 0 || ah.scatter_max > 6) return false;
-    if (ah.scatter_max > 4 && (aw.max_taps > 0 ? aw.max_taps : aw.ksize) <= 16) return false;  // (6 open rows: the wide-window instantiations only)
+    // 5-6 open rows with windows of <= 16 taps: the MAXC-6 narrow instantiations (aa_fused_u8_v3_c{1,3,4}l*.hip), which exist for
+    // Hamming and Lanczos only.  Bicubic reaches 5 open rows there too and keeps the two-launch path (a follow-up).
+    if (ah.scatter_max > 4 && (aw.max_taps > 0 ? aw.max_taps : aw.ksize) <= 16 && !v3_six_narrow_filter(ah.filter)) return false;
   }
   const int taps_w = aw.max_taps > 0 ? aw.max_taps : aw.ksize;
   int tw = round_tw(taps_w);
   if (flt && tw != 0 && tw < 6) tw = 6;  // the float variant is instantiated for windows of 6, 8, 12 and 16 taps
+  const bool six = !up && ah.scatter_max > 4 && taps_w <= 16;  // (the narrow MAXC-6 route: windows of 6, 8, 12 and 16 taps)
+  if (six && tw < 6) tw = 6;
   // windows of 17 .. 34 taps: Pillow arithmetic, shrinking heights.  (With growing heights — test.py's (120, 1200) — the gather form with
   // such windows was built and measured SLOWER than the two-launch path: bicubic channels_last 0.226 vs 0.205 ms per 128 images.)
   if (tw > 16 && up) return false;
@@ -60,6 +67,7 @@ static bool v3_shape_ok(int dtype, int layout, int64_t N, int64_t Cin, int64_t H
     if (!flt && !planar && !out_f32 && aa_fused_u8_nhwc_applicable(dtype, layout, N, Cin, H, W, &ah, &aw)) return false;
   }
   if (nseg > 128 || (size_t)aa_v3_group() * nseg * 16 > 64 * 1024) return false;
+  if (six && nseg > 64) return false;  // (the narrow MAXC-6 route has the one-DMA-per-row form only)
   const int64_t nstrips = (oW + cap - 1) / cap + 1;  // (balanced strips can be one more)
   if (!aa_grid_fits((planar ? N * Cin : N) * nstrips)) return false;
   *flt_out = flt; *planar_out = planar; *tw_out = tw;
@@ -159,13 +167,17 @@ int aa_try_fused_u8_nhwc_v3(const AAProblem &q, const char **variant) {
   }
 
   int rc;
-  if (split) {
+  const int taps_w = q.aw.max_taps > 0 ? q.aw.max_taps : q.aw.ksize;
+  const bool six = !split && !up && q.ah.scatter_max > 4 && taps_w <= 16;  // (v3_shape_ok: Hamming / Lanczos only; exact in either precision mode)
+  if (six) {
+    rc = C == 3 ? aa_v3_launch_c3l(tw, flt, p, q, lds) : C == 4 ? aa_v3_launch_c4l(tw, flt, p, q, lds) : aa_v3_launch_c1l(tw, flt, p, q, lds);
+  } else if (split) {
     p.byte_store = 1;  // (a quad's first lane stores its pixel's bytes)
     rc = C == 3 ? aa_v3_launch_c3s(tw, q.ah.scatter_max, p, q, lds) : C == 4 ? aa_v3_launch_c4s(tw, q.ah.scatter_max, p, q, lds)
                                                                              : aa_v3_launch_c1s(tw, q.ah.scatter_max, p, q, lds);
   } else if (up) {
     const int taps_h = q.ah.max_taps > 0 ? q.ah.max_taps : q.ah.ksize;
-    const bool nonneg = q.aw.filter != AA_FILTER_CUBIC && q.ah.filter != AA_FILTER_CUBIC;
+    const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
     rc = C == 3   ? aa_v3_launch_up_c3(tw, taps_h, nonneg, flt, p, q, lds)
          : C == 4 ? aa_v3_launch_up_c4(tw, taps_h, nonneg, flt, p, q, lds)
                   : aa_v3_launch_up_c1(tw, taps_h, nonneg, flt, p, q, lds);
@@ -185,7 +197,7 @@ int aa_try_fused_u8_nhwc_v3(const AAProblem &q, const char **variant) {
          : C == 4 ? aa_v3_launch_c4(tw, q.ah.scatter_max, flt, p, q, lds)
                   : aa_v3_launch_c1(tw, q.ah.scatter_max, flt, p, q, lds);
   }
-  const bool fastv = flt && q.fast && !up && tw <= 16;
+  const bool fastv = flt && q.fast && !up && !six && tw <= 16;
   if (rc == 1 && q.out_f32) *variant = planar ? (fastv ? "fused_u8_planar_to_f32_v3_fast" : "fused_u8_planar_to_f32_v3")
                                               : (p.outm == 1 ? (fastv ? "fused_u8_nhwc_to_f32_nchw_v3_fast" : "fused_u8_nhwc_to_f32_nchw_v3")
                                                              : (fastv ? "fused_u8_nhwc_to_f32_nhwc_v3_fast" : "fused_u8_nhwc_to_f32_nhwc_v3"));

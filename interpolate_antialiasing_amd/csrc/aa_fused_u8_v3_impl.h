@@ -863,7 +863,7 @@ int launch_k(FusedU8V3Params p, const AAProblem &q, size_t lds, int64_t) {
 
 template <int C, int TW, int G, int MAXC>
 int launch_gm(const FusedU8V3Params &p, const AAProblem &q, size_t lds, int64_t grid) {
-  const bool nonneg = q.aw.filter != AA_FILTER_CUBIC && q.ah.filter != AA_FILTER_CUBIC;
+  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
   const bool periodic = ((unsigned long long)G * (unsigned long long)p.row_pitch) % 16 == 0;
   if (p.nseg > 64) {  // wide segments (large down-scales): the generic-address variant only
     return nonneg ? launch_k<C, TW, G, MAXC, true, true, false>(p, q, lds, grid)
@@ -934,7 +934,7 @@ int dispatch_tw(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, 
 // window addressing, up to 6 open output rows (what a scatter record holds).  Instantiated in aa_fused_u8_v3_c{1,3,4}w.hip.
 template <int C, int TW, int MAXC>
 int launch_wide_m(const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  const bool nonneg = q.aw.filter != AA_FILTER_CUBIC && q.ah.filter != AA_FILTER_CUBIC;
+  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
   if (p.nseg > 64) return nonneg ? launch_k<C, TW, 8, MAXC, true, true, false>(p, q, lds, 0) : launch_k<C, TW, 8, MAXC, true, false, false>(p, q, lds, 0);
   return nonneg ? launch_k<C, TW, 8, MAXC, false, true, false>(p, q, lds, 0) : launch_k<C, TW, 8, MAXC, false, false, false>(p, q, lds, 0);
 }
@@ -968,10 +968,24 @@ int dispatch_tw_wide_flt(int tw, int maxc, const FusedU8V3Params &p, const AAPro
   return 0;
 }
 
+// Narrow windows (<= 16 taps) with 5 or 6 open output rows: Lanczos down-scaling by 1 .. ~2.7 (support 3: an input row feeds up to 6
+// output rows, what a scatter record holds).  Negative weights (NONNEG = false), generic window addressing, one staging DMA per row
+// (v3_shape_ok keeps their segments within 64 pieces).  Instantiated in aa_fused_u8_v3_c{1,3,4}l.hip (Pillow arithmetic) and
+// aa_fused_u8_v3_c{1,3,4}lf.hip (float arithmetic: the harness's semantics, float32 out), so that no existing kernel changes.
+template <int C, bool FLT>
+int dispatch_tw_six(int tw, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
+  if (p.nseg > 64) return 0;
+  if (tw <= 6) return launch_k<C, 6, 8, 6, false, false, false, FLT>(p, q, lds, 0);
+  if (tw <= 8) return launch_k<C, 8, 8, 6, false, false, false, FLT>(p, q, lds, 0);
+  if (tw <= 12) return launch_k<C, 12, 8, 6, false, false, false, FLT>(p, q, lds, 0);
+  if (tw <= 16) return launch_k<C, 16, 8, 6, false, false, false, FLT>(p, q, lds, 0);
+  return 0;
+}
+
 // split windows (template parameter SP): 35 .. 136 taps, four lanes per output pixel; instantiated in aa_fused_u8_v3_c{1,3,4}s.hip
 template <int C, int TW, int MAXC>
 int launch_split_m(const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  const bool nonneg = q.aw.filter != AA_FILTER_CUBIC && q.ah.filter != AA_FILTER_CUBIC;
+  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
   if (p.nseg > 64)
     return nonneg ? launch_k<C, TW, 8, MAXC, true, true, false, false, 0, 0, 4>(p, q, lds, 0) : launch_k<C, TW, 8, MAXC, true, false, false, false, 0, 0, 4>(p, q, lds, 0);
   return nonneg ? launch_k<C, TW, 8, MAXC, false, true, false, false, 0, 0, 4>(p, q, lds, 0) : launch_k<C, TW, 8, MAXC, false, false, false, false, 0, 0, 4>(p, q, lds, 0);
@@ -996,7 +1010,7 @@ int dispatch_tw_split(int tws, int maxc, const FusedU8V3Params &p, const AAProbl
 template <int PLANES, int TW>
 int launch_planes(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
   static_assert(PLANES == 3, "three planes");
-  const bool nonneg = q.aw.filter != AA_FILTER_CUBIC && q.ah.filter != AA_FILTER_CUBIC;
+  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
   if (maxc <= 2) return nonneg ? launch_k<3, TW, 8, 2, false, true, false, false, 0, 3>(p, q, lds, 0) : launch_k<3, TW, 8, 2, false, false, false, false, 0, 3>(p, q, lds, 0);
   if (maxc <= 3) return nonneg ? launch_k<3, TW, 8, 3, false, true, false, false, 0, 3>(p, q, lds, 0) : launch_k<3, TW, 8, 3, false, false, false, false, 0, 3>(p, q, lds, 0);
   return nonneg ? launch_k<3, TW, 8, 4, false, true, false, false, 0, 3>(p, q, lds, 0) : launch_k<3, TW, 8, 4, false, false, false, false, 0, 3>(p, q, lds, 0);
@@ -1085,6 +1099,10 @@ int aa_v3_launch_c4wf(int tw, int maxc, const FusedU8V3Params &p, const AAProble
 int aa_v3_launch_c1s(int tws, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
 int aa_v3_launch_c3s(int tws, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
 int aa_v3_launch_c4s(int tws, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
+// narrow windows with 5-6 open output rows (aa_fused_u8_v3_c{1,3,4}l.hip; float arithmetic in aa_fused_u8_v3_c{1,3,4}lf.hip)
+int aa_v3_launch_c1l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
+int aa_v3_launch_c3l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
+int aa_v3_launch_c4l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
 // growing heights (aa_fused_u8_v3_c{1,3,4}u.hip)
 int aa_v3_launch_up_c1(int tw, int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
 int aa_v3_launch_up_c3(int tw, int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);

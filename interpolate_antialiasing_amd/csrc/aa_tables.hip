@@ -37,12 +37,43 @@ template <typename S>
 __device__ inline S filt_box(S x) {
   return (x > -0.5 && x <= 0.5) ? (S)1.0 : (S)0.0;
 }
+// Pillow's Hamming and Lanczos (src/libImaging/Resample.c: sinc_filter, hamming_filter, lanczos_filter), evaluated in double from the
+// scalar_t argument and narrowed to scalar_t.  Library sin / cos (not the fast intrinsics): the PIL kind must match Pillow's libm
+// coefficients to the bit before they are quantised.
+__device__ inline double sinc_d(double x) {
+  if (x == 0.0) return 1.0;
+  x = x * M_PI;
+  return sin(x) / x;
+}
+template <typename S>
+__device__ inline S filt_hamming(S xs) {
+  double x = (double)xs;
+  if (x < 0.0) x = -x;
+  if (x == 0.0) return (S)1.0;
+  if (x >= 1.0) return (S)0.0;
+  x = x * M_PI;
+  // Pillow writes the window constants as FLOAT literals (0.54f, 0.46f), promoted to double in the product
+  return (S)(sin(x) / x * ((double)0.54f + (double)0.46f * cos(x)));
+}
+template <typename S>
+__device__ inline S filt_lanczos(S xs) {
+  const double x = (double)xs;
+  if (-3.0 <= x && x < 3.0) return (S)(sinc_d(x) * sinc_d(x / 3.0));
+  return (S)0.0;
+}
 template <typename S>
 __device__ inline S apply_filter(int filter, S x) {
-  return filter == AA_FILTER_LINEAR ? filt_linear<S>(x) : (filter == AA_FILTER_CUBIC ? filt_cubic<S>(x) : filt_box<S>(x));
+  switch (filter) {
+    case AA_FILTER_LINEAR: return filt_linear<S>(x);
+    case AA_FILTER_CUBIC: return filt_cubic<S>(x);
+    case AA_FILTER_BOX: return filt_box<S>(x);
+    case AA_FILTER_HAMMING: return filt_hamming<S>(x);
+    case AA_FILTER_LANCZOS: return filt_lanczos<S>(x);
+    default: return (S)0.0;  // (unreachable: aa_table_ksize rejects unknown ids before any launch)
+  }
 }
 
-__device__ inline int interp_size_of(int filter) { return filter == AA_FILTER_LINEAR ? 2 : (filter == AA_FILTER_CUBIC ? 4 : 1); }
+__device__ inline int interp_size_of(int filter) { return aa_filter_info(filter).interp_size; }
 
 // Reference arithmetic, scalar_t = float (s2.2:207-209, :242, :253-278).  Every promotion spelled out.
 __device__ void table_build_f32_one(int i, int filter, int in_size, int out_size, int ksize, float scale, char *table) {
@@ -130,7 +161,7 @@ __device__ void table_build_pil_one(int i, int filter, int in_size, int out_size
 
   double scale = (double)in_size / (double)out_size;
   double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double fsupport = filter == AA_FILTER_LINEAR ? 1.0 : (filter == AA_FILTER_CUBIC ? 2.0 : 0.5);
+  const double fsupport = aa_filter_info(filter).support;
   const double support = fsupport * filterscale;
   const double center = 0.0 + ((double)i + 0.5) * scale;
   const double ss = 1.0 / filterscale;

@@ -8,7 +8,8 @@ Mirrors step_two_dot_two/extension_interpolate.cpp:46-51 (same names, argument m
     linear_backward(grad_output, output_size, input_size, align_corners=False) -> Tensor   (:16-24)
     forward(...)                                               legacy name of linear_forward used by every other
                                                                step (step_three/extension_interpolate.cpp:17-19)
-plus cubic_backward / nearest_backward (the commented-out intent at test.py:111-116).
+plus cubic_backward / nearest_backward (the commented-out intent at test.py:111-116), and Pillow's two other antialiasing filters
+with the same signatures: lanczos_forward / hamming_forward, lanczos_backward / hamming_backward (PIL.Image.LANCZOS / HAMMING).
 
 ``output_size`` is (H, W); ``input_size`` is the full NCHW size (test.py:140-143).  antialias=True and
 scale_factors={} are hard-wired exactly as in the reference wrappers.  The callee allocates and returns a fresh
@@ -36,7 +37,8 @@ from . import _lib, tables
 
 __all__ = ["linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
-           "cubic_backward_nd", "set_uint8_mode",
+           "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
+           "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
            "get_uint8_mode", "last_variant"]
 
 _uint8_mode = "pil"
@@ -504,6 +506,52 @@ def nearest_backward(grad_output: torch.Tensor, output_size: Sequence[int], inpu
     return _backward(_lib.FILTER_BOX, "nearest_backward", grad_output, output_size, input_size, align_corners, atomic)
 
 
+def lanczos_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
+                    uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
+                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None) -> torch.Tensor:
+    """Antialiased Lanczos-3 forward (Pillow's Image.LANCZOS; uint8 in the default mode equals PIL.Image.resize bit for bit)."""
+    return _forward(_lib.FILTER_LANCZOS, "lanczos_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
+                    mean, std, precision)
+
+
+def hamming_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
+                    uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
+                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None) -> torch.Tensor:
+    """Antialiased Hamming-windowed forward (Pillow's Image.HAMMING; uint8 in the default mode equals PIL.Image.resize bit for bit)."""
+    return _forward(_lib.FILTER_HAMMING, "hamming_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
+                    mean, std, precision)
+
+
+def lanczos_backward(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],
+                     align_corners: bool = False, *, atomic: bool = False) -> torch.Tensor:
+    """Backward of lanczos_forward — the true adjoint."""
+    return _backward(_lib.FILTER_LANCZOS, "lanczos_backward", grad_output, output_size, input_size, align_corners, atomic)
+
+
+def hamming_backward(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],
+                     align_corners: bool = False, *, atomic: bool = False) -> torch.Tensor:
+    """Backward of hamming_forward — the true adjoint."""
+    return _backward(_lib.FILTER_HAMMING, "hamming_backward", grad_output, output_size, input_size, align_corners, atomic)
+
+
+def lanczos_forward_nd(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False) -> torch.Tensor:
+    return _forward_nd(_lib.FILTER_LANCZOS, "lanczos_forward_nd", input, output_size, align_corners)
+
+
+def hamming_forward_nd(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False) -> torch.Tensor:
+    return _forward_nd(_lib.FILTER_HAMMING, "hamming_forward_nd", input, output_size, align_corners)
+
+
+def lanczos_backward_nd(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],
+                        align_corners: bool = False) -> torch.Tensor:
+    return _backward_nd(_lib.FILTER_LANCZOS, "lanczos_backward_nd", grad_output, output_size, input_size, align_corners)
+
+
+def hamming_backward_nd(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],
+                        align_corners: bool = False) -> torch.Tensor:
+    return _backward_nd(_lib.FILTER_HAMMING, "hamming_backward_nd", grad_output, output_size, input_size, align_corners)
+
+
 # legacy export of every step but step_two_dot_two (step_three/extension_interpolate.cpp:17-19)
 forward = linear_forward
 
@@ -514,8 +562,9 @@ def _register_torch_ops() -> None:
     fwd_schema = "(Tensor input, int[] output_size, bool align_corners=False) -> Tensor"
     bwd_schema = "(Tensor grad_output, int[] output_size, int[] input_size, bool align_corners=False) -> Tensor"
     fwds = {"linear_forward": linear_forward, "nearest_forward": nearest_forward, "cubic_forward": cubic_forward,
-            "forward": linear_forward}
-    bwds = {"linear_backward": linear_backward, "cubic_backward": cubic_backward, "nearest_backward": nearest_backward}
+            "forward": linear_forward, "lanczos_forward": lanczos_forward, "hamming_forward": hamming_forward}
+    bwds = {"linear_backward": linear_backward, "cubic_backward": cubic_backward, "nearest_backward": nearest_backward,
+            "lanczos_backward": lanczos_backward, "hamming_backward": hamming_backward}
     for name in fwds:
         lib.define(name + fwd_schema)
     for name in bwds:
@@ -554,6 +603,8 @@ def _register_torch_ops() -> None:
     _make_autograd("forward", "linear_backward")
     _make_autograd("cubic_forward", "cubic_backward")
     _make_autograd("nearest_forward", "nearest_backward")
+    _make_autograd("lanczos_forward", "lanczos_backward")
+    _make_autograd("hamming_forward", "hamming_backward")
     globals()["_torch_library"] = lib  # keep alive
 
 

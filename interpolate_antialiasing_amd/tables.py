@@ -17,7 +17,8 @@ import torch
 from . import _lib
 
 FILTER_IDS = {"linear": _lib.FILTER_LINEAR, "bilinear": _lib.FILTER_LINEAR, "cubic": _lib.FILTER_CUBIC,
-              "bicubic": _lib.FILTER_CUBIC, "box": _lib.FILTER_BOX, "nearest": _lib.FILTER_BOX}
+              "bicubic": _lib.FILTER_CUBIC, "box": _lib.FILTER_BOX, "nearest": _lib.FILTER_BOX, "hamming": _lib.FILTER_HAMMING,
+              "lanczos": _lib.FILTER_LANCZOS}
 KIND_IDS = {"pil": _lib.TABLE_PIL, "f32": _lib.TABLE_F32, "f64": _lib.TABLE_F64}
 HEADER_BYTES = ctypes.sizeof(_lib.TableHeader)  # 64
 

@@ -1,6 +1,13 @@
 #!/usr/bin/env python3
-"""Throughput map over test.py's five output sizes (test.py:15-21) x dtype / layout / arithmetic: which kernel ran and at what
-algorithmic GB/s.  Usage: python tools/perf_map.py [batch]   (GPU only; writes one line per case)."""
+"""Throughput map: which kernel ran and at what speed, per filter x shape x dtype / layout / arithmetic, beside the generic two-launch
+path (set_fused(0)) timed in the same process, the two alternated.  GPU only; writes one line per case.
+
+    python tools/perf_map.py [batch] [--filters linear,cubic] [--shapes test|filters]
+
+--shapes test (default): test.py's five output sizes of its 438x906 images (test.py:15-21).  --shapes filters: the shapes that reach
+every route of the fused uint8 kernel for Pillow's Hamming / Lanczos (tests/golden/make_golden_filters.py's list); the batch is
+scaled per shape to move about as many input bytes as `batch` 438x906 images."""
+import argparse
 import os
 import sys
 
@@ -9,12 +16,27 @@ import torch  # noqa: E402
 
 from interpolate_antialiasing_amd import _lib, extension_interpolate as aa  # noqa: E402
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
+ap = argparse.ArgumentParser()
+ap.add_argument("batch", nargs="?", type=int, default=128)
+ap.add_argument("--filters", default="linear,cubic", help="comma-separated: linear, cubic, box, hamming, lanczos")
+ap.add_argument("--shapes", default="test", choices=("test", "filters"))
+ap.add_argument("--reps", type=int, default=20)
+args = ap.parse_args()
+
+B = args.batch
 H, W = 438, 906
-SIZES = [(320, 196), (460, 220), (120, 96), (1200, 196), (120, 1200), (1200, 1200)]  # (W, H) as test.py writes them
+OPS = {"linear": aa.linear_forward, "cubic": aa.cubic_forward, "box": aa.nearest_forward, "hamming": aa.hamming_forward,
+       "lanczos": aa.lanczos_forward}
+if args.shapes == "test":
+    SHAPES = [("test", (H, W), (oh, ow)) for (ow, oh) in [(320, 196), (460, 220), (120, 96), (1200, 196), (120, 1200), (1200, 1200)]]
+else:
+    SHAPES = [("narrow", (438, 906), (220, 460)), ("narrow", (438, 906), (196, 1200)), ("narrow", (1080, 1920), (720, 1280)),
+              ("narrow", (1000, 1000), (999, 999)), ("narrow", (512, 512), (384, 384)), ("wide", (438, 906), (196, 320)),
+              ("split", (438, 906), (96, 120)), ("split", (2160, 3840), (224, 224)), ("up", (438, 906), (1200, 1200)),
+              ("up", (196, 320), (438, 906))]
 
 
-def timed(fn, reps=20):
+def timed(fn, reps):
     for _ in range(3):
         fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -26,19 +48,45 @@ def timed(fn, reps=20):
     return e0.elapsed_time(e1) / reps
 
 
+def fused_and_generic(fn, reps):
+    """-> (fused ms, fused variant, generic ms, generic variant): two alternating rounds each, the faster of each kept."""
+    best = {1: (1e30, ""), 0: (1e30, "")}
+    for _ in range(2):
+        for mode in (1, 0):
+            prev = _lib.set_fused(mode)
+            try:
+                ms = timed(fn, reps)
+                variant = _lib.last_variant()
+            finally:
+                _lib.set_fused(prev)
+            if ms < best[mode][0]:
+                best[mode] = (ms, variant)
+    return best[1][0], best[1][1], best[0][0], best[0][1]
+
+
 torch.manual_seed(0)
-u8 = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device="cuda").permute(0, 3, 1, 2)
-cases = [
-    ("u8 nhwc pil", u8, dict(uint8_mode="pil"), 1),
-    ("u8 nhwc harness", u8, dict(uint8_mode="harness"), 1),
-    ("u8 nchw pil", u8.contiguous(), dict(uint8_mode="pil"), 1),
-    ("f32 nchw", u8.float().contiguous(), {}, 4),
-    ("f32 nhwc", u8.float().contiguous(memory_format=torch.channels_last), {}, 4),
-    ("f16 nchw", u8.half().contiguous(), {}, 2),
-]
-for fname, op in (("linear", aa.linear_forward), ("cubic", aa.cubic_forward)):
-    for (ow, oh) in SIZES:
+print(f"# batch {B} (per 438x906 image's bytes); ms per call; Mpix/s = output pixels per second; fused vs generic (set_fused(0))", flush=True)
+for (tag, (h, w), (oh, ow)) in SHAPES:
+    b = max(1, round(B * H * W / (h * w)))
+    u8 = torch.randint(0, 256, (b, h, w, 3), dtype=torch.uint8, device="cuda").permute(0, 3, 1, 2)
+    cases = [
+        ("u8 nhwc pil", u8, dict(uint8_mode="pil"), 1),
+        ("u8 nhwc harness", u8, dict(uint8_mode="harness"), 1),
+        ("u8 nchw pil", u8.contiguous(), dict(uint8_mode="pil"), 1),
+        ("f32 nchw", u8.float().contiguous(), {}, 4),
+        ("f32 nhwc", u8.float().contiguous(memory_format=torch.channels_last), {}, 4),
+        ("f16 nchw", u8.half().contiguous(), {}, 2),
+    ]
+    if args.shapes == "filters":
+        cases.insert(3, ("u8 nhwc->f32", u8, dict(out_dtype=torch.float32, out_format="nchw"), 1))
+    for fname in args.filters.split(","):
+        op = OPS[fname]
         for cname, x, kw, es in cases:
-            ms = timed(lambda: op(x, [oh, ow], **kw))
-            nbytes = B * 3 * es * (H * W + oh * ow)
-            print(f"{fname:6s} ({ow:4d},{oh:4d}) {cname:16s} {ms:8.4f} ms {nbytes / ms / 1e6:7.0f} GB/s  {_lib.last_variant()}", flush=True)
+            fms, fv, gms, gv = fused_and_generic(lambda: op(x, [oh, ow], **kw), args.reps)
+            mpix = b * oh * ow / 1e6
+            nbytes = b * 3 * es * (h * w) + b * 3 * (4 if "f32" in cname else es) * (oh * ow)
+            print(f"{fname:7s} {tag:6s} {h:4d}x{w:<4d}->{oh:4d}x{ow:<4d} b{b:<4d} {cname:16s} fused {fms:8.4f} ms {mpix / fms * 1e3:8.0f} Mpix/s "
+                  f"{nbytes / fms / 1e6:6.0f} GB/s {fv:34s} generic {gms:8.4f} ms {mpix / gms * 1e3:8.0f} Mpix/s {gv:26s} x{gms / fms:5.2f}",
+                  flush=True)
+    del cases, u8
+    torch.cuda.empty_cache()
