@@ -167,6 +167,9 @@ int aa_table_query2(const void *table_a_dev, const void *table_b_dev, aa_table_h
  * start on an element boundary (AA_ERR_BAD_SHAPE otherwise). */
 size_t aa_workspace_bytes(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW,
                           const aa_axis *ax_h, const aa_axis *ax_w);
+/* The same for aa_resample_fwd_ex with `flags` (AA_FLAG_PREMUL_ALPHA changes the answer; without it this is aa_workspace_bytes). */
+size_t aa_workspace_bytes_ex(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW,
+                             const aa_axis *ax_h, const aa_axis *ax_w, unsigned flags);
 
 /* Forward: replaces ti_upsample_{bilinear,bicubic,nearest}2d_cpu + the separable driver + both passes
  * (s2.2/aa_interpolation_impl.h:731-807, :628-683, :536-625, :131-187, :29-120).
@@ -190,6 +193,16 @@ int aa_resample_fwd(const void *in_dev, void *out_dev, void *workspace_dev, size
  * arithmetic, for f64 images and wherever no tolerance kernel applies (the exact kernels run: bit-identical results are always
  * within tolerance).  aa_workspace_bytes() answers for both. */
 #define AA_FLAG_FAST 1u
+/* AA_FLAG_PREMUL_ALPHA — resize an image with STRAIGHT alpha the way Pillow's Image.resize does for RGBA / LA: the colour channels are
+ * premultiplied by alpha (RGBA -> RGBa: t = c*a + 128, c' = ((t >> 8) + t) >> 8), the premultiplied image is resampled, and every
+ * output pixel is converted back (c' = c where a is 0 or 255, else min(255, 255*c / a), truncating); alpha itself resamples as an
+ * ordinary channel.  Bit-exact with Pillow.  Only for uint8 images with AA_TABLE_PIL tables and C == 2 or 4, the last channel being
+ * alpha, in either layout; any other combination returns AA_ERR_BAD_DTYPE.  Output size == input size copies the input unchanged
+ * (Pillow returns a copy).  Channels_last RGBA with narrow windows and shrinking heights runs fused in one launch; everything else
+ * premultiplies into the workspace, resamples, and un-premultiplies the output in place (aa_workspace_bytes_ex answers for it;
+ * aa_resample_fwd_strided has no workspace and returns AA_ERR_STRIDES there).  A library that predates this flag rejects it as an
+ * unknown flag bit (AA_ERR_BAD_SHAPE): the ABI version stays 3. */
+#define AA_FLAG_PREMUL_ALPHA 2u
 int aa_resample_fwd_ex(const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int dtype,
                        int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w,
                        unsigned flags, aa_stream_t stream);

@@ -23,6 +23,7 @@ TABLE_PIL, TABLE_F32, TABLE_F64 = 0, 1, 2
 ERR_BAD_DTYPE = -2
 ERR_STRIDES = -10
 FLAG_FAST = 1
+FLAG_PREMUL_ALPHA = 2
 
 # every symbol include/aa_interp.h declares (tests check the .so exports exactly these)
 EXPORTS = (
@@ -30,6 +31,7 @@ EXPORTS = (
     "aa_table_transposed_ksize", "aa_table_transpose", "aa_table_query", "aa_table_query2", "aa_table_build2", "aa_workspace_bytes", "aa_resample_fwd",
     "aa_resample_bwd", "aa_resample_bwd_atomic", "aa_workspace_bytes_bwd", "aa_resample_axis_fwd", "aa_set_fused",
     "aa_last_variant", "aa_probe_copy", "aa_workspace_bytes_u8_to_f32", "aa_resample_fwd_u8_to_f32", "aa_set_store_form", "aa_set_plane_groups", "aa_resample_fwd_ex", "aa_resample_fwd_strided",
+    "aa_workspace_bytes_ex",
 )
 
 
@@ -101,6 +103,8 @@ def load() -> ctypes.CDLL:
     L.aa_table_build2.restype = i32
     L.aa_workspace_bytes.argtypes = [i32, i32, i64, i64, i64, i64, i64, i64, ax, ax]
     L.aa_workspace_bytes.restype = sz
+    L.aa_workspace_bytes_ex.argtypes = [i32, i32, i64, i64, i64, i64, i64, i64, ax, ax, ctypes.c_uint]
+    L.aa_workspace_bytes_ex.restype = sz
     L.aa_resample_fwd.argtypes = [vp, vp, vp, sz, i32, i32, i64, i64, i64, i64, ax, ax, vp]
     L.aa_resample_fwd.restype = i32
     L.aa_resample_fwd_ex.argtypes = [vp, vp, vp, sz, i32, i32, i64, i64, i64, i64, ax, ax, ctypes.c_uint, vp]

@@ -247,6 +247,21 @@ int aa_table_transpose(const void *table_dev, void *tr_table_dev, size_t tr_tabl
   return aa_launch_table_transpose(h, table_dev, tr_table_dev, tr_ksize, (hipStream_t)stream);
 }
 
+// AA_FLAG_PREMUL_ALPHA: uint8 images of Pillow's integer arithmetic with 2 or 4 channels, straight alpha last
+static bool alpha_ok(int dtype, int64_t C, const aa_axis *ax_h, const aa_axis *ax_w) {
+  return dtype == AA_U8 && (C == 2 || C == 4) && ax_h->kind == AA_TABLE_PIL && ax_w->kind == AA_TABLE_PIL;
+}
+
+size_t aa_workspace_bytes_ex(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW,
+                             const aa_axis *ax_h, const aa_axis *ax_w, unsigned flags) {
+  if (!(flags & AA_FLAG_PREMUL_ALPHA)) return aa_workspace_bytes(dtype, layout, N, C, H, W, oH, oW, ax_h, ax_w);
+  if (!ax_h || !ax_w || N <= 0 || !alpha_ok(dtype, C, ax_h, ax_w)) return 0;
+  if (oH == H && oW == W) return 0;  // (a copy)
+  if (g_fused_enabled == 1 && aa_fused_u8_v3_applicable(dtype, layout, N, C, H, W, ax_h, ax_w, 0, AA_NCHW, 1)) return 0;
+  // the three-step fallback: the premultiplied copy of the input, then what the ordinary resample of it needs
+  return aa_align16((size_t)(N * C * H * W)) + aa_workspace_bytes(dtype, layout, N, C, H, W, oH, oW, ax_h, ax_w);
+}
+
 size_t aa_workspace_bytes(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW,
                           const aa_axis *ax_h, const aa_axis *ax_w) {
   (void)oH;
@@ -296,7 +311,11 @@ int aa_resample_fwd_strided(const void *in_dev, void *out_dev, int dtype, int la
     return AA_ERR_BAD_LAYOUT;
   }
   const bool dense = row_pitch == W * (layout == AA_NHWC ? C : 1) * es && (N * (layout == AA_NCHW ? C : 1) <= 1 || img_pitch == H * row_pitch);
-  if (dense) return resample_fwd_impl(in_dev, out_dev, nullptr, 0, dtype, layout, N, C, H, W, ax_h, ax_w, flags, 0, 0, stream);
+  if (dense) {
+    const int rc = resample_fwd_impl(in_dev, out_dev, nullptr, 0, dtype, layout, N, C, H, W, ax_h, ax_w, flags, 0, 0, stream);
+    // (no workspace here: the straight-alpha three-step route is "no kernel for this view", as for a pitched one)
+    return (rc == AA_ERR_WORKSPACE && (flags & AA_FLAG_PREMUL_ALPHA)) ? AA_ERR_STRIDES : rc;
+  }
   if (img_pitch == 0 && N * (layout == AA_NCHW ? C : 1) > 1) return AA_ERR_STRIDES;  // (a broadcast batch: make it dense)
   return resample_fwd_impl(in_dev, out_dev, nullptr, 0, dtype, layout, N, C, H, W, ax_h, ax_w, flags, row_pitch, img_pitch ? img_pitch : H * row_pitch, stream);
 }
@@ -304,7 +323,7 @@ int aa_resample_fwd_strided(const void *in_dev, void *out_dev, int dtype, int la
 static int resample_fwd_impl(const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int dtype,
                              int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w,
                              unsigned flags, int64_t row_pitch, int64_t img_pitch, aa_stream_t stream) {
-  if (flags & ~(unsigned)AA_FLAG_FAST) return AA_ERR_BAD_SHAPE;
+  if (flags & ~(unsigned)(AA_FLAG_FAST | AA_FLAG_PREMUL_ALPHA)) return AA_ERR_BAD_SHAPE;
   if (dtype < AA_U8 || dtype > AA_BF16) return AA_ERR_BAD_DTYPE;
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   if (N < 0 || C <= 0 || H <= 0 || W <= 0) return AA_ERR_BAD_SHAPE;
@@ -314,6 +333,8 @@ static int resample_fwd_impl(const void *in_dev, void *out_dev, void *workspace_
   if (rc != AA_OK) return rc;
   rc = check_dtype_kind(dtype, ax_h->kind, ax_w->kind);
   if (rc != AA_OK) return rc;
+  const bool alpha = (flags & AA_FLAG_PREMUL_ALPHA) != 0;
+  if (alpha && !alpha_ok(dtype, C, ax_h, ax_w)) return AA_ERR_BAD_DTYPE;
   if (N == 0) {  // empty batch is allowed (s2.2:747-750)
     g_last_variant = "empty";
     return AA_OK;
@@ -334,9 +355,37 @@ static int resample_fwd_impl(const void *in_dev, void *out_dev, void *workspace_
   p.in_row_pitch = row_pitch; p.in_img_pitch = img_pitch;
   // (Pillow's integer arithmetic and double arithmetic have no tolerance mode; uint8 images with AA_TABLE_F32 tables = the harness's float arithmetic do)
   p.fast = (flags & AA_FLAG_FAST) && dtype != AA_F64 && ax_w->kind == AA_TABLE_F32 ? 1 : 0;
+  p.alpha = alpha ? 1 : 0;
 
   const char *variant = "none";
   rc = 0;
+  if (alpha) {
+    if (p.oH == H && p.oW == W) {  // Pillow's resize returns a copy: no lossy round trip through premultiplied values
+      if (row_pitch) return AA_ERR_STRIDES;
+      if (hipMemcpyAsync(out_dev, in_dev, (size_t)(N * C * H * W), hipMemcpyDeviceToDevice, p.stream) != hipSuccess) return AA_ERR_HIP;
+      g_last_variant = "alpha_copy";
+      return AA_OK;
+    }
+    rc = g_fused_enabled == 1 ? aa_try_fused_u8_nhwc_v3(p, &variant) : 0;
+    if (rc < 0) return rc;
+    if (rc == 1) {
+      g_last_variant = variant;
+      return AA_OK;
+    }
+    // three steps: premultiplied copy of the input into the workspace, the ordinary resample of it, un-premultiply in place
+    if (row_pitch) return AA_ERR_STRIDES;
+    const size_t copy_bytes = aa_align16((size_t)(N * C * H * W));
+    const size_t need = copy_bytes + aa_workspace_bytes(dtype, layout, N, C, H, W, p.oH, p.oW, ax_h, ax_w);
+    if (!workspace_dev || workspace_bytes < need) return AA_ERR_WORKSPACE;
+    rc = aa_launch_premul_u8(in_dev, workspace_dev, layout, N, C, H, W, p.stream);
+    if (rc != AA_OK) return rc;
+    rc = resample_fwd_impl(workspace_dev, out_dev, (char *)workspace_dev + copy_bytes, workspace_bytes - copy_bytes, dtype, layout, N, C, H, W,
+                           ax_h, ax_w, flags & ~(unsigned)AA_FLAG_PREMUL_ALPHA, 0, 0, stream);
+    if (rc != AA_OK) return rc;
+    rc = aa_launch_unpremul_u8(out_dev, layout, N, C, p.oH, p.oW, p.stream);
+    if (rc == AA_OK) g_last_variant = "alpha_3step";
+    return rc;
+  }
   if (g_fused_enabled) {
     if (g_fused_enabled == 1 && p.fast && dtype != AA_U8) rc = aa_try_fused_float_nchw_fast(p, &variant);  // declines -> the exact kernels (always within tolerance)
     if (rc == 0 && g_fused_enabled == 1) rc = aa_try_fused_u8_nhwc_v3(p, &variant);

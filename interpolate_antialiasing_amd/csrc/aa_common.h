@@ -129,6 +129,7 @@ struct AAProblem {
   // uniformly spaced) lie these many BYTES apart.  0 = the dense tensor.  Only the kernels that say so take pitched problems.
   int64_t in_row_pitch = 0, in_img_pitch = 0;
   int fast = 0;  // AA_FLAG_FAST: the caller accepts results within 1e-4 relative of the reference's (FMA accumulation)
+  int alpha = 0;  // AA_FLAG_PREMUL_ALPHA: uint8, Pillow tables, C 2 / 4 with straight alpha last; only the kernels that say so take it
 };
 
 // generic two-launch separable path (always available); returns variant name through *variant
@@ -147,7 +148,11 @@ int aa_try_fused_u8_nhwc_v3(const AAProblem &p, const char **variant);  // LDS-D
 // The *_applicable predicates hold EVERY reason a fused path can decline that does not depend on the pointers (shape, LDS
 // size, grid size, dispatch widths): aa_workspace_bytes() answers 0 exactly when aa_resample_fwd() will not need one.
 bool aa_fused_u8_v3_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw,
-                               int out_f32 = 0, int out_layout = AA_NCHW);
+                               int out_f32 = 0, int out_layout = AA_NCHW, int alpha = 0);
+// the three-step straight-alpha fallback (aa_alpha.hip): premultiply a dense uint8 image of C = 2 / 4 channels (alpha last, either layout)
+// into `dst`, and un-premultiply one in place
+int aa_launch_premul_u8(const void *src, void *dst, int layout, int64_t N, int64_t C, int64_t H, int64_t W, hipStream_t stream);
+int aa_launch_unpremul_u8(void *img, int layout, int64_t N, int64_t C, int64_t H, int64_t W, hipStream_t stream);
 bool aa_fused_u8_nhwc_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
 bool aa_fused_float_nchw_up_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
 bool aa_fused_float_nchw_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);

@@ -9,8 +9,10 @@ static bool v3_six_narrow_filter(int filter) { return filter == AA_FILTER_LANCZO
 // Everything the kernel needs that can be known without the pointers (aa_workspace_bytes asks before they exist).
 static bool v3_shape_ok(int dtype, int layout, int64_t N, int64_t Cin, int64_t H, int64_t W, const aa_axis &ah, const aa_axis &aw, bool *flt_out,
                         bool *planar_out, int *tw_out, int out_f32 = 0, int out_layout = AA_NCHW, bool *up_out = nullptr,
-                        int *cap_out = nullptr) {
+                        int *cap_out = nullptr, int alpha = 0) {
   if (dtype != AA_U8) return false;
+  // straight alpha: the ALPHA instantiations cover Pillow arithmetic, 4 interleaved channels, uint8 out, narrow windows of shrinking heights
+  if (alpha && (out_f32 || layout != AA_NHWC || Cin != 4 || ah.kind != AA_TABLE_PIL || aw.kind != AA_TABLE_PIL || H < ah.out_size)) return false;
   if (out_f32 && (ah.kind != AA_TABLE_F32 || aw.kind != AA_TABLE_F32)) return false;  // float output = float arithmetic
   const bool flt = ah.kind == AA_TABLE_F32 && aw.kind == AA_TABLE_F32;  // the reference harness's uint8 semantics
   if (!flt && (ah.kind != AA_TABLE_PIL || aw.kind != AA_TABLE_PIL)) return false;
@@ -68,6 +70,7 @@ static bool v3_shape_ok(int dtype, int layout, int64_t N, int64_t Cin, int64_t H
   }
   if (nseg > 128 || (size_t)aa_v3_group() * nseg * 16 > 64 * 1024) return false;
   if (six && nseg > 64) return false;  // (the narrow MAXC-6 route has the one-DMA-per-row form only)
+  if (alpha && (split || tw > 16 || nseg > 64)) return false;  // (aa_fused_u8_v3_c4a*.hip: one DMA per row)
   const int64_t nstrips = (oW + cap - 1) / cap + 1;  // (balanced strips can be one more)
   if (!aa_grid_fits((planar ? N * Cin : N) * nstrips)) return false;
   *flt_out = flt; *planar_out = planar; *tw_out = tw;
@@ -77,16 +80,16 @@ static bool v3_shape_ok(int dtype, int layout, int64_t N, int64_t Cin, int64_t H
 }
 
 bool aa_fused_u8_v3_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw,
-                               int out_f32, int out_layout) {
+                               int out_f32, int out_layout, int alpha) {
   bool flt, planar;
   int tw;
-  return ah && aw && v3_shape_ok(dtype, layout, N, C, H, W, *ah, *aw, &flt, &planar, &tw, out_f32, out_layout);
+  return ah && aw && v3_shape_ok(dtype, layout, N, C, H, W, *ah, *aw, &flt, &planar, &tw, out_f32, out_layout, nullptr, nullptr, alpha);
 }
 
 int aa_try_fused_u8_nhwc_v3(const AAProblem &q, const char **variant) {
   bool flt, planar, up = false;
   int tw, cap = 64;
-  if (!v3_shape_ok(q.dtype, q.layout, q.N, q.C, q.H, q.W, q.ah, q.aw, &flt, &planar, &tw, q.out_f32, q.out_layout, &up, &cap)) return 0;
+  if (!v3_shape_ok(q.dtype, q.layout, q.N, q.C, q.H, q.W, q.ah, q.aw, &flt, &planar, &tw, q.out_f32, q.out_layout, &up, &cap, q.alpha)) return 0;
   const int C = planar ? 1 : (int)q.C;
   const int64_t NI = planar ? q.N * q.C : q.N;  // images the kernel sees
   const int G = aa_v3_group();
@@ -143,6 +146,14 @@ int aa_try_fused_u8_nhwc_v3(const AAProblem &q, const char **variant) {
   // single-plane form keeps: growing heights; windows beyond 12 taps (8 in float arithmetic: the wider instantiations need 133-147 VGPRs
   // = 3 waves per SIMD); segments beyond 16 pieces (down-scaling by 4 and more: the single planes' staging DMAs are full enough as they
   // are, measured +4 % at 1024 -> 224).
+  if (q.alpha) {  // (v3_shape_ok: channels_last RGBA, narrow windows, shrinking heights)
+    const int taps_w = q.aw.max_taps > 0 ? q.aw.max_taps : q.aw.ksize;
+    const bool six = q.ah.scatter_max > 4 && taps_w <= 16;
+    const int rc = six ? aa_v3_launch_c4al(tw, p, q, lds) : aa_v3_launch_c4a(tw, q.ah.scatter_max, p, q, lds);
+    if (rc == 1) *variant = six ? "fused_u8_nhwc_pil_alpha6_v3" : "fused_u8_nhwc_pil_alpha_v3";
+    return rc;
+  }
+
   if (planar && NI >= 2 && !up && tw <= (flt ? 8 : 12) && tw >= 4 && p.nseg <= 16 && G == 8 && q.ah.scatter_max <= 4 && (!q.out_f32 || p.outm == 1) &&
       3 * p.img_in_bytes <= 0x7FFFFFF0ull && 3 * p.img_out_bytes <= 0x7FFFFFF0ull && g_aa_plane_groups != 0) {
     FusedU8V3Params pg = p;

@@ -32,6 +32,7 @@
 
 #include <type_traits>
 
+#include "aa_alpha.h"
 #include "aa_common.h"
 
 #ifndef AA_V3_ABL
@@ -181,12 +182,17 @@ __device__ inline void wait_vmcnt(int n) {  // rounding n DOWN only waits longer
 //     runs the vertical pass redundantly.  Integer sums are associative, so the result is Pillow's bit for bit whatever the split.  This is
 //     the form for windows beyond what one lane's registers hold (35 .. 136 taps: down-scaling by 17 .. 68 bilinear, 9 .. 34 bicubic); a
 //     strip is 16 columns, stored bytewise by each quad's first lane (outputs are tiny at such scales).
-template <int C, int TW, int G, bool TWO_DMA, int MAXC, bool NONNEG, bool PERIODIC, bool FLT = false, int UPK = 0, int PL = 0, int SP = 1>
+// ALPHA: straight alpha in channel 3 (AA_FLAG_PREMUL_ALPHA; Pillow's RGBA resize): each window pixel's colour is premultiplied by its
+//     alpha in registers as the horizontal pass reads it (aa_premul8), and each output pixel is un-premultiplied after the clip, before
+//     any store form packs it (aa_unpremul8).  Pillow arithmetic, 4 interleaved channels.
+template <int C, int TW, int G, bool TWO_DMA, int MAXC, bool NONNEG, bool PERIODIC, bool FLT = false, int UPK = 0, int PL = 0, int SP = 1,
+          bool ALPHA = false>
 __global__ void __launch_bounds__(512) AA_V3_OCC
 fused_u8_nhwc_v3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const char *__restrict__ tab_w,
                         const char *__restrict__ tab_h, const FusedU8V3Params p) {
   static_assert(PL == 0 || (PL == C && !PERIODIC && UPK == 0 && !TWO_DMA), "plane groups: shrinking heights, fixed stage layout");
   static_assert(SP == 1 || (SP == 4 && !FLT && !PERIODIC && UPK == 0 && PL == 0), "split windows: integer arithmetic, shrinking heights");
+  static_assert(!ALPHA || (C == 4 && !FLT && PL == 0), "premultiplied alpha: Pillow arithmetic, 4 interleaved channels");
   constexpr int PLN = PL > 0 ? PL : 1;  // windows per lane and row
   constexpr int CB = PL > 0 ? 1 : C;    // bytes per pixel in a staged row
   constexpr int NV1 = (CB * TW + 3) / 4;  // dwords holding one window
@@ -434,6 +440,12 @@ fused_u8_nhwc_v3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ ou
   // merged across the branches below the compiler kept it in a lane mask: a v_cndmask + v_cmp per output row)
   const int emit_path = __builtin_amdgcn_readfirstlane((FLT && p.outm != 0) ? 1 : (p.byte_store ? 2 : 0));
   auto emit = [&](int oy) {  // accumulator set 0 is complete: clip, pack, merge quads, store; then slide the sets down
+    if constexpr (ALPHA) {  // un-premultiply the clipped pixel; every store form below clips (x >> 22) again, which keeps b << 22 as b
+      const int al = clip8_int(A[0][3]);
+#pragma unroll
+      for (int c = 0; c < 3; c++) A[0][c] = aa_unpremul8(clip8_int(A[0][c]), al) << 22;
+      A[0][3] = al << 22;
+    }
     if constexpr (FLT) {
       if (emit_path == 1) {  // (wave-uniform) float32 output: the accumulators themselves, one 256-byte row piece per plane
         float v[C];
@@ -593,7 +605,10 @@ fused_u8_nhwc_v3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ ou
 #pragma unroll
         for (int c = 0; c < C; c++) {
           const int bi = PL > 0 ? c * (4 * NV1) + j : j * C + c;  // (plane groups: channel c's own window)
-          const int px = (int)((v[bi >> 2] >> (8 * (bi & 3))) & 0xffu);
+          int px = (int)((v[bi >> 2] >> (8 * (bi & 3))) & 0xffu);
+          if constexpr (ALPHA) {  // (C == 4: pixel j is dword v[j], its alpha the top byte)
+            if (c < 3) px = aa_premul8(px, (int)(v[j] >> 24));
+          }
           acc[c] += px * wreg[j];
         }
       }
@@ -830,9 +845,10 @@ int pick_ybands(int64_t items_per_band, double slots, int taps_h, int64_t H, int
   return (int)ybands;
 }
 
-template <int C, int TW, int G, int MAXC, bool TWO, bool NONNEG, bool PERIODIC, bool FLT = false, int UPK = 0, int PL = 0, int SP = 1>
+template <int C, int TW, int G, int MAXC, bool TWO, bool NONNEG, bool PERIODIC, bool FLT = false, int UPK = 0, int PL = 0, int SP = 1,
+          bool ALPHA = false>
 int launch_k(FusedU8V3Params p, const AAProblem &q, size_t lds, int64_t) {
-  auto kern = fused_u8_nhwc_v3_kernel<C, TW, G, TWO, MAXC, NONNEG, PERIODIC, FLT, UPK, PL, SP>;
+  auto kern = fused_u8_nhwc_v3_kernel<C, TW, G, TWO, MAXC, NONNEG, PERIODIC, FLT, UPK, PL, SP, ALPHA>;
   auto resident = [&](int s) {  // resident workgroups of s strips per CU for this instantiation and this problem's LDS
     int nb = aa_resident_blocks(kern, 64 * s, lds * s);
     if (nb <= 0) nb = 16 / s;
@@ -972,13 +988,38 @@ int dispatch_tw_wide_flt(int tw, int maxc, const FusedU8V3Params &p, const AAPro
 // output rows, what a scatter record holds).  Negative weights (NONNEG = false), generic window addressing, one staging DMA per row
 // (v3_shape_ok keeps their segments within 64 pieces).  Instantiated in aa_fused_u8_v3_c{1,3,4}l.hip (Pillow arithmetic) and
 // aa_fused_u8_v3_c{1,3,4}lf.hip (float arithmetic: the harness's semantics, float32 out), so that no existing kernel changes.
-template <int C, bool FLT>
+template <int C, bool FLT, bool ALPHA = false>
 int dispatch_tw_six(int tw, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
   if (p.nseg > 64) return 0;
-  if (tw <= 6) return launch_k<C, 6, 8, 6, false, false, false, FLT>(p, q, lds, 0);
-  if (tw <= 8) return launch_k<C, 8, 8, 6, false, false, false, FLT>(p, q, lds, 0);
-  if (tw <= 12) return launch_k<C, 12, 8, 6, false, false, false, FLT>(p, q, lds, 0);
-  if (tw <= 16) return launch_k<C, 16, 8, 6, false, false, false, FLT>(p, q, lds, 0);
+  if (tw <= 6) return launch_k<C, 6, 8, 6, false, false, false, FLT, 0, 0, 1, ALPHA>(p, q, lds, 0);
+  if (tw <= 8) return launch_k<C, 8, 8, 6, false, false, false, FLT, 0, 0, 1, ALPHA>(p, q, lds, 0);
+  if (tw <= 12) return launch_k<C, 12, 8, 6, false, false, false, FLT, 0, 0, 1, ALPHA>(p, q, lds, 0);
+  if (tw <= 16) return launch_k<C, 16, 8, 6, false, false, false, FLT, 0, 0, 1, ALPHA>(p, q, lds, 0);
+  return 0;
+}
+
+// Straight alpha (AA_FLAG_PREMUL_ALPHA), 4 interleaved channels, narrow windows (<= 16 taps), <= 4 open output rows: Pillow arithmetic,
+// generic window addressing, one staging DMA per row (wider segments take the three-step fallback), accumulator sets for 2 or 4 open
+// rows.  Instantiated in aa_fused_u8_v3_c4a.hip; the six-row form is dispatch_tw_six<4, false, true> (aa_fused_u8_v3_c4al.hip).
+// (templates over the channel count, like the other dispatchers, so that only the translation unit that names them instantiates the kernels)
+template <int C, int TW>
+int launch_alpha(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
+  static_assert(C == 4, "premultiplied alpha: RGBA");
+  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
+  if (maxc <= 2) return nonneg ? launch_k<C, TW, 8, 2, false, true, false, false, 0, 0, 1, true>(p, q, lds, 0)
+                               : launch_k<C, TW, 8, 2, false, false, false, false, 0, 0, 1, true>(p, q, lds, 0);
+  return nonneg ? launch_k<C, TW, 8, 4, false, true, false, false, 0, 0, 1, true>(p, q, lds, 0)
+                : launch_k<C, TW, 8, 4, false, false, false, false, 0, 0, 1, true>(p, q, lds, 0);
+}
+template <int C>
+int dispatch_tw_alpha(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
+  if (p.nseg > 64 || maxc > 4) return 0;
+  if (tw <= 2) return launch_alpha<C, 2>(maxc, p, q, lds);
+  if (tw <= 4) return launch_alpha<C, 4>(maxc, p, q, lds);
+  if (tw <= 6) return launch_alpha<C, 6>(maxc, p, q, lds);
+  if (tw <= 8) return launch_alpha<C, 8>(maxc, p, q, lds);
+  if (tw <= 12) return launch_alpha<C, 12>(maxc, p, q, lds);
+  if (tw <= 16) return launch_alpha<C, 16>(maxc, p, q, lds);
   return 0;
 }
 
@@ -1103,6 +1144,9 @@ int aa_v3_launch_c4s(int tws, int maxc, const FusedU8V3Params &p, const AAProble
 int aa_v3_launch_c1l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
 int aa_v3_launch_c3l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
 int aa_v3_launch_c4l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
+// straight alpha, 4 channels: narrow windows (aa_fused_u8_v3_c4a.hip) and narrow windows with 5-6 open output rows (aa_fused_u8_v3_c4al.hip)
+int aa_v3_launch_c4a(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
+int aa_v3_launch_c4al(int tw, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
 // growing heights (aa_fused_u8_v3_c{1,3,4}u.hip)
 int aa_v3_launch_up_c1(int tw, int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
 int aa_v3_launch_up_c3(int tw, int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);

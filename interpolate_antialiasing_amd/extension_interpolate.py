@@ -24,6 +24,9 @@ Differences, all additive:
   * ``precision="fast"`` (f32 / f16 / bf16): the opt-in tolerance mode — FMA accumulation, results within 1e-4 relative of the
     reference's (BASELINE.json's float bar) instead of bit-identical; the default ``"exact"`` rounds product and sum separately in
     the reference's tap order.  In fast mode a NaN / Inf pixel also reaches outputs whose 16-byte-aligned window holds it;
+  * ``alpha=True`` (uint8, ``uint8_mode="pil"``, 2 or 4 channels with straight alpha last): Pillow's RGBA / LA resize — colour is
+    premultiplied by alpha, resampled, and converted back, bit-exact with PIL.Image.resize on an "RGBA" / "LA" image; the same
+    size in and out returns a copy;
   * the same callables are registered as ``torch.ops.extension_interpolate.*``.
 """
 from __future__ import annotations
@@ -136,12 +139,18 @@ def _user_scales(scale_factors, n: int):
 
 def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequence[int], align_corners: bool,
              uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
-             out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None) -> torch.Tensor:
+             out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None, alpha: bool = False) -> torch.Tensor:
     if not isinstance(input, torch.Tensor):
         raise TypeError(f"{name}(): argument 'input' must be Tensor")
     if precision not in (None, "exact", "fast"):
         raise ValueError("precision must be 'exact' (default: the reference's results bit for bit) or 'fast' (within 1e-4 relative)")
     flags = _lib.FLAG_FAST if precision == "fast" else 0
+    if alpha:
+        _check_alpha(name, input, uint8_mode, out_dtype, out_format, mean, std)
+        flags |= _lib.FLAG_PREMUL_ALPHA
+        if tuple(input.shape[2:]) == tuple(int(v) for v in output_size):
+            _require_gpu(input, name)
+            return input.clone()  # Pillow returns a copy: no lossy round trip through premultiplied values
     if out_dtype is not None or out_format is not None or mean is not None or std is not None:
         if input.dtype != torch.uint8 or out_dtype not in (None, torch.float32):
             raise NotImplementedError("out_dtype / out_format / mean / std: the fused conversion takes uint8 input and gives float32")
@@ -175,14 +184,14 @@ def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequen
         return out
     dt = _DTYPE_IDS[x.dtype]
     # host-side plan: the two cached tables' axis descriptors and the workspace size for this exact call shape
-    key = (filter_id, dt, layout, n, c, h, w, oh, ow, bool(align_corners), kind, sh, sw, dev.index, _lib.fused_epoch)
+    key = (filter_id, dt, layout, n, c, h, w, oh, ow, bool(align_corners), kind, sh, sw, dev.index, _lib.fused_epoch, bool(alpha))
     plan = _plans.get(key)
     cur = torch.cuda.current_device()
     if plan is None:
         with torch.cuda.device(dev):
             th, tw = tables.get_table_pair(filter_id, kind, h, oh, w, ow, align_corners, sh, sw, dev)
             ah, aw = th.axis(), tw.axis()
-            ws_bytes = L.aa_workspace_bytes(dt, layout, n, c, h, w, oh, ow, ctypes.byref(ah), ctypes.byref(aw))
+            ws_bytes = L.aa_workspace_bytes_ex(dt, layout, n, c, h, w, oh, ow, ctypes.byref(ah), ctypes.byref(aw), flags)
         plan = (ah, aw, ws_bytes, ctypes.byref(ah), ctypes.byref(aw), th, tw)  # (th, tw keep the device buffers alive)
         if len(_plans) > 4096:
             _plans.clear()
@@ -198,7 +207,7 @@ def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequen
             return out
         x, layout2 = _memory_format(input)  # no kernel for this view: the dense copy after all (the plan was made for this layout)
         if layout2 != layout:
-            return _forward(filter_id, name, x, output_size, align_corners, uint8_mode, scale_factors, None, None, None, None, precision)
+            return _forward(filter_id, name, x, output_size, align_corners, uint8_mode, scale_factors, None, None, None, None, precision, alpha)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     if dev.index == cur:
         rc = L.aa_resample_fwd_ex(x.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, dt, layout,
@@ -209,6 +218,18 @@ def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequen
                                       layout, n, c, h, w, pah, paw, flags, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, name)
     return out
+
+
+def _check_alpha(name: str, input: torch.Tensor, uint8_mode, out_dtype, out_format, mean, std) -> None:
+    """alpha=True (Pillow's RGBA / LA resize) is defined for uint8 images in Pillow's arithmetic with 2 or 4 channels, alpha last."""
+    if input.dtype != torch.uint8:
+        raise ValueError(f"{name}(): alpha=True takes uint8 images (Pillow's RGBA / LA resize), got {input.dtype}")
+    if (uint8_mode or _uint8_mode) != "pil":
+        raise ValueError(f"{name}(): alpha=True is Pillow's arithmetic; uint8_mode='harness' has no premultiplied alpha")
+    if out_dtype is not None or out_format is not None or mean is not None or std is not None:
+        raise ValueError(f"{name}(): alpha=True gives uint8 in the input's layout; out_dtype / out_format / mean / std do not apply")
+    if input.dim() != 4 or input.shape[1] not in (2, 4):
+        raise ValueError(f"{name}(): alpha=True needs [N, 2 or 4, H, W] with straight alpha in the last channel, got {list(input.shape)}")
 
 
 def _forward_to_float(filter_id: int, name: str, input: torch.Tensor, output_size: Sequence[int], align_corners: bool,
@@ -467,26 +488,29 @@ def nearest_forward_nd(input: torch.Tensor, output_size: Sequence[int], align_co
 # ---- the reference's callables ---------------------------------------------------------------------------
 def linear_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
-                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None) -> torch.Tensor:
+                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
+                    alpha: bool = False) -> torch.Tensor:
     """Anti-Aliased Linear Interpolation forward (s2.2/extension_interpolate.cpp:7-14,47)."""
     return _forward(_lib.FILTER_LINEAR, "linear_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision)
+                    mean, std, precision, alpha)
 
 
 def nearest_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
-                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None) -> torch.Tensor:
+                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
+                    alpha: bool = False) -> torch.Tensor:
     """Anti-Aliased "Nearest" (really: box filter) forward (s2.2/extension_interpolate.cpp:26-33,48)."""
     return _forward(_lib.FILTER_BOX, "nearest_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision)
+                    mean, std, precision, alpha)
 
 
 def cubic_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
-                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None) -> torch.Tensor:
+                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
+                    alpha: bool = False) -> torch.Tensor:
     """Anti-Aliased Cubic Interpolation forward (s2.2/extension_interpolate.cpp:35-42,49)."""
     return _forward(_lib.FILTER_CUBIC, "cubic_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision)
+                    mean, std, precision, alpha)
 
 
 def linear_backward(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],
@@ -508,18 +532,20 @@ def nearest_backward(grad_output: torch.Tensor, output_size: Sequence[int], inpu
 
 def lanczos_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
-                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None) -> torch.Tensor:
+                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
+                    alpha: bool = False) -> torch.Tensor:
     """Antialiased Lanczos-3 forward (Pillow's Image.LANCZOS; uint8 in the default mode equals PIL.Image.resize bit for bit)."""
     return _forward(_lib.FILTER_LANCZOS, "lanczos_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision)
+                    mean, std, precision, alpha)
 
 
 def hamming_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
-                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None) -> torch.Tensor:
+                    out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
+                    alpha: bool = False) -> torch.Tensor:
     """Antialiased Hamming-windowed forward (Pillow's Image.HAMMING; uint8 in the default mode equals PIL.Image.resize bit for bit)."""
     return _forward(_lib.FILTER_HAMMING, "hamming_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision)
+                    mean, std, precision, alpha)
 
 
 def lanczos_backward(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],

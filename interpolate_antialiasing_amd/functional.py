@@ -10,11 +10,21 @@ _MODES = {"bilinear": "linear_forward", "linear": "linear_forward", "bicubic": "
           "hamming": "hamming_forward"}
 
 
-def interpolate_aa(input: torch.Tensor, size: Sequence[int], mode: str = "bilinear", align_corners: bool = False) -> torch.Tensor:
+def interpolate_aa(input: torch.Tensor, size: Sequence[int], mode: str = "bilinear", align_corners: bool = False, *,
+                   alpha: bool = False) -> torch.Tensor:
     """Antialiased resize of a 4-D GPU tensor to ``size`` = (H, W); differentiable for float dtypes.
     ``mode``: bilinear | bicubic | nearest (= box filter, as in the reference) | lanczos | hamming (Pillow's filters of those names).
     3-D (NCL) and 5-D (NCDHW) inputs take the N-d front-ends (forward only): ``mode`` linear/bilinear/trilinear | bicubic | nearest |
-    lanczos | hamming."""
+    lanczos | hamming.
+    ``alpha=True``: a uint8 [N, 2 or 4, H, W] image with straight alpha last, resized as Pillow resizes "LA" / "RGBA" (premultiplied)."""
+    if alpha:
+        from . import extension_interpolate as ext
+
+        if mode not in _MODES:
+            raise ValueError(mode)
+        if input.dim() != 4:
+            raise ValueError(f"alpha=True needs a 4-D [N, 2 or 4, H, W] uint8 tensor, got {input.dim()}-D")
+        return getattr(ext, _MODES[mode])(input, [int(size[0]), int(size[1])], bool(align_corners), alpha=True)
     if input.dim() in (3, 5):
         from . import extension_interpolate as ext
 

@@ -6,7 +6,11 @@ path (set_fused(0)) timed in the same process, the two alternated.  GPU only; wr
 
 --shapes test (default): test.py's five output sizes of its 438x906 images (test.py:15-21).  --shapes filters: the shapes that reach
 every route of the fused uint8 kernel for Pillow's Hamming / Lanczos (tests/golden/make_golden_filters.py's list); the batch is
-scaled per shape to move about as many input bytes as `batch` 438x906 images."""
+scaled per shape to move about as many input bytes as `batch` 438x906 images.
+
+--alpha: straight-alpha RGBA / LA (alpha=True) per route instead: the fused alpha kernel against the plain 4-channel kernel on the same
+shape (alpha=False) and against the set_fused(0) three-step route (premultiply, generic resample, un-premultiply), at the batch given per
+shape (1024 RGBA images at 438x906 -> 196x320 bilinear is the headline)."""
 import argparse
 import os
 import sys
@@ -21,6 +25,7 @@ ap.add_argument("batch", nargs="?", type=int, default=128)
 ap.add_argument("--filters", default="linear,cubic", help="comma-separated: linear, cubic, box, hamming, lanczos")
 ap.add_argument("--shapes", default="test", choices=("test", "filters"))
 ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--alpha", action="store_true")
 args = ap.parse_args()
 
 B = args.batch
@@ -63,6 +68,41 @@ def fused_and_generic(fn, reps):
                 best[mode] = (ms, variant)
     return best[1][0], best[1][1], best[0][0], best[0][1]
 
+
+
+def alpha_map():
+    # (filter, in, out, batch, channels): the routes of alpha=True — fused narrow and six-row windows, and the fallback's wide, split,
+    # growing and LA cases
+    cases = [("linear", (438, 906), (196, 320), 1024, 4), ("box", (438, 906), (196, 320), 1024, 4), ("hamming", (438, 906), (196, 320), 1024, 4),
+             ("lanczos", (1080, 1920), (720, 1280), 32, 4), ("cubic", (438, 906), (196, 320), 1024, 4), ("linear", (2160, 3840), (224, 224), 64, 4),
+             ("linear", (438, 906), (1200, 1200), 32, 4), ("linear", (438, 906), (196, 320), 1024, 2)]
+    print("# ms per call (best of 2 alternating rounds); alpha = alpha=True, set_fused(1): the fused alpha kernel, or where it declines the "
+          "default three-step route (its resample is whatever fused kernel applies); plain = alpha=False, set_fused(1); fallback = alpha=True, "
+          "set_fused(0): premultiply, GENERIC two-pass resample, un-premultiply", flush=True)
+    for fname, (h, w), (oh, ow), b, c in cases:
+        x = torch.randint(0, 256, (b, h, w, c), dtype=torch.uint8, device="cuda").permute(0, 3, 1, 2)
+        op = OPS[fname]
+        best = {}
+        for _ in range(2):
+            for key, mode, alpha in (("alpha", 1, True), ("plain", 1, False), ("fallback", 0, True)):
+                prev = _lib.set_fused(mode)
+                try:
+                    ms = timed(lambda: op(x, [oh, ow], alpha=alpha), args.reps)
+                    v = _lib.last_variant()
+                finally:
+                    _lib.set_fused(prev)
+                if ms < best.get(key, (1e30, ""))[0]:
+                    best[key] = (ms, v)
+        (am, av), (pm, pv), (fm, fv) = best["alpha"], best["plain"], best["fallback"]
+        print(f"{fname:7s} {h:4d}x{w:<4d}->{oh:4d}x{ow:<4d} b{b:<5d} C{c} alpha {am:8.4f} ms {av:28s} plain {pm:8.4f} ms {pv:28s} "
+              f"fallback {fm:8.4f} ms  alpha/plain x{am / pm:5.2f}  fallback/alpha x{fm / am:5.2f}", flush=True)
+        del x
+        torch.cuda.empty_cache()
+
+
+if args.alpha:
+    alpha_map()
+    sys.exit(0)
 
 torch.manual_seed(0)
 print(f"# batch {B} (per 438x906 image's bytes); ms per call; Mpix/s = output pixels per second; fused vs generic (set_fused(0))", flush=True)
