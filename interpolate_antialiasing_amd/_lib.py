@@ -179,9 +179,9 @@ def last_variant() -> str:
 # sources a kernel variant is compiled from (csrc/): profiles/*.json summaries are stamped with their fingerprint, and bench.py
 # flags a committed counter summary as stale when the sources of the kernel it describes have changed since
 KERNEL_SOURCES = {
-    "fused_u8_nhwc_pil_v3": ("aa_fused_u8_v3_impl.h", "aa_fused_u8_v3.hip", "aa_fused_u8_v3_c3.hip", "aa_common.h"),
+    "fused_u8_nhwc_pil_v3": ("aa_fused_u8_v3_impl.h", "aa_fused_u8_v3.hip", "aa_fused_u8_v3_unit.hip", "aa_fused_u8_v3_list.h", "aa_common.h"),
     "fused_u8_nhwc_pil": ("aa_fused_u8.hip", "aa_common.h"),
-    "fused_u8_planar_pil_v3": ("aa_fused_u8_v3_impl.h", "aa_fused_u8_v3.hip", "aa_fused_u8_v3_c3g.hip", "aa_fused_u8_v3_c1.hip", "aa_common.h"),
+    "fused_u8_planar_pil_v3": ("aa_fused_u8_v3_impl.h", "aa_fused_u8_v3.hip", "aa_fused_u8_v3_unit.hip", "aa_fused_u8_v3_list.h", "aa_common.h"),
 }
 
 

@@ -2,7 +2,7 @@
 //
 // Third design, after measuring the first two on MI355X (DESIGN.md §Kernels has the numbers):
 //   v1 (aa_fused_u8.hip)     per-lane window loads from global memory -> TCP 95 % busy, 3.4 TB/s;
-//   v2 (aa_fused_u8_v2.hip)  LDS-DMA staging + producer/consumer waves + shared LDS ring -> the data-movement skeleton
+//   v2 (since removed)       LDS-DMA staging + producer/consumer waves + shared LDS ring -> the data-movement skeleton
 //                            alone (all arithmetic removed) takes 0.33 ms per 1024 images: LDS bound (window reads with
 //                            2-3-way bank conflicts + 3 byte-writes per pixel + ring reads), plus barrier coupling.
 // v3 keeps v2's clean global path and removes everything else that touched LDS:
@@ -22,9 +22,9 @@
 // Integer arithmetic is associative, so accumulating taps in scatter order gives bit-identical Pillow results.
 
 //
-// This header holds the kernel template and its launch chain; it is compiled once per channel count
-// (aa_fused_u8_v3_c1.hip / _c3.hip / _c4.hip) so that the instantiations build in parallel, and the host-side
-// dispatcher lives in aa_fused_u8_v3.hip.
+// This header holds the kernel template and launch_k, which launches one instantiation.  The compiled set is listed in
+// aa_fused_u8_v3_list.h and instantiated by aa_fused_u8_v3_unit.hip, compiled once per unit so that the units build in
+// parallel; the host-side plan lives in aa_fused_u8_v3.hip.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -62,7 +62,7 @@
 #endif
 
 #ifndef AA_V3_FLT_FAST
-#define AA_V3_FLT_FAST 0  // 1 (aa_fused_u8_v3_c{1,3,4}ff.hip): the float-arithmetic kernels in the opt-in TOLERANCE mode (AA_FLAG_FAST): every tap of
+#define AA_V3_FLT_FAST 0  // 1 (the units c1ff, c3ff, c4ff, c3gff): the float-arithmetic kernels in the opt-in TOLERANCE mode (AA_FLAG_FAST): every tap of
                           // both passes is one fused multiply-add instead of a separately rounded product and sum.  Results differ from the
                           // reference harness's by rounding only (<= 1e-4 relative; after the truncating byte() at most one count)
 #endif
@@ -74,7 +74,7 @@
                            // SLOWER (1.02 ms vs 0.283 ms per 1024 images): a misaligned LDS dword is not a one-pass access.
 #endif
 
-// (shared by the per-channel-count translation units and the host-side dispatcher)
+// (shared by the units and the host-side plan)
 struct FusedU8V3Params {
   int H, W, oH, oW;
   int ksize_w, ksize_h;
@@ -95,7 +95,7 @@ struct FusedU8V3Params {
   int outm, normalize, cin;
   float mean[4], std[4];
   unsigned row_pitch;  // bytes between consecutive input rows (= W * C for a dense tensor; larger for a cropped view)
-  int fast;        // AA_FLAG_FAST on a float-arithmetic problem: the FMA instantiations (aa_fused_u8_v3_c{1,3,4}ff.hip)
+  int fast;        // AA_FLAG_FAST on a float-arithmetic problem: the FMA instantiations (AA_V3_FLT_FAST)
   int byte_store;  // output rows that are not whole dwords (oW*C % 4 != 0, or C == 3 with oW % 4 != 0) or an output pointer that
                    // is not dword aligned: every lane stores its own bytes instead of the quad-merged dword stores
   // plane-group kernels (template parameter PL): bytes between the channel planes of one image, input and output
@@ -813,14 +813,6 @@ fused_u8_nhwc_v3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ ou
   }
 }
 
-// staged rows per wave: 8; developer builds (-DAA_V2_TUNING) read AA_V3_G
-inline int aa_v3_group() {
-#ifdef AA_V2_TUNING
-  if (const char *e = aa_knob("AA_V3_G")) return atoi(e);
-#endif
-  return 8;
-}
-
 // Row bands: every extra band re-reads and re-filters ~taps_h halo rows, but the grid must fill the chip's resident
 // wave slots a near-integer number of times or the last partial round idles most CUs.  Pick the band count
 // minimising (1 + halo fraction) / round efficiency.
@@ -847,7 +839,7 @@ int pick_ybands(int64_t items_per_band, double slots, int taps_h, int64_t H, int
 
 template <int C, int TW, int G, int MAXC, bool TWO, bool NONNEG, bool PERIODIC, bool FLT = false, int UPK = 0, int PL = 0, int SP = 1,
           bool ALPHA = false>
-int launch_k(FusedU8V3Params p, const AAProblem &q, size_t lds, int64_t) {
+int launch_k(FusedU8V3Params p, const AAProblem &q, size_t lds) {
   auto kern = fused_u8_nhwc_v3_kernel<C, TW, G, TWO, MAXC, NONNEG, PERIODIC, FLT, UPK, PL, SP, ALPHA>;
   auto resident = [&](int s) {  // resident workgroups of s strips per CU for this instantiation and this problem's LDS
     int nb = aa_resident_blocks(kern, 64 * s, lds * s);
@@ -877,236 +869,6 @@ int launch_k(FusedU8V3Params p, const AAProblem &q, size_t lds, int64_t) {
   return 1;
 }
 
-template <int C, int TW, int G, int MAXC>
-int launch_gm(const FusedU8V3Params &p, const AAProblem &q, size_t lds, int64_t grid) {
-  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
-  const bool periodic = ((unsigned long long)G * (unsigned long long)p.row_pitch) % 16 == 0;
-  if (p.nseg > 64) {  // wide segments (large down-scales): the generic-address variant only
-    return nonneg ? launch_k<C, TW, G, MAXC, true, true, false>(p, q, lds, grid)
-                  : launch_k<C, TW, G, MAXC, true, false, false>(p, q, lds, grid);
-  }
-  if (nonneg) return periodic ? launch_k<C, TW, G, MAXC, false, true, true>(p, q, lds, grid)
-                              : launch_k<C, TW, G, MAXC, false, true, false>(p, q, lds, grid);
-  return periodic ? launch_k<C, TW, G, MAXC, false, false, true>(p, q, lds, grid)
-                  : launch_k<C, TW, G, MAXC, false, false, false>(p, q, lds, grid);
-}
-
-template <int C, int TW, int G>
-int launch_g(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds, int64_t grid) {
-  if (maxc <= 2) return launch_gm<C, TW, G, 2>(p, q, lds, grid);
-  if (maxc <= 3) return launch_gm<C, TW, G, 3>(p, q, lds, grid);
-  return launch_gm<C, TW, G, 4>(p, q, lds, grid);
-}
-
-template <int C, int TW>
-int launch(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds, int64_t grid) {
-#ifdef AA_V2_TUNING
-  if (aa_v3_group() == 4) return launch_g<C, TW, 4>(maxc, p, q, lds, grid);
-  if (aa_v3_group() == 6) return launch_g<C, TW, 6>(maxc, p, q, lds, grid);
-  if (aa_v3_group() == 10) return launch_g<C, TW, 10>(maxc, p, q, lds, grid);
-  if (aa_v3_group() == 12) return launch_g<C, TW, 12>(maxc, p, q, lds, grid);
-  if (aa_v3_group() == 16) return launch_g<C, TW, 16>(maxc, p, q, lds, grid);
-#endif
-  return launch_g<C, TW, 8>(maxc, p, q, lds, grid);
-}
-
-// harness (float) arithmetic: the down-scaling window widths only, generic window addressing
-template <int C, int TW>
-int launch_flt(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds, int64_t grid) {
-  const bool two = p.nseg > 64;
-  if (maxc <= 2) return two ? launch_k<C, TW, 8, 2, true, false, false, true>(p, q, lds, grid)
-                            : launch_k<C, TW, 8, 2, false, false, false, true>(p, q, lds, grid);
-  if (maxc <= 3) return two ? launch_k<C, TW, 8, 3, true, false, false, true>(p, q, lds, grid)
-                            : launch_k<C, TW, 8, 3, false, false, false, true>(p, q, lds, grid);
-  return two ? launch_k<C, TW, 8, 4, true, false, false, true>(p, q, lds, grid)
-             : launch_k<C, TW, 8, 4, false, false, false, true>(p, q, lds, grid);
-}
-
-template <int C>
-int dispatch_tw_flt(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds, int64_t grid) {
-  if (tw <= 6) return launch_flt<C, 6>(maxc, p, q, lds, grid);
-  if (tw <= 8) return launch_flt<C, 8>(maxc, p, q, lds, grid);
-  if (tw <= 12) return launch_flt<C, 12>(maxc, p, q, lds, grid);
-  if (tw <= 16) return launch_flt<C, 16>(maxc, p, q, lds, grid);  // (test.py's 906 -> 120 thumbnails: 16 taps)
-  return 0;
-}
-
-template <int C>
-int dispatch_tw(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds, int64_t grid) {
-#ifdef AA_V3_HEADLINE_ONLY  // developer builds: one window width, so the file compiles in seconds
-  return tw == 6 ? launch<C, 6>(maxc, p, q, lds, grid) : 0;
-#endif
-  if (tw <= 2) return launch<C, 2>(maxc, p, q, lds, grid);
-  if (tw <= 4) return launch<C, 4>(maxc, p, q, lds, grid);
-  if (tw <= 6) return launch<C, 6>(maxc, p, q, lds, grid);
-  if (tw <= 8) return launch<C, 8>(maxc, p, q, lds, grid);
-  if (tw <= 12) return launch<C, 12>(maxc, p, q, lds, grid);
-  if (tw <= 16) return launch<C, 16>(maxc, p, q, lds, grid);  // (bicubic thumbnails: 1750 -> 500 has 15 taps)
-  return 0;
-}
-
-// Wide windows (17 .. 34 taps: test.py's 906 -> 120 thumbnails have 17 bilinear / 33 bicubic taps; the reference's loop takes any
-// ids_size, s2.2:52-56,81-85): the same kernel with a longer window in registers — Pillow arithmetic, shrinking heights, generic
-// window addressing, up to 6 open output rows (what a scatter record holds).  Instantiated in aa_fused_u8_v3_c{1,3,4}w.hip.
-template <int C, int TW, int MAXC>
-int launch_wide_m(const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
-  if (p.nseg > 64) return nonneg ? launch_k<C, TW, 8, MAXC, true, true, false>(p, q, lds, 0) : launch_k<C, TW, 8, MAXC, true, false, false>(p, q, lds, 0);
-  return nonneg ? launch_k<C, TW, 8, MAXC, false, true, false>(p, q, lds, 0) : launch_k<C, TW, 8, MAXC, false, false, false>(p, q, lds, 0);
-}
-template <int C, int TW>
-int launch_wide(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (maxc <= 2) return launch_wide_m<C, TW, 2>(p, q, lds);
-  if (maxc <= 3) return launch_wide_m<C, TW, 3>(p, q, lds);
-  if (maxc <= 4) return launch_wide_m<C, TW, 4>(p, q, lds);
-  return launch_wide_m<C, TW, 6>(p, q, lds);
-}
-template <int C>
-int dispatch_tw_wide(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (tw <= 24) return launch_wide<C, 24>(maxc, p, q, lds);
-  if (tw <= 34) return launch_wide<C, 34>(maxc, p, q, lds);
-  return 0;
-}
-
-// ... and in float arithmetic (the harness's semantics, float32 out): aa_fused_u8_v3_c{1,3,4}wf.hip
-template <int C, int TW>
-int launch_wide_flt(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  const bool two = p.nseg > 64;
-  if (maxc <= 2) return two ? launch_k<C, TW, 8, 2, true, false, false, true>(p, q, lds, 0) : launch_k<C, TW, 8, 2, false, false, false, true>(p, q, lds, 0);
-  if (maxc <= 3) return two ? launch_k<C, TW, 8, 3, true, false, false, true>(p, q, lds, 0) : launch_k<C, TW, 8, 3, false, false, false, true>(p, q, lds, 0);
-  if (maxc <= 4) return two ? launch_k<C, TW, 8, 4, true, false, false, true>(p, q, lds, 0) : launch_k<C, TW, 8, 4, false, false, false, true>(p, q, lds, 0);
-  return two ? launch_k<C, TW, 8, 6, true, false, false, true>(p, q, lds, 0) : launch_k<C, TW, 8, 6, false, false, false, true>(p, q, lds, 0);
-}
-template <int C>
-int dispatch_tw_wide_flt(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (tw <= 24) return launch_wide_flt<C, 24>(maxc, p, q, lds);
-  if (tw <= 34) return launch_wide_flt<C, 34>(maxc, p, q, lds);
-  return 0;
-}
-
-// Narrow windows (<= 16 taps) with 5 or 6 open output rows: Lanczos down-scaling by 1 .. ~2.7 (support 3: an input row feeds up to 6
-// output rows, what a scatter record holds).  Negative weights (NONNEG = false), generic window addressing, one staging DMA per row
-// (v3_shape_ok keeps their segments within 64 pieces).  Instantiated in aa_fused_u8_v3_c{1,3,4}l.hip (Pillow arithmetic) and
-// aa_fused_u8_v3_c{1,3,4}lf.hip (float arithmetic: the harness's semantics, float32 out), so that no existing kernel changes.
-template <int C, bool FLT, bool ALPHA = false>
-int dispatch_tw_six(int tw, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (p.nseg > 64) return 0;
-  if (tw <= 6) return launch_k<C, 6, 8, 6, false, false, false, FLT, 0, 0, 1, ALPHA>(p, q, lds, 0);
-  if (tw <= 8) return launch_k<C, 8, 8, 6, false, false, false, FLT, 0, 0, 1, ALPHA>(p, q, lds, 0);
-  if (tw <= 12) return launch_k<C, 12, 8, 6, false, false, false, FLT, 0, 0, 1, ALPHA>(p, q, lds, 0);
-  if (tw <= 16) return launch_k<C, 16, 8, 6, false, false, false, FLT, 0, 0, 1, ALPHA>(p, q, lds, 0);
-  return 0;
-}
-
-// Straight alpha (AA_FLAG_PREMUL_ALPHA), 4 interleaved channels, narrow windows (<= 16 taps), <= 4 open output rows: Pillow arithmetic,
-// generic window addressing, one staging DMA per row (wider segments take the three-step fallback), accumulator sets for 2 or 4 open
-// rows.  Instantiated in aa_fused_u8_v3_c4a.hip; the six-row form is dispatch_tw_six<4, false, true> (aa_fused_u8_v3_c4al.hip).
-// (templates over the channel count, like the other dispatchers, so that only the translation unit that names them instantiates the kernels)
-template <int C, int TW>
-int launch_alpha(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  static_assert(C == 4, "premultiplied alpha: RGBA");
-  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
-  if (maxc <= 2) return nonneg ? launch_k<C, TW, 8, 2, false, true, false, false, 0, 0, 1, true>(p, q, lds, 0)
-                               : launch_k<C, TW, 8, 2, false, false, false, false, 0, 0, 1, true>(p, q, lds, 0);
-  return nonneg ? launch_k<C, TW, 8, 4, false, true, false, false, 0, 0, 1, true>(p, q, lds, 0)
-                : launch_k<C, TW, 8, 4, false, false, false, false, 0, 0, 1, true>(p, q, lds, 0);
-}
-template <int C>
-int dispatch_tw_alpha(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (p.nseg > 64 || maxc > 4) return 0;
-  if (tw <= 2) return launch_alpha<C, 2>(maxc, p, q, lds);
-  if (tw <= 4) return launch_alpha<C, 4>(maxc, p, q, lds);
-  if (tw <= 6) return launch_alpha<C, 6>(maxc, p, q, lds);
-  if (tw <= 8) return launch_alpha<C, 8>(maxc, p, q, lds);
-  if (tw <= 12) return launch_alpha<C, 12>(maxc, p, q, lds);
-  if (tw <= 16) return launch_alpha<C, 16>(maxc, p, q, lds);
-  return 0;
-}
-
-// split windows (template parameter SP): 35 .. 136 taps, four lanes per output pixel; instantiated in aa_fused_u8_v3_c{1,3,4}s.hip
-template <int C, int TW, int MAXC>
-int launch_split_m(const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
-  if (p.nseg > 64)
-    return nonneg ? launch_k<C, TW, 8, MAXC, true, true, false, false, 0, 0, 4>(p, q, lds, 0) : launch_k<C, TW, 8, MAXC, true, false, false, false, 0, 0, 4>(p, q, lds, 0);
-  return nonneg ? launch_k<C, TW, 8, MAXC, false, true, false, false, 0, 0, 4>(p, q, lds, 0) : launch_k<C, TW, 8, MAXC, false, false, false, false, 0, 0, 4>(p, q, lds, 0);
-}
-template <int C, int TW>
-int launch_split(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (maxc <= 2) return launch_split_m<C, TW, 2>(p, q, lds);
-  if (maxc <= 3) return launch_split_m<C, TW, 3>(p, q, lds);
-  if (maxc <= 4) return launch_split_m<C, TW, 4>(p, q, lds);
-  return launch_split_m<C, TW, 6>(p, q, lds);
-}
-template <int C>
-int dispatch_tw_split(int tws, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {  // tws: taps per LANE
-  if (tws <= 16) return launch_split<C, 16>(maxc, p, q, lds);
-  if (tws <= 24) return launch_split<C, 24>(maxc, p, q, lds);
-  if (tws <= 34) return launch_split<C, 34>(maxc, p, q, lds);
-  return 0;
-}
-
-// plane groups (template parameter PL): the three planes of a planar image in one wave; instantiated in aa_fused_u8_v3_c3g.hip
-// (templates over the plane count so that only the translation units that name them instantiate the kernels)
-template <int PLANES, int TW>
-int launch_planes(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  static_assert(PLANES == 3, "three planes");
-  const bool nonneg = aa_filters_nonneg(q.aw.filter, q.ah.filter);
-  if (maxc <= 2) return nonneg ? launch_k<3, TW, 8, 2, false, true, false, false, 0, 3>(p, q, lds, 0) : launch_k<3, TW, 8, 2, false, false, false, false, 0, 3>(p, q, lds, 0);
-  if (maxc <= 3) return nonneg ? launch_k<3, TW, 8, 3, false, true, false, false, 0, 3>(p, q, lds, 0) : launch_k<3, TW, 8, 3, false, false, false, false, 0, 3>(p, q, lds, 0);
-  return nonneg ? launch_k<3, TW, 8, 4, false, true, false, false, 0, 3>(p, q, lds, 0) : launch_k<3, TW, 8, 4, false, false, false, false, 0, 3>(p, q, lds, 0);
-}
-// ... in float arithmetic (harness semantics, float32 planes out): aa_fused_u8_v3_c3gf.hip, and c3gff.hip for the tolerance mode
-template <int PLANES, int TW>
-int launch_planes_flt(int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  static_assert(PLANES == 3, "three planes");
-  if (maxc <= 2) return launch_k<3, TW, 8, 2, false, false, false, true, 0, 3>(p, q, lds, 0);
-  if (maxc <= 3) return launch_k<3, TW, 8, 3, false, false, false, true, 0, 3>(p, q, lds, 0);
-  return launch_k<3, TW, 8, 4, false, false, false, true, 0, 3>(p, q, lds, 0);
-}
-template <int PLANES>
-int dispatch_tw_planes_flt(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (maxc > 4) return 0;
-  if (tw <= 6) return launch_planes_flt<PLANES, 6>(maxc, p, q, lds);
-  if (tw <= 8) return launch_planes_flt<PLANES, 8>(maxc, p, q, lds);
-  return 0;  // (12 taps in float arithmetic: 133-141 VGPRs, three waves per SIMD — the single-plane form keeps them)
-}
-template <int PLANES>
-int dispatch_tw_planes(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (maxc > 4) return 0;
-  if (tw <= 4) return launch_planes<PLANES, 4>(maxc, p, q, lds);
-  if (tw <= 6) return launch_planes<PLANES, 6>(maxc, p, q, lds);
-  if (tw <= 8) return launch_planes<PLANES, 8>(maxc, p, q, lds);
-  if (tw <= 12) return launch_planes<PLANES, 12>(maxc, p, q, lds);
-  return 0;  // (16 taps: 147 VGPRs, three waves per SIMD — the single-plane form is faster)
-}
-
-// growing heights (gather-form vertical pass): generic window addressing, one DMA per row, no scatter accumulators.  Ring of 2
-// rows for the triangle / box filters (never negative: the intermediate needs no clamp), of 6 for everything else.
-template <int C, int TW>
-int launch_up(int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (flt) {
-    if constexpr (TW >= 6 && TW <= 16)
-      return upk <= 2 ? launch_k<C, TW, 8, 1, false, false, false, true, 2>(p, q, lds, 0)
-                      : launch_k<C, TW, 8, 1, false, false, false, true, 6>(p, q, lds, 0);
-    return 0;
-  }
-  return (nonneg && upk <= 2) ? launch_k<C, TW, 8, 1, false, true, false, false, 2>(p, q, lds, 0)
-                              : launch_k<C, TW, 8, 1, false, false, false, false, 6>(p, q, lds, 0);
-}
-
-template <int C>
-int dispatch_up(int tw, int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds) {
-  if (flt && tw < 6) tw = 6;
-  if (tw <= 2) return launch_up<C, 2>(upk, nonneg, flt, p, q, lds);
-  if (tw <= 4) return launch_up<C, 4>(upk, nonneg, flt, p, q, lds);
-  if (tw <= 6) return launch_up<C, 6>(upk, nonneg, flt, p, q, lds);
-  if (tw <= 8) return launch_up<C, 8>(upk, nonneg, flt, p, q, lds);
-  if (tw <= 12) return launch_up<C, 12>(upk, nonneg, flt, p, q, lds);
-  if (tw <= 16) return launch_up<C, 16>(upk, nonneg, flt, p, q, lds);
-  return 0;
-}
-
 int round_tw(int taps) {
   const int opts[] = {2, 4, 6, 8, 12, 16, 24, 34};
   for (int o : opts)
@@ -1116,38 +878,19 @@ int round_tw(int taps) {
 
 }  // namespace
 
-// per-channel-count entry points (one translation unit each)
-int aa_v3_launch_c1(int tw, int maxc, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c3(int tw, int maxc, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c4(int tw, int maxc, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-// float arithmetic in the tolerance mode (aa_fused_u8_v3_c{1,3,4}ff.hip)
-int aa_v3_launch_c1ff(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c3ff(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c4ff(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-// wide windows, 17 .. 34 taps (aa_fused_u8_v3_c{1,3,4}w.hip)
-int aa_v3_launch_c1w(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c3w(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c4w(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-// plane groups: planar images of three channels (aa_fused_u8_v3_c3g.hip)
-int aa_v3_launch_c3g(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c3gf(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);   // float arithmetic
-int aa_v3_launch_c3gff(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);  // ... in the tolerance mode
-// wide windows in float arithmetic (aa_fused_u8_v3_c{1,3,4}wf.hip)
-int aa_v3_launch_c1wf(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c3wf(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c4wf(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-// split windows, 35 .. 136 taps (aa_fused_u8_v3_c{1,3,4}s.hip)
-int aa_v3_launch_c1s(int tws, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c3s(int tws, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c4s(int tws, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-// narrow windows with 5-6 open output rows (aa_fused_u8_v3_c{1,3,4}l.hip; float arithmetic in aa_fused_u8_v3_c{1,3,4}lf.hip)
-int aa_v3_launch_c1l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c3l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c4l(int tw, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-// straight alpha, 4 channels: narrow windows (aa_fused_u8_v3_c4a.hip) and narrow windows with 5-6 open output rows (aa_fused_u8_v3_c4al.hip)
-int aa_v3_launch_c4a(int tw, int maxc, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_c4al(int tw, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-// growing heights (aa_fused_u8_v3_c{1,3,4}u.hip)
-int aa_v3_launch_up_c1(int tw, int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_up_c3(int tw, int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
-int aa_v3_launch_up_c4(int tw, int upk, bool nonneg, bool flt, const FusedU8V3Params &p, const AAProblem &q, size_t lds);
+// ---- the layer above the kernel: aa_fused_u8_v3.hip plans, aa_fused_u8_v3_unit.hip launches, aa_fused_u8_v3_list.h lists
+enum V3Route {
+#define V3_ROUTE(route, ...) V3_##route,
+#include "aa_fused_u8_v3_list.h"
+};
+enum V3Arith { V3_PIL = 1, V3_FLT = 2, V3_BOTH = 3 };
+
+// One kernel of the compiled set, as the plan chose it: its route and every template argument, and the unit that compiled it
+struct V3Kernel;
+typedef int (*V3Launch)(const V3Kernel &k, const FusedU8V3Params *p, const AAProblem *q, size_t lds);  // (q == nullptr: does the unit
+                                                                                                       // hold k?  Launches nothing)
+struct V3Kernel {
+  int route, C, TW, MAXC, UPK, PL, SP;
+  bool ALPHA, FLT, fast, NONNEG, TWO_DMA, PERIODIC;  // fast: AA_V3_FLT_FAST
+  V3Launch launch;
+};

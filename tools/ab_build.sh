@@ -1,20 +1,22 @@
 #!/bin/bash
-# Developer A/B builds of libaa_interp.so: tools/ab_build.sh NAME "-DFLAG=1 ..." [file.hip ...]
-# Recompiles the listed translation units (default: the headline u8 kernel's, aa_fused_u8_v3_c3.hip) with the extra flags into
-# build_ab/NAME/ and links them with the stock objects into interpolate_antialiasing_amd/csrc/libaa_interp_NAME.so.
+# Developer A/B builds of libaa_interp.so: tools/ab_build.sh NAME "-DFLAG=1 ..." [object.o ...]
+# Recompiles the listed objects (default: the headline u8 kernel's, aa_fused_u8_v3_c3.o) with the extra flags into build_ab/NAME/,
+# using the Makefile's own compile command for each, and links them with the stock objects (every object the Makefile links, so run
+# make first) into interpolate_antialiasing_amd/csrc/libaa_interp_NAME.so.
 # Use with AA_INTERP_LIB=.../libaa_interp_NAME.so (see _lib.py).  Not part of the product build.
 set -e
 NAME=$1; FLAGS=$2; shift 2 || true
-FILES=${@:-aa_fused_u8_v3_c3.hip}
+PICK=${@:-aa_fused_u8_v3_c3.o}
 cd "$(dirname "$0")/../interpolate_antialiasing_amd/csrc"
 mkdir -p build_ab/$NAME
 OBJS=""
-for f in aa_api aa_tables aa_generic aa_fused_u8 aa_fused_u8_v3 aa_fused_u8_v3_c1 aa_fused_u8_v3_c3 aa_fused_u8_v3_c4 aa_fused_u8_v3_c1f aa_fused_u8_v3_c3f aa_fused_u8_v3_c4f aa_fused_u8_v3_c1u aa_fused_u8_v3_c3u aa_fused_u8_v3_c4u aa_fused_float aa_fused_float_up aa_backward; do
-  if echo " $FILES " | grep -q " $f.hip "; then
-    /opt/rocm/bin/hipcc $FLAGS -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -c $f.hip -o build_ab/$NAME/$f.o &
-    OBJS="$OBJS build_ab/$NAME/$f.o"
+for o in $(make -s print-objs); do
+  if echo " $PICK " | grep -q " $o "; then
+    CMD=$(make -s -n -B TUNING="$FLAGS" "$o" | grep hipcc)
+    eval "${CMD% -o *} -o build_ab/$NAME/$o" &
+    OBJS="$OBJS build_ab/$NAME/$o"
   else
-    OBJS="$OBJS $f.o"
+    OBJS="$OBJS $o"
   fi
 done
 wait
