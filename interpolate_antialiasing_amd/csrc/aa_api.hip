@@ -6,7 +6,7 @@
 
 #include "aa_common.h"
 
-int g_aa_store_form = -1;  // (aa_common.h; read by aa_fused_float_up.hip)
+int g_aa_store_form = -1;  // (aa_common.h; read by aa_fused_float.hip)
 int g_aa_plane_groups = 1;  // (aa_common.h; read by aa_fused_u8_v3.hip)
 
 namespace {
@@ -269,8 +269,7 @@ size_t aa_workspace_bytes(int dtype, int layout, int64_t N, int64_t C, int64_t H
   if (g_fused_enabled) {
     if (g_fused_enabled == 1 && aa_fused_u8_v3_applicable(dtype, layout, N, C, H, W, ax_h, ax_w)) return 0;
     if (aa_fused_u8_nhwc_applicable(dtype, layout, N, C, H, W, ax_h, ax_w)) return 0;
-    if (aa_fused_float_nchw_applicable(dtype, layout, N, C, H, W, ax_h, ax_w)) return 0;
-    if (aa_fused_float_nchw_up_applicable(dtype, layout, N, C, H, W, ax_h, ax_w)) return 0;
+    if (aa_fused_float_applicable(dtype, layout, N, C, H, W, ax_h, ax_w)) return 0;
   }
   return aa_generic_workspace_bytes(dtype, ax_w->kind, N, C, H, oW);
 }
@@ -354,7 +353,8 @@ static int resample_fwd_impl(const void *in_dev, void *out_dev, void *workspace_
   p.stream = (hipStream_t)stream;
   p.in_row_pitch = row_pitch; p.in_img_pitch = img_pitch;
   // (Pillow's integer arithmetic and double arithmetic have no tolerance mode; uint8 images with AA_TABLE_F32 tables = the harness's float arithmetic do)
-  p.fast = (flags & AA_FLAG_FAST) && dtype != AA_F64 && ax_w->kind == AA_TABLE_F32 ? 1 : 0;
+  // (the first-generation kernels of mode 2 have no tolerance mode either)
+  p.fast = (flags & AA_FLAG_FAST) && dtype != AA_F64 && ax_w->kind == AA_TABLE_F32 && g_fused_enabled == 1 ? 1 : 0;
   p.alpha = alpha ? 1 : 0;
 
   const char *variant = "none";
@@ -387,11 +387,9 @@ static int resample_fwd_impl(const void *in_dev, void *out_dev, void *workspace_
     return rc;
   }
   if (g_fused_enabled) {
-    if (g_fused_enabled == 1 && p.fast && dtype != AA_U8) rc = aa_try_fused_float_nchw_fast(p, &variant);  // declines -> the exact kernels (always within tolerance)
-    if (rc == 0 && g_fused_enabled == 1) rc = aa_try_fused_u8_nhwc_v3(p, &variant);
-    if (rc == 0 && !row_pitch) rc = aa_try_fused_u8_nhwc(p, &variant);  // (only the two main kernels take pitched views)
-    if (rc == 0) rc = aa_try_fused_float_nchw(p, &variant);
-    if (rc == 0 && !row_pitch) rc = aa_try_fused_float_nchw_up(p, &variant);
+    if (g_fused_enabled == 1) rc = aa_try_fused_u8_nhwc_v3(p, &variant);
+    if (rc == 0 && !row_pitch) rc = aa_try_fused_u8_nhwc(p, &variant);  // (the first-generation kernel takes dense tensors only)
+    if (rc == 0) rc = aa_try_fused_float(p, &variant);
   }
   if (rc < 0) return rc;
   if (rc == 1) {

@@ -48,7 +48,7 @@ __host__ __device__ inline size_t aa_table_weights_end(int kind, int64_t out, in
   return aa_align16(aa_table_w_off(out) + (size_t)out * (size_t)ksize * aa_weight_elem_bytes(kind));
 }
 // gather section (AA_TABLE_F32 and AA_TABLE_PIL tables; F32 also transposed): one 32-byte record per OUTPUT index
-// {xmin, xsize, w[0..5]} — a table row in one scalar load for kernels whose vertical pass gathers (aa_fused_float_up.hip, the UPK mode of aa_fused_u8_v3_impl.h)
+// {xmin, xsize, w[0..5]} — a table row in one scalar load for kernels whose vertical pass gathers (aa_fused_float_up_impl.h, the UPK mode of aa_fused_u8_v3_impl.h)
 __host__ __device__ inline size_t aa_table_gather_bytes(int kind, int64_t out) { return (kind == AA_TABLE_F32 || kind == AA_TABLE_PIL) ? 32 * (size_t)out : 0; }
 __host__ __device__ inline size_t aa_table_total_bytes(int kind, int64_t out, int ksize) {
   return aa_table_weights_end(kind, out, ksize) + aa_table_gather_bytes(kind, out);
@@ -140,10 +140,8 @@ size_t aa_generic_workspace_bytes(int dtype, int kind_w, int64_t N, int64_t C, i
 int aa_launch_generic_convert(const AAProblem &p, const char **variant);  // u8 -> f32 (+ layout, normalisation), two launches
 // fused single-launch paths; return 1 when they took the problem, 0 when not applicable, <0 on error
 int aa_try_fused_u8_nhwc(const AAProblem &p, const char **variant);
-int aa_try_fused_float_nchw(const AAProblem &p, const char **variant);
-int aa_try_fused_float_nchw_up(const AAProblem &p, const char **variant);  // H <= oH: adjoint (gather form), up-scaling
-int aa_try_fused_float_nchw_fast(const AAProblem &p, const char **variant);  // tolerance mode (aa_fused_float.hip built with -DAA_F32_FAST_BUILD)
-bool aa_fused_float_nchw_fast_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
+// float planes and fp32 channels_last: shrinking heights (scatter form), then growing ones (gather form: the adjoint, up-scaling)
+int aa_try_fused_float(const AAProblem &p, const char **variant);
 int aa_try_fused_u8_nhwc_v3(const AAProblem &p, const char **variant);  // LDS-DMA staged, wave-autonomous, V pass in registers
 // The *_applicable predicates hold EVERY reason a fused path can decline that does not depend on the pointers (shape, LDS
 // size, grid size, dispatch widths): aa_workspace_bytes() answers 0 exactly when aa_resample_fwd() will not need one.
@@ -154,8 +152,7 @@ bool aa_fused_u8_v3_applicable(int dtype, int layout, int64_t N, int64_t C, int6
 int aa_launch_premul_u8(const void *src, void *dst, int layout, int64_t N, int64_t C, int64_t H, int64_t W, hipStream_t stream);
 int aa_launch_unpremul_u8(void *img, int layout, int64_t N, int64_t C, int64_t H, int64_t W, hipStream_t stream);
 bool aa_fused_u8_nhwc_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
-bool aa_fused_float_nchw_up_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
-bool aa_fused_float_nchw_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
+bool aa_fused_float_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
 // Input pixels the windows (tw taps each) of one strip of <= 64 consecutive outputs cover, from the spread the table
 // kernel MEASURED (header.span64p1; explicit scale factors and align_corners make it differ from 63 * in / out).
 // -1 = unknown (a caller that did not fill aa_axis.span64p1): the fused kernels decline.

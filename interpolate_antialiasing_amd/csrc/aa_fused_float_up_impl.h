@@ -1,8 +1,8 @@
-// aa_fused_float_up.hip — fused single-launch resample for fp32 NCHW planes whose height does not shrink (H <= oH):
+// aa_fused_float_up_impl.h — fused single-launch resample for fp32 NCHW planes whose height does not shrink (H <= oH):
 // the gather form of the true adjoint (aa_resample_bwd = forward resample of grad_out with the transposed tables,
 // BASELINE config 5: [.,3,196,320] -> [.,3,438,906]) and forward up-scaling (test.py's 906x438 -> 1200x1200 sizes).
 //
-// aa_fused_float.hip keeps its vertical pass in registers in scatter form, which needs every output row to complete
+// aa_fused_float_impl.h keeps its vertical pass in registers in scatter form, which needs every output row to complete
 // once and in order — true when the height shrinks.  When it grows, every input row feeds several output rows and an
 // output row needs only the last few input rows, so the vertical pass runs in GATHER form over a small register ring.
 // This path is write-bound (4.76 MB out per 0.75 MB in for the backward of config A) and its arithmetic is tiny (2-4 taps
@@ -15,10 +15,10 @@
 //   * the 4 windows of a lane overlap (heights and widths grow here), so the lane reads their UNION once per input row
 //     (U = taps + spread of 4 neighbouring window starts, measured by the table kernel: header.span4p1) and every output
 //     accumulates over the union with its own weights; positions outside an output's own taps are skipped with scalar
-//     lane masks exactly as in aa_fused_float.hip (never added with a zero weight: no non-finite neighbour leaks in, sums
+//     lane masks exactly as in aa_fused_float_impl.h (never added with a zero weight: no non-finite neighbour leaks in, sums
 //     are the reference's bit for bit: tap 0 first, product and sum rounded separately, -ffp-contract=off);
 //   * input-row segments are staged into a private G-slot LDS ring by LDS-DMA, the source rounded down to a multiple of
-//     four floats OF THE ROW (constant phase of the LDS image, see aa_fused_float.hip);
+//     four floats OF THE ROW (constant phase of the LDS image, see aa_fused_float_impl.h);
 //   * the horizontal-pass results of the KR most recent input rows live in a register ring; an output row is emitted as
 //     soon as its last input row has been pushed, so its window is always the ring's LAST ysize entries: the gather is
 //     one of KR static unrollings selected by ysize alone; weights come from the table row by scalar loads issued one
@@ -26,15 +26,16 @@
 //   * output stores and staging DMAs share the in-order vmcnt counter and there are ~2 stores per DMA, so the wave keeps
 //     the issue index of every slot's DMA and waits for exactly the operations older than it (a 4-level decision tree).
 
+//
+// This header holds the kernel template and launch_k, which launches one instantiation; aa_fused_float_impl.h says where the compiled set,
+// the units and the plan live.
+#pragma once
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include "aa_common.h"
 
-#ifndef AA_UP_G
-#define AA_UP_G 8  // staged input rows per wave
-#endif
 #ifndef AA_UP_DMA_AUX
 #define AA_UP_DMA_AUX 0    // cache-policy bits of the staging DMA (developer knob; nt loads are slower: neighbouring strips and bands re-read rows)
 #endif
@@ -96,7 +97,7 @@ __device__ inline float select_by_mask_up(float a, float b, unsigned long long m
 }
 
 // 16-bit planes (round 3, template parameter DT): halves are staged and read as halves and converted on the way into the fp32 arithmetic;
-// results are rounded once, at the store (= half(reference_fp32(float(x))), like aa_fused_float.hip); a lane's CPL results leave as one
+// results are rounded once, at the store (= half(reference_fp32(float(x))), like aa_fused_float_impl.h); a lane's CPL results leave as one
 // 8-byte store.  The streaming store forms that cut pieces at sector boundaries are fp32-only: 16-bit outputs take the plain forms.
 template <int DT> __device__ inline float up_elem_to_f32(unsigned short bits);
 template <> __device__ inline float up_elem_to_f32<AA_F16>(unsigned short bits) {
@@ -248,7 +249,7 @@ fused_f32_nchw_up_kernel(const void *__restrict__ in, void *__restrict__ out, co
 
   // one input row: wait for its DMA, union window from LDS, reference-order accumulation per output, refill, push
   // 16-bit elements, odd W: the dword holding the tensor's final element straddles the end of the tensor and is refused by the range
-  // check (see aa_fused_float.hip: nothing may be read past a tensor); lane 0 fetches that element on its own into the staged row
+  // check (see aa_fused_float_impl.h: nothing may be read past a tensor); lane 0 fetches that element on its own into the staged row
   const int fix_row = (ES == 2 && (p.W & 1) && (long long)plane + 1 == p.n_groups / p.ybands) ? p.H - 1 : -1;
   auto hpass_row = [&]() {
     const int my_idx = __builtin_amdgcn_readlane(idxv, slot_top);
@@ -542,112 +543,4 @@ int launch_k(FusedF32UpParams p, const AAProblem &q, size_t lds) {
   return 1;
 }
 
-template <int U, int CPL, int DT>
-int launch_kr(int kr, const FusedF32UpParams &p, const AAProblem &q, size_t lds) {
-  if (kr <= 2) return launch_k<U, AA_UP_G, 2, CPL, DT>(p, q, lds);
-  if (kr <= 4) return launch_k<U, AA_UP_G, 4, CPL, DT>(p, q, lds);
-  return launch_k<U, AA_UP_G, 6, CPL, DT>(p, q, lds);
-}
-
-// Columns per lane and union width: the widest CPL whose CPL * U lane masks fit the scalar registers (<= 20) and whose
-// strip segment is one DMA instruction (<= 64 pieces); U = taps + spread of CPL neighbouring window starts.
-struct UpGeometry { int cpl, u, nstrips, strip_w, nseg; };
-
-bool up_geometry(int64_t W, const aa_axis &aw, UpGeometry *g, int es = 4) {
-  const int taps_w = aw.max_taps > 0 ? aw.max_taps : aw.ksize;
-  if (taps_w > 8 || aw.span64p1 <= 0 || aw.span4p1 <= 0) return false;
-  const int64_t oW = aw.out_size;
-  const int cands[3] = {4, 2, 1};
-  for (int ci = 0; ci < 3; ci++) {
-    const int cpl = cands[ci];
-    if (cpl > 1 && oW < 64 * cpl) continue;  // narrow outputs: keep the lanes busy
-    // spread of cpl neighbouring window starts (span4p1 - 1 covers 4; 2 neighbours spread at most as much)
-    const int spread = cpl == 1 ? 0 : aw.span4p1 - 1;
-    int u = taps_w + spread;
-    const int opts[6] = {2, 3, 4, 5, 6, 8};
-    int uu = 0;
-    for (int o : opts)
-      if (u <= o) { uu = o; break; }
-    if (uu == 0 || uu * cpl > 20 || W < uu) continue;
-    // floats a strip of 64 * cpl outputs covers: cpl * spread of 64 starts (+3: rounded down to a multiple of 4) + union
-    const int span = cpl * (aw.span64p1 - 1) + cpl + uu + (16 / es - 1);  // (+: the segment start rounded down to a 16-byte piece of the row)
-    const int nseg = (span * es + 15) / 16 + 1;
-    if (nseg > 64) continue;
-    g->cpl = cpl; g->u = uu; g->nseg = nseg;
-    g->strip_w = 64 * cpl;
-    g->nstrips = (int)((oW + g->strip_w - 1) / g->strip_w);
-    return true;
-  }
-  return false;
-}
-
 }  // namespace
-
-bool aa_fused_float_nchw_up_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah,
-                                       const aa_axis *aw) {
-  if ((dtype != AA_F32 && dtype != AA_F16 && dtype != AA_BF16) || layout != AA_NCHW) return false;
-  if (!ah || !aw || ah->kind != AA_TABLE_F32 || aw->kind != AA_TABLE_F32) return false;
-  const int es = dtype == AA_F32 ? 4 : 2;
-  if (H > ah->out_size) return false;  // shrinking heights: aa_fused_float.hip
-  const int taps_h = ah->max_taps > 0 ? ah->max_taps : ah->ksize;
-  if (taps_h > 6 || ah->gather_off <= 0) return false;  // (a gather record holds 6 weights)
-  UpGeometry g;
-  if (!up_geometry(W, *aw, &g, es)) return false;
-  if ((uint64_t)H * W * 4 > 0xFFFFFFF0ull || (uint64_t)ah->out_size * aw->out_size * 4 > 0xFFFFFFF0ull) return false;
-  if (!aa_grid_fits(N * C * g.nstrips)) return false;
-  return true;
-}
-
-int aa_try_fused_float_nchw_up(const AAProblem &q, const char **variant) {
-  if (!aa_fused_float_nchw_up_applicable(q.dtype, q.layout, q.N, q.C, q.H, q.W, &q.ah, &q.aw)) return 0;
-  const int taps_h = q.ah.max_taps > 0 ? q.ah.max_taps : q.ah.ksize;
-  const int es = q.dtype == AA_F32 ? 4 : 2;
-  if (((uintptr_t)q.out & (es - 1)) != 0 || ((uintptr_t)q.in & (es - 1)) != 0) return 0;
-  UpGeometry g;
-  up_geometry(q.W, q.aw, &g, es);
-
-  FusedF32UpParams p;
-  p.H = (int)q.H; p.W = (int)q.W; p.oH = (int)q.oH; p.oW = (int)q.oW;
-  p.ksize_w = q.aw.ksize; p.ksize_h = q.ah.ksize;
-  p.plane_in_bytes = (unsigned long long)q.H * q.W * es;
-  p.plane_out_bytes = (unsigned long long)q.oH * q.oW * es;
-  p.total_in_bytes = p.plane_in_bytes * (unsigned long long)(q.N * q.C);
-  p.total_out_bytes = p.plane_out_bytes * (unsigned long long)(q.N * q.C);
-  p.nstrips = g.nstrips;
-  p.strip_w = g.strip_w;
-  p.strips_per_block = p.nstrips <= 8 ? p.nstrips : 4;
-  p.nseg = g.nseg;
-  p.seg_bytes = p.nseg * 16;
-  p.gather_off = q.ah.gather_off;
-  p.store_nt = g_aa_store_form < 0 ? (p.total_out_bytes > (64ull << 20) ? 1 : 0) : (g_aa_store_form ? 1 : 0);  // (aa_set_store_form: tests of the
-                                                                                                               // streaming forms at small sizes)
-  // rows or planes that are not whole 64-byte sectors: stream only the whole sectors of each piece (see the store)
-  if (es == 4 && p.store_nt && g.cpl == 4 && ((((uintptr_t)q.out) | (uint64_t)q.oW * 4u | p.plane_out_bytes) & 63u) != 0 && !aa_knob("AA_UP_NO_SPLIT"))
-    p.store_nt = 2;
-  // ... and when the rows are 8-byte but not 16-byte aligned (oW = 906): strips cut at the sector boundaries of each row instead
-  // (see the store).  Measured, [256,3,196,320] gradients -> 438 x W (ms, split + pacing | sector-aligned pieces): W = 898 0.347 | 0.312,
-  // 906 0.321 | 0.301-0.311; rows that are 16-byte aligned are better off with the split: 900 0.257 | 0.303, 904 0.269 | 0.284
-  if (p.store_nt == 2 && q.oW % 4 == 2 && ((uintptr_t)q.out & 15) == 0 && !aa_knob("AA_UP_NO_ALN")) {
-    p.store_nt = 3;
-    p.strip_w = 240;
-    p.nstrips = (int)((q.oW + 14 + 239) / 240);
-    p.strips_per_block = p.nstrips <= 8 ? p.nstrips : 4;
-  }
-  p.pace_all = aa_knob("AA_UP_PACE_ALL") ? 1 : 0;
-  p.ybands = 1;
-  p.n_groups = 0;
-  const size_t lds = (size_t)AA_UP_G * p.seg_bytes + (p.store_nt == 3 ? 1088 : 0);  // per strip: stage ring (+ the aligned-store staging area)
-
-  int rc = 0;
-#define AA_UP_CASE(UU, CC)                                                                     \
-  if (g.u == UU && g.cpl == CC)                                                                \
-    rc = q.dtype == AA_F32 ? launch_kr<UU, CC, AA_F32>(taps_h, p, q, lds)                      \
-                           : (q.dtype == AA_F16 ? launch_kr<UU, CC, AA_F16>(taps_h, p, q, lds) \
-                                                : launch_kr<UU, CC, AA_BF16>(taps_h, p, q, lds))
-  AA_UP_CASE(2, 4); else AA_UP_CASE(3, 4); else AA_UP_CASE(4, 4); else AA_UP_CASE(5, 4);
-  else AA_UP_CASE(2, 2); else AA_UP_CASE(3, 2); else AA_UP_CASE(4, 2); else AA_UP_CASE(5, 2); else AA_UP_CASE(6, 2); else AA_UP_CASE(8, 2);
-  else AA_UP_CASE(2, 1); else AA_UP_CASE(3, 1); else AA_UP_CASE(4, 1); else AA_UP_CASE(5, 1); else AA_UP_CASE(6, 1); else AA_UP_CASE(8, 1);
-#undef AA_UP_CASE
-  if (rc == 1) *variant = q.dtype == AA_F32 ? "fused_f32_nchw_up" : (q.dtype == AA_F16 ? "fused_f16_nchw_up" : "fused_bf16_nchw_up");
-  return rc;
-}

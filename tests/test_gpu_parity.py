@@ -817,8 +817,24 @@ def test_fused_segments_follow_the_tables_scale(aa):
 def test_workspace_answer_matches_dispatch(aa):
     """aa_workspace_bytes() says 0 exactly when aa_resample_fwd() will not ask for one: thumbnail shapes whose windows (13-16
     taps) are too wide for the newest uint8 kernel and whose intermediate ring is too big for the first one must run the
-    generic path with a workspace instead of failing (uint8 channels_last bicubic 1750 -> 500, bilinear 2400 -> 400)."""
-    from interpolate_antialiasing_amd import _lib
+    generic path with a workspace instead of failing (uint8 channels_last bicubic 1750 -> 500, bilinear 2400 -> 400).  The fused
+    float kernels keep the same promise on each of their routes (fp32 and fp16 planes, fp32 channels_last, growing heights), and a
+    float shape none of them takes (bilinear 2200 -> 100 columns: 45 taps) gets a workspace and the generic path."""
+    import ctypes
+
+    from interpolate_antialiasing_amd import _lib, tables
+
+    L = _lib.load()
+
+    def ws_bytes(fn, x, size):  # what aa_workspace_bytes() answers for the call fn(x, size)
+        filt = _lib.FILTER_CUBIC if fn is aa.cubic_forward else _lib.FILTER_LINEAR
+        kind = _lib.TABLE_PIL if x.dtype == torch.uint8 else _lib.TABLE_F32
+        n, c, h, w = x.shape
+        ah = tables.get_table(filt, kind, h, size[0], False, 0.0, x.device).axis()
+        aw = tables.get_table(filt, kind, w, size[1], False, 0.0, x.device).axis()
+        dt = {torch.uint8: _lib.U8, torch.float32: _lib.F32, torch.float16: _lib.F16}[x.dtype]
+        layout = _lib.NCHW if x.is_contiguous() else _lib.NHWC
+        return L.aa_workspace_bytes(dt, layout, n, c, h, w, size[0], size[1], ctypes.byref(ah), ctypes.byref(aw))
 
     torch.manual_seed(12)
     for fn, shape, size, want in ((aa.cubic_forward, (2, 1750, 1750, 3), [500, 500], "fused_u8_nhwc_pil_v3"),     # 15 taps
@@ -837,8 +853,25 @@ def test_workspace_answer_matches_dispatch(aa):
             _lib.set_fused(1)
         assert torch.equal(y, y0), (shape, size, v)
         assert v == want, (v, shape, size)  # 13-16 taps: the 16-tap window instantiation of the newest kernel
+        assert (ws_bytes(fn, x, size) == 0) == v.startswith("fused_"), (v, shape, size)
         exp = oracle.pil_resize_u8("cubic" if fn is aa.cubic_forward else "linear", x[:1].cpu().numpy(), tuple(size))
         assert np.array_equal(y[:1].cpu().numpy(), exp), (shape, size, v)
+    # the fused float kernels: every route of their plan, and a shape none takes (bilinear 2200 -> 100 columns: 45 taps, NQ 11 holds 41)
+    for fn, x, size, want in ((aa.linear_forward, torch.randn(2, 3, 438, 906, device="cuda"), [196, 320], "fused_f32_nchw"),
+                              (aa.cubic_forward, torch.randn(2, 3, 438, 906, device="cuda").half(), [196, 320], "fused_f16_nchw"),
+                              (aa.linear_forward, torch.randn(2, 438, 906, 3, device="cuda").permute(0, 3, 1, 2), [196, 320], "fused_f32_nhwc"),
+                              (aa.linear_forward, torch.randn(2, 3, 196, 320, device="cuda"), [438, 906], "fused_f32_nchw_up"),
+                              (aa.linear_forward, torch.randn(1, 3, 64, 2200, device="cuda"), [32, 100], "generic_2pass_f32")):
+        y = fn(x, size)
+        v = _lib.last_variant()
+        try:
+            _lib.set_fused(0)
+            y0 = fn(x, size)
+        finally:
+            _lib.set_fused(1)
+        assert v == want, (v, tuple(x.shape), size)
+        assert torch.equal(y, y0), (tuple(x.shape), size, v)
+        assert (ws_bytes(fn, x, size) == 0) == v.startswith("fused_"), (v, tuple(x.shape), size)
 
 
 # ------------------------------------------------------------------------------------------------ §8f-3: decode-adjacent fusion
