@@ -4,7 +4,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "aa_common.h"
+#include "aa_plan.h"
 
 int g_aa_store_form = -1;  // (aa_common.h; read by aa_fused_float.hip)
 int g_aa_plane_groups = 1;  // (aa_common.h; read by aa_fused_u8_v3.hip)
@@ -63,6 +63,164 @@ int check_dtype_kind(int dtype, int kh, int kw) {
   if (dtype == AA_U8 && (kh == AA_TABLE_PIL || kh == AA_TABLE_F32)) return AA_OK;
   if ((dtype == AA_F16 || dtype == AA_BF16) && kh == AA_TABLE_F32) return AA_OK;
   return AA_ERR_BAD_DTYPE;
+}
+
+// ---- the forward: one plan, for workspace sizing and launch alike --------------------------------------------------------------------
+
+// AA_FLAG_PREMUL_ALPHA: uint8 images of Pillow's integer arithmetic with 2 or 4 channels, straight alpha last
+bool alpha_ok(int dtype, int64_t C, const aa_axis &ah, const aa_axis &aw) {
+  return dtype == AA_U8 && (C == 2 || C == 4) && ah.kind == AA_TABLE_PIL && aw.kind == AA_TABLE_PIL;
+}
+
+// The problem without its pointers.  oH / oW: the axes' out_size at the entry points, the caller's at aa_workspace_bytes (whose answer
+// has always sized the two-pass intermediate from its oW argument).
+AAProblem problem(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW, const aa_axis &ah,
+                  const aa_axis &aw, unsigned flags) {
+  AAProblem q{};
+  q.dtype = dtype; q.layout = layout;
+  q.N = N; q.C = C; q.H = H; q.W = W; q.oH = oH; q.oW = oW;
+  q.ah = ah; q.aw = aw;
+  q.fast = (flags & AA_FLAG_FAST) ? 1 : 0;
+  q.alpha = (flags & AA_FLAG_PREMUL_ALPHA) ? 1 : 0;
+  return q;
+}
+
+enum FwdRoute { FWD_EMPTY, FWD_ALPHA_COPY, FWD_V3, FWD_V1, FWD_FLOAT, FWD_GENERIC, FWD_CONVERT, FWD_ALPHA_3STEP };
+
+// Which path a forward takes and the workspace it needs, decided once from the problem without its pointers: the aa_workspace_bytes*
+// functions answer from it and the forward runs it, so the answer is 0 exactly when the forward needs no workspace.
+struct FwdPlan {
+  int route;
+  int inner;    // FWD_ALPHA_3STEP: the route of its resample of the premultiplied copy
+  size_t copy;  // FWD_ALPHA_3STEP: the premultiplied copy, the first part of the workspace
+  size_t ws;    // the resample's two-pass intermediate
+  V3Plan v3;    // the chosen family's plan
+  V1Plan v1;
+  F32Plan f32;
+  size_t bytes() const { return copy + ws; }
+};
+
+FwdPlan plan_fwd(const AAProblem &q) {
+  const int mode = g_fused_enabled;  // aa_set_fused: 1 tries v3, v1, float in this order; 2 v1 and float; 0 the two-pass path only
+  FwdPlan pl{};
+  if (q.N == 0) {  // empty batch is allowed (s2.2:747-750)
+    pl.route = FWD_EMPTY;
+  } else if (q.alpha) {
+    if (q.oH == q.H && q.oW == q.W) {  // Pillow's resize returns a copy: no lossy round trip through premultiplied values
+      pl.route = FWD_ALPHA_COPY;
+    } else if (mode == 1 && aa_v3_plan(q, false, &pl.v3)) {
+      pl.route = FWD_V3;
+    } else {  // three steps: premultiplied copy of the input into the workspace, the ordinary resample of it, un-premultiply in place
+      AAProblem d = q;
+      d.alpha = 0;
+      d.in_row_pitch = d.in_img_pitch = 0;
+      pl = plan_fwd(d);
+      pl.inner = pl.route;
+      pl.route = FWD_ALPHA_3STEP;
+      pl.copy = aa_align16((size_t)(q.N * q.C * q.H * q.W));
+    }
+  } else {
+    // (Pillow's integer arithmetic and double arithmetic have no tolerance mode; uint8 images with AA_TABLE_F32 tables = the harness's
+    // float arithmetic do.  The first-generation kernels of mode 2 have no tolerance mode either)
+    const bool fast = q.fast && mode == 1 && q.dtype != AA_F64 && q.aw.kind == AA_TABLE_F32;
+    // uint8 -> float32 (out_f32): v3 or the two-pass conversion.  The first-generation kernel takes dense tensors only.
+    const bool v3 = mode == 1 && aa_v3_plan(q, fast, &pl.v3);
+    if (!q.out_f32 && mode != 0 && !q.in_row_pitch && (!v3 || pl.v3.v1_first) && aa_v1_plan(q, &pl.v1)) pl.route = FWD_V1;
+    else if (v3) pl.route = FWD_V3;
+    else if (!q.out_f32 && mode != 0 && aa_f32_plan(q, fast, &pl.f32)) pl.route = FWD_FLOAT;
+    else {
+      pl.route = q.out_f32 ? FWD_CONVERT : FWD_GENERIC;
+      pl.ws = aa_generic_workspace_bytes(q.dtype, q.out_f32 ? AA_TABLE_F32 : q.aw.kind, q.N, q.C, q.H, q.oW);
+    }
+  }
+  return pl;
+}
+
+int run_fwd(const FwdPlan &pl, int route, const AAProblem &q) {
+  const char *variant = "none";
+  int rc;
+  switch (route) {
+    case FWD_EMPTY: rc = AA_OK; variant = "empty"; break;
+    case FWD_V3: rc = aa_v3_launch(pl.v3, q); variant = pl.v3.variant; break;
+    case FWD_V1: rc = aa_v1_launch(pl.v1, q); variant = "fused_u8_nhwc_pil"; break;
+    case FWD_FLOAT: rc = aa_f32_launch(pl.f32, q); variant = pl.f32.variant; break;
+    case FWD_ALPHA_COPY:
+      if (q.in_row_pitch) return AA_ERR_STRIDES;
+      if (hipMemcpyAsync(q.out, q.in, (size_t)(q.N * q.C * q.H * q.W), hipMemcpyDeviceToDevice, q.stream) != hipSuccess) return AA_ERR_HIP;
+      rc = AA_OK;
+      variant = "alpha_copy";
+      break;
+    case FWD_GENERIC:
+    case FWD_CONVERT:
+      if (q.in_row_pitch) return AA_ERR_STRIDES;  // no kernel for this view: the caller makes a dense copy (what the two-launch path needs anyway)
+      if (!q.ws || q.ws_bytes < pl.ws) return AA_ERR_WORKSPACE;
+      rc = route == FWD_GENERIC ? aa_launch_generic_fwd(q, &variant) : aa_launch_generic_convert(q, &variant);
+      break;
+    default: {  // FWD_ALPHA_3STEP
+      if (q.in_row_pitch) return AA_ERR_STRIDES;
+      if (!q.ws || q.ws_bytes < pl.bytes()) return AA_ERR_WORKSPACE;
+      AAProblem d = q;  // the resample reads the premultiplied copy and has the rest of the workspace
+      d.in = q.ws;
+      d.ws = (char *)q.ws + pl.copy;
+      d.ws_bytes = q.ws_bytes - pl.copy;
+      d.alpha = 0;
+      rc = aa_launch_premul_u8(q.in, q.ws, q.layout, q.N, q.C, q.H, q.W, q.stream);
+      if (rc == AA_OK) rc = run_fwd(pl, pl.inner, d);
+      if (rc == AA_OK) rc = aa_launch_unpremul_u8(q.out, q.layout, q.N, q.C, q.oH, q.oW, q.stream);
+      variant = "alpha_3step";
+    }
+  }
+  if (rc == AA_OK) g_last_variant = variant;
+  return rc;
+}
+
+// What every forward does after its own argument checks: plan, check the pointers, run the route
+int resample(AAProblem &q, const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  const FwdPlan pl = plan_fwd(q);
+  if (pl.route != FWD_EMPTY) {
+    if (!in_dev || !out_dev) return AA_ERR_NULL;
+    // a tensor of 2 / 4 / 8-byte elements starts on an element boundary; anything else is not a tensor (and the kernels' dispatch must
+    // not depend on the pointers: aa_workspace_bytes answers from the shape alone)
+    const uintptr_t es = q.dtype == AA_U8 ? 1 : (q.dtype == AA_F64 ? 8 : (q.dtype == AA_F32 ? 4 : 2));
+    if ((((uintptr_t)in_dev | (uintptr_t)out_dev) & (es - 1)) != 0) return AA_ERR_BAD_SHAPE;
+  }
+  q.in = in_dev; q.out = out_dev; q.ws = workspace_dev; q.ws_bytes = workspace_bytes;
+  q.stream = (hipStream_t)stream;
+  return run_fwd(pl, pl.route, q);
+}
+
+int resample_fwd_impl(const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int dtype, int layout, int64_t N,
+                      int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w, unsigned flags, int64_t row_pitch,
+                      int64_t img_pitch, aa_stream_t stream) {
+  if (flags & ~(unsigned)(AA_FLAG_FAST | AA_FLAG_PREMUL_ALPHA)) return AA_ERR_BAD_SHAPE;
+  if (dtype < AA_U8 || dtype > AA_BF16) return AA_ERR_BAD_DTYPE;
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (N < 0 || C <= 0 || H <= 0 || W <= 0) return AA_ERR_BAD_SHAPE;
+  int rc = check_axis(ax_h, H);
+  if (rc != AA_OK) return rc;
+  rc = check_axis(ax_w, W);
+  if (rc != AA_OK) return rc;
+  rc = check_dtype_kind(dtype, ax_h->kind, ax_w->kind);
+  if (rc != AA_OK) return rc;
+  if ((flags & AA_FLAG_PREMUL_ALPHA) && !alpha_ok(dtype, C, *ax_h, *ax_w)) return AA_ERR_BAD_DTYPE;
+  AAProblem q = problem(dtype, layout, N, C, H, W, ax_h->out_size, ax_w->out_size, *ax_h, *ax_w, flags);
+  q.in_row_pitch = row_pitch;
+  q.in_img_pitch = img_pitch;
+  return resample(q, in_dev, out_dev, workspace_dev, workspace_bytes, stream);
+}
+
+// the decode-adjacent conversion's settings; the checks in their order (the fields are filled first: aa_workspace_bytes_u8_to_f32 plans
+// with them whatever the checks say)
+int fill_convert(AAProblem &q, const aa_convert &cv) {
+  q.out_f32 = 1;
+  q.out_layout = cv.out_layout;
+  q.normalize = cv.normalize ? 1 : 0;
+  for (int i = 0; i < 4; i++) { q.mean[i] = cv.mean[i]; q.std[i] = cv.std[i]; }
+  q.fast = (cv.flags & AA_FLAG_FAST) ? 1 : 0;
+  if (cv.out_layout != AA_NCHW && cv.out_layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (cv.normalize && q.C > 4) return AA_ERR_BAD_SHAPE;
+  if (cv.flags & ~(uint32_t)AA_FLAG_FAST) return AA_ERR_BAD_SHAPE;
+  return AA_OK;
 }
 
 }  // namespace
@@ -247,31 +405,16 @@ int aa_table_transpose(const void *table_dev, void *tr_table_dev, size_t tr_tabl
   return aa_launch_table_transpose(h, table_dev, tr_table_dev, tr_ksize, (hipStream_t)stream);
 }
 
-// AA_FLAG_PREMUL_ALPHA: uint8 images of Pillow's integer arithmetic with 2 or 4 channels, straight alpha last
-static bool alpha_ok(int dtype, int64_t C, const aa_axis *ax_h, const aa_axis *ax_w) {
-  return dtype == AA_U8 && (C == 2 || C == 4) && ax_h->kind == AA_TABLE_PIL && ax_w->kind == AA_TABLE_PIL;
-}
-
 size_t aa_workspace_bytes_ex(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW,
                              const aa_axis *ax_h, const aa_axis *ax_w, unsigned flags) {
-  if (!(flags & AA_FLAG_PREMUL_ALPHA)) return aa_workspace_bytes(dtype, layout, N, C, H, W, oH, oW, ax_h, ax_w);
-  if (!ax_h || !ax_w || N <= 0 || !alpha_ok(dtype, C, ax_h, ax_w)) return 0;
-  if (oH == H && oW == W) return 0;  // (a copy)
-  if (g_fused_enabled == 1 && aa_fused_u8_v3_applicable(dtype, layout, N, C, H, W, ax_h, ax_w, 0, AA_NCHW, 1)) return 0;
-  // the three-step fallback: the premultiplied copy of the input, then what the ordinary resample of it needs
-  return aa_align16((size_t)(N * C * H * W)) + aa_workspace_bytes(dtype, layout, N, C, H, W, oH, oW, ax_h, ax_w);
+  if (!ax_h || !ax_w || N <= 0) return 0;
+  if ((flags & AA_FLAG_PREMUL_ALPHA) && !alpha_ok(dtype, C, *ax_h, *ax_w)) return 0;
+  return plan_fwd(problem(dtype, layout, N, C, H, W, oH, oW, *ax_h, *ax_w, flags)).bytes();
 }
 
 size_t aa_workspace_bytes(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW,
                           const aa_axis *ax_h, const aa_axis *ax_w) {
-  (void)oH;
-  if (!ax_h || !ax_w || N <= 0) return 0;
-  if (g_fused_enabled) {
-    if (g_fused_enabled == 1 && aa_fused_u8_v3_applicable(dtype, layout, N, C, H, W, ax_h, ax_w)) return 0;
-    if (aa_fused_u8_nhwc_applicable(dtype, layout, N, C, H, W, ax_h, ax_w)) return 0;
-    if (aa_fused_float_applicable(dtype, layout, N, C, H, W, ax_h, ax_w)) return 0;
-  }
-  return aa_generic_workspace_bytes(dtype, ax_w->kind, N, C, H, oW);
+  return aa_workspace_bytes_ex(dtype, layout, N, C, H, W, oH, oW, ax_h, ax_w, 0u);
 }
 
 int aa_resample_fwd(const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int dtype,
@@ -279,10 +422,6 @@ int aa_resample_fwd(const void *in_dev, void *out_dev, void *workspace_dev, size
                     aa_stream_t stream) {
   return aa_resample_fwd_ex(in_dev, out_dev, workspace_dev, workspace_bytes, dtype, layout, N, C, H, W, ax_h, ax_w, 0u, stream);
 }
-
-static int resample_fwd_impl(const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int dtype,
-                             int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w,
-                             unsigned flags, int64_t row_pitch, int64_t img_pitch, aa_stream_t stream);
 
 int aa_resample_fwd_ex(const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int dtype,
                        int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w,
@@ -319,109 +458,12 @@ int aa_resample_fwd_strided(const void *in_dev, void *out_dev, int dtype, int la
   return resample_fwd_impl(in_dev, out_dev, nullptr, 0, dtype, layout, N, C, H, W, ax_h, ax_w, flags, row_pitch, img_pitch ? img_pitch : H * row_pitch, stream);
 }
 
-static int resample_fwd_impl(const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int dtype,
-                             int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w,
-                             unsigned flags, int64_t row_pitch, int64_t img_pitch, aa_stream_t stream) {
-  if (flags & ~(unsigned)(AA_FLAG_FAST | AA_FLAG_PREMUL_ALPHA)) return AA_ERR_BAD_SHAPE;
-  if (dtype < AA_U8 || dtype > AA_BF16) return AA_ERR_BAD_DTYPE;
-  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
-  if (N < 0 || C <= 0 || H <= 0 || W <= 0) return AA_ERR_BAD_SHAPE;
-  int rc = check_axis(ax_h, H);
-  if (rc != AA_OK) return rc;
-  rc = check_axis(ax_w, W);
-  if (rc != AA_OK) return rc;
-  rc = check_dtype_kind(dtype, ax_h->kind, ax_w->kind);
-  if (rc != AA_OK) return rc;
-  const bool alpha = (flags & AA_FLAG_PREMUL_ALPHA) != 0;
-  if (alpha && !alpha_ok(dtype, C, ax_h, ax_w)) return AA_ERR_BAD_DTYPE;
-  if (N == 0) {  // empty batch is allowed (s2.2:747-750)
-    g_last_variant = "empty";
-    return AA_OK;
-  }
-  if (!in_dev || !out_dev) return AA_ERR_NULL;
-  {  // a tensor of 2 / 4 / 8-byte elements starts on an element boundary; anything else is not a tensor (and the kernels' dispatch must
-     // not depend on the pointers: aa_workspace_bytes answers from the shape alone)
-    const uintptr_t es = dtype == AA_U8 ? 1 : (dtype == AA_F64 ? 8 : (dtype == AA_F32 ? 4 : 2));
-    if ((((uintptr_t)in_dev | (uintptr_t)out_dev) & (es - 1)) != 0) return AA_ERR_BAD_SHAPE;
-  }
-
-  AAProblem p;
-  p.in = in_dev; p.out = out_dev; p.ws = workspace_dev; p.ws_bytes = workspace_bytes;
-  p.dtype = dtype; p.layout = layout;
-  p.N = N; p.C = C; p.H = H; p.W = W; p.oH = ax_h->out_size; p.oW = ax_w->out_size;
-  p.ah = *ax_h; p.aw = *ax_w;
-  p.stream = (hipStream_t)stream;
-  p.in_row_pitch = row_pitch; p.in_img_pitch = img_pitch;
-  // (Pillow's integer arithmetic and double arithmetic have no tolerance mode; uint8 images with AA_TABLE_F32 tables = the harness's float arithmetic do)
-  // (the first-generation kernels of mode 2 have no tolerance mode either)
-  p.fast = (flags & AA_FLAG_FAST) && dtype != AA_F64 && ax_w->kind == AA_TABLE_F32 && g_fused_enabled == 1 ? 1 : 0;
-  p.alpha = alpha ? 1 : 0;
-
-  const char *variant = "none";
-  rc = 0;
-  if (alpha) {
-    if (p.oH == H && p.oW == W) {  // Pillow's resize returns a copy: no lossy round trip through premultiplied values
-      if (row_pitch) return AA_ERR_STRIDES;
-      if (hipMemcpyAsync(out_dev, in_dev, (size_t)(N * C * H * W), hipMemcpyDeviceToDevice, p.stream) != hipSuccess) return AA_ERR_HIP;
-      g_last_variant = "alpha_copy";
-      return AA_OK;
-    }
-    rc = g_fused_enabled == 1 ? aa_try_fused_u8_nhwc_v3(p, &variant) : 0;
-    if (rc < 0) return rc;
-    if (rc == 1) {
-      g_last_variant = variant;
-      return AA_OK;
-    }
-    // three steps: premultiplied copy of the input into the workspace, the ordinary resample of it, un-premultiply in place
-    if (row_pitch) return AA_ERR_STRIDES;
-    const size_t copy_bytes = aa_align16((size_t)(N * C * H * W));
-    const size_t need = copy_bytes + aa_workspace_bytes(dtype, layout, N, C, H, W, p.oH, p.oW, ax_h, ax_w);
-    if (!workspace_dev || workspace_bytes < need) return AA_ERR_WORKSPACE;
-    rc = aa_launch_premul_u8(in_dev, workspace_dev, layout, N, C, H, W, p.stream);
-    if (rc != AA_OK) return rc;
-    rc = resample_fwd_impl(workspace_dev, out_dev, (char *)workspace_dev + copy_bytes, workspace_bytes - copy_bytes, dtype, layout, N, C, H, W,
-                           ax_h, ax_w, flags & ~(unsigned)AA_FLAG_PREMUL_ALPHA, 0, 0, stream);
-    if (rc != AA_OK) return rc;
-    rc = aa_launch_unpremul_u8(out_dev, layout, N, C, p.oH, p.oW, p.stream);
-    if (rc == AA_OK) g_last_variant = "alpha_3step";
-    return rc;
-  }
-  if (g_fused_enabled) {
-    if (g_fused_enabled == 1) rc = aa_try_fused_u8_nhwc_v3(p, &variant);
-    if (rc == 0 && !row_pitch) rc = aa_try_fused_u8_nhwc(p, &variant);  // (the first-generation kernel takes dense tensors only)
-    if (rc == 0) rc = aa_try_fused_float(p, &variant);
-  }
-  if (rc < 0) return rc;
-  if (rc == 1) {
-    g_last_variant = variant;
-    return AA_OK;
-  }
-  if (row_pitch) return AA_ERR_STRIDES;  // no kernel for this view: the caller makes a dense copy (what the two-launch path needs anyway)
-  const size_t need = aa_generic_workspace_bytes(dtype, ax_w->kind, N, C, H, p.oW);
-  if (!workspace_dev || workspace_bytes < need) return AA_ERR_WORKSPACE;
-  rc = aa_launch_generic_fwd(p, &variant);
-  if (rc == AA_OK) g_last_variant = variant;
-  return rc;
-}
-
-static int fill_convert(AAProblem &p, const aa_convert *cv, int64_t C) {
-  if (!cv) return AA_ERR_NULL;
-  if (cv->out_layout != AA_NCHW && cv->out_layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
-  if (cv->normalize && C > 4) return AA_ERR_BAD_SHAPE;
-  p.out_f32 = 1;
-  p.out_layout = cv->out_layout;
-  p.normalize = cv->normalize ? 1 : 0;
-  for (int i = 0; i < 4; i++) { p.mean[i] = cv->mean[i]; p.std[i] = cv->std[i]; }
-  if (cv->flags & ~(uint32_t)AA_FLAG_FAST) return AA_ERR_BAD_SHAPE;
-  p.fast = (cv->flags & AA_FLAG_FAST) ? 1 : 0;
-  return AA_OK;
-}
-
 size_t aa_workspace_bytes_u8_to_f32(int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w,
                                     const aa_convert *cv) {
   if (!ax_h || !ax_w || !cv || N <= 0) return 0;
-  if (g_fused_enabled == 1 && aa_fused_u8_v3_applicable(AA_U8, layout, N, C, H, W, ax_h, ax_w, 1, cv->out_layout)) return 0;
-  return aa_generic_workspace_bytes(AA_U8, AA_TABLE_F32, N, C, H, ax_w->out_size);
+  AAProblem q = problem(AA_U8, layout, N, C, H, W, ax_h->out_size, ax_w->out_size, *ax_h, *ax_w, 0u);
+  (void)fill_convert(q, *cv);
+  return plan_fwd(q).bytes();
 }
 
 int aa_resample_fwd_u8_to_f32(const void *in_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int layout,
@@ -434,31 +476,11 @@ int aa_resample_fwd_u8_to_f32(const void *in_dev, void *out_dev, void *workspace
   rc = check_axis(ax_w, W);
   if (rc != AA_OK) return rc;
   if (ax_h->kind != AA_TABLE_F32 || ax_w->kind != AA_TABLE_F32) return AA_ERR_BAD_DTYPE;  // float output = float arithmetic
-  AAProblem p;
-  rc = fill_convert(p, cv, C);
+  if (!cv) return AA_ERR_NULL;
+  AAProblem q = problem(AA_U8, layout, N, C, H, W, ax_h->out_size, ax_w->out_size, *ax_h, *ax_w, 0u);
+  rc = fill_convert(q, *cv);
   if (rc != AA_OK) return rc;
-  if (N == 0) {
-    g_last_variant = "empty";
-    return AA_OK;
-  }
-  if (!in_dev || !out_dev) return AA_ERR_NULL;
-  p.in = in_dev; p.out = out_dev; p.ws = workspace_dev; p.ws_bytes = workspace_bytes;
-  p.dtype = AA_U8; p.layout = layout;
-  p.N = N; p.C = C; p.H = H; p.W = W; p.oH = ax_h->out_size; p.oW = ax_w->out_size;
-  p.ah = *ax_h; p.aw = *ax_w;
-  p.stream = (hipStream_t)stream;
-  const char *variant = "none";
-  rc = g_fused_enabled == 1 ? aa_try_fused_u8_nhwc_v3(p, &variant) : 0;
-  if (rc < 0) return rc;
-  if (rc == 1) {
-    g_last_variant = variant;
-    return AA_OK;
-  }
-  const size_t need = aa_generic_workspace_bytes(AA_U8, AA_TABLE_F32, N, C, H, p.oW);
-  if (!workspace_dev || workspace_bytes < need) return AA_ERR_WORKSPACE;
-  rc = aa_launch_generic_convert(p, &variant);
-  if (rc == AA_OK) g_last_variant = variant;
-  return rc;
+  return resample(q, in_dev, out_dev, workspace_dev, workspace_bytes, stream);
 }
 
 size_t aa_workspace_bytes_bwd(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW) {
@@ -501,13 +523,10 @@ int aa_resample_bwd_atomic(const void *grad_out_dev, void *grad_in_dev, void *wo
   if (!grad_out_dev || !grad_in_dev) return AA_ERR_NULL;
   const size_t need = aa_workspace_bytes_bwd(dtype, layout, N, C, H, W, ax_h->out_size, ax_w->out_size);
   if (!workspace_dev || workspace_bytes < need) return AA_ERR_WORKSPACE;
-  AAProblem p;
-  p.in = grad_out_dev; p.out = grad_in_dev; p.ws = workspace_dev; p.ws_bytes = workspace_bytes;
-  p.dtype = dtype; p.layout = layout;
-  p.N = N; p.C = C; p.H = H; p.W = W; p.oH = ax_h->out_size; p.oW = ax_w->out_size;
-  p.ah = *ax_h; p.aw = *ax_w;
-  p.stream = (hipStream_t)stream;
-  rc = aa_launch_bwd_atomic(p);
+  AAProblem q = problem(dtype, layout, N, C, H, W, ax_h->out_size, ax_w->out_size, *ax_h, *ax_w, 0u);
+  q.in = grad_out_dev; q.out = grad_in_dev; q.ws = workspace_dev; q.ws_bytes = workspace_bytes;
+  q.stream = (hipStream_t)stream;
+  rc = aa_launch_bwd_atomic(q);
   if (rc == AA_OK) g_last_variant = "bwd_scatter_atomics";
   return rc;
 }

@@ -138,21 +138,11 @@ int aa_launch_axis_fwd(const void *in, void *out, int dtype, int64_t outer, int6
                        hipStream_t stream);
 size_t aa_generic_workspace_bytes(int dtype, int kind_w, int64_t N, int64_t C, int64_t H, int64_t oW);
 int aa_launch_generic_convert(const AAProblem &p, const char **variant);  // u8 -> f32 (+ layout, normalisation), two launches
-// fused single-launch paths; return 1 when they took the problem, 0 when not applicable, <0 on error
-int aa_try_fused_u8_nhwc(const AAProblem &p, const char **variant);
-// float planes and fp32 channels_last: shrinking heights (scatter form), then growing ones (gather form: the adjoint, up-scaling)
-int aa_try_fused_float(const AAProblem &p, const char **variant);
-int aa_try_fused_u8_nhwc_v3(const AAProblem &p, const char **variant);  // LDS-DMA staged, wave-autonomous, V pass in registers
-// The *_applicable predicates hold EVERY reason a fused path can decline that does not depend on the pointers (shape, LDS
-// size, grid size, dispatch widths): aa_workspace_bytes() answers 0 exactly when aa_resample_fwd() will not need one.
-bool aa_fused_u8_v3_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw,
-                               int out_f32 = 0, int out_layout = AA_NCHW, int alpha = 0);
+// (the fused single-launch families: aa_plan.h)
 // the three-step straight-alpha fallback (aa_alpha.hip): premultiply a dense uint8 image of C = 2 / 4 channels (alpha last, either layout)
 // into `dst`, and un-premultiply one in place
 int aa_launch_premul_u8(const void *src, void *dst, int layout, int64_t N, int64_t C, int64_t H, int64_t W, hipStream_t stream);
 int aa_launch_unpremul_u8(void *img, int layout, int64_t N, int64_t C, int64_t H, int64_t W, hipStream_t stream);
-bool aa_fused_u8_nhwc_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
-bool aa_fused_float_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw);
 // Input pixels the windows (tw taps each) of one strip of <= 64 consecutive outputs cover, from the spread the table
 // kernel MEASURED (header.span64p1; explicit scale factors and align_corners make it differ from 63 * in / out).
 // -1 = unknown (a caller that did not fill aa_axis.span64p1): the fused kernels decline.

@@ -1,8 +1,8 @@
 // aa_fused_float.hip — host-side plan of the fused float kernels: fp32 / fp16 / bf16 / fp64 planes and fp32 channels_last with
 // shrinking heights (aa_fused_float_impl.h), fp32 / fp16 / bf16 planes with growing heights, the gather form of the adjoint among them
-// (aa_fused_float_up_impl.h).  f32_plan() makes every decision that does not depend on the pointers: the route, the strip geometry and
-// all template arguments of the kernel that will run.  aa_try_fused_float() adds the few that do and launches through the unit that
-// compiled the kernel.  The compiled set is aa_fused_float_list.h.
+// (aa_fused_float_up_impl.h).  aa_f32_plan() makes every decision that does not depend on the pointers: the route, the strip geometry and
+// all template arguments of the kernel that will run.  aa_f32_launch() adds the few that do and launches through the unit that compiled
+// the kernel.  The compiled set is aa_fused_float_list.h.
 
 #include "aa_fused_float_impl.h"
 
@@ -135,21 +135,17 @@ bool f32_plan(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W,
 
 }  // namespace
 
-bool aa_fused_float_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw) {
-  F32Plan k;
-  return ah && aw && f32_plan(dtype, layout, N, C, H, W, *ah, *aw, false, &k);
+bool aa_f32_plan(const AAProblem &q, bool fast, F32Plan *k) {
+  if (!f32_plan(q.dtype, q.layout, q.N, q.C, q.H, q.W, q.ah, q.aw, fast, k)) return false;
+  // a pitched view: 32-bit offsets inside a plane (image), whole elements apart; growing heights: dense only
+  const int es = q.dtype == AA_F64 ? 8 : (q.dtype == AA_F32 ? 4 : 2);
+  return !q.in_row_pitch || !(k->kernel == F32_UP || (uint64_t)q.H * (uint64_t)q.in_row_pitch > 0x7FFFFFF0ull || (q.in_row_pitch & (es - 1)) ||
+                              (q.in_img_pitch & (es - 1)));
 }
 
-int aa_try_fused_float(const AAProblem &q, const char **variant) {
-  F32Plan k;
-  if (!f32_plan(q.dtype, q.layout, q.N, q.C, q.H, q.W, q.ah, q.aw, q.fast != 0, &k)) return 0;
+int aa_f32_launch(const F32Plan &pl, const AAProblem &q) {
+  F32Plan k = pl;
   const int es = q.dtype == AA_F64 ? 8 : (q.dtype == AA_F32 ? 4 : 2);
-
-  // ---- the choices that depend on the pointers and the view
-  // a pitched view: 32-bit offsets inside a plane (image), whole elements apart; growing heights: dense only
-  if (q.in_row_pitch && (k.kernel == F32_UP || (uint64_t)q.H * (uint64_t)q.in_row_pitch > 0x7FFFFFF0ull || (q.in_row_pitch & (es - 1)) ||
-                         (q.in_img_pitch & (es - 1))))
-    return 0;
   if (k.kernel == F32_UP) {
     // the store form (see the kernel's store): streaming for outputs far larger than the caches, or as aa_set_store_form says (tests of
     // the streaming forms at small sizes)
@@ -169,9 +165,5 @@ int aa_try_fused_float(const AAProblem &q, const char **variant) {
       k.lds_extra = 1088;
     }
   }
-  // ----
-
-  const int rc = k.launch(k, &q);
-  if (rc == 1) *variant = k.variant;
-  return rc;
+  return aa_launch_status(k.launch(k, &q));
 }

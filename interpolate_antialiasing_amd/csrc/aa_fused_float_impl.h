@@ -37,7 +37,7 @@
 
 #include <type_traits>
 
-#include "aa_common.h"
+#include "aa_plan.h"
 
 #ifndef AA_F32_FAST
 #define AA_F32_FAST 0
@@ -526,17 +526,4 @@ enum F32KernelKind { F32_DOWN, F32_UP };
 enum F32UnitId {
 #define F32_UNIT(name, ...) F32_UNIT_##name,
 #include "aa_fused_float_list.h"
-};
-
-// One kernel of the compiled set, as the plan chose it, with its strip geometry and the unit that compiled it
-struct F32Plan;
-typedef int (*F32Launch)(const F32Plan &k, const AAProblem *q);  // (q == nullptr: does the unit hold k?  Launches nothing)
-struct F32Plan {
-  // F32_DOWN: fused_f32_nchw_kernel<NQ = width, G, NDMA, MAXC = vert, DT, CS = cs>;
-  // F32_UP: fused_f32_nchw_up_kernel<U = width, G, KR = vert, CPL = cs, DT> (NDMA 1)
-  int kernel, DT, cs, width, vert, G, NDMA;
-  int nstrips, strip_w, nseg;
-  int store_nt, lds_extra;  // F32_UP: the store form and the LDS it adds per strip (aa_try_fused_float: they depend on the pointers)
-  const char *variant;
-  F32Launch launch;
 };

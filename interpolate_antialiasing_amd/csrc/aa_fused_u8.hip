@@ -17,13 +17,13 @@
 //   * vertical pass: as soon as the ring holds rows [ymin, ymin+ysize) of the next output row, lanes take one
 //     dword (4 interleaved channel values) each, tap weights are wave-uniform scalars, and the finished row is
 //     stored with fully coalesced dword stores.  One barrier per output row; the ring depth makes the
-//     write-after-read hazard impossible (see ring_rows in the launcher).
+//     write-after-read hazard impossible (see ring_rows in aa_v1_plan).
 // No MFMA: this is a gather-weighted-sum with ~2.3 MAC per input byte, HBM-bound by design.
 
 #include <math.h>
 #include <stdlib.h>
 
-#include "aa_common.h"
+#include "aa_plan.h"
 
 namespace {
 
@@ -40,7 +40,7 @@ struct FusedU8Params {
   int ksize_w, ksize_h;
   int ybands, xbands;
   int bw;         // output columns per x band (multiple of 4)
-  int ring_rows;        // LDS ring depth in rows (any value >= the hazard bound computed by the launcher)
+  int ring_rows;        // LDS ring depth in rows (any value >= the hazard bound computed by aa_v1_plan)
   unsigned ring_magic;  // floor(2^32 / ring_rows) + 1: slot(r) = r - ring_rows * mulhi(r, magic), exact for r < 2^20
   int pitch;      // LDS bytes per ring row (multiple of 16)
   unsigned long long img_in_bytes, img_out_bytes, total_in_bytes;
@@ -237,7 +237,7 @@ fused_u8_nhwc_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, 
       }
     }
     // no second barrier: the next chunk's horizontal pass writes rows >= r_end, whose ring slots cannot alias the
-    // rows still being read here because ring_rows >= taps_h + 2*K*ceil(scale_h) + 2 (launcher).
+    // rows still being read here because ring_rows >= taps_h + 2*K*ceil(scale_h) + 2 (aa_v1_plan).
   }
 }
 
@@ -253,7 +253,7 @@ int launch(const FusedU8Params &p, int block, size_t lds, int64_t grid, hipStrea
   hipLaunchKernelGGL((fused_u8_nhwc_kernel<C, TW, kRowsPerBarrier, rows_in_flight(TW), false>), dim3((unsigned)grid),
                      dim3(block), lds, stream, p.in, p.out, p.tab_w, p.tab_h, p);
   AA_HIP_CHECK_LAUNCH();
-  return 1;
+  return AA_OK;
 }
 
 template <int C>
@@ -263,8 +263,7 @@ int dispatch_tw(int tw, const FusedU8Params &p, int block, size_t lds, int64_t g
   if (tw <= 6) return launch<C, 6>(p, block, lds, grid, stream);
   if (tw <= 8) return launch<C, 8>(p, block, lds, grid, stream);
   if (tw <= 12) return launch<C, 12>(p, block, lds, grid, stream);
-  if (tw <= 16) return launch<C, 16>(p, block, lds, grid, stream);
-  return 0;
+  return launch<C, 16>(p, block, lds, grid, stream);  // (the plan's round_tw: <= 16)
 }
 
 int round_tw(int taps) {
@@ -274,57 +273,39 @@ int round_tw(int taps) {
   return 0;
 }
 
-int next_pow2(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 }  // namespace
 
-static void v1_geometry(int64_t C, int64_t H, int64_t oW, const aa_axis &ah, int *xbands_o, int *bw_o, int *ring_rows_o, int *pitch_o) {
+bool aa_v1_plan(const AAProblem &q, V1Plan *pl) {
+  const aa_axis &ah = q.ah, &aw = q.aw;
+  if (q.dtype != AA_U8 || q.layout != AA_NHWC || ah.kind != AA_TABLE_PIL || aw.kind != AA_TABLE_PIL) return false;
+  if (q.C != 1 && q.C != 3 && q.C != 4) return false;
+  const int taps_w = aw.max_taps > 0 ? aw.max_taps : aw.ksize;
+  const int tw = round_tw(taps_w);
+  if (tw == 0 || q.W < tw) return false;
+  if ((aw.out_size * q.C) % 4 != 0) return false;            // rows stored as whole dwords
+  if ((uint64_t)q.H * q.W * q.C > 0xFFFFFFF0ull) return false;  // 32-bit offsets inside one image
+  const int taps_h = ah.max_taps > 0 ? ah.max_taps : ah.ksize;
+  if (taps_h > 64) return false;
+  if (q.H >= (1 << 20)) return false;
   // column bands: at most 1024 lanes, a multiple of 4 columns so every band starts dword-aligned
+  const int64_t oW = aw.out_size;
   int xbands = (int)((oW + 1023) / 1024);
   int bw = (int)((oW + xbands - 1) / xbands);
   bw = (bw + 3) & ~3;
   xbands = (int)((oW + bw - 1) / bw);
   // ring depth: while slow waves still read chunk i's rows [ymin(first oy of chunk i), r_end(i)), fast waves may
   // already write chunk i+1's rows [r_end(i), r_end(i+1)): span <= taps_h + 2*K*max(scale_h,1) (+ rounding slack)
-  const int taps_h = ah.max_taps > 0 ? ah.max_taps : ah.ksize;
-  const double scale_h = (double)H / (double)ah.out_size;
-  *ring_rows_o = taps_h + (int)(2.0 * kRowsPerBarrier * (scale_h > 1.0 ? scale_h : 1.0) + 0.999) + 4;
-  *pitch_o = ((bw * (int)C + 15) / 16) * 16;
-  *xbands_o = xbands;
-  *bw_o = bw;
-}
-
-bool aa_fused_u8_nhwc_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah,
-                                 const aa_axis *aw) {
-  if (dtype != AA_U8 || layout != AA_NHWC) return false;
-  if (!ah || !aw || ah->kind != AA_TABLE_PIL || aw->kind != AA_TABLE_PIL) return false;
-  if (C != 1 && C != 3 && C != 4) return false;
-  const int taps_w = aw->max_taps > 0 ? aw->max_taps : aw->ksize;
-  const int tw = round_tw(taps_w);
-  if (tw == 0 || W < tw) return false;
-  if ((aw->out_size * C) % 4 != 0) return false;        // rows stored as whole dwords
-  if ((uint64_t)H * W * C > 0xFFFFFFF0ull) return false;  // 32-bit offsets inside one image
-  const int taps_h = ah->max_taps > 0 ? ah->max_taps : ah->ksize;
-  if (taps_h > 64) return false;
-  if (H >= (1 << 20)) return false;
-  int xbands, bw, ring_rows, pitch;
-  v1_geometry(C, H, aw->out_size, *ah, &xbands, &bw, &ring_rows, &pitch);
+  const double scale_h = (double)q.H / (double)ah.out_size;
+  const int ring_rows = taps_h + (int)(2.0 * kRowsPerBarrier * (scale_h > 1.0 ? scale_h : 1.0) + 0.999) + 4;
+  const int pitch = ((bw * (int)q.C + 15) / 16) * 16;
   if ((size_t)ring_rows * pitch > 64 * 1024) return false;  // the intermediate ring must fit the workgroup's LDS
-  if (!aa_grid_fits(N * xbands)) return false;
+  if (!aa_grid_fits(q.N * xbands)) return false;            // (with at most 64 row bands: the launch's grid fits)
+  *pl = V1Plan{tw, (int)q.C, xbands, bw, ring_rows, pitch, ((bw + 63) / 64) * 64, (size_t)ring_rows * pitch};
   return true;
 }
 
-int aa_try_fused_u8_nhwc(const AAProblem &q, const char **variant) {
-  if (!aa_fused_u8_nhwc_applicable(q.dtype, q.layout, q.N, q.C, q.H, q.W, &q.ah, &q.aw)) return 0;
-  const int C = (int)q.C;
-  const int taps_w = q.aw.max_taps > 0 ? q.aw.max_taps : q.aw.ksize;
+int aa_v1_launch(const V1Plan &pl, const AAProblem &q) {
   const int taps_h = q.ah.max_taps > 0 ? q.ah.max_taps : q.ah.ksize;
-  const int tw = round_tw(taps_w);
-
   FusedU8Params p;
   p.in = (const uint8_t *)q.in;
   p.out = (uint8_t *)q.out;
@@ -332,26 +313,21 @@ int aa_try_fused_u8_nhwc(const AAProblem &q, const char **variant) {
   p.tab_h = (const char *)q.ah.table_dev;
   p.H = (int)q.H; p.W = (int)q.W; p.oH = (int)q.oH; p.oW = (int)q.oW;
   p.ksize_w = q.aw.ksize; p.ksize_h = q.ah.ksize;
-  p.img_in_bytes = (unsigned long long)q.H * q.W * C;
-  p.img_out_bytes = (unsigned long long)q.oH * q.oW * C;
+  p.img_in_bytes = (unsigned long long)q.H * q.W * pl.C;
+  p.img_out_bytes = (unsigned long long)q.oH * q.oW * pl.C;
   p.total_in_bytes = p.img_in_bytes * (unsigned long long)q.N;
-  p.byte_store = ((uintptr_t)q.out & 3) != 0 ? 1 : 0;  // (no pointer-dependent decline: aa_workspace_bytes answered 0 from the shape alone)
-
-  int xbands, bw, ring_rows, pitch;
-  v1_geometry(q.C, q.H, q.oW, q.ah, &xbands, &bw, &ring_rows, &pitch);
-  const int block = ((bw + 63) / 64) * 64;
-  p.ring_rows = ring_rows;
-  p.ring_magic = (unsigned)(0x100000000ull / (unsigned)ring_rows) + 1u;
-  p.pitch = pitch;
-  const size_t lds = (size_t)ring_rows * p.pitch;
+  p.byte_store = ((uintptr_t)q.out & 3) != 0 ? 1 : 0;
+  p.ring_rows = pl.ring_rows;
+  p.ring_magic = (unsigned)(0x100000000ull / (unsigned)pl.ring_rows) + 1u;
+  p.pitch = pl.pitch;
 
   // row bands.  Every extra band re-reads and re-filters ~taps_h halo rows, but the grid must fill the chip's
   // resident-workgroup slots a near-integer number of times or the last partial round idles most CUs
   // (2048 workgroups on 1280 slots ran 2 rounds for 1.6 rounds of work).  Pick the band count minimising
   // (1 + halo fraction) / round efficiency.
   const int cus = aa_device_cu_count();
-  const int waves_per_block = block / 64;
-  int blocks_per_cu = (int)((160 * 1024) / (lds > 0 ? lds : 1));
+  const int waves_per_block = pl.block / 64;
+  int blocks_per_cu = (int)((160 * 1024) / (pl.lds > 0 ? pl.lds : 1));
   if (blocks_per_cu > 32 / waves_per_block) blocks_per_cu = 32 / waves_per_block;
   if (blocks_per_cu > 8) blocks_per_cu = 8;
   if (blocks_per_cu < 1) blocks_per_cu = 1;
@@ -360,7 +336,7 @@ int aa_try_fused_u8_nhwc(const AAProblem &q, const char **variant) {
   int64_t ybands = 1;
   double best = 1e30;
   for (int64_t yb = 1; yb <= max_yb && yb <= 64; yb++) {
-    const double items = (double)q.N * xbands * yb;
+    const double items = (double)q.N * pl.xbands * yb;
     const double rounds = items / slots;
     const double eff = rounds / ceil(rounds);
     const double halo = 1.0 + (double)(yb - 1) * taps_h / (double)q.H;
@@ -372,18 +348,13 @@ int aa_try_fused_u8_nhwc(const AAProblem &q, const char **variant) {
   }
   if (const char *e = aa_knob("AA_FUSED_YBANDS")) {  // tuning knob for experiments; not used by tests or bench
     const int64_t v = atoll(e);
-    if (v >= 1 && v <= max_yb) ybands = v;
+    if (v >= 1 && v <= max_yb) ybands = v < 64 ? v : 64;  // (the plan bounds the grid for 64 bands)
   }
   p.ybands = (int)ybands;
-  p.xbands = xbands;
-  p.bw = bw;
-  const int64_t grid = q.N * ybands * xbands;
-  if (grid > 0x7FFFFFFF) return 0;
-
-  int rc;
-  if (C == 3) rc = dispatch_tw<3>(tw, p, block, lds, grid, q.stream);
-  else if (C == 4) rc = dispatch_tw<4>(tw, p, block, lds, grid, q.stream);
-  else rc = dispatch_tw<1>(tw, p, block, lds, grid, q.stream);
-  if (rc == 1) *variant = "fused_u8_nhwc_pil";
-  return rc;
+  p.xbands = pl.xbands;
+  p.bw = pl.bw;
+  const int64_t grid = q.N * ybands * pl.xbands;
+  if (pl.C == 3) return dispatch_tw<3>(pl.TW, p, pl.block, pl.lds, grid, q.stream);
+  if (pl.C == 4) return dispatch_tw<4>(pl.TW, p, pl.block, pl.lds, grid, q.stream);
+  return dispatch_tw<1>(pl.TW, p, pl.block, pl.lds, grid, q.stream);
 }

@@ -1,6 +1,6 @@
-// aa_fused_u8_v3.hip — host-side dispatcher of the fused uint8 kernel.  v3_plan() makes every decision that does not depend on the
-// pointers: the route and all template arguments of the kernel that will run.  aa_try_fused_u8_nhwc_v3() adds the few that do and
-// launches through the unit that compiled the kernel.  The kernel and its design notes are in aa_fused_u8_v3_impl.h, the compiled set
+// aa_fused_u8_v3.hip — host-side dispatcher of the fused uint8 kernel.  aa_v3_plan() makes every decision that does not depend on the
+// pointers: the route and all template arguments of the kernel that will run.  aa_v3_launch() adds the few that do and launches through
+// the unit that compiled the kernel.  The kernel and its design notes are in aa_fused_u8_v3_impl.h, the compiled set
 // in aa_fused_u8_v3_list.h.
 
 #include "aa_fused_u8_v3_impl.h"
@@ -24,23 +24,15 @@ static V3Launch v3_unit(const V3Kernel &k) {
   return nullptr;
 }
 
-struct V3Plan {
-  V3Kernel k;       // the kernel (PERIODIC: see aa_try_fused_u8_nhwc_v3)
-  V3Kernel groups;  // plane groups: the same problem, three planes per wave (groups.launch == nullptr: not for this shape)
-  bool planar, up;
-  int C;     // bytes per pixel of the data (1: planar)
-  int cap;   // output columns per strip
-  int nseg;  // 16-byte pieces per staged row segment
-  const char *variant;
-};
-
 // filters whose shrinking heights may take the narrow-window MAXC-6 instantiations (5-6 open output rows with <= 16 taps)
 static bool v3_six_narrow_filter(int filter) { return filter == AA_FILTER_LANCZOS || filter == AA_FILTER_HAMMING; }
 
 // Everything the kernel needs that can be known without the pointers (aa_workspace_bytes asks before they exist).  false: no kernel.
-static bool v3_plan(int dtype, int layout, int64_t N, int64_t Cin, int64_t H, int64_t W, const aa_axis &ah, const aa_axis &aw, int out_f32,
-                    int out_layout, int alpha, int fast, V3Plan *pl) {
-  if (dtype != AA_U8) return false;
+bool aa_v3_plan(const AAProblem &q, bool fast, V3Plan *pl) {
+  const int64_t N = q.N, Cin = q.C, H = q.H, W = q.W;
+  const aa_axis &ah = q.ah, &aw = q.aw;
+  const int layout = q.layout, out_f32 = q.out_f32, out_layout = q.out_layout, alpha = q.alpha;
+  if (q.dtype != AA_U8) return false;
   // straight alpha: the ALPHA instantiations cover Pillow arithmetic, 4 interleaved channels, uint8 out, narrow windows of shrinking heights
   if (alpha && (out_f32 || layout != AA_NHWC || Cin != 4 || ah.kind != AA_TABLE_PIL || aw.kind != AA_TABLE_PIL || H < ah.out_size)) return false;
   if (out_f32 && (ah.kind != AA_TABLE_F32 || aw.kind != AA_TABLE_F32)) return false;  // float output = float arithmetic
@@ -86,6 +78,7 @@ static bool v3_plan(int dtype, int layout, int64_t N, int64_t Cin, int64_t H, in
   if (span_px < 0) return false;
   int nseg = (span_px * C + 3 + 15 + 15) / 16;
   int cap = split ? 16 : 64;  // output columns per strip
+  bool v1_first = false;
   if (up && nseg > 64) {
     // the gather form is instantiated with one staging DMA per row (64 pieces): strong down-scaling in W (test.py's 906 -> 120
     // with growing heights) gets strips of 32 columns — half the lanes idle, but such a shape is bound by its input stream
@@ -94,15 +87,21 @@ static bool v3_plan(int dtype, int layout, int64_t N, int64_t Cin, int64_t H, in
     nseg = (span_px * C + 3 + 15 + 15) / 16;
     cap = 32;
     if (nseg > 64) return false;
-    // ... unless the first-generation kernel (Pillow arithmetic, channels_last, uint8 out) takes the shape: its block-wide tiles
-    // handle these wide windows better (measured, [128,3,438,906] -> 1200 x 120: 0.060 ms against 0.095 ms here)
-    if (!flt && !planar && !out_f32 && aa_fused_u8_nhwc_applicable(dtype, layout, N, Cin, H, W, &ah, &aw)) return false;
+    // ... but the first-generation kernel (Pillow arithmetic, channels_last, uint8 out) runs when it takes the shape: its block-wide
+    // tiles handle these wide windows better (measured, [128,3,438,906] -> 1200 x 120: 0.060 ms against 0.095 ms here)
+    v1_first = !flt && !planar && !out_f32;
   }
   if (nseg > 128 || (size_t)8 * nseg * 16 > 64 * 1024) return false;  // (8 staged rows per wave: the kernel's G)
   if (six && nseg > 64) return false;  // (the narrow MAXC-6 route has the one-DMA-per-row form only)
   if (alpha && (split || tw > 16 || nseg > 64)) return false;  // (the ALPHA routes: one DMA per row)
   const int64_t nstrips = (oW + cap - 1) / cap + 1;  // (balanced strips can be one more)
   if (!aa_grid_fits((planar ? N * Cin : N) * nstrips)) return false;
+  // a pitched view (cropped / batch-sliced tensor): rows q.in_row_pitch bytes apart, images (planes) q.in_img_pitch bytes apart; 32-bit
+  // offsets inside an image, and growing heights take dense tensors only
+  if (q.in_row_pitch && ((uint64_t)H * (uint64_t)q.in_row_pitch > 0x7FFFFFF0ull || up)) return false;
+  pl->row_pitch = q.in_row_pitch ? (unsigned)q.in_row_pitch : (unsigned)(W * C);
+  pl->img_in_bytes = q.in_img_pitch ? (unsigned long long)q.in_img_pitch : (unsigned long long)H * W * C;
+  pl->img_out_bytes = (unsigned long long)oH * oW * C * (out_f32 ? 4 : 1);
 
   // the kernel
   const int sm = ah.scatter_max;
@@ -136,13 +135,19 @@ static bool v3_plan(int dtype, int layout, int64_t N, int64_t Cin, int64_t H, in
   pl->groups = k;
   pl->groups.route = V3_PLANES;
   pl->groups.C = pl->groups.PL = 3;
-  pl->groups.launch = planar && N * Cin >= 2 && k.route == V3_NARROW && nseg <= 16 ? v3_unit(pl->groups) : nullptr;
+  // ... when three planes' offsets stay within 32 bits, and aa_set_plane_groups has not turned them off
+  const bool groups = planar && N * Cin >= 2 && k.route == V3_NARROW && nseg <= 16 && 3 * pl->img_in_bytes <= 0x7FFFFFF0ull &&
+                      3 * pl->img_out_bytes <= 0x7FFFFFF0ull && g_aa_plane_groups != 0;
+  pl->groups.launch = groups ? v3_unit(pl->groups) : nullptr;
+  // PERIODIC (single planes): the 8 ring slots' row phases repeat when 8 rows span whole 16-byte pieces, in the routes that list that form
+  k.PERIODIC = (8ull * pl->row_pitch) % 16 == 0;
+  if (!k.launch(k, nullptr, nullptr, 0)) k.PERIODIC = false;
 
   pl->planar = planar;
-  pl->up = up;
   pl->C = C;
   pl->cap = cap;
   pl->nseg = nseg;
+  pl->v1_first = v1_first;
 #define V3_FAST(s) (k.fast ? s "_fast" : s)
   pl->variant = alpha    ? (six ? "fused_u8_nhwc_pil_alpha6_v3" : "fused_u8_nhwc_pil_alpha_v3")
                 : !flt   ? (planar ? "fused_u8_planar_pil_v3" : "fused_u8_nhwc_pil_v3")
@@ -153,43 +158,28 @@ static bool v3_plan(int dtype, int layout, int64_t N, int64_t Cin, int64_t H, in
   return true;
 }
 
-bool aa_fused_u8_v3_applicable(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ah, const aa_axis *aw,
-                               int out_f32, int out_layout, int alpha) {
-  V3Plan pl;
-  return ah && aw && v3_plan(dtype, layout, N, C, H, W, *ah, *aw, out_f32, out_layout, alpha, 0, &pl);
-}
-
-int aa_try_fused_u8_nhwc_v3(const AAProblem &q, const char **variant) {
-  V3Plan pl;
-  if (!v3_plan(q.dtype, q.layout, q.N, q.C, q.H, q.W, q.ah, q.aw, q.out_f32, q.out_layout, q.alpha, q.fast, &pl)) return 0;
+int aa_v3_launch(const V3Plan &pl, const AAProblem &q) {
   const int C = pl.C;
   const int64_t NI = pl.planar ? q.N * q.C : q.N;  // images the kernel sees
 
   FusedU8V3Params p;
   p.H = (int)q.H; p.W = (int)q.W; p.oH = (int)q.oH; p.oW = (int)q.oW;
   p.ksize_w = q.aw.ksize; p.ksize_h = q.ah.ksize;
-  // a pitched view (cropped / batch-sliced tensor): rows q.in_row_pitch bytes apart, images (planes) q.in_img_pitch bytes apart
-  p.row_pitch = q.in_row_pitch ? (unsigned)q.in_row_pitch : (unsigned)(q.W * C);
-  p.img_in_bytes = q.in_img_pitch ? (unsigned long long)q.in_img_pitch : (unsigned long long)q.H * q.W * C;
-  p.img_out_bytes = (unsigned long long)q.oH * q.oW * C * (q.out_f32 ? 4 : 1);
+  p.row_pitch = pl.row_pitch;
+  p.img_in_bytes = pl.img_in_bytes;
+  p.img_out_bytes = pl.img_out_bytes;
   p.outm = q.out_f32 ? (pl.planar || q.out_layout == AA_NCHW ? 1 : 2) : 0;
   p.normalize = q.out_f32 ? q.normalize : 0;
   p.cin = (int)q.C;
   p.fast = pl.k.fast ? 1 : 0;
   for (int c = 0; c < 4; c++) { p.mean[c] = q.mean[c]; p.std[c] = q.std[c]; }
 
-  // ---- the choices that depend on the pointers and the view
-  if (q.in_row_pitch && ((uint64_t)q.H * (uint64_t)q.in_row_pitch > 0x7FFFFFF0ull || pl.up)) return 0;  // (32-bit offsets inside an image; growing heights: dense only)
+  // ---- the choices that depend on the pointers
   // byte stores: output rows that are not whole dwords, an output that is not dword aligned, or split windows (a quad's first lane stores
   // its pixel's bytes)
   p.byte_store = (pl.k.route == V3_SPLIT || (!q.out_f32 && ((q.oW * C) % 4 != 0 || (C == 3 && q.oW % 4 != 0) || ((uintptr_t)q.out & 3) != 0))) ? 1 : 0;
   if (q.out_f32 && ((uintptr_t)q.out & 3) != 0) return AA_ERR_BAD_SHAPE;  // a float tensor that is not float aligned
   p.in_mis = (int)((uintptr_t)q.in & 15);
-  // PERIODIC: the 8 ring slots' row phases repeat when 8 rows span whole 16-byte pieces, in the routes that list that form
-  pl.k.PERIODIC = (8ull * p.row_pitch) % 16 == 0;
-  if (!pl.k.launch(pl.k, nullptr, nullptr, 0)) pl.k.PERIODIC = false;
-  // plane groups: three planes' offsets stay within 32 bits, and aa_set_plane_groups has not turned them off
-  const bool groups = pl.groups.launch && 3 * p.img_in_bytes <= 0x7FFFFFF0ull && 3 * p.img_out_bytes <= 0x7FFFFFF0ull && g_aa_plane_groups != 0;
   // ----
 
   p.total_in_bytes = q.in_row_pitch ? p.img_in_bytes * (unsigned long long)(NI - 1) + (unsigned long long)(q.H - 1) * p.row_pitch + (unsigned long long)q.W * C + p.in_mis
@@ -214,7 +204,7 @@ int aa_try_fused_u8_nhwc_v3(const AAProblem &q, const char **variant) {
   p.plane_in_bytes = p.plane_out_bytes = 0;
   p.pl_planes = 0;
 
-  if (groups) {  // if the plane-group launch declines, the single-plane form runs
+  if (pl.groups.launch) {  // if the plane-group launch declines, the single-plane form runs
     FusedU8V3Params pg = p;
     pg.plane_in_bytes = p.img_in_bytes;  // (the single-plane form's "images" are the planes)
     pg.plane_out_bytes = p.img_out_bytes;
@@ -223,12 +213,7 @@ int aa_try_fused_u8_nhwc_v3(const AAProblem &q, const char **variant) {
     pg.n_images = (NI + 2) / 3;  // groups of three consecutive planes (the last one may hold one or two)
     pg.pl_planes = NI;
     const int rc = pl.groups.launch(pl.groups, &pg, &q, (size_t)8 * 1024);  // (a 1-KiB stage slot per row: the kernel's fixed layout)
-    if (rc != 0) {
-      if (rc == 1) *variant = pl.variant;
-      return rc;
-    }
+    if (rc != 0) return aa_launch_status(rc);
   }
-  const int rc = pl.k.launch(pl.k, &p, &q, (size_t)8 * p.seg_bytes);
-  if (rc == 1) *variant = pl.variant;
-  return rc;
+  return aa_launch_status(pl.k.launch(pl.k, &p, &q, (size_t)8 * p.seg_bytes));
 }

@@ -33,7 +33,7 @@
 #include <type_traits>
 
 #include "aa_alpha.h"
-#include "aa_common.h"
+#include "aa_plan.h"
 
 #ifndef AA_V3_ABL
 #define AA_V3_ABL 0  // developer ablations (wrong results!): 1 no stores, 2 no DMA waits, 4 no DMA at all,
@@ -884,13 +884,3 @@ enum V3Route {
 #include "aa_fused_u8_v3_list.h"
 };
 enum V3Arith { V3_PIL = 1, V3_FLT = 2, V3_BOTH = 3 };
-
-// One kernel of the compiled set, as the plan chose it: its route and every template argument, and the unit that compiled it
-struct V3Kernel;
-typedef int (*V3Launch)(const V3Kernel &k, const FusedU8V3Params *p, const AAProblem *q, size_t lds);  // (q == nullptr: does the unit
-                                                                                                       // hold k?  Launches nothing)
-struct V3Kernel {
-  int route, C, TW, MAXC, UPK, PL, SP;
-  bool ALPHA, FLT, fast, NONNEG, TWO_DMA, PERIODIC;  // fast: AA_V3_FLT_FAST
-  V3Launch launch;
-};

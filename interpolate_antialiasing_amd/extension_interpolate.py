@@ -354,8 +354,6 @@ def _axis_pass_2d(L, x, y, dt, kind, outer, n_in, n_out, inner, table, dev, stre
     if L.aa_workspace_bytes(dt, _lib.NCHW, n2, 1, h2, w2, oh2, ow2, ctypes.byref(ah), ctypes.byref(aw)) != 0:
         return False  # no fused kernel for this pass (or they are disabled): the single-axis kernel is the cheaper form
     rc = L.aa_resample_fwd(x.data_ptr(), y.data_ptr(), None, 0, dt, _lib.NCHW, n2, 1, h2, w2, ctypes.byref(ah), ctypes.byref(aw), stream)
-    if rc == -6:  # AA_ERR_WORKSPACE: a pointer-dependent decline (an unaligned view) after the shape said yes
-        return False
     _lib.check(rc, "aa_resample_fwd (axis pass)")
     return True
 
