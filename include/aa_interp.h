@@ -147,7 +147,9 @@ int aa_table_transposed_ksize(int filter, int kind, int64_t in_size, int64_t out
 /* Build the adjoint (gather-form) table of `table_dev` on device: for every INPUT index x, the contiguous
  * range of outputs whose window holds x and their weights.  The result is a packed table whose in_size/out_size
  * are swapped, usable with aa_resample_fwd to compute the TRUE adjoint (what test.py:387-398 asks for; the
- * reference's own backward header is non-AA).  F32/F64 kinds only.  Asynchronous. */
+ * reference's own backward header is non-AA).  F32/F64 kinds only.  Table-build time: reads the forward header before
+ * and the new header after the launch (two synchronisations).  header.max_taps of the result is the widest range FOUND; rows of
+ * tr_ksize entries that cannot hold it would drop gradient taps, so that is AA_ERR_KSIZE and the table must not be used. */
 int aa_table_transpose(const void *table_dev, void *tr_table_dev, size_t tr_table_bytes, int tr_ksize,
                        aa_stream_t stream);
 

@@ -402,7 +402,13 @@ int aa_table_transpose(const void *table_dev, void *tr_table_dev, size_t tr_tabl
   if (h.kind == AA_TABLE_PIL) return AA_ERR_BAD_DTYPE;
   if (tr_ksize <= 0 || tr_ksize > AA_MAX_KSIZE) return AA_ERR_KSIZE;
   if (tr_table_bytes < aa_table_total_bytes(h.kind, h.in_size, tr_ksize)) return AA_ERR_WORKSPACE;
-  return aa_launch_table_transpose(h, table_dev, tr_table_dev, tr_ksize, (hipStream_t)stream);
+  rc = aa_launch_table_transpose(h, table_dev, tr_table_dev, tr_ksize, (hipStream_t)stream);
+  if (rc != AA_OK) return rc;
+  // the kernel recorded the widest row it FOUND: rows of tr_ksize entries that cannot hold it would drop gradient taps
+  aa_table_header th;
+  rc = aa_table_query(tr_table_dev, &th, stream);  // table-build time only
+  if (rc != AA_OK) return rc;
+  return th.max_taps > tr_ksize ? AA_ERR_KSIZE : AA_OK;
 }
 
 size_t aa_workspace_bytes_ex(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW,

@@ -257,7 +257,10 @@ __global__ void table_transpose_kernel(const char *fwd, int32_t *tmin, int32_t *
   }
   int cnt = lo - first;
   if (cnt < 0) cnt = 0;
-  if (cnt > tr_ksize) cnt = tr_ksize;  // cannot happen when tr_ksize comes from aa_table_transposed_ksize
+  // header.max_taps gets the count BEFORE the clamp: a row capacity short of it (tr_ksize not from aa_table_transposed_ksize, or that
+  // estimate wrong) would drop gradient taps, so the host compares max_taps with tr_ksize and refuses the table (AA_ERR_KSIZE)
+  atomicMax(max_taps, cnt > 1 ? cnt : 1);
+  if (cnt > tr_ksize) cnt = tr_ksize;  // (memory safety only: such a table is never handed to a kernel)
   tmin[x] = cnt > 0 ? first : (first < out_size ? first : out_size - 1);  // (kept monotone: the span measurement and the fused kernels' segments rely on it)
   tsize[x] = cnt;
   int k = 0;
@@ -266,7 +269,6 @@ __global__ void table_transpose_kernel(const char *fwd, int32_t *tmin, int32_t *
     tw[k] = w[(size_t)o * ksize + (x - xmin[o])];
   }
   for (; k < tr_ksize; k++) tw[k] = (WT)0;
-  atomicMax(max_taps, cnt > 1 ? cnt : 1);
 }
 
 // Scatter section of AA_TABLE_PIL tables: one 32-byte record per INPUT index x, read by the fused kernels with a

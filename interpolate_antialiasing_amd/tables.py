@@ -224,6 +224,9 @@ def get_transposed_table(fwd: WeightTable, scale: float = 0.0) -> WeightTable:
                    "aa_table_transpose")
         hdr = _lib.TableHeader()
         _lib.check(L.aa_table_query(ctypes.c_void_p(buf.data_ptr()), ctypes.byref(hdr), s), "aa_table_query")
+    if int(hdr.max_taps) > tk:  # (aa_table_transpose refuses this itself: a table whose rows dropped taps is never cached)
+        raise _lib.AAInterpError(f"transposed weight table: an input index feeds {int(hdr.max_taps)} outputs but rows hold {tk} "
+                                 f"(filter {fwd.filter}, {fwd.in_size} -> {fwd.out_size})")
     t = WeightTable(buf, fwd.filter, fwd.kind, fwd.out_size, fwd.in_size, tk, int(hdr.max_taps), fwd.align_corners, True,
                     span64p1=int(hdr.span64p1), span4p1=int(hdr.span4p1), gather_off=int(hdr.gather_off))
     with _cache_lock:
