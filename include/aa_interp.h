@@ -218,18 +218,31 @@ int aa_resample_fwd_ex(const void *in_dev, void *out_dev, void *workspace_dev, s
 int aa_resample_fwd_strided(const void *in_dev, void *out_dev, int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W,
                             const int64_t *in_strides, const aa_axis *ax_h, const aa_axis *ax_w, unsigned flags, aa_stream_t stream);
 
-/* Decode-adjacent forward: uint8 image in, float32 tensor out, ONE launch.  Replaces what the reference's harness
+/* Decode-adjacent forward: uint8 image in, float tensor out (float32; float16 / bfloat16 on request), ONE launch.  Replaces what the reference's harness
  * does around the op on the CPU — np.asarray(pil) -> transpose(2,0,1) -> .float() -> op (test.py:337-339,55; README.md:416
  * prices those conversions at 0.33 of 2.27 ms) — and, optionally, the per-channel normalisation that follows in a data
  * loader.  out = op(float(in)) in the reference's fp32 arithmetic (AA_TABLE_F32 tables; bit-identical to aa_resample_fwd on
  * the converted tensor), written in cv->out_layout, which may differ from the input's; with cv->normalize,
- * out = (out - mean[c]) / std[c] in fp32 (C <= 4).  in_dev [N,C,H,W] uint8 in `layout`; out_dev [N,C,oH,oW] float32. */
+ * out = (out - mean[c]) / std[c] in fp32 (C <= 4).  in_dev [N,C,H,W] uint8 in `layout`; out_dev [N,C,oH,oW] float32.
+ *
+ * AA_FLAG_OUT_F16 / AA_FLAG_OUT_BF16 (valid in aa_convert.flags ONLY; aa_resample_fwd_ex and aa_resample_fwd_strided reject them as
+ * unknown bits): out_dev holds 2-byte elements, float16 or bfloat16, what a model trained in 16-bit precision reads.  The result is
+ * round_to_nearest_even_16(f32_result), f32_result being exactly what the call writes without the bit, normalisation included: fp32
+ * arithmetic, fp32 normalisation, ONE rounding at the store (the convention of AA_F16 / AA_BF16 images above) — and no float32 tensor
+ * written and read again by a cast.  With neither bit the output is float32.  Both bits: AA_ERR_BAD_DTYPE.  out_dev must be aligned to
+ * its element (2 bytes; 4 for float32), AA_ERR_BAD_SHAPE otherwise; an output that is only 2-byte aligned, or whose rows are an odd
+ * number of elements, is served by the same kernels (2-byte stores instead of paired ones), so aa_workspace_bytes_u8_to_f32 does not
+ * depend on the pointer.  A library that predates these bits rejects them as unknown flag bits (AA_ERR_BAD_SHAPE): the ABI version
+ * stays 3. */
+#define AA_FLAG_OUT_F16 4u
+#define AA_FLAG_OUT_BF16 8u
 typedef struct aa_convert {
-  int32_t out_layout; /* aa_layout of the float32 output */
+  int32_t out_layout; /* aa_layout of the float output */
   int32_t normalize;  /* 0: raw op result */
   float mean[4];
   float std[4];
-  uint32_t flags;     /* 0, or AA_FLAG_FAST: the tolerance mode (fused multiply-adds; results within 1e-4 relative of the exact mode's) */
+  uint32_t flags;     /* 0, or any of: AA_FLAG_FAST, the tolerance mode (fused multiply-adds; results within 1e-4 relative of the exact
+                         mode's); AA_FLAG_OUT_F16 or AA_FLAG_OUT_BF16, the output's element type (see above) */
 } aa_convert;
 size_t aa_workspace_bytes_u8_to_f32(int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w,
                                     const aa_convert *cv);

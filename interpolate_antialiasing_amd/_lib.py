@@ -24,6 +24,8 @@ ERR_BAD_DTYPE = -2
 ERR_STRIDES = -10
 FLAG_FAST = 1
 FLAG_PREMUL_ALPHA = 2
+FLAG_OUT_F16 = 4   # aa_convert.flags only: the decode-adjacent forward writes float16 ...
+FLAG_OUT_BF16 = 8  # ... or bfloat16 instead of float32
 
 # every symbol include/aa_interp.h declares (tests check the .so exports exactly these)
 EXPORTS = (

@@ -183,6 +183,8 @@ int resample(AAProblem &q, const void *in_dev, void *out_dev, void *workspace_de
     // not depend on the pointers: aa_workspace_bytes answers from the shape alone)
     const uintptr_t es = q.dtype == AA_U8 ? 1 : (q.dtype == AA_F64 ? 8 : (q.dtype == AA_F32 ? 4 : 2));
     if ((((uintptr_t)in_dev | (uintptr_t)out_dev) & (es - 1)) != 0) return AA_ERR_BAD_SHAPE;
+    // (a float output of uint8 images: its own element size)
+    if (q.out_f32 && ((uintptr_t)out_dev & (q.out_elem == AA_F32 ? 3 : 1)) != 0) return AA_ERR_BAD_SHAPE;
   }
   q.in = in_dev; q.out = out_dev; q.ws = workspace_dev; q.ws_bytes = workspace_bytes;
   q.stream = (hipStream_t)stream;
@@ -217,9 +219,11 @@ int fill_convert(AAProblem &q, const aa_convert &cv) {
   q.normalize = cv.normalize ? 1 : 0;
   for (int i = 0; i < 4; i++) { q.mean[i] = cv.mean[i]; q.std[i] = cv.std[i]; }
   q.fast = (cv.flags & AA_FLAG_FAST) ? 1 : 0;
+  q.out_elem = (cv.flags & AA_FLAG_OUT_F16) ? AA_F16 : (cv.flags & AA_FLAG_OUT_BF16) ? AA_BF16 : AA_F32;
   if (cv.out_layout != AA_NCHW && cv.out_layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   if (cv.normalize && q.C > 4) return AA_ERR_BAD_SHAPE;
-  if (cv.flags & ~(uint32_t)AA_FLAG_FAST) return AA_ERR_BAD_SHAPE;
+  if (cv.flags & ~(uint32_t)(AA_FLAG_FAST | AA_FLAG_OUT_F16 | AA_FLAG_OUT_BF16)) return AA_ERR_BAD_SHAPE;
+  if ((cv.flags & AA_FLAG_OUT_F16) && (cv.flags & AA_FLAG_OUT_BF16)) return AA_ERR_BAD_DTYPE;  // one element type
   return AA_OK;
 }
 

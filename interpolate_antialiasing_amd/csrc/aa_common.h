@@ -119,8 +119,10 @@ struct AAProblem {
   aa_axis ah, aw;
   hipStream_t stream;
   // decode-adjacent conversion (aa_resample_fwd_u8_to_f32): uint8 in, float32 out, optional layout change and per-channel
-  // (v - mean) / std.  out_f32 == 0: the output has the input's dtype and layout.
+  // (v - mean) / std.  out_f32 == 0: the output has the input's dtype and layout.  out_elem: the float output's element type, AA_F32, or
+  // AA_F16 / AA_BF16 (AA_FLAG_OUT_F16 / AA_FLAG_OUT_BF16): the same fp32 result rounded to nearest even once, at the store.
   int out_f32 = 0;
+  int out_elem = AA_F32;
   int out_layout = AA_NCHW;
   int normalize = 0;
   float mean[4] = {0.f, 0.f, 0.f, 0.f};

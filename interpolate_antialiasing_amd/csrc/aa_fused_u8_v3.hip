@@ -45,7 +45,8 @@ bool aa_v3_plan(const AAProblem &q, bool fast, V3Plan *pl) {
   // a planar wave holds one channel: it can write its own float plane, not an interleaved pixel
   if (out_f32 && planar && Cin != 1 && out_layout != AA_NCHW) return false;
   const int64_t oH = ah.out_size, oW = aw.out_size;
-  if (out_f32 && (uint64_t)oH * oW * (planar ? 1 : Cin) * 4 > 0xFFFFFFF0ull) return false;
+  const int out_es = q.out_elem == AA_F32 ? 4 : 2;  // bytes per element of a float output (float16 / bfloat16: 2)
+  if (out_f32 && (uint64_t)oH * oW * (planar ? 1 : Cin) * out_es > 0xFFFFFFF0ull) return false;
   const bool up = H < oH;  // growing heights: the vertical pass gathers (template parameter UPK of the kernel)
   const int taps_h = ah.max_taps > 0 ? ah.max_taps : ah.ksize;
   const int taps_w = aw.max_taps > 0 ? aw.max_taps : aw.ksize;
@@ -101,7 +102,7 @@ bool aa_v3_plan(const AAProblem &q, bool fast, V3Plan *pl) {
   if (q.in_row_pitch && ((uint64_t)H * (uint64_t)q.in_row_pitch > 0x7FFFFFF0ull || up)) return false;
   pl->row_pitch = q.in_row_pitch ? (unsigned)q.in_row_pitch : (unsigned)(W * C);
   pl->img_in_bytes = q.in_img_pitch ? (unsigned long long)q.in_img_pitch : (unsigned long long)H * W * C;
-  pl->img_out_bytes = (unsigned long long)oH * oW * C * (out_f32 ? 4 : 1);
+  pl->img_out_bytes = (unsigned long long)oH * oW * C * (out_f32 ? out_es : 1);
 
   // the kernel
   const int sm = ah.scatter_max;
@@ -123,6 +124,7 @@ bool aa_v3_plan(const AAProblem &q, bool fast, V3Plan *pl) {
   k.NONNEG = !flt && !six && aa_filters_nonneg(aw.filter, ah.filter) && (!up || taps_h <= 2);
   k.UPK = !up ? 0 : (taps_h <= 2 && (flt || k.NONNEG)) ? 2 : 6;
   k.TWO_DMA = nseg > 64;  // wide segments (large down-scales): the generic-address form
+  if (out_f32 && q.out_elem != AA_F32 && !v3_route_has_out16(k.route)) return false;
   k.launch = v3_unit(k);
   if (!k.launch) return false;
 
@@ -149,11 +151,13 @@ bool aa_v3_plan(const AAProblem &q, bool fast, V3Plan *pl) {
   pl->nseg = nseg;
   pl->v1_first = v1_first;
 #define V3_FAST(s) (k.fast ? s "_fast" : s)
+#define V3_TO(a, b) (q.out_elem == AA_F16 ? V3_FAST(a "f16" b) : q.out_elem == AA_BF16 ? V3_FAST(a "bf16" b) : V3_FAST(a "f32" b))
   pl->variant = alpha    ? (six ? "fused_u8_nhwc_pil_alpha6_v3" : "fused_u8_nhwc_pil_alpha_v3")
                 : !flt   ? (planar ? "fused_u8_planar_pil_v3" : "fused_u8_nhwc_pil_v3")
                 : !out_f32 ? (planar ? V3_FAST("fused_u8_planar_harness_v3") : V3_FAST("fused_u8_nhwc_harness_v3"))
-                : planar ? V3_FAST("fused_u8_planar_to_f32_v3")
-                : out_layout == AA_NCHW ? V3_FAST("fused_u8_nhwc_to_f32_nchw_v3") : V3_FAST("fused_u8_nhwc_to_f32_nhwc_v3");
+                : planar ? V3_TO("fused_u8_planar_to_", "_v3")
+                : out_layout == AA_NCHW ? V3_TO("fused_u8_nhwc_to_", "_nchw_v3") : V3_TO("fused_u8_nhwc_to_", "_nhwc_v3");
+#undef V3_TO
 #undef V3_FAST
   return true;
 }
@@ -170,6 +174,7 @@ int aa_v3_launch(const V3Plan &pl, const AAProblem &q) {
   p.img_out_bytes = pl.img_out_bytes;
   p.outm = q.out_f32 ? (pl.planar || q.out_layout == AA_NCHW ? 1 : 2) : 0;
   p.normalize = q.out_f32 ? q.normalize : 0;
+  p.out16 = !q.out_f32 ? 0 : q.out_elem == AA_F16 ? 1 : q.out_elem == AA_BF16 ? 2 : 0;
   p.cin = (int)q.C;
   p.fast = pl.k.fast ? 1 : 0;
   for (int c = 0; c < 4; c++) { p.mean[c] = q.mean[c]; p.std[c] = q.std[c]; }
@@ -178,7 +183,10 @@ int aa_v3_launch(const V3Plan &pl, const AAProblem &q) {
   // byte stores: output rows that are not whole dwords, an output that is not dword aligned, or split windows (a quad's first lane stores
   // its pixel's bytes)
   p.byte_store = (pl.k.route == V3_SPLIT || (!q.out_f32 && ((q.oW * C) % 4 != 0 || (C == 3 && q.oW % 4 != 0) || ((uintptr_t)q.out & 3) != 0))) ? 1 : 0;
-  if (q.out_f32 && ((uintptr_t)q.out & 3) != 0) return AA_ERR_BAD_SHAPE;  // a float tensor that is not float aligned
+  if (q.out_f32 && ((uintptr_t)q.out & (p.out16 ? 1 : 3)) != 0) return AA_ERR_BAD_SHAPE;  // a float tensor that is not element aligned
+  // 16-bit floats leave in pairs (dword stores) when the output and every row of it start on dword boundaries: even oW — then every
+  // strip is an even number of columns wide too — or interleaved C = 4, whose pixels are 8 bytes
+  p.pair_store = (p.out16 && ((uintptr_t)q.out & 3) == 0 && (q.oW % 2 == 0 || (C == 4 && p.outm == 2))) ? 1 : 0;
   p.in_mis = (int)((uintptr_t)q.in & 15);
   // ----
 

@@ -103,6 +103,13 @@ struct FusedU8V3Params {
   long long pl_planes;  // planes of the whole tensor (N * C): a group is PL CONSECUTIVE planes, whatever image they belong to — planes are
                         // independent and uniformly spaced, so grayscale batches and 2-, 4-, 5-channel planar images group the same way; the
                         // last group may hold fewer (its missing planes are refused by the range check and never stored)
+  // float output only: 0 = float32 elements; 1 = float16, 2 = bfloat16 (the kernel's O16 instantiations) — the SAME fp32 result
+  // (normalisation included), rounded to nearest even once, at the store.  pair_store (16-bit elements): 1 = two neighbouring values
+  // leave in one dword (planes, and interleaved C = 3: the even lane stores its own and its right neighbour's; interleaved C = 4: a
+  // lane's four halves are 8 bytes); 0 = every lane stores its own 2-byte elements: rows that do not start on dword boundaries (odd
+  // oW) or an output that is only 2-byte aligned
+  // (at the end of the block: every other field stays where the float32 and uint8 kernels have always read it)
+  int out16, pair_store;
 };
 
 namespace {
@@ -125,6 +132,24 @@ __device__ inline unsigned pack4_clip8(int a0, int a1, int a2, int a3) {  // sem
       : "=&v"(d)
       : "v"(a0), "v"(a1), "v"(a2), "v"(a3));
   return d;
+}
+
+// two fp32 values rounded to nearest even and packed, `lo` in the low half: bfloat16 (one instruction on gfx950; NaN stays NaN) / float16
+__device__ inline unsigned pack2_bf16(float lo, float hi) {
+  unsigned d;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(d) : "v"(lo), "v"(hi));
+  return d;
+}
+__device__ inline unsigned pack2_f16(float lo, float hi) {  // (two RNE conversions and a pack: the packed conversion truncates)
+  typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+  const half2_t t = {(_Float16)lo, (_Float16)hi};
+  return __builtin_bit_cast(unsigned, t);
+}
+
+// the value of the lane to the right (odd lanes: their own).  Every lane of the quad is read, so the `old` operand is never used: passing
+// the value itself spares the register a constant would occupy across the row loop
+__device__ inline float right_neighbour(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0xF5 /*quad_perm:[1,1,3,3]*/, 0xF, 0xF, false));
 }
 
 __device__ inline int clip8_int(int acc) {  // Pillow clip8(ss >> 22) as a plain integer 0..255
@@ -185,14 +210,22 @@ __device__ inline void wait_vmcnt(int n) {  // rounding n DOWN only waits longer
 // ALPHA: straight alpha in channel 3 (AA_FLAG_PREMUL_ALPHA; Pillow's RGBA resize): each window pixel's colour is premultiplied by its
 //     alpha in registers as the horizontal pass reads it (aa_premul8), and each output pixel is un-premultiplied after the clip, before
 //     any store form packs it (aa_unpremul8).  Pillow arithmetic, 4 interleaved channels.
+// O16: float16 / bfloat16 output of the float-arithmetic kernels (FusedU8V3Params::out16) INSTEAD of float32 output.  The 16-bit store
+//     forms were first built as one more launch constant of the float32 store branch, in five shapes; every one cost the float32 kernels
+//     scalar-register spills (they sit at the limit of 106: even an empty extra branch adds spills to 16 of the 24 kernels of a unit)
+//     and the 3- and 4-channel kernels 1 to 5 vector registers, a wave per SIMD for those at 80 and 96.  So the 16-bit forms are
+//     instantiations of their own — of the routes NARROW, UP and PLANES (aa_fused_u8_v3_unit.hip) — and the float32 kernels keep the
+//     register and spill counts they had.  Which 16-bit form runs (pairs or single elements, float16 or bfloat16, planes or interleaved
+//     channels) is a launch constant of those instantiations.
 template <int C, int TW, int G, bool TWO_DMA, int MAXC, bool NONNEG, bool PERIODIC, bool FLT = false, int UPK = 0, int PL = 0, int SP = 1,
-          bool ALPHA = false>
+          bool ALPHA = false, bool O16 = false>
 __global__ void __launch_bounds__(512) AA_V3_OCC
 fused_u8_nhwc_v3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const char *__restrict__ tab_w,
                         const char *__restrict__ tab_h, const FusedU8V3Params p) {
   static_assert(PL == 0 || (PL == C && !PERIODIC && UPK == 0 && !TWO_DMA), "plane groups: shrinking heights, fixed stage layout");
   static_assert(SP == 1 || (SP == 4 && !FLT && !PERIODIC && UPK == 0 && PL == 0), "split windows: integer arithmetic, shrinking heights");
   static_assert(!ALPHA || (C == 4 && !FLT && PL == 0), "premultiplied alpha: Pillow arithmetic, 4 interleaved channels");
+  static_assert(!O16 || (FLT && SP == 1), "16-bit float output: float arithmetic");
   constexpr int PLN = PL > 0 ? PL : 1;  // windows per lane and row
   constexpr int CB = PL > 0 ? 1 : C;    // bytes per pixel in a staged row
   constexpr int NV1 = (CB * TW + 3) / 4;  // dwords holding one window
@@ -438,7 +471,10 @@ fused_u8_nhwc_v3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ ou
   };
   // which store form the kernel uses is a launch constant: a scalar, so that the per-row choice is a scalar compare (as a bool
   // merged across the branches below the compiler kept it in a lane mask: a v_cndmask + v_cmp per output row)
-  const int emit_path = __builtin_amdgcn_readfirstlane((FLT && p.outm != 0) ? 1 : (p.byte_store ? 2 : 0));
+  // 0: merged dword stores of bytes; 2: byte stores; odd = float output: 1 float32; O16: | 2 stored in pairs (else singly), | 4 bfloat16
+  // (else float16), | 8 channel planes (else interleaved channels)
+  const int emit_path = __builtin_amdgcn_readfirstlane(
+      (FLT && p.outm != 0) ? (O16 ? (1 | (p.pair_store ? 2 : 0) | (p.out16 == 2 ? 4 : 0) | ((C == 1 || p.outm == 1) ? 8 : 0)) : 1) : (p.byte_store ? 2 : 0));
   auto emit = [&](int oy) {  // accumulator set 0 is complete: clip, pack, merge quads, store; then slide the sets down
     if constexpr (ALPHA) {  // un-premultiply the clipped pixel; every store form below clips (x >> 22) again, which keeps b << 22 as b
       const int al = clip8_int(A[0][3]);
@@ -447,6 +483,70 @@ fused_u8_nhwc_v3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ ou
       A[0][3] = al << 22;
     }
     if constexpr (FLT) {
+      if constexpr (O16) {
+        if (emit_path & 1) {  // (wave-uniform) float16 / bfloat16 output: the value the float32 form stores, rounded to nearest even ONCE
+          int lane_o = lane;
+          asm volatile("" : "+v"(lane_o));  // (address arithmetic of this path stays inside it, see the byte-store path)
+          auto pack2 = [&](float lo, float hi) -> unsigned { return (emit_path & 4) ? pack2_bf16(lo, hi) : pack2_f16(lo, hi); };
+          auto value = [&](int c) -> float {
+            const float x = __int_as_float(A[0][c]);
+            return p.normalize ? (x - nm_mean[c]) / nm_std[c] : x;
+          };
+          // pairs: the even lane stores its own value and its right neighbour's (one DPP move, one packed conversion).  Strips start on
+          // multiples of 4 columns, so a pair never straddles two strips, and the paired forms run only when every strip is an even number
+          // of columns wide (pair_store): an even lane's partner is active too.  (All 64 lanes convert: lanes beyond the strip hold a
+          // duplicate of lane 0.)  Lane 0 is active and even, so every store below is certainly issued.
+          const bool pairs = (emit_path & 2) != 0;
+          const bool all = lane_o < bw, st = all && (!pairs || (lane_o & 1) == 0);
+          if (emit_path & 8) {  // planes, one after the other: a dword per even lane, or 2 bytes per lane
+            if constexpr (UPK > 0) vm_issued += C;
+            const unsigned fv = (unsigned)(ox0 + lane_o) * 2u;
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+              const unsigned fs = ((unsigned)c * (unsigned)p.oH + (unsigned)oy) * (unsigned)p.oW * 2u;
+              const float x = value(c);
+              const unsigned d = pack2(x, right_neighbour(x));
+              if (pairs) {
+                if (st && (PL == 0 || c < pl_valid)) __builtin_amdgcn_raw_buffer_store_b32(d, orsrc, fv, fs, AA_V3_F32OUT_AUX);
+              } else {
+                if (st && (PL == 0 || c < pl_valid)) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)d, orsrc, fv, fs, AA_V3_F32OUT_AUX);
+              }
+            }
+          } else if constexpr (C > 1) {  // interleaved channels
+            const unsigned fv = (unsigned)(ox0 + lane_o) * (unsigned)(2 * C), fs = (unsigned)oy * (unsigned)p.oW * (unsigned)(2 * C);
+            float x[C];
+#pragma unroll
+            for (int c = 0; c < C; c++) x[c] = value(c);
+            unsigned d[3];
+            if constexpr (C == 3) {  // two pixels = 12 bytes from the even lane: {r, g} {b, r'} {g', b'}
+              d[2] = pack2(right_neighbour(x[1]), right_neighbour(x[2]));
+              d[1] = pack2(x[2], right_neighbour(x[0]));
+              d[0] = pack2(x[0], x[1]);
+            } else {  // a pixel = 8 bytes from its own lane
+              d[0] = pack2(x[0], x[1]);
+              d[1] = pack2(x[2], x[C - 1]);
+              d[2] = 0;
+            }
+            if (!pairs) {  // 2 bytes per lane and channel
+              if constexpr (UPK > 0) vm_issued += C;
+#pragma unroll
+              for (int c = 0; c < C; c++)
+                if (all) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(d[c >> 1] >> (16 * (c & 1))), orsrc, fv + 2u * (unsigned)c, fs, AA_V3_F32OUT_AUX);
+            } else {
+              if constexpr (UPK > 0) vm_issued += 1;
+              if constexpr (C == 3) {
+                typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
+                const u32x3 t = {d[0], d[1], d[2]};
+                if (st) __builtin_amdgcn_raw_buffer_store_b96(t, orsrc, fv, fs, AA_V3_F32OUT_AUX);
+              } else {
+                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+                const u32x2 t = {d[0], d[1]};
+                if (all) __builtin_amdgcn_raw_buffer_store_b64(t, orsrc, fv, fs, AA_V3_F32OUT_AUX);
+              }
+            }
+          }
+        }
+      } else
       if (emit_path == 1) {  // (wave-uniform) float32 output: the accumulators themselves, one 256-byte row piece per plane
         float v[C];
         int lane_o = lane;
@@ -838,9 +938,9 @@ int pick_ybands(int64_t items_per_band, double slots, int taps_h, int64_t H, int
 }
 
 template <int C, int TW, int G, int MAXC, bool TWO, bool NONNEG, bool PERIODIC, bool FLT = false, int UPK = 0, int PL = 0, int SP = 1,
-          bool ALPHA = false>
+          bool ALPHA = false, bool O16 = false>
 int launch_k(FusedU8V3Params p, const AAProblem &q, size_t lds) {
-  auto kern = fused_u8_nhwc_v3_kernel<C, TW, G, TWO, MAXC, NONNEG, PERIODIC, FLT, UPK, PL, SP, ALPHA>;
+  auto kern = fused_u8_nhwc_v3_kernel<C, TW, G, TWO, MAXC, NONNEG, PERIODIC, FLT, UPK, PL, SP, ALPHA, O16>;
   auto resident = [&](int s) {  // resident workgroups of s strips per CU for this instantiation and this problem's LDS
     int nb = aa_resident_blocks(kern, 64 * s, lds * s);
     if (nb <= 0) nb = 16 / s;
@@ -884,3 +984,6 @@ enum V3Route {
 #include "aa_fused_u8_v3_list.h"
 };
 enum V3Arith { V3_PIL = 1, V3_FLT = 2, V3_BOTH = 3 };
+// routes whose float-arithmetic kernels are also instantiated with float16 / bfloat16 output (template parameter O16); in the others such
+// a problem has no fused kernel and takes the two-launch path
+constexpr bool v3_route_has_out16(int route) { return route == V3_NARROW || route == V3_UP || route == V3_PLANES; }

@@ -53,6 +53,13 @@ int v3_launch_unit(const V3Kernel &k, const FusedU8V3Params *p, const AAProblem 
             constexpr bool TWO = F & S::T, NONNEG = F & S::N, PERIODIC = F & S::P;
             if (k.FLT != FLT || k.TW != TW || k.MAXC != MAXC || k.UPK != UPK || k.TWO_DMA != TWO || k.NONNEG != NONNEG || k.PERIODIC != PERIODIC)
               return false;
+            // float16 / bfloat16 output (p->out16) has instantiations of its own, in the routes v3_route_has_out16 names
+            if constexpr (FLT && v3_route_has_out16(R)) {
+              if (q && p->out16) {
+                rc = launch_k<C, TW, 8, MAXC, TWO, NONNEG, PERIODIC, FLT, UPK, PL, SP, ALPHA, true>(*p, *q, lds);
+                return true;
+              }
+            }
             rc = q ? launch_k<C, TW, 8, MAXC, TWO, NONNEG, PERIODIC, FLT, UPK, PL, SP, ALPHA>(*p, *q, lds) : 1;
             return true;
           });

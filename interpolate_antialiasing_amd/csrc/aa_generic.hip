@@ -437,8 +437,9 @@ int aa_launch_generic_fwd(const AAProblem &p, const char **variant) {
 // per-channel (v - mean) / std.  Same arithmetic as the harness path (PipeF32, taps in order).
 namespace {
 struct ConvertArgs { int in_nhwc, out_nhwc, normalize; float mean[4], std[4]; };
+template <typename TOut>  // float, or f16_t / bf16_t: the fp32 result rounded to nearest even at the store
 __global__ void __launch_bounds__(256)
-vpass_convert(const float *__restrict__ mid, float *__restrict__ out, const char *__restrict__ table, int64_t total, int C, int H,
+vpass_convert(const float *__restrict__ mid, TOut *__restrict__ out, const char *__restrict__ table, int64_t total, int C, int H,
               int oH, int oW, int ksize, const ConvertArgs cv) {
   const TableView<float> tv = make_table_view<float>(table, oH, ksize);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -465,8 +466,13 @@ vpass_convert(const float *__restrict__ mid, float *__restrict__ out, const char
     float acc = src[0] * w[0];
     for (int j = 1; j < cnt; j++) acc = acc + src[j * rstride] * w[j];
     if (cv.normalize) acc = (acc - cv.mean[c & 3]) / cv.std[c & 3];
-    out[idx] = acc;
+    out[idx] = Store<TOut, float>::cvt(acc, 0);
   }
+}
+template <typename TOut>
+void launch_vpass_convert(const AAProblem &p, const float *mid, int64_t vtotal, const ConvertArgs &cv) {
+  hipLaunchKernelGGL(vpass_convert<TOut>, dim3(grid_for(vtotal)), dim3(256), 0, p.stream, mid, (TOut *)p.out, (const char *)p.ah.table_dev,
+                     vtotal, (int)p.C, (int)p.H, (int)p.oH, (int)p.oW, p.ah.ksize, cv);
 }
 }  // namespace
 
@@ -485,10 +491,11 @@ int aa_launch_generic_convert(const AAProblem &p, const char **variant) {
   cv.in_nhwc = nhwc; cv.out_nhwc = p.out_layout == AA_NHWC; cv.normalize = p.normalize;
   for (int i = 0; i < 4; i++) { cv.mean[i] = p.mean[i]; cv.std[i] = p.std[i]; }
   const int64_t vtotal = N * C * oH * oW;
-  hipLaunchKernelGGL(vpass_convert, dim3(grid_for(vtotal)), dim3(256), 0, p.stream, (const float *)mid, (float *)p.out,
-                     (const char *)p.ah.table_dev, vtotal, (int)C, (int)H, (int)oH, (int)oW, p.ah.ksize, cv);
+  if (p.out_elem == AA_F16) launch_vpass_convert<f16_t>(p, mid, vtotal, cv);
+  else if (p.out_elem == AA_BF16) launch_vpass_convert<bf16_t>(p, mid, vtotal, cv);
+  else launch_vpass_convert<float>(p, mid, vtotal, cv);
   AA_HIP_CHECK_LAUNCH();
-  *variant = "generic_2pass_u8_to_f32";
+  *variant = p.out_elem == AA_F16 ? "generic_2pass_u8_to_f16" : p.out_elem == AA_BF16 ? "generic_2pass_u8_to_bf16" : "generic_2pass_u8_to_f32";
   return AA_OK;
 }
 

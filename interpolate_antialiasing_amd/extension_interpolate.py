@@ -152,11 +152,12 @@ def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequen
             _require_gpu(input, name)
             return input.clone()  # Pillow returns a copy: no lossy round trip through premultiplied values
     if out_dtype is not None or out_format is not None or mean is not None or std is not None:
-        if input.dtype != torch.uint8 or out_dtype not in (None, torch.float32):
+        if input.dtype != torch.uint8 or out_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
             raise NotImplementedError("out_dtype / out_format / mean / std: the fused conversion takes uint8 input and gives float32")
         if uint8_mode == "pil":
             raise NotImplementedError("float32 output is the reference's fp32 arithmetic (uint8_mode='harness'), not Pillow's integers")
-        return _forward_to_float(filter_id, name, input, output_size, align_corners, scale_factors, out_format, mean, std, flags)
+        return _forward_to_float(filter_id, name, input, output_size, align_corners, scale_factors, out_format, mean, std, flags,
+                                 out_dtype or torch.float32)
     n, c, h, w, oh, ow = _check_sizes(input.shape, output_size)
     if input.numel() == 0 and (c == 0):  # empty batch allowed, nothing else (s2.2:747-750)
         raise RuntimeError(f"Non-empty 4D data tensor expected but got a tensor with sizes {list(input.shape)}")
@@ -233,12 +234,14 @@ def _check_alpha(name: str, input: torch.Tensor, uint8_mode, out_dtype, out_form
 
 
 def _forward_to_float(filter_id: int, name: str, input: torch.Tensor, output_size: Sequence[int], align_corners: bool,
-                      scale_factors, out_format: Optional[str], mean, std, flags: int = 0) -> torch.Tensor:
+                      scale_factors, out_format: Optional[str], mean, std, flags: int = 0, out_dtype=torch.float32) -> torch.Tensor:
     """Decode-adjacent forward: uint8 in, float32 out, one launch.  The reference's harness spends 0.33 of its
     2.27 ms per image on np.asarray(pil) -> transpose -> .float() before the op (test.py:337-339,55; README.md:416); here the
     uint8 bytes (HWC = channels_last, or CHW) are read directly, the op runs in the reference's fp32 arithmetic and the
     float32 result is written in the requested layout ("nchw" / "nhwc"; default: the input's), optionally normalised
-    per channel as (v - mean[c]) / std[c].  Equals ``op(input.float())`` bit for bit."""
+    per channel as (v - mean[c]) / std[c].  Equals ``op(input.float())`` bit for bit.  out_dtype torch.float16 / torch.bfloat16:
+    that float32 result, normalisation included, rounded to nearest even once as it is stored, i.e. what ``.to(out_dtype)`` of it
+    gives, without the float32 tensor and the second pass."""
     n, c, h, w, oh, ow = _check_sizes(input.shape, output_size)
     if input.numel() == 0 and c == 0:
         raise RuntimeError(f"Non-empty 4D data tensor expected but got a tensor with sizes {list(input.shape)}")
@@ -251,7 +254,7 @@ def _forward_to_float(filter_id: int, name: str, input: torch.Tensor, output_siz
     cv = _lib.Convert()
     cv.out_layout = out_layout
     cv.normalize = 0
-    cv.flags = flags
+    cv.flags = flags | {torch.float16: _lib.FLAG_OUT_F16, torch.bfloat16: _lib.FLAG_OUT_BF16}.get(out_dtype, 0)
     if (mean is None) != (std is None):
         raise ValueError("mean and std must be given together")
     if mean is not None:
@@ -264,7 +267,7 @@ def _forward_to_float(filter_id: int, name: str, input: torch.Tensor, output_siz
     sh, sw = _user_scales(scale_factors, 2)
     dev = x.device
     mf = torch.channels_last if out_layout == _lib.NHWC else torch.contiguous_format
-    out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=dev, memory_format=mf)
+    out = torch.empty((n, c, oh, ow), dtype=out_dtype, device=dev, memory_format=mf)
     if n == 0:
         return out
     with torch.cuda.device(dev):
