@@ -250,14 +250,22 @@ int aa_resample_fwd_u8_to_f32(const void *in_dev, void *out_dev, void *workspace
                               int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h, const aa_axis *ax_w,
                               const aa_convert *cv, aa_stream_t stream);
 
-/* Backward (true adjoint): grad_in[N,C,H,W] = H^T V^T grad_out[N,C,oH,oW], F32/F64 only.  Replaces
+/* Backward (true adjoint): grad_in[N,C,H,W] = H^T V^T grad_out[N,C,oH,oW].  Replaces
  * ti_upsample_bilinear2d_backward_cpu (s2.2/aa_interpolation_backward_impl.h:185-219) in API shape.
- * tr_h / tr_w are TRANSPOSED tables from aa_table_transpose (gather form: deterministic, no atomics, no zero fill). */
+ * tr_h / tr_w are TRANSPOSED tables from aa_table_transpose (gather form: deterministic, no atomics, no zero fill).
+ * dtype: AA_F32 (AA_TABLE_F32 tables), AA_F64 (AA_TABLE_F64), and AA_F16 / AA_BF16 gradients with transposed AA_TABLE_F32 tables, which
+ * follow the convention of AA_F16 / AA_BF16 images above: grad_in = round_to_nearest_even_16(adjoint_fp32(float(grad_out))), fp32
+ * arithmetic in the fp32 backward's own order, fp32 intermediate between the passes, ONE rounding at the store; bit for bit the fp32
+ * call's result cast to 16 bits, on every route.  Any other dtype / table kind: AA_ERR_BAD_DTYPE (the answer of a library older than
+ * this addition to 16-bit gradients; the ABI version is unchanged, the change is additive).  Workspace: aa_workspace_bytes(dtype, layout,
+ * N, C, oH, oW, H, W, tr_h, tr_w), as for the forward this call is. */
 int aa_resample_bwd(const void *grad_out_dev, void *grad_in_dev, void *workspace_dev, size_t workspace_bytes, int dtype,
                     int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *tr_h, const aa_axis *tr_w,
                     aa_stream_t stream);
 /* Scatter form of the same adjoint with fp32/fp64 atomics straight from the FORWARD tables (BASELINE config 5
- * names it); grad_in is zero-filled first by the call.  Results agree with aa_resample_bwd to rounding only. */
+ * names it); grad_in is zero-filled first by the call.  Results agree with aa_resample_bwd to rounding only.
+ * AA_F32 / AA_F64 only: AA_F16 / AA_BF16 gradients are AA_ERR_BAD_DTYPE here.  Atomic adds that round to 16 bits one by one are a
+ * different and worse result than one rounding of the fp32 sum; an fp32 scatter followed by a cast is this call in AA_F32. */
 int aa_resample_bwd_atomic(const void *grad_out_dev, void *grad_in_dev, void *workspace_dev, size_t workspace_bytes,
                            int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h,
                            const aa_axis *ax_w, aa_stream_t stream);

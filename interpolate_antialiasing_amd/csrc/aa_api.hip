@@ -505,7 +505,9 @@ size_t aa_workspace_bytes_bwd(int dtype, int layout, int64_t N, int64_t C, int64
 int aa_resample_bwd(const void *grad_out_dev, void *grad_in_dev, void *workspace_dev, size_t workspace_bytes, int dtype,
                     int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *tr_h, const aa_axis *tr_w,
                     aa_stream_t stream) {
-  if (dtype != AA_F32 && dtype != AA_F64) return AA_ERR_BAD_DTYPE;
+  // 16-bit gradients: storage types, as 16-bit images are in the forward (fp32 arithmetic with AA_TABLE_F32 tables, fp32 intermediate,
+  // one rounding at the store); any other table kind is refused by the forward's own check below
+  if (dtype != AA_F32 && dtype != AA_F64 && dtype != AA_F16 && dtype != AA_BF16) return AA_ERR_BAD_DTYPE;
   if (!tr_h || !tr_w) return AA_ERR_NULL;
   // The adjoint in gather form IS a forward resample of grad_out [N,C,oH,oW] with the transposed tables
   // (tr_w: oW -> W, tr_h: oH -> H); the two 1-D adjoints act on different axes and commute.
@@ -517,6 +519,7 @@ int aa_resample_bwd(const void *grad_out_dev, void *grad_in_dev, void *workspace
 int aa_resample_bwd_atomic(const void *grad_out_dev, void *grad_in_dev, void *workspace_dev, size_t workspace_bytes,
                            int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis *ax_h,
                            const aa_axis *ax_w, aa_stream_t stream) {
+  // (16-bit gradients have the gather form only: atomic adds that round to 16 bits one by one are a different and worse result)
   if (dtype != AA_F32 && dtype != AA_F64) return AA_ERR_BAD_DTYPE;
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   if (N < 0 || C <= 0 || H <= 0 || W <= 0) return AA_ERR_BAD_SHAPE;

@@ -1,4 +1,4 @@
-// aa_fused_float.hip — host-side plan of the fused float kernels: fp32 / fp16 / bf16 / fp64 planes and fp32 channels_last with
+// aa_fused_float.hip — host-side plan of the fused float kernels: fp32 / fp16 / bf16 / fp64 planes and fp32 / fp16 / bf16 channels_last with
 // shrinking heights (aa_fused_float_impl.h), fp32 / fp16 / bf16 planes with growing heights, the gather form of the adjoint among them
 // (aa_fused_float_up_impl.h).  aa_f32_plan() makes every decision that does not depend on the pointers: the route, the strip geometry and
 // all template arguments of the kernel that will run.  aa_f32_launch() adds the few that do and launches through the unit that compiled
@@ -48,7 +48,8 @@ bool finish(int unit, int rows, F32Plan *k) {
 }
 
 // Shrinking heights, the vertical pass in scatter form.  Planes: a lane reads its window with NQ aligned reads of EPQ elements
-// (EPQ * NQ - (EPQ - 1) taps).  fp32 channels_last with 3 or 4 channels: a lane per output element, taps read one by one (4 * NQ taps).
+// (EPQ * NQ - (EPQ - 1) taps).  fp32 / fp16 / bf16 channels_last with 3 or 4 channels: a lane per output element, taps read one by one
+// (4 * NQ taps, whatever the element size).
 bool down_plan(int unit, int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const aa_axis &ah, const aa_axis &aw, F32Plan *k) {
   const int64_t cs = (layout == AA_NHWC && C > 1) ? C : 1;
   const int *widths = widths_of(unit, dtype, cs);
@@ -66,13 +67,15 @@ bool down_plan(int unit, int dtype, int layout, int64_t N, int64_t C, int64_t H,
   const int nq = k->width = widths[w];
   k->DT = dtype;
   k->cs = (int)cs;
-  // strips of 64 output elements (whole 128-byte lines per stored fp32 row piece); 32, then 16 when the segment does not fit two DMAs
+  // strips of 64 output elements (whole 128-byte lines per stored fp32 row piece, one line per 16-bit one); 32, then 16 when the segment
+  // does not fit two DMAs
   for (k->strip_w = 64;; k->strip_w /= 2) {
     if (cs != 1) {  // the strip's pixels: ceil((strip_w - 1) / C) + 1; the spread of their window starts, bounded through the measured
-                    // spread of 4 neighbours (3 steps) and of 64; + the segment start rounded down to 4 floats
+                    // spread of 4 neighbours (3 steps) and of 64; + the segment start rounded down to 4 elements; in staged pieces of
+                    // pe elements (4 floats, 8 halves)
       const int steps = ((k->strip_w - 1) / (int)cs + 1 + 2) / 3;
       const int spread = steps * (aw.span4p1 - 1) < aw.span64p1 - 1 ? steps * (aw.span4p1 - 1) : aw.span64p1 - 1;
-      k->nseg = ((spread + 4 * nq) * (int)cs + 3 + (int)cs + 3) / 4 + 1;
+      k->nseg = ((spread + 4 * nq) * (int)cs + 3 + (int)cs + pe - 1) / pe + 1;
     } else {  // the spread of the strip's window starts (+EPQ-1: the first one rounded down to the 16-byte grid) + one window
       const int win = (epq - 1) + epq * nq;
       k->nseg = ((k->strip_w == 64 ? aa_strip_span_px(aw, win) : k->strip_w == 32 ? aa_strip_span_px32(aw, win) : aa_strip_span_px16(aw, win)) +
@@ -85,7 +88,8 @@ bool down_plan(int unit, int dtype, int layout, int64_t N, int64_t C, int64_t H,
   if (!aa_grid_fits(N * C * k->nstrips)) return false;
   static const char *const kNames[2][5] = {{"", "fused_f32_nchw", "fused_f64_nchw", "fused_f16_nchw", "fused_bf16_nchw"},  // [fast][aa_dtype]
                                            {"", "fused_f32_nchw_fast", "", "fused_f16_nchw_fast", "fused_bf16_nchw_fast"}};
-  k->variant = cs != 1 ? "fused_f32_nhwc" : kNames[unit == F32_UNIT_fast][dtype];
+  static const char *const kNhwc[5] = {"", "fused_f32_nhwc", "", "fused_f16_nhwc", "fused_bf16_nhwc"};
+  k->variant = cs != 1 ? kNhwc[dtype] : kNames[unit == F32_UNIT_fast][dtype];
   return finish(unit, ah.scatter_max, k);
 }
 
@@ -129,6 +133,8 @@ bool f32_plan(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W,
   if (fast && down_plan(F32_UNIT_fast, dtype, layout, N, C, H, W, ah, aw, k)) return true;
   *k = F32Plan{};
   if (down_plan(F32_UNIT_down, dtype, layout, N, C, H, W, ah, aw, k)) return true;
+  *k = F32Plan{};
+  if (down_plan(F32_UNIT_nhwc16, dtype, layout, N, C, H, W, ah, aw, k)) return true;  // (16-bit channels_last: a unit of its own)
   *k = F32Plan{};
   return up_plan(dtype, layout, N, C, H, W, ah, aw, k);
 }

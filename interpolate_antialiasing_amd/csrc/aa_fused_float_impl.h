@@ -154,6 +154,12 @@ template <> __device__ inline unsigned f32_to_elem<AA_BF16>(float a) {  // round
 // channels_last, s2.2:752): a "plane" is an image, a row holds W*CS floats, a lane owns one output ELEMENT (pixel ox = e / CS,
 // channel e % CS) so that a wave's row piece is still 256 contiguous bytes; its taps sit CS floats apart, so the window is
 // read tap by tap (ds_read_b32 at the exact tap address: no shift, TWP = 4*NQ taps) — same arithmetic, same order.
+// fp16 / bf16 channels_last (fused_f16_nhwc / fused_bf16_nhwc) take the same route with 2-byte elements: the taps are ds_read_u16 at
+// the exact (2-byte aligned) tap address, a staged 16-byte piece holds 8 elements, a wave's row piece is 128 contiguous bytes.  The
+// segment starts at a multiple of 4 ELEMENTS OF THE ROW, as a plane's does, and the DMA reads from exactly that byte address, so the
+// element at row position x lands at LDS offset 2 * (x - seg0) whether or not the row (W*CS odd: C = 3, W odd) starts on an odd half;
+// the tensor's final element, whose dword then straddles the end of the tensor, is fetched on its own (fix_row / patch_last, with the
+// row's W*CS elements where a plane has W).  An fp16 product is v_fma_mix_f32 on the low half with a -0.0 addend, as for planes.
 template <int NQ, int G, int NDMA, int MAXC, int DT, int CS = 1>
 __global__ void __launch_bounds__(512)
 fused_f32_nchw_kernel(const void *__restrict__ in, void *__restrict__ out, const char *__restrict__ tab_w,
@@ -174,7 +180,8 @@ fused_f32_nchw_kernel(const void *__restrict__ in, void *__restrict__ out, const
   // more than 28 window positions: their lane masks no longer fit the scalar registers (two per position), so the AND form is used —
   // one 0 / ~0 VECTOR register per position (see sub_masked)
   constexpr bool ANDM = AA_F32_ANDMASK != 0 || TWP > 28;
-  static_assert(CS == 1 || DT == AA_F32, "interleaved channels: fp32 only");
+  static_assert(CS == 1 || DT == AA_F32 || DT == AA_F16 || DT == AA_BF16, "interleaved channels: fp32, fp16, bf16");
+  static_assert(CS == 1 || EPQ == 4, "interleaved channels: TWP = 4 * NQ taps, segments start on 4 elements of the row");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
 
   const int lane = threadIdx.x & 63;
@@ -249,7 +256,8 @@ fused_f32_nchw_kernel(const void *__restrict__ in, void *__restrict__ out, const
   // the last byte of a mapped page that is a memory fault (seen once in 90 000 fuzz problems: a bf16 tensor of 19 x 512 bytes at
   // the end of an allocator block).  The final element is fetched on its own instead (patch_last below).
   if (remaining > 0xFFFFFFFCull) remaining = 0xFFFFFFFCull;
-  const int fix_row = (ES == 2 && (p.Wp & 1) && (long long)plane + 1 == p.n_groups / p.ybands) ? p.H - 1 : -1;
+  const int row_w = CS == 1 ? p.Wp : p.W;  // the row's elements (W * CS for interleaved channels)
+  const int fix_row = (ES == 2 && (row_w & 1) && (long long)plane + 1 == p.n_groups / p.ybands) ? p.H - 1 : -1;
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void *)((const uint8_t *)in + plane_off), 0, (unsigned)remaining, 0x00020000);
   const unsigned row_bytes = p.row_pitch;
@@ -313,6 +321,8 @@ fused_f32_nchw_kernel(const void *__restrict__ in, void *__restrict__ out, const
         else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(A[0]), orsrc, store_voff, (unsigned)oy * out_row_bytes, 0);
       }
     } else {
+      // (interleaved 16-bit channels too: one 2-byte store per lane, a 128-byte row piece per wave.  The packed form — the even lane takes its
+      // right neighbour's rounded element with one DPP move and stores a dword — was built and measured 3-4 % slower: DESIGN.md §1d)
       if (active) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)f32_to_elem<DT>(A[0]), orsrc, store_voff, (unsigned)oy * out_row_bytes, 0);
     }
 #pragma unroll
@@ -326,12 +336,16 @@ fused_f32_nchw_kernel(const void *__restrict__ in, void *__restrict__ out, const
     const __attribute__((address_space(3))) unit_t *src =
         (const __attribute__((address_space(3))) unit_t *)(uintptr_t)(lane_lds + (unsigned)(slot * p.seg_bytes));
     unit_t d[NQ];
-    float dt[CS == 1 ? 1 : TWP];  // (interleaved channels: the taps, CS floats apart)
+    unsigned dt[CS == 1 ? 1 : TWP];  // (interleaved channels: the taps' bits, CS elements apart; 16-bit ones in the low half)
     if constexpr (CS == 1) {
 #pragma unroll
       for (int q = 0; q < NQ; q++) d[q] = src[q];
-    } else {
-      const __attribute__((address_space(3))) float *st = (const __attribute__((address_space(3))) float *)src;
+    } else if constexpr (ES == 4) {
+      const __attribute__((address_space(3))) unsigned *st = (const __attribute__((address_space(3))) unsigned *)src;
+#pragma unroll
+      for (int q = 0; q < TWP; q++) dt[q] = st[q * CS];
+    } else {  // 2-byte reads at the exact tap address (2-byte aligned only)
+      const __attribute__((address_space(3))) unsigned short *st = (const __attribute__((address_space(3))) unsigned short *)src;
 #pragma unroll
       for (int q = 0; q < TWP; q++) dt[q] = st[q * CS];
     }
@@ -339,11 +353,12 @@ fused_f32_nchw_kernel(const void *__restrict__ in, void *__restrict__ out, const
 #pragma unroll
     for (int q = 0; q < TWP; q++) {
       if constexpr (DT == AA_F16) {  // (see fma_mix_f16)
-        const unsigned pk = d[q >> 2][(q >> 1) & 1];
+        const unsigned pk = CS == 1 ? d[CS == 1 ? q >> 2 : 0][(q >> 1) & 1] : dt[CS == 1 ? 0 : q];
+        const bool hi = CS == 1 && (q & 1);  // (interleaved channels: the tap is the low half)
         if constexpr (AA_F32_FAST != 0) {
-          acc = (q & 1) ? fma_mix_f16<1>(pk, wreg[q], acc) : fma_mix_f16<0>(pk, wreg[q], acc);
+          acc = hi ? fma_mix_f16<1>(pk, wreg[q], acc) : fma_mix_f16<0>(pk, wreg[q], acc);
         } else {
-          const float prod = (q & 1) ? fma_mix_f16<1>(pk, wreg[q], neg_zero) : fma_mix_f16<0>(pk, wreg[q], neg_zero);
+          const float prod = hi ? fma_mix_f16<1>(pk, wreg[q], neg_zero) : fma_mix_f16<0>(pk, wreg[q], neg_zero);
           if constexpr (ANDM) {
             acc = sub_masked(acc, prod, mk[q]);
           } else {
@@ -354,7 +369,7 @@ fused_f32_nchw_kernel(const void *__restrict__ in, void *__restrict__ out, const
         continue;
       }
       real dq;  // window position q as a real
-      if constexpr (CS != 1) dq = dt[q];
+      if constexpr (CS != 1) dq = elem_to_f32<DT>(dt[q]);
       else if constexpr (DT == AA_F64) dq = __longlong_as_double(((unsigned long long)d[q >> 1][2 * (q & 1) + 1] << 32) | d[q >> 1][2 * (q & 1)]);
       else if constexpr (DT == AA_F32) dq = __uint_as_float(d[q / EPQ][q % EPQ]);
       else dq = elem_to_f32<DT>(d[q >> 2][(q >> 1) & 1] >> (16 * (q & 1)));
@@ -399,11 +414,11 @@ fused_f32_nchw_kernel(const void *__restrict__ in, void *__restrict__ out, const
   // 16-bit elements, odd W: the staged image of the tensor's very last row lacks its final element (see fix_row); lane 0 reads
   // that element with an ordinary 2-byte load and puts it (and a zero for the position beyond the row) into the slot
   auto patch_last = [&](int slot) {
-    const int pos = p.Wp - 1 - seg0;  // position inside the strip's segment (even: seg0 is a multiple of 4, W is odd)
+    const int pos = row_w - 1 - seg0;  // position inside the strip's segment (even: seg0 is a multiple of 4, the row's W is odd)
     if (pos < 0 || pos >= p.nseg * (16 / ES)) return;
     if (lane == 0) {
       const unsigned short v = *(const unsigned short *)((const uint8_t *)in + plane_off + (unsigned long long)(p.H - 1) * row_bytes +
-                                                         (unsigned long long)(p.Wp - 1) * 2u);
+                                                         (unsigned long long)(row_w - 1) * 2u);
       *(unsigned *)(lds + lds_base + slot * p.seg_bytes + pos * 2) = (unsigned)v;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

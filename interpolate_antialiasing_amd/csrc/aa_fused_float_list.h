@@ -2,7 +2,7 @@
 // defines F32_SET and / or F32_UNIT first.
 //
 // F32_SET(unit, element types, CS, widths): kernels of one unit.  Shrinking heights (fused_f32_nchw_kernel): CS is the channel stride
-// (1: planes, 3 / 4: fp32 channels_last), the widths are NQ.  Growing heights (fused_f32_nchw_up_kernel): CS is CPL, the widths are U;
+// (1: planes, 3 / 4: fp32 / fp16 / bf16 channels_last), the widths are NQ.  Growing heights (fused_f32_nchw_up_kernel): CS is CPL, the widths are U;
 // CPL * U lane masks fit the scalar registers (<= 20).  The plan takes the smallest width that holds the window.
 //
 // F32_UNIT(name, kernel, fast, MAXC or KR, G, NDMA): one translation unit, aa_fused_float_unit.hip compiled into aa_fused_float_<name>.o with
@@ -22,6 +22,8 @@ F32_SET(down, (AA_F32, AA_F16, AA_BF16), 1, (2, 3, 4, 5, 7, 9, 11))  // (9: 33 t
 F32_SET(down, (AA_F64),                  1, (2, 4, 6, 8, 11))
 F32_SET(down, (AA_F32),                  3, (2, 3, 4, 5, 7, 9))
 F32_SET(down, (AA_F32),                  4, (2, 3, 4, 5, 7, 9))
+F32_SET(nhwc16, (AA_F16, AA_BF16),       3, (2, 3, 4, 5, 7, 9))  // (a unit of its own: in `down` they would add 63 % to its kernels)
+F32_SET(nhwc16, (AA_F16, AA_BF16),       4, (2, 3, 4, 5, 7, 9))
 F32_SET(fast, (AA_F32, AA_F16, AA_BF16), 1, (2, 3, 4, 5, 7, 9, 11))  // (what it lacks, the tolerance mode runs exact)
 //      unit  element types           CPL U
 F32_SET(up,   (AA_F32, AA_F16, AA_BF16), 4, (2, 3, 4, 5))
@@ -33,6 +35,7 @@ F32_SET(up,   (AA_F32, AA_F16, AA_BF16), 1, (2, 3, 4, 5, 6, 8))
 //       name  kernel fast MAXC / KR     G       NDMA
 F32_UNIT(down, DOWN,  0,   (2, 3, 4, 6), (8, 4), (1, 2))
 F32_UNIT(fast, DOWN,  1,   (2, 3, 4, 6), (8, 4), (1, 2))
+F32_UNIT(nhwc16, DOWN, 0,  (2, 3, 4, 6), (8, 4), (1, 2))
 F32_UNIT(up,   UP,    0,   (2, 4, 6),    (8),    (1))
 
 #undef F32_SET

@@ -21,6 +21,10 @@ Differences, all additive:
     default ``uint8_mode="pil"`` is bit-exact with PIL.Image.resize (integer arithmetic, uint8 intermediate);
     ``uint8_mode="harness"`` reproduces test.py:52-58,72,75 (float(), fp32 op, clamp for bicubic, truncating byte());
   * the backward is the TRUE adjoint of the antialiased forward (the reference header's is the non-AA one, SURVEY §0.3);
+  * float16 / bfloat16 are differentiable too: the backward (gather form) takes 16-bit gradients and gives
+    ``backward(g.float()).to(g.dtype)`` bit for bit in 2-D and 1-D: fp32 arithmetic in the fp32 backward's own order, one rounding to
+    nearest even at the store (a 3-D backward rounds once per axis).  The registered autograd and interpolate_aa go through it;
+    ``atomic=True`` stays float32 / float64 (adds rounded to 16 bits one by one are a different and worse result);
   * ``precision="fast"`` (f32 / f16 / bf16): the opt-in tolerance mode — FMA accumulation, results within 1e-4 relative of the
     reference's (BASELINE.json's float bar) instead of bit-identical; the default ``"exact"`` rounds product and sum separately in
     the reference's tap order.  In fast mode a NaN / Inf pixel also reaches outputs whose 16-byte-aligned window holds it;
@@ -49,6 +53,7 @@ _plans = {}  # per call shape: (axis descriptors, workspace bytes); see _forward
 
 _DTYPE_IDS = {torch.uint8: _lib.U8, torch.float32: _lib.F32, torch.float64: _lib.F64, torch.float16: _lib.F16,
               torch.bfloat16: _lib.BF16}
+_GRAD_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)  # what the backward takes
 _DTYPE_NAMES = {torch.float16: "Half", torch.bfloat16: "BFloat16", torch.int8: "Char", torch.int16: "Short",
                 torch.int32: "Int", torch.int64: "Long", torch.bool: "Bool", torch.uint8: "Byte"}
 
@@ -293,9 +298,13 @@ def _backward(filter_id: int, name: str, grad_output: torch.Tensor, output_size:
         if grad_output.size(i) != full[i]:
             raise RuntimeError("Expected grad_output to have the same shape as output; "
                                f"output.size({i}) = {full[i]} but got grad_output.size({i}) = {grad_output.size(i)}")
-    if grad_output.dtype not in (torch.float32, torch.float64):
+    if grad_output.dtype not in _GRAD_DTYPES:
         raise NotImplementedError(f'"ti_upsample_bilinear2d_backward_cpu" not implemented for '
                                   f'\'{_DTYPE_NAMES.get(grad_output.dtype, str(grad_output.dtype))}\'')
+    if atomic and grad_output.dtype in (torch.float16, torch.bfloat16):
+        # adds that round to 16 bits one by one are a different and worse result than one rounding of the fp32 sum
+        raise NotImplementedError(f"{name}(): atomic=True takes float32 / float64 gradients only; a {grad_output.dtype} gradient has "
+                                  "the gather form (atomic=False), or cast it to float32 for the scatter")
     _require_gpu(grad_output, name)
     L = _lib.load()
     go, layout = _memory_format(grad_output)
@@ -304,7 +313,7 @@ def _backward(filter_id: int, name: str, grad_output: torch.Tensor, output_size:
     gi = torch.empty((n, c, h, w), dtype=go.dtype, device=dev, memory_format=mf)
     if n == 0:
         return gi
-    kind = _lib.TABLE_F32 if go.dtype == torch.float32 else _lib.TABLE_F64
+    kind = _table_kind(go.dtype, None)  # 16-bit gradients: fp32 arithmetic, one rounding at the store
     dt = _DTYPE_IDS[go.dtype]
     with torch.cuda.device(dev):
         th = tables.get_table(filter_id, kind, h, oh, align_corners, 0.0, dev)
@@ -417,7 +426,10 @@ def _backward_nd(filter_id: int, name: str, grad_output: torch.Tensor, output_si
                  align_corners: bool) -> torch.Tensor:
     """True adjoint of `_forward_nd`: one pass per axis with the transposed table of that axis (the 1-D adjoints act on
     different axes and commute).  The reference's backward header carries 1-D/3-D loops as well
-    (aa_interpolation_backward_impl.h:58-78,110-150), non-antialiased like its 2-D one."""
+    (aa_interpolation_backward_impl.h:58-78,110-150), non-antialiased like its 2-D one.
+    float16 / bfloat16 gradients: fp32 arithmetic in every pass, intermediates in the gradient's dtype, so a 3-D backward rounds
+    once per resampled axis, as the 16-bit N-d forward does; a 1-D backward is one pass and equals the fp32 backward of the
+    up-cast gradient, cast back, bit for bit."""
     nd = len(input_size) - 2
     if nd not in (1, 2, 3) or len(output_size) != nd:
         raise RuntimeError(f"It is expected input_size equals to 3, 4 or 5 and output_size to match, but got {list(input_size)} "
@@ -428,14 +440,14 @@ def _backward_nd(filter_id: int, name: str, grad_output: torch.Tensor, output_si
     if list(grad_output.shape) != full:
         raise RuntimeError(f"Expected grad_output to have the same shape as output; output.shape = {full} but got "
                            f"grad_output.shape = {list(grad_output.shape)}")
-    if grad_output.dtype not in (torch.float32, torch.float64):
+    if grad_output.dtype not in _GRAD_DTYPES:
         raise NotImplementedError(f'"ti_upsample_bilinear2d_backward_cpu" not implemented for '
                                   f'\'{_DTYPE_NAMES.get(grad_output.dtype, str(grad_output.dtype))}\'')
     _require_gpu(grad_output, name)
     L = _lib.load()
     g = grad_output.contiguous()
     dev = g.device
-    kind = _lib.TABLE_F32 if g.dtype == torch.float32 else _lib.TABLE_F64
+    kind = _table_kind(g.dtype, None)
     dt = _DTYPE_IDS[g.dtype]
     if g.numel() == 0:
         return torch.zeros([int(v) for v in input_size], dtype=g.dtype, device=dev)
@@ -516,7 +528,8 @@ def cubic_forward(input: torch.Tensor, output_size: Sequence[int], align_corners
 
 def linear_backward(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],
                     align_corners: bool = False, *, atomic: bool = False) -> torch.Tensor:
-    """Backward of linear_forward (s2.2/extension_interpolate.cpp:16-24,50) — the true AA adjoint."""
+    """Backward of linear_forward (s2.2/extension_interpolate.cpp:16-24,50) — the true AA adjoint.  float32 / float64 gradients, and
+    float16 / bfloat16 ones in the gather form (atomic=False): backward(g.float()).to(g.dtype) bit for bit."""
     return _backward(_lib.FILTER_LINEAR, "linear_backward", grad_output, output_size, input_size, align_corners, atomic)
 
 
@@ -612,7 +625,8 @@ def _register_torch_ops() -> None:
         lib.impl(name, lambda grad_output, output_size, input_size, align_corners=False: torch.empty(
             tuple(input_size), dtype=grad_output.dtype, device=grad_output.device, memory_format=_mf(grad_output)), "Meta")
 
-    # autograd: d(forward)/d(input) is the matching backward op (true adjoint)
+    # autograd: d(forward)/d(input) is the matching backward op (true adjoint); differentiable for float32 / float64 and for
+    # float16 / bfloat16 (the gradient arrives in the input's dtype and the backward ops take it as it is)
     def _make_autograd(fwd_name, bwd_name):
         def setup_context(ctx, inputs, output):
             input, output_size, align_corners = inputs

@@ -12,7 +12,8 @@ _MODES = {"bilinear": "linear_forward", "linear": "linear_forward", "bicubic": "
 
 def interpolate_aa(input: torch.Tensor, size: Sequence[int], mode: str = "bilinear", align_corners: bool = False, *,
                    alpha: bool = False) -> torch.Tensor:
-    """Antialiased resize of a 4-D GPU tensor to ``size`` = (H, W); differentiable for float dtypes.
+    """Antialiased resize of a 4-D GPU tensor to ``size`` = (H, W); differentiable for float32 / float64 and for float16 / bfloat16
+    (the gradient has the input's dtype and memory format: fp32 arithmetic, one rounding to nearest even at the store).
     ``mode``: bilinear | bicubic | nearest (= box filter, as in the reference) | lanczos | hamming (Pillow's filters of those names).
     3-D (NCL) and 5-D (NCDHW) inputs take the N-d front-ends (forward only): ``mode`` linear/bilinear/trilinear | bicubic | nearest |
     lanczos | hamming.

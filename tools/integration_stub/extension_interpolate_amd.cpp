@@ -117,7 +117,9 @@ torch::Tensor interpolate_linear_backward(const torch::Tensor &grad_output, at::
   const bool cl = !grad_output.is_contiguous() && grad_output.is_contiguous(at::MemoryFormat::ChannelsLast);
   const auto go = cl ? grad_output : grad_output.contiguous();
   const int dtype = dtype_of(go);
-  TORCH_CHECK_NOT_IMPLEMENTED(dtype == AA_F32 || dtype == AA_F64, "backward takes float or double gradients");
+  // half / bfloat16 gradients: fp32 arithmetic with AA_TABLE_F32 tables, one rounding at the store (gather form)
+  TORCH_CHECK_NOT_IMPLEMENTED(dtype == AA_F32 || dtype == AA_F64 || dtype == AA_F16 || dtype == AA_BF16,
+                              "backward takes float, double, half or bfloat16 gradients");
   const int kind = dtype == AA_F64 ? AA_TABLE_F64 : AA_TABLE_F32;
   hipStream_t stream = c10::hip::getCurrentHIPStream(go.device().index()).stream();
   auto gi = torch::empty({N, C, H, W}, go.options().memory_format(cl ? at::MemoryFormat::ChannelsLast : at::MemoryFormat::Contiguous));

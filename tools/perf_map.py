@@ -116,6 +116,8 @@ for (tag, (h, w), (oh, ow)) in SHAPES:
         ("f32 nchw", u8.float().contiguous(), {}, 4),
         ("f32 nhwc", u8.float().contiguous(memory_format=torch.channels_last), {}, 4),
         ("f16 nchw", u8.half().contiguous(), {}, 2),
+        ("f16 nhwc", u8.half().contiguous(memory_format=torch.channels_last), {}, 2),
+        ("bf16 nhwc", u8.bfloat16().contiguous(memory_format=torch.channels_last), {}, 2),
     ]
     if args.shapes == "filters":
         cases.insert(3, ("u8 nhwc->f32", u8, dict(out_dtype=torch.float32, out_format="nchw"), 1))
