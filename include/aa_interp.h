@@ -119,7 +119,8 @@ typedef struct aa_axis {
                             their staged row segments from it) and the generic two-launch path runs */
   int32_t span4p1;       /* from the table header; 0 = unknown */
   int32_t gather_off;    /* from the table header; 0 = no gather section */
-  int32_t reserved[2];
+  int32_t reserved[2];   /* reserved[0] = 1 for a table from aa_table_build_box: in_size is the hull's length, and equal sizes in and out
+                            do not mean "nothing to do"; 0 otherwise.  reserved[1] = 0 */
 } aa_axis;
 
 /* Version / diagnostics. */
@@ -162,6 +163,25 @@ int aa_table_build2(int filter, int kind, int align_corners, int64_t in_a, int64
 /* aa_table_query for the two tables of a call (H and W axis) with ONE synchronisation: a shape never seen before costs two table builds, and a
  * data pipeline of random crops meets a new shape on every call. */
 int aa_table_query2(const void *table_a_dev, const void *table_b_dev, aa_table_header *host_a, aa_table_header *host_b, aa_stream_t stream);
+
+/* ---- box tables: Pillow's Image.resize(box=...) ------------------------------------------------------------------------------------
+ * Pillow's precompute_coeffs(inSize, in0, in1, outSize) resamples the sub-pixel source interval [in0, in1) of an axis: scale =
+ * (float)(in1 - in0) / out (Pillow's C takes the box as floats: pass float values in the doubles), centre of output i = in0 + (i + 0.5) * scale, windows clipped to the whole axis [0, inSize).  The windows of all
+ * outputs together cover the HULL [origin, origin + hull) = [xmin of output 0, end of the last output's window); the caller computes it
+ * (the same double arithmetic) and hands the resample calls the hull as a view of the image (aa_resample_fwd_strided; rows and columns
+ * outside the hull are never read).  A box table is an ordinary packed table whose in_size is `hull` and whose xmin[] are relative to
+ * `origin`; centres and weights are computed from the UNSHIFTED in0, and clipping to the hull equals clipping to the image because the
+ * hull is exactly the extreme windows.  AA_TABLE_PIL only (the reference has no box): other kinds AA_ERR_BAD_DTYPE.  in0 = 0, in1 =
+ * inSize, origin = 0, hull = inSize gives aa_table_build's table bit for bit.  Set aa_axis.reserved[0] = 1 for such a table. */
+/* ksize of a box table (host arithmetic), or a negative aa_status.  hull: the table's in_size. */
+int aa_table_ksize_box(int filter, int kind, int64_t hull, int64_t out_size, double in0, double in1);
+/* Bytes aa_table_build_box needs for one such table. */
+size_t aa_table_build_bytes_box(int filter, int kind, int64_t hull, int64_t out_size, double in0, double in1);
+/* Build the two box tables of a call (a: the H axis, b: the W axis; an axis without a box passes in0 = 0, in1 = inSize, origin = 0)
+ * as ONE launch (very large tables — a hull beyond 32768 or an output beyond 16384 — one after the other, as aa_table_build2 does); aa_table_query2 then reads both headers with one synchronisation.  Asynchronous on `stream`. */
+int aa_table_build_box(int filter, int kind, int64_t origin_a, int64_t hull_a, int64_t out_a, double in0_a, double in1_a, void *table_a_dev,
+                       size_t bytes_a, int64_t origin_b, int64_t hull_b, int64_t out_b, double in0_b, double in1_b, void *table_b_dev,
+                       size_t bytes_b, aa_stream_t stream);
 
 /* Workspace (bytes) the forward needs for this problem; 0 when a fused single-launch path applies.  The answer depends on the
  * shape and the tables only, never on the pointers: which kernel runs is decided from the same facts, and a uint8 view that starts
@@ -278,6 +298,23 @@ size_t aa_workspace_bytes_bwd(int dtype, int layout, int64_t N, int64_t C, int64
  * for aa_resample_fwd except u8 with AA_TABLE_F32 (the harness mode needs a float intermediate). */
 int aa_resample_axis_fwd(const void *in_dev, void *out_dev, int dtype, int64_t outer, int64_t in_size, int64_t inner,
                          const aa_axis *ax, aa_stream_t stream);
+
+/* Pillow's Image.reduce for 8-bit channels (ImagingReduce): every output pixel is the rounded mean of an fx x fy block of input pixels.
+ *   in_dev  [N,C,H,W] uint8 in `layout`; in_strides = the view's strides in ELEMENTS for (N, C, H, W) under the rules of
+ *           aa_resample_fwd_strided (rows of consecutive elements, any row pitch, planes uniformly spaced), or NULL for a dense tensor;
+ *   box     {x0, y0, x1, y1}, an integer rectangle inside the image (Pillow's order: x first); NULL = the whole image;
+ *   out_dev [N,C,ceil((y1-y0)/fy),ceil((x1-x0)/fx)] uint8, dense, in `layout`.
+ * Output (Y, X) covers the block that starts at (y0 + Y*fy, x0 + X*fx), clipped to the box: the last row and column of blocks, and the
+ * corner, may be partial.  With n the pixels in the block and ss their sum: out = ((ss + n/2) * mult(n)) >> 24 in unsigned 32-bit
+ * arithmetic, mult(n) = (uint32)(4294967296.0f / (float)(256 * n)), a float32 division made on the host (a launch has at most four n).
+ * fx * fy <= 65536, AA_ERR_BAD_SHAPE beyond; C is 1..4 for AA_NHWC, anything for AA_NCHW.  fx = fy = 1 copies the box.  One launch, no
+ * workspace, asynchronous on `stream`.  Added without an ABI version change (additive). */
+int aa_reduce_u8(const void *in_dev, void *out_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const int64_t *in_strides,
+                 const int64_t *box, int fx, int fy, aa_stream_t stream);
+/* The two conversions Image.reduce and Image.resize put around an RGBA / LA image (see AA_FLAG_PREMUL_ALPHA), on dense uint8 tensors
+ * with C == 2 or 4, alpha last: straight -> premultiplied from src_dev into dst_dev, and premultiplied -> straight in place. */
+int aa_premultiply_u8(const void *src_dev, void *dst_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, aa_stream_t stream);
+int aa_unpremultiply_u8(void *img_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, aa_stream_t stream);
 
 /* Device-to-device copy of `bytes` bytes with 16-byte vector loads/stores, enqueued on `stream`: the probe bench.py times
  * on the box to report the attainable HBM copy ceiling next to the 8 TB/s spec peak.  form 0: one element per

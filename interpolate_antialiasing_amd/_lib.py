@@ -33,7 +33,8 @@ EXPORTS = (
     "aa_table_transposed_ksize", "aa_table_transpose", "aa_table_query", "aa_table_query2", "aa_table_build2", "aa_workspace_bytes", "aa_resample_fwd",
     "aa_resample_bwd", "aa_resample_bwd_atomic", "aa_workspace_bytes_bwd", "aa_resample_axis_fwd", "aa_set_fused",
     "aa_last_variant", "aa_probe_copy", "aa_workspace_bytes_u8_to_f32", "aa_resample_fwd_u8_to_f32", "aa_set_store_form", "aa_set_plane_groups", "aa_resample_fwd_ex", "aa_resample_fwd_strided",
-    "aa_workspace_bytes_ex",
+    "aa_workspace_bytes_ex", "aa_table_ksize_box", "aa_table_build_bytes_box", "aa_table_build_box", "aa_reduce_u8", "aa_premultiply_u8",
+    "aa_unpremultiply_u8",
 )
 
 
@@ -129,6 +130,18 @@ def load() -> ctypes.CDLL:
     L.aa_resample_fwd_u8_to_f32.restype = i32
     L.aa_probe_copy.argtypes = [vp, vp, sz, i32, vp]
     L.aa_probe_copy.restype = i32
+    L.aa_table_ksize_box.argtypes = [i32, i32, i64, i64, dbl, dbl]
+    L.aa_table_ksize_box.restype = i32
+    L.aa_table_build_bytes_box.argtypes = [i32, i32, i64, i64, dbl, dbl]
+    L.aa_table_build_bytes_box.restype = sz
+    L.aa_table_build_box.argtypes = [i32, i32, i64, i64, i64, dbl, dbl, vp, sz, i64, i64, i64, dbl, dbl, vp, sz, vp]
+    L.aa_table_build_box.restype = i32
+    L.aa_reduce_u8.argtypes = [vp, vp, i32, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), i32, i32, vp]
+    L.aa_reduce_u8.restype = i32
+    L.aa_premultiply_u8.argtypes = [vp, vp, i32, i64, i64, i64, i64, vp]
+    L.aa_premultiply_u8.restype = i32
+    L.aa_unpremultiply_u8.argtypes = [vp, i32, i64, i64, i64, i64, vp]
+    L.aa_unpremultiply_u8.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

@@ -1,0 +1,144 @@
+"""Host arithmetic of Pillow's ``Image.resize(size, resample, box=..., reducing_gap=...)`` and ``Image.reduce``: plain Python doubles and
+ints, no torch, no GPU.  Everything here restates Pillow's own Python (Image.resize, Image._get_safe_box) or the double arithmetic of
+its C (precompute_coeffs), so that the device code only ever sees integers and the two doubles in0 / in1.
+
+ORDER OF COORDINATES: ``box`` and ``factor`` are Pillow's — x first: box = (x0, y0, x1, y1), factor = (fx, fy) — while ``output_size``
+everywhere in this package is (H, W).
+"""
+from __future__ import annotations
+
+import math
+import struct
+from typing import Optional, Sequence, Tuple
+
+# Pillow's filter supports (Resample.c's filter structs; Image._filters_support) by the package's filter names
+SUPPORT = {"box": 0.5, "nearest": 0.5, "linear": 1.0, "bilinear": 1.0, "hamming": 1.0, "cubic": 2.0, "bicubic": 2.0, "lanczos": 3.0}
+MAX_REDUCE_BLOCK = 65536  # fx * fy the reduce kernel's 32-bit sums hold
+
+
+def f32(v: float) -> float:
+    """v rounded to float32: Pillow's C takes the resize box as four floats."""
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+def box_f32(box: Sequence[float]) -> Tuple[float, float, float, float]:
+    """The box as Pillow's C resize sees it.  (The Python above it — the reducing_gap logic — works on the doubles.)  A box narrower
+    than the floats can tell apart is empty there, and is refused here with Pillow's words."""
+    x0, y0, x1, y1 = (f32(v) for v in box)
+    if x1 - x0 <= 0 or y1 - y0 <= 0:
+        raise ValueError("box can't be empty")
+    return x0, y0, x1, y1
+
+
+def check_box(box: Sequence[float], width: int, height: int) -> Tuple[float, float, float, float]:
+    """Pillow's checks of a resize / reduce box (x0, y0, x1, y1), with its wording."""
+    if len(box) != 4:
+        raise ValueError("box must be (x0, y0, x1, y1)")
+    x0, y0, x1, y1 = (float(v) for v in box)
+    if not all(math.isfinite(v) for v in (x0, y0, x1, y1)):
+        raise ValueError("box must hold finite numbers")
+    if x0 < 0 or y0 < 0:
+        raise ValueError("box offset can't be negative")
+    if x1 > width or y1 > height:
+        raise ValueError("box can't exceed original image size")
+    if x1 - x0 <= 0 or y1 - y0 <= 0:
+        raise ValueError("box can't be empty")
+    return x0, y0, x1, y1
+
+
+def check_int_box(box: Optional[Sequence[int]], width: int, height: int) -> Tuple[int, int, int, int]:
+    """The integer box of Image.reduce; None = the whole image."""
+    if box is None:
+        return 0, 0, int(width), int(height)
+    if len(box) != 4 or any(int(v) != v for v in box):
+        raise ValueError("reduce box must be four integers (x0, y0, x1, y1)")
+    x0, y0, x1, y1 = check_box(box, width, height)
+    return int(x0), int(y0), int(x1), int(y1)
+
+
+def check_factor(factor) -> Tuple[int, int]:
+    """Image.reduce's factor: an int or (fx, fy), each at least 1; fx * fy within what the kernel's sums hold."""
+    if isinstance(factor, (tuple, list)):
+        if len(factor) != 2:
+            raise ValueError("factor must be an int or (fx, fy)")
+        fx, fy = factor
+    else:
+        fx = fy = factor
+    if int(fx) != fx or int(fy) != fy or fx < 1 or fy < 1:
+        raise ValueError("the factor must be greater than 0")
+    fx, fy = int(fx), int(fy)
+    if fx * fy > MAX_REDUCE_BLOCK:
+        raise ValueError(f"reduce: fx * fy = {fx * fy} is beyond the supported {MAX_REDUCE_BLOCK}")
+    return fx, fy
+
+
+def reduced_size(box: Sequence[int], factor: Tuple[int, int]) -> Tuple[int, int]:
+    """(width, height) of Image.reduce's result."""
+    x0, y0, x1, y1 = box
+    return (x1 - x0 + factor[0] - 1) // factor[0], (y1 - y0 + factor[1] - 1) // factor[1]
+
+
+def check_reducing_gap(reducing_gap) -> Optional[float]:
+    if reducing_gap is None:
+        return None
+    if reducing_gap < 1.0:
+        raise ValueError("reducing_gap must be 1.0 or greater")
+    return float(reducing_gap)
+
+
+def reducing_factors(box: Sequence[float], out_w: int, out_h: int, reducing_gap: float) -> Tuple[int, int]:
+    """Image.resize: the integer factors (fx, fy) of the reduce that goes first."""
+    fx = int((box[2] - box[0]) / out_w / reducing_gap) or 1
+    fy = int((box[3] - box[1]) / out_h / reducing_gap) or 1
+    return fx, fy
+
+
+def safe_box(width: int, height: int, out_w: int, out_h: int, filter_name: str, box: Sequence[float]) -> Tuple[int, int, int, int]:
+    """Image._get_safe_box: the integer box the reduce must cover so that the filter that follows still sees every pixel it needs."""
+    s = SUPPORT[filter_name] - 0.5
+    sx = s * ((box[2] - box[0]) / out_w)
+    sy = s * ((box[3] - box[1]) / out_h)
+    return (max(0, int(box[0] - sx)), max(0, int(box[1] - sy)), min(width, math.ceil(box[2] + sx)), min(height, math.ceil(box[3] + sy)))
+
+
+def shifted_box(box: Sequence[float], rb: Sequence[int], factor: Tuple[int, int]) -> Tuple[float, float, float, float]:
+    """Image.resize: the box in the coordinates of the reduced image."""
+    fx, fy = factor
+    return (box[0] - rb[0]) / fx, (box[1] - rb[1]) / fy, (box[2] - rb[0]) / fx, (box[3] - rb[1]) / fy
+
+
+def reducing_plan(width: int, height: int, out_w: int, out_h: int, filter_name: str, box: Sequence[float], reducing_gap: float):
+    """-> None when both factors are 1 (the plain resize), else (factor, reduce box, the box for the resize of the reduced image)."""
+    factor = reducing_factors(box, out_w, out_h, reducing_gap)
+    if factor[0] <= 1 and factor[1] <= 1:
+        return None
+    rb = safe_box(width, height, out_w, out_h, filter_name, box)
+    return factor, rb, shifted_box(box, rb, factor)
+
+
+def axis_hull(in_size: int, out_size: int, in0: float, in1: float, filter_name: str) -> Tuple[int, int]:
+    """[o, e): what the windows of precompute_coeffs(in_size, in0, in1, out_size) cover together — the first output's xmin and the end of
+    the last output's window, both clipped to the axis (window starts and ends are non-decreasing in the output index).  The same
+    double operations, in the same order, as the C; in0 and in1 hold float32 values (box_f32), and the scale is their FLOAT difference
+    over the output size."""
+    scale = f32(in1 - in0) / out_size
+    filterscale = 1.0 if scale < 1.0 else scale
+    support = SUPPORT[filter_name] * filterscale
+    first = in0 + (0 + 0.5) * scale
+    last = in0 + ((out_size - 1) + 0.5) * scale
+    o = int(first - support + 0.5)
+    if o < 0:
+        o = 0
+    e = int(last + support + 0.5)
+    if e > in_size:
+        e = in_size
+    return o, e
+
+
+def axis_is_full(in_size: int, in0: float, in1: float) -> bool:
+    return in0 == 0 and in1 == in_size
+
+
+def is_plain_crop(box: Sequence[float], out_w: int, out_h: int) -> bool:
+    """Pillow's C resize: integer offsets and a box of exactly the output's size is a crop, not a filter."""
+    return box[0] == int(box[0]) and box[1] == int(box[1]) and box[2] - box[0] == out_w and box[3] - box[1] == out_h

@@ -4,7 +4,9 @@
 #include <math.h>
 #include <string.h>
 
+#include "aa_box.h"
 #include "aa_plan.h"
+#include "aa_reduce.h"
 
 int g_aa_store_form = -1;  // (aa_common.h; read by aa_fused_float.hip)
 int g_aa_plane_groups = 1;  // (aa_common.h; read by aa_fused_u8_v3.hip)
@@ -106,7 +108,9 @@ FwdPlan plan_fwd(const AAProblem &q) {
   if (q.N == 0) {  // empty batch is allowed (s2.2:747-750)
     pl.route = FWD_EMPTY;
   } else if (q.alpha) {
-    if (q.oH == q.H && q.oW == q.W) {  // Pillow's resize returns a copy: no lossy round trip through premultiplied values
+    // Pillow's resize returns a copy: no lossy round trip through premultiplied values.  (A box table's in_size is its hull: equal
+    // sizes say nothing there, and the caller decides what a full box of the same size is)
+    if (q.oH == q.H && q.oW == q.W && !q.ah.reserved[0] && !q.aw.reserved[0]) {
       pl.route = FWD_ALPHA_COPY;
     } else if (mode == 1 && aa_v3_plan(q, false, &pl.v3)) {
       pl.route = FWD_V3;
@@ -413,6 +417,101 @@ int aa_table_transpose(const void *table_dev, void *tr_table_dev, size_t tr_tabl
   rc = aa_table_query(tr_table_dev, &th, stream);  // table-build time only
   if (rc != AA_OK) return rc;
   return th.max_taps > tr_ksize ? AA_ERR_KSIZE : AA_OK;
+}
+
+// ---- box tables (Image.resize(box=...)) ------------------------------------------------------------------------------------------------
+int aa_table_ksize_box(int filter, int kind, int64_t hull, int64_t out_size, double in0, double in1) {
+  if (interp_size_of(filter) < 0) return AA_ERR_BAD_FILTER;
+  if (!valid_kind(kind)) return AA_ERR_BAD_DTYPE;
+  if (kind != AA_TABLE_PIL) return AA_ERR_BAD_DTYPE;  // the reference has no box
+  if (hull <= 0 || out_size <= 0 || hull > INT32_MAX / 4 || out_size > INT32_MAX / 4) return AA_ERR_BAD_SHAPE;
+  if (!(in0 >= 0.0) || !(in1 > in0) || !(in1 <= (double)(INT32_MAX / 4))) return AA_ERR_BAD_SHAPE;
+  const int k = ksize_for(filter, kind, (double)(float)(in1 - in0) / (double)out_size);  // (Pillow's C: a float difference)
+  if (k > AA_MAX_KSIZE) return AA_ERR_KSIZE;
+  return k;
+}
+
+size_t aa_table_build_bytes_box(int filter, int kind, int64_t hull, int64_t out_size, double in0, double in1) {
+  const int k = aa_table_ksize_box(filter, kind, hull, out_size, in0, in1);
+  if (k < 0) return 0;
+  return aa_table_total_bytes(kind, out_size, k) + aa_table_scatter_bytes(kind, hull, scatter_ksize_for(filter, kind, hull, out_size));
+}
+
+int aa_table_build_box(int filter, int kind, int64_t origin_a, int64_t hull_a, int64_t out_a, double in0_a, double in1_a, void *table_a_dev,
+                       size_t bytes_a, int64_t origin_b, int64_t hull_b, int64_t out_b, double in0_b, double in1_b, void *table_b_dev,
+                       size_t bytes_b, aa_stream_t stream) {
+  const int ka = aa_table_ksize_box(filter, kind, hull_a, out_a, in0_a, in1_a);
+  if (ka < 0) return ka;
+  const int kb = aa_table_ksize_box(filter, kind, hull_b, out_b, in0_b, in1_b);
+  if (kb < 0) return kb;
+  if (origin_a < 0 || origin_b < 0 || origin_a > INT32_MAX / 4 || origin_b > INT32_MAX / 4) return AA_ERR_BAD_SHAPE;
+  if (!table_a_dev || !table_b_dev) return AA_ERR_NULL;
+  const int ska = scatter_ksize_for(filter, kind, hull_a, out_a), skb = scatter_ksize_for(filter, kind, hull_b, out_b);
+  if (bytes_a < aa_table_total_bytes(kind, out_a, ka) + aa_table_scatter_bytes(kind, hull_a, ska)) return AA_ERR_WORKSPACE;
+  if (bytes_b < aa_table_total_bytes(kind, out_b, kb) + aa_table_scatter_bytes(kind, hull_b, skb)) return AA_ERR_WORKSPACE;
+  const AABoxAxis a = {origin_a, hull_a, out_a, in0_a, in1_a, ka, ska, table_a_dev};
+  const AABoxAxis b = {origin_b, hull_b, out_b, in0_b, in1_b, kb, skb, table_b_dev};
+  return aa_launch_table_build_box_pair(filter, a, b, (hipStream_t)stream);
+}
+
+// ---- Image.reduce ------------------------------------------------------------------------------------------------------------------------
+int aa_reduce_u8(const void *in_dev, void *out_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const int64_t *in_strides,
+                 const int64_t *box, int fx, int fy, aa_stream_t stream) {
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (N < 0 || C <= 0 || H <= 0 || W <= 0 || H > INT32_MAX / 4 || W > INT32_MAX / 4) return AA_ERR_BAD_SHAPE;
+  if (fx < 1 || fy < 1 || (int64_t)fx * fy > 65536) return AA_ERR_BAD_SHAPE;
+  if (layout == AA_NHWC && C > 4) return AA_ERR_BAD_SHAPE;
+  const int64_t x0 = box ? box[0] : 0, y0 = box ? box[1] : 0, x1 = box ? box[2] : W, y1 = box ? box[3] : H;
+  if (x0 < 0 || y0 < 0 || x1 > W || y1 > H || x1 <= x0 || y1 <= y0) return AA_ERR_BAD_SHAPE;
+  if (N == 0) return AA_OK;
+  if (!in_dev || !out_dev) return AA_ERR_NULL;
+  int64_t sN, sC, sH, sW;
+  if (in_strides) {
+    sN = in_strides[0]; sC = in_strides[1]; sH = in_strides[2]; sW = in_strides[3];
+  } else if (layout == AA_NCHW) {
+    sN = C * H * W; sC = H * W; sH = W; sW = 1;
+  } else {
+    sN = H * W * C; sC = 1; sH = W * C; sW = C;
+  }
+  AAReduceJob job;
+  if (layout == AA_NCHW) {  // (the rules of aa_resample_fwd_strided)
+    if (sW != 1 || sH < W || sC < 0 || sN < 0 || (C > 1 && N > 1 && sN != C * sC)) return AA_ERR_STRIDES;
+    job.images = N * C;
+    job.C = 1;
+    job.row_pitch = sH;
+    job.img_pitch = C > 1 ? sC : sN;
+  } else {
+    if (sC != 1 || sW != C || sH < W * C || sN < 0) return AA_ERR_STRIDES;
+    job.images = N;
+    job.C = (int)C;
+    job.row_pitch = sH;
+    job.img_pitch = sN;
+  }
+  if (job.img_pitch == 0 && job.images > 1) return AA_ERR_STRIDES;  // (a broadcast batch: make it dense)
+  job.in = (const uint8_t *)in_dev + y0 * job.row_pitch + x0 * job.C;
+  job.out = (uint8_t *)out_dev;
+  job.bw = (int)(x1 - x0); job.bh = (int)(y1 - y0);
+  job.fx = fx; job.fy = fy;
+  job.stream = (hipStream_t)stream;
+  return aa_launch_reduce_u8(job);
+}
+
+int aa_premultiply_u8(const void *src_dev, void *dst_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, aa_stream_t stream) {
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (N < 0 || H <= 0 || W <= 0) return AA_ERR_BAD_SHAPE;
+  if (C != 2 && C != 4) return AA_ERR_BAD_DTYPE;
+  if (N == 0) return AA_OK;
+  if (!src_dev || !dst_dev) return AA_ERR_NULL;
+  return aa_launch_premul_u8(src_dev, dst_dev, layout, N, C, H, W, (hipStream_t)stream);
+}
+
+int aa_unpremultiply_u8(void *img_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, aa_stream_t stream) {
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (N < 0 || H <= 0 || W <= 0) return AA_ERR_BAD_SHAPE;
+  if (C != 2 && C != 4) return AA_ERR_BAD_DTYPE;
+  if (N == 0) return AA_OK;
+  if (!img_dev) return AA_ERR_NULL;
+  return aa_launch_unpremul_u8(img_dev, layout, N, C, H, W, (hipStream_t)stream);
 }
 
 size_t aa_workspace_bytes_ex(int dtype, int layout, int64_t N, int64_t C, int64_t H, int64_t W, int64_t oH, int64_t oW,

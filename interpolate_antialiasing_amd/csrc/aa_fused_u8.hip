@@ -279,6 +279,8 @@ bool aa_v1_plan(const AAProblem &q, V1Plan *pl) {
   const aa_axis &ah = q.ah, &aw = q.aw;
   if (q.dtype != AA_U8 || q.layout != AA_NHWC || ah.kind != AA_TABLE_PIL || aw.kind != AA_TABLE_PIL) return false;
   if (q.C != 1 && q.C != 3 && q.C != 4) return false;
+  // box tables (aa_table_build_box): the ring depth below infers the vertical scale from H / oH, and a hull says little about the scale
+  if (ah.reserved[0] || aw.reserved[0]) return false;
   const int taps_w = aw.max_taps > 0 ? aw.max_taps : aw.ksize;
   const int tw = round_tw(taps_w);
   if (tw == 0 || q.W < tw) return false;

@@ -10,6 +10,7 @@
 // one pixel (SURVEY §7 "Weight parity").  Float divisions are evaluated in double and narrowed, which is the
 // correctly rounded float quotient (53 >= 2*24+2 bits), so the result does not depend on the fp32 division mode.
 
+#include "aa_box.h"
 #include "aa_common.h"
 
 namespace {
@@ -153,24 +154,29 @@ __global__ void table_build_f64(int filter, int in_size, int out_size, int ksize
 
 // Pillow: precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c, cited by URL in the reference:
 // README.md:18,40; s2.2/aa_interpolation_impl.h:289-291).  double coefficients -> 22-bit fixed point int32.
-__device__ void table_build_pil_one(int i, int filter, int in_size, int out_size, int ksize, char *table) {
+// BoxArgs (Image.resize(box=...), precompute_coeffs's in0 / in1): the source interval of the axis and the origin of the hull the table
+// indexes.  Pillow's C takes the box as FLOATS: in0 and in1 hold float values, and the scale is their float difference over the output
+// size.  on == 0 (no box: in0 = 0, origin = 0): every expression below is the one it was before boxes existed (0.0 + x is exact).
+struct BoxArgs { double in0, in1; int origin, on; };
+__device__ void table_build_pil_one(int i, int filter, int in_size, int out_size, int ksize, char *table, const BoxArgs &bx) {
   int32_t *xmin_p = (int32_t *)(table + aa_table_xmin_off());
   int32_t *xsize_p = (int32_t *)(table + aa_table_xsize_off(out_size));
   int32_t *kk = (int32_t *)(table + aa_table_w_off(out_size)) + (size_t)i * ksize;
   int32_t *max_taps = &((aa_table_header *)table)->max_taps;
 
-  double scale = (double)in_size / (double)out_size;
+  double scale = bx.on ? (double)(float)(bx.in1 - bx.in0) / (double)out_size : (double)in_size / (double)out_size;
   double filterscale = scale < 1.0 ? 1.0 : scale;
   const double fsupport = aa_filter_info(filter).support;
   const double support = fsupport * filterscale;
-  const double center = 0.0 + ((double)i + 0.5) * scale;
+  const double center = bx.in0 + ((double)i + 0.5) * scale;
   const double ss = 1.0 / filterscale;
+  // windows clip to the hull [origin, origin + in_size): the hull is exactly the extreme windows clipped to the image, so this is Pillow's clip
   int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
+  if (xmin < bx.origin) xmin = bx.origin;
   int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
+  if (xmax > bx.origin + in_size) xmax = bx.origin + in_size;
   xmax -= xmin;
-  xmin_p[i] = xmin;
+  xmin_p[i] = xmin - bx.origin;  // (the weights below are computed from the unshifted xmin and centre)
   xsize_p[i] = xmax;
   // two sweeps (sum, then normalise + quantise) so no per-thread array is needed
   double ww = 0.0;
@@ -184,9 +190,9 @@ __device__ void table_build_pil_one(int i, int filter, int in_size, int out_size
   for (; x < ksize; x++) kk[x] = 0;
   atomicMax(max_taps, (int32_t)(xmax > 1 ? xmax : 1));
 }
-__global__ void table_build_pil(int filter, int in_size, int out_size, int ksize, char *table) {
+__global__ void table_build_pil(int filter, int in_size, int out_size, int ksize, char *table, BoxArgs bx) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < out_size) table_build_pil_one(i, filter, in_size, out_size, ksize, table);
+  if (i < out_size) table_build_pil_one(i, filter, in_size, out_size, ksize, table, bx);
 }
 
 // header.span64p1 = 1 + max_i (xmin[min(i+63, out-1)] - xmin[i]): the fused kernels stage, per strip of <= 64 consecutive
@@ -320,27 +326,30 @@ __global__ void table_scatter_kernel(const char *fwd, int32_t *rec_all, int32_t 
 // above, run by ONE workgroup with a barrier between them.  A table is a few thousand entries of a few dozen operations: the five launches
 // cost five launch latencies (a cold call = a shape never seen: two tables = ~0.1 ms of them; a data pipeline of random crops meets a
 // new shape every call).  Same device functions, same results.
-struct TableJob { aa_table_header h; int in_size, out_size, ksize; double scale; char *table; };
+struct TableJob { aa_table_header h; int in_size, out_size, ksize; double scale; char *table; BoxArgs bx; };
 template <int KIND>
-__device__ void table_build_body(const aa_table_header &h, int filter, int in_size, int out_size, int ksize, double scale, char *table);
+__device__ void table_build_body(const aa_table_header &h, int filter, int in_size, int out_size, int ksize, double scale, char *table,
+                                 const BoxArgs &bx);
 template <int KIND>
-__global__ void __launch_bounds__(1024) table_build_all(aa_table_header h, int filter, int in_size, int out_size, int ksize, double scale, char *table) {
-  table_build_body<KIND>(h, filter, in_size, out_size, ksize, scale, table);
+__global__ void __launch_bounds__(1024) table_build_all(aa_table_header h, int filter, int in_size, int out_size, int ksize, double scale, char *table,
+                                                        BoxArgs bx) {
+  table_build_body<KIND>(h, filter, in_size, out_size, ksize, scale, table, bx);
 }
 // ... and the two tables of a call (H and W axis) as the two workgroups of one launch
 template <int KIND>
 __global__ void __launch_bounds__(1024) table_build_pair(TableJob a, TableJob b, int filter) {
   const TableJob &j = blockIdx.x == 0 ? a : b;
-  table_build_body<KIND>(j.h, filter, j.in_size, j.out_size, j.ksize, j.scale, j.table);
+  table_build_body<KIND>(j.h, filter, j.in_size, j.out_size, j.ksize, j.scale, j.table, j.bx);
 }
 template <int KIND>
-__device__ void table_build_body(const aa_table_header &h, int filter, int in_size, int out_size, int ksize, double scale, char *table) {
+__device__ void table_build_body(const aa_table_header &h, int filter, int in_size, int out_size, int ksize, double scale, char *table,
+                                 const BoxArgs &bx) {
   if (threadIdx.x == 0) *(aa_table_header *)table = h;
   __syncthreads();
   for (int i = threadIdx.x; i < out_size; i += blockDim.x) {
     if constexpr (KIND == AA_TABLE_F32) table_build_f32_one(i, filter, in_size, out_size, ksize, (float)scale, table);
     else if constexpr (KIND == AA_TABLE_F64) table_build_f64_one(i, filter, in_size, out_size, ksize, scale, table);
-    else table_build_pil_one(i, filter, in_size, out_size, ksize, table);
+    else table_build_pil_one(i, filter, in_size, out_size, ksize, table, bx);
   }
   __threadfence();
   __syncthreads();
@@ -378,11 +387,31 @@ bool aa_table_pair_fits(int64_t in_a, int64_t out_a, int64_t in_b, int64_t out_b
 
 int aa_launch_table_build_pair(int filter, int kind, int align_corners, int64_t in_a, int64_t out_a, double scale_a, int ksize_a, int sk_a, void *tab_a,
                                int64_t in_b, int64_t out_b, double scale_b, int ksize_b, int sk_b, void *tab_b, hipStream_t stream) {
-  TableJob a = {make_header(filter, kind, in_a, out_a, align_corners, ksize_a, sk_a), (int)in_a, (int)out_a, ksize_a, scale_a, (char *)tab_a};
-  TableJob b = {make_header(filter, kind, in_b, out_b, align_corners, ksize_b, sk_b), (int)in_b, (int)out_b, ksize_b, scale_b, (char *)tab_b};
+  TableJob a = {make_header(filter, kind, in_a, out_a, align_corners, ksize_a, sk_a), (int)in_a, (int)out_a, ksize_a, scale_a, (char *)tab_a,
+                BoxArgs{0.0, (double)in_a, 0, 0}};
+  TableJob b = {make_header(filter, kind, in_b, out_b, align_corners, ksize_b, sk_b), (int)in_b, (int)out_b, ksize_b, scale_b, (char *)tab_b,
+                BoxArgs{0.0, (double)in_b, 0, 0}};
   if (kind == AA_TABLE_F32) hipLaunchKernelGGL(table_build_pair<AA_TABLE_F32>, dim3(2), dim3(1024), 0, stream, a, b, filter);
   else if (kind == AA_TABLE_F64) hipLaunchKernelGGL(table_build_pair<AA_TABLE_F64>, dim3(2), dim3(1024), 0, stream, a, b, filter);
   else hipLaunchKernelGGL(table_build_pair<AA_TABLE_PIL>, dim3(2), dim3(1024), 0, stream, a, b, filter);
+  AA_HIP_CHECK_LAUNCH();
+  return AA_OK;
+}
+
+static int launch_table_build(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale, int ksize, int scatter_ksize,
+                              void *table_dev, const BoxArgs &bx, hipStream_t stream);
+
+int aa_launch_table_build_box_pair(int filter, const AABoxAxis &a, const AABoxAxis &b, hipStream_t stream) {
+  if (!aa_table_pair_fits(a.hull, a.out, b.hull, b.out)) {  // very large tables: one after the other, as aa_table_build2 does
+    const int rc = launch_table_build(filter, AA_TABLE_PIL, a.hull, a.out, 0, 0.0, a.ksize, a.scatter_ksize, a.table, BoxArgs{a.in0, a.in1, (int)a.origin, 1}, stream);
+    if (rc != AA_OK) return rc;
+    return launch_table_build(filter, AA_TABLE_PIL, b.hull, b.out, 0, 0.0, b.ksize, b.scatter_ksize, b.table, BoxArgs{b.in0, b.in1, (int)b.origin, 1}, stream);
+  }
+  TableJob ja = {make_header(filter, AA_TABLE_PIL, a.hull, a.out, 0, a.ksize, a.scatter_ksize), (int)a.hull, (int)a.out, a.ksize, 0.0, (char *)a.table,
+                 BoxArgs{a.in0, a.in1, (int)a.origin, 1}};
+  TableJob jb = {make_header(filter, AA_TABLE_PIL, b.hull, b.out, 0, b.ksize, b.scatter_ksize), (int)b.hull, (int)b.out, b.ksize, 0.0, (char *)b.table,
+                 BoxArgs{b.in0, b.in1, (int)b.origin, 1}};
+  hipLaunchKernelGGL(table_build_pair<AA_TABLE_PIL>, dim3(2), dim3(1024), 0, stream, ja, jb, filter);
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }
@@ -413,15 +442,20 @@ static aa_table_header make_header(int filter, int kind, int64_t in_size, int64_
 
 int aa_launch_table_build(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale,
                           int ksize, int scatter_ksize, void *table_dev, hipStream_t stream) {
+  return launch_table_build(filter, kind, in_size, out_size, align_corners, scale, ksize, scatter_ksize, table_dev, BoxArgs{0.0, (double)in_size, 0, 0}, stream);
+}
+
+static int launch_table_build(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale, int ksize, int scatter_ksize,
+                              void *table_dev, const BoxArgs &bx, hipStream_t stream) {
   const aa_table_header h = make_header(filter, kind, in_size, out_size, align_corners, ksize, scatter_ksize);
   char *t = (char *)table_dev;
   if (out_size <= 16384 && in_size <= 32768) {  // one launch, one workgroup (see table_build_all); larger tables: the five launches below
     if (kind == AA_TABLE_F32)
-      hipLaunchKernelGGL(table_build_all<AA_TABLE_F32>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t);
+      hipLaunchKernelGGL(table_build_all<AA_TABLE_F32>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t, bx);
     else if (kind == AA_TABLE_F64)
-      hipLaunchKernelGGL(table_build_all<AA_TABLE_F64>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t);
+      hipLaunchKernelGGL(table_build_all<AA_TABLE_F64>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t, bx);
     else
-      hipLaunchKernelGGL(table_build_all<AA_TABLE_PIL>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t);
+      hipLaunchKernelGGL(table_build_all<AA_TABLE_PIL>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t, bx);
     AA_HIP_CHECK_LAUNCH();
     return AA_OK;
   }
@@ -448,7 +482,7 @@ int aa_launch_table_build(int filter, int kind, int64_t in_size, int64_t out_siz
     }
   } else {
     hipLaunchKernelGGL(table_build_pil, dim3(blocks), dim3(threads), 0, stream, filter, (int)in_size, (int)out_size, ksize,
-                       t);
+                       t, bx);
     if (h.scatter_off) {
       // scatter (adjoint-form) section for the fused kernels' in-register vertical pass: for every INPUT index the
       // outputs it feeds and their fixed-point weights

@@ -31,6 +31,13 @@ Differences, all additive:
   * ``alpha=True`` (uint8, ``uint8_mode="pil"``, 2 or 4 channels with straight alpha last): Pillow's RGBA / LA resize — colour is
     premultiplied by alpha, resampled, and converted back, bit-exact with PIL.Image.resize on an "RGBA" / "LA" image; the same
     size in and out returns a copy;
+  * ``box=(x0, y0, x1, y1)`` on the five forwards (uint8, ``uint8_mode="pil"``): Pillow's ``Image.resize(size, resample, box=...)``, the
+    sub-pixel source rectangle to resample from, bit-exact with Pillow.  PILLOW'S ORDER, X FIRST — unlike ``output_size``, which is
+    (H, W).  Not a crop view: windows clip at the image's edge, so the neighbours outside the box contribute;
+  * ``reducing_gap=g`` on the same forwards: Pillow's two-step resize (``Image.reduce`` by integer factors, then the filter), what
+    ``Image.thumbnail`` does with 2.0.  The result is Pillow's ``reducing_gap`` result, not the plain one.  Two launches plus the table
+    build, through a temporary uint8 tensor in the input's layout;
+  * ``reduce(input, factor, box=None, alpha=False)``: Pillow's ``Image.reduce`` (integer box means), bit-exact;
   * the same callables are registered as ``torch.ops.extension_interpolate.*``.
 """
 from __future__ import annotations
@@ -40,9 +47,9 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib, tables
+from . import _lib, boxmath, tables
 
-__all__ = ["linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+__all__ = ["reduce", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -56,6 +63,10 @@ _DTYPE_IDS = {torch.uint8: _lib.U8, torch.float32: _lib.F32, torch.float64: _lib
 _GRAD_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)  # what the backward takes
 _DTYPE_NAMES = {torch.float16: "Half", torch.bfloat16: "BFloat16", torch.int8: "Char", torch.int16: "Short",
                 torch.int32: "Int", torch.int64: "Long", torch.bool: "Bool", torch.uint8: "Byte"}
+
+
+_FILTER_NAMES = {_lib.FILTER_LINEAR: "linear", _lib.FILTER_CUBIC: "cubic", _lib.FILTER_BOX: "box", _lib.FILTER_HAMMING: "hamming",
+                 _lib.FILTER_LANCZOS: "lanczos"}
 
 
 def set_uint8_mode(mode: str) -> None:
@@ -144,11 +155,15 @@ def _user_scales(scale_factors, n: int):
 
 def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequence[int], align_corners: bool,
              uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
-             out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None, alpha: bool = False) -> torch.Tensor:
+             out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None, alpha: bool = False,
+             box: Optional[Sequence[float]] = None, reducing_gap: Optional[float] = None) -> torch.Tensor:
     if not isinstance(input, torch.Tensor):
         raise TypeError(f"{name}(): argument 'input' must be Tensor")
     if precision not in (None, "exact", "fast"):
         raise ValueError("precision must be 'exact' (default: the reference's results bit for bit) or 'fast' (within 1e-4 relative)")
+    if box is not None or reducing_gap is not None:
+        return _forward_boxed(filter_id, name, input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format, mean, std,
+                              alpha, box, reducing_gap)
     flags = _lib.FLAG_FAST if precision == "fast" else 0
     if alpha:
         _check_alpha(name, input, uint8_mode, out_dtype, out_format, mean, std)
@@ -223,6 +238,172 @@ def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequen
             rc = L.aa_resample_fwd_ex(x.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, dt,
                                       layout, n, c, h, w, pah, paw, flags, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, name)
+    return out
+
+def _layout_of(x: torch.Tensor):
+    """-> (tensor, layout, strides or None): the tensor as the kernels can read it — dense in one of the two layouts, a pitched view
+    (strides given), or, failing both, a contiguous copy.  Callers pass the part of the image they will read (the hull, the box), so a
+    copy is of that part only."""
+    if x.is_contiguous():
+        return x, _lib.NCHW, None
+    if x.is_contiguous(memory_format=torch.channels_last):
+        return x, _lib.NHWC, None
+    pv = _pitched_view(x)
+    if pv is not None:
+        return x, pv[0], pv[1]
+    return x.contiguous(), _lib.NCHW, None
+
+
+def _forward_boxed(filter_id: int, name: str, input: torch.Tensor, output_size: Sequence[int], align_corners: bool, uint8_mode, scale_factors,
+                   out_dtype, out_format, mean, std, alpha: bool, box, reducing_gap) -> torch.Tensor:
+    """Image.resize(size, resample, box, reducing_gap) as Pillow's Python and C order it: checks, the optional reduce with its shifted
+    box, then a full box (today's path, same tables, same variant), a plain crop, or the box tables.  Every check comes before any GPU use."""
+    what = "box" if box is not None else "reducing_gap"
+    gap = boxmath.check_reducing_gap(reducing_gap)
+    if input.dtype != torch.uint8:
+        raise NotImplementedError(f"{name}(): {what} is Pillow's uint8 resize; {input.dtype} images have none (the reference has no box)")
+    if (uint8_mode or _uint8_mode) != "pil":
+        raise NotImplementedError(f"{name}(): {what} is Pillow's arithmetic; uint8_mode='harness' has none (the reference has no box)")
+    if out_dtype is not None or out_format is not None or mean is not None or std is not None:
+        raise NotImplementedError(f"{name}(): {what} gives uint8 in the input's layout; out_dtype / out_format / mean / std do not apply")
+    if align_corners or scale_factors is not None:
+        raise NotImplementedError("uint8_mode='pil' has no align_corners and no scale factors (Pillow has neither)")
+    if alpha:
+        _check_alpha(name, input, uint8_mode, out_dtype, out_format, mean, std)
+        if gap is not None:
+            raise NotImplementedError(f"{name}(): alpha=True with reducing_gap: Pillow drops reducing_gap for RGBA / LA images; reduce(alpha=True) "
+                                      "and a resize with the shifted box are the two steps, if that is what is wanted")
+    n, c, h, w, oh, ow = _check_sizes(input.shape, output_size)
+    bx = boxmath.check_box(box, w, h) if box is not None else (0.0, 0.0, float(w), float(h))
+
+    def plain(x):  # today's call, unchanged
+        return _forward(filter_id, name, x, output_size, False, "pil", None, None, None, None, None, None, alpha)
+
+    x = input
+    full = boxmath.axis_is_full(w, bx[0], bx[2]) and boxmath.axis_is_full(h, bx[1], bx[3])
+    if gap is not None and not (full and (h, w) == (oh, ow)):
+        plan = boxmath.reducing_plan(w, h, ow, oh, _FILTER_NAMES[filter_id], bx, gap)
+        if plan is not None:
+            factor, rb, bx = plan
+            boxmath.check_factor(factor)
+            x = reduce(x, factor, rb)
+            h, w = int(x.shape[2]), int(x.shape[3])
+            full = boxmath.axis_is_full(w, bx[0], bx[2]) and boxmath.axis_is_full(h, bx[1], bx[3])
+    if full:
+        return plain(x)
+    bx = boxmath.box_f32(bx)  # Pillow's C resize takes the box as floats
+    if boxmath.axis_is_full(w, bx[0], bx[2]) and boxmath.axis_is_full(h, bx[1], bx[3]):
+        return plain(x)
+    _require_gpu(x, name)
+    if boxmath.is_plain_crop(bx, ow, oh):  # Pillow's C: integer offsets and a box of the output's size is a crop, no filter
+        x0, y0 = int(bx[0]), int(bx[1])
+        crop = x[:, :, y0:y0 + oh, x0:x0 + ow]
+        t, lay, _ = _layout_of(crop)  # (the layout follows the input's; a view no kernel reads was copied here already)
+        mf = torch.channels_last if lay == _lib.NHWC else torch.contiguous_format
+        out = t if t is not crop else crop.clone(memory_format=mf)
+        if alpha and n:  # (Pillow converts to premultiplied and back around the crop as around any resize)
+            L = _lib.load()
+            lay = _lib.NHWC if mf == torch.channels_last else _lib.NCHW
+            with torch.cuda.device(out.device):
+                s = torch.cuda.current_stream(out.device).cuda_stream
+                _lib.check(L.aa_premultiply_u8(out.data_ptr(), out.data_ptr(), lay, n, c, oh, ow, s), name)
+                _lib.check(L.aa_unpremultiply_u8(out.data_ptr(), lay, n, c, oh, ow, s), name)
+        return out
+    return _forward_box(filter_id, name, x, oh, ow, bx, alpha)
+
+
+def _forward_box(filter_id: int, name: str, input: torch.Tensor, oh: int, ow: int, bx, alpha: bool) -> torch.Tensor:
+    """The resampling kernels, untouched, on the HULL of the box: per axis the hull [o, e) of all filter windows (boxmath.axis_hull) is
+    handed to them as a pitched view of the input, with a table whose in_size is e - o (tables.get_box_table_pair).  Rows and columns
+    outside the hull are neither read nor copied: where no fused kernel takes the view, the dense fallback copies the hull."""
+    L = _lib.load()
+    n, c, h, w = (int(v) for v in input.shape)
+    fname = _FILTER_NAMES[filter_id]
+    oy, ey = boxmath.axis_hull(h, oh, bx[1], bx[3], fname)
+    ox, ex = boxmath.axis_hull(w, ow, bx[0], bx[2], fname)
+    if ey <= oy or ex <= ox:
+        raise ValueError("box can't be empty")
+    hull, layout, _ = _layout_of(input[:, :, oy:ey, ox:ex])  # (a view no kernel reads: a copy of the hull, never of the image)
+    dev = hull.device
+    mf = torch.channels_last if layout == _lib.NHWC else torch.contiguous_format
+    out = torch.empty((n, c, oh, ow), dtype=torch.uint8, device=dev, memory_format=mf)
+    if n == 0:
+        return out
+    flags = _lib.FLAG_PREMUL_ALPHA if alpha else 0
+    hh, hw = ey - oy, ex - ox
+    with torch.cuda.device(dev):
+        # (th, tw are held until the launch is enqueued: the LRU may drop them at any later call)
+        th, tw = tables.get_box_table_pair(filter_id, (oy, hh, oh, bx[1], bx[3]), (ox, hw, ow, bx[0], bx[2]), dev)
+        ah, aw = th.axis(), tw.axis()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if not hull.is_contiguous(memory_format=mf):
+            pv = _pitched_view(hull)
+            if pv is not None and pv[0] == layout:
+                strides = (ctypes.c_int64 * 4)(*pv[1])
+                rc = L.aa_resample_fwd_strided(hull.data_ptr(), out.data_ptr(), _lib.U8, layout, n, c, hh, hw, strides, ctypes.byref(ah),
+                                               ctypes.byref(aw), flags, stream)
+                if rc != _lib.ERR_STRIDES:
+                    _lib.check(rc, name)
+                    return out
+            hull = hull.contiguous(memory_format=mf)  # no kernel for this view: the dense copy of the hull (not of the image)
+        ws_bytes = L.aa_workspace_bytes_ex(_lib.U8, layout, n, c, hh, hw, oh, ow, ctypes.byref(ah), ctypes.byref(aw), flags)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        rc = L.aa_resample_fwd_ex(hull.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, _lib.U8, layout,
+                                  n, c, hh, hw, ctypes.byref(ah), ctypes.byref(aw), flags, stream)
+    _lib.check(rc, name)
+    return out
+
+
+def reduce(input: torch.Tensor, factor, box: Optional[Sequence[int]] = None, *, alpha: bool = False) -> torch.Tensor:
+    """Pillow's ``Image.reduce(factor, box)`` for uint8 images [N, C, H, W], bit-exact: every output pixel is the rounded mean of an
+    fx x fy block of input pixels; the blocks of the last row and column (and the corner) may be partial.
+
+    ORDER OF COORDINATES — PILLOW'S, X FIRST: ``factor`` is an int or **(fx, fy)** and ``box`` is **(x0, y0, x1, y1)**, an integer
+    rectangle inside the image (default: all of it).  ``output_size`` elsewhere in this module is (H, W); these two are not.
+
+    The result is [N, C, ceil((y1 - y0) / fy), ceil((x1 - x0) / fx)], uint8, in the input's layout.  One launch, no workspace; a crop or a
+    batch slice of a larger tensor is read where it lies.  fx * fy <= 65536.  ``alpha=True`` ([N, 2 or 4, H, W], straight alpha last):
+    premultiply, reduce, convert back, as Image.reduce does for RGBA / LA."""
+    if not isinstance(input, torch.Tensor):
+        raise TypeError("reduce(): argument 'input' must be Tensor")
+    fx, fy = boxmath.check_factor(factor)
+    if input.dim() != 4:
+        raise RuntimeError(f"It is expected input_size equals to 4, but got size {input.dim()}")
+    if input.dtype != torch.uint8:
+        raise NotImplementedError(f"reduce(): Image.reduce's 8-bit arithmetic takes uint8 images, got {input.dtype}")
+    n, c, h, w = (int(v) for v in input.shape)
+    if not (h > 0 and w > 0 and c > 0):
+        raise RuntimeError(f"Non-empty 4D data tensor expected but got a tensor with sizes {list(input.shape)}")
+    x0, y0, x1, y1 = boxmath.check_int_box(box, w, h)
+    if alpha and c not in (2, 4):
+        raise ValueError(f"reduce(): alpha=True needs [N, 2 or 4, H, W] with straight alpha in the last channel, got {list(input.shape)}")
+    _require_gpu(input, "reduce")
+    L = _lib.load()
+    x, layout, strides = _layout_of(input[:, :, y0:y1, x0:x1])  # (the box only: a view no kernel reads is copied, the rest of the image is not)
+    h, w = y1 - y0, x1 - x0
+    x0, y0, x1, y1 = 0, 0, w, h
+    channels_last = layout == _lib.NHWC
+    if channels_last and c > 4:  # interleaved pixels of up to 4 bytes; anything wider goes through planes
+        x, layout, strides = x.contiguous(), _lib.NCHW, None
+    mf = torch.channels_last if layout == _lib.NHWC else torch.contiguous_format
+    dev = x.device
+    ow, oh = boxmath.reduced_size((x0, y0, x1, y1), (fx, fy))
+    out = torch.empty((n, c, oh, ow), dtype=torch.uint8, device=dev, memory_format=mf)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if alpha:  # a premultiplied copy of the box
+            x = x.clone(memory_format=mf)
+            strides = None
+            _lib.check(L.aa_premultiply_u8(x.data_ptr(), x.data_ptr(), layout, n, c, h, w, stream), "reduce")
+        cs = (ctypes.c_int64 * 4)(*strides) if strides is not None else None
+        cb = (ctypes.c_int64 * 4)(x0, y0, x1, y1)
+        _lib.check(L.aa_reduce_u8(x.data_ptr(), out.data_ptr(), layout, n, c, h, w, cs, cb, fx, fy, stream), "reduce")
+        if alpha:
+            _lib.check(L.aa_unpremultiply_u8(out.data_ptr(), layout, n, c, oh, ow, stream), "reduce")
+    if channels_last and layout == _lib.NCHW:
+        out = out.contiguous(memory_format=torch.channels_last)
     return out
 
 
@@ -502,28 +683,28 @@ def nearest_forward_nd(input: torch.Tensor, output_size: Sequence[int], align_co
 def linear_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
                     out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
-                    alpha: bool = False) -> torch.Tensor:
+                    alpha: bool = False, box: Optional[Sequence[float]] = None, reducing_gap: Optional[float] = None) -> torch.Tensor:
     """Anti-Aliased Linear Interpolation forward (s2.2/extension_interpolate.cpp:7-14,47)."""
     return _forward(_lib.FILTER_LINEAR, "linear_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision, alpha)
+                    mean, std, precision, alpha, box, reducing_gap)
 
 
 def nearest_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
                     out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
-                    alpha: bool = False) -> torch.Tensor:
+                    alpha: bool = False, box: Optional[Sequence[float]] = None, reducing_gap: Optional[float] = None) -> torch.Tensor:
     """Anti-Aliased "Nearest" (really: box filter) forward (s2.2/extension_interpolate.cpp:26-33,48)."""
     return _forward(_lib.FILTER_BOX, "nearest_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision, alpha)
+                    mean, std, precision, alpha, box, reducing_gap)
 
 
 def cubic_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
                     out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
-                    alpha: bool = False) -> torch.Tensor:
+                    alpha: bool = False, box: Optional[Sequence[float]] = None, reducing_gap: Optional[float] = None) -> torch.Tensor:
     """Anti-Aliased Cubic Interpolation forward (s2.2/extension_interpolate.cpp:35-42,49)."""
     return _forward(_lib.FILTER_CUBIC, "cubic_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision, alpha)
+                    mean, std, precision, alpha, box, reducing_gap)
 
 
 def linear_backward(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],
@@ -547,19 +728,19 @@ def nearest_backward(grad_output: torch.Tensor, output_size: Sequence[int], inpu
 def lanczos_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
                     out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
-                    alpha: bool = False) -> torch.Tensor:
+                    alpha: bool = False, box: Optional[Sequence[float]] = None, reducing_gap: Optional[float] = None) -> torch.Tensor:
     """Antialiased Lanczos-3 forward (Pillow's Image.LANCZOS; uint8 in the default mode equals PIL.Image.resize bit for bit)."""
     return _forward(_lib.FILTER_LANCZOS, "lanczos_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision, alpha)
+                    mean, std, precision, alpha, box, reducing_gap)
 
 
 def hamming_forward(input: torch.Tensor, output_size: Sequence[int], align_corners: bool = False, *,
                     uint8_mode: Optional[str] = None, scale_factors: Optional[Sequence[float]] = None, out_dtype=None,
                     out_format: Optional[str] = None, mean=None, std=None, precision: Optional[str] = None,
-                    alpha: bool = False) -> torch.Tensor:
+                    alpha: bool = False, box: Optional[Sequence[float]] = None, reducing_gap: Optional[float] = None) -> torch.Tensor:
     """Antialiased Hamming-windowed forward (Pillow's Image.HAMMING; uint8 in the default mode equals PIL.Image.resize bit for bit)."""
     return _forward(_lib.FILTER_HAMMING, "hamming_forward", input, output_size, align_corners, uint8_mode, scale_factors, out_dtype, out_format,
-                    mean, std, precision, alpha)
+                    mean, std, precision, alpha, box, reducing_gap)
 
 
 def lanczos_backward(grad_output: torch.Tensor, output_size: Sequence[int], input_size: Sequence[int],
@@ -610,6 +791,8 @@ def _register_torch_ops() -> None:
     for name in bwds:
         lib.define(name + bwd_schema)
 
+    lib.define("reduce(Tensor input, int[] factor, int[]? box=None, bool alpha=False) -> Tensor")
+
     def _mf(x):
         return torch.channels_last if (x.dim() == 4 and not x.is_contiguous()
                                        and x.is_contiguous(memory_format=torch.channels_last)) else torch.contiguous_format
@@ -619,6 +802,16 @@ def _register_torch_ops() -> None:
         lib.impl(name, lambda input, output_size, align_corners=False: torch.empty(
             (input.shape[0], input.shape[1], output_size[0], output_size[1]), dtype=input.dtype, device=input.device,
             memory_format=_mf(input)), "Meta")
+    def _reduce_meta(input, factor, box=None, alpha=False):
+        fx, fy = boxmath.check_factor(tuple(factor) if len(factor) != 1 else factor[0])
+        bx = boxmath.check_int_box(box, input.shape[3], input.shape[2])
+        ow, oh = boxmath.reduced_size(bx, (fx, fy))
+        return torch.empty((input.shape[0], input.shape[1], oh, ow), dtype=input.dtype, device=input.device, memory_format=_mf(input))
+
+    lib.impl("reduce", lambda input, factor, box=None, alpha=False: reduce(
+        input, tuple(factor) if len(factor) != 1 else factor[0], box, alpha=alpha), "CUDA")
+    lib.impl("reduce", _reduce_meta, "Meta")
+
     for name, fn in bwds.items():
         lib.impl(name, (lambda f: lambda grad_output, output_size, input_size, align_corners=False:
                         f(grad_output, output_size, input_size, align_corners))(fn), "CUDA")

@@ -7,6 +7,7 @@ scale, device), built once by a HIP kernel and cached.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import threading
 from dataclasses import dataclass
@@ -49,12 +50,14 @@ class WeightTable:
     span64p1: int = 0  # 1 + the widest spread of 64 consecutive outputs' window starts (measured on device; 0 = unknown)
     span4p1: int = 0   # the same over 4 consecutive outputs
     gather_off: int = 0  # byte offset of the per-output gather records (F32 and Pillow tables)
+    box: bool = False  # a box table (get_box_table_pair): in_size is the hull's length, xmin[] are relative to the hull's origin
 
     def axis(self) -> _lib.Axis:
         if not self.buf.is_cuda:
             raise _lib.AAInterpError("weight table is not on a GPU")
         return _lib.Axis(ctypes.c_void_p(self.buf.data_ptr()), self.in_size, self.out_size, self.ksize, self.max_taps,
-                         self.kind, self.filter, self.scatter_off, self.scatter_ksize, self.scatter_max, self.span64p1, self.span4p1, self.gather_off)
+                         self.kind, self.filter, self.scatter_off, self.scatter_ksize, self.scatter_max, self.span64p1, self.span4p1, self.gather_off,
+                         (ctypes.c_int32 * 2)(1 if self.box else 0, 0))
 
     # ---- transport -----------------------------------------------------------------------------------
     def meta(self) -> torch.Tensor:
@@ -115,6 +118,7 @@ _cache_lock = threading.Lock()
 def clear_cache() -> None:
     with _cache_lock:
         _cache.clear()
+        _box_cache.clear()
 
 
 def cache_key(filter_id: int, kind: int, in_size: int, out_size: int, align_corners: bool, scale: float,
@@ -182,6 +186,62 @@ def get_table_pair(filter_id: int, kind: int, in_h: int, out_h: int, in_w: int, 
         th = get_table(filter_id, kind, in_h, out_h, align_corners, scale_h, device)
     if tw is None:
         tw = get_table(filter_id, kind, in_w, out_w, align_corners, scale_w, device)
+    return th, tw
+
+
+# ---- box tables (Image.resize(box=...)) -----------------------------------------------------------------------------------------
+# Random boxes never repeat, so their tables stay out of `_cache` (which never forgets): a small LRU of their own.  An evicted table's
+# buffer goes back to the caching allocator only after the launch that used it was enqueued (the caller holds the pair until then),
+# and the stream orders every later use of that memory behind it.
+# Buffers come in size classes (a power of two, 16 KiB at least), so what the full LRU holds does not drift with the boxes' sizes.
+BOX_CACHE_SIZE = 32
+BOX_TABLE_MIN_BYTES = 16384
+
+
+def _box_table_alloc(nbytes: int, device: torch.device) -> torch.Tensor:
+    return torch.empty(max(BOX_TABLE_MIN_BYTES, 1 << max(int(nbytes) - 1, 0).bit_length()), dtype=torch.uint8, device=device)
+
+_box_cache: "collections.OrderedDict[Tuple, Tuple[WeightTable, WeightTable]]" = collections.OrderedDict()
+
+
+def get_box_table_pair(filter_id: int, axis_h: Tuple[int, int, int, float, float], axis_w: Tuple[int, int, int, float, float],
+                       device: torch.device):
+    """The two AA_TABLE_PIL box tables of a call: ONE launch and ONE header read-back.  axis_* = (origin, hull, out_size, in0, in1):
+    Pillow's source interval [in0, in1) of the axis and the hull [origin, origin + hull) of its windows (boxmath.axis_hull); an axis
+    without a box is (0, in_size, out_size, 0.0, in_size)."""
+    device = torch.device(device)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (int(filter_id), tuple(axis_h), tuple(axis_w), idx)
+    with _cache_lock:
+        pair = _box_cache.get(key)
+        if pair is not None:
+            _box_cache.move_to_end(key)
+            return pair
+    L = _lib.load()
+    kind = _lib.TABLE_PIL
+    (o_h, n_h, out_h, a_h, b_h), (o_w, n_w, out_w, a_w, b_w) = axis_h, axis_w
+    k_h = L.aa_table_ksize_box(filter_id, kind, n_h, out_h, a_h, b_h)
+    _lib.check(k_h, "aa_table_ksize_box")
+    k_w = L.aa_table_ksize_box(filter_id, kind, n_w, out_w, a_w, b_w)
+    _lib.check(k_w, "aa_table_ksize_box")
+    nb_h = L.aa_table_build_bytes_box(filter_id, kind, n_h, out_h, a_h, b_h)
+    nb_w = L.aa_table_build_bytes_box(filter_id, kind, n_w, out_w, a_w, b_w)
+    with torch.cuda.device(device):
+        bh = _box_table_alloc(nb_h, device)
+        bw = _box_table_alloc(nb_w, device)
+        s = _stream_ptr(device)
+        _lib.check(L.aa_table_build_box(filter_id, kind, o_h, n_h, out_h, a_h, b_h, ctypes.c_void_p(bh.data_ptr()), nb_h,
+                                        o_w, n_w, out_w, a_w, b_w, ctypes.c_void_p(bw.data_ptr()), nb_w, s), "aa_table_build_box")
+        hh, hw = _lib.TableHeader(), _lib.TableHeader()
+        _lib.check(L.aa_table_query2(ctypes.c_void_p(bh.data_ptr()), ctypes.c_void_p(bw.data_ptr()), ctypes.byref(hh), ctypes.byref(hw), s),
+                   "aa_table_query2")
+    th = _from_header(bh, filter_id, kind, n_h, out_h, k_h, False, hh)
+    tw = _from_header(bw, filter_id, kind, n_w, out_w, k_w, False, hw)
+    th.box = tw.box = True
+    with _cache_lock:
+        _box_cache[key] = (th, tw)
+        while len(_box_cache) > BOX_CACHE_SIZE:
+            _box_cache.popitem(last=False)
     return th, tw
 
 
