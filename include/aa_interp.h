@@ -316,6 +316,44 @@ int aa_reduce_u8(const void *in_dev, void *out_dev, int layout, int64_t N, int64
 int aa_premultiply_u8(const void *src_dev, void *dst_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, aa_stream_t stream);
 int aa_unpremultiply_u8(void *img_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, aa_stream_t stream);
 
+/* ---- ragged batches: N uint8 images of N sizes, each with its own box, into one dense batch -----------------------------------------
+ * A decoder or a RandomResizedCrop loader produces N images of N different sizes, each with its own box, all going to one
+ * [N, C, oH, oW] batch.  Through the calls above that is N table pairs, N header read-backs (aa_table_query2 synchronises) and N launches.
+ * The three calls below do it with THREE launches and no synchronisation whatever N, bit-exact with Pillow (AA_TABLE_PIL arithmetic):
+ * aa_many_plan is host arithmetic only — per item and axis the float32 box, the hull [o, e) of all windows (the double operations of
+ * precompute_coeffs, in its order), ksize (aa_table_ksize_box's arithmetic), the offsets of the item's two tables in one table arena and
+ * of its horizontally resampled intermediate [hull_h, oW, C], and prefix sums of work units — written as one packed descriptor block
+ * into caller memory; the caller copies the block to the device (one asynchronous copy) and aa_resample_many_u8 enqueues: one kernel
+ * that builds every item's two coefficient sets into the arena (xmin, xsize, int32 weights in 22-bit fixed point; no scatter, gather or
+ * span section, nothing measured, nothing read back), the horizontal pass over (item, hull row, strip of output columns), and the vertical
+ * pass over (item, output row, strip).  Rows and columns outside an item's hull are never read.  Item i of the result equals
+ * aa_resample_fwd on that image with the box tables of its box — a full box, an integer box of the output's size (Pillow's plain
+ * crop) and equal sizes in and out (a copy) included: their windows are one tap of weight 1.
+ * layout: the class ALL items share and the layout of the dense output — AA_NHWC: interleaved pixels (stride_ch = 1, stride_px = C),
+ * AA_NCHW: planes of consecutive bytes (stride_px = 1).  Any row pitch, any plane pitch, any byte offset; the stride of an axis of one
+ * element is not looked at.  C is 1..4.  Added without an ABI version change (additive). */
+typedef struct aa_many_image {
+  const void *data_dev;  /* byte (row 0, column 0, channel 0) of the image */
+  int64_t H, W;
+  int64_t stride_row, stride_px, stride_ch; /* in BYTES */
+  double box[4];         /* x0, y0, x1, y1 — Pillow's order, x first; rounded to float32 by the plan, as Pillow's C does */
+  int32_t has_box;       /* 0: the whole image (box[] is not read) */
+  int32_t reserved;
+} aa_many_image;
+/* Bytes of the packed descriptor block for n items. */
+size_t aa_many_desc_bytes(int64_t n);
+/* Plan a call: fills desc_host (desc_bytes >= aa_many_desc_bytes(n); any host memory, pinned if the copy is to be asynchronous) and
+ * reports the workspace the call needs: table arena + intermediates (offsets across items are 64-bit).  No HIP call: works without a
+ * device.  Errors: AA_ERR_BAD_SHAPE for an empty box, a box beyond its image, C outside 1..4, a size beyond INT32_MAX / 4 within one
+ * image, or more work units than one grid holds; AA_ERR_STRIDES for an item that is not in `layout`'s class; AA_ERR_KSIZE. */
+int aa_many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, void *desc_host,
+                 size_t desc_bytes, size_t *workspace_bytes);
+/* Enqueue the three launches.  desc_dev: the device copy of desc_host (8-byte aligned), in flight or complete on `stream`; desc_host is
+ * read only to size the grids and to check the arguments against the plan.  out_dev [n, C, oH, oW] uint8, dense, in `layout`.
+ * workspace_dev: 16-byte aligned, at least the plan's size.  Nothing is allocated, nothing is synchronised.  n == 0 launches nothing. */
+int aa_resample_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
+                        void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
 /* Device-to-device copy of `bytes` bytes with 16-byte vector loads/stores, enqueued on `stream`: the probe bench.py times
  * on the box to report the attainable HBM copy ceiling next to the 8 TB/s spec peak.  form 0: one element per
  * thread; 1: grid-stride; 2: four elements per thread, loads in flight before the stores; 3: form 2, streaming (nt) policy;

@@ -34,7 +34,7 @@ EXPORTS = (
     "aa_resample_bwd", "aa_resample_bwd_atomic", "aa_workspace_bytes_bwd", "aa_resample_axis_fwd", "aa_set_fused",
     "aa_last_variant", "aa_probe_copy", "aa_workspace_bytes_u8_to_f32", "aa_resample_fwd_u8_to_f32", "aa_set_store_form", "aa_set_plane_groups", "aa_resample_fwd_ex", "aa_resample_fwd_strided",
     "aa_workspace_bytes_ex", "aa_table_ksize_box", "aa_table_build_bytes_box", "aa_table_build_box", "aa_reduce_u8", "aa_premultiply_u8",
-    "aa_unpremultiply_u8",
+    "aa_unpremultiply_u8", "aa_many_desc_bytes", "aa_many_plan", "aa_resample_many_u8",
 )
 
 
@@ -59,6 +59,40 @@ class Axis(ctypes.Structure):
 class Convert(ctypes.Structure):
     _fields_ = [("out_layout", ctypes.c_int32), ("normalize", ctypes.c_int32), ("mean", ctypes.c_float * 4),
                 ("std", ctypes.c_float * 4), ("flags", ctypes.c_uint32)]
+
+
+class ManyImage(ctypes.Structure):
+    """aa_many_image: one item of the ragged call (strides in bytes; box = x0, y0, x1, y1)."""
+    _fields_ = [("data_dev", ctypes.c_void_p), ("H", ctypes.c_int64), ("W", ctypes.c_int64), ("stride_row", ctypes.c_int64),
+                ("stride_px", ctypes.c_int64), ("stride_ch", ctypes.c_int64), ("box", ctypes.c_double * 4), ("has_box", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class ManyHeader(ctypes.Structure):
+    """Head of the descriptor block aa_many_plan writes (csrc/aa_many.h AAManyHeader; opaque to C callers, mirrored here for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("C", ctypes.c_int32), ("oH", ctypes.c_int32), ("oW", ctypes.c_int32),
+                ("filter", ctypes.c_int32), ("layout", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("hunits", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64 * 2)]
+
+
+class ManyItem(ctypes.Structure):
+    """One item of that block (csrc/aa_many.h AAManyItem): offsets in bytes into the workspace, hulls [o, o + hull) per axis."""
+    _fields_ = [("src", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("plane_stride", ctypes.c_int64), ("tab_h", ctypes.c_int64),
+                ("tab_w", ctypes.c_int64), ("inter", ctypes.c_int64), ("in0_h", ctypes.c_double), ("in1_h", ctypes.c_double),
+                ("in0_w", ctypes.c_double), ("in1_w", ctypes.c_double), ("oy", ctypes.c_int32), ("hull_h", ctypes.c_int32),
+                ("ox", ctypes.c_int32), ("hull_w", ctypes.c_int32), ("ksize_h", ctypes.c_int32), ("ksize_w", ctypes.c_int32),
+                ("box_on", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
+
+
+def many_desc_view(buf, n: int):
+    """(header, items, prefix) of a descriptor block held in a ctypes buffer: [header][n items][int64 prefix[n + 1]]."""
+    hd = ManyHeader.from_buffer(buf, 0)
+    items = (ManyItem * n).from_buffer(buf, ctypes.sizeof(ManyHeader))
+    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(ManyHeader) + n * ctypes.sizeof(ManyItem))
+    return hd, items, prefix
 
 
 class AAInterpError(RuntimeError):
@@ -142,6 +176,12 @@ def load() -> ctypes.CDLL:
     L.aa_premultiply_u8.restype = i32
     L.aa_unpremultiply_u8.argtypes = [vp, i32, i64, i64, i64, i64, vp]
     L.aa_unpremultiply_u8.restype = i32
+    L.aa_many_desc_bytes.argtypes = [i64]
+    L.aa_many_desc_bytes.restype = sz
+    L.aa_many_plan.argtypes = [i32, i32, i64, i64, i64, i64, ctypes.POINTER(ManyImage), vp, sz, ctypes.POINTER(sz)]
+    L.aa_many_plan.restype = i32
+    L.aa_resample_many_u8.argtypes = [vp, vp, i64, i64, i64, i64, i32, vp, vp, sz, vp]
+    L.aa_resample_many_u8.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

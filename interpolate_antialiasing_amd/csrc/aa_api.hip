@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "aa_box.h"
+#include "aa_many.h"
 #include "aa_plan.h"
 #include "aa_reduce.h"
 
@@ -452,6 +453,23 @@ int aa_table_build_box(int filter, int kind, int64_t origin_a, int64_t hull_a, i
   const AABoxAxis a = {origin_a, hull_a, out_a, in0_a, in1_a, ka, ska, table_a_dev};
   const AABoxAxis b = {origin_b, hull_b, out_b, in0_b, in1_b, kb, skb, table_b_dev};
   return aa_launch_table_build_box_pair(filter, a, b, (hipStream_t)stream);
+}
+
+// ---- ragged batches ------------------------------------------------------------------------------------------------------------------
+size_t aa_many_desc_bytes(int64_t n) { return aa_many_desc_size(n); }
+
+int aa_many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, void *desc_host,
+                 size_t desc_bytes, size_t *workspace_bytes) {
+  return aa_many_plan_host(filter, layout, n, C, oH, oW, images, desc_host, desc_bytes, workspace_bytes);
+}
+
+int aa_resample_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
+                        void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (n < 0 || C < 1 || C > 4 || oH <= 0 || oW <= 0) return AA_ERR_BAD_SHAPE;
+  if (!desc_host) return AA_ERR_NULL;
+  if (n > 0 && (!desc_dev || !out_dev || !workspace_dev)) return AA_ERR_NULL;
+  return aa_launch_many_u8(desc_host, desc_dev, n, C, oH, oW, layout, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- Image.reduce ------------------------------------------------------------------------------------------------------------------------

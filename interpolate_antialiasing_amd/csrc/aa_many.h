@@ -1,0 +1,43 @@
+// aa_many.h — the ragged call (include/aa_interp.h, "ragged batches"): N uint8 images of N sizes, each with its own box, into one dense
+// batch.  The packed descriptor block aa_many_plan writes on the host and the three kernels read on the device:
+//   [ AAManyHeader : 64 B ][ AAManyItem x n ][ int64 hunit_prefix[n + 1] ]
+// Everything a kernel needs about an item is in its record: no table header, nothing read back.
+#pragma once
+
+#include "aa_common.h"
+
+#define AA_MANY_MAGIC 0x594E4D41  // 'AMNY'
+#define AA_MANY_STRIP 64          // output columns per workgroup of the horizontal pass
+#define AA_MANY_VBYTES 1024       // output-row bytes per workgroup of the vertical pass (256 lanes x 4)
+
+struct AAManyHeader {
+  int32_t magic, n, C, oH, oW, filter, layout, reserved0;
+  int64_t hunits;     // work units of the horizontal pass, all items: hunit_prefix[n]
+  int64_t ws_bytes;   // table arena + intermediates
+  int64_t reserved[2];
+};
+static_assert(sizeof(AAManyHeader) == 64, "descriptor header is 64 bytes");
+
+// One item.  The image is read where it lies: byte (row y, column x, channel c) is at src + y * row_stride + x * E + c (interleaved class,
+// E = C) or src + c * plane_stride + y * row_stride + x (planar class).  tab_h / tab_w / inter are byte offsets into the workspace.
+// A table is [ int32 xmin[out] ][ int32 xsize[out] ][ int32 w[out * ksize] ], xmin relative to the hull's origin.
+struct AAManyItem {
+  const uint8_t *src;
+  int64_t row_stride, plane_stride;
+  int64_t tab_h, tab_w, inter;
+  double in0_h, in1_h, in0_w, in1_w;  // Pillow's source interval per axis, float32 values (box_f32)
+  int32_t oy, hull_h, ox, hull_w;     // the hull [o, o + hull) of all windows per axis: nothing outside it is read
+  int32_t ksize_h, ksize_w;
+  int32_t box_on;                     // 1: the scale is the FLOAT difference of the interval over the output size (a box); 0: in / out
+  int32_t reserved;
+};
+static_assert(sizeof(AAManyItem) == 112, "descriptor item is 112 bytes");
+
+inline size_t aa_many_table_bytes(int64_t out, int ksize) { return aa_align16(4 * (size_t)out * (2 + (size_t)ksize)); }
+__host__ __device__ inline int64_t aa_many_inter_pitch(int64_t oW, int E) { return (oW * E + 3) & ~(int64_t)3; }  // rows of the intermediate start on a dword
+
+size_t aa_many_desc_size(int64_t n);
+int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, void *desc_host,
+                      size_t desc_bytes, size_t *workspace_bytes);
+int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
+                      void *workspace_dev, size_t workspace_bytes, hipStream_t stream);

@@ -1,0 +1,303 @@
+// aa_many.hip — the ragged call: a list of uint8 images of different sizes, each with its own box, resampled into one dense batch with
+// Pillow's 8bpc arithmetic.  Three launches whatever N:
+//   1. many_tables  every item's two AA_TABLE_PIL coefficient sets into one arena (aa_pil_coeffs.h: the packed tables' own expressions);
+//   2. many_hpass   one workgroup per (item, plane, hull row, strip of 64 output columns), found from prefix sums: the grid is the sum of
+//                   the items' work, not N x the largest item;
+//   3. many_vpass   one workgroup per (item, plane, output row, 1 KiB of the row).
+// The host planner (aa_many_plan_host) computes every hull, ksize and offset with the same double arithmetic the table kernel uses, so
+// nothing comes back from the device: no header read-back, no atomicMax, no synchronisation, no allocation.
+
+#include <math.h>
+#include <string.h>
+
+#include "aa_many.h"
+#include "aa_pil_coeffs.h"
+
+using namespace aa_coeffs;
+
+namespace {
+
+__device__ inline uint8_t clip8(int32_t a) {  // Pillow's clip8(ss >> PRECISION_BITS)
+  a >>= 22;
+  return (uint8_t)(a < 0 ? 0 : (a > 255 ? 255 : a));
+}
+
+// ---- 1. tables -------------------------------------------------------------------------------------------------------------------------
+// One thread per (item, axis, output index): every item has oH + oW of them.
+__global__ void __launch_bounds__(256) many_tables(const AAManyItem *items, char *ws, int64_t n, int oH, int oW, int filter) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per = oH + oW;
+  if (t >= n * per) return;
+  const AAManyItem &it = items[t / per];
+  const int r = (int)(t % per);
+  const bool vert = r < oH;
+  const int i = vert ? r : r - oH;
+  const int out = vert ? oH : oW;
+  const int ksize = vert ? it.ksize_h : it.ksize_w;
+  const int hull = vert ? it.hull_h : it.hull_w;
+  const BoxArgs bx = {vert ? it.in0_h : it.in0_w, vert ? it.in1_h : it.in1_w, vert ? it.oy : it.ox, it.box_on};
+  int32_t *xmin_p = (int32_t *)(ws + (vert ? it.tab_h : it.tab_w));
+  int32_t *xsize_p = xmin_p + out;
+  int32_t *kk = xsize_p + out + (size_t)i * ksize;
+  // (no box: the hull is the whole axis, origin 0, and in / out is the scale — aa_table_build's table)
+  const PilWindow wd = pil_window(i, filter, hull, out, bx);
+  xmin_p[i] = wd.xmin - bx.origin;
+  xsize_p[i] = wd.xsize;
+  pil_weights(wd, filter, ksize, kk);
+}
+
+// ---- 2. horizontal pass ------------------------------------------------------------------------------------------------------------------
+// E = bytes per pixel of a row (C for interleaved pixels, 1 for a plane).  64 * E lanes: lane j computes byte j of the strip's output, i.e.
+// column x0 + j / E, channel j % E.  The input bytes the strip's windows cover are staged into LDS in chunks of up to kChunkBytes with
+// dword loads from the dword at or below the segment's first byte (bytes outside the segment are never read: the ragged dwords at both
+// ends are assembled from byte loads), so rows at any alignment load coalesced; every lane then adds the taps of its window that lie in
+// the chunk.  Integer sums: the order of the taps does not matter.
+constexpr int kChunkDwords = 2048;
+constexpr int kChunkBytes = 4 * kChunkDwords;
+
+template <int E>
+__global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem *items, const int64_t *prefix, char *ws, int n, int oW, int planes) {
+  __shared__ uint32_t seg[kChunkDwords];
+  const int64_t unit = blockIdx.x;
+  int lo = 0, hi = n;  // the item whose units hold `unit`: prefix[lo] <= unit < prefix[lo + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (prefix[mid] <= unit) lo = mid; else hi = mid;
+  }
+  const AAManyItem &it = items[lo];
+  int64_t u = unit - prefix[lo];
+  const int nstrips = (oW + AA_MANY_STRIP - 1) / AA_MANY_STRIP;
+  const int strip = (int)(u % nstrips);
+  u /= nstrips;
+  const int hull_h = it.hull_h, hull_w = it.hull_w;
+  const int row = (int)(u % hull_h);
+  const int plane = (int)(u / hull_h);
+  if (plane >= planes) return;  // (never: the grid is prefix[n]; uniform per workgroup)
+  const int x0 = strip * AA_MANY_STRIP;
+  const int x1 = x0 + AA_MANY_STRIP < oW ? x0 + AA_MANY_STRIP : oW;
+  const int32_t *xmin_p = (const int32_t *)(ws + it.tab_w);
+  const int32_t *xsize_p = xmin_p + oW;
+  const int32_t *w_all = xsize_p + oW;
+  const int ksize = it.ksize_w;
+  // window starts and ends do not decrease with the output index: the strip's windows cover [first start, last end)
+  int seg0 = xmin_p[x0], seg1 = xmin_p[x1 - 1] + xsize_p[x1 - 1];
+  if (seg0 < 0) seg0 = 0;
+  if (seg1 > hull_w) seg1 = hull_w;
+  const uint8_t *rowp = it.src + (int64_t)plane * it.plane_stride + (int64_t)(it.oy + row) * it.row_stride + (int64_t)it.ox * E;
+
+  const int j = threadIdx.x;
+  const int x = x0 + j / E, c = j % E;
+  const bool active = x < x1;
+  int mx = 0, ms = 0;
+  const int32_t *wp = w_all;
+  if (active) {
+    mx = xmin_p[x];
+    ms = xsize_p[x];
+    if (ms > ksize) ms = ksize;
+    wp = w_all + (size_t)x * ksize;
+  }
+  int32_t ss = 1 << 21;
+  constexpr int kChunkCols = (kChunkBytes - 4) / E;
+  const uint8_t *lds = (const uint8_t *)seg;
+  for (int c0 = seg0; c0 < seg1; c0 += kChunkCols) {
+    const int c1 = c0 + kChunkCols < seg1 ? c0 + kChunkCols : seg1;
+    const uint8_t *a = rowp + (int64_t)c0 * E, *a_end = rowp + (int64_t)c1 * E;
+    const int shift = (int)((uintptr_t)a & 3);
+    const uint8_t *a4 = a - shift;
+    const int ndw = (shift + (c1 - c0) * E + 3) >> 2;
+    __syncthreads();  // (the previous chunk has been consumed)
+    for (int i = j; i < ndw; i += AA_MANY_STRIP * E) {
+      const uint8_t *p = a4 + 4 * (int64_t)i;
+      uint32_t v;
+      if (p >= a && p + 4 <= a_end) {
+        v = *(const uint32_t *)p;
+      } else {
+        v = 0;
+        for (int b = 0; b < 4; b++)
+          if (p + b >= a && p + b < a_end) v |= (uint32_t)p[b] << (8 * b);
+      }
+      seg[i] = v;
+    }
+    __syncthreads();
+    if (active) {
+      const int k_lo = (mx > c0 ? mx : c0) - mx;
+      const int k_hi = (mx + ms < c1 ? mx + ms : c1) - mx;
+      const int at = shift + (mx - c0) * E + c;  // (k >= k_lo keeps the index inside the chunk)
+      for (int k = k_lo; k < k_hi; k++) ss += (int32_t)lds[at + k * E] * wp[k];
+    }
+  }
+  if (active) {
+    uint8_t *inter = (uint8_t *)ws + it.inter + ((int64_t)plane * hull_h + row) * aa_many_inter_pitch(oW, E);
+    inter[x0 * E + j] = clip8(ss);
+  }
+}
+
+// ---- 3. vertical pass --------------------------------------------------------------------------------------------------------------------
+// Lane j owns bytes [4j, 4j + 4) of the output row, whatever they are (columns of a plane, channels of interleaved pixels): one aligned
+// dword load per tap row of the intermediate (its rows start on a dword), four sums, one dword store where the output address is
+// dword-aligned and all four bytes exist, byte stores otherwise.
+__global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const char *ws, uint8_t *out, int oH, int oW, int planes, int E, int nstrips) {
+  int64_t u = blockIdx.x;
+  const int strip = (int)(u % nstrips);
+  u /= nstrips;
+  const int y = (int)(u % oH);
+  u /= oH;
+  const int plane = (int)(u % planes);
+  const AAManyItem &it = items[u / planes];
+  const int rowbytes = oW * E;
+  const int b = (strip * 256 + (int)threadIdx.x) * 4;
+  if (b >= rowbytes) return;
+  const int32_t *xmin_p = (const int32_t *)(ws + it.tab_h);
+  const int32_t *xsize_p = xmin_p + oH;
+  const int ksize = it.ksize_h;
+  const int32_t *wp = xsize_p + oH + (size_t)y * ksize;
+  int r0 = xmin_p[y], nr = xsize_p[y];
+  if (nr > ksize) nr = ksize;
+  if (r0 < 0) r0 = 0;
+  if (r0 + nr > it.hull_h) nr = it.hull_h - r0;
+  const int64_t pitch = aa_many_inter_pitch(oW, E);
+  const uint8_t *ip = (const uint8_t *)ws + it.inter + ((int64_t)plane * it.hull_h + r0) * pitch + b;
+  int32_t s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21, s3 = 1 << 21;
+  for (int k = 0; k < nr; k++) {
+    const uint32_t v = *(const uint32_t *)(ip + k * pitch);
+    const int32_t wk = wp[k];
+    s0 += (int32_t)(v & 255u) * wk;
+    s1 += (int32_t)((v >> 8) & 255u) * wk;
+    s2 += (int32_t)((v >> 16) & 255u) * wk;
+    s3 += (int32_t)(v >> 24) * wk;
+  }
+  const uint32_t r0b = clip8(s0), r1b = clip8(s1), r2b = clip8(s2), r3b = clip8(s3);
+  uint8_t *op = out + (((int64_t)(u / planes) * planes + plane) * oH + y) * rowbytes + b;
+  const int nb = rowbytes - b < 4 ? rowbytes - b : 4;
+  if (nb == 4 && ((uintptr_t)op & 3) == 0) {
+    *(uint32_t *)op = r0b | (r1b << 8) | (r2b << 16) | (r3b << 24);
+  } else {
+    op[0] = (uint8_t)r0b;
+    if (nb > 1) op[1] = (uint8_t)r1b;
+    if (nb > 2) op[2] = (uint8_t)r2b;
+    if (nb > 3) op[3] = (uint8_t)r3b;
+  }
+}
+
+}  // namespace
+
+// ---- host: the planner -------------------------------------------------------------------------------------------------------------------
+size_t aa_many_desc_size(int64_t n) {
+  if (n < 0) return 0;
+  return sizeof(AAManyHeader) + (size_t)n * sizeof(AAManyItem) + ((size_t)n + 1) * sizeof(int64_t);
+}
+
+// The hull [o, e) of an axis: the first output's window start and the last output's window end, each clipped to the axis
+// (boxmath.axis_hull; the same pil_window the table kernel evaluates).
+static void axis_hull(int filter, int64_t in_size, int64_t out_size, double in0, double in1, int on, int64_t *o, int64_t *e) {
+  const BoxArgs bx = {in0, in1, 0, on};
+  const PilWindow first = pil_window(0, filter, (int)in_size, (int)out_size, bx);
+  const PilWindow last = pil_window((int)out_size - 1, filter, (int)in_size, (int)out_size, bx);
+  *o = first.xmin;
+  *e = (int64_t)last.xmin + last.xsize;
+}
+
+int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, void *desc_host,
+                      size_t desc_bytes, size_t *workspace_bytes) {
+  if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  const int64_t kMax = INT32_MAX / 4;
+  if (n < 0 || n > kMax || C < 1 || C > 4 || oH <= 0 || oW <= 0 || oH > kMax || oW > kMax) return AA_ERR_BAD_SHAPE;
+  if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
+  if (desc_bytes < aa_many_desc_size(n)) return AA_ERR_WORKSPACE;
+  const int E = layout == AA_NHWC ? (int)C : 1;
+  const int64_t planes = layout == AA_NHWC ? 1 : C;
+  const int64_t pitch = aa_many_inter_pitch(oW, E);
+  const int64_t nstrips = (oW + AA_MANY_STRIP - 1) / AA_MANY_STRIP;
+  const int64_t vstrips = (oW * E + AA_MANY_VBYTES - 1) / AA_MANY_VBYTES;
+  if (n * planes * oH * vstrips > INT32_MAX || n * (oH + oW) > (int64_t)INT32_MAX * 256) return AA_ERR_BAD_SHAPE;  // (grids of the launches)
+
+  AAManyHeader *hd = (AAManyHeader *)desc_host;
+  AAManyItem *items = (AAManyItem *)(hd + 1);
+  int64_t *prefix = (int64_t *)(items + n);
+  size_t off = 0;  // the arena first, then the intermediates
+  int64_t units = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const aa_many_image &im = images[i];
+    AAManyItem it;
+    memset(&it, 0, sizeof(it));
+    if (!im.data_dev) return AA_ERR_NULL;
+    if (im.H <= 0 || im.W <= 0 || im.H > kMax || im.W > kMax) return AA_ERR_BAD_SHAPE;
+    // (the stride of an axis of one element never matters)
+    if (layout == AA_NHWC ? ((C > 1 && im.stride_ch != 1) || (im.W > 1 && im.stride_px != C)) : (im.W > 1 && im.stride_px != 1)) return AA_ERR_STRIDES;
+    double x0 = 0.0, y0 = 0.0, x1 = (double)im.W, y1 = (double)im.H;
+    int on = 0;
+    if (im.has_box) {  // Pillow's C takes the box as floats
+      x0 = (double)(float)im.box[0]; y0 = (double)(float)im.box[1]; x1 = (double)(float)im.box[2]; y1 = (double)(float)im.box[3];
+      if (!(x0 >= 0.0) || !(y0 >= 0.0) || !(x1 <= (double)im.W) || !(y1 <= (double)im.H)) return AA_ERR_BAD_SHAPE;  // beyond the image (or NaN)
+      if (!(x1 - x0 > 0.0) || !(y1 - y0 > 0.0)) return AA_ERR_BAD_SHAPE;                                           // empty
+      on = !(x0 == 0.0 && y0 == 0.0 && x1 == (double)im.W && y1 == (double)im.H);  // a full box is no box
+    }
+    int64_t oy, ey, ox, ex;
+    axis_hull(filter, im.H, oH, y0, y1, on, &oy, &ey);
+    axis_hull(filter, im.W, oW, x0, x1, on, &ox, &ex);
+    if (ey <= oy || ex <= ox) return AA_ERR_BAD_SHAPE;
+    const int kh = on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ey - oy, oH, y0, y1) : aa_table_ksize(filter, AA_TABLE_PIL, im.H, oH, 0, 0.0);
+    if (kh < 0) return kh;
+    const int kw = on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ex - ox, oW, x0, x1) : aa_table_ksize(filter, AA_TABLE_PIL, im.W, oW, 0, 0.0);
+    if (kw < 0) return kw;
+    it.src = (const uint8_t *)im.data_dev;
+    it.row_stride = im.stride_row;
+    it.plane_stride = layout == AA_NHWC ? 0 : (C > 1 ? im.stride_ch : 0);
+    it.in0_h = y0; it.in1_h = y1; it.in0_w = x0; it.in1_w = x1;
+    it.oy = (int32_t)oy; it.hull_h = (int32_t)(ey - oy); it.ox = (int32_t)ox; it.hull_w = (int32_t)(ex - ox);
+    it.ksize_h = kh; it.ksize_w = kw;
+    it.box_on = on;
+    it.tab_h = (int64_t)off;
+    off += aa_many_table_bytes(oH, kh);
+    it.tab_w = (int64_t)off;
+    off += aa_many_table_bytes(oW, kw);
+    prefix[i] = units;
+    units += planes * (ey - oy) * nstrips;
+    if (units > INT32_MAX) return AA_ERR_BAD_SHAPE;  // (one grid)
+    items[i] = it;
+  }
+  prefix[n] = units;
+  for (int64_t i = 0; i < n; i++) {
+    items[i].inter = (int64_t)off;
+    off += aa_align16((size_t)(planes * items[i].hull_h * pitch));
+  }
+  memset(hd, 0, sizeof(*hd));
+  hd->magic = AA_MANY_MAGIC;
+  hd->n = (int32_t)n; hd->C = (int32_t)C; hd->oH = (int32_t)oH; hd->oW = (int32_t)oW;
+  hd->filter = filter; hd->layout = layout;
+  hd->hunits = units;
+  hd->ws_bytes = (int64_t)off;
+  *workspace_bytes = off;
+  return AA_OK;
+}
+
+// ---- host: the three launches ------------------------------------------------------------------------------------------------------------
+int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
+                      void *workspace_dev, size_t workspace_bytes, hipStream_t stream) {
+  const AAManyHeader *hd = (const AAManyHeader *)desc_host;
+  if (hd->magic != AA_MANY_MAGIC || hd->n != n || hd->C != C || hd->oH != oH || hd->oW != oW || hd->layout != layout) return AA_ERR_BAD_SHAPE;
+  if (n == 0) return AA_OK;
+  if (workspace_bytes < (size_t)hd->ws_bytes) return AA_ERR_WORKSPACE;
+  if (((uintptr_t)workspace_dev & 15) || ((uintptr_t)desc_dev & 7)) return AA_ERR_BAD_SHAPE;
+  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
+  const int64_t *prefix = (const int64_t *)(items + n);
+  const int E = layout == AA_NHWC ? (int)C : 1;
+  const int planes = layout == AA_NHWC ? 1 : (int)C;
+  char *ws = (char *)workspace_dev;
+
+  const int64_t tthreads = n * (oH + oW);
+  hipLaunchKernelGGL(many_tables, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, items, ws, n, (int)oH, (int)oW, hd->filter);
+  const dim3 hgrid((unsigned)hd->hunits);
+  switch (E) {
+    case 1: hipLaunchKernelGGL(many_hpass<1>, hgrid, dim3(AA_MANY_STRIP * 1), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
+    case 2: hipLaunchKernelGGL(many_hpass<2>, hgrid, dim3(AA_MANY_STRIP * 2), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
+    case 3: hipLaunchKernelGGL(many_hpass<3>, hgrid, dim3(AA_MANY_STRIP * 3), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
+    default: hipLaunchKernelGGL(many_hpass<4>, hgrid, dim3(AA_MANY_STRIP * 4), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
+  }
+  const int vstrips = (int)((oW * E + AA_MANY_VBYTES - 1) / AA_MANY_VBYTES);
+  hipLaunchKernelGGL(many_vpass, dim3((unsigned)(n * planes * oH * vstrips)), dim3(256), 0, stream, items, (const char *)ws, (uint8_t *)out_dev, (int)oH,
+                     (int)oW, planes, E, vstrips);
+  AA_HIP_CHECK_LAUNCH();
+  return AA_OK;
+}

@@ -38,6 +38,9 @@ Differences, all additive:
     ``Image.thumbnail`` does with 2.0.  The result is Pillow's ``reducing_gap`` result, not the plain one.  Two launches plus the table
     build, through a temporary uint8 tensor in the input's layout;
   * ``reduce(input, factor, box=None, alpha=False)``: Pillow's ``Image.reduce`` (integer box means), bit-exact;
+  * ``resize_many(images, output_size, mode, boxes=None)``: a LIST of uint8 images of different sizes, each with its own box, into one
+    dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
+    whatever N, no table cache traffic, no synchronisation;
   * the same callables are registered as ``torch.ops.extension_interpolate.*``.
 """
 from __future__ import annotations
@@ -49,7 +52,7 @@ import torch
 
 from . import _lib, boxmath, tables
 
-__all__ = ["reduce", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+__all__ = ["reduce", "resize_many", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -404,6 +407,148 @@ def reduce(input: torch.Tensor, factor, box: Optional[Sequence[int]] = None, *, 
             _lib.check(L.aa_unpremultiply_u8(out.data_ptr(), layout, n, c, oh, ow, stream), "reduce")
     if channels_last and layout == _lib.NCHW:
         out = out.contiguous(memory_format=torch.channels_last)
+    return out
+
+
+_MANY_FILTERS = {"linear_forward": _lib.FILTER_LINEAR, "cubic_forward": _lib.FILTER_CUBIC, "nearest_forward": _lib.FILTER_BOX,
+                 "lanczos_forward": _lib.FILTER_LANCZOS, "hamming_forward": _lib.FILTER_HAMMING}
+
+
+def _many_class(t: torch.Tensor):
+    """Layout class of one [C, H, W] item as it lies in memory: -> (interleaved pixels?, planar?).  The stride of an axis of one element
+    never matters, so a single-channel image is both."""
+    c, h, w = t.shape
+    sc, sh, sw = t.stride()
+    if min(sc, sh, sw) < 0:
+        return False, False
+    inter = (c == 1 or sc == 1) and (w == 1 or sw == c)
+    planar = w == 1 or sw == 1
+    return inter, planar
+
+
+def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, boxes=None, channels: Optional[int] = None,
+                alpha: bool = False, reducing_gap: Optional[float] = None, uint8_mode: Optional[str] = None, out_dtype=None,
+                out_format: Optional[str] = None, mean=None, std=None, align_corners: bool = False,
+                scale_factors: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """Resize a list of uint8 images of different sizes into one batch: ``y[i]`` is ``<mode>_forward(images[i][None], output_size,
+    box=boxes[i])[0]`` bit for bit, i.e. ``PIL.Image.resize((ow, oh), FILTER, box=boxes[i])``.
+
+    ``images``: a sequence of N uint8 GPU tensors [C, H_i, W_i] (or [1, C, H_i, W_i]), or one [N, C, H, W] tensor whose slices are the
+    items.  Same C (1..4) and device for all.  Items are read where they lie, at any row pitch, plane pitch and byte offset (crops,
+    slices), in one of two layout classes: interleaved pixels (``hwc.permute(2, 0, 1)``: the result is channels_last) or planes (rows of
+    consecutive bytes: the result is contiguous).  An item in neither form is copied into the class of the others; of two classes in
+    one list the minority is copied (a tie: the planar items).
+    ``boxes``: None, or N entries, each None or (x0, y0, x1, y1) — PILLOW'S ORDER, X FIRST, unlike ``output_size`` = (H, W).
+    ``mode``: bilinear | bicubic | nearest (the box filter) | lanczos | hamming.  Pillow's arithmetic only.
+    N == 0 gives an empty [0, C, oh, ow] tensor; a list then says its C with ``channels=``.
+
+    Three launches and one non-blocking copy of a packed descriptor whatever N; every hull, ksize and offset is host arithmetic
+    (aa_many_plan), so nothing is read back, and the table caches are neither read nor written.  Not built here: alpha, reducing_gap,
+    uint8_mode="harness", float images or outputs, align_corners, scale factors (each raises NotImplementedError)."""
+    from .functional import _MODES
+
+    name = "resize_many"
+    for opt, given in (("alpha", bool(alpha)), ("reducing_gap", reducing_gap is not None), ("out_dtype", out_dtype is not None),
+                       ("out_format", out_format is not None), ("mean", mean is not None), ("std", std is not None),
+                       ("align_corners", bool(align_corners)), ("scale_factors", scale_factors is not None)):
+        if given:
+            raise NotImplementedError(f"{name}(): {opt} is not built for a list of images; the single-image forwards have it")
+    if (uint8_mode or _uint8_mode) != "pil":
+        if (uint8_mode or _uint8_mode) != "harness":
+            raise ValueError("uint8_mode must be 'pil' or 'harness'")
+        raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
+    if mode not in _MODES:
+        raise ValueError(mode)
+    filter_id = _MANY_FILTERS[_MODES[mode]]
+    if len(output_size) != 2:
+        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
+    oh, ow = int(output_size[0]), int(output_size[1])
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise RuntimeError(f"{name}(): one tensor must be [N, C, H, W], got {list(images.shape)}")
+        if channels is None:
+            channels = int(images.shape[1])
+        items = list(images.unbind(0))
+        dev0 = images.device
+    else:
+        items, dev0 = [], None
+        for i, t in enumerate(images):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}(): images[{i}] must be Tensor")
+            if t.dim() == 4 and t.shape[0] == 1:
+                t = t[0]
+            if t.dim() != 3:
+                raise RuntimeError(f"{name}(): images[{i}] must be [C, H, W] or [1, C, H, W], got {list(t.shape)}")
+            items.append(t)
+    n = len(items)
+    if n == 0 and channels is None:
+        raise ValueError(f"{name}(): an empty list needs channels= (the C of the [0, C, oh, ow] result)")
+    c = int(channels) if channels is not None else int(items[0].shape[0])
+    if not (1 <= c <= 4):
+        raise ValueError(f"{name}(): images of 1 to 4 channels, got C = {c}")
+    if not (oh > 0 and ow > 0):
+        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    if boxes is not None and len(boxes) != n:
+        raise ValueError(f"{name}(): boxes must hold one entry per image ({n}), got {len(boxes)}")
+    checked = []
+    for i, t in enumerate(items):
+        if t.dtype != torch.uint8:
+            raise NotImplementedError(f"{name}(): images[{i}] is {t.dtype}; a list of images is Pillow's uint8 resize only")
+        if int(t.shape[0]) != c:
+            raise ValueError(f"{name}(): every image must have the same C: images[{i}] has {int(t.shape[0])}, expected {c}")
+        h, w = int(t.shape[1]), int(t.shape[2])
+        if not (h > 0 and w > 0):
+            raise RuntimeError(f"Input and output sizes should be greater than 0, but got input (H: {h}, W: {w}) output (H: {oh}, W: {ow})")
+        if t.device != items[0].device:
+            raise ValueError(f"{name}(): every image must be on the same device: images[{i}] is on {t.device}, images[0] on {items[0].device}")
+        bx = boxes[i] if boxes is not None else None
+        if bx is not None:
+            bx = boxmath.box_f32(boxmath.check_box(bx, w, h))  # Pillow's checks and wording; its C takes the box as floats
+        checked.append(bx)
+    if n == 0:
+        if dev0 is None:
+            dev0 = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        return torch.empty((0, c, oh, ow), dtype=torch.uint8, device=dev0)
+    for t in items:
+        _require_gpu(t, name)
+    dev = items[0].device
+    # one layout class for the call: the majority's; whoever is not in it is copied
+    classes = [_many_class(t) for t in items]
+    n_inter = sum(1 for a, b in classes if a and not b)
+    n_planar = sum(1 for a, b in classes if b and not a)
+    interleaved = c > 1 and n_inter > 0 and n_inter >= n_planar
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        recs = (_lib.ManyImage * n)()
+        keep = []
+        for i, t in enumerate(items):
+            if not classes[i][0 if interleaved else 1]:
+                t = t.permute(1, 2, 0).contiguous().permute(2, 0, 1) if interleaved else t.contiguous()
+                keep.append(t)
+            r = recs[i]
+            r.data_dev = t.data_ptr()
+            r.H, r.W = int(t.shape[1]), int(t.shape[2])
+            # (the stride of an axis of one element is arbitrary: hand over the class's own)
+            r.stride_ch = 1 if interleaved else (t.stride(0) if c > 1 else 0)
+            r.stride_row = t.stride(1) if r.H > 1 else 0
+            r.stride_px = (c if interleaved else 1)
+            bx = checked[i]
+            if bx is not None:
+                r.has_box = 1
+                r.box[0], r.box[1], r.box[2], r.box[3] = bx
+        desc_bytes = L.aa_many_desc_bytes(n)
+        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
+        ws_bytes = ctypes.c_size_t(0)
+        _lib.check(L.aa_many_plan(filter_id, layout, n, c, oh, ow, recs, desc_host.data_ptr(), desc_bytes, ctypes.byref(ws_bytes)), name)
+        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
+        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
+        ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
+        out = torch.empty((n, c, oh, ow), dtype=torch.uint8, device=dev,
+                          memory_format=torch.channels_last if interleaved else torch.contiguous_format)
+        rc = L.aa_resample_many_u8(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, name)
     return out
 
 
@@ -811,6 +956,31 @@ def _register_torch_ops() -> None:
     lib.impl("reduce", lambda input, factor, box=None, alpha=False: reduce(
         input, tuple(factor) if len(factor) != 1 else factor[0], box, alpha=alpha), "CUDA")
     lib.impl("reduce", _reduce_meta, "Meta")
+
+    # a list of images into one batch; boxes flattened to 4 N values, a full-image box standing for None
+    lib.define('resize_many(Tensor[] images, int[] output_size, str mode="bilinear", float[]? boxes=None) -> Tensor')
+
+    def _many_boxes(images, boxes):
+        if boxes is None:
+            return None
+        if len(boxes) != 4 * len(images):
+            raise ValueError(f"resize_many(): boxes must hold 4 values per image ({4 * len(images)}), got {len(boxes)}")
+        return [tuple(boxes[4 * i:4 * i + 4]) for i in range(len(images))]
+
+    def _many_meta(images, output_size, mode="bilinear", boxes=None):
+        if not images:
+            raise ValueError("resize_many(): the op needs at least one image (an empty list has no C)")
+        items = [t[0] if t.dim() == 4 else t for t in images]
+        classes = [_many_class(t) for t in items]
+        n_inter = sum(1 for a, b in classes if a and not b)
+        n_planar = sum(1 for a, b in classes if b and not a)
+        c = int(items[0].shape[0])
+        mf = torch.channels_last if (c > 1 and n_inter > 0 and n_inter >= n_planar) else torch.contiguous_format
+        return torch.empty((len(items), c, output_size[0], output_size[1]), dtype=items[0].dtype, device=items[0].device, memory_format=mf)
+
+    lib.impl("resize_many", lambda images, output_size, mode="bilinear", boxes=None: resize_many(
+        list(images), output_size, mode, boxes=_many_boxes(images, boxes)), "CUDA")
+    lib.impl("resize_many", _many_meta, "Meta")
 
     for name, fn in bwds.items():
         lib.impl(name, (lambda f: lambda grad_output, output_size, input_size, align_corners=False:

@@ -1,0 +1,192 @@
+#!/usr/bin/env python
+"""A loader's batch — N images of N sizes, one RandomResizedCrop box each, all to 224 x 224 — three ways, alternating in one process:
+
+  (a) the per-image loop with boxes never seen before: every call builds two box tables and reads their headers back (one stream
+      synchronisation per image) — the case resize_many is for;
+  (b) the same loop with fixed boxes and warm caches (the 32-entry box LRU widened so that all N pairs stay in it);
+  (c) resize_many: one call per batch, fresh boxes every batch (it has no cache to warm).
+
+Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
+min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
+results into one tensor; (c) writes the batch.
+
+  python tools/resize_many_bench.py                      # the timing table
+  python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
+                                                         # kernel trace; every input reaches the GPU in ONE host-to-device copy)
+  python tools/resize_many_bench.py --summarise DIR      # kernels and copies per call, kernel time and bytes / time from that trace
+"""
+import argparse
+import csv
+import glob
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+N, OUT, SEED, WARM_CALLS = 64, (224, 224), 7, 3
+MODES = {"bilinear": "linear", "bicubic": "cubic"}
+
+
+def sizes(rng):
+    return [(int(rng.integers(256, 1025)), int(rng.integers(256, 1025))) for _ in range(N)]
+
+
+def random_resized_crop_box(rng, h, w):
+    """torchvision's RandomResizedCrop.get_params (scale 0.08 .. 1, ratio 3/4 .. 4/3) -> Pillow's (x0, y0, x1, y1)."""
+    area = h * w
+    for _ in range(10):
+        target = area * rng.uniform(0.08, 1.0)
+        ratio = np.exp(rng.uniform(np.log(3 / 4), np.log(4 / 3)))
+        cw, ch = int(round(np.sqrt(target * ratio))), int(round(np.sqrt(target / ratio)))
+        if 0 < cw <= w and 0 < ch <= h:
+            y0, x0 = int(rng.integers(0, h - ch + 1)), int(rng.integers(0, w - cw + 1))
+            return (x0, y0, x0 + cw, y0 + ch)
+    return (0, 0, w, h)
+
+
+def algorithm_bytes(shapes, boxes, filter_name):
+    """Bytes the three-launch algorithm moves for one batch: every item's hull in, its intermediate out and in again, the batch out."""
+    from interpolate_antialiasing_amd import boxmath
+
+    oh, ow = OUT
+    hull = inter = 0
+    for (h, w), bx in zip(shapes, boxes):
+        b = boxmath.box_f32(bx)
+        oy, ey = boxmath.axis_hull(h, oh, b[1], b[3], filter_name)
+        ox, ex = boxmath.axis_hull(w, ow, b[0], b[2], filter_name)
+        hull += (ey - oy) * (ex - ox) * 3
+        inter += (ey - oy) * ow * 3
+    return hull, inter, N * oh * ow * 3
+
+
+def summarise(trace_dir, calls):
+    """Kernels and copies per resize_many call, and kernel time per launch, from a profiler's kernel / memory-copy trace CSVs."""
+    rows = []
+    for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as f:
+            rows += list(csv.DictReader(f))
+    ours = {}
+    for r in rows:
+        name = r.get("Kernel_Name", "")
+        for k in ("many_tables", "many_hpass", "many_vpass"):
+            if k in name:
+                ours.setdefault(k, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    copies = []
+    for path in glob.glob(os.path.join(trace_dir, "**", "*memory_copy_trace.csv"), recursive=True):
+        with open(path) as f:
+            copies += list(csv.DictReader(f))
+    h2d = sum(1 for r in copies if "HOST_TO_DEVICE" in (r.get("Direction", "") + r.get("Kind", "")).upper())
+    print(f"trace: {len(rows)} kernel launches in all, {sum(len(v) for v in ours.values())} of them resize_many's, over {calls} calls")
+    for k in ("many_tables", "many_hpass", "many_vpass"):
+        v = ours.get(k, [])
+        if v:
+            steady = v[WARM_CALLS:] if len(v) > WARM_CALLS else v
+            print(f"  {k}: {len(v) / calls:.2f} launches per call, median {statistics.median(steady):.1f} us, min {min(steady):.1f}, max {max(steady):.1f}")
+    print(f"  kernels per call: {sum(len(v) for v in ours.values()) / calls:.2f} (expected 3, whatever N)")
+    print(f"  host-to-device copies in the trace: {h2d} = 1 (all inputs, at set-up) + {(h2d - 1) / calls:.2f} per call (expected 1: the descriptor)")
+    return {k: statistics.median(v[WARM_CALLS:] if len(v) > WARM_CALLS else v) for k, v in ours.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--batches", type=int, default=20)
+    ap.add_argument("--trace", type=int, default=0)
+    ap.add_argument("--trace-mode", default="bilinear")
+    ap.add_argument("--summarise", default=None)
+    args = ap.parse_args()
+
+    rng = np.random.default_rng(SEED)
+    shapes = sizes(rng)
+    if args.summarise:
+        calls = WARM_CALLS + max(args.trace, 1)
+        med = summarise(args.summarise, calls)
+        brng = np.random.default_rng(SEED + 1)
+        boxes = [random_resized_crop_box(brng, h, w) for h, w in shapes]
+        hull, inter, out = algorithm_bytes(shapes, boxes, MODES[args.trace_mode])
+        print(f"bytes one batch moves ({args.trace_mode}, one draw of boxes): hull in {hull / 1e6:.2f} MB + intermediate {inter / 1e6:.2f} MB twice + out {out / 1e6:.2f} MB")
+        for k, b in (("many_hpass", hull + inter), ("many_vpass", inter + out)):
+            if k in med:
+                print(f"  {k}: {b / 1e6:.2f} MB over {med[k]:.1f} us = {b / med[k] / 1e6:.3f} TB/s")
+        return
+
+    import torch
+
+    from interpolate_antialiasing_amd import extension_interpolate as aa
+    from interpolate_antialiasing_amd import tables
+
+    assert torch.cuda.is_available(), "this benchmark needs the GPU"
+    # every image in one flat buffer, uploaded once; the items are HWC views into it (at whatever alignment their offsets give)
+    flat = rng.integers(0, 256, sum(h * w * 3 for h, w in shapes), dtype=np.uint8)
+    dev_flat = torch.from_numpy(flat).cuda()
+    images, off = [], 0
+    for h, w in shapes:
+        images.append(dev_flat[off:off + h * w * 3].view(h, w, 3).permute(2, 0, 1))
+        off += h * w * 3
+    brng = np.random.default_rng(SEED + 1)
+
+    def fresh_boxes():
+        return [random_resized_crop_box(brng, h, w) for h, w in shapes]
+
+    if args.trace:
+        for _ in range(WARM_CALLS + args.trace):
+            aa.resize_many(images, list(OUT), args.trace_mode, boxes=fresh_boxes())
+        torch.cuda.synchronize()
+        return
+
+    fwd = {"bilinear": aa.linear_forward, "bicubic": aa.cubic_forward}
+    fixed = fresh_boxes()
+    tables.BOX_CACHE_SIZE = max(tables.BOX_CACHE_SIZE, 4 * N)  # (b) only stays warm if the LRU can hold its N pairs
+
+    def loop(mode, boxes):
+        f = fwd[mode]
+        for img, bx in zip(images, boxes):
+            f(img[None], list(OUT), box=bx)
+
+    def timed(fn):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        start.record()
+        for _ in range(args.batches):
+            fn()
+        end.record()
+        torch.cuda.synchronize()
+        return start.elapsed_time(end) / args.batches
+
+    print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+    for mode in MODES:
+        contestants = {
+            "a: per-image loop, unseen boxes": lambda: loop(mode, fresh_boxes()),
+            "b: per-image loop, fixed boxes, warm": lambda: loop(mode, fixed),
+            "c: resize_many": lambda: aa.resize_many(images, list(OUT), mode, boxes=fresh_boxes()),
+        }
+        for fn in contestants.values():  # warm-up of every contestant
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        # (c) gives the loop's bytes on the fixed boxes
+        want = torch.cat([fwd[mode](img[None], list(OUT), box=bx) for img, bx in zip(images, fixed)])
+        assert torch.equal(aa.resize_many(images, list(OUT), mode, boxes=fixed), want), "resize_many differs from the per-image loop"
+        times = {k: [] for k in contestants}
+        for _ in range(args.rounds):
+            for k, fn in contestants.items():
+                times[k].append(timed(fn))
+        print(f"\n{mode}")
+        stat = {}
+        for k, v in times.items():
+            stat[k] = (statistics.median(v), min(v), max(v))
+            print(f"  {k:40s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]")
+        (ma, la, ha), (mb, lb, hb), (mc, lc, hc) = stat.values()
+        gain, spreads = ma - mc, (ha - la) + (hc - lc)
+        verdict = "PASS" if gain > spreads else "FAIL: the design has failed its purpose"
+        print(f"  (c) against (a): {ma / mc:.2f} x; median gain {gain:.3f} ms against the two spreads together {spreads:.3f} ms: {verdict}")
+        print(f"  (c) against (b): {mb / mc:.2f} x (no bar: what a fused single-launch follow-up would have to beat)")
+
+
+if __name__ == "__main__":
+    main()
