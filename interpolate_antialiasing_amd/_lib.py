@@ -6,6 +6,7 @@ needs it (the CPU oracle under oracle/ is test infrastructure and is never impor
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -17,6 +18,21 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "aa_interp.h")
 # enums (include/aa_interp.h)
 AA_OK = 0
 FILTER_LINEAR, FILTER_CUBIC, FILTER_BOX, FILTER_HAMMING, FILTER_LANCZOS = 0, 1, 2, 3, 4
+# The five filters in one place; every table of filter names, ids, modes and supports in the package is derived from this one.
+# support: Pillow's (Resample.c's filter structs, Image._filters_support); op: the stem of its callables' names (<op>_forward, ...).
+Filter = collections.namedtuple("Filter", "id name aliases support op")
+FILTERS = (Filter(FILTER_LINEAR, "linear", ("bilinear",), 1.0, "linear"), Filter(FILTER_CUBIC, "cubic", ("bicubic",), 2.0, "cubic"),
+           Filter(FILTER_BOX, "box", ("nearest",), 0.5, "nearest"), Filter(FILTER_HAMMING, "hamming", (), 1.0, "hamming"),
+           Filter(FILTER_LANCZOS, "lanczos", (), 3.0, "lanczos"))
+FILTER_NAMES = {f.id: f.name for f in FILTERS}
+
+
+def by_filter_name(value) -> dict:
+    """{name or alias: value(filter)} over the five filters."""
+    return {n: value(f) for f in FILTERS for n in (f.name,) + f.aliases}
+
+
+FILTER_IDS = by_filter_name(lambda f: f.id)
 U8, F32, F64, F16, BF16 = 0, 1, 2, 3, 4
 NCHW, NHWC = 0, 1
 TABLE_PIL, TABLE_F32, TABLE_F64 = 0, 1, 2

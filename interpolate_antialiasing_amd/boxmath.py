@@ -11,8 +11,9 @@ import math
 import struct
 from typing import Optional, Sequence, Tuple
 
-# Pillow's filter supports (Resample.c's filter structs; Image._filters_support) by the package's filter names
-SUPPORT = {"box": 0.5, "nearest": 0.5, "linear": 1.0, "bilinear": 1.0, "hamming": 1.0, "cubic": 2.0, "bicubic": 2.0, "lanczos": 3.0}
+from ._lib import by_filter_name  # (ctypes only: nothing is loaded)
+
+SUPPORT = by_filter_name(lambda f: f.support)  # Pillow's filter supports by the package's filter names
 MAX_REDUCE_BLOCK = 65536  # fx * fy the reduce kernel's 32-bit sums hold
 
 

@@ -300,43 +300,41 @@ static int scatter_ksize_for(int filter, int kind, int64_t in_size, int64_t out_
   return (kind == AA_TABLE_PIL || kind == AA_TABLE_F32 || kind == AA_TABLE_F64) ? 6 : 0;
 }
 
+// What every build call works out per table before it launches: its ksize (negative: the status the call returns), scatter ksize and scale into the
+// job spec, and -> the bytes its buffer must hold (0 for a negative ksize).  A box table: in_size is the hull's length, and Pillow's scale comes from the box.
+static size_t table_spec(AATableSpec &s, int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale, void *table,
+                         int box = 0, int64_t origin = 0, double in0 = 0.0, double in1 = 0.0) {
+  const int k = box ? aa_table_ksize_box(filter, kind, in_size, out_size, in0, in1) : aa_table_ksize(filter, kind, in_size, out_size, align_corners, scale);
+  s = AATableSpec{in_size, out_size, (box || k < 0) ? 0.0 : scale_for(kind, in_size, out_size, align_corners, scale), k,
+                  scatter_ksize_for(filter, kind, in_size, out_size), table, box, origin, in0, in1};
+  return k < 0 ? 0 : aa_table_total_bytes(kind, out_size, k) + aa_table_scatter_bytes(kind, in_size, s.scatter_ksize);
+}
+
 size_t aa_table_build_bytes(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale) {
-  const int k = aa_table_ksize(filter, kind, in_size, out_size, align_corners, scale);
-  if (k < 0) return 0;
-  return aa_table_total_bytes(kind, out_size, k) + aa_table_scatter_bytes(kind, in_size, scatter_ksize_for(filter, kind, in_size, out_size));
+  AATableSpec s;
+  return table_spec(s, filter, kind, in_size, out_size, align_corners, scale, nullptr);
 }
 
 int aa_table_build(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale,
                    void *table_dev, size_t table_bytes, aa_stream_t stream) {
-  const int k = aa_table_ksize(filter, kind, in_size, out_size, align_corners, scale);
-  if (k < 0) return k;
+  AATableSpec s;
+  const size_t need = table_spec(s, filter, kind, in_size, out_size, align_corners, scale, table_dev);
+  if (s.ksize < 0) return s.ksize;
   if (!table_dev) return AA_ERR_NULL;
-  const int sk = scatter_ksize_for(filter, kind, in_size, out_size);
-  if (table_bytes < aa_table_total_bytes(kind, out_size, k) + aa_table_scatter_bytes(kind, in_size, sk)) return AA_ERR_WORKSPACE;
-  return aa_launch_table_build(filter, kind, in_size, out_size, align_corners,
-                               scale_for(kind, in_size, out_size, align_corners, scale), k, sk, table_dev,
-                               (hipStream_t)stream);
+  if (table_bytes < need) return AA_ERR_WORKSPACE;
+  return aa_launch_table_jobs(filter, kind, align_corners, &s, 1, (hipStream_t)stream);
 }
 
 int aa_table_build2(int filter, int kind, int align_corners, int64_t in_a, int64_t out_a, double scale_a, void *table_a_dev, size_t bytes_a,
                     int64_t in_b, int64_t out_b, double scale_b, void *table_b_dev, size_t bytes_b, aa_stream_t stream) {
-  const int ka = aa_table_ksize(filter, kind, in_a, out_a, align_corners, scale_a);
-  if (ka < 0) return ka;
-  const int kb = aa_table_ksize(filter, kind, in_b, out_b, align_corners, scale_b);
-  if (kb < 0) return kb;
+  AATableSpec s[2];
+  const size_t need_a = table_spec(s[0], filter, kind, in_a, out_a, align_corners, scale_a, table_a_dev);
+  if (s[0].ksize < 0) return s[0].ksize;
+  const size_t need_b = table_spec(s[1], filter, kind, in_b, out_b, align_corners, scale_b, table_b_dev);
+  if (s[1].ksize < 0) return s[1].ksize;
   if (!table_a_dev || !table_b_dev) return AA_ERR_NULL;
-  const int ska = scatter_ksize_for(filter, kind, in_a, out_a), skb = scatter_ksize_for(filter, kind, in_b, out_b);
-  if (bytes_a < aa_table_total_bytes(kind, out_a, ka) + aa_table_scatter_bytes(kind, in_a, ska)) return AA_ERR_WORKSPACE;
-  if (bytes_b < aa_table_total_bytes(kind, out_b, kb) + aa_table_scatter_bytes(kind, in_b, skb)) return AA_ERR_WORKSPACE;
-  if (!aa_table_pair_fits(in_a, out_a, in_b, out_b)) {  // very large tables: one after the other
-    const int rc = aa_launch_table_build(filter, kind, in_a, out_a, align_corners, scale_for(kind, in_a, out_a, align_corners, scale_a), ka, ska, table_a_dev,
-                                         (hipStream_t)stream);
-    if (rc != AA_OK) return rc;
-    return aa_launch_table_build(filter, kind, in_b, out_b, align_corners, scale_for(kind, in_b, out_b, align_corners, scale_b), kb, skb, table_b_dev,
-                                 (hipStream_t)stream);
-  }
-  return aa_launch_table_build_pair(filter, kind, align_corners, in_a, out_a, scale_for(kind, in_a, out_a, align_corners, scale_a), ka, ska, table_a_dev, in_b,
-                                    out_b, scale_for(kind, in_b, out_b, align_corners, scale_b), kb, skb, table_b_dev, (hipStream_t)stream);
+  if (bytes_a < need_a || bytes_b < need_b) return AA_ERR_WORKSPACE;
+  return aa_launch_table_jobs(filter, kind, align_corners, s, 2, (hipStream_t)stream);
 }
 
 int aa_table_transposed_ksize(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale) {
@@ -433,26 +431,22 @@ int aa_table_ksize_box(int filter, int kind, int64_t hull, int64_t out_size, dou
 }
 
 size_t aa_table_build_bytes_box(int filter, int kind, int64_t hull, int64_t out_size, double in0, double in1) {
-  const int k = aa_table_ksize_box(filter, kind, hull, out_size, in0, in1);
-  if (k < 0) return 0;
-  return aa_table_total_bytes(kind, out_size, k) + aa_table_scatter_bytes(kind, hull, scatter_ksize_for(filter, kind, hull, out_size));
+  AATableSpec s;
+  return table_spec(s, filter, kind, hull, out_size, 0, 0.0, nullptr, 1, 0, in0, in1);
 }
 
 int aa_table_build_box(int filter, int kind, int64_t origin_a, int64_t hull_a, int64_t out_a, double in0_a, double in1_a, void *table_a_dev,
                        size_t bytes_a, int64_t origin_b, int64_t hull_b, int64_t out_b, double in0_b, double in1_b, void *table_b_dev,
                        size_t bytes_b, aa_stream_t stream) {
-  const int ka = aa_table_ksize_box(filter, kind, hull_a, out_a, in0_a, in1_a);
-  if (ka < 0) return ka;
-  const int kb = aa_table_ksize_box(filter, kind, hull_b, out_b, in0_b, in1_b);
-  if (kb < 0) return kb;
+  AATableSpec s[2];
+  const size_t need_a = table_spec(s[0], filter, kind, hull_a, out_a, 0, 0.0, table_a_dev, 1, origin_a, in0_a, in1_a);
+  if (s[0].ksize < 0) return s[0].ksize;
+  const size_t need_b = table_spec(s[1], filter, kind, hull_b, out_b, 0, 0.0, table_b_dev, 1, origin_b, in0_b, in1_b);
+  if (s[1].ksize < 0) return s[1].ksize;
   if (origin_a < 0 || origin_b < 0 || origin_a > INT32_MAX / 4 || origin_b > INT32_MAX / 4) return AA_ERR_BAD_SHAPE;
   if (!table_a_dev || !table_b_dev) return AA_ERR_NULL;
-  const int ska = scatter_ksize_for(filter, kind, hull_a, out_a), skb = scatter_ksize_for(filter, kind, hull_b, out_b);
-  if (bytes_a < aa_table_total_bytes(kind, out_a, ka) + aa_table_scatter_bytes(kind, hull_a, ska)) return AA_ERR_WORKSPACE;
-  if (bytes_b < aa_table_total_bytes(kind, out_b, kb) + aa_table_scatter_bytes(kind, hull_b, skb)) return AA_ERR_WORKSPACE;
-  const AABoxAxis a = {origin_a, hull_a, out_a, in0_a, in1_a, ka, ska, table_a_dev};
-  const AABoxAxis b = {origin_b, hull_b, out_b, in0_b, in1_b, kb, skb, table_b_dev};
-  return aa_launch_table_build_box_pair(filter, a, b, (hipStream_t)stream);
+  if (bytes_a < need_a || bytes_b < need_b) return AA_ERR_WORKSPACE;
+  return aa_launch_table_jobs(filter, kind, 0, s, 2, (hipStream_t)stream);
 }
 
 // ---- ragged batches ------------------------------------------------------------------------------------------------------------------

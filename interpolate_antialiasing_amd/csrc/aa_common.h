@@ -94,12 +94,7 @@ extern int g_aa_plane_groups;
     if (hipGetLastError() != hipSuccess) return AA_ERR_HIP; \
   } while (0)
 
-// entry points implemented in the .hip files and called from aa_api.cpp
-bool aa_table_pair_fits(int64_t in_a, int64_t out_a, int64_t in_b, int64_t out_b);
-int aa_launch_table_build_pair(int filter, int kind, int align_corners, int64_t in_a, int64_t out_a, double scale_a, int ksize_a, int sk_a, void *tab_a,
-                               int64_t in_b, int64_t out_b, double scale_b, int ksize_b, int sk_b, void *tab_b, hipStream_t stream);
-int aa_launch_table_build(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale,
-                          int ksize, int scatter_ksize, void *table_dev, hipStream_t stream);
+// entry points implemented in the .hip files and called from aa_api.cpp (the table builds' launcher: aa_box.h)
 // bytes of the scatter section appended to AA_TABLE_PIL tables (0 when scatter_ksize == 0)
 __host__ __device__ inline size_t aa_table_scatter_pitch(int kind) { return kind == AA_TABLE_F64 ? 64 : 32; }
 __host__ __device__ inline size_t aa_table_scatter_bytes(int kind, int64_t in_size, int scatter_ksize) {

@@ -250,14 +250,9 @@ struct TableJob { aa_table_header h; int in_size, out_size, ksize; double scale;
 template <int KIND>
 __device__ void table_build_body(const aa_table_header &h, int filter, int in_size, int out_size, int ksize, double scale, char *table,
                                  const BoxArgs &bx);
+// One workgroup per table: a grid of one builds `a`, a grid of two the two tables of a call (H and W axis) in one launch
 template <int KIND>
-__global__ void __launch_bounds__(1024) table_build_all(aa_table_header h, int filter, int in_size, int out_size, int ksize, double scale, char *table,
-                                                        BoxArgs bx) {
-  table_build_body<KIND>(h, filter, in_size, out_size, ksize, scale, table, bx);
-}
-// ... and the two tables of a call (H and W axis) as the two workgroups of one launch
-template <int KIND>
-__global__ void __launch_bounds__(1024) table_build_pair(TableJob a, TableJob b, int filter) {
+__global__ void __launch_bounds__(1024) table_build_jobs(TableJob a, TableJob b, int filter) {
   const TableJob &j = blockIdx.x == 0 ? a : b;
   table_build_body<KIND>(j.h, filter, j.in_size, j.out_size, j.ksize, j.scale, j.table, j.bx);
 }
@@ -299,43 +294,6 @@ __device__ void table_build_body(const aa_table_header &h, int filter, int in_si
 
 }  // namespace
 
-static aa_table_header make_header(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, int ksize, int scatter_ksize);
-
-bool aa_table_pair_fits(int64_t in_a, int64_t out_a, int64_t in_b, int64_t out_b) {
-  return out_a <= 16384 && in_a <= 32768 && out_b <= 16384 && in_b <= 32768;
-}
-
-int aa_launch_table_build_pair(int filter, int kind, int align_corners, int64_t in_a, int64_t out_a, double scale_a, int ksize_a, int sk_a, void *tab_a,
-                               int64_t in_b, int64_t out_b, double scale_b, int ksize_b, int sk_b, void *tab_b, hipStream_t stream) {
-  TableJob a = {make_header(filter, kind, in_a, out_a, align_corners, ksize_a, sk_a), (int)in_a, (int)out_a, ksize_a, scale_a, (char *)tab_a,
-                BoxArgs{0.0, (double)in_a, 0, 0}};
-  TableJob b = {make_header(filter, kind, in_b, out_b, align_corners, ksize_b, sk_b), (int)in_b, (int)out_b, ksize_b, scale_b, (char *)tab_b,
-                BoxArgs{0.0, (double)in_b, 0, 0}};
-  if (kind == AA_TABLE_F32) hipLaunchKernelGGL(table_build_pair<AA_TABLE_F32>, dim3(2), dim3(1024), 0, stream, a, b, filter);
-  else if (kind == AA_TABLE_F64) hipLaunchKernelGGL(table_build_pair<AA_TABLE_F64>, dim3(2), dim3(1024), 0, stream, a, b, filter);
-  else hipLaunchKernelGGL(table_build_pair<AA_TABLE_PIL>, dim3(2), dim3(1024), 0, stream, a, b, filter);
-  AA_HIP_CHECK_LAUNCH();
-  return AA_OK;
-}
-
-static int launch_table_build(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale, int ksize, int scatter_ksize,
-                              void *table_dev, const BoxArgs &bx, hipStream_t stream);
-
-int aa_launch_table_build_box_pair(int filter, const AABoxAxis &a, const AABoxAxis &b, hipStream_t stream) {
-  if (!aa_table_pair_fits(a.hull, a.out, b.hull, b.out)) {  // very large tables: one after the other, as aa_table_build2 does
-    const int rc = launch_table_build(filter, AA_TABLE_PIL, a.hull, a.out, 0, 0.0, a.ksize, a.scatter_ksize, a.table, BoxArgs{a.in0, a.in1, (int)a.origin, 1}, stream);
-    if (rc != AA_OK) return rc;
-    return launch_table_build(filter, AA_TABLE_PIL, b.hull, b.out, 0, 0.0, b.ksize, b.scatter_ksize, b.table, BoxArgs{b.in0, b.in1, (int)b.origin, 1}, stream);
-  }
-  TableJob ja = {make_header(filter, AA_TABLE_PIL, a.hull, a.out, 0, a.ksize, a.scatter_ksize), (int)a.hull, (int)a.out, a.ksize, 0.0, (char *)a.table,
-                 BoxArgs{a.in0, a.in1, (int)a.origin, 1}};
-  TableJob jb = {make_header(filter, AA_TABLE_PIL, b.hull, b.out, 0, b.ksize, b.scatter_ksize), (int)b.hull, (int)b.out, b.ksize, 0.0, (char *)b.table,
-                 BoxArgs{b.in0, b.in1, (int)b.origin, 1}};
-  hipLaunchKernelGGL(table_build_pair<AA_TABLE_PIL>, dim3(2), dim3(1024), 0, stream, ja, jb, filter);
-  AA_HIP_CHECK_LAUNCH();
-  return AA_OK;
-}
-
 static aa_table_header make_header(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, int ksize, int scatter_ksize) {
   aa_table_header h = {};
   h.magic = AA_TABLE_MAGIC;
@@ -360,25 +318,13 @@ static aa_table_header make_header(int filter, int kind, int64_t in_size, int64_
   return h;
 }
 
-int aa_launch_table_build(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale,
-                          int ksize, int scatter_ksize, void *table_dev, hipStream_t stream) {
-  return launch_table_build(filter, kind, in_size, out_size, align_corners, scale, ksize, scatter_ksize, table_dev, BoxArgs{0.0, (double)in_size, 0, 0}, stream);
-}
-
-static int launch_table_build(int filter, int kind, int64_t in_size, int64_t out_size, int align_corners, double scale, int ksize, int scatter_ksize,
-                              void *table_dev, const BoxArgs &bx, hipStream_t stream) {
-  const aa_table_header h = make_header(filter, kind, in_size, out_size, align_corners, ksize, scatter_ksize);
-  char *t = (char *)table_dev;
-  if (out_size <= 16384 && in_size <= 32768) {  // one launch, one workgroup (see table_build_all); larger tables: the five launches below
-    if (kind == AA_TABLE_F32)
-      hipLaunchKernelGGL(table_build_all<AA_TABLE_F32>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t, bx);
-    else if (kind == AA_TABLE_F64)
-      hipLaunchKernelGGL(table_build_all<AA_TABLE_F64>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t, bx);
-    else
-      hipLaunchKernelGGL(table_build_all<AA_TABLE_PIL>, dim3(1), dim3(1024), 0, stream, h, filter, (int)in_size, (int)out_size, ksize, scale, t, bx);
-    AA_HIP_CHECK_LAUNCH();
-    return AA_OK;
-  }
+// One launch per phase: a table beyond one workgroup's reach (identity tables of the N-d passes have millions of rows)
+static int launch_table_phases(int filter, int kind, const TableJob &j, hipStream_t stream) {
+  const aa_table_header &h = j.h;
+  const int in_size = j.in_size, out_size = j.out_size, ksize = j.ksize;
+  const double scale = j.scale;
+  const BoxArgs &bx = j.bx;
+  char *t = j.table;
   hipLaunchKernelGGL(table_write_header, dim3(1), dim3(64), 0, stream, h, t);
   const int threads = 128;
   const int blocks = (int)((out_size + threads - 1) / threads);
@@ -415,6 +361,32 @@ static int launch_table_build(int filter, int kind, int64_t in_size, int64_t out
   hipLaunchKernelGGL(table_span_kernel, dim3(blocks), dim3(threads), 0, stream, t, (int)out_size);
   if (h.gather_off) hipLaunchKernelGGL(table_gather_kernel, dim3(blocks), dim3(threads), 0, stream, t, (int)out_size, ksize, h.gather_off);
   AA_HIP_CHECK_LAUNCH();
+  return AA_OK;
+}
+
+int aa_launch_table_jobs(int filter, int kind, int align_corners, const AATableSpec *specs, int n, hipStream_t stream) {
+  TableJob jobs[2];
+  bool fits[2];
+  for (int i = 0; i < n; i++) {
+    const AATableSpec &s = specs[i];
+    jobs[i] = {make_header(filter, kind, s.in_size, s.out_size, align_corners, s.ksize, s.scatter_ksize), (int)s.in_size, (int)s.out_size, s.ksize, s.scale,
+               (char *)s.table, s.box ? BoxArgs{s.in0, s.in1, (int)s.origin, 1} : BoxArgs{0.0, (double)s.in_size, 0, 0}};
+    fits[i] = s.out_size <= 16384 && s.in_size <= 32768;  // (what table_build_body's one workgroup walks in a launch latency or two)
+  }
+  const bool pair = n == 2 && fits[0] && fits[1];
+  for (int i = 0; i < (pair ? 1 : n); i++) {
+    if (!fits[i]) {
+      const int rc = launch_table_phases(filter, kind, jobs[i], stream);
+      if (rc != AA_OK) return rc;
+      continue;
+    }
+    const TableJob &a = jobs[i], &b = jobs[pair ? 1 : i];
+    const dim3 grid(pair ? 2 : 1), block(1024);
+    if (kind == AA_TABLE_F32) hipLaunchKernelGGL(table_build_jobs<AA_TABLE_F32>, grid, block, 0, stream, a, b, filter);
+    else if (kind == AA_TABLE_F64) hipLaunchKernelGGL(table_build_jobs<AA_TABLE_F64>, grid, block, 0, stream, a, b, filter);
+    else hipLaunchKernelGGL(table_build_jobs<AA_TABLE_PIL>, grid, block, 0, stream, a, b, filter);
+    AA_HIP_CHECK_LAUNCH();
+  }
   return AA_OK;
 }
 

@@ -68,10 +68,6 @@ _DTYPE_NAMES = {torch.float16: "Half", torch.bfloat16: "BFloat16", torch.int8: "
                 torch.int32: "Int", torch.int64: "Long", torch.bool: "Bool", torch.uint8: "Byte"}
 
 
-_FILTER_NAMES = {_lib.FILTER_LINEAR: "linear", _lib.FILTER_CUBIC: "cubic", _lib.FILTER_BOX: "box", _lib.FILTER_HAMMING: "hamming",
-                 _lib.FILTER_LANCZOS: "lanczos"}
-
-
 def set_uint8_mode(mode: str) -> None:
     global _uint8_mode
     if mode not in ("pil", "harness"):
@@ -102,29 +98,30 @@ def _check_sizes(input_size: Sequence[int], output_size: Sequence[int]):
     return n, c, h, w, oh, ow
 
 
-def _memory_format(x: torch.Tensor):
-    """input.suggest_memory_format() restricted to the two dense layouts the kernels take; anything else is
-    made contiguous first (the reference walks arbitrary strides through TensorIterator)."""
+def _memory_format(x: torch.Tensor, layout: int = _lib.NCHW) -> torch.Tensor:
+    """The one dense copy of the 2-D resample paths (the reference walks arbitrary strides through TensorIterator): whatever no kernel
+    reads where it lies comes through here, as the part of the image that will be read.  Tests count copies by wrapping this function."""
+    return x.contiguous(memory_format=torch.channels_last if layout == _lib.NHWC else torch.contiguous_format)
+
+
+def _layout_of(x: torch.Tensor, pitched: bool = True):
+    """-> (tensor, layout, strides or None): the tensor as the kernels can read it — dense in one of the two layouts, a pitched view
+    (strides given), or, failing both, a contiguous copy.  Callers pass the part of the image they will read (the hull, the box), so a
+    copy is of that part only.  pitched=False: the caller's entry point has no strided form.
+    A pitched view (aa_resample_fwd_strided) has rows of consecutive elements, any row pitch, and planes uniformly spaced — what a crop
+    x[:, :, y0:y1, x0:x1] or (channels_last) a batch slice of a dense tensor is."""
     if x.is_contiguous():
-        return x, _lib.NCHW
+        return x, _lib.NCHW, None
     if x.is_contiguous(memory_format=torch.channels_last):
-        return x, _lib.NHWC
-    return x.contiguous(), _lib.NCHW
-
-
-def _pitched_view(x: torch.Tensor):
-    """A non-dense 4-D view the kernels can read where it lies (aa_resample_fwd_strided): rows of consecutive elements, any row pitch,
-    planes uniformly spaced — what a crop x[:, :, y0:y1, x0:x1] or (channels_last) a batch slice of a dense tensor is.
-    -> (layout, strides) or None."""
+        return x, _lib.NHWC, None
     n, c, h, w = x.shape
-    sn, sc, sh, sw = x.stride()
-    if min(sn, sc, sh, sw) < 0 or x.numel() == 0:
-        return None
-    if sw == 1 and sh >= w and (c == 1 or n == 1 or sn == c * sc) and (c == 1 or sc >= 1):
-        return _lib.NCHW, (sn, sc, sh, sw)
-    if sc == 1 and sw == c and sh >= w * c and c > 1:
-        return _lib.NHWC, (sn, sc, sh, sw)
-    return None
+    sn, sc, sh, sw = strides = x.stride()
+    if pitched and min(strides) >= 0 and x.numel() != 0:
+        if sw == 1 and sh >= w and (c == 1 or n == 1 or sn == c * sc) and (c == 1 or sc >= 1):
+            return x, _lib.NCHW, strides
+        if sc == 1 and sw == c and sh >= w * c and c > 1:
+            return x, _lib.NHWC, strides
+    return _memory_format(x), _lib.NCHW, None
 
 
 def _table_kind(dtype: torch.dtype, uint8_mode: Optional[str]) -> int:
@@ -154,6 +151,44 @@ def _user_scales(scale_factors, n: int):
     if len(sf) != n or any(v < 0 for v in sf):
         raise RuntimeError(f"scale_factors must hold {n} positive values, got {list(scale_factors)}")
     return sf
+
+
+def _plan_launch(L, th, tw, dt: int, layout: int, n: int, c: int, h: int, w: int, oh: int, ow: int, flags: int, cv=None):
+    """The host-side plan of one launch, made under the device's guard: the two tables' axis descriptors, the workspace size, and the
+    byref objects _launch hands over.  (th, tw ride along to keep the device buffers alive.)  cv: the uint8-to-float entry point's aa_convert."""
+    ah, aw = th.axis(), tw.axis()
+    pah, paw = ctypes.byref(ah), ctypes.byref(aw)
+    if cv is None:
+        ws_bytes = L.aa_workspace_bytes_ex(dt, layout, n, c, h, w, oh, ow, pah, paw, flags)
+    else:
+        ws_bytes = L.aa_workspace_bytes_u8_to_f32(layout, n, c, h, w, pah, paw, ctypes.byref(cv))
+    return (ah, aw, ws_bytes, pah, paw, th, tw)
+
+
+def _launch(L, name: str, x: torch.Tensor, out: torch.Tensor, plan, dt: int, layout: int, n: int, c: int, h: int, w: int, flags: int,
+            strides=None, cv=None) -> bool:
+    """Enqueue the resample of x [n, c, h, w] into out with a plan of _plan_launch: allocates the workspace, launches, checks.  x is dense
+    in `layout`, or the pitched view `strides` describes; then -> False means that no kernel reads this view where it lies and nothing was
+    launched: the caller makes the dense copy of its choice and calls again.  No device guard when x's device is the current one."""
+    dev = x.device
+    if dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            return _launch(L, name, x, out, plan, dt, layout, n, c, h, w, flags, strides, cv)
+    ws_bytes, pah, paw = plan[2:5]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if strides is not None:
+        rc = L.aa_resample_fwd_strided(x.data_ptr(), out.data_ptr(), dt, layout, n, c, h, w, (ctypes.c_int64 * 4)(*strides), pah, paw, flags, stream)
+        if rc == _lib.ERR_STRIDES:
+            return False
+    else:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None  # (held until the launch is enqueued)
+        pws = ws.data_ptr() if ws is not None else None
+        if cv is None:
+            rc = L.aa_resample_fwd_ex(x.data_ptr(), out.data_ptr(), pws, ws_bytes, dt, layout, n, c, h, w, pah, paw, flags, stream)
+        else:
+            rc = L.aa_resample_fwd_u8_to_f32(x.data_ptr(), out.data_ptr(), pws, ws_bytes, layout, n, c, h, w, pah, paw, ctypes.byref(cv), stream)
+    _lib.check(rc, name)
+    return True
 
 
 def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequence[int], align_corners: bool,
@@ -188,13 +223,7 @@ def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequen
         raise NotImplementedError(f'"upsample_generic_Nd" not implemented for \'{_DTYPE_NAMES.get(input.dtype, str(input.dtype))}\'')
     _require_gpu(input, name)
     L = _lib.load()
-    pitched = None
-    if not (input.is_contiguous() or input.is_contiguous(memory_format=torch.channels_last)):
-        pitched = _pitched_view(input)  # a crop / batch slice: read in place when a fused kernel takes it (no .contiguous() round trip)
-    if pitched is not None:
-        x, layout = input, pitched[0]
-    else:
-        x, layout = _memory_format(input)
+    x, layout, strides = _layout_of(input)  # a crop / batch slice is read in place when a fused kernel takes it (no .contiguous() round trip)
     kind = _table_kind(x.dtype, uint8_mode)
     if kind == _lib.TABLE_PIL and align_corners:
         raise NotImplementedError("uint8_mode='pil' has no align_corners (Pillow has none); use uint8_mode='harness'")
@@ -210,51 +239,19 @@ def _forward(filter_id: int, name: str, input: torch.Tensor, output_size: Sequen
     # host-side plan: the two cached tables' axis descriptors and the workspace size for this exact call shape
     key = (filter_id, dt, layout, n, c, h, w, oh, ow, bool(align_corners), kind, sh, sw, dev.index, _lib.fused_epoch, bool(alpha))
     plan = _plans.get(key)
-    cur = torch.cuda.current_device()
     if plan is None:
         with torch.cuda.device(dev):
             th, tw = tables.get_table_pair(filter_id, kind, h, oh, w, ow, align_corners, sh, sw, dev)
-            ah, aw = th.axis(), tw.axis()
-            ws_bytes = L.aa_workspace_bytes_ex(dt, layout, n, c, h, w, oh, ow, ctypes.byref(ah), ctypes.byref(aw), flags)
-        plan = (ah, aw, ws_bytes, ctypes.byref(ah), ctypes.byref(aw), th, tw)  # (th, tw keep the device buffers alive)
+            plan = _plan_launch(L, th, tw, dt, layout, n, c, h, w, oh, ow, flags)
         if len(_plans) > 4096:
             _plans.clear()
         _plans[key] = plan
-    ah, aw, ws_bytes, pah, paw = plan[:5]
-    if pitched is not None:
-        strides = (ctypes.c_int64 * 4)(*pitched[1])
-        with torch.cuda.device(dev):
-            rc = L.aa_resample_fwd_strided(x.data_ptr(), out.data_ptr(), dt, layout, n, c, h, w, strides, pah, paw, flags,
-                                           torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.ERR_STRIDES:
-            _lib.check(rc, name)
-            return out
-        x, layout2 = _memory_format(input)  # no kernel for this view: the dense copy after all (the plan was made for this layout)
-        if layout2 != layout:
+    if not _launch(L, name, x, out, plan, dt, layout, n, c, h, w, flags, strides):
+        x = _memory_format(input)  # no kernel for this view: the dense copy after all, NCHW whatever the view's layout
+        if layout != _lib.NCHW:  # (the plan was made for the view's layout)
             return _forward(filter_id, name, x, output_size, align_corners, uint8_mode, scale_factors, None, None, None, None, precision, alpha)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    if dev.index == cur:
-        rc = L.aa_resample_fwd_ex(x.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, dt, layout,
-                                  n, c, h, w, pah, paw, flags, torch.cuda.current_stream(dev).cuda_stream)
-    else:
-        with torch.cuda.device(dev):
-            rc = L.aa_resample_fwd_ex(x.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, dt,
-                                      layout, n, c, h, w, pah, paw, flags, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, name)
+        _launch(L, name, x, out, plan, dt, layout, n, c, h, w, flags)
     return out
-
-def _layout_of(x: torch.Tensor):
-    """-> (tensor, layout, strides or None): the tensor as the kernels can read it — dense in one of the two layouts, a pitched view
-    (strides given), or, failing both, a contiguous copy.  Callers pass the part of the image they will read (the hull, the box), so a
-    copy is of that part only."""
-    if x.is_contiguous():
-        return x, _lib.NCHW, None
-    if x.is_contiguous(memory_format=torch.channels_last):
-        return x, _lib.NHWC, None
-    pv = _pitched_view(x)
-    if pv is not None:
-        return x, pv[0], pv[1]
-    return x.contiguous(), _lib.NCHW, None
 
 
 def _forward_boxed(filter_id: int, name: str, input: torch.Tensor, output_size: Sequence[int], align_corners: bool, uint8_mode, scale_factors,
@@ -285,7 +282,7 @@ def _forward_boxed(filter_id: int, name: str, input: torch.Tensor, output_size: 
     x = input
     full = boxmath.axis_is_full(w, bx[0], bx[2]) and boxmath.axis_is_full(h, bx[1], bx[3])
     if gap is not None and not (full and (h, w) == (oh, ow)):
-        plan = boxmath.reducing_plan(w, h, ow, oh, _FILTER_NAMES[filter_id], bx, gap)
+        plan = boxmath.reducing_plan(w, h, ow, oh, _lib.FILTER_NAMES[filter_id], bx, gap)
         if plan is not None:
             factor, rb, bx = plan
             boxmath.check_factor(factor)
@@ -321,12 +318,12 @@ def _forward_box(filter_id: int, name: str, input: torch.Tensor, oh: int, ow: in
     outside the hull are neither read nor copied: where no fused kernel takes the view, the dense fallback copies the hull."""
     L = _lib.load()
     n, c, h, w = (int(v) for v in input.shape)
-    fname = _FILTER_NAMES[filter_id]
+    fname = _lib.FILTER_NAMES[filter_id]
     oy, ey = boxmath.axis_hull(h, oh, bx[1], bx[3], fname)
     ox, ex = boxmath.axis_hull(w, ow, bx[0], bx[2], fname)
     if ey <= oy or ex <= ox:
         raise ValueError("box can't be empty")
-    hull, layout, _ = _layout_of(input[:, :, oy:ey, ox:ex])  # (a view no kernel reads: a copy of the hull, never of the image)
+    hull, layout, strides = _layout_of(input[:, :, oy:ey, ox:ex])  # (a view no kernel reads: a copy of the hull, never of the image)
     dev = hull.device
     mf = torch.channels_last if layout == _lib.NHWC else torch.contiguous_format
     out = torch.empty((n, c, oh, ow), dtype=torch.uint8, device=dev, memory_format=mf)
@@ -337,23 +334,10 @@ def _forward_box(filter_id: int, name: str, input: torch.Tensor, oh: int, ow: in
     with torch.cuda.device(dev):
         # (th, tw are held until the launch is enqueued: the LRU may drop them at any later call)
         th, tw = tables.get_box_table_pair(filter_id, (oy, hh, oh, bx[1], bx[3]), (ox, hw, ow, bx[0], bx[2]), dev)
-        ah, aw = th.axis(), tw.axis()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if not hull.is_contiguous(memory_format=mf):
-            pv = _pitched_view(hull)
-            if pv is not None and pv[0] == layout:
-                strides = (ctypes.c_int64 * 4)(*pv[1])
-                rc = L.aa_resample_fwd_strided(hull.data_ptr(), out.data_ptr(), _lib.U8, layout, n, c, hh, hw, strides, ctypes.byref(ah),
-                                               ctypes.byref(aw), flags, stream)
-                if rc != _lib.ERR_STRIDES:
-                    _lib.check(rc, name)
-                    return out
-            hull = hull.contiguous(memory_format=mf)  # no kernel for this view: the dense copy of the hull (not of the image)
-        ws_bytes = L.aa_workspace_bytes_ex(_lib.U8, layout, n, c, hh, hw, oh, ow, ctypes.byref(ah), ctypes.byref(aw), flags)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        rc = L.aa_resample_fwd_ex(hull.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, _lib.U8, layout,
-                                  n, c, hh, hw, ctypes.byref(ah), ctypes.byref(aw), flags, stream)
-    _lib.check(rc, name)
+        plan = _plan_launch(L, th, tw, _lib.U8, layout, n, c, hh, hw, oh, ow, flags)
+        if not _launch(L, name, hull, out, plan, _lib.U8, layout, n, c, hh, hw, flags, strides):
+            hull = _memory_format(hull, layout)  # no kernel for this view: the dense copy of the hull (not of the image), in the hull's layout
+            _launch(L, name, hull, out, plan, _lib.U8, layout, n, c, hh, hw, flags)
     return out
 
 
@@ -410,10 +394,6 @@ def reduce(input: torch.Tensor, factor, box: Optional[Sequence[int]] = None, *, 
     return out
 
 
-_MANY_FILTERS = {"linear_forward": _lib.FILTER_LINEAR, "cubic_forward": _lib.FILTER_CUBIC, "nearest_forward": _lib.FILTER_BOX,
-                 "lanczos_forward": _lib.FILTER_LANCZOS, "hamming_forward": _lib.FILTER_HAMMING}
-
-
 def _many_class(t: torch.Tensor):
     """Layout class of one [C, H, W] item as it lies in memory: -> (interleaved pixels?, planar?).  The stride of an axis of one element
     never matters, so a single-channel image is both."""
@@ -445,8 +425,6 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
     Three launches and one non-blocking copy of a packed descriptor whatever N; every hull, ksize and offset is host arithmetic
     (aa_many_plan), so nothing is read back, and the table caches are neither read nor written.  Not built here: alpha, reducing_gap,
     uint8_mode="harness", float images or outputs, align_corners, scale factors (each raises NotImplementedError)."""
-    from .functional import _MODES
-
     name = "resize_many"
     for opt, given in (("alpha", bool(alpha)), ("reducing_gap", reducing_gap is not None), ("out_dtype", out_dtype is not None),
                        ("out_format", out_format is not None), ("mean", mean is not None), ("std", std is not None),
@@ -457,9 +435,9 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
         if (uint8_mode or _uint8_mode) != "harness":
             raise ValueError("uint8_mode must be 'pil' or 'harness'")
         raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
-    if mode not in _MODES:
+    if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
-    filter_id = _MANY_FILTERS[_MODES[mode]]
+    filter_id = _lib.FILTER_IDS[mode]
     if len(output_size) != 2:
         raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
     oh, ow = int(output_size[0]), int(output_size[1])
@@ -578,7 +556,7 @@ def _forward_to_float(filter_id: int, name: str, input: torch.Tensor, output_siz
         raise RuntimeError(f"Non-empty 4D data tensor expected but got a tensor with sizes {list(input.shape)}")
     _require_gpu(input, name)
     L = _lib.load()
-    x, layout = _memory_format(input)
+    x, layout, _ = _layout_of(input, pitched=False)  # (the uint8-to-float entry point has no strided form)
     if out_format not in (None, "nchw", "nhwc"):
         raise ValueError("out_format must be 'nchw', 'nhwc' or None (same as the input)")
     out_layout = layout if out_format is None else (_lib.NHWC if out_format == "nhwc" else _lib.NCHW)
@@ -603,13 +581,8 @@ def _forward_to_float(filter_id: int, name: str, input: torch.Tensor, output_siz
         return out
     with torch.cuda.device(dev):
         th, tw = tables.get_table_pair(filter_id, _lib.TABLE_F32, h, oh, w, ow, align_corners, sh, sw, dev)
-        ah, aw = th.axis(), tw.axis()
-        ws_bytes = L.aa_workspace_bytes_u8_to_f32(layout, n, c, h, w, ctypes.byref(ah), ctypes.byref(aw), ctypes.byref(cv))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        rc = L.aa_resample_fwd_u8_to_f32(x.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, layout,
-                                         n, c, h, w, ctypes.byref(ah), ctypes.byref(aw), ctypes.byref(cv),
-                                         torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, name)
+        plan = _plan_launch(L, th, tw, _lib.U8, layout, n, c, h, w, oh, ow, 0, cv)
+        _launch(L, name, x, out, plan, _lib.U8, layout, n, c, h, w, 0, None, cv)
     return out
 
 
@@ -633,7 +606,7 @@ def _backward(filter_id: int, name: str, grad_output: torch.Tensor, output_size:
                                   "the gather form (atomic=False), or cast it to float32 for the scatter")
     _require_gpu(grad_output, name)
     L = _lib.load()
-    go, layout = _memory_format(grad_output)
+    go, layout, _ = _layout_of(grad_output, pitched=False)  # (the backward has no strided form)
     dev = go.device
     mf = torch.channels_last if layout == _lib.NHWC else torch.contiguous_format
     gi = torch.empty((n, c, h, w), dtype=go.dtype, device=dev, memory_format=mf)
@@ -644,28 +617,22 @@ def _backward(filter_id: int, name: str, grad_output: torch.Tensor, output_size:
     with torch.cuda.device(dev):
         th = tables.get_table(filter_id, kind, h, oh, align_corners, 0.0, dev)
         tw = tables.get_table(filter_id, kind, w, ow, align_corners, 0.0, dev)
-        s = tables._stream_ptr(dev)
         if atomic:
             ah, aw = th.axis(), tw.axis()
             ws_bytes = L.aa_workspace_bytes_bwd(dt, layout, n, c, h, w, oh, ow)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             rc = L.aa_resample_bwd_atomic(ctypes.c_void_p(go.data_ptr()), ctypes.c_void_p(gi.data_ptr()),
                                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, dt, layout, n, c, h, w,
-                                          ctypes.byref(ah), ctypes.byref(aw), s)
+                                          ctypes.byref(ah), ctypes.byref(aw), tables._stream_ptr(dev))
+            _lib.check(rc, name)
         else:
-            trh = tables.get_transposed_table(th).axis()
-            trw = tables.get_transposed_table(tw).axis()
-            # the gather-form adjoint is a forward resample of grad_out with the transposed tables
-            ws_bytes = L.aa_workspace_bytes(dt, layout, n, c, oh, ow, h, w, ctypes.byref(trh), ctypes.byref(trw))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-            rc = L.aa_resample_bwd(ctypes.c_void_p(go.data_ptr()), ctypes.c_void_p(gi.data_ptr()),
-                                   ctypes.c_void_p(ws.data_ptr() if ws is not None else 0), ws_bytes, dt, layout,
-                                   n, c, h, w, ctypes.byref(trh), ctypes.byref(trw), s)
-    _lib.check(rc, name)
+            # the gather-form adjoint is a forward resample of grad_out with the transposed tables (what aa_resample_bwd does)
+            plan = _plan_launch(L, tables.get_transposed_table(th), tables.get_transposed_table(tw), dt, layout, n, c, oh, ow, h, w, 0)
+            _launch(L, name, go, gi, plan, dt, layout, n, c, oh, ow, 0)
     return gi
 
 
-def _axis_pass_2d(L, x, y, dt, kind, outer, n_in, n_out, inner, table, dev, stream) -> bool:
+def _axis_pass_2d(L, x, y, dt, kind, outer, n_in, n_out, inner, table, dev) -> bool:
     """One separable pass of an N-d resample through the FUSED 2-D kernels: the dense array [outer][n][inner] is a stack of 2-D
     images in which only one axis changes — [1,1,outer,n] -> [1,1,outer,n_out] when inner == 1 (the pass runs along rows),
     [outer,1,n,inner] -> [outer,1,n_out,inner] otherwise (along columns) — and the other axis gets the IDENTITY table (box filter,
@@ -688,11 +655,10 @@ def _axis_pass_2d(L, x, y, dt, kind, outer, n_in, n_out, inner, table, dev, stre
         tw = tables.get_table(_lib.FILTER_BOX, kind, inner, inner, False, 0.0, dev)
     if max(h2, w2, oh2, ow2) >= (1 << 24):
         return False
-    ah, aw = th.axis(), tw.axis()
-    if L.aa_workspace_bytes(dt, _lib.NCHW, n2, 1, h2, w2, oh2, ow2, ctypes.byref(ah), ctypes.byref(aw)) != 0:
+    plan = _plan_launch(L, th, tw, dt, _lib.NCHW, n2, 1, h2, w2, oh2, ow2, 0)
+    if plan[2] != 0:
         return False  # no fused kernel for this pass (or they are disabled): the single-axis kernel is the cheaper form
-    rc = L.aa_resample_fwd(x.data_ptr(), y.data_ptr(), None, 0, dt, _lib.NCHW, n2, 1, h2, w2, ctypes.byref(ah), ctypes.byref(aw), stream)
-    _lib.check(rc, "aa_resample_fwd (axis pass)")
+    _launch(L, "aa_resample_fwd (axis pass)", x, y, plan, dt, _lib.NCHW, n2, 1, h2, w2, 0)
     return True
 
 
@@ -739,7 +705,7 @@ def _forward_nd(filter_id: int, name: str, input: torch.Tensor, output_size: Seq
             t = tables.get_table(filter_id, kind, n_in, n_out, align_corners, 0.0, dev)
             shape[2 + k] = n_out
             y = torch.empty(shape, dtype=x.dtype, device=dev)
-            if not _axis_pass_2d(L, x, y, dt, kind, outer, n_in, n_out, inner, t, dev, s):
+            if not _axis_pass_2d(L, x, y, dt, kind, outer, n_in, n_out, inner, t, dev):
                 ax = t.axis()
                 rc = L.aa_resample_axis_fwd(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), dt, outer, n_in, inner,
                                             ctypes.byref(ax), s)
@@ -792,7 +758,7 @@ def _backward_nd(filter_id: int, name: str, grad_output: torch.Tensor, output_si
             tr = tables.get_transposed_table(fwd)  # maps n_out_fwd -> n_in_fwd
             shape[2 + k] = n_in_fwd
             y = torch.empty(shape, dtype=g.dtype, device=dev)
-            if not _axis_pass_2d(L, g, y, dt, kind, outer, n_out_fwd, n_in_fwd, inner, tr, dev, s):
+            if not _axis_pass_2d(L, g, y, dt, kind, outer, n_out_fwd, n_in_fwd, inner, tr, dev):
                 ax = tr.axis()
                 rc = L.aa_resample_axis_fwd(ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(y.data_ptr()), dt, outer, n_out_fwd, inner,
                                             ctypes.byref(ax), s)

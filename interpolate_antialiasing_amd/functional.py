@@ -5,9 +5,11 @@ from typing import Optional, Sequence
 
 import torch
 
-_MODES = {"bilinear": "linear_forward", "linear": "linear_forward", "bicubic": "cubic_forward",
-          "cubic": "cubic_forward", "nearest": "nearest_forward", "box": "nearest_forward", "lanczos": "lanczos_forward",
-          "hamming": "hamming_forward"}
+from ._lib import by_filter_name
+
+# mode -> name of the 2-D callable / of the N-d front-end
+_MODES = by_filter_name(lambda f: f.op + "_forward")
+_MODES_ND = {**{n: v + "_nd" for n, v in _MODES.items()}, "trilinear": "linear_forward_nd"}
 
 
 def interpolate_aa(input: torch.Tensor, size: Sequence[int], mode: str = "bilinear", align_corners: bool = False, *,
@@ -32,12 +34,9 @@ def interpolate_aa(input: torch.Tensor, size: Sequence[int], mode: str = "biline
     if input.dim() in (3, 5):
         from . import extension_interpolate as ext
 
-        fn = {"linear": ext.linear_forward_nd, "bilinear": ext.linear_forward_nd, "trilinear": ext.linear_forward_nd,
-              "bicubic": ext.cubic_forward_nd, "cubic": ext.cubic_forward_nd, "nearest": ext.nearest_forward_nd,
-              "box": ext.nearest_forward_nd, "lanczos": ext.lanczos_forward_nd, "hamming": ext.hamming_forward_nd}.get(mode)
-        if fn is None:
+        if mode not in _MODES_ND:
             raise ValueError(mode)
-        return fn(input, [int(v) for v in size], bool(align_corners))
+        return getattr(ext, _MODES_ND[mode])(input, [int(v) for v in size], bool(align_corners))
     if mode not in _MODES:
         raise ValueError(mode)  # test.py:78-79
     op = getattr(torch.ops.extension_interpolate, _MODES[mode])

@@ -17,9 +17,7 @@ import torch
 
 from . import _lib
 
-FILTER_IDS = {"linear": _lib.FILTER_LINEAR, "bilinear": _lib.FILTER_LINEAR, "cubic": _lib.FILTER_CUBIC,
-              "bicubic": _lib.FILTER_CUBIC, "box": _lib.FILTER_BOX, "nearest": _lib.FILTER_BOX, "hamming": _lib.FILTER_HAMMING,
-              "lanczos": _lib.FILTER_LANCZOS}
+FILTER_IDS = _lib.FILTER_IDS
 KIND_IDS = {"pil": _lib.TABLE_PIL, "f32": _lib.TABLE_F32, "f64": _lib.TABLE_F64}
 HEADER_BYTES = ctypes.sizeof(_lib.TableHeader)  # 64
 
@@ -129,27 +127,65 @@ def cache_key(filter_id: int, kind: int, in_size: int, out_size: int, align_corn
             dev.type, idx, bool(transposed))
 
 
+def _from_header(buf, filter_id, kind, in_size, out_size, k, align_corners, hdr, transposed=False) -> WeightTable:
+    """A table from its arguments and what the device measured into its header (a transposed table's scatter fields are 0 there)."""
+    return WeightTable(buf, filter_id, kind, in_size, out_size, k, int(hdr.max_taps), bool(align_corners), transposed,
+                       int(hdr.scatter_off), int(hdr.scatter_ksize), int(hdr.scatter_max), int(hdr.span64p1), int(hdr.span4p1), int(hdr.gather_off))
+
+
+def _read_headers(L, ptrs, s):
+    """The headers of one or two tables just built on stream ``s``: one synchronisation either way."""
+    hdrs = [_lib.TableHeader() for _ in ptrs]
+    if len(ptrs) == 1:
+        _lib.check(L.aa_table_query(ptrs[0], ctypes.byref(hdrs[0]), s), "aa_table_query")
+    else:
+        _lib.check(L.aa_table_query2(ptrs[0], ptrs[1], ctypes.byref(hdrs[0]), ctypes.byref(hdrs[1]), s), "aa_table_query2")
+    return hdrs
+
+
+def _table_alloc(nbytes: int, device: torch.device) -> torch.Tensor:
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _build(filter_id: int, kind: int, axes, align_corners: bool, device: torch.device, alloc=_table_alloc, box: bool = False):
+    """Uncached device-side build of the one or two tables of ``axes``: one build call and one header read-back whichever.  A plain axis
+    is (in_size, out_size, scale); a box axis (always two) is get_box_table_pair's (origin, hull, out_size, in0, in1)."""
+    L = _lib.load()
+    ac = int(align_corners)
+    if box:
+        ksize, nbytes, what = L.aa_table_ksize_box, L.aa_table_build_bytes_box, "aa_table_ksize_box"
+        sized = [(n, n_out, (n, n_out, in0, in1)) for _, n, n_out, in0, in1 in axes]
+    else:
+        ksize, nbytes, what = L.aa_table_ksize, L.aa_table_build_bytes, "aa_table_ksize"
+        axes = [(n, n_out, float(scale or 0.0)) for n, n_out, scale in axes]
+        sized = [(n, n_out, (n, n_out, ac, scale)) for n, n_out, scale in axes]
+    ks = []
+    for _, _, args in sized:
+        ks.append(ksize(filter_id, kind, *args))
+        _lib.check(ks[-1], what)
+    nb = [nbytes(filter_id, kind, *args) for _, _, args in sized]
+    with torch.cuda.device(device):
+        bufs = [alloc(n, device) for n in nb]
+        ptrs = [ctypes.c_void_p(b.data_ptr()) for b in bufs]
+        s = _stream_ptr(device)
+        if box:
+            _lib.check(L.aa_table_build_box(filter_id, kind, *axes[0], ptrs[0], nb[0], *axes[1], ptrs[1], nb[1], s), "aa_table_build_box")
+        elif len(axes) == 2:
+            _lib.check(L.aa_table_build2(filter_id, kind, ac, *axes[0], ptrs[0], nb[0], *axes[1], ptrs[1], nb[1], s), "aa_table_build2")
+        else:
+            n, n_out, scale = axes[0]
+            _lib.check(L.aa_table_build(filter_id, kind, n, n_out, ac, scale, ptrs[0], nb[0], s), "aa_table_build")
+        hdrs = _read_headers(L, ptrs, s)
+    out = [_from_header(buf, filter_id, kind, n, n_out, k, align_corners, hdr) for buf, (n, n_out, _), k, hdr in zip(bufs, sized, ks, hdrs)]
+    for t in out:
+        t.box = box
+    return out
+
+
 def build_table(filter_id: int, kind: int, in_size: int, out_size: int, align_corners: bool, scale: float,
                 device: torch.device) -> WeightTable:
     """Uncached device-side build (one launch + one 64-byte header read-back)."""
-    L = _lib.load()
-    k = L.aa_table_ksize(filter_id, kind, in_size, out_size, int(align_corners), float(scale or 0.0))
-    _lib.check(k, "aa_table_ksize")
-    nbytes = L.aa_table_build_bytes(filter_id, kind, in_size, out_size, int(align_corners), float(scale or 0.0))
-    with torch.cuda.device(device):
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        s = _stream_ptr(device)
-        _lib.check(L.aa_table_build(filter_id, kind, in_size, out_size, int(align_corners), float(scale or 0.0),
-                                    ctypes.c_void_p(buf.data_ptr()), nbytes, s), "aa_table_build")
-        hdr = _lib.TableHeader()
-        _lib.check(L.aa_table_query(ctypes.c_void_p(buf.data_ptr()), ctypes.byref(hdr), s), "aa_table_query")
-    return WeightTable(buf, filter_id, kind, in_size, out_size, k, int(hdr.max_taps), bool(align_corners), False,
-                       int(hdr.scatter_off), int(hdr.scatter_ksize), int(hdr.scatter_max), int(hdr.span64p1), int(hdr.span4p1), int(hdr.gather_off))
-
-
-def _from_header(buf, filter_id, kind, in_size, out_size, k, align_corners, hdr) -> WeightTable:
-    return WeightTable(buf, filter_id, kind, in_size, out_size, k, int(hdr.max_taps), bool(align_corners), False,
-                       int(hdr.scatter_off), int(hdr.scatter_ksize), int(hdr.scatter_max), int(hdr.span64p1), int(hdr.span4p1), int(hdr.gather_off))
+    return _build(filter_id, kind, [(in_size, out_size, scale)], align_corners, device)[0]
 
 
 def get_table_pair(filter_id: int, kind: int, in_h: int, out_h: int, in_w: int, out_w: int, align_corners: bool, scale_h: float, scale_w: float,
@@ -162,23 +198,7 @@ def get_table_pair(filter_id: int, kind: int, in_h: int, out_h: int, in_w: int, 
     with _cache_lock:
         th, tw = _cache.get(kh), _cache.get(kw)
     if th is None and tw is None and kh != kw:
-        L = _lib.load()
-        with torch.cuda.device(device):
-            k_h = L.aa_table_ksize(filter_id, kind, in_h, out_h, int(align_corners), float(scale_h or 0.0))
-            _lib.check(k_h, "aa_table_ksize")
-            k_w = L.aa_table_ksize(filter_id, kind, in_w, out_w, int(align_corners), float(scale_w or 0.0))
-            _lib.check(k_w, "aa_table_ksize")
-            nb_h = L.aa_table_build_bytes(filter_id, kind, in_h, out_h, int(align_corners), float(scale_h or 0.0))
-            nb_w = L.aa_table_build_bytes(filter_id, kind, in_w, out_w, int(align_corners), float(scale_w or 0.0))
-            bh = torch.empty(nb_h, dtype=torch.uint8, device=device)
-            bw = torch.empty(nb_w, dtype=torch.uint8, device=device)
-            _lib.check(L.aa_table_build2(filter_id, kind, int(align_corners), in_h, out_h, float(scale_h or 0.0), ctypes.c_void_p(bh.data_ptr()), nb_h,
-                                         in_w, out_w, float(scale_w or 0.0), ctypes.c_void_p(bw.data_ptr()), nb_w, _stream_ptr(device)), "aa_table_build2")
-            hh, hw = _lib.TableHeader(), _lib.TableHeader()
-            _lib.check(L.aa_table_query2(ctypes.c_void_p(bh.data_ptr()), ctypes.c_void_p(bw.data_ptr()), ctypes.byref(hh), ctypes.byref(hw),
-                                         _stream_ptr(device)), "aa_table_query2")
-        th = _from_header(bh, filter_id, kind, in_h, out_h, k_h, align_corners, hh)
-        tw = _from_header(bw, filter_id, kind, in_w, out_w, k_w, align_corners, hw)
+        th, tw = _build(filter_id, kind, [(in_h, out_h, scale_h), (in_w, out_w, scale_w)], align_corners, device)
         with _cache_lock:
             _cache[kh], _cache[kw] = th, tw
         return th, tw
@@ -217,27 +237,7 @@ def get_box_table_pair(filter_id: int, axis_h: Tuple[int, int, int, float, float
         if pair is not None:
             _box_cache.move_to_end(key)
             return pair
-    L = _lib.load()
-    kind = _lib.TABLE_PIL
-    (o_h, n_h, out_h, a_h, b_h), (o_w, n_w, out_w, a_w, b_w) = axis_h, axis_w
-    k_h = L.aa_table_ksize_box(filter_id, kind, n_h, out_h, a_h, b_h)
-    _lib.check(k_h, "aa_table_ksize_box")
-    k_w = L.aa_table_ksize_box(filter_id, kind, n_w, out_w, a_w, b_w)
-    _lib.check(k_w, "aa_table_ksize_box")
-    nb_h = L.aa_table_build_bytes_box(filter_id, kind, n_h, out_h, a_h, b_h)
-    nb_w = L.aa_table_build_bytes_box(filter_id, kind, n_w, out_w, a_w, b_w)
-    with torch.cuda.device(device):
-        bh = _box_table_alloc(nb_h, device)
-        bw = _box_table_alloc(nb_w, device)
-        s = _stream_ptr(device)
-        _lib.check(L.aa_table_build_box(filter_id, kind, o_h, n_h, out_h, a_h, b_h, ctypes.c_void_p(bh.data_ptr()), nb_h,
-                                        o_w, n_w, out_w, a_w, b_w, ctypes.c_void_p(bw.data_ptr()), nb_w, s), "aa_table_build_box")
-        hh, hw = _lib.TableHeader(), _lib.TableHeader()
-        _lib.check(L.aa_table_query2(ctypes.c_void_p(bh.data_ptr()), ctypes.c_void_p(bw.data_ptr()), ctypes.byref(hh), ctypes.byref(hw), s),
-                   "aa_table_query2")
-    th = _from_header(bh, filter_id, kind, n_h, out_h, k_h, False, hh)
-    tw = _from_header(bw, filter_id, kind, n_w, out_w, k_w, False, hw)
-    th.box = tw.box = True
+    th, tw = _build(filter_id, _lib.TABLE_PIL, [tuple(axis_h), tuple(axis_w)], False, device, _box_table_alloc, box=True)
     with _cache_lock:
         _box_cache[key] = (th, tw)
         while len(_box_cache) > BOX_CACHE_SIZE:
@@ -282,13 +282,11 @@ def get_transposed_table(fwd: WeightTable, scale: float = 0.0) -> WeightTable:
         s = _stream_ptr(device)
         _lib.check(L.aa_table_transpose(ctypes.c_void_p(fwd.buf.data_ptr()), ctypes.c_void_p(buf.data_ptr()), nbytes, tk, s),
                    "aa_table_transpose")
-        hdr = _lib.TableHeader()
-        _lib.check(L.aa_table_query(ctypes.c_void_p(buf.data_ptr()), ctypes.byref(hdr), s), "aa_table_query")
+        hdr, = _read_headers(L, [ctypes.c_void_p(buf.data_ptr())], s)
     if int(hdr.max_taps) > tk:  # (aa_table_transpose refuses this itself: a table whose rows dropped taps is never cached)
         raise _lib.AAInterpError(f"transposed weight table: an input index feeds {int(hdr.max_taps)} outputs but rows hold {tk} "
                                  f"(filter {fwd.filter}, {fwd.in_size} -> {fwd.out_size})")
-    t = WeightTable(buf, fwd.filter, fwd.kind, fwd.out_size, fwd.in_size, tk, int(hdr.max_taps), fwd.align_corners, True,
-                    span64p1=int(hdr.span64p1), span4p1=int(hdr.span4p1), gather_off=int(hdr.gather_off))
+    t = _from_header(buf, fwd.filter, fwd.kind, fwd.out_size, fwd.in_size, tk, fwd.align_corners, hdr, transposed=True)
     with _cache_lock:
         _cache[key] = t
     return t

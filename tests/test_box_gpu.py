@@ -132,12 +132,48 @@ def test_box_on_an_axis_too_long_for_the_paired_table_build(aa):
     assert np.array_equal(got[0], want)
 
 
-def test_box_on_a_view_no_kernel_reads(aa):
-    """A flipped image: only its hull is copied, and the result is that of the dense tensor."""
+def test_box_on_a_view_no_kernel_reads(aa, monkeypatch):
+    """A flipped image: only its hull is copied, and the result is that of the dense tensor.  Counted through the one copy function of
+    the resample paths: a view no kernel reads costs the boxed call exactly one copy, of the hull's shape and not the image's, whether the
+    view is refused at sight (rows not dense) or by the strided entry point (a crop, with the fused kernels off), and the fallback's
+    result keeps the hull's layout."""
+    from interpolate_antialiasing_amd import _lib, boxmath
+
     t = _gpu(ref.batch((2, 3, 97, 131), 31), False)
     flipped = t.flip(3)
     assert torch.equal(aa.cubic_forward(flipped, [30, 40], box=G.BOX1), aa.cubic_forward(flipped.contiguous(), [30, 40], box=G.BOX1))
     assert torch.equal(aa.reduce(flipped, (3, 5), (5, 7, 50, 36)), aa.reduce(flipped.contiguous(), (3, 5), (5, 7, 50, 36)))
+
+    copies = []
+    real = aa._memory_format
+    monkeypatch.setattr(aa, "_memory_format", lambda v, *a: (copies.append(tuple(v.shape)), real(v, *a))[1])
+    bx = boxmath.box_f32(G.BOX1)
+    (oy, ey), (ox, ex) = boxmath.axis_hull(97, 30, bx[1], bx[3], "cubic"), boxmath.axis_hull(131, 40, bx[0], bx[2], "cubic")
+    hull = (2, 3, ey - oy, ex - ox)
+    assert hull[2] < 97 and hull[3] < 131
+    want = aa.cubic_forward(t, [30, 40], box=G.BOX1)
+    copies.clear()
+    columns = t.transpose(2, 3).contiguous().transpose(2, 3)  # the same image stored column by column: no dense rows
+    assert not columns.is_contiguous() and not columns.is_contiguous(memory_format=torch.channels_last)
+    y = aa.cubic_forward(columns, [30, 40], box=G.BOX1)
+    print("copies of a column-major image:", copies, "hull:", hull)
+    assert copies == [hull]
+    assert torch.equal(y, want)
+    for cl in (False, True):
+        mf = torch.channels_last if cl else torch.contiguous_format
+        big = _gpu(ref.batch((2, 3, 120, 160), 32), cl)
+        crop = big[:, :, 9:106, 13:144]
+        assert not crop.is_contiguous() and not crop.is_contiguous(memory_format=torch.channels_last)
+        try:
+            _lib.set_fused(0)  # no kernel reads a pitched view now: the strided entry point answers AA_ERR_STRIDES
+            want = aa.cubic_forward(crop.contiguous(memory_format=mf), [30, 40], box=G.BOX1)
+            copies.clear()
+            y = aa.cubic_forward(crop, [30, 40], box=G.BOX1)
+        finally:
+            _lib.set_fused(1)
+        print("copies of a crop, channels_last", cl, ":", copies, "hull:", hull)
+        assert copies == [hull]
+        assert torch.equal(y, want) and y.is_contiguous(memory_format=mf)
 
 
 def test_interpolate_aa_passes_box_and_gap(aa):

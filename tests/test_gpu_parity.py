@@ -83,19 +83,80 @@ def test_device_pil_tables_bit_exact(aa, filt):
         dxmin, dxsize, dw = t.unpack()
         assert t.ksize == k
         assert np.array_equal(dxmin, xmin) and np.array_equal(dxsize, xsize) and np.array_equal(dw, kk), (filt, n_in, n_out)
-        sc = t.unpack_scatter()
-        if sc is not None and t.scatter_max <= t.scatter_ksize:  # the adjoint-form records the fused kernels read
-            first, count, w, completes = sc
-            last = xmin + np.maximum(xsize, 1) - 1  # last input index of every output's window
-            dense = np.zeros((n_in, n_out), np.int64)
-            for o in range(n_out):
-                dense[xmin[o]:xmin[o] + xsize[o], o] = kk[o, :xsize[o]]
-            for x in range(n_in):
-                fed = np.nonzero((xmin <= x) & (last >= x))[0]
-                assert count[x] == len(fed) and (len(fed) == 0 or first[x] == fed[0]), (filt, n_in, n_out, x)
-                assert np.array_equal(w[x, :count[x]], dense[x, first[x]:first[x] + count[x]]) and not w[x, count[x]:].any()
-                assert completes[x] == np.count_nonzero(last == x) and (completes[x] == 0 or last[first[x]] == x)
-            assert completes.sum() == n_out
+        _check_scatter_records(t, xmin, xsize, kk, (filt, n_in, n_out))
+
+
+def _check_scatter_records(t, xmin, xsize, w_rows, what):
+    """The adjoint-form records the fused kernels read, against the table's own rows: per input index the first output it feeds, how many,
+    their weights, and how many outputs it completes.  (Where an input feeds more outputs than a record holds, no kernel reads them.)"""
+    sc = t.unpack_scatter()
+    if sc is None or t.scatter_max > t.scatter_ksize:
+        return
+    n_in, n_out = t.in_size, t.out_size
+    first, count, w, completes = sc
+    last = xmin + np.maximum(xsize, 1) - 1  # last input index of every output's window
+    dense = np.zeros((n_in, n_out), np.int64 if w_rows.dtype.kind == "i" else w_rows.dtype)
+    for o in range(n_out):
+        dense[xmin[o]:xmin[o] + xsize[o], o] = w_rows[o, :xsize[o]]
+    for x in range(n_in):
+        fed = np.nonzero((xmin <= x) & (last >= x))[0]
+        assert count[x] == len(fed) and (len(fed) == 0 or first[x] == fed[0]), (what, x)
+        assert np.array_equal(w[x, :count[x]], dense[x, first[x]:first[x] + count[x]]) and not w[x, count[x]:].any(), (what, x)
+        assert completes[x] == np.count_nonzero(last == x) and (completes[x] == 0 or last[first[x]] == x), (what, x)
+    assert completes.sum() == n_out, what
+
+
+@pytest.mark.parametrize("n_in,n_out", [(32769, 300), (600, 16385)])
+def test_large_tables_bit_exact(aa, n_in, n_out):
+    """Tables just over each limit of the one-workgroup build (32768 inputs, 16384 outputs): one launch per phase instead, the same table."""
+    from interpolate_antialiasing_amd import _lib, tables
+
+    cases = [(_lib.TABLE_PIL, "linear", None), (_lib.TABLE_PIL, "cubic", None), (_lib.TABLE_F32, "linear", np.float32),
+             (_lib.TABLE_F64, "linear", np.float64)]
+    for kind, filt, dt in cases:
+        if dt is None:
+            k, xmin, xsize, w, _ = oracle.pil_coeffs(filt, n_in, n_out)
+        else:
+            k, xmin, xsize, w = oracle.weights(filt, n_in, n_out, False, dt)
+        t = tables.build_table(oracle.FILTERS[filt], kind, n_in, n_out, False, 0.0, torch.device("cuda"))
+        dxmin, dxsize, dw = t.unpack()
+        what = (kind, filt, n_in, n_out)
+        assert t.ksize == k, what
+        assert np.array_equal(dxmin, xmin) and np.array_equal(dxsize, xsize) and np.array_equal(dw, w), what
+        assert dw.dtype == w.dtype, what
+        assert t.max_taps == max(1, int(xsize.max())), what
+        _check_scatter_records(t, dxmin, dxsize, dw, what)
+
+
+def _gather_records(t):
+    """The per-output gather records {xmin, xsize, w[0..5]} of a table as int32[out, 8] (float weights as their bits), or None."""
+    if not t.gather_off:
+        return None
+    raw = t.buf.detach().cpu().numpy()
+    return raw[t.gather_off:t.gather_off + 32 * t.out_size].view(np.int32).reshape(t.out_size, 8).copy()
+
+
+@pytest.mark.parametrize("kind", ["pil", "f32"])
+def test_table_pair_equals_single_builds(aa, kind):
+    """The two tables of a call built by one launch (get_table_pair on a cold cache) are the tables built one at a time: every field
+    and every decoded section.  (Sections, not raw buffers: the padding between them is never written.)"""
+    import dataclasses
+
+    from interpolate_antialiasing_amd import tables
+
+    kind = tables.KIND_IDS[kind]
+    dev = torch.device("cuda")
+    tables.clear_cache()
+    pair = tables.get_table_pair(tables.FILTER_IDS["linear"], kind, 438, 196, 906, 320, False, 0.0, 0.0, dev)
+    for got, (n_in, n_out) in zip(pair, ((438, 196), (906, 320))):
+        one = tables.build_table(tables.FILTER_IDS["linear"], kind, n_in, n_out, False, 0.0, dev)
+        assert got.buf.data_ptr() != one.buf.data_ptr()
+        for f in dataclasses.fields(tables.WeightTable):
+            if f.name != "buf":
+                assert getattr(got, f.name) == getattr(one, f.name), (f.name, n_in, n_out)
+        assert got.max_taps > 0 and got.span64p1 > 0 and got.scatter_off > 0 and got.gather_off > 0
+        for a, b in zip(got.unpack() + got.unpack_scatter() + (_gather_records(got),), one.unpack() + one.unpack_scatter() + (_gather_records(one),)):
+            assert a.dtype == b.dtype and np.array_equal(a, b), (n_in, n_out)
 
 
 def test_align_corners_tables(aa):

@@ -44,7 +44,7 @@ e1.record()
 e1.synchronize()
 res["whole call, HIP events"] = e0.elapsed_time(e1) / REPS * 1e3
 # the pieces
-res["_check_sizes + dtype lookup + _memory_format"] = per_call(lambda: (aa._check_sizes(x.shape, [196, 320]), aa._DTYPE_IDS[x.dtype], aa._memory_format(x)), sync=False)
+res["_check_sizes + dtype lookup + _layout_of"] = per_call(lambda: (aa._check_sizes(x.shape, [196, 320]), aa._DTYPE_IDS[x.dtype], aa._layout_of(x)), sync=False)
 res["torch.empty (channels_last output)"] = per_call(lambda: torch.empty((1, 3, 196, 320), dtype=torch.uint8, device=dev, memory_format=torch.channels_last))
 key = (0, 0, 1, 1, 3, 438, 906, 196, 320, False, 0, 0.0, 0.0, 0, 0)
 d = {key: 1}
