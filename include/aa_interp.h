@@ -331,14 +331,18 @@ int aa_unpremultiply_u8(void *img_dev, int layout, int64_t N, int64_t C, int64_t
  * crop) and equal sizes in and out (a copy) included: their windows are one tap of weight 1.
  * layout: the class ALL items share and the layout of the dense output — AA_NHWC: interleaved pixels (stride_ch = 1, stride_px = C),
  * AA_NCHW: planes of consecutive bytes (stride_px = 1).  Any row pitch, any plane pitch, any byte offset; the stride of an axis of one
- * element is not looked at.  C is 1..4.  Added without an ABI version change (additive). */
+ * element is not looked at.  C is 1..4.  Added without an ABI version change (additive).
+ * aa_many_image.flags (the field was `reserved`, always 0): AA_MANY_FLIP_X mirrors that item's output left to right (RandomHorizontalFlip);
+ * any other bit makes aa_many_plan return AA_ERR_BAD_SHAPE.  Only aa_resample_many_u8_to_float serves a plan in which an item flips:
+ * aa_resample_many_u8 returns AA_ERR_BAD_SHAPE for it (its kernel does not flip).  Zero-initialised callers see no change. */
+#define AA_MANY_FLIP_X 1
 typedef struct aa_many_image {
   const void *data_dev;  /* byte (row 0, column 0, channel 0) of the image */
   int64_t H, W;
   int64_t stride_row, stride_px, stride_ch; /* in BYTES */
   double box[4];         /* x0, y0, x1, y1 — Pillow's order, x first; rounded to float32 by the plan, as Pillow's C does */
   int32_t has_box;       /* 0: the whole image (box[] is not read) */
-  int32_t reserved;
+  int32_t flags;         /* 0, or AA_MANY_FLIP_X */
 } aa_many_image;
 /* Bytes of the packed descriptor block for n items. */
 size_t aa_many_desc_bytes(int64_t n);
@@ -353,6 +357,19 @@ int aa_many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64
  * workspace_dev: 16-byte aligned, at least the plan's size.  Nothing is allocated, nothing is synchronised.  n == 0 launches nothing. */
 int aa_resample_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
                         void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+/* The same three launches with a CONVERTING vertical pass: what a model reads instead of Pillow's bytes, with no uint8 batch and no
+ * float32 intermediate in between.  With u = the bytes aa_resample_many_u8 writes for the plan (Pillow's, bit for bit):
+ *   f = (float)u;  with cv->normalize, f = (f - cv->mean[c]) / cv->std[c] in fp32 (one rounded subtraction, one correctly rounded
+ *   division; mean / std in 0..255 units);  element = f, or round_to_nearest_even_16(f) with AA_FLAG_OUT_F16 / AA_FLAG_OUT_BF16 in
+ *   cv->flags;  written at column oW - 1 - x instead of x for an item planned with AA_MANY_FLIP_X;  in cv->out_layout, which may differ
+ *   from `layout`, the class of the items.
+ * This is NOT aa_resample_fwd_u8_to_f32's result: that call resamples in fp32 arithmetic throughout and has no box; this one converts
+ * Pillow's byte.  out_dev [n, C, oH, oW] elements, dense, in cv->out_layout, aligned to its element (AA_ERR_BAD_SHAPE otherwise); rows
+ * at any alignment beyond that are served (every store is one element).  Both output bits:
+ * AA_ERR_BAD_DTYPE; AA_FLAG_FAST or an unknown bit: AA_ERR_BAD_SHAPE.  Every other argument and check as aa_resample_many_u8, all before
+ * any launch.  n == 0 launches nothing.  Added without an ABI version change (additive). */
+int aa_resample_many_u8_to_float(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout,
+                                 void *out_dev, void *workspace_dev, size_t workspace_bytes, const aa_convert *cv, aa_stream_t stream);
 
 /* Device-to-device copy of `bytes` bytes with 16-byte vector loads/stores, enqueued on `stream`: the probe bench.py times
  * on the box to report the attainable HBM copy ceiling next to the 8 TB/s spec peak.  form 0: one element per

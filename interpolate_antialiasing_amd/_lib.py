@@ -50,7 +50,7 @@ EXPORTS = (
     "aa_resample_bwd", "aa_resample_bwd_atomic", "aa_workspace_bytes_bwd", "aa_resample_axis_fwd", "aa_set_fused",
     "aa_last_variant", "aa_probe_copy", "aa_workspace_bytes_u8_to_f32", "aa_resample_fwd_u8_to_f32", "aa_set_store_form", "aa_set_plane_groups", "aa_resample_fwd_ex", "aa_resample_fwd_strided",
     "aa_workspace_bytes_ex", "aa_table_ksize_box", "aa_table_build_bytes_box", "aa_table_build_box", "aa_reduce_u8", "aa_premultiply_u8",
-    "aa_unpremultiply_u8", "aa_many_desc_bytes", "aa_many_plan", "aa_resample_many_u8",
+    "aa_unpremultiply_u8", "aa_many_desc_bytes", "aa_many_plan", "aa_resample_many_u8", "aa_resample_many_u8_to_float",
 )
 
 
@@ -81,7 +81,7 @@ class ManyImage(ctypes.Structure):
     """aa_many_image: one item of the ragged call (strides in bytes; box = x0, y0, x1, y1)."""
     _fields_ = [("data_dev", ctypes.c_void_p), ("H", ctypes.c_int64), ("W", ctypes.c_int64), ("stride_row", ctypes.c_int64),
                 ("stride_px", ctypes.c_int64), ("stride_ch", ctypes.c_int64), ("box", ctypes.c_double * 4), ("has_box", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("flags", ctypes.c_int32)]
 
 
 class ManyHeader(ctypes.Structure):
@@ -100,6 +100,7 @@ class ManyItem(ctypes.Structure):
                 ("box_on", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+MANY_FLIP_X = 1     # aa_many_image.flags: mirror the item's output left to right (aa_resample_many_u8_to_float only)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
 
@@ -198,6 +199,8 @@ def load() -> ctypes.CDLL:
     L.aa_many_plan.restype = i32
     L.aa_resample_many_u8.argtypes = [vp, vp, i64, i64, i64, i64, i32, vp, vp, sz, vp]
     L.aa_resample_many_u8.restype = i32
+    L.aa_resample_many_u8_to_float.argtypes = [vp, vp, i64, i64, i64, i64, i32, vp, vp, sz, cvp, vp]
+    L.aa_resample_many_u8_to_float.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

@@ -466,6 +466,20 @@ int aa_resample_many_u8(const void *desc_host, const void *desc_dev, int64_t n, 
   return aa_launch_many_u8(desc_host, desc_dev, n, C, oH, oW, layout, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
+int aa_resample_many_u8_to_float(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout,
+                                 void *out_dev, void *workspace_dev, size_t workspace_bytes, const aa_convert *cv, aa_stream_t stream) {
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (n < 0 || C < 1 || C > 4 || oH <= 0 || oW <= 0) return AA_ERR_BAD_SHAPE;
+  if (!desc_host || !cv) return AA_ERR_NULL;
+  if (cv->out_layout != AA_NCHW && cv->out_layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if ((cv->flags & AA_FLAG_OUT_F16) && (cv->flags & AA_FLAG_OUT_BF16)) return AA_ERR_BAD_DTYPE;
+  if (cv->flags & ~(AA_FLAG_OUT_F16 | AA_FLAG_OUT_BF16)) return AA_ERR_BAD_SHAPE;  // (AA_FLAG_FAST: the conversion has one arithmetic)
+  if (n > 0 && (!desc_dev || !out_dev || !workspace_dev)) return AA_ERR_NULL;
+  const int out_elem = (cv->flags & AA_FLAG_OUT_F16) ? AA_F16 : ((cv->flags & AA_FLAG_OUT_BF16) ? AA_BF16 : AA_F32);
+  return aa_launch_many_float(desc_host, desc_dev, n, C, oH, oW, layout, out_dev, workspace_dev, workspace_bytes, out_elem, cv->out_layout,
+                              cv->normalize, cv->mean, cv->std, (hipStream_t)stream);
+}
+
 // ---- Image.reduce ------------------------------------------------------------------------------------------------------------------------
 int aa_reduce_u8(const void *in_dev, void *out_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const int64_t *in_strides,
                  const int64_t *box, int fx, int fy, aa_stream_t stream) {

@@ -11,7 +11,7 @@
 #define AA_MANY_VBYTES 1024       // output-row bytes per workgroup of the vertical pass (256 lanes x 4)
 
 struct AAManyHeader {
-  int32_t magic, n, C, oH, oW, filter, layout, reserved0;
+  int32_t magic, n, C, oH, oW, filter, layout, reserved0;  // reserved0: 1 when some item flips (only the converting pass serves it)
   int64_t hunits;     // work units of the horizontal pass, all items: hunit_prefix[n]
   int64_t ws_bytes;   // table arena + intermediates
   int64_t reserved[2];
@@ -29,7 +29,7 @@ struct AAManyItem {
   int32_t oy, hull_h, ox, hull_w;     // the hull [o, o + hull) of all windows per axis: nothing outside it is read
   int32_t ksize_h, ksize_w;
   int32_t box_on;                     // 1: the scale is the FLOAT difference of the interval over the output size (a box); 0: in / out
-  int32_t reserved;
+  int32_t reserved;                   // bit 0: AA_MANY_FLIP_X, the converting vertical pass writes the item mirrored left to right
 };
 static_assert(sizeof(AAManyItem) == 112, "descriptor item is 112 bytes");
 
@@ -41,3 +41,7 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
                       size_t desc_bytes, size_t *workspace_bytes);
 int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
                       void *workspace_dev, size_t workspace_bytes, hipStream_t stream);
+// The same with the converting vertical pass: out_elem AA_F32 / AA_F16 / AA_BF16, out_layout the layout of the dense output.
+int aa_launch_many_float(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
+                         void *workspace_dev, size_t workspace_bytes, int out_elem, int out_layout, int normalize, const float *mean,
+                         const float *std, hipStream_t stream);

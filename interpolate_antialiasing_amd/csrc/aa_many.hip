@@ -3,7 +3,9 @@
 //   1. many_tables  every item's two AA_TABLE_PIL coefficient sets into one arena (aa_pil_coeffs.h: the packed tables' own expressions);
 //   2. many_hpass   one workgroup per (item, plane, hull row, strip of 64 output columns), found from prefix sums: the grid is the sum of
 //                   the items' work, not N x the largest item;
-//   3. many_vpass   one workgroup per (item, plane, output row, 1 KiB of the row).
+//   3. many_vpass   one workgroup per (item, plane, output row, 1 KiB of the row);
+//      or many_vpass_float, the converting form: the same sums, then byte -> float -> (v - mean) / std -> f32 / f16 / bf16, written in the
+//      requested layout, mirrored left to right for the items that flip.
 // The host planner (aa_many_plan_host) computes every hull, ksize and offset with the same double arithmetic the table kernel uses, so
 // nothing comes back from the device: no header read-back, no atomicMax, no synchronisation, no allocation.
 
@@ -179,6 +181,92 @@ __global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const
   }
 }
 
+
+// ---- 3b. converting vertical pass --------------------------------------------------------------------------------------------------------
+// The bytes of many_vpass (same tables, same intermediate, same integer sums), converted as they leave: element = (T)(((float)byte -
+// mean[c]) / std[c]), at column oW - 1 - x of an item that flips, in the class's own layout or the other one (XL).
+// A workgroup owns kVPixels<E> pixels of one output row of one plane: lane j the bytes [4j, 4j + 4) of that piece, as in many_vpass.
+// Every lane stores its four results where they belong, one element each (an element store is always aligned: the entry point checks the
+// output's address against its element), so rows at any element alignment, flips and both output layouts are one code path.  From
+// interleaved pixels to planes a store instruction of a wave then covers E planes with short runs; a form that staged the workgroup's
+// results in LDS and stored aligned 8- / 16-byte pieces of one plane row per lane measured 5 % slower on that case.
+struct ManyConvert { int normalize; float mean[4], std[4]; };
+struct f16_t { _Float16 v; };
+struct bf16_t { uint16_t v; };
+template <typename T> __device__ inline T to_elem(float a);
+template <> __device__ inline float to_elem<float>(float a) { return a; }
+template <> __device__ inline f16_t to_elem<f16_t>(float a) { f16_t r; r.v = (_Float16)a; return r; }  // round to nearest even
+template <> __device__ inline bf16_t to_elem<bf16_t>(float a) {                                        // round to nearest even
+  const unsigned u = __float_as_uint(a);
+  bf16_t r;
+  if ((u & 0x7fffffffu) > 0x7f800000u) r.v = (uint16_t)((u >> 16) | 0x0040u);
+  else r.v = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+  return r;
+}
+__device__ inline float pick4(const float (&a)[4], int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : (c == 2 ? a[2] : a[3])); }
+
+template <int E> constexpr int kVLanes = E == 3 ? 192 : 256;   // lanes of a workgroup: 4 bytes each, a whole number of pixels together
+template <int E> constexpr int kVPixels = kVLanes<E> * 4 / E;  // 1024, 512, 256, 256
+
+template <typename T, int E, bool XL>
+__global__ void __launch_bounds__(kVLanes<E>) many_vpass_float(const AAManyItem *items, const char *ws, T *out, int oH, int oW, int planes,
+                                                               int nstrips, const ManyConvert cv) {
+  constexpr int PX = kVPixels<E>;
+  int64_t u = blockIdx.x;
+  const int strip = (int)(u % nstrips);
+  u /= nstrips;
+  const int y = (int)(u % oH);
+  u /= oH;
+  const int plane = (int)(u % planes);
+  const int64_t n = u / planes;
+  const AAManyItem &it = items[n];
+  const int x0 = strip * PX;
+  const int npx = oW - x0 < PX ? oW - x0 : PX;
+  const int j = threadIdx.x;
+  const int nb = npx * E - 4 * j;  // bytes of the piece from this lane's first (4 or more: all four results exist; <= 0: none)
+  if (nb <= 0) return;
+  const bool flip = (it.reserved & 1) != 0;
+  const int xr = flip ? oW - x0 - npx : x0;  // the output column the piece's run(s) start at
+
+  float f[4];
+  {
+    const int32_t *xmin_p = (const int32_t *)(ws + it.tab_h);
+    const int32_t *xsize_p = xmin_p + oH;
+    const int ksize = it.ksize_h;
+    const int32_t *wp = xsize_p + oH + (size_t)y * ksize;
+    int r0 = xmin_p[y], nr = xsize_p[y];
+    if (nr > ksize) nr = ksize;
+    if (r0 < 0) r0 = 0;
+    if (r0 + nr > it.hull_h) nr = it.hull_h - r0;
+    const int64_t pitch = aa_many_inter_pitch(oW, E);
+    const uint8_t *ip = (const uint8_t *)ws + it.inter + ((int64_t)plane * it.hull_h + r0) * pitch + (int64_t)x0 * E + 4 * j;
+    int32_t s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21, s3 = 1 << 21;
+    for (int k = 0; k < nr; k++) {
+      const uint32_t v = *(const uint32_t *)(ip + k * pitch);
+      const int32_t wk = wp[k];
+      s0 += (int32_t)(v & 255u) * wk;
+      s1 += (int32_t)((v >> 8) & 255u) * wk;
+      s2 += (int32_t)((v >> 16) & 255u) * wk;
+      s3 += (int32_t)(v >> 24) * wk;
+    }
+    f[0] = (float)clip8(s0); f[1] = (float)clip8(s1); f[2] = (float)clip8(s2); f[3] = (float)clip8(s3);
+  }
+
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (i >= nb) break;
+    const int q = 4 * j + i, px = q / E, c = q % E;
+    float v = f[i];
+    if (cv.normalize) v = (v - pick4(cv.mean, plane + c)) / pick4(cv.std, plane + c);  // (one of plane and c is 0)
+    const int64_t x = xr + (flip ? npx - 1 - px : px);
+    int64_t at;
+    if (!XL) at = (((n * planes + plane) * oH + y) * oW + x) * E + c;
+    else if (E > 1) at = ((n * E + c) * oH + y) * oW + x;
+    else at = ((n * oH + y) * oW + x) * planes + plane;
+    out[at] = to_elem<T>(v);
+  }
+}
+
 }  // namespace
 
 // ---- host: the planner -------------------------------------------------------------------------------------------------------------------
@@ -217,12 +305,14 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
   int64_t *prefix = (int64_t *)(items + n);
   size_t off = 0;  // the arena first, then the intermediates
   int64_t units = 0;
+  int flips = 0;
   for (int64_t i = 0; i < n; i++) {
     const aa_many_image &im = images[i];
     AAManyItem it;
     memset(&it, 0, sizeof(it));
     if (!im.data_dev) return AA_ERR_NULL;
     if (im.H <= 0 || im.W <= 0 || im.H > kMax || im.W > kMax) return AA_ERR_BAD_SHAPE;
+    if (im.flags & ~AA_MANY_FLIP_X) return AA_ERR_BAD_SHAPE;
     // (the stride of an axis of one element never matters)
     if (layout == AA_NHWC ? ((C > 1 && im.stride_ch != 1) || (im.W > 1 && im.stride_px != C)) : (im.W > 1 && im.stride_px != 1)) return AA_ERR_STRIDES;
     double x0 = 0.0, y0 = 0.0, x1 = (double)im.W, y1 = (double)im.H;
@@ -248,6 +338,8 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
     it.oy = (int32_t)oy; it.hull_h = (int32_t)(ey - oy); it.ox = (int32_t)ox; it.hull_w = (int32_t)(ex - ox);
     it.ksize_h = kh; it.ksize_w = kw;
     it.box_on = on;
+    it.reserved = im.flags & AA_MANY_FLIP_X;
+    flips |= it.reserved;
     it.tab_h = (int64_t)off;
     off += aa_many_table_bytes(oH, kh);
     it.tab_w = (int64_t)off;
@@ -266,6 +358,7 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
   hd->magic = AA_MANY_MAGIC;
   hd->n = (int32_t)n; hd->C = (int32_t)C; hd->oH = (int32_t)oH; hd->oW = (int32_t)oW;
   hd->filter = filter; hd->layout = layout;
+  hd->reserved0 = flips;
   hd->hunits = units;
   hd->ws_bytes = (int64_t)off;
   *workspace_bytes = off;
@@ -273,19 +366,18 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
 }
 
 // ---- host: the three launches ------------------------------------------------------------------------------------------------------------
-int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
-                      void *workspace_dev, size_t workspace_bytes, hipStream_t stream) {
-  const AAManyHeader *hd = (const AAManyHeader *)desc_host;
+// The checks of both entry points against the plan; the tables and the horizontal pass, which both share.
+static int many_check(const AAManyHeader *hd, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout,
+                      const void *workspace_dev, size_t workspace_bytes) {
   if (hd->magic != AA_MANY_MAGIC || hd->n != n || hd->C != C || hd->oH != oH || hd->oW != oW || hd->layout != layout) return AA_ERR_BAD_SHAPE;
   if (n == 0) return AA_OK;
   if (workspace_bytes < (size_t)hd->ws_bytes) return AA_ERR_WORKSPACE;
   if (((uintptr_t)workspace_dev & 15) || ((uintptr_t)desc_dev & 7)) return AA_ERR_BAD_SHAPE;
-  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
-  const int64_t *prefix = (const int64_t *)(items + n);
-  const int E = layout == AA_NHWC ? (int)C : 1;
-  const int planes = layout == AA_NHWC ? 1 : (int)C;
-  char *ws = (char *)workspace_dev;
+  return AA_OK;
+}
 
+static void launch_many_tables_hpass(const AAManyHeader *hd, const AAManyItem *items, const int64_t *prefix, char *ws, int64_t n, int64_t oH,
+                                     int64_t oW, int E, int planes, hipStream_t stream) {
   const int64_t tthreads = n * (oH + oW);
   hipLaunchKernelGGL(many_tables, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, items, ws, n, (int)oH, (int)oW, hd->filter);
   const dim3 hgrid((unsigned)hd->hunits);
@@ -295,9 +387,74 @@ int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, in
     case 3: hipLaunchKernelGGL(many_hpass<3>, hgrid, dim3(AA_MANY_STRIP * 3), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
     default: hipLaunchKernelGGL(many_hpass<4>, hgrid, dim3(AA_MANY_STRIP * 4), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
   }
+}
+
+int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
+                      void *workspace_dev, size_t workspace_bytes, hipStream_t stream) {
+  const AAManyHeader *hd = (const AAManyHeader *)desc_host;
+  const int rc = many_check(hd, desc_dev, n, C, oH, oW, layout, workspace_dev, workspace_bytes);
+  if (rc != AA_OK) return rc;
+  if (hd->reserved0) return AA_ERR_BAD_SHAPE;  // an item flips: the uint8 pass does not
+  if (n == 0) return AA_OK;
+  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
+  const int64_t *prefix = (const int64_t *)(items + n);
+  const int E = layout == AA_NHWC ? (int)C : 1;
+  const int planes = layout == AA_NHWC ? 1 : (int)C;
+  char *ws = (char *)workspace_dev;
+  launch_many_tables_hpass(hd, items, prefix, ws, n, oH, oW, E, planes, stream);
   const int vstrips = (int)((oW * E + AA_MANY_VBYTES - 1) / AA_MANY_VBYTES);
   hipLaunchKernelGGL(many_vpass, dim3((unsigned)(n * planes * oH * vstrips)), dim3(256), 0, stream, items, (const char *)ws, (uint8_t *)out_dev, (int)oH,
                      (int)oW, planes, E, vstrips);
+  AA_HIP_CHECK_LAUNCH();
+  return AA_OK;
+}
+
+template <typename T, int E, bool XL>
+static void launch_vpass_float(const AAManyItem *items, const char *ws, void *out, int64_t n, int64_t oH, int64_t oW, int planes,
+                               const ManyConvert &cv, hipStream_t stream) {
+  const int nstrips = (int)((oW + kVPixels<E> - 1) / kVPixels<E>);
+  hipLaunchKernelGGL((many_vpass_float<T, E, XL>), dim3((unsigned)(n * planes * oH * nstrips)), dim3(kVLanes<E>), 0, stream, items, ws,
+                     (T *)out, (int)oH, (int)oW, planes, nstrips, cv);
+}
+
+template <typename T>
+static void launch_vpass_float_e(int E, bool xl, const AAManyItem *items, const char *ws, void *out, int64_t n, int64_t oH, int64_t oW, int planes,
+                                 const ManyConvert &cv, hipStream_t stream) {
+  switch (E * 2 + (xl ? 1 : 0)) {
+    case 2: launch_vpass_float<T, 1, false>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+    case 3: launch_vpass_float<T, 1, true>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+    case 4: launch_vpass_float<T, 2, false>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+    case 5: launch_vpass_float<T, 2, true>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+    case 6: launch_vpass_float<T, 3, false>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+    case 7: launch_vpass_float<T, 3, true>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+    case 8: launch_vpass_float<T, 4, false>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+    default: launch_vpass_float<T, 4, true>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+  }
+}
+
+int aa_launch_many_float(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
+                         void *workspace_dev, size_t workspace_bytes, int out_elem, int out_layout, int normalize, const float *mean,
+                         const float *std, hipStream_t stream) {
+  const AAManyHeader *hd = (const AAManyHeader *)desc_host;
+  const int rc = many_check(hd, desc_dev, n, C, oH, oW, layout, workspace_dev, workspace_bytes);
+  if (rc != AA_OK) return rc;
+  if ((uintptr_t)out_dev & (out_elem == AA_F32 ? 3 : 1)) return AA_ERR_BAD_SHAPE;
+  if (n == 0) return AA_OK;
+  const int E = layout == AA_NHWC ? (int)C : 1;
+  const int planes = layout == AA_NHWC ? 1 : (int)C;
+  const bool xl = out_layout != layout && C > 1;  // (one channel: the two layouts are the same bytes)
+  const int64_t px = E == 1 ? kVPixels<1> : (E == 2 ? kVPixels<2> : kVPixels<4>);
+  if (n * planes * oH * ((oW + px - 1) / px) > INT32_MAX) return AA_ERR_BAD_SHAPE;  // (the grid of the converting pass)
+  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
+  const int64_t *prefix = (const int64_t *)(items + n);
+  char *ws = (char *)workspace_dev;
+  ManyConvert cv;
+  cv.normalize = normalize ? 1 : 0;
+  for (int i = 0; i < 4; i++) { cv.mean[i] = normalize && i < C ? mean[i] : 0.f; cv.std[i] = normalize && i < C ? std[i] : 1.f; }
+  launch_many_tables_hpass(hd, items, prefix, ws, n, oH, oW, E, planes, stream);
+  if (out_elem == AA_F16) launch_vpass_float_e<f16_t>(E, xl, items, ws, out_dev, n, oH, oW, planes, cv, stream);
+  else if (out_elem == AA_BF16) launch_vpass_float_e<bf16_t>(E, xl, items, ws, out_dev, n, oH, oW, planes, cv, stream);
+  else launch_vpass_float_e<float>(E, xl, items, ws, out_dev, n, oH, oW, planes, cv, stream);
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }

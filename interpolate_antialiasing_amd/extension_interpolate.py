@@ -38,6 +38,8 @@ Differences, all additive:
     ``Image.thumbnail`` does with 2.0.  The result is Pillow's ``reducing_gap`` result, not the plain one.  Two launches plus the table
     build, through a temporary uint8 tensor in the input's layout;
   * ``reduce(input, factor, box=None, alpha=False)``: Pillow's ``Image.reduce`` (integer box means), bit-exact;
+  * ``resize_many_to_float(images, output_size, mode, boxes=None, flips=None, out_dtype=, out_format=, mean=, std=)``: ``resize_many``
+    and the float conversion, normalisation, layout change and horizontal flips a model needs after it, in the same three launches.
   * ``resize_many(images, output_size, mode, boxes=None)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation;
@@ -46,13 +48,14 @@ Differences, all additive:
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional, Sequence
 
 import torch
 
 from . import _lib, boxmath, tables
 
-__all__ = ["reduce", "resize_many", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+__all__ = ["reduce", "resize_many", "resize_many_to_float", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -424,7 +427,8 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
 
     Three launches and one non-blocking copy of a packed descriptor whatever N; every hull, ksize and offset is host arithmetic
     (aa_many_plan), so nothing is read back, and the table caches are neither read nor written.  Not built here: alpha, reducing_gap,
-    uint8_mode="harness", float images or outputs, align_corners, scale factors (each raises NotImplementedError)."""
+    uint8_mode="harness", float images or outputs, align_corners, scale factors (each raises NotImplementedError); float, normalised,
+    flipped output in either layout is ``resize_many_to_float``."""
     name = "resize_many"
     for opt, given in (("alpha", bool(alpha)), ("reducing_gap", reducing_gap is not None), ("out_dtype", out_dtype is not None),
                        ("out_format", out_format is not None), ("mean", mean is not None), ("std", std is not None),
@@ -435,6 +439,69 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
         if (uint8_mode or _uint8_mode) != "harness":
             raise ValueError("uint8_mode must be 'pil' or 'harness'")
         raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
+    return _resize_many(name, images, output_size, mode, boxes, channels, None)
+
+
+def resize_many_to_float(images, output_size: Sequence[int], mode: str = "bilinear", *, boxes=None, flips=None,
+                         channels: Optional[int] = None, out_dtype=torch.float32, out_format: Optional[str] = None, mean=None,
+                         std=None) -> torch.Tensor:
+    """``resize_many`` and the conversion a model needs after it, in the same three launches: with ``u = resize_many(images, output_size,
+    mode, boxes=boxes)`` (Pillow's bytes), the result is, bit for bit,
+
+        f = u.float();  f = (f - mean[c]) / std[c]  (fp32, when given);  y = f.to(out_dtype);  y[i] = y[i].flip(-1) where flips[i]
+
+    written in ``out_format``: ``PIL.Image.resize(..., box=)``, ``transpose(FLIP_LEFT_RIGHT)``, a ToTensor-style conversion and Normalize
+    folded into 0..255 units, without the uint8 batch, a float32 intermediate or a second pass.
+
+    ``images``, ``output_size``, ``mode``, ``boxes``, ``channels``: exactly ``resize_many``'s.
+    ``out_dtype``: torch.float32 | torch.float16 | torch.bfloat16 (rounded to nearest even once, at the store).
+    ``out_format``: "nchw" | "nhwc" | None (the class of the items, as ``resize_many``'s output).
+    ``mean`` / ``std``: None, or C floats each in 0..255 units (the convention of the single-image forwards), given together.
+    ``flips``: None, or N truthy / falsy entries; a truthy entry mirrors that item's output left to right (RandomHorizontalFlip).
+
+    This is NOT the single-image forwards' ``out_dtype`` result: those resample in fp32 arithmetic throughout (uint8_mode="harness") and
+    take no box; this call converts Pillow's byte, what torchvision's PIL pipeline produces."""
+    name = "resize_many_to_float"
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+    if out_format not in (None, "nchw", "nhwc"):
+        raise ValueError("out_format must be 'nchw', 'nhwc' or None (same as the input)")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std must be given together")
+    if _uint8_mode != "pil":
+        raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
+    return _resize_many(name, images, output_size, mode, boxes, channels,
+                        {"out_dtype": out_dtype, "out_format": out_format, "mean": mean, "std": std, "flips": flips})
+
+
+def _many_convert(name: str, conv: dict, n: int, c: int):
+    """The conversion options of resize_many_to_float, checked -> (aa_convert without its layout, flips or None, out_dtype)."""
+    out_dtype = conv["out_dtype"]
+    cv = _lib.Convert()
+    cv.normalize = 0
+    cv.flags = {torch.float16: _lib.FLAG_OUT_F16, torch.bfloat16: _lib.FLAG_OUT_BF16}.get(out_dtype, 0)
+    mean, std = conv["mean"], conv["std"]
+    if mean is not None:
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        if len(mean) != c or len(std) != c or c > 4:
+            raise RuntimeError(f"mean/std must hold one value per channel (C = {c} <= 4)")
+        for i in range(c):
+            if not math.isfinite(mean[i]):
+                raise ValueError(f"{name}(): mean[{i}] = {mean[i]} is not finite")
+            if not math.isfinite(std[i]) or std[i] == 0.0:
+                raise ValueError(f"{name}(): std[{i}] = {std[i]} must be finite and not zero")
+            cv.mean[i], cv.std[i] = mean[i], std[i]
+        cv.normalize = 1
+    flips = conv["flips"]
+    if flips is not None:
+        flips = [bool(v) for v in flips]
+        if len(flips) != n:
+            raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
+    return cv, flips, out_dtype
+
+
+def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes, channels: Optional[int], conv: Optional[dict]) -> torch.Tensor:
+    """resize_many (conv None) and resize_many_to_float (conv: its options): the checks, the layout class, the plan and the launches."""
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
     filter_id = _lib.FILTER_IDS[mode]
@@ -483,10 +550,13 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
         if bx is not None:
             bx = boxmath.box_f32(boxmath.check_box(bx, w, h))  # Pillow's checks and wording; its C takes the box as floats
         checked.append(bx)
+    cv, flips, out_dtype = None, None, torch.uint8
+    if conv is not None:
+        cv, flips, out_dtype = _many_convert(name, conv, n, c)
     if n == 0:
         if dev0 is None:
             dev0 = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        return torch.empty((0, c, oh, ow), dtype=torch.uint8, device=dev0)
+        return torch.empty((0, c, oh, ow), dtype=out_dtype, device=dev0)
     for t in items:
         _require_gpu(t, name)
     dev = items[0].device
@@ -496,6 +566,11 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
     n_planar = sum(1 for a, b in classes if b and not a)
     interleaved = c > 1 and n_inter > 0 and n_inter >= n_planar
     layout = _lib.NHWC if interleaved else _lib.NCHW
+    out_nhwc = interleaved
+    if cv is not None:
+        if conv["out_format"] is not None:
+            out_nhwc = conv["out_format"] == "nhwc"
+        cv.out_layout = _lib.NHWC if out_nhwc else _lib.NCHW
     L = _lib.load()
     with torch.cuda.device(dev):
         recs = (_lib.ManyImage * n)()
@@ -515,6 +590,8 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
             if bx is not None:
                 r.has_box = 1
                 r.box[0], r.box[1], r.box[2], r.box[3] = bx
+            if flips is not None and flips[i]:
+                r.flags = _lib.MANY_FLIP_X
         desc_bytes = L.aa_many_desc_bytes(n)
         desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
         ws_bytes = ctypes.c_size_t(0)
@@ -522,10 +599,15 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
         desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
         desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
         ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
-        out = torch.empty((n, c, oh, ow), dtype=torch.uint8, device=dev,
-                          memory_format=torch.channels_last if interleaved else torch.contiguous_format)
-        rc = L.aa_resample_many_u8(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   torch.cuda.current_stream(dev).cuda_stream)
+        out = torch.empty((n, c, oh, ow), dtype=out_dtype, device=dev,
+                          memory_format=torch.channels_last if out_nhwc else torch.contiguous_format)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if cv is None:
+            rc = L.aa_resample_many_u8(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       stream)
+        else:
+            rc = L.aa_resample_many_u8_to_float(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(),
+                                                ws.numel(), ctypes.byref(cv), stream)
     _lib.check(rc, name)
     return out
 
@@ -947,6 +1029,21 @@ def _register_torch_ops() -> None:
     lib.impl("resize_many", lambda images, output_size, mode="bilinear", boxes=None: resize_many(
         list(images), output_size, mode, boxes=_many_boxes(images, boxes)), "CUDA")
     lib.impl("resize_many", _many_meta, "Meta")
+    lib.define('resize_many_to_float(Tensor[] images, int[] output_size, str mode="bilinear", float[]? boxes=None, bool[]? flips=None, '
+               'ScalarType? out_dtype=None, str? out_format=None, float[]? mean=None, float[]? std=None) -> Tensor')
+
+    def _many_float_meta(images, output_size, mode="bilinear", boxes=None, flips=None, out_dtype=None, out_format=None, mean=None, std=None):
+        u = _many_meta(images, output_size, mode, boxes)
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        nhwc = u.is_contiguous(memory_format=torch.channels_last) and not u.is_contiguous() if out_format is None else out_format == "nhwc"
+        return torch.empty(u.shape, dtype=out_dtype, device="meta", memory_format=torch.channels_last if nhwc else torch.contiguous_format)
+
+    lib.impl("resize_many_to_float", lambda images, output_size, mode="bilinear", boxes=None, flips=None, out_dtype=None,
+             out_format=None, mean=None, std=None: resize_many_to_float(
+                 list(images), output_size, mode, boxes=_many_boxes(images, boxes), flips=flips,
+                 out_dtype=torch.float32 if out_dtype is None else out_dtype, out_format=out_format,
+                 mean=mean, std=std), "CUDA")
+    lib.impl("resize_many_to_float", _many_float_meta, "Meta")
 
     for name, fn in bwds.items():
         lib.impl(name, (lambda f: lambda grad_output, output_size, input_size, align_corners=False:

@@ -1,0 +1,350 @@
+"""resize_many_to_float on the GPU.  Expected values never come from the call under test: the bytes are the CPU restatement's (pinned to
+Pillow by the CPU tests; the fixture's CRC where the result is bytes again) or, for an ad-hoc shape, the unchanged resize_many's, and the
+conversion is torch's on the CPU: ((b.float() - mean) / std).to(dtype), .flip(-1).  Bit patterns are compared: tolerance 0."""
+import ctypes
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import resize_many_ref as ref  # noqa: E402
+
+from interpolate_antialiasing_amd import _lib  # noqa: E402
+from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
+from interpolate_antialiasing_amd import tables  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+G = ref.gen()
+CASE_NAMES = [cs[0] for cs in G.CASES]
+MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "box", "hamming": "hamming", "lanczos": "lanczos"}
+CLASSES = [(name, cls) for name in CASE_NAMES for cls in (("planar",) if G.case(name)[1] == 1 else ("interleaved", "planar"))]
+NORMALISED = [(name, cls) for name, cls in CLASSES if name in ("m_mixed", "m_c1", "m_c2", "m_c4", "m_strips", "m_tiny37")]
+DTYPES = [torch.float32, torch.float16, torch.bfloat16]
+FORMATS = ["nchw", "nhwc"]
+MEAN = [123.675, 116.28, 103.53, 127.5]
+STD = [58.395, 57.12, 57.375, 64.0]
+
+
+def _to_gpu(x_chw, cls):
+    """[C, H, W] numpy -> a GPU tensor [C, H, W] lying in memory as the class says."""
+    if cls == "interleaved":
+        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
+    return torch.from_numpy(np.ascontiguousarray(x_chw)).cuda()
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(name, cls):
+    """The case's images on the GPU (shared between tests, never written): a list, or one [N, C, H, W] tensor for a batch case."""
+    cs = G.case(name)
+    items = [_to_gpu(ref.item(name, i), cls) for i in range(len(cs[3]))]
+    if cs[6]:
+        x = torch.stack(items)
+        return x.contiguous(memory_format=torch.channels_last) if cls == "interleaved" else x.contiguous()
+    return items
+
+
+def _boxes(name):
+    return [it[2] for it in G.case(name)[3]]
+
+
+@functools.lru_cache(maxsize=None)
+def _bytes(name, f):
+    """Pillow's bytes of one case and filter from the CPU restatement: [N, C, oH, oW] uint8 on the CPU (shared, never written)."""
+    cs = G.case(name)
+    return torch.from_numpy(np.stack([G.restated(cs, f, i, ref.item(name, i)).transpose(2, 0, 1) for i in range(len(cs[3]))]))
+
+
+def _convert(b, dtype, norm, flips=None):
+    """The definition, by torch on the CPU: b [N, C, oH, oW] uint8 -> the expected tensor."""
+    c = b.shape[1]
+    f = b.float()
+    if norm:
+        f = (f - torch.tensor(MEAN[:c]).view(1, c, 1, 1)) / torch.tensor(STD[:c]).view(1, c, 1, 1)
+    y = f.to(dtype)
+    if flips is not None:
+        y = torch.stack([y[i].flip(-1) if flips[i] else y[i] for i in range(len(flips))])
+    return y
+
+
+def _bits(t):
+    t = t.cpu().contiguous()
+    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+def _assert_bits(got, want, what):
+    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), what
+    a, b = _bits(got), _bits(want)
+    if not torch.equal(a, b):
+        bad = (a != b).nonzero()
+        raise AssertionError(f"{what}: {len(bad)} of {a.numel()} elements differ, first at {bad[0].tolist()}: "
+                             f"{got.cpu()[tuple(bad[0])].item()} != {want[tuple(bad[0])].item()}")
+
+
+def _assert_format(y, fmt, c):
+    if c > 1:
+        assert y.is_contiguous(memory_format=torch.channels_last) == (fmt == "nhwc") and y.is_contiguous() == (fmt == "nchw")
+    else:
+        assert y.is_contiguous()
+
+
+def _norm(c, norm=True):
+    return {"mean": MEAN[:c], "std": STD[:c]} if norm else {}
+
+
+@pytest.mark.parametrize("name,cls", CLASSES)
+def test_identity_every_case_filter_class_and_format_is_pillows_bytes(name, cls):
+    cs = G.case(name)
+    for f in cs[4]:
+        for fmt in FORMATS:
+            y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), out_format=fmt)
+            assert y.dtype == torch.float32 and tuple(y.shape) == (len(cs[3]), cs[1]) + tuple(cs[2])
+            _assert_format(y, fmt, cs[1])
+            got = y.to(torch.uint8).cpu()
+            assert torch.equal(got.float(), y.cpu())  # whole bytes, nothing else
+            for i in range(len(cs[3])):
+                ref.assert_matches_fixture(f"{name}/{f}/{i}", ref.item(name, i), got[i].permute(1, 2, 0).numpy())
+        # out_format None follows the class of the items
+        y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[cs[4][0]], boxes=_boxes(name))
+        _assert_format(y, "nhwc" if cls == "interleaved" else "nchw", cs[1])
+        _assert_bits(y, _convert(_bytes(name, cs[4][0]), torch.float32, False), f"{name}/{cls}/default format")
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16", "bf16"])
+@pytest.mark.parametrize("name,cls", NORMALISED)
+def test_normalised_every_dtype_class_and_format(name, cls, dtype):
+    cs = G.case(name)
+    for f in cs[4]:
+        want = _convert(_bytes(name, f), dtype, True)
+        for fmt in FORMATS:
+            y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), out_dtype=dtype, out_format=fmt,
+                                        **_norm(cs[1]))
+            _assert_format(y, fmt, cs[1])
+            _assert_bits(y, want, f"{name}/{f}/{cls}/{fmt}/{dtype}")
+    # without mean / std the 16-bit types are the byte, converted
+    f = cs[4][0]
+    y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), out_dtype=dtype, out_format="nchw")
+    _assert_bits(y, _convert(_bytes(name, f), dtype, False), f"{name}/{f}/{cls}/no normalisation/{dtype}")
+
+
+@pytest.mark.parametrize("cls", ["interleaved", "planar"])
+@pytest.mark.parametrize("name,f,flips", [("m_mixed", "cubic", [True, False] * 4 + [True]), ("m_mixed", "linear", [False, True] * 4 + [False]),
+                                           ("m_strips", "hamming", [True, False]), ("m_strips", "hamming", [False, True])])
+def test_flips_mirror_the_flagged_items_and_leave_the_others(name, f, flips, cls):
+    cs = G.case(name)
+    for dtype in DTYPES:
+        plain = _convert(_bytes(name, f), dtype, True)
+        want = _convert(_bytes(name, f), dtype, True, flips)
+        for i, fl in enumerate(flips):  # (what the expectation itself says: flagged items mirrored, the others untouched)
+            assert torch.equal(_bits(want[i]), _bits(plain[i].flip(-1) if fl else plain[i]))
+        for fmt in FORMATS:
+            y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), flips=flips, out_dtype=dtype,
+                                        out_format=fmt, **_norm(cs[1]))
+            _assert_format(y, fmt, cs[1])
+            _assert_bits(y, want, f"{name}/{f}/{cls}/{fmt}/{dtype}/flips")
+    # truthy / falsy entries of any kind
+    y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), flips=[int(v) for v in flips],
+                                out_dtype=torch.bfloat16, out_format="nchw", **_norm(cs[1]))
+    _assert_bits(y, _convert(_bytes(name, f), torch.bfloat16, True, flips), f"{name}/{f}/{cls}/int flips")
+
+
+def _adhoc(c, sizes, cls, seed):
+    rng = np.random.default_rng(seed)
+    return [_to_gpu(rng.integers(0, 256, (c, h, w), dtype=np.uint8), cls) for h, w in sizes]
+
+
+@pytest.mark.parametrize("ow", [1, 2])
+def test_flips_of_outputs_one_and_two_columns_wide(ow):
+    imgs = _adhoc(3, [(23, 31), (9, 5), (40, 2)], "interleaved", 100 + ow)
+    boxes = [None, (0.5, 1.0, 4.25, 8.0), None]
+    flips = [True, False, True]
+    u = aa.resize_many(imgs, [7, ow], "bicubic", boxes=boxes).cpu()
+    y = aa.resize_many_to_float(imgs, [7, ow], "bicubic", boxes=boxes, flips=flips, out_dtype=torch.bfloat16, out_format="nchw", **_norm(3))
+    assert y.is_contiguous()
+    _assert_bits(y, _convert(u, torch.bfloat16, True, flips), f"ow = {ow}")
+
+
+# Rows longer than one workgroup's piece of the converting pass (1024 / 512 / 256 / 256 pixels for 1 / 2 / 3 / 4 bytes per pixel), the last
+# piece ragged, odd widths (rows of 16-bit elements that start 2-byte aligned only), flipped and not.
+@pytest.mark.parametrize("c,cls,ow", [(3, "interleaved", 301), (3, "interleaved", 513), (4, "interleaved", 259), (2, "interleaved", 515),
+                                      (2, "planar", 1031), (1, "planar", 1027)])
+def test_rows_of_several_pieces(c, cls, ow):
+    imgs = _adhoc(c, [(5, 400), (4, 37)], cls, 200 + ow)
+    flips = [True, False]
+    u = aa.resize_many(imgs, [3, ow], "bilinear").cpu()
+    for dtype in DTYPES:
+        want = _convert(u, dtype, True, flips)
+        for fmt in FORMATS:
+            y = aa.resize_many_to_float(imgs, [3, ow], "bilinear", flips=flips, out_dtype=dtype, out_format=fmt, **_norm(c))
+            _assert_format(y, fmt, c)
+            _assert_bits(y, want, f"C = {c}/{cls}/ow = {ow}/{fmt}/{dtype}")
+
+
+def _pitched_crop(x_chw, cls, k):
+    """The image as a crop of a larger padded buffer: an odd byte offset and a row pitch that is no multiple of 4."""
+    c, h, w = x_chw.shape
+    off = 1 + 2 * (k % 2)
+    if cls == "interleaved":
+        pitch = w * c + 5
+        pitch += 1 if pitch % 4 == 0 else 0
+        buf = torch.full((off + h * pitch + 16,), 0xA5, dtype=torch.uint8, device="cuda")
+        v = buf.as_strided((c, h, w), (1, pitch, c), off)
+    else:
+        pitch = w + 6
+        pitch += 1 if pitch % 4 == 0 else 0
+        plane = h * pitch + 7
+        buf = torch.full((off + c * plane + 16,), 0xA5, dtype=torch.uint8, device="cuda")
+        v = buf.as_strided((c, h, w), (plane, pitch, 1), off)
+    assert pitch % 4 != 0 and v.data_ptr() % 2 == 1
+    v.copy_(torch.from_numpy(np.ascontiguousarray(x_chw)).cuda())
+    return v
+
+
+@pytest.mark.parametrize("cls", ["interleaved", "planar"])
+@pytest.mark.parametrize("name", ["m_mixed", "m_c4"])
+def test_crops_at_odd_offsets_and_pitches_equal_the_dense_call(name, cls):
+    cs = G.case(name)
+    crops = [_pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[3]))]
+    flips = [i % 3 == 0 for i in range(len(cs[3]))]
+    for f in cs[4]:
+        kw = dict(boxes=_boxes(name), flips=flips, out_dtype=torch.float16, out_format="nchw", **_norm(cs[1]))
+        y = aa.resize_many_to_float(crops, list(cs[2]), MODE[f], **kw)
+        dense = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], **kw)
+        assert y.stride() == dense.stride() and torch.equal(_bits(y), _bits(dense))
+        _assert_bits(y, _convert(_bytes(name, f), torch.float16, True, flips), f"{name}/{f}/{cls}/crops")
+
+
+def test_c_abi_output_that_is_only_two_byte_aligned():
+    """float16, odd oW, interleaved -> nchw, out_dev = a buffer's address + 2: the same elements as the aligned call, and the elements
+    before and after the output region keep their sentinel."""
+    name, f = "m_mixed", "cubic"
+    cs = G.case(name)
+    imgs, boxes = _inputs(name, "interleaved"), _boxes(name)
+    n, c, (oh, ow) = len(imgs), cs[1], cs[2]
+    assert ow % 2 == 1
+    flips = [i % 2 == 1 for i in range(n)]
+    aligned = aa.resize_many_to_float(imgs, [oh, ow], MODE[f], boxes=boxes, flips=flips, out_dtype=torch.float16, out_format="nchw", **_norm(c))
+    L = _lib.load()
+    recs = (_lib.ManyImage * n)()
+    for i, t in enumerate(imgs):
+        r = recs[i]
+        r.data_dev, r.H, r.W = t.data_ptr(), int(t.shape[1]), int(t.shape[2])
+        r.stride_ch, r.stride_row, r.stride_px = 1, t.stride(1), c
+        if boxes[i] is not None:
+            r.has_box = 1
+            for q in range(4):
+                r.box[q] = boxes[i][q]
+        r.flags = _lib.MANY_FLIP_X if flips[i] else 0
+    desc_bytes = L.aa_many_desc_bytes(n)
+    desc_host = torch.empty(desc_bytes, dtype=torch.uint8)
+    ws_bytes = ctypes.c_size_t(0)
+    assert L.aa_many_plan(_lib.FILTER_IDS[MODE[f]], _lib.NHWC, n, c, oh, ow, recs, desc_host.data_ptr(), desc_bytes, ctypes.byref(ws_bytes)) == 0
+    desc_dev = desc_host.cuda()
+    ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device="cuda")
+    numel = n * c * oh * ow
+    sentinel = -1234.0
+    buf = torch.full((1 + numel + 7,), sentinel, dtype=torch.float16, device="cuda")
+    out_ptr = buf.data_ptr() + 2
+    assert out_ptr % 4 == 2
+    cv = _lib.Convert()
+    cv.out_layout, cv.normalize, cv.flags = _lib.NCHW, 1, _lib.FLAG_OUT_F16
+    for i in range(c):
+        cv.mean[i], cv.std[i] = MEAN[i], STD[i]
+    rc = L.aa_resample_many_u8_to_float(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, _lib.NHWC, out_ptr, ws.data_ptr(), ws.numel(),
+                                        ctypes.byref(cv), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0
+    torch.cuda.synchronize()
+    got = buf.cpu()
+    assert torch.equal(_bits(got[1:1 + numel].view(n, c, oh, ow)), _bits(aligned))
+    assert (got[:1] == sentinel).all() and (got[1 + numel:] == sentinel).all()
+    _assert_bits(aligned, _convert(_bytes(name, f), torch.float16, True, flips), "the aligned call")
+
+
+def _strips_call(imgs, **kw):
+    return aa.resize_many_to_float(imgs, [4, 130], "hamming", boxes=_boxes("m_strips"), flips=[True, False], out_dtype=torch.bfloat16,
+                                   out_format="nchw", **_norm(3), **kw)
+
+
+def _strips_want():
+    return _convert(_bytes("m_strips", "hamming"), torch.bfloat16, True, [True, False])
+
+
+def test_non_default_stream():
+    imgs = _inputs("m_strips", "interleaved")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        y = _strips_call(imgs)
+    s.synchronize()
+    _assert_bits(y, _strips_want(), "non-default stream")
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_non_current_device():
+    imgs = [t.to("cuda:1") for t in _inputs("m_strips", "interleaved")]
+    assert torch.cuda.current_device() == 0
+    y = _strips_call(imgs)
+    assert y.device == imgs[0].device and torch.cuda.current_device() == 0
+    torch.cuda.synchronize(1)
+    _assert_bits(y, _strips_want(), "non-current device")
+
+
+def test_torch_op():
+    name = "m_c2"
+    imgs, boxes = _inputs(name, "interleaved"), _boxes(name)
+    flat = []
+    for t, b in zip(imgs, boxes):
+        flat += [float(v) for v in (b if b is not None else (0, 0, t.shape[2], t.shape[1]))]
+    flips = [False, True, True]
+    y = torch.ops.extension_interpolate.resize_many_to_float(imgs, [19, 77], "bicubic", flat, flips, torch.bfloat16, "nchw", MEAN[:2], STD[:2])
+    assert y.is_contiguous()
+    _assert_bits(y, _convert(_bytes(name, "cubic"), torch.bfloat16, True, flips), "the torch op")
+    y = torch.ops.extension_interpolate.resize_many_to_float(imgs, [19, 77], "bicubic", flat)
+    assert y.dtype == torch.float32 and y.is_contiguous(memory_format=torch.channels_last)
+    _assert_bits(y, _convert(_bytes(name, "cubic"), torch.float32, False), "the torch op, defaults")
+
+
+def test_a_mixed_list_copies_the_minority():
+    name = "m_c4"
+    inter, planar = _inputs(name, "interleaved"), _inputs(name, "planar")
+    flips = [True, False, True]
+    want = _convert(_bytes(name, "cubic"), torch.float16, True, flips)
+    kw = dict(boxes=_boxes(name), flips=flips, out_dtype=torch.float16, **_norm(4))
+    y = aa.resize_many_to_float([inter[0], planar[1], inter[2]], [19, 77], "bicubic", **kw)
+    assert y.is_contiguous(memory_format=torch.channels_last)  # (out_format None: the class of the call)
+    _assert_bits(y, want, "two interleaved, one planar")
+    y = aa.resize_many_to_float([planar[0], inter[1], planar[2]], [19, 77], "bicubic", **kw)
+    assert y.is_contiguous()
+    _assert_bits(y, want, "two planar, one interleaved")
+    y = aa.resize_many_to_float([planar[0], inter[1], planar[2]], [19, 77], "bicubic", out_format="nhwc", **kw)
+    assert y.is_contiguous(memory_format=torch.channels_last)
+    _assert_bits(y, want, "two planar, one interleaved, nhwc")
+
+
+def test_permuting_the_items_permutes_the_output():
+    name, f = "m_mixed", "lanczos"
+    imgs, boxes = _inputs(name, "interleaved"), _boxes(name)
+    perm = [4, 8, 0, 6, 2, 7, 1, 5, 3]
+    flips = [i % 2 == 0 for i in range(9)]
+    yp = aa.resize_many_to_float([imgs[p] for p in perm], [30, 45], MODE[f], boxes=[boxes[p] for p in perm], flips=[flips[p] for p in perm],
+                                 out_dtype=torch.bfloat16, out_format="nchw", **_norm(3))
+    _assert_bits(yp, _convert(_bytes(name, f), torch.bfloat16, True, flips)[perm], "permuted items")
+
+
+def test_empty_batch_and_no_cache_is_read_or_written():
+    for dtype in DTYPES:
+        e = aa.resize_many_to_float([], [30, 45], channels=3, out_dtype=dtype)
+        assert tuple(e.shape) == (0, 3, 30, 45) and e.dtype == dtype and e.is_cuda
+        e = aa.resize_many_to_float(_inputs("m_batchbox", "planar")[:0], [30, 45], out_dtype=dtype, flips=[], **_norm(3))
+        assert tuple(e.shape) == (0, 3, 30, 45) and e.dtype == dtype and e.is_cuda
+    before = (len(tables._cache), len(tables._box_cache), len(aa._plans))
+    y = aa.resize_many_to_float(_inputs("m_mixed", "interleaved"), [30, 45], "bicubic", boxes=_boxes("m_mixed"), out_dtype=torch.bfloat16,
+                                out_format="nchw", **_norm(3))
+    torch.cuda.synchronize()
+    assert (len(tables._cache), len(tables._box_cache), len(aa._plans)) == before
+    _assert_bits(y, _convert(_bytes("m_mixed", "cubic"), torch.bfloat16, True), "m_mixed/cubic")

@@ -6,13 +6,23 @@
   (b) the same loop with fixed boxes and warm caches (the 32-entry box LRU widened so that all N pairs stay in it);
   (c) resize_many: one call per batch, fresh boxes every batch (it has no cache to warm).
 
+and the step after it — the batch as the normalised float tensor a model reads (bicubic, NCHW, mean / std, half the items flipped; bfloat16
+and float32) — two ways:
+
+  (d) the composition: resize_many, then .float(), - mean, / std, .to(dtype), .contiguous(), an indexed .flip(-1);
+  (e) resize_many_to_float: one call, the same three launches as (c).
+
+(e) must beat (d) by more than the two spreads together; both give the same bits.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
 
   python tools/resize_many_bench.py                      # the timing table
+  python tools/resize_many_bench.py --float-only         # only the (d) / (e) table
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
+  python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
   python tools/resize_many_bench.py --summarise DIR      # kernels and copies per call, kernel time and bytes / time from that trace
 """
 import argparse
@@ -91,6 +101,12 @@ def summarise(trace_dir, calls):
     return {k: statistics.median(v[WARM_CALLS:] if len(v) > WARM_CALLS else v) for k, v in ours.items()}
 
 
+def _lib_path():
+    from interpolate_antialiasing_amd import _lib
+
+    return _lib.LIB_PATH
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -98,6 +114,8 @@ def main():
     ap.add_argument("--trace", type=int, default=0)
     ap.add_argument("--trace-mode", default="bilinear")
     ap.add_argument("--summarise", default=None)
+    ap.add_argument("--float-only", action="store_true")
+    ap.add_argument("--trace-float", action="store_true", help="with --trace: the calls are resize_many_to_float (bfloat16, nchw, mean / std, flips)")
     args = ap.parse_args()
 
     rng = np.random.default_rng(SEED)
@@ -134,7 +152,11 @@ def main():
 
     if args.trace:
         for _ in range(WARM_CALLS + args.trace):
-            aa.resize_many(images, list(OUT), args.trace_mode, boxes=fresh_boxes())
+            if args.trace_float:
+                aa.resize_many_to_float(images, list(OUT), args.trace_mode, boxes=fresh_boxes(), flips=[i % 2 == 1 for i in range(N)],
+                                        out_dtype=torch.bfloat16, out_format="nchw", mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375])
+            else:
+                aa.resize_many(images, list(OUT), args.trace_mode, boxes=fresh_boxes())
         torch.cuda.synchronize()
         return
 
@@ -159,7 +181,7 @@ def main():
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
     print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
-    for mode in MODES:
+    for mode in ([] if args.float_only else MODES):
         contestants = {
             "a: per-image loop, unseen boxes": lambda: loop(mode, fresh_boxes()),
             "b: per-image loop, fixed boxes, warm": lambda: loop(mode, fixed),
@@ -186,6 +208,49 @@ def main():
         verdict = "PASS" if gain > spreads else "FAIL: the design has failed its purpose"
         print(f"  (c) against (a): {ma / mc:.2f} x; median gain {gain:.3f} ms against the two spreads together {spreads:.3f} ms: {verdict}")
         print(f"  (c) against (b): {mb / mc:.2f} x (no bar: what a fused single-launch follow-up would have to beat)")
+
+    # the float batch: the composition against the one call
+    mean, std = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
+    mean_t, std_t = (torch.tensor(v, device="cuda").view(1, 3, 1, 1) for v in (mean, std))
+    flips = [i % 2 == 1 for i in range(N)]
+    flip_idx = torch.tensor([i for i in range(N) if flips[i]], device="cuda")
+    mode = "bicubic"
+
+    def composition(dtype, boxes):
+        y = ((aa.resize_many(images, list(OUT), mode, boxes=boxes).float() - mean_t) / std_t).to(dtype).contiguous()
+        y[flip_idx] = y[flip_idx].flip(-1)
+        return y
+
+    def one_call(dtype, boxes):
+        return aa.resize_many_to_float(images, list(OUT), mode, boxes=boxes, flips=flips, out_dtype=dtype, out_format="nchw", mean=mean, std=std)
+
+    print(f"\nthe float batch ({mode}, nchw, mean / std, {len(flip_idx)} of {N} items flipped; library: {os.path.basename(_lib_path())})")
+    for dtype in (torch.bfloat16, torch.float32):
+        contestants = {
+            "d: resize_many + torch conversion": lambda: composition(dtype, fresh_boxes()),
+            "e: resize_many_to_float": lambda: one_call(dtype, fresh_boxes()),
+        }
+        for fn in contestants.values():
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        a, b = composition(dtype, fixed), one_call(dtype, fixed)
+        assert a.stride() == b.stride() and torch.equal(a.view(torch.int16 if dtype == torch.bfloat16 else torch.int32),
+                                                        b.view(torch.int16 if dtype == torch.bfloat16 else torch.int32)), \
+            "resize_many_to_float differs from the composition"
+        times = {k: [] for k in contestants}
+        for _ in range(args.rounds):
+            for k, fn in contestants.items():
+                times[k].append(timed(fn))
+        print(f"\n{str(dtype).replace('torch.', '')}")
+        stat = {}
+        for k, v in times.items():
+            stat[k] = (statistics.median(v), min(v), max(v))
+            print(f"  {k:40s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]")
+        (md, ld, hd), (me, le, he) = stat.values()
+        gain, spreads = md - me, (hd - ld) + (he - le)
+        verdict = "PASS" if gain > spreads else "FAIL: the gain is within the spread"
+        print(f"  (e) against (d): {md / me:.2f} x; median gain {gain:.3f} ms against the two spreads together {spreads:.3f} ms: {verdict}")
 
 
 if __name__ == "__main__":
