@@ -149,8 +149,20 @@ __global__ void table_gather_kernel(char *table, int out_size, int ksize, int ga
   if (i < out_size) table_gather_one(i, table, out_size, ksize, gather_off);
 }
 
+// The alignment padding of a table (up to 8 bytes after xsize[], up to 12 after the weight rows) is zeroed: no kernel reads it, but a table
+// travels as bytes (the broadcast to other ranks, the caches), and every byte of it is defined by its arguments alone.
+__device__ void table_zero_padding(const aa_table_header &h, char *table) {
+  const size_t w0 = aa_table_w_off(h.out_size);
+  for (size_t b = aa_table_xsize_off(h.out_size) + 4 * (size_t)h.out_size; b < w0; b++) table[b] = 0;
+  const size_t w1 = aa_table_weights_end(h.kind, h.out_size, h.ksize);
+  for (size_t b = w0 + (size_t)h.out_size * (size_t)h.ksize * aa_weight_elem_bytes(h.kind); b < w1; b++) table[b] = 0;
+}
+
 __global__ void table_write_header(aa_table_header h, char *table) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *(aa_table_header *)table = h;
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    *(aa_table_header *)table = h;
+    table_zero_padding(h, table);
+  }
 }
 
 // ---- adjoint (gather-form) table -----------------------------------------------------------------------
@@ -232,6 +244,7 @@ __device__ void table_scatter_one(int x, const char *fwd, int32_t *rec_all, int3
     const int o = first + k;
     rw[k] = (k < cnt) ? w[(size_t)o * ksize + (x - xmin[o])] : (WT)0;
   }
+  if constexpr (sizeof(WT) == 8) rec[14] = rec[15] = 0;  // (the 8 bytes that fill a double record up to 64)
   atomicMax(scatter_max, cnt > 1 ? cnt : 1);
 }
 template <typename WT>
@@ -259,7 +272,10 @@ __global__ void __launch_bounds__(1024) table_build_jobs(TableJob a, TableJob b,
 template <int KIND>
 __device__ void table_build_body(const aa_table_header &h, int filter, int in_size, int out_size, int ksize, double scale, char *table,
                                  const BoxArgs &bx) {
-  if (threadIdx.x == 0) *(aa_table_header *)table = h;
+  if (threadIdx.x == 0) {
+    *(aa_table_header *)table = h;
+    table_zero_padding(h, table);
+  }
   __syncthreads();
   for (int i = threadIdx.x; i < out_size; i += blockDim.x) {
     if constexpr (KIND == AA_TABLE_F32) table_build_f32_one(i, filter, in_size, out_size, ksize, (float)scale, table);
