@@ -352,6 +352,20 @@ size_t aa_many_desc_bytes(int64_t n);
  * image, or more work units than one grid holds; AA_ERR_STRIDES for an item that is not in `layout`'s class; AA_ERR_KSIZE. */
 int aa_many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, void *desc_host,
                  size_t desc_bytes, size_t *workspace_bytes);
+/* PLACED plans: item i is resized to ITS OWN size [vH, vW] exactly as Pillow would (box included), and that result's top-left corner
+ * is put at (oy, ox) of the dense [oH, oW] output.  A negative offset crops, a positive one pads; what falls outside the output is never
+ * computed, and what the item does not cover is fill[c] (Resize + CenterCrop, letterbox, fit-and-pad).  An item that lies wholly
+ * outside is legal: all fill, no work.  vH, vW in 1 .. INT32_MAX / 4, |oy|, |ox| <= INT32_MAX / 4, AA_ERR_BAD_SHAPE beyond.
+ * The block of a placed plan is larger: desc_bytes >= aa_many_desc_bytes_placed(n), and that many bytes are copied to the device.
+ * places NULL, or every place {oH, oW, 0, 0}: exactly aa_many_plan's block (aa_many_desc_bytes(n) suffices), whatever the fill.
+ * fill NULL: 0; entries beyond C are not looked at by the kernels.  aa_resample_many_u8 and aa_resample_many_u8_to_float serve a placed
+ * plan with their signatures unchanged: the fill byte is converted like any other byte, and a flip mirrors the whole output row.
+ * Added without an ABI version change (additive). */
+typedef struct aa_many_place { int64_t vH, vW, oy, ox; } aa_many_place;   /* size Pillow resizes to; where its corner lands */
+size_t aa_many_desc_bytes_placed(int64_t n);
+int aa_many_plan_placed(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                        const aa_many_place *places /* NULL: aa_many_plan */, const uint8_t fill[4] /* NULL: 0 */,
+                        void *desc_host, size_t desc_bytes, size_t *workspace_bytes);
 /* Enqueue the three launches.  desc_dev: the device copy of desc_host (8-byte aligned), in flight or complete on `stream`; desc_host is
  * read only to size the grids and to check the arguments against the plan.  out_dev [n, C, oH, oW] uint8, dense, in `layout`.
  * workspace_dev: 16-byte aligned, at least the plan's size.  Nothing is allocated, nothing is synchronised.  n == 0 launches nothing. */

@@ -51,6 +51,7 @@ EXPORTS = (
     "aa_last_variant", "aa_probe_copy", "aa_workspace_bytes_u8_to_f32", "aa_resample_fwd_u8_to_f32", "aa_set_store_form", "aa_set_plane_groups", "aa_resample_fwd_ex", "aa_resample_fwd_strided",
     "aa_workspace_bytes_ex", "aa_table_ksize_box", "aa_table_build_bytes_box", "aa_table_build_box", "aa_reduce_u8", "aa_premultiply_u8",
     "aa_unpremultiply_u8", "aa_many_desc_bytes", "aa_many_plan", "aa_resample_many_u8", "aa_resample_many_u8_to_float",
+    "aa_many_desc_bytes_placed", "aa_many_plan_placed",
 )
 
 
@@ -100,6 +101,18 @@ class ManyItem(ctypes.Structure):
                 ("box_on", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class ManyPlace(ctypes.Structure):
+    """aa_many_place: the size [vH, vW] Pillow resizes an item to and where that result's corner lands on the canvas."""
+    _fields_ = [("vH", ctypes.c_int64), ("vW", ctypes.c_int64), ("oy", ctypes.c_int64), ("ox", ctypes.c_int64)]
+
+
+class ManyPlaced(ctypes.Structure):
+    """A placed plan's second record of an item (csrc/aa_many.h AAManyPlace): per axis the item's own size v, the covered part
+    [v0, v0 + m) of it and the canvas index d that part starts at."""
+    _fields_ = [("vh", ctypes.c_int32), ("vw", ctypes.c_int32), ("v0h", ctypes.c_int32), ("v0w", ctypes.c_int32), ("mh", ctypes.c_int32),
+                ("mw", ctypes.c_int32), ("dy", ctypes.c_int32), ("dx", ctypes.c_int32)]
+
+
 MANY_FLIP_X = 1     # aa_many_image.flags: mirror the item's output left to right (aa_resample_many_u8_to_float only)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
@@ -110,6 +123,11 @@ def many_desc_view(buf, n: int):
     items = (ManyItem * n).from_buffer(buf, ctypes.sizeof(ManyHeader))
     prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(ManyHeader) + n * ctypes.sizeof(ManyItem))
     return hd, items, prefix
+
+
+def many_placed_view(buf, n: int):
+    """The placement records of a placed plan's block (ManyHeader.reserved[0] == 1): they follow the prefix sums."""
+    return (ManyPlaced * n).from_buffer(buf, ctypes.sizeof(ManyHeader) + n * ctypes.sizeof(ManyItem) + 8 * (n + 1))
 
 
 class AAInterpError(RuntimeError):
@@ -197,6 +215,11 @@ def load() -> ctypes.CDLL:
     L.aa_many_desc_bytes.restype = sz
     L.aa_many_plan.argtypes = [i32, i32, i64, i64, i64, i64, ctypes.POINTER(ManyImage), vp, sz, ctypes.POINTER(sz)]
     L.aa_many_plan.restype = i32
+    L.aa_many_desc_bytes_placed.argtypes = [i64]
+    L.aa_many_desc_bytes_placed.restype = sz
+    L.aa_many_plan_placed.argtypes = [i32, i32, i64, i64, i64, i64, ctypes.POINTER(ManyImage), ctypes.POINTER(ManyPlace),
+                                      ctypes.POINTER(ctypes.c_uint8), vp, sz, ctypes.POINTER(sz)]
+    L.aa_many_plan_placed.restype = i32
     L.aa_resample_many_u8.argtypes = [vp, vp, i64, i64, i64, i64, i32, vp, vp, sz, vp]
     L.aa_resample_many_u8.restype = i32
     L.aa_resample_many_u8_to_float.argtypes = [vp, vp, i64, i64, i64, i64, i32, vp, vp, sz, cvp, vp]

@@ -136,6 +136,35 @@ def axis_hull(in_size: int, out_size: int, in0: float, in1: float, filter_name: 
     return o, e
 
 
+def fit_sizes(shapes, shorter: Optional[int] = None, longer: Optional[int] = None):
+    """[(H_i, W_i)] -> [(vh_i, vw_i)], aspect ratio kept.  shorter=s: the short side becomes s and the long one int(s * long / short),
+    torchvision's Resize(int).  longer=s: the long side becomes s and the short one max(1, int(s * short / long)), the letterbox fit.
+    Exactly one of the two."""
+    if (shorter is None) == (longer is None):
+        raise ValueError("fit_sizes: give exactly one of shorter= and longer=")
+    s = int(shorter if shorter is not None else longer)
+    if s <= 0:
+        raise ValueError("fit_sizes: the side must be positive")
+    out = []
+    for h, w in shapes:
+        h, w = int(h), int(w)
+        if h <= 0 or w <= 0:
+            raise ValueError("fit_sizes: shapes must be positive")
+        short, long = (h, w) if h <= w else (w, h)
+        if shorter is not None:
+            a, b = s, int(s * long / short)  # (short side, long side)
+        else:
+            a, b = max(1, int(s * short / long)), s
+        out.append((a, b) if h <= w else (b, a))
+    return out
+
+
+def center_offset(v: int, o: int) -> int:
+    """Where the corner of an axis of v pixels lands on a canvas axis of o so that it is centred: a crop (v >= o) with the arithmetic of
+    torchvision's center_crop (Python's round, half to even), a pad (v < o) with the smaller half first."""
+    return -int(round((v - o) / 2.0)) if v >= o else (o - v) // 2
+
+
 def axis_is_full(in_size: int, in0: float, in1: float) -> bool:
     return in0 == 0 and in1 == in_size
 

@@ -454,7 +454,14 @@ size_t aa_many_desc_bytes(int64_t n) { return aa_many_desc_size(n); }
 
 int aa_many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, void *desc_host,
                  size_t desc_bytes, size_t *workspace_bytes) {
-  return aa_many_plan_host(filter, layout, n, C, oH, oW, images, desc_host, desc_bytes, workspace_bytes);
+  return aa_many_plan_host(filter, layout, n, C, oH, oW, images, nullptr, nullptr, desc_host, desc_bytes, workspace_bytes);
+}
+
+size_t aa_many_desc_bytes_placed(int64_t n) { return aa_many_desc_size_placed(n); }
+
+int aa_many_plan_placed(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                        const aa_many_place *places, const uint8_t fill[4], void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
+  return aa_many_plan_host(filter, layout, n, C, oH, oW, images, places, fill, desc_host, desc_bytes, workspace_bytes);
 }
 
 int aa_resample_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,

@@ -35,6 +35,23 @@ __host__ __device__ inline bool aa_filters_nonneg(int filter_a, int filter_b) {
   return aa_filter_info(filter_a).nonneg && aa_filter_info(filter_b).nonneg;
 }
 
+// ---- four clipped sums in one dword --------------------------------------------------------------------
+// Pillow's clip8(ss >> PRECISION_BITS) is ONE gfx950 instruction for two values: v_ashr_pk_u8_i32 D, S0, S1, sh
+// writes D[7:0] = sat_u8(S0 >> sh), D[15:8] = sat_u8(S1 >> sh) and PRESERVES the other half of D (op_sel[3]=1
+// targets D[31:16] instead) — measured on MI355X (tools/microbench/test_pk.hip).  Written as inline asm on purpose:
+// ROCm 7.2's hipcc pattern-matches `clip(a)|clip(b)<<8` to this instruction but then treats the preserved upper
+// half as zero when the 16-bit result is widened, which corrupts bytes 2-3 of a packed dword (found by the parity
+// tests).  The form `r0 | r1 << 8 | r2 << 16 | r3 << 24` over four separately clipped values (the ragged call's
+// plain vertical pass) is not matched and needs no asm.  VALU results are interlocked in hardware, so no manual wait
+// states are needed around these.
+__device__ inline unsigned pack4_clip8(int a0, int a1, int a2, int a3) {
+  unsigned d;
+  asm("v_ashr_pk_u8_i32 %0, %1, %2, 22\n\tv_ashr_pk_u8_i32 %0, %3, %4, 22 op_sel:[0,0,0,1]"
+      : "=&v"(d)
+      : "v"(a0), "v"(a1), "v"(a2), "v"(a3));
+  return d;
+}
+
 // ---- packed table views --------------------------------------------------------------------------------
 __host__ __device__ inline size_t aa_align16(size_t x) { return (x + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t aa_weight_elem_bytes(int kind) { return kind == AA_TABLE_F64 ? 8 : 4; }

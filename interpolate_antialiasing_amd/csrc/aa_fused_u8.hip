@@ -66,19 +66,7 @@ __device__ inline void load_window(__amdgpu_buffer_rsrc_t rsrc, unsigned off, un
   }
 }
 
-// Pillow's clip8(ss >> PRECISION_BITS) is ONE gfx950 instruction for two values: v_ashr_pk_u8_i32 D, S0, S1, sh
-// writes D[7:0] = sat_u8(S0 >> sh), D[15:8] = sat_u8(S1 >> sh) and PRESERVES the other half of D (op_sel[3]=1
-// targets D[31:16] instead) — measured on MI355X (tools/microbench/test_pk.hip).  Written as inline asm on purpose:
-// ROCm 7.2's hipcc pattern-matches `clip(a)|clip(b)<<8` to this instruction but then treats the preserved upper
-// half as zero when the 16-bit result is widened, which corrupts bytes 2-3 of a packed dword (found by the parity
-// tests).  VALU results are interlocked in hardware, so no manual wait states are needed around these.
-__device__ inline unsigned pack4_clip8(int a0, int a1, int a2, int a3) {
-  unsigned d;
-  asm("v_ashr_pk_u8_i32 %0, %1, %2, 22\n\tv_ashr_pk_u8_i32 %0, %3, %4, 22 op_sel:[0,0,0,1]"
-      : "=&v"(d)
-      : "v"(a0), "v"(a1), "v"(a2), "v"(a3));
-  return d;
-}
+// (pack4_clip8, Pillow's clip8(ss >> PRECISION_BITS) of four sums in two instructions: aa_common.h)
 
 // K output rows per barrier; RB input rows of loads in flight per lane.
 // UA: byte-unaligned window loads (NV dwords straight at the window's byte offset; correct and ~1.16x faster than

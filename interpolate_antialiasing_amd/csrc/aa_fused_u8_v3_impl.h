@@ -126,13 +126,7 @@ constexpr int kStoreAuxInterleaved = AA_V3_STORE_AUX;
 
 
 
-__device__ inline unsigned pack4_clip8(int a0, int a1, int a2, int a3) {  // semantics: see aa_fused_u8.hip
-  unsigned d;
-  asm("v_ashr_pk_u8_i32 %0, %1, %2, 22\n\tv_ashr_pk_u8_i32 %0, %3, %4, 22 op_sel:[0,0,0,1]"
-      : "=&v"(d)
-      : "v"(a0), "v"(a1), "v"(a2), "v"(a3));
-  return d;
-}
+// (pack4_clip8: aa_common.h)
 
 // two fp32 values rounded to nearest even and packed, `lo` in the low half: bfloat16 (one instruction on gfx950; NaN stays NaN) / float16
 __device__ inline unsigned pack2_bf16(float lo, float hi) {

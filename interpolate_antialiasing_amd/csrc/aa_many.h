@@ -1,7 +1,8 @@
 // aa_many.h — the ragged call (include/aa_interp.h, "ragged batches"): N uint8 images of N sizes, each with its own box, into one dense
 // batch.  The packed descriptor block aa_many_plan writes on the host and the three kernels read on the device:
-//   [ AAManyHeader : 64 B ][ AAManyItem x n ][ int64 hunit_prefix[n + 1] ]
-// Everything a kernel needs about an item is in its record: no table header, nothing read back.
+//   [ AAManyHeader : 64 B ][ AAManyItem x n ][ int64 hunit_prefix[n + 1] ]            a plain plan (aa_many_desc_size)
+//   [ AAManyHeader : 64 B ][ AAManyItem x n ][ int64 hunit_prefix[n + 1] ][ AAManyPlace x n ]   a placed plan (aa_many_desc_size_placed)
+// Everything a kernel needs about an item is in its record(s): no table header, nothing read back.
 #pragma once
 
 #include "aa_common.h"
@@ -14,7 +15,7 @@ struct AAManyHeader {
   int32_t magic, n, C, oH, oW, filter, layout, reserved0;  // reserved0: 1 when some item flips (only the converting pass serves it)
   int64_t hunits;     // work units of the horizontal pass, all items: hunit_prefix[n]
   int64_t ws_bytes;   // table arena + intermediates
-  int64_t reserved[2];
+  int64_t reserved[2]; // [0]: 1 for a placed plan (AAManyPlace records follow the prefix sums); [1]: its fill, byte c = channel c's
 };
 static_assert(sizeof(AAManyHeader) == 64, "descriptor header is 64 bytes");
 
@@ -33,12 +34,25 @@ struct AAManyItem {
 };
 static_assert(sizeof(AAManyItem) == 112, "descriptor item is 112 bytes");
 
+// A placed plan's second record of an item: the item is resized to its own size [vh, vw] and that result's corner lies at (py, px) of
+// the [oH, oW] canvas.  Per axis the covered part of the result is [v0, v0 + m) and lands at canvas index d = v0 + p; the item's table of
+// that axis holds m entries (index 0 is result index v0), its intermediate hull_h rows of mw columns, each row led by (dx * E) & 3 bytes
+// so that a canvas dword of the vertical pass is a dword of the intermediate.  An item covered on no axis has m = hull = ksize = 0.
+struct AAManyPlace {
+  int32_t vh, vw, v0h, v0w, mh, mw, dy, dx;
+};
+static_assert(sizeof(AAManyPlace) == 32, "placement record is 32 bytes");
+__host__ __device__ inline int aa_many_placed_lead(int dx, int E) { return (int)(((int64_t)dx * E) & 3); }
+__host__ __device__ inline int64_t aa_many_placed_pitch(int dx, int mw, int E) { return (aa_many_placed_lead(dx, E) + (int64_t)mw * E + 3) & ~(int64_t)3; }
+
 inline size_t aa_many_table_bytes(int64_t out, int ksize) { return aa_align16(4 * (size_t)out * (2 + (size_t)ksize)); }
 __host__ __device__ inline int64_t aa_many_inter_pitch(int64_t oW, int E) { return (oW * E + 3) & ~(int64_t)3; }  // rows of the intermediate start on a dword
 
 size_t aa_many_desc_size(int64_t n);
-int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, void *desc_host,
-                      size_t desc_bytes, size_t *workspace_bytes);
+size_t aa_many_desc_size_placed(int64_t n);
+// places NULL, or every place the whole canvas at offset 0: the plain plan, whatever the fill.
+int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                      const aa_many_place *places, const uint8_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes);
 int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
                       void *workspace_dev, size_t workspace_bytes, hipStream_t stream);
 // The same with the converting vertical pass: out_elem AA_F32 / AA_F16 / AA_BF16, out_layout the layout of the dense output.

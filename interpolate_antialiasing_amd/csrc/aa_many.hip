@@ -6,6 +6,9 @@
 //   3. many_vpass   one workgroup per (item, plane, output row, 1 KiB of the row);
 //      or many_vpass_float, the converting form: the same sums, then byte -> float -> (v - mean) / std -> f32 / f16 / bf16, written in the
 //      requested layout, mirrored left to right for the items that flip.
+// A PLACED plan (template parameter PL) gives every item its own output size and a place on the canvas: the tables hold the covered
+// part of the item's own resize only, the horizontal pass computes the covered columns only, and the vertical pass, still one grid over
+// the whole canvas, writes the fill wherever the item is not.  The plain instantiations take none of it.
 // The host planner (aa_many_plan_host) computes every hull, ksize and offset with the same double arithmetic the table kernel uses, so
 // nothing comes back from the device: no header read-back, no atomicMax, no synchronisation, no allocation.
 
@@ -25,8 +28,11 @@ __device__ inline uint8_t clip8(int32_t a) {  // Pillow's clip8(ss >> PRECISION_
 }
 
 // ---- 1. tables -------------------------------------------------------------------------------------------------------------------------
-// One thread per (item, axis, output index): every item has oH + oW of them.
-__global__ void __launch_bounds__(256) many_tables(const AAManyItem *items, char *ws, int64_t n, int oH, int oW, int filter) {
+// One thread per (item, axis, output index): every item has oH + oW of them.  PL: an axis has its m <= o covered indices, the threads
+// beyond them idle; entry i is the window of index v0 + i of the item's own size v, at the scale of the whole axis (or box) over v.
+template <bool PL>
+__global__ void __launch_bounds__(256) many_tables(const AAManyItem *items, const AAManyPlace *places, char *ws, int64_t n, int oH, int oW,
+                                                   int filter) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int per = oH + oW;
   if (t >= n * per) return;
@@ -34,7 +40,15 @@ __global__ void __launch_bounds__(256) many_tables(const AAManyItem *items, char
   const int r = (int)(t % per);
   const bool vert = r < oH;
   const int i = vert ? r : r - oH;
-  const int out = vert ? oH : oW;
+  int out = vert ? oH : oW;
+  int v = out, v0 = 0;
+  if (PL) {
+    const AAManyPlace &pl = places[t / per];
+    out = vert ? pl.mh : pl.mw;
+    if (i >= out) return;
+    v = vert ? pl.vh : pl.vw;
+    v0 = vert ? pl.v0h : pl.v0w;
+  }
   const int ksize = vert ? it.ksize_h : it.ksize_w;
   const int hull = vert ? it.hull_h : it.hull_w;
   const BoxArgs bx = {vert ? it.in0_h : it.in0_w, vert ? it.in1_h : it.in1_w, vert ? it.oy : it.ox, it.box_on};
@@ -42,7 +56,10 @@ __global__ void __launch_bounds__(256) many_tables(const AAManyItem *items, char
   int32_t *xsize_p = xmin_p + out;
   int32_t *kk = xsize_p + out + (size_t)i * ksize;
   // (no box: the hull is the whole axis, origin 0, and in / out is the scale — aa_table_build's table)
-  const PilWindow wd = pil_window(i, filter, hull, out, bx);
+  // (PL, no box: in1 is the whole axis as a double, so in1 / v is the plain call's in / out)
+  const PilWindow wd = PL ? pil_window_at(v0 + i, filter, (bx.on ? (double)(float)(bx.in1 - bx.in0) : bx.in1) / (double)v, bx.in0, bx.origin,
+                                          bx.origin + hull)
+                          : pil_window(i, filter, hull, out, bx);
   xmin_p[i] = wd.xmin - bx.origin;
   xsize_p[i] = wd.xsize;
   pil_weights(wd, filter, ksize, kk);
@@ -57,8 +74,10 @@ __global__ void __launch_bounds__(256) many_tables(const AAManyItem *items, char
 constexpr int kChunkDwords = 2048;
 constexpr int kChunkBytes = 4 * kChunkDwords;
 
-template <int E>
-__global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem *items, const int64_t *prefix, char *ws, int n, int oW, int planes) {
+// PL: the item's own strip count, its covered columns [0, mw) of the table, and its own row pitch and lead in the intermediate.
+template <int E, bool PL>
+__global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem *items, const AAManyPlace *places, const int64_t *prefix, char *ws,
+                                                                int n, int oW, int planes) {
   __shared__ uint32_t seg[kChunkDwords];
   const int64_t unit = blockIdx.x;
   int lo = 0, hi = n;  // the item whose units hold `unit`: prefix[lo] <= unit < prefix[lo + 1]
@@ -68,6 +87,14 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
   }
   const AAManyItem &it = items[lo];
   int64_t u = unit - prefix[lo];
+  int lead = 0;
+  int64_t pitch = aa_many_inter_pitch(oW, E);
+  if (PL) {
+    const AAManyPlace &pl = places[lo];
+    oW = pl.mw;
+    lead = aa_many_placed_lead(pl.dx, E);
+    pitch = aa_many_placed_pitch(pl.dx, pl.mw, E);
+  }
   const int nstrips = (oW + AA_MANY_STRIP - 1) / AA_MANY_STRIP;
   const int strip = (int)(u % nstrips);
   u /= nstrips;
@@ -129,8 +156,8 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
     }
   }
   if (active) {
-    uint8_t *inter = (uint8_t *)ws + it.inter + ((int64_t)plane * hull_h + row) * aa_many_inter_pitch(oW, E);
-    inter[x0 * E + j] = clip8(ss);
+    uint8_t *inter = (uint8_t *)ws + it.inter + ((int64_t)plane * hull_h + row) * pitch;
+    inter[lead + x0 * E + j] = clip8(ss);
   }
 }
 
@@ -138,7 +165,54 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
 // Lane j owns bytes [4j, 4j + 4) of the output row, whatever they are (columns of a plane, channels of interleaved pixels): one aligned
 // dword load per tap row of the intermediate (its rows start on a dword), four sums, one dword store where the output address is
 // dword-aligned and all four bytes exist, byte stores otherwise.
-__global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const char *ws, uint8_t *out, int oH, int oW, int planes, int E, int nstrips) {
+// The four sums of one lane down the window of entry t of an item's vertical table (`out` entries): tap row k is the dword at byte `at` of
+// row r0 + k of the plane's intermediate (rows `pitch` bytes apart), its weight w[t][k].  All three vertical passes are this.
+struct Sums4 { int32_t s0, s1, s2, s3; };
+__device__ inline Sums4 vtap_sums(const AAManyItem &it, const char *ws, int out, int t, int plane, int64_t pitch, int64_t at) {
+  const int32_t *xmin_p = (const int32_t *)(ws + it.tab_h);
+  const int32_t *xsize_p = xmin_p + out;
+  const int ksize = it.ksize_h;
+  const int32_t *wp = xsize_p + out + (size_t)t * ksize;
+  int r0 = xmin_p[t], nr = xsize_p[t];
+  if (nr > ksize) nr = ksize;
+  if (r0 < 0) r0 = 0;
+  if (r0 + nr > it.hull_h) nr = it.hull_h - r0;
+  const uint8_t *ip = (const uint8_t *)ws + it.inter + ((int64_t)plane * it.hull_h + r0) * pitch + at;
+  Sums4 s = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+  for (int k = 0; k < nr; k++) {
+    const uint32_t v = *(const uint32_t *)(ip + k * pitch);
+    const int32_t wk = wp[k];
+    s.s0 += (int32_t)(v & 255u) * wk;
+    s.s1 += (int32_t)((v >> 8) & 255u) * wk;
+    s.s2 += (int32_t)((v >> 16) & 255u) * wk;
+    s.s3 += (int32_t)(v >> 24) * wk;
+  }
+  return s;
+}
+
+// PL, the four bytes [b, b + 4) of canvas row y, packed: a row the item does not cover, or four bytes beside its columns, are the fill and
+// read nothing; otherwise the four sums (the dword of the intermediate that holds the canvas dword: its rows are led so), each byte then
+// the sum or the fill, because a dword may straddle the item's edge.  What the dword holds beyond the covered columns lies inside the
+// item's own rows of the intermediate and is not used.
+__device__ inline uint32_t placed_bytes(const AAManyItem &it, const AAManyPlace &pl, const char *ws, uint32_t fill, int plane, int E, int y, int b) {
+  uint32_t fw = 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++) fw |= ((fill >> (8 * (E == 1 ? plane : (b + q) % E))) & 255u) << (8 * q);
+  const int ty = y - pl.dy;
+  const int cb0 = pl.dx * E, cb1 = cb0 + pl.mw * E;  // the covered bytes of a canvas row
+  if (ty < 0 || ty >= pl.mh || b + 4 <= cb0 || b >= cb1) return fw;
+  const Sums4 s = vtap_sums(it, ws, pl.mh, ty, plane, aa_many_placed_pitch(pl.dx, pl.mw, E), b - (cb0 & ~3));
+  const uint32_t sw = pack4_clip8(s.s0, s.s1, s.s2, s.s3);  // (`clip8(a) | clip8(b) << 8 ...` of one word is what hipcc miscompiles: aa_common.h)
+  uint32_t mask = 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++)
+    if (b + q >= cb0 && b + q < cb1) mask |= 255u << (8 * q);
+  return (sw & mask) | (fw & ~mask);
+}
+
+template <bool PL>
+__global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const AAManyPlace *places, const char *ws, uint8_t *out, int oH, int oW,
+                                                  int planes, int E, int nstrips, uint32_t fill) {
   int64_t u = blockIdx.x;
   const int strip = (int)(u % nstrips);
   u /= nstrips;
@@ -149,26 +223,14 @@ __global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const
   const int rowbytes = oW * E;
   const int b = (strip * 256 + (int)threadIdx.x) * 4;
   if (b >= rowbytes) return;
-  const int32_t *xmin_p = (const int32_t *)(ws + it.tab_h);
-  const int32_t *xsize_p = xmin_p + oH;
-  const int ksize = it.ksize_h;
-  const int32_t *wp = xsize_p + oH + (size_t)y * ksize;
-  int r0 = xmin_p[y], nr = xsize_p[y];
-  if (nr > ksize) nr = ksize;
-  if (r0 < 0) r0 = 0;
-  if (r0 + nr > it.hull_h) nr = it.hull_h - r0;
-  const int64_t pitch = aa_many_inter_pitch(oW, E);
-  const uint8_t *ip = (const uint8_t *)ws + it.inter + ((int64_t)plane * it.hull_h + r0) * pitch + b;
-  int32_t s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21, s3 = 1 << 21;
-  for (int k = 0; k < nr; k++) {
-    const uint32_t v = *(const uint32_t *)(ip + k * pitch);
-    const int32_t wk = wp[k];
-    s0 += (int32_t)(v & 255u) * wk;
-    s1 += (int32_t)((v >> 8) & 255u) * wk;
-    s2 += (int32_t)((v >> 16) & 255u) * wk;
-    s3 += (int32_t)(v >> 24) * wk;
+  uint32_t r0b, r1b, r2b, r3b;
+  if (PL) {
+    const uint32_t w = placed_bytes(it, places[u / planes], ws, fill, plane, E, y, b);
+    r0b = w & 255u; r1b = (w >> 8) & 255u; r2b = (w >> 16) & 255u; r3b = w >> 24;
+  } else {
+    const Sums4 s = vtap_sums(it, ws, oH, y, plane, aa_many_inter_pitch(oW, E), b);
+    r0b = clip8(s.s0); r1b = clip8(s.s1); r2b = clip8(s.s2); r3b = clip8(s.s3);  // (this form hipcc does not turn into the packed shift: aa_common.h)
   }
-  const uint32_t r0b = clip8(s0), r1b = clip8(s1), r2b = clip8(s2), r3b = clip8(s3);
   uint8_t *op = out + (((int64_t)(u / planes) * planes + plane) * oH + y) * rowbytes + b;
   const int nb = rowbytes - b < 4 ? rowbytes - b : 4;
   if (nb == 4 && ((uintptr_t)op & 3) == 0) {
@@ -208,9 +270,9 @@ __device__ inline float pick4(const float (&a)[4], int c) { return c == 0 ? a[0]
 template <int E> constexpr int kVLanes = E == 3 ? 192 : 256;   // lanes of a workgroup: 4 bytes each, a whole number of pixels together
 template <int E> constexpr int kVPixels = kVLanes<E> * 4 / E;  // 1024, 512, 256, 256
 
-template <typename T, int E, bool XL>
-__global__ void __launch_bounds__(kVLanes<E>) many_vpass_float(const AAManyItem *items, const char *ws, T *out, int oH, int oW, int planes,
-                                                               int nstrips, const ManyConvert cv) {
+template <typename T, int E, bool XL, bool PL>
+__global__ void __launch_bounds__(kVLanes<E>) many_vpass_float(const AAManyItem *items, const AAManyPlace *places, const char *ws, T *out, int oH,
+                                                               int oW, int planes, int nstrips, const ManyConvert cv, uint32_t fill) {
   constexpr int PX = kVPixels<E>;
   int64_t u = blockIdx.x;
   const int strip = (int)(u % nstrips);
@@ -229,27 +291,12 @@ __global__ void __launch_bounds__(kVLanes<E>) many_vpass_float(const AAManyItem 
   const int xr = flip ? oW - x0 - npx : x0;  // the output column the piece's run(s) start at
 
   float f[4];
-  {
-    const int32_t *xmin_p = (const int32_t *)(ws + it.tab_h);
-    const int32_t *xsize_p = xmin_p + oH;
-    const int ksize = it.ksize_h;
-    const int32_t *wp = xsize_p + oH + (size_t)y * ksize;
-    int r0 = xmin_p[y], nr = xsize_p[y];
-    if (nr > ksize) nr = ksize;
-    if (r0 < 0) r0 = 0;
-    if (r0 + nr > it.hull_h) nr = it.hull_h - r0;
-    const int64_t pitch = aa_many_inter_pitch(oW, E);
-    const uint8_t *ip = (const uint8_t *)ws + it.inter + ((int64_t)plane * it.hull_h + r0) * pitch + (int64_t)x0 * E + 4 * j;
-    int32_t s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21, s3 = 1 << 21;
-    for (int k = 0; k < nr; k++) {
-      const uint32_t v = *(const uint32_t *)(ip + k * pitch);
-      const int32_t wk = wp[k];
-      s0 += (int32_t)(v & 255u) * wk;
-      s1 += (int32_t)((v >> 8) & 255u) * wk;
-      s2 += (int32_t)((v >> 16) & 255u) * wk;
-      s3 += (int32_t)(v >> 24) * wk;
-    }
-    f[0] = (float)clip8(s0); f[1] = (float)clip8(s1); f[2] = (float)clip8(s2); f[3] = (float)clip8(s3);
+  if (PL) {  // (the piece starts on a dword of the canvas row: kVPixels<E> * E is a multiple of 4)
+    const uint32_t w = placed_bytes(it, places[n], ws, fill, plane, E, y, x0 * E + 4 * j);
+    f[0] = (float)(w & 255u); f[1] = (float)((w >> 8) & 255u); f[2] = (float)((w >> 16) & 255u); f[3] = (float)(w >> 24);
+  } else {
+    const Sums4 s = vtap_sums(it, ws, oH, y, plane, aa_many_inter_pitch(oW, E), (int64_t)x0 * E + 4 * j);
+    f[0] = (float)clip8(s.s0); f[1] = (float)clip8(s.s1); f[2] = (float)clip8(s.s2); f[3] = (float)clip8(s.s3);
   }
 
 #pragma unroll
@@ -275,24 +322,36 @@ size_t aa_many_desc_size(int64_t n) {
   return sizeof(AAManyHeader) + (size_t)n * sizeof(AAManyItem) + ((size_t)n + 1) * sizeof(int64_t);
 }
 
-// The hull [o, e) of an axis: the first output's window start and the last output's window end, each clipped to the axis
-// (boxmath.axis_hull; the same pil_window the table kernel evaluates).
-static void axis_hull(int filter, int64_t in_size, int64_t out_size, double in0, double in1, int on, int64_t *o, int64_t *e) {
+size_t aa_many_desc_size_placed(int64_t n) {
+  if (n < 0) return 0;
+  return aa_many_desc_size(n) + (size_t)n * sizeof(AAManyPlace);
+}
+
+// The hull [o, e) of the outputs [v0, v1) of an axis resized to out_size: the window start of v0 and the window end of v1 - 1, each
+// clipped to the axis (boxmath.axis_hull; the same window the table kernel evaluates).  The scale comes from the whole axis (or the box)
+// over the whole out_size, whatever part of the outputs is asked for.
+static void axis_hull(int filter, int64_t in_size, int64_t out_size, double in0, double in1, int on, int64_t v0, int64_t v1, int64_t *o, int64_t *e) {
   const BoxArgs bx = {in0, in1, 0, on};
-  const PilWindow first = pil_window(0, filter, (int)in_size, (int)out_size, bx);
-  const PilWindow last = pil_window((int)out_size - 1, filter, (int)in_size, (int)out_size, bx);
+  const PilWindow first = pil_window((int)v0, filter, (int)in_size, (int)out_size, bx);
+  const PilWindow last = pil_window((int)v1 - 1, filter, (int)in_size, (int)out_size, bx);
   *o = first.xmin;
   *e = (int64_t)last.xmin + last.xsize;
 }
 
-int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, void *desc_host,
-                      size_t desc_bytes, size_t *workspace_bytes) {
+int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                      const aa_many_place *places, const uint8_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
   if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   const int64_t kMax = INT32_MAX / 4;
   if (n < 0 || n > kMax || C < 1 || C > 4 || oH <= 0 || oW <= 0 || oH > kMax || oW > kMax) return AA_ERR_BAD_SHAPE;
   if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
-  if (desc_bytes < aa_many_desc_size(n)) return AA_ERR_WORKSPACE;
+  bool placed = false;  // every item the whole canvas at offset 0 is the plain plan: nothing of the canvas is left to the fill
+  for (int64_t i = 0; places && i < n; i++) {
+    const aa_many_place &p = places[i];
+    if (p.vH <= 0 || p.vW <= 0 || p.vH > kMax || p.vW > kMax || p.oy < -kMax || p.oy > kMax || p.ox < -kMax || p.ox > kMax) return AA_ERR_BAD_SHAPE;
+    placed = placed || p.vH != oH || p.vW != oW || p.oy != 0 || p.ox != 0;
+  }
+  if (desc_bytes < (placed ? aa_many_desc_size_placed(n) : aa_many_desc_size(n))) return AA_ERR_WORKSPACE;
   const int E = layout == AA_NHWC ? (int)C : 1;
   const int64_t planes = layout == AA_NHWC ? 1 : C;
   const int64_t pitch = aa_many_inter_pitch(oW, E);
@@ -303,6 +362,7 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
   AAManyHeader *hd = (AAManyHeader *)desc_host;
   AAManyItem *items = (AAManyItem *)(hd + 1);
   int64_t *prefix = (int64_t *)(items + n);
+  AAManyPlace *pls = (AAManyPlace *)(prefix + n + 1);  // (a placed plan only)
   size_t off = 0;  // the arena first, then the intermediates
   int64_t units = 0;
   int flips = 0;
@@ -323,14 +383,31 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
       if (!(x1 - x0 > 0.0) || !(y1 - y0 > 0.0)) return AA_ERR_BAD_SHAPE;                                           // empty
       on = !(x0 == 0.0 && y0 == 0.0 && x1 == (double)im.W && y1 == (double)im.H);  // a full box is no box
     }
-    int64_t oy, ey, ox, ex;
-    axis_hull(filter, im.H, oH, y0, y1, on, &oy, &ey);
-    axis_hull(filter, im.W, oW, x0, x1, on, &ox, &ex);
-    if (ey <= oy || ex <= ox) return AA_ERR_BAD_SHAPE;
-    const int kh = on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ey - oy, oH, y0, y1) : aa_table_ksize(filter, AA_TABLE_PIL, im.H, oH, 0, 0.0);
-    if (kh < 0) return kh;
-    const int kw = on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ex - ox, oW, x0, x1) : aa_table_ksize(filter, AA_TABLE_PIL, im.W, oW, 0, 0.0);
-    if (kw < 0) return kw;
+    // the item's own output size and the part [v0, v0 + m) of it that lies on the canvas, per axis (plain: all of the canvas)
+    int64_t vH = oH, vW = oW, v0h = 0, v0w = 0, mh = oH, mw = oW;
+    if (placed) {
+      const aa_many_place &p = places[i];
+      vH = p.vH; vW = p.vW;
+      v0h = p.oy < 0 ? -p.oy : 0;
+      v0w = p.ox < 0 ? -p.ox : 0;
+      mh = (vH < oH - p.oy ? vH : oH - p.oy) - v0h;
+      mw = (vW < oW - p.ox ? vW : oW - p.ox) - v0w;
+      if (mh <= 0 || mw <= 0) mh = mw = 0;  // off the canvas: all fill, no table, no work unit
+      AAManyPlace pl = {(int32_t)vH, (int32_t)vW, (int32_t)(mh ? v0h : 0), (int32_t)(mh ? v0w : 0), (int32_t)mh, (int32_t)mw,
+                        (int32_t)(mh ? v0h + p.oy : 0), (int32_t)(mh ? v0w + p.ox : 0)};
+      pls[i] = pl;
+    }
+    int64_t oy = 0, ey = 0, ox = 0, ex = 0;
+    int kh = 0, kw = 0;
+    if (mh > 0) {
+      axis_hull(filter, im.H, vH, y0, y1, on, v0h, v0h + mh, &oy, &ey);
+      axis_hull(filter, im.W, vW, x0, x1, on, v0w, v0w + mw, &ox, &ex);
+      if (ey <= oy || ex <= ox) return AA_ERR_BAD_SHAPE;
+      kh = on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ey - oy, vH, y0, y1) : aa_table_ksize(filter, AA_TABLE_PIL, im.H, vH, 0, 0.0);
+      if (kh < 0) return kh;
+      kw = on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ex - ox, vW, x0, x1) : aa_table_ksize(filter, AA_TABLE_PIL, im.W, vW, 0, 0.0);
+      if (kw < 0) return kw;
+    }
     it.src = (const uint8_t *)im.data_dev;
     it.row_stride = im.stride_row;
     it.plane_stride = layout == AA_NHWC ? 0 : (C > 1 ? im.stride_ch : 0);
@@ -341,18 +418,18 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
     it.reserved = im.flags & AA_MANY_FLIP_X;
     flips |= it.reserved;
     it.tab_h = (int64_t)off;
-    off += aa_many_table_bytes(oH, kh);
+    off += aa_many_table_bytes(mh, kh);
     it.tab_w = (int64_t)off;
-    off += aa_many_table_bytes(oW, kw);
+    off += aa_many_table_bytes(mw, kw);
     prefix[i] = units;
-    units += planes * (ey - oy) * nstrips;
+    units += planes * (ey - oy) * (placed ? (mw + AA_MANY_STRIP - 1) / AA_MANY_STRIP : nstrips);
     if (units > INT32_MAX) return AA_ERR_BAD_SHAPE;  // (one grid)
     items[i] = it;
   }
   prefix[n] = units;
   for (int64_t i = 0; i < n; i++) {
     items[i].inter = (int64_t)off;
-    off += aa_align16((size_t)(planes * items[i].hull_h * pitch));
+    off += aa_align16((size_t)(planes * items[i].hull_h * (placed ? aa_many_placed_pitch(pls[i].dx, pls[i].mw, E) : pitch)));
   }
   memset(hd, 0, sizeof(*hd));
   hd->magic = AA_MANY_MAGIC;
@@ -361,6 +438,10 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
   hd->reserved0 = flips;
   hd->hunits = units;
   hd->ws_bytes = (int64_t)off;
+  if (placed) {
+    hd->reserved[0] = 1;
+    for (int c = 0; fill && c < 4; c++) hd->reserved[1] |= (int64_t)fill[c] << (8 * c);
+  }
   *workspace_bytes = off;
   return AA_OK;
 }
@@ -376,17 +457,31 @@ static int many_check(const AAManyHeader *hd, const void *desc_dev, int64_t n, i
   return AA_OK;
 }
 
-static void launch_many_tables_hpass(const AAManyHeader *hd, const AAManyItem *items, const int64_t *prefix, char *ws, int64_t n, int64_t oH,
-                                     int64_t oW, int E, int planes, hipStream_t stream) {
+template <int E, bool PL>
+static void launch_hpass(const AAManyHeader *hd, const AAManyItem *items, const AAManyPlace *places, const int64_t *prefix, char *ws, int64_t n,
+                         int64_t oW, int planes, hipStream_t stream) {
+  if (hd->hunits == 0) return;  // (a placed plan whose items all lie off the canvas)
+  hipLaunchKernelGGL((many_hpass<E, PL>), dim3((unsigned)hd->hunits), dim3(AA_MANY_STRIP * E), 0, stream, items, places, prefix, ws, (int)n, (int)oW,
+                     planes);
+}
+
+template <bool PL>
+static void launch_many_tables_hpass(const AAManyHeader *hd, const AAManyItem *items, const AAManyPlace *places, const int64_t *prefix, char *ws,
+                                     int64_t n, int64_t oH, int64_t oW, int E, int planes, hipStream_t stream) {
   const int64_t tthreads = n * (oH + oW);
-  hipLaunchKernelGGL(many_tables, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, items, ws, n, (int)oH, (int)oW, hd->filter);
-  const dim3 hgrid((unsigned)hd->hunits);
+  hipLaunchKernelGGL(many_tables<PL>, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, items, places, ws, n, (int)oH, (int)oW,
+                     hd->filter);
   switch (E) {
-    case 1: hipLaunchKernelGGL(many_hpass<1>, hgrid, dim3(AA_MANY_STRIP * 1), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
-    case 2: hipLaunchKernelGGL(many_hpass<2>, hgrid, dim3(AA_MANY_STRIP * 2), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
-    case 3: hipLaunchKernelGGL(many_hpass<3>, hgrid, dim3(AA_MANY_STRIP * 3), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
-    default: hipLaunchKernelGGL(many_hpass<4>, hgrid, dim3(AA_MANY_STRIP * 4), 0, stream, items, prefix, ws, (int)n, (int)oW, planes); break;
+    case 1: launch_hpass<1, PL>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    case 2: launch_hpass<2, PL>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    case 3: launch_hpass<3, PL>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    default: launch_hpass<4, PL>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
   }
+}
+
+// The device copy's placement records (a placed plan: they follow the prefix sums) and the plan's fill.
+static const AAManyPlace *many_places(const AAManyHeader *hd, const int64_t *prefix_dev, int64_t n) {
+  return (hd->reserved[0] & 1) ? (const AAManyPlace *)(prefix_dev + n + 1) : nullptr;
 }
 
 int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
@@ -401,34 +496,58 @@ int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, in
   const int E = layout == AA_NHWC ? (int)C : 1;
   const int planes = layout == AA_NHWC ? 1 : (int)C;
   char *ws = (char *)workspace_dev;
-  launch_many_tables_hpass(hd, items, prefix, ws, n, oH, oW, E, planes, stream);
+  const AAManyPlace *places = many_places(hd, prefix, n);
   const int vstrips = (int)((oW * E + AA_MANY_VBYTES - 1) / AA_MANY_VBYTES);
-  hipLaunchKernelGGL(many_vpass, dim3((unsigned)(n * planes * oH * vstrips)), dim3(256), 0, stream, items, (const char *)ws, (uint8_t *)out_dev, (int)oH,
-                     (int)oW, planes, E, vstrips);
+  const dim3 vgrid((unsigned)(n * planes * oH * vstrips));
+  if (places) {
+    launch_many_tables_hpass<true>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
+    hipLaunchKernelGGL(many_vpass<true>, vgrid, dim3(256), 0, stream, items, places, (const char *)ws, (uint8_t *)out_dev, (int)oH, (int)oW, planes, E,
+                       vstrips, (uint32_t)hd->reserved[1]);
+  } else {
+    launch_many_tables_hpass<false>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
+    hipLaunchKernelGGL(many_vpass<false>, vgrid, dim3(256), 0, stream, items, places, (const char *)ws, (uint8_t *)out_dev, (int)oH, (int)oW, planes, E,
+                       vstrips, 0u);
+  }
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }
 
+// What the converting pass is launched with besides its template arguments.
+struct ManyFloatArgs {
+  const AAManyItem *items;
+  const AAManyPlace *places;  // null: a plain plan
+  const char *ws;
+  void *out;
+  int64_t n, oH, oW;
+  int planes;
+  ManyConvert cv;
+  uint32_t fill;
+  hipStream_t stream;
+};
+
 template <typename T, int E, bool XL>
-static void launch_vpass_float(const AAManyItem *items, const char *ws, void *out, int64_t n, int64_t oH, int64_t oW, int planes,
-                               const ManyConvert &cv, hipStream_t stream) {
-  const int nstrips = (int)((oW + kVPixels<E> - 1) / kVPixels<E>);
-  hipLaunchKernelGGL((many_vpass_float<T, E, XL>), dim3((unsigned)(n * planes * oH * nstrips)), dim3(kVLanes<E>), 0, stream, items, ws,
-                     (T *)out, (int)oH, (int)oW, planes, nstrips, cv);
+static void launch_vpass_float(const ManyFloatArgs &a) {
+  const int nstrips = (int)((a.oW + kVPixels<E> - 1) / kVPixels<E>);
+  const dim3 grid((unsigned)(a.n * a.planes * a.oH * nstrips));
+  if (a.places)
+    hipLaunchKernelGGL((many_vpass_float<T, E, XL, true>), grid, dim3(kVLanes<E>), 0, a.stream, a.items, a.places, a.ws, (T *)a.out, (int)a.oH, (int)a.oW,
+                       a.planes, nstrips, a.cv, a.fill);
+  else
+    hipLaunchKernelGGL((many_vpass_float<T, E, XL, false>), grid, dim3(kVLanes<E>), 0, a.stream, a.items, a.places, a.ws, (T *)a.out, (int)a.oH,
+                       (int)a.oW, a.planes, nstrips, a.cv, 0u);
 }
 
 template <typename T>
-static void launch_vpass_float_e(int E, bool xl, const AAManyItem *items, const char *ws, void *out, int64_t n, int64_t oH, int64_t oW, int planes,
-                                 const ManyConvert &cv, hipStream_t stream) {
+static void launch_vpass_float_e(int E, bool xl, const ManyFloatArgs &a) {
   switch (E * 2 + (xl ? 1 : 0)) {
-    case 2: launch_vpass_float<T, 1, false>(items, ws, out, n, oH, oW, planes, cv, stream); break;
-    case 3: launch_vpass_float<T, 1, true>(items, ws, out, n, oH, oW, planes, cv, stream); break;
-    case 4: launch_vpass_float<T, 2, false>(items, ws, out, n, oH, oW, planes, cv, stream); break;
-    case 5: launch_vpass_float<T, 2, true>(items, ws, out, n, oH, oW, planes, cv, stream); break;
-    case 6: launch_vpass_float<T, 3, false>(items, ws, out, n, oH, oW, planes, cv, stream); break;
-    case 7: launch_vpass_float<T, 3, true>(items, ws, out, n, oH, oW, planes, cv, stream); break;
-    case 8: launch_vpass_float<T, 4, false>(items, ws, out, n, oH, oW, planes, cv, stream); break;
-    default: launch_vpass_float<T, 4, true>(items, ws, out, n, oH, oW, planes, cv, stream); break;
+    case 2: launch_vpass_float<T, 1, false>(a); break;
+    case 3: launch_vpass_float<T, 1, true>(a); break;
+    case 4: launch_vpass_float<T, 2, false>(a); break;
+    case 5: launch_vpass_float<T, 2, true>(a); break;
+    case 6: launch_vpass_float<T, 3, false>(a); break;
+    case 7: launch_vpass_float<T, 3, true>(a); break;
+    case 8: launch_vpass_float<T, 4, false>(a); break;
+    default: launch_vpass_float<T, 4, true>(a); break;
   }
 }
 
@@ -451,10 +570,13 @@ int aa_launch_many_float(const void *desc_host, const void *desc_dev, int64_t n,
   ManyConvert cv;
   cv.normalize = normalize ? 1 : 0;
   for (int i = 0; i < 4; i++) { cv.mean[i] = normalize && i < C ? mean[i] : 0.f; cv.std[i] = normalize && i < C ? std[i] : 1.f; }
-  launch_many_tables_hpass(hd, items, prefix, ws, n, oH, oW, E, planes, stream);
-  if (out_elem == AA_F16) launch_vpass_float_e<f16_t>(E, xl, items, ws, out_dev, n, oH, oW, planes, cv, stream);
-  else if (out_elem == AA_BF16) launch_vpass_float_e<bf16_t>(E, xl, items, ws, out_dev, n, oH, oW, planes, cv, stream);
-  else launch_vpass_float_e<float>(E, xl, items, ws, out_dev, n, oH, oW, planes, cv, stream);
+  const AAManyPlace *places = many_places(hd, prefix, n);
+  if (places) launch_many_tables_hpass<true>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
+  else launch_many_tables_hpass<false>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
+  const ManyFloatArgs a = {items, places, ws, out_dev, n, oH, oW, planes, cv, (uint32_t)hd->reserved[1], stream};
+  if (out_elem == AA_F16) launch_vpass_float_e<f16_t>(E, xl, a);
+  else if (out_elem == AA_BF16) launch_vpass_float_e<bf16_t>(E, xl, a);
+  else launch_vpass_float_e<float>(E, xl, a);
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }

@@ -79,20 +79,25 @@ struct BoxArgs { double in0, in1; int origin, on; };
 // The window of output i: [xmin, xmin + xsize) in UNSHIFTED axis coordinates, clipped to [origin, origin + in_size), and the centre and
 // the inverse filter scale its weights are evaluated with.
 struct PilWindow { int xmin, xsize; double center, ss; };
-__host__ __device__ inline PilWindow pil_window(int i, int filter, int in_size, int out_size, const BoxArgs &bx) {
-  double scale = bx.on ? (double)(float)(bx.in1 - bx.in0) / (double)out_size : (double)in_size / (double)out_size;
+// The two inputs of a window apart: the scale (from the whole axis or the box over the whole output size, never from a hull) and the
+// interval [lo, hi) the window clips to.  pil_window below is this with both derived from in_size, as they were before they parted.
+__host__ __device__ inline PilWindow pil_window_at(int i, int filter, double scale, double in0, int lo, int hi) {
   double filterscale = scale < 1.0 ? 1.0 : scale;
   const double fsupport = aa_filter_info(filter).support;
   const double support = fsupport * filterscale;
-  const double center = bx.in0 + ((double)i + 0.5) * scale;
+  const double center = in0 + ((double)i + 0.5) * scale;
   const double ss = 1.0 / filterscale;
-  // windows clip to the hull [origin, origin + in_size): the hull is exactly the extreme windows clipped to the image, so this is Pillow's clip
+  // windows clip to the hull [lo, hi): the hull is exactly the extreme windows clipped to the image, so this is Pillow's clip
   int xmin = (int)(center - support + 0.5);
-  if (xmin < bx.origin) xmin = bx.origin;
+  if (xmin < lo) xmin = lo;
   int xmax = (int)(center + support + 0.5);
-  if (xmax > bx.origin + in_size) xmax = bx.origin + in_size;
+  if (xmax > hi) xmax = hi;
   xmax -= xmin;
   return PilWindow{xmin, xmax, center, ss};
+}
+__host__ __device__ inline PilWindow pil_window(int i, int filter, int in_size, int out_size, const BoxArgs &bx) {
+  double scale = bx.on ? (double)(float)(bx.in1 - bx.in0) / (double)out_size : (double)in_size / (double)out_size;
+  return pil_window_at(i, filter, scale, bx.in0, bx.origin, bx.origin + in_size);
 }
 // The ksize int32 weights of that output (zero padded from xsize to ksize), computed from the unshifted xmin and centre.
 __device__ inline void pil_weights(const PilWindow &wd, int filter, int ksize, int32_t *kk) {

@@ -42,7 +42,8 @@ Differences, all additive:
     and the float conversion, normalisation, layout change and horizontal flips a model needs after it, in the same three launches.
   * ``resize_many(images, output_size, mode, boxes=None)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
-    whatever N, no table cache traffic, no synchronisation;
+    whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
+    output size and a place on the [oH, oW] canvas (Resize + CenterCrop, letterbox): cropped or padded, only the covered part computed;
   * the same callables are registered as ``torch.ops.extension_interpolate.*``.
 """
 from __future__ import annotations
@@ -410,7 +411,7 @@ def _many_class(t: torch.Tensor):
 
 
 def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, boxes=None, channels: Optional[int] = None,
-                alpha: bool = False, reducing_gap: Optional[float] = None, uint8_mode: Optional[str] = None, out_dtype=None,
+                sizes=None, offsets=None, fill=0, alpha: bool = False, reducing_gap: Optional[float] = None, uint8_mode: Optional[str] = None, out_dtype=None,
                 out_format: Optional[str] = None, mean=None, std=None, align_corners: bool = False,
                 scale_factors: Optional[Sequence[float]] = None) -> torch.Tensor:
     """Resize a list of uint8 images of different sizes into one batch: ``y[i]`` is ``<mode>_forward(images[i][None], output_size,
@@ -424,6 +425,18 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
     ``boxes``: None, or N entries, each None or (x0, y0, x1, y1) — PILLOW'S ORDER, X FIRST, unlike ``output_size`` = (H, W).
     ``mode``: bilinear | bicubic | nearest (the box filter) | lanczos | hamming.  Pillow's arithmetic only.
     N == 0 gives an empty [0, C, oh, ow] tensor; a list then says its C with ``channels=``.
+
+    Placement (all keyword-only, all defaulting to the above): item i is resized to ITS OWN size and pasted onto the [oh, ow] canvas,
+
+        R_i = PIL.Image.resize((vw_i, vh_i), FILTER, box=boxes[i]);  y[i, c, y, x] = R_i[y - py_i, x - px_i, c] where that exists, else fill[c]
+
+    bit for bit.  Only the part of R_i that lies on the canvas is computed; an item wholly off the canvas is legal and all fill.
+    ``sizes``: None, or N entries, each None (``output_size``) or (vh, vw), height first like ``output_size``.
+    ``offsets``: None, "center", or N entries, each None (= (0, 0)) or integers (py, px); negative crops, positive pads.  "center", per
+    axis: ``-int(round((v - o) / 2.0))`` for v >= o (torchvision's center_crop), ``(o - v) // 2`` for v < o.
+    ``fill``: one int or C ints in 0..255 (default 0); without ``sizes`` / ``offsets`` it has no effect.
+    ``Resize(256)`` + ``CenterCrop(224)`` is ``sizes=boxmath.fit_sizes(shapes, shorter=256), offsets="center"`` on a 224 x 224 canvas; a
+    letterbox is ``sizes=boxmath.fit_sizes(shapes, longer=640), offsets="center", fill=114`` on a 640 x 640 one.
 
     Three launches and one non-blocking copy of a packed descriptor whatever N; every hull, ksize and offset is host arithmetic
     (aa_many_plan), so nothing is read back, and the table caches are neither read nor written.  Not built here: alpha, reducing_gap,
@@ -439,11 +452,11 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
         if (uint8_mode or _uint8_mode) != "harness":
             raise ValueError("uint8_mode must be 'pil' or 'harness'")
         raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
-    return _resize_many(name, images, output_size, mode, boxes, channels, None)
+    return _resize_many(name, images, output_size, mode, boxes, channels, None, (sizes, offsets, fill))
 
 
 def resize_many_to_float(images, output_size: Sequence[int], mode: str = "bilinear", *, boxes=None, flips=None,
-                         channels: Optional[int] = None, out_dtype=torch.float32, out_format: Optional[str] = None, mean=None,
+                         channels: Optional[int] = None, sizes=None, offsets=None, fill=0, out_dtype=torch.float32, out_format: Optional[str] = None, mean=None,
                          std=None) -> torch.Tensor:
     """``resize_many`` and the conversion a model needs after it, in the same three launches: with ``u = resize_many(images, output_size,
     mode, boxes=boxes)`` (Pillow's bytes), the result is, bit for bit,
@@ -453,7 +466,9 @@ def resize_many_to_float(images, output_size: Sequence[int], mode: str = "biline
     written in ``out_format``: ``PIL.Image.resize(..., box=)``, ``transpose(FLIP_LEFT_RIGHT)``, a ToTensor-style conversion and Normalize
     folded into 0..255 units, without the uint8 batch, a float32 intermediate or a second pass.
 
-    ``images``, ``output_size``, ``mode``, ``boxes``, ``channels``: exactly ``resize_many``'s.
+    ``images``, ``output_size``, ``mode``, ``boxes``, ``channels``, ``sizes``, ``offsets``, ``fill``: exactly ``resize_many``'s; ``u`` above is
+    then the placed ``resize_many(..., sizes=, offsets=, fill=)``: the fill byte is converted like any other byte, and a flip mirrors the
+    whole canvas row.
     ``out_dtype``: torch.float32 | torch.float16 | torch.bfloat16 (rounded to nearest even once, at the store).
     ``out_format``: "nchw" | "nhwc" | None (the class of the items, as ``resize_many``'s output).
     ``mean`` / ``std``: None, or C floats each in 0..255 units (the convention of the single-image forwards), given together.
@@ -471,7 +486,67 @@ def resize_many_to_float(images, output_size: Sequence[int], mode: str = "biline
     if _uint8_mode != "pil":
         raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
     return _resize_many(name, images, output_size, mode, boxes, channels,
-                        {"out_dtype": out_dtype, "out_format": out_format, "mean": mean, "std": std, "flips": flips})
+                        {"out_dtype": out_dtype, "out_format": out_format, "mean": mean, "std": std, "flips": flips}, (sizes, offsets, fill))
+
+
+_MANY_MAX = (2 ** 31 - 1) // 4  # the library's bound on a size or an offset of the ragged call
+
+
+def _many_int_pair(name: str, arg: str, i: int, v):
+    """One (a, b) entry of sizes / offsets as two ints; anything that is not two integers raises, naming the argument and the item."""
+    try:
+        a, b = v
+        if isinstance(a, bool) or isinstance(b, bool) or int(a) != a or int(b) != b:
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}(): {arg}[{i}] must be two integers, got {v!r}") from None
+    return int(a), int(b)
+
+
+def _many_places(name: str, place, n: int, c: int, oh: int, ow: int):
+    """sizes / offsets / fill, checked -> (None or [(vh, vw, py, px)] per item, the C fill bytes)."""
+    sizes, offsets, fill = place
+    try:
+        fills = [fill] if not isinstance(fill, (tuple, list)) else list(fill)
+        if any(isinstance(v, bool) or int(v) != v for v in fills):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}(): fill must be one int or {c} ints in 0..255, got {fill!r}") from None
+    if len(fills) == 1 and not isinstance(fill, (tuple, list)):
+        fills = fills * c
+    if len(fills) != c:
+        raise ValueError(f"{name}(): fill must be one int or one per channel ({c}), got {len(fills)}")
+    for k, v in enumerate(fills):
+        if not (0 <= v <= 255):
+            raise ValueError(f"{name}(): fill[{k}] = {v} is outside 0..255")
+    fills = [int(v) for v in fills]
+    if sizes is None and offsets is None:
+        return None, fills
+    if sizes is not None and len(sizes) != n:
+        raise ValueError(f"{name}(): sizes must hold one entry per image ({n}), got {len(sizes)}")
+    center = isinstance(offsets, str)
+    if center and offsets != "center":
+        raise ValueError(f"{name}(): offsets must be None, 'center' or one entry per image, got {offsets!r}")
+    if offsets is not None and not center and len(offsets) != n:
+        raise ValueError(f"{name}(): offsets must hold one entry per image ({n}), got {len(offsets)}")
+    places = []
+    for i in range(n):
+        vh, vw = oh, ow
+        if sizes is not None and sizes[i] is not None:
+            vh, vw = _many_int_pair(name, "sizes", i, sizes[i])
+            if vh <= 0 or vw <= 0:
+                raise ValueError(f"{name}(): sizes[{i}] = ({vh}, {vw}) must be positive")
+            if vh > _MANY_MAX or vw > _MANY_MAX:
+                raise ValueError(f"{name}(): sizes[{i}] = ({vh}, {vw}) is beyond the supported {_MANY_MAX}")
+        py, px = 0, 0
+        if center:
+            py, px = boxmath.center_offset(vh, oh), boxmath.center_offset(vw, ow)
+        elif offsets is not None and offsets[i] is not None:
+            py, px = _many_int_pair(name, "offsets", i, offsets[i])
+            if abs(py) > _MANY_MAX or abs(px) > _MANY_MAX:
+                raise ValueError(f"{name}(): offsets[{i}] = ({py}, {px}) is beyond the supported {_MANY_MAX}")
+        places.append((vh, vw, py, px))
+    return places, fills
 
 
 def _many_convert(name: str, conv: dict, n: int, c: int):
@@ -500,8 +575,10 @@ def _many_convert(name: str, conv: dict, n: int, c: int):
     return cv, flips, out_dtype
 
 
-def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes, channels: Optional[int], conv: Optional[dict]) -> torch.Tensor:
-    """resize_many (conv None) and resize_many_to_float (conv: its options): the checks, the layout class, the plan and the launches."""
+def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes, channels: Optional[int], conv: Optional[dict],
+                 place=(None, None, 0)) -> torch.Tensor:
+    """resize_many (conv None) and resize_many_to_float (conv: its options): the checks, the layout class, the plan and the launches.
+    place: (sizes, offsets, fill)."""
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
     filter_id = _lib.FILTER_IDS[mode]
@@ -553,6 +630,7 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
     cv, flips, out_dtype = None, None, torch.uint8
     if conv is not None:
         cv, flips, out_dtype = _many_convert(name, conv, n, c)
+    places, fills = _many_places(name, place, n, c, oh, ow)
     if n == 0:
         if dev0 is None:
             dev0 = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -592,10 +670,20 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
                 r.box[0], r.box[1], r.box[2], r.box[3] = bx
             if flips is not None and flips[i]:
                 r.flags = _lib.MANY_FLIP_X
-        desc_bytes = L.aa_many_desc_bytes(n)
+        # (places that are all the whole canvas at offset 0 plan to the plain block: the tail of the larger one is then copied as it is
+        # and never read)
+        desc_bytes = L.aa_many_desc_bytes(n) if places is None else L.aa_many_desc_bytes_placed(n)
         desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
         ws_bytes = ctypes.c_size_t(0)
-        _lib.check(L.aa_many_plan(filter_id, layout, n, c, oh, ow, recs, desc_host.data_ptr(), desc_bytes, ctypes.byref(ws_bytes)), name)
+        if places is None:
+            rc = L.aa_many_plan(filter_id, layout, n, c, oh, ow, recs, desc_host.data_ptr(), desc_bytes, ctypes.byref(ws_bytes))
+        else:
+            precs = (_lib.ManyPlace * n)()
+            for i, p in enumerate(places):
+                precs[i].vH, precs[i].vW, precs[i].oy, precs[i].ox = p
+            rc = L.aa_many_plan_placed(filter_id, layout, n, c, oh, ow, recs, precs, (ctypes.c_uint8 * 4)(*fills), desc_host.data_ptr(),
+                                       desc_bytes, ctypes.byref(ws_bytes))
+        _lib.check(rc, name)
         desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
         desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
         ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
@@ -1006,7 +1094,9 @@ def _register_torch_ops() -> None:
     lib.impl("reduce", _reduce_meta, "Meta")
 
     # a list of images into one batch; boxes flattened to 4 N values, a full-image box standing for None
-    lib.define('resize_many(Tensor[] images, int[] output_size, str mode="bilinear", float[]? boxes=None) -> Tensor')
+    # sizes and offsets flattened to 2 N ints (height first), fill to 1 or C ints
+    lib.define('resize_many(Tensor[] images, int[] output_size, str mode="bilinear", float[]? boxes=None, int[]? sizes=None, '
+               'int[]? offsets=None, int[]? fill=None) -> Tensor')
 
     def _many_boxes(images, boxes):
         if boxes is None:
@@ -1015,7 +1105,17 @@ def _register_torch_ops() -> None:
             raise ValueError(f"resize_many(): boxes must hold 4 values per image ({4 * len(images)}), got {len(boxes)}")
         return [tuple(boxes[4 * i:4 * i + 4]) for i in range(len(images))]
 
-    def _many_meta(images, output_size, mode="bilinear", boxes=None):
+    def _many_pairs(images, flat, what):
+        if flat is None:
+            return None
+        if len(flat) != 2 * len(images):
+            raise ValueError(f"resize_many(): {what} must hold 2 values per image ({2 * len(images)}), got {len(flat)}")
+        return [tuple(flat[2 * i:2 * i + 2]) for i in range(len(images))]
+
+    def _many_fill(fill):
+        return 0 if fill is None else (fill[0] if len(fill) == 1 else list(fill))
+
+    def _many_meta(images, output_size, mode="bilinear", boxes=None, sizes=None, offsets=None, fill=None):
         if not images:
             raise ValueError("resize_many(): the op needs at least one image (an empty list has no C)")
         items = [t[0] if t.dim() == 4 else t for t in images]
@@ -1026,23 +1126,27 @@ def _register_torch_ops() -> None:
         mf = torch.channels_last if (c > 1 and n_inter > 0 and n_inter >= n_planar) else torch.contiguous_format
         return torch.empty((len(items), c, output_size[0], output_size[1]), dtype=items[0].dtype, device=items[0].device, memory_format=mf)
 
-    lib.impl("resize_many", lambda images, output_size, mode="bilinear", boxes=None: resize_many(
-        list(images), output_size, mode, boxes=_many_boxes(images, boxes)), "CUDA")
+    lib.impl("resize_many", lambda images, output_size, mode="bilinear", boxes=None, sizes=None, offsets=None, fill=None: resize_many(
+        list(images), output_size, mode, boxes=_many_boxes(images, boxes), sizes=_many_pairs(images, sizes, "sizes"),
+        offsets=_many_pairs(images, offsets, "offsets"), fill=_many_fill(fill)), "CUDA")
     lib.impl("resize_many", _many_meta, "Meta")
     lib.define('resize_many_to_float(Tensor[] images, int[] output_size, str mode="bilinear", float[]? boxes=None, bool[]? flips=None, '
-               'ScalarType? out_dtype=None, str? out_format=None, float[]? mean=None, float[]? std=None) -> Tensor')
+               'ScalarType? out_dtype=None, str? out_format=None, float[]? mean=None, float[]? std=None, int[]? sizes=None, '
+               'int[]? offsets=None, int[]? fill=None) -> Tensor')
 
-    def _many_float_meta(images, output_size, mode="bilinear", boxes=None, flips=None, out_dtype=None, out_format=None, mean=None, std=None):
+    def _many_float_meta(images, output_size, mode="bilinear", boxes=None, flips=None, out_dtype=None, out_format=None, mean=None, std=None,
+                         sizes=None, offsets=None, fill=None):
         u = _many_meta(images, output_size, mode, boxes)
         out_dtype = torch.float32 if out_dtype is None else out_dtype
         nhwc = u.is_contiguous(memory_format=torch.channels_last) and not u.is_contiguous() if out_format is None else out_format == "nhwc"
         return torch.empty(u.shape, dtype=out_dtype, device="meta", memory_format=torch.channels_last if nhwc else torch.contiguous_format)
 
     lib.impl("resize_many_to_float", lambda images, output_size, mode="bilinear", boxes=None, flips=None, out_dtype=None,
-             out_format=None, mean=None, std=None: resize_many_to_float(
+             out_format=None, mean=None, std=None, sizes=None, offsets=None, fill=None: resize_many_to_float(
                  list(images), output_size, mode, boxes=_many_boxes(images, boxes), flips=flips,
                  out_dtype=torch.float32 if out_dtype is None else out_dtype, out_format=out_format,
-                 mean=mean, std=std), "CUDA")
+                 mean=mean, std=std, sizes=_many_pairs(images, sizes, "sizes"), offsets=_many_pairs(images, offsets, "offsets"),
+                 fill=_many_fill(fill)), "CUDA")
     lib.impl("resize_many_to_float", _many_float_meta, "Meta")
 
     for name, fn in bwds.items():

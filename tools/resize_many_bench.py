@@ -14,12 +14,24 @@ and float32) — two ways:
 
 (e) must beat (d) by more than the two spreads together; both give the same bits.
 
+--placed, on the same N images, two recipes a loader has besides RandomResizedCrop, each against the loop a user writes without the
+placed call: <mode>_forward(img[None], [vh, vw]) per image (tables warm in the cache: the sizes do not change), a slice copy into a
+preallocated batch, and for eval the torch conversion of the batch:
+
+  eval       Resize(256) + CenterCrop(224): fit_sizes(shorter=256), canvas 224 x 224, "center", bicubic, bfloat16 NCHW with mean / std;
+  letterbox  fit_sizes(longer=640), canvas 640 x 640, "center", bilinear, fill 114, uint8.
+
+Both ways give the same bits; kernel launches per batch are counted with torch's profiler where it works.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
 
   python tools/resize_many_bench.py                      # the timing table
   python tools/resize_many_bench.py --float-only         # only the (d) / (e) table
+  python tools/resize_many_bench.py --placed > out.txt   # only the placed call against the per-image loop (below);
+                                                         # profiles/resize_many_placed.txt is this output, after the default table of
+                                                         # the parent commit (twice) and of this one from the same session
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -101,6 +113,90 @@ def summarise(trace_dir, calls):
     return {k: statistics.median(v[WARM_CALLS:] if len(v) > WARM_CALLS else v) for k, v in ours.items()}
 
 
+def count_launches(torch, fn):
+    """Kernel launches of one fn() from torch's profiler; None where torch has no profiler or it records no device activity.  An error
+    of fn() itself, or of a profiler that is there, is an error."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+    except ImportError:
+        return None
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    kernels = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and "memcpy" not in e.name.lower()
+               and "memset" not in e.name.lower()]
+    return len(kernels) or None
+
+
+def placed(args, torch, aa, images, shapes, timed):
+    """The placed call against the per-image loop: eval (Resize + CenterCrop, to normalised bfloat16) and letterbox (uint8)."""
+    from interpolate_antialiasing_amd import boxmath
+
+    mean, std = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
+    mean_t, std_t = (torch.tensor(v, device="cuda").view(1, 3, 1, 1) for v in (mean, std))
+    fwd = {"bilinear": aa.linear_forward, "bicubic": aa.cubic_forward}
+
+    def paste_loop(mode, vs, canvas, batch):
+        oh, ow = canvas
+        for i, (img, (vh, vw)) in enumerate(zip(images, vs)):
+            r = fwd[mode](img[None], [vh, vw])[0]
+            py, px = boxmath.center_offset(vh, oh), boxmath.center_offset(vw, ow)
+            y0, y1, x0, x1 = max(0, py), min(oh, py + vh), max(0, px), min(ow, px + vw)
+            batch[i, :, y0:y1, x0:x1] = r[:, y0 - py:y1 - py, x0 - px:x1 - px]
+        return batch
+
+    eval_sizes, eval_canvas = boxmath.fit_sizes(shapes, shorter=256), (224, 224)
+    eval_batch = torch.empty((N, 3) + eval_canvas, dtype=torch.uint8, device="cuda", memory_format=torch.channels_last)
+    lb_sizes, lb_canvas = boxmath.fit_sizes(shapes, longer=640), (640, 640)
+    lb_batch = torch.empty((N, 3) + lb_canvas, dtype=torch.uint8, device="cuda", memory_format=torch.channels_last)
+
+    def eval_loop():
+        u = paste_loop("bicubic", eval_sizes, eval_canvas, eval_batch)
+        return ((u.float() - mean_t) / std_t).to(torch.bfloat16).contiguous()
+
+    def eval_call():
+        return aa.resize_many_to_float(images, list(eval_canvas), "bicubic", sizes=eval_sizes, offsets="center", out_dtype=torch.bfloat16,
+                                       out_format="nchw", mean=mean, std=std)
+
+    def lb_loop():
+        lb_batch.fill_(114)
+        return paste_loop("bilinear", lb_sizes, lb_canvas, lb_batch)
+
+    def lb_call():
+        return aa.resize_many(images, list(lb_canvas), "bilinear", sizes=lb_sizes, offsets="center", fill=114)
+
+    print(f"resize_many_bench --placed: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}); library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+    for title, loop_fn, call_fn, sz, canvas in (("eval: fit_sizes(shorter=256) -> 224 x 224 center, bicubic, bfloat16 nchw, mean / std", eval_loop, eval_call,
+                                                 eval_sizes, eval_canvas),
+                                                ("letterbox: fit_sizes(longer=640) -> 640 x 640 center, bilinear, fill 114, uint8", lb_loop, lb_call,
+                                                 lb_sizes, lb_canvas)):
+        contestants = {"loop: per-image forward + slice copy": loop_fn, "call: one placed call": call_fn}
+        for fn in contestants.values():  # warm-up of every contestant (the loop's tables are cached from here on)
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        a, b = loop_fn(), call_fn()
+        assert a.dtype == b.dtype and torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16 else a,
+                                                  b.view(torch.int16) if b.dtype == torch.bfloat16 else b), "the placed call differs from the loop"
+        times = {k: [] for k in contestants}
+        for _ in range(args.rounds):
+            for k, fn in contestants.items():
+                times[k].append(timed(fn))
+        resampled = sum(vh * vw for vh, vw in sz) / (N * canvas[0] * canvas[1])
+        print(f"\n{title}")
+        print(f"  pixels the loop resamples per pixel of the batch: {resampled:.2f}")
+        stat = {}
+        for k, v in times.items():
+            stat[k] = (statistics.median(v), min(v), max(v))
+            launches = count_launches(torch, contestants[k])
+            print(f"  {k:40s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]   kernel launches per batch: "
+                  f"{launches if launches is not None else 'not measured'}")
+        (ml, ll, hl), (mc, lc, hc) = stat.values()
+        print(f"  call against loop: {ml / mc:.2f} x; median gain {ml - mc:.3f} ms, the two spreads together {(hl - ll) + (hc - lc):.3f} ms")
+
+
 def _lib_path():
     from interpolate_antialiasing_amd import _lib
 
@@ -115,6 +211,7 @@ def main():
     ap.add_argument("--trace-mode", default="bilinear")
     ap.add_argument("--summarise", default=None)
     ap.add_argument("--float-only", action="store_true")
+    ap.add_argument("--placed", action="store_true", help="only the placed call (eval and letterbox) against the per-image loop")
     ap.add_argument("--trace-float", action="store_true", help="with --trace: the calls are resize_many_to_float (bfloat16, nchw, mean / std, flips)")
     args = ap.parse_args()
 
@@ -178,6 +275,10 @@ def main():
         end.record()
         torch.cuda.synchronize()
         return start.elapsed_time(end) / args.batches
+
+    if args.placed:
+        placed(args, torch, aa, images, shapes, timed)
+        return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
     print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
