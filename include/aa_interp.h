@@ -385,6 +385,33 @@ int aa_resample_many_u8(const void *desc_host, const void *desc_dev, int64_t n, 
 int aa_resample_many_u8_to_float(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout,
                                  void *out_dev, void *workspace_dev, size_t workspace_bytes, const aa_convert *cv, aa_stream_t stream);
 
+/* PATCH plans: the ragged batch as the token matrix a native-resolution vision transformer reads (NaViT, NaFlex, VLM towers), in the same
+ * three launches.  Item i is resized to ITS OWN size [vH_i, vW_i] = sizes[2 i], sizes[2 i + 1], a multiple of the patch [ph, pw] per
+ * axis; there is no canvas, no offset and no fill.  With gh = vH / ph, gw = vW / pw, T_i = gh * gw tokens and D = C * ph * pw, and with
+ *   R_i = what aa_resample_many_u8_to_float writes for the one item on a [vH_i, vW_i] output in AA_NCHW, flipped if the item flips,
+ * token t = gy * gw + gx of item i is, bit for bit,
+ *   AA_PATCH_CPP:  tok[c * ph * pw + py * pw + px] = R_i[c][gy * ph + py][gx * pw + px]     (a Conv2d(C, dim, patch, stride = patch) weight's order)
+ *   AA_PATCH_PPC:  tok[(py * pw + px) * C + c]     = R_i[c][gy * ph + py][gx * pw + px]     (einops "(p1 p2 c)")
+ * and the output is [rows, D] elements, dense: pad_to = 0 packs the items, item i's tokens at rows T_0 + .. + T_(i-1) on, rows = the sum;
+ * pad_to = L > 0 gives every item L rows, [n, L, D], rows = n * L, item i's tokens at row i * L on and its rows beyond T_i all-zero bits
+ * (+0.0: pad rows are not normalised).
+ * aa_many_plan_patches is host arithmetic only, like aa_many_plan (same records, same errors); desc_bytes >= aa_many_desc_bytes_patches(n),
+ * and that many bytes are copied to the device.  AA_ERR_BAD_SHAPE also for a patch below 1, a size that is not a positive multiple of the
+ * patch, T_i > pad_to, pad_to < 0, and more work units than one grid holds (2^31 - 1).  It reports the workspace and the output's rows.
+ * aa_resample_many_u8_to_patches enqueues the table kernel, the horizontal pass and a vertical pass that converts as
+ * aa_resample_many_u8_to_float does and stores every element at its place in its token.  n, C, the layout class and the sizes are the
+ * plan's.  cv: normalize / mean / std and the AA_FLAG_OUT_* bits as there (both bits AA_ERR_BAD_DTYPE, AA_FLAG_FAST or an unknown bit
+ * AA_ERR_BAD_SHAPE); cv->out_layout is not looked at.  patch_format: AA_PATCH_CPP or AA_PATCH_PPC, AA_ERR_BAD_LAYOUT otherwise.  out_dev
+ * aligned to its element; desc_dev, workspace_dev as aa_resample_many_u8; a block that is not a patch plan's AA_ERR_BAD_SHAPE.  Every check
+ * comes before any launch; nothing is allocated, synchronised or read back.  Added without an ABI version change (additive). */
+#define AA_PATCH_CPP 0
+#define AA_PATCH_PPC 1
+size_t aa_many_desc_bytes_patches(int64_t n);
+int aa_many_plan_patches(int filter, int layout, int64_t n, int64_t C, int64_t ph, int64_t pw, const aa_many_image *images,
+                         const int64_t *sizes, int64_t pad_to, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, int64_t *rows);
+int aa_resample_many_u8_to_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
+                                   const aa_convert *cv, int patch_format, aa_stream_t stream);
+
 /* Device-to-device copy of `bytes` bytes with 16-byte vector loads/stores, enqueued on `stream`: the probe bench.py times
  * on the box to report the attainable HBM copy ceiling next to the 8 TB/s spec peak.  form 0: one element per
  * thread; 1: grid-stride; 2: four elements per thread, loads in flight before the stores; 3: form 2, streaming (nt) policy;

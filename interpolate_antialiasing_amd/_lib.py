@@ -51,7 +51,7 @@ EXPORTS = (
     "aa_last_variant", "aa_probe_copy", "aa_workspace_bytes_u8_to_f32", "aa_resample_fwd_u8_to_f32", "aa_set_store_form", "aa_set_plane_groups", "aa_resample_fwd_ex", "aa_resample_fwd_strided",
     "aa_workspace_bytes_ex", "aa_table_ksize_box", "aa_table_build_bytes_box", "aa_table_build_box", "aa_reduce_u8", "aa_premultiply_u8",
     "aa_unpremultiply_u8", "aa_many_desc_bytes", "aa_many_plan", "aa_resample_many_u8", "aa_resample_many_u8_to_float",
-    "aa_many_desc_bytes_placed", "aa_many_plan_placed",
+    "aa_many_desc_bytes_placed", "aa_many_plan_placed", "aa_many_desc_bytes_patches", "aa_many_plan_patches", "aa_resample_many_u8_to_patches",
 )
 
 
@@ -114,6 +114,7 @@ class ManyPlaced(ctypes.Structure):
 
 
 MANY_FLIP_X = 1     # aa_many_image.flags: mirror the item's output left to right (aa_resample_many_u8_to_float only)
+PATCH_CPP, PATCH_PPC = 0, 1  # aa_resample_many_u8_to_patches: token vector [C, ph, pw] or [ph, pw, C]
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
 
@@ -128,6 +129,12 @@ def many_desc_view(buf, n: int):
 def many_placed_view(buf, n: int):
     """The placement records of a placed plan's block (ManyHeader.reserved[0] == 1): they follow the prefix sums."""
     return (ManyPlaced * n).from_buffer(buf, ctypes.sizeof(ManyHeader) + n * ctypes.sizeof(ManyItem) + 8 * (n + 1))
+
+
+def many_patch_view(buf, n: int):
+    """(vunit_prefix[n + 1], tok0[n + 1]) of a patch plan's block: they follow the placement records."""
+    off = ctypes.sizeof(ManyHeader) + n * ctypes.sizeof(ManyItem) + 8 * (n + 1) + n * ctypes.sizeof(ManyPlaced)
+    return (ctypes.c_int64 * (n + 1)).from_buffer(buf, off), (ctypes.c_int64 * (n + 1)).from_buffer(buf, off + 8 * (n + 1))
 
 
 class AAInterpError(RuntimeError):
@@ -224,6 +231,13 @@ def load() -> ctypes.CDLL:
     L.aa_resample_many_u8.restype = i32
     L.aa_resample_many_u8_to_float.argtypes = [vp, vp, i64, i64, i64, i64, i32, vp, vp, sz, cvp, vp]
     L.aa_resample_many_u8_to_float.restype = i32
+    L.aa_many_desc_bytes_patches.argtypes = [i64]
+    L.aa_many_desc_bytes_patches.restype = sz
+    L.aa_many_plan_patches.argtypes = [i32, i32, i64, i64, i64, i64, ctypes.POINTER(ManyImage), ctypes.POINTER(i64), i64, vp, sz,
+                                       ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_many_plan_patches.restype = i32
+    L.aa_resample_many_u8_to_patches.argtypes = [vp, vp, vp, vp, sz, cvp, i32, vp]
+    L.aa_resample_many_u8_to_patches.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

@@ -159,6 +159,67 @@ def fit_sizes(shapes, shorter: Optional[int] = None, longer: Optional[int] = Non
     return out
 
 
+def check_patch(patch) -> Tuple[int, int]:
+    try:
+        ph, pw = patch
+        if isinstance(ph, bool) or isinstance(pw, bool) or int(ph) != ph or int(pw) != pw:
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"patch must be two integers (ph, pw), got {patch!r}") from None
+    if ph < 1 or pw < 1:
+        raise ValueError(f"patch = ({ph}, {pw}) must be positive")
+    return int(ph), int(pw)
+
+
+def patch_grids(sizes, patch):
+    """[(vh_i, vw_i)] -> [(gh_i, gw_i)]: how many (ph, pw) patches each size holds per axis.  A size that is not a positive multiple of the
+    patch on both axes raises ValueError naming the item."""
+    ph, pw = check_patch(patch)
+    out = []
+    for i, (vh, vw) in enumerate(sizes):
+        if vh <= 0 or vw <= 0:
+            raise ValueError(f"sizes[{i}] = ({vh}, {vw}) must be positive")
+        if vh % ph != 0 or vw % pw != 0:
+            raise ValueError(f"sizes[{i}] = ({vh}, {vw}) is not a multiple of the patch ({ph}, {pw})")
+        out.append((int(vh) // ph, int(vw) // pw))
+    return out
+
+
+def token_offsets(sizes, patch):
+    """N + 1 prefix sums of the token counts gh_i * gw_i: item i's tokens are rows [offsets[i], offsets[i + 1]) of the packed matrix.  The
+    cu_seqlens of a variable-length attention (the caller puts them on the device)."""
+    out = [0]
+    for gh, gw in patch_grids(sizes, patch):
+        out.append(out[-1] + gh * gw)
+    return out
+
+
+def fit_patch_sizes(shapes, patch, min_tokens: int = 1, max_tokens: Optional[int] = None):
+    """[(H_i, W_i)] -> [(vh_i, vw_i)], multiples of the patch (ph, pw) with the aspect ratio kept as well as they allow: the usual rule of
+    native-resolution vision towers.  Per axis the nearest multiple (Python's round, at least one patch); if that gives more than
+    max_tokens patches, both axes are divided by beta = sqrt(h * w / (max_tokens * ph * pw)) and rounded DOWN to a multiple (at least one
+    patch); else if it gives fewer than min_tokens, both are multiplied by beta = sqrt(min_tokens * ph * pw / (h * w)) and rounded UP."""
+    ph, pw = check_patch(patch)
+    min_tokens = int(min_tokens)
+    if min_tokens < 1 or (max_tokens is not None and int(max_tokens) < min_tokens):
+        raise ValueError("fit_patch_sizes: 1 <= min_tokens <= max_tokens")
+    out = []
+    for h, w in shapes:
+        h, w = int(h), int(w)
+        if h <= 0 or w <= 0:
+            raise ValueError("fit_patch_sizes: shapes must be positive")
+        vh, vw = max(ph, round(h / ph) * ph), max(pw, round(w / pw) * pw)
+        tokens = (vh // ph) * (vw // pw)
+        if max_tokens is not None and tokens > max_tokens:
+            beta = math.sqrt(h * w / (int(max_tokens) * ph * pw))
+            vh, vw = max(ph, math.floor(h / beta / ph) * ph), max(pw, math.floor(w / beta / pw) * pw)
+        elif tokens < min_tokens:
+            beta = math.sqrt(min_tokens * ph * pw / (h * w))
+            vh, vw = math.ceil(h * beta / ph) * ph, math.ceil(w * beta / pw) * pw
+        out.append((vh, vw))
+    return out
+
+
 def center_offset(v: int, o: int) -> int:
     """Where the corner of an axis of v pixels lands on a canvas axis of o so that it is centred: a crop (v >= o) with the arithmetic of
     torchvision's center_crop (Python's round, half to even), a pad (v < o) with the smaller half first."""

@@ -487,6 +487,25 @@ int aa_resample_many_u8_to_float(const void *desc_host, const void *desc_dev, in
                               cv->normalize, cv->mean, cv->std, (hipStream_t)stream);
 }
 
+size_t aa_many_desc_bytes_patches(int64_t n) { return aa_many_desc_size_patches(n); }
+
+int aa_many_plan_patches(int filter, int layout, int64_t n, int64_t C, int64_t ph, int64_t pw, const aa_many_image *images, const int64_t *sizes,
+                         int64_t pad_to, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, int64_t *rows) {
+  if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
+  return aa_many_plan_patches_host(filter, layout, n, C, ph, pw, images, sizes, pad_to, desc_host, desc_bytes, workspace_bytes, rows);
+}
+
+int aa_resample_many_u8_to_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
+                                   const aa_convert *cv, int patch_format, aa_stream_t stream) {
+  if (!desc_host || !cv) return AA_ERR_NULL;
+  if (patch_format != AA_PATCH_CPP && patch_format != AA_PATCH_PPC) return AA_ERR_BAD_LAYOUT;
+  if ((cv->flags & AA_FLAG_OUT_F16) && (cv->flags & AA_FLAG_OUT_BF16)) return AA_ERR_BAD_DTYPE;
+  if (cv->flags & ~(AA_FLAG_OUT_F16 | AA_FLAG_OUT_BF16)) return AA_ERR_BAD_SHAPE;  // (AA_FLAG_FAST: the conversion has one arithmetic)
+  const int out_elem = (cv->flags & AA_FLAG_OUT_F16) ? AA_F16 : ((cv->flags & AA_FLAG_OUT_BF16) ? AA_BF16 : AA_F32);
+  return aa_launch_many_patches(desc_host, desc_dev, out_dev, workspace_dev, workspace_bytes, out_elem, patch_format == AA_PATCH_PPC, cv->normalize,
+                                cv->mean, cv->std, (hipStream_t)stream);
+}
+
 // ---- Image.reduce ------------------------------------------------------------------------------------------------------------------------
 int aa_reduce_u8(const void *in_dev, void *out_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, const int64_t *in_strides,
                  const int64_t *box, int fx, int fy, aa_stream_t stream) {

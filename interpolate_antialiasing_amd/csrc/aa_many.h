@@ -2,6 +2,7 @@
 // batch.  The packed descriptor block aa_many_plan writes on the host and the three kernels read on the device:
 //   [ AAManyHeader : 64 B ][ AAManyItem x n ][ int64 hunit_prefix[n + 1] ]            a plain plan (aa_many_desc_size)
 //   [ AAManyHeader : 64 B ][ AAManyItem x n ][ int64 hunit_prefix[n + 1] ][ AAManyPlace x n ]   a placed plan (aa_many_desc_size_placed)
+//   [ ... a placed plan ... ][ int64 vunit_prefix[n + 1] ][ int64 tok0[n + 1] ][ AAManyPatchInfo ]   a patch plan (aa_many_desc_size_patches)
 // Everything a kernel needs about an item is in its record(s): no table header, nothing read back.
 #pragma once
 
@@ -15,7 +16,8 @@ struct AAManyHeader {
   int32_t magic, n, C, oH, oW, filter, layout, reserved0;  // reserved0: 1 when some item flips (only the converting pass serves it)
   int64_t hunits;     // work units of the horizontal pass, all items: hunit_prefix[n]
   int64_t ws_bytes;   // table arena + intermediates
-  int64_t reserved[2]; // [0]: 1 for a placed plan (AAManyPlace records follow the prefix sums); [1]: its fill, byte c = channel c's
+  int64_t reserved[2]; // [0]: bit 0 a placed plan (AAManyPlace records follow the prefix sums), bit 1 a patch plan (its tail follows
+                       // them); [1]: a placed plan's fill, byte c = channel c's
 };
 static_assert(sizeof(AAManyHeader) == 64, "descriptor header is 64 bytes");
 
@@ -45,11 +47,25 @@ static_assert(sizeof(AAManyPlace) == 32, "placement record is 32 bytes");
 __host__ __device__ inline int aa_many_placed_lead(int dx, int E) { return (int)(((int64_t)dx * E) & 3); }
 __host__ __device__ inline int64_t aa_many_placed_pitch(int dx, int mw, int E) { return (aa_many_placed_lead(dx, E) + (int64_t)mw * E + 3) & ~(int64_t)3; }
 
+// A patch plan (resize_many_to_patches): a placed plan in which every item is the whole of its own [vh, vw] canvas (place {vh, vw, 0, 0};
+// the header's oH, oW are the largest vh and vw, which only size the grid of the table kernel), followed by the work units of the
+// patch-writing vertical pass and where each item's token rows start.  Item i has planes * vh_i * ceil(vw_i / kVPixels<E>) image units, then
+// ceil((pad_to - T_i) * D / AA_MANY_PAD_ELEMS) pad units (pad_to > 0 only); its first token is row tok0[i] of the output, tok0[n] the
+// output's rows.
+#define AA_MANY_PAD_ELEMS 4096  // zero elements per pad unit
+struct AAManyPatchInfo {
+  int32_t ph, pw;
+  int64_t pad_to;  // 0: packed rows
+};
+static_assert(sizeof(AAManyPatchInfo) == 16, "patch tail is 16 bytes");
+__host__ __device__ constexpr int aa_many_vpixels(int E) { return E == 1 ? 1024 : (E == 2 ? 512 : 256); }  // kVPixels<E> of aa_many.hip
+
 inline size_t aa_many_table_bytes(int64_t out, int ksize) { return aa_align16(4 * (size_t)out * (2 + (size_t)ksize)); }
 __host__ __device__ inline int64_t aa_many_inter_pitch(int64_t oW, int E) { return (oW * E + 3) & ~(int64_t)3; }  // rows of the intermediate start on a dword
 
 size_t aa_many_desc_size(int64_t n);
 size_t aa_many_desc_size_placed(int64_t n);
+size_t aa_many_desc_size_patches(int64_t n);
 // places NULL, or every place the whole canvas at offset 0: the plain plan, whatever the fill.
 int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
                       const aa_many_place *places, const uint8_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes);
@@ -59,3 +75,9 @@ int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, in
 int aa_launch_many_float(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
                          void *workspace_dev, size_t workspace_bytes, int out_elem, int out_layout, int normalize, const float *mean,
                          const float *std, hipStream_t stream);
+// The patch plan and its launches: sizes[2 i], sizes[2 i + 1] = (vH_i, vW_i), multiples of (ph, pw); pad_to 0 = packed rows.  The plan
+// reports the output's rows; the launch takes everything else from the plan's header.  ppc: token vectors [ph, pw, C] instead of [C, ph, pw].
+int aa_many_plan_patches_host(int filter, int layout, int64_t n, int64_t C, int64_t ph, int64_t pw, const aa_many_image *images, const int64_t *sizes,
+                              int64_t pad_to, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, int64_t *rows);
+int aa_launch_many_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int out_elem,
+                           int ppc, int normalize, const float *mean, const float *std, hipStream_t stream);

@@ -5,7 +5,9 @@
 //                   the items' work, not N x the largest item;
 //   3. many_vpass   one workgroup per (item, plane, output row, 1 KiB of the row);
 //      or many_vpass_float, the converting form: the same sums, then byte -> float -> (v - mean) / std -> f32 / f16 / bf16, written in the
-//      requested layout, mirrored left to right for the items that flip.
+//      requested layout, mirrored left to right for the items that flip;
+//      or many_vpass_patches, the same conversion with ragged work units: every item its own size, its pixels scattered into the rows
+//      of a packed (or zero-padded) matrix of ViT patch tokens.
 // A PLACED plan (template parameter PL) gives every item its own output size and a place on the canvas: the tables hold the covered
 // part of the item's own resize only, the horizontal pass computes the covered columns only, and the vertical pass, still one grid over
 // the whole canvas, writes the fill wherever the item is not.  The plain instantiations take none of it.
@@ -314,6 +316,76 @@ __global__ void __launch_bounds__(kVLanes<E>) many_vpass_float(const AAManyItem 
   }
 }
 
+// ---- 3c. patch-writing vertical pass -------------------------------------------------------------------------------------------------------
+// A patch plan (aa_many.h): item i is the whole of its own [vh, vw] canvas, cut into gh x gw patches of ph x pw pixels; token t = gy * gw +
+// gx of the item is row tok0[i] + t of the [rows, D] output, D = C * ph * pw.  The grid is ragged like the horizontal pass's: one
+// workgroup per unit, its item found by binary search in vunit_prefix.  An IMAGE unit is many_vpass_float's (plane, row y, strip of
+// kVPixels<E> pixels) within the item's own size: the same bytes from placed_bytes, the same conversion, the same mirrored column for an
+// item that flips; only the address of the store differs.  Pixel (channel ch, y, x) goes to row tok0 + (y / ph) * gw + x / pw, column
+//   (ch * ph + y % ph) * pw + x % pw        token vector [C, ph, pw]  (PPC false)
+//   ((y % ph) * pw + x % pw) * C + ch       token vector [ph, pw, C]  (PPC true)
+// so a store instruction of a wave writes runs of pw elements (planes, [C, ph, pw]), pw * C elements (interleaved pixels, [ph, pw, C]) or
+// single elements C or ph * pw apart (the two crossed combinations), each run in another token row.  A PAD unit (pad_to > 0) zeroes
+// AA_MANY_PAD_ELEMS elements of the item's rows [T_i, pad_to), which are contiguous: consecutive lanes, consecutive elements.
+template <typename T, int E, bool PPC>
+__global__ void __launch_bounds__(kVLanes<E>) many_vpass_patches(const AAManyItem *items, const AAManyPlace *places, const int64_t *vprefix,
+                                                                 const int64_t *tok0, const char *ws, T *out, int n, int planes, int ph, int pw,
+                                                                 int64_t pad_to, const ManyConvert cv) {
+  constexpr int PX = kVPixels<E>;
+  static_assert(PX * E == kVLanes<E> * 4 && PX == aa_many_vpixels(E), "a strip is four bytes per lane, and the planner counts the same strips");
+  const int64_t unit = blockIdx.x;
+  int lo = 0, hi = n;  // the item whose units hold `unit`: vprefix[lo] <= unit < vprefix[lo + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (vprefix[mid] <= unit) lo = mid; else hi = mid;
+  }
+  const AAManyItem &it = items[lo];
+  const AAManyPlace &pl = places[lo];
+  int64_t u = unit - vprefix[lo];
+  const int vh = pl.vh, vw = pl.vw, gw = vw / pw;
+  const int C = planes * E;  // (one of the two is 1)
+  const int64_t D = (int64_t)C * ph * pw;
+  const int nstrips = (vw + PX - 1) / PX;
+  const int64_t image_units = (int64_t)planes * vh * nstrips;
+  const int j = threadIdx.x;
+  if (u >= image_units) {  // (uniform per workgroup)
+    const int64_t tokens = (int64_t)(vh / ph) * gw;
+    const int64_t e0 = (u - image_units) * AA_MANY_PAD_ELEMS;
+    const int64_t left = (pad_to - tokens) * D - e0;
+    const int cnt = left < AA_MANY_PAD_ELEMS ? (int)left : AA_MANY_PAD_ELEMS;
+    T *p = out + (tok0[lo] + tokens) * D + e0;
+    const T zero = T();
+    for (int k = j; k < cnt; k += kVLanes<E>) p[k] = zero;
+    return;
+  }
+  const int strip = (int)(u % nstrips);
+  u /= nstrips;
+  const int y = (int)(u % vh);
+  const int plane = (int)(u / vh);
+  const int x0 = strip * PX;
+  const int npx = vw - x0 < PX ? vw - x0 : PX;
+  const int nb = npx * E - 4 * j;  // bytes of the piece from this lane's first (4 or more: all four results exist; <= 0: none)
+  if (nb <= 0) return;
+  const bool flip = (it.reserved & 1) != 0;
+
+  const uint32_t w = placed_bytes(it, pl, ws, 0u, plane, E, y, x0 * E + 4 * j);  // (the item covers its canvas: never the fill)
+  const float f[4] = {(float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), (float)(w >> 24)};
+
+  const int gy = y / ph, py = y - gy * ph;
+  const int64_t row0 = tok0[lo] + (int64_t)gy * gw;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (i >= nb) break;
+    const int q = 4 * j + i, px = q / E, c = q % E;
+    float v = f[i];
+    if (cv.normalize) v = (v - pick4(cv.mean, plane + c)) / pick4(cv.std, plane + c);  // (one of plane and c is 0)
+    const int x = flip ? vw - 1 - (x0 + px) : x0 + px;
+    const int gx = x / pw, qx = x - gx * pw;
+    const int64_t col = PPC ? (int64_t)(py * pw + qx) * C + (plane + c) : ((int64_t)(plane + c) * ph + py) * pw + qx;
+    out[(row0 + gx) * D + col] = to_elem<T>(v);
+  }
+}
+
 }  // namespace
 
 // ---- host: the planner -------------------------------------------------------------------------------------------------------------------
@@ -327,6 +399,11 @@ size_t aa_many_desc_size_placed(int64_t n) {
   return aa_many_desc_size(n) + (size_t)n * sizeof(AAManyPlace);
 }
 
+size_t aa_many_desc_size_patches(int64_t n) {
+  if (n < 0) return 0;
+  return aa_many_desc_size_placed(n) + 2 * ((size_t)n + 1) * sizeof(int64_t) + sizeof(AAManyPatchInfo);
+}
+
 // The hull [o, e) of the outputs [v0, v1) of an axis resized to out_size: the window start of v0 and the window end of v1 - 1, each
 // clipped to the axis (boxmath.axis_hull; the same window the table kernel evaluates).  The scale comes from the whole axis (or the box)
 // over the whole out_size, whatever part of the outputs is asked for.
@@ -338,14 +415,16 @@ static void axis_hull(int filter, int64_t in_size, int64_t out_size, double in0,
   *e = (int64_t)last.xmin + last.xsize;
 }
 
-int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
-                      const aa_many_place *places, const uint8_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
+// own_canvas: a patch plan.  Every place is the whole of its item's own canvas, [oH, oW] is only the largest of them: the plan is a
+// placed one whatever the places (the patch pass reads the records), and there is no dense vertical grid to bound.
+static int many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images, const aa_many_place *places,
+                     const uint8_t *fill, bool own_canvas, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
   if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   const int64_t kMax = INT32_MAX / 4;
   if (n < 0 || n > kMax || C < 1 || C > 4 || oH <= 0 || oW <= 0 || oH > kMax || oW > kMax) return AA_ERR_BAD_SHAPE;
   if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
-  bool placed = false;  // every item the whole canvas at offset 0 is the plain plan: nothing of the canvas is left to the fill
+  bool placed = own_canvas;  // every item the whole canvas at offset 0 is the plain plan: nothing of the canvas is left to the fill
   for (int64_t i = 0; places && i < n; i++) {
     const aa_many_place &p = places[i];
     if (p.vH <= 0 || p.vW <= 0 || p.vH > kMax || p.vW > kMax || p.oy < -kMax || p.oy > kMax || p.ox < -kMax || p.ox > kMax) return AA_ERR_BAD_SHAPE;
@@ -357,7 +436,7 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
   const int64_t pitch = aa_many_inter_pitch(oW, E);
   const int64_t nstrips = (oW + AA_MANY_STRIP - 1) / AA_MANY_STRIP;
   const int64_t vstrips = (oW * E + AA_MANY_VBYTES - 1) / AA_MANY_VBYTES;
-  if (n * planes * oH * vstrips > INT32_MAX || n * (oH + oW) > (int64_t)INT32_MAX * 256) return AA_ERR_BAD_SHAPE;  // (grids of the launches)
+  if ((!own_canvas && n * planes * oH * vstrips > INT32_MAX) || n * (oH + oW) > (int64_t)INT32_MAX * 256) return AA_ERR_BAD_SHAPE;  // (grids of the launches)
 
   AAManyHeader *hd = (AAManyHeader *)desc_host;
   AAManyItem *items = (AAManyItem *)(hd + 1);
@@ -443,6 +522,59 @@ int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, 
     for (int c = 0; fill && c < 4; c++) hd->reserved[1] |= (int64_t)fill[c] << (8 * c);
   }
   *workspace_bytes = off;
+  return AA_OK;
+}
+
+int aa_many_plan_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                      const aa_many_place *places, const uint8_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
+  return many_plan(filter, layout, n, C, oH, oW, images, places, fill, false, desc_host, desc_bytes, workspace_bytes);
+}
+
+// The tail of a patch plan's block: vunit_prefix[n + 1], tok0[n + 1], AAManyPatchInfo.
+static int64_t *patch_tail(const void *desc, int64_t n) { return (int64_t *)((char *)desc + aa_many_desc_size_placed(n)); }
+
+int aa_many_plan_patches_host(int filter, int layout, int64_t n, int64_t C, int64_t ph, int64_t pw, const aa_many_image *images, const int64_t *sizes,
+                              int64_t pad_to, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, int64_t *rows) {
+  const int64_t kMax = INT32_MAX / 4;
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (n < 0 || n > kMax || C < 1 || C > 4 || ph < 1 || pw < 1 || ph > kMax || pw > kMax || pad_to < 0 || pad_to > INT32_MAX) return AA_ERR_BAD_SHAPE;
+  if (!desc_host || !workspace_bytes || !rows || (n > 0 && (!images || !sizes))) return AA_ERR_NULL;
+  if (desc_bytes < aa_many_desc_size_patches(n)) return AA_ERR_WORKSPACE;
+  const int E = layout == AA_NHWC ? (int)C : 1;
+  const int64_t planes = layout == AA_NHWC ? 1 : C;
+  const int64_t D = C * ph * pw;
+  if (D > INT32_MAX) return AA_ERR_BAD_SHAPE;
+  int64_t *vprefix = patch_tail(desc_host, n), *tok0 = vprefix + n + 1;
+  // (the tail first: the placed plan below does not touch these bytes)
+  aa_many_place *places = n ? new aa_many_place[(size_t)n] : nullptr;
+  int64_t oH = 1, oW = 1, units = 0, row = 0;
+  int rc = AA_OK;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t vH = sizes[2 * i], vW = sizes[2 * i + 1];
+    if (vH <= 0 || vW <= 0 || vH > kMax || vW > kMax || vH % ph || vW % pw) { rc = AA_ERR_BAD_SHAPE; break; }
+    const int64_t tokens = (vH / ph) * (vW / pw);
+    if (pad_to && tokens > pad_to) { rc = AA_ERR_BAD_SHAPE; break; }
+    const aa_many_place p = {vH, vW, 0, 0};
+    places[i] = p;
+    oH = vH > oH ? vH : oH;
+    oW = vW > oW ? vW : oW;
+    vprefix[i] = units;
+    tok0[i] = pad_to ? i * pad_to : row;
+    row += tokens;
+    units += planes * vH * ((vW + aa_many_vpixels(E) - 1) / aa_many_vpixels(E));
+    if (pad_to) units += ((pad_to - tokens) * D + AA_MANY_PAD_ELEMS - 1) / AA_MANY_PAD_ELEMS;
+    if (units > INT32_MAX) { rc = AA_ERR_BAD_SHAPE; break; }  // (one grid)
+  }
+  vprefix[n] = units;
+  tok0[n] = pad_to ? n * pad_to : row;
+  if (rc == AA_OK) rc = many_plan(filter, layout, n, C, oH, oW, images, places, nullptr, true, desc_host, desc_bytes, workspace_bytes);
+  delete[] places;
+  if (rc != AA_OK) return rc;
+  AAManyHeader *hd = (AAManyHeader *)desc_host;
+  hd->reserved[0] |= 2;
+  AAManyPatchInfo *info = (AAManyPatchInfo *)(tok0 + n + 1);
+  info->ph = (int32_t)ph; info->pw = (int32_t)pw; info->pad_to = pad_to;
+  *rows = tok0[n];
   return AA_OK;
 }
 
@@ -577,6 +709,73 @@ int aa_launch_many_float(const void *desc_host, const void *desc_dev, int64_t n,
   if (out_elem == AA_F16) launch_vpass_float_e<f16_t>(E, xl, a);
   else if (out_elem == AA_BF16) launch_vpass_float_e<bf16_t>(E, xl, a);
   else launch_vpass_float_e<float>(E, xl, a);
+  AA_HIP_CHECK_LAUNCH();
+  return AA_OK;
+}
+
+// ---- host: the patch plan's three launches ---------------------------------------------------------------------------------------------------
+struct ManyPatchArgs {
+  const AAManyItem *items;
+  const AAManyPlace *places;
+  const int64_t *vprefix, *tok0;
+  const char *ws;
+  void *out;
+  int n, planes, ph, pw;
+  int64_t pad_to, vunits;
+  ManyConvert cv;
+  hipStream_t stream;
+};
+
+template <typename T, int E, bool PPC>
+static void launch_vpass_patches(const ManyPatchArgs &a) {
+  hipLaunchKernelGGL((many_vpass_patches<T, E, PPC>), dim3((unsigned)a.vunits), dim3(kVLanes<E>), 0, a.stream, a.items, a.places, a.vprefix, a.tok0,
+                     a.ws, (T *)a.out, a.n, a.planes, a.ph, a.pw, a.pad_to, a.cv);
+}
+
+template <typename T>
+static void launch_vpass_patches_e(int E, bool ppc, const ManyPatchArgs &a) {
+  switch (E * 2 + (ppc ? 1 : 0)) {
+    case 2: launch_vpass_patches<T, 1, false>(a); break;
+    case 3: launch_vpass_patches<T, 1, true>(a); break;
+    case 4: launch_vpass_patches<T, 2, false>(a); break;
+    case 5: launch_vpass_patches<T, 2, true>(a); break;
+    case 6: launch_vpass_patches<T, 3, false>(a); break;
+    case 7: launch_vpass_patches<T, 3, true>(a); break;
+    case 8: launch_vpass_patches<T, 4, false>(a); break;
+    default: launch_vpass_patches<T, 4, true>(a); break;
+  }
+}
+
+int aa_launch_many_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int out_elem,
+                           int ppc, int normalize, const float *mean, const float *std, hipStream_t stream) {
+  const AAManyHeader *hd = (const AAManyHeader *)desc_host;
+  if (hd->magic != AA_MANY_MAGIC || (hd->reserved[0] & 3) != 3 || hd->n < 0 || hd->C < 1 || hd->C > 4) return AA_ERR_BAD_SHAPE;  // not a patch plan
+  const int64_t n = hd->n, C = hd->C;
+  const int layout = hd->layout;
+  if (n == 0) return AA_OK;
+  if (!desc_dev || !out_dev || !workspace_dev) return AA_ERR_NULL;
+  const int rc = many_check(hd, desc_dev, n, C, hd->oH, hd->oW, layout, workspace_dev, workspace_bytes);
+  if (rc != AA_OK) return rc;
+  if ((uintptr_t)out_dev & (out_elem == AA_F32 ? 3 : 1)) return AA_ERR_BAD_SHAPE;
+  const int64_t *tail_host = patch_tail(desc_host, n);
+  const AAManyPatchInfo *info = (const AAManyPatchInfo *)(tail_host + 2 * (n + 1));
+  const int64_t vunits = tail_host[n];
+  if (vunits <= 0 || vunits > INT32_MAX) return AA_ERR_BAD_SHAPE;
+  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
+  const int64_t *prefix = (const int64_t *)(items + n);
+  const AAManyPlace *places = (const AAManyPlace *)(prefix + n + 1);
+  const int64_t *tail_dev = patch_tail(desc_dev, n);
+  const int E = layout == AA_NHWC ? (int)C : 1;
+  const int planes = layout == AA_NHWC ? 1 : (int)C;
+  char *ws = (char *)workspace_dev;
+  ManyConvert cv;
+  cv.normalize = normalize ? 1 : 0;
+  for (int i = 0; i < 4; i++) { cv.mean[i] = normalize && i < C ? mean[i] : 0.f; cv.std[i] = normalize && i < C ? std[i] : 1.f; }
+  launch_many_tables_hpass<true>(hd, items, places, prefix, ws, n, hd->oH, hd->oW, E, planes, stream);
+  const ManyPatchArgs a = {items, places, tail_dev, tail_dev + n + 1, ws, out_dev, (int)n, planes, info->ph, info->pw, info->pad_to, vunits, cv, stream};
+  if (out_elem == AA_F16) launch_vpass_patches_e<f16_t>(E, ppc != 0, a);
+  else if (out_elem == AA_BF16) launch_vpass_patches_e<bf16_t>(E, ppc != 0, a);
+  else launch_vpass_patches_e<float>(E, ppc != 0, a);
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }

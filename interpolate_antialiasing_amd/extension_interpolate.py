@@ -40,6 +40,9 @@ Differences, all additive:
   * ``reduce(input, factor, box=None, alpha=False)``: Pillow's ``Image.reduce`` (integer box means), bit-exact;
   * ``resize_many_to_float(images, output_size, mode, boxes=None, flips=None, out_dtype=, out_format=, mean=, std=)``: ``resize_many``
     and the float conversion, normalisation, layout change and horizontal flips a model needs after it, in the same three launches.
+  * ``resize_many_to_patches(images, patch, mode, sizes=, patch_format=, pad_to=, ...)``: the same list, every item resized to its own
+    multiple of the patch, converted and cut into ViT patch tokens: one packed [sum T_i, C * ph * pw] matrix (or a zero-padded
+    [N, L, C * ph * pw] one) from the same three launches;
   * ``resize_many(images, output_size, mode, boxes=None)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -56,7 +59,7 @@ import torch
 
 from . import _lib, boxmath, tables
 
-__all__ = ["reduce", "resize_many", "resize_many_to_float", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+__all__ = ["reduce", "resize_many", "resize_many_to_float", "resize_many_to_patches", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -441,7 +444,7 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
     Three launches and one non-blocking copy of a packed descriptor whatever N; every hull, ksize and offset is host arithmetic
     (aa_many_plan), so nothing is read back, and the table caches are neither read nor written.  Not built here: alpha, reducing_gap,
     uint8_mode="harness", float images or outputs, align_corners, scale factors (each raises NotImplementedError); float, normalised,
-    flipped output in either layout is ``resize_many_to_float``."""
+    flipped output in either layout is ``resize_many_to_float``, packed ViT patch tokens are ``resize_many_to_patches``."""
     name = "resize_many"
     for opt, given in (("alpha", bool(alpha)), ("reducing_gap", reducing_gap is not None), ("out_dtype", out_dtype is not None),
                        ("out_format", out_format is not None), ("mean", mean is not None), ("std", std is not None),
@@ -575,16 +578,9 @@ def _many_convert(name: str, conv: dict, n: int, c: int):
     return cv, flips, out_dtype
 
 
-def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes, channels: Optional[int], conv: Optional[dict],
-                 place=(None, None, 0)) -> torch.Tensor:
-    """resize_many (conv None) and resize_many_to_float (conv: its options): the checks, the layout class, the plan and the launches.
-    place: (sizes, offsets, fill)."""
-    if mode not in _lib.FILTER_IDS:
-        raise ValueError(mode)
-    filter_id = _lib.FILTER_IDS[mode]
-    if len(output_size) != 2:
-        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
-    oh, ow = int(output_size[0]), int(output_size[1])
+def _many_items(name: str, images, channels: Optional[int], empty: str):
+    """The images of a ragged call -> ([C, H, W] items, the device of a batch tensor or None, N, C).  empty: the shape of the N == 0 result,
+    for the message that asks for channels=."""
     if isinstance(images, torch.Tensor):
         if images.dim() != 4:
             raise RuntimeError(f"{name}(): one tensor must be [N, C, H, W], got {list(images.shape)}")
@@ -604,12 +600,17 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
             items.append(t)
     n = len(items)
     if n == 0 and channels is None:
-        raise ValueError(f"{name}(): an empty list needs channels= (the C of the [0, C, oh, ow] result)")
+        raise ValueError(f"{name}(): an empty list needs channels= (the C of the {empty} result)")
     c = int(channels) if channels is not None else int(items[0].shape[0])
     if not (1 <= c <= 4):
         raise ValueError(f"{name}(): images of 1 to 4 channels, got C = {c}")
-    if not (oh > 0 and ow > 0):
-        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    return items, dev0, n, c
+
+
+def _many_check_items(name: str, items, c: int, boxes, out_size):
+    """Dtype, C, sizes, device and box of every item -> the boxes as Pillow's C sees them (None: the whole image).  out_size(i): the
+    (H, W) item i is resized to, for the wording of the size check."""
+    n = len(items)
     if boxes is not None and len(boxes) != n:
         raise ValueError(f"{name}(): boxes must hold one entry per image ({n}), got {len(boxes)}")
     checked = []
@@ -620,6 +621,7 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
             raise ValueError(f"{name}(): every image must have the same C: images[{i}] has {int(t.shape[0])}, expected {c}")
         h, w = int(t.shape[1]), int(t.shape[2])
         if not (h > 0 and w > 0):
+            oh, ow = out_size(i)
             raise RuntimeError(f"Input and output sizes should be greater than 0, but got input (H: {h}, W: {w}) output (H: {oh}, W: {ow})")
         if t.device != items[0].device:
             raise ValueError(f"{name}(): every image must be on the same device: images[{i}] is on {t.device}, images[0] on {items[0].device}")
@@ -627,6 +629,55 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
         if bx is not None:
             bx = boxmath.box_f32(boxmath.check_box(bx, w, h))  # Pillow's checks and wording; its C takes the box as floats
         checked.append(bx)
+    return checked
+
+
+def _many_layout(items, c: int):
+    """One layout class for the call: the majority's; whoever is not in it is copied.  -> (per-item classes, interleaved pixels?)"""
+    classes = [_many_class(t) for t in items]
+    n_inter = sum(1 for a, b in classes if a and not b)
+    n_planar = sum(1 for a, b in classes if b and not a)
+    return classes, c > 1 and n_inter > 0 and n_inter >= n_planar
+
+
+def _many_records(items, classes, interleaved: bool, c: int, checked, flips):
+    """The aa_many_image records of the items in the call's class -> (records, the copies that must outlive the launches)."""
+    recs = (_lib.ManyImage * len(items))()
+    keep = []
+    for i, t in enumerate(items):
+        if not classes[i][0 if interleaved else 1]:
+            t = t.permute(1, 2, 0).contiguous().permute(2, 0, 1) if interleaved else t.contiguous()
+            keep.append(t)
+        r = recs[i]
+        r.data_dev = t.data_ptr()
+        r.H, r.W = int(t.shape[1]), int(t.shape[2])
+        # (the stride of an axis of one element is arbitrary: hand over the class's own)
+        r.stride_ch = 1 if interleaved else (t.stride(0) if c > 1 else 0)
+        r.stride_row = t.stride(1) if r.H > 1 else 0
+        r.stride_px = (c if interleaved else 1)
+        bx = checked[i]
+        if bx is not None:
+            r.has_box = 1
+            r.box[0], r.box[1], r.box[2], r.box[3] = bx
+        if flips is not None and flips[i]:
+            r.flags = _lib.MANY_FLIP_X
+    return recs, keep
+
+
+def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes, channels: Optional[int], conv: Optional[dict],
+                 place=(None, None, 0)) -> torch.Tensor:
+    """resize_many (conv None) and resize_many_to_float (conv: its options): the checks, the layout class, the plan and the launches.
+    place: (sizes, offsets, fill)."""
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    filter_id = _lib.FILTER_IDS[mode]
+    if len(output_size) != 2:
+        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
+    oh, ow = int(output_size[0]), int(output_size[1])
+    items, dev0, n, c = _many_items(name, images, channels, "[0, C, oh, ow]")
+    if not (oh > 0 and ow > 0):
+        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    checked = _many_check_items(name, items, c, boxes, lambda i: (oh, ow))
     cv, flips, out_dtype = None, None, torch.uint8
     if conv is not None:
         cv, flips, out_dtype = _many_convert(name, conv, n, c)
@@ -638,11 +689,7 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
     for t in items:
         _require_gpu(t, name)
     dev = items[0].device
-    # one layout class for the call: the majority's; whoever is not in it is copied
-    classes = [_many_class(t) for t in items]
-    n_inter = sum(1 for a, b in classes if a and not b)
-    n_planar = sum(1 for a, b in classes if b and not a)
-    interleaved = c > 1 and n_inter > 0 and n_inter >= n_planar
+    classes, interleaved = _many_layout(items, c)
     layout = _lib.NHWC if interleaved else _lib.NCHW
     out_nhwc = interleaved
     if cv is not None:
@@ -651,25 +698,7 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
         cv.out_layout = _lib.NHWC if out_nhwc else _lib.NCHW
     L = _lib.load()
     with torch.cuda.device(dev):
-        recs = (_lib.ManyImage * n)()
-        keep = []
-        for i, t in enumerate(items):
-            if not classes[i][0 if interleaved else 1]:
-                t = t.permute(1, 2, 0).contiguous().permute(2, 0, 1) if interleaved else t.contiguous()
-                keep.append(t)
-            r = recs[i]
-            r.data_dev = t.data_ptr()
-            r.H, r.W = int(t.shape[1]), int(t.shape[2])
-            # (the stride of an axis of one element is arbitrary: hand over the class's own)
-            r.stride_ch = 1 if interleaved else (t.stride(0) if c > 1 else 0)
-            r.stride_row = t.stride(1) if r.H > 1 else 0
-            r.stride_px = (c if interleaved else 1)
-            bx = checked[i]
-            if bx is not None:
-                r.has_box = 1
-                r.box[0], r.box[1], r.box[2], r.box[3] = bx
-            if flips is not None and flips[i]:
-                r.flags = _lib.MANY_FLIP_X
+        recs, keep = _many_records(items, classes, interleaved, c, checked, flips)
         # (places that are all the whole canvas at offset 0 plan to the plain block: the tail of the larger one is then copied as it is
         # and never read)
         desc_bytes = L.aa_many_desc_bytes(n) if places is None else L.aa_many_desc_bytes_placed(n)
@@ -696,6 +725,120 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
         else:
             rc = L.aa_resample_many_u8_to_float(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(),
                                                 ws.numel(), ctypes.byref(cv), stream)
+    _lib.check(rc, name)
+    return out
+
+
+def _patch_sizes(name: str, sizes, patch, n: int, pad_to):
+    """patch, sizes and pad_to of resize_many_to_patches, checked -> ((ph, pw), [(vh, vw)] per item, L or None)."""
+    try:
+        ph, pw = boxmath.check_patch(patch)
+    except ValueError as e:
+        raise ValueError(f"{name}(): {e}") from None
+    if ph > _MANY_MAX or pw > _MANY_MAX:
+        raise ValueError(f"{name}(): patch = ({ph}, {pw}) is beyond the supported {_MANY_MAX}")
+    if sizes is None:
+        raise ValueError(f"{name}(): sizes is required: N entries (vh, vw), or one pair for all items")
+    try:
+        one = len(sizes) == 2 and not isinstance(sizes[0], (tuple, list)) and int(sizes[0]) == sizes[0]
+    except (TypeError, ValueError):
+        one = False
+    if one:
+        sizes = [tuple(sizes)] * n
+    if len(sizes) != n:
+        raise ValueError(f"{name}(): sizes must hold one entry per image ({n}), got {len(sizes)}")
+    out = []
+    for i in range(n):
+        vh, vw = _many_int_pair(name, "sizes", i, sizes[i])
+        if vh <= 0 or vw <= 0:
+            raise ValueError(f"{name}(): sizes[{i}] = ({vh}, {vw}) must be positive")
+        if vh > _MANY_MAX or vw > _MANY_MAX:
+            raise ValueError(f"{name}(): sizes[{i}] = ({vh}, {vw}) is beyond the supported {_MANY_MAX}")
+        out.append((vh, vw))
+    try:
+        grids = boxmath.patch_grids(out, (ph, pw))  # (the divisibility check, naming the item)
+    except ValueError as e:
+        raise ValueError(f"{name}(): {e}") from None
+    if pad_to is not None:
+        if isinstance(pad_to, bool) or int(pad_to) != pad_to or pad_to < 1 or pad_to > 2 ** 31 - 1:
+            raise ValueError(f"{name}(): pad_to must be None or a positive integer, got {pad_to!r}")
+        pad_to = int(pad_to)
+        for i, (gh, gw) in enumerate(grids):
+            if gh * gw > pad_to:
+                raise ValueError(f"{name}(): sizes[{i}] = {out[i]} is {gh * gw} tokens, more than pad_to = {pad_to}")
+    return (ph, pw), out, pad_to
+
+
+def resize_many_to_patches(images, patch: Sequence[int], mode: str = "bicubic", *, sizes=None, boxes=None, flips=None,
+                           channels: Optional[int] = None, patch_format: str = "cpp", pad_to: Optional[int] = None, out_dtype=torch.float32,
+                           mean=None, std=None) -> torch.Tensor:
+    """The ragged batch as the packed patch tokens a native-resolution vision transformer reads (NaViT, NaFlex, VLM towers): item i is
+    resized to ITS OWN size ``sizes[i] = (vh_i, vw_i)``, a multiple of ``patch = (ph, pw)``, converted like ``resize_many_to_float`` and
+    cut into ``ph x pw`` patches, all in the same three launches.  With ``gh = vh // ph``, ``gw = vw // pw``, ``T = gh * gw``, ``D = C * ph * pw``
+    and
+
+        R_i = resize_many_to_float([images[i]], (vh_i, vw_i), mode, boxes=[boxes[i]], flips=[flips[i]], out_dtype=out_dtype,
+                                   out_format="nchw", mean=mean, std=std)[0]
+        P_i = R_i.view(C, gh, ph, gw, pw)
+        P_i = P_i.permute(1, 3, 0, 2, 4).reshape(T, D)    patch_format="cpp": a token is [C, ph, pw], a Conv2d(C, dim, patch, stride=patch) weight flattened
+        P_i = P_i.permute(1, 3, 2, 4, 0).reshape(T, D)    patch_format="ppc": a token is [ph, pw, C], einops '(p1 p2 c)'
+
+    the result is, bit for bit, ``torch.cat(P_0 .. P_{N-1})``, [sum T_i, D], item i at rows ``boxmath.token_offsets(sizes, patch)[i]`` on
+    (``pad_to=None``); or [N, L, D] with ``tok[i, :T_i] = P_i`` and literal zeros (+0.0, not normalised) beyond (``pad_to=L``; an item of
+    more than L tokens raises ValueError).  A flip mirrors the item's own resized image before it is cut.
+
+    ``images``, ``mode``, ``boxes``, ``flips``, ``channels``, ``out_dtype``, ``mean``, ``std``: ``resize_many_to_float``'s.  ``sizes``: N entries
+    (vh, vw), height first, or one pair for all items; ``boxmath.fit_patch_sizes`` makes them from the images' shapes.  There is no canvas:
+    no ``output_size``, ``offsets`` or ``fill``.  N == 0 gives [0, D] or [0, L, D]; a list then says its C with ``channels=``.
+
+    One contiguous tensor from three launches and one non-blocking descriptor copy whatever N and whatever the sizes; nothing is read
+    back, no table cache is touched, the call does not synchronise."""
+    name = "resize_many_to_patches"
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+    if patch_format not in ("cpp", "ppc"):
+        raise ValueError("patch_format must be 'cpp' (token = [C, ph, pw]) or 'ppc' (token = [ph, pw, C])")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std must be given together")
+    if _uint8_mode != "pil":
+        raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    filter_id = _lib.FILTER_IDS[mode]
+    items, dev0, n, c = _many_items(name, images, channels, "[0, C * ph * pw]")
+    (ph, pw), sizes, pad_to = _patch_sizes(name, sizes, patch, n, pad_to)
+    checked = _many_check_items(name, items, c, boxes, lambda i: sizes[i])
+    cv, flips, out_dtype = _many_convert(name, {"out_dtype": out_dtype, "mean": mean, "std": std, "flips": flips}, n, c)
+    d = c * ph * pw
+    rows = boxmath.token_offsets(sizes, (ph, pw))[-1]
+    shape = (rows, d) if pad_to is None else (n, pad_to, d)
+    if n == 0:
+        if dev0 is None:
+            dev0 = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        return torch.empty(shape, dtype=out_dtype, device=dev0)
+    for t in items:
+        _require_gpu(t, name)
+    dev = items[0].device
+    classes, interleaved = _many_layout(items, c)
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    cv.out_layout = _lib.NCHW  # (not looked at: the token layout is patch_format)
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        recs, keep = _many_records(items, classes, interleaved, c, checked, flips)
+        flat = (ctypes.c_int64 * (2 * n))(*[v for s in sizes for v in s])
+        desc_bytes = L.aa_many_desc_bytes_patches(n)
+        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
+        ws_bytes, out_rows = ctypes.c_size_t(0), ctypes.c_int64(0)
+        _lib.check(L.aa_many_plan_patches(filter_id, layout, n, c, ph, pw, recs, flat, pad_to or 0, desc_host.data_ptr(), desc_bytes,
+                                          ctypes.byref(ws_bytes), ctypes.byref(out_rows)), name)
+        assert out_rows.value == (rows if pad_to is None else n * pad_to), (out_rows.value, rows, pad_to)
+        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
+        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
+        ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
+        out = torch.empty(shape, dtype=out_dtype, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = L.aa_resample_many_u8_to_patches(desc_host.data_ptr(), desc_dev.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), ctypes.byref(cv),
+                                              _lib.PATCH_PPC if patch_format == "ppc" else _lib.PATCH_CPP, stream)
     _lib.check(rc, name)
     return out
 
@@ -1148,6 +1291,33 @@ def _register_torch_ops() -> None:
                  mean=mean, std=std, sizes=_many_pairs(images, sizes, "sizes"), offsets=_many_pairs(images, offsets, "offsets"),
                  fill=_many_fill(fill)), "CUDA")
     lib.impl("resize_many_to_float", _many_float_meta, "Meta")
+
+    # per-item sizes flattened to 2 N ints (height first), or one pair for all; the Meta shape follows from them alone
+    lib.define('resize_many_to_patches(Tensor[] images, int[] patch, str mode, int[] sizes, float[]? boxes, bool[]? flips, str patch_format, '
+               'int? pad_to, ScalarType? out_dtype, float[]? mean, float[]? std) -> Tensor')
+
+    def _patch_pairs(images, sizes):
+        if len(sizes) == 2:
+            return [tuple(sizes)] * len(images)
+        if len(sizes) != 2 * len(images):
+            raise ValueError(f"resize_many_to_patches(): sizes must hold 2 values per image ({2 * len(images)}) or one pair, got {len(sizes)}")
+        return [tuple(sizes[2 * i:2 * i + 2]) for i in range(len(images))]
+
+    def _many_patches_meta(images, patch, mode, sizes, boxes, flips, patch_format, pad_to, out_dtype, mean, std):
+        if not images:
+            raise ValueError("resize_many_to_patches(): the op needs at least one image (an empty list has no C)")
+        t = images[0]
+        c = int(t.shape[1] if t.dim() == 4 else t.shape[0])
+        (ph, pw), pairs, pad_to = _patch_sizes("resize_many_to_patches", _patch_pairs(images, sizes), tuple(patch), len(images), pad_to)
+        rows = boxmath.token_offsets(pairs, (ph, pw))[-1]
+        shape = (rows, c * ph * pw) if pad_to is None else (len(images), pad_to, c * ph * pw)
+        return torch.empty(shape, dtype=torch.float32 if out_dtype is None else out_dtype, device="meta")
+
+    lib.impl("resize_many_to_patches", lambda images, patch, mode, sizes, boxes, flips, patch_format, pad_to, out_dtype, mean, std:
+             resize_many_to_patches(list(images), tuple(patch), mode, sizes=_patch_pairs(images, sizes), boxes=_many_boxes(images, boxes), flips=flips,
+                                    patch_format=patch_format, pad_to=pad_to, out_dtype=torch.float32 if out_dtype is None else out_dtype,
+                                    mean=mean, std=std), "CUDA")
+    lib.impl("resize_many_to_patches", _many_patches_meta, "Meta")
 
     for name, fn in bwds.items():
         lib.impl(name, (lambda f: lambda grad_output, output_size, input_size, align_corners=False:

@@ -23,6 +23,15 @@ preallocated batch, and for eval the torch conversion of the batch:
 
 Both ways give the same bits; kernel launches per batch are counted with torch's profiler where it works.
 
+--patches, on the same N images: the packed ViT patch tokens of a native-resolution tower (patch 14, fit_patch_sizes(max_tokens=256),
+bicubic, bfloat16, mean / std; both token formats, both layout classes of the items), two ways:
+
+  composition  per item resize_many_to_float([img], its own size) and view / permute / reshape, then one cat: the code a user writes
+               without the call;
+  call         resize_many_to_patches: one call, three launches whatever N.
+
+Both give the same bits.  No bar is set: the numbers are reported as they come.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
@@ -32,9 +41,12 @@ results into one tensor; (c) writes the batch.
   python tools/resize_many_bench.py --placed > out.txt   # only the placed call against the per-image loop (below);
                                                          # profiles/resize_many_placed.txt is this output, after the default table of
                                                          # the parent commit (twice) and of this one from the same session
+  python tools/resize_many_bench.py --patches > out.txt  # only the patch tokens against the per-item composition;
+                                                         # profiles/resize_many_patches.txt is this output
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
+  python tools/resize_many_bench.py --trace 20 --trace-patches # the same with resize_many_to_patches calls (the --patches workload, cpp)
   python tools/resize_many_bench.py --summarise DIR      # kernels and copies per call, kernel time and bytes / time from that trace
 """
 import argparse
@@ -197,6 +209,60 @@ def placed(args, torch, aa, images, shapes, timed):
         print(f"  call against loop: {ml / mc:.2f} x; median gain {ml - mc:.3f} ms, the two spreads together {(hl - ll) + (hc - lc):.3f} ms")
 
 
+def patches(args, torch, aa, images, shapes, timed):
+    """resize_many_to_patches against the per-item composition through resize_many_to_float."""
+    from interpolate_antialiasing_amd import boxmath
+
+    mean, std = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
+    ph = pw = 14
+    vs = boxmath.fit_patch_sizes(shapes, (ph, pw), max_tokens=256)
+    offs = boxmath.token_offsets(vs, (ph, pw))
+    dtype = torch.bfloat16
+    perms = {"cpp": (1, 3, 0, 2, 4), "ppc": (1, 3, 2, 4, 0)}
+    by_class = {"interleaved": images, "planar": [img.contiguous() for img in images]}
+
+    def composition(imgs, fmt, n=N):
+        toks = []
+        for img, (vh, vw) in zip(imgs[:n], vs[:n]):
+            r = aa.resize_many_to_float([img], [vh, vw], "bicubic", out_dtype=dtype, out_format="nchw", mean=mean, std=std)[0]
+            toks.append(r.view(3, vh // ph, ph, vw // pw, pw).permute(*perms[fmt]).reshape((vh // ph) * (vw // pw), 3 * ph * pw))
+        return torch.cat(toks)
+
+    def call(imgs, fmt, n=N):
+        return aa.resize_many_to_patches(imgs[:n], (ph, pw), "bicubic", sizes=vs[:n], patch_format=fmt, out_dtype=dtype, mean=mean, std=std)
+
+    print(f"resize_many_bench --patches: N = {N} uint8 images, H and W in [256, 1024] (seed {SEED}); library: {os.path.basename(_lib_path())}")
+    print(f"patch {ph} x {pw}, fit_patch_sizes(max_tokens=256): {offs[-1]} tokens of {3 * ph * pw} elements, {min(b - a for a, b in zip(offs, offs[1:]))} .. "
+          f"{max(b - a for a, b in zip(offs, offs[1:]))} per item; bicubic, bfloat16, mean / std")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+    for cls, imgs in by_class.items():
+        for fmt in perms:
+            contestants = {"composition: per-item call + view/permute/cat": lambda: composition(imgs, fmt), "call: resize_many_to_patches": lambda: call(imgs, fmt)}
+            for fn in contestants.values():
+                fn()
+                fn()
+            torch.cuda.synchronize()
+            a, b = composition(imgs, fmt), call(imgs, fmt)
+            assert a.shape == b.shape and torch.equal(a.view(torch.int16), b.view(torch.int16)), "resize_many_to_patches differs from the composition"
+            times = {k: [] for k in contestants}
+            for _ in range(args.rounds):
+                for k, fn in contestants.items():
+                    times[k].append(timed(fn))
+            print(f"\n{cls} items, token format {fmt}")
+            stat = {}
+            for k, v in times.items():
+                stat[k] = (statistics.median(v), min(v), max(v))
+                launches = count_launches(torch, contestants[k])
+                print(f"  {k:48s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]   kernel launches per batch: "
+                      f"{launches if launches is not None else 'not measured'}")
+            (mc, lc, hc), (mo, lo, ho) = stat.values()
+            verdict = "the one call is faster" if mo < mc else "THE ONE CALL IS NOT FASTER than the composition"
+            print(f"  call against composition: {mc / mo:.2f} x; median gain {mc - mo:.3f} ms, the two spreads together {(hc - lc) + (ho - lo):.3f} ms: {verdict}")
+    counts = {n: count_launches(torch, lambda: call(images, "cpp", n)) for n in (1, 8, N)}
+    print("\nkernel launches of one resize_many_to_patches call by N (expected 3, whatever N): "
+          + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
+
+
 def _lib_path():
     from interpolate_antialiasing_amd import _lib
 
@@ -212,6 +278,9 @@ def main():
     ap.add_argument("--summarise", default=None)
     ap.add_argument("--float-only", action="store_true")
     ap.add_argument("--placed", action="store_true", help="only the placed call (eval and letterbox) against the per-image loop")
+    ap.add_argument("--patches", action="store_true", help="only resize_many_to_patches against the per-item composition")
+    ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
+                    "with --summarise: kernel times only")
     ap.add_argument("--trace-float", action="store_true", help="with --trace: the calls are resize_many_to_float (bfloat16, nchw, mean / std, flips)")
     args = ap.parse_args()
 
@@ -220,6 +289,8 @@ def main():
     if args.summarise:
         calls = WARM_CALLS + max(args.trace, 1)
         med = summarise(args.summarise, calls)
+        if args.trace_patches:
+            return
         brng = np.random.default_rng(SEED + 1)
         boxes = [random_resized_crop_box(brng, h, w) for h, w in shapes]
         hull, inter, out = algorithm_bytes(shapes, boxes, MODES[args.trace_mode])
@@ -249,7 +320,12 @@ def main():
 
     if args.trace:
         for _ in range(WARM_CALLS + args.trace):
-            if args.trace_float:
+            if args.trace_patches:
+                from interpolate_antialiasing_amd import boxmath
+
+                aa.resize_many_to_patches(images, (14, 14), "bicubic", sizes=boxmath.fit_patch_sizes(shapes, (14, 14), max_tokens=256),
+                                          out_dtype=torch.bfloat16, mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375])
+            elif args.trace_float:
                 aa.resize_many_to_float(images, list(OUT), args.trace_mode, boxes=fresh_boxes(), flips=[i % 2 == 1 for i in range(N)],
                                         out_dtype=torch.bfloat16, out_format="nchw", mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375])
             else:
@@ -278,6 +354,9 @@ def main():
 
     if args.placed:
         placed(args, torch, aa, images, shapes, timed)
+        return
+    if args.patches:
+        patches(args, torch, aa, images, shapes, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
