@@ -1,6 +1,7 @@
-"""resize_many_to_float on the GPU.  Expected values never come from the call under test: the bytes are the CPU restatement's (pinned to
-Pillow by the CPU tests; the fixture's CRC where the result is bytes again) or, for an ad-hoc shape, the unchanged resize_many's, and the
-conversion is torch's on the CPU: ((b.float() - mean) / std).to(dtype), .flip(-1).  Bit patterns are compared: tolerance 0."""
+"""resize_many_to_float on the GPU.  Expected values never come from the package: the bytes are the CPU restatement's (pinned to Pillow by
+the CPU tests; the fixture's CRC where the result is bytes again), for an ad-hoc shape too — where a test also compares with resize_many, it
+first asserts that resize_many's bytes are the restatement's, because both calls share their horizontal pass and their vertical sums —
+and the conversion is torch's on the CPU: ((b.float() - mean) / std).to(dtype), .flip(-1).  Bit patterns are compared: tolerance 0."""
 import ctypes
 import functools
 import os
@@ -158,12 +159,20 @@ def _adhoc(c, sizes, cls, seed):
     return [_to_gpu(rng.integers(0, 256, (c, h, w), dtype=np.uint8), cls) for h, w in sizes]
 
 
+def _adhoc_restated(imgs, size, f, boxes=None):
+    """Pillow's bytes of ad-hoc images from the CPU restatement: [N, C, oH, oW] uint8 on the CPU."""
+    boxes = boxes if boxes is not None else [None] * len(imgs)
+    return torch.from_numpy(np.stack([G._br.resize_box_restated(f, np.ascontiguousarray(t.permute(1, 2, 0).cpu().numpy()), size[0], size[1], b)
+                                      .transpose(2, 0, 1) for t, b in zip(imgs, boxes)]))
+
+
 @pytest.mark.parametrize("ow", [1, 2])
 def test_flips_of_outputs_one_and_two_columns_wide(ow):
     imgs = _adhoc(3, [(23, 31), (9, 5), (40, 2)], "interleaved", 100 + ow)
     boxes = [None, (0.5, 1.0, 4.25, 8.0), None]
     flips = [True, False, True]
     u = aa.resize_many(imgs, [7, ow], "bicubic", boxes=boxes).cpu()
+    assert torch.equal(u, _adhoc_restated(imgs, (7, ow), "cubic", boxes))  # (what is converted below is Pillow's, not the package's own)
     y = aa.resize_many_to_float(imgs, [7, ow], "bicubic", boxes=boxes, flips=flips, out_dtype=torch.bfloat16, out_format="nchw", **_norm(3))
     assert y.is_contiguous()
     _assert_bits(y, _convert(u, torch.bfloat16, True, flips), f"ow = {ow}")
@@ -177,6 +186,7 @@ def test_rows_of_several_pieces(c, cls, ow):
     imgs = _adhoc(c, [(5, 400), (4, 37)], cls, 200 + ow)
     flips = [True, False]
     u = aa.resize_many(imgs, [3, ow], "bilinear").cpu()
+    assert torch.equal(u, _adhoc_restated(imgs, (3, ow), "linear"))  # (what is converted below is Pillow's, not the package's own)
     for dtype in DTYPES:
         want = _convert(u, dtype, True, flips)
         for fmt in FORMATS:

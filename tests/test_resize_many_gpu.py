@@ -179,6 +179,7 @@ def test_a_mixed_list_copies_the_minority():
     name = "m_c4"
     inter, planar = _inputs(name, "interleaved"), _inputs(name, "planar")
     want = aa.resize_many(inter, [19, 77], "bicubic", boxes=_boxes(name))
+    _check_against_fixture(name, "cubic", want)  # (what the mixed lists are compared with is Pillow's)
     y = aa.resize_many([inter[0], planar[1], inter[2]], [19, 77], "bicubic", boxes=_boxes(name))
     assert y.is_contiguous(memory_format=torch.channels_last) and torch.equal(y, want)
     y = aa.resize_many([planar[0], inter[1], planar[2]], [19, 77], "bicubic", boxes=_boxes(name))
