@@ -412,6 +412,35 @@ int aa_many_plan_patches(int filter, int layout, int64_t n, int64_t C, int64_t p
 int aa_resample_many_u8_to_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
                                    const aa_convert *cv, int patch_format, aa_stream_t stream);
 
+/* ---- ragged Image.reduce: N uint8 images of N sizes, each with its own integer box and factors, into one arena ------------------------
+ * Pillow's first step of Image.resize(reducing_gap=...) for a list: every large item is read ONCE by an integer box mean, and the ragged
+ * resize above then runs over the small results, which it reads where they lie (an arena offset is just another pointer of an
+ * aa_many_image).  ONE launch whatever n.  Item i of the result equals aa_reduce_u8 on that image with its box and factors, bit for bit
+ * (the same device code): dense in the call's class, [rh, rw, C] (AA_NHWC) or [C, rh, rw] (AA_NCHW), rw = ceil((x1 - x0) / fx),
+ * rh = ceil((y1 - y0) / fy), at out_offsets[i] of the arena, a multiple of 16.
+ * aa_reduce_many_plan is host arithmetic only (no HIP call: works without a device).  It writes one packed descriptor block into caller
+ * memory — per item the box's first byte, the pitches, the arena offset, the sizes, the tiling and the four multipliers
+ * (uint32)(4294967296.0f / (float)(256 * n)) of aa_reduce_u8, then int64 prefix sums of work units — and reports the arena's size.
+ * layout: the class ALL items share, under the rules of aa_many_image; C is 1..4.  Errors: AA_ERR_BAD_SHAPE for C outside 1..4, an
+ * empty box or one beyond its image, a factor below 1 or fx * fy > 65536, a size beyond INT32_MAX / 4, or more work units than one grid
+ * holds; AA_ERR_STRIDES for an item that is not in `layout`'s class; AA_ERR_NULL; AA_ERR_WORKSPACE for desc_bytes below
+ * aa_reduce_many_desc_bytes(n).
+ * aa_reduce_many_u8 enqueues the launch.  desc_dev: the device copy of desc_host (8-byte aligned), in flight or complete on `stream`;
+ * desc_host is read to size the grid and to check the block's magic, n and arena_bytes against the plan before anything runs.
+ * arena_dev: 16-byte aligned, at least the plan's size.  Nothing is allocated, synchronised or read back; n == 0 launches nothing.
+ * Added without an ABI version change (additive). */
+typedef struct aa_reduce_item {
+  const void *data_dev;                      /* byte (row 0, column 0, channel 0) of the IMAGE, not of the box */
+  int64_t H, W;
+  int64_t stride_row, stride_px, stride_ch;  /* bytes; the rules of aa_many_image for `layout`'s class */
+  int64_t box[4];                            /* x0, y0, x1, y1 integers inside the image, Pillow's order */
+  int32_t fx, fy;                            /* >= 1, fx * fy <= 65536; 1, 1 copies the box */
+} aa_reduce_item;
+size_t aa_reduce_many_desc_bytes(int64_t n);
+int aa_reduce_many_plan(int layout, int64_t n, int64_t C, const aa_reduce_item *items, void *desc_host, size_t desc_bytes,
+                        size_t *arena_bytes, int64_t *out_offsets /* n byte offsets into the arena */);
+int aa_reduce_many_u8(const void *desc_host, const void *desc_dev, void *arena_dev, size_t arena_bytes, aa_stream_t stream);
+
 /* Device-to-device copy of `bytes` bytes with 16-byte vector loads/stores, enqueued on `stream`: the probe bench.py times
  * on the box to report the attainable HBM copy ceiling next to the 8 TB/s spec peak.  form 0: one element per
  * thread; 1: grid-stride; 2: four elements per thread, loads in flight before the stores; 3: form 2, streaming (nt) policy;

@@ -52,6 +52,7 @@ EXPORTS = (
     "aa_workspace_bytes_ex", "aa_table_ksize_box", "aa_table_build_bytes_box", "aa_table_build_box", "aa_reduce_u8", "aa_premultiply_u8",
     "aa_unpremultiply_u8", "aa_many_desc_bytes", "aa_many_plan", "aa_resample_many_u8", "aa_resample_many_u8_to_float",
     "aa_many_desc_bytes_placed", "aa_many_plan_placed", "aa_many_desc_bytes_patches", "aa_many_plan_patches", "aa_resample_many_u8_to_patches",
+    "aa_reduce_many_desc_bytes", "aa_reduce_many_plan", "aa_reduce_many_u8",
 )
 
 
@@ -113,6 +114,26 @@ class ManyPlaced(ctypes.Structure):
                 ("mw", ctypes.c_int32), ("dy", ctypes.c_int32), ("dx", ctypes.c_int32)]
 
 
+class ReduceItem(ctypes.Structure):
+    """aa_reduce_item: one item of the ragged Image.reduce (strides in bytes; box = x0, y0, x1, y1 integers; factors fx, fy)."""
+    _fields_ = [("data_dev", ctypes.c_void_p), ("H", ctypes.c_int64), ("W", ctypes.c_int64), ("stride_row", ctypes.c_int64),
+                ("stride_px", ctypes.c_int64), ("stride_ch", ctypes.c_int64), ("box", ctypes.c_int64 * 4), ("fx", ctypes.c_int32),
+                ("fy", ctypes.c_int32)]
+
+
+class ReduceManyHeader(ctypes.Structure):
+    """Head of the block aa_reduce_many_plan writes (csrc/aa_reduce_many.h AAReduceManyHeader; opaque to C callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("C", ctypes.c_int32), ("layout", ctypes.c_int32), ("E", ctypes.c_int32),
+                ("planes", ctypes.c_int32), ("units", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64 * 3)]
+
+
+class ReduceManyItem(ctypes.Structure):
+    """One item of that block (csrc/aa_reduce_many.h AAReduceManyItem): the box's first byte, pitches, arena offset, sizes, tiling, mults."""
+    _fields_ = [("src", ctypes.c_void_p), ("row_pitch", ctypes.c_int64), ("plane_pitch", ctypes.c_int64), ("out_off", ctypes.c_int64),
+                ("bw", ctypes.c_int32), ("bh", ctypes.c_int32), ("fx", ctypes.c_int32), ("fy", ctypes.c_int32), ("rw", ctypes.c_int32),
+                ("rh", ctypes.c_int32), ("sx", ctypes.c_int32), ("xtiles", ctypes.c_int32), ("mult", ctypes.c_uint32 * 4)]
+
+
 MANY_FLIP_X = 1     # aa_many_image.flags: mirror the item's output left to right (aa_resample_many_u8_to_float only)
 PATCH_CPP, PATCH_PPC = 0, 1  # aa_resample_many_u8_to_patches: token vector [C, ph, pw] or [ph, pw, C]
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
@@ -123,6 +144,14 @@ def many_desc_view(buf, n: int):
     hd = ManyHeader.from_buffer(buf, 0)
     items = (ManyItem * n).from_buffer(buf, ctypes.sizeof(ManyHeader))
     prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(ManyHeader) + n * ctypes.sizeof(ManyItem))
+    return hd, items, prefix
+
+
+def reduce_many_desc_view(buf, n: int):
+    """(header, items, prefix) of a ragged reduce's block held in a ctypes buffer: [header][n items][int64 prefix[n + 1]]."""
+    hd = ReduceManyHeader.from_buffer(buf, 0)
+    items = (ReduceManyItem * n).from_buffer(buf, ctypes.sizeof(ReduceManyHeader))
+    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(ReduceManyHeader) + n * ctypes.sizeof(ReduceManyItem))
     return hd, items, prefix
 
 
@@ -238,6 +267,12 @@ def load() -> ctypes.CDLL:
     L.aa_many_plan_patches.restype = i32
     L.aa_resample_many_u8_to_patches.argtypes = [vp, vp, vp, vp, sz, cvp, i32, vp]
     L.aa_resample_many_u8_to_patches.restype = i32
+    L.aa_reduce_many_desc_bytes.argtypes = [i64]
+    L.aa_reduce_many_desc_bytes.restype = sz
+    L.aa_reduce_many_plan.argtypes = [i32, i64, i64, ctypes.POINTER(ReduceItem), vp, sz, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_reduce_many_plan.restype = i32
+    L.aa_reduce_many_u8.argtypes = [vp, vp, vp, sz, vp]
+    L.aa_reduce_many_u8.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

@@ -117,6 +117,47 @@ def reducing_plan(width: int, height: int, out_w: int, out_h: int, filter_name: 
     return factor, rb, shifted_box(box, rb, factor)
 
 
+def reducing_plans(shapes, output_size, mode: str, boxes=None, sizes=None, reducing_gap=2.0):
+    """``reducing_plan`` for a list: shapes [(H_i, W_i)], the (H, W) every item is resized to (``sizes[i]`` where given, height first, else
+    ``output_size``) and one box per item (None: the whole image) -> N entries, each None (both factors are 1: the plain resize) or
+    (factor (fx, fy), reduce box (x0, y0, x1, y1) ints, the box for the resize of the reduced image, four doubles).  Pillow computes the
+    factors from the box and the size it resizes to, never from a place on a canvas.  An item whose box is full and whose size is its
+    own is None whatever the gap: Pillow returns a copy before it looks at reducing_gap.  Errors name the item."""
+    if mode not in SUPPORT:
+        raise ValueError(mode)
+    gap = check_reducing_gap(reducing_gap)
+    if gap is None:
+        raise ValueError("reducing_gap must be 1.0 or greater")
+    n = len(shapes)
+    if boxes is not None and len(boxes) != n:
+        raise ValueError(f"boxes must hold one entry per image ({n}), got {len(boxes)}")
+    if sizes is not None and len(sizes) != n:
+        raise ValueError(f"sizes must hold one entry per image ({n}), got {len(sizes)}")
+    if len(output_size) != 2:
+        raise ValueError(f"output_size must be (H, W), got {output_size!r}")
+    plans = []
+    for i, (h, w) in enumerate(shapes):
+        h, w = int(h), int(w)
+        oh, ow = output_size if sizes is None or sizes[i] is None else sizes[i]
+        oh, ow = int(oh), int(ow)
+        if h <= 0 or w <= 0 or oh <= 0 or ow <= 0:
+            raise ValueError(f"images[{i}]: sizes must be positive, got input (H: {h}, W: {w}) output (H: {oh}, W: {ow})")
+        bx = (0.0, 0.0, float(w), float(h))
+        if boxes is not None and boxes[i] is not None:
+            try:
+                bx = check_box(boxes[i], w, h)
+            except (ValueError, TypeError) as e:
+                raise ValueError(f"boxes[{i}]: {e}") from None
+        if axis_is_full(w, bx[0], bx[2]) and axis_is_full(h, bx[1], bx[3]) and (h, w) == (oh, ow):
+            plans.append(None)
+            continue
+        plan = reducing_plan(w, h, ow, oh, mode, bx, gap)
+        if plan is not None and plan[0][0] * plan[0][1] > MAX_REDUCE_BLOCK:
+            raise ValueError(f"images[{i}]: fx * fy = {plan[0][0] * plan[0][1]} beyond {MAX_REDUCE_BLOCK}")
+        plans.append(plan)
+    return plans
+
+
 def axis_hull(in_size: int, out_size: int, in0: float, in1: float, filter_name: str) -> Tuple[int, int]:
     """[o, e): what the windows of precompute_coeffs(in_size, in0, in1, out_size) cover together — the first output's xmin and the end of
     the last output's window, both clipped to the axis (window starts and ends are non-decreasing in the output index).  The same

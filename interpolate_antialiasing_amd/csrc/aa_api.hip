@@ -6,6 +6,7 @@
 
 #include "aa_box.h"
 #include "aa_many.h"
+#include "aa_reduce_many.h"
 #include "aa_plan.h"
 #include "aa_reduce.h"
 
@@ -546,6 +547,19 @@ int aa_reduce_u8(const void *in_dev, void *out_dev, int layout, int64_t N, int64
   job.fx = fx; job.fy = fy;
   job.stream = (hipStream_t)stream;
   return aa_launch_reduce_u8(job);
+}
+
+// ---- ragged Image.reduce -----------------------------------------------------------------------------------------------------------------
+size_t aa_reduce_many_desc_bytes(int64_t n) { return aa_reduce_many_desc_size(n); }
+
+int aa_reduce_many_plan(int layout, int64_t n, int64_t C, const aa_reduce_item *items, void *desc_host, size_t desc_bytes, size_t *arena_bytes,
+                        int64_t *out_offsets) {
+  return aa_reduce_many_plan_host(layout, n, C, items, desc_host, desc_bytes, arena_bytes, out_offsets);
+}
+
+int aa_reduce_many_u8(const void *desc_host, const void *desc_dev, void *arena_dev, size_t arena_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_reduce_many_u8(desc_host, desc_dev, arena_dev, arena_bytes, (hipStream_t)stream);
 }
 
 int aa_premultiply_u8(const void *src_dev, void *dst_dev, int layout, int64_t N, int64_t C, int64_t H, int64_t W, aa_stream_t stream) {

@@ -47,6 +47,9 @@ Differences, all additive:
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
     output size and a place on the [oH, oW] canvas (Resize + CenterCrop, letterbox): cropped or padded, only the covered part computed;
+  * ``reduce_many(images, factors, boxes=None)``: ``Image.reduce`` for such a list, every item with its own integer box and factors,
+    in one launch; ``reduce_many_for_resize(images, output_size, mode, boxes=, sizes=, reducing_gap=)``: Pillow's first step of
+    ``resize(..., reducing_gap=)`` for the list — the reduced images and shifted boxes that go into the three ragged calls above;
   * the same callables are registered as ``torch.ops.extension_interpolate.*``.
 """
 from __future__ import annotations
@@ -59,7 +62,7 @@ import torch
 
 from . import _lib, boxmath, tables
 
-__all__ = ["reduce", "resize_many", "resize_many_to_float", "resize_many_to_patches", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+__all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -444,13 +447,15 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
     Three launches and one non-blocking copy of a packed descriptor whatever N; every hull, ksize and offset is host arithmetic
     (aa_many_plan), so nothing is read back, and the table caches are neither read nor written.  Not built here: alpha, reducing_gap,
     uint8_mode="harness", float images or outputs, align_corners, scale factors (each raises NotImplementedError); float, normalised,
-    flipped output in either layout is ``resize_many_to_float``, packed ViT patch tokens are ``resize_many_to_patches``."""
+    flipped output in either layout is ``resize_many_to_float``, packed ViT patch tokens are ``resize_many_to_patches``.  Pillow's
+    ``reducing_gap`` is a step of its own, ``reduce_many_for_resize``, whose images and boxes go into any of the three calls."""
     name = "resize_many"
     for opt, given in (("alpha", bool(alpha)), ("reducing_gap", reducing_gap is not None), ("out_dtype", out_dtype is not None),
                        ("out_format", out_format is not None), ("mean", mean is not None), ("std", std is not None),
                        ("align_corners", bool(align_corners)), ("scale_factors", scale_factors is not None)):
         if given:
-            raise NotImplementedError(f"{name}(): {opt} is not built for a list of images; the single-image forwards have it")
+            hint = "; reduce_many_for_resize() is that step for a list, its results go into this call" if opt == "reducing_gap" else ""
+            raise NotImplementedError(f"{name}(): {opt} is not built for a list of images; the single-image forwards have it{hint}")
     if (uint8_mode or _uint8_mode) != "pil":
         if (uint8_mode or _uint8_mode) != "harness":
             raise ValueError("uint8_mode must be 'pil' or 'harness'")
@@ -841,6 +846,177 @@ def resize_many_to_patches(images, patch: Sequence[int], mode: str = "bicubic", 
                                               _lib.PATCH_PPC if patch_format == "ppc" else _lib.PATCH_CPP, stream)
     _lib.check(rc, name)
     return out
+
+
+def _reduce_many_factors(name: str, factors, n: int):
+    """factors of reduce_many -> [(fx, fy)] per item: one int, one (fx, fy) — a pair of plain integers, as ``reduce`` takes it — or N
+    entries, each an int or a pair."""
+    def one(what, f):
+        try:
+            return boxmath.check_factor(f)
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"{name}(): {what}: {e}") from None
+
+    if not isinstance(factors, (tuple, list)) or (len(factors) == 2 and not any(isinstance(v, (tuple, list)) for v in factors)):
+        return [one("factors", factors)] * n
+    if len(factors) != n:
+        raise ValueError(f"{name}(): factors must be one int, one (fx, fy) or one entry per image ({n}), got {len(factors)}")
+    return [one(f"factors[{i}]", f) for i, f in enumerate(factors)]
+
+
+def _reduce_many_channels(images, channels: Optional[int]):
+    """The result of a ragged reduce is a list, so an empty list of images needs no C: any will do."""
+    if channels is None and not isinstance(images, torch.Tensor) and len(images) == 0:
+        return 1
+    return channels
+
+
+def _reduce_many_check_items(name: str, items, c: int):
+    """Dtype, C, sizes and device of every item of a ragged reduce."""
+    for i, t in enumerate(items):
+        if t.dtype != torch.uint8:
+            raise NotImplementedError(f"{name}(): images[{i}] is {t.dtype}; a list of images is Pillow's uint8 arithmetic only")
+        if int(t.shape[0]) != c:
+            raise ValueError(f"{name}(): every image must have the same C: images[{i}] has {int(t.shape[0])}, expected {c}")
+        if not (int(t.shape[1]) > 0 and int(t.shape[2]) > 0):
+            raise RuntimeError(f"{name}(): images[{i}] is empty: {list(t.shape)}")
+        if t.device != items[0].device:
+            raise ValueError(f"{name}(): every image must be on the same device: images[{i}] is on {t.device}, images[0] on {items[0].device}")
+
+
+def _reduce_many_launch(name: str, items, c: int, factors, rboxes):
+    """The plan, the descriptor copy and the one launch of a ragged reduce -> N views [C, rh_i, rw_i] of one arena.  items: checked
+    [C, H, W] uint8 GPU tensors (at least one); factors [(fx, fy)], rboxes [(x0, y0, x1, y1)] integer boxes inside their images."""
+    n = len(items)
+    dev = items[0].device
+    classes, interleaved = _many_layout(items, c)
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        recs = (_lib.ReduceItem * n)()
+        keep = []  # (copies of items outside the class: the stream orders their release after the launch)
+        for i, t in enumerate(items):
+            if not classes[i][0 if interleaved else 1]:
+                t = t.permute(1, 2, 0).contiguous().permute(2, 0, 1) if interleaved else t.contiguous()
+                keep.append(t)
+            r = recs[i]
+            r.data_dev = t.data_ptr()
+            r.H, r.W = int(t.shape[1]), int(t.shape[2])
+            # (the stride of an axis of one element is arbitrary: hand over the class's own)
+            r.stride_ch = 1 if interleaved else (t.stride(0) if c > 1 else 0)
+            r.stride_row = t.stride(1) if r.H > 1 else 0
+            r.stride_px = c if interleaved else 1
+            r.box[0], r.box[1], r.box[2], r.box[3] = rboxes[i]
+            r.fx, r.fy = factors[i]
+        desc_bytes = L.aa_reduce_many_desc_bytes(n)
+        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
+        arena_bytes = ctypes.c_size_t(0)
+        offs = (ctypes.c_int64 * n)()
+        _lib.check(L.aa_reduce_many_plan(layout, n, c, recs, desc_host.data_ptr(), desc_bytes, ctypes.byref(arena_bytes), offs), name)
+        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
+        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
+        arena = torch.empty(max(arena_bytes.value, 16), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = L.aa_reduce_many_u8(desc_host.data_ptr(), desc_dev.data_ptr(), arena.data_ptr(), arena.numel(), stream)
+    _lib.check(rc, name)
+    views = []
+    for i in range(n):
+        rw, rh = boxmath.reduced_size(rboxes[i], factors[i])
+        flat = arena[offs[i]:offs[i] + c * rh * rw]
+        views.append(flat.view(rh, rw, c).permute(2, 0, 1) if interleaved else flat.view(c, rh, rw))
+    return views
+
+
+def reduce_many(images, factors, *, boxes=None, channels: Optional[int] = None):
+    """Pillow's ``Image.reduce(factors[i], boxes[i])`` for a list of uint8 images of different sizes, bit-exact, in ONE launch whatever
+    N: ``y[i]`` is ``reduce(images[i][None], factors[i], boxes[i])[0]`` bit for bit.
+
+    ``images``: what ``resize_many`` takes — a sequence of N uint8 GPU tensors [C, H_i, W_i] (or [1, C, H_i, W_i]), or one [N, C, H, W]
+    tensor whose slices are the items; same C (1..4) and device for all.  Items are read where they lie, at any row pitch, plane pitch
+    and byte offset; the call's layout class is chosen as in ``resize_many``, and an item outside it is copied into it first.
+    ``factors`` — PILLOW'S ORDER, X FIRST: one int, one (fx, fy), or N entries, each an int or (fx, fy); fx * fy <= 65536.  (A plain pair of
+    integers is always ONE (fx, fy): two per-item ints are written [(a, a), (b, b)].)
+    ``boxes``: None, or N entries, each None or an INTEGER box (x0, y0, x1, y1) inside its image.
+
+    The result is a list of N views [C, ceil((y1 - y0) / fy_i), ceil((x1 - x0) / fx_i)] of ONE arena tensor, each dense in the call's
+    class (interleaved items: strides (1, rw * C, C)), each starting on a 16-byte boundary: they go straight into ``resize_many``,
+    ``resize_many_to_float`` or ``resize_many_to_patches``.  One launch, one non-blocking copy of a packed descriptor from pinned memory,
+    no synchronisation, no table cache traffic.  N == 0 gives [].  There is no ``alpha``: Pillow drops ``reducing_gap`` for RGBA / LA
+    images, and ``reduce(alpha=True)`` serves a single one."""
+    name = "reduce_many"
+    if _uint8_mode != "pil":
+        raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
+    items, dev0, n, c = _many_items(name, images, _reduce_many_channels(images, channels), "[]")
+    facs = _reduce_many_factors(name, factors, n)
+    if boxes is not None and len(boxes) != n:
+        raise ValueError(f"{name}(): boxes must hold one entry per image ({n}), got {len(boxes)}")
+    _reduce_many_check_items(name, items, c)
+    rboxes = []
+    for i, t in enumerate(items):
+        try:
+            rboxes.append(boxmath.check_int_box(boxes[i] if boxes is not None else None, int(t.shape[2]), int(t.shape[1])))
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"{name}(): boxes[{i}]: {e}") from None
+    if n == 0:
+        return []
+    for t in items:
+        _require_gpu(t, name)
+    return _reduce_many_launch(name, items, c, facs, rboxes)
+
+
+def reduce_many_for_resize(images, output_size: Sequence[int], mode: str = "bilinear", *, boxes=None, sizes=None, reducing_gap: float = 2.0,
+                           channels: Optional[int] = None):
+    """Pillow's first step of ``Image.resize(size, FILTER, box=boxes[i], reducing_gap=g)`` for a whole list -> ``(images2, boxes2)``, the
+    arguments of the resize that follows:
+
+        small, b2 = reduce_many_for_resize(decoded, [224, 224], "bicubic", boxes=crops, reducing_gap=2.0)    # one launch
+        y = resize_many(small, [224, 224], "bicubic", boxes=b2)                                                 # three
+
+    gives, item for item, the bytes of ``PIL.Image.resize((224, 224), BICUBIC, box=crops[i], reducing_gap=2.0)``; the same holds for
+    ``resize_many_to_float`` and ``resize_many_to_patches`` and every option they take (flips, placement, conversion), since a reduced item
+    is just another image in device memory.  Per item the factors, the reduce box (Image._get_safe_box) and the shifted box are
+    ``boxmath.reducing_plans``: Pillow's arithmetic, from the box and the size the item is resized to (``sizes[i]``, height first, else
+    ``output_size``) — never from a place on a canvas, so offsets do not enter.
+
+    Items that Pillow would not reduce (both factors 1, or a full box at the item's own size) come back as the VERY SAME tensor objects
+    with their box unchanged: not copied, not launched on.  The others come back as views of one arena (``reduce_many``) with the shifted
+    box as four doubles (the resize rounds them to float32, as Pillow's C does).  If no item reduces there is no arena and no launch.
+    ``boxes2`` is None only when every entry is None.  There is no ``alpha``: Pillow drops ``reducing_gap`` for RGBA / LA images."""
+    name = "reduce_many_for_resize"
+    if _uint8_mode != "pil":
+        raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if len(output_size) != 2:
+        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
+    oh, ow = int(output_size[0]), int(output_size[1])
+    items, dev0, n, c = _many_items(name, images, _reduce_many_channels(images, channels), "[]")
+    same = items if isinstance(images, torch.Tensor) else list(images)  # (what comes back for an item that is not reduced)
+    if not (oh > 0 and ow > 0):
+        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    if sizes is not None:
+        if len(sizes) != n:
+            raise ValueError(f"{name}(): sizes must hold one entry per image ({n}), got {len(sizes)}")
+        sizes = [None if s is None else _many_int_pair(name, "sizes", i, s) for i, s in enumerate(sizes)]
+        for i, s in enumerate(sizes):
+            if s is not None and (s[0] <= 0 or s[1] <= 0):
+                raise ValueError(f"{name}(): sizes[{i}] = ({s[0]}, {s[1]}) must be positive")
+    _reduce_many_check_items(name, items, c)
+    try:
+        plans = boxmath.reducing_plans([(int(t.shape[1]), int(t.shape[2])) for t in items], (oh, ow), mode, boxes, sizes, reducing_gap)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"{name}(): {e}") from None
+    images2 = list(same)
+    boxes2 = list(boxes) if boxes is not None else [None] * n
+    for t in items:
+        _require_gpu(t, name)
+    idx = [i for i, p in enumerate(plans) if p is not None]
+    if idx:
+        views = _reduce_many_launch(name, [items[i] for i in idx], c, [plans[i][0] for i in idx], [plans[i][1] for i in idx])
+        for k, i in enumerate(idx):
+            images2[i] = views[k]
+            boxes2[i] = plans[i][2]
+    return images2, (None if all(b is None for b in boxes2) else boxes2)
 
 
 def _check_alpha(name: str, input: torch.Tensor, uint8_mode, out_dtype, out_format, mean, std) -> None:
@@ -1318,6 +1494,45 @@ def _register_torch_ops() -> None:
                                     patch_format=patch_format, pad_to=pad_to, out_dtype=torch.float32 if out_dtype is None else out_dtype,
                                     mean=mean, std=std), "CUDA")
     lib.impl("resize_many_to_patches", _many_patches_meta, "Meta")
+
+    # the ragged Image.reduce: factors one int, one (fx, fy) or 2 N ints (x first); boxes 4 N ints, a full-image box standing for None
+    lib.define("reduce_many(Tensor[] images, int[] factors, int[]? boxes=None) -> Tensor[]")
+
+    def _reduce_many_args(images, factors, boxes):
+        n = len(images)
+        if len(factors) == 1:
+            facs = int(factors[0])
+        elif len(factors) == 2:
+            facs = (int(factors[0]), int(factors[1]))
+        elif len(factors) == 2 * n:
+            facs = [(int(factors[2 * i]), int(factors[2 * i + 1])) for i in range(n)]
+        else:
+            raise ValueError(f"reduce_many(): factors must hold 1 value, one (fx, fy) or 2 values per image ({2 * n}), got {len(factors)}")
+        if boxes is not None and len(boxes) != 4 * n:
+            raise ValueError(f"reduce_many(): boxes must hold 4 values per image ({4 * n}), got {len(boxes)}")
+        return facs, (None if boxes is None else [tuple(int(v) for v in boxes[4 * i:4 * i + 4]) for i in range(n)])
+
+    def _reduce_many_meta(images, factors, boxes=None):
+        facs, bxs = _reduce_many_args(images, factors, boxes)
+        items = [t[0] if t.dim() == 4 else t for t in images]
+        if not items:
+            return []
+        c = int(items[0].shape[0])
+        facs = _reduce_many_factors("reduce_many", facs, len(items))
+        _, interleaved = _many_layout(items, c)
+        outs = []
+        for i, t in enumerate(items):
+            bx = boxmath.check_int_box(bxs[i] if bxs is not None else None, int(t.shape[2]), int(t.shape[1]))
+            rw, rh = boxmath.reduced_size(bx, facs[i])
+            outs.append(torch.empty_strided((c, rh, rw), (1, rw * c, c) if interleaved else (rh * rw, rw, 1), dtype=t.dtype, device=t.device))
+        return outs
+
+    def _reduce_many_cuda(images, factors, boxes=None):
+        facs, bxs = _reduce_many_args(images, factors, boxes)
+        return reduce_many(list(images), facs, boxes=bxs)
+
+    lib.impl("reduce_many", _reduce_many_cuda, "CUDA")
+    lib.impl("reduce_many", _reduce_many_meta, "Meta")
 
     for name, fn in bwds.items():
         lib.impl(name, (lambda f: lambda grad_output, output_size, input_size, align_corners=False:

@@ -32,6 +32,17 @@ bicubic, bfloat16, mean / std; both token formats, both layout classes of the it
 
 Both give the same bits.  No bar is set: the numbers are reported as they come.
 
+--gap, on a workload of its own — N camera-sized images (H in [1080, 3000], W in [1440, 4000], about 1.1 GB), bicubic, reducing_gap 2.0 —
+Pillow's two-step resize for the list, three ways, for RandomResizedCrop boxes to 224 x 224 and for the eval recipe (fit_sizes(shorter=256),
+centred on 224 x 224):
+
+  (a) the per-image loop of cubic_forward(img[None], size, box=, reducing_gap=2.0): the same bytes, the reference for time;
+  (b) resize_many without a gap: other bytes (Pillow's one-step resize), today's long-window path;
+  (c) reduce_many_for_resize + resize_many: four launches whatever N.
+
+(c) must beat (a) with the min .. max ranges of the rounds apart; (b) against (c) is reported whichever way it falls.  Then the reduce
+kernel's own rate: a uniform 64 x 1080 x 1920 x 3 batch at factor (4, 4) through the dense reduce() and through reduce_many, in input GB/s.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
@@ -43,6 +54,7 @@ results into one tensor; (c) writes the batch.
                                                          # the parent commit (twice) and of this one from the same session
   python tools/resize_many_bench.py --patches > out.txt  # only the patch tokens against the per-item composition;
                                                          # profiles/resize_many_patches.txt is this output
+  python tools/resize_many_bench.py --gap > out.txt      # only the reducing_gap step for a list (above); profiles/resize_many_gap.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -263,6 +275,138 @@ def patches(args, torch, aa, images, shapes, timed):
           + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
 
 
+def gap(args, torch, aa, timed):
+    """Pillow's reducing_gap for a list: the per-image loop, resize_many without a gap, and reduce_many_for_resize + resize_many."""
+    from interpolate_antialiasing_amd import boxmath
+
+    g = 2.0
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)]
+    flat = rng.integers(0, 256, sum(h * w * 3 for h, w in shapes), dtype=np.uint8)
+    dev_flat = torch.from_numpy(flat).cuda()
+    images, off = [], 0
+    for h, w in shapes:
+        images.append(dev_flat[off:off + h * w * 3].view(h, w, 3).permute(2, 0, 1))
+        off += h * w * 3
+    brng = np.random.default_rng(SEED + 1)
+    boxes = [random_resized_crop_box(brng, h, w) for h, w in shapes]
+    print(f"resize_many_bench --gap: N = {N} interleaved uint8 images, H in [1080, 3000], W in [1440, 4000], {len(flat) / 1e9:.3f} GB (seed {SEED}); "
+          f"bicubic, reducing_gap {g}; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+
+    eval_sizes, canvas = boxmath.fit_sizes(shapes, shorter=256), (224, 224)
+    eval_batch = torch.empty((N, 3) + canvas, dtype=torch.uint8, device="cuda", memory_format=torch.channels_last)
+
+    def crop_loop():
+        return [aa.cubic_forward(img[None], list(OUT), box=bx, reducing_gap=g) for img, bx in zip(images, boxes)]
+
+    def crop_call():
+        small, b2 = aa.reduce_many_for_resize(images, list(OUT), "bicubic", boxes=boxes, reducing_gap=g)
+        return aa.resize_many(small, list(OUT), "bicubic", boxes=b2)
+
+    def eval_loop():
+        oh, ow = canvas
+        for i, (img, (vh, vw)) in enumerate(zip(images, eval_sizes)):
+            r = aa.cubic_forward(img[None], [vh, vw], reducing_gap=g)[0]
+            py, px = boxmath.center_offset(vh, oh), boxmath.center_offset(vw, ow)
+            y0, y1, x0, x1 = max(0, py), min(oh, py + vh), max(0, px), min(ow, px + vw)
+            eval_batch[i, :, y0:y1, x0:x1] = r[:, y0 - py:y1 - py, x0 - px:x1 - px]
+        return eval_batch
+
+    def eval_call():
+        small, b2 = aa.reduce_many_for_resize(images, list(canvas), "bicubic", sizes=eval_sizes, reducing_gap=g)
+        return aa.resize_many(small, list(canvas), "bicubic", boxes=b2, sizes=eval_sizes, offsets="center")
+
+    tables = (
+        ("one RandomResizedCrop box each -> 224 x 224", boxmath.reducing_plans(shapes, OUT, "bicubic", boxes, None, g),
+         {"a: per-image loop, reducing_gap": crop_loop,
+          "b: resize_many, no gap (other bytes)": lambda: aa.resize_many(images, list(OUT), "bicubic", boxes=boxes),
+          "c: reduce_many_for_resize + resize_many": crop_call}, lambda: torch.cat(crop_loop())),
+        ("eval: fit_sizes(shorter=256) -> 224 x 224 center", boxmath.reducing_plans(shapes, canvas, "bicubic", None, eval_sizes, g),
+         {"a: per-image loop, reducing_gap + slice copy": eval_loop,
+          "b: placed resize_many, no gap (other bytes)": lambda: aa.resize_many(images, list(canvas), "bicubic", sizes=eval_sizes, offsets="center"),
+          "c: reduce_many_for_resize + placed resize_many": eval_call}, lambda: eval_loop().clone()),
+    )
+    for title, plans, contestants, want in tables:
+        for fn in contestants.values():  # warm-up of every contestant (the loop's tables are cached from here on)
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        names = list(contestants)
+        assert torch.equal(contestants[names[2]](), want()), "reduce_many_for_resize + resize_many differs from the per-image loop"
+        times = {k: [] for k in contestants}
+        for _ in range(args.rounds):
+            for k, fn in contestants.items():
+                times[k].append(timed(fn))
+        facs = sorted({p[0] for p in plans if p is not None})
+        print(f"\n{title}")
+        print(f"  items reduced: {sum(1 for p in plans if p is not None)} of {N}; factors {facs[0]} .. {facs[-1]}, {len(facs)} different")
+        stat = {}
+        for k, v in times.items():
+            stat[k] = (statistics.median(v), min(v), max(v))
+            launches = count_launches(torch, contestants[k])
+            print(f"  {k:48s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]   kernel launches per batch: "
+                  f"{launches if launches is not None else 'not measured'}")
+        (ma, la, ha), (mb, lb, hb), (mc, lc, hc) = stat.values()
+        verdict = "PASS: the ranges do not overlap" if hc < la else "FAIL: (c) is not faster than (a) beyond the ranges of the rounds"
+        print(f"  (c) against (a): {ma / mc:.2f} x; (c) at most {hc:.3f} ms, (a) at least {la:.3f} ms: {verdict}")
+        print(f"  (c) against (b): {mb / mc:.2f} x (no bar: (b) computes other bytes; above 1 the gap path is the faster one)")
+
+    reduce_rate(args, torch, aa, timed)
+
+
+def kernel_times(torch, fn, part, calls=12):
+    """Device durations in us of the kernels whose name holds `part`, over `calls` runs of fn(), from torch's profiler; [] where it
+    records no device activity."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+    except ImportError:
+        return []
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        for _ in range(calls):
+            fn()
+        torch.cuda.synchronize()
+    return [e.time_range.elapsed_us() for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and part in e.name]
+
+
+def reduce_rate(args, torch, aa, timed):
+    """The reduce kernel's own rate: the dense kernel is the yardstick.  A call of reduce_many also plans N records on the host, so the
+    kernels' own device times are reported beside the calls' times."""
+    x = torch.randint(0, 256, (N, 1080, 1920, 3), dtype=torch.uint8, device="cuda", generator=torch.Generator(device="cuda").manual_seed(SEED))
+    x = x.permute(0, 3, 1, 2)
+    contestants = {"dense reduce(), factor (4, 4)": lambda: aa.reduce(x, (4, 4)), "reduce_many, factor (4, 4)": lambda: aa.reduce_many(x, (4, 4)),
+                   "dense reduce(), factor (5, 5)": lambda: aa.reduce(x, (5, 5)), "reduce_many, factor (5, 5)": lambda: aa.reduce_many(x, (5, 5))}
+    for fn in contestants.values():
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    for f in ((4, 4), (5, 5)):
+        assert torch.equal(torch.stack(aa.reduce_many(x, f)), aa.reduce(x, f)), "reduce_many differs from reduce"
+    times = {k: [] for k in contestants}
+    for _ in range(args.rounds):
+        for k, fn in contestants.items():
+            times[k].append(timed(fn))
+    print(f"\nthe reduce kernel's own rate: uniform {N} x 1080 x 1920 x 3 interleaved, {x.numel() / 1e6:.1f} MB in (library: {os.path.basename(_lib_path())})")
+    print("  (5, 5) runs the run-time-fx form in both kernels; ms per call, then the kernel's own device time and its input GB/s: median [min .. max]")
+    stat = {}
+    for k, v in times.items():
+        kt = kernel_times(torch, contestants[k], "reduce")
+        stat[k] = (statistics.median(kt), min(kt), max(kt)) if kt else None
+        line = f"  {k:32s} call {statistics.median(v):8.4f} [{min(v):8.4f} .. {max(v):8.4f}] ms"
+        if kt:
+            m, lo, hi = stat[k]
+            line += f"   kernel {m:8.1f} [{lo:8.1f} .. {hi:8.1f}] us   {x.numel() / m / 1e3:8.1f} [{x.numel() / hi / 1e3:8.1f} .. {x.numel() / lo / 1e3:8.1f}] GB/s"
+        else:
+            line += "   kernel time not measured"
+        print(line)
+    names = list(contestants)
+    for d, m in ((names[0], names[1]), (names[2], names[3])):
+        if stat[d] and stat[m]:
+            apart = stat[m][1] > stat[d][2] or stat[m][2] < stat[d][1]
+            print(f"  {m} against {d}: {stat[m][0] / stat[d][0]:.3f} x the kernel time; the ranges {'do not overlap' if apart else 'overlap'}")
+
+
 def _lib_path():
     from interpolate_antialiasing_amd import _lib
 
@@ -279,6 +423,8 @@ def main():
     ap.add_argument("--float-only", action="store_true")
     ap.add_argument("--placed", action="store_true", help="only the placed call (eval and letterbox) against the per-image loop")
     ap.add_argument("--patches", action="store_true", help="only resize_many_to_patches against the per-item composition")
+    ap.add_argument("--gap", action="store_true", help="only Pillow's reducing_gap for a list: the loop, resize_many without a gap, and the new step")
+    ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
     ap.add_argument("--trace-float", action="store_true", help="with --trace: the calls are resize_many_to_float (bfloat16, nchw, mean / std, flips)")
@@ -357,6 +503,9 @@ def main():
         return
     if args.patches:
         patches(args, torch, aa, images, shapes, timed)
+        return
+    if args.gap:
+        (reduce_rate if args.rate_only else gap)(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
