@@ -334,15 +334,25 @@ int aa_unpremultiply_u8(void *img_dev, int layout, int64_t N, int64_t C, int64_t
  * element is not looked at.  C is 1..4.  Added without an ABI version change (additive).
  * aa_many_image.flags (the field was `reserved`, always 0): AA_MANY_FLIP_X mirrors that item's output left to right (RandomHorizontalFlip);
  * any other bit makes aa_many_plan return AA_ERR_BAD_SHAPE.  Only aa_resample_many_u8_to_float serves a plan in which an item flips:
- * aa_resample_many_u8 returns AA_ERR_BAD_SHAPE for it (its kernel does not flip).  Zero-initialised callers see no change. */
+ * aa_resample_many_u8 returns AA_ERR_BAD_SHAPE for it (its kernel does not flip).  Zero-initialised callers see no change.
+ * AA_MANY_PREMUL_ALPHA resizes that item the way Pillow's Image.resize resizes an RGBA / LA image (AA_FLAG_PREMUL_ALPHA above, for a
+ * list): C must be 2 or 4 with STRAIGHT alpha in the last channel, AA_ERR_BAD_SHAPE from aa_many_plan / aa_many_plan_placed otherwise.
+ * The colour bytes are premultiplied by alpha as the horizontal pass reads them, the intermediate holds horizontally filtered
+ * premultiplied bytes, and the vertical pass converts every output pixel back with its own resampled alpha; a placed plan's fill is
+ * written as given, never converted.  An item whose size asked for (its own [vH, vW]; [oH, oW] in a plain plan) equals its [H, W] and
+ * whose box is absent or the whole image BY VALUE is Pillow's copy: the plan serves it without the conversions, so it comes out
+ * unchanged.  The flag changes nothing else of a plan (hulls, ksizes, offsets, workspace), combines with AA_MANY_FLIP_X, and is served
+ * by aa_resample_many_u8 and aa_resample_many_u8_to_float, plain and placed, in both layout classes, in the same three launches;
+ * aa_many_plan_patches returns AA_ERR_BAD_SHAPE for it, and aa_resample_many_u8_to_patches for a block that carries it. */
 #define AA_MANY_FLIP_X 1
+#define AA_MANY_PREMUL_ALPHA 2
 typedef struct aa_many_image {
   const void *data_dev;  /* byte (row 0, column 0, channel 0) of the image */
   int64_t H, W;
   int64_t stride_row, stride_px, stride_ch; /* in BYTES */
   double box[4];         /* x0, y0, x1, y1 — Pillow's order, x first; rounded to float32 by the plan, as Pillow's C does */
   int32_t has_box;       /* 0: the whole image (box[] is not read) */
-  int32_t flags;         /* 0, or AA_MANY_FLIP_X */
+  int32_t flags;         /* 0, or any of AA_MANY_FLIP_X, AA_MANY_PREMUL_ALPHA */
 } aa_many_image;
 /* Bytes of the packed descriptor block for n items. */
 size_t aa_many_desc_bytes(int64_t n);

@@ -135,6 +135,7 @@ class ReduceManyItem(ctypes.Structure):
 
 
 MANY_FLIP_X = 1     # aa_many_image.flags: mirror the item's output left to right (aa_resample_many_u8_to_float only)
+MANY_PREMUL_ALPHA = 2  # aa_many_image.flags: Pillow's RGBA / LA resize of that item (C 2 or 4, straight alpha last; not for patch plans)
 PATCH_CPP, PATCH_PPC = 0, 1  # aa_resample_many_u8_to_patches: token vector [C, ph, pw] or [ph, pw, C]
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 

@@ -17,7 +17,8 @@ struct AAManyHeader {
   int64_t hunits;     // work units of the horizontal pass, all items: hunit_prefix[n]
   int64_t ws_bytes;   // table arena + intermediates
   int64_t reserved[2]; // [0]: bit 0 a placed plan (AAManyPlace records follow the prefix sums), bit 1 a patch plan (its tail follows
-                       // them); [1]: a placed plan's fill, byte c = channel c's
+                       // them), bit 2 some item has bit 1 of its `reserved` (the launches take the alpha instantiations; never with
+                       // bit 1); [1]: a placed plan's fill, byte c = channel c's
 };
 static_assert(sizeof(AAManyHeader) == 64, "descriptor header is 64 bytes");
 
@@ -33,6 +34,8 @@ struct AAManyItem {
   int32_t ksize_h, ksize_w;
   int32_t box_on;                     // 1: the scale is the FLOAT difference of the interval over the output size (a box); 0: in / out
   int32_t reserved;                   // bit 0: AA_MANY_FLIP_X, the converting vertical pass writes the item mirrored left to right
+                                      // bit 1: AA_MANY_PREMUL_ALPHA and not Pillow's copy (size asked for == [H, W], no box or the
+                                      // whole image): the horizontal pass premultiplies what it stages, the vertical passes convert back
 };
 static_assert(sizeof(AAManyItem) == 112, "descriptor item is 112 bytes");
 

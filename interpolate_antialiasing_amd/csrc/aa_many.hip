@@ -11,12 +11,16 @@
 // A PLACED plan (template parameter PL) gives every item its own output size and a place on the canvas: the tables hold the covered
 // part of the item's own resize only, the horizontal pass computes the covered columns only, and the vertical pass, still one grid over
 // the whole canvas, writes the fill wherever the item is not.  The plain instantiations take none of it.
+// An ALPHA plan (template parameter AL: some item asked for AA_MANY_PREMUL_ALPHA and is not Pillow's copy) resizes such items the way
+// Pillow resizes RGBA / LA: the horizontal pass premultiplies the colour bytes it stages, the intermediate holds filtered premultiplied
+// bytes, and the vertical passes convert every output pixel back with its own resampled alpha.  Same plan, same workspace, same launches.
 // The host planner (aa_many_plan_host) computes every hull, ksize and offset with the same double arithmetic the table kernel uses, so
 // nothing comes back from the device: no header read-back, no atomicMax, no synchronisation, no allocation.
 
 #include <math.h>
 #include <string.h>
 
+#include "aa_alpha.h"
 #include "aa_many.h"
 #include "aa_pil_coeffs.h"
 
@@ -76,10 +80,44 @@ __global__ void __launch_bounds__(256) many_tables(const AAManyItem *items, cons
 constexpr int kChunkDwords = 2048;
 constexpr int kChunkBytes = 4 * kChunkDwords;
 
+// The four bytes at a4 + 4 i of a staged segment [a, a_end): one dword load where all four lie inside (at any alignment: global memory
+// serves an unaligned dword), else assembled from byte loads (bytes outside the segment read as 0 and are never looked at).
+__device__ inline uint32_t stage_dword(const uint8_t *a4, const uint8_t *a, const uint8_t *a_end, int i) {
+  const uint8_t *p = a4 + 4 * (int64_t)i;
+  if (p >= a && p + 4 <= a_end) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+  }
+  uint32_t v = 0;
+  for (int b = 0; b < 4; b++)
+    if (p + b >= a && p + b < a_end) v |= (uint32_t)p[b] << (8 * b);
+  return v;
+}
+
+// Straight -> premultiplied for the pixels of one dword (aa_alpha.h): two LA pixels; four bytes of a colour plane by the four bytes of
+// the alpha plane at the same columns.
+__device__ inline uint32_t premul_la2(uint32_t v) {
+  return (uint32_t)aa_premul8((int)(v & 255u), (int)((v >> 8) & 255u)) | ((uint32_t)aa_premul8((int)((v >> 16) & 255u), (int)(v >> 24)) << 16) |
+         (v & 0xff00ff00u);
+}
+__device__ inline uint32_t premul_planes4(uint32_t v, uint32_t a) {
+  return (uint32_t)aa_premul8((int)(v & 255u), (int)(a & 255u)) | ((uint32_t)aa_premul8((int)((v >> 8) & 255u), (int)((a >> 8) & 255u)) << 8) |
+         ((uint32_t)aa_premul8((int)((v >> 16) & 255u), (int)((a >> 16) & 255u)) << 16) | ((uint32_t)aa_premul8((int)(v >> 24), (int)(a >> 24)) << 24);
+}
+
 // PL: the item's own strip count, its covered columns [0, mw) of the table, and its own row pitch and lead in the intermediate.
-template <int E, bool PL>
+// AL (E = 1, 2, 4; the plan's header says some item has bit 1 of `reserved`): a workgroup of such an item stages its chunk PREMULTIPLIED
+// (Pillow's RGBA -> RGBa, LA -> La), once per pixel and in LDS only, so the intermediate holds filtered premultiplied bytes.  Where the
+// pixels of the row are aligned to the staged dwords (E = 4: shift 0; E = 2: shift even) the staging lane converts its dword in registers
+// on the way in; otherwise the chunk is staged as it lies and converted in place, one lane per pixel with byte accesses, behind one more
+// barrier.  A colour plane's staging lane loads, beside its dword, the four alpha bytes of the same columns (plane planes - 1, the same
+// row: an unaligned dword load where the two rows are misaligned to each other) and multiplies in registers: no second buffer, no
+// barrier.  The alpha plane's own workgroups, and items without the bit, run the plain code.
+template <int E, bool PL, bool AL>
 __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem *items, const AAManyPlace *places, const int64_t *prefix, char *ws,
                                                                 int n, int oW, int planes) {
+  static_assert(!AL || E == 1 || E == 2 || E == 4, "alpha is the last of 2 or 4 channels");
   __shared__ uint32_t seg[kChunkDwords];
   const int64_t unit = blockIdx.x;
   int lo = 0, hi = n;  // the item whose units hold `unit`: prefix[lo] <= unit < prefix[lo + 1]
@@ -115,6 +153,9 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
   if (seg0 < 0) seg0 = 0;
   if (seg1 > hull_w) seg1 = hull_w;
   const uint8_t *rowp = it.src + (int64_t)plane * it.plane_stride + (int64_t)(it.oy + row) * it.row_stride + (int64_t)it.ox * E;
+  // AL: this workgroup premultiplies what it stages; aoff, a colour plane's distance to the same byte of the alpha plane
+  const bool al = AL && (it.reserved & 2) != 0 && (E > 1 || plane < planes - 1);
+  const int64_t aoff = AL && E == 1 ? (int64_t)(planes - 1 - plane) * it.plane_stride : 0;
 
   const int j = threadIdx.x;
   const int x = x0 + j / E, c = j % E;
@@ -137,17 +178,38 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
     const uint8_t *a4 = a - shift;
     const int ndw = (shift + (c1 - c0) * E + 3) >> 2;
     __syncthreads();  // (the previous chunk has been consumed)
-    for (int i = j; i < ndw; i += AA_MANY_STRIP * E) {
-      const uint8_t *p = a4 + 4 * (int64_t)i;
-      uint32_t v;
-      if (p >= a && p + 4 <= a_end) {
-        v = *(const uint32_t *)p;
+    if (AL && al) {  // (uniform per workgroup)
+      constexpr int NT = AA_MANY_STRIP * E;
+      if (E == 1) {  // (the alpha bytes of a staged dword's columns: aoff further on, at whatever alignment that is)
+        for (int i = j; i < ndw; i += NT) seg[i] = premul_planes4(stage_dword(a4, a, a_end, i), stage_dword(a4 + aoff, a + aoff, a_end + aoff, i));
+      } else if (shift % E == 0) {  // (every pixel lies within one staged dword)
+        for (int i = j; i < ndw; i += NT) {
+          const uint32_t v = stage_dword(a4, a, a_end, i);
+          seg[i] = E == 4 ? aa_premul_px(v) : premul_la2(v);
+        }
       } else {
-        v = 0;
-        for (int b = 0; b < 4; b++)
-          if (p + b >= a && p + b < a_end) v |= (uint32_t)p[b] << (8 * b);
+        for (int i = j; i < ndw; i += NT) seg[i] = stage_dword(a4, a, a_end, i);
+        __syncthreads();
+        uint8_t *ldsw = (uint8_t *)seg;
+        for (int p = j; p < c1 - c0; p += NT) {  // (a lane touches the bytes of its own pixel only)
+          const int at = shift + p * E;
+          const int av = ldsw[at + E - 1];
+          for (int ch = 0; ch < E - 1; ch++) ldsw[at + ch] = (uint8_t)aa_premul8(ldsw[at + ch], av);
+        }
       }
-      seg[i] = v;
+    } else {  // (stage_dword, written out as it always was: the instantiations without alpha keep the code they had)
+      for (int i = j; i < ndw; i += AA_MANY_STRIP * E) {
+        const uint8_t *p = a4 + 4 * (int64_t)i;
+        uint32_t v;
+        if (p >= a && p + 4 <= a_end) {
+          v = *(const uint32_t *)p;
+        } else {
+          v = 0;
+          for (int b = 0; b < 4; b++)
+            if (p + b >= a && p + b < a_end) v |= (uint32_t)p[b] << (8 * b);
+        }
+        seg[i] = v;
+      }
     }
     __syncthreads();
     if (active) {
@@ -192,19 +254,51 @@ __device__ inline Sums4 vtap_sums(const AAManyItem &it, const char *ws, int out,
   return s;
 }
 
+// AL, an item with bit 1 of `reserved`: the intermediate holds premultiplied bytes, so the four clipped bytes w of a lane are converted
+// back (Pillow's RGBa -> RGBA, La -> LA; aa_alpha.h) with the resampled alpha of their own output pixel: in the lane for interleaved
+// pixels (one RGBA pixel, or two LA pixels: a row's bytes start on a dword of the canvas and E divides 4), and for a colour plane from a
+// second walk down the same window of the alpha plane, plane planes - 1, at the same columns.  The alpha plane's bytes are final.
+__device__ inline uint32_t unpremul_px(uint32_t w) {
+  const int a = (int)(w >> 24);
+  return (uint32_t)aa_unpremul8((int)(w & 255u), a) | ((uint32_t)aa_unpremul8((int)((w >> 8) & 255u), a) << 8) |
+         ((uint32_t)aa_unpremul8((int)((w >> 16) & 255u), a) << 16) | (w & 0xff000000u);
+}
+__device__ inline uint32_t unpremul_la2(uint32_t w) {
+  return (uint32_t)aa_unpremul8((int)(w & 255u), (int)((w >> 8) & 255u)) | ((uint32_t)aa_unpremul8((int)((w >> 16) & 255u), (int)(w >> 24)) << 16) |
+         (w & 0xff00ff00u);
+}
+__device__ inline uint32_t unpremul_planes4(uint32_t w, uint32_t a) {
+  return (uint32_t)aa_unpremul8((int)(w & 255u), (int)(a & 255u)) | ((uint32_t)aa_unpremul8((int)((w >> 8) & 255u), (int)((a >> 8) & 255u)) << 8) |
+         ((uint32_t)aa_unpremul8((int)((w >> 16) & 255u), (int)((a >> 16) & 255u)) << 16) |
+         ((uint32_t)aa_unpremul8((int)(w >> 24), (int)(a >> 24)) << 24);
+}
+__device__ inline uint32_t straight_bytes(const AAManyItem &it, const char *ws, int out, int t, int plane, int planes, int E, int64_t pitch,
+                                          int64_t at, uint32_t w) {
+  if (E == 4) return unpremul_px(w);
+  if (E == 2) return unpremul_la2(w);
+  if (plane == planes - 1) return w;
+  const Sums4 a = vtap_sums(it, ws, out, t, planes - 1, pitch, at);
+  return unpremul_planes4(w, pack4_clip8(a.s0, a.s1, a.s2, a.s3));
+}
+
 // PL, the four bytes [b, b + 4) of canvas row y, packed: a row the item does not cover, or four bytes beside its columns, are the fill and
 // read nothing; otherwise the four sums (the dword of the intermediate that holds the canvas dword: its rows are led so), each byte then
 // the sum or the fill, because a dword may straddle the item's edge.  What the dword holds beyond the covered columns lies inside the
-// item's own rows of the intermediate and is not used.
-__device__ inline uint32_t placed_bytes(const AAManyItem &it, const AAManyPlace &pl, const char *ws, uint32_t fill, int plane, int E, int y, int b) {
+// item's own rows of the intermediate and is not used.  AL: the sums' bytes are converted before the fill is mixed in, so in a dword
+// that holds a fill pixel and an item pixel (LA at an odd dx) only the item's is converted; the fill is written as given.
+template <bool AL>
+__device__ inline uint32_t placed_bytes(const AAManyItem &it, const AAManyPlace &pl, const char *ws, uint32_t fill, int plane, int planes, int E, int y,
+                                        int b) {
   uint32_t fw = 0;
 #pragma unroll
   for (int q = 0; q < 4; q++) fw |= ((fill >> (8 * (E == 1 ? plane : (b + q) % E))) & 255u) << (8 * q);
   const int ty = y - pl.dy;
   const int cb0 = pl.dx * E, cb1 = cb0 + pl.mw * E;  // the covered bytes of a canvas row
   if (ty < 0 || ty >= pl.mh || b + 4 <= cb0 || b >= cb1) return fw;
-  const Sums4 s = vtap_sums(it, ws, pl.mh, ty, plane, aa_many_placed_pitch(pl.dx, pl.mw, E), b - (cb0 & ~3));
-  const uint32_t sw = pack4_clip8(s.s0, s.s1, s.s2, s.s3);  // (`clip8(a) | clip8(b) << 8 ...` of one word is what hipcc miscompiles: aa_common.h)
+  const int64_t pitch = aa_many_placed_pitch(pl.dx, pl.mw, E);
+  const Sums4 s = vtap_sums(it, ws, pl.mh, ty, plane, pitch, b - (cb0 & ~3));
+  uint32_t sw = pack4_clip8(s.s0, s.s1, s.s2, s.s3);  // (`clip8(a) | clip8(b) << 8 ...` of one word is what hipcc miscompiles: aa_common.h)
+  if (AL && (it.reserved & 2)) sw = straight_bytes(it, ws, pl.mh, ty, plane, planes, E, pitch, b - (cb0 & ~3), sw);
   uint32_t mask = 0;
 #pragma unroll
   for (int q = 0; q < 4; q++)
@@ -212,7 +306,7 @@ __device__ inline uint32_t placed_bytes(const AAManyItem &it, const AAManyPlace 
   return (sw & mask) | (fw & ~mask);
 }
 
-template <bool PL>
+template <bool PL, bool AL>
 __global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const AAManyPlace *places, const char *ws, uint8_t *out, int oH, int oW,
                                                   int planes, int E, int nstrips, uint32_t fill) {
   int64_t u = blockIdx.x;
@@ -227,7 +321,12 @@ __global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const
   if (b >= rowbytes) return;
   uint32_t r0b, r1b, r2b, r3b;
   if (PL) {
-    const uint32_t w = placed_bytes(it, places[u / planes], ws, fill, plane, E, y, b);
+    const uint32_t w = placed_bytes<AL>(it, places[u / planes], ws, fill, plane, planes, E, y, b);
+    r0b = w & 255u; r1b = (w >> 8) & 255u; r2b = (w >> 16) & 255u; r3b = w >> 24;
+  } else if (AL && (it.reserved & 2)) {
+    const int64_t pitch = aa_many_inter_pitch(oW, E);
+    const Sums4 s = vtap_sums(it, ws, oH, y, plane, pitch, b);
+    const uint32_t w = straight_bytes(it, ws, oH, y, plane, planes, E, pitch, b, pack4_clip8(s.s0, s.s1, s.s2, s.s3));
     r0b = w & 255u; r1b = (w >> 8) & 255u; r2b = (w >> 16) & 255u; r3b = w >> 24;
   } else {
     const Sums4 s = vtap_sums(it, ws, oH, y, plane, aa_many_inter_pitch(oW, E), b);
@@ -272,7 +371,7 @@ __device__ inline float pick4(const float (&a)[4], int c) { return c == 0 ? a[0]
 template <int E> constexpr int kVLanes = E == 3 ? 192 : 256;   // lanes of a workgroup: 4 bytes each, a whole number of pixels together
 template <int E> constexpr int kVPixels = kVLanes<E> * 4 / E;  // 1024, 512, 256, 256
 
-template <typename T, int E, bool XL, bool PL>
+template <typename T, int E, bool XL, bool PL, bool AL>
 __global__ void __launch_bounds__(kVLanes<E>) many_vpass_float(const AAManyItem *items, const AAManyPlace *places, const char *ws, T *out, int oH,
                                                                int oW, int planes, int nstrips, const ManyConvert cv, uint32_t fill) {
   constexpr int PX = kVPixels<E>;
@@ -294,7 +393,12 @@ __global__ void __launch_bounds__(kVLanes<E>) many_vpass_float(const AAManyItem 
 
   float f[4];
   if (PL) {  // (the piece starts on a dword of the canvas row: kVPixels<E> * E is a multiple of 4)
-    const uint32_t w = placed_bytes(it, places[n], ws, fill, plane, E, y, x0 * E + 4 * j);
+    const uint32_t w = placed_bytes<AL>(it, places[n], ws, fill, plane, planes, E, y, x0 * E + 4 * j);
+    f[0] = (float)(w & 255u); f[1] = (float)((w >> 8) & 255u); f[2] = (float)((w >> 16) & 255u); f[3] = (float)(w >> 24);
+  } else if (AL && (it.reserved & 2)) {
+    const int64_t pitch = aa_many_inter_pitch(oW, E), at = (int64_t)x0 * E + 4 * j;
+    const Sums4 s = vtap_sums(it, ws, oH, y, plane, pitch, at);
+    const uint32_t w = straight_bytes(it, ws, oH, y, plane, planes, E, pitch, at, pack4_clip8(s.s0, s.s1, s.s2, s.s3));
     f[0] = (float)(w & 255u); f[1] = (float)((w >> 8) & 255u); f[2] = (float)((w >> 16) & 255u); f[3] = (float)(w >> 24);
   } else {
     const Sums4 s = vtap_sums(it, ws, oH, y, plane, aa_many_inter_pitch(oW, E), (int64_t)x0 * E + 4 * j);
@@ -368,7 +472,7 @@ __global__ void __launch_bounds__(kVLanes<E>) many_vpass_patches(const AAManyIte
   if (nb <= 0) return;
   const bool flip = (it.reserved & 1) != 0;
 
-  const uint32_t w = placed_bytes(it, pl, ws, 0u, plane, E, y, x0 * E + 4 * j);  // (the item covers its canvas: never the fill)
+  const uint32_t w = placed_bytes<false>(it, pl, ws, 0u, plane, planes, E, y, x0 * E + 4 * j);  // (the item covers its canvas: never the fill)
   const float f[4] = {(float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), (float)(w >> 24)};
 
   const int gy = y / ph, py = y - gy * ph;
@@ -444,14 +548,15 @@ static int many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, i
   AAManyPlace *pls = (AAManyPlace *)(prefix + n + 1);  // (a placed plan only)
   size_t off = 0;  // the arena first, then the intermediates
   int64_t units = 0;
-  int flips = 0;
+  int flips = 0, alphas = 0;
   for (int64_t i = 0; i < n; i++) {
     const aa_many_image &im = images[i];
     AAManyItem it;
     memset(&it, 0, sizeof(it));
     if (!im.data_dev) return AA_ERR_NULL;
     if (im.H <= 0 || im.W <= 0 || im.H > kMax || im.W > kMax) return AA_ERR_BAD_SHAPE;
-    if (im.flags & ~AA_MANY_FLIP_X) return AA_ERR_BAD_SHAPE;
+    if (im.flags & ~(AA_MANY_FLIP_X | AA_MANY_PREMUL_ALPHA)) return AA_ERR_BAD_SHAPE;
+    if ((im.flags & AA_MANY_PREMUL_ALPHA) && (own_canvas || (C != 2 && C != 4))) return AA_ERR_BAD_SHAPE;  // (straight alpha is the last of 2 or 4)
     // (the stride of an axis of one element never matters)
     if (layout == AA_NHWC ? ((C > 1 && im.stride_ch != 1) || (im.W > 1 && im.stride_px != C)) : (im.W > 1 && im.stride_px != 1)) return AA_ERR_STRIDES;
     double x0 = 0.0, y0 = 0.0, x1 = (double)im.W, y1 = (double)im.H;
@@ -496,6 +601,12 @@ static int many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, i
     it.box_on = on;
     it.reserved = im.flags & AA_MANY_FLIP_X;
     flips |= it.reserved;
+    // Image.resize returns self.copy() before it looks at the mode where the size asked for is the image's and the box is the whole
+    // image: such an item is never premultiplied (the round trip loses colour at low alpha); its windows are one tap of weight 1
+    if ((im.flags & AA_MANY_PREMUL_ALPHA) && !(on == 0 && vH == im.H && vW == im.W)) {
+      it.reserved |= 2;
+      alphas = 1;
+    }
     it.tab_h = (int64_t)off;
     off += aa_many_table_bytes(mh, kh);
     it.tab_w = (int64_t)off;
@@ -521,6 +632,7 @@ static int many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, i
     hd->reserved[0] = 1;
     for (int c = 0; fill && c < 4; c++) hd->reserved[1] |= (int64_t)fill[c] << (8 * c);
   }
+  if (alphas) hd->reserved[0] |= 4;
   *workspace_bytes = off;
   return AA_OK;
 }
@@ -589,11 +701,15 @@ static int many_check(const AAManyHeader *hd, const void *desc_dev, int64_t n, i
   return AA_OK;
 }
 
-template <int E, bool PL>
+// Some item of the plan is resampled premultiplied (AAManyItem.reserved bit 1): the AL instantiations.  The planner sets the bit for
+// C = 2 or 4 only.
+static bool many_alpha(const AAManyHeader *hd) { return (hd->reserved[0] & 4) != 0 && (hd->C == 2 || hd->C == 4); }
+
+template <int E, bool PL, bool AL>
 static void launch_hpass(const AAManyHeader *hd, const AAManyItem *items, const AAManyPlace *places, const int64_t *prefix, char *ws, int64_t n,
                          int64_t oW, int planes, hipStream_t stream) {
   if (hd->hunits == 0) return;  // (a placed plan whose items all lie off the canvas)
-  hipLaunchKernelGGL((many_hpass<E, PL>), dim3((unsigned)hd->hunits), dim3(AA_MANY_STRIP * E), 0, stream, items, places, prefix, ws, (int)n, (int)oW,
+  hipLaunchKernelGGL((many_hpass<E, PL, AL>), dim3((unsigned)hd->hunits), dim3(AA_MANY_STRIP * E), 0, stream, items, places, prefix, ws, (int)n, (int)oW,
                      planes);
 }
 
@@ -603,11 +719,19 @@ static void launch_many_tables_hpass(const AAManyHeader *hd, const AAManyItem *i
   const int64_t tthreads = n * (oH + oW);
   hipLaunchKernelGGL(many_tables<PL>, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, items, places, ws, n, (int)oH, (int)oW,
                      hd->filter);
+  if (many_alpha(hd)) {  // (C is 2 or 4: E is 1, 2 or 4)
+    switch (E) {
+      case 1: launch_hpass<1, PL, true>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+      case 2: launch_hpass<2, PL, true>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+      default: launch_hpass<4, PL, true>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    }
+    return;
+  }
   switch (E) {
-    case 1: launch_hpass<1, PL>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
-    case 2: launch_hpass<2, PL>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
-    case 3: launch_hpass<3, PL>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
-    default: launch_hpass<4, PL>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    case 1: launch_hpass<1, PL, false>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    case 2: launch_hpass<2, PL, false>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    case 3: launch_hpass<3, PL, false>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    default: launch_hpass<4, PL, false>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
   }
 }
 
@@ -631,14 +755,15 @@ int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, in
   const AAManyPlace *places = many_places(hd, prefix, n);
   const int vstrips = (int)((oW * E + AA_MANY_VBYTES - 1) / AA_MANY_VBYTES);
   const dim3 vgrid((unsigned)(n * planes * oH * vstrips));
+  const bool al = many_alpha(hd);
   if (places) {
     launch_many_tables_hpass<true>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
-    hipLaunchKernelGGL(many_vpass<true>, vgrid, dim3(256), 0, stream, items, places, (const char *)ws, (uint8_t *)out_dev, (int)oH, (int)oW, planes, E,
-                       vstrips, (uint32_t)hd->reserved[1]);
+    hipLaunchKernelGGL((al ? many_vpass<true, true> : many_vpass<true, false>), vgrid, dim3(256), 0, stream, items, places, (const char *)ws,
+                       (uint8_t *)out_dev, (int)oH, (int)oW, planes, E, vstrips, (uint32_t)hd->reserved[1]);
   } else {
     launch_many_tables_hpass<false>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
-    hipLaunchKernelGGL(many_vpass<false>, vgrid, dim3(256), 0, stream, items, places, (const char *)ws, (uint8_t *)out_dev, (int)oH, (int)oW, planes, E,
-                       vstrips, 0u);
+    hipLaunchKernelGGL((al ? many_vpass<false, true> : many_vpass<false, false>), vgrid, dim3(256), 0, stream, items, places, (const char *)ws,
+                       (uint8_t *)out_dev, (int)oH, (int)oW, planes, E, vstrips, 0u);
   }
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
@@ -654,19 +779,28 @@ struct ManyFloatArgs {
   int planes;
   ManyConvert cv;
   uint32_t fill;
+  bool alpha;  // many_alpha() of the plan
   hipStream_t stream;
 };
 
-template <typename T, int E, bool XL>
-static void launch_vpass_float(const ManyFloatArgs &a) {
+template <typename T, int E, bool XL, bool AL>
+static void launch_vpass_float_al(const ManyFloatArgs &a) {
   const int nstrips = (int)((a.oW + kVPixels<E> - 1) / kVPixels<E>);
   const dim3 grid((unsigned)(a.n * a.planes * a.oH * nstrips));
   if (a.places)
-    hipLaunchKernelGGL((many_vpass_float<T, E, XL, true>), grid, dim3(kVLanes<E>), 0, a.stream, a.items, a.places, a.ws, (T *)a.out, (int)a.oH, (int)a.oW,
-                       a.planes, nstrips, a.cv, a.fill);
+    hipLaunchKernelGGL((many_vpass_float<T, E, XL, true, AL>), grid, dim3(kVLanes<E>), 0, a.stream, a.items, a.places, a.ws, (T *)a.out, (int)a.oH,
+                       (int)a.oW, a.planes, nstrips, a.cv, a.fill);
   else
-    hipLaunchKernelGGL((many_vpass_float<T, E, XL, false>), grid, dim3(kVLanes<E>), 0, a.stream, a.items, a.places, a.ws, (T *)a.out, (int)a.oH,
+    hipLaunchKernelGGL((many_vpass_float<T, E, XL, false, AL>), grid, dim3(kVLanes<E>), 0, a.stream, a.items, a.places, a.ws, (T *)a.out, (int)a.oH,
                        (int)a.oW, a.planes, nstrips, a.cv, 0u);
+}
+
+template <typename T, int E, bool XL>
+static void launch_vpass_float(const ManyFloatArgs &a) {
+  if constexpr (E != 3) {
+    if (a.alpha) return launch_vpass_float_al<T, E, XL, true>(a);
+  }
+  launch_vpass_float_al<T, E, XL, false>(a);
 }
 
 template <typename T>
@@ -705,7 +839,7 @@ int aa_launch_many_float(const void *desc_host, const void *desc_dev, int64_t n,
   const AAManyPlace *places = many_places(hd, prefix, n);
   if (places) launch_many_tables_hpass<true>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
   else launch_many_tables_hpass<false>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
-  const ManyFloatArgs a = {items, places, ws, out_dev, n, oH, oW, planes, cv, (uint32_t)hd->reserved[1], stream};
+  const ManyFloatArgs a = {items, places, ws, out_dev, n, oH, oW, planes, cv, (uint32_t)hd->reserved[1], many_alpha(hd), stream};
   if (out_elem == AA_F16) launch_vpass_float_e<f16_t>(E, xl, a);
   else if (out_elem == AA_BF16) launch_vpass_float_e<bf16_t>(E, xl, a);
   else launch_vpass_float_e<float>(E, xl, a);
@@ -749,7 +883,7 @@ static void launch_vpass_patches_e(int E, bool ppc, const ManyPatchArgs &a) {
 int aa_launch_many_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int out_elem,
                            int ppc, int normalize, const float *mean, const float *std, hipStream_t stream) {
   const AAManyHeader *hd = (const AAManyHeader *)desc_host;
-  if (hd->magic != AA_MANY_MAGIC || (hd->reserved[0] & 3) != 3 || hd->n < 0 || hd->C < 1 || hd->C > 4) return AA_ERR_BAD_SHAPE;  // not a patch plan
+  if (hd->magic != AA_MANY_MAGIC || (hd->reserved[0] & 7) != 3 || hd->n < 0 || hd->C < 1 || hd->C > 4) return AA_ERR_BAD_SHAPE;  // not a patch plan
   const int64_t n = hd->n, C = hd->C;
   const int layout = hd->layout;
   if (n == 0) return AA_OK;

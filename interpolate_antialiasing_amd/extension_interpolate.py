@@ -38,12 +38,12 @@ Differences, all additive:
     ``Image.thumbnail`` does with 2.0.  The result is Pillow's ``reducing_gap`` result, not the plain one.  Two launches plus the table
     build, through a temporary uint8 tensor in the input's layout;
   * ``reduce(input, factor, box=None, alpha=False)``: Pillow's ``Image.reduce`` (integer box means), bit-exact;
-  * ``resize_many_to_float(images, output_size, mode, boxes=None, flips=None, out_dtype=, out_format=, mean=, std=)``: ``resize_many``
+  * ``resize_many_to_float(images, output_size, mode, boxes=None, flips=None, out_dtype=, out_format=, mean=, std=, alpha=False)``: ``resize_many``
     and the float conversion, normalisation, layout change and horizontal flips a model needs after it, in the same three launches.
   * ``resize_many_to_patches(images, patch, mode, sizes=, patch_format=, pad_to=, ...)``: the same list, every item resized to its own
     multiple of the patch, converted and cut into ViT patch tokens: one packed [sum T_i, C * ph * pw] matrix (or a zero-padded
     [N, L, C * ph * pw] one) from the same three launches;
-  * ``resize_many(images, output_size, mode, boxes=None)``: a LIST of uint8 images of different sizes, each with its own box, into one
+  * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
     output size and a place on the [oH, oW] canvas (Resize + CenterCrop, letterbox): cropped or padded, only the covered part computed;
@@ -444,13 +444,19 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
     ``Resize(256)`` + ``CenterCrop(224)`` is ``sizes=boxmath.fit_sizes(shapes, shorter=256), offsets="center"`` on a 224 x 224 canvas; a
     letterbox is ``sizes=boxmath.fit_sizes(shapes, longer=640), offsets="center", fill=114`` on a 640 x 640 one.
 
+    ``alpha=True`` (2 or 4 channels, STRAIGHT alpha last): every item is resized the way Pillow resizes an "LA" / "RGBA" image — colour
+    premultiplied by alpha, resampled, converted back with the resampled alpha — so ``y[i]`` is ``<mode>_forward(images[i][None], ...,
+    box=boxes[i], alpha=True)[0]``, and with placement ``R_i`` above is the RGBA / LA resize.  ``fill`` is written as given (straight
+    values, never converted).  An item whose own size equals its image's and whose box is None or the whole image is Pillow's copy and
+    comes out unchanged.  Same three launches, same workspace: the horizontal pass premultiplies as it reads, the vertical pass converts back.
+
     Three launches and one non-blocking copy of a packed descriptor whatever N; every hull, ksize and offset is host arithmetic
-    (aa_many_plan), so nothing is read back, and the table caches are neither read nor written.  Not built here: alpha, reducing_gap,
+    (aa_many_plan), so nothing is read back, and the table caches are neither read nor written.  Not built here: reducing_gap,
     uint8_mode="harness", float images or outputs, align_corners, scale factors (each raises NotImplementedError); float, normalised,
     flipped output in either layout is ``resize_many_to_float``, packed ViT patch tokens are ``resize_many_to_patches``.  Pillow's
     ``reducing_gap`` is a step of its own, ``reduce_many_for_resize``, whose images and boxes go into any of the three calls."""
     name = "resize_many"
-    for opt, given in (("alpha", bool(alpha)), ("reducing_gap", reducing_gap is not None), ("out_dtype", out_dtype is not None),
+    for opt, given in (("reducing_gap", reducing_gap is not None), ("out_dtype", out_dtype is not None),
                        ("out_format", out_format is not None), ("mean", mean is not None), ("std", std is not None),
                        ("align_corners", bool(align_corners)), ("scale_factors", scale_factors is not None)):
         if given:
@@ -460,12 +466,12 @@ def resize_many(images, output_size: Sequence[int], mode: str = "bilinear", *, b
         if (uint8_mode or _uint8_mode) != "harness":
             raise ValueError("uint8_mode must be 'pil' or 'harness'")
         raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
-    return _resize_many(name, images, output_size, mode, boxes, channels, None, (sizes, offsets, fill))
+    return _resize_many(name, images, output_size, mode, boxes, channels, None, (sizes, offsets, fill), bool(alpha))
 
 
 def resize_many_to_float(images, output_size: Sequence[int], mode: str = "bilinear", *, boxes=None, flips=None,
                          channels: Optional[int] = None, sizes=None, offsets=None, fill=0, out_dtype=torch.float32, out_format: Optional[str] = None, mean=None,
-                         std=None) -> torch.Tensor:
+                         std=None, alpha: bool = False) -> torch.Tensor:
     """``resize_many`` and the conversion a model needs after it, in the same three launches: with ``u = resize_many(images, output_size,
     mode, boxes=boxes)`` (Pillow's bytes), the result is, bit for bit,
 
@@ -481,6 +487,8 @@ def resize_many_to_float(images, output_size: Sequence[int], mode: str = "biline
     ``out_format``: "nchw" | "nhwc" | None (the class of the items, as ``resize_many``'s output).
     ``mean`` / ``std``: None, or C floats each in 0..255 units (the convention of the single-image forwards), given together.
     ``flips``: None, or N truthy / falsy entries; a truthy entry mirrors that item's output left to right (RandomHorizontalFlip).
+    ``alpha``: ``resize_many``'s; ``u`` above is then ``resize_many(..., alpha=True)``, and the alpha channel is converted with
+    ``mean[C - 1]`` / ``std[C - 1]`` like any other.
 
     This is NOT the single-image forwards' ``out_dtype`` result: those resample in fp32 arithmetic throughout (uint8_mode="harness") and
     take no box; this call converts Pillow's byte, what torchvision's PIL pipeline produces."""
@@ -494,7 +502,8 @@ def resize_many_to_float(images, output_size: Sequence[int], mode: str = "biline
     if _uint8_mode != "pil":
         raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
     return _resize_many(name, images, output_size, mode, boxes, channels,
-                        {"out_dtype": out_dtype, "out_format": out_format, "mean": mean, "std": std, "flips": flips}, (sizes, offsets, fill))
+                        {"out_dtype": out_dtype, "out_format": out_format, "mean": mean, "std": std, "flips": flips}, (sizes, offsets, fill),
+                        bool(alpha))
 
 
 _MANY_MAX = (2 ** 31 - 1) // 4  # the library's bound on a size or an offset of the ragged call
@@ -645,8 +654,9 @@ def _many_layout(items, c: int):
     return classes, c > 1 and n_inter > 0 and n_inter >= n_planar
 
 
-def _many_records(items, classes, interleaved: bool, c: int, checked, flips):
-    """The aa_many_image records of the items in the call's class -> (records, the copies that must outlive the launches)."""
+def _many_records(items, classes, interleaved: bool, c: int, checked, flips, alpha: bool = False):
+    """The aa_many_image records of the items in the call's class -> (records, the copies that must outlive the launches).  alpha: every
+    record asks for Pillow's RGBA / LA resize; which items are Pillow's copies instead is the planner's decision."""
     recs = (_lib.ManyImage * len(items))()
     keep = []
     for i, t in enumerate(items):
@@ -666,13 +676,15 @@ def _many_records(items, classes, interleaved: bool, c: int, checked, flips):
             r.box[0], r.box[1], r.box[2], r.box[3] = bx
         if flips is not None and flips[i]:
             r.flags = _lib.MANY_FLIP_X
+        if alpha:
+            r.flags |= _lib.MANY_PREMUL_ALPHA
     return recs, keep
 
 
 def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes, channels: Optional[int], conv: Optional[dict],
-                 place=(None, None, 0)) -> torch.Tensor:
+                 place=(None, None, 0), alpha: bool = False) -> torch.Tensor:
     """resize_many (conv None) and resize_many_to_float (conv: its options): the checks, the layout class, the plan and the launches.
-    place: (sizes, offsets, fill)."""
+    place: (sizes, offsets, fill).  alpha: Pillow's RGBA / LA resize of every item."""
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
     filter_id = _lib.FILTER_IDS[mode]
@@ -680,6 +692,9 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
         raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
     oh, ow = int(output_size[0]), int(output_size[1])
     items, dev0, n, c = _many_items(name, images, channels, "[0, C, oh, ow]")
+    if alpha and c not in (2, 4):
+        raise NotImplementedError(f"{name}(): alpha=True is built for 2- or 4-channel images with straight alpha last (Pillow's LA / RGBA "
+                                  f"resize), got C = {c}")
     if not (oh > 0 and ow > 0):
         raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
     checked = _many_check_items(name, items, c, boxes, lambda i: (oh, ow))
@@ -703,7 +718,7 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
         cv.out_layout = _lib.NHWC if out_nhwc else _lib.NCHW
     L = _lib.load()
     with torch.cuda.device(dev):
-        recs, keep = _many_records(items, classes, interleaved, c, checked, flips)
+        recs, keep = _many_records(items, classes, interleaved, c, checked, flips, alpha)
         # (places that are all the whole canvas at offset 0 plan to the plain block: the tail of the larger one is then copied as it is
         # and never read)
         desc_bytes = L.aa_many_desc_bytes(n) if places is None else L.aa_many_desc_bytes_placed(n)
@@ -942,7 +957,7 @@ def reduce_many(images, factors, *, boxes=None, channels: Optional[int] = None):
     class (interleaved items: strides (1, rw * C, C)), each starting on a 16-byte boundary: they go straight into ``resize_many``,
     ``resize_many_to_float`` or ``resize_many_to_patches``.  One launch, one non-blocking copy of a packed descriptor from pinned memory,
     no synchronisation, no table cache traffic.  N == 0 gives [].  There is no ``alpha``: Pillow drops ``reducing_gap`` for RGBA / LA
-    images, and ``reduce(alpha=True)`` serves a single one."""
+    images (``resize_many(alpha=True)`` takes them as they are), and ``reduce(alpha=True)`` serves a single one."""
     name = "reduce_many"
     if _uint8_mode != "pil":
         raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
@@ -1415,7 +1430,7 @@ def _register_torch_ops() -> None:
     # a list of images into one batch; boxes flattened to 4 N values, a full-image box standing for None
     # sizes and offsets flattened to 2 N ints (height first), fill to 1 or C ints
     lib.define('resize_many(Tensor[] images, int[] output_size, str mode="bilinear", float[]? boxes=None, int[]? sizes=None, '
-               'int[]? offsets=None, int[]? fill=None) -> Tensor')
+               'int[]? offsets=None, int[]? fill=None, bool alpha=False) -> Tensor')
 
     def _many_boxes(images, boxes):
         if boxes is None:
@@ -1434,7 +1449,7 @@ def _register_torch_ops() -> None:
     def _many_fill(fill):
         return 0 if fill is None else (fill[0] if len(fill) == 1 else list(fill))
 
-    def _many_meta(images, output_size, mode="bilinear", boxes=None, sizes=None, offsets=None, fill=None):
+    def _many_meta(images, output_size, mode="bilinear", boxes=None, sizes=None, offsets=None, fill=None, alpha=False):
         if not images:
             raise ValueError("resize_many(): the op needs at least one image (an empty list has no C)")
         items = [t[0] if t.dim() == 4 else t for t in images]
@@ -1445,27 +1460,27 @@ def _register_torch_ops() -> None:
         mf = torch.channels_last if (c > 1 and n_inter > 0 and n_inter >= n_planar) else torch.contiguous_format
         return torch.empty((len(items), c, output_size[0], output_size[1]), dtype=items[0].dtype, device=items[0].device, memory_format=mf)
 
-    lib.impl("resize_many", lambda images, output_size, mode="bilinear", boxes=None, sizes=None, offsets=None, fill=None: resize_many(
+    lib.impl("resize_many", lambda images, output_size, mode="bilinear", boxes=None, sizes=None, offsets=None, fill=None, alpha=False: resize_many(
         list(images), output_size, mode, boxes=_many_boxes(images, boxes), sizes=_many_pairs(images, sizes, "sizes"),
-        offsets=_many_pairs(images, offsets, "offsets"), fill=_many_fill(fill)), "CUDA")
+        offsets=_many_pairs(images, offsets, "offsets"), fill=_many_fill(fill), alpha=alpha), "CUDA")
     lib.impl("resize_many", _many_meta, "Meta")
     lib.define('resize_many_to_float(Tensor[] images, int[] output_size, str mode="bilinear", float[]? boxes=None, bool[]? flips=None, '
                'ScalarType? out_dtype=None, str? out_format=None, float[]? mean=None, float[]? std=None, int[]? sizes=None, '
-               'int[]? offsets=None, int[]? fill=None) -> Tensor')
+               'int[]? offsets=None, int[]? fill=None, bool alpha=False) -> Tensor')
 
     def _many_float_meta(images, output_size, mode="bilinear", boxes=None, flips=None, out_dtype=None, out_format=None, mean=None, std=None,
-                         sizes=None, offsets=None, fill=None):
+                         sizes=None, offsets=None, fill=None, alpha=False):
         u = _many_meta(images, output_size, mode, boxes)
         out_dtype = torch.float32 if out_dtype is None else out_dtype
         nhwc = u.is_contiguous(memory_format=torch.channels_last) and not u.is_contiguous() if out_format is None else out_format == "nhwc"
         return torch.empty(u.shape, dtype=out_dtype, device="meta", memory_format=torch.channels_last if nhwc else torch.contiguous_format)
 
     lib.impl("resize_many_to_float", lambda images, output_size, mode="bilinear", boxes=None, flips=None, out_dtype=None,
-             out_format=None, mean=None, std=None, sizes=None, offsets=None, fill=None: resize_many_to_float(
+             out_format=None, mean=None, std=None, sizes=None, offsets=None, fill=None, alpha=False: resize_many_to_float(
                  list(images), output_size, mode, boxes=_many_boxes(images, boxes), flips=flips,
                  out_dtype=torch.float32 if out_dtype is None else out_dtype, out_format=out_format,
                  mean=mean, std=std, sizes=_many_pairs(images, sizes, "sizes"), offsets=_many_pairs(images, offsets, "offsets"),
-                 fill=_many_fill(fill)), "CUDA")
+                 fill=_many_fill(fill), alpha=alpha), "CUDA")
     lib.impl("resize_many_to_float", _many_float_meta, "Meta")
 
     # per-item sizes flattened to 2 N ints (height first), or one pair for all; the Meta shape follows from them alone

@@ -43,6 +43,15 @@ centred on 224 x 224):
 (c) must beat (a) with the min .. max ranges of the rounds apart; (b) against (c) is reported whichever way it falls.  Then the reduce
 kernel's own rate: a uniform 64 x 1080 x 1920 x 3 batch at factor (4, 4) through the dense reduce() and through reduce_many, in input GB/s.
 
+--alpha, on the default workload's sizes as RGBA images (C = 4, interleaved pixels and planes), RandomResizedCrop boxes to 224 x 224, bicubic:
+
+  (a) the per-image loop of cubic_forward(img[None], size, box=, alpha=True): the same bytes, the reference for time;
+  (b) resize_many(alpha=True): three launches whatever N;
+  (c) resize_many without alpha on the same tensors: other bytes, what the fusion of the two conversions costs;
+  (d) resize_many_to_float(alpha=True, bfloat16, nchw, mean / std).
+
+(b) is expected to beat (a) with the ranges of the rounds apart; (b) against (c) is reported as it comes.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
@@ -55,6 +64,7 @@ results into one tensor; (c) writes the batch.
   python tools/resize_many_bench.py --patches > out.txt  # only the patch tokens against the per-item composition;
                                                          # profiles/resize_many_patches.txt is this output
   python tools/resize_many_bench.py --gap > out.txt      # only the reducing_gap step for a list (above); profiles/resize_many_gap.txt
+  python tools/resize_many_bench.py --alpha > out.txt    # only Pillow's RGBA resize for a list (above); profiles/resize_many_alpha.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -355,6 +365,57 @@ def gap(args, torch, aa, timed):
     reduce_rate(args, torch, aa, timed)
 
 
+def alpha(args, torch, aa, shapes, timed):
+    """Pillow's RGBA resize for a list: the per-image loop with alpha=True, the one call, the one call without alpha (the cost of the
+    fusion) and the converting call, on the default workload's sizes as RGBA, in both layout classes."""
+    rng = np.random.default_rng(SEED + 2)
+    brng = np.random.default_rng(SEED + 1)
+    boxes = [random_resized_crop_box(brng, h, w) for h, w in shapes]
+    mean, std = [123.675, 116.28, 103.53, 127.5], [58.395, 57.12, 57.375, 64.0]
+    flat = rng.integers(0, 256, sum(h * w * 4 for h, w in shapes), dtype=np.uint8)
+    dev_flat = torch.from_numpy(flat).cuda()
+    print(f"resize_many_bench --alpha: N = {N} RGBA uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}, "
+          f"bicubic; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+    for cls in ("interleaved", "planar"):
+        images, off = [], 0
+        for h, w in shapes:
+            v = dev_flat[off:off + h * w * 4]
+            images.append(v.view(h, w, 4).permute(2, 0, 1) if cls == "interleaved" else v.view(4, h, w))
+            off += h * w * 4
+        contestants = {
+            "a: per-image loop, alpha=True": lambda: [aa.cubic_forward(img[None], list(OUT), box=bx, alpha=True) for img, bx in zip(images, boxes)],
+            "b: resize_many(alpha=True)": lambda: aa.resize_many(images, list(OUT), "bicubic", boxes=boxes, alpha=True),
+            "c: resize_many, no alpha (other bytes)": lambda: aa.resize_many(images, list(OUT), "bicubic", boxes=boxes),
+            "d: resize_many_to_float(alpha=True, bf16, nchw)": lambda: aa.resize_many_to_float(
+                images, list(OUT), "bicubic", boxes=boxes, out_dtype=torch.bfloat16, out_format="nchw", mean=mean, std=std, alpha=True),
+        }
+        for fn in contestants.values():  # warm-up of every contestant (the loop's tables are cached from here on)
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        names = list(contestants)
+        assert torch.equal(contestants[names[1]](), torch.cat(contestants[names[0]]())), "resize_many(alpha=True) differs from the per-image loop"
+        times = {k: [] for k in contestants}
+        for _ in range(args.rounds):
+            for k, fn in contestants.items():
+                times[k].append(timed(fn))
+        print(f"\n{cls}")
+        stat = {}
+        for k, v in times.items():
+            stat[k] = (statistics.median(v), min(v), max(v))
+            launches = count_launches(torch, contestants[k])
+            print(f"  {k:48s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]   kernel launches per batch: "
+                  f"{launches if launches is not None else 'not measured'}")
+        (ma, la, ha), (mb, lb, hb), (mc, lc, hc), _ = stat.values()
+        verdict = "PASS: the ranges do not overlap" if hb < la else "FAIL: (b) is not faster than (a) beyond the ranges of the rounds"
+        print(f"  (b) against (a): {ma / mb:.2f} x; (b) at most {hb:.3f} ms, (a) at least {la:.3f} ms: {verdict}")
+        print(f"  (b) against (c): {mb / mc:.3f} x the time (no bar: the cost of premultiplying in the horizontal pass and converting back in the vertical)")
+        counts = {n: count_launches(torch, lambda: aa.resize_many(images[:n], list(OUT), "bicubic", boxes=boxes[:n], alpha=True)) for n in (1, 8, N)}
+        print("  kernel launches of one resize_many(alpha=True) call by N (expected 3, whatever N): "
+              + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
+
+
 def kernel_times(torch, fn, part, calls=12):
     """Device durations in us of the kernels whose name holds `part`, over `calls` runs of fn(), from torch's profiler; [] where it
     records no device activity."""
@@ -424,6 +485,7 @@ def main():
     ap.add_argument("--placed", action="store_true", help="only the placed call (eval and letterbox) against the per-image loop")
     ap.add_argument("--patches", action="store_true", help="only resize_many_to_patches against the per-item composition")
     ap.add_argument("--gap", action="store_true", help="only Pillow's reducing_gap for a list: the loop, resize_many without a gap, and the new step")
+    ap.add_argument("--alpha", action="store_true", help="only Pillow's RGBA resize for a list: the loop with alpha=True against resize_many(alpha=True)")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -506,6 +568,9 @@ def main():
         return
     if args.gap:
         (reduce_rate if args.rate_only else gap)(args, torch, aa, timed)
+        return
+    if args.alpha:
+        alpha(args, torch, aa, shapes, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
