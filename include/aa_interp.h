@@ -422,6 +422,41 @@ int aa_many_plan_patches(int filter, int layout, int64_t n, int64_t C, int64_t p
 int aa_resample_many_u8_to_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
                                    const aa_convert *cv, int patch_format, aa_stream_t stream);
 
+/* NEAREST plans: what travels with the image in segmentation, depth and instance-mask training — the label map — through the same box,
+ * size, place and flip as its image, but with Pillow's Image.NEAREST (AA_FILTER_BOX, which the reference binds as "nearest", is the box
+ * filter; this is not it).  Item i of the result is, element for element,
+ *   R_i = PIL.Image.resize((vW_i, vH_i), Image.NEAREST, box=box_i), pasted at (oy_i, ox_i) of an [oH, oW] canvas of fill[c], and the whole
+ *   canvas row mirrored left to right for an item planned with AA_MANY_FLIP_X (as aa_resample_many_u8_to_float mirrors it).
+ * Pillow picks the source index of an axis by accumulating a double step, not by a closed form (the two differ: 2 -> 7 is the smallest
+ * case): with the box as float32 values b0, b1 (no box: 0 and the image's size),
+ *   a = (double)(b1 - b0 as a FLOAT difference) / out_size;  xo = (double)b0 + a * 0.5;  idx[x] = (int)xo;  xo = xo + a   for x = 0, 1, ...
+ * Pillow resizes "I;16" alone through its generic transform, which evaluates idx[x] = (int)(a * (x + 0.5) + (double)b0) afresh for every
+ * x; elem_bytes 2 is that mode and follows it (the plan's second double is then b0).
+ * aa_many_plan_nearest is host arithmetic only (no HIP call: works without a device).  It takes aa_many_image records (flags: 0 or
+ * AA_MANY_FLIP_X, any other bit AA_ERR_BAD_SHAPE; strides in bytes under the rules of `layout`'s class, with elem_bytes in place of one
+ * byte) and aa_many_place records (NULL: every item the whole canvas at offset 0), and writes one packed descriptor block — per item and
+ * axis the covered part [v0, v0 + m) of the placed result, the two doubles a and xo computed with exactly the operations above, and the
+ * workspace offsets of the item's two index tables — into desc_host, desc_bytes >= aa_many_desc_bytes_nearest(n).  elem_bytes: 1 (uint8,
+ * C = 1..4), 2 or 4 (int16 / int32 id maps: C must be 1, AA_ERR_BAD_SHAPE otherwise; data and strides aligned to the element,
+ * AA_ERR_STRIDES otherwise); any other value AA_ERR_BAD_DTYPE.  Elements are copied, so signedness does not matter.  fill: C values, each
+ * within what the element holds, signed or unsigned (AA_ERR_BAD_SHAPE beyond); NULL: 0.  The other errors are aa_many_plan_placed's:
+ * AA_ERR_BAD_SHAPE for an empty box, a box beyond its image, C outside 1..4, a size or offset beyond INT32_MAX / 4, or more work units than
+ * one grid holds; AA_ERR_STRIDES for an item that is not in `layout`'s class; AA_ERR_WORKSPACE for a short block; AA_ERR_NULL.
+ * aa_resample_many_nearest enqueues TWO launches whatever n: a table kernel (one lane per item and axis runs the sum above in order from
+ * index 0 of the item's own size, clamps every index to the image, and stores the covered entries) and a gather over (item, plane, canvas
+ * row, 1 KiB of the row) that writes every byte of the output and nothing else.  n, C, the sizes, the class and elem_bytes are the plan's.
+ * out_elem_bytes: elem_bytes, or 8 (C = 1 only): every element sign-extended (elem_bytes 2, 4) or zero-extended (elem_bytes 1) to int64,
+ * what a loss reads; anything else AA_ERR_BAD_DTYPE.  out_dev [n, C, oH, oW] elements, dense, in the plan's layout, aligned to its element;
+ * desc_dev (8-byte aligned) and workspace_dev (16-byte aligned, at least the plan's size) as aa_resample_many_u8.  Every check comes before
+ * the first launch; nothing is allocated, synchronised or read back, and no table cache is touched.  n == 0 launches nothing.
+ * Added without an ABI version change (additive). */
+size_t aa_many_desc_bytes_nearest(int64_t n);
+int aa_many_plan_nearest(int layout, int elem_bytes, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                         const aa_many_place *places /* may be NULL */, const int32_t *fill /* C values; NULL: 0 */, void *desc_host,
+                         size_t desc_bytes, size_t *workspace_bytes);
+int aa_resample_many_nearest(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
+                             int out_elem_bytes /* elem_bytes or 8 */, aa_stream_t stream);
+
 /* ---- ragged Image.reduce: N uint8 images of N sizes, each with its own integer box and factors, into one arena ------------------------
  * Pillow's first step of Image.resize(reducing_gap=...) for a list: every large item is read ONCE by an integer box mean, and the ragged
  * resize above then runs over the small results, which it reads where they lie (an arena offset is just another pointer of an

@@ -53,6 +53,7 @@ EXPORTS = (
     "aa_unpremultiply_u8", "aa_many_desc_bytes", "aa_many_plan", "aa_resample_many_u8", "aa_resample_many_u8_to_float",
     "aa_many_desc_bytes_placed", "aa_many_plan_placed", "aa_many_desc_bytes_patches", "aa_many_plan_patches", "aa_resample_many_u8_to_patches",
     "aa_reduce_many_desc_bytes", "aa_reduce_many_plan", "aa_reduce_many_u8",
+    "aa_many_desc_bytes_nearest", "aa_many_plan_nearest", "aa_resample_many_nearest",
 )
 
 
@@ -114,6 +115,23 @@ class ManyPlaced(ctypes.Structure):
                 ("mw", ctypes.c_int32), ("dy", ctypes.c_int32), ("dx", ctypes.c_int32)]
 
 
+class NearHeader(ctypes.Structure):
+    """Head of the block aa_many_plan_nearest writes (csrc/aa_many_nearest.h AANearHeader; opaque to C callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("C", ctypes.c_int32), ("oH", ctypes.c_int32), ("oW", ctypes.c_int32),
+                ("layout", ctypes.c_int32), ("elem_bytes", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("fill", ctypes.c_int32 * 4)]
+
+
+class NearItem(ctypes.Structure):
+    """One item of that block (csrc/aa_many_nearest.h AANearItem): per axis Pillow's two doubles (step a, first centre xo0), the item's own
+    size v, the covered part [v0, v0 + m) of it and the canvas index d it starts at; dxo is dx on the mirrored row of an item that flips."""
+    _fields_ = [("src", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("plane_stride", ctypes.c_int64), ("tab_h", ctypes.c_int64),
+                ("tab_w", ctypes.c_int64), ("a_h", ctypes.c_double), ("xo0_h", ctypes.c_double), ("a_w", ctypes.c_double),
+                ("xo0_w", ctypes.c_double), ("in_h", ctypes.c_int32), ("in_w", ctypes.c_int32), ("vh", ctypes.c_int32), ("vw", ctypes.c_int32),
+                ("v0h", ctypes.c_int32), ("v0w", ctypes.c_int32), ("mh", ctypes.c_int32), ("mw", ctypes.c_int32), ("dy", ctypes.c_int32),
+                ("dx", ctypes.c_int32), ("dxo", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int64)]
+
+
 class ReduceItem(ctypes.Structure):
     """aa_reduce_item: one item of the ragged Image.reduce (strides in bytes; box = x0, y0, x1, y1 integers; factors fx, fy)."""
     _fields_ = [("data_dev", ctypes.c_void_p), ("H", ctypes.c_int64), ("W", ctypes.c_int64), ("stride_row", ctypes.c_int64),
@@ -153,6 +171,14 @@ def reduce_many_desc_view(buf, n: int):
     hd = ReduceManyHeader.from_buffer(buf, 0)
     items = (ReduceManyItem * n).from_buffer(buf, ctypes.sizeof(ReduceManyHeader))
     prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(ReduceManyHeader) + n * ctypes.sizeof(ReduceManyItem))
+    return hd, items, prefix
+
+
+def near_desc_view(buf, n: int):
+    """(header, items, prefix) of a NEAREST plan's block held in a ctypes buffer: [header][n items][int64 unit_prefix[n + 1]]."""
+    hd = NearHeader.from_buffer(buf, 0)
+    items = (NearItem * n).from_buffer(buf, ctypes.sizeof(NearHeader))
+    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(NearHeader) + n * ctypes.sizeof(NearItem))
     return hd, items, prefix
 
 
@@ -274,6 +300,13 @@ def load() -> ctypes.CDLL:
     L.aa_reduce_many_plan.restype = i32
     L.aa_reduce_many_u8.argtypes = [vp, vp, vp, sz, vp]
     L.aa_reduce_many_u8.restype = i32
+    L.aa_many_desc_bytes_nearest.argtypes = [i64]
+    L.aa_many_desc_bytes_nearest.restype = sz
+    L.aa_many_plan_nearest.argtypes = [i32, i32, i64, i64, i64, i64, ctypes.POINTER(ManyImage), ctypes.POINTER(ManyPlace),
+                                       ctypes.POINTER(ctypes.c_int32), vp, sz, ctypes.POINTER(sz)]
+    L.aa_many_plan_nearest.restype = i32
+    L.aa_resample_many_nearest.argtypes = [vp, vp, vp, vp, sz, i32, vp]
+    L.aa_resample_many_nearest.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

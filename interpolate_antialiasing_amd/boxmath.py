@@ -177,6 +177,43 @@ def axis_hull(in_size: int, out_size: int, in0: float, in1: float, filter_name: 
     return o, e
 
 
+def nearest_axis(in_size: int, out_size: int, b0: Optional[float] = None, b1: Optional[float] = None, closed_form: bool = False) -> Tuple[float, float]:
+    """(a, xo0) of one axis of Pillow's ``Image.resize(size, NEAREST, box=)``: the step and the first centre, both doubles.  b0, b1: the
+    box's two values on this axis (None: the whole axis).  Pillow's C takes the box as floats, takes their FLOAT difference, and only then
+    divides in double.  closed_form: the second value is float32(b0) itself (see nearest_indices)."""
+    f0 = f32(0.0 if b0 is None else b0)
+    f1 = f32(float(in_size) if b1 is None else b1)
+    a = f32(f1 - f0) / out_size
+    return a, (f0 if closed_form else f0 + a * 0.5)
+
+
+def nearest_indices(in_size: int, out_size: int, b0: Optional[float] = None, b1: Optional[float] = None, clamp: bool = False,
+                    closed_form: bool = False):
+    """The source index of every output index of one axis of ``Image.resize(size, NEAREST, box=)``, as Pillow's affine scaling picks it:
+
+        a = float64(float32(b1) - float32(b0)) / out_size;  xo = float64(float32(b0)) + a * 0.5
+        for x in 0 .. out_size - 1:  idx[x] = int(xo);  xo = xo + a
+
+    The ACCUMULATION is the specification: one double add per step, in order.  The closed form ``a * (x + 0.5) + b0`` gives another table
+    (2 -> 7 is the smallest case: it reaches exactly 1.0 where the accumulated sum is just below it).  For a box check_box accepts, xo is
+    never negative, so int() is the C's truncation.
+    closed_form=True is that other table, and it is what Pillow computes for ONE mode: "I;16" is a "special" image type there, served by
+    the generic transform, which evaluates ``a * (x + 0.5) + b0`` afresh for every x.  resize_many_nearest follows Pillow in both: int16
+    items take closed_form=True, uint8 and int32 items the accumulation.
+    clamp: what the device table kernel stores, indices above in_size - 1 pulled back (none occurs for a box inside the image; the
+    tests assert that on their cases)."""
+    a, xo = nearest_axis(in_size, out_size, b0, b1, closed_form)
+    idx = []
+    for x in range(int(out_size)):
+        i = int(a * (x + 0.5) + xo) if closed_form else int(xo)
+        if clamp:
+            i = min(max(i, 0), int(in_size) - 1)
+        idx.append(i)
+        if not closed_form:
+            xo = xo + a
+    return idx
+
+
 def fit_sizes(shapes, shorter: Optional[int] = None, longer: Optional[int] = None):
     """[(H_i, W_i)] -> [(vh_i, vw_i)], aspect ratio kept.  shorter=s: the short side becomes s and the long one int(s * long / short),
     torchvision's Resize(int).  longer=s: the long side becomes s and the short one max(1, int(s * short / long)), the letterbox fit.

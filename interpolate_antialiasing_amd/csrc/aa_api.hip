@@ -6,6 +6,7 @@
 
 #include "aa_box.h"
 #include "aa_many.h"
+#include "aa_many_nearest.h"
 #include "aa_reduce_many.h"
 #include "aa_plan.h"
 #include "aa_reduce.h"
@@ -505,6 +506,19 @@ int aa_resample_many_u8_to_patches(const void *desc_host, const void *desc_dev, 
   const int out_elem = (cv->flags & AA_FLAG_OUT_F16) ? AA_F16 : ((cv->flags & AA_FLAG_OUT_BF16) ? AA_BF16 : AA_F32);
   return aa_launch_many_patches(desc_host, desc_dev, out_dev, workspace_dev, workspace_bytes, out_elem, patch_format == AA_PATCH_PPC, cv->normalize,
                                 cv->mean, cv->std, (hipStream_t)stream);
+}
+
+size_t aa_many_desc_bytes_nearest(int64_t n) { return aa_near_desc_size(n); }
+
+int aa_many_plan_nearest(int layout, int elem_bytes, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                         const aa_many_place *places, const int32_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
+  return aa_near_plan_host(layout, elem_bytes, n, C, oH, oW, images, places, fill, desc_host, desc_bytes, workspace_bytes);
+}
+
+int aa_resample_many_nearest(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
+                             int out_elem_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_many_nearest(desc_host, desc_dev, out_dev, workspace_dev, workspace_bytes, out_elem_bytes, (hipStream_t)stream);
 }
 
 // ---- Image.reduce ------------------------------------------------------------------------------------------------------------------------

@@ -621,15 +621,24 @@ def _many_items(name: str, images, channels: Optional[int], empty: str):
     return items, dev0, n, c
 
 
-def _many_check_items(name: str, items, c: int, boxes, out_size):
+def _many_check_items(name: str, items, c: int, boxes, out_size, dtypes=None):
     """Dtype, C, sizes, device and box of every item -> the boxes as Pillow's C sees them (None: the whole image).  out_size(i): the
-    (H, W) item i is resized to, for the wording of the size check."""
+    (H, W) item i is resized to, for the wording of the size check.  dtypes: None (uint8 only), or the dtypes the call copies (one per
+    call, the first item's; more than one byte per element only with one channel)."""
     n = len(items)
     if boxes is not None and len(boxes) != n:
         raise ValueError(f"{name}(): boxes must hold one entry per image ({n}), got {len(boxes)}")
     checked = []
     for i, t in enumerate(items):
-        if t.dtype != torch.uint8:
+        if dtypes is not None:
+            if t.dtype not in dtypes:
+                raise NotImplementedError(f"{name}(): images[{i}] is {t.dtype}; built for {', '.join(str(d) for d in dtypes)}")
+            if t.dtype != items[0].dtype:
+                raise ValueError(f"{name}(): every image must have the same dtype: images[{i}] is {t.dtype}, images[0] {items[0].dtype}")
+            if t.element_size() > 1 and c != 1:
+                raise NotImplementedError(f"{name}(): images[{i}] is {t.dtype} with C = {c}; {t.dtype} maps have one channel (Pillow's "
+                                          f"\"I;16\" and \"I\"), only torch.uint8 has up to 4")
+        elif t.dtype != torch.uint8:
             raise NotImplementedError(f"{name}(): images[{i}] is {t.dtype}; a list of images is Pillow's uint8 resize only")
         if int(t.shape[0]) != c:
             raise ValueError(f"{name}(): every image must have the same C: images[{i}] has {int(t.shape[0])}, expected {c}")
@@ -745,6 +754,121 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
         else:
             rc = L.aa_resample_many_u8_to_float(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(),
                                                 ws.numel(), ctypes.byref(cv), stream)
+    _lib.check(rc, name)
+    return out
+
+
+_NEAREST_RANGE = {torch.uint8: (0, 255), torch.int16: (-32768, 32767), torch.int32: (-2 ** 31, 2 ** 31 - 1)}  # the dtypes the call copies
+
+
+def _nearest_fill(name: str, fill, c: int, dtype: torch.dtype):
+    """fill of resize_many_nearest, checked -> C ints within the dtype's range."""
+    lo, hi = _NEAREST_RANGE[dtype]
+    try:
+        fills = [fill] if not isinstance(fill, (tuple, list)) else list(fill)
+        if any(isinstance(v, bool) or int(v) != v for v in fills):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}(): fill must be one int or {c} ints in {lo}..{hi}, got {fill!r}") from None
+    if len(fills) == 1 and not isinstance(fill, (tuple, list)):
+        fills = fills * c
+    if len(fills) != c:
+        raise ValueError(f"{name}(): fill must be one int or one per channel ({c}), got {len(fills)}")
+    for k, v in enumerate(fills):
+        if not (lo <= v <= hi):
+            raise ValueError(f"{name}(): fill[{k}] = {v} is outside {lo}..{hi} ({dtype})")
+    return [int(v) for v in fills]
+
+
+def resize_many_nearest(images, output_size: Sequence[int], *, boxes=None, flips=None, channels: Optional[int] = None, sizes=None,
+                        offsets=None, fill=0, out_dtype=None) -> torch.Tensor:
+    """The label maps of a ragged batch, with Pillow's ``Image.NEAREST``: what goes through the same crop, size, placement and flip as its
+    image in segmentation, depth, instance-mask and panoptic training, where a filtered class id is a wrong class id.  Per item i, bit
+    for bit,
+
+        R_i = PIL.Image.resize((vw_i, vh_i), Image.NEAREST, box=boxes[i])    # vh_i, vw_i = sizes[i], or output_size
+        y[i, c, Y, X] = R_i[Y - py_i, X - px_i, c] where that exists, else fill[c]
+        y[i] = y[i].flip(-1) where flips[i]                                  # the whole canvas row, as resize_many_to_float does
+
+    ``images``, ``boxes`` (Pillow's order, x first), ``channels``, ``sizes``, ``offsets`` (``"center"`` included) and ``flips`` are exactly
+    ``resize_many`` / ``resize_many_to_float``'s arguments, with the same checks, the same two layout classes and the same reading of
+    every item where it lies: pass the SAME ``boxes, sizes, offsets, flips`` to ``resize_many_to_float`` for the images and to this call
+    for the masks.
+    Items are ``torch.uint8`` with 1..4 channels (Pillow's "L", "LA", "RGB", "RGBA"; NEAREST treats every channel alike, so there is no
+    ``alpha=``), or ``torch.int16`` / ``torch.int32`` with one channel ("I;16", "I"); one dtype per call.  Elements are copied, never
+    computed with.
+    ``fill``: one int or C ints within the dtype's range (255 as the ignore index of a uint8 map, -1 of an int32 one).
+    ``out_dtype``: None (the items' dtype) or ``torch.int64``, for one channel only: exactly ``y.long()`` (zero-extended from uint8,
+    sign-extended from int16 / int32), what ``cross_entropy`` takes, without the second pass.
+    The result is contiguous for planar items and channels_last for interleaved ones; N == 0 gives an empty [0, C, oh, ow] tensor.
+
+    Three things that are easy to get wrong:
+    * This is NOT ``mode="nearest"`` of the other calls: that one is the box filter (the reference's naming), which averages.
+    * It is Pillow's ``resize(box=)``, which for an integer box is NOT promised equal to ``crop(box).resize()``: the source index of
+      output x is ``int(xo)`` after x additions of the step to ``xo = x0 + step / 2`` (``boxmath.nearest_indices``), and that sum starts
+      from the box's x0, not from 0, so its rounding differs.  (Pillow serves "I;16" alone through its generic transform, which
+      evaluates ``step * (x + 0.5) + x0`` afresh for every x; int16 items follow Pillow there, ``nearest_indices(closed_form=True)``,
+      so an int16 map and a uint8 map of one geometry can differ by one source pixel where the two forms fall on either side of an
+      integer, exactly as the two Pillow images do.)
+    * A [K, H, W] stack of instance masks with K > 4 goes in as K single-plane items (``stack[k:k + 1]`` views) with the same box
+      repeated, not as one K-channel item.
+
+    Two launches and one non-blocking copy of a packed descriptor whatever N: a table kernel that runs Pillow's accumulation per item and
+    axis, and a gather that writes every byte of the output.  Nothing is read back; the table caches are neither read nor written."""
+    name = "resize_many_nearest"
+    if out_dtype not in (None, torch.int64):
+        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built; None (the items' dtype) or torch.int64")
+    if len(output_size) != 2:
+        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
+    oh, ow = int(output_size[0]), int(output_size[1])
+    items, dev0, n, c = _many_items(name, images, channels, "[0, C, oh, ow]")
+    if not (oh > 0 and ow > 0):
+        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    checked = _many_check_items(name, items, c, boxes, lambda i: (oh, ow), tuple(_NEAREST_RANGE))
+    dtype = items[0].dtype if n else (images.dtype if isinstance(images, torch.Tensor) and images.dtype in _NEAREST_RANGE else torch.uint8)
+    if out_dtype is torch.int64 and c != 1:
+        raise NotImplementedError(f"{name}(): out_dtype torch.int64 is built for one channel (a class-id map), got C = {c}")
+    if flips is not None:
+        flips = [bool(v) for v in flips]
+        if len(flips) != n:
+            raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
+    places, _ = _many_places(name, (sizes, offsets, 0), n, c, oh, ow)
+    fills = _nearest_fill(name, fill, c, dtype)
+    res_dtype = dtype if out_dtype is None else out_dtype
+    if n == 0:
+        if dev0 is None:
+            dev0 = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        return torch.empty((0, c, oh, ow), dtype=res_dtype, device=dev0)
+    for t in items:
+        _require_gpu(t, name)
+    dev = items[0].device
+    classes, interleaved = _many_layout(items, c)
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    eb = items[0].element_size()
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        recs, keep = _many_records(items, classes, interleaved, c, checked, flips)
+        for r in recs:  # (the records hold strides in elements; the library takes bytes)
+            r.stride_row, r.stride_px, r.stride_ch = r.stride_row * eb, r.stride_px * eb, r.stride_ch * eb
+        desc_bytes = L.aa_many_desc_bytes_nearest(n)
+        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
+        ws_bytes = ctypes.c_size_t(0)
+        precs = None
+        if places is not None:
+            precs = (_lib.ManyPlace * n)()
+            for i, p in enumerate(places):
+                precs[i].vH, precs[i].vW, precs[i].oy, precs[i].ox = p
+        rc = L.aa_many_plan_nearest(layout, eb, n, c, oh, ow, recs, precs, (ctypes.c_int32 * 4)(*(fills + [0] * (4 - c))), desc_host.data_ptr(),
+                                    desc_bytes, ctypes.byref(ws_bytes))
+        _lib.check(rc, name)
+        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
+        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
+        ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
+        out = torch.empty((n, c, oh, ow), dtype=res_dtype, device=dev,
+                          memory_format=torch.channels_last if interleaved else torch.contiguous_format)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = L.aa_resample_many_nearest(desc_host.data_ptr(), desc_dev.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        out.element_size(), stream)
     _lib.check(rc, name)
     return out
 
@@ -1509,6 +1633,22 @@ def _register_torch_ops() -> None:
                                     patch_format=patch_format, pad_to=pad_to, out_dtype=torch.float32 if out_dtype is None else out_dtype,
                                     mean=mean, std=std), "CUDA")
     lib.impl("resize_many_to_patches", _many_patches_meta, "Meta")
+
+    # Pillow's NEAREST for the label maps: the same flattened boxes / sizes / offsets / fill as resize_many, flips as resize_many_to_float
+    lib.define('resize_many_nearest(Tensor[] images, int[] output_size, float[]? boxes=None, bool[]? flips=None, int[]? sizes=None, '
+               'int[]? offsets=None, int[]? fill=None, ScalarType? out_dtype=None) -> Tensor')
+
+    def _many_nearest_meta(images, output_size, boxes=None, flips=None, sizes=None, offsets=None, fill=None, out_dtype=None):
+        u = _many_meta(images, output_size)
+        nhwc = u.is_contiguous(memory_format=torch.channels_last) and not u.is_contiguous()
+        return torch.empty(u.shape, dtype=u.dtype if out_dtype is None else out_dtype, device="meta",
+                           memory_format=torch.channels_last if nhwc else torch.contiguous_format)
+
+    lib.impl("resize_many_nearest", lambda images, output_size, boxes=None, flips=None, sizes=None, offsets=None, fill=None, out_dtype=None:
+             resize_many_nearest(list(images), output_size, boxes=_many_boxes(images, boxes), flips=flips,
+                                 sizes=_many_pairs(images, sizes, "sizes"), offsets=_many_pairs(images, offsets, "offsets"),
+                                 fill=_many_fill(fill), out_dtype=out_dtype), "CUDA")
+    lib.impl("resize_many_nearest", _many_nearest_meta, "Meta")
 
     # the ragged Image.reduce: factors one int, one (fx, fy) or 2 N ints (x first); boxes 4 N ints, a full-image box standing for None
     lib.define("reduce_many(Tensor[] images, int[] factors, int[]? boxes=None) -> Tensor[]")

@@ -52,6 +52,16 @@ kernel's own rate: a uniform 64 x 1080 x 1920 x 3 batch at factor (4, 4) through
 
 (b) is expected to beat (a) with the ranges of the rounds apart; (b) against (c) is reported as it comes.
 
+--nearest, on two workloads of its own — the label maps that travel with the images — Pillow's NEAREST for a list, against the loop a user
+writes without the call (per image: index tensors from boxmath.nearest_indices, two index_selects, a flip, a pad, .long()) and against a
+plain device copy of the output's bytes, the write floor:
+
+  crops      64 camera-sized single-channel uint8 maps (H in [1080, 3000], W in [1440, 4000]), one RandomResizedCrop box each -> 224 x 224,
+             half the items flipped, out_dtype=torch.int64;
+  letterbox  16 maps of 1024 x 2048 -> fit_sizes(longer=1024), centred on a 1024 x 1024 canvas, fill 255, uint8.
+
+Both ways give the same elements.  No bar is set; what is required is two kernel launches whatever N, and that the numbers are written down.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
@@ -65,6 +75,7 @@ results into one tensor; (c) writes the batch.
                                                          # profiles/resize_many_patches.txt is this output
   python tools/resize_many_bench.py --gap > out.txt      # only the reducing_gap step for a list (above); profiles/resize_many_gap.txt
   python tools/resize_many_bench.py --alpha > out.txt    # only Pillow's RGBA resize for a list (above); profiles/resize_many_alpha.txt
+  python tools/resize_many_bench.py --nearest > out.txt  # only Pillow's NEAREST for a list (above); profiles/resize_many_nearest.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -416,6 +427,99 @@ def alpha(args, torch, aa, shapes, timed):
               + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
 
 
+def nearest(args, torch, aa, timed):
+    """resize_many_nearest against the per-image torch loop and the write floor, on the two label-map workloads."""
+    from interpolate_antialiasing_amd import boxmath
+
+    rng = np.random.default_rng(SEED)
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    crop_shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)]
+    crop_maps = [torch.randint(0, 21, (1, h, w), dtype=torch.uint8, device="cuda", generator=gen) for h, w in crop_shapes]
+    brng = np.random.default_rng(SEED + 1)
+    crop_boxes = [random_resized_crop_box(brng, h, w) for h, w in crop_shapes]
+    crop_flips = [i % 2 == 1 for i in range(N)]
+    lb_shapes = [(1024, 2048)] * 16
+    lb_maps = [torch.randint(0, 21, (1, h, w), dtype=torch.uint8, device="cuda", generator=gen) for h, w in lb_shapes]
+    lb_sizes, lb_canvas = boxmath.fit_sizes(lb_shapes, longer=1024), (1024, 1024)
+
+    def tables_of(shapes, boxes, vs):
+        """The loop's index tensors, built on the host and uploaded: per image (rows, columns)."""
+        out = []
+        for (h, w), bx, (vh, vw) in zip(shapes, boxes, vs):
+            b = boxmath.box_f32(bx) if bx is not None else (None, None, None, None)
+            out.append((torch.tensor(boxmath.nearest_indices(h, vh, b[1], b[3]), device="cuda"),
+                        torch.tensor(boxmath.nearest_indices(w, vw, b[0], b[2]), device="cuda")))
+        return out
+
+    def loop(maps, tabs, vs, canvas, flips, fill, long):
+        oh, ow = canvas
+        res = []
+        for i, (m, (iy, ix), (vh, vw)) in enumerate(zip(maps, tabs, vs)):
+            r = m.index_select(1, iy).index_select(2, ix)
+            py, px = boxmath.center_offset(vh, oh), boxmath.center_offset(vw, ow)
+            if (vh, vw) != (oh, ow):
+                r = torch.nn.functional.pad(r, (px, ow - px - vw, py, oh - py - vh), value=fill)
+            if flips is not None and flips[i]:
+                r = r.flip(-1)
+            res.append(r.long() if long else r)
+        return torch.stack(res)
+
+    crop_vs = [OUT] * N
+    crop_tabs = tables_of(crop_shapes, crop_boxes, crop_vs)
+    lb_tabs = tables_of(lb_shapes, [None] * 16, lb_sizes)
+    workloads = (
+        (f"crops: {N} single-channel uint8 maps, H in [1080, 3000], W in [1440, 4000], one RandomResizedCrop box each -> {OUT}, {sum(crop_flips)} flipped, int64 out",
+         {"loop: tables built on the host per batch": lambda: loop(crop_maps, tables_of(crop_shapes, crop_boxes, crop_vs), crop_vs, OUT, crop_flips, 0, True),
+          "loop: tables already on the device": lambda: loop(crop_maps, crop_tabs, crop_vs, OUT, crop_flips, 0, True),
+          "call: resize_many_nearest": lambda: aa.resize_many_nearest(crop_maps, list(OUT), boxes=crop_boxes, flips=crop_flips, out_dtype=torch.int64)},
+         lambda n: aa.resize_many_nearest(crop_maps[:n], list(OUT), boxes=crop_boxes[:n], flips=crop_flips[:n], out_dtype=torch.int64), N),
+        (f"letterbox: 16 uint8 maps of 1024 x 2048 -> {lb_sizes[0]}, centred on {lb_canvas}, fill 255, uint8 out",
+         {"loop: tables built on the host per batch": lambda: loop(lb_maps, tables_of(lb_shapes, [None] * 16, lb_sizes), lb_sizes, lb_canvas, None, 255, False),
+          "loop: tables already on the device": lambda: loop(lb_maps, lb_tabs, lb_sizes, lb_canvas, None, 255, False),
+          "call: resize_many_nearest": lambda: aa.resize_many_nearest(lb_maps, list(lb_canvas), sizes=lb_sizes, offsets="center", fill=255)},
+         lambda n: aa.resize_many_nearest(lb_maps[:n], list(lb_canvas), sizes=lb_sizes[:n], offsets="center", fill=255), 16),
+    )
+    print(f"resize_many_bench --nearest: Pillow's NEAREST for label maps (seed {SEED}); library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+    for title, contestants, call_n, n_all in workloads:
+        names = list(contestants)
+        for fn in contestants.values():
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        want, got = contestants[names[1]](), contestants[names[2]]()
+        assert want.dtype == got.dtype and torch.equal(want, got), "resize_many_nearest differs from the per-image loop"
+        src = torch.empty_like(got)
+        dst = torch.empty_like(got)
+        contestants = dict(contestants)
+        contestants["floor: device copy of the output's bytes"] = lambda: dst.copy_(src)
+        times = {k: [] for k in contestants}
+        for _ in range(args.rounds):
+            for k, fn in contestants.items():
+                times[k].append(timed(fn))
+        print(f"\n{title}")
+        print(f"  output: {got.numel() * got.element_size() / 1e6:.2f} MB")
+        stat = {}
+        for k, v in times.items():
+            stat[k] = (statistics.median(v), min(v), max(v))
+            launches = count_launches(torch, contestants[k])
+            print(f"  {k:48s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]   kernel launches per batch: "
+                  f"{launches if launches is not None else 'not measured'}")
+        (mh, _, _), (md, ld, hd), (mc, lc, hc), (mf, _, _) = stat.values()
+        verdict = "the one call is faster" if hc < ld else ("THE ONE CALL IS NOT FASTER than the loop" if mc >= md else "faster by the medians, the ranges overlap")
+        print(f"  call against the loop with tables on the device: {md / mc:.2f} x; against the loop that builds them: {mh / mc:.2f} x: {verdict}")
+        for part in ("near_tables", "near_gather"):
+            kt = kernel_times(torch, contestants[names[2]], part)
+            if kt:
+                print(f"  {part}: device time median {statistics.median(kt):8.1f} us [{min(kt):8.1f} .. {max(kt):8.1f}] over {len(kt)} launches")
+            else:
+                print(f"  {part}: device time not measured")
+        print(f"  the floor copy: {mf * 1e3:.1f} us per batch by device events")
+        counts = {n: count_launches(torch, lambda: call_n(n)) for n in (1, 8, n_all)}
+        print("  kernel launches of one resize_many_nearest call by N (expected 2, whatever N): "
+              + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
+
+
 def kernel_times(torch, fn, part, calls=12):
     """Device durations in us of the kernels whose name holds `part`, over `calls` runs of fn(), from torch's profiler; [] where it
     records no device activity."""
@@ -486,6 +590,7 @@ def main():
     ap.add_argument("--patches", action="store_true", help="only resize_many_to_patches against the per-item composition")
     ap.add_argument("--gap", action="store_true", help="only Pillow's reducing_gap for a list: the loop, resize_many without a gap, and the new step")
     ap.add_argument("--alpha", action="store_true", help="only Pillow's RGBA resize for a list: the loop with alpha=True against resize_many(alpha=True)")
+    ap.add_argument("--nearest", action="store_true", help="only Pillow's NEAREST for label maps: resize_many_nearest against the per-image torch loop")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -571,6 +676,9 @@ def main():
         return
     if args.alpha:
         alpha(args, torch, aa, shapes, timed)
+        return
+    if args.nearest:
+        nearest(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
