@@ -88,19 +88,26 @@ class ManyImage(ctypes.Structure):
 
 
 class ManyHeader(ctypes.Structure):
-    """Head of the descriptor block aa_many_plan writes (csrc/aa_many.h AAManyHeader; opaque to C callers, mirrored here for the tests)."""
+    """Head of the descriptor block aa_many_plan writes (csrc/aa_many.h AAManyHeader; opaque to C callers, mirrored here for the tests).
+    The three live fields are read by the names csrc/aa_many.h gives them, ``flips``, ``kind`` (MANY_PLAN_* bits) and ``fill``; the
+    ctypes fields keep the names they had while the words were unused, which earlier code iterates over by name."""
     _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("C", ctypes.c_int32), ("oH", ctypes.c_int32), ("oW", ctypes.c_int32),
                 ("filter", ctypes.c_int32), ("layout", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("hunits", ctypes.c_int64),
                 ("ws_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64 * 2)]
+    flips = property(lambda self: self.reserved0)
+    kind = property(lambda self: self.reserved[0])
+    fill = property(lambda self: self.reserved[1])
 
 
 class ManyItem(ctypes.Structure):
-    """One item of that block (csrc/aa_many.h AAManyItem): offsets in bytes into the workspace, hulls [o, o + hull) per axis."""
+    """One item of that block (csrc/aa_many.h AAManyItem): offsets in bytes into the workspace, hulls [o, o + hull) per axis.  ``flags``
+    (MANY_ITEM_* bits) reads the last field by the name csrc/aa_many.h gives it."""
     _fields_ = [("src", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("plane_stride", ctypes.c_int64), ("tab_h", ctypes.c_int64),
                 ("tab_w", ctypes.c_int64), ("inter", ctypes.c_int64), ("in0_h", ctypes.c_double), ("in1_h", ctypes.c_double),
                 ("in0_w", ctypes.c_double), ("in1_w", ctypes.c_double), ("oy", ctypes.c_int32), ("hull_h", ctypes.c_int32),
                 ("ox", ctypes.c_int32), ("hull_w", ctypes.c_int32), ("ksize_h", ctypes.c_int32), ("ksize_w", ctypes.c_int32),
                 ("box_on", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+    flags = property(lambda self: self.reserved)
 
 
 class ManyPlace(ctypes.Structure):
@@ -155,6 +162,8 @@ class ReduceManyItem(ctypes.Structure):
 MANY_FLIP_X = 1     # aa_many_image.flags: mirror the item's output left to right (aa_resample_many_u8_to_float only)
 MANY_PREMUL_ALPHA = 2  # aa_many_image.flags: Pillow's RGBA / LA resize of that item (C 2 or 4, straight alpha last; not for patch plans)
 PATCH_CPP, PATCH_PPC = 0, 1  # aa_resample_many_u8_to_patches: token vector [C, ph, pw] or [ph, pw, C]
+MANY_PLAN_PLACED, MANY_PLAN_PATCHES, MANY_PLAN_ALPHA = 1, 2, 4  # ManyHeader.kind (csrc/aa_many.h AA_MANY_PLAN_*)
+MANY_ITEM_FLIP, MANY_ITEM_ALPHA = 1, 2  # ManyItem.flags (csrc/aa_many.h AA_MANY_ITEM_*)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
 
@@ -183,7 +192,7 @@ def near_desc_view(buf, n: int):
 
 
 def many_placed_view(buf, n: int):
-    """The placement records of a placed plan's block (ManyHeader.reserved[0] == 1): they follow the prefix sums."""
+    """The placement records of a placed plan's block (ManyHeader.kind has MANY_PLAN_PLACED): they follow the prefix sums."""
     return (ManyPlaced * n).from_buffer(buf, ctypes.sizeof(ManyHeader) + n * ctypes.sizeof(ManyItem) + 8 * (n + 1))
 
 

@@ -6,21 +6,35 @@
 // Everything a kernel needs about an item is in its record(s): no table header, nothing read back.
 #pragma once
 
+#include <stddef.h>
+
 #include "aa_common.h"
 
 #define AA_MANY_MAGIC 0x594E4D41  // 'AMNY'
 #define AA_MANY_STRIP 64          // output columns per workgroup of the horizontal pass
 #define AA_MANY_VBYTES 1024       // output-row bytes per workgroup of the vertical pass (256 lanes x 4)
 
+// What a plan is (AAManyHeader.kind) and what an item asks of the kernels (AAManyItem.flags).  Both fields, the header's `flips` and its
+// `fill` were called `reserved` while they were unused; the offsets and sizes are what they were.
+#define AA_MANY_PLAN_PLACED 1   // AAManyPlace records follow the prefix sums
+#define AA_MANY_PLAN_PATCHES 2  // a patch plan: its tail follows them (always with AA_MANY_PLAN_PLACED, never with AA_MANY_PLAN_ALPHA)
+#define AA_MANY_PLAN_ALPHA 4    // some item has AA_MANY_ITEM_ALPHA: the launches take the alpha instantiations
+#define AA_MANY_ITEM_FLIP 1     // AA_MANY_FLIP_X: the converting vertical pass writes the item mirrored left to right
+#define AA_MANY_ITEM_ALPHA 2    // AA_MANY_PREMUL_ALPHA and not Pillow's copy (size asked for == [H, W], no box or the whole image): the
+                                // horizontal pass premultiplies what it stages, the vertical passes convert back
+static_assert(AA_MANY_ITEM_FLIP == AA_MANY_FLIP_X, "an item's flip bit is the caller's");
+
 struct AAManyHeader {
-  int32_t magic, n, C, oH, oW, filter, layout, reserved0;  // reserved0: 1 when some item flips (only the converting pass serves it)
+  int32_t magic, n, C, oH, oW, filter, layout;
+  int32_t flips;      // 1 when some item has AA_MANY_ITEM_FLIP (only the converting passes serve it)
   int64_t hunits;     // work units of the horizontal pass, all items: hunit_prefix[n]
   int64_t ws_bytes;   // table arena + intermediates
-  int64_t reserved[2]; // [0]: bit 0 a placed plan (AAManyPlace records follow the prefix sums), bit 1 a patch plan (its tail follows
-                       // them), bit 2 some item has bit 1 of its `reserved` (the launches take the alpha instantiations; never with
-                       // bit 1); [1]: a placed plan's fill, byte c = channel c's
+  int64_t kind;       // AA_MANY_PLAN_* bits; 0: a plain plan
+  int64_t fill;       // a placed plan's fill, byte c = channel c's
 };
 static_assert(sizeof(AAManyHeader) == 64, "descriptor header is 64 bytes");
+static_assert(offsetof(AAManyHeader, flips) == 28 && offsetof(AAManyHeader, kind) == 48 && offsetof(AAManyHeader, fill) == 56,
+              "the renamed header fields keep their offsets");
 
 // One item.  The image is read where it lies: byte (row y, column x, channel c) is at src + y * row_stride + x * E + c (interleaved class,
 // E = C) or src + c * plane_stride + y * row_stride + x (planar class).  tab_h / tab_w / inter are byte offsets into the workspace.
@@ -33,11 +47,10 @@ struct AAManyItem {
   int32_t oy, hull_h, ox, hull_w;     // the hull [o, o + hull) of all windows per axis: nothing outside it is read
   int32_t ksize_h, ksize_w;
   int32_t box_on;                     // 1: the scale is the FLOAT difference of the interval over the output size (a box); 0: in / out
-  int32_t reserved;                   // bit 0: AA_MANY_FLIP_X, the converting vertical pass writes the item mirrored left to right
-                                      // bit 1: AA_MANY_PREMUL_ALPHA and not Pillow's copy (size asked for == [H, W], no box or the
-                                      // whole image): the horizontal pass premultiplies what it stages, the vertical passes convert back
+  int32_t flags;                      // AA_MANY_ITEM_* bits
 };
 static_assert(sizeof(AAManyItem) == 112, "descriptor item is 112 bytes");
+static_assert(offsetof(AAManyItem, flags) == 108, "the renamed item field keeps its offset");
 
 // A placed plan's second record of an item: the item is resized to its own size [vh, vw] and that result's corner lies at (py, px) of
 // the [oH, oW] canvas.  Per axis the covered part of the result is [v0, v0 + m) and lands at canvas index d = v0 + p; the item's table of

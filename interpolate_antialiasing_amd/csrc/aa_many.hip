@@ -21,7 +21,7 @@
 #include <string.h>
 
 #include "aa_alpha.h"
-#include "aa_many.h"
+#include "aa_many_host.h"
 #include "aa_pil_coeffs.h"
 
 using namespace aa_coeffs;
@@ -107,7 +107,7 @@ __device__ inline uint32_t premul_planes4(uint32_t v, uint32_t a) {
 }
 
 // PL: the item's own strip count, its covered columns [0, mw) of the table, and its own row pitch and lead in the intermediate.
-// AL (E = 1, 2, 4; the plan's header says some item has bit 1 of `reserved`): a workgroup of such an item stages its chunk PREMULTIPLIED
+// AL (E = 1, 2, 4; the plan's header says some item has AA_MANY_ITEM_ALPHA): a workgroup of such an item stages its chunk PREMULTIPLIED
 // (Pillow's RGBA -> RGBa, LA -> La), once per pixel and in LDS only, so the intermediate holds filtered premultiplied bytes.  Where the
 // pixels of the row are aligned to the staged dwords (E = 4: shift 0; E = 2: shift even) the staging lane converts its dword in registers
 // on the way in; otherwise the chunk is staged as it lies and converted in place, one lane per pixel with byte accesses, behind one more
@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
   if (seg1 > hull_w) seg1 = hull_w;
   const uint8_t *rowp = it.src + (int64_t)plane * it.plane_stride + (int64_t)(it.oy + row) * it.row_stride + (int64_t)it.ox * E;
   // AL: this workgroup premultiplies what it stages; aoff, a colour plane's distance to the same byte of the alpha plane
-  const bool al = AL && (it.reserved & 2) != 0 && (E > 1 || plane < planes - 1);
+  const bool al = AL && (it.flags & AA_MANY_ITEM_ALPHA) != 0 && (E > 1 || plane < planes - 1);
   const int64_t aoff = AL && E == 1 ? (int64_t)(planes - 1 - plane) * it.plane_stride : 0;
 
   const int j = threadIdx.x;
@@ -254,7 +254,7 @@ __device__ inline Sums4 vtap_sums(const AAManyItem &it, const char *ws, int out,
   return s;
 }
 
-// AL, an item with bit 1 of `reserved`: the intermediate holds premultiplied bytes, so the four clipped bytes w of a lane are converted
+// AL, an item with AA_MANY_ITEM_ALPHA: the intermediate holds premultiplied bytes, so the four clipped bytes w of a lane are converted
 // back (Pillow's RGBa -> RGBA, La -> LA; aa_alpha.h) with the resampled alpha of their own output pixel: in the lane for interleaved
 // pixels (one RGBA pixel, or two LA pixels: a row's bytes start on a dword of the canvas and E divides 4), and for a colour plane from a
 // second walk down the same window of the alpha plane, plane planes - 1, at the same columns.  The alpha plane's bytes are final.
@@ -298,7 +298,7 @@ __device__ inline uint32_t placed_bytes(const AAManyItem &it, const AAManyPlace 
   const int64_t pitch = aa_many_placed_pitch(pl.dx, pl.mw, E);
   const Sums4 s = vtap_sums(it, ws, pl.mh, ty, plane, pitch, b - (cb0 & ~3));
   uint32_t sw = pack4_clip8(s.s0, s.s1, s.s2, s.s3);  // (`clip8(a) | clip8(b) << 8 ...` of one word is what hipcc miscompiles: aa_common.h)
-  if (AL && (it.reserved & 2)) sw = straight_bytes(it, ws, pl.mh, ty, plane, planes, E, pitch, b - (cb0 & ~3), sw);
+  if (AL && (it.flags & AA_MANY_ITEM_ALPHA)) sw = straight_bytes(it, ws, pl.mh, ty, plane, planes, E, pitch, b - (cb0 & ~3), sw);
   uint32_t mask = 0;
 #pragma unroll
   for (int q = 0; q < 4; q++)
@@ -323,7 +323,7 @@ __global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const
   if (PL) {
     const uint32_t w = placed_bytes<AL>(it, places[u / planes], ws, fill, plane, planes, E, y, b);
     r0b = w & 255u; r1b = (w >> 8) & 255u; r2b = (w >> 16) & 255u; r3b = w >> 24;
-  } else if (AL && (it.reserved & 2)) {
+  } else if (AL && (it.flags & AA_MANY_ITEM_ALPHA)) {
     const int64_t pitch = aa_many_inter_pitch(oW, E);
     const Sums4 s = vtap_sums(it, ws, oH, y, plane, pitch, b);
     const uint32_t w = straight_bytes(it, ws, oH, y, plane, planes, E, pitch, b, pack4_clip8(s.s0, s.s1, s.s2, s.s3));
@@ -388,14 +388,14 @@ __global__ void __launch_bounds__(kVLanes<E>) many_vpass_float(const AAManyItem 
   const int j = threadIdx.x;
   const int nb = npx * E - 4 * j;  // bytes of the piece from this lane's first (4 or more: all four results exist; <= 0: none)
   if (nb <= 0) return;
-  const bool flip = (it.reserved & 1) != 0;
+  const bool flip = (it.flags & AA_MANY_ITEM_FLIP) != 0;
   const int xr = flip ? oW - x0 - npx : x0;  // the output column the piece's run(s) start at
 
   float f[4];
   if (PL) {  // (the piece starts on a dword of the canvas row: kVPixels<E> * E is a multiple of 4)
     const uint32_t w = placed_bytes<AL>(it, places[n], ws, fill, plane, planes, E, y, x0 * E + 4 * j);
     f[0] = (float)(w & 255u); f[1] = (float)((w >> 8) & 255u); f[2] = (float)((w >> 16) & 255u); f[3] = (float)(w >> 24);
-  } else if (AL && (it.reserved & 2)) {
+  } else if (AL && (it.flags & AA_MANY_ITEM_ALPHA)) {
     const int64_t pitch = aa_many_inter_pitch(oW, E), at = (int64_t)x0 * E + 4 * j;
     const Sums4 s = vtap_sums(it, ws, oH, y, plane, pitch, at);
     const uint32_t w = straight_bytes(it, ws, oH, y, plane, planes, E, pitch, at, pack4_clip8(s.s0, s.s1, s.s2, s.s3));
@@ -470,7 +470,7 @@ __global__ void __launch_bounds__(kVLanes<E>) many_vpass_patches(const AAManyIte
   const int npx = vw - x0 < PX ? vw - x0 : PX;
   const int nb = npx * E - 4 * j;  // bytes of the piece from this lane's first (4 or more: all four results exist; <= 0: none)
   if (nb <= 0) return;
-  const bool flip = (it.reserved & 1) != 0;
+  const bool flip = (it.flags & AA_MANY_ITEM_FLIP) != 0;
 
   const uint32_t w = placed_bytes<false>(it, pl, ws, 0u, plane, planes, E, y, x0 * E + 4 * j);  // (the item covers its canvas: never the fill)
   const float f[4] = {(float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), (float)(w >> 24)};
@@ -525,13 +525,13 @@ static int many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, i
                      const uint8_t *fill, bool own_canvas, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
   if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
-  const int64_t kMax = INT32_MAX / 4;
+  const int64_t kMax = kAAManyMax;
   if (n < 0 || n > kMax || C < 1 || C > 4 || oH <= 0 || oW <= 0 || oH > kMax || oW > kMax) return AA_ERR_BAD_SHAPE;
   if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
   bool placed = own_canvas;  // every item the whole canvas at offset 0 is the plain plan: nothing of the canvas is left to the fill
   for (int64_t i = 0; places && i < n; i++) {
     const aa_many_place &p = places[i];
-    if (p.vH <= 0 || p.vW <= 0 || p.vH > kMax || p.vW > kMax || p.oy < -kMax || p.oy > kMax || p.ox < -kMax || p.ox > kMax) return AA_ERR_BAD_SHAPE;
+    if (!aa_many_place_ok(p)) return AA_ERR_BAD_SHAPE;
     placed = placed || p.vH != oH || p.vW != oW || p.oy != 0 || p.ox != 0;
   }
   if (desc_bytes < (placed ? aa_many_desc_size_placed(n) : aa_many_desc_size(n))) return AA_ERR_WORKSPACE;
@@ -549,62 +549,44 @@ static int many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, i
   size_t off = 0;  // the arena first, then the intermediates
   int64_t units = 0;
   int flips = 0, alphas = 0;
+  // (straight alpha is the last of 2 or 4 channels, and a patch plan has none)
+  const int allowed_flags = AA_MANY_FLIP_X | (!own_canvas && (C == 2 || C == 4) ? AA_MANY_PREMUL_ALPHA : 0);
+  const aa_many_place whole = {oH, oW, 0, 0};
   for (int64_t i = 0; i < n; i++) {
     const aa_many_image &im = images[i];
     AAManyItem it;
     memset(&it, 0, sizeof(it));
-    if (!im.data_dev) return AA_ERR_NULL;
-    if (im.H <= 0 || im.W <= 0 || im.H > kMax || im.W > kMax) return AA_ERR_BAD_SHAPE;
-    if (im.flags & ~(AA_MANY_FLIP_X | AA_MANY_PREMUL_ALPHA)) return AA_ERR_BAD_SHAPE;
-    if ((im.flags & AA_MANY_PREMUL_ALPHA) && (own_canvas || (C != 2 && C != 4))) return AA_ERR_BAD_SHAPE;  // (straight alpha is the last of 2 or 4)
-    // (the stride of an axis of one element never matters)
-    if (layout == AA_NHWC ? ((C > 1 && im.stride_ch != 1) || (im.W > 1 && im.stride_px != C)) : (im.W > 1 && im.stride_px != 1)) return AA_ERR_STRIDES;
-    double x0 = 0.0, y0 = 0.0, x1 = (double)im.W, y1 = (double)im.H;
-    int on = 0;
-    if (im.has_box) {  // Pillow's C takes the box as floats
-      x0 = (double)(float)im.box[0]; y0 = (double)(float)im.box[1]; x1 = (double)(float)im.box[2]; y1 = (double)(float)im.box[3];
-      if (!(x0 >= 0.0) || !(y0 >= 0.0) || !(x1 <= (double)im.W) || !(y1 <= (double)im.H)) return AA_ERR_BAD_SHAPE;  // beyond the image (or NaN)
-      if (!(x1 - x0 > 0.0) || !(y1 - y0 > 0.0)) return AA_ERR_BAD_SHAPE;                                           // empty
-      on = !(x0 == 0.0 && y0 == 0.0 && x1 == (double)im.W && y1 == (double)im.H);  // a full box is no box
-    }
+    AAManyBox bx;
+    const int rc = aa_many_check_image_box(im, (im.flags & ~allowed_flags) == 0, layout, C, 1, C, &bx);
+    if (rc != AA_OK) return rc;
     // the item's own output size and the part [v0, v0 + m) of it that lies on the canvas, per axis (plain: all of the canvas)
-    int64_t vH = oH, vW = oW, v0h = 0, v0w = 0, mh = oH, mw = oW;
-    if (placed) {
-      const aa_many_place &p = places[i];
-      vH = p.vH; vW = p.vW;
-      v0h = p.oy < 0 ? -p.oy : 0;
-      v0w = p.ox < 0 ? -p.ox : 0;
-      mh = (vH < oH - p.oy ? vH : oH - p.oy) - v0h;
-      mw = (vW < oW - p.ox ? vW : oW - p.ox) - v0w;
-      if (mh <= 0 || mw <= 0) mh = mw = 0;  // off the canvas: all fill, no table, no work unit
-      AAManyPlace pl = {(int32_t)vH, (int32_t)vW, (int32_t)(mh ? v0h : 0), (int32_t)(mh ? v0w : 0), (int32_t)mh, (int32_t)mw,
-                        (int32_t)(mh ? v0h + p.oy : 0), (int32_t)(mh ? v0w + p.ox : 0)};
-      pls[i] = pl;
-    }
+    const AAManyPlace pl = aa_many_cover(placed ? places[i] : whole, oH, oW);
+    if (placed) pls[i] = pl;
+    const int64_t vH = pl.vh, vW = pl.vw, v0h = pl.v0h, v0w = pl.v0w, mh = pl.mh, mw = pl.mw;  // (off the canvas: no table, no work unit)
     int64_t oy = 0, ey = 0, ox = 0, ex = 0;
     int kh = 0, kw = 0;
     if (mh > 0) {
-      axis_hull(filter, im.H, vH, y0, y1, on, v0h, v0h + mh, &oy, &ey);
-      axis_hull(filter, im.W, vW, x0, x1, on, v0w, v0w + mw, &ox, &ex);
+      axis_hull(filter, im.H, vH, bx.y0, bx.y1, bx.on, v0h, v0h + mh, &oy, &ey);
+      axis_hull(filter, im.W, vW, bx.x0, bx.x1, bx.on, v0w, v0w + mw, &ox, &ex);
       if (ey <= oy || ex <= ox) return AA_ERR_BAD_SHAPE;
-      kh = on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ey - oy, vH, y0, y1) : aa_table_ksize(filter, AA_TABLE_PIL, im.H, vH, 0, 0.0);
+      kh = bx.on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ey - oy, vH, bx.y0, bx.y1) : aa_table_ksize(filter, AA_TABLE_PIL, im.H, vH, 0, 0.0);
       if (kh < 0) return kh;
-      kw = on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ex - ox, vW, x0, x1) : aa_table_ksize(filter, AA_TABLE_PIL, im.W, vW, 0, 0.0);
+      kw = bx.on ? aa_table_ksize_box(filter, AA_TABLE_PIL, ex - ox, vW, bx.x0, bx.x1) : aa_table_ksize(filter, AA_TABLE_PIL, im.W, vW, 0, 0.0);
       if (kw < 0) return kw;
     }
     it.src = (const uint8_t *)im.data_dev;
     it.row_stride = im.stride_row;
     it.plane_stride = layout == AA_NHWC ? 0 : (C > 1 ? im.stride_ch : 0);
-    it.in0_h = y0; it.in1_h = y1; it.in0_w = x0; it.in1_w = x1;
+    it.in0_h = bx.y0; it.in1_h = bx.y1; it.in0_w = bx.x0; it.in1_w = bx.x1;
     it.oy = (int32_t)oy; it.hull_h = (int32_t)(ey - oy); it.ox = (int32_t)ox; it.hull_w = (int32_t)(ex - ox);
     it.ksize_h = kh; it.ksize_w = kw;
-    it.box_on = on;
-    it.reserved = im.flags & AA_MANY_FLIP_X;
-    flips |= it.reserved;
+    it.box_on = bx.on;
+    it.flags = im.flags & AA_MANY_ITEM_FLIP;
+    flips |= it.flags;
     // Image.resize returns self.copy() before it looks at the mode where the size asked for is the image's and the box is the whole
     // image: such an item is never premultiplied (the round trip loses colour at low alpha); its windows are one tap of weight 1
-    if ((im.flags & AA_MANY_PREMUL_ALPHA) && !(on == 0 && vH == im.H && vW == im.W)) {
-      it.reserved |= 2;
+    if ((im.flags & AA_MANY_PREMUL_ALPHA) && !(bx.on == 0 && vH == im.H && vW == im.W)) {
+      it.flags |= AA_MANY_ITEM_ALPHA;
       alphas = 1;
     }
     it.tab_h = (int64_t)off;
@@ -625,14 +607,14 @@ static int many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, i
   hd->magic = AA_MANY_MAGIC;
   hd->n = (int32_t)n; hd->C = (int32_t)C; hd->oH = (int32_t)oH; hd->oW = (int32_t)oW;
   hd->filter = filter; hd->layout = layout;
-  hd->reserved0 = flips;
+  hd->flips = flips;
   hd->hunits = units;
   hd->ws_bytes = (int64_t)off;
   if (placed) {
-    hd->reserved[0] = 1;
-    for (int c = 0; fill && c < 4; c++) hd->reserved[1] |= (int64_t)fill[c] << (8 * c);
+    hd->kind = AA_MANY_PLAN_PLACED;
+    for (int c = 0; fill && c < 4; c++) hd->fill |= (int64_t)fill[c] << (8 * c);
   }
-  if (alphas) hd->reserved[0] |= 4;
+  if (alphas) hd->kind |= AA_MANY_PLAN_ALPHA;
   *workspace_bytes = off;
   return AA_OK;
 }
@@ -647,7 +629,7 @@ static int64_t *patch_tail(const void *desc, int64_t n) { return (int64_t *)((ch
 
 int aa_many_plan_patches_host(int filter, int layout, int64_t n, int64_t C, int64_t ph, int64_t pw, const aa_many_image *images, const int64_t *sizes,
                               int64_t pad_to, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, int64_t *rows) {
-  const int64_t kMax = INT32_MAX / 4;
+  const int64_t kMax = kAAManyMax;
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   if (n < 0 || n > kMax || C < 1 || C > 4 || ph < 1 || pw < 1 || ph > kMax || pw > kMax || pad_to < 0 || pad_to > INT32_MAX) return AA_ERR_BAD_SHAPE;
   if (!desc_host || !workspace_bytes || !rows || (n > 0 && (!images || !sizes))) return AA_ERR_NULL;
@@ -683,7 +665,7 @@ int aa_many_plan_patches_host(int filter, int layout, int64_t n, int64_t C, int6
   delete[] places;
   if (rc != AA_OK) return rc;
   AAManyHeader *hd = (AAManyHeader *)desc_host;
-  hd->reserved[0] |= 2;
+  hd->kind |= AA_MANY_PLAN_PATCHES;
   AAManyPatchInfo *info = (AAManyPatchInfo *)(tok0 + n + 1);
   info->ph = (int32_t)ph; info->pw = (int32_t)pw; info->pad_to = pad_to;
   *rows = tok0[n];
@@ -701,43 +683,52 @@ static int many_check(const AAManyHeader *hd, const void *desc_dev, int64_t n, i
   return AA_OK;
 }
 
-// Some item of the plan is resampled premultiplied (AAManyItem.reserved bit 1): the AL instantiations.  The planner sets the bit for
+// Some item of the plan is resampled premultiplied (AA_MANY_ITEM_ALPHA): the AL instantiations.  The planner sets the bit for
 // C = 2 or 4 only.
-static bool many_alpha(const AAManyHeader *hd) { return (hd->reserved[0] & 4) != 0 && (hd->C == 2 || hd->C == 4); }
+static bool many_alpha(const AAManyHeader *hd) { return (hd->kind & AA_MANY_PLAN_ALPHA) != 0 && (hd->C == 2 || hd->C == 4); }
+
+// What the launches take from a checked plan: the bytes per pixel of a row and the planes of its class, and the device copy's records
+// (the placement records follow the prefix sums: a placed plan only, else null).
+struct ManyViews {
+  int E, planes;
+  const AAManyItem *items;
+  const int64_t *prefix;
+  const AAManyPlace *places;
+};
+static ManyViews many_views(const AAManyHeader *hd, const void *desc_dev) {
+  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
+  const int64_t *prefix = (const int64_t *)(items + hd->n);
+  const bool nhwc = hd->layout == AA_NHWC;
+  return {nhwc ? hd->C : 1, nhwc ? 1 : hd->C, items, prefix,
+          (hd->kind & AA_MANY_PLAN_PLACED) ? (const AAManyPlace *)(prefix + hd->n + 1) : nullptr};
+}
 
 template <int E, bool PL, bool AL>
-static void launch_hpass(const AAManyHeader *hd, const AAManyItem *items, const AAManyPlace *places, const int64_t *prefix, char *ws, int64_t n,
-                         int64_t oW, int planes, hipStream_t stream) {
+static void launch_hpass(const AAManyHeader *hd, const ManyViews &v, char *ws, int64_t oW, hipStream_t stream) {
   if (hd->hunits == 0) return;  // (a placed plan whose items all lie off the canvas)
-  hipLaunchKernelGGL((many_hpass<E, PL, AL>), dim3((unsigned)hd->hunits), dim3(AA_MANY_STRIP * E), 0, stream, items, places, prefix, ws, (int)n, (int)oW,
-                     planes);
+  hipLaunchKernelGGL((many_hpass<E, PL, AL>), dim3((unsigned)hd->hunits), dim3(AA_MANY_STRIP * E), 0, stream, v.items, v.places, v.prefix, ws, (int)hd->n,
+                     (int)oW, v.planes);
 }
 
 template <bool PL>
-static void launch_many_tables_hpass(const AAManyHeader *hd, const AAManyItem *items, const AAManyPlace *places, const int64_t *prefix, char *ws,
-                                     int64_t n, int64_t oH, int64_t oW, int E, int planes, hipStream_t stream) {
-  const int64_t tthreads = n * (oH + oW);
-  hipLaunchKernelGGL(many_tables<PL>, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, items, places, ws, n, (int)oH, (int)oW,
+static void launch_many_tables_hpass(const AAManyHeader *hd, const ManyViews &v, char *ws, int64_t oH, int64_t oW, hipStream_t stream) {
+  const int64_t n = hd->n, tthreads = n * (oH + oW);
+  hipLaunchKernelGGL(many_tables<PL>, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, v.items, v.places, ws, n, (int)oH, (int)oW,
                      hd->filter);
   if (many_alpha(hd)) {  // (C is 2 or 4: E is 1, 2 or 4)
-    switch (E) {
-      case 1: launch_hpass<1, PL, true>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
-      case 2: launch_hpass<2, PL, true>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
-      default: launch_hpass<4, PL, true>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+    switch (v.E) {
+      case 1: launch_hpass<1, PL, true>(hd, v, ws, oW, stream); break;
+      case 2: launch_hpass<2, PL, true>(hd, v, ws, oW, stream); break;
+      default: launch_hpass<4, PL, true>(hd, v, ws, oW, stream); break;
     }
     return;
   }
-  switch (E) {
-    case 1: launch_hpass<1, PL, false>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
-    case 2: launch_hpass<2, PL, false>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
-    case 3: launch_hpass<3, PL, false>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
-    default: launch_hpass<4, PL, false>(hd, items, places, prefix, ws, n, oW, planes, stream); break;
+  switch (v.E) {
+    case 1: launch_hpass<1, PL, false>(hd, v, ws, oW, stream); break;
+    case 2: launch_hpass<2, PL, false>(hd, v, ws, oW, stream); break;
+    case 3: launch_hpass<3, PL, false>(hd, v, ws, oW, stream); break;
+    default: launch_hpass<4, PL, false>(hd, v, ws, oW, stream); break;
   }
-}
-
-// The device copy's placement records (a placed plan: they follow the prefix sums) and the plan's fill.
-static const AAManyPlace *many_places(const AAManyHeader *hd, const int64_t *prefix_dev, int64_t n) {
-  return (hd->reserved[0] & 1) ? (const AAManyPlace *)(prefix_dev + n + 1) : nullptr;
 }
 
 int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, int64_t C, int64_t oH, int64_t oW, int layout, void *out_dev,
@@ -745,28 +736,33 @@ int aa_launch_many_u8(const void *desc_host, const void *desc_dev, int64_t n, in
   const AAManyHeader *hd = (const AAManyHeader *)desc_host;
   const int rc = many_check(hd, desc_dev, n, C, oH, oW, layout, workspace_dev, workspace_bytes);
   if (rc != AA_OK) return rc;
-  if (hd->reserved0) return AA_ERR_BAD_SHAPE;  // an item flips: the uint8 pass does not
+  if (hd->flips) return AA_ERR_BAD_SHAPE;  // an item flips: the uint8 pass does not
   if (n == 0) return AA_OK;
-  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
-  const int64_t *prefix = (const int64_t *)(items + n);
-  const int E = layout == AA_NHWC ? (int)C : 1;
-  const int planes = layout == AA_NHWC ? 1 : (int)C;
+  const ManyViews v = many_views(hd, desc_dev);
+  const int E = v.E, planes = v.planes;
   char *ws = (char *)workspace_dev;
-  const AAManyPlace *places = many_places(hd, prefix, n);
   const int vstrips = (int)((oW * E + AA_MANY_VBYTES - 1) / AA_MANY_VBYTES);
   const dim3 vgrid((unsigned)(n * planes * oH * vstrips));
   const bool al = many_alpha(hd);
-  if (places) {
-    launch_many_tables_hpass<true>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
-    hipLaunchKernelGGL((al ? many_vpass<true, true> : many_vpass<true, false>), vgrid, dim3(256), 0, stream, items, places, (const char *)ws,
-                       (uint8_t *)out_dev, (int)oH, (int)oW, planes, E, vstrips, (uint32_t)hd->reserved[1]);
+  if (v.places) {
+    launch_many_tables_hpass<true>(hd, v, ws, oH, oW, stream);
+    hipLaunchKernelGGL((al ? many_vpass<true, true> : many_vpass<true, false>), vgrid, dim3(256), 0, stream, v.items, v.places, (const char *)ws,
+                       (uint8_t *)out_dev, (int)oH, (int)oW, planes, E, vstrips, (uint32_t)hd->fill);
   } else {
-    launch_many_tables_hpass<false>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
-    hipLaunchKernelGGL((al ? many_vpass<false, true> : many_vpass<false, false>), vgrid, dim3(256), 0, stream, items, places, (const char *)ws,
+    launch_many_tables_hpass<false>(hd, v, ws, oH, oW, stream);
+    hipLaunchKernelGGL((al ? many_vpass<false, true> : many_vpass<false, false>), vgrid, dim3(256), 0, stream, v.items, v.places, (const char *)ws,
                        (uint8_t *)out_dev, (int)oH, (int)oW, planes, E, vstrips, 0u);
   }
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
+}
+
+// The conversion of both converting passes: no normalisation is mean 0, std 1, never read.
+static ManyConvert many_convert(int normalize, const float *mean, const float *std, int64_t C) {
+  ManyConvert cv;
+  cv.normalize = normalize ? 1 : 0;
+  for (int i = 0; i < 4; i++) { cv.mean[i] = normalize && i < C ? mean[i] : 0.f; cv.std[i] = normalize && i < C ? std[i] : 1.f; }
+  return cv;
 }
 
 // What the converting pass is launched with besides its template arguments.
@@ -825,21 +821,16 @@ int aa_launch_many_float(const void *desc_host, const void *desc_dev, int64_t n,
   if (rc != AA_OK) return rc;
   if ((uintptr_t)out_dev & (out_elem == AA_F32 ? 3 : 1)) return AA_ERR_BAD_SHAPE;
   if (n == 0) return AA_OK;
-  const int E = layout == AA_NHWC ? (int)C : 1;
-  const int planes = layout == AA_NHWC ? 1 : (int)C;
+  const ManyViews v = many_views(hd, desc_dev);
+  const int E = v.E, planes = v.planes;
   const bool xl = out_layout != layout && C > 1;  // (one channel: the two layouts are the same bytes)
   const int64_t px = E == 1 ? kVPixels<1> : (E == 2 ? kVPixels<2> : kVPixels<4>);
   if (n * planes * oH * ((oW + px - 1) / px) > INT32_MAX) return AA_ERR_BAD_SHAPE;  // (the grid of the converting pass)
-  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
-  const int64_t *prefix = (const int64_t *)(items + n);
   char *ws = (char *)workspace_dev;
-  ManyConvert cv;
-  cv.normalize = normalize ? 1 : 0;
-  for (int i = 0; i < 4; i++) { cv.mean[i] = normalize && i < C ? mean[i] : 0.f; cv.std[i] = normalize && i < C ? std[i] : 1.f; }
-  const AAManyPlace *places = many_places(hd, prefix, n);
-  if (places) launch_many_tables_hpass<true>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
-  else launch_many_tables_hpass<false>(hd, items, places, prefix, ws, n, oH, oW, E, planes, stream);
-  const ManyFloatArgs a = {items, places, ws, out_dev, n, oH, oW, planes, cv, (uint32_t)hd->reserved[1], many_alpha(hd), stream};
+  if (v.places) launch_many_tables_hpass<true>(hd, v, ws, oH, oW, stream);
+  else launch_many_tables_hpass<false>(hd, v, ws, oH, oW, stream);
+  const ManyFloatArgs a = {v.items, v.places, ws, out_dev, n, oH, oW, planes, many_convert(normalize, mean, std, C), (uint32_t)hd->fill,
+                           many_alpha(hd), stream};
   if (out_elem == AA_F16) launch_vpass_float_e<f16_t>(E, xl, a);
   else if (out_elem == AA_BF16) launch_vpass_float_e<bf16_t>(E, xl, a);
   else launch_vpass_float_e<float>(E, xl, a);
@@ -883,33 +874,27 @@ static void launch_vpass_patches_e(int E, bool ppc, const ManyPatchArgs &a) {
 int aa_launch_many_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int out_elem,
                            int ppc, int normalize, const float *mean, const float *std, hipStream_t stream) {
   const AAManyHeader *hd = (const AAManyHeader *)desc_host;
-  if (hd->magic != AA_MANY_MAGIC || (hd->reserved[0] & 7) != 3 || hd->n < 0 || hd->C < 1 || hd->C > 4) return AA_ERR_BAD_SHAPE;  // not a patch plan
+  const int64_t patch_plan = AA_MANY_PLAN_PLACED | AA_MANY_PLAN_PATCHES;  // (and no AA_MANY_PLAN_ALPHA)
+  if (hd->magic != AA_MANY_MAGIC || (hd->kind & (patch_plan | AA_MANY_PLAN_ALPHA)) != patch_plan || hd->n < 0 || hd->C < 1 || hd->C > 4) return AA_ERR_BAD_SHAPE;
   const int64_t n = hd->n, C = hd->C;
-  const int layout = hd->layout;
   if (n == 0) return AA_OK;
   if (!desc_dev || !out_dev || !workspace_dev) return AA_ERR_NULL;
-  const int rc = many_check(hd, desc_dev, n, C, hd->oH, hd->oW, layout, workspace_dev, workspace_bytes);
+  const int rc = many_check(hd, desc_dev, n, C, hd->oH, hd->oW, hd->layout, workspace_dev, workspace_bytes);
   if (rc != AA_OK) return rc;
   if ((uintptr_t)out_dev & (out_elem == AA_F32 ? 3 : 1)) return AA_ERR_BAD_SHAPE;
   const int64_t *tail_host = patch_tail(desc_host, n);
   const AAManyPatchInfo *info = (const AAManyPatchInfo *)(tail_host + 2 * (n + 1));
   const int64_t vunits = tail_host[n];
   if (vunits <= 0 || vunits > INT32_MAX) return AA_ERR_BAD_SHAPE;
-  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
-  const int64_t *prefix = (const int64_t *)(items + n);
-  const AAManyPlace *places = (const AAManyPlace *)(prefix + n + 1);
+  const ManyViews v = many_views(hd, desc_dev);  // (a patch plan is a placed one: v.places is there)
   const int64_t *tail_dev = patch_tail(desc_dev, n);
-  const int E = layout == AA_NHWC ? (int)C : 1;
-  const int planes = layout == AA_NHWC ? 1 : (int)C;
   char *ws = (char *)workspace_dev;
-  ManyConvert cv;
-  cv.normalize = normalize ? 1 : 0;
-  for (int i = 0; i < 4; i++) { cv.mean[i] = normalize && i < C ? mean[i] : 0.f; cv.std[i] = normalize && i < C ? std[i] : 1.f; }
-  launch_many_tables_hpass<true>(hd, items, places, prefix, ws, n, hd->oH, hd->oW, E, planes, stream);
-  const ManyPatchArgs a = {items, places, tail_dev, tail_dev + n + 1, ws, out_dev, (int)n, planes, info->ph, info->pw, info->pad_to, vunits, cv, stream};
-  if (out_elem == AA_F16) launch_vpass_patches_e<f16_t>(E, ppc != 0, a);
-  else if (out_elem == AA_BF16) launch_vpass_patches_e<bf16_t>(E, ppc != 0, a);
-  else launch_vpass_patches_e<float>(E, ppc != 0, a);
+  launch_many_tables_hpass<true>(hd, v, ws, hd->oH, hd->oW, stream);
+  const ManyPatchArgs a = {v.items, v.places, tail_dev, tail_dev + n + 1, ws, out_dev, (int)n, v.planes, info->ph, info->pw, info->pad_to, vunits,
+                           many_convert(normalize, mean, std, C), stream};
+  if (out_elem == AA_F16) launch_vpass_patches_e<f16_t>(v.E, ppc != 0, a);
+  else if (out_elem == AA_BF16) launch_vpass_patches_e<bf16_t>(v.E, ppc != 0, a);
+  else launch_vpass_patches_e<float>(v.E, ppc != 0, a);
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }

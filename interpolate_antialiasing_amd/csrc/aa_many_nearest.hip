@@ -14,6 +14,7 @@
 
 #include <string.h>
 
+#include "aa_many_host.h"
 #include "aa_many_nearest.h"
 
 namespace {
@@ -185,13 +186,12 @@ int aa_near_plan_host(int layout, int elem_bytes, int64_t n, int64_t C, int64_t 
                       const aa_many_place *places, const int32_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) return AA_ERR_BAD_DTYPE;
-  const int64_t kMax = INT32_MAX / 4;
+  const int64_t kMax = kAAManyMax;
   if (n < 0 || n > kMax || C < 1 || C > 4 || oH <= 0 || oW <= 0 || oH > kMax || oW > kMax) return AA_ERR_BAD_SHAPE;
   if (elem_bytes > 1 && C != 1) return AA_ERR_BAD_SHAPE;  // (2- and 4-byte elements are single-channel id maps)
   if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
   for (int64_t i = 0; places && i < n; i++) {
-    const aa_many_place &p = places[i];
-    if (p.vH <= 0 || p.vW <= 0 || p.vH > kMax || p.vW > kMax || p.oy < -kMax || p.oy > kMax || p.ox < -kMax || p.ox > kMax) return AA_ERR_BAD_SHAPE;
+    if (!aa_many_place_ok(places[i])) return AA_ERR_BAD_SHAPE;
   }
   for (int c = 0; fill && c < C; c++) {  // what the element holds, signed or unsigned
     const int64_t lo = elem_bytes == 4 ? INT32_MIN : -((int64_t)1 << (8 * elem_bytes - 1)), hi = elem_bytes == 4 ? INT32_MAX : ((int64_t)1 << (8 * elem_bytes)) - 1;
@@ -210,51 +210,31 @@ int aa_near_plan_host(int layout, int elem_bytes, int64_t n, int64_t C, int64_t 
   AANearItem *items = (AANearItem *)(hd + 1);
   int64_t *prefix = (int64_t *)(items + n);
   size_t off = 0;
+  const aa_many_place whole = {oH, oW, 0, 0};
   for (int64_t i = 0; i < n; i++) {
     const aa_many_image &im = images[i];
     AANearItem it;
     memset(&it, 0, sizeof(it));
-    if (!im.data_dev) return AA_ERR_NULL;
-    if (im.H <= 0 || im.W <= 0 || im.H > kMax || im.W > kMax) return AA_ERR_BAD_SHAPE;
-    if (im.flags & ~AA_MANY_FLIP_X) return AA_ERR_BAD_SHAPE;
-    // (the stride of an axis of one element never matters)
-    if (layout == AA_NHWC ? ((C > 1 && im.stride_ch != 1) || (im.W > 1 && im.stride_px != PB)) : (im.W > 1 && im.stride_px != elem_bytes)) return AA_ERR_STRIDES;
-    if (((uintptr_t)im.data_dev % elem_bytes) || (im.H > 1 && im.stride_row % elem_bytes) || (planes > 1 && im.stride_ch % elem_bytes)) return AA_ERR_STRIDES;
-    double x0 = 0.0, y0 = 0.0, x1 = (double)im.W, y1 = (double)im.H;
-    if (im.has_box) {  // Pillow's C takes the box as floats
-      x0 = (double)(float)im.box[0]; y0 = (double)(float)im.box[1]; x1 = (double)(float)im.box[2]; y1 = (double)(float)im.box[3];
-      if (!(x0 >= 0.0) || !(y0 >= 0.0) || !(x1 <= (double)im.W) || !(y1 <= (double)im.H)) return AA_ERR_BAD_SHAPE;  // beyond the image (or NaN)
-      if (!(x1 - x0 > 0.0) || !(y1 - y0 > 0.0)) return AA_ERR_BAD_SHAPE;                                           // empty
-    }
+    AAManyBox bx;
+    const int rc = aa_many_check_image_box(im, (im.flags & ~AA_MANY_FLIP_X) == 0, layout, C, elem_bytes, PB, &bx);
+    if (rc != AA_OK) return rc;
     // the item's own size and the part [v0, v0 + m) of it that lies on the canvas, per axis (no places: all of the canvas)
-    int64_t vH = oH, vW = oW, v0h = 0, v0w = 0, mh = oH, mw = oW, dy = 0, dx = 0;
-    if (places) {
-      const aa_many_place &p = places[i];
-      vH = p.vH; vW = p.vW;
-      v0h = p.oy < 0 ? -p.oy : 0;
-      v0w = p.ox < 0 ? -p.ox : 0;
-      mh = (vH < oH - p.oy ? vH : oH - p.oy) - v0h;
-      mw = (vW < oW - p.ox ? vW : oW - p.ox) - v0w;
-      if (mh <= 0 || mw <= 0) mh = mw = 0;  // off the canvas: all fill, no table
-      dy = mh ? v0h + p.oy : 0;
-      dx = mh ? v0w + p.ox : 0;
-      if (!mh) v0h = v0w = 0;
-    }
+    const AAManyPlace pl = aa_many_cover(places ? places[i] : whole, oH, oW);
     const bool flip = (im.flags & AA_MANY_FLIP_X) != 0;
     it.src = (const uint8_t *)im.data_dev;
     it.row_stride = im.H > 1 ? im.stride_row : 0;
     it.plane_stride = planes > 1 ? im.stride_ch : 0;
-    near_axis(y0, y1, vH, elem_bytes == 2, &it.a_h, &it.xo0_h);
-    near_axis(x0, x1, vW, elem_bytes == 2, &it.a_w, &it.xo0_w);
+    near_axis(bx.y0, bx.y1, pl.vh, elem_bytes == 2, &it.a_h, &it.xo0_h);
+    near_axis(bx.x0, bx.x1, pl.vw, elem_bytes == 2, &it.a_w, &it.xo0_w);
     it.in_h = (int32_t)im.H; it.in_w = (int32_t)im.W;
-    it.vh = (int32_t)vH; it.vw = (int32_t)vW; it.v0h = (int32_t)v0h; it.v0w = (int32_t)v0w;
-    it.mh = (int32_t)mh; it.mw = (int32_t)mw; it.dy = (int32_t)dy; it.dx = (int32_t)dx;
-    it.dxo = (int32_t)(mw ? (flip ? oW - dx - mw : dx) : 0);
+    it.vh = pl.vh; it.vw = pl.vw; it.v0h = pl.v0h; it.v0w = pl.v0w;
+    it.mh = pl.mh; it.mw = pl.mw; it.dy = pl.dy; it.dx = pl.dx;
+    it.dxo = (int32_t)(pl.mw ? (flip ? oW - pl.dx - pl.mw : pl.dx) : 0);
     it.flags = im.flags & AA_MANY_FLIP_X;
     it.tab_h = (int64_t)off;
-    off += aa_near_tab_h_bytes(mh);
+    off += aa_near_tab_h_bytes(pl.mh);
     it.tab_w = (int64_t)off;
-    off += aa_near_tab_w_bytes((int64_t)it.dxo * UP, mw * UP, elem_bytes);
+    off += aa_near_tab_w_bytes((int64_t)it.dxo * UP, (int64_t)pl.mw * UP, elem_bytes);
     prefix[i] = i * per_item;
     items[i] = it;
   }

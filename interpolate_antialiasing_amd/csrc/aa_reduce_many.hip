@@ -9,6 +9,7 @@
 // The host planner computes, per item, the box's first byte, the result's size and 16-byte aligned place in one arena, the tiling and
 // the four multipliers (the float32 division of aa_reduce.hip): nothing is allocated, synchronised or read back.
 
+#include "aa_many_host.h"
 #include "aa_reduce_many.h"
 #include "aa_reduce_tile.h"
 
@@ -64,7 +65,7 @@ size_t aa_reduce_many_desc_size(int64_t n) {
 int aa_reduce_many_plan_host(int layout, int64_t n, int64_t C, const aa_reduce_item *in, void *desc_host, size_t desc_bytes, size_t *arena_bytes,
                              int64_t *out_offsets) {
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
-  const int64_t kMax = INT32_MAX / 4;
+  const int64_t kMax = kAAManyMax;
   if (n < 0 || n > kMax || C < 1 || C > 4) return AA_ERR_BAD_SHAPE;
   if (!desc_host || !arena_bytes || (n > 0 && (!in || !out_offsets))) return AA_ERR_NULL;
   if (desc_bytes < aa_reduce_many_desc_size(n)) return AA_ERR_WORKSPACE;
@@ -80,11 +81,8 @@ int aa_reduce_many_plan_host(int layout, int64_t n, int64_t C, const aa_reduce_i
     const aa_reduce_item &im = in[i];
     AAReduceManyItem it;
     memset(&it, 0, sizeof(it));
-    if (!im.data_dev) return AA_ERR_NULL;
-    if (im.H <= 0 || im.W <= 0 || im.H > kMax || im.W > kMax) return AA_ERR_BAD_SHAPE;
-    if (im.fx < 1 || im.fy < 1 || (int64_t)im.fx * im.fy > 65536) return AA_ERR_BAD_SHAPE;
-    // (the stride of an axis of one element never matters)
-    if (layout == AA_NHWC ? ((C > 1 && im.stride_ch != 1) || (im.W > 1 && im.stride_px != C)) : (im.W > 1 && im.stride_px != 1)) return AA_ERR_STRIDES;
+    const int rc = aa_many_check_image(im, im.fx >= 1 && im.fy >= 1 && (int64_t)im.fx * im.fy <= 65536, layout, C, 1, C);
+    if (rc != AA_OK) return rc;
     const int64_t x0 = im.box[0], y0 = im.box[1], x1 = im.box[2], y1 = im.box[3];
     if (x0 < 0 || y0 < 0 || x1 > im.W || y1 > im.H || x1 <= x0 || y1 <= y0) return AA_ERR_BAD_SHAPE;
     const int bw = (int)(x1 - x0), bh = (int)(y1 - y0);

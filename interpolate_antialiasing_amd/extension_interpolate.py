@@ -520,25 +520,28 @@ def _many_int_pair(name: str, arg: str, i: int, v):
     return int(a), int(b)
 
 
-def _many_places(name: str, place, n: int, c: int, oh: int, ow: int):
-    """sizes / offsets / fill, checked -> (None or [(vh, vw, py, px)] per item, the C fill bytes)."""
-    sizes, offsets, fill = place
+def _many_fill(name: str, fill, c: int, lo: int = 0, hi: int = 255, note: str = ""):
+    """fill of a canvas call, checked -> C ints in lo..hi.  note: what the range message adds (the dtype of a NEAREST call)."""
     try:
         fills = [fill] if not isinstance(fill, (tuple, list)) else list(fill)
         if any(isinstance(v, bool) or int(v) != v for v in fills):
             raise TypeError
     except (TypeError, ValueError):
-        raise ValueError(f"{name}(): fill must be one int or {c} ints in 0..255, got {fill!r}") from None
+        raise ValueError(f"{name}(): fill must be one int or {c} ints in {lo}..{hi}, got {fill!r}") from None
     if len(fills) == 1 and not isinstance(fill, (tuple, list)):
         fills = fills * c
     if len(fills) != c:
         raise ValueError(f"{name}(): fill must be one int or one per channel ({c}), got {len(fills)}")
     for k, v in enumerate(fills):
-        if not (0 <= v <= 255):
-            raise ValueError(f"{name}(): fill[{k}] = {v} is outside 0..255")
-    fills = [int(v) for v in fills]
+        if not (lo <= v <= hi):
+            raise ValueError(f"{name}(): fill[{k}] = {v} is outside {lo}..{hi}{note}")
+    return [int(v) for v in fills]
+
+
+def _many_places(name: str, sizes, offsets, n: int, oh: int, ow: int):
+    """sizes / offsets, checked -> None or [(vh, vw, py, px)] per item."""
     if sizes is None and offsets is None:
-        return None, fills
+        return None
     if sizes is not None and len(sizes) != n:
         raise ValueError(f"{name}(): sizes must hold one entry per image ({n}), got {len(sizes)}")
     center = isinstance(offsets, str)
@@ -563,7 +566,39 @@ def _many_places(name: str, place, n: int, c: int, oh: int, ow: int):
             if abs(py) > _MANY_MAX or abs(px) > _MANY_MAX:
                 raise ValueError(f"{name}(): offsets[{i}] = ({py}, {px}) is beyond the supported {_MANY_MAX}")
         places.append((vh, vw, py, px))
-    return places, fills
+    return places
+
+
+def _many_pack_places(places):
+    """None or [(vh, vw, py, px)] -> None or the aa_many_place records."""
+    if places is None:
+        return None
+    precs = (_lib.ManyPlace * len(places))()
+    for i, p in enumerate(places):
+        precs[i].vH, precs[i].vW, precs[i].oy, precs[i].ox = p
+    return precs
+
+
+def _many_canvas(name: str, images, output_size: Sequence[int], channels: Optional[int], empty: str = "[0, C, oh, ow]", alpha: bool = False):
+    """output_size and the images of a call with a canvas, checked in the calls' order -> (oh, ow, items, device of a batch tensor or
+    None, N, C).  alpha: the call resizes the way Pillow resizes LA / RGBA."""
+    if len(output_size) != 2:
+        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
+    oh, ow = int(output_size[0]), int(output_size[1])
+    items, dev0, n, c = _many_items(name, images, channels, empty)
+    if alpha and c not in (2, 4):
+        raise NotImplementedError(f"{name}(): alpha=True is built for 2- or 4-channel images with straight alpha last (Pillow's LA / RGBA "
+                                  f"resize), got C = {c}")
+    if not (oh > 0 and ow > 0):
+        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    return oh, ow, items, dev0, n, c
+
+
+def _many_empty_device(dev0):
+    """Where the empty result of N == 0 lives: the batch tensor's device, else the current GPU, else the CPU."""
+    if dev0 is not None:
+        return dev0
+    return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
 
 
 def _many_convert(name: str, conv: dict, n: int, c: int):
@@ -663,11 +698,11 @@ def _many_layout(items, c: int):
     return classes, c > 1 and n_inter > 0 and n_inter >= n_planar
 
 
-def _many_records(items, classes, interleaved: bool, c: int, checked, flips, alpha: bool = False):
-    """The aa_many_image records of the items in the call's class -> (records, the copies that must outlive the launches).  alpha: every
-    record asks for Pillow's RGBA / LA resize; which items are Pillow's copies instead is the planner's decision."""
-    recs = (_lib.ManyImage * len(items))()
-    keep = []
+def _many_fill_records(recs, items, classes, interleaved: bool, c: int, keep: list, eb: int = 1):
+    """Where every item lies, in the call's class, into the leading fields that aa_many_image and aa_reduce_item share: data_dev, H, W
+    and the three strides in bytes (eb per element).  Yields (i, record i) as each is written, so that the caller adds its own fields
+    in the same pass.  An item outside the class is copied into it, and the copy appended to ``keep``: it must outlive the launches
+    (the stream orders its release after them)."""
     for i, t in enumerate(items):
         if not classes[i][0 if interleaved else 1]:
             t = t.permute(1, 2, 0).contiguous().permute(2, 0, 1) if interleaved else t.contiguous()
@@ -676,18 +711,44 @@ def _many_records(items, classes, interleaved: bool, c: int, checked, flips, alp
         r.data_dev = t.data_ptr()
         r.H, r.W = int(t.shape[1]), int(t.shape[2])
         # (the stride of an axis of one element is arbitrary: hand over the class's own)
-        r.stride_ch = 1 if interleaved else (t.stride(0) if c > 1 else 0)
-        r.stride_row = t.stride(1) if r.H > 1 else 0
-        r.stride_px = (c if interleaved else 1)
+        r.stride_ch = (1 if interleaved else (t.stride(0) if c > 1 else 0)) * eb
+        r.stride_row = (t.stride(1) if r.H > 1 else 0) * eb
+        r.stride_px = (c if interleaved else 1) * eb
+        yield i, r
+
+
+def _many_records(items, classes, interleaved: bool, c: int, checked, flips, alpha: bool = False, eb: int = 1):
+    """The aa_many_image records of the items in the call's class -> (records, the copies that must outlive the launches).  alpha: every
+    record asks for Pillow's RGBA / LA resize; which items are Pillow's copies instead is the planner's decision."""
+    recs, keep = (_lib.ManyImage * len(items))(), []
+    for i, r in _many_fill_records(recs, items, classes, interleaved, c, keep, eb):
         bx = checked[i]
         if bx is not None:
             r.has_box = 1
-            r.box[0], r.box[1], r.box[2], r.box[3] = bx
+            r.box[:] = bx
         if flips is not None and flips[i]:
             r.flags = _lib.MANY_FLIP_X
         if alpha:
             r.flags |= _lib.MANY_PREMUL_ALPHA
     return recs, keep
+
+
+def _many_run(name: str, dev, desc_bytes: int, plan, alloc_out, launch):
+    """What every ragged call ends with, on `dev`: a pinned block, ``plan(desc_host, desc_bytes, byref(workspace bytes))``, the
+    non-blocking copy of the block, the workspace, the output of ``alloc_out()`` and ``launch(desc_host, desc_dev, out, workspace,
+    stream)`` on the current stream -> (out, workspace).  Whatever the launch reads besides (copies of items) the caller keeps alive
+    until this returns."""
+    with torch.cuda.device(dev):
+        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
+        ws_bytes = ctypes.c_size_t(0)
+        _lib.check(plan(desc_host.data_ptr(), desc_bytes, ctypes.byref(ws_bytes)), name)
+        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
+        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
+        ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
+        out = alloc_out()
+        rc = launch(desc_host.data_ptr(), desc_dev.data_ptr(), out, ws, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, name)
+    return out, ws
 
 
 def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes, channels: Optional[int], conv: Optional[dict],
@@ -697,24 +758,16 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
     filter_id = _lib.FILTER_IDS[mode]
-    if len(output_size) != 2:
-        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
-    oh, ow = int(output_size[0]), int(output_size[1])
-    items, dev0, n, c = _many_items(name, images, channels, "[0, C, oh, ow]")
-    if alpha and c not in (2, 4):
-        raise NotImplementedError(f"{name}(): alpha=True is built for 2- or 4-channel images with straight alpha last (Pillow's LA / RGBA "
-                                  f"resize), got C = {c}")
-    if not (oh > 0 and ow > 0):
-        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    oh, ow, items, dev0, n, c = _many_canvas(name, images, output_size, channels, alpha=alpha)
     checked = _many_check_items(name, items, c, boxes, lambda i: (oh, ow))
     cv, flips, out_dtype = None, None, torch.uint8
     if conv is not None:
         cv, flips, out_dtype = _many_convert(name, conv, n, c)
-    places, fills = _many_places(name, place, n, c, oh, ow)
+    sizes, offsets, fill = place
+    fills = _many_fill(name, fill, c)
+    places = _many_places(name, sizes, offsets, n, oh, ow)
     if n == 0:
-        if dev0 is None:
-            dev0 = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        return torch.empty((0, c, oh, ow), dtype=out_dtype, device=dev0)
+        return torch.empty((0, c, oh, ow), dtype=out_dtype, device=_many_empty_device(dev0))
     for t in items:
         _require_gpu(t, name)
     dev = items[0].device
@@ -726,58 +779,28 @@ def _resize_many(name: str, images, output_size: Sequence[int], mode: str, boxes
             out_nhwc = conv["out_format"] == "nhwc"
         cv.out_layout = _lib.NHWC if out_nhwc else _lib.NCHW
     L = _lib.load()
-    with torch.cuda.device(dev):
-        recs, keep = _many_records(items, classes, interleaved, c, checked, flips, alpha)
-        # (places that are all the whole canvas at offset 0 plan to the plain block: the tail of the larger one is then copied as it is
-        # and never read)
-        desc_bytes = L.aa_many_desc_bytes(n) if places is None else L.aa_many_desc_bytes_placed(n)
-        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
-        ws_bytes = ctypes.c_size_t(0)
-        if places is None:
-            rc = L.aa_many_plan(filter_id, layout, n, c, oh, ow, recs, desc_host.data_ptr(), desc_bytes, ctypes.byref(ws_bytes))
-        else:
-            precs = (_lib.ManyPlace * n)()
-            for i, p in enumerate(places):
-                precs[i].vH, precs[i].vW, precs[i].oy, precs[i].ox = p
-            rc = L.aa_many_plan_placed(filter_id, layout, n, c, oh, ow, recs, precs, (ctypes.c_uint8 * 4)(*fills), desc_host.data_ptr(),
-                                       desc_bytes, ctypes.byref(ws_bytes))
-        _lib.check(rc, name)
-        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
-        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
-        ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
-        out = torch.empty((n, c, oh, ow), dtype=out_dtype, device=dev,
-                          memory_format=torch.channels_last if out_nhwc else torch.contiguous_format)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    recs, keep = _many_records(items, classes, interleaved, c, checked, flips, alpha)
+    precs = _many_pack_places(places)
+    # (places that are all the whole canvas at offset 0 plan to the plain block: the tail of the larger one is then copied as it is
+    # and never read)
+    desc_bytes = L.aa_many_desc_bytes(n) if precs is None else L.aa_many_desc_bytes_placed(n)
+
+    def plan(desc, nbytes, ws_bytes):
+        if precs is None:
+            return L.aa_many_plan(filter_id, layout, n, c, oh, ow, recs, desc, nbytes, ws_bytes)
+        return L.aa_many_plan_placed(filter_id, layout, n, c, oh, ow, recs, precs, (ctypes.c_uint8 * 4)(*fills), desc, nbytes, ws_bytes)
+
+    def launch(desc_host, desc_dev, out, ws, stream):
         if cv is None:
-            rc = L.aa_resample_many_u8(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       stream)
-        else:
-            rc = L.aa_resample_many_u8_to_float(desc_host.data_ptr(), desc_dev.data_ptr(), n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(),
-                                                ws.numel(), ctypes.byref(cv), stream)
-    _lib.check(rc, name)
-    return out
+            return L.aa_resample_many_u8(desc_host, desc_dev, n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        return L.aa_resample_many_u8_to_float(desc_host, desc_dev, n, c, oh, ow, layout, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              ctypes.byref(cv), stream)
+
+    mf = torch.channels_last if out_nhwc else torch.contiguous_format
+    return _many_run(name, dev, desc_bytes, plan, lambda: torch.empty((n, c, oh, ow), dtype=out_dtype, device=dev, memory_format=mf), launch)[0]
 
 
 _NEAREST_RANGE = {torch.uint8: (0, 255), torch.int16: (-32768, 32767), torch.int32: (-2 ** 31, 2 ** 31 - 1)}  # the dtypes the call copies
-
-
-def _nearest_fill(name: str, fill, c: int, dtype: torch.dtype):
-    """fill of resize_many_nearest, checked -> C ints within the dtype's range."""
-    lo, hi = _NEAREST_RANGE[dtype]
-    try:
-        fills = [fill] if not isinstance(fill, (tuple, list)) else list(fill)
-        if any(isinstance(v, bool) or int(v) != v for v in fills):
-            raise TypeError
-    except (TypeError, ValueError):
-        raise ValueError(f"{name}(): fill must be one int or {c} ints in {lo}..{hi}, got {fill!r}") from None
-    if len(fills) == 1 and not isinstance(fill, (tuple, list)):
-        fills = fills * c
-    if len(fills) != c:
-        raise ValueError(f"{name}(): fill must be one int or one per channel ({c}), got {len(fills)}")
-    for k, v in enumerate(fills):
-        if not (lo <= v <= hi):
-            raise ValueError(f"{name}(): fill[{k}] = {v} is outside {lo}..{hi} ({dtype})")
-    return [int(v) for v in fills]
 
 
 def resize_many_nearest(images, output_size: Sequence[int], *, boxes=None, flips=None, channels: Optional[int] = None, sizes=None,
@@ -818,12 +841,7 @@ def resize_many_nearest(images, output_size: Sequence[int], *, boxes=None, flips
     name = "resize_many_nearest"
     if out_dtype not in (None, torch.int64):
         raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built; None (the items' dtype) or torch.int64")
-    if len(output_size) != 2:
-        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
-    oh, ow = int(output_size[0]), int(output_size[1])
-    items, dev0, n, c = _many_items(name, images, channels, "[0, C, oh, ow]")
-    if not (oh > 0 and ow > 0):
-        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    oh, ow, items, dev0, n, c = _many_canvas(name, images, output_size, channels)
     checked = _many_check_items(name, items, c, boxes, lambda i: (oh, ow), tuple(_NEAREST_RANGE))
     dtype = items[0].dtype if n else (images.dtype if isinstance(images, torch.Tensor) and images.dtype in _NEAREST_RANGE else torch.uint8)
     if out_dtype is torch.int64 and c != 1:
@@ -832,13 +850,11 @@ def resize_many_nearest(images, output_size: Sequence[int], *, boxes=None, flips
         flips = [bool(v) for v in flips]
         if len(flips) != n:
             raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
-    places, _ = _many_places(name, (sizes, offsets, 0), n, c, oh, ow)
-    fills = _nearest_fill(name, fill, c, dtype)
+    places = _many_places(name, sizes, offsets, n, oh, ow)
+    fills = _many_fill(name, fill, c, *_NEAREST_RANGE[dtype], note=f" ({dtype})")
     res_dtype = dtype if out_dtype is None else out_dtype
     if n == 0:
-        if dev0 is None:
-            dev0 = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        return torch.empty((0, c, oh, ow), dtype=res_dtype, device=dev0)
+        return torch.empty((0, c, oh, ow), dtype=res_dtype, device=_many_empty_device(dev0))
     for t in items:
         _require_gpu(t, name)
     dev = items[0].device
@@ -846,31 +862,16 @@ def resize_many_nearest(images, output_size: Sequence[int], *, boxes=None, flips
     layout = _lib.NHWC if interleaved else _lib.NCHW
     eb = items[0].element_size()
     L = _lib.load()
-    with torch.cuda.device(dev):
-        recs, keep = _many_records(items, classes, interleaved, c, checked, flips)
-        for r in recs:  # (the records hold strides in elements; the library takes bytes)
-            r.stride_row, r.stride_px, r.stride_ch = r.stride_row * eb, r.stride_px * eb, r.stride_ch * eb
-        desc_bytes = L.aa_many_desc_bytes_nearest(n)
-        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
-        ws_bytes = ctypes.c_size_t(0)
-        precs = None
-        if places is not None:
-            precs = (_lib.ManyPlace * n)()
-            for i, p in enumerate(places):
-                precs[i].vH, precs[i].vW, precs[i].oy, precs[i].ox = p
-        rc = L.aa_many_plan_nearest(layout, eb, n, c, oh, ow, recs, precs, (ctypes.c_int32 * 4)(*(fills + [0] * (4 - c))), desc_host.data_ptr(),
-                                    desc_bytes, ctypes.byref(ws_bytes))
-        _lib.check(rc, name)
-        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
-        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
-        ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
-        out = torch.empty((n, c, oh, ow), dtype=res_dtype, device=dev,
-                          memory_format=torch.channels_last if interleaved else torch.contiguous_format)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = L.aa_resample_many_nearest(desc_host.data_ptr(), desc_dev.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        out.element_size(), stream)
-    _lib.check(rc, name)
-    return out
+    recs, keep = _many_records(items, classes, interleaved, c, checked, flips, eb=eb)  # (the library takes strides in bytes)
+    precs = _many_pack_places(places)
+    cfill = (ctypes.c_int32 * 4)(*(fills + [0] * (4 - c)))
+    mf = torch.channels_last if interleaved else torch.contiguous_format
+    return _many_run(
+        name, dev, L.aa_many_desc_bytes_nearest(n),
+        lambda desc, nbytes, ws_bytes: L.aa_many_plan_nearest(layout, eb, n, c, oh, ow, recs, precs, cfill, desc, nbytes, ws_bytes),
+        lambda: torch.empty((n, c, oh, ow), dtype=res_dtype, device=dev, memory_format=mf),
+        lambda desc_host, desc_dev, out, ws, stream: L.aa_resample_many_nearest(desc_host, desc_dev, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                                                out.element_size(), stream))[0]
 
 
 def _patch_sizes(name: str, sizes, patch, n: int, pad_to):
@@ -957,9 +958,7 @@ def resize_many_to_patches(images, patch: Sequence[int], mode: str = "bicubic", 
     rows = boxmath.token_offsets(sizes, (ph, pw))[-1]
     shape = (rows, d) if pad_to is None else (n, pad_to, d)
     if n == 0:
-        if dev0 is None:
-            dev0 = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        return torch.empty(shape, dtype=out_dtype, device=dev0)
+        return torch.empty(shape, dtype=out_dtype, device=_many_empty_device(dev0))
     for t in items:
         _require_gpu(t, name)
     dev = items[0].device
@@ -967,24 +966,20 @@ def resize_many_to_patches(images, patch: Sequence[int], mode: str = "bicubic", 
     layout = _lib.NHWC if interleaved else _lib.NCHW
     cv.out_layout = _lib.NCHW  # (not looked at: the token layout is patch_format)
     L = _lib.load()
-    with torch.cuda.device(dev):
-        recs, keep = _many_records(items, classes, interleaved, c, checked, flips)
-        flat = (ctypes.c_int64 * (2 * n))(*[v for s in sizes for v in s])
-        desc_bytes = L.aa_many_desc_bytes_patches(n)
-        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
-        ws_bytes, out_rows = ctypes.c_size_t(0), ctypes.c_int64(0)
-        _lib.check(L.aa_many_plan_patches(filter_id, layout, n, c, ph, pw, recs, flat, pad_to or 0, desc_host.data_ptr(), desc_bytes,
-                                          ctypes.byref(ws_bytes), ctypes.byref(out_rows)), name)
-        assert out_rows.value == (rows if pad_to is None else n * pad_to), (out_rows.value, rows, pad_to)
-        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
-        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
-        ws = torch.empty(max(ws_bytes.value, 16), dtype=torch.uint8, device=dev)
-        out = torch.empty(shape, dtype=out_dtype, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = L.aa_resample_many_u8_to_patches(desc_host.data_ptr(), desc_dev.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), ctypes.byref(cv),
-                                              _lib.PATCH_PPC if patch_format == "ppc" else _lib.PATCH_CPP, stream)
-    _lib.check(rc, name)
-    return out
+    recs, keep = _many_records(items, classes, interleaved, c, checked, flips)
+    flat = (ctypes.c_int64 * (2 * n))(*[v for s in sizes for v in s])
+    out_rows = ctypes.c_int64(0)
+
+    def plan(desc, nbytes, ws_bytes):
+        rc = L.aa_many_plan_patches(filter_id, layout, n, c, ph, pw, recs, flat, pad_to or 0, desc, nbytes, ws_bytes, ctypes.byref(out_rows))
+        assert rc < 0 or out_rows.value == (rows if pad_to is None else n * pad_to), (out_rows.value, rows, pad_to)
+        return rc
+
+    fmt = _lib.PATCH_PPC if patch_format == "ppc" else _lib.PATCH_CPP
+    return _many_run(
+        name, dev, L.aa_many_desc_bytes_patches(n), plan, lambda: torch.empty(shape, dtype=out_dtype, device=dev),
+        lambda desc_host, desc_dev, out, ws, stream: L.aa_resample_many_u8_to_patches(desc_host, desc_dev, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                                                      ctypes.byref(cv), fmt, stream))[0]
 
 
 def _reduce_many_factors(name: str, factors, n: int):
@@ -1031,33 +1026,15 @@ def _reduce_many_launch(name: str, items, c: int, factors, rboxes):
     classes, interleaved = _many_layout(items, c)
     layout = _lib.NHWC if interleaved else _lib.NCHW
     L = _lib.load()
-    with torch.cuda.device(dev):
-        recs = (_lib.ReduceItem * n)()
-        keep = []  # (copies of items outside the class: the stream orders their release after the launch)
-        for i, t in enumerate(items):
-            if not classes[i][0 if interleaved else 1]:
-                t = t.permute(1, 2, 0).contiguous().permute(2, 0, 1) if interleaved else t.contiguous()
-                keep.append(t)
-            r = recs[i]
-            r.data_dev = t.data_ptr()
-            r.H, r.W = int(t.shape[1]), int(t.shape[2])
-            # (the stride of an axis of one element is arbitrary: hand over the class's own)
-            r.stride_ch = 1 if interleaved else (t.stride(0) if c > 1 else 0)
-            r.stride_row = t.stride(1) if r.H > 1 else 0
-            r.stride_px = c if interleaved else 1
-            r.box[0], r.box[1], r.box[2], r.box[3] = rboxes[i]
-            r.fx, r.fy = factors[i]
-        desc_bytes = L.aa_reduce_many_desc_bytes(n)
-        desc_host = torch.empty(desc_bytes, dtype=torch.uint8, pin_memory=True)  # (the caching host allocator)
-        arena_bytes = ctypes.c_size_t(0)
-        offs = (ctypes.c_int64 * n)()
-        _lib.check(L.aa_reduce_many_plan(layout, n, c, recs, desc_host.data_ptr(), desc_bytes, ctypes.byref(arena_bytes), offs), name)
-        desc_dev = torch.empty(desc_bytes, dtype=torch.uint8, device=dev)
-        desc_dev.copy_(desc_host, non_blocking=True)  # (the host allocator holds the block until the copy has run)
-        arena = torch.empty(max(arena_bytes.value, 16), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = L.aa_reduce_many_u8(desc_host.data_ptr(), desc_dev.data_ptr(), arena.data_ptr(), arena.numel(), stream)
-    _lib.check(rc, name)
+    recs, keep = (_lib.ReduceItem * n)(), []  # (keep: the copies of items outside the class, alive until the launch is enqueued)
+    for i, r in _many_fill_records(recs, items, classes, interleaved, c, keep):
+        r.box[:] = rboxes[i]
+        r.fx, r.fy = factors[i]
+    offs = (ctypes.c_int64 * n)()
+    # (the call's workspace is its result: the arena)
+    arena = _many_run(name, dev, L.aa_reduce_many_desc_bytes(n),
+                      lambda desc, nbytes, arena_bytes: L.aa_reduce_many_plan(layout, n, c, recs, desc, nbytes, arena_bytes, offs), lambda: None,
+                      lambda desc_host, desc_dev, _, ws, stream: L.aa_reduce_many_u8(desc_host, desc_dev, ws.data_ptr(), ws.numel(), stream))[1]
     views = []
     for i in range(n):
         rw, rh = boxmath.reduced_size(rboxes[i], factors[i])
@@ -1126,13 +1103,8 @@ def reduce_many_for_resize(images, output_size: Sequence[int], mode: str = "bili
         raise NotImplementedError(f"{name}(): uint8_mode='harness' is not built for a list of images (Pillow's arithmetic only)")
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
-    if len(output_size) != 2:
-        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
-    oh, ow = int(output_size[0]), int(output_size[1])
-    items, dev0, n, c = _many_items(name, images, _reduce_many_channels(images, channels), "[]")
+    oh, ow, items, dev0, n, c = _many_canvas(name, images, output_size, _reduce_many_channels(images, channels), "[]")
     same = items if isinstance(images, torch.Tensor) else list(images)  # (what comes back for an item that is not reduced)
-    if not (oh > 0 and ow > 0):
-        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
     if sizes is not None:
         if len(sizes) != n:
             raise ValueError(f"{name}(): sizes must hold one entry per image ({n}), got {len(sizes)}")

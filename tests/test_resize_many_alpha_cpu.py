@@ -85,7 +85,7 @@ def _plan(layout, c, oh, ow, items, flags, places=None, fill=None, f="cubic"):
         fl = (ctypes.c_uint8 * 4)(*(list(fill or []) + [0] * (4 - len(fill or []))))
         rc = L.aa_many_plan_placed(FILTER_IDS[f], layout, n, c, oh, ow, recs, precs, fl, ctypes.addressof(buf), nbytes, ctypes.byref(ws))
     hd, its, prefix = _lib.many_desc_view(buf, n)
-    pls = _lib.many_placed_view(buf, n) if (rc == 0 and hd.reserved[0] & 1) else None
+    pls = _lib.many_placed_view(buf, n) if (rc == 0 and hd.kind & _lib.MANY_PLAN_PLACED) else None
     return rc, hd, its, prefix, pls, ws.value, buf
 
 
@@ -101,12 +101,12 @@ ONE = [(20, 30, None)]
 def test_plan_accepts_the_flag_for_two_and_four_channels(layout, c):
     rc, hd, its, _, _, _, _ = _plan(layout, c, 10, 10, ONE, [ALPHA])
     assert rc == 0, _lib.load().aa_strerror(rc)
-    assert its[0].reserved == 2 and hd.reserved[0] == 4 and hd.reserved0 == 0
+    assert its[0].flags == _lib.MANY_ITEM_ALPHA and hd.kind == _lib.MANY_PLAN_ALPHA and hd.flips == 0
     rc, hd, its, _, _, _, _ = _plan(layout, c, 10, 10, ONE * 3, [0, ALPHA | FLIP, FLIP])
     assert rc == 0
-    assert [it.reserved for it in its] == [0, 3, 1] and hd.reserved[0] == 4 and hd.reserved0 == 1
+    assert [it.flags for it in its] == [0, _lib.MANY_ITEM_FLIP | _lib.MANY_ITEM_ALPHA, _lib.MANY_ITEM_FLIP] and hd.kind == _lib.MANY_PLAN_ALPHA and hd.flips == 1
     rc, hd, its, _, _, _, _ = _plan(layout, c, 10, 10, ONE, [0])
-    assert rc == 0 and its[0].reserved == 0 and hd.reserved[0] == 0
+    assert rc == 0 and its[0].flags == 0 and hd.kind == 0
 
 
 @pytest.mark.parametrize("layout", [_lib.NHWC, _lib.NCHW])
@@ -129,9 +129,9 @@ def test_copy_rule_plain(layout, c):
     items = [(19, 37, None), (19, 37, (0.0, 0.0, 37.0, 19.0)), (19, 37, (2.5, 1.0, 30.0, 17.5)), (40, 50, None), (19, 37, (0, 0, 37, 18.5))]
     rc, hd, its, _, _, _, _ = _plan(layout, c, 19, 37, items, [ALPHA] * 5)
     assert rc == 0
-    assert [it.reserved for it in its] == [0, 0, 2, 2, 2] and hd.reserved[0] == 4
+    assert [it.flags for it in its] == [0, 0, _lib.MANY_ITEM_ALPHA, _lib.MANY_ITEM_ALPHA, _lib.MANY_ITEM_ALPHA] and hd.kind == _lib.MANY_PLAN_ALPHA
     rc, hd, its, _, _, _, _ = _plan(layout, c, 19, 37, items[:2], [ALPHA | FLIP, ALPHA])  # nothing but copies: no alpha launch at all
-    assert rc == 0 and [it.reserved for it in its] == [1, 0] and hd.reserved[0] == 0 and hd.reserved0 == 1
+    assert rc == 0 and [it.flags for it in its] == [_lib.MANY_ITEM_FLIP, 0] and hd.kind == 0 and hd.flips == 1
 
 
 @pytest.mark.parametrize("layout", [_lib.NHWC, _lib.NCHW])
@@ -142,10 +142,10 @@ def test_copy_rule_placed(layout, c):
     places = [it[3] + it[4] for it in cs[5]] + [(12, 17, 0, 0)]  # the last: the canvas's size is not the item's own
     rc, hd, its, _, pls, _, _ = _plan(layout, c, 30, 45, items, [ALPHA] * 5, places=places, fill=[1, 2, 3, 4][:c])
     assert rc == 0 and pls is not None
-    assert [it.reserved for it in its] == [0, 0, 2, 2, 2] and hd.reserved[0] == 5
+    assert [it.flags for it in its] == [0, 0, _lib.MANY_ITEM_ALPHA, _lib.MANY_ITEM_ALPHA, _lib.MANY_ITEM_ALPHA] and hd.kind == _lib.MANY_PLAN_PLACED | _lib.MANY_PLAN_ALPHA
     # a placed call whose places are all the canvas plans plain: the copy rule sees (oH, oW)
     rc, hd, its, _, pls, _, _ = _plan(layout, c, 12, 17, items[:2], [ALPHA] * 2, places=[(12, 17, 0, 0)] * 2, fill=[0] * c)
-    assert rc == 0 and pls is None and [it.reserved for it in its] == [0, 0] and hd.reserved[0] == 0
+    assert rc == 0 and pls is None and [it.flags for it in its] == [0, 0] and hd.kind == 0
 
 
 @pytest.mark.parametrize("layout", [_lib.NHWC, _lib.NCHW])
@@ -160,12 +160,12 @@ def test_the_flag_changes_no_other_field(name, layout):
         assert a[0] == 0 and b[0] == 0
         assert a[5] == b[5] and a[1].ws_bytes == b[1].ws_bytes
         assert _fields(a[1], ("reserved",)) == _fields(b[1], ("reserved",))
-        assert a[1].reserved[0] == b[1].reserved[0] | 4 and a[1].reserved[1] == b[1].reserved[1]
+        assert a[1].kind == b[1].kind | _lib.MANY_PLAN_ALPHA and a[1].fill == b[1].fill
         assert list(a[3]) == list(b[3])
         for i in range(len(items)):
             assert _fields(a[2][i], ("reserved",)) == _fields(b[2][i], ("reserved",)), (name, f, i)
             h, w, box, size, _ = cs[5][i]
-            assert a[2][i].reserved == (0 if G.is_copy(h, w, size[0], size[1], box) else 2) and b[2][i].reserved == 0
+            assert a[2][i].flags == (0 if G.is_copy(h, w, size[0], size[1], box) else _lib.MANY_ITEM_ALPHA) and b[2][i].flags == 0
             if places is not None:
                 assert _fields(a[4][i]) == _fields(b[4][i])
 

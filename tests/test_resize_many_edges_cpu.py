@@ -197,7 +197,7 @@ def test_the_planner_accepts_every_case_and_counts_the_same_units(name, cls):
     for f in cs.filters:
         rc, hd, its, pls, _buf = _plan(name, f, cls)
         assert rc == 0, (name, f, cls, _lib.strerror(rc))  # (AA_ERR_KSIZE would refuse a case before the GPU ever saw it)
-        assert hd.reserved[0] == (1 if cs.kind == "placed" else 0)
+        assert hd.kind == (_lib.MANY_PLAN_PLACED if cs.kind == "placed" else 0)
         assert hd.hunits == ref.hunits(name, f, cls), (name, f, cls)
         for i in range(len(cs.items)):
             ay, ax = ref.axis(name, f, i, 0), ref.axis(name, f, i, 1)

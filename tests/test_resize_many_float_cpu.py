@@ -174,10 +174,10 @@ def test_abi_version_stays_3_and_the_symbol_is_exported():
 def test_plan_accepts_the_flip_flag_and_records_it_in_the_item():
     rc, _, hd, its, _ = _plan([0, _lib.MANY_FLIP_X, 0])
     assert rc == 0
-    assert [it.reserved for it in its] == [0, 1, 0]
-    assert hd.reserved0 == 1  # some item flips
+    assert [it.flags for it in its] == [0, _lib.MANY_ITEM_FLIP, 0]
+    assert hd.flips == 1  # some item flips
     rc, _, hd, its, _ = _plan([0, 0])
-    assert rc == 0 and [it.reserved for it in its] == [0, 0] and hd.reserved0 == 0
+    assert rc == 0 and [it.flags for it in its] == [0, 0] and hd.flips == 0
     # the flag changes nothing else of the plan
     a, b = _plan([0, 0])[3], _plan([1, 1])[3]
     for x, y in zip(a, b):

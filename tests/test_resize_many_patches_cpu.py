@@ -141,12 +141,12 @@ def test_plan_rows_units_and_records(name, layout):
         hd, its, _ = _lib.many_desc_view(buf, n)
         pls = _lib.many_placed_view(buf, n)
         vprefix, tok0 = _lib.many_patch_view(buf, n)
-        assert (hd.n, hd.C, hd.layout, hd.ws_bytes, hd.reserved[0]) == (n, c, layout, ws, 3)
+        assert (hd.n, hd.C, hd.layout, hd.ws_bytes, hd.kind) == (n, c, layout, ws, _lib.MANY_PLAN_PLACED | _lib.MANY_PLAN_PATCHES)
         assert (hd.oH, hd.oW) == (max(s[0] for s in sizes), max(s[1] for s in sizes))
         units, row = 0, 0
         for i, (vh, vw) in enumerate(sizes):
             assert (pls[i].vh, pls[i].vw, pls[i].v0h, pls[i].v0w, pls[i].mh, pls[i].mw, pls[i].dy, pls[i].dx) == (vh, vw, 0, 0, vh, vw, 0, 0)
-            assert its[i].reserved == int(items[i][4])
+            assert its[i].flags == int(items[i][4])
             assert vprefix[i] == units and tok0[i] == (i * pad_to if pad_to else row)
             units += planes * vh * ((vw + VPIXELS[e] - 1) // VPIXELS[e])
             if pad_to:

@@ -62,7 +62,8 @@ def test_center_offsets_against_literal_values():
     assert boxmath.center_offset(224, 224) == 0
     # a pad: the smaller half first
     assert boxmath.center_offset(219, 224) == 2 and boxmath.center_offset(217, 224) == 3 and boxmath.center_offset(1, 640) == 319
-    places, fills = aa._many_places("resize_many", ([(229, 231), None, (219, 300)], "center", 114), 3, 3, 224, 224)
+    places = aa._many_places("resize_many", [(229, 231), None, (219, 300)], "center", 3, 224, 224)
+    fills = aa._many_fill("resize_many", 114, 3)
     assert places == [(229, 231, -2, -4), (224, 224, 0, 0), (219, 300, 2, -38)] and fills == [114, 114, 114]
 
 
@@ -128,7 +129,7 @@ def test_plan_covered_ranges_hulls_ksizes_units_and_workspace(name, layout):
         hd, its, prefix = _lib.many_desc_view(buf, n)
         pls = _lib.many_placed_view(buf, n)
         assert (hd.n, hd.C, hd.oH, hd.oW, hd.filter, hd.layout, hd.ws_bytes) == (n, c, oh, ow, FILTER_IDS[f], layout, ws)
-        assert hd.reserved[0] == 1 and hd.reserved[1] == sum(v << (8 * k) for k, v in enumerate(fill))
+        assert hd.kind == _lib.MANY_PLAN_PLACED and hd.fill == sum(v << (8 * k) for k, v in enumerate(fill))
         spans, units = [], 0
         for i, (h, w, box, (vh, vw), (py, px)) in enumerate(items):
             it, pl = its[i], pls[i]
