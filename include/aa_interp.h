@@ -492,6 +492,35 @@ int aa_reduce_many_u8(const void *desc_host, const void *desc_dev, void *arena_d
  * 4: write only (fills dst); 5: read only (sums src). */
 int aa_probe_copy(const void *src_dev, void *dst_dev, size_t bytes, int form, aa_stream_t stream);
 
+/* The launch shape a fused family would give a problem: how many strips share a workgroup, how many row bands the image is cut into and
+ * how many workgroups are launched (csrc/aa_launch_shape.h; the tests freeze the decisions through this call).  Host arithmetic only:
+ * works without a device, the caller states the CU count and what the occupancy query would answer.  AA_ERR_NULL for a null pointer,
+ * AA_ERR_BAD_SHAPE for an unknown family or sizes no plan produces (nstrips, items, H, oH, taps, cus < 1; strips_per_block outside 1..8;
+ * AA_LAUNCH_V1: threads no positive multiple of 64).  Added without an ABI version change (additive). */
+enum aa_launch_family { AA_LAUNCH_V1 = 0, AA_LAUNCH_V3 = 1, AA_LAUNCH_F32_DOWN = 2, AA_LAUNCH_F32_UP = 3 };
+typedef struct aa_launch_shape_in {
+  int32_t family;           /* aa_launch_family */
+  int32_t nstrips;          /* strips of 64 output columns per row band (AA_LAUNCH_V1: 1) */
+  int32_t strips_per_block; /* the plan's choice, 1..8 ... */
+  int32_t spb_forced;       /* ... and whether the model must keep it */
+  int64_t items;            /* images or planes the kernel sees (AA_LAUNCH_V1: N * column bands) */
+  int64_t H, oH;
+  int32_t taps_h, taps_w;
+  uint64_t lds;             /* bytes of LDS per strip (AA_LAUNCH_V1: per workgroup) */
+  int32_t saturation;       /* AA_LAUNCH_F32_DOWN: the saturation model applies (fp32 elements) */
+  int32_t threads;          /* AA_LAUNCH_V1: threads per workgroup */
+  int32_t cus;              /* compute units of the device */
+  int32_t occupancy[9];     /* [s], s = 1..8: resident workgroups of s strips per CU as the runtime reports them, -1: the query failed */
+} aa_launch_shape_in;
+typedef struct aa_launch_shape_out {
+  int32_t strips_per_block, ybands;
+  int32_t resident;         /* resident workgroups per CU the band count was chosen with */
+  int32_t reserved;
+  int64_t groups;           /* items x ybands */
+  int64_t grid;             /* workgroups; 0: more than 2^31 - 1, the launch fails with AA_ERR_HIP */
+} aa_launch_shape_out;
+int aa_probe_launch_shape(const aa_launch_shape_in *in, aa_launch_shape_out *out);
+
 /* Kernel selection, process-wide; returns the previous setting.  1 (default): fused single-launch kernels, newest
  * design first; 2: first-generation fused kernels only (A/B measurements); 0: none.
  * With 0 every call takes the generic two-launch path — used by tests to cross-check the fused kernels against an

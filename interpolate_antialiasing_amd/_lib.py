@@ -48,7 +48,7 @@ EXPORTS = (
     "aa_abi_version", "aa_strerror", "aa_device_count", "aa_table_ksize", "aa_table_bytes", "aa_table_build_bytes", "aa_table_build",
     "aa_table_transposed_ksize", "aa_table_transpose", "aa_table_query", "aa_table_query2", "aa_table_build2", "aa_workspace_bytes", "aa_resample_fwd",
     "aa_resample_bwd", "aa_resample_bwd_atomic", "aa_workspace_bytes_bwd", "aa_resample_axis_fwd", "aa_set_fused",
-    "aa_last_variant", "aa_probe_copy", "aa_workspace_bytes_u8_to_f32", "aa_resample_fwd_u8_to_f32", "aa_set_store_form", "aa_set_plane_groups", "aa_resample_fwd_ex", "aa_resample_fwd_strided",
+    "aa_last_variant", "aa_probe_copy", "aa_probe_launch_shape", "aa_workspace_bytes_u8_to_f32", "aa_resample_fwd_u8_to_f32", "aa_set_store_form", "aa_set_plane_groups", "aa_resample_fwd_ex", "aa_resample_fwd_strided",
     "aa_workspace_bytes_ex", "aa_table_ksize_box", "aa_table_build_bytes_box", "aa_table_build_box", "aa_reduce_u8", "aa_premultiply_u8",
     "aa_unpremultiply_u8", "aa_many_desc_bytes", "aa_many_plan", "aa_resample_many_u8", "aa_resample_many_u8_to_float",
     "aa_many_desc_bytes_placed", "aa_many_plan_placed", "aa_many_desc_bytes_patches", "aa_many_plan_patches", "aa_resample_many_u8_to_patches",
@@ -158,6 +158,22 @@ class ReduceManyItem(ctypes.Structure):
                 ("bw", ctypes.c_int32), ("bh", ctypes.c_int32), ("fx", ctypes.c_int32), ("fy", ctypes.c_int32), ("rw", ctypes.c_int32),
                 ("rh", ctypes.c_int32), ("sx", ctypes.c_int32), ("xtiles", ctypes.c_int32), ("mult", ctypes.c_uint32 * 4)]
 
+
+class LaunchShapeIn(ctypes.Structure):
+    """aa_launch_shape_in: what a fused family's launch shape is chosen from (csrc/aa_launch_shape.h); occupancy[s] for s = 1..8 strips."""
+    _fields_ = [("family", ctypes.c_int32), ("nstrips", ctypes.c_int32), ("strips_per_block", ctypes.c_int32), ("spb_forced", ctypes.c_int32),
+                ("items", ctypes.c_int64), ("H", ctypes.c_int64), ("oH", ctypes.c_int64), ("taps_h", ctypes.c_int32), ("taps_w", ctypes.c_int32),
+                ("lds", ctypes.c_uint64), ("saturation", ctypes.c_int32), ("threads", ctypes.c_int32), ("cus", ctypes.c_int32),
+                ("occupancy", ctypes.c_int32 * 9)]
+
+
+class LaunchShapeOut(ctypes.Structure):
+    """aa_launch_shape_out: strips per workgroup, row bands, resident workgroups used, items x bands, workgroups (0: beyond a grid)."""
+    _fields_ = [("strips_per_block", ctypes.c_int32), ("ybands", ctypes.c_int32), ("resident", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("groups", ctypes.c_int64), ("grid", ctypes.c_int64)]
+
+
+LAUNCH_V1, LAUNCH_V3, LAUNCH_F32_DOWN, LAUNCH_F32_UP = 0, 1, 2, 3  # aa_launch_family
 
 MANY_FLIP_X = 1     # aa_many_image.flags: mirror the item's output left to right (aa_resample_many_u8_to_float only)
 MANY_PREMUL_ALPHA = 2  # aa_many_image.flags: Pillow's RGBA / LA resize of that item (C 2 or 4, straight alpha last; not for patch plans)
@@ -271,6 +287,8 @@ def load() -> ctypes.CDLL:
     L.aa_resample_fwd_u8_to_f32.restype = i32
     L.aa_probe_copy.argtypes = [vp, vp, sz, i32, vp]
     L.aa_probe_copy.restype = i32
+    L.aa_probe_launch_shape.argtypes = [ctypes.POINTER(LaunchShapeIn), ctypes.POINTER(LaunchShapeOut)]
+    L.aa_probe_launch_shape.restype = i32
     L.aa_table_ksize_box.argtypes = [i32, i32, i64, i64, dbl, dbl]
     L.aa_table_ksize_box.restype = i32
     L.aa_table_build_bytes_box.argtypes = [i32, i32, i64, i64, dbl, dbl]

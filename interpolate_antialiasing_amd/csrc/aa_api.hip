@@ -4,7 +4,10 @@
 #include <math.h>
 #include <string.h>
 
+#include <mutex>
+
 #include "aa_box.h"
+#include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_nearest.h"
 #include "aa_reduce_many.h"
@@ -246,6 +249,46 @@ int aa_device_cu_count() {
     cached[dev] = n;
   }
   return cached[dev];
+}
+
+int aa_resident_blocks(int family, const void *kern, int threads, size_t lds) {
+  // (The kernel's address is part of the key.  Until round 3 it was not, and a kernel could be sized with the register budget of whichever
+  //  instantiation had asked first with the same threads and LDS bytes — found when the plane-group kernels, whose LDS size is fixed,
+  //  ran 40 % slower after a sibling had run)
+  struct Entry { const void *kern; int dev, threads; size_t lds; int nb; };
+  constexpr int kEntries = 256;
+  struct Cache { std::mutex mu; Entry e[kEntries]; int n = 0, next = 0; };
+  static Cache caches[4];
+  Cache &c = caches[family & 3];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lock(c.mu);
+  for (int i = 0; i < c.n; i++)
+    if (c.e[i].kern == kern && c.e[i].dev == dev && c.e[i].threads == threads && c.e[i].lds == lds) return c.e[i].nb;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) != hipSuccess || nb <= 0) {
+    (void)hipGetLastError();
+    nb = -1;
+  }
+  c.e[c.next] = Entry{kern, dev, threads, lds, nb};  // (a full cache forgets its oldest entry)
+  c.next = c.next + 1 == kEntries ? 0 : c.next + 1;
+  if (c.n < kEntries) c.n++;
+  return nb;
+}
+
+aa_launch_shape_out aa_kernel_launch_shape(int family, const void *kern, int nstrips, int spb, int spb_forced, int64_t items, const AAProblem &q,
+                                           size_t lds, const int *tag, int saturation, int threads) {
+  aa_launch_shape_in in{};
+  in.family = family; in.nstrips = nstrips; in.strips_per_block = spb; in.spb_forced = spb_forced;
+  in.items = items; in.H = q.H; in.oH = q.oH; in.lds = lds; in.saturation = saturation; in.threads = threads;
+  in.taps_h = q.ah.max_taps > 0 ? q.ah.max_taps : q.ah.ksize;
+  in.taps_w = q.aw.max_taps > 0 ? q.aw.max_taps : q.aw.ksize;
+  in.cus = aa_device_cu_count();
+  struct Kern { int family; const void *kern; size_t lds; } k{family, kern, lds};
+  aa_launch_shape_out out;
+  aa_launch_shape(in, [](void *c, int s) { const Kern &k = *(const Kern *)c; return aa_resident_blocks(k.family, k.kern, 64 * s, k.lds * s); },
+                  &k, tag, &out);
+  return out;
 }
 
 extern "C" {

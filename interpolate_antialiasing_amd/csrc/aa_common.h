@@ -179,35 +179,13 @@ inline bool aa_grid_fits(int64_t units) { return units > 0 && units <= (int64_t)
 // CU count of the current device (cached); 256 on MI355X
 int aa_device_cu_count();
 // Resident workgroups per CU of `kern` at `threads` threads and `lds` bytes of dynamic LDS, cached per (kernel, device,
-// threads, lds) behind a mutex — the occupancy query costs microseconds, and a B = 1 call is ~10 us end to end.  -1 when
-// the query fails (callers fall back to an estimate; it only feeds launch-shape heuristics, never results).
-#include <mutex>
-template <typename K>
-int aa_resident_blocks(K kern, int threads, size_t lds) {
-  // (K is the kernel's function-pointer TYPE, shared by every instantiation of a kernel template: the kernel itself is part of the key.
-  //  Until round 3 it was not, and a kernel could be sized with the register budget of whichever instantiation had asked first with the
-  //  same threads and LDS bytes — found when the plane-group kernels, whose LDS size is fixed, ran 40 % slower after a sibling had run)
-  struct Entry { const void *kern; int dev, threads; size_t lds; int nb; };
-  constexpr int kEntries = 256;
-  static std::mutex mu;
-  static Entry cache[kEntries];
-  static int n = 0, next = 0;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const void *id = (const void *)kern;
-  std::lock_guard<std::mutex> lock(mu);
-  for (int i = 0; i < n; i++)
-    if (cache[i].kern == id && cache[i].dev == dev && cache[i].threads == threads && cache[i].lds == lds) return cache[i].nb;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) != hipSuccess || nb <= 0) {
-    (void)hipGetLastError();
-    nb = -1;
-  }
-  cache[next] = Entry{id, dev, threads, lds, nb};  // (a full cache forgets its oldest entry)
-  next = next + 1 == kEntries ? 0 : next + 1;
-  if (n < kEntries) n++;
-  return nb;
-}
+// threads, lds) behind a mutex, one cache of 256 entries per `family` (aa_launch_family) — the occupancy query costs microseconds,
+// and a B = 1 call is ~10 us end to end.  -1 when the query fails (the launch-shape model, aa_launch_shape.h, falls back to an
+// estimate; it only feeds launch-shape heuristics, never results).
+int aa_resident_blocks(int family, const void *kern, int threads, size_t lds);
+// Launch shape of a fused family's kernel for problem q (aa_launch_shape.h); occupancy from aa_resident_blocks of `kern`, `lds` bytes a strip
+aa_launch_shape_out aa_kernel_launch_shape(int family, const void *kern, int nstrips, int spb, int spb_forced, int64_t items, const AAProblem &q,
+                                           size_t lds, const int *tag = nullptr, int saturation = 0, int threads = 0);
 
 int aa_launch_probe_copy(const void *src, void *dst, size_t bytes, int form, hipStream_t stream);
 // scatter-add adjoint

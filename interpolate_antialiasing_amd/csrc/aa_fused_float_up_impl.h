@@ -471,74 +471,16 @@ fused_f32_nchw_up_kernel(const void *__restrict__ in, void *__restrict__ out, co
   }
 }
 
-int pick_ybands_up(int64_t items_per_band, int waves_per_item, double slots, int taps_h, int64_t H, int64_t oH) {
-  // a band re-reads ~taps_h input rows; input rows are the cheap side here, so only the round efficiency matters much
-  const int64_t max_yb = oH / 16 > 1 ? oH / 16 : 1;
-  int64_t ybands = 1;
-  double best = 1e30;
-  // Single-strip workgroups whose whole problem fits the chip in about one round: this write-bound kernel is fastest with
-  // about 20 waves per CU in flight, not with every slot filled over several rounds (measured on one box,
-  // [64,3,438,906] -> 1200x1200: 7.5 waves per CU 0.32 ms, 15 0.304-0.319, 19 0.297-0.313, 24 x 3 rounds 0.327-0.344).  Workgroups
-  // of several strips (906-wide gradients: 4 strips with the pacing barrier) measured best with the round model below.
-  const double target_waves = 20.0 * aa_device_cu_count();
-  const double waves_per_band = (double)items_per_band * waves_per_item;
-  if (waves_per_item == 1 && waves_per_band <= target_waves * 1.25 && !aa_knob("AA_FUSED_YBANDS")) {
-    int64_t yb = (int64_t)(target_waves / (waves_per_band > 0 ? waves_per_band : 1) + 0.5);
-    yb = yb < 1 ? 1 : (yb > max_yb ? max_yb : yb);
-    if (yb > 64) yb = 64;
-    return (int)yb;
-  }
-  for (int64_t yb = 1; yb <= max_yb && yb <= 64; yb++) {
-    const double rounds = (double)items_per_band * yb / slots;
-    const double eff = rounds / ceil(rounds);
-    const double halo = 1.0 + (double)(yb - 1) * taps_h / (double)(H + oH);
-    const double cost = halo / eff;
-    if (cost < best - 1e-9) {
-      best = cost;
-      ybands = yb;
-    }
-  }
-  if (const char *e = aa_knob("AA_FUSED_YBANDS")) {
-    const int64_t v = atoll(e);
-    if (v >= 1 && v <= max_yb) ybands = v;
-  }
-  return (int)ybands;
-}
-
 template <int U, int G, int KR, int CPL, int DT>
 int launch_k(FusedF32UpParams p, const AAProblem &q, size_t lds) {
   auto kern = fused_f32_nchw_up_kernel<U, G, KR, CPL, DT>;
-  auto resident = [&](int s) {  // workgroups of s strips a CU holds (-1: their rings do not fit a workgroup's LDS)
-    if (lds * s > 64 * 1024) return -1;  // (never for s == 1: a strip's ring is at most 8 KiB)
-    int nb = aa_resident_blocks(kern, 64 * s, lds * s);
-    if (nb <= 0) {  // a failed query only costs the heuristic its input: estimate from LDS and wave slots
-      nb = (int)((160 * 1024) / (lds * s > 0 ? lds * s : 1));
-      if (nb > 32 / s) nb = 32 / s;
-      if (nb < 1) nb = 1;
-    }
-    return nb;
-  };
-  // strips of a band share a workgroup unless single-strip workgroups put more waves on a CU (see aa_fused_u8_v3_impl.h)
-  int spb = p.strips_per_block;
-  if (const char *e = aa_knob("AA_UP_SPB")) {  // experiment knob
-    const int v = atoi(e);
-    if (v >= 1 && v <= 8) spb = v;
-  }
-  if (spb > 1 && (resident(spb) < 0 || resident(1) > resident(spb) * spb)) spb = 1;
-  p.strips_per_block = spb;
-  const int sgroups = (p.nstrips + spb - 1) / spb;
-  const size_t lds_blk = lds * spb;
-  const int taps_h = q.ah.max_taps > 0 ? q.ah.max_taps : q.ah.ksize;
-  const int64_t planes = q.N * q.C;
-  p.ybands = pick_ybands_up(planes * sgroups, spb, (double)aa_device_cu_count() * resident(spb), taps_h, q.H, q.oH);
-  p.n_groups = planes * (int64_t)p.ybands;
-  const int64_t grid = (p.n_groups + 7) / 8 * 8 * sgroups;
-  if (grid > 0x7FFFFFFF) return 0;
-  if (aa_knob("AA_UP_DEBUG"))
-    fprintf(stderr, "up: U=%d KR=%d CPL=%d nstrips=%d spb=%d resident=%d ybands=%d groups=%lld grid=%lld lds=%zu nt=%d\n", U, KR, CPL, p.nstrips, spb,
-            resident(spb), p.ybands, (long long)p.n_groups, (long long)grid, lds_blk, p.store_nt);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * spb), lds_blk, q.stream, (const void *)q.in, (void *)q.out,
-                     (const char *)q.aw.table_dev, (const char *)q.ah.table_dev, p);
+  const int tag[4] = {U, KR, CPL, p.store_nt};
+  // strips per workgroup, row bands and the grid: aa_launch_shape.h, from this instantiation's occupancy at this problem's LDS
+  const aa_launch_shape_out s = aa_kernel_launch_shape(AA_LAUNCH_F32_UP, (const void *)kern, p.nstrips, p.strips_per_block, 0, q.N * q.C, q, lds, tag);
+  if (s.grid == 0) return 0;
+  p.strips_per_block = s.strips_per_block; p.ybands = s.ybands; p.n_groups = s.groups;
+  hipLaunchKernelGGL(kern, dim3((unsigned)s.grid), dim3(64 * s.strips_per_block), lds * s.strips_per_block, q.stream, (const void *)q.in,
+                     (void *)q.out, (const char *)q.aw.table_dev, (const char *)q.ah.table_dev, p);
   AA_HIP_CHECK_LAUNCH();
   return 1;
 }

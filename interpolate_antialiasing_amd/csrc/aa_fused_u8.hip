@@ -295,7 +295,6 @@ bool aa_v1_plan(const AAProblem &q, V1Plan *pl) {
 }
 
 int aa_v1_launch(const V1Plan &pl, const AAProblem &q) {
-  const int taps_h = q.ah.max_taps > 0 ? q.ah.max_taps : q.ah.ksize;
   FusedU8Params p;
   p.in = (const uint8_t *)q.in;
   p.out = (uint8_t *)q.out;
@@ -311,40 +310,12 @@ int aa_v1_launch(const V1Plan &pl, const AAProblem &q) {
   p.ring_magic = (unsigned)(0x100000000ull / (unsigned)pl.ring_rows) + 1u;
   p.pitch = pl.pitch;
 
-  // row bands.  Every extra band re-reads and re-filters ~taps_h halo rows, but the grid must fill the chip's
-  // resident-workgroup slots a near-integer number of times or the last partial round idles most CUs
-  // (2048 workgroups on 1280 slots ran 2 rounds for 1.6 rounds of work).  Pick the band count minimising
-  // (1 + halo fraction) / round efficiency.
-  const int cus = aa_device_cu_count();
-  const int waves_per_block = pl.block / 64;
-  int blocks_per_cu = (int)((160 * 1024) / (pl.lds > 0 ? pl.lds : 1));
-  if (blocks_per_cu > 32 / waves_per_block) blocks_per_cu = 32 / waves_per_block;
-  if (blocks_per_cu > 8) blocks_per_cu = 8;
-  if (blocks_per_cu < 1) blocks_per_cu = 1;
-  const double slots = (double)cus * blocks_per_cu;
-  const int64_t max_yb = q.oH / 8 > 1 ? q.oH / 8 : 1;
-  int64_t ybands = 1;
-  double best = 1e30;
-  for (int64_t yb = 1; yb <= max_yb && yb <= 64; yb++) {
-    const double items = (double)q.N * pl.xbands * yb;
-    const double rounds = items / slots;
-    const double eff = rounds / ceil(rounds);
-    const double halo = 1.0 + (double)(yb - 1) * taps_h / (double)q.H;
-    const double cost = halo / eff;
-    if (cost < best - 1e-9) {
-      best = cost;
-      ybands = yb;
-    }
-  }
-  if (const char *e = aa_knob("AA_FUSED_YBANDS")) {  // tuning knob for experiments; not used by tests or bench
-    const int64_t v = atoll(e);
-    if (v >= 1 && v <= max_yb) ybands = v < 64 ? v : 64;  // (the plan bounds the grid for 64 bands)
-  }
-  p.ybands = (int)ybands;
+  // row bands (aa_launch_shape.h; this family asks no occupancy: blocks per CU from its LDS and waves); the plan bounds the grid: aa_grid_fits
+  const aa_launch_shape_out s = aa_kernel_launch_shape(AA_LAUNCH_V1, nullptr, 1, 1, 0, q.N * pl.xbands, q, pl.lds, nullptr, 0, pl.block);
+  p.ybands = s.ybands;
   p.xbands = pl.xbands;
   p.bw = pl.bw;
-  const int64_t grid = q.N * ybands * pl.xbands;
-  if (pl.C == 3) return dispatch_tw<3>(pl.TW, p, pl.block, pl.lds, grid, q.stream);
-  if (pl.C == 4) return dispatch_tw<4>(pl.TW, p, pl.block, pl.lds, grid, q.stream);
-  return dispatch_tw<1>(pl.TW, p, pl.block, pl.lds, grid, q.stream);
+  if (pl.C == 3) return dispatch_tw<3>(pl.TW, p, pl.block, pl.lds, s.groups, q.stream);
+  if (pl.C == 4) return dispatch_tw<4>(pl.TW, p, pl.block, pl.lds, s.groups, q.stream);
+  return dispatch_tw<1>(pl.TW, p, pl.block, pl.lds, s.groups, q.stream);
 }

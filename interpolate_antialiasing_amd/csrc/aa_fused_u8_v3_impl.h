@@ -907,58 +907,16 @@ fused_u8_nhwc_v3_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ ou
   }
 }
 
-// Row bands: every extra band re-reads and re-filters ~taps_h halo rows, but the grid must fill the chip's resident
-// wave slots a near-integer number of times or the last partial round idles most CUs.  Pick the band count
-// minimising (1 + halo fraction) / round efficiency.
-int pick_ybands(int64_t items_per_band, double slots, int taps_h, int64_t H, int64_t oH) {
-  const int64_t max_yb = oH / 8 > 1 ? oH / 8 : 1;
-  int64_t ybands = 1;
-  double best = 1e30;
-  for (int64_t yb = 1; yb <= max_yb && yb <= 64; yb++) {
-    const double rounds = (double)items_per_band * yb / slots;
-    const double eff = rounds / ceil(rounds);
-    const double halo = 1.0 + (double)(yb - 1) * taps_h / (double)H;
-    const double cost = halo / eff;
-    if (cost < best - 1e-9) {
-      best = cost;
-      ybands = yb;
-    }
-  }
-  if (const char *e = aa_knob("AA_FUSED_YBANDS")) {  // experiment knob
-    const int64_t v = atoll(e);
-    if (v >= 1 && v <= max_yb) ybands = v;
-  }
-  return (int)ybands;
-}
-
 template <int C, int TW, int G, int MAXC, bool TWO, bool NONNEG, bool PERIODIC, bool FLT = false, int UPK = 0, int PL = 0, int SP = 1,
           bool ALPHA = false, bool O16 = false>
 int launch_k(FusedU8V3Params p, const AAProblem &q, size_t lds) {
   auto kern = fused_u8_nhwc_v3_kernel<C, TW, G, TWO, MAXC, NONNEG, PERIODIC, FLT, UPK, PL, SP, ALPHA, O16>;
-  auto resident = [&](int s) {  // resident workgroups of s strips per CU for this instantiation and this problem's LDS
-    int nb = aa_resident_blocks(kern, 64 * s, lds * s);
-    if (nb <= 0) nb = 16 / s;
-    return nb < 1 ? 1 : nb;
-  };
-  // Strips of a band share a workgroup (neighbouring segments share sectors, their stores meet in L2) unless that leaves
-  // wave slots of the CU empty: 5 strips -> 4 workgroups = 20 of 24 waves, and 24 single-strip workgroups are 5 % faster;
-  // 4 strips fill the CU either way and stay grouped (measured: grouped 0.396 ms vs 0.425 ms for the 906x438 shape).
-  int spb = p.strips_per_block;
-  if (spb > 1 && !p.spb_forced && resident(1) > resident(spb) * spb) spb = 1;
-  p.strips_per_block = spb;
-  const int sgroups = (p.nstrips + spb - 1) / spb;
-  const size_t lds_blk = lds * spb;
-  const int taps_h = q.ah.max_taps > 0 ? q.ah.max_taps : q.ah.ksize;
-  p.ybands = pick_ybands(p.n_images * sgroups, (double)aa_device_cu_count() * resident(spb), taps_h, q.H, q.oH);
-  if (aa_knob("AA_V3_DEBUG"))
-    fprintf(stderr, "[aa v3] strips %d spb %d (resident(1) %d, resident(%d) %d) ybands %d lds/strip %zu images %lld\n", p.nstrips, spb,
-            resident(1), p.nstrips <= 8 ? p.nstrips : 4, resident(p.nstrips <= 8 ? p.nstrips : 4), p.ybands, lds, (long long)p.n_images);
-  const int64_t groups8 = (p.n_images * (int64_t)p.ybands + 7) / 8 * 8;  // whole rounds of the 8 XCDs (see the kernel)
-  const int64_t grid = groups8 * sgroups;
-  if (grid > 0x7FFFFFFF) return 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * spb), lds_blk,
-                     q.stream, (const uint8_t *)q.in - p.in_mis, (uint8_t *)q.out, (const char *)q.aw.table_dev,
-                     (const char *)q.ah.table_dev, p);
+  // strips per workgroup, row bands and the grid: aa_launch_shape.h, from this instantiation's occupancy at this problem's LDS
+  const aa_launch_shape_out s = aa_kernel_launch_shape(AA_LAUNCH_V3, (const void *)kern, p.nstrips, p.strips_per_block, p.spb_forced, p.n_images, q, lds);
+  if (s.grid == 0) return 0;
+  p.strips_per_block = s.strips_per_block; p.ybands = s.ybands;
+  hipLaunchKernelGGL(kern, dim3((unsigned)s.grid), dim3(64 * s.strips_per_block), lds * s.strips_per_block, q.stream,
+                     (const uint8_t *)q.in - p.in_mis, (uint8_t *)q.out, (const char *)q.aw.table_dev, (const char *)q.ah.table_dev, p);
   AA_HIP_CHECK_LAUNCH();
   return 1;
 }
