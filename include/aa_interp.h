@@ -521,6 +521,36 @@ typedef struct aa_launch_shape_out {
 } aa_launch_shape_out;
 int aa_probe_launch_shape(const aa_launch_shape_in *in, aa_launch_shape_out *out);
 
+/* Launch shape of the fused families, process-wide: a test hook, like aa_set_store_form (the library reads no environment variables).
+ * Which shape a launch gets follows from the batch size and the card's occupancy, so a test of ordinary size meets the largest band count
+ * and single-strip workgroups only; this makes every shape reachable at any size.  0 means "the model chooses", the default is (0, 0).
+ * Applied inside the model, after the knobs of developer builds, so aa_probe_launch_shape answers under it too.  A request is honoured
+ * only where it is a shape the kernels are written for; otherwise that component is the model's own answer — nothing is moved to a
+ * nearby value and nothing fails.  Whether it is honoured follows from what the plan knows (strips, LDS per strip, oH), never from an
+ * occupancy answer:
+ *   ybands  honoured when 1 <= ybands <= min(max_yb, 64), max_yb = max(oH / 8, 1) (AA_LAUNCH_F32_UP: oH / 16), the rule of the
+ *           developer knob.
+ *   spb     honoured when the family is not AA_LAUNCH_V1 (one workgroup form), 1 <= spb <= 8, spb <= nstrips and lds * spb <= 64 KiB
+ *           (all three families).  It is then kept as a forced plan's is (no drop to single strips) and the band count is chosen for it,
+ *           or forced in turn.
+ * Returns the previous setting, spb + 256 * ybands (a request outside 0..255 / 0..65535 is stored as the nearest value of that range:
+ * no rule honours it either way).
+ * What the kernels presume about the grouping (read before any forced shape ran): all three are compiled with __launch_bounds__(512),
+ * eight waves; a wave's stage ring lies at wv * G * seg_bytes (plane groups: wv * G * 1024) of a dynamic LDS block launched as
+ * lds * spb bytes, and float up's 1088-byte areas of the 240-column store form lie behind the rings at spb * G * seg_bytes + wv * 1088,
+ * inside the same product (their 1088 bytes are part of lds); the kernels read strips_per_block from their parameter block, which the
+ * launch fills from this answer together with the block size, so sgroups, the strip of a wave and the surplus exits (strip >= nstrips,
+ * group >= items * ybands) agree with the grid; the pacing barriers (v3's unrolled groups, float up's AA_UP_PACE rows) are taken only by
+ * workgroups all of whose waves are alive, the waves of a workgroup share one band and so run the same number of groups and rows, and
+ * float down has no barrier.  Nothing presumes the plan's own spb.  More than 64 KiB of dynamic LDS needs an attribute no launch sets:
+ * hence the LDS rule, stricter than the v3 knob's.  The first-generation kernel has no strips. */
+int aa_set_launch_shape(int spb, int ybands);
+
+/* The question and the answer of the last fused launch of aa_resample_fwd* on this thread (thread-local, like aa_last_variant); in the
+ * question, occupancy[s] holds what the runtime answered where the model asked it, 0 where it did not.  AA_ERR_BAD_SHAPE when the last
+ * such call (or aa_resample_bwd_atomic, aa_resample_axis_fwd) launched no fused kernel; AA_ERR_NULL.  Additive, like the probe. */
+int aa_last_launch_shape(aa_launch_shape_in *in, aa_launch_shape_out *out);
+
 /* Kernel selection, process-wide; returns the previous setting.  1 (default): fused single-launch kernels, newest
  * design first; 2: first-generation fused kernels only (A/B measurements); 0: none.
  * With 0 every call takes the generic two-launch path — used by tests to cross-check the fused kernels against an

@@ -37,6 +37,7 @@ U8, F32, F64, F16, BF16 = 0, 1, 2, 3, 4
 NCHW, NHWC = 0, 1
 TABLE_PIL, TABLE_F32, TABLE_F64 = 0, 1, 2
 ERR_BAD_DTYPE = -2
+ERR_BAD_SHAPE = -4
 ERR_STRIDES = -10
 FLAG_FAST = 1
 FLAG_PREMUL_ALPHA = 2
@@ -54,6 +55,7 @@ EXPORTS = (
     "aa_many_desc_bytes_placed", "aa_many_plan_placed", "aa_many_desc_bytes_patches", "aa_many_plan_patches", "aa_resample_many_u8_to_patches",
     "aa_reduce_many_desc_bytes", "aa_reduce_many_plan", "aa_reduce_many_u8",
     "aa_many_desc_bytes_nearest", "aa_many_plan_nearest", "aa_resample_many_nearest",
+    "aa_set_launch_shape", "aa_last_launch_shape",
 )
 
 
@@ -289,6 +291,10 @@ def load() -> ctypes.CDLL:
     L.aa_probe_copy.restype = i32
     L.aa_probe_launch_shape.argtypes = [ctypes.POINTER(LaunchShapeIn), ctypes.POINTER(LaunchShapeOut)]
     L.aa_probe_launch_shape.restype = i32
+    L.aa_set_launch_shape.argtypes = [i32, i32]
+    L.aa_set_launch_shape.restype = i32
+    L.aa_last_launch_shape.argtypes = [ctypes.POINTER(LaunchShapeIn), ctypes.POINTER(LaunchShapeOut)]
+    L.aa_last_launch_shape.restype = i32
     L.aa_table_ksize_box.argtypes = [i32, i32, i64, i64, dbl, dbl]
     L.aa_table_ksize_box.restype = i32
     L.aa_table_build_bytes_box.argtypes = [i32, i32, i64, i64, dbl, dbl]
@@ -381,6 +387,23 @@ def set_plane_groups(enabled: int) -> int:
 
 def last_variant() -> str:
     return load().aa_last_variant().decode()
+
+
+def set_launch_shape(spb: int = 0, ybands: int = 0):
+    """Test hook: strips per workgroup and row bands of the fused launches (process-wide), 0 = the model chooses; a request the kernels are
+    not written for is not looked at (include/aa_interp.h has the rules).  Returns the previous setting as (spb, ybands)."""
+    prev = int(load().aa_set_launch_shape(int(spb), int(ybands)))
+    return prev & 0xFF, prev >> 8
+
+
+def last_launch_shape():
+    """(LaunchShapeIn, LaunchShapeOut) of this thread's last fused launch, or None when the last call launched no fused kernel."""
+    q, out = LaunchShapeIn(), LaunchShapeOut()
+    rc = load().aa_last_launch_shape(ctypes.byref(q), ctypes.byref(out))
+    if rc == ERR_BAD_SHAPE:
+        return None
+    check(rc, "aa_last_launch_shape")
+    return q, out
 
 
 # sources a kernel variant is compiled from (csrc/): profiles/*.json summaries are stamped with their fingerprint, and bench.py

@@ -20,6 +20,8 @@ int g_aa_plane_groups = 1;  // (aa_common.h; read by aa_fused_u8_v3.hip)
 namespace {
 
 thread_local const char *g_last_variant = "none";
+// aa_last_launch_shape: the question and the answer of this thread's last fused launch; not valid once a call took another path
+thread_local struct { bool valid; aa_launch_shape_in in; aa_launch_shape_out out; } g_last_shape = {};
 int g_fused_enabled = 1;
 
 // (s2.2/aa_interpolation_impl.h:287, :377, :333 for the reference's three filters; aa_common.h's table for all of them)
@@ -149,6 +151,7 @@ FwdPlan plan_fwd(const AAProblem &q) {
 int run_fwd(const FwdPlan &pl, int route, const AAProblem &q) {
   const char *variant = "none";
   int rc;
+  g_last_shape.valid = false;
   switch (route) {
     case FWD_EMPTY: rc = AA_OK; variant = "empty"; break;
     case FWD_V3: rc = aa_v3_launch(pl.v3, q); variant = pl.v3.variant; break;
@@ -284,10 +287,16 @@ aa_launch_shape_out aa_kernel_launch_shape(int family, const void *kern, int nst
   in.taps_h = q.ah.max_taps > 0 ? q.ah.max_taps : q.ah.ksize;
   in.taps_w = q.aw.max_taps > 0 ? q.aw.max_taps : q.aw.ksize;
   in.cus = aa_device_cu_count();
-  struct Kern { int family; const void *kern; size_t lds; } k{family, kern, lds};
+  struct Kern { int family; const void *kern; size_t lds; int32_t *asked; } k{family, kern, lds, in.occupancy};
   aa_launch_shape_out out;
-  aa_launch_shape(in, [](void *c, int s) { const Kern &k = *(const Kern *)c; return aa_resident_blocks(k.family, k.kern, 64 * s, k.lds * s); },
+  aa_launch_shape(in, [](void *c, int s) {
+                    const Kern &k = *(const Kern *)c;
+                    const int nb = aa_resident_blocks(k.family, k.kern, 64 * s, k.lds * s);
+                    if (s >= 1 && s <= 8) k.asked[s] = nb;  // (for aa_last_launch_shape: the answers this launch was shaped from)
+                    return nb;
+                  },
                   &k, tag, &out);
+  g_last_shape.valid = true; g_last_shape.in = in; g_last_shape.out = out;
   return out;
 }
 
@@ -763,6 +772,7 @@ int aa_resample_bwd_atomic(const void *grad_out_dev, void *grad_in_dev, void *wo
   q.stream = (hipStream_t)stream;
   rc = aa_launch_bwd_atomic(q);
   if (rc == AA_OK) g_last_variant = "bwd_scatter_atomics";
+  g_last_shape.valid = false;
   return rc;
 }
 
@@ -778,6 +788,7 @@ int aa_resample_axis_fwd(const void *in_dev, void *out_dev, int dtype, int64_t o
   if (outer == 0) return AA_OK;
   if (!in_dev || !out_dev) return AA_ERR_NULL;
   g_last_variant = "generic_axis";
+  g_last_shape.valid = false;
   return aa_launch_axis_fwd(in_dev, out_dev, dtype, outer, in_size, inner, *ax, (hipStream_t)stream);
 }
 
@@ -807,5 +818,13 @@ int aa_set_plane_groups(int enabled) {
 }
 
 const char *aa_last_variant(void) { return g_last_variant; }
+
+int aa_last_launch_shape(aa_launch_shape_in *in, aa_launch_shape_out *out) {
+  if (!in || !out) return AA_ERR_NULL;
+  if (!g_last_shape.valid) return AA_ERR_BAD_SHAPE;
+  *in = g_last_shape.in;
+  *out = g_last_shape.out;
+  return AA_OK;
+}
 
 }  // extern "C"

@@ -2,9 +2,15 @@
 #include "aa_launch_shape.h"
 #include <math.h>
 #include <stdio.h>
+#include <atomic>
 #include "aa_common.h"  // aa_knob
 
 namespace {
+
+// aa_set_launch_shape (aa_interp.h): spb in the low byte, ybands above it; 0: the model chooses.  One relaxed load per launch.
+std::atomic<int> g_forced_shape{0};
+int forced_spb() { return g_forced_shape.load(std::memory_order_relaxed) & 0xFF; }
+int forced_ybands() { return g_forced_shape.load(std::memory_order_relaxed) >> 8; }
 
 // ---- what differs between the families, besides the band rules of float down and float up below ------------------------------
 struct FamilyPolicy {
@@ -72,6 +78,8 @@ int pick_ybands(const aa_launch_shape_in &in, int64_t items_per_band, int spb, d
   const FamilyPolicy &f = kPolicy[in.family];
   const bool down = in.family == AA_LAUNCH_F32_DOWN;
   const int64_t max_yb = in.oH / f.rows_per_band > 1 ? in.oH / f.rows_per_band : 1;
+  // the test hook, over the model and the knob alike: a band count the kernels are written for, or it is not looked at
+  if (const int fy = forced_ybands(); fy >= 1 && fy <= max_yb && fy <= 64) return fy;
   const char *knob = aa_knob("AA_FUSED_YBANDS");  // experiment knob; not used by tests or bench
   if (in.family == AA_LAUNCH_F32_UP && !knob)
     if (const int64_t yb = up_target_waves_bands(in, items_per_band, spb, max_yb)) return (int)yb;
@@ -121,6 +129,10 @@ void aa_launch_shape(const aa_launch_shape_in &in, AAResidentFn ask, void *ctx, 
   const char *f32_spb = in.family == AA_LAUNCH_F32_DOWN ? aa_knob("AA_F32_SPB") : nullptr;  // experiment knob, after the drop
   const int v = f32_spb ? atoi(f32_spb) : 0, r = v >= 1 && v <= 8 ? resident(v) : 0;
   if (r > 0) spb = v, nb = r;
+  // the test hook (aa_set_launch_shape), after the knobs and kept like a forced plan's: a grouping the kernels are written for (see
+  // aa_interp.h for what was read in them), decided by what the plan knows alone, or it is not looked at
+  if (const int fs = forced_spb(); fs >= 1 && fs <= 8 && in.family != AA_LAUNCH_V1 && fs <= in.nstrips && in.lds * fs <= 64 * 1024 && fs != spb)
+    spb = fs, nb = 0;
   if (!nb) nb = resident(spb);
   const int sgroups = (in.nstrips + spb - 1) / spb;
   *out = aa_launch_shape_out{spb, pick_ybands(in, in.items * sgroups, spb, (double)in.cus * nb, in.saturation ? nb * spb : 0), nb, 0, 0, 0};
@@ -138,6 +150,12 @@ void aa_launch_shape(const aa_launch_shape_in &in, AAResidentFn ask, void *ctx, 
   if (in.family == AA_LAUNCH_F32_UP && grid == out->grid && t && aa_knob("AA_UP_DEBUG"))
     fprintf(stderr, "up: U=%d KR=%d CPL=%d nstrips=%d spb=%d resident=%d ybands=%d groups=%lld grid=%lld lds=%zu nt=%d\n", t[0], t[1], t[2],
             in.nstrips, spb, nb, out->ybands, (long long)out->groups, (long long)grid, (size_t)in.lds * spb, t[3]);
+}
+
+int aa_set_launch_shape(int spb, int ybands) {
+  // (requests no rule honours are all alike: stored as the nearest value of the range the return value can carry)
+  const int s = spb < 0 ? 0 : spb > 255 ? 255 : spb, y = ybands < 0 ? 0 : ybands > 0xFFFF ? 0xFFFF : ybands;
+  return g_forced_shape.exchange(s | (y << 8), std::memory_order_relaxed);
 }
 
 int aa_probe_launch_shape(const aa_launch_shape_in *in, aa_launch_shape_out *out) {
