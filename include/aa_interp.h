@@ -457,6 +457,53 @@ int aa_many_plan_nearest(int layout, int elem_bytes, int64_t n, int64_t C, int64
 int aa_resample_many_nearest(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
                              int out_elem_bytes /* elem_bytes or 8 */, aa_stream_t stream);
 
+/* MAPS plans: the measured map of a batch — depth and disparity as 16-bit or float32, height maps, 16-bit rasters, int32 counters —
+ * through the same box, size, place and flip as its image, FILTERED, with the arithmetic Pillow keeps for its three wide single-band
+ * modes (Resample.c: ImagingResampleHorizontal_16bpc / _32bpc and their vertical twins).  elem: AA_MAPS_U16 is "I;16", AA_MAPS_I32 "I",
+ * AA_MAPS_F32 "F"; one channel.  Item i of the result is, bit for bit,
+ *   R_i = PIL.Image.resize((vW_i, vH_i), FILTER, box=box_i), pasted at (oy_i, ox_i) of an [oH, oW] canvas of `fill`, and the whole canvas
+ *   row mirrored left to right for an item planned with AA_MANY_FLIP_X.
+ * The arithmetic: windows and coefficients are precompute_coeffs's (the box as floats, the scale their FLOAT difference over the size,
+ * windows clipped to the image), and the weights stay its normalised doubles (no normalize_coeffs_8bpc).  Every output of every pass is
+ *   ss = 0.0;  ss = ss + (double)in[xmin + x] * k[x]  for x ascending   (product rounded to double, then the sum: no fused multiply-add)
+ * stored by the mode's rule after EACH pass, with ROUND_UP(f) = (int)(f >= 0 ? f + 0.5 : f - 0.5):
+ *   AA_MAPS_F32: (float)ss.   AA_MAPS_I32: ROUND_UP(ss) (beyond int32: unspecified, as in Pillow's C).
+ *   AA_MAPS_U16: r = ROUND_UP(ss); low byte CLIP8(r % 256) (C's remainder), high byte CLIP8(r >> 8).  That is no clamp: a negative r
+ *   gives 0, r > 65535 gives 0xFF00 | (r & 255), and the vertical pass reads the wrapped intermediate.  overflow AA_MAPS_OVERFLOW_CLAMP
+ *   stores min(max(r, 0), 65535) in both passes instead; the argument is checked and otherwise ignored for the other two elements.
+ * Which passes run is Pillow's decision per item: none (the element is copied) when the box has the size asked for at an integer offset
+ * (no box: the image's own size); else the horizontal pass only if vW != W or the box does not span the width, the vertical one only if
+ * vH != H or the box does not span the height.  A pass that is skipped is not run as an identity filter.
+ * aa_many_plan_maps is host arithmetic only (no HIP call: works without a device).  It takes aa_many_image records (flags: 0 or
+ * AA_MANY_FLIP_X, any other bit AA_ERR_BAD_SHAPE; strides in bytes under the planar rules with one channel: stride_px is the element's
+ * bytes; data and stride_row aligned to the ELEMENT only, so rows of a uint16 view may start on an odd element; AA_ERR_STRIDES
+ * otherwise) and aa_many_place records (NULL: every item the whole canvas at offset 0), and writes one packed descriptor block into
+ * desc_host, desc_bytes >= aa_many_desc_bytes_maps(n): per item the passes that run, per axis the covered part of the placed result,
+ * the hull of its windows, ksize, and the workspace offsets.  The workspace is a table arena — a table is [int32 xmin[m]][int32
+ * xsize[m]][double w[m * ksize]], m the covered results of the axis, the doubles 8-byte aligned — plus, for the items whose horizontal
+ * pass runs, an intermediate of the element's type that holds only the rows the vertical pass reads.  fill: an integer in 0..65535
+ * (AA_MAPS_U16) or within int32 (AA_MAPS_I32), or a finite value whose float is finite (AA_MAPS_F32, written as (float)fill);
+ * AA_ERR_BAD_SHAPE otherwise.  Other errors: AA_ERR_BAD_FILTER; AA_ERR_BAD_DTYPE for an unknown elem; AA_ERR_BAD_SHAPE for an unknown
+ * overflow, an empty box, a box beyond its image, a size or offset beyond INT32_MAX / 4, or more work units than one grid holds;
+ * AA_ERR_KSIZE; AA_ERR_WORKSPACE for a short block; AA_ERR_NULL.
+ * aa_resample_many_maps enqueues THREE launches whatever n (two when no item's horizontal pass runs on the canvas): a table kernel
+ * (device double arithmetic, aa_pil_coeffs.h's expressions), the horizontal pass over the items that have one, and a vertical pass over
+ * (item, canvas row, 256 columns) that writes every element of the output and nothing else.  Everything is the plan's.  out_dev
+ * [n, 1, oH, oW] elements, dense, aligned to the element; desc_dev (8-byte aligned) and workspace_dev (16-byte aligned, at least the
+ * plan's size) as aa_resample_many_u8.  Every check comes before the first launch; nothing is allocated, synchronised or read back, and
+ * no table cache is touched.  n == 0 launches nothing.  Added without an ABI version change (additive). */
+#define AA_MAPS_U16 0
+#define AA_MAPS_I32 1
+#define AA_MAPS_F32 2
+#define AA_MAPS_OVERFLOW_PILLOW 0
+#define AA_MAPS_OVERFLOW_CLAMP 1
+size_t aa_many_desc_bytes_maps(int64_t n);
+int aa_many_plan_maps(int filter, int elem, int64_t n, int64_t oH, int64_t oW, const aa_many_image *images,
+                      const aa_many_place *places /* may be NULL */, double fill, int overflow, void *desc_host, size_t desc_bytes,
+                      size_t *workspace_bytes);
+int aa_resample_many_maps(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
+                          aa_stream_t stream);
+
 /* ---- ragged Image.reduce: N uint8 images of N sizes, each with its own integer box and factors, into one arena ------------------------
  * Pillow's first step of Image.resize(reducing_gap=...) for a list: every large item is read ONCE by an integer box mean, and the ragged
  * resize above then runs over the small results, which it reads where they lie (an arena offset is just another pointer of an

@@ -55,6 +55,7 @@ EXPORTS = (
     "aa_many_desc_bytes_placed", "aa_many_plan_placed", "aa_many_desc_bytes_patches", "aa_many_plan_patches", "aa_resample_many_u8_to_patches",
     "aa_reduce_many_desc_bytes", "aa_reduce_many_plan", "aa_reduce_many_u8",
     "aa_many_desc_bytes_nearest", "aa_many_plan_nearest", "aa_resample_many_nearest",
+    "aa_many_desc_bytes_maps", "aa_many_plan_maps", "aa_resample_many_maps",
     "aa_set_launch_shape", "aa_last_launch_shape",
 )
 
@@ -141,6 +142,25 @@ class NearItem(ctypes.Structure):
                 ("dx", ctypes.c_int32), ("dxo", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int64)]
 
 
+class MapsHeader(ctypes.Structure):
+    """Head of the block aa_many_plan_maps writes (csrc/aa_many_maps.h AAMapsHeader; opaque to C callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("oH", ctypes.c_int32), ("oW", ctypes.c_int32), ("filter", ctypes.c_int32),
+                ("elem", ctypes.c_int32), ("overflow", ctypes.c_int32), ("fill", ctypes.c_uint32), ("hunits", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64 * 2)]
+
+
+class MapsItem(ctypes.Structure):
+    """One item of that block (csrc/aa_many_maps.h AAMapsItem): the passes Pillow runs (flags, MAPS_ITEM_*), per axis Pillow's origin and
+    scale, the hull [o, o + hull) its pass reads, ksize, the item's own size v, the covered part [v0, v0 + m) and the canvas index d."""
+    _fields_ = [("src", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("tab_h", ctypes.c_int64), ("tab_w", ctypes.c_int64),
+                ("inter", ctypes.c_int64), ("in0_h", ctypes.c_double), ("scale_h", ctypes.c_double), ("in0_w", ctypes.c_double),
+                ("scale_w", ctypes.c_double), ("in_h", ctypes.c_int32), ("in_w", ctypes.c_int32), ("oy", ctypes.c_int32),
+                ("hull_h", ctypes.c_int32), ("ox", ctypes.c_int32), ("hull_w", ctypes.c_int32), ("ksize_h", ctypes.c_int32),
+                ("ksize_w", ctypes.c_int32), ("vh", ctypes.c_int32), ("vw", ctypes.c_int32), ("v0h", ctypes.c_int32), ("v0w", ctypes.c_int32),
+                ("mh", ctypes.c_int32), ("mw", ctypes.c_int32), ("dy", ctypes.c_int32), ("dx", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class ReduceItem(ctypes.Structure):
     """aa_reduce_item: one item of the ragged Image.reduce (strides in bytes; box = x0, y0, x1, y1 integers; factors fx, fy)."""
     _fields_ = [("data_dev", ctypes.c_void_p), ("H", ctypes.c_int64), ("W", ctypes.c_int64), ("stride_row", ctypes.c_int64),
@@ -182,6 +202,11 @@ MANY_PREMUL_ALPHA = 2  # aa_many_image.flags: Pillow's RGBA / LA resize of that 
 PATCH_CPP, PATCH_PPC = 0, 1  # aa_resample_many_u8_to_patches: token vector [C, ph, pw] or [ph, pw, C]
 MANY_PLAN_PLACED, MANY_PLAN_PATCHES, MANY_PLAN_ALPHA = 1, 2, 4  # ManyHeader.kind (csrc/aa_many.h AA_MANY_PLAN_*)
 MANY_ITEM_FLIP, MANY_ITEM_ALPHA = 1, 2  # ManyItem.flags (csrc/aa_many.h AA_MANY_ITEM_*)
+MAPS_U16, MAPS_I32, MAPS_F32 = 0, 1, 2  # aa_many_plan_maps elem: Pillow's "I;16", "I", "F"
+MAPS_OVERFLOW = {"pillow": 0, "clamp": 1}  # aa_many_plan_maps overflow (AA_MAPS_OVERFLOW_*)
+MAPS_ITEM_FLIP, MAPS_ITEM_HPASS, MAPS_ITEM_VPASS = 1, 2, 4  # MapsItem.flags (csrc/aa_many_maps.h AA_MAPS_ITEM_*)
+MAPS_HROWS = 16     # hull rows per work unit of the maps call's horizontal pass (csrc/aa_many_maps.h AA_MAPS_HROWS)
+MAPS_VCOLS = 256    # canvas columns per work unit of the maps call's vertical pass (csrc/aa_many_maps.h AA_MAPS_VCOLS)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
 
@@ -206,6 +231,14 @@ def near_desc_view(buf, n: int):
     hd = NearHeader.from_buffer(buf, 0)
     items = (NearItem * n).from_buffer(buf, ctypes.sizeof(NearHeader))
     prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(NearHeader) + n * ctypes.sizeof(NearItem))
+    return hd, items, prefix
+
+
+def maps_desc_view(buf, n: int):
+    """(header, items, prefix) of a maps plan's block held in a ctypes buffer: [header][n items][int64 hunit_prefix[n + 1]]."""
+    hd = MapsHeader.from_buffer(buf, 0)
+    items = (MapsItem * n).from_buffer(buf, ctypes.sizeof(MapsHeader))
+    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(MapsHeader) + n * ctypes.sizeof(MapsItem))
     return hd, items, prefix
 
 
@@ -340,6 +373,13 @@ def load() -> ctypes.CDLL:
     L.aa_many_plan_nearest.restype = i32
     L.aa_resample_many_nearest.argtypes = [vp, vp, vp, vp, sz, i32, vp]
     L.aa_resample_many_nearest.restype = i32
+    L.aa_many_desc_bytes_maps.argtypes = [i64]
+    L.aa_many_desc_bytes_maps.restype = sz
+    L.aa_many_plan_maps.argtypes = [i32, i32, i64, i64, i64, ctypes.POINTER(ManyImage), ctypes.POINTER(ManyPlace), ctypes.c_double, i32,
+                                    vp, sz, ctypes.POINTER(sz)]
+    L.aa_many_plan_maps.restype = i32
+    L.aa_resample_many_maps.argtypes = [vp, vp, vp, vp, sz, vp]
+    L.aa_resample_many_maps.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

@@ -9,6 +9,7 @@
 #include "aa_box.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
+#include "aa_many_maps.h"
 #include "aa_many_nearest.h"
 #include "aa_reduce_many.h"
 #include "aa_plan.h"
@@ -571,6 +572,19 @@ int aa_resample_many_nearest(const void *desc_host, const void *desc_dev, void *
                              int out_elem_bytes, aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_many_nearest(desc_host, desc_dev, out_dev, workspace_dev, workspace_bytes, out_elem_bytes, (hipStream_t)stream);
+}
+
+size_t aa_many_desc_bytes_maps(int64_t n) { return aa_maps_desc_size(n); }
+
+int aa_many_plan_maps(int filter, int elem, int64_t n, int64_t oH, int64_t oW, const aa_many_image *images, const aa_many_place *places,
+                      double fill, int overflow, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
+  return aa_maps_plan_host(filter, elem, n, oH, oW, images, places, fill, overflow, desc_host, desc_bytes, workspace_bytes);
+}
+
+int aa_resample_many_maps(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
+                          aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_many_maps(desc_host, desc_dev, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- Image.reduce ------------------------------------------------------------------------------------------------------------------------

@@ -874,6 +874,105 @@ def resize_many_nearest(images, output_size: Sequence[int], *, boxes=None, flips
                                                                                 out.element_size(), stream))[0]
 
 
+# the dtypes resize_many_maps filters: Pillow's mode, the library's element id, the fill's range (None: a finite float)
+_MAPS_MODES = {torch.uint16: ("I;16", _lib.MAPS_U16, (0, 65535)), torch.int32: ("I", _lib.MAPS_I32, (-2 ** 31, 2 ** 31 - 1)),
+               torch.float32: ("F", _lib.MAPS_F32, None)}
+_MAPS_NOT_BUILT = {"alpha": "Pillow's LA / RGBA resize is resize_many(alpha=True), uint8 only",
+                   "reducing_gap": "Pillow's Image.reduce refuses \"I;16\"; reduce_many_for_resize is the uint8 step",
+                   "out_dtype": "the result has the items' dtype", "mean": "the result has the items' dtype, not normalised",
+                   "std": "the result has the items' dtype, not normalised", "out_format": "one channel has one layout",
+                   "patch": "packed patch tokens are resize_many_to_patches, uint8 only"}
+
+
+def resize_many_maps(maps, output_size: Sequence[int], mode: str = "bilinear", *, boxes=None, flips=None, channels: Optional[int] = None,
+                     sizes=None, offsets=None, fill=0, overflow: str = "pillow", **not_built) -> torch.Tensor:
+    """The measured maps of a ragged batch — depth and disparity stored as 16-bit PNG or float32, height maps, 16-bit medical and
+    satellite rasters, int32 counters — FILTERED through the same crop, size, placement and flip as their image, with the arithmetic
+    Pillow keeps for its three wide single-band modes.  Per item i, bit for bit,
+
+        R_i = PIL.Image.resize((vw_i, vh_i), FILTER, box=boxes[i])          # vh_i, vw_i = sizes[i], or output_size
+        y[i, 0, Y, X] = R_i[Y - py_i, X - px_i] where that exists, else fill
+        y[i] = y[i].flip(-1) where flips[i]                                  # the whole canvas row
+
+    ``maps``, ``boxes`` (Pillow's order, x first), ``channels``, ``sizes``, ``offsets`` (``"center"`` included) and ``flips`` are exactly
+    ``resize_many_nearest``'s arguments, with the same checks and the same reading of every item where it lies (any row pitch; rows of a
+    uint16 view may start on an odd element): pass the SAME ``boxes, sizes, offsets, flips`` as the images get.
+    Items are ``torch.uint16`` (Pillow's "I;16"), ``torch.int32`` ("I") or ``torch.float32`` ("F"), one channel, one dtype per call; a
+    [N, 1, H, W] tensor is the list of its items.  ``t.view(torch.uint16)`` of an int16 tensor is free — but this is NOT the bits
+    ``resize_many_nearest`` gives for int16: NEAREST copies elements, this call computes with the UNSIGNED value.
+    ``mode``: bilinear | bicubic | nearest (the box filter) | lanczos | hamming.
+    ``fill``: an int in 0..65535 for uint16, within int32 for int32; a finite float for float32, written as ``float32(fill)``.
+    ``overflow`` (uint16 only; accepted and ignored for the other two): ``"pillow"`` stores what Pillow stores, which is no clamp — with
+    ``r`` the rounded sum, the low byte is ``CLIP8(r % 256)`` and the high byte ``CLIP8(r >> 8)``, so a negative ``r`` gives 0 but
+    ``r > 65535`` gives ``0xFF00 | (r & 255)`` (bicubic or Lanczos overshoot beside a 65535 wraps, e.g. to 65302), after the horizontal
+    pass too, and the vertical pass reads the wrapped value.  ``"clamp"`` stores ``min(max(r, 0), 65535)`` in both passes instead.
+    The result is [N, 1, oh, ow] in the items' dtype, contiguous; N == 0 gives the empty tensor.
+
+    The arithmetic (Resample.c, the 16bpc / 32bpc passes) is neither the uint8 fixed-point path of ``resize_many`` nor the fp32 path of
+    the single-image forwards: coefficients are precompute_coeffs's normalised DOUBLES, every output of every pass is one double sum over
+    its window in ascending order (product rounded, then the sum: no fused multiply-add), and the store rule — ``float32(ss)``; for the
+    integer modes ``int(ss + 0.5)`` or ``int(ss - 0.5)`` by the sign — is applied after EACH pass.  Pillow runs the horizontal pass only
+    if the width changes or the box does not span it, the vertical one likewise, and copies when the box has the size asked for at an
+    integer offset; a skipped pass is not run as an identity filter.  int32 results beyond int32 are undefined in Pillow's C and
+    unspecified here.
+
+    Three launches and one non-blocking copy of a packed descriptor whatever N (two when no item's horizontal pass runs): a table kernel
+    that evaluates the double coefficients on the device, the horizontal pass into an intermediate of the items' dtype that holds only
+    the rows the vertical pass reads, and a vertical pass that writes every element of the output.  Nothing is read back; the table
+    caches are neither read nor written.  Not built: more than one channel, alpha, reducing_gap, out_dtype / mean / std, patches."""
+    name = "resize_many_maps"
+    for opt in not_built:
+        if opt not in _MAPS_NOT_BUILT:
+            raise TypeError(f"{name}() got an unexpected keyword argument '{opt}'")
+        raise NotImplementedError(f"{name}(): {opt} is not built for maps ({_MAPS_NOT_BUILT[opt]})")
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if overflow not in _lib.MAPS_OVERFLOW:
+        raise ValueError(f"{name}(): overflow must be 'pillow' or 'clamp', got {overflow!r}")
+    oh, ow, items, dev0, n, c = _many_canvas(name, maps, output_size, channels, "[0, 1, oh, ow]")
+    checked = _many_check_items(name, items, c, boxes, lambda i: (oh, ow), tuple(_MAPS_MODES))
+    dtype = items[0].dtype if n else (maps.dtype if isinstance(maps, torch.Tensor) and maps.dtype in _MAPS_MODES else torch.float32)
+    if c != 1:  # (an empty batch that names its C)
+        raise NotImplementedError(f"{name}(): {dtype} maps have one channel (Pillow's \"I;16\", \"I\" and \"F\"), got C = {c}")
+    if flips is not None:
+        flips = [bool(v) for v in flips]
+        if len(flips) != n:
+            raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
+    places = _many_places(name, sizes, offsets, n, oh, ow)
+    _, elem, fill_range = _MAPS_MODES[dtype]
+    if fill_range is not None:
+        fill = _many_fill(name, fill, 1, *fill_range, note=f" ({dtype})")[0]
+    else:
+        try:
+            if isinstance(fill, bool):
+                raise TypeError
+            fill = float(fill)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}(): fill must be one finite float for {dtype}, got {fill!r}") from None
+        try:
+            finite = math.isfinite(fill) and math.isfinite(boxmath.f32(fill))
+        except OverflowError:  # (beyond float32)
+            finite = False
+        if not finite:
+            raise ValueError(f"{name}(): fill = {fill} is not finite as {dtype}")
+    if n == 0:
+        return torch.empty((0, 1, oh, ow), dtype=dtype, device=_many_empty_device(dev0))
+    for t in items:
+        _require_gpu(t, name)
+    dev = items[0].device
+    classes = [_many_class(t) for t in items]
+    L = _lib.load()
+    recs, keep = _many_records(items, classes, False, 1, checked, flips, eb=items[0].element_size())  # (the library takes strides in bytes)
+    precs = _many_pack_places(places)
+    filter_id, over = _lib.FILTER_IDS[mode], _lib.MAPS_OVERFLOW[overflow]
+    return _many_run(
+        name, dev, L.aa_many_desc_bytes_maps(n),
+        lambda desc, nbytes, ws_bytes: L.aa_many_plan_maps(filter_id, elem, n, oh, ow, recs, precs, float(fill), over, desc, nbytes, ws_bytes),
+        lambda: torch.empty((n, 1, oh, ow), dtype=dtype, device=dev),
+        lambda desc_host, desc_dev, out, ws, stream: L.aa_resample_many_maps(desc_host, desc_dev, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                                             stream))[0]
+
+
 def _patch_sizes(name: str, sizes, patch, n: int, pad_to):
     """patch, sizes and pad_to of resize_many_to_patches, checked -> ((ph, pw), [(vh, vw)] per item, L or None)."""
     try:
@@ -1621,6 +1720,26 @@ def _register_torch_ops() -> None:
                                  sizes=_many_pairs(images, sizes, "sizes"), offsets=_many_pairs(images, offsets, "offsets"),
                                  fill=_many_fill(fill), out_dtype=out_dtype), "CUDA")
     lib.impl("resize_many_nearest", _many_nearest_meta, "Meta")
+
+    # Pillow's I;16 / I / F resize for the measured maps: the same flattened boxes / sizes / offsets and flips; one fill, a float
+    lib.define('resize_many_maps(Tensor[] maps, int[] output_size, str mode="bilinear", float[]? boxes=None, bool[]? flips=None, '
+               'int[]? sizes=None, int[]? offsets=None, float? fill=None, str overflow="pillow") -> Tensor')
+
+    def _many_maps_meta(maps, output_size, mode="bilinear", boxes=None, flips=None, sizes=None, offsets=None, fill=None, overflow="pillow"):
+        if not maps:
+            raise ValueError("resize_many_maps(): the op needs at least one map (an empty list has no dtype)")
+        return torch.empty((len(maps), 1, output_size[0], output_size[1]), dtype=maps[0].dtype, device="meta")
+
+    def _many_maps_fill(maps, fill):
+        if fill is None:
+            return 0
+        return fill if maps and maps[0].dtype == torch.float32 else (int(fill) if int(fill) == fill else fill)
+
+    lib.impl("resize_many_maps", lambda maps, output_size, mode="bilinear", boxes=None, flips=None, sizes=None, offsets=None, fill=None,
+             overflow="pillow": resize_many_maps(list(maps), output_size, mode, boxes=_many_boxes(maps, boxes), flips=flips,
+                                                 sizes=_many_pairs(maps, sizes, "sizes"), offsets=_many_pairs(maps, offsets, "offsets"),
+                                                 fill=_many_maps_fill(maps, fill), overflow=overflow), "CUDA")
+    lib.impl("resize_many_maps", _many_maps_meta, "Meta")
 
     # the ragged Image.reduce: factors one int, one (fx, fy) or 2 N ints (x first); boxes 4 N ints, a full-image box standing for None
     lib.define("reduce_many(Tensor[] images, int[] factors, int[]? boxes=None) -> Tensor[]")

@@ -62,6 +62,12 @@ plain device copy of the output's bytes, the write floor:
 
 Both ways give the same elements.  No bar is set; what is required is two kernel launches whatever N, and that the numbers are written down.
 
+--maps: resize_many_maps (Pillow's "I;16" / "I" / "F" resize: double coefficients, double sums, the mode's store after each pass) on
+64 camera-sized uint16 maps, H in [1080, 3000], W in [1440, 4000], one RandomResizedCrop box each -> 224 x 224, bilinear and bicubic,
+half the items flipped.  No other GPU code produces these bits, so the contestants are the same call issued once per item (64 x 3
+launches) and the one call (3 launches); resize_many_nearest on the same geometry (the maps viewed as int16) is the copy-only floor.
+No bar is set; what is required is three launches whatever N, and that the numbers are written down.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
@@ -76,6 +82,7 @@ results into one tensor; (c) writes the batch.
   python tools/resize_many_bench.py --gap > out.txt      # only the reducing_gap step for a list (above); profiles/resize_many_gap.txt
   python tools/resize_many_bench.py --alpha > out.txt    # only Pillow's RGBA resize for a list (above); profiles/resize_many_alpha.txt
   python tools/resize_many_bench.py --nearest > out.txt  # only Pillow's NEAREST for a list (above); profiles/resize_many_nearest.txt
+  python tools/resize_many_bench.py --maps > out.txt     # only Pillow's I;16 resize for a list (below); profiles/resize_many_maps.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -520,6 +527,62 @@ def nearest(args, torch, aa, timed):
               + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
 
 
+def maps(args, torch, aa, timed):
+    """resize_many_maps against the same call issued once per item, and resize_many_nearest on the same geometry as the copy-only floor."""
+    rng = np.random.default_rng(SEED)
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)]
+    # (int16 noise viewed as uint16: the whole range, and the int16 views go to resize_many_nearest as they are)
+    signed = [torch.randint(-32768, 32768, (1, h, w), dtype=torch.int16, device="cuda", generator=gen) for h, w in shapes]
+    items = [t.view(torch.uint16) for t in signed]
+    brng = np.random.default_rng(SEED + 1)
+    boxes = [random_resized_crop_box(brng, h, w) for h, w in shapes]
+    flips = [i % 2 == 1 for i in range(N)]
+    print(f"resize_many_bench --maps: Pillow's I;16 resize for a list (seed {SEED}); library: {os.path.basename(_lib_path())}")
+    print(f"{N} single-channel uint16 maps, H in [1080, 3000], W in [1440, 4000], one RandomResizedCrop box each -> {OUT}, {sum(flips)} flipped")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+    for mode in MODES:
+        def one_call(n=N):
+            return aa.resize_many_maps(items[:n], list(OUT), mode, boxes=boxes[:n], flips=flips[:n])
+
+        def per_item():
+            return [aa.resize_many_maps(items[i:i + 1], list(OUT), mode, boxes=boxes[i:i + 1], flips=flips[i:i + 1]) for i in range(N)]
+
+        def floor():
+            return aa.resize_many_nearest(signed, list(OUT), boxes=boxes, flips=flips)
+
+        contestants = {"loop: resize_many_maps once per item": per_item, "call: resize_many_maps": one_call,
+                       "floor: resize_many_nearest, same geometry (copies only)": floor}
+        for fn in contestants.values():
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        assert torch.equal(torch.cat(per_item()).view(torch.int16), one_call().view(torch.int16)), "the one call differs from the call per item"
+        times = {k: [] for k in contestants}
+        for _ in range(args.rounds):
+            for k, fn in contestants.items():
+                times[k].append(timed(fn))
+        print(f"\n{mode}")
+        stat = {}
+        for k, v in times.items():
+            stat[k] = (statistics.median(v), min(v), max(v))
+            launches = count_launches(torch, contestants[k])
+            print(f"  {k:56s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]   kernel launches per batch: "
+                  f"{launches if launches is not None else 'not measured'}")
+        (ml, ll, hl), (mc, lc, hc), (mf, _, _) = stat.values()
+        verdict = "the one call is faster" if hc < ll else ("THE ONE CALL IS NOT FASTER than the call per item" if mc >= ml else "faster by the medians, the ranges overlap")
+        print(f"  one call against the call per item: {ml / mc:.2f} x: {verdict}; against the copy-only floor: {mc / mf:.2f} x its time")
+        for part in ("maps_tables", "maps_hpass", "maps_vpass"):
+            kt = kernel_times(torch, one_call, part)
+            if kt:
+                print(f"  {part}: device time median {statistics.median(kt):8.1f} us [{min(kt):8.1f} .. {max(kt):8.1f}] over {len(kt)} launches")
+            else:
+                print(f"  {part}: device time not measured")
+        counts = {n: count_launches(torch, lambda: one_call(n)) for n in (1, 8, N)}
+        print("  kernel launches of one resize_many_maps call by N (expected 3, whatever N): "
+              + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
+
+
 def kernel_times(torch, fn, part, calls=12):
     """Device durations in us of the kernels whose name holds `part`, over `calls` runs of fn(), from torch's profiler; [] where it
     records no device activity."""
@@ -591,6 +654,7 @@ def main():
     ap.add_argument("--gap", action="store_true", help="only Pillow's reducing_gap for a list: the loop, resize_many without a gap, and the new step")
     ap.add_argument("--alpha", action="store_true", help="only Pillow's RGBA resize for a list: the loop with alpha=True against resize_many(alpha=True)")
     ap.add_argument("--nearest", action="store_true", help="only Pillow's NEAREST for label maps: resize_many_nearest against the per-image torch loop")
+    ap.add_argument("--maps", action="store_true", help="only Pillow's I;16 resize for measured maps: resize_many_maps against the call per item")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -679,6 +743,9 @@ def main():
         return
     if args.nearest:
         nearest(args, torch, aa, timed)
+        return
+    if args.maps:
+        maps(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
