@@ -504,6 +504,53 @@ int aa_many_plan_maps(int filter, int elem, int64_t n, int64_t oH, int64_t oW, c
 int aa_resample_many_maps(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
                           aa_stream_t stream);
 
+/* Subsampled YCbCr planes to an RGB batch (resize_many_ycbcr): what a JPEG or video decoder next to the GPU produces, taken to the
+ * batch without an RGB image in between.  Item i has a luma plane [H, W] and two chroma planes [ceil(H / sy), ceil(W / sx)], chroma
+ * centred (JFIF siting); with b its box (or the whole luma plane) and cb = (b.x0 / sx, b.y0 / sy, b.x1 / sx, b.y1 / sy) in float32,
+ *   P = merge("YCbCr", [resize(Y, b), resize(Cb, cb), resize(Cr, cb)]).convert("RGB")       each resize Pillow's "L" resize to (vW, vH)
+ * is pasted at its place of the canvas, everything else the fill, which is three RGB bytes written as given; the whole canvas row is
+ * mirrored for an item with AA_MANY_FLIP_X.  Bit for bit Pillow's bytes: every plane goes through both 8bpc passes at its own
+ * resolution, each rounded to a byte, and Pillow's YCbCr -> RGB integer conversion runs once per output pixel (csrc/aa_ycbcr.h).
+ * This is NOT what decoding to RGB with a decoder's chroma upsampling and resizing that gives: the roundings fall elsewhere.
+ * aa_ycbcr_image: byte (row y, column x) of the luma plane is at y_dev + y * y_stride_row + x; of a chroma plane at
+ * c{b,r}_dev + y * c{b,r}_stride_row + x * chroma_stride_px.  chroma_stride_px 1: two planes, each anywhere with its own pitch;
+ * 2: interleaved Cb Cr pairs (NV12), cr_dev == cb_dev + 1 and equal pitches (AA_ERR_STRIDES otherwise).  ONE arrangement per call
+ * (AA_ERR_STRIDES for a mixed list).  box, has_box, flags as aa_many_image's, in luma coordinates; flags 0 or AA_MANY_FLIP_X.
+ * aa_many_plan_ycbcr is host arithmetic only (no HIP call: works without a device) and does every check: AA_ERR_NULL for a null
+ * plane; AA_ERR_BAD_SHAPE for an unknown subsampling, a chroma shape other than [ceil(H / sy), ceil(W / sx)], a box beyond the luma
+ * plane, a bad place; the other errors are aa_many_plan_placed's.  desc_bytes >= aa_many_desc_bytes_ycbcr(n), and that many bytes are
+ * copied to the device.  n == 0 plans an empty block (AA_OK), which launches nothing.
+ * aa_resample_many_ycbcr enqueues THREE launches whatever n when the chroma is planar (one table kernel and one horizontal pass over
+ * all 3 n planes, one converting vertical pass) and FIVE when it is interleaved (luma and chroma pairs have a table kernel and a
+ * horizontal pass each: their rows differ in bytes per pixel).  cv NULL: out_dev is uint8 [n, 3, oH, oW] in out_layout; otherwise
+ * aa_resample_many_u8_to_float's conversion of those bytes (cv->out_layout is not read: out_layout says it), out_dev aligned to its
+ * element.  desc_dev (8-byte aligned), workspace_dev (16-byte aligned, at least the plan's size) as aa_resample_many_u8.  Every check
+ * comes before the first launch; nothing is allocated, synchronised or read back, no table cache is touched.
+ * aa_ycbcr_to_rgb_u8: the conversion alone, on the host, n_px interleaved triples to n_px interleaved triples, with the code the
+ * kernel compiles.  Added without an ABI version change (additive). */
+#define AA_YCC_444 0  /* sx, sy = 1, 1 */
+#define AA_YCC_422 1  /* 2, 1 */
+#define AA_YCC_420 2  /* 2, 2 */
+#define AA_YCC_440 3  /* 1, 2 */
+typedef struct aa_ycbcr_image {
+  const void *y_dev, *cb_dev, *cr_dev;
+  int64_t H, W;            /* the luma plane */
+  int64_t cH, cW;          /* the chroma planes: checked against H, W and the subsampling */
+  int64_t y_stride_row, cb_stride_row, cr_stride_row; /* in BYTES */
+  int32_t chroma_stride_px; /* 1: planes; 2: interleaved Cb Cr pairs */
+  int32_t subsampling;     /* AA_YCC_* */
+  double box[4];           /* x0, y0, x1, y1 in luma coordinates */
+  int32_t has_box;
+  int32_t flags;           /* 0 or AA_MANY_FLIP_X */
+} aa_ycbcr_image;
+size_t aa_many_desc_bytes_ycbcr(int64_t n);
+int aa_many_plan_ycbcr(int filter, int64_t n, int64_t oH, int64_t oW, const aa_ycbcr_image *images,
+                       const aa_many_place *places /* may be NULL */, const uint8_t fill_rgb[3] /* NULL: 0 */, void *desc_host,
+                       size_t desc_bytes, size_t *workspace_bytes);
+int aa_resample_many_ycbcr(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
+                           const aa_convert *cv /* NULL: uint8 */, int out_layout, aa_stream_t stream);
+int aa_ycbcr_to_rgb_u8(const uint8_t *ycbcr, uint8_t *rgb, int64_t n_px);
+
 /* ---- ragged Image.reduce: N uint8 images of N sizes, each with its own integer box and factors, into one arena ------------------------
  * Pillow's first step of Image.resize(reducing_gap=...) for a list: every large item is read ONCE by an integer box mean, and the ragged
  * resize above then runs over the small results, which it reads where they lie (an arena offset is just another pointer of an

@@ -56,6 +56,7 @@ EXPORTS = (
     "aa_reduce_many_desc_bytes", "aa_reduce_many_plan", "aa_reduce_many_u8",
     "aa_many_desc_bytes_nearest", "aa_many_plan_nearest", "aa_resample_many_nearest",
     "aa_many_desc_bytes_maps", "aa_many_plan_maps", "aa_resample_many_maps",
+    "aa_many_desc_bytes_ycbcr", "aa_many_plan_ycbcr", "aa_resample_many_ycbcr", "aa_ycbcr_to_rgb_u8",
     "aa_set_launch_shape", "aa_last_launch_shape",
 )
 
@@ -161,6 +162,23 @@ class MapsItem(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class YccImage(ctypes.Structure):
+    """aa_ycbcr_image: one item of the ragged YCbCr call (strides in bytes; box = x0, y0, x1, y1 in luma coordinates)."""
+    _fields_ = [("y_dev", ctypes.c_void_p), ("cb_dev", ctypes.c_void_p), ("cr_dev", ctypes.c_void_p), ("H", ctypes.c_int64), ("W", ctypes.c_int64),
+                ("cH", ctypes.c_int64), ("cW", ctypes.c_int64), ("y_stride_row", ctypes.c_int64), ("cb_stride_row", ctypes.c_int64),
+                ("cr_stride_row", ctypes.c_int64), ("chroma_stride_px", ctypes.c_int32), ("subsampling", ctypes.c_int32),
+                ("box", ctypes.c_double * 4), ("has_box", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class YccHeader(ctypes.Structure):
+    """Head of the block aa_many_plan_ycbcr writes (csrc/aa_many_ycbcr.h AAYccHeader; opaque to C callers, mirrored for the tests): plan A
+    (a placed ManyHeader block: the luma items, then the Cb and the Cr items when the chroma is planar) at off_a, plan B (the interleaved
+    chroma pairs) at off_b or 0."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("oH", ctypes.c_int32), ("oW", ctypes.c_int32), ("filter", ctypes.c_int32),
+                ("interleaved", ctypes.c_int32), ("flips", ctypes.c_int32), ("fill", ctypes.c_uint32), ("off_a", ctypes.c_int64),
+                ("off_b", ctypes.c_int64), ("ws_b", ctypes.c_int64), ("ws_bytes", ctypes.c_int64)]
+
+
 class ReduceItem(ctypes.Structure):
     """aa_reduce_item: one item of the ragged Image.reduce (strides in bytes; box = x0, y0, x1, y1 integers; factors fx, fy)."""
     _fields_ = [("data_dev", ctypes.c_void_p), ("H", ctypes.c_int64), ("W", ctypes.c_int64), ("stride_row", ctypes.c_int64),
@@ -207,6 +225,8 @@ MAPS_OVERFLOW = {"pillow": 0, "clamp": 1}  # aa_many_plan_maps overflow (AA_MAPS
 MAPS_ITEM_FLIP, MAPS_ITEM_HPASS, MAPS_ITEM_VPASS = 1, 2, 4  # MapsItem.flags (csrc/aa_many_maps.h AA_MAPS_ITEM_*)
 MAPS_HROWS = 16     # hull rows per work unit of the maps call's horizontal pass (csrc/aa_many_maps.h AA_MAPS_HROWS)
 MAPS_VCOLS = 256    # canvas columns per work unit of the maps call's vertical pass (csrc/aa_many_maps.h AA_MAPS_VCOLS)
+YCC_SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "440": 3}  # aa_ycbcr_image.subsampling (AA_YCC_*)
+YCC_VROWS, YCC_VCOLS = 4, 256  # canvas rows and columns per work unit of the YCbCr call's vertical pass (csrc/aa_many_ycbcr.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
 
@@ -380,6 +400,15 @@ def load() -> ctypes.CDLL:
     L.aa_many_plan_maps.restype = i32
     L.aa_resample_many_maps.argtypes = [vp, vp, vp, vp, sz, vp]
     L.aa_resample_many_maps.restype = i32
+    L.aa_many_desc_bytes_ycbcr.argtypes = [i64]
+    L.aa_many_desc_bytes_ycbcr.restype = sz
+    L.aa_many_plan_ycbcr.argtypes = [i32, i64, i64, i64, ctypes.POINTER(YccImage), ctypes.POINTER(ManyPlace), ctypes.POINTER(ctypes.c_uint8),
+                                     vp, sz, ctypes.POINTER(sz)]
+    L.aa_many_plan_ycbcr.restype = i32
+    L.aa_resample_many_ycbcr.argtypes = [vp, vp, vp, vp, sz, cvp, i32, vp]
+    L.aa_resample_many_ycbcr.restype = i32
+    L.aa_ycbcr_to_rgb_u8.argtypes = [vp, vp, i64]
+    L.aa_ycbcr_to_rgb_u8.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

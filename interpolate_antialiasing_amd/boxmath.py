@@ -311,3 +311,39 @@ def axis_is_full(in_size: int, in0: float, in1: float) -> bool:
 def is_plain_crop(box: Sequence[float], out_w: int, out_h: int) -> bool:
     """Pillow's C resize: integer offsets and a box of exactly the output's size is a crop, not a filter."""
     return box[0] == int(box[0]) and box[1] == int(box[1]) and box[2] - box[0] == out_w and box[3] - box[1] == out_h
+
+
+# ---- subsampled YCbCr planes (resize_many_ycbcr) ----------------------------------------------------------------------------------------------
+SUBSAMPLING = {"444": (1, 1), "422": (2, 1), "420": (2, 2), "440": (1, 2)}  # name -> (sx, sy), the luma samples per chroma sample
+
+
+def check_subsampling(subsampling: str) -> Tuple[int, int]:
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {', '.join(repr(k) for k in SUBSAMPLING)}, got {subsampling!r}")
+    return SUBSAMPLING[subsampling]
+
+
+def chroma_shape(h: int, w: int, subsampling: str) -> Tuple[int, int]:
+    """(h, w) of the chroma planes of an [h, w] luma plane: ceil(h / sy), ceil(w / sx), what a JPEG or video decoder produces."""
+    sx, sy = check_subsampling(subsampling)
+    return -(-int(h) // sy), -(-int(w) // sx)
+
+
+def chroma_box(box: Optional[Sequence[float]], shape: Sequence[int], subsampling: str) -> Tuple[float, float, float, float]:
+    """The box of the chroma planes for a luma box (x0, y0, x1, y1), or for the whole [H, W] = ``shape`` luma plane when None: the luma
+    box as Pillow's C sees it (float32 values) over the subsampling, in float32 — a division by 1 or 2, which is exact.  Chroma is
+    centred (JFIF siting), so chroma sample j covers the luma interval [j * s, (j + 1) * s) and the coordinates simply scale.  It is a
+    proper box even for None: for an odd W, W / sx is half a sample less than the chroma plane's width."""
+    sx, sy = check_subsampling(subsampling)
+    b = box_f32(box) if box is not None else (0.0, 0.0, f32(float(shape[1])), f32(float(shape[0])))
+    return f32(b[0] / sx), f32(b[1] / sy), f32(b[2] / sx), f32(b[3] / sy)
+
+
+_YCC_COEFFS = (1.402, -0.34414, -0.71414, 1.772)  # R from Cr, G from Cb, G from Cr, B from Cb (Pillow's ConvertYCbCr.c)
+
+
+def ycbcr_rgb_tables():
+    """Pillow's four YCbCr -> RGB tables (R_Cr, G_Cb, G_Cr, B_Cb), 256 ints each: ``int(c * 64 * (v - 128) + 0.5)`` with C's cast, which
+    truncates towards zero (Python's int() does too).  R = clip(Y + (R_Cr[Cr] >> 6)), G = clip(Y + ((G_Cb[Cb] + G_Cr[Cr]) >> 6)),
+    B = clip(Y + (B_Cb[Cb] >> 6)), >> arithmetic.  The library computes the same entries in registers (csrc/aa_ycbcr.h)."""
+    return tuple([int(c * 64 * (v - 128) + 0.5) for v in range(256)] for c in _YCC_COEFFS)

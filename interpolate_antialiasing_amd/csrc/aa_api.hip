@@ -11,6 +11,8 @@
 #include "aa_many.h"
 #include "aa_many_maps.h"
 #include "aa_many_nearest.h"
+#include "aa_many_ycbcr.h"
+#include "aa_ycbcr.h"
 #include "aa_reduce_many.h"
 #include "aa_plan.h"
 #include "aa_reduce.h"
@@ -585,6 +587,36 @@ int aa_resample_many_maps(const void *desc_host, const void *desc_dev, void *out
                           aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_many_maps(desc_host, desc_dev, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t aa_many_desc_bytes_ycbcr(int64_t n) { return aa_ycc_desc_size(n); }
+
+int aa_many_plan_ycbcr(int filter, int64_t n, int64_t oH, int64_t oW, const aa_ycbcr_image *images, const aa_many_place *places,
+                       const uint8_t fill_rgb[3], void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
+  return aa_ycc_plan_host(filter, n, oH, oW, images, places, fill_rgb, desc_host, desc_bytes, workspace_bytes);
+}
+
+int aa_resample_many_ycbcr(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes,
+                           const aa_convert *cv, int out_layout, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  int out_elem = AA_U8;
+  if (cv) {
+    if ((cv->flags & AA_FLAG_OUT_F16) && (cv->flags & AA_FLAG_OUT_BF16)) return AA_ERR_BAD_DTYPE;
+    if (cv->flags & ~(AA_FLAG_OUT_F16 | AA_FLAG_OUT_BF16)) return AA_ERR_BAD_SHAPE;  // (AA_FLAG_FAST: the conversion has one arithmetic)
+    out_elem = (cv->flags & AA_FLAG_OUT_F16) ? AA_F16 : ((cv->flags & AA_FLAG_OUT_BF16) ? AA_BF16 : AA_F32);
+  }
+  return aa_launch_many_ycbcr(desc_host, desc_dev, out_dev, workspace_dev, workspace_bytes, out_elem, out_layout, cv ? cv->normalize : 0,
+                              cv ? cv->mean : nullptr, cv ? cv->std : nullptr, (hipStream_t)stream);
+}
+
+int aa_ycbcr_to_rgb_u8(const uint8_t *ycbcr, uint8_t *rgb, int64_t n_px) {
+  if (n_px < 0) return AA_ERR_BAD_SHAPE;
+  if (n_px > 0 && (!ycbcr || !rgb)) return AA_ERR_NULL;
+  for (int64_t i = 0; i < n_px; i++) {
+    const uint32_t v = aa_ycbcr_to_rgb(ycbcr[3 * i], ycbcr[3 * i + 1], ycbcr[3 * i + 2]);
+    rgb[3 * i] = (uint8_t)v; rgb[3 * i + 1] = (uint8_t)(v >> 8); rgb[3 * i + 2] = (uint8_t)(v >> 16);
+  }
+  return AA_OK;
 }
 
 // ---- Image.reduce ------------------------------------------------------------------------------------------------------------------------

@@ -97,3 +97,9 @@ int aa_many_plan_patches_host(int filter, int layout, int64_t n, int64_t C, int6
                               int64_t pad_to, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, int64_t *rows);
 int aa_launch_many_patches(const void *desc_host, const void *desc_dev, void *out_dev, void *workspace_dev, size_t workspace_bytes, int out_elem,
                            int ppc, int normalize, const float *mean, const float *std, hipStream_t stream);
+// For a planner that composes placed plans of its own (aa_many_ycbcr.hip): aa_many_plan_host's block with the placement records always
+// present (a patch plan's `own_canvas`: no bound on a dense vertical grid, which the composing planner has itself), and the table kernel
+// and the horizontal pass of such a block, enqueued on their own (two launches; none for n == 0 or when no item lies on the canvas).
+int aa_many_plan_placed_always_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                                    const aa_many_place *places, void *desc_host, size_t desc_bytes, size_t *workspace_bytes);
+int aa_launch_many_tables_hpass(const void *desc_host, const void *desc_dev, void *workspace_dev, size_t workspace_bytes, hipStream_t stream);

@@ -898,3 +898,19 @@ int aa_launch_many_patches(const void *desc_host, const void *desc_dev, void *ou
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }
+
+// ---- host: for composing planners (aa_many.h) ------------------------------------------------------------------------------------------------
+int aa_many_plan_placed_always_host(int filter, int layout, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
+                                    const aa_many_place *places, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
+  return many_plan(filter, layout, n, C, oH, oW, images, places, nullptr, true, desc_host, desc_bytes, workspace_bytes);
+}
+
+int aa_launch_many_tables_hpass(const void *desc_host, const void *desc_dev, void *workspace_dev, size_t workspace_bytes, hipStream_t stream) {
+  const AAManyHeader *hd = (const AAManyHeader *)desc_host;
+  if (hd->magic != AA_MANY_MAGIC || (hd->kind & (AA_MANY_PLAN_PLACED | AA_MANY_PLAN_ALPHA)) != AA_MANY_PLAN_PLACED) return AA_ERR_BAD_SHAPE;
+  const int rc = many_check(hd, desc_dev, hd->n, hd->C, hd->oH, hd->oW, hd->layout, workspace_dev, workspace_bytes);
+  if (rc != AA_OK || hd->n == 0) return rc;
+  launch_many_tables_hpass<true>(hd, many_views(hd, desc_dev), (char *)workspace_dev, hd->oH, hd->oW, stream);
+  AA_HIP_CHECK_LAUNCH();
+  return AA_OK;
+}

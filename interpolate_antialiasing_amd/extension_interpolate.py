@@ -973,6 +973,167 @@ def resize_many_maps(maps, output_size: Sequence[int], mode: str = "bilinear", *
                                                                              stream))[0]
 
 
+def _ycbcr_plane(name: str, i: int, what: str, t, dims: int):
+    """One plane of item i, checked -> a uint8 tensor of `dims` dimensions ([H, W], or [h, w, 2] for interleaved chroma)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}(): images[{i}] {what} must be Tensor")
+    if t.dtype != torch.uint8:
+        raise TypeError(f"{name}(): images[{i}] {what} is {t.dtype}; the planes of a decoder are torch.uint8")
+    if dims == 2 and t.dim() == 3 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != dims or (dims == 3 and t.shape[2] != 2):
+        shape = "[H, W] or [1, H, W]" if dims == 2 else "[h, w, 2]"
+        raise ValueError(f"{name}(): images[{i}] {what} must be {shape}, got {list(t.shape)}")
+    if min(t.shape) <= 0:
+        raise ValueError(f"{name}(): images[{i}] {what} is empty: {list(t.shape)}")
+    return t
+
+
+def _ycbcr_in_place(t: torch.Tensor, px: int) -> torch.Tensor:
+    """A plane as the library reads it: unit pixel stride (px elements per pixel: 2 for interleaved pairs), any row pitch, any offset;
+    anything else is copied."""
+    ok = t.stride(0) >= 0 and (t.shape[1] == 1 or t.stride(1) == px) and (px == 1 or t.stride(2) == 1)
+    return t if ok else t.contiguous()
+
+
+def resize_many_ycbcr(images, output_size: Sequence[int], mode: str = "bilinear", *, subsampling="420", boxes=None, flips=None, sizes=None,
+                      offsets=None, fill=None, out_dtype=None, out_format: str = "nchw", mean=None, std=None) -> torch.Tensor:
+    """What a JPEG or video decoder next to the GPU produces — a luma plane and subsampled chroma planes — taken straight to the RGB batch
+    a model reads, without expanding the chroma, a colour-conversion pass or an RGB image in between.  Per item i, bit for bit,
+
+        b  = boxes[i] or (0, 0, W, H)                                   # float32 values, luma coordinates
+        cb = boxmath.chroma_box(boxes[i], (H, W), subsampling)          # b over (sx, sy), float32
+        r  = lambda p, bx: Image.fromarray(p, "L").resize((vw, vh), FILTER, box=bx)
+        R_i = Image.merge("YCbCr", [r(Y, b), r(Cb, cb), r(Cr, cb)]).convert("RGB")
+
+    so every plane is resized exactly as Pillow resizes an "L" image, at its own resolution (both 8bpc passes, each rounded to a byte),
+    and the three bytes of a pixel then go through Pillow's YCbCr -> RGB conversion.  After that the call is ``resize_many_to_float``:
+    ``R_i`` is pasted at ``offsets[i]`` of the [oh, ow] canvas, the rest is ``fill``, the canvas row is mirrored where ``flips[i]``, and a
+    float ``out_dtype`` gives ``(float(byte) - mean[c]) / std[c]`` in fp32, rounded once.
+    This is NOT what decoding to RGB with the decoder's chroma upsampling and resizing that image gives: the roundings fall elsewhere.
+
+    ``images``: N tuples ``(Y, Cb, Cr)`` or ``(Y, CbCr)`` of uint8 GPU tensors.  ``Y`` is [H, W] (or [1, H, W]); ``Cb`` and ``Cr`` are
+    [h, w] each, anywhere, each with its own pitch; ``CbCr`` is one [h, w, 2] tensor of interleaved pairs, Cb first (NV12).  One
+    arrangement per call.  Planes are read where they lie: unit pixel stride, any row pitch, any offset; anything else is copied.
+    ``subsampling``: "444" | "422" | "420" | "440", one string or one per item; [h, w] must be ``boxmath.chroma_shape(H, W, subsampling)``
+    = [ceil(H / sy), ceil(W / sx)] (ValueError otherwise).  Chroma is centred (JFIF siting).
+    ``boxes``, ``flips``, ``sizes``, ``offsets``: exactly ``resize_many_to_float``'s, in luma coordinates.
+    ``fill``: None (black) or three RGB values, written as given, never converted.
+    ``out_dtype``: None / torch.uint8 (Pillow's RGB bytes) | torch.float32 | torch.float16 | torch.bfloat16; ``mean`` / ``std`` (three
+    values each, 0..255 units, given together) with a float ``out_dtype`` only.
+    ``out_format``: "nchw" (contiguous [N, 3, oh, ow]) | "nhwc" (the same shape, channels_last).  N == 0 gives the empty tensor.
+
+    Three launches whatever N when the chroma is planar (one table kernel and one horizontal pass over all 3 N planes, one converting
+    vertical pass), five when it is interleaved (luma and chroma pairs each have the first two), one non-blocking copy of a packed
+    descriptor, nothing read back, no table cache touched.  Not built: video-range or BT.709 matrices, left-sited chroma, NV21, alpha,
+    patches, reducing_gap."""
+    name = "resize_many_ycbcr"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if out_dtype not in (None, torch.uint8, torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built; None / torch.uint8, torch.float32, torch.float16 or torch.bfloat16")
+    if out_format not in ("nchw", "nhwc"):
+        raise ValueError("out_format must be 'nchw' or 'nhwc'")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std must be given together")
+    as_bytes = out_dtype in (None, torch.uint8)
+    if as_bytes and mean is not None:
+        raise ValueError(f"{name}(): mean / std need a float out_dtype")
+    if len(output_size) != 2:
+        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
+    oh, ow = int(output_size[0]), int(output_size[1])
+    if not (oh > 0 and ow > 0):
+        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    images = list(images)
+    n = len(images)
+    subs = [subsampling] * n if isinstance(subsampling, str) else list(subsampling)
+    if len(subs) != n:
+        raise ValueError(f"{name}(): subsampling must be one string or one per image ({n}), got {len(subs)}")
+    if boxes is not None and len(boxes) != n:
+        raise ValueError(f"{name}(): boxes must hold one entry per image ({n}), got {len(boxes)}")
+    planes, arrangement = [], None
+    for i, item in enumerate(images):
+        if not isinstance(item, (tuple, list)) or len(item) not in (2, 3):
+            raise TypeError(f"{name}(): images[{i}] must be a (Y, Cb, Cr) or (Y, CbCr) tuple of tensors")
+        boxmath.check_subsampling(subs[i])
+        y = _ycbcr_plane(name, i, "Y", item[0], 2)
+        if len(item) == 3:
+            chroma = [_ycbcr_plane(name, i, "Cb", item[1], 2), _ycbcr_plane(name, i, "Cr", item[2], 2)]
+        else:
+            chroma = [_ycbcr_plane(name, i, "CbCr", item[1], 3)]
+        if arrangement is None:
+            arrangement = len(item)
+        elif arrangement != len(item):
+            raise ValueError(f"{name}(): one chroma arrangement per call: images[{i}] has {len(item) - 1} chroma tensor(s), images[0] "
+                             f"{arrangement - 1} (planar (Y, Cb, Cr) or interleaved (Y, CbCr))")
+        h, w = int(y.shape[0]), int(y.shape[1])
+        want = boxmath.chroma_shape(h, w, subs[i])
+        for t in chroma:
+            if tuple(t.shape[:2]) != want:
+                raise ValueError(f"{name}(): images[{i}] is [{h}, {w}] with subsampling {subs[i]!r}: its chroma must be {list(want)}, got "
+                                 f"{list(t.shape[:2])}")
+            if t.device != y.device:
+                raise ValueError(f"{name}(): images[{i}]: every plane must be on the same device")
+        if planes and y.device != planes[0][0].device:
+            raise ValueError(f"{name}(): every image must be on the same device: images[{i}] is on {y.device}, images[0] on {planes[0][0].device}")
+        planes.append((y, chroma))
+    checked = []
+    for i, (y, _) in enumerate(planes):
+        bx = boxes[i] if boxes is not None else None
+        checked.append(None if bx is None else boxmath.box_f32(boxmath.check_box(bx, int(y.shape[1]), int(y.shape[0]))))
+    cv, res_dtype = None, torch.uint8
+    if as_bytes:
+        if flips is not None:
+            flips = [bool(v) for v in flips]
+            if len(flips) != n:
+                raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
+    else:
+        cv, flips, res_dtype = _many_convert(name, {"out_dtype": out_dtype, "mean": mean, "std": std, "flips": flips}, n, 3)
+    fills = _many_fill(name, 0 if fill is None else fill, 3)
+    places = _many_places(name, sizes, offsets, n, oh, ow)
+    if n == 0:
+        return torch.empty((0, 3, oh, ow), dtype=res_dtype, device=_many_empty_device(None))
+    for y, chroma in planes:
+        for t in [y] + chroma:
+            _require_gpu(t, name)
+    dev = planes[0][0].device
+    nhwc = out_format == "nhwc"
+    if cv is not None:
+        cv.out_layout = _lib.NHWC if nhwc else _lib.NCHW
+    L = _lib.load()
+    recs, keep = (_lib.YccImage * n)(), []
+    for i, (y, chroma) in enumerate(planes):
+        y = _ycbcr_in_place(y, 1)
+        chroma = [_ycbcr_in_place(t, 1 if arrangement == 3 else 2) for t in chroma]
+        keep += [y] + chroma  # (copies must outlive the launches; the stream orders their release after them)
+        r = recs[i]
+        r.y_dev, r.cb_dev = y.data_ptr(), chroma[0].data_ptr()
+        r.cr_dev = chroma[1].data_ptr() if arrangement == 3 else chroma[0].data_ptr() + 1
+        r.H, r.W = int(y.shape[0]), int(y.shape[1])
+        r.cH, r.cW = int(chroma[0].shape[0]), int(chroma[0].shape[1])
+        # (the pitch of a plane of one row is arbitrary)
+        r.y_stride_row = y.stride(0) if r.H > 1 else 0
+        r.cb_stride_row = chroma[0].stride(0) if r.cH > 1 else 0
+        r.cr_stride_row = chroma[-1].stride(0) if r.cH > 1 else 0
+        r.chroma_stride_px = 1 if arrangement == 3 else 2
+        r.subsampling = _lib.YCC_SUBSAMPLING[subs[i]]
+        if checked[i] is not None:
+            r.has_box = 1
+            r.box[:] = checked[i]
+        if flips is not None and flips[i]:
+            r.flags = _lib.MANY_FLIP_X
+    precs = _many_pack_places(places)
+    cfill = (ctypes.c_uint8 * 3)(*fills)
+    layout = _lib.NHWC if nhwc else _lib.NCHW
+    mf = torch.channels_last if nhwc else torch.contiguous_format
+    return _many_run(
+        name, dev, L.aa_many_desc_bytes_ycbcr(n),
+        lambda desc, nbytes, ws_bytes: L.aa_many_plan_ycbcr(_lib.FILTER_IDS[mode], n, oh, ow, recs, precs, cfill, desc, nbytes, ws_bytes),
+        lambda: torch.empty((n, 3, oh, ow), dtype=res_dtype, device=dev, memory_format=mf),
+        lambda desc_host, desc_dev, out, ws, stream: L.aa_resample_many_ycbcr(desc_host, desc_dev, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                                              ctypes.byref(cv) if cv is not None else None, layout, stream))[0]
+
+
 def _patch_sizes(name: str, sizes, patch, n: int, pad_to):
     """patch, sizes and pad_to of resize_many_to_patches, checked -> ((ph, pw), [(vh, vw)] per item, L or None)."""
     try:
@@ -1740,6 +1901,37 @@ def _register_torch_ops() -> None:
                                                  sizes=_many_pairs(maps, sizes, "sizes"), offsets=_many_pairs(maps, offsets, "offsets"),
                                                  fill=_many_maps_fill(maps, fill), overflow=overflow), "CUDA")
     lib.impl("resize_many_maps", _many_maps_meta, "Meta")
+
+    # subsampled YCbCr planes to an RGB batch: N luma planes; N interleaved [h, w, 2] chroma tensors, or 2 N planes (Cb_0, Cr_0, Cb_1, ...);
+    # subsampling one string or N joined by commas; the same flattened boxes / sizes / offsets / fill as resize_many
+    lib.define('resize_many_ycbcr(Tensor[] luma, Tensor[] chroma, int[] output_size, str mode="bilinear", str subsampling="420", '
+               'float[]? boxes=None, bool[]? flips=None, int[]? sizes=None, int[]? offsets=None, int[]? fill=None, ScalarType? out_dtype=None, '
+               'str out_format="nchw", float[]? mean=None, float[]? std=None) -> Tensor')
+
+    def _ycbcr_tuples(luma, chroma):
+        n = len(luma)
+        if len(chroma) == n:
+            return [(luma[i], chroma[i]) for i in range(n)]
+        if len(chroma) == 2 * n:
+            return [(luma[i], chroma[2 * i], chroma[2 * i + 1]) for i in range(n)]
+        raise ValueError(f"resize_many_ycbcr(): chroma must hold one [h, w, 2] tensor or two planes per luma plane ({n}), got {len(chroma)}")
+
+    def _ycbcr_meta(luma, chroma, output_size, mode="bilinear", subsampling="420", boxes=None, flips=None, sizes=None, offsets=None, fill=None,
+                    out_dtype=None, out_format="nchw", mean=None, std=None):
+        _ycbcr_tuples(luma, chroma)
+        mf = torch.channels_last if out_format == "nhwc" else torch.contiguous_format
+        return torch.empty((len(luma), 3, output_size[0], output_size[1]), dtype=torch.uint8 if out_dtype is None else out_dtype, device="meta",
+                           memory_format=mf)
+
+    def _ycbcr_cuda(luma, chroma, output_size, mode="bilinear", subsampling="420", boxes=None, flips=None, sizes=None, offsets=None, fill=None,
+                    out_dtype=None, out_format="nchw", mean=None, std=None):
+        subs = subsampling.split(",") if "," in subsampling else subsampling
+        return resize_many_ycbcr(_ycbcr_tuples(luma, chroma), output_size, mode, subsampling=subs, boxes=_many_boxes(luma, boxes), flips=flips,
+                                 sizes=_many_pairs(luma, sizes, "sizes"), offsets=_many_pairs(luma, offsets, "offsets"),
+                                 fill=None if fill is None else list(fill), out_dtype=out_dtype, out_format=out_format, mean=mean, std=std)
+
+    lib.impl("resize_many_ycbcr", _ycbcr_cuda, "CUDA")
+    lib.impl("resize_many_ycbcr", _ycbcr_meta, "Meta")
 
     # the ragged Image.reduce: factors one int, one (fx, fy) or 2 N ints (x first); boxes 4 N ints, a full-image box standing for None
     lib.define("reduce_many(Tensor[] images, int[] factors, int[]? boxes=None) -> Tensor[]")

@@ -62,6 +62,11 @@ plain device copy of the output's bytes, the write floor:
 
 Both ways give the same elements.  No bar is set; what is required is two kernel launches whatever N, and that the numbers are written down.
 
+--ycbcr: resize_many_ycbcr on 64 camera-sized pictures held as 4:2:0 planes (1.5 B/px), one RandomResizedCrop box each -> 224 x 224
+bicubic, normalised bfloat16 NCHW out, planar and interleaved chroma, against (a) resize_many_to_float on the same pictures as interleaved
+RGB (3 B/px, no conversion) and (b) what a user does today: repeat_interleave of the chroma, a torch colour conversion to an interleaved
+uint8 RGB image per item, then (a).  Times, launch counts and the kernel-level split of (a) and of the new call.
+
 --maps: resize_many_maps (Pillow's "I;16" / "I" / "F" resize: double coefficients, double sums, the mode's store after each pass) on
 64 camera-sized uint16 maps, H in [1080, 3000], W in [1440, 4000], one RandomResizedCrop box each -> 224 x 224, bilinear and bicubic,
 half the items flipped.  No other GPU code produces these bits, so the contestants are the same call issued once per item (64 x 3
@@ -83,6 +88,7 @@ results into one tensor; (c) writes the batch.
   python tools/resize_many_bench.py --alpha > out.txt    # only Pillow's RGBA resize for a list (above); profiles/resize_many_alpha.txt
   python tools/resize_many_bench.py --nearest > out.txt  # only Pillow's NEAREST for a list (above); profiles/resize_many_nearest.txt
   python tools/resize_many_bench.py --maps > out.txt     # only Pillow's I;16 resize for a list (below); profiles/resize_many_maps.txt
+  python tools/resize_many_bench.py --ycbcr > out.txt    # only 4:2:0 planes to the batch (above); profiles/resize_many_ycbcr.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -583,6 +589,89 @@ def maps(args, torch, aa, timed):
               + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
 
 
+def ycbcr(args, torch, aa, timed):
+    """resize_many_ycbcr (4:2:0 planes in, planar and interleaved chroma) against two things that exist without it: (a) resize_many_to_float
+    on the same pictures as interleaved RGB, which reads twice the bytes and converts nothing, and (b) what a user does today: expand the
+    chroma, convert to an interleaved uint8 RGB image per item in torch, then (a)."""
+    rng = np.random.default_rng(SEED)
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)]
+    brng = np.random.default_rng(SEED + 1)
+    boxes = [random_resized_crop_box(brng, h, w) for h, w in shapes]
+    mean, std = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
+    kw = dict(boxes=boxes, out_dtype=torch.bfloat16, out_format="nchw", mean=mean, std=std)
+    rnd = lambda *s: torch.randint(0, 256, s, dtype=torch.uint8, device="cuda", generator=gen)  # noqa: E731
+    planar = [(rnd(h, w), rnd(-(-h // 2), -(-w // 2)), rnd(-(-h // 2), -(-w // 2))) for h, w in shapes]
+    inter = [(y, torch.stack([cb, cr], dim=-1).contiguous()) for y, cb, cr in planar]
+
+    def to_rgb(y, cb, cr):
+        """What a user writes today: nearest chroma expansion, the JFIF matrix in float, an interleaved uint8 image."""
+        h, w = y.shape
+        cbf = cb.repeat_interleave(2, 0).repeat_interleave(2, 1)[:h, :w].float() - 128.0
+        crf = cr.repeat_interleave(2, 0).repeat_interleave(2, 1)[:h, :w].float() - 128.0
+        yf = y.float()
+        rgb = torch.stack([yf + 1.402 * crf, yf - 0.34414 * cbf - 0.71414 * crf, yf + 1.772 * cbf], dim=-1)
+        return rgb.round().clamp(0, 255).to(torch.uint8).permute(2, 0, 1)
+
+    rgb = [to_rgb(*p) for p in planar]
+    contestants = {
+        "a: resize_many_to_float on interleaved RGB (3 B/px in)": lambda: aa.resize_many_to_float(rgb, list(OUT), "bicubic", **kw),
+        "b: expand + convert in torch per item, then (a)": lambda: aa.resize_many_to_float([to_rgb(*p) for p in planar], list(OUT), "bicubic", **kw),
+        "c: resize_many_ycbcr, planes (Y, Cb, Cr)": lambda: aa.resize_many_ycbcr(planar, list(OUT), "bicubic", subsampling="420", **kw),
+        "d: resize_many_ycbcr, interleaved (Y, CbCr)": lambda: aa.resize_many_ycbcr(inter, list(OUT), "bicubic", subsampling="420", **kw),
+    }
+    print(f"resize_many_bench --ycbcr: 4:2:0 planes to a normalised bfloat16 NCHW batch (seed {SEED}); library: {os.path.basename(_lib_path())}")
+    print(f"{N} pictures, H in [1080, 3000], W in [1440, 4000], one RandomResizedCrop box each -> {OUT}, bicubic, mean / std")
+    print(f"input bytes: planes {sum(y.numel() + cb.numel() + cr.numel() for y, cb, cr in planar) / 1e6:.1f} MB, "
+          f"interleaved RGB {sum(t.numel() for t in rgb) / 1e6:.1f} MB")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+    for fn in contestants.values():
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    c, d = list(contestants.values())[2:]
+    if args.trace:  # (under a profiler's kernel trace: the kernel-level split of (a), (c) and (d), the same number of calls each)
+        for fn in (list(contestants.values())[0], c, d):
+            for _ in range(args.trace):
+                fn()
+        torch.cuda.synchronize()
+        return
+    assert torch.equal(c().view(torch.int16), d().view(torch.int16)), "planar and interleaved chroma differ"
+    u_new = aa.resize_many_ycbcr(planar, list(OUT), "bicubic", subsampling="420", boxes=boxes).int()
+    u_old = aa.resize_many(rgb, list(OUT), "bicubic", boxes=boxes).int()
+    print(f"bytes of (c) against bytes of (a) (not promised equal: the roundings fall elsewhere, and (a)'s chroma was expanded by "
+          f"repetition): mean |difference| {(u_new - u_old).abs().float().mean().item():.3f}, largest {(u_new - u_old).abs().max().item()}")
+    times = {k: [] for k in contestants}
+    for _ in range(args.rounds):
+        for k, fn in contestants.items():
+            times[k].append(timed(fn))
+    stat = {}
+    for k, v in times.items():
+        stat[k] = (statistics.median(v), min(v), max(v))
+        launches = count_launches(torch, contestants[k])
+        print(f"  {k:56s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]   kernel launches per batch: "
+              f"{launches if launches is not None else 'not measured'}")
+    (ma, la, ha), (mb, _, _), (mc, lc, hc), (md, ld, hd) = stat.values()
+    for label, (m, lo, hi) in (("planes", (mc, lc, hc)), ("interleaved", (md, ld, hd))):
+        verdict = "faster than (a)" if hi < la else ("SLOWER THAN (a)" if lo > ha else ("slower than (a) by the medians, the ranges overlap" if m >= ma
+                                                                                          else "faster than (a) by the medians, the ranges overlap"))
+        print(f"  resize_many_ycbcr, {label}: {ma / m:.2f} x (a), {mb / m:.2f} x (b): {verdict}")
+    for name, fn, parts in (("a", list(contestants.values())[0], ("many_tables", "many_hpass", "many_vpass")),
+                            ("c", c, ("many_tables", "many_hpass", "ycc_vpass")), ("d", d, ("many_tables", "many_hpass", "ycc_vpass"))):
+        for part in parts:
+            kt = kernel_times(torch, fn, part, calls=12)
+            if kt:  # (interleaved chroma: two launches of the first two kernels per call, so the time is summed per call)
+                print(f"  ({name}) {part}: {len(kt) / 12:.0f} launch(es) per call, device time {sum(kt) / 12:8.1f} us per call "
+                      f"[single launches {min(kt):8.1f} .. {max(kt):8.1f}] over 12 calls")
+            else:
+                print(f"  ({name}) {part}: device time not measured")
+    for label, images in (("planes", planar), ("interleaved", inter)):
+        counts = {n: count_launches(torch, lambda: aa.resize_many_ycbcr(images[:n], list(OUT), "bicubic", subsampling="420",
+                                                                         **{**kw, "boxes": boxes[:n]})) for n in (1, 8, N)}
+        print(f"  kernel launches of one resize_many_ycbcr call, {label}, by N (expected {3 if label == 'planes' else 5}, whatever N): "
+              + ", ".join(f"N = {n}: {v if v is not None else 'not measured'}" for n, v in counts.items()))
+
+
 def kernel_times(torch, fn, part, calls=12):
     """Device durations in us of the kernels whose name holds `part`, over `calls` runs of fn(), from torch's profiler; [] where it
     records no device activity."""
@@ -655,6 +744,8 @@ def main():
     ap.add_argument("--alpha", action="store_true", help="only Pillow's RGBA resize for a list: the loop with alpha=True against resize_many(alpha=True)")
     ap.add_argument("--nearest", action="store_true", help="only Pillow's NEAREST for label maps: resize_many_nearest against the per-image torch loop")
     ap.add_argument("--maps", action="store_true", help="only Pillow's I;16 resize for measured maps: resize_many_maps against the call per item")
+    ap.add_argument("--ycbcr", action="store_true", help="only resize_many_ycbcr (4:2:0 planes in) against resize_many_to_float on interleaved RGB "
+                    "and against the torch conversion a user writes today; with --trace K: K calls of the planar form for a kernel trace")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -695,6 +786,9 @@ def main():
     def fresh_boxes():
         return [random_resized_crop_box(brng, h, w) for h, w in shapes]
 
+    if args.trace and args.ycbcr:
+        ycbcr(args, torch, aa, None)
+        return
     if args.trace:
         for _ in range(WARM_CALLS + args.trace):
             if args.trace_patches:
@@ -746,6 +840,9 @@ def main():
         return
     if args.maps:
         maps(args, torch, aa, timed)
+        return
+    if args.ycbcr:
+        ycbcr(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
