@@ -230,36 +230,28 @@ YCC_VROWS, YCC_VCOLS = 4, 256  # canvas rows and columns per work unit of the YC
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
 
-def many_desc_view(buf, n: int):
-    """(header, items, prefix) of a descriptor block held in a ctypes buffer: [header][n items][int64 prefix[n + 1]]."""
-    hd = ManyHeader.from_buffer(buf, 0)
-    items = (ManyItem * n).from_buffer(buf, ctypes.sizeof(ManyHeader))
-    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(ManyHeader) + n * ctypes.sizeof(ManyItem))
+def desc_view(buf, n: int, Header, Item):
+    """(header, items, prefix) of a planner's block held in a ctypes buffer, [Header][n Items][int64 prefix[n + 1]]: the four below."""
+    hd = Header.from_buffer(buf, 0)
+    items = (Item * n).from_buffer(buf, ctypes.sizeof(Header))
+    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(Header) + n * ctypes.sizeof(Item))
     return hd, items, prefix
+
+
+def many_desc_view(buf, n: int):  # (any of aa_many_plan's blocks: what follows the prefix sums is many_placed_view's, many_patch_view's)
+    return desc_view(buf, n, ManyHeader, ManyItem)
 
 
 def reduce_many_desc_view(buf, n: int):
-    """(header, items, prefix) of a ragged reduce's block held in a ctypes buffer: [header][n items][int64 prefix[n + 1]]."""
-    hd = ReduceManyHeader.from_buffer(buf, 0)
-    items = (ReduceManyItem * n).from_buffer(buf, ctypes.sizeof(ReduceManyHeader))
-    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(ReduceManyHeader) + n * ctypes.sizeof(ReduceManyItem))
-    return hd, items, prefix
+    return desc_view(buf, n, ReduceManyHeader, ReduceManyItem)
 
 
 def near_desc_view(buf, n: int):
-    """(header, items, prefix) of a NEAREST plan's block held in a ctypes buffer: [header][n items][int64 unit_prefix[n + 1]]."""
-    hd = NearHeader.from_buffer(buf, 0)
-    items = (NearItem * n).from_buffer(buf, ctypes.sizeof(NearHeader))
-    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(NearHeader) + n * ctypes.sizeof(NearItem))
-    return hd, items, prefix
+    return desc_view(buf, n, NearHeader, NearItem)
 
 
 def maps_desc_view(buf, n: int):
-    """(header, items, prefix) of a maps plan's block held in a ctypes buffer: [header][n items][int64 hunit_prefix[n + 1]]."""
-    hd = MapsHeader.from_buffer(buf, 0)
-    items = (MapsItem * n).from_buffer(buf, ctypes.sizeof(MapsHeader))
-    prefix = (ctypes.c_int64 * (n + 1)).from_buffer(buf, ctypes.sizeof(MapsHeader) + n * ctypes.sizeof(MapsItem))
-    return hd, items, prefix
+    return desc_view(buf, n, MapsHeader, MapsItem)
 
 
 def many_placed_view(buf, n: int):

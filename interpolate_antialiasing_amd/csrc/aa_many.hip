@@ -16,11 +16,13 @@
 // bytes, and the vertical passes convert every output pixel back with its own resampled alpha.  Same plan, same workspace, same launches.
 // The host planner (aa_many_plan_host) computes every hull, ksize and offset with the same double arithmetic the table kernel uses, so
 // nothing comes back from the device: no header read-back, no atomicMax, no synchronisation, no allocation.
+// Shared with the other ragged calls: aa_many_dev.h (the item of a work unit, the table view, the element types), aa_many_host.h (checks).
 
 #include <math.h>
 #include <string.h>
 
 #include "aa_alpha.h"
+#include "aa_many_dev.h"
 #include "aa_many_host.h"
 #include "aa_pil_coeffs.h"
 
@@ -63,8 +65,7 @@ __global__ void __launch_bounds__(256) many_tables(const AAManyItem *items, cons
   int32_t *kk = xsize_p + out + (size_t)i * ksize;
   // (no box: the hull is the whole axis, origin 0, and in / out is the scale — aa_table_build's table)
   // (PL, no box: in1 is the whole axis as a double, so in1 / v is the plain call's in / out)
-  const PilWindow wd = PL ? pil_window_at(v0 + i, filter, (bx.on ? (double)(float)(bx.in1 - bx.in0) : bx.in1) / (double)v, bx.in0, bx.origin,
-                                          bx.origin + hull)
+  const PilWindow wd = PL ? pil_window_at(v0 + i, filter, aa_pil_scale(bx.on, bx.in0, bx.in1, bx.in1, v), bx.in0, bx.origin, bx.origin + hull)
                           : pil_window(i, filter, hull, out, bx);
   xmin_p[i] = wd.xmin - bx.origin;
   xsize_p[i] = wd.xsize;
@@ -120,11 +121,7 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
   static_assert(!AL || E == 1 || E == 2 || E == 4, "alpha is the last of 2 or 4 channels");
   __shared__ uint32_t seg[kChunkDwords];
   const int64_t unit = blockIdx.x;
-  int lo = 0, hi = n;  // the item whose units hold `unit`: prefix[lo] <= unit < prefix[lo + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (prefix[mid] <= unit) lo = mid; else hi = mid;
-  }
+  const int lo = aa_unit_item(prefix, n, unit);
   const AAManyItem &it = items[lo];
   int64_t u = unit - prefix[lo];
   int lead = 0;
@@ -144,12 +141,9 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
   if (plane >= planes) return;  // (never: the grid is prefix[n]; uniform per workgroup)
   const int x0 = strip * AA_MANY_STRIP;
   const int x1 = x0 + AA_MANY_STRIP < oW ? x0 + AA_MANY_STRIP : oW;
-  const int32_t *xmin_p = (const int32_t *)(ws + it.tab_w);
-  const int32_t *xsize_p = xmin_p + oW;
-  const int32_t *w_all = xsize_p + oW;
-  const int ksize = it.ksize_w;
+  const AATab<int32_t> tab = aa_tab<int32_t>(ws + it.tab_w, oW, it.ksize_w);
   // window starts and ends do not decrease with the output index: the strip's windows cover [first start, last end)
-  int seg0 = xmin_p[x0], seg1 = xmin_p[x1 - 1] + xsize_p[x1 - 1];
+  int seg0 = tab.xmin[x0], seg1 = tab.xmin[x1 - 1] + tab.xsize[x1 - 1];
   if (seg0 < 0) seg0 = 0;
   if (seg1 > hull_w) seg1 = hull_w;
   const uint8_t *rowp = it.src + (int64_t)plane * it.plane_stride + (int64_t)(it.oy + row) * it.row_stride + (int64_t)it.ox * E;
@@ -161,12 +155,11 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * E) many_hpass(const AAManyItem
   const int x = x0 + j / E, c = j % E;
   const bool active = x < x1;
   int mx = 0, ms = 0;
-  const int32_t *wp = w_all;
+  const int32_t *wp = tab.w;
   if (active) {
-    mx = xmin_p[x];
-    ms = xsize_p[x];
-    if (ms > ksize) ms = ksize;
-    wp = w_all + (size_t)x * ksize;
+    mx = tab.xmin[x];
+    ms = tab.taps(x);
+    wp = tab.row(x);
   }
   int32_t ss = 1 << 21;
   constexpr int kChunkCols = (kChunkBytes - 4) / E;
@@ -353,19 +346,7 @@ __global__ void __launch_bounds__(256) many_vpass(const AAManyItem *items, const
 // output's address against its element), so rows at any element alignment, flips and both output layouts are one code path.  From
 // interleaved pixels to planes a store instruction of a wave then covers E planes with short runs; a form that staged the workgroup's
 // results in LDS and stored aligned 8- / 16-byte pieces of one plane row per lane measured 5 % slower on that case.
-struct ManyConvert { int normalize; float mean[4], std[4]; };
-struct f16_t { _Float16 v; };
-struct bf16_t { uint16_t v; };
-template <typename T> __device__ inline T to_elem(float a);
-template <> __device__ inline float to_elem<float>(float a) { return a; }
-template <> __device__ inline f16_t to_elem<f16_t>(float a) { f16_t r; r.v = (_Float16)a; return r; }  // round to nearest even
-template <> __device__ inline bf16_t to_elem<bf16_t>(float a) {                                        // round to nearest even
-  const unsigned u = __float_as_uint(a);
-  bf16_t r;
-  if ((u & 0x7fffffffu) > 0x7f800000u) r.v = (uint16_t)((u >> 16) | 0x0040u);
-  else r.v = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  return r;
-}
+struct ManyConvert { int normalize; float mean[4], std[4]; };  // (the element types and to_elem: aa_many_dev.h)
 __device__ inline float pick4(const float (&a)[4], int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : (c == 2 ? a[2] : a[3])); }
 
 template <int E> constexpr int kVLanes = E == 3 ? 192 : 256;   // lanes of a workgroup: 4 bytes each, a whole number of pixels together
@@ -438,11 +419,7 @@ __global__ void __launch_bounds__(kVLanes<E>) many_vpass_patches(const AAManyIte
   constexpr int PX = kVPixels<E>;
   static_assert(PX * E == kVLanes<E> * 4 && PX == aa_many_vpixels(E), "a strip is four bytes per lane, and the planner counts the same strips");
   const int64_t unit = blockIdx.x;
-  int lo = 0, hi = n;  // the item whose units hold `unit`: vprefix[lo] <= unit < vprefix[lo + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (vprefix[mid] <= unit) lo = mid; else hi = mid;
-  }
+  const int lo = aa_unit_item(vprefix, n, unit);
   const AAManyItem &it = items[lo];
   const AAManyPlace &pl = places[lo];
   int64_t u = unit - vprefix[lo];
@@ -493,10 +470,7 @@ __global__ void __launch_bounds__(kVLanes<E>) many_vpass_patches(const AAManyIte
 }  // namespace
 
 // ---- host: the planner -------------------------------------------------------------------------------------------------------------------
-size_t aa_many_desc_size(int64_t n) {
-  if (n < 0) return 0;
-  return sizeof(AAManyHeader) + (size_t)n * sizeof(AAManyItem) + ((size_t)n + 1) * sizeof(int64_t);
-}
+size_t aa_many_desc_size(int64_t n) { return aa_desc_size(sizeof(AAManyHeader), sizeof(AAManyItem), n); }
 
 size_t aa_many_desc_size_placed(int64_t n) {
   if (n < 0) return 0;
@@ -525,15 +499,10 @@ static int many_plan(int filter, int layout, int64_t n, int64_t C, int64_t oH, i
                      const uint8_t *fill, bool own_canvas, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
   if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
-  const int64_t kMax = kAAManyMax;
-  if (n < 0 || n > kMax || C < 1 || C > 4 || oH <= 0 || oW <= 0 || oH > kMax || oW > kMax) return AA_ERR_BAD_SHAPE;
-  if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
+  const int rc0 = aa_many_check_canvas(n, kAAManyMax, C >= 1 && C <= 4, oH, oW, desc_host, workspace_bytes, images, places);
+  if (rc0 != AA_OK) return rc0;
   bool placed = own_canvas;  // every item the whole canvas at offset 0 is the plain plan: nothing of the canvas is left to the fill
-  for (int64_t i = 0; places && i < n; i++) {
-    const aa_many_place &p = places[i];
-    if (!aa_many_place_ok(p)) return AA_ERR_BAD_SHAPE;
-    placed = placed || p.vH != oH || p.vW != oW || p.oy != 0 || p.ox != 0;
-  }
+  for (int64_t i = 0; places && i < n; i++) placed = placed || places[i].vH != oH || places[i].vW != oW || places[i].oy != 0 || places[i].ox != 0;
   if (desc_bytes < (placed ? aa_many_desc_size_placed(n) : aa_many_desc_size(n))) return AA_ERR_WORKSPACE;
   const int E = layout == AA_NHWC ? (int)C : 1;
   const int64_t planes = layout == AA_NHWC ? 1 : C;
@@ -696,11 +665,10 @@ struct ManyViews {
   const AAManyPlace *places;
 };
 static ManyViews many_views(const AAManyHeader *hd, const void *desc_dev) {
-  const AAManyItem *items = (const AAManyItem *)((const char *)desc_dev + sizeof(AAManyHeader));
-  const int64_t *prefix = (const int64_t *)(items + hd->n);
+  const AADescView<AAManyItem> v = aa_desc_view<AAManyHeader, AAManyItem>(desc_dev, hd->n);
   const bool nhwc = hd->layout == AA_NHWC;
-  return {nhwc ? hd->C : 1, nhwc ? 1 : hd->C, items, prefix,
-          (hd->kind & AA_MANY_PLAN_PLACED) ? (const AAManyPlace *)(prefix + hd->n + 1) : nullptr};
+  return {nhwc ? hd->C : 1, nhwc ? 1 : hd->C, v.items, v.prefix,
+          (hd->kind & AA_MANY_PLAN_PLACED) ? (const AAManyPlace *)(v.prefix + hd->n + 1) : nullptr};
 }
 
 template <int E, bool PL, bool AL>
@@ -877,11 +845,8 @@ int aa_launch_many_patches(const void *desc_host, const void *desc_dev, void *ou
   const int64_t patch_plan = AA_MANY_PLAN_PLACED | AA_MANY_PLAN_PATCHES;  // (and no AA_MANY_PLAN_ALPHA)
   if (hd->magic != AA_MANY_MAGIC || (hd->kind & (patch_plan | AA_MANY_PLAN_ALPHA)) != patch_plan || hd->n < 0 || hd->C < 1 || hd->C > 4) return AA_ERR_BAD_SHAPE;
   const int64_t n = hd->n, C = hd->C;
-  if (n == 0) return AA_OK;
-  if (!desc_dev || !out_dev || !workspace_dev) return AA_ERR_NULL;
-  const int rc = many_check(hd, desc_dev, n, C, hd->oH, hd->oW, hd->layout, workspace_dev, workspace_bytes);
-  if (rc != AA_OK) return rc;
-  if ((uintptr_t)out_dev & (out_elem == AA_F32 ? 3 : 1)) return AA_ERR_BAD_SHAPE;
+  const int rc = aa_many_check_launch(n, desc_dev, out_dev, workspace_dev, workspace_bytes, hd->ws_bytes, out_elem == AA_F32 ? 4 : 2);
+  if (rc != AA_OK || n == 0) return rc;
   const int64_t *tail_host = patch_tail(desc_host, n);
   const AAManyPatchInfo *info = (const AAManyPatchInfo *)(tail_host + 2 * (n + 1));
   const int64_t vunits = tail_host[n];

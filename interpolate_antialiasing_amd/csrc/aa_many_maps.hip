@@ -17,10 +17,12 @@
 // offset; a skipped pass is never run as an identity filter (Lanczos at scale 1 has non-zero off-centre taps).  The planner decides that
 // per item on the host with the table kernel's own window arithmetic, so nothing comes back from the device.
 // Built with -ffp-contract=off like every user of aa_pil_coeffs.h; the accumulation must stay a multiply and an add.
+// Shared with the other ragged calls: aa_many_dev.h (the item of a work unit, the table view and hull clamp), aa_many_host.h (checks, scale).
 
 #include <math.h>
 #include <string.h>
 
+#include "aa_many_dev.h"
 #include "aa_many_host.h"
 #include "aa_many_maps.h"
 #include "aa_pil_coeffs.h"
@@ -132,11 +134,7 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * kHWaves) maps_hpass(const AAMa
   __shared__ __attribute__((aligned(16))) uint8_t segs[kHWaves][kHSegBytes];
   constexpr int kSegElems = kHSegBytes / (int)sizeof(T);
   const int64_t unit = blockIdx.x;
-  int lo = 0, hi = n;  // the item whose units hold `unit`: prefix[lo] <= unit < prefix[lo + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (prefix[mid] <= unit) lo = mid; else hi = mid;
-  }
+  const int lo = aa_unit_item(prefix, n, unit);
   const AAMapsItem &it = items[lo];
   if (!(it.flags & AA_MAPS_ITEM_HPASS)) return;  // (never: such an item has no unit; uniform per workgroup)
   const int64_t u = unit - prefix[lo];
@@ -147,23 +145,18 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * kHWaves) maps_hpass(const AAMa
   const int lane = (int)threadIdx.x & (AA_MANY_STRIP - 1), wave = (int)threadIdx.x / AA_MANY_STRIP;
   T *seg = (T *)segs[wave];
   const int x = x0 + lane;
-  const char *tab = ws + it.tab_w;
-  const int32_t *xmin_p = (const int32_t *)tab;
-  const int32_t *xsize_p = xmin_p + mw;
-  const int ksize = it.ksize_w;
-  const double *w_all = (const double *)(tab + aa_maps_table_w_off(mw));
+  const AATab<double> tab = aa_tab<double>(ws + it.tab_w, mw, it.ksize_w);
+  const int ksize = tab.ksize;
   int mx = 0, ms = 0;
   if (x < mw) {
-    mx = xmin_p[x];
-    ms = xsize_p[x];
-    if (ms > ksize) ms = ksize;
-    if (mx < 0) mx = 0;
-    if (mx + ms > it.hull_w) ms = it.hull_w - mx;  // (never: the hull is the union of these windows)
+    mx = tab.xmin[x];
+    ms = tab.taps(x);
+    aa_clamp_to_hull(mx, ms, it.hull_w);  // (the second clamp never: the hull is the union of these windows)
   }
   // the strip's first and last window starts (starts do not decrease with the output index): what the strip reads of a row for the taps
   // [c0, c0 + kHTaps) is [first + c0, last + c0 + kHTaps), clipped to the hull
   const int xl = x0 + AA_MANY_STRIP - 1 < mw ? x0 + AA_MANY_STRIP - 1 : mw - 1;
-  int mxf = xmin_p[x0], mxl = xmin_p[xl];
+  int mxf = tab.xmin[x0], mxl = tab.xmin[xl];
   if (mxf < 0) mxf = 0;
   if (mxl < 0) mxl = 0;
   double ss[kHPer];
@@ -173,7 +166,7 @@ __global__ void __launch_bounds__(AA_MANY_STRIP * kHWaves) maps_hpass(const AAMa
     __syncthreads();  // (the previous chunk has been consumed)
     for (int idx = (int)threadIdx.x; idx < AA_MANY_STRIP * kHTaps; idx += AA_MANY_STRIP * kHWaves) {
       const int xx = idx / kHTaps, k = idx % kHTaps;
-      wl[xx][k] = (x0 + xx < mw && c0 + k < ksize) ? w_all[(size_t)(x0 + xx) * ksize + c0 + k] : 0.0;
+      wl[xx][k] = (x0 + xx < mw && c0 + k < ksize) ? tab.w[(size_t)(x0 + xx) * ksize + c0 + k] : 0.0;
     }
     __syncthreads();
     const int s0 = mxf + c0;
@@ -241,16 +234,10 @@ __global__ void __launch_bounds__(AA_MAPS_VCOLS) maps_vpass(const AAMapsItem *it
     const gbytes base = hp ? as_global(ws) + it.inter + (int64_t)x * (int64_t)sizeof(T)
                            : as_global(it.src) + (int64_t)it.oy * it.row_stride + (int64_t)(it.ox + x) * (int64_t)sizeof(T);
     if (it.flags & AA_MAPS_ITEM_VPASS) {
-      const char *tab = ws + it.tab_h;
-      const int32_t *xmin_p = (const int32_t *)tab;
-      const int32_t *xsize_p = xmin_p + it.mh;
-      const int ksize = it.ksize_h;
-      const double *k = (const double *)(tab + aa_maps_table_w_off(it.mh)) + (size_t)ty * ksize;
-      int r0 = xmin_p[ty], nr = xsize_p[ty];
-      if (nr > ksize) nr = ksize;
-      if (r0 < 0) r0 = 0;
-      if (r0 + nr > it.hull_h) nr = it.hull_h - r0;  // (never: the hull is the union of these windows)
-      v = store_rule<T>(window_sum<T>(base + (int64_t)r0 * pitch, pitch, k, nr), clamp);
+      const AATab<double> tab = aa_tab<double>(ws + it.tab_h, it.mh, it.ksize_h);
+      int r0 = tab.xmin[ty], nr = tab.taps(ty);
+      aa_clamp_to_hull(r0, nr, it.hull_h);  // (the second clamp never: the hull is the union of these windows)
+      v = store_rule<T>(window_sum<T>(base + (int64_t)r0 * pitch, pitch, tab.row(ty), nr), clamp);
     } else {  // Pillow's copy of this axis: hull row ty is result row v0h + ty
       v = load_at<T>(base + (int64_t)ty * pitch);
     }
@@ -261,10 +248,7 @@ __global__ void __launch_bounds__(AA_MAPS_VCOLS) maps_vpass(const AAMapsItem *it
 }  // namespace
 
 // ---- host: the planner -------------------------------------------------------------------------------------------------------------------
-size_t aa_maps_desc_size(int64_t n) {
-  if (n < 0) return 0;
-  return sizeof(AAMapsHeader) + (size_t)n * sizeof(AAMapsItem) + ((size_t)n + 1) * sizeof(int64_t);
-}
+size_t aa_maps_desc_size(int64_t n) { return aa_desc_size(sizeof(AAMapsHeader), sizeof(AAMapsItem), n); }
 
 // One axis of one item.  run: the hull [o, o + hull) of the windows of results [v0, v0 + m) (the first window's start and the last one's
 // end, each clipped to the axis: boxmath.axis_hull, with the window the table kernel evaluates) and Pillow's ksize.  Not run: the m
@@ -294,12 +278,8 @@ int aa_maps_plan_host(int filter, int elem, int64_t n, int64_t oH, int64_t oW, c
   if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
   if (elem != AA_MAPS_U16 && elem != AA_MAPS_I32 && elem != AA_MAPS_F32) return AA_ERR_BAD_DTYPE;
   if (overflow != AA_MAPS_OVERFLOW_PILLOW && overflow != AA_MAPS_OVERFLOW_CLAMP) return AA_ERR_BAD_SHAPE;
-  const int64_t kMax = kAAManyMax;
-  if (n < 0 || n > kMax || oH <= 0 || oW <= 0 || oH > kMax || oW > kMax) return AA_ERR_BAD_SHAPE;
-  if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
-  for (int64_t i = 0; places && i < n; i++) {
-    if (!aa_many_place_ok(places[i])) return AA_ERR_BAD_SHAPE;
-  }
+  const int rc0 = aa_many_check_canvas(n, kAAManyMax, true, oH, oW, desc_host, workspace_bytes, images, places);
+  if (rc0 != AA_OK) return rc0;
   // the fill as the element holds it: an integer of the type's range, or a finite float, written as (float)fill
   uint32_t fill_bits = 0;
   if (elem == AA_MAPS_F32) {
@@ -340,9 +320,8 @@ int aa_maps_plan_host(int filter, int elem, int64_t n, int64_t oH, int64_t oW, c
     it.row_stride = im.H > 1 ? im.stride_row : 0;
     it.in_h = (int32_t)im.H; it.in_w = (int32_t)im.W;
     it.in0_h = bx.y0; it.in0_w = bx.x0;
-    // the scale: Pillow's C takes the box as floats, takes their FLOAT difference, and only then divides in double
-    it.scale_h = (bx.on ? (double)(float)(bx.y1 - bx.y0) : H) / (double)pl.vh;
-    it.scale_w = (bx.on ? (double)(float)(bx.x1 - bx.x0) : W) / (double)pl.vw;
+    it.scale_h = aa_pil_scale(bx.on, bx.y0, bx.y1, H, pl.vh);
+    it.scale_w = aa_pil_scale(bx.on, bx.x0, bx.x1, W, pl.vw);
     it.vh = pl.vh; it.vw = pl.vw; it.v0h = pl.v0h; it.v0w = pl.v0w;
     it.mh = pl.mh; it.mw = pl.mw; it.dy = pl.dy; it.dx = pl.dx;
     it.flags = im.flags & AA_MAPS_ITEM_FLIP;
@@ -401,21 +380,18 @@ int aa_launch_many_maps(const void *desc_host, const void *desc_dev, void *out_d
   if (hd->elem != AA_MAPS_U16 && hd->elem != AA_MAPS_I32 && hd->elem != AA_MAPS_F32) return AA_ERR_BAD_SHAPE;
   if (!aa_filter_valid(hd->filter) || hd->n < 0 || hd->oH <= 0 || hd->oW <= 0) return AA_ERR_BAD_SHAPE;
   const int64_t n = hd->n;
-  if (n == 0) return AA_OK;
-  if (!desc_dev || !out_dev || !workspace_dev) return AA_ERR_NULL;
-  if (workspace_bytes < (size_t)hd->ws_bytes) return AA_ERR_WORKSPACE;
-  if (((uintptr_t)workspace_dev & 15) || ((uintptr_t)desc_dev & 7) || ((uintptr_t)out_dev % aa_maps_elem_bytes(hd->elem))) return AA_ERR_BAD_SHAPE;
+  const int rc = aa_many_check_launch(n, desc_dev, out_dev, workspace_dev, workspace_bytes, hd->ws_bytes, (size_t)aa_maps_elem_bytes(hd->elem));
+  if (rc != AA_OK || n == 0) return rc;
   const int64_t vstrips = ((int64_t)hd->oW + AA_MAPS_VCOLS - 1) / AA_MAPS_VCOLS;
   if (n * hd->oH * vstrips > INT32_MAX || hd->hunits < 0 || hd->hunits > INT32_MAX) return AA_ERR_BAD_SHAPE;
-  const AAMapsItem *items = (const AAMapsItem *)((const char *)desc_dev + sizeof(AAMapsHeader));
-  const int64_t *prefix = (const int64_t *)(items + n);
+  const AADescView<AAMapsItem> v = aa_desc_view<AAMapsHeader, AAMapsItem>(desc_dev, n);
   char *ws = (char *)workspace_dev;
   const int64_t tthreads = n * ((int64_t)hd->oH + hd->oW);
-  hipLaunchKernelGGL(maps_tables, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, items, ws, n, (int)hd->oH, (int)hd->oW, hd->filter);
+  hipLaunchKernelGGL(maps_tables, dim3((unsigned)((tthreads + 255) / 256)), dim3(256), 0, stream, v.items, ws, n, (int)hd->oH, (int)hd->oW, hd->filter);
   switch (hd->elem) {
-    case AA_MAPS_U16: launch_passes<uint16_t>(hd, items, prefix, ws, out_dev, (int)vstrips, stream); break;
-    case AA_MAPS_I32: launch_passes<int32_t>(hd, items, prefix, ws, out_dev, (int)vstrips, stream); break;
-    default: launch_passes<float>(hd, items, prefix, ws, out_dev, (int)vstrips, stream); break;
+    case AA_MAPS_U16: launch_passes<uint16_t>(hd, v.items, v.prefix, ws, out_dev, (int)vstrips, stream); break;
+    case AA_MAPS_I32: launch_passes<int32_t>(hd, v.items, v.prefix, ws, out_dev, (int)vstrips, stream); break;
+    default: launch_passes<float>(hd, v.items, v.prefix, ws, out_dev, (int)vstrips, stream); break;
   }
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;

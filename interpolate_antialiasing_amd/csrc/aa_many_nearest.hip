@@ -167,32 +167,24 @@ __global__ void __launch_bounds__(256) near_gather(const AANearItem *items, cons
 }  // namespace
 
 // ---- host: the planner -------------------------------------------------------------------------------------------------------------------
-size_t aa_near_desc_size(int64_t n) {
-  if (n < 0) return 0;
-  return sizeof(AANearHeader) + (size_t)n * sizeof(AANearItem) + ((size_t)n + 1) * sizeof(int64_t);
-}
+size_t aa_near_desc_size(int64_t n) { return aa_desc_size(sizeof(AANearHeader), sizeof(AANearItem), n); }
 
-// Pillow's two doubles of an axis: the box as floats, their FLOAT difference, then a double division; the first centre (closed: b0 itself).
+// Pillow's two doubles of an axis: the step, aa_pil_scale of the box (float32 values already, and NEAREST takes their float difference
+// with or without a box); the first centre (closed: b0 itself).
 static void near_axis(double b0, double b1, int64_t out_size, bool closed, double *a, double *xo0) {
-  const float f0 = (float)b0, f1 = (float)b1;
-  const float d = f1 - f0;
-  const double step = (double)d / (double)out_size;
+  const double step = aa_pil_scale(1, b0, b1, 0.0, out_size);
   const double half = step * 0.5;
   *a = step;
-  *xo0 = closed ? (double)f0 : (double)f0 + half;
+  *xo0 = closed ? b0 : b0 + half;
 }
 
 int aa_near_plan_host(int layout, int elem_bytes, int64_t n, int64_t C, int64_t oH, int64_t oW, const aa_many_image *images,
                       const aa_many_place *places, const int32_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) return AA_ERR_BAD_DTYPE;
-  const int64_t kMax = kAAManyMax;
-  if (n < 0 || n > kMax || C < 1 || C > 4 || oH <= 0 || oW <= 0 || oH > kMax || oW > kMax) return AA_ERR_BAD_SHAPE;
-  if (elem_bytes > 1 && C != 1) return AA_ERR_BAD_SHAPE;  // (2- and 4-byte elements are single-channel id maps)
-  if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
-  for (int64_t i = 0; places && i < n; i++) {
-    if (!aa_many_place_ok(places[i])) return AA_ERR_BAD_SHAPE;
-  }
+  // (2- and 4-byte elements are single-channel id maps)
+  const int rc0 = aa_many_check_canvas(n, kAAManyMax, C >= 1 && C <= 4 && (elem_bytes == 1 || C == 1), oH, oW, desc_host, workspace_bytes, images, places);
+  if (rc0 != AA_OK) return rc0;
   for (int c = 0; fill && c < C; c++) {  // what the element holds, signed or unsigned
     const int64_t lo = elem_bytes == 4 ? INT32_MIN : -((int64_t)1 << (8 * elem_bytes - 1)), hi = elem_bytes == 4 ? INT32_MAX : ((int64_t)1 << (8 * elem_bytes)) - 1;
     if (fill[c] < lo || fill[c] > hi) return AA_ERR_BAD_SHAPE;
@@ -272,11 +264,9 @@ int aa_launch_many_nearest(const void *desc_host, const void *desc_dev, void *ou
   if (EB != 1 && EB != 2 && EB != 4) return AA_ERR_BAD_SHAPE;
   if (out_elem_bytes != EB && out_elem_bytes != 8) return AA_ERR_BAD_DTYPE;
   if (out_elem_bytes == 8 && hd->C != 1) return AA_ERR_BAD_DTYPE;  // (the int64 form is for single-channel maps)
-  if (n == 0) return AA_OK;
-  if (!desc_dev || !out_dev || !workspace_dev) return AA_ERR_NULL;
-  if (workspace_bytes < (size_t)hd->ws_bytes) return AA_ERR_WORKSPACE;
-  if (((uintptr_t)workspace_dev & 15) || ((uintptr_t)desc_dev & 7) || ((uintptr_t)out_dev % out_elem_bytes)) return AA_ERR_BAD_SHAPE;
-  const AANearItem *items = (const AANearItem *)((const char *)desc_dev + sizeof(AANearHeader));
+  const int rc = aa_many_check_launch(n, desc_dev, out_dev, workspace_dev, workspace_bytes, hd->ws_bytes, (size_t)out_elem_bytes);
+  if (rc != AA_OK || n == 0) return rc;
+  const AANearItem *items = aa_desc_view<AANearHeader, AANearItem>(desc_dev, n).items;
   const int E = hd->layout == AA_NHWC ? hd->C : 1;
   const int planes = hd->layout == AA_NHWC ? 1 : hd->C;
   const int64_t PB = (int64_t)aa_near_units_per_pixel(E, EB) * EB;

@@ -15,31 +15,20 @@
 
 #include <vector>
 
+#include "aa_many_dev.h"
 #include "aa_many_host.h"
 #include "aa_many_ycbcr.h"
 #include "aa_ycbcr.h"
 
 namespace {
 
-// many_vpass_float's conversion of a byte, (T)(((float)byte - mean[c]) / std[c]): its to_elem, word for word (aa_many.hip keeps its own
-// in its anonymous namespace, like the other kernel files).
+// many_vpass_float's conversion of a byte, (T)(((float)byte - mean[c]) / std[c]), with its to_elem (aa_many_dev.h).
 struct YccConvert { int normalize; float mean[3], std[3]; };
-struct f16_t { _Float16 v; };
-struct bf16_t { uint16_t v; };
-template <typename T> __device__ inline T to_elem(float a);
-template <> __device__ inline float to_elem<float>(float a) { return a; }
-template <> __device__ inline f16_t to_elem<f16_t>(float a) { f16_t r; r.v = (_Float16)a; return r; }  // round to nearest even
-template <> __device__ inline bf16_t to_elem<bf16_t>(float a) {                                        // round to nearest even
-  const unsigned u = __float_as_uint(a);
-  bf16_t r;
-  if ((u & 0x7fffffffu) > 0x7f800000u) r.v = (uint16_t)((u >> 16) | 0x0040u);
-  else r.v = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  return r;
-}
 
 // The clipped bytes of NDW consecutive dwords from byte `at` of the intermediate's rows, down the window of entry t of an item's vertical
-// table (`out` entries): many_vpass's sums.  ok[d]: dword d lies inside the row; one that does not is not read and counts as 0 (of four
-// interleaved pairs the first two may lie before the item's first column, the last two beyond its last).
+// table (`out` entries): many_vpass's sums (vtap_sums of aa_many.hip, for NDW dwords with a validity mask; one definition for both
+// changes the registers of one file's kernels or the other's, profiles/ragged_shared_refactor.txt).  ok[d]: dword d lies inside the
+// row; one that does not counts as 0 (of four pairs the first two may lie before the item's first column, the last two beyond its last).
 template <int NDW>
 __device__ inline void vwalk(const AAManyItem &it, const char *ws, int out, int t, int64_t pitch, int64_t at, const bool (&ok)[NDW],
                              uint32_t (&res)[NDW]) {
@@ -69,8 +58,6 @@ __device__ inline void vwalk(const AAManyItem &it, const char *ws, int out, int 
 #pragma unroll
   for (int d = 0; d < NDW; d++) res[d] = pack4_clip8(s[4 * d], s[4 * d + 1], s[4 * d + 2], s[4 * d + 3]);
 }
-
-__device__ inline uint32_t byte_of(uint32_t w, int q) { return (w >> (8 * q)) & 255u; }
 
 // T: uint8_t, float, f16_t, bf16_t.  IL: plan B holds interleaved chroma pairs.  NHWC: the output's layout.
 template <typename T, bool IL, bool NHWC>
@@ -208,9 +195,9 @@ void launch_vpass_t(bool il, bool nhwc, const YccArgs &a) {
   else nhwc ? launch_vpass<T, false, true>(a) : launch_vpass<T, false, false>(a);
 }
 
-const AAManyItem *plan_items(const void *plan) { return (const AAManyItem *)((const char *)plan + sizeof(AAManyHeader)); }
+const AAManyItem *plan_items(const void *plan) { return aa_desc_view<AAManyHeader, AAManyItem>(plan, 0).items; }
 // (a placed plan: the placement records follow the prefix sums)
-const AAManyPlace *plan_places(const void *plan, int64_t n) { return (const AAManyPlace *)((const int64_t *)(plan_items(plan) + n) + n + 1); }
+const AAManyPlace *plan_places(const void *plan, int64_t n) { return (const AAManyPlace *)(aa_desc_view<AAManyHeader, AAManyItem>(plan, n).prefix + n + 1); }
 
 }  // namespace
 
@@ -225,8 +212,9 @@ size_t aa_ycc_desc_size(int64_t n) {
 int aa_ycc_plan_host(int filter, int64_t n, int64_t oH, int64_t oW, const aa_ycbcr_image *images, const aa_many_place *places,
                      const uint8_t *fill, void *desc_host, size_t desc_bytes, size_t *workspace_bytes) {
   if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
-  if (n < 0 || n > kAAManyMax / 3 || oH <= 0 || oW <= 0 || oH > kAAManyMax || oW > kAAManyMax) return AA_ERR_BAD_SHAPE;
-  if (!desc_host || !workspace_bytes || (n > 0 && !images)) return AA_ERR_NULL;
+  // (the places are checked where the composed plans are made, after the images)
+  const int rc0 = aa_many_check_canvas(n, kAAManyMax / 3, true, oH, oW, desc_host, workspace_bytes, images, nullptr);
+  if (rc0 != AA_OK) return rc0;
   if (desc_bytes < aa_ycc_desc_size(n)) return AA_ERR_WORKSPACE;
   const int64_t ygroups = (oH + AA_YCC_VROWS - 1) / AA_YCC_VROWS, vstrips = (oW + AA_YCC_VCOLS - 1) / AA_YCC_VCOLS;
   if (n * ygroups * vstrips > INT32_MAX) return AA_ERR_BAD_SHAPE;  // (the grid of the vertical pass)
@@ -317,17 +305,14 @@ int aa_launch_many_ycbcr(const void *desc_host, const void *desc_dev, void *out_
   if (out_layout != AA_NCHW && out_layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
   if (out_elem != AA_U8 && out_elem != AA_F32 && out_elem != AA_F16 && out_elem != AA_BF16) return AA_ERR_BAD_DTYPE;
   const int64_t n = hd->n;
-  if (n == 0) return AA_OK;
-  if (!desc_dev || !out_dev || !workspace_dev) return AA_ERR_NULL;
-  if (workspace_bytes < (size_t)hd->ws_bytes) return AA_ERR_WORKSPACE;
-  if (((uintptr_t)workspace_dev & 15) || ((uintptr_t)desc_dev & 7)) return AA_ERR_BAD_SHAPE;
-  if ((uintptr_t)out_dev & (out_elem == AA_F32 ? 3 : (out_elem == AA_U8 ? 0 : 1))) return AA_ERR_BAD_SHAPE;
+  int rc = aa_many_check_launch(n, desc_dev, out_dev, workspace_dev, workspace_bytes, hd->ws_bytes, out_elem == AA_F32 ? 4 : (out_elem == AA_U8 ? 1 : 2));
+  if (rc != AA_OK || n == 0) return rc;
   const bool il = hd->interleaved != 0;
   const char *plan_a = (const char *)desc_host + hd->off_a, *plan_a_dev = (const char *)desc_dev + hd->off_a;
   const char *plan_b = il ? (const char *)desc_host + hd->off_b : nullptr, *plan_b_dev = il ? (const char *)desc_dev + hd->off_b : nullptr;
   char *ws_a = (char *)workspace_dev, *ws_b = ws_a + hd->ws_b;
   const int64_t na = il ? n : 3 * n;
-  int rc = aa_launch_many_tables_hpass(plan_a, plan_a_dev, ws_a, (size_t)hd->ws_b, stream);
+  rc = aa_launch_many_tables_hpass(plan_a, plan_a_dev, ws_a, (size_t)hd->ws_b, stream);
   if (rc != AA_OK) return rc;
   if (il) {
     rc = aa_launch_many_tables_hpass(plan_b, plan_b_dev, ws_b, (size_t)(hd->ws_bytes - hd->ws_b), stream);

@@ -3,12 +3,13 @@
 // integer box sum, and the ragged resize (aa_many.hip, untouched) then runs over the small results, which it reads where they lie.
 //
 // The grid is the sum of all items' work units.  A workgroup of 256 lanes takes one unit = (item, plane, output row Y, a tile of output
-// columns whose input bytes per row fit 4096), finds its item by the binary search over the prefix sums that many_hpass uses, reads that
+// columns whose input bytes per row fit 4096), finds its item by the binary search over the prefix sums that many_hpass uses (aa_unit_item, aa_many_dev.h), reads that
 // item's record (uniform per workgroup: scalar loads) and runs reduce_tile (aa_reduce_tile.h) — the dense kernel's body, bit for bit.  fx
 // differs per item, so it is a run-time value, with a per-workgroup switch to the compile-time forms for 2, 3, 4 and 8.  Row starts have any alignment, and no byte beyond the end of a box's row is read.
 // The host planner computes, per item, the box's first byte, the result's size and 16-byte aligned place in one arena, the tiling and
 // the four multipliers (the float32 division of aa_reduce.hip): nothing is allocated, synchronised or read back.
 
+#include "aa_many_dev.h"
 #include "aa_many_host.h"
 #include "aa_reduce_many.h"
 #include "aa_reduce_tile.h"
@@ -21,11 +22,7 @@ __global__ void __launch_bounds__(kReduceThreads) reduce_many_u8_kernel(const AA
                                                                         int E) {
   __shared__ __attribute__((aligned(16))) uint32_t colsum[kReduceTile];
   const int64_t unit = blockIdx.x;
-  int lo = 0, hi = n;  // the item whose units hold `unit`: prefix[lo] <= unit < prefix[lo + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (prefix[mid] <= unit) lo = mid; else hi = mid;
-  }
+  const int lo = aa_unit_item(prefix, n, unit);
   const AAReduceManyItem &it = items[lo];
   int64_t u = unit - prefix[lo];
   const int xtiles = it.xtiles, rh = it.rh, rw = it.rw, fx = it.fx, fy = it.fy, bh = it.bh, sx = it.sx;
@@ -57,10 +54,7 @@ __global__ void __launch_bounds__(kReduceThreads) reduce_many_u8_kernel(const AA
 }  // namespace
 
 // ---- host: the planner -------------------------------------------------------------------------------------------------------------------
-size_t aa_reduce_many_desc_size(int64_t n) {
-  if (n < 0) return 0;
-  return sizeof(AAReduceManyHeader) + (size_t)n * sizeof(AAReduceManyItem) + ((size_t)n + 1) * sizeof(int64_t);
-}
+size_t aa_reduce_many_desc_size(int64_t n) { return aa_desc_size(sizeof(AAReduceManyHeader), sizeof(AAReduceManyItem), n); }
 
 int aa_reduce_many_plan_host(int layout, int64_t n, int64_t C, const aa_reduce_item *in, void *desc_host, size_t desc_bytes, size_t *arena_bytes,
                              int64_t *out_offsets) {
@@ -127,9 +121,8 @@ int aa_launch_reduce_many_u8(const void *desc_host, const void *desc_dev, void *
   if (!desc_dev || !arena_dev) return AA_ERR_NULL;
   if (arena_bytes < (size_t)hd->arena_bytes) return AA_ERR_WORKSPACE;
   if (((uintptr_t)arena_dev & 15) || ((uintptr_t)desc_dev & 7)) return AA_ERR_BAD_SHAPE;
-  const AAReduceManyItem *items = (const AAReduceManyItem *)((const char *)desc_dev + sizeof(AAReduceManyHeader));
-  const int64_t *prefix = (const int64_t *)(items + n);
-  hipLaunchKernelGGL(reduce_many_u8_kernel, dim3((unsigned)hd->units), dim3(kReduceThreads), 0, stream, items, prefix, (uint8_t *)arena_dev, (int)n,
+  const AADescView<AAReduceManyItem> v = aa_desc_view<AAReduceManyHeader, AAReduceManyItem>(desc_dev, n);
+  hipLaunchKernelGGL(reduce_many_u8_kernel, dim3((unsigned)hd->units), dim3(kReduceThreads), 0, stream, v.items, v.prefix, (uint8_t *)arena_dev, (int)n,
                      hd->E);
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;

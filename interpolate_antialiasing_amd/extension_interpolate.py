@@ -579,18 +579,36 @@ def _many_pack_places(places):
     return precs
 
 
-def _many_canvas(name: str, images, output_size: Sequence[int], channels: Optional[int], empty: str = "[0, C, oh, ow]", alpha: bool = False):
-    """output_size and the images of a call with a canvas, checked in the calls' order -> (oh, ow, items, device of a batch tensor or
-    None, N, C).  alpha: the call resizes the way Pillow resizes LA / RGBA."""
+def _many_flips(name: str, flips, n: int):
+    """flips of a ragged call, checked -> None or N bools."""
+    if flips is None:
+        return None
+    flips = [bool(v) for v in flips]
+    if len(flips) != n:
+        raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
+    return flips
+
+
+def _many_output_size(name: str, output_size: Sequence[int], images_checked: bool = True):
+    """output_size of a call with a canvas -> (oh, ow).  The calls look at its length before the images and at its values after them:
+    images_checked False is the first look alone."""
     if len(output_size) != 2:
         raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
     oh, ow = int(output_size[0]), int(output_size[1])
+    if images_checked and not (oh > 0 and ow > 0):
+        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    return oh, ow
+
+
+def _many_canvas(name: str, images, output_size: Sequence[int], channels: Optional[int], empty: str = "[0, C, oh, ow]", alpha: bool = False):
+    """output_size and the images of a call with a canvas, checked in the calls' order -> (oh, ow, items, device of a batch tensor or
+    None, N, C).  alpha: the call resizes the way Pillow resizes LA / RGBA."""
+    _many_output_size(name, output_size, images_checked=False)
     items, dev0, n, c = _many_items(name, images, channels, empty)
     if alpha and c not in (2, 4):
         raise NotImplementedError(f"{name}(): alpha=True is built for 2- or 4-channel images with straight alpha last (Pillow's LA / RGBA "
                                   f"resize), got C = {c}")
-    if not (oh > 0 and ow > 0):
-        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    oh, ow = _many_output_size(name, output_size)
     return oh, ow, items, dev0, n, c
 
 
@@ -619,12 +637,7 @@ def _many_convert(name: str, conv: dict, n: int, c: int):
                 raise ValueError(f"{name}(): std[{i}] = {std[i]} must be finite and not zero")
             cv.mean[i], cv.std[i] = mean[i], std[i]
         cv.normalize = 1
-    flips = conv["flips"]
-    if flips is not None:
-        flips = [bool(v) for v in flips]
-        if len(flips) != n:
-            raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
-    return cv, flips, out_dtype
+    return cv, _many_flips(name, conv["flips"], n), out_dtype
 
 
 def _many_items(name: str, images, channels: Optional[int], empty: str):
@@ -656,6 +669,11 @@ def _many_items(name: str, images, channels: Optional[int], empty: str):
     return items, dev0, n, c
 
 
+def _many_box(bx, w: int, h: int):
+    """One entry of boxes for a [h, w] image -> None, or the box as Pillow's C sees it: Pillow's checks and wording, then floats."""
+    return None if bx is None else boxmath.box_f32(boxmath.check_box(bx, w, h))
+
+
 def _many_check_items(name: str, items, c: int, boxes, out_size, dtypes=None):
     """Dtype, C, sizes, device and box of every item -> the boxes as Pillow's C sees them (None: the whole image).  out_size(i): the
     (H, W) item i is resized to, for the wording of the size check.  dtypes: None (uint8 only), or the dtypes the call copies (one per
@@ -683,10 +701,7 @@ def _many_check_items(name: str, items, c: int, boxes, out_size, dtypes=None):
             raise RuntimeError(f"Input and output sizes should be greater than 0, but got input (H: {h}, W: {w}) output (H: {oh}, W: {ow})")
         if t.device != items[0].device:
             raise ValueError(f"{name}(): every image must be on the same device: images[{i}] is on {t.device}, images[0] on {items[0].device}")
-        bx = boxes[i] if boxes is not None else None
-        if bx is not None:
-            bx = boxmath.box_f32(boxmath.check_box(bx, w, h))  # Pillow's checks and wording; its C takes the box as floats
-        checked.append(bx)
+        checked.append(_many_box(boxes[i] if boxes is not None else None, w, h))
     return checked
 
 
@@ -846,10 +861,7 @@ def resize_many_nearest(images, output_size: Sequence[int], *, boxes=None, flips
     dtype = items[0].dtype if n else (images.dtype if isinstance(images, torch.Tensor) and images.dtype in _NEAREST_RANGE else torch.uint8)
     if out_dtype is torch.int64 and c != 1:
         raise NotImplementedError(f"{name}(): out_dtype torch.int64 is built for one channel (a class-id map), got C = {c}")
-    if flips is not None:
-        flips = [bool(v) for v in flips]
-        if len(flips) != n:
-            raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
+    flips = _many_flips(name, flips, n)
     places = _many_places(name, sizes, offsets, n, oh, ow)
     fills = _many_fill(name, fill, c, *_NEAREST_RANGE[dtype], note=f" ({dtype})")
     res_dtype = dtype if out_dtype is None else out_dtype
@@ -934,10 +946,7 @@ def resize_many_maps(maps, output_size: Sequence[int], mode: str = "bilinear", *
     dtype = items[0].dtype if n else (maps.dtype if isinstance(maps, torch.Tensor) and maps.dtype in _MAPS_MODES else torch.float32)
     if c != 1:  # (an empty batch that names its C)
         raise NotImplementedError(f"{name}(): {dtype} maps have one channel (Pillow's \"I;16\", \"I\" and \"F\"), got C = {c}")
-    if flips is not None:
-        flips = [bool(v) for v in flips]
-        if len(flips) != n:
-            raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
+    flips = _many_flips(name, flips, n)
     places = _many_places(name, sizes, offsets, n, oh, ow)
     _, elem, fill_range = _MAPS_MODES[dtype]
     if fill_range is not None:
@@ -1039,11 +1048,7 @@ def resize_many_ycbcr(images, output_size: Sequence[int], mode: str = "bilinear"
     as_bytes = out_dtype in (None, torch.uint8)
     if as_bytes and mean is not None:
         raise ValueError(f"{name}(): mean / std need a float out_dtype")
-    if len(output_size) != 2:
-        raise RuntimeError(f"It is expected output_size equals to 2, but got size {len(output_size)}")
-    oh, ow = int(output_size[0]), int(output_size[1])
-    if not (oh > 0 and ow > 0):
-        raise RuntimeError(f"Input and output sizes should be greater than 0, but got output (H: {oh}, W: {ow})")
+    oh, ow = _many_output_size(name, output_size)
     images = list(images)
     n = len(images)
     subs = [subsampling] * n if isinstance(subsampling, str) else list(subsampling)
@@ -1077,16 +1082,10 @@ def resize_many_ycbcr(images, output_size: Sequence[int], mode: str = "bilinear"
         if planes and y.device != planes[0][0].device:
             raise ValueError(f"{name}(): every image must be on the same device: images[{i}] is on {y.device}, images[0] on {planes[0][0].device}")
         planes.append((y, chroma))
-    checked = []
-    for i, (y, _) in enumerate(planes):
-        bx = boxes[i] if boxes is not None else None
-        checked.append(None if bx is None else boxmath.box_f32(boxmath.check_box(bx, int(y.shape[1]), int(y.shape[0]))))
+    checked = [_many_box(boxes[i] if boxes is not None else None, int(y.shape[1]), int(y.shape[0])) for i, (y, _) in enumerate(planes)]
     cv, res_dtype = None, torch.uint8
     if as_bytes:
-        if flips is not None:
-            flips = [bool(v) for v in flips]
-            if len(flips) != n:
-                raise ValueError(f"{name}(): flips must hold one entry per image ({n}), got {len(flips)}")
+        flips = _many_flips(name, flips, n)
     else:
         cv, flips, res_dtype = _many_convert(name, {"out_dtype": out_dtype, "mean": mean, "std": std, "flips": flips}, n, 3)
     fills = _many_fill(name, 0 if fill is None else fill, 3)

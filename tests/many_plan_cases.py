@@ -98,6 +98,48 @@ def plan_nearest(layout, eb, c, oh, ow, recs, n, places=None, fill=None, nbytes=
                     lambda b, nb, ws: L.aa_many_plan_nearest(layout, eb, n, c, oh, ow, recs, _places(places), cf, b, nb, ws))
 
 
+def plan_maps(f, elem, oh, ow, recs, n, places=None, fill=0.0, overflow=0, nbytes=None):
+    """aa_many_plan_maps."""
+    L = _lib.load()
+    fid = _lib.FILTER_IDS[f] if isinstance(f, str) else f
+    return _planned(L.aa_many_desc_bytes_maps(max(n, 0)) if nbytes is None else nbytes,
+                    lambda b, nb, ws: L.aa_many_plan_maps(fid, elem, n, oh, ow, recs, _places(places), fill, overflow, b, nb, ws))
+
+
+def ycc_images(items, interleaved, flags=None):
+    """items [(H, W, subsampling, box or None)] -> aa_ycbcr_image records: every plane's pitch beyond its row; interleaved pairs are one
+    plane of 2-byte pixels, Cr one byte after Cb at the same pitch."""
+    sub = gen("resize_many_ycbcr").SUBSAMPLING
+    recs = (_lib.YccImage * max(len(items), 1))()
+    for i, (h, w, ss, box) in enumerate(items):
+        r = recs[i]
+        sx, sy = sub[ss]
+        r.H, r.W, r.cH, r.cW = h, w, -(-h // sy), -(-w // sx)
+        r.y_dev, r.cb_dev = (1 << 20) + 65536 * i, (1 << 24) + 65536 * i
+        r.y_stride_row = w + 3
+        if interleaved:
+            r.cr_dev, r.chroma_stride_px = r.cb_dev + 1, 2
+            r.cb_stride_row = r.cr_stride_row = 2 * r.cW + 6
+        else:
+            r.cr_dev, r.chroma_stride_px = (1 << 25) + 65536 * i, 1
+            r.cb_stride_row, r.cr_stride_row = r.cW + 3, r.cW + 5
+        r.subsampling = _lib.YCC_SUBSAMPLING[ss]
+        if box is not None:
+            r.has_box = 1
+            r.box[0], r.box[1], r.box[2], r.box[3] = box
+        r.flags = flags[i] if flags is not None else 0
+    return recs
+
+
+def plan_ycbcr(f, oh, ow, recs, n, places=None, fill=None, nbytes=None):
+    """aa_many_plan_ycbcr."""
+    L = _lib.load()
+    fid = _lib.FILTER_IDS[f] if isinstance(f, str) else f
+    fl = None if fill is None else (ctypes.c_uint8 * 3)(*fill)
+    return _planned(L.aa_many_desc_bytes_ycbcr(n) if nbytes is None else nbytes,
+                    lambda b, nb, ws: L.aa_many_plan_ycbcr(fid, n, oh, ow, recs, _places(places), fl, b, nb, ws))
+
+
 def reduce_items(layout, c, items):
     """items [(H, W, integer box, (fx, fy))] -> aa_reduce_item records."""
     recs = (_lib.ReduceItem * max(len(items), 1))()
@@ -159,6 +201,27 @@ def _case_plans():
             reduced = [(items[i][0], items[i][1], p[1], p[0]) for i, p in enumerate(plans) if p is not None]
             for ln, layout in LAYOUTS:
                 yield f"reduce/{name}/{f}/{ln}", plan_reduce(layout, c, reduce_items(layout, c, reduced), len(reduced))
+    g = gen("resize_many_maps")
+    for name, cs in g.CASES.items():
+        (oh, ow), n = cs["canvas"], len(cs["items"])
+        geo = [g.geometry(cs, i) for i in range(n)]
+        flags = [FLIP if cs.get("flips") is not None and cs["flips"][i] else 0 for i in range(n)]
+        places = [q[3] + q[4] for q in geo] if cs.get("placed") else None
+        for dt in cs["dtypes"]:
+            elem, eb = {"u16": (_lib.MAPS_U16, 2), "i32": (_lib.MAPS_I32, 4), "f32": (_lib.MAPS_F32, 4)}[dt]
+            fill = float(g.FILLS[dt]) if cs.get("placed") else 0.0
+            for f in cs["filters"]:
+                for on, over in sorted(_lib.MAPS_OVERFLOW.items()) if dt == "u16" else [("pillow", 0)]:
+                    yield (f"maps/{name}/{f}/{dt}" + (f"/{on}" if dt == "u16" else ""),
+                           plan_maps(f, elem, oh, ow, images(_lib.NCHW, 1, geo, flags, eb), n, places, fill, over))
+    g = gen("resize_many_ycbcr")
+    for name, cs in g.CASES.items():
+        (oh, ow), n = cs["canvas"], len(cs["items"])
+        flags = [FLIP if cs.get("flips") and cs["flips"][i] else 0 for i in range(n)]
+        places = g.places(name) if cs.get("sizes") or cs.get("offsets") else None
+        for f in cs["filters"]:
+            for an, il in (("planar", False), ("interleaved", True)):
+                yield f"ycbcr/{name}/{f}/{an}", plan_ycbcr(f, oh, ow, ycc_images(cs["items"], il, flags), n, places, cs.get("fill"))
 
 
 def _error_plans():
@@ -230,6 +293,41 @@ def _error_plans():
     yield "err/reduce/stride_planar", red(layout=P)
     yield "err/reduce/null_image", red(recs=strided(reduce_items(N, 3, rok), data_dev=None))
     yield "err/reduce/short_block", red(nbytes=_lib.load().aa_reduce_many_desc_bytes(2) - 1)
+
+    U, F = _lib.MAPS_U16, _lib.MAPS_F32
+    maps = lambda **kw: plan_maps(**{**dict(f="linear", elem=U, oh=10, ow=12, recs=images(P, 1, ok, eb=2), n=2), **kw})  # noqa: E731
+    fmaps = lambda **kw: maps(**{**dict(elem=F, recs=images(P, 1, ok, eb=4)), **kw})  # noqa: E731
+    yield "err/maps/ok", maps()
+    yield "err/maps/n_negative", maps(n=-1)
+    yield "err/maps/null_images", maps(recs=None)
+    yield "err/maps/elem", maps(elem=3)
+    yield "err/maps/overflow", maps(overflow=2)
+    yield "err/maps/fill_nan", fmaps(fill=float("nan"))
+    yield "err/maps/fill_inf", fmaps(fill=float("inf"))
+    yield "err/maps/fill_beyond_f32", fmaps(fill=1e39)
+    yield "err/maps/fill_fraction_u16", maps(fill=1.5)
+    yield "err/maps/fill_65536_u16", maps(fill=65536.0)
+    yield "err/maps/place_size", maps(places=[(7, 9, 0, 0), (0, 9, 0, 0)])
+    yield "err/maps/short_block", maps(nbytes=_lib.load().aa_many_desc_bytes_maps(2) - 1)
+    yield "err/maps/box_beyond", maps(recs=images(P, 1, [ok[0], (9, 11, (0, 0, 12, 9))], eb=2))
+    yield "err/maps/box_empty", maps(recs=images(P, 1, [ok[0], (9, 11, (5, 5, 5, 8))], eb=2))
+    yield "err/maps/unaligned_data", maps(recs=strided(images(P, 1, ok, eb=2), data_dev=4097))
+    yield "err/maps/unaligned_row", fmaps(recs=strided(images(P, 1, ok, eb=4), stride_row=14 * 4 + 2))
+    yield "err/maps/flag_alpha", maps(recs=images(P, 1, ok, [FLIP, ALPHA], eb=2))
+    yield "err/maps/ksize", plan_maps("lanczos", U, 10, 10, images(P, 1, [(20000, 30, None)], eb=2), 1, [(1, 10, 0, 0)])
+
+    yok = [(20, 30, "420", None), (9, 11, "420", (1.5, 2.0, 10.0, 8.5))]
+    ycc = lambda il=False, **kw: plan_ycbcr(**{**dict(f="linear", oh=10, ow=12, recs=ycc_images(yok, il), n=2), **kw})  # noqa: E731
+    yield "err/ycbcr/ok", ycc()
+    yield "err/ycbcr/ok_interleaved", ycc(True)
+    yield "err/ycbcr/null_plane", ycc(recs=strided(ycc_images(yok, False), cb_dev=None))
+    yield "err/ycbcr/subsampling", ycc(recs=strided(ycc_images(yok, False), subsampling=4))
+    yield "err/ycbcr/chroma_height", ycc(recs=strided(ycc_images(yok, False), cH=6))
+    yield "err/ycbcr/other_arrangement", ycc(recs=strided(ycc_images(yok, False), chroma_stride_px=2))
+    yield "err/ycbcr/cr_not_beside_cb", ycc(recs=strided(ycc_images(yok, True), cr_dev=(1 << 24) + 65536 + 2))
+    yield "err/ycbcr/n_beyond", ycc(n=KMAX // 3 + 1, nbytes=_lib.load().aa_many_desc_bytes_ycbcr(2))
+    yield "err/ycbcr/short_block", ycc(nbytes=_lib.load().aa_many_desc_bytes_ycbcr(2) - 1)
+    yield "err/ycbcr/flag_alpha", ycc(recs=ycc_images(yok, False, [FLIP, ALPHA]))
 
 
 def plans():

@@ -24,8 +24,8 @@ def planned():
 
 def test_the_key_set_is_complete(planned):
     assert sorted(planned) == sorted(FROZEN)
-    assert GROUPS == ["alpha", "err", "many", "nearest", "patches", "placed", "reduce"]
-    assert {k.split("/")[1] for k in FROZEN if k.startswith("err/")} == {"many", "patches", "nearest", "reduce"}
+    assert GROUPS == ["alpha", "err", "many", "maps", "nearest", "patches", "placed", "reduce", "ycbcr"]
+    assert {k.split("/")[1] for k in FROZEN if k.startswith("err/")} == {"many", "patches", "nearest", "reduce", "maps", "ycbcr"}
 
 
 @pytest.mark.parametrize("group", GROUPS)
