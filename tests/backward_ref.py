@@ -22,15 +22,13 @@ the bound away from a long-double one, so an fp64 err / bound is the sum of two 
 """
 from __future__ import annotations
 
-import importlib.util
 import math
-import os
 
 import numpy as np
 
+import kit_golden
 import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILTERS = ("linear", "cubic", "box", "hamming", "lanczos")
 FILTER_ID = {"linear": 0, "cubic": 1, "box": 2, "hamming": 3, "lanczos": 4}
 INTERP_SIZE = {"linear": 2, "cubic": 4, "box": 1, "hamming": 2, "lanczos": 6}  # 2 x support
@@ -38,14 +36,7 @@ UNIT = {np.dtype(np.float32): 2.0 ** -24, np.dtype(np.float64): 2.0 ** -53}
 MAX_KSIZE = 4096  # AA_MAX_KSIZE
 
 
-def _restatement():
-    spec = importlib.util.spec_from_file_location("make_golden_filters", os.path.join(ROOT, "tests", "golden", "make_golden_filters.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-M = _restatement()
+M = kit_golden.generator("filters")
 
 
 # ---- one axis ---------------------------------------------------------------------------------------------------------

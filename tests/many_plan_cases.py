@@ -5,26 +5,15 @@ bytes); the block is a zero-initialised buffer and the planners memset their rec
 says what a plan should hold: tests/golden/many_plans.json records what the planners wrote before they were restructured.  Not a test
 module."""
 import ctypes
-import functools
-import importlib.util
-import os
 import struct
+
+from kit_golden import generator as gen  # the generator module of one ragged fixture: its CASES are the cases enumerated here
 
 from interpolate_antialiasing_amd import _lib, boxmath
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAYOUTS = (("nhwc", _lib.NHWC), ("nchw", _lib.NCHW))
 KMAX = (2 ** 31 - 1) // 4
 FLIP, ALPHA = _lib.MANY_FLIP_X, _lib.MANY_PREMUL_ALPHA
-
-
-@functools.lru_cache(maxsize=None)
-def gen(stem):
-    """The generator module of one ragged fixture: its CASES are the cases enumerated here."""
-    spec = importlib.util.spec_from_file_location(f"make_golden_{stem}", os.path.join(ROOT, "tests", "golden", f"make_golden_{stem}.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def _lie(r, layout, c, h, w, eb=1):

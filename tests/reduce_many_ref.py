@@ -3,26 +3,14 @@
 restatement (which the generator asserted to be Pillow's on every entry), once each, and left unchanged.  Nothing here calls the code
 under test.  Not a test module."""
 import functools
-import importlib.util
-import os
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "box", "hamming": "hamming", "lanczos": "lanczos"}
+import kit_golden
+from kit_golden import MODE  # noqa: F401
 
-
-@functools.lru_cache(maxsize=None)
-def gen():
-    spec = importlib.util.spec_from_file_location("make_golden_reduce_many", os.path.join(ROOT, "tests", "golden", "make_golden_reduce_many.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@functools.lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "reduce_many.npz"), allow_pickle=False))
+gen = functools.partial(kit_golden.generator, "reduce_many")
+fixture = functools.partial(kit_golden.fixture, "reduce_many")
 
 
 def case(name):
@@ -53,9 +41,7 @@ def boxes(name):
 @functools.lru_cache(maxsize=None)
 def item(name, i):
     """[C, H, W] uint8 input of item i of case `name` (read-only: shared between tests)."""
-    x = np.ascontiguousarray(gen().item_input(case(name), i))
-    x.setflags(write=False)
-    return x
+    return kit_golden.readonly(gen().item_input(case(name), i))
 
 
 @functools.lru_cache(maxsize=None)
@@ -80,9 +66,7 @@ def resized(name, f, i):
     key = f"{name}/{f}/{i}"
     incrc, outcrc, _ = g.expected(fixture(), key)
     assert g.crc(item(name, i)) == incrc and g.crc(out) == outcrc, f"{key}: the restatement is not the fixture's Pillow output"
-    out = np.ascontiguousarray(out)
-    out.setflags(write=False)
-    return out
+    return kit_golden.readonly(out)
 
 
 def _assert_samples(key, what, got_hwc, outcrc, samples):

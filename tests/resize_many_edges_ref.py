@@ -3,34 +3,22 @@ with Pillow (tests/golden/resize_many_edges.npz), loaded once; item inputs regen
 each, and left unchanged; the tile sizes of the kernels read out of their source text, and the work units they imply for a case, worked
 out from the restatement's coefficients.  Nothing here calls the code under test.  Not a test module."""
 import functools
-import importlib.util
 import os
 import re
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "interpolate_antialiasing_amd", "csrc")
-MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "box", "hamming": "hamming", "lanczos": "lanczos"}
+import kit_golden
+from kit_golden import MODE  # noqa: F401
 
-
-@functools.lru_cache(maxsize=None)
-def gen():
-    spec = importlib.util.spec_from_file_location("make_golden_resize_many_edges",
-                                                  os.path.join(ROOT, "tests", "golden", "make_golden_resize_many_edges.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+CSRC = os.path.join(kit_golden.ROOT, "interpolate_antialiasing_amd", "csrc")
+gen = functools.partial(kit_golden.generator, "resize_many_edges")
+fixture = functools.partial(kit_golden.fixture, "resize_many_edges")
 
 
 def br():
     """make_golden_box_reduce: box_coeffs, resize_box_restated."""
     return gen()._rm._br
-
-
-@functools.lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "resize_many_edges.npz"), allow_pickle=False))
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,17 +38,13 @@ def classes(names):
 @functools.lru_cache(maxsize=None)
 def item(name, i):
     """[C, H, W] uint8 input of item i of case `name` (read-only: shared between tests)."""
-    x = np.ascontiguousarray(gen().item_input(case(name), i))
-    x.setflags(write=False)
-    return x
+    return kit_golden.readonly(gen().item_input(case(name), i))
 
 
 @functools.lru_cache(maxsize=None)
 def restated(name, f, i):
     """The expected [oH, oW, C] bytes of one item from the CPU restatement (read-only: shared between tests)."""
-    y = np.ascontiguousarray(gen().restated(case(name), f, i, item(name, i)))
-    y.setflags(write=False)
-    return y
+    return kit_golden.readonly(gen().restated(case(name), f, i, item(name, i)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -93,16 +77,7 @@ def expected(key):
 def assert_matches_fixture(key, x_chw, got_hwc):
     """got_hwc [oH, oW, C] equals the expected array of fixture entry `key`: the input is the fixture's (CRC-32), the sampled pixels are
     Pillow's (they say where a mismatch lies) and the whole array has the fixture's CRC-32."""
-    g = gen()
-    incrc, outcrc, samples = expected(key)
-    assert g.crc(x_chw) == incrc, f"{key}: the regenerated input is not the fixture's"
-    got = np.ascontiguousarray(got_hwc)
-    px = got.reshape(-1, got.shape[-1])
-    idx = g.sample_pixels(len(px))
-    assert px[idx].shape == samples.shape, f"{key}: output shape {got.shape}"
-    bad = np.nonzero((px[idx] != samples).any(axis=1))[0]
-    assert bad.size == 0, f"{key}: {bad.size} of {len(idx)} sampled pixels differ, first at flat pixel {idx[bad[0]]}: {px[idx[bad[0]]]} != {samples[bad[0]]}"
-    assert g.crc(got) == outcrc, f"{key}: the sampled pixels match but the whole output's CRC-32 differs from the fixture's"
+    kit_golden.assert_sampled(key, gen(), *expected(key), x_chw, got_hwc)
 
 
 # ---- the tile sizes, from the source text ----------------------------------------------------------------------------------------------

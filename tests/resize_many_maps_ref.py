@@ -15,16 +15,18 @@ The arithmetic, stated once:
 The loops run over taps in order and are vectorised over outputs."""
 import fractions
 import functools
-import importlib.util
 import math
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (os.path.dirname(HERE), HERE):  # (the fixture's generator loads this file by its path)
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import kit_golden  # noqa: E402
 
 from interpolate_antialiasing_amd import boxmath  # noqa: E402
 
@@ -208,17 +210,8 @@ def many(xs, canvas, name: str, boxes=None, sizes=None, offsets=None, flips=None
 
 
 # ---- the fixture -------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def gen():
-    spec = importlib.util.spec_from_file_location("make_golden_resize_many_maps", os.path.join(ROOT, "tests", "golden", "make_golden_resize_many_maps.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@functools.lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "resize_many_maps.npz"), allow_pickle=False))
+gen = functools.partial(kit_golden.generator, "resize_many_maps")
+fixture = functools.partial(kit_golden.fixture, "resize_many_maps")
 
 
 @functools.lru_cache(maxsize=None)

@@ -2,31 +2,22 @@
 (tests/golden/make_golden_resize_many_nearest.py) and the fixture it made with Pillow (tests/golden/resize_many_nearest.npz), loaded once;
 item inputs regenerated from their seeds, once each, and left unchanged.  Not a test module."""
 import functools
-import importlib.util
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (os.path.dirname(HERE), HERE):  # (the fixture's generator loads this file by its path)
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import kit_golden  # noqa: E402
 
 from interpolate_antialiasing_amd import boxmath  # noqa: E402
 
-
-@functools.lru_cache(maxsize=None)
-def gen():
-    spec = importlib.util.spec_from_file_location("make_golden_resize_many_nearest",
-                                                  os.path.join(ROOT, "tests", "golden", "make_golden_resize_many_nearest.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@functools.lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "resize_many_nearest.npz"), allow_pickle=False))
+gen = functools.partial(kit_golden.generator, "resize_many_nearest")
+fixture = functools.partial(kit_golden.fixture, "resize_many_nearest")
 
 
 def case_names():
@@ -40,9 +31,8 @@ def inputs(name):
     cs = g.case(name)
     xs = []
     for i in range(g.n_items(cs)):
-        x = np.ascontiguousarray(g.item_input(cs, i))
+        x = kit_golden.readonly(g.item_input(cs, i))
         assert g.crc(x) == int(fixture()[name + "__incrc"][i]), f"{name}: the regenerated input {i} is not the fixture's"
-        x.setflags(write=False)
         xs.append(x)
     return tuple(xs)
 

@@ -2,28 +2,14 @@
 made with Pillow (tests/golden/resize_many_patches.npz), loaded once; item inputs regenerated from their seeds and the expected token
 matrices computed from the CPU restatement, once each, and left unchanged.  Nothing here calls the code under test.  Not a test module."""
 import functools
-import importlib.util
-import os
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "box", "hamming": "hamming", "lanczos": "lanczos"}
-MEAN, STD = [123.675, 116.28, 103.53, 127.5], [58.395, 57.12, 57.375, 64.0]
+import kit_golden
+from kit_golden import MEAN, MODE, STD  # noqa: F401
 
-
-@functools.lru_cache(maxsize=None)
-def gen():
-    spec = importlib.util.spec_from_file_location("make_golden_resize_many_patches",
-                                                  os.path.join(ROOT, "tests", "golden", "make_golden_resize_many_patches.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@functools.lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "resize_many_patches.npz"), allow_pickle=False))
+gen = functools.partial(kit_golden.generator, "resize_many_patches")
+fixture = functools.partial(kit_golden.fixture, "resize_many_patches")
 
 
 def case(name):
@@ -37,9 +23,7 @@ def names():
 @functools.lru_cache(maxsize=None)
 def item(name, i):
     """[C, H, W] uint8 input of item i of case `name` (read-only: shared between tests)."""
-    x = np.ascontiguousarray(gen().item_input(case(name), i))
-    x.setflags(write=False)
-    return x
+    return kit_golden.readonly(gen().item_input(case(name), i))
 
 
 def inputs(name):

@@ -2,26 +2,11 @@
 with Pillow (tests/golden/resize_many_placed.npz), loaded once; item inputs regenerated from their seeds, once each, and left unchanged.
 Not a test module."""
 import functools
-import importlib.util
-import os
 
-import numpy as np
+import kit_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@functools.lru_cache(maxsize=None)
-def gen():
-    spec = importlib.util.spec_from_file_location("make_golden_resize_many_placed",
-                                                  os.path.join(ROOT, "tests", "golden", "make_golden_resize_many_placed.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@functools.lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "resize_many_placed.npz"), allow_pickle=False))
+gen = functools.partial(kit_golden.generator, "resize_many_placed")
+fixture = functools.partial(kit_golden.fixture, "resize_many_placed")
 
 
 @functools.lru_cache(maxsize=None)
@@ -32,9 +17,7 @@ def _expected_index():
 @functools.lru_cache(maxsize=None)
 def item(name, i):
     """[C, H, W] uint8 input of item i of case `name` (read-only: shared between tests)."""
-    x = np.ascontiguousarray(gen().item_input(gen().case(name), i))
-    x.setflags(write=False)
-    return x
+    return kit_golden.readonly(gen().item_input(gen().case(name), i))
 
 
 def boxes(name):
@@ -66,13 +49,4 @@ def expected(key):
 def assert_matches_fixture(key, x_chw, got_hwc):
     """got_hwc [oH, oW, C] equals the expected canvas of fixture entry `key`: the input is the fixture's (CRC-32), the sampled pixels are
     Pillow's (they say where a mismatch lies) and the whole canvas has the fixture's CRC-32."""
-    g = gen()
-    incrc, outcrc, samples = expected(key)
-    assert g.crc(x_chw) == incrc, f"{key}: the regenerated input is not the fixture's"
-    got = np.ascontiguousarray(got_hwc)
-    px = got.reshape(-1, got.shape[-1])
-    idx = g.sample_pixels(len(px))
-    assert px[idx].shape == samples.shape, f"{key}: output shape {got.shape}"
-    bad = np.nonzero((px[idx] != samples).any(axis=1))[0]
-    assert bad.size == 0, f"{key}: {bad.size} of {len(idx)} sampled pixels differ, first at flat pixel {idx[bad[0]]}: {px[idx[bad[0]]]} != {samples[bad[0]]}"
-    assert g.crc(got) == outcrc, f"{key}: the sampled pixels match but the whole canvas's CRC-32 differs from the fixture's"
+    kit_golden.assert_sampled(key, gen(), *expected(key), x_chw, got_hwc)

@@ -1,25 +1,11 @@
 """Shared by the resize_many tests: the fixture generator (tests/golden/make_golden_resize_many.py), the fixture it made with Pillow
 (tests/golden/resize_many.npz), loaded once; item inputs regenerated from their seeds, once each, and left unchanged."""
 import functools
-import importlib.util
-import os
 
-import numpy as np
+import kit_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@functools.lru_cache(maxsize=None)
-def gen():
-    spec = importlib.util.spec_from_file_location("make_golden_resize_many", os.path.join(ROOT, "tests", "golden", "make_golden_resize_many.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@functools.lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "resize_many.npz"), allow_pickle=False))
+gen = functools.partial(kit_golden.generator, "resize_many")
+fixture = functools.partial(kit_golden.fixture, "resize_many")
 
 
 @functools.lru_cache(maxsize=None)
@@ -30,9 +16,7 @@ def _expected_index():
 @functools.lru_cache(maxsize=None)
 def item(name, i):
     """[C, H, W] uint8 input of item i of case `name` (read-only: shared between tests)."""
-    x = np.ascontiguousarray(gen().item_input(gen().case(name), i))
-    x.setflags(write=False)
-    return x
+    return kit_golden.readonly(gen().item_input(gen().case(name), i))
 
 
 def expected(key):
@@ -48,13 +32,4 @@ def expected(key):
 def assert_matches_fixture(key, x_chw, got_hwc):
     """got_hwc [oH, oW, C] equals Pillow's output of fixture entry `key`: the input is the fixture's (CRC-32), the sampled pixels are
     Pillow's (they say where a mismatch lies) and the whole output has Pillow's CRC-32."""
-    g = gen()
-    incrc, outcrc, samples = expected(key)
-    assert g.crc(x_chw) == incrc, f"{key}: the regenerated input is not the fixture's"
-    got = np.ascontiguousarray(got_hwc)
-    px = got.reshape(-1, got.shape[-1])
-    idx = g.sample_pixels(len(px))
-    assert px[idx].shape == samples.shape, f"{key}: output shape {got.shape}"
-    bad = np.nonzero((px[idx] != samples).any(axis=1))[0]
-    assert bad.size == 0, f"{key}: {bad.size} of {len(idx)} sampled pixels differ, first at flat pixel {idx[bad[0]]}: {px[idx[bad[0]]]} != {samples[bad[0]]}"
-    assert g.crc(got) == outcrc, f"{key}: the sampled pixels match but the whole output's CRC-32 differs from Pillow's"
+    kit_golden.assert_sampled(key, gen(), *expected(key), x_chw, got_hwc)

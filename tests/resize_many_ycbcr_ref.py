@@ -3,28 +3,14 @@ Pillow (tests/golden/resize_many_ycbcr.npz), and a numpy restatement of the call
 Pillow's "L" resize that the placed tests use (resize_many_placed_ref.gen()'s resize_box_restated), then the table conversion.
 Not a test module."""
 import functools
-import importlib.util
-import os
 
 import numpy as np
 
+import kit_golden
 import resize_many_placed_ref as placed_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@functools.lru_cache(maxsize=None)
-def gen():
-    spec = importlib.util.spec_from_file_location("make_golden_resize_many_ycbcr",
-                                                  os.path.join(ROOT, "tests", "golden", "make_golden_resize_many_ycbcr.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@functools.lru_cache(maxsize=None)
-def fixture():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "resize_many_ycbcr.npz"), allow_pickle=False))
+gen = functools.partial(kit_golden.generator, "resize_many_ycbcr")
+fixture = functools.partial(kit_golden.fixture, "resize_many_ycbcr")
 
 
 def expected(name, f):

@@ -1,29 +1,19 @@
 """Straight-alpha (RGBA / LA) resizing without a GPU: the Pillow-made fixture, the premultiply / un-premultiply arithmetic the kernels
 use, argument checks of the Python surface and the C-ABI."""
 import ctypes
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kit_golden
 
-
-def _maker():
-    spec = importlib.util.spec_from_file_location("make_golden_alpha", os.path.join(ROOT, "tests", "golden", "make_golden_alpha.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-M = _maker()
+M = kit_golden.generator("alpha")
 
 
 @pytest.fixture(scope="module")
 def fx():
-    return np.load(os.path.join(ROOT, "tests", "golden", "alpha.npz"), allow_pickle=False)
+    return kit_golden.fixture("alpha")
 
 
 def test_fixture_inputs_regenerate(fx):

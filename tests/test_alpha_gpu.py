@@ -1,56 +1,31 @@
 """Straight-alpha (RGBA / LA) resizing on the GPU (-m gpu): bit-exact parity with PIL.Image.resize on every route (with the variant each
 route takes), every (colour, alpha) pair through the fused kernel, fused against the three-step fallback, strided views, a batch, and
 alpha=False unchanged.  Expected values come from tests/golden/alpha.npz (made by tests/golden/make_golden_alpha.py with Pillow)."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kit_golden
+import kit_gpu
+
 pytestmark = pytest.mark.gpu
 
 FUSED = ("fused_u8_nhwc_pil_alpha_v3", "fused_u8_nhwc_pil_alpha6_v3")
 FALLBACK = "alpha_3step"
 
 
-def _maker():
-    spec = importlib.util.spec_from_file_location("make_golden_alpha", os.path.join(ROOT, "tests", "golden", "make_golden_alpha.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-M = _maker()
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    return extension_interpolate
+M = kit_golden.generator("alpha")
+aa = kit_gpu.aa_fixture()
 
 
 @pytest.fixture(scope="module")
 def fx():
-    return np.load(os.path.join(ROOT, "tests", "golden", "alpha.npz"), allow_pickle=False)
+    return kit_golden.fixture("alpha")
 
 
 def _op(aa, name):
     return {"nearest": aa.nearest_forward, "linear": aa.linear_forward, "cubic": aa.cubic_forward, "hamming": aa.hamming_forward,
             "lanczos": aa.lanczos_forward}[name]
-
-
-def _to_gpu(img_hwc, channels_last):
-    t = torch.from_numpy(np.ascontiguousarray(img_hwc)[None]).cuda().permute(0, 3, 1, 2)
-    return t if channels_last else t.contiguous()
-
-
-def _hwc(y):
-    return y[0].permute(1, 2, 0).contiguous().cpu().numpy()
 
 
 # routes of channels_last RGBA cases that follow from their window widths and open output rows (the other cases take either)
@@ -71,10 +46,10 @@ def test_pillow_parity_every_case(aa, fx, name):
             assert M.crc(img) == in_crc, ("fixture input generator changed", case, c)
             for channels_last in (True, False):
                 _lib.load().aa_set_fused(1)
-                y = _op(aa, name)(_to_gpu(img, channels_last), [oh, ow], alpha=True)
+                y = _op(aa, name)(kit_gpu.image_gpu(img, channels_last), [oh, ow], alpha=True)
                 torch.cuda.synchronize()
                 variant = _lib.last_variant()
-                got = _hwc(y)
+                got = kit_gpu.hwc(y[0])
                 tag = (case, c, name, "nhwc" if channels_last else "nchw", variant)
                 if M.crc(got) != exp_crc:
                     pix = M.sample_pixels(oh, ow)
@@ -104,10 +79,10 @@ def test_every_colour_alpha_pair_through_the_fused_kernel(aa, fx):
     a = np.ones((256, 1), np.uint8) * np.arange(256, dtype=np.uint8)[None, :]
     small = np.stack([c, 255 - c, c ^ 0x5A, a], axis=-1)
     img = small.repeat(2, axis=0).repeat(2, axis=1)
-    y = aa.nearest_forward(_to_gpu(img, True), [256, 256], alpha=True)
+    y = aa.nearest_forward(kit_gpu.image_gpu(img, True), [256, 256], alpha=True)
     torch.cuda.synchronize()
     assert _lib.last_variant() == FUSED[0]
-    got = _hwc(y)
+    got = kit_gpu.hwc(y[0])
     pre, un = fx["premul"].astype(np.int64), fx["unpremul"]
     for ch in range(3):
         exp = un[pre[small[:, :, ch], a], a]
@@ -180,7 +155,7 @@ def test_batch_of_64(aa, fx):
     x = torch.from_numpy(imgs).cuda().permute(0, 3, 1, 2)
     y = aa.linear_forward(x, [oh, ow], alpha=True)
     assert _lib.last_variant() == FUSED[0]
-    assert M.crc(_hwc(y[:1])) == M.expected(fx, case, 4, "linear")[1]
+    assert M.crc(kit_gpu.hwc(y[0])) == M.expected(fx, case, 4, "linear")[1]
     for k in (1, 17, 40, 63):
         assert torch.equal(y[k:k + 1], aa.linear_forward(x[k:k + 1], [oh, ow], alpha=True)), k
 
@@ -191,7 +166,7 @@ def test_alpha_false_is_unchanged(aa, fx):
     for name in M.FILTERS:
         case, (h, w), (oh, ow), _, seed = M.CASES[0]
         img = M.make_image(h, w, 4, seed)
-        x = _to_gpu(img, True)
+        x = kit_gpu.image_gpu(img, True)
         y = _op(aa, name)(x, [oh, ow]).cpu().numpy()
         if name in oracle.FILTERS:  # (the oracle restates Pillow's bilinear, bicubic and box filters)
             exp = oracle.pil_resize_u8(name, np.ascontiguousarray(img.transpose(2, 0, 1))[None], (oh, ow), nthreads=4)
@@ -199,10 +174,10 @@ def test_alpha_false_is_unchanged(aa, fx):
         for ch in range(4):  # channels stay independent: each equals the channel resized on its own
             one = _op(aa, name)(x[:, ch:ch + 1].contiguous(), [oh, ow]).cpu().numpy()
             assert np.array_equal(y[:, ch:ch + 1], one), (name, ch)
-        ya = _hwc(_op(aa, name)(x, [oh, ow], alpha=True))
+        ya = kit_gpu.hwc(_op(aa, name)(x, [oh, ow], alpha=True)[0])
         assert M.crc(ya) == M.expected(fx, case, 4, name)[1], name
-        assert not np.array_equal(ya, _hwc(torch.from_numpy(y))), name
-    same = _to_gpu(M.make_image(24, 40, 4, 9), True)
+        assert not np.array_equal(ya, kit_gpu.hwc(torch.from_numpy(y)[0])), name
+    same = kit_gpu.image_gpu(M.make_image(24, 40, 4, 9), True)
     out = aa.linear_forward(same, [24, 40], alpha=True)
     assert torch.equal(out, same) and out.data_ptr() != same.data_ptr()
 

@@ -13,22 +13,15 @@ import pytest
 import torch
 
 import backward_ref as R
+import kit_gpu
 
 pytestmark = pytest.mark.gpu
 
 NP = {torch.float32: np.float32, torch.float64: np.float64}
 WORST = {}     # (dtype name, form) -> largest err / bound seen
 _DENSE = {}
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    yield extension_interpolate
-    print("\nbackward vs dense fp64 reference, worst err / bound:", {f"{k[0]}/{k[1]}": round(v, 4) for k, v in sorted(WORST.items())})
+aa = kit_gpu.aa_fixture(lambda: print("\nbackward vs dense fp64 reference, worst err / bound:",
+                                     {f"{k[0]}/{k[1]}": round(v, 4) for k, v in sorted(WORST.items())}))
 
 
 def _bwd(aa, name):
@@ -58,25 +51,6 @@ def _layout(g, cl):
     return g.contiguous(memory_format=torch.channels_last) if cl else g.contiguous()
 
 
-class _Knobs:
-    """set_fused / set_store_form for one block, restored on the way out."""
-
-    def __init__(self, fused=1, store=-1):
-        self.fused, self.store = fused, store
-
-    def __enter__(self):
-        from interpolate_antialiasing_amd import _lib
-
-        self.prev_fused = _lib.set_fused(self.fused)
-        self.prev_store = _lib.set_store_form(self.store)
-
-    def __exit__(self, *exc):
-        from interpolate_antialiasing_amd import _lib
-
-        _lib.set_fused(self.prev_fused)
-        _lib.set_store_form(self.prev_store)
-
-
 FORMS = {"gather_fused": (False, 1, -1), "gather_generic": (False, 0, -1), "gather_store1": (False, 1, 1), "atomic": (True, 1, -1)}
 
 
@@ -87,7 +61,7 @@ def _run_forms(aa, name, g, in_shape, ac, forms, gi, bnd, variants, tag):
     oh, ow = g.shape[2:]
     for form in forms:
         atomic, fused, store = FORMS[form]
-        with _Knobs(fused, store):
+        with kit_gpu.Knobs(fused, store):
             got = _bwd(aa, name)(g, [oh, ow], [n, c, h, w], ac, atomic=atomic)
             v = _lib.last_variant()
         variants.setdefault(form, set()).add(v)
@@ -327,7 +301,7 @@ def test_every_element_of_grad_input_is_written(aa, dt):
             return body.view(n, h, w, c).permute(0, 3, 1, 2) if cl else body.view(n, c, h, w)
 
         for fused in (1, 0):
-            with _Knobs(fused, -1):
+            with kit_gpu.Knobs(fused, -1):
                 trh, trw = tables.get_transposed_table(th).axis(), tables.get_transposed_table(tw).axis()
                 ws_bytes = L.aa_workspace_bytes(did, layout, n, c, oh, ow, h, w, ctypes.byref(trh), ctypes.byref(trw))
                 ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -374,7 +348,7 @@ def test_nonfinite_gradients_do_not_leak(aa, dt):
             g = torch.from_numpy(g_np).cuda()
             for form in ("gather_fused", "gather_generic"):
                 _, fused, store = FORMS[form]
-                with _Knobs(fused, store):
+                with kit_gpu.Knobs(fused, store):
                     got = _bwd(aa, name)(g, [oh, ow], [n, c, h, w], False).cpu().numpy()
                 tag = (name, (h, w), (oh, ow), form)
                 assert np.array_equal(np.isnan(got), np.isnan(gi)), ("NaN mask", tag, int(np.isnan(got).sum()), int(np.isnan(gi).sum()))
@@ -400,7 +374,7 @@ def test_nd_backward_vs_dense_reference(aa, dt):
             g_np = rng.standard_normal(lead + osizes).astype(NP[dt])
             gi, ab = R.backward_dense(mats, g_np)
             for fused in (1, 0):
-                with _Knobs(fused, -1):
+                with kit_gpu.Knobs(fused, -1):
                     got = fns[name](torch.from_numpy(g_np).cuda(), list(osizes), list(lead + sizes), ac)
                     seen.add(_lib.last_variant())
                 _judge(got, gi, R.bound(mats, ab, NP[dt]), dt, "nd_fused" if fused else "nd_generic", (name, sizes, osizes, ac))

@@ -11,30 +11,18 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import box_reduce_ref as ref  # noqa: E402
+import kit_gpu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 G = ref.gen()
+aa = kit_gpu.aa_fixture()
 BOX = {cs[0]: cs for cs in G.BOX_CASES}
 GAP = {cs[0]: cs for cs in G.GAP_CASES}
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    return extension_interpolate
 
 
 def _op(aa, name):
     return {"box": aa.nearest_forward, "linear": aa.linear_forward, "cubic": aa.cubic_forward, "hamming": aa.hamming_forward,
             "lanczos": aa.lanczos_forward}[name]
-
-
-def _gpu(x_nchw, channels_last):
-    t = torch.from_numpy(np.array(x_nchw, order="C")).cuda()
-    return t.contiguous(memory_format=torch.channels_last) if channels_last else t.contiguous()
 
 
 def _nhwc(y):
@@ -53,7 +41,7 @@ def test_box_equals_pillow(aa, name, flt):
     _, shape, seed, (oh, ow), box, _, alpha = BOX[name]
     x = ref.batch(shape, seed)
     for cl in _layouts(shape[1]):
-        y = _op(aa, flt)(_gpu(x, cl), [oh, ow], box=box, alpha=alpha)
+        y = _op(aa, flt)(kit_gpu.nchw_gpu(x, cl), [oh, ow], box=box, alpha=alpha)
         assert y.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
         ref.assert_matches_fixture(f"{name}/{flt}", x, _nhwc(y))
 
@@ -61,7 +49,7 @@ def test_box_equals_pillow(aa, name, flt):
 def test_wide_windows_take_the_generic_path(aa):
     """More than 136 taps: no fused kernel; the dense fallback copies the hull and runs the two launches."""
     _, shape, seed, (oh, ow), box, _, _ = BOX["b_wide"]
-    aa.cubic_forward(_gpu(ref.batch(shape, seed), True), [oh, ow], box=box)
+    aa.cubic_forward(kit_gpu.nchw_gpu(ref.batch(shape, seed), True), [oh, ow], box=box)
     assert not aa.last_variant().startswith("fused"), aa.last_variant()
 
 
@@ -73,7 +61,7 @@ def test_headline_shape_stays_fused(aa, flt):
 
     _, shape, seed, (oh, ow), box, _, _ = BOX["b_headline"]
     x = ref.batch(shape, seed)
-    t = _gpu(x, True)
+    t = kit_gpu.nchw_gpu(x, True)
     y = _op(aa, flt)(t, [oh, ow], box=box)
     variant = aa.last_variant()
     ref.assert_matches_fixture(f"b_headline/{flt}", x, _nhwc(y))
@@ -92,7 +80,7 @@ def test_full_box_is_the_plain_call(aa):
 
     x = ref.batch((2, 3, 97, 131), 31)
     for cl in (True, False):
-        t = _gpu(x, cl)
+        t = kit_gpu.nchw_gpu(x, cl)
         for flt in G.FILTER_NAMES:
             plain = _op(aa, flt)(t, [30, 40])
             v = aa.last_variant()
@@ -104,7 +92,7 @@ def test_full_box_is_the_plain_call(aa):
 
 
 def test_integer_box_of_the_output_size_is_a_crop(aa):
-    t = _gpu(ref.batch((2, 3, 97, 131), 31), True)
+    t = kit_gpu.nchw_gpu(ref.batch((2, 3, 97, 131), 31), True)
     y = aa.lanczos_forward(t, [30, 40], box=(11, 5, 51, 35))
     assert torch.equal(y, t[:, :, 5:35, 11:51]) and y.is_contiguous(memory_format=torch.channels_last)
 
@@ -112,7 +100,7 @@ def test_integer_box_of_the_output_size_is_a_crop(aa):
 def test_box_on_a_view_of_a_larger_tensor(aa):
     """The input itself a crop: the hull is a view of a view."""
     rng = np.random.default_rng(8)
-    big = _gpu(rng.integers(0, 256, (3, 3, 120, 160), dtype=np.uint8), True)
+    big = kit_gpu.nchw_gpu(rng.integers(0, 256, (3, 3, 120, 160), dtype=np.uint8), True)
     crop = big[1:, :, 9:106, 13:144]
     box = G.BOX1
     for flt in ("linear", "cubic"):
@@ -127,7 +115,7 @@ def test_box_on_an_axis_too_long_for_the_paired_table_build(aa):
     rng = np.random.default_rng(10)
     x = rng.integers(0, 256, (1, 1, 4, 40000), dtype=np.uint8)
     box = (10.5, 0, 39990.5, 4)
-    got = _nhwc(aa.linear_forward(_gpu(x, False), [4, 100], box=box))
+    got = _nhwc(aa.linear_forward(kit_gpu.nchw_gpu(x, False), [4, 100], box=box))
     want = G.resize_box_restated("linear", x[0].transpose(1, 2, 0), 4, 100, box)
     assert np.array_equal(got[0], want)
 
@@ -139,7 +127,7 @@ def test_box_on_a_view_no_kernel_reads(aa, monkeypatch):
     result keeps the hull's layout."""
     from interpolate_antialiasing_amd import _lib, boxmath
 
-    t = _gpu(ref.batch((2, 3, 97, 131), 31), False)
+    t = kit_gpu.nchw_gpu(ref.batch((2, 3, 97, 131), 31), False)
     flipped = t.flip(3)
     assert torch.equal(aa.cubic_forward(flipped, [30, 40], box=G.BOX1), aa.cubic_forward(flipped.contiguous(), [30, 40], box=G.BOX1))
     assert torch.equal(aa.reduce(flipped, (3, 5), (5, 7, 50, 36)), aa.reduce(flipped.contiguous(), (3, 5), (5, 7, 50, 36)))
@@ -161,7 +149,7 @@ def test_box_on_a_view_no_kernel_reads(aa, monkeypatch):
     assert torch.equal(y, want)
     for cl in (False, True):
         mf = torch.channels_last if cl else torch.contiguous_format
-        big = _gpu(ref.batch((2, 3, 120, 160), 32), cl)
+        big = kit_gpu.nchw_gpu(ref.batch((2, 3, 120, 160), 32), cl)
         crop = big[:, :, 9:106, 13:144]
         assert not crop.is_contiguous() and not crop.is_contiguous(memory_format=torch.channels_last)
         try:
@@ -179,7 +167,7 @@ def test_box_on_a_view_no_kernel_reads(aa, monkeypatch):
 def test_interpolate_aa_passes_box_and_gap(aa):
     from interpolate_antialiasing_amd.functional import interpolate_aa
 
-    t = _gpu(ref.batch((2, 3, 97, 131), 31), True)
+    t = kit_gpu.nchw_gpu(ref.batch((2, 3, 97, 131), 31), True)
     assert torch.equal(interpolate_aa(t, [30, 40], "bicubic", box=G.BOX1), aa.cubic_forward(t, [30, 40], box=G.BOX1))
     assert torch.equal(interpolate_aa(t, [10, 12], "bilinear", reducing_gap=2.0), aa.linear_forward(t, [10, 12], reducing_gap=2.0))
 
@@ -191,7 +179,7 @@ def test_box_tables_have_a_bounded_cache_of_their_own(aa):
 
     rng = np.random.default_rng(9)
     x = ref.batch((1, 3, 97, 131), 44)
-    t = _gpu(x, True)
+    t = kit_gpu.nchw_gpu(x, True)
     img = x[0].transpose(1, 2, 0)
     aa.cubic_forward(t, [30, 40], box=(1.5, 1.5, 100, 90))  # (warm: the library's own one-off allocations)
     torch.cuda.synchronize()
@@ -221,7 +209,7 @@ def test_reducing_gap_equals_pillow(aa, name, flt):
     _, shape, seed, (oh, ow), box, gap, _ = GAP[name]
     x = ref.batch(shape, seed)
     for cl in (True, False):
-        t = _gpu(x, cl)
+        t = kit_gpu.nchw_gpu(x, cl)
         y = _op(aa, flt)(t, [oh, ow], box=box, reducing_gap=gap)
         assert y.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
         ref.assert_matches_fixture(f"{name}/{flt}", x, _nhwc(y))

@@ -1,21 +1,15 @@
 """Hamming and Lanczos (Pillow's other two antialiasing filters): host-side checks that need no GPU."""
-import importlib.util
+import functools
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kit_golden
 
-
-def _restatement():
-    """tests/golden/make_golden_filters.py: the Python restatement of Pillow's coefficients (imports numpy and math only)."""
-    spec = importlib.util.spec_from_file_location("make_golden_filters", os.path.join(ROOT, "tests", "golden", "make_golden_filters.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+# tests/golden/make_golden_filters.py: the Python restatement of Pillow's coefficients (imports numpy and math only)
+_restatement = functools.partial(kit_golden.generator, "filters")
 
 
 def _f32_ksize(support, n_in, n_out, align_corners=False):
@@ -187,7 +181,7 @@ def test_fixture_matches_the_restatement():
     """tests/golden/filters.npz read through its packed-layout readers: tables equal the restated ones, every image and float input
     regenerates to the stored CRC-32, and Pillow's sampled output pixels equal the restated Pillow arithmetic."""
     m = _restatement()
-    fx = np.load(os.path.join(ROOT, "tests", "golden", "filters.npz"), allow_pickle=False)
+    fx = kit_golden.fixture("filters")
     for name in ("hamming", "lanczos"):
         for n_in, n_out in m.TABLE_PAIRS:
             if n_out > 2000:

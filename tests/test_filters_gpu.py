@@ -1,41 +1,25 @@
 """Hamming and Lanczos on the GPU (-m gpu): weight tables, Pillow parity of the uint8 kernels on every route (with the variant each
 shape takes), the harness / float32-output modes, float dtypes, the adjoint, the N-d front-ends.  Expected values come from
 tests/golden/filters.npz (made by tests/golden/make_golden_filters.py with Pillow)."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kit_golden
+import kit_gpu
+
 pytestmark = pytest.mark.gpu
 
 FILTER_NAMES = ("hamming", "lanczos")
 
 
-def _restatement():
-    spec = importlib.util.spec_from_file_location("make_golden_filters", os.path.join(ROOT, "tests", "golden", "make_golden_filters.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-M = _restatement()
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    return extension_interpolate
+M = kit_golden.generator("filters")
+aa = kit_gpu.aa_fixture()
 
 
 @pytest.fixture(scope="module")
 def fx():
-    return np.load(os.path.join(ROOT, "tests", "golden", "filters.npz"), allow_pickle=False)
+    return kit_golden.fixture("filters")
 
 
 def _fwd(aa, name):
@@ -116,15 +100,6 @@ def _expected_variant(case, c, planar):
     return "fused_u8_nhwc_pil_v3"
 
 
-def _to_gpu(img, planar):
-    t = torch.from_numpy(img).cuda().permute(2, 0, 1).unsqueeze(0)  # [1, C, H, W] channels_last storage
-    return t.contiguous() if planar else t
-
-
-def _hwc(y):
-    return y[0].permute(1, 2, 0).contiguous().cpu().numpy()
-
-
 def _u8_runs():
     for case, (h, w), (oh, ow), chans, seed in M.U8_CASES:
         for c in chans:
@@ -143,15 +118,15 @@ def test_u8_pillow_parity_every_route(aa, fx, name):
         img = M.make_image(h, w, c, seed)
         in_crc, out_crc, sample = M.u8_expected(fx, case, c, name)
         assert M.crc(img) == in_crc, ("fixture image generator changed", case, c)
-        x = _to_gpu(img, planar)
-        y = _hwc(f(x, [oh, ow]))
+        x = kit_gpu.image_gpu(img, not planar)
+        y = kit_gpu.hwc(f(x, [oh, ow])[0])
         variant = _lib.last_variant()
         assert np.array_equal(y.reshape(-1, c)[M.sample_pixels(oh, ow)], sample), (name, case, c, planar, variant)
         assert M.crc(y) == out_crc, (name, case, c, planar, variant)
         assert variant == _expected_variant(case, c, planar), (name, case, c, planar, variant)
         prev = _lib.set_fused(0)
         try:
-            yg = _hwc(f(x, [oh, ow]))
+            yg = kit_gpu.hwc(f(x, [oh, ow])[0])
             assert _lib.last_variant().startswith("generic"), _lib.last_variant()
         finally:
             _lib.set_fused(prev)
@@ -171,7 +146,7 @@ def test_u8_pillow_parity_on_a_crop_view(aa, fx, planar):
         x = big.permute(0, 3, 1, 2).contiguous()[:, :, 7:1087, 13:1933]
     assert not x.is_contiguous() and not x.is_contiguous(memory_format=torch.channels_last)
     for name in FILTER_NAMES:
-        y = _hwc(_fwd(aa, name)(x, [720, 1280]))
+        y = kit_gpu.hwc(_fwd(aa, name)(x, [720, 1280])[0])
         assert M.crc(y) == M.u8_expected(fx, "hd_720x1280", 3, name)[1], (name, planar, _lib.last_variant())
         assert _lib.last_variant() == ("fused_u8_planar_pil_v3" if planar else "fused_u8_nhwc_pil_v3"), _lib.last_variant()
 
@@ -189,7 +164,7 @@ def test_u8_harness_and_to_f32_lanczos(aa):
     cases = {cs[0]: cs for cs in M.U8_CASES}
     for case, c, planar in NARROW:
         _, (h, w), (oh, ow), _, seed = cases[case]
-        x = _to_gpu(M.make_image(h, w, c, seed), planar)
+        x = kit_gpu.image_gpu(M.make_image(h, w, c, seed), not planar)
         yh = aa.lanczos_forward(x, [oh, ow], uint8_mode="harness")
         vh = _lib.last_variant()
         assert not vh.startswith("generic"), (case, c, planar, vh)

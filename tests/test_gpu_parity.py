@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import kit_gpu
 import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,26 +20,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 FILTS = ("linear", "cubic", "box")
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    return extension_interpolate
+aa = kit_gpu.aa_fixture()
 
 
 def _fn(aa, filt):
     return {"linear": aa.linear_forward, "cubic": aa.cubic_forward, "box": aa.nearest_forward}[filt]
-
-
-def _gpu(a, channels_last=False):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    if channels_last:
-        t = t.contiguous(memory_format=torch.channels_last)
-    return t
 
 
 # ------------------------------------------------------------------------------------------------ tables
@@ -180,7 +166,7 @@ def test_forward_vs_reference_golden(aa, golden_forward, case, channels_last):
     for filt in FILTS:
         for dt in ("f32", "f64"):
             xin = x if dt == "f32" else x.astype(np.float64)
-            y = _fn(aa, filt)(_gpu(xin, channels_last), size, ac)
+            y = _fn(aa, filt)(kit_gpu.nchw_gpu(xin, channels_last), size, ac)
             exp = golden_forward[f"{case}_{filt}_{dt}"]
             assert y.shape == exp.shape
             if channels_last and x.shape[1] > 1:
@@ -195,9 +181,9 @@ def test_forward_vs_reference_golden(aa, golden_forward, case, channels_last):
 def test_forward_known_answer_and_headline_fp32(aa, golden_kat):
     rgb = golden_kat["rgb"]
     x = np.ascontiguousarray(rgb.transpose(2, 0, 1)[None]).astype(np.float32)  # config 0: fp32 NCHW [1,3,438,906]
-    y = aa.linear_forward(_gpu(x), [196, 320], False).cpu().numpy()
+    y = aa.linear_forward(kit_gpu.nchw_gpu(x), [196, 320], False).cpu().numpy()
     assert np.array_equal(y, golden_kat["lin_320x196_f32"])
-    yc = aa.cubic_forward(_gpu(x), [196, 320], False).cpu().numpy()
+    yc = aa.cubic_forward(kit_gpu.nchw_gpu(x), [196, 320], False).cpu().numpy()
     assert np.array_equal(yc, golden_kat["cubic_320x196_f32"])
     # the reference's committed PNG = truncation of the fp32 result (test.py:75)
     assert np.array_equal(y[0].astype(np.uint8).transpose(1, 2, 0), golden_kat["lin_320x196_u8"])
@@ -211,7 +197,7 @@ def test_forward_random_vs_oracle(aa, shape, size):
     for filt in FILTS:
         for cl in (False, True):
             exp = oracle.forward(filt, x, size, nthreads=8)
-            got = _fn(aa, filt)(_gpu(x, cl), list(size), False).cpu().numpy()
+            got = _fn(aa, filt)(kit_gpu.nchw_gpu(x, cl), list(size), False).cpu().numpy()
             assert np.array_equal(got, exp), (filt, cl, float(np.abs(got - exp).max()))
 
 
@@ -270,10 +256,10 @@ def test_u8_random_vs_oracle(aa, shape, size):
         for cl in (False, True):
             xin = oracle.as_channels_last(x) if cl else x
             exp = oracle.pil_resize_u8(filt, xin, size, nthreads=8)
-            got = _fn(aa, filt)(_gpu(x, cl), list(size), False, uint8_mode="pil").cpu().numpy()
+            got = _fn(aa, filt)(kit_gpu.nchw_gpu(x, cl), list(size), False, uint8_mode="pil").cpu().numpy()
             assert np.array_equal(got, exp), (filt, cl)
             exph = oracle.harness_u8(filt, xin, size, nthreads=8)
-            goth = _fn(aa, filt)(_gpu(x, cl), list(size), False, uint8_mode="harness").cpu().numpy()
+            goth = _fn(aa, filt)(kit_gpu.nchw_gpu(x, cl), list(size), False, uint8_mode="harness").cpu().numpy()
             assert np.array_equal(goth, exph), (filt, cl, "harness")
 
 
@@ -286,7 +272,7 @@ def test_u8_extremes(aa):
     yy, xx = np.meshgrid(np.arange(64), np.arange(80), indexing="ij")
     cb = (((yy // 3 + xx // 3) % 2) * 255).astype(np.uint8)[None, None].repeat(3, 1)
     exp = oracle.pil_resize_u8("cubic", cb, (23, 31))
-    got = aa.cubic_forward(_gpu(cb), [23, 31]).cpu().numpy()
+    got = aa.cubic_forward(kit_gpu.nchw_gpu(cb), [23, 31]).cpu().numpy()
     assert np.array_equal(got, exp)
 
 
@@ -342,11 +328,11 @@ def test_backward_true_adjoint_golden(aa, golden_backward, case, atomic):
     n, c, oh, ow = go.shape
     for filt, bw in (("linear", aa.linear_backward), ("cubic", aa.cubic_backward)):
         exp = golden_backward[f"{case}_{filt}_gi"]  # fp64 autograd of F.interpolate(antialias=True)
-        g64 = bw(_gpu(go), [oh, ow], [n, c, h, w], False, atomic=atomic).cpu().numpy()
+        g64 = bw(kit_gpu.nchw_gpu(go), [oh, ow], [n, c, h, w], False, atomic=atomic).cpu().numpy()
         assert np.abs(g64 - exp).max() < 1e-11
-        g32 = bw(_gpu(go.astype(np.float32)), [oh, ow], [n, c, h, w], False, atomic=atomic).cpu().numpy()
+        g32 = bw(kit_gpu.nchw_gpu(go.astype(np.float32)), [oh, ow], [n, c, h, w], False, atomic=atomic).cpu().numpy()
         np.testing.assert_allclose(g32, exp, rtol=1e-4, atol=1e-4)
-        gcl = bw(_gpu(go, True), [oh, ow], [n, c, h, w], False, atomic=atomic)
+        gcl = bw(kit_gpu.nchw_gpu(go, True), [oh, ow], [n, c, h, w], False, atomic=atomic)
         assert np.abs(gcl.cpu().numpy() - exp).max() < 1e-11
     # and NOT the header's non-AA backward
     assert np.abs(g32 - golden_backward[f"{case}_legacy_nonaa_gi"]).max() > 0.1
@@ -582,16 +568,6 @@ def test_half_precision_is_rounded_fp32(aa, dtype, channels_last):
             assert torch.equal(y1[:1].cpu().view(torch.int16), exp1.view(torch.int16)), (filt, shape, size)
 
 
-def _oracle_axis(filt, a, axis, n_out, align_corners=False):
-    """One separable pass along `axis` with the 2-D oracle: the axis becomes W of an [outer, inner, 1, n] image (the
-    H pass is 1 -> 1, a single tap of weight exactly 1)."""
-    moved = np.moveaxis(a, axis, -1)
-    lead = moved.shape[:-1]
-    img = np.ascontiguousarray(moved.reshape(-1, 1, 1, moved.shape[-1]))
-    out = oracle.forward(filt, img, (1, n_out), align_corners)
-    return np.moveaxis(out.reshape(*lead, n_out), -1, axis)
-
-
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
 def test_1d_and_3d_front_ends(aa, dt):
     """NCL and NCDHW: the reference's driver resamples the LAST axis first (s2.2:658); the oracle is its
@@ -600,23 +576,23 @@ def test_1d_and_3d_front_ends(aa, dt):
     x1 = (rng.random((3, 4, 97)) * 255).astype(dt)
     for filt, fn in (("linear", aa.linear_forward_nd), ("cubic", aa.cubic_forward_nd), ("box", aa.nearest_forward_nd)):
         for n_out in (31, 97, 150):
-            got = fn(_gpu(x1), [n_out]).cpu().numpy()
-            assert np.array_equal(got, _oracle_axis(filt, x1, 2, n_out)), (filt, n_out)
+            got = fn(kit_gpu.nchw_gpu(x1), [n_out]).cpu().numpy()
+            assert np.array_equal(got, kit_gpu.oracle_axis(filt, x1, 2, n_out)), (filt, n_out)
     x3 = (rng.random((2, 3, 19, 23, 29)) * 255).astype(dt)
     for filt, fn in (("linear", aa.linear_forward_nd), ("cubic", aa.cubic_forward_nd)):
         for size in ((7, 9, 11), (19, 40, 10), (30, 23, 29)):
             exp = x3
             for axis in (4, 3, 2):
-                exp = _oracle_axis(filt, exp, axis, size[axis - 2])
-            got = fn(_gpu(x3), list(size)).cpu().numpy()
+                exp = kit_gpu.oracle_axis(filt, exp, axis, size[axis - 2])
+            got = fn(kit_gpu.nchw_gpu(x3), list(size)).cpu().numpy()
             assert got.shape == (2, 3) + size and np.array_equal(got, exp), (filt, size)
     # align_corners only changes the scale (s2.2:314-315); 4-D input goes to the 2-D path; functional wrapper
-    got = aa.linear_forward_nd(_gpu(x1), [40], True).cpu().numpy()
-    assert np.array_equal(got, _oracle_axis("linear", x1, 2, 40, True))
+    got = aa.linear_forward_nd(kit_gpu.nchw_gpu(x1), [40], True).cpu().numpy()
+    assert np.array_equal(got, kit_gpu.oracle_axis("linear", x1, 2, 40, True))
     x2 = (rng.random((1, 2, 20, 30)) * 255).astype(dt)
-    assert np.array_equal(aa.linear_forward_nd(_gpu(x2), [7, 9]).cpu().numpy(), oracle.forward("linear", x2, (7, 9)))
+    assert np.array_equal(aa.linear_forward_nd(kit_gpu.nchw_gpu(x2), [7, 9]).cpu().numpy(), oracle.forward("linear", x2, (7, 9)))
     from interpolate_antialiasing_amd.functional import interpolate_aa
-    assert np.array_equal(interpolate_aa(_gpu(x3), (7, 9, 11), "trilinear").cpu().numpy(), aa.linear_forward_nd(_gpu(x3), [7, 9, 11]).cpu().numpy())
+    assert np.array_equal(interpolate_aa(kit_gpu.nchw_gpu(x3), (7, 9, 11), "trilinear").cpu().numpy(), aa.linear_forward_nd(kit_gpu.nchw_gpu(x3), [7, 9, 11]).cpu().numpy())
 
 
 def test_nd_passes_take_the_fused_kernels(aa):
@@ -639,7 +615,7 @@ def test_nd_passes_take_the_fused_kernels(aa):
             _lib.set_fused(1)
         assert v.startswith("fused"), (v, tuple(x.shape), size)
         assert torch.equal(y1, y0), (tuple(x.shape), size)
-    exp = _oracle_axis("linear", x1[:1].cpu().numpy(), 2, 1300)
+    exp = kit_gpu.oracle_axis("linear", x1[:1].cpu().numpy(), 2, 1300)
     assert np.array_equal(aa.linear_forward_nd(x1[:1], [1300]).cpu().numpy(), exp)
     # passes that would NOT be one fused launch go to the single-axis kernel (one launch, no workspace), never to the two-launch path
     # with an identity pass: the fused kernels switched off, fp64 with growing sizes (no fused kernel), rows too short for the
@@ -653,12 +629,12 @@ def test_nd_passes_take_the_fused_kernels(aa):
         finally:
             _lib.set_fused(1)
         assert v == "generic_axis", (v, tuple(x.shape), size, fused)
-        assert np.array_equal(y[:1].cpu().numpy(), _oracle_axis("linear", x[:1].cpu().numpy(), 2, size[0]))
+        assert np.array_equal(y[:1].cpu().numpy(), kit_gpu.oracle_axis("linear", x[:1].cpu().numpy(), 2, size[0]))
     xd = torch.rand(1, 2, 40, 60, 70, device="cuda", dtype=torch.float64)  # the depth axis GROWS: fp64 has no fused kernel for growing heights
     yd = aa.linear_forward_nd(xd, [50, 60, 70])
     # (passes run last axis first: W and H keep their size = identity passes through the fused kernel, then the depth pass declines)
     assert _lib.last_variant() == "generic_axis", _lib.last_variant()
-    assert np.array_equal(yd.cpu().numpy(), _oracle_axis("linear", xd.cpu().numpy(), 2, 50))
+    assert np.array_equal(yd.cpu().numpy(), kit_gpu.oracle_axis("linear", xd.cpu().numpy(), 2, 50))
     g = torch.randn(4, 3, 1300, device="cuda", dtype=torch.float64)
     try:
         _lib.set_fused(1)
@@ -748,7 +724,7 @@ def test_explicit_scale_factors(aa):
 
         mid = apply(x, tabs[1], ow)                                # W pass first (s2.2:658)
         exp = np.swapaxes(apply(np.swapaxes(mid, 2, 3), tabs[0], oh), 2, 3)
-        got = _fn(aa, filt)(_gpu(x), [oh, ow], False, scale_factors=[sh, sw]).cpu().numpy()
+        got = _fn(aa, filt)(kit_gpu.nchw_gpu(x), [oh, ow], False, scale_factors=[sh, sw]).cpu().numpy()
         assert np.array_equal(got, exp), filt
     with pytest.raises(NotImplementedError, match="no scale factors"):
         aa.linear_forward(torch.zeros(1, 3, 8, 8, dtype=torch.uint8, device="cuda"), [4, 4], scale_factors=[0.5, 0.5])
@@ -833,11 +809,11 @@ def test_harness_five_sizes_vs_pil(aa, golden_kat, golden_harness, mode, filt):
         assert np.array_equal(r["proto"], exp), (w, h, r["variant"])
         # the shim's fused form of the same semantics (uint8 in, uint8 out) in both layouts
         for cl in (False, True):
-            y = fn(_gpu(chw, cl), [h, w], False, uint8_mode="harness")
+            y = fn(kit_gpu.nchw_gpu(chw, cl), [h, w], False, uint8_mode="harness")
             assert np.array_equal(y[0].permute(1, 2, 0).cpu().numpy(), exp), (w, h, cl)
         p = harness.evaluate(rgb, (w, h), mode, "pil", pil_dn=pil)
         assert p["max"] == 0.0 and np.array_equal(p["proto"], pil), (w, h, p["variant"])
-        ycl = fn(_gpu(chw, True), [h, w], False)  # channels_last = what PIL itself holds (HWC)
+        ycl = fn(kit_gpu.nchw_gpu(chw, True), [h, w], False)  # channels_last = what PIL itself holds (HWC)
         assert np.array_equal(ycl[0].permute(1, 2, 0).cpu().numpy(), pil), (w, h)
 
 
@@ -1360,19 +1336,19 @@ def test_fuzz_vs_oracle_small(aa):
         if kind == 0:
             x = (rng.random((n, c, h, w)) * 300 - 40).astype(np.float32)
             exp = oracle.forward(filt, x, (oh, ow))
-            got = _fn(aa, filt)(_gpu(x, cl), [oh, ow]).cpu().numpy()
+            got = _fn(aa, filt)(kit_gpu.nchw_gpu(x, cl), [oh, ow]).cpu().numpy()
         elif kind == 1:
             x = (rng.random((n, c, h, w)) * 300 - 40).astype(np.float64)
             exp = oracle.forward(filt, x, (oh, ow))
-            got = _fn(aa, filt)(_gpu(x, cl), [oh, ow]).cpu().numpy()
+            got = _fn(aa, filt)(kit_gpu.nchw_gpu(x, cl), [oh, ow]).cpu().numpy()
         elif kind == 2:
             x = rng.integers(0, 256, (n, c, h, w), dtype=np.uint8)
             exp = oracle.pil_resize_u8(filt, x, (oh, ow))
-            got = _fn(aa, filt)(_gpu(x, cl), [oh, ow]).cpu().numpy()
+            got = _fn(aa, filt)(kit_gpu.nchw_gpu(x, cl), [oh, ow]).cpu().numpy()
         else:
             x = rng.integers(0, 256, (n, c, h, w), dtype=np.uint8)
             exp = oracle.harness_u8(filt, x, (oh, ow))
-            got = _fn(aa, filt)(_gpu(x, cl), [oh, ow], uint8_mode="harness").cpu().numpy()
+            got = _fn(aa, filt)(kit_gpu.nchw_gpu(x, cl), [oh, ow], uint8_mode="harness").cpu().numpy()
         assert np.array_equal(got, exp), (it, kind, filt, (n, c, h, w), (oh, ow), cl)
 
 
@@ -1405,15 +1381,15 @@ def test_generic_wide_windows_vs_oracle(aa):
         f = _fn(aa, filt)
         xf = (rng.random((n, c, h, w)) * 300 - 40).astype(np.float32)
         xu = rng.integers(0, 256, (n, c, h, w), dtype=np.uint8)
-        got = f(_gpu(xf, cl), [oh, ow])
+        got = f(kit_gpu.nchw_gpu(xf, cl), [oh, ow])
         generic += _lib.last_variant().startswith("generic")
         assert np.array_equal(got.cpu().numpy(), oracle.forward(filt, xf, (oh, ow))), ("f32", c, cl, filt, (n, h, w), (oh, ow))
         xd = xf.astype(np.float64) * 1.000001
-        assert np.array_equal(f(_gpu(xd, cl), [oh, ow]).cpu().numpy(), oracle.forward(filt, xd, (oh, ow))), ("f64", c, cl, filt)
-        got = f(_gpu(xu, cl), [oh, ow])
+        assert np.array_equal(f(kit_gpu.nchw_gpu(xd, cl), [oh, ow]).cpu().numpy(), oracle.forward(filt, xd, (oh, ow))), ("f64", c, cl, filt)
+        got = f(kit_gpu.nchw_gpu(xu, cl), [oh, ow])
         generic += _lib.last_variant().startswith("generic")
         assert np.array_equal(got.cpu().numpy(), oracle.pil_resize_u8(filt, xu, (oh, ow))), ("pil", c, cl, filt, (n, h, w), (oh, ow))
-        got = f(_gpu(xu, cl), [oh, ow], uint8_mode="harness")
+        got = f(kit_gpu.nchw_gpu(xu, cl), [oh, ow], uint8_mode="harness")
         assert np.array_equal(got.cpu().numpy(), oracle.harness_u8(filt, xu, (oh, ow))), ("harness", c, cl, filt)
         for dt in (torch.float16, torch.bfloat16):  # 16-bit floats: fp32 arithmetic on the widened input, one rounding at the end
             xh = torch.from_numpy(xf).to(dt)
@@ -1450,16 +1426,16 @@ def test_u8_growing_heights_take_the_fused_gather_form(aa):
     for c, cl, filt, (n, h, w), (oh, ow) in cases:
         f = _fn(aa, filt)
         x = rng.integers(0, 256, (n, c, h, w), dtype=np.uint8)
-        got = f(_gpu(x, cl), [oh, ow])
+        got = f(kit_gpu.nchw_gpu(x, cl), [oh, ow])
         v = _lib.last_variant()
         fused += v.endswith("_v3")
         assert np.array_equal(got.cpu().numpy(), oracle.pil_resize_u8(filt, x, (oh, ow))), ("pil", v, c, cl, filt, (n, h, w), (oh, ow))
-        got = f(_gpu(x, cl), [oh, ow], uint8_mode="harness")
+        got = f(kit_gpu.nchw_gpu(x, cl), [oh, ow], uint8_mode="harness")
         v = _lib.last_variant()
         fused += v.endswith("_v3")
         assert np.array_equal(got.cpu().numpy(), oracle.harness_u8(filt, x, (oh, ow))), ("harness", v, c, cl, filt, (n, h, w), (oh, ow))
         if c in (3, 4) and cl:  # decode-adjacent conversion: uint8 HWC in, float32 NCHW out == the oracle's fp32 forward
-            got = f(_gpu(x, cl), [oh, ow], out_dtype=torch.float32, out_format="nchw")
+            got = f(kit_gpu.nchw_gpu(x, cl), [oh, ow], out_dtype=torch.float32, out_format="nchw")
             exp = oracle.forward(filt, x.astype(np.float32), (oh, ow))
             assert np.array_equal(got.cpu().numpy(), exp), ("to_f32", _lib.last_variant(), c, filt)
     assert fused >= 18, fused
@@ -1529,7 +1505,7 @@ def test_fast_precision_mode_is_within_tolerance(aa, golden_forward):
                               ("cubic", (2, 3, 61, 53), (17, 23)), ("linear", (2, 3, 100, 300), (37, 128))):
         x = (rng.random(shape, dtype=np.float32) * 255).astype(np.float32)
         exp = oracle.forward(filt, x, size, nthreads=8)
-        xt = _gpu(x)
+        xt = kit_gpu.nchw_gpu(x)
         y_exact = _fn(aa, filt)(xt, list(size))
         assert np.array_equal(y_exact.cpu().numpy(), exp), (filt, shape)
         y_fast = _fn(aa, filt)(xt, list(size), precision="fast")
@@ -1552,12 +1528,12 @@ def test_fast_precision_mode_is_within_tolerance(aa, golden_forward):
         ac = bool(golden_forward[f"{case}_align"])
         for filt in FILTS:
             exp = golden_forward[f"{case}_{filt}_f32"]
-            got = _fn(aa, filt)(_gpu(x), size, ac, precision="fast").cpu().numpy()
+            got = _fn(aa, filt)(kit_gpu.nchw_gpu(x), size, ac, precision="fast").cpu().numpy()
             np.testing.assert_allclose(got, exp, rtol=1e-4, atol=1e-4 * max(1.0, float(np.abs(exp).max())))
             n += 1
     assert n >= 15
     # layouts / dtypes without a tolerance kernel run the exact ones (always within tolerance), uint8 ignores the flag
-    xcl = _gpu((rng.random((2, 3, 120, 200), dtype=np.float32) * 255).astype(np.float32), channels_last=True)
+    xcl = kit_gpu.nchw_gpu((rng.random((2, 3, 120, 200), dtype=np.float32) * 255).astype(np.float32), channels_last=True)
     assert torch.equal(aa.linear_forward(xcl, [50, 80], precision="fast"), aa.linear_forward(xcl, [50, 80]))
     xd = torch.rand(1, 2, 90, 130, device="cuda", dtype=torch.float64)
     assert torch.equal(aa.linear_forward(xd, [40, 60], precision="fast"), aa.linear_forward(xd, [40, 60]))
@@ -1582,7 +1558,7 @@ def test_fast_precision_mode_is_within_tolerance(aa, golden_forward):
     # non-finite behaviour
     x = (rng.random((1, 1, 120, 400), dtype=np.float32) * 255).astype(np.float32)
     x[0, 0, 60, 200] = np.nan
-    xt = _gpu(x)
+    xt = kit_gpu.nchw_gpu(x)
     ne = torch.isnan(aa.linear_forward(xt, [50, 100])).cpu().numpy()[0, 0]
     nf = torch.isnan(aa.linear_forward(xt, [50, 100], precision="fast")).cpu().numpy()[0, 0]
     assert ne.any() and (nf | ~ne).all(), "fast mode must poison at least the outputs exact mode poisons"

@@ -16,8 +16,6 @@ and that the kernel family expected for the case really ran (last_variant; for t
 name, the table figures the route follows from).  Organised by store mechanism and buffer, at the smallest shapes where each exists.
 reduce and resize_many* do not report a variant: their cases are pinned by their arguments alone."""
 import functools
-import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -26,66 +24,24 @@ import torch
 import backward_ref as R
 import box_reduce_ref as BR
 import guard_ref as G
+import kit_golden
+import kit_gpu
 import oracle
 import resize_many_ref as MR
+from kit_golden import MEAN, MODE, STD
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEADS = [0, 1]
 HALVES = (torch.float16, torch.bfloat16)
 TAG = {torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32", torch.float64: "f64"}
 FLOATS = [torch.float32, torch.float16, torch.bfloat16, torch.float64]
-MEAN, STD = [123.675, 116.28, 103.53, 127.5], [58.395, 57.12, 57.375, 64.0]
 SEEN = {}  # group -> variants that ran, printed at the end of the module
 BRG = BR.gen()
 MG = MR.gen()
-
-
-def _alpha_maker():
-    spec = importlib.util.spec_from_file_location("make_golden_alpha", os.path.join(ROOT, "tests", "golden", "make_golden_alpha.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-AM = _alpha_maker()
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    yield extension_interpolate
-    print("\nguard sweep, variants that ran:", {k: sorted(v) for k, v in sorted(SEEN.items())})
-
-
-@pytest.fixture(scope="module")
-def lib(aa):
-    from interpolate_antialiasing_amd import _lib
-
-    return _lib
-
-
-class _Knobs:
-    """set_fused / set_store_form / set_plane_groups for one block, restored on the way out."""
-
-    def __init__(self, fused=1, store=-1, groups=1):
-        self.want = (fused, store, groups)
-
-    def __enter__(self):
-        from interpolate_antialiasing_amd import _lib
-
-        self.prev = (_lib.set_fused(self.want[0]), _lib.set_store_form(self.want[1]), _lib.set_plane_groups(self.want[2]))
-
-    def __exit__(self, *exc):
-        from interpolate_antialiasing_amd import _lib
-
-        _lib.set_fused(self.prev[0])
-        _lib.set_store_form(self.prev[1])
-        _lib.set_plane_groups(self.prev[2])
+AM = kit_golden.generator("alpha")
+aa = kit_gpu.aa_fixture(lambda: print("\nguard sweep, variants that ran:", {k: sorted(v) for k, v in sorted(SEEN.items())}))
+lib = kit_gpu.lib_fixture()
 
 
 def _fwd(aa, filt):
@@ -95,11 +51,6 @@ def _fwd(aa, filt):
 
 def _bwd(aa, filt):
     return {"linear": aa.linear_backward, "cubic": aa.cubic_backward, "lanczos": aa.lanczos_backward}[filt]
-
-
-def _gpu(a, channels_last=False):
-    t = torch.from_numpy(np.array(a, order="C")).cuda()  # (a copy: the cached inputs are read-only)
-    return t.contiguous(memory_format=torch.channels_last) if channels_last else t
 
 
 @functools.lru_cache(maxsize=None)
@@ -114,20 +65,6 @@ def _f32(shape, seed):
     x = (np.random.default_rng(seed).random(shape, dtype=np.float32) * 255).astype(np.float32)
     x.setflags(write=False)
     return x
-
-
-def _bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def _assert_bits(got, want, what):
-    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), (what, got.dtype, tuple(got.shape), want.dtype, tuple(want.shape))
-    a, b = _bits(got), _bits(want)
-    if not torch.equal(a, b):
-        bad = (a != b).nonzero()
-        raise AssertionError(f"{what}: {len(bad)} of {a.numel()} elements differ from the reference, first at {bad[0].tolist()}: "
-                             f"{got.cpu()[tuple(bad[0])].item()} != {want[tuple(bad[0])].item()}")
 
 
 @functools.lru_cache(maxsize=None)
@@ -167,15 +104,12 @@ def _guarded(monkeypatch, call, lead, group, variant=None, placed=True, flat_at_
     for fill in (0xFF, 0x00):
         with G.guarded(monkeypatch, lead, fill) as rec:
             try:
-                y = call()
-                v = _lib.last_variant()
-                rec.check()  # (a)
+                with kit_gpu.gpu_error_ends_the_session(f"{tag}, lead {lead}"):
+                    y = call()
+                    v = _lib.last_variant()
+                    rec.check()  # (a)
             except G.GuardViolation as e:
                 raise AssertionError(f"{tag}, lead {lead}, variant {v}: {e}") from None
-            except RuntimeError as e:
-                if not isinstance(e, _lib.AAInterpError) and ("HIP error" in str(e) or "illegal memory access" in str(e)):
-                    pytest.exit(f"the GPU reported an error in {tag}, lead {lead}; nothing more is launched: {e}", returncode=3)
-                raise
         if placed:
             _placed(rec, y, lead)
         assert sum(r.flat for r in rec.records) >= flat_at_least, (tag, [repr(r) for r in rec.records])
@@ -268,13 +202,13 @@ U8_CASES = [
 def test_fused_uint8_pillow_arithmetic(aa, lib, monkeypatch, case, lead):
     name, c, cl, filt, (n, h, w), (oh, ow), route, knobs = case
     shape = (n, c, h, w)
-    x = _gpu(_u8(shape, 11), cl)
+    x = kit_gpu.nchw_gpu(_u8(shape, 11), cl)
     want = "fused_u8_nhwc_pil" if route == "V1" else ("fused_u8_nhwc_pil_v3" if cl else "fused_u8_planar_pil_v3")
     _assert_route(lib, route, filt, h, w, oh, ow, name)
-    with _Knobs(**knobs):
+    with kit_gpu.Knobs(**knobs):
         y, v, _ = _guarded(monkeypatch, lambda: _fwd(aa, filt)(x, [oh, ow]), lead, "1 fused uint8", want, flat_at_least=2, tag=name)
     assert y.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
-    _assert_bits(y, _pil_ref(filt, shape, 11, (oh, ow)), (name, lead, v))
+    kit_gpu.assert_bits(y, _pil_ref(filt, shape, 11, (oh, ow)), (name, lead, v))
 
 
 # ------------------------------------------------------------------------------------------------ 2. straight alpha
@@ -293,7 +227,7 @@ def test_straight_alpha(aa, lib, monkeypatch, case, lead):
     name, c, cl, filt, want, route = case
     (h, w), (oh, ow), seed = next((cs[1], cs[2], cs[4]) for cs in AM.CASES if cs[0] == name)
     img = AM.make_image(h, w, c, seed)
-    fx = np.load(os.path.join(ROOT, "tests", "golden", "alpha.npz"), allow_pickle=False)
+    fx = kit_golden.fixture("alpha")
     in_crc, exp_crc, exp_samples = AM.expected(fx, name, c, filt)
     assert AM.crc(img) == in_crc
     t = torch.from_numpy(np.ascontiguousarray(img)[None]).cuda().permute(0, 3, 1, 2)
@@ -324,7 +258,7 @@ TO_FLOAT = [
 def test_uint8_to_float(aa, monkeypatch, case, dtype, lead):
     name, c, cl, (h, w), (oh, ow) = case
     shape = (2, c, h, w)
-    x = _gpu(_u8(shape, 12), cl)
+    x = kit_gpu.nchw_gpu(_u8(shape, 12), cl)
     f32 = _float_ref("linear", shape, 12, (oh, ow), from_u8=True)
     m32, s32 = np.asarray(MEAN[:c], np.float32).reshape(1, c, 1, 1), np.asarray(STD[:c], np.float32).reshape(1, c, 1, 1)
     for fmt in ("nchw", "nhwc"):
@@ -336,17 +270,17 @@ def test_uint8_to_float(aa, monkeypatch, case, dtype, lead):
                                want, flat_at_least=2 if want.startswith("fused") else 3, tag=(name, fmt, norm))
             assert y.is_contiguous(memory_format=torch.channels_last if fmt == "nhwc" else torch.contiguous_format)
             exp = torch.from_numpy(np.array((f32 - m32) / s32 if norm else f32)).to(dtype)
-            _assert_bits(y, exp, (name, TAG[dtype], fmt, norm, lead, v))
+            kit_gpu.assert_bits(y, exp, (name, TAG[dtype], fmt, norm, lead, v))
 
 
 @pytest.mark.parametrize("lead", LEADS)
 @pytest.mark.parametrize("cl", [True, False], ids=["nhwc", "planar"])
 def test_harness_uint8_output(aa, monkeypatch, cl, lead):
     shape, size = (2, 3, 33, 70), (9, 33)
-    x = _gpu(_u8(shape, 13), cl)
+    x = kit_gpu.nchw_gpu(_u8(shape, 13), cl)
     want = "fused_u8_nhwc_harness_v3" if cl else "fused_u8_planar_harness_v3"
     y, v, _ = _guarded(monkeypatch, lambda: aa.linear_forward(x, list(size), uint8_mode="harness"), lead, "3 harness uint8", want, flat_at_least=2, tag=cl)
-    _assert_bits(y, torch.from_numpy(np.ascontiguousarray(oracle.harness_u8("linear", _u8(shape, 13), size))), (cl, lead, v))
+    kit_gpu.assert_bits(y, torch.from_numpy(np.ascontiguousarray(oracle.harness_u8("linear", _u8(shape, 13), size))), (cl, lead, v))
 
 
 # ------------------------------------------------------------------------------------------------ 4. fused floats
@@ -364,7 +298,7 @@ def _exact_float_case(aa, monkeypatch, group, filt, shape, size, dtype, cl, lead
                          tag=(filt, shape, size, TAG[dtype], cl))
     assert y.dtype == dtype and y.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
     exp = torch.from_numpy(oracle.forward(filt, wide, size)).to(dtype)  # (16-bit: the fp32 reference rounded once)
-    _assert_bits(y, exp, (filt, shape, size, TAG[dtype], cl, lead, v))
+    kit_gpu.assert_bits(y, exp, (filt, shape, size, TAG[dtype], cl, lead, v))
     return v
 
 
@@ -394,7 +328,7 @@ UP_SHAPES = [("linear", (1, 2, 20, 128), (44, 512)), ("linear", (1, 2, 30, 90), 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=lambda d: TAG[d])
 def test_fused_float_growing_heights_every_store_form(aa, monkeypatch, dtype, form, lead):
     for filt, shape, size in UP_SHAPES:
-        with _Knobs(store=form):
+        with kit_gpu.Knobs(store=form):
             _exact_float_case(aa, monkeypatch, "4 fused float growing", filt, shape, size, dtype, False, lead, f"fused_{TAG[dtype]}_nchw_up", 2)
 
 
@@ -416,7 +350,7 @@ def test_tolerance_mode(aa, monkeypatch, lead):
     np.testing.assert_allclose(yh.float().cpu().numpy(), exact.float().numpy(), rtol=2e-3, atol=0.25)
     u8shape, u8size = (2, 3, 33, 70), (9, 33)
     for cl in (True, False):
-        xb = _gpu(_u8(u8shape, 13), cl)
+        xb = kit_gpu.nchw_gpu(_u8(u8shape, 13), cl)
         want = "fused_u8_nhwc_harness_v3_fast" if cl else "fused_u8_planar_harness_v3_fast"
         yb, _, _ = _guarded(monkeypatch, lambda: aa.linear_forward(xb, list(u8size), uint8_mode="harness", precision="fast"), lead, "4 tolerance mode",
                             want, flat_at_least=2, tag=("harness", cl))
@@ -436,14 +370,14 @@ def test_tolerance_mode(aa, monkeypatch, lead):
 def test_generic_two_launch_path(aa, monkeypatch, kind, cl, size, lead):
     """aa_set_fused(0): the intermediate of the two launches lies in a workspace whose size the shape alone decided."""
     shape = (2, 3, 21, 34)
-    with _Knobs(fused=0):
+    with kit_gpu.Knobs(fused=0):
         if kind.startswith("u8"):
-            x = _gpu(_u8(shape, 16), cl)
+            x = kit_gpu.nchw_gpu(_u8(shape, 16), cl)
             mode = kind[3:]
             y, v, _ = _guarded(monkeypatch, lambda: aa.cubic_forward(x, list(size), uint8_mode=mode), lead, "5 generic", f"generic_2pass_{kind}",
                                flat_at_least=3, tag=(kind, cl, size))
             exp = _pil_ref("cubic", shape, 16, size) if mode == "pil" else torch.from_numpy(np.ascontiguousarray(oracle.harness_u8("cubic", _u8(shape, 16), size)))
-            _assert_bits(y, exp, (kind, cl, size, lead, v))
+            kit_gpu.assert_bits(y, exp, (kind, cl, size, lead, v))
         else:
             dtype = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32, "f64": torch.float64}[kind]
             _exact_float_case(aa, monkeypatch, "5 generic", "cubic", shape, size, dtype, cl, lead, f"generic_2pass_{kind}", 3)
@@ -476,12 +410,12 @@ def test_sixteen_bit_backward(aa, monkeypatch, dt, cl, fused, lead):
             g = g0.contiguous(memory_format=torch.channels_last) if cl else g0
             want = f"fused_{TAG[dt]}_nchw_up" if (fused and not cl and i == 0) else f"generic_2pass_{TAG[dt]}"
             tag = (name, (n, c, h, w), (oh, ow), TAG[dt], cl, fused)
-            with _Knobs(fused=fused):
+            with kit_gpu.Knobs(fused=fused):
                 got, v, _ = _guarded(monkeypatch, lambda: _bwd(aa, name)(g, [oh, ow], [n, c, h, w]), lead, "6 backward 16-bit", want,
                                      flat_at_least=4 if want.startswith("fused") else 5, tag=tag)
                 ref = _bwd(aa, name)(g.float(), [oh, ow], [n, c, h, w]).to(dt)
             assert got.dtype == dt and got.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format), tag
-            _assert_bits(got, ref.cpu(), (tag, lead, v))
+            kit_gpu.assert_bits(got, ref.cpu(), (tag, lead, v))
             mats = [_dense(name, h, oh), _dense(name, w, ow)]
             gi, ab = R.backward_dense(mats, g0.float().cpu().numpy().astype(np.float64))
             b32 = R.bound(mats, ab, np.float32)
@@ -498,7 +432,7 @@ def test_float32_atomic_backward_through_python(aa, monkeypatch, cl, lead):
     for i, ((n, c, h, w), (oh, ow)) in enumerate(BWD_SHAPES):
         for name in ("linear", "cubic"):
             g_np = np.random.default_rng(700 + i).standard_normal((n, c, oh, ow)).astype(np.float32)
-            g = _gpu(g_np, cl)
+            g = kit_gpu.nchw_gpu(g_np, cl)
             tag = (name, (n, c, h, w), (oh, ow), cl)
             got, v, _ = _guarded(monkeypatch, lambda: _bwd(aa, name)(g, [oh, ow], [n, c, h, w], atomic=True), lead, "6 backward atomics",
                                  "bwd_scatter_atomics", flat_at_least=2, tag=tag)
@@ -509,14 +443,6 @@ def test_float32_atomic_backward_through_python(aa, monkeypatch, cl, lead):
 
 
 # ------------------------------------------------------------------------------------------------ 7. N-d front-ends
-def _oracle_axis(filt, a, axis, n_out):
-    """One separable pass along `axis` with the 2-D oracle (test_gpu_parity's): the axis becomes W of an [outer, 1, 1, n] image."""
-    moved = np.moveaxis(a, axis, -1)
-    lead = moved.shape[:-1]
-    out = oracle.forward(filt, np.ascontiguousarray(moved.reshape(-1, 1, 1, moved.shape[-1])), (1, n_out))
-    return np.moveaxis(out.reshape(*lead, n_out), -1, axis)
-
-
 ND_VARIANTS = ("generic_axis", "fused_f32_nchw", "fused_f32_nchw_up")
 ND_CASES = [((3, 4), (97,), (31,)), ((3, 4), (97,), (150,)), ((4, 3), (400,), (130,)), ((1, 2), (19, 23, 29), (7, 40, 29)), ((2, 2), (9, 11, 13), (12, 5, 20))]
 
@@ -529,17 +455,17 @@ def test_nd_forward_and_backward(aa, monkeypatch, case, lead):
     nd = len(sizes)
     for filt, fwd, bwd in (("linear", aa.linear_forward_nd, aa.linear_backward_nd), ("cubic", aa.cubic_forward_nd, aa.cubic_backward_nd)):
         x_np = _f32(lead_dims + sizes, 17)
-        x = _gpu(x_np)
+        x = kit_gpu.nchw_gpu(x_np)
         y, v, rec = _guarded(monkeypatch, lambda: fwd(x, list(osizes)), lead, "7 N-d", ND_VARIANTS, tag=(filt, case))
         assert len(rec.outputs()) == nd
         for t in rec.outputs():
             assert G.unwritten_float(t) == 0, (filt, case, tuple(t.shape))
         exp = x_np
         for axis in range(nd + 1, 1, -1):
-            exp = _oracle_axis(filt, exp, axis, osizes[axis - 2])
-        _assert_bits(y, torch.from_numpy(np.ascontiguousarray(exp)), (filt, case, lead, v))
+            exp = kit_gpu.oracle_axis(filt, exp, axis, osizes[axis - 2])
+        kit_gpu.assert_bits(y, torch.from_numpy(np.ascontiguousarray(exp)), (filt, case, lead, v))
         g_np = np.random.default_rng(18).standard_normal(lead_dims + osizes).astype(np.float32)
-        g = _gpu(g_np)
+        g = kit_gpu.nchw_gpu(g_np)
         gi_t, v, rec = _guarded(monkeypatch, lambda: bwd(g, list(osizes), list(lead_dims + sizes)), lead, "7 N-d", ND_VARIANTS, tag=(filt, case, "backward"))
         assert len(rec.outputs()) == nd
         for t in rec.outputs():
@@ -579,9 +505,9 @@ def test_reduce(aa, monkeypatch, case, lead):
     x = _u8(shape, 19)
     want = torch.from_numpy(np.stack([BRG.reduce_restated(img, factor, box) for img in x.transpose(0, 2, 3, 1)]).transpose(0, 3, 1, 2))
     for cl in ((False,) if shape[1] == 1 else (True, False)):
-        y, _, _ = _guarded(monkeypatch, lambda: aa.reduce(_gpu(x, cl), factor, box), lead, "8 reduce", None, tag=(name, cl))
+        y, _, _ = _guarded(monkeypatch, lambda: aa.reduce(kit_gpu.nchw_gpu(x, cl), factor, box), lead, "8 reduce", None, tag=(name, cl))
         assert y.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
-        _assert_bits(y, want, (name, cl, lead))
+        kit_gpu.assert_bits(y, want, (name, cl, lead))
 
 
 # ------------------------------------------------------------------------------------------------ 9. box= and reducing_gap=
@@ -598,7 +524,7 @@ def test_box_and_reducing_gap(aa, monkeypatch, cl, lead):
     fused = "fused_u8_nhwc_pil_v3" if cl else "fused_u8_planar_pil_v3"
     _, shape, seed, (oh, ow), box, _, _ = BOXC["b_down_c3"]
     x_np = BR.batch(shape, seed)
-    x = _gpu(x_np, cl)
+    x = kit_gpu.nchw_gpu(x_np, cl)
     for flt, want in (("linear", fused), ("lanczos", U8_ANY)):  # (bilinear: 7 taps, 3 open rows, a view the fused kernel reads in place)
         y, v, rec = _guarded(monkeypatch, lambda: _fwd(aa, flt)(x, [oh, ow], box=box), lead, "9 box", want, flat_at_least=2, tag=("box", flt, cl))
         assert all(r.nbytes >= 16384 for r in [r for r in rec.records if r.flat][:2])  # (the two box tables come in size classes)
@@ -609,7 +535,7 @@ def test_box_and_reducing_gap(aa, monkeypatch, cl, lead):
     for name, flt in (("g_box_2.0", "linear"), ("g_full_3.0", "cubic")):
         _, shape, seed, (oh, ow), box, gap, _ = GAPC[name]
         g_np = BR.batch(shape, seed)
-        xg = _gpu(g_np, cl)
+        xg = kit_gpu.nchw_gpu(g_np, cl)
         y, v, rec = _guarded(monkeypatch, lambda: _fwd(aa, flt)(xg, [oh, ow], box=box, reducing_gap=gap), lead, "9 reducing_gap", U8_ANY,
                              flat_at_least=2, tag=(name, flt, cl))
         assert len(rec.outputs()) == 2  # the reduced intermediate and the output, both at the placement
@@ -617,18 +543,11 @@ def test_box_and_reducing_gap(aa, monkeypatch, cl, lead):
 
 
 # ------------------------------------------------------------------------------------------------ 10. resize_many, resize_many_to_float
-MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "box", "hamming": "hamming", "lanczos": "lanczos"}
-
-
-def _item_gpu(x_chw, cls):
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.ascontiguousarray(x_chw)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
 def _many_inputs(name, cls):
-    return [_item_gpu(MR.item(name, i), cls) for i in range(len(MG.case(name)[3]))]
+    return [kit_gpu.to_gpu(MR.item(name, i), cls) for i in range(len(MG.case(name)[3]))]
 
 
 @functools.lru_cache(maxsize=None)
@@ -662,13 +581,13 @@ def test_resize_many_planar_item_of_two_chunks(aa, monkeypatch, lead):
     rng = np.random.default_rng(20)
     sizes = [(5, 9000), (8, 64), (3, 8189)]
     items = [rng.integers(0, 256, (3, h, w), dtype=np.uint8) for h, w in sizes]
-    imgs = [_item_gpu(a, "planar") for a in items]
+    imgs = [kit_gpu.to_gpu(a, "planar") for a in items]
     for f, size in (("linear", (7, 9)), ("cubic", (4, 70))):
         want = torch.from_numpy(np.stack([BRG.resize_box_restated(f, np.ascontiguousarray(a.transpose(1, 2, 0)), size[0], size[1]).transpose(2, 0, 1)
                                           for a in items]))
         y, _, _ = _guarded(monkeypatch, lambda: aa.resize_many(imgs, list(size), MODE[f]), lead, "10 resize_many", None, flat_at_least=2, tag=(f, size))
         assert y.is_contiguous()
-        _assert_bits(y, want, (f, size, lead))
+        kit_gpu.assert_bits(y, want, (f, size, lead))
 
 
 @pytest.mark.parametrize("lead", LEADS)
@@ -695,7 +614,7 @@ def test_resize_many_to_float(aa, monkeypatch, name, f, cls, dtype, lead):
             want = fl.to(dtype)
             if flips is not None:
                 want = torch.stack([want[i].flip(-1) if flips[i] else want[i] for i in range(n)])
-            _assert_bits(y, want, (name, f, cls, fmt, TAG[dtype], flips is not None, lead))
+            kit_gpu.assert_bits(y, want, (name, f, cls, fmt, TAG[dtype], flips is not None, lead))
 
 
 # ------------------------------------------------------------------------------------------------ 11. tables alone

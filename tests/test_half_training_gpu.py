@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import backward_ref as R
+import kit_gpu
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -29,35 +30,7 @@ U16 = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
 SUB = {torch.float16: 2.0 ** -25, torch.bfloat16: 0.0}
 WORST = {}
 _DENSE = {}
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    yield extension_interpolate
-    print("\n16-bit backward vs dense fp64 reference, worst err / bound:", {k: round(v, 4) for k, v in sorted(WORST.items())})
-
-
-class _Knobs:
-    """set_fused / set_store_form for one block, restored on the way out."""
-
-    def __init__(self, fused=1, store=-1):
-        self.fused, self.store = fused, store
-
-    def __enter__(self):
-        from interpolate_antialiasing_amd import _lib
-
-        self.prev_fused = _lib.set_fused(self.fused)
-        self.prev_store = _lib.set_store_form(self.store)
-
-    def __exit__(self, *exc):
-        from interpolate_antialiasing_amd import _lib
-
-        _lib.set_fused(self.prev_fused)
-        _lib.set_store_form(self.prev_store)
+aa = kit_gpu.aa_fixture(lambda: print("\n16-bit backward vs dense fp64 reference, worst err / bound:", {k: round(v, 4) for k, v in sorted(WORST.items())}))
 
 
 FORMS = {"gather_fused": (1, -1), "gather_generic": (0, -1), "gather_store1": (1, 1)}
@@ -85,10 +58,6 @@ def _dense(name, n_in, n_out, ac):
     if key not in _DENSE:
         _DENSE[key] = R.dense(name, n_in, n_out, ac, np.float32)
     return _DENSE[key]
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16)
 
 
 def _layout(g, cl):
@@ -132,7 +101,7 @@ def test_backward_is_the_cast_fp32_backward_bit_for_bit(aa, dt):
             for cl in (False, True):
                 g = _layout(g0, cl)
                 for form, (fused, store) in FORMS.items():
-                    with _Knobs(fused, store):
+                    with kit_gpu.Knobs(fused, store):
                         got = _bwd(aa, name)(g, [oh, ow], [n, c, h, w], ac)
                         v = _lib.last_variant()
                         ref = _bwd(aa, name)(g.float(), [oh, ow], [n, c, h, w], ac).to(dt)
@@ -141,7 +110,7 @@ def test_backward_is_the_cast_fp32_backward_bit_for_bit(aa, dt):
                     assert got.dtype == dt and tuple(got.shape) == (n, c, h, w), tag
                     assert got.is_contiguous(memory_format=torch.channels_last if _is_cl(g) else torch.contiguous_format), tag
                     assert torch.isfinite(got.float()).all(), tag
-                    assert torch.equal(_bits(got), _bits(ref)), (tag, int((_bits(got) != _bits(ref)).sum()))
+                    assert torch.equal(kit_gpu.bits(got), kit_gpu.bits(ref)), (tag, int((kit_gpu.bits(got) != kit_gpu.bits(ref)).sum()))
     print("\nvariants:", {f"{k[0]}/{'nhwc' if k[1] else 'nchw'}": sorted(v) for k, v in variants.items()})
     assert f"fused_{TAG[dt]}_nchw_up" in variants[("gather_fused", False)], variants
     assert f"fused_{TAG[dt]}_nchw_up" in variants[("gather_store1", False)], variants
@@ -158,7 +127,7 @@ def test_backward_vs_dense_fp64_adjoint(aa, dt):
             for cl in (False, True):
                 g = _layout(g0, cl)
                 for form, (fused, store) in FORMS.items():
-                    with _Knobs(fused, store):
+                    with kit_gpu.Knobs(fused, store):
                         got = _bwd(aa, name)(g, [oh, ow], [n, c, h, w], ac)
                     _judge16(got, g0, mats, dt, 1, form, (name, (n, c, h, w), (oh, ow), ac, cl))
 
@@ -173,13 +142,13 @@ def test_nd_backward_vs_dense_fp64_adjoint(aa, dt):
             mats = [_dense(name, a, b, False) for a, b in zip(sizes, osizes)]
             g = _grad(lead + osizes, dt, 300 + len(sizes), 10.0)
             for fused in (1, 0):
-                with _Knobs(fused, -1):
+                with kit_gpu.Knobs(fused, -1):
                     got = fns[name](g, list(osizes), list(lead + sizes), False)
                     ref = fns[name](g.float(), list(osizes), list(lead + sizes), False).to(dt)
                 assert got.dtype == dt and tuple(got.shape) == lead + sizes
                 _judge16(got, g, mats, dt, len(sizes), f"nd{len(sizes)}_{'fused' if fused else 'generic'}", (name, sizes, osizes, fused))
                 if len(sizes) == 1:
-                    assert torch.equal(_bits(got), _bits(ref)), (name, sizes, osizes, fused)
+                    assert torch.equal(kit_gpu.bits(got), kit_gpu.bits(ref)), (name, sizes, osizes, fused)
 
 
 @pytest.mark.parametrize("dt", HALVES)
@@ -201,7 +170,7 @@ def test_autograd_in_sixteen_bits(aa, dt, cl):
         assert x.grad is not None and x.grad.dtype == dt and x.grad.stride() == x.stride(), tag
         assert x.grad.is_contiguous(memory_format=mf), tag
         assert torch.isfinite(x.grad.float()).all(), tag
-        assert torch.equal(_bits(x.grad), _bits(direct)), tag
+        assert torch.equal(kit_gpu.bits(x.grad), kit_gpu.bits(direct)), tag
 
     big = _grad((n, c, 2 * oh, ow + 40), dt, 6)
     for name in ("linear", "cubic", "lanczos"):
@@ -243,7 +212,7 @@ def test_nonfinite_sixteen_bit_gradients_do_not_leak(aa, dt):
                 gl = _layout(g, cl)
                 for form in ("gather_fused", "gather_generic"):
                     fused, store = FORMS[form]
-                    with _Knobs(fused, store):
+                    with kit_gpu.Knobs(fused, store):
                         got = _bwd(aa, name)(gl, [oh, ow], [n, c, h, w], False)
                         ref = _bwd(aa, name)(gl.float(), [oh, ow], [n, c, h, w], False)
                     tag = (name, (h, w), (oh, ow), cl, form)
@@ -272,7 +241,7 @@ def test_integration_stub_backward_in_sixteen_bits(aa):
             g = _layout(_grad((2, 3, 23, 37), dt, 11), cl)
             a = stub.linear_backward(g, [23, 37], [2, 3, 61, 90], False)
             b = aa.linear_backward(g, [23, 37], [2, 3, 61, 90])
-            assert a.dtype == dt and a.stride() == b.stride() and torch.equal(_bits(a), _bits(b)), (dt, cl)
+            assert a.dtype == dt and a.stride() == b.stride() and torch.equal(kit_gpu.bits(a), kit_gpu.bits(b)), (dt, cl)
 
 
 # ------------------------------------------------------------------------------------------------ the 16-bit channels_last forward
@@ -295,16 +264,16 @@ def _check_nhwc(aa, filt, x, size, tag, oracle_too=True):
     assert _is_cl(x), tag
     y = _fwd(aa, filt)(x, list(size))
     v = _lib.last_variant()
-    with _Knobs(0, -1):
+    with kit_gpu.Knobs(0, -1):
         y0 = _fwd(aa, filt)(x, list(size))
         v0 = _lib.last_variant()
     assert v == f"fused_{TAG[dt]}_nhwc", (tag, v)
     assert v0.startswith("generic_2pass"), (tag, v0)
     assert y.dtype == dt and _is_cl(y) and tuple(y.shape) == tuple(x.shape[:2]) + tuple(size), tag
-    assert torch.equal(_bits(y), _bits(y0)), (tag, int((_bits(y) != _bits(y0)).sum()))
+    assert torch.equal(kit_gpu.bits(y), kit_gpu.bits(y0)), (tag, int((kit_gpu.bits(y) != kit_gpu.bits(y0)).sum()))
     if oracle_too:
         exp = torch.from_numpy(oracle.forward(filt, x[:1].float().cpu().numpy(), tuple(size))).to(dt)
-        assert torch.equal(_bits(y[:1].cpu()), _bits(exp)), (tag, "oracle")
+        assert torch.equal(kit_gpu.bits(y[:1].cpu()), kit_gpu.bits(exp)), (tag, "oracle")
     return y
 
 
@@ -346,14 +315,14 @@ def test_nhwc16_tensor_ending_on_its_allocation(aa, dt):
     x = big.permute(0, 3, 1, 2)
     y = aa.linear_forward(x, [512, 4])
     v = _lib.last_variant()
-    with _Knobs(0, -1):
+    with kit_gpu.Knobs(0, -1):
         y0 = aa.linear_forward(x, [512, 4])
     torch.cuda.synchronize()
     assert v == f"fused_{TAG[dt]}_nhwc", v
-    assert torch.equal(_bits(y[-1, :, -1, -1]), _bits(y0[-1, :, -1, -1])), "the last output pixel"
-    assert torch.equal(_bits(y), _bits(y0))
+    assert torch.equal(kit_gpu.bits(y[-1, :, -1, -1]), kit_gpu.bits(y0[-1, :, -1, -1])), "the last output pixel"
+    assert torch.equal(kit_gpu.bits(y), kit_gpu.bits(y0))
     exp = torch.from_numpy(oracle.forward("linear", x[-1:].float().cpu().numpy(), (512, 4))).to(dt)
-    assert torch.equal(_bits(y[-1:].cpu()), _bits(exp)), "oracle, last image"
+    assert torch.equal(kit_gpu.bits(y[-1:].cpu()), kit_gpu.bits(exp)), "oracle, last image"
     del big, x, y, y0
 
 
@@ -383,7 +352,7 @@ def test_nhwc16_nonfinite_pixels_do_not_leak(aa, dt, c):
     for filt in ("linear", "cubic"):
         y = _fwd(aa, filt)(x, [13, 23])
         assert _lib.last_variant() == f"fused_{TAG[dt]}_nhwc"
-        with _Knobs(0, -1):
+        with kit_gpu.Knobs(0, -1):
             y0 = _fwd(aa, filt)(x, [13, 23])
         yf, y0f = y.float(), y0.float()
         assert torch.isnan(y0f).any() and torch.isinf(y0f).any() and torch.isfinite(y0f).sum() > y0f.numel() // 2
@@ -426,7 +395,7 @@ def test_nhwc16_views_are_read_in_place(aa, monkeypatch, dt, c):
         assert codes == [_lib.AA_OK] and copies == [], (what, codes, copies)
         ref = aa.linear_forward(view.contiguous(memory_format=torch.channels_last), size if view.shape[2] == h else [17, 27])
         assert _lib.last_variant() == want, what
-        assert torch.equal(_bits(y), _bits(ref)) and _is_cl(y), what
+        assert torch.equal(kit_gpu.bits(y), kit_gpu.bits(ref)) and _is_cl(y), what
     if c == 3:
         assert (views[1][1].storage_offset() & 1) == 1, "the second crop is meant to start on an odd element"
     # a dense tensor that is only 2-byte aligned
@@ -437,7 +406,7 @@ def test_nhwc16_views_are_read_in_place(aa, monkeypatch, dt, c):
     assert odd.data_ptr() % 4 == 2 and _is_cl(odd)
     y = aa.cubic_forward(odd, size)
     assert _lib.last_variant() == want
-    assert torch.equal(_bits(y), _bits(aa.cubic_forward(x, size)))
+    assert torch.equal(kit_gpu.bits(y), kit_gpu.bits(aa.cubic_forward(x, size)))
 
 
 @pytest.mark.parametrize("dt", HALVES)
@@ -464,7 +433,7 @@ def test_nhwc16_workspace_answer_matches_dispatch(aa, dt):
     y = aa.linear_forward(x, [16, 100])
     assert _lib.last_variant().startswith("generic_2pass"), _lib.last_variant()
     exp = torch.from_numpy(oracle.forward("linear", x.float().cpu().numpy(), (16, 100))).to(dt)
-    assert torch.equal(_bits(y.cpu()), _bits(exp))
+    assert torch.equal(kit_gpu.bits(y.cpu()), kit_gpu.bits(exp))
 
 
 @pytest.mark.parametrize("dt", HALVES)
@@ -476,4 +445,4 @@ def test_nhwc16_fast_precision_runs_the_exact_kernel(aa, dt, c):
     y = aa.linear_forward(x, [13, 23])
     yf = aa.linear_forward(x, [13, 23], precision="fast")
     assert _lib.last_variant() == f"fused_{TAG[dt]}_nhwc", _lib.last_variant()
-    assert torch.equal(_bits(y), _bits(yf))
+    assert torch.equal(kit_gpu.bits(y), kit_gpu.bits(yf))

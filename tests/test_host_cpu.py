@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import kit_golden
 import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,25 +117,11 @@ def test_shard_range_partitions_exactly():
         sharding.shard_range(8, 2, 2)
 
 
-def _pack_table_numpy(filt, n_in, n_out):
-    """Build the packed F32 table format on the CPU from the oracle (tests only)."""
-    k, xmin, xsize, w = oracle.weights(filt, n_in, n_out, False, np.float32)
-    woff = (64 + 8 * n_out + 15) & ~15
-    buf = np.zeros(woff + 4 * n_out * k, np.uint8)
-    hdr = np.zeros(16, np.int32)
-    hdr[:9] = [0x42544141, oracle.FILTERS[filt], 1, n_in, n_out, k, 0, int(max(1, xsize.max())), 0]
-    buf[:64] = hdr.view(np.uint8)
-    buf[64:64 + 4 * n_out] = xmin.astype(np.int32).view(np.uint8)
-    buf[64 + 4 * n_out:64 + 8 * n_out] = xsize.astype(np.int32).view(np.uint8)
-    buf[woff:] = w.astype(np.float32).reshape(-1).view(np.uint8)
-    return buf, k, int(max(1, xsize.max()))
-
-
 def test_weight_table_pack_unpack_roundtrip():
     from interpolate_antialiasing_amd import _lib
     from interpolate_antialiasing_amd.tables import WeightTable
 
-    buf, k, mt = _pack_table_numpy("linear", 906, 320)
+    buf, k, mt = kit_golden.pack_table_numpy("linear", 906, 320)
     t = WeightTable(torch.from_numpy(buf), 0, _lib.TABLE_F32, 906, 320, k, mt)
     xmin, xsize, w = t.unpack()
     ko, xo, so, wo = oracle.weights("linear", 906, 320)
@@ -151,16 +138,16 @@ sys.path.insert(0, sys.argv[1])
 from interpolate_antialiasing_amd import _lib, sharding
 from interpolate_antialiasing_amd.tables import WeightTable
 sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
-from test_host_cpu import _pack_table_numpy
+from kit_golden import pack_table_numpy
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 dist.init_process_group("gloo", rank=rank, world_size=world)
 # rank 0 owns the table; everyone else receives it with the single broadcast the path has
 t = None
 if rank == 0:
-    buf, k, mt = _pack_table_numpy("linear", 438, 196)
+    buf, k, mt = pack_table_numpy("linear", 438, 196)
     t = WeightTable(torch.from_numpy(buf), 0, _lib.TABLE_F32, 438, 196, k, mt)
 got = sharding.broadcast_table(t, src=0, device=torch.device("cpu"))
-ref, k, mt = _pack_table_numpy("linear", 438, 196)
+ref, k, mt = pack_table_numpy("linear", 438, 196)
 assert np.array_equal(got.buf.numpy(), ref) and got.ksize == k and got.max_taps == mt and got.in_size == 438
 # batch shard of config 3 + the bench's reductions
 a, b = sharding.shard_range(8192, rank, world)

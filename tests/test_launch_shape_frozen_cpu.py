@@ -3,33 +3,11 @@ bands, groups and grid recorded there: what the four fused families' own launch 
 model replaced their copies (tests/golden/make_golden_launch_shapes.py made it from that commit's sources and lists the branches the
 rows reach).  No GPU: the model is host arithmetic, the CU count and the occupancy answers are part of a row."""
 import ctypes
-import json
-import os
 
 import pytest
 
 from interpolate_antialiasing_amd import _lib
-
-with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_shapes.json")) as _f:
-    FROZEN = json.load(_f)
-FAMILIES = {"v1": _lib.LAUNCH_V1, "v3": _lib.LAUNCH_V3, "f32_down": _lib.LAUNCH_F32_DOWN, "f32_up": _lib.LAUNCH_F32_UP}
-
-
-def _input(family, nstrips, spb, forced, items, H, oH, taps_h, taps_w, lds, saturation, threads, occupancy, cus=None):
-    q = _lib.LaunchShapeIn()
-    q.family, q.nstrips, q.strips_per_block, q.spb_forced = family, nstrips, spb, forced
-    q.items, q.H, q.oH, q.taps_h, q.taps_w = items, H, oH, taps_h, taps_w
-    q.lds, q.saturation, q.threads, q.cus = lds, saturation, threads, FROZEN["cus"] if cus is None else cus
-    q.occupancy[0] = -1
-    for s, nb in enumerate(occupancy, 1):
-        q.occupancy[s] = nb
-    return q
-
-
-def _shape(q):
-    out = _lib.LaunchShapeOut()
-    rc = _lib.load().aa_probe_launch_shape(ctypes.byref(q), ctypes.byref(out))
-    return rc, [out.strips_per_block, out.ybands, out.groups, out.grid]
+from launch_shape_cases import FAMILIES, FROZEN, question, shape
 
 
 def test_the_fixture_reaches_every_branch():
@@ -44,7 +22,7 @@ def test_every_launch_shape_is_the_frozen_one(family):
     assert len(rows) >= 100
     different = []
     for r in rows:
-        rc, got = _shape(_input(*r[:13]))
+        rc, got = shape(question(*r[:13]))
         if rc != 0 or got != r[13:]:
             different.append((r[:13], "rc %d" % rc, got, r[13:]))
     assert not different, f"{len(different)} of {len(rows)} shapes differ, the first: {different[0]}"
@@ -53,16 +31,16 @@ def test_every_launch_shape_is_the_frozen_one(family):
 def test_bad_inputs_are_refused():
     L = _lib.load()
     good = [_lib.LAUNCH_V3, 5, 5, 0, 64, 438, 196, 5, 5, 4096, 0, 0, [24, 12, 8, 6, 4, 4, 3, 3]]
-    assert _shape(_input(*good))[0] == 0
+    assert shape(question(*good))[0] == 0
     out = _lib.LaunchShapeOut()
     assert L.aa_probe_launch_shape(None, ctypes.byref(out)) == -5  # AA_ERR_NULL
-    assert L.aa_probe_launch_shape(ctypes.byref(_input(*good)), None) == -5
+    assert L.aa_probe_launch_shape(ctypes.byref(question(*good)), None) == -5
     for col, bad in ((0, 4), (0, -1), (1, 0), (2, 0), (2, 9), (4, 0), (5, 0), (6, 0), (7, 0), (8, 0)):
         row = list(good)
         row[col] = bad
-        assert _shape(_input(*row))[0] == -4, (col, bad)  # AA_ERR_BAD_SHAPE
-    assert _shape(_input(*good, cus=0))[0] == -4
+        assert shape(question(*row))[0] == -4, (col, bad)  # AA_ERR_BAD_SHAPE
+    assert shape(question(*good, cus=0))[0] == -4
     v1 = [_lib.LAUNCH_V1, 1, 1, 0, 64, 438, 196, 5, 5, 9000, 0, 256, [-1] * 8]
-    assert _shape(_input(*v1))[0] == 0
+    assert shape(question(*v1))[0] == 0
     for threads in (0, 32, 100):
-        assert _shape(_input(*(v1[:11] + [threads] + v1[12:])))[0] == -4
+        assert shape(question(*(v1[:11] + [threads] + v1[12:])))[0] == -4

@@ -21,9 +21,7 @@ widths that give five strips, so that groups of 2 and of 4 leave a short last gr
 count is read from aa_last_launch_shape, not restated.  Inputs are seeded noise with rows of all 0 / all 255 at the top, the bottom and
 across the middle band seams (floats: rows a million times larger than their neighbours).  Batch 2."""
 import functools
-import importlib.util
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -32,40 +30,27 @@ import torch
 import backward_ref as R
 import box_reduce_ref as BR
 import guard_ref as G
+import kit_golden
+import kit_gpu
 import oracle
+from kit_golden import MEAN, STD
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TAG = {torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32", torch.float64: "f64"}
-MEAN, STD = [123.675, 116.28, 103.53, 127.5], [58.395, 57.12, 57.375, 64.0]
 ROWS_PER_BAND = {0: 8, 1: 8, 2: 8, 3: 16}  # aa_launch_family -> output rows a band has at least
 SEEN = {}  # family -> shapes that ran, printed at the end of the module
 
 
-def _alpha_maker():
-    spec = importlib.util.spec_from_file_location("make_golden_alpha", os.path.join(ROOT, "tests", "golden", "make_golden_alpha.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+def _report():
+    from interpolate_antialiasing_amd import _lib
 
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import _lib, extension_interpolate
-
-    yield extension_interpolate
     _lib.set_launch_shape(0, 0)
     print("\nlaunch-shape sweep, (spb, ybands) that ran:", {k: sorted(v) for k, v in sorted(SEEN.items())})
 
 
-@pytest.fixture(scope="module")
-def lib(aa):
-    from interpolate_antialiasing_amd import _lib
-
-    return _lib
+aa = kit_gpu.aa_fixture(_report)
+lib = kit_gpu.lib_fixture()
 
 
 @pytest.fixture(autouse=True)
@@ -121,25 +106,6 @@ def _float_input(shape, seed, dtype, cl=False, signed=True):
     return (xg.contiguous(memory_format=torch.channels_last) if cl else xg), np.ascontiguousarray(wide)
 
 
-def _gpu(a, cl=False):
-    t = torch.from_numpy(np.array(a, order="C")).cuda()
-    return t.contiguous(memory_format=torch.channels_last) if cl else t
-
-
-def _bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def _assert_bits(got, want, what):
-    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), (what, got.dtype, tuple(got.shape), want.dtype, tuple(want.shape))
-    a, b = _bits(got), _bits(want)
-    if not torch.equal(a, b):
-        bad = (a != b).nonzero()
-        raise AssertionError(f"{what}: {len(bad)} of {a.numel()} elements differ from the reference, first at {bad[0].tolist()}: "
-                             f"{got.cpu()[tuple(bad[0])].item()} != {want.cpu()[tuple(bad[0])].item()}")
-
-
 def _fwd(aa, filt):
     return {"linear": aa.linear_forward, "cubic": aa.cubic_forward, "lanczos": aa.lanczos_forward}[filt]
 
@@ -152,16 +118,13 @@ def _guarded(monkeypatch, lib, call, tag):
     for fill in (0xFF, 0x00):
         with G.guarded(monkeypatch, 0, fill) as rec:
             try:
-                y = call()
-                v = lib.last_variant()
-                shape = lib.last_launch_shape()
-                rec.check()
+                with kit_gpu.gpu_error_ends_the_session(tag):
+                    y = call()
+                    v = lib.last_variant()
+                    shape = lib.last_launch_shape()
+                    rec.check()
             except G.GuardViolation as e:
                 raise AssertionError(f"{tag}: {e}") from None
-            except RuntimeError as e:
-                if not isinstance(e, lib.AAInterpError) and ("HIP error" in str(e) or "illegal memory access" in str(e)):
-                    pytest.exit(f"the GPU reported an error in {tag}; nothing more is launched: {e}", returncode=3)
-                raise
         runs.append((y, v, shape))
         if y.dtype != torch.uint8:
             break
@@ -214,7 +177,7 @@ def _sweep(monkeypatch, lib, call, family, variant, verify, tag, nstrips=5, grou
 
 def _exactly(want):
     want = want if isinstance(want, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(want))
-    return lambda y, what: _assert_bits(y, want, what)
+    return lambda y, what: kit_gpu.assert_bits(y, want, what)
 
 
 # ------------------------------------------------------------------------------------------------ 1. the fused uint8 kernel (v3)
@@ -244,7 +207,7 @@ def _v3_expected(name):
     _, c, _, filt, (n, h, w), size, _, _, kw = next(cs for cs in V3_CASES if cs[0] == name)
     x = _u8((n, c, h, w), 31)
     if kw.get("alpha"):  # Pillow: premultiply, resize the four channels, un-premultiply (the formulas tests/golden/alpha.npz was made with)
-        am = _alpha_maker()
+        am = kit_golden.generator("alpha")
         a = x[:, 3:4]
         pre = np.concatenate([am.premul_formula(x[:, :3], np.broadcast_to(a, x[:, :3].shape)), a], axis=1)
         r = oracle.pil_resize_u8(filt, np.ascontiguousarray(pre), size)
@@ -280,7 +243,7 @@ def _assert_route(lib, name, filt, h, w, oh, ow):
 @pytest.mark.parametrize("case", V3_CASES, ids=lambda c: c[0])
 def test_fused_uint8_kernel(aa, lib, monkeypatch, case):
     name, c, cl, filt, (n, h, w), (oh, ow), strips, groups, kw = case
-    x = _gpu(_u8((n, c, h, w), 31), cl)
+    x = kit_gpu.nchw_gpu(_u8((n, c, h, w), 31), cl)
     if "uint8_mode" not in kw:
         _assert_route(lib, name, filt, h, w, oh, ow)
     want = ("fused_u8_nhwc_pil_alpha_v3" if kw.get("alpha") else
@@ -296,7 +259,7 @@ def test_fused_uint8_kernel(aa, lib, monkeypatch, case):
 def test_fused_uint8_to_float(aa, lib, monkeypatch, fmt, dtype, ow):
     """uint8 to normalised float in one launch; 16-bit outputs leave in pairs where the rows are whole dwords (even oW)."""
     shape, size = (2, 3, 86, 600), (41, ow)
-    x = _gpu(_u8(shape, 32), True)
+    x = kit_gpu.nchw_gpu(_u8(shape, 32), True)
     f32 = oracle.forward("linear", np.ascontiguousarray(_u8(shape, 32).astype(np.float32)), size)
     m32, s32 = np.asarray(MEAN[:3], np.float32).reshape(1, 3, 1, 1), np.asarray(STD[:3], np.float32).reshape(1, 3, 1, 1)
     exp = torch.from_numpy(np.array((f32 - m32) / s32)).to(dtype)
@@ -308,7 +271,7 @@ def test_fused_uint8_to_float(aa, lib, monkeypatch, fmt, dtype, ow):
 def test_first_generation_kernel_bands_only(aa, lib, monkeypatch):
     """aa_set_fused(2): every band count, and a grouping request is not looked at (the kernel has one workgroup form)."""
     shape, size = (2, 3, 86, 200), (41, 92)  # (this kernel stores rows of whole dwords)
-    x = _gpu(_u8(shape, 33), True)
+    x = kit_gpu.nchw_gpu(_u8(shape, 33), True)
     exp = _exactly(oracle.pil_resize_u8("linear", _u8(shape, 33), size))
     lib.set_fused(2)
     call = lambda: aa.linear_forward(x, list(size))  # noqa: E731
@@ -363,7 +326,7 @@ def test_tolerance_mode_is_the_same_under_every_shape(aa, lib, monkeypatch):
                  lambda y, what: np.testing.assert_allclose(y.cpu().numpy(), exp, rtol=1e-4, atol=1e-4 * 255, err_msg=str(what)), "fast")
     first = next(iter(got.values()))
     for shape_, y in got.items():
-        _assert_bits(y, first, ("fast", shape_))
+        kit_gpu.assert_bits(y, first, ("fast", shape_))
 
 
 # ------------------------------------------------------------------------------------------------ 4. float, growing heights
@@ -431,15 +394,7 @@ def test_gather_backward_of_a_down_scale(aa, lib, monkeypatch, dtype):
                  ("backward", TAG[dtype]))
     first = next(iter(got.values()))
     for shape_, y in got.items():
-        _assert_bits(y, first, ("backward", TAG[dtype], shape_))
-
-
-def _oracle_axis(filt, a, axis, n_out):
-    """One separable pass along `axis` with the 2-D oracle: the axis becomes W of an [outer, 1, 1, n] image."""
-    moved = np.moveaxis(a, axis, -1)
-    lead = moved.shape[:-1]
-    out = oracle.forward(filt, np.ascontiguousarray(moved.reshape(-1, 1, 1, moved.shape[-1])), (1, n_out))
-    return np.moveaxis(out.reshape(*lead, n_out), -1, axis)
+        kit_gpu.assert_bits(y, first, ("backward", TAG[dtype], shape_))
 
 
 def test_one_axis_pass(aa, lib, monkeypatch):
@@ -447,8 +402,8 @@ def test_one_axis_pass(aa, lib, monkeypatch):
     identity table across."""
     shape, osizes = (1, 2, 40, 4, 160), (83, 4, 160)
     x_np = _f32((1, 2, 40, 640), 39).reshape(shape)
-    x = _gpu(x_np)
+    x = kit_gpu.nchw_gpu(x_np)
     exp = x_np
     for axis in (4, 3, 2):
-        exp = _oracle_axis("linear", exp, axis, osizes[axis - 2])
+        exp = kit_gpu.oracle_axis("linear", exp, axis, osizes[axis - 2])
     _sweep(monkeypatch, lib, lambda: aa.linear_forward_nd(x, list(osizes)), lib.LAUNCH_F32_UP, "fused_f32_nchw_up", _exactly(exp), "depth pass", 5)

@@ -10,7 +10,7 @@ import itertools
 import pytest
 
 from interpolate_antialiasing_amd import _lib
-from test_launch_shape_frozen_cpu import FAMILIES, FROZEN, _input, _shape
+from launch_shape_cases import FAMILIES, FROZEN, question, shape
 
 V1, V3, DOWN, UP = _lib.LAUNCH_V1, _lib.LAUNCH_V3, _lib.LAUNCH_F32_DOWN, _lib.LAUNCH_F32_UP
 STRIPPED = {"v3": V3, "f32_down": DOWN, "f32_up": UP}
@@ -29,16 +29,16 @@ def model_chooses_afterwards():
 def _row(family, nstrips=5, spb=None, forced=0, items=6, H=180, oH=83, lds=4096, occupancy=OCC, cus=None, taps_w=5):
     """One question of the model.  The first generation has no strips: one of 256 threads."""
     if family == V1:
-        return _input(V1, 1, 1, 0, items, H, oH, 5, taps_w, lds, 0, 256, [-1] * 8, cus=cus)
+        return question(V1, 1, 1, 0, items, H, oH, 5, taps_w, lds, 0, 256, [-1] * 8, cus=cus)
     spb = (nstrips if nstrips <= 8 else 4) if spb is None else spb
-    return _input(family, nstrips, spb, forced, items, H, oH, 5, taps_w, lds, 1 if family == DOWN else 0, 0, occupancy, cus=cus)
+    return question(family, nstrips, spb, forced, items, H, oH, 5, taps_w, lds, 1 if family == DOWN else 0, 0, occupancy, cus=cus)
 
 
 def _ask(q, spb=0, ybands=0):
     """[spb, ybands, groups, grid] of q with the hook at (spb, ybands); the hook is at (0, 0) afterwards."""
     _lib.set_launch_shape(spb, ybands)
     try:
-        rc, got = _shape(q)
+        rc, got = shape(q)
     finally:
         _lib.set_launch_shape(0, 0)
     assert rc == 0
@@ -200,10 +200,10 @@ def test_the_frozen_model_after_setting_and_resetting(family):
     for i, r in enumerate(sample):
         want = (1 + i % 8, 1 + i % 5)
         assert _lib.set_launch_shape(*want) == (0, 0)
-        rc, forced = _shape(_input(*r[:13]))
+        rc, forced = shape(question(*r[:13]))
         assert rc == 0
         moved += forced != r[13:]
         assert _lib.set_launch_shape(0, 0) == want
-        rc, got = _shape(_input(*r[:13]))
+        rc, got = shape(question(*r[:13]))
         assert rc == 0 and got == r[13:], (r[:13], got, r[13:])
     assert moved >= len(sample) // 4, (family, moved)  # (the hook did change answers in between)

@@ -10,9 +10,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import kit_golden  # noqa: E402
 import many_plan_cases  # noqa: E402
 
-with open(os.path.join(many_plan_cases.ROOT, "tests", "golden", "many_plans.json")) as _f:
+with open(os.path.join(kit_golden.GOLDEN, "many_plans.json")) as _f:
     FROZEN = json.load(_f)
 GROUPS = sorted({k.split("/")[0] for k in FROZEN})
 

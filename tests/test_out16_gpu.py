@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import kit_gpu
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -17,16 +18,7 @@ DTYPES = (torch.float16, torch.bfloat16)
 TAG = {torch.float16: "f16", torch.bfloat16: "bf16"}
 MEAN, STD = [123.675, 116.28, 103.53, 110.25], [58.395, 57.12, 57.375, 60.5]
 VARIANTS = {}  # (what, dtype tag) -> variants seen, printed at the end of the module
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    yield extension_interpolate
-    print("\n16-bit output, variants that ran:", {f"{k[0]}/{k[1]}": sorted(v) for k, v in sorted(VARIANTS.items())})
+aa = kit_gpu.aa_fixture(lambda: print("\n16-bit output, variants that ran:", {f"{k[0]}/{k[1]}": sorted(v) for k, v in sorted(VARIANTS.items())}))
 
 
 def _fn(aa, filt):
@@ -71,11 +63,6 @@ def _seeded(seed, n, c, h, w):
     return np.random.default_rng(seed).integers(0, 256, (n, c, h, w), dtype=np.uint8)
 
 
-def _gpu(chw_u8, channels_last):
-    t = torch.from_numpy(np.ascontiguousarray(chw_u8)).cuda()
-    return t.contiguous(memory_format=torch.channels_last) if channels_last else t
-
-
 # ---------------------------------------------------------------------------------------------- 1. the known-answer image
 @pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: TAG[d])
 @pytest.mark.parametrize("size", ([196, 320], [196, 319]), ids=lambda s: f"{s[0]}x{s[1]}")
@@ -87,7 +74,7 @@ def test_known_answer_image(aa, golden_kat, dtype, size):
 
     rgb = golden_kat["rgb"]  # [438, 906, 3] uint8
     chw = np.ascontiguousarray(rgb.transpose(2, 0, 1))[None]
-    hwc, planar = _gpu(chw, True), _gpu(chw, False)
+    hwc, planar = kit_gpu.nchw_gpu(chw, True), kit_gpu.nchw_gpu(chw, False)
     tag = TAG[dtype]
     for filt in ("linear", "cubic"):
         for x, fmts in ((hwc, ("nchw", "nhwc", None)), (planar, ("nchw", None, "nhwc"))):
@@ -136,7 +123,7 @@ def _run_small(aa, case, dtype, filt):
 
     name, c, cl, hw, size = case
     chw = _seeded(1000 + 7 * SMALL.index(case), 2, c, hw[0], hw[1])
-    x = _gpu(chw, cl)
+    x = kit_gpu.nchw_gpu(chw, cl)
     seen = []
     for fmt in (("nchw", "nhwc") if cl else ("nchw",)):
         for norm in (True, False):
@@ -202,7 +189,7 @@ def test_output_two_bytes_into_an_allocation(aa, dtype):
     stream = torch.cuda.current_stream().cuda_stream
     for name, c, cl, hw, size in (SMALL[0], SMALL[4], SMALL[-2]):
         chw = _seeded(77, 2, c, hw[0], hw[1])
-        x = _gpu(chw, cl)
+        x = kit_gpu.nchw_gpu(chw, cl)
         layout = _lib.NHWC if cl else _lib.NCHW
         th, tw = tables.get_table_pair(_lib.FILTER_LINEAR, _lib.TABLE_F32, hw[0], size[0], hw[1], size[1], False, 0.0, 0.0, x.device)
         ah, aw = th.axis(), tw.axis()
@@ -257,7 +244,7 @@ def test_fast_precision(aa, golden_kat, dtype):
     for key, arr, size in (("kat", chw, [196, 320]), ("fast_small_even", small, [13, 132]), ("fast_small_odd", small, [13, 131])):
         for cl, fmt in ((True, "nchw"), (True, "nhwc"), (False, "nchw")):
             exp = _expected16(key, "linear", arr, size, False, dtype)
-            y = aa.linear_forward(_gpu(arr, cl), size, out_dtype=dtype, out_format=fmt, precision="fast")
+            y = aa.linear_forward(kit_gpu.nchw_gpu(arr, cl), size, out_dtype=dtype, out_format=fmt, precision="fast")
             v = _lib.last_variant()
             VARIANTS.setdefault(("fast", TAG[dtype]), set()).add(v)
             assert v.startswith("fused_u8_") and f"_to_{TAG[dtype]}_" in v and v.endswith("_fast"), (key, fmt, v)
@@ -273,7 +260,7 @@ def test_float32_and_uint8_outputs_unchanged(aa):
     from interpolate_antialiasing_amd import _lib
 
     chw = _seeded(9, 2, 3, 40, 300)
-    x = _gpu(chw, True)
+    x = kit_gpu.nchw_gpu(chw, True)
     for fmt, variant in (("nchw", "fused_u8_nhwc_to_f32_nchw_v3"), ("nhwc", "fused_u8_nhwc_to_f32_nhwc_v3")):
         for norm in (False, True):
             y = aa.linear_forward(x, [13, 132], out_dtype=torch.float32, out_format=fmt, **_norm_args(3, norm))

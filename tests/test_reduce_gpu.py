@@ -11,24 +11,12 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import box_reduce_ref as ref  # noqa: E402
+import kit_gpu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 G = ref.gen()
+aa = kit_gpu.aa_fixture()
 CASES = {cs[0]: cs for cs in G.REDUCE_CASES}
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    return extension_interpolate
-
-
-def _gpu(x_nchw, channels_last):
-    t = torch.from_numpy(np.array(x_nchw, order="C")).cuda()
-    return t.contiguous(memory_format=torch.channels_last) if channels_last else t.contiguous()
 
 
 def _nhwc(y):
@@ -45,14 +33,14 @@ def test_reduce_equals_pillow(aa, name):
     _, shape, seed, fill, factor, box, alpha = CASES[name]
     x = ref.batch(shape, seed, fill)
     for cl in _layouts(shape[1]):
-        y = aa.reduce(_gpu(x, cl), factor, box, alpha=alpha)
+        y = aa.reduce(kit_gpu.nchw_gpu(x, cl), factor, box, alpha=alpha)
         assert y.dtype == torch.uint8 and y.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
         ref.assert_matches_fixture(name, x, _nhwc(y))
 
 
 def test_constant_images_stay_constant(aa):
     for fill in (255, 0):
-        y = aa.reduce(_gpu(ref.batch((1, 3, 37, 53), 0, fill), True), (7, 9))
+        y = aa.reduce(kit_gpu.nchw_gpu(ref.batch((1, 3, 37, 53), 0, fill), True), (7, 9))
         assert tuple(y.shape) == (1, 3, 5, 8) and bool((y == fill).all())
 
 
@@ -60,7 +48,7 @@ def test_constant_images_stay_constant(aa):
 def test_views_are_read_where_they_lie(aa, channels_last):
     """A crop and a batch slice of a larger tensor give what their dense copies give (and the crop what the box of the whole gives)."""
     rng = np.random.default_rng(3)
-    big = _gpu(rng.integers(0, 256, (4, 3, 61, 83), dtype=np.uint8), channels_last)
+    big = kit_gpu.nchw_gpu(rng.integers(0, 256, (4, 3, 61, 83), dtype=np.uint8), channels_last)
     mf = torch.channels_last if channels_last else torch.contiguous_format
     crop = big[:, :, 7:44, 5:58]  # (odd byte offsets in both layouts)
     assert not crop.is_contiguous(memory_format=mf)
@@ -81,7 +69,7 @@ def test_views_are_read_where_they_lie(aa, channels_last):
 def test_factor_one_with_a_full_box_is_a_copy(aa):
     x = ref.batch((2, 3, 37, 53), 13)
     for cl in (True, False):
-        t = _gpu(x, cl)
+        t = kit_gpu.nchw_gpu(x, cl)
         y = aa.reduce(t, 1)
         assert torch.equal(y, t) and y.data_ptr() != t.data_ptr()
         assert torch.equal(aa.reduce(t, (1, 1), (5, 7, 50, 36)), t[:, :, 7:36, 5:50])
@@ -92,11 +80,11 @@ def test_blocks_wider_than_a_tile(aa):
     rng = np.random.default_rng(4)
     x = rng.integers(0, 256, (1, 3, 5, 3001), dtype=np.uint8)
     for cl in (True, False):
-        got = _nhwc(aa.reduce(_gpu(x, cl), (1400, 2)))
+        got = _nhwc(aa.reduce(kit_gpu.nchw_gpu(x, cl), (1400, 2)))
         want = np.stack([G.reduce_restated(img, (1400, 2)) for img in x.transpose(0, 2, 3, 1)])
         assert np.array_equal(got, want)
 
 
 def test_reduce_torch_op(aa):
-    x = _gpu(ref.batch((2, 3, 37, 53), 13), True)
+    x = kit_gpu.nchw_gpu(ref.batch((2, 3, 37, 53), 13), True)
     assert torch.equal(torch.ops.extension_interpolate.reduce(x, [8, 4], [5, 7, 50, 36]), aa.reduce(x, (8, 4), (5, 7, 50, 36)))

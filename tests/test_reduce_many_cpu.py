@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import kit_golden  # noqa: E402
 import reduce_many_ref as ref  # noqa: E402
 
 from interpolate_antialiasing_amd import _lib, boxmath  # noqa: E402
@@ -70,7 +71,7 @@ def test_fixture_holds_every_case_of_the_issue():
         assert len({ref.plan(name, by[name][5][0], i)[0] for i in range(7) if ref.plan(name, by[name][5][0], i) is not None}) >= 2
     assert by["g_fit"][8] == boxmath.fit_sizes(ref.shapes("g_fit"), shorter=40)
     assert by["g_patch"][8] == boxmath.fit_patch_sizes(ref.shapes("g_patch"), G.PATCH, max_tokens=48)
-    assert os.path.getsize(os.path.join(ref.ROOT, "tests", "golden", "reduce_many.npz")) < 100 * 1024
+    assert os.path.getsize(os.path.join(kit_golden.GOLDEN, "reduce_many.npz")) < 100 * 1024
 
 
 # ---- boxmath.reducing_plans ----------------------------------------------------------------------------------------------------------------

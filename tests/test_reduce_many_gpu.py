@@ -12,8 +12,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import guard_ref  # noqa: E402
+import kit_gpu  # noqa: E402
 import reduce_many_ref as ref  # noqa: E402
 import resize_many_patches_ref as pref  # noqa: E402
+from kit_golden import MODE  # noqa: E402
+from kit_gpu import FORWARD  # noqa: E402
 
 from interpolate_antialiasing_amd import _lib, boxmath, tables  # noqa: E402
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
@@ -21,17 +24,7 @@ from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E4
 pytestmark = pytest.mark.gpu
 
 G = ref.gen()
-MODE = ref.MODE
-FORWARD = {"linear": aa.linear_forward, "cubic": aa.cubic_forward, "box": aa.nearest_forward, "hamming": aa.hamming_forward,
-           "lanczos": aa.lanczos_forward}
 CLASSES = [(name, cls) for name in ref.names() for cls in (("planar",) if G.case(name)[1] == 1 else ("interleaved", "planar"))]
-
-
-def _to_gpu(x_chw, cls):
-    """[C, H, W] numpy -> a GPU tensor [C, H, W] lying in memory as the class says."""
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.ascontiguousarray(x_chw)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
@@ -41,11 +34,7 @@ def _inputs(name, cls):
     if cs[7]:
         x = torch.from_numpy(ref.batch(name)).cuda()
         return x.contiguous(memory_format=torch.channels_last) if cls == "interleaved" else x
-    return [_to_gpu(ref.item(name, i), cls) for i in range(ref.count(name))]
-
-
-def _hwc(t):
-    return t.permute(1, 2, 0).cpu().numpy()
+    return [kit_gpu.to_gpu(ref.item(name, i), cls) for i in range(ref.count(name))]
 
 
 def _plans(name, f):
@@ -82,7 +71,7 @@ def test_reduce_many_equals_pillows_reduce_per_item(name, cls):
         _check_views(name, cls, cs[1], outs)
         for o, i, fac, rb in zip(outs, idx, factors, rboxes):
             assert tuple(o.shape) == (cs[1],) + boxmath.reduced_size(rb, fac)[::-1]
-            ref.assert_reduce_matches_fixture(f"{name}/{f}/{i}", _hwc(o))
+            ref.assert_reduce_matches_fixture(f"{name}/{f}/{i}", kit_gpu.hwc(o))
 
 
 def test_reduce_many_factor_forms_and_whole_images():
@@ -91,9 +80,9 @@ def test_reduce_many_factor_forms_and_whole_images():
     for factors, per_item in ((3, [(3, 3)] * 3), ((2, 5), [(2, 5)] * 3), ([4, (1, 7), (64, 40)], [(4, 4), (1, 7), (64, 40)])):
         outs = aa.reduce_many(imgs, factors)
         for o, x, fac in zip(outs, whole, per_item):
-            assert np.array_equal(_hwc(o), G.reduce_restated(x, fac)), (factors, fac)
+            assert np.array_equal(kit_gpu.hwc(o), G.reduce_restated(x, fac)), (factors, fac)
     outs = aa.reduce_many(imgs, 1, boxes=[(3, 2, 40, 33), None, (0, 0, 1, 1)])  # factor 1 copies the box
-    assert np.array_equal(_hwc(outs[0]), whole[0][2:33, 3:40]) and np.array_equal(_hwc(outs[1]), whole[1]) and tuple(outs[2].shape) == (2, 1, 1)
+    assert np.array_equal(kit_gpu.hwc(outs[0]), whole[0][2:33, 3:40]) and np.array_equal(kit_gpu.hwc(outs[1]), whole[1]) and tuple(outs[2].shape) == (2, 1, 1)
     assert aa.reduce_many([], 2) == [] and aa.reduce_many(_inputs("g_batchbox", "planar")[:0], 2) == []
 
 
@@ -145,7 +134,7 @@ def test_no_cache_is_read_or_written_and_nothing_synchronises(monkeypatch):
     monkeypatch.undo()
     assert (len(tables._cache), len(tables._box_cache), len(aa._plans)) == before
     y = aa.resize_many(small, [30, 45], "bicubic", boxes=b2)
-    ref.assert_resize_matches_fixture("g_mixed/cubic/4", ref.item("g_mixed", 4), _hwc(y[4]))
+    ref.assert_resize_matches_fixture("g_mixed/cubic/4", ref.item("g_mixed", 4), kit_gpu.hwc(y[4]))
 
 
 # 3 ---- through resize_many_to_float
@@ -215,32 +204,12 @@ def test_each_item_equals_the_single_image_call(name, cls):
 
 
 # 7 ---- items read where they lie
-def _pitched_crop(x_chw, cls, k):
-    """The image as a crop of a larger padded buffer: an odd byte offset and a row pitch that is no multiple of 4."""
-    c, h, w = x_chw.shape
-    off = 1 + 2 * (k % 2)
-    if cls == "interleaved":
-        pitch = w * c + 5
-        pitch += 1 if pitch % 4 == 0 else 0
-        buf = torch.full((off + h * pitch + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (1, pitch, c), off)
-    else:
-        pitch = w + 6
-        pitch += 1 if pitch % 4 == 0 else 0
-        plane = h * pitch + 7
-        buf = torch.full((off + c * plane + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (plane, pitch, 1), off)
-    assert pitch % 4 != 0 and v.data_ptr() % 2 == 1
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x_chw)).cuda())
-    return v
-
-
 @pytest.mark.parametrize("cls", ["interleaved", "planar"])
 @pytest.mark.parametrize("name", ["g_mixed", "g_c4", "g_seam"])
 def test_crops_at_odd_offsets_and_pitches_are_read_in_place(name, cls, monkeypatch):
     cs = G.case(name)
     f = cs[5][0]
-    crops = [_pitched_crop(ref.item(name, i), cls, i) for i in range(ref.count(name))]
+    crops = [kit_gpu.pitched_crop(ref.item(name, i), cls, i) for i in range(ref.count(name))]
     imgs, factors, rboxes, idx = _reduce_args(name, f, crops)
     monkeypatch.setattr(torch.Tensor, "contiguous", lambda *a, **k: pytest.fail("an item in the class was copied"))
     outs = aa.reduce_many(imgs, factors, boxes=rboxes)
@@ -248,7 +217,7 @@ def test_crops_at_odd_offsets_and_pitches_are_read_in_place(name, cls, monkeypat
     dense = aa.reduce_many(_reduce_args(name, f, _inputs(name, cls))[0], factors, boxes=rboxes)
     for o, d, i in zip(outs, dense, idx):
         assert o.stride() == d.stride() and torch.equal(o, d)
-        ref.assert_reduce_matches_fixture(f"{name}/{f}/{i}", _hwc(o))
+        ref.assert_reduce_matches_fixture(f"{name}/{f}/{i}", kit_gpu.hwc(o))
 
 
 def test_a_mixed_list_copies_the_minority_and_an_item_in_neither_class():
@@ -263,14 +232,14 @@ def test_a_mixed_list_copies_the_minority_and_an_item_in_neither_class():
         outs = aa.reduce_many(items, factors, boxes=rboxes)
         _check_views(name, cls, 4, outs)
         for o, w in zip(outs, want):
-            assert np.array_equal(_hwc(o), w)
+            assert np.array_equal(kit_gpu.hwc(o), w)
     wide = torch.zeros((4, 64, 80), dtype=torch.uint8, device="cuda")
     odd = wide[:, :, ::2]  # columns two bytes apart: neither class
     odd.copy_(planar[2])
     outs = aa.reduce_many([inter[0], inter[1], odd], factors, boxes=rboxes)
     _check_views(name, "interleaved", 4, outs)
     for o, w in zip(outs, want):
-        assert np.array_equal(_hwc(o), w)
+        assert np.array_equal(kit_gpu.hwc(o), w)
     assert full[2] is None
 
 
@@ -318,7 +287,7 @@ def test_non_default_stream():
         y = aa.resize_many(small, [4, 375], MODE[f], boxes=b2)
     s.synchronize()
     for i in range(2):
-        ref.assert_resize_matches_fixture(f"{name}/{f}/{i}", ref.item(name, i), _hwc(y[i]))
+        ref.assert_resize_matches_fixture(f"{name}/{f}/{i}", ref.item(name, i), kit_gpu.hwc(y[i]))
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
@@ -331,4 +300,4 @@ def test_non_current_device():
     y = aa.resize_many(small, [4, 375], MODE[f], boxes=b2)
     torch.cuda.synchronize(1)
     for i in range(2):
-        ref.assert_resize_matches_fixture(f"{name}/{f}/{i}", ref.item(name, i), _hwc(y[i]))
+        ref.assert_resize_matches_fixture(f"{name}/{f}/{i}", ref.item(name, i), kit_gpu.hwc(y[i]))

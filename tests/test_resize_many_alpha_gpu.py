@@ -13,7 +13,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import guard_ref  # noqa: E402
+import kit_golden  # noqa: E402
+import kit_gpu  # noqa: E402
 import resize_many_alpha_ref as ref  # noqa: E402
+from kit_golden import MEAN, STD  # noqa: E402
+from kit_gpu import FORWARD  # noqa: E402
 
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
 from interpolate_antialiasing_amd import tables  # noqa: E402
@@ -22,26 +26,15 @@ pytestmark = pytest.mark.gpu
 
 G = ref.gen()
 CASE_NAMES = [cs[0] for cs in G.CASES]
-FORWARD = {"linear": aa.linear_forward, "cubic": aa.cubic_forward, "box": aa.nearest_forward, "hamming": aa.hamming_forward,
-           "lanczos": aa.lanczos_forward}
-MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "nearest", "hamming": "hamming", "lanczos": "lanczos"}
+MODE = {**kit_golden.MODE, "box": "nearest"}  # (on purpose: the alias of the box filter's mode)
 CLS = ["interleaved", "planar"]
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
-MEAN = [123.675, 116.28, 103.53, 127.5]
-STD = [58.395, 57.12, 57.375, 64.0]
-
-
-def _to_gpu(x_chw, cls):
-    """[C, H, W] numpy -> a GPU tensor [C, H, W] lying in memory as the class says."""
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.ascontiguousarray(x_chw)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(name, cls):
     """The case's images on the GPU (shared between tests, never written)."""
-    return [_to_gpu(ref.item(name, i), cls) for i in range(len(G.case(name)[5]))]
+    return [kit_gpu.to_gpu(ref.item(name, i), cls) for i in range(len(G.case(name)[5]))]
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,26 +43,8 @@ def _bytes(name, f, alpha=True):
     return torch.from_numpy(np.stack([ref.restated(name, f, i, alpha).transpose(2, 0, 1) for i in range(len(G.case(name)[5]))]))
 
 
-def _check_against_fixture(name, f, y):
-    cs = G.case(name)
-    assert tuple(y.shape) == (len(cs[5]), cs[1]) + tuple(cs[2]) and y.dtype == torch.uint8
-    got = y.cpu()
-    for i in range(len(cs[5])):
-        ref.assert_matches_fixture(f"{name}/{f}/{i}", ref.item(name, i), got[i].permute(1, 2, 0).numpy())
-    assert torch.equal(got, _bytes(name, f)), (name, f)
-
-
-def _assert_class_format(y, cls):
-    assert y.is_contiguous(memory_format=torch.channels_last) == (cls == "interleaved") and y.is_contiguous() == (cls == "planar")
-
-
-def _assert_equal_u8(got, want, what):
-    got, want = got.cpu(), want.cpu()
-    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), what
-    if not torch.equal(got, want):
-        bad = (got != want).nonzero()
-        raise AssertionError(f"{what}: {len(bad)} of {got.numel()} bytes differ, first at {bad[0].tolist()}: "
-                             f"{got[tuple(bad[0])].item()} != {want[tuple(bad[0])].item()}")
+# (a case keeps its items at [5]; the whole result is the restatement's too)
+_check_against_fixture = functools.partial(kit_gpu.check_against_fixture, ref, 5, restated=_bytes)
 
 
 # ---- the fixture ---------------------------------------------------------------------------------------------------------------------
@@ -79,7 +54,7 @@ def test_every_case_filter_and_layout_class_equals_pillow(name, cls):
     cs = G.case(name)
     for f in cs[4]:
         y = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], alpha=True, **ref.kwargs(name))
-        _assert_class_format(y, cls)
+        kit_gpu.assert_class_format(y, cls, cs[1])
         _check_against_fixture(name, f, y)
 
 
@@ -97,7 +72,7 @@ def test_each_item_equals_the_single_image_alpha_call_pasted(name, cls):
             y0, y1, x0, x1 = max(0, py), min(oh, py + vh), max(0, px), min(ow, px + vw)
             if y1 > y0 and x1 > x0:
                 want[:, y0:y1, x0:x1] = one[:, y0 - py:y1 - py, x0 - px:x1 - px]
-            _assert_equal_u8(y[i], want, (name, f, i))
+            kit_gpu.assert_bits(y[i], want, (name, f, i))
 
 
 def test_alpha_false_on_the_same_inputs_is_todays_result():
@@ -109,40 +84,20 @@ def test_alpha_false_on_the_same_inputs_is_todays_result():
                 before = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], **ref.kwargs(name))
                 with_alpha = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], alpha=True, **ref.kwargs(name))
                 after = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], alpha=False, **ref.kwargs(name))
-                _assert_equal_u8(before, _bytes(name, f, False), (name, cls, f))
-                _assert_equal_u8(after, _bytes(name, f, False), (name, cls, f))
+                kit_gpu.assert_bits(before, _bytes(name, f, False), (name, cls, f))
+                kit_gpu.assert_bits(after, _bytes(name, f, False), (name, cls, f))
                 assert not torch.equal(with_alpha.cpu(), _bytes(name, f, False))
 
 
 # ---- items read where they lie -------------------------------------------------------------------------------------------------------
-def _pitched_crop(x_chw, cls, k):
-    """The image as a crop of a larger padded buffer: an odd byte offset and a row pitch that is no multiple of 4."""
-    c, h, w = x_chw.shape
-    off = 1 + 2 * (k % 2)
-    if cls == "interleaved":
-        pitch = w * c + 5
-        pitch += 1 if pitch % 4 == 0 else 0
-        buf = torch.full((off + h * pitch + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (1, pitch, c), off)
-    else:
-        pitch = w + 6
-        pitch += 1 if pitch % 4 == 0 else 0
-        plane = h * pitch + 7
-        buf = torch.full((off + c * plane + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (plane, pitch, 1), off)
-    assert pitch % 4 != 0 and v.data_ptr() % 2 == 1
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x_chw)).cuda())
-    return v
-
-
 @pytest.mark.parametrize("cls", CLS)
 @pytest.mark.parametrize("name", ["a_rgba", "a_la", "a_placed4", "a_placed2"])
 def test_crops_at_odd_offsets_and_pitches_are_read_in_place(name, cls):
     cs = G.case(name)
-    crops = [_pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[5]))]
+    crops = [kit_gpu.pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[5]))]
     for f in cs[4]:
         y = aa.resize_many(crops, list(cs[2]), MODE[f], alpha=True, **ref.kwargs(name))
-        _assert_class_format(y, cls)
+        kit_gpu.assert_class_format(y, cls, cs[1])
         _check_against_fixture(name, f, y)
 
 
@@ -164,7 +119,7 @@ def test_rgba_planes_sliced_out_of_a_five_plane_buffer(first):
         items.append(v)
     for f in ("cubic", "lanczos"):
         y = aa.resize_many(items, list(cs[2]), MODE[f], alpha=True, boxes=ref.boxes(name))
-        _assert_class_format(y, "planar")
+        kit_gpu.assert_class_format(y, "planar", cs[1])
         _check_against_fixture(name, f, y)
 
 
@@ -177,10 +132,10 @@ def test_one_batch_tensor_in_both_memory_formats(cls):
     x = x.contiguous(memory_format=torch.channels_last) if cls == "interleaved" else x.contiguous()
     want = torch.from_numpy(np.stack([G.resize_alpha_restated("cubic", xs[i].transpose(1, 2, 0), oh, ow, boxes[i]).transpose(2, 0, 1) for i in range(n)]))
     y = aa.resize_many(x, [oh, ow], "bicubic", boxes=boxes, alpha=True)
-    _assert_class_format(y, cls)
-    _assert_equal_u8(y, want, cls)
+    kit_gpu.assert_class_format(y, cls, c)
+    kit_gpu.assert_bits(y, want, cls)
     same = aa.resize_many(x, [h, w], "bicubic", alpha=True)  # every slice is Pillow's copy
-    _assert_equal_u8(same, x, cls)
+    kit_gpu.assert_bits(same, x, cls)
 
 
 @pytest.mark.parametrize("minority", CLS)
@@ -190,7 +145,7 @@ def test_a_list_mixing_the_classes_copies_the_minority(minority):
     majority = "planar" if minority == "interleaved" else "interleaved"
     imgs = [_inputs(name, minority if i == 2 else majority)[i] for i in range(len(cs[5]))]
     y = aa.resize_many(imgs, list(cs[2]), "bicubic", alpha=True, boxes=ref.boxes(name))
-    _assert_class_format(y, majority)
+    kit_gpu.assert_class_format(y, majority, cs[1])
     _check_against_fixture(name, "cubic", y)
 
 
@@ -199,29 +154,14 @@ def test_a_list_mixing_the_classes_copies_the_minority(minority):
 def test_hulls_across_a_staging_chunk_seam(c, cls, h, w):
     x = ref.seam_item(c, h, w, 7)
     want = torch.from_numpy(ref.seam_restated(c, h, w, 7).transpose(2, 0, 1).copy())[None]
-    for img in (_to_gpu(x, cls), _pitched_crop(x, cls, 0)):
+    for img in (kit_gpu.to_gpu(x, cls), kit_gpu.pitched_crop(x, cls, 0)):
         y = aa.resize_many([img], list(ref.SEAM_OUT), "bilinear", alpha=True)
-        _assert_class_format(y, cls)
-        _assert_equal_u8(y, want, (c, cls, h, w))
+        kit_gpu.assert_class_format(y, cls, c)
+        kit_gpu.assert_bits(y, want, (c, cls, h, w))
     assert not np.array_equal(ref.seam_restated(c, h, w, 7), ref.seam_restated(c, h, w, 7, False))
 
 
 # ---- resize_many_to_float ------------------------------------------------------------------------------------------------------------
-def _bits(t):
-    t = t.cpu().contiguous()
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def _convert(u, dtype, flips, normalize=True):
-    """The docstring's definition, by torch on the CPU: u [N, C, oH, oW] uint8 -> the expected tensor."""
-    c = u.shape[1]
-    f = u.float()
-    if normalize:
-        f = (f - torch.tensor(MEAN[:c]).view(1, c, 1, 1)) / torch.tensor(STD[:c]).view(1, c, 1, 1)
-    y = f.to(dtype)
-    return torch.stack([y[i].flip(-1) if flips[i] else y[i] for i in range(len(flips))])
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16", "bf16"])
 @pytest.mark.parametrize("cls", CLS)
 @pytest.mark.parametrize("name", ["a_rgba", "a_la", "a_placed4", "a_placed2"])
@@ -240,7 +180,7 @@ def test_to_float_is_the_alpha_bytes_converted(name, cls, dtype):
                                             **kw, **ref.kwargs(name))
                 nhwc = fmt == "nhwc" or (fmt is None and cls == "interleaved")
                 assert y.is_contiguous(memory_format=torch.channels_last) == nhwc and y.is_contiguous() == (not nhwc)
-                assert y.dtype == dtype and torch.equal(_bits(y), _bits(_convert(u, dtype, fl, normalize))), (name, f, cls, fmt, dtype, normalize)
+                assert y.dtype == dtype and torch.equal(kit_gpu.bits(y), kit_gpu.bits(kit_gpu.convert(u, dtype, normalize, fl))), (name, f, cls, fmt, dtype, normalize)
 
 
 def test_to_float_without_alpha_is_unchanged():
@@ -248,7 +188,7 @@ def test_to_float_without_alpha_is_unchanged():
     cs = G.case(name)
     for cls in CLS:
         y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], out_dtype=torch.float32, out_format="nchw", boxes=ref.boxes(name))
-        assert torch.equal(_bits(y), _bits(_bytes(name, f, False).float()))
+        assert torch.equal(kit_gpu.bits(y), kit_gpu.bits(_bytes(name, f, False).float()))
 
 
 # ---- guard bands ---------------------------------------------------------------------------------------------------------------------
@@ -291,7 +231,7 @@ def test_guard_bands_bf16_nchw(monkeypatch, name, cls):
         rec.check()
         assert len(rec.records) == 3 and rec.record_of(y) is not None
         assert guard_ref.unwritten_float(y) == 0
-    assert torch.equal(_bits(y), _bits(_convert(_bytes(name, f), torch.bfloat16, flips)))
+    assert torch.equal(kit_gpu.bits(y), kit_gpu.bits(kit_gpu.convert(_bytes(name, f), torch.bfloat16, flips=flips)))
     for t, b in zip(imgs, before):
         assert torch.equal(t.cpu(), b)
 
@@ -319,23 +259,11 @@ def test_guard_bands_of_a_seam_case(monkeypatch, c, cls, h, w):
         z = aa.resize_many_to_float([img], list(ref.SEAM_OUT), "bilinear", out_dtype=torch.float16, alpha=True)
         rec.check()
         assert guard_ref.unwritten_float(z) == 0
-    assert torch.equal(_bits(z), _bits(want.to(torch.float16)))
+    assert torch.equal(kit_gpu.bits(z), kit_gpu.bits(want.to(torch.float16)))
     assert torch.equal(buf, held)
 
 
 # ---- the call's promises -------------------------------------------------------------------------------------------------------------
-def _count_launches(fn):
-    """Kernel launches of one fn() from torch's profiler (tools/resize_many_bench.py count_launches)."""
-    from torch.profiler import ProfilerActivity, profile
-
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and "memcpy" not in e.name.lower()
-            and "memset" not in e.name.lower()]
-
-
 def test_three_launches_whatever_n():
     name = "a_placed4"
     cs = G.case(name)
@@ -350,7 +278,7 @@ def test_three_launches_whatever_n():
     }
     for k, fn in calls.items():
         fn()  # (module load and allocator warm-up stay outside the count)
-        names = _count_launches(fn)
+        names = kit_gpu.count_launches(fn)
         assert len(names) == 3, (k, names)
         assert [sum(1 for nm in names if part in nm) for part in ("many_tables", "many_hpass", "many_vpass")] == [1, 1, 1], (k, names)
 

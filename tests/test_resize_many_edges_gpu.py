@@ -7,51 +7,38 @@ import functools
 import os
 import sys
 
-import numpy as np
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import guard_ref  # noqa: E402
+import kit_gpu  # noqa: E402
 import resize_many_edges_ref as ref  # noqa: E402
-from test_resize_many_gpu import _pitched_crop  # noqa: E402
+from kit_golden import MEAN, MODE, STD  # noqa: E402
+from kit_gpu import FORWARD  # noqa: E402
 
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 G = ref.gen()
-MODE = ref.MODE
-FORWARD = {"linear": aa.linear_forward, "cubic": aa.cubic_forward, "box": aa.nearest_forward}
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
 FORMATS = ["nchw", "nhwc"]
-MEAN = [123.675, 116.28, 103.53, 127.5]
-STD = [58.395, 57.12, 57.375, 64.0]
 ALL = [cs.name for cs in G.CASES]
-
-
-def _to_gpu(x_chw, cls):
-    """[C, H, W] numpy -> a GPU tensor [C, H, W] lying in memory as the class says."""
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.ascontiguousarray(x_chw)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(name, cls):
     """The case's images on the GPU (shared between tests, never written)."""
-    return [_to_gpu(ref.item(name, i), cls) for i in range(len(G.case(name).items))]
+    return [kit_gpu.to_gpu(ref.item(name, i), cls) for i in range(len(G.case(name).items))]
 
 
 def _check(name, f, cls, y):
     """y, the call's uint8 result, is Pillow's: against the restatement first (a mismatch names its work units), then the fixture."""
     cs = G.case(name)
     assert tuple(y.shape) == (len(cs.items), cs.c) + tuple(cs.out) and y.dtype == torch.uint8
-    if cs.c > 1:
-        assert y.is_contiguous(memory_format=torch.channels_last) == (cls == "interleaved") and y.is_contiguous() == (cls == "planar")
-    else:
-        assert y.is_contiguous()
+    kit_gpu.assert_class_format(y, cls, cs.c)
     got = y.cpu()
     wrong = ref.where(name, f, cls, got.numpy(), ref.restated_batch(name, f))
     assert wrong is None, wrong
@@ -71,7 +58,7 @@ def test_every_case_filter_and_layout_class_equals_pillow(name, cls):
 def test_chunked_rows_of_crops_at_odd_offsets_and_pitches(name, cls):
     """Every chunk of a row starts at another alignment, and no two items share one."""
     cs = G.case(name)
-    crops = [_pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs.items))]
+    crops = [kit_gpu.pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs.items))]
     for f in cs.filters:
         y = aa.resize_many(crops, list(cs.out), MODE[f], **ref.kw(name))
         dense = aa.resize_many(_inputs(name, cls), list(cs.out), MODE[f], **ref.kw(name))
@@ -91,31 +78,16 @@ def test_each_item_equals_the_single_image_call(name, cls):
 
 
 # ---- resize_many_to_float ----------------------------------------------------------------------------------------------------------------
-def _convert(b, dtype, flips):
-    """The definition, by torch on the CPU: b [N, C, oH, oW] uint8 -> the expected tensor."""
-    c = b.shape[1]
-    y = ((b.float() - torch.tensor(MEAN[:c]).view(1, c, 1, 1)) / torch.tensor(STD[:c]).view(1, c, 1, 1)).to(dtype)
-    if flips is not None:
-        y = torch.stack([y[i].flip(-1) if flips[i] else y[i] for i in range(len(flips))])
-    return y
-
-
-def _bits(t):
-    t = t.cpu().contiguous()
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def _assert_bits(got, want, name, f, cls, fmt, flips):
+def _piece(name, cls, flips):
+    """For kit_gpu.assert_bits: the column of the unflipped row a wrong element was computed as, and its piece of the converting pass."""
     cs = G.case(name)
-    what = f"{name}/{f}/{cls}/{fmt}/{got.dtype}/flips {flips}"
-    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), what
-    a, b = _bits(got), _bits(want)
-    if not torch.equal(a, b):
-        n, ch, y, x = (a != b).nonzero()[0].tolist()
-        e = ref.elem_bytes(cs.c, cls)
-        src = cs.out[1] - 1 - x if flips is not None and flips[n] else x  # the column of the unflipped row this element was computed as
-        raise AssertionError(f"{what}: {int((a != b).sum())} of {a.numel()} elements differ, first at {[n, ch, y, x]}: {got.cpu()[n, ch, y, x].item()} != "
-                             f"{want[n, ch, y, x].item()}; computed as column {src} = piece {src // ref.constants()['VPIXELS'][e]} of the converting pass")
+
+    def explain(at):
+        n, _, _, x = at
+        src = cs.out[1] - 1 - x if flips is not None and flips[n] else x
+        return f"computed as column {src} = piece {src // ref.constants()['VPIXELS'][ref.elem_bytes(cs.c, cls)]} of the converting pass"
+
+    return explain
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16", "bf16"])
@@ -126,13 +98,13 @@ def test_to_float_is_the_restated_bytes_converted(name, cls, dtype):
     for f in cs.filters:
         b = torch.from_numpy(ref.restated_batch(name, f))
         for flips in (None, [i % 2 == 0 for i in range(n)]):
-            want = _convert(b, dtype, flips)
+            want = kit_gpu.convert(b, dtype, flips=flips)
             for fmt in FORMATS:
                 y = aa.resize_many_to_float(_inputs(name, cls), list(cs.out), MODE[f], flips=flips, out_dtype=dtype, out_format=fmt, mean=MEAN[:c],
                                             std=STD[:c], **ref.kw(name))
                 if c > 1:
                     assert y.is_contiguous(memory_format=torch.channels_last) == (fmt == "nhwc") and y.is_contiguous() == (fmt == "nchw")
-                _assert_bits(y, want, name, f, cls, fmt, flips)
+                kit_gpu.assert_bits(y, want, f"{name}/{f}/{cls}/{fmt}/{y.dtype}/flips {flips}", _piece(name, cls, flips))
 
 
 # ---- guard bands -------------------------------------------------------------------------------------------------------------------------
@@ -163,7 +135,7 @@ def test_guard_bands_bf16(monkeypatch, name, cls, lead):
     n, c = len(cs.items), cs.c
     flips = [i % 2 == 1 for i in range(n)]
     f = cs.filters[0]
-    want = _convert(torch.from_numpy(ref.restated_batch(name, f)), torch.bfloat16, flips)
+    want = kit_gpu.convert(torch.from_numpy(ref.restated_batch(name, f)), torch.bfloat16, flips=flips)
     for fmt in FORMATS:
         with guard_ref.guarded(monkeypatch, lead) as rec:
             y = aa.resize_many_to_float(_inputs(name, cls), list(cs.out), MODE[f], flips=flips, out_dtype=torch.bfloat16, out_format=fmt, mean=MEAN[:c],
@@ -171,4 +143,4 @@ def test_guard_bands_bf16(monkeypatch, name, cls, lead):
             rec.check()
             assert len(rec.records) == 3 and rec.record_of(y) is not None and y.data_ptr() % 4 == 2 * lead
             assert guard_ref.unwritten_float(y) == 0, (name, cls, fmt, lead)
-        _assert_bits(y, want, name, f, cls, fmt, flips)
+        kit_gpu.assert_bits(y, want, f"{name}/{f}/{cls}/{fmt}/{y.dtype}/flips {flips}", _piece(name, cls, flips))

@@ -9,12 +9,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from kit_golden import MEAN, STD  # noqa: E402
+
 from interpolate_antialiasing_amd import _lib  # noqa: E402
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
 
 BAD_DTYPE, BAD_SHAPE, WORKSPACE = -2, -4, -6
-MEAN = [123.675, 116.28, 103.53, 127.5]
-STD = [58.395, 57.12, 57.375, 64.0]
 
 
 def _u8(c=3, h=20, w=30):

@@ -13,7 +13,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import kit_gpu  # noqa: E402
 import resize_many_ref as ref  # noqa: E402
+from kit_golden import MEAN, MODE, STD  # noqa: E402
 
 from interpolate_antialiasing_amd import _lib  # noqa: E402
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
@@ -23,31 +25,17 @@ pytestmark = pytest.mark.gpu
 
 G = ref.gen()
 CASE_NAMES = [cs[0] for cs in G.CASES]
-MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "box", "hamming": "hamming", "lanczos": "lanczos"}
 CLASSES = [(name, cls) for name in CASE_NAMES for cls in (("planar",) if G.case(name)[1] == 1 else ("interleaved", "planar"))]
 NORMALISED = [(name, cls) for name, cls in CLASSES if name in ("m_mixed", "m_c1", "m_c2", "m_c4", "m_strips", "m_tiny37")]
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
 FORMATS = ["nchw", "nhwc"]
-MEAN = [123.675, 116.28, 103.53, 127.5]
-STD = [58.395, 57.12, 57.375, 64.0]
-
-
-def _to_gpu(x_chw, cls):
-    """[C, H, W] numpy -> a GPU tensor [C, H, W] lying in memory as the class says."""
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.ascontiguousarray(x_chw)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(name, cls):
     """The case's images on the GPU (shared between tests, never written): a list, or one [N, C, H, W] tensor for a batch case."""
     cs = G.case(name)
-    items = [_to_gpu(ref.item(name, i), cls) for i in range(len(cs[3]))]
-    if cs[6]:
-        x = torch.stack(items)
-        return x.contiguous(memory_format=torch.channels_last) if cls == "interleaved" else x.contiguous()
-    return items
+    return kit_gpu.batch_or_list([kit_gpu.to_gpu(ref.item(name, i), cls) for i in range(len(cs[3]))], cs[6], cls)
 
 
 def _boxes(name):
@@ -59,32 +47,6 @@ def _bytes(name, f):
     """Pillow's bytes of one case and filter from the CPU restatement: [N, C, oH, oW] uint8 on the CPU (shared, never written)."""
     cs = G.case(name)
     return torch.from_numpy(np.stack([G.restated(cs, f, i, ref.item(name, i)).transpose(2, 0, 1) for i in range(len(cs[3]))]))
-
-
-def _convert(b, dtype, norm, flips=None):
-    """The definition, by torch on the CPU: b [N, C, oH, oW] uint8 -> the expected tensor."""
-    c = b.shape[1]
-    f = b.float()
-    if norm:
-        f = (f - torch.tensor(MEAN[:c]).view(1, c, 1, 1)) / torch.tensor(STD[:c]).view(1, c, 1, 1)
-    y = f.to(dtype)
-    if flips is not None:
-        y = torch.stack([y[i].flip(-1) if flips[i] else y[i] for i in range(len(flips))])
-    return y
-
-
-def _bits(t):
-    t = t.cpu().contiguous()
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def _assert_bits(got, want, what):
-    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), what
-    a, b = _bits(got), _bits(want)
-    if not torch.equal(a, b):
-        bad = (a != b).nonzero()
-        raise AssertionError(f"{what}: {len(bad)} of {a.numel()} elements differ, first at {bad[0].tolist()}: "
-                             f"{got.cpu()[tuple(bad[0])].item()} != {want[tuple(bad[0])].item()}")
 
 
 def _assert_format(y, fmt, c):
@@ -113,7 +75,7 @@ def test_identity_every_case_filter_class_and_format_is_pillows_bytes(name, cls)
         # out_format None follows the class of the items
         y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[cs[4][0]], boxes=_boxes(name))
         _assert_format(y, "nhwc" if cls == "interleaved" else "nchw", cs[1])
-        _assert_bits(y, _convert(_bytes(name, cs[4][0]), torch.float32, False), f"{name}/{cls}/default format")
+        kit_gpu.assert_bits(y, kit_gpu.convert(_bytes(name, cs[4][0]), torch.float32, False), f"{name}/{cls}/default format")
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16", "bf16"])
@@ -121,16 +83,16 @@ def test_identity_every_case_filter_class_and_format_is_pillows_bytes(name, cls)
 def test_normalised_every_dtype_class_and_format(name, cls, dtype):
     cs = G.case(name)
     for f in cs[4]:
-        want = _convert(_bytes(name, f), dtype, True)
+        want = kit_gpu.convert(_bytes(name, f), dtype, True)
         for fmt in FORMATS:
             y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), out_dtype=dtype, out_format=fmt,
                                         **_norm(cs[1]))
             _assert_format(y, fmt, cs[1])
-            _assert_bits(y, want, f"{name}/{f}/{cls}/{fmt}/{dtype}")
+            kit_gpu.assert_bits(y, want, f"{name}/{f}/{cls}/{fmt}/{dtype}")
     # without mean / std the 16-bit types are the byte, converted
     f = cs[4][0]
     y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), out_dtype=dtype, out_format="nchw")
-    _assert_bits(y, _convert(_bytes(name, f), dtype, False), f"{name}/{f}/{cls}/no normalisation/{dtype}")
+    kit_gpu.assert_bits(y, kit_gpu.convert(_bytes(name, f), dtype, False), f"{name}/{f}/{cls}/no normalisation/{dtype}")
 
 
 @pytest.mark.parametrize("cls", ["interleaved", "planar"])
@@ -139,24 +101,24 @@ def test_normalised_every_dtype_class_and_format(name, cls, dtype):
 def test_flips_mirror_the_flagged_items_and_leave_the_others(name, f, flips, cls):
     cs = G.case(name)
     for dtype in DTYPES:
-        plain = _convert(_bytes(name, f), dtype, True)
-        want = _convert(_bytes(name, f), dtype, True, flips)
+        plain = kit_gpu.convert(_bytes(name, f), dtype, True)
+        want = kit_gpu.convert(_bytes(name, f), dtype, True, flips)
         for i, fl in enumerate(flips):  # (what the expectation itself says: flagged items mirrored, the others untouched)
-            assert torch.equal(_bits(want[i]), _bits(plain[i].flip(-1) if fl else plain[i]))
+            assert torch.equal(kit_gpu.bits(want[i]), kit_gpu.bits(plain[i].flip(-1) if fl else plain[i]))
         for fmt in FORMATS:
             y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), flips=flips, out_dtype=dtype,
                                         out_format=fmt, **_norm(cs[1]))
             _assert_format(y, fmt, cs[1])
-            _assert_bits(y, want, f"{name}/{f}/{cls}/{fmt}/{dtype}/flips")
+            kit_gpu.assert_bits(y, want, f"{name}/{f}/{cls}/{fmt}/{dtype}/flips")
     # truthy / falsy entries of any kind
     y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name), flips=[int(v) for v in flips],
                                 out_dtype=torch.bfloat16, out_format="nchw", **_norm(cs[1]))
-    _assert_bits(y, _convert(_bytes(name, f), torch.bfloat16, True, flips), f"{name}/{f}/{cls}/int flips")
+    kit_gpu.assert_bits(y, kit_gpu.convert(_bytes(name, f), torch.bfloat16, True, flips), f"{name}/{f}/{cls}/int flips")
 
 
 def _adhoc(c, sizes, cls, seed):
     rng = np.random.default_rng(seed)
-    return [_to_gpu(rng.integers(0, 256, (c, h, w), dtype=np.uint8), cls) for h, w in sizes]
+    return [kit_gpu.to_gpu(rng.integers(0, 256, (c, h, w), dtype=np.uint8), cls) for h, w in sizes]
 
 
 def _adhoc_restated(imgs, size, f, boxes=None):
@@ -175,7 +137,7 @@ def test_flips_of_outputs_one_and_two_columns_wide(ow):
     assert torch.equal(u, _adhoc_restated(imgs, (7, ow), "cubic", boxes))  # (what is converted below is Pillow's, not the package's own)
     y = aa.resize_many_to_float(imgs, [7, ow], "bicubic", boxes=boxes, flips=flips, out_dtype=torch.bfloat16, out_format="nchw", **_norm(3))
     assert y.is_contiguous()
-    _assert_bits(y, _convert(u, torch.bfloat16, True, flips), f"ow = {ow}")
+    kit_gpu.assert_bits(y, kit_gpu.convert(u, torch.bfloat16, True, flips), f"ow = {ow}")
 
 
 # Rows longer than one workgroup's piece of the converting pass (1024 / 512 / 256 / 256 pixels for 1 / 2 / 3 / 4 bytes per pixel), the last
@@ -188,45 +150,25 @@ def test_rows_of_several_pieces(c, cls, ow):
     u = aa.resize_many(imgs, [3, ow], "bilinear").cpu()
     assert torch.equal(u, _adhoc_restated(imgs, (3, ow), "linear"))  # (what is converted below is Pillow's, not the package's own)
     for dtype in DTYPES:
-        want = _convert(u, dtype, True, flips)
+        want = kit_gpu.convert(u, dtype, True, flips)
         for fmt in FORMATS:
             y = aa.resize_many_to_float(imgs, [3, ow], "bilinear", flips=flips, out_dtype=dtype, out_format=fmt, **_norm(c))
             _assert_format(y, fmt, c)
-            _assert_bits(y, want, f"C = {c}/{cls}/ow = {ow}/{fmt}/{dtype}")
-
-
-def _pitched_crop(x_chw, cls, k):
-    """The image as a crop of a larger padded buffer: an odd byte offset and a row pitch that is no multiple of 4."""
-    c, h, w = x_chw.shape
-    off = 1 + 2 * (k % 2)
-    if cls == "interleaved":
-        pitch = w * c + 5
-        pitch += 1 if pitch % 4 == 0 else 0
-        buf = torch.full((off + h * pitch + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (1, pitch, c), off)
-    else:
-        pitch = w + 6
-        pitch += 1 if pitch % 4 == 0 else 0
-        plane = h * pitch + 7
-        buf = torch.full((off + c * plane + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (plane, pitch, 1), off)
-    assert pitch % 4 != 0 and v.data_ptr() % 2 == 1
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x_chw)).cuda())
-    return v
+            kit_gpu.assert_bits(y, want, f"C = {c}/{cls}/ow = {ow}/{fmt}/{dtype}")
 
 
 @pytest.mark.parametrize("cls", ["interleaved", "planar"])
 @pytest.mark.parametrize("name", ["m_mixed", "m_c4"])
 def test_crops_at_odd_offsets_and_pitches_equal_the_dense_call(name, cls):
     cs = G.case(name)
-    crops = [_pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[3]))]
+    crops = [kit_gpu.pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[3]))]
     flips = [i % 3 == 0 for i in range(len(cs[3]))]
     for f in cs[4]:
         kw = dict(boxes=_boxes(name), flips=flips, out_dtype=torch.float16, out_format="nchw", **_norm(cs[1]))
         y = aa.resize_many_to_float(crops, list(cs[2]), MODE[f], **kw)
         dense = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], **kw)
-        assert y.stride() == dense.stride() and torch.equal(_bits(y), _bits(dense))
-        _assert_bits(y, _convert(_bytes(name, f), torch.float16, True, flips), f"{name}/{f}/{cls}/crops")
+        assert y.stride() == dense.stride() and torch.equal(kit_gpu.bits(y), kit_gpu.bits(dense))
+        kit_gpu.assert_bits(y, kit_gpu.convert(_bytes(name, f), torch.float16, True, flips), f"{name}/{f}/{cls}/crops")
 
 
 def test_c_abi_output_that_is_only_two_byte_aligned():
@@ -270,9 +212,9 @@ def test_c_abi_output_that_is_only_two_byte_aligned():
     assert rc == 0
     torch.cuda.synchronize()
     got = buf.cpu()
-    assert torch.equal(_bits(got[1:1 + numel].view(n, c, oh, ow)), _bits(aligned))
+    assert torch.equal(kit_gpu.bits(got[1:1 + numel].view(n, c, oh, ow)), kit_gpu.bits(aligned))
     assert (got[:1] == sentinel).all() and (got[1 + numel:] == sentinel).all()
-    _assert_bits(aligned, _convert(_bytes(name, f), torch.float16, True, flips), "the aligned call")
+    kit_gpu.assert_bits(aligned, kit_gpu.convert(_bytes(name, f), torch.float16, True, flips), "the aligned call")
 
 
 def _strips_call(imgs, **kw):
@@ -281,7 +223,7 @@ def _strips_call(imgs, **kw):
 
 
 def _strips_want():
-    return _convert(_bytes("m_strips", "hamming"), torch.bfloat16, True, [True, False])
+    return kit_gpu.convert(_bytes("m_strips", "hamming"), torch.bfloat16, True, [True, False])
 
 
 def test_non_default_stream():
@@ -291,7 +233,7 @@ def test_non_default_stream():
     with torch.cuda.stream(s):
         y = _strips_call(imgs)
     s.synchronize()
-    _assert_bits(y, _strips_want(), "non-default stream")
+    kit_gpu.assert_bits(y, _strips_want(), "non-default stream")
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
@@ -301,7 +243,7 @@ def test_non_current_device():
     y = _strips_call(imgs)
     assert y.device == imgs[0].device and torch.cuda.current_device() == 0
     torch.cuda.synchronize(1)
-    _assert_bits(y, _strips_want(), "non-current device")
+    kit_gpu.assert_bits(y, _strips_want(), "non-current device")
 
 
 def test_torch_op():
@@ -313,27 +255,27 @@ def test_torch_op():
     flips = [False, True, True]
     y = torch.ops.extension_interpolate.resize_many_to_float(imgs, [19, 77], "bicubic", flat, flips, torch.bfloat16, "nchw", MEAN[:2], STD[:2])
     assert y.is_contiguous()
-    _assert_bits(y, _convert(_bytes(name, "cubic"), torch.bfloat16, True, flips), "the torch op")
+    kit_gpu.assert_bits(y, kit_gpu.convert(_bytes(name, "cubic"), torch.bfloat16, True, flips), "the torch op")
     y = torch.ops.extension_interpolate.resize_many_to_float(imgs, [19, 77], "bicubic", flat)
     assert y.dtype == torch.float32 and y.is_contiguous(memory_format=torch.channels_last)
-    _assert_bits(y, _convert(_bytes(name, "cubic"), torch.float32, False), "the torch op, defaults")
+    kit_gpu.assert_bits(y, kit_gpu.convert(_bytes(name, "cubic"), torch.float32, False), "the torch op, defaults")
 
 
 def test_a_mixed_list_copies_the_minority():
     name = "m_c4"
     inter, planar = _inputs(name, "interleaved"), _inputs(name, "planar")
     flips = [True, False, True]
-    want = _convert(_bytes(name, "cubic"), torch.float16, True, flips)
+    want = kit_gpu.convert(_bytes(name, "cubic"), torch.float16, True, flips)
     kw = dict(boxes=_boxes(name), flips=flips, out_dtype=torch.float16, **_norm(4))
     y = aa.resize_many_to_float([inter[0], planar[1], inter[2]], [19, 77], "bicubic", **kw)
     assert y.is_contiguous(memory_format=torch.channels_last)  # (out_format None: the class of the call)
-    _assert_bits(y, want, "two interleaved, one planar")
+    kit_gpu.assert_bits(y, want, "two interleaved, one planar")
     y = aa.resize_many_to_float([planar[0], inter[1], planar[2]], [19, 77], "bicubic", **kw)
     assert y.is_contiguous()
-    _assert_bits(y, want, "two planar, one interleaved")
+    kit_gpu.assert_bits(y, want, "two planar, one interleaved")
     y = aa.resize_many_to_float([planar[0], inter[1], planar[2]], [19, 77], "bicubic", out_format="nhwc", **kw)
     assert y.is_contiguous(memory_format=torch.channels_last)
-    _assert_bits(y, want, "two planar, one interleaved, nhwc")
+    kit_gpu.assert_bits(y, want, "two planar, one interleaved, nhwc")
 
 
 def test_permuting_the_items_permutes_the_output():
@@ -343,7 +285,7 @@ def test_permuting_the_items_permutes_the_output():
     flips = [i % 2 == 0 for i in range(9)]
     yp = aa.resize_many_to_float([imgs[p] for p in perm], [30, 45], MODE[f], boxes=[boxes[p] for p in perm], flips=[flips[p] for p in perm],
                                  out_dtype=torch.bfloat16, out_format="nchw", **_norm(3))
-    _assert_bits(yp, _convert(_bytes(name, f), torch.bfloat16, True, flips)[perm], "permuted items")
+    kit_gpu.assert_bits(yp, kit_gpu.convert(_bytes(name, f), torch.bfloat16, True, flips)[perm], "permuted items")
 
 
 def test_empty_batch_and_no_cache_is_read_or_written():
@@ -357,4 +299,4 @@ def test_empty_batch_and_no_cache_is_read_or_written():
                                 out_format="nchw", **_norm(3))
     torch.cuda.synchronize()
     assert (len(tables._cache), len(tables._box_cache), len(aa._plans)) == before
-    _assert_bits(y, _convert(_bytes("m_mixed", "cubic"), torch.bfloat16, True), "m_mixed/cubic")
+    kit_gpu.assert_bits(y, kit_gpu.convert(_bytes("m_mixed", "cubic"), torch.bfloat16, True), "m_mixed/cubic")

@@ -4,13 +4,15 @@ import functools
 import os
 import sys
 
-import numpy as np
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import kit_gpu  # noqa: E402
 import resize_many_ref as ref  # noqa: E402
+from kit_golden import MODE  # noqa: E402
+from kit_gpu import FORWARD  # noqa: E402
 
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
 from interpolate_antialiasing_amd import tables  # noqa: E402
@@ -19,44 +21,21 @@ pytestmark = pytest.mark.gpu
 
 G = ref.gen()
 CASE_NAMES = [cs[0] for cs in G.CASES]
-FORWARD = {"linear": aa.linear_forward, "cubic": aa.cubic_forward, "box": aa.nearest_forward, "hamming": aa.hamming_forward,
-           "lanczos": aa.lanczos_forward}
-MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "box", "hamming": "hamming", "lanczos": "lanczos"}
 CLASSES = [(name, cls) for name in CASE_NAMES for cls in (("planar",) if G.case(name)[1] == 1 else ("interleaved", "planar"))]
-
-
-def _to_gpu(x_chw, cls):
-    """[C, H, W] numpy -> a GPU tensor [C, H, W] lying in memory as the class says."""
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.ascontiguousarray(x_chw)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(name, cls):
     """The case's images on the GPU (shared between tests, never written): a list, or one [N, C, H, W] tensor for a batch case."""
     cs = G.case(name)
-    items = [_to_gpu(ref.item(name, i), cls) for i in range(len(cs[3]))]
-    if cs[6]:
-        x = torch.stack(items)
-        return x.contiguous(memory_format=torch.channels_last) if cls == "interleaved" else x.contiguous()
-    return items
+    return kit_gpu.batch_or_list([kit_gpu.to_gpu(ref.item(name, i), cls) for i in range(len(cs[3]))], cs[6], cls)
 
 
 def _boxes(name):
     return [it[2] for it in G.case(name)[3]]
 
 
-def _hwc(y_i):
-    return y_i.permute(1, 2, 0).cpu().numpy()
-
-
-def _check_against_fixture(name, f, y):
-    cs = G.case(name)
-    assert tuple(y.shape) == (len(cs[3]), cs[1]) + tuple(cs[2]) and y.dtype == torch.uint8
-    got = y.cpu()
-    for i in range(len(cs[3])):
-        ref.assert_matches_fixture(f"{name}/{f}/{i}", ref.item(name, i), got[i].permute(1, 2, 0).numpy())
+_check_against_fixture = functools.partial(kit_gpu.check_against_fixture, ref, 3)  # (a case keeps its items at [3])
 
 
 @pytest.mark.parametrize("name,cls", CLASSES)
@@ -64,38 +43,15 @@ def test_every_case_filter_and_layout_class_equals_pillow(name, cls):
     cs = G.case(name)
     for f in cs[4]:
         y = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name))
-        if cs[1] > 1:
-            assert y.is_contiguous(memory_format=torch.channels_last) == (cls == "interleaved") and y.is_contiguous() == (cls == "planar")
-        else:
-            assert y.is_contiguous()
+        kit_gpu.assert_class_format(y, cls, cs[1])
         _check_against_fixture(name, f, y)
-
-
-def _pitched_crop(x_chw, cls, k):
-    """The image as a crop of a larger padded buffer: an odd byte offset and a row pitch that is no multiple of 4."""
-    c, h, w = x_chw.shape
-    off = 1 + 2 * (k % 2)
-    if cls == "interleaved":
-        pitch = w * c + 5
-        pitch += 1 if pitch % 4 == 0 else 0
-        buf = torch.full((off + h * pitch + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (1, pitch, c), off)
-    else:
-        pitch = w + 6
-        pitch += 1 if pitch % 4 == 0 else 0
-        plane = h * pitch + 7
-        buf = torch.full((off + c * plane + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (plane, pitch, 1), off)
-    assert pitch % 4 != 0 and v.data_ptr() % 2 == 1
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x_chw)).cuda())
-    return v
 
 
 @pytest.mark.parametrize("cls", ["interleaved", "planar"])
 @pytest.mark.parametrize("name", ["m_mixed", "m_c4"])
 def test_crops_at_odd_offsets_and_pitches_are_read_in_place(name, cls):
     cs = G.case(name)
-    crops = [_pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[3]))]
+    crops = [kit_gpu.pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[3]))]
     for f in cs[4]:
         y = aa.resize_many(crops, list(cs[2]), MODE[f], boxes=_boxes(name))
         dense = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], boxes=_boxes(name))
@@ -135,9 +91,9 @@ def test_one_image_and_no_image():
     imgs, boxes = _inputs("m_mixed", "interleaved"), _boxes("m_mixed")
     for i in (1, 6):
         y = aa.resize_many([imgs[i]], [30, 45], "bilinear", boxes=[boxes[i]])
-        ref.assert_matches_fixture(f"m_mixed/linear/{i}", ref.item("m_mixed", i), _hwc(y[0]))
+        ref.assert_matches_fixture(f"m_mixed/linear/{i}", ref.item("m_mixed", i), kit_gpu.hwc(y[0]))
     y = aa.resize_many([imgs[0][None]], [30, 45], "bilinear")  # a [1, C, H, W] item, no boxes at all
-    ref.assert_matches_fixture("m_mixed/linear/0", ref.item("m_mixed", 0), _hwc(y[0]))
+    ref.assert_matches_fixture("m_mixed/linear/0", ref.item("m_mixed", 0), kit_gpu.hwc(y[0]))
     e = aa.resize_many([], [30, 45], channels=3)
     assert tuple(e.shape) == (0, 3, 30, 45) and e.dtype == torch.uint8 and e.is_cuda
     e = aa.resize_many(_inputs("m_batchbox", "planar")[:0], [30, 45])

@@ -13,6 +13,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import guard_ref  # noqa: E402
+import kit_gpu  # noqa: E402
 import resize_many_maps_ref as ref  # noqa: E402
 
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
@@ -25,20 +26,10 @@ COMBOS = [(case, name, dt) for case, cs in G.CASES.items() for dt in cs["dtypes"
 TORCH_DT = {"u16": torch.uint16, "i32": torch.int32, "f32": torch.float32}
 
 
-def _bits(t):
-    """A tensor's bits as a dtype torch.equal serves everywhere."""
-    return t.view(torch.int16) if t.dtype == torch.uint16 else (t.view(torch.int32) if t.dtype == torch.float32 else t)
-
-
 def _assert_bits(y, exp_np, what):
     """y [N, 1, oH, oW] on the GPU against a numpy [N, oH, oW] batch."""
-    exp = torch.from_numpy(np.ascontiguousarray(exp_np))[:, None]
-    assert y.dtype == exp.dtype and tuple(y.shape) == tuple(exp.shape) and y.is_contiguous(), what
-    got = y.cpu()
-    if not torch.equal(_bits(got), _bits(exp)):
-        bad = (_bits(got) != _bits(exp)).nonzero()
-        at = tuple(bad[0].tolist())
-        raise AssertionError(f"{what}: {len(bad)} elements differ, first at {list(at)}: {got[at].item()!r} != {exp[at].item()!r}")
+    assert y.is_contiguous(), what
+    kit_gpu.assert_bits(y, torch.from_numpy(np.ascontiguousarray(exp_np))[:, None], what)
 
 
 @functools.lru_cache(maxsize=None)
@@ -116,7 +107,7 @@ def test_a_batch_tensor_is_the_list_of_its_items():
         kw = dict(boxes=[None, (2.5, 1.0, 30.0, 20.0), (3, 1, 20, 13)], flips=[True, False, True])
         a = aa.resize_many_maps(x, [12, 17], "hamming", **kw)
         b = aa.resize_many_maps([x[i] for i in range(3)], [12, 17], "hamming", **kw)
-        assert tuple(a.shape) == (3, 1, 12, 17) and torch.equal(_bits(a), _bits(b))
+        assert tuple(a.shape) == (3, 1, 12, 17) and torch.equal(kit_gpu.bits(a), kit_gpu.bits(b))
         _assert_bits(a, ref.many([x[i, 0].cpu().numpy() for i in range(3)], (12, 17), "hamming", **kw), dt)
 
 
@@ -144,22 +135,10 @@ def test_guard_bands(monkeypatch, case, name, dt):
             assert rec.record_of(y) is not None
         outs.append(y)
         _assert_bits(y, ref.expected(case, name, dt), (case, name, dt, lead))
-    assert torch.equal(_bits(outs[0]), _bits(outs[1]))
+    assert torch.equal(kit_gpu.bits(outs[0]), kit_gpu.bits(outs[1]))
 
 
 # ---- the call's promises ---------------------------------------------------------------------------------------------------------------------
-def _count_launches(fn):
-    """Kernel launches of one fn() from torch's profiler (tools/resize_many_bench.py count_launches)."""
-    from torch.profiler import ProfilerActivity, profile
-
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and "memcpy" not in e.name.lower()
-            and "memset" not in e.name.lower()]
-
-
 def test_three_launches_whatever_n():
     maps = list(_maps("ragged", "u16"))
     kw = ref.call_args("ragged", "u16")
@@ -167,7 +146,7 @@ def test_three_launches_whatever_n():
              5: lambda: aa.resize_many_maps(maps, [20, 23], "bicubic", boxes=kw["boxes"])}
     for k, fn in calls.items():
         fn()  # (module load and allocator warm-up stay outside the count)
-        names = _count_launches(fn)
+        names = kit_gpu.count_launches(fn)
         assert len(names) == 3, (k, names)
         assert [sum(1 for nm in names if part in nm) for part in ("maps_tables", "maps_hpass", "maps_vpass")] == [1, 1, 1], (k, names)
 

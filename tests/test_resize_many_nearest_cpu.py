@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import kit_golden
 import resize_many_nearest_ref as ref
 from interpolate_antialiasing_amd import _lib, boxmath
 from interpolate_antialiasing_amd import extension_interpolate as aa
@@ -28,7 +29,7 @@ def test_restatement_reproduces_the_fixture(name):
 def test_fixture_is_small_and_holds_every_case():
     import os
 
-    path = os.path.join(ref.ROOT, "tests", "golden", "resize_many_nearest.npz")
+    path = os.path.join(kit_golden.GOLDEN, "resize_many_nearest.npz")
     assert os.path.getsize(path) < 100 * 1024
     assert set(ref.fixture()) == {n for name in ref.case_names() for n in (name, name + "__incrc")}
 

@@ -12,6 +12,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import guard_ref  # noqa: E402
+import kit_gpu  # noqa: E402
 import resize_many_nearest_ref as ref  # noqa: E402
 
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
@@ -24,22 +25,11 @@ CLASSES = [(cs[0], cls) for cs in G.CASES for cls in (("planar",) if cs[2] == 1 
 SINGLE = [cs[0] for cs in G.CASES if cs[2] == 1]
 
 
-def _to_gpu(x_chw, cls):
-    """[C, H, W] numpy -> a GPU tensor [C, H, W] lying in memory as the class says."""
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.array(x_chw)).cuda()  # (a copy: the shared inputs are read-only)
-
-
 @functools.lru_cache(maxsize=None)
 def _inputs(name, cls):
     """The case's images on the GPU (shared between tests, never written): a list, or one [N, C, H, W] tensor for a batch case."""
     cs = G.case(name)
-    items = [_to_gpu(x, cls) for x in ref.inputs(name)]
-    if cs[9]:
-        x = torch.stack(items)
-        return x.contiguous(memory_format=torch.channels_last) if cls == "interleaved" else x.contiguous()
-    return items
+    return kit_gpu.batch_or_list([kit_gpu.to_gpu(x, cls) for x in ref.inputs(name)], cs[9], cls)
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,28 +38,13 @@ def _expected(name):
     return torch.from_numpy(np.ascontiguousarray(ref.expected(name).transpose(0, 3, 1, 2)))
 
 
-def _assert_class_format(y, cls, c):
-    if c > 1:
-        assert y.is_contiguous(memory_format=torch.channels_last) == (cls == "interleaved") and y.is_contiguous() == (cls == "planar")
-    else:
-        assert y.is_contiguous()
-
-
-def _assert_equal(y, exp, what):
-    assert y.dtype == exp.dtype and tuple(y.shape) == tuple(exp.shape), what
-    got = y.cpu()
-    if not torch.equal(got, exp):
-        bad = (got != exp).nonzero()
-        raise AssertionError(f"{what}: {len(bad)} elements differ, first at {bad[0].tolist()}: {got[tuple(bad[0])]} != {exp[tuple(bad[0])]}")
-
-
 # ---- every fixture case, every class -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,cls", CLASSES)
 def test_fixture_case(name, cls):
     cs = G.case(name)
     y = aa.resize_many_nearest(_inputs(name, cls), list(cs[3]), **ref.call_args(name))
-    _assert_class_format(y, cls, cs[2])
-    _assert_equal(y, _expected(name), (name, cls))
+    kit_gpu.assert_class_format(y, cls, cs[2])
+    kit_gpu.assert_bits(y, _expected(name), (name, cls))
 
 
 @pytest.mark.parametrize("name", SINGLE)
@@ -79,7 +54,7 @@ def test_int64_output_is_long_of_the_result(name):
     y = aa.resize_many_nearest(_inputs(name, "planar"), list(cs[3]), out_dtype=torch.int64, **ref.call_args(name))
     assert y.is_contiguous()
     exp = _expected(name)
-    _assert_equal(y, exp.long(), name)
+    kit_gpu.assert_bits(y, exp.long(), name)
     if name in ("i16", "i32", "i16_seam", "i32_seam"):
         assert int(exp.min()) < 0 and int(y.min()) == int(exp.min())  # the negative ids and the fill -1 stayed negative
     if cs[1] == "u1":
@@ -93,7 +68,7 @@ def test_the_torch_op_runs_the_call():
     y = torch.ops.extension_interpolate.resize_many_nearest(
         _inputs(name, "interleaved"), list(cs[3]), boxes=[float(v) for i, b in enumerate(kw["boxes"]) for v in (b or (0, 0, cs[5][i][1], cs[5][i][0]))],
         flips=kw["flips"], sizes=[v for s in kw["sizes"] for v in s], offsets=[v for o in kw["offsets"] for v in o], fill=kw["fill"])
-    _assert_equal(y, _expected(name), name)
+    kit_gpu.assert_bits(y, _expected(name), name)
 
 
 # ---- the paired-geometry promise -------------------------------------------------------------------------------------------------------------
@@ -105,7 +80,7 @@ def test_same_geometry_arguments_serve_image_and_mask(name, cls):
     imgs = _inputs(name, cls)
     kw = ref.call_args(name)
     mask = aa.resize_many_nearest(imgs, list(cs[3]), **kw)
-    _assert_equal(mask, torch.from_numpy(np.ascontiguousarray(ref.restate(cs, ref.inputs(name)).transpose(0, 3, 1, 2))), (name, cls))
+    kit_gpu.assert_bits(mask, torch.from_numpy(np.ascontiguousarray(ref.restate(cs, ref.inputs(name)).transpose(0, 3, 1, 2))), (name, cls))
     image = aa.resize_many_to_float(imgs, list(cs[3]), "nearest", **kw)
     kw_u8 = {k: v for k, v in kw.items() if k != "flips"}
     u = aa.resize_many(imgs, list(cs[3]), "nearest", **kw_u8).float()
@@ -126,21 +101,21 @@ def test_crops_of_larger_tensors_offset_and_pitch(cls):
         c, h, w = x.shape
         big = np.full((c, h + 5, w + 7 + i), 99, np.uint8)
         big[:, 2:2 + h, 3 + i:3 + i + w] = x
-        views.append(_to_gpu(big, cls)[:, 2:2 + h, 3 + i:3 + i + w])
+        views.append(kit_gpu.to_gpu(big, cls)[:, 2:2 + h, 3 + i:3 + i + w])
     assert not any(v.is_contiguous() for v in views)
     y = aa.resize_many_nearest(views, list(cs[3]), **ref.call_args(name))
-    _assert_class_format(y, cls, 3)
-    _assert_equal(y, _expected(name), (name, cls))
+    kit_gpu.assert_class_format(y, cls, 3)
+    kit_gpu.assert_bits(y, _expected(name), (name, cls))
 
 
 def test_minority_class_items_are_copied():
     name = "plain_c3"
     cs = G.case(name)
     xs = ref.inputs(name)
-    mixed = [_to_gpu(x, "interleaved" if i < 3 else "planar") for i, x in enumerate(xs)]
+    mixed = [kit_gpu.to_gpu(x, "interleaved" if i < 3 else "planar") for i, x in enumerate(xs)]
     y = aa.resize_many_nearest(mixed, list(cs[3]), **ref.call_args(name))
-    _assert_class_format(y, "interleaved", 3)
-    _assert_equal(y, _expected(name), name)
+    kit_gpu.assert_class_format(y, "interleaved", 3)
+    kit_gpu.assert_bits(y, _expected(name), name)
 
 
 def test_instance_mask_stack_goes_in_as_single_plane_views():
@@ -150,7 +125,7 @@ def test_instance_mask_stack_goes_in_as_single_plane_views():
     box = (2.5, 1.0, 30.0, 20.5)
     y = aa.resize_many_nearest([t[k:k + 1] for k in range(6)], (10, 12), boxes=[box] * 6)
     exp = np.stack([ref.resize_nearest(stack[k:k + 1], (10, 12), box).transpose(2, 0, 1) for k in range(6)])
-    _assert_equal(y, torch.from_numpy(exp), "stack")
+    kit_gpu.assert_bits(y, torch.from_numpy(exp), "stack")
 
 
 def test_more_items_than_single_lane_waves():
@@ -165,7 +140,7 @@ def test_more_items_than_single_lane_waves():
     flips = [i % 2 == 1 for i in range(n)]
     y = aa.resize_many_nearest([t] * n, (4, 6), boxes=boxes, sizes=sizes, offsets=offsets, flips=flips, fill=255)
     exp = np.stack([ref.place(ref.resize_nearest(x, sizes[i], boxes[i]), (4, 6), offsets[i], (255,), flips[i]).transpose(2, 0, 1) for i in range(n)])
-    _assert_equal(y, torch.from_numpy(np.ascontiguousarray(exp)), "1100 items")
+    kit_gpu.assert_bits(y, torch.from_numpy(np.ascontiguousarray(exp)), "1100 items")
 
 
 @pytest.mark.parametrize("dtype,c,cls", [(np.uint8, 1, "planar"), (np.uint8, 3, "interleaved"), (np.uint8, 3, "planar"), (np.int16, 1, "planar"),
@@ -189,7 +164,7 @@ def test_items_ending_exactly_on_their_allocation(dtype, c, cls):
         items.append(t)
         exps.append(ref.resize_nearest(x, (11, 16), box, closed_form=dtype == np.int16).transpose(2, 0, 1))
     y = aa.resize_many_nearest(items, (11, 16), boxes=[None, (2.5, 1.5, 7.0, 5.0)])
-    _assert_equal(y, torch.from_numpy(np.stack(exps)), (dtype, c, cls))
+    kit_gpu.assert_bits(y, torch.from_numpy(np.stack(exps)), (dtype, c, cls))
 
 
 # ---- guard bands -----------------------------------------------------------------------------------------------------------------------------
@@ -258,9 +233,9 @@ def test_side_stream_and_a_second_call_reusing_nothing():
         y3 = aa.resize_many_nearest(imgs, list(cs[3]), **ref.call_args(name))
     s.synchronize()
     assert (len(tables._cache), len(tables._box_cache)) == before  # the table caches are neither read nor written
-    _assert_equal(y1, _expected(name), "first")
-    _assert_equal(y2, _expected(other), "second")
-    _assert_equal(y3, _expected(name), "third")
+    kit_gpu.assert_bits(y1, _expected(name), "first")
+    kit_gpu.assert_bits(y2, _expected(other), "second")
+    kit_gpu.assert_bits(y3, _expected(name), "third")
     assert y1.data_ptr() != y3.data_ptr()
 
 

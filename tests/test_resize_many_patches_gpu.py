@@ -15,6 +15,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import guard_ref as G  # noqa: E402
+import kit_gpu  # noqa: E402
 import resize_many_patches_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -22,22 +23,7 @@ pytestmark = pytest.mark.gpu
 CLASSES = ["interleaved", "planar"]
 FORMATS = ["cpp", "ppc"]
 TAG = {torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32"}
-BITS = {4: torch.int32, 2: torch.int16}
-
-
-@pytest.fixture(scope="module")
-def aa():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from interpolate_antialiasing_amd import extension_interpolate
-
-    return extension_interpolate
-
-
-def _item_gpu(x_chw, cls):
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.array(x_chw, order="C")).cuda()  # (a copy: the cached inputs are read-only)
+aa = kit_gpu.aa_fixture()
 
 
 @functools.lru_cache(maxsize=None)
@@ -47,26 +33,12 @@ def _images(name, cls):
     if ref.case(name)[6]:
         t = torch.from_numpy(np.stack(xs)).cuda()
         return t.contiguous(memory_format=torch.channels_last) if cls == "interleaved" else t
-    return [_item_gpu(x, cls) for x in xs]
+    return [kit_gpu.to_gpu(x, cls) for x in xs]
 
 
 def _call(aa, name, f, cls, **kw):
     cs = ref.case(name)
     return aa.resize_many_to_patches(_images(name, cls), cs[2], ref.MODE[f], sizes=ref.sizes(name), boxes=ref.boxes(name), flips=ref.flips(name), **kw)
-
-
-def _bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(BITS[t.element_size()])
-
-
-def _assert_bits(got, want, what):
-    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), (what, got.dtype, tuple(got.shape), want.dtype, tuple(want.shape))
-    a, b = _bits(got), _bits(want)
-    if not torch.equal(a, b):
-        bad = (a != b).nonzero()
-        raise AssertionError(f"{what}: {len(bad)} of {a.numel()} elements differ from the reference, first at {bad[0].tolist()}: "
-                             f"{got.cpu()[tuple(bad[0])].item()} != {want[tuple(bad[0])].item()}")
 
 
 def _whole_bytes(y, what):
@@ -118,7 +90,7 @@ def test_normalised_equals_torch_cpu_conversion_of_the_restated_bytes(aa, name, 
         for fmt in FORMATS:
             y = _call(aa, name, f, cls, patch_format=fmt, out_dtype=dtype, mean=ref.MEAN[:c], std=ref.STD[:c])
             assert y.is_contiguous()
-            _assert_bits(y, _normalised(name, f, fmt, dtype), (name, f, cls, fmt, TAG[dtype]))
+            kit_gpu.assert_bits(y, _normalised(name, f, fmt, dtype), (name, f, cls, fmt, TAG[dtype]))
 
 
 # ---- pad_to ---------------------------------------------------------------------------------------------------------------------------------
@@ -146,9 +118,9 @@ def test_pad_rows_are_all_zero_bits(aa, cls, extra):
                 for i, t in enumerate(counts):
                     want[i, :t] = packed[at:at + t]
                     at += t
-                _assert_bits(z, want, (name, f, cls, fmt, L, TAG[dtype]))
+                kit_gpu.assert_bits(z, want, (name, f, cls, fmt, L, TAG[dtype]))
                 for i, t in enumerate(counts):
-                    assert int(_bits(z[i, t:]).count_nonzero()) == 0, (name, f, cls, fmt, L, i)
+                    assert int(kit_gpu.bits(z[i, t:]).count_nonzero()) == 0, (name, f, cls, fmt, L, i)
 
 
 # ---- the call against the composition through the unchanged resize_many_to_float ---------------------------------------------------------------
@@ -160,7 +132,7 @@ def test_equals_the_composition_through_resize_many_to_float(aa, cls):
     boxes = [None, (3.25, 10.5, 60.0, 100.75), None, None, (0, 0, 15, 15)]
     flips = [False, True, True, False, False]
     ph, pw, c = 8, 8, 3
-    imgs = [_item_gpu(rng.integers(0, 256, (c, h, w), dtype=np.uint8), cls) for h, w in shapes]
+    imgs = [kit_gpu.to_gpu(rng.integers(0, 256, (c, h, w), dtype=np.uint8), cls) for h, w in shapes]
     for mode in ("bicubic", "lanczos"):
         for dtype in (torch.float32, torch.bfloat16):
             rs = [aa.resize_many_to_float([imgs[i]], list(sizes[i]), mode, boxes=[boxes[i]], flips=[flips[i]], out_dtype=dtype, out_format="nchw",
@@ -170,7 +142,7 @@ def test_equals_the_composition_through_resize_many_to_float(aa, cls):
                                   for r, (vh, vw) in zip(rs, sizes)])
                 y = aa.resize_many_to_patches(imgs, (ph, pw), mode, sizes=sizes, boxes=boxes, flips=flips, patch_format=fmt, out_dtype=dtype,
                                               mean=ref.MEAN[:c], std=ref.STD[:c])
-                _assert_bits(y, want.cpu(), (cls, mode, TAG[dtype], fmt))
+                kit_gpu.assert_bits(y, want.cpu(), (cls, mode, TAG[dtype], fmt))
 
 
 # ---- guard band: every output element written, nothing else touched ------------------------------------------------------------------------
@@ -194,8 +166,8 @@ def test_guard_band(aa, monkeypatch, pad, cls, dtype, lead):
         assert r is not None and not r.flat and y.data_ptr() % G.ALIGN == (lead * y.element_size()) % G.ALIGN
         assert G.unwritten_float(y) == 0, (name, f, fmt, cls, L, lead, "output elements still hold the fill")
         packed = _normalised(name, f, fmt, dtype)
-        want = packed if L is None else torch.from_numpy(ref.padded(packed.view(BITS[packed.element_size()]).numpy(), counts, L)).view(dtype)
-        _assert_bits(y, want, (name, f, fmt, cls, L, lead))
+        want = packed if L is None else torch.from_numpy(ref.padded(kit_gpu.bits(packed).numpy(), counts, L)).view(dtype)
+        kit_gpu.assert_bits(y, want, (name, f, fmt, cls, L, lead))
 
 
 # ---- the torch op ---------------------------------------------------------------------------------------------------------------------------
@@ -208,4 +180,4 @@ def test_torch_op_equals_the_python_call(aa):
     for fmt, pad, dtype in (("cpp", None, None), ("ppc", max(ref.token_counts(name)) + 1, torch.bfloat16)):
         y = op(imgs, [14, 14], ref.MODE[f], flat_sizes, flat_boxes, ref.flips(name), fmt, pad, dtype, ref.MEAN[:3], ref.STD[:3])
         want = _call(aa, name, f, "interleaved", patch_format=fmt, pad_to=pad, out_dtype=dtype or torch.float32, mean=ref.MEAN[:3], std=ref.STD[:3])
-        _assert_bits(y, want.cpu(), (fmt, pad, dtype))
+        kit_gpu.assert_bits(y, want.cpu(), (fmt, pad, dtype))

@@ -12,7 +12,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import guard_ref  # noqa: E402
+import kit_gpu  # noqa: E402
 import resize_many_placed_ref as ref  # noqa: E402
+from kit_golden import MEAN, MODE, STD  # noqa: E402
+from kit_gpu import FORWARD  # noqa: E402
 
 from interpolate_antialiasing_amd import extension_interpolate as aa  # noqa: E402
 from interpolate_antialiasing_amd import tables  # noqa: E402
@@ -21,31 +24,15 @@ pytestmark = pytest.mark.gpu
 
 G = ref.gen()
 CASE_NAMES = [cs[0] for cs in G.CASES]
-FORWARD = {"linear": aa.linear_forward, "cubic": aa.cubic_forward, "box": aa.nearest_forward, "hamming": aa.hamming_forward,
-           "lanczos": aa.lanczos_forward}
-MODE = {"linear": "bilinear", "cubic": "bicubic", "box": "box", "hamming": "hamming", "lanczos": "lanczos"}
 CLASSES = [(name, cls) for name in CASE_NAMES for cls in (("planar",) if G.case(name)[1] == 1 else ("interleaved", "planar"))]
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
-MEAN = [123.675, 116.28, 103.53, 127.5]
-STD = [58.395, 57.12, 57.375, 64.0]
-
-
-def _to_gpu(x_chw, cls):
-    """[C, H, W] numpy -> a GPU tensor [C, H, W] lying in memory as the class says."""
-    if cls == "interleaved":
-        return torch.from_numpy(np.ascontiguousarray(x_chw.transpose(1, 2, 0))).cuda().permute(2, 0, 1)
-    return torch.from_numpy(np.ascontiguousarray(x_chw)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(name, cls):
     """The case's images on the GPU (shared between tests, never written): a list, or one [N, C, H, W] tensor for a batch case."""
     cs = G.case(name)
-    items = [_to_gpu(ref.item(name, i), cls) for i in range(len(cs[5]))]
-    if cs[7]:
-        x = torch.stack(items)
-        return x.contiguous(memory_format=torch.channels_last) if cls == "interleaved" else x.contiguous()
-    return items
+    return kit_gpu.batch_or_list([kit_gpu.to_gpu(ref.item(name, i), cls) for i in range(len(cs[5]))], cs[7], cls)
 
 
 def _kw(name):
@@ -60,19 +47,7 @@ def _bytes(name, f):
     return torch.from_numpy(np.stack([G.restated(cs, f, i, ref.item(name, i)).transpose(2, 0, 1) for i in range(len(cs[5]))]))
 
 
-def _check_against_fixture(name, f, y):
-    cs = G.case(name)
-    assert tuple(y.shape) == (len(cs[5]), cs[1]) + tuple(cs[2]) and y.dtype == torch.uint8
-    got = y.cpu()
-    for i in range(len(cs[5])):
-        ref.assert_matches_fixture(f"{name}/{f}/{i}", ref.item(name, i), got[i].permute(1, 2, 0).numpy())
-
-
-def _assert_class_format(y, cls, c):
-    if c > 1:
-        assert y.is_contiguous(memory_format=torch.channels_last) == (cls == "interleaved") and y.is_contiguous() == (cls == "planar")
-    else:
-        assert y.is_contiguous()
+_check_against_fixture = functools.partial(kit_gpu.check_against_fixture, ref, 5)  # (a case keeps its items at [5])
 
 
 @pytest.mark.parametrize("name,cls", CLASSES)
@@ -80,7 +55,7 @@ def test_every_case_filter_and_layout_class_equals_pillow(name, cls):
     cs = G.case(name)
     for f in cs[4]:
         y = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], **_kw(name))
-        _assert_class_format(y, cls, cs[1])
+        kit_gpu.assert_class_format(y, cls, cs[1])
         _check_against_fixture(name, f, y)
 
 
@@ -105,31 +80,11 @@ def test_each_item_equals_the_single_image_call_cropped_and_pasted(name, cls):
         assert torch.equal(aa.resize_many(imgs, [oh, ow], "bicubic", **kw)[0], plain[0])
 
 
-def _pitched_crop(x_chw, cls, k):
-    """The image as a crop of a larger padded buffer: an odd byte offset and a row pitch that is no multiple of 4."""
-    c, h, w = x_chw.shape
-    off = 1 + 2 * (k % 2)
-    if cls == "interleaved":
-        pitch = w * c + 5
-        pitch += 1 if pitch % 4 == 0 else 0
-        buf = torch.full((off + h * pitch + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (1, pitch, c), off)
-    else:
-        pitch = w + 6
-        pitch += 1 if pitch % 4 == 0 else 0
-        plane = h * pitch + 7
-        buf = torch.full((off + c * plane + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-        v = buf.as_strided((c, h, w), (plane, pitch, 1), off)
-    assert pitch % 4 != 0 and v.data_ptr() % 2 == 1
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x_chw)).cuda())
-    return v
-
-
 @pytest.mark.parametrize("cls", ["interleaved", "planar"])
 @pytest.mark.parametrize("name", ["p_edges", "p_c4"])
 def test_crops_at_odd_offsets_and_pitches_are_read_in_place(name, cls):
     cs = G.case(name)
-    crops = [_pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[5]))]
+    crops = [kit_gpu.pitched_crop(ref.item(name, i), cls, i) for i in range(len(cs[5]))]
     for f in cs[4]:
         y = aa.resize_many(crops, list(cs[2]), MODE[f], **_kw(name))
         dense = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], **_kw(name))
@@ -138,28 +93,6 @@ def test_crops_at_odd_offsets_and_pitches_are_read_in_place(name, cls):
 
 
 # ---- resize_many_to_float ------------------------------------------------------------------------------------------------------------
-def _bits(t):
-    t = t.cpu().contiguous()
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def _assert_bits(got, want, what):
-    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), what
-    a, b = _bits(got), _bits(want)
-    if not torch.equal(a, b):
-        bad = (a != b).nonzero()
-        raise AssertionError(f"{what}: {len(bad)} of {a.numel()} elements differ, first at {bad[0].tolist()}: "
-                             f"{got.cpu()[tuple(bad[0])].item()} != {want[tuple(bad[0])].item()}")
-
-
-def _convert(u, dtype, flips):
-    """The docstring's definition, by torch on the CPU: u [N, C, oH, oW] uint8 -> the expected tensor."""
-    c = u.shape[1]
-    f = (u.float() - torch.tensor(MEAN[:c]).view(1, c, 1, 1)) / torch.tensor(STD[:c]).view(1, c, 1, 1)
-    y = f.to(dtype)
-    return torch.stack([y[i].flip(-1) if flips[i] else y[i] for i in range(len(flips))])
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16", "bf16"])
 @pytest.mark.parametrize("cls", ["interleaved", "planar"])
 @pytest.mark.parametrize("name", ["p_letterbox", "p_edges"])
@@ -170,16 +103,16 @@ def test_to_float_is_the_placed_bytes_converted(name, cls, dtype):
     for f in cs[4]:
         u = aa.resize_many(_inputs(name, cls), list(cs[2]), MODE[f], **_kw(name)).cpu()
         assert torch.equal(u, _bytes(name, f)), (name, f)  # (the placed bytes are Pillow's: what is converted below is not the call's own)
-        want = _convert(u, dtype, flips)
+        want = kit_gpu.convert(u, dtype, flips=flips)
         for fmt in ("nchw", "nhwc"):
             y = aa.resize_many_to_float(_inputs(name, cls), list(cs[2]), MODE[f], flips=flips, out_dtype=dtype, out_format=fmt, mean=MEAN[:c],
                                         std=STD[:c], **_kw(name))
             assert y.is_contiguous(memory_format=torch.channels_last) == (fmt == "nhwc") and y.is_contiguous() == (fmt == "nchw")
-            assert torch.equal(_bits(y), _bits(want)), (name, f, cls, fmt, dtype)
+            assert torch.equal(kit_gpu.bits(y), kit_gpu.bits(want)), (name, f, cls, fmt, dtype)
     # the fill area holds (fill[c] - mean[c]) / std[c], rounded once: item 4 of p_edges is all fill, row 0 of p_letterbox's item 2 too
     fillv = ((torch.tensor(ref.fill(name)).float() - torch.tensor(MEAN[:c])) / torch.tensor(STD[:c])).to(dtype)
     area = y[4] if name == "p_edges" else y[2][:, :1, :]
-    assert torch.equal(_bits(area), _bits(fillv.view(c, 1, 1).expand_as(area))), (name, dtype)
+    assert torch.equal(kit_gpu.bits(area), kit_gpu.bits(fillv.view(c, 1, 1).expand_as(area))), (name, dtype)
 
 
 # ---- guard bands ---------------------------------------------------------------------------------------------------------------------
@@ -217,7 +150,7 @@ def test_guard_bands_bf16_nchw(monkeypatch, name, cls):
         rec.check()
         assert len(rec.records) == 3 and rec.record_of(y) is not None
         assert guard_ref.unwritten_float(y) == 0
-    _assert_bits(y, _convert(_bytes(name, f), torch.bfloat16, flips), (name, f, cls))
+    kit_gpu.assert_bits(y, kit_gpu.convert(_bytes(name, f), torch.bfloat16, flips=flips), (name, f, cls))
 
 
 # ---- caches, the torch op ------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import kit_golden  # noqa: E402
 import resize_many_ycbcr_ref as ref  # noqa: E402
 
 from interpolate_antialiasing_amd import _lib, boxmath  # noqa: E402
@@ -38,7 +39,7 @@ def test_fixture_regenerates_from_pillow():
 
 
 def test_fixture_is_small_and_stores_the_hash():
-    assert os.path.getsize(os.path.join(ref.ROOT, "tests", "golden", "resize_many_ycbcr.npz")) < 400 * 1024
+    assert os.path.getsize(os.path.join(kit_golden.GOLDEN, "resize_many_ycbcr.npz")) < 400 * 1024
     assert ref.stored_sha256() == SHA
 
 

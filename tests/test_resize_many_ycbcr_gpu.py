@@ -13,6 +13,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import guard_ref  # noqa: E402
+import kit_golden  # noqa: E402
+import kit_gpu  # noqa: E402
 import resize_many_ycbcr_ref as ref  # noqa: E402
 
 from interpolate_antialiasing_amd import boxmath, tables  # noqa: E402
@@ -22,19 +24,7 @@ pytestmark = pytest.mark.gpu
 
 G = ref.gen()
 COMBOS = [tuple(k.split("/")) for k in G.keys()]
-MEAN, STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
-
-
-def _assert_equal(got, want, what):
-    """Two tensors of one dtype and shape, by bits (16-bit floats and float32 viewed as integers)."""
-    assert got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), (what, got.dtype, tuple(got.shape), want.dtype, tuple(want.shape))
-    a, b = got.cpu().contiguous(), want.cpu().contiguous()
-    if a.dtype != torch.uint8:
-        a, b = (t.view(torch.int32 if t.dtype == torch.float32 else torch.int16) for t in (a, b))
-    if not torch.equal(a, b):
-        bad = (a != b).nonzero()
-        at = tuple(bad[0].tolist())
-        raise AssertionError(f"{what}: {len(bad)} of {a.numel()} elements differ, first at {list(at)}: {got.cpu()[at].item()!r} != {want.cpu()[at].item()!r}")
+MEAN, STD = kit_golden.MEAN[:3], kit_golden.STD[:3]
 
 
 def _nchw(batch_nhwc):
@@ -66,8 +56,8 @@ def test_fixture_case(name, f):
     case that clamps on both sides."""
     y = _call(name, f)
     assert y.is_contiguous()
-    _assert_equal(y, _nchw(ref.expected(name, f)), (name, f, "fixture"))
-    _assert_equal(y, _nchw(ref.restate(name, f)), (name, f, "restatement"))
+    kit_gpu.assert_bits(y, _nchw(ref.expected(name, f)), (name, f, "fixture"))
+    kit_gpu.assert_bits(y, _nchw(ref.restate(name, f)), (name, f, "restatement"))
 
 
 @pytest.mark.parametrize("name,f", [("frac", "lanczos"), ("odd129", "cubic"), ("vwide", "linear"), ("long", "lanczos"), ("mixed", "cubic"),
@@ -77,25 +67,17 @@ def test_interleaved_chroma_gives_the_planes_values(name, f, fmt):
     """(Y, CbCr) with one [h, w, 2] tensor, the NV12 arrangement, in both output layouts."""
     y = _call(name, f, images=_interleaved(_planes(name)), out_format=fmt)
     assert y.is_contiguous(memory_format=torch.channels_last if fmt == "nhwc" else torch.contiguous_format)
-    _assert_equal(y, _nchw(ref.expected(name, f)), (name, f, fmt))
+    kit_gpu.assert_bits(y, _nchw(ref.expected(name, f)), (name, f, fmt))
 
 
 @pytest.mark.parametrize("name,f", [("odd65", "lanczos"), ("vwide", "linear"), ("placed", "cubic"), ("clamp", "cubic"), ("tiny1", "linear")])
 def test_uint8_channels_last(name, f):
     y = _call(name, f, out_format="nhwc")
     assert y.is_contiguous(memory_format=torch.channels_last)
-    _assert_equal(y, _nchw(ref.expected(name, f)), (name, f))
+    kit_gpu.assert_bits(y, _nchw(ref.expected(name, f)), (name, f))
 
 
 # ---- the float outputs -------------------------------------------------------------------------------------------------------------------------
-def _convert(b, dtype, norm):
-    """The definition, by torch on the CPU: b [N, 3, oH, oW] uint8 (pasted, filled and mirrored already) -> the expected tensor."""
-    f = b.float()
-    if norm:
-        f = (f - torch.tensor(MEAN).view(1, 3, 1, 1)) / torch.tensor(STD).view(1, 3, 1, 1)
-    return f.to(dtype)
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("fmt", ["nchw", "nhwc"])
 @pytest.mark.parametrize("norm", [False, True])
@@ -106,8 +88,8 @@ def test_float_outputs_are_the_bytes_converted(dtype, fmt, norm):
         u = _call(name, f, images=images)
         y = _call(name, f, images=images, out_dtype=dtype, out_format=fmt, **kw)
         assert y.is_contiguous(memory_format=torch.channels_last if fmt == "nhwc" else torch.contiguous_format)
-        _assert_equal(u, _nchw(ref.expected(name, f)), (name, "bytes"))
-        _assert_equal(y, _convert(u.cpu(), dtype, norm), (name, dtype, fmt, norm))
+        kit_gpu.assert_bits(u, _nchw(ref.expected(name, f)), (name, "bytes"))
+        kit_gpu.assert_bits(y, kit_gpu.convert(u.cpu(), dtype, norm), (name, dtype, fmt, norm))
 
 
 # ---- the composition: resize_many per plane, then the tables -----------------------------------------------------------------------------------
@@ -142,7 +124,7 @@ def test_composition_of_the_existing_calls(f):
     yi, cbi, cri = y[:, 0].int(), cb[:, 0].long(), cr[:, 0].long()
     fl = lambda v: torch.div(v, 64, rounding_mode="floor")  # noqa: E731  (the arithmetic shift by 6)
     want = torch.stack([yi + fl(t[0][cri]), yi + fl(t[1][cbi] + t[2][cri]), yi + fl(t[3][cbi])], dim=1).clamp(0, 255).to(torch.uint8)
-    _assert_equal(got, want, f)
+    kit_gpu.assert_bits(got, want, f)
 
 
 # ---- planes read where they lie ----------------------------------------------------------------------------------------------------------------
@@ -174,7 +156,7 @@ def test_planes_at_odd_offsets_and_pitches(interleaved):
               offsets=[(-3, 2), (1, -4), (0, 3)], fill=(7, 8, 9), flips=[False, True, True])
     got = aa.resize_many_ycbcr(images, [18, 27], "bicubic", **kw)
     dense = [tuple(p.contiguous() for p in it) for it in planes3]
-    _assert_equal(got, aa.resize_many_ycbcr(dense, [18, 27], "bicubic", **kw), "views against dense copies")
+    kit_gpu.assert_bits(got, aa.resize_many_ycbcr(dense, [18, 27], "bicubic", **kw), "views against dense copies")
     # and against the restatement
     res = [ref.restate_item("cubic", *(p.cpu().numpy() for p in it), "420", kw["boxes"][i], *kw["sizes"][i]) for i, it in enumerate(dense)]
     want = np.empty((3, 18, 27, 3), np.uint8)
@@ -185,7 +167,7 @@ def test_planes_at_odd_offsets_and_pitches(interleaved):
         want[i, y0:y1, x0:x1] = r[y0 - py:y1 - py, x0 - px:x1 - px]
         if kw["flips"][i]:
             want[i] = want[i, :, ::-1]
-    _assert_equal(got, _nchw(want), "restatement")
+    kit_gpu.assert_bits(got, _nchw(want), "restatement")
 
 
 # ---- guard bands -------------------------------------------------------------------------------------------------------------------------------
@@ -203,9 +185,9 @@ def test_guard_bands(monkeypatch, name, f, il, out):
             rec.check()
             assert rec.record_of(y) is not None
         outs.append(y)
-    _assert_equal(outs[0], outs[1], (name, out))
+    kit_gpu.assert_bits(outs[0], outs[1], (name, out))
     want = _nchw(ref.expected(name, f))
-    _assert_equal(outs[0], want if out[0] is None else _convert(want, out[0], False), (name, out, "value"))
+    kit_gpu.assert_bits(outs[0], want if out[0] is None else kit_gpu.convert(want, out[0], False), (name, out, "value"))
 
 
 # ---- the torch op ------------------------------------------------------------------------------------------------------------------------------
@@ -218,27 +200,15 @@ def test_the_torch_op_runs_the_call():
     args = dict(subsampling=",".join(kw["subsampling"]), boxes=flat_boxes, flips=kw["flips"], sizes=[v for s in kw["sizes"] for v in s],
                 offsets=[v for o in kw["offsets"] for v in o], fill=list(kw["fill"]))
     y = op([it[0] for it in items], [p for it in items for p in it[1:]], list(cs["canvas"]), "cubic", **args)
-    _assert_equal(y, _nchw(ref.expected("placed", "cubic")), "op, planes")
+    kit_gpu.assert_bits(y, _nchw(ref.expected("placed", "cubic")), "op, planes")
     y = op([it[0] for it in items], [c for _, c in _interleaved(items)], list(cs["canvas"]), "cubic", out_dtype=torch.float16, out_format="nhwc", **args)
     assert y.is_contiguous(memory_format=torch.channels_last)
-    _assert_equal(y, _convert(_nchw(ref.expected("placed", "cubic")), torch.float16, False), "op, interleaved")
+    kit_gpu.assert_bits(y, kit_gpu.convert(_nchw(ref.expected("placed", "cubic")), torch.float16, False), "op, interleaved")
     meta = op([it[0].to("meta") for it in items], [p.to("meta") for it in items for p in it[1:]], list(cs["canvas"]), "cubic", **args)
     assert tuple(meta.shape) == tuple(y.shape) and meta.dtype == torch.uint8 and meta.device.type == "meta"
 
 
 # ---- the call's promises -----------------------------------------------------------------------------------------------------------------------
-def _count_launches(fn):
-    """Kernel launches of one fn() from torch's profiler (tools/resize_many_bench.py count_launches)."""
-    from torch.profiler import ProfilerActivity, profile
-
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and "memcpy" not in e.name.lower()
-            and "memset" not in e.name.lower()]
-
-
 def test_three_launches_planar_and_five_interleaved_whatever_n():
     """What csrc/aa_many_ycbcr.hip's header documents: tables + horizontal pass over all planes + the converting vertical pass; luma and
     chroma pairs have the first two each when the chroma is interleaved."""
@@ -249,7 +219,7 @@ def test_three_launches_planar_and_five_interleaved_whatever_n():
         for images, want in ((items[:k], [1, 1, 1]), (_interleaved(items[:k]), [2, 2, 1])):
             fn = lambda: aa.resize_many_ycbcr(images, [13, 19], "cubic", out_dtype=torch.bfloat16, mean=MEAN, std=STD, **sub(k))  # noqa: E731
             fn()  # (module load and allocator warm-up stay outside the count)
-            names = _count_launches(fn)
+            names = kit_gpu.count_launches(fn)
             assert len(names) == sum(want), (k, names)
             assert [sum(1 for nm in names if part in nm) for part in ("many_tables", "many_hpass", "ycc_vpass")] == want, (k, names)
 
@@ -262,4 +232,4 @@ def test_no_cache_is_read_or_written_and_a_side_stream_is_served():
         y = _call("center", "linear")
     s.synchronize()
     assert (len(tables._cache), len(tables._box_cache), len(aa._plans)) == before
-    _assert_equal(y, _nchw(ref.expected("center", "linear")), "side stream")
+    kit_gpu.assert_bits(y, _nchw(ref.expected("center", "linear")), "side stream")
