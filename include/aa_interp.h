@@ -551,6 +551,43 @@ int aa_resample_many_ycbcr(const void *desc_host, const void *desc_dev, void *ou
                            const aa_convert *cv /* NULL: uint8 */, int out_layout, aa_stream_t stream);
 int aa_ycbcr_to_rgb_u8(const uint8_t *ycbcr, uint8_t *rgb, int64_t n_px);
 
+/* ---- ragged position grids: one learned [H0, W0, D] embedding resampled to N token grids, forward and backward ------------------------
+ * What follows the patch plans above in a native-resolution vision transformer: its position embedding, a float grid [H0, W0, D], is
+ * resampled to every item's own token grid [gh_i, gw_i] and packed in the patch tokens' row order; it is a parameter, so there is a
+ * backward.  The arithmetic is aa_resample_fwd's for float images with AA_TABLE_F32 tables: item i is, bit for bit, what that call gives
+ * the grid as a [1, D, H0, W0] float32 image at size [gh_i, gw_i] (the horizontal pass first, an fp32 intermediate, taps in order, product
+ * and sum rounded apart), token t = ty * gw_i + tx holding the D channels of output pixel (ty, tx), rounded to nearest even ONCE to the
+ * output's element.  The output is [rows, D], dense: pad_to = 0 packs the items, item i's tokens at rows T_0 + .. + T_(i-1) on;
+ * pad_to = L > 0 gives every item L rows, rows = n * L, item i's tokens at row i * L on and its rows beyond T_i all-zero bits.
+ * aa_embed_many_plan is host arithmetic only (no HIP call: works without a device).  grids: n pairs (gh_i, gw_i), height first.  It
+ * writes one packed descriptor block — per item the ksize and scale of its two tables (aa_table_ksize's arithmetic), the row capacity of
+ * their adjoints (aa_table_transposed_ksize) and the four offsets into one table arena, then the int64 first rows of the items — into
+ * desc_host, desc_bytes >= aa_embed_many_desc_bytes(n), and reports the workspace (the arena) and the output's rows.  Errors:
+ * AA_ERR_BAD_FILTER; AA_ERR_BAD_SHAPE for n < 0, D, H0 or W0 below 1, any of them or a grid side beyond INT32_MAX / 4, a grid side below
+ * 1, T_i beyond INT32_MAX / 4 or beyond pad_to, pad_to < 0, or more lanes than one grid holds; AA_ERR_NULL; AA_ERR_WORKSPACE for a short
+ * block; AA_ERR_KSIZE.
+ * aa_resample_embed_many enqueues TWO launches whatever n: a table kernel (one workgroup per item and axis, the device functions of
+ * aa_table_build) and the resample, one lane per output row and four channels (one where D, a stride or an address is no multiple of
+ * four elements).  embed_dev: element (y, x, d) at embed_dev + (y * stride_row + x * stride_px + d) elements, strides in ELEMENTS, any
+ * non-negative value, the address aligned to the element (AA_ERR_STRIDES otherwise); in_dtype and out_dtype AA_F32, AA_F16 or AA_BF16,
+ * independently (AA_ERR_BAD_DTYPE otherwise).  out_dev [rows, D] elements, aligned to its element.
+ * aa_resample_embed_many_bwd enqueues TWO launches whatever n: the table kernel, which also builds every table's adjoint (the rows of
+ * aa_table_transpose), and a gather with one lane per source cell and four channels (or one).  With G_i the rows of item i in
+ * grad_tokens_dev ([rows, D] of grad_dtype, dense, the plan's rows; pad rows are not read) and b_i = aa_resample_bwd of float(G_i) as a
+ * [1, D, gh_i, gw_i] image in AA_F32 (the gather form), grad_embed_dev [H0, W0, D] of out_dtype, dense, is
+ *   acc = b_0;  acc = acc + b_i in fp32 for i = 1 .. n - 1 in ascending order;  element = acc rounded to nearest even once.
+ * No atomics: the result is deterministic and does not depend on the launch shape.  n == 0 launches nothing (the caller zero-fills).
+ * Both: desc_dev (8-byte aligned) and workspace_dev (16-byte aligned, at least the plan's size) as aa_resample_many_u8; n, D, H0, W0,
+ * the filter and pad_to are the plan's.  Every check comes before the first launch; nothing is allocated, synchronised or read back, and
+ * no table cache is touched.  Added without an ABI version change (additive). */
+size_t aa_embed_many_desc_bytes(int64_t n);
+int aa_embed_many_plan(int filter, int64_t n, int64_t D, int64_t H0, int64_t W0, const int64_t *grids, int64_t pad_to /* 0: packed */,
+                       void *desc_host, size_t desc_bytes, size_t *workspace_bytes, int64_t *out_rows);
+int aa_resample_embed_many(const void *desc_host, const void *desc_dev, const void *embed_dev, int in_dtype, int64_t stride_row,
+                           int64_t stride_px, void *out_dev, int out_dtype, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+int aa_resample_embed_many_bwd(const void *desc_host, const void *desc_dev, const void *grad_tokens_dev, int grad_dtype, void *grad_embed_dev,
+                               int out_dtype, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
 /* ---- ragged Image.reduce: N uint8 images of N sizes, each with its own integer box and factors, into one arena ------------------------
  * Pillow's first step of Image.resize(reducing_gap=...) for a list: every large item is read ONCE by an integer box mean, and the ragged
  * resize above then runs over the small results, which it reads where they lie (an arena offset is just another pointer of an

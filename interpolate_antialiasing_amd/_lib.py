@@ -58,6 +58,7 @@ EXPORTS = (
     "aa_many_desc_bytes_maps", "aa_many_plan_maps", "aa_resample_many_maps",
     "aa_many_desc_bytes_ycbcr", "aa_many_plan_ycbcr", "aa_resample_many_ycbcr", "aa_ycbcr_to_rgb_u8",
     "aa_set_launch_shape", "aa_last_launch_shape",
+    "aa_embed_many_desc_bytes", "aa_embed_many_plan", "aa_resample_embed_many", "aa_resample_embed_many_bwd",
 )
 
 
@@ -199,6 +200,21 @@ class ReduceManyItem(ctypes.Structure):
                 ("rh", ctypes.c_int32), ("sx", ctypes.c_int32), ("xtiles", ctypes.c_int32), ("mult", ctypes.c_uint32 * 4)]
 
 
+class EmbedHeader(ctypes.Structure):
+    """Head of the block aa_embed_many_plan writes (csrc/aa_embed_many.h AAEmbedHeader; opaque to C callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("D", ctypes.c_int32), ("H0", ctypes.c_int32), ("W0", ctypes.c_int32),
+                ("filter", ctypes.c_int32), ("pad_to", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("out_rows", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64 * 2)]
+
+
+class EmbedItem(ctypes.Structure):
+    """One item of that block (csrc/aa_embed_many.h AAEmbedItem): the workspace offsets of its two tables and their adjoints, its token
+    grid, the tables' row lengths and the two float scales."""
+    _fields_ = [("tab_h", ctypes.c_int64), ("tab_w", ctypes.c_int64), ("tr_h", ctypes.c_int64), ("tr_w", ctypes.c_int64),
+                ("gh", ctypes.c_int32), ("gw", ctypes.c_int32), ("ksize_h", ctypes.c_int32), ("ksize_w", ctypes.c_int32),
+                ("trk_h", ctypes.c_int32), ("trk_w", ctypes.c_int32), ("scale_h", ctypes.c_float), ("scale_w", ctypes.c_float)]
+
+
 class LaunchShapeIn(ctypes.Structure):
     """aa_launch_shape_in: what a fused family's launch shape is chosen from (csrc/aa_launch_shape.h); occupancy[s] for s = 1..8 strips."""
     _fields_ = [("family", ctypes.c_int32), ("nstrips", ctypes.c_int32), ("strips_per_block", ctypes.c_int32), ("spb_forced", ctypes.c_int32),
@@ -252,6 +268,10 @@ def near_desc_view(buf, n: int):
 
 def maps_desc_view(buf, n: int):
     return desc_view(buf, n, MapsHeader, MapsItem)
+
+
+def embed_desc_view(buf, n: int):
+    return desc_view(buf, n, EmbedHeader, EmbedItem)
 
 
 def many_placed_view(buf, n: int):
@@ -401,6 +421,14 @@ def load() -> ctypes.CDLL:
     L.aa_resample_many_ycbcr.restype = i32
     L.aa_ycbcr_to_rgb_u8.argtypes = [vp, vp, i64]
     L.aa_ycbcr_to_rgb_u8.restype = i32
+    L.aa_embed_many_desc_bytes.argtypes = [i64]
+    L.aa_embed_many_desc_bytes.restype = sz
+    L.aa_embed_many_plan.argtypes = [i32, i64, i64, i64, i64, ctypes.POINTER(i64), i64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_embed_many_plan.restype = i32
+    L.aa_resample_embed_many.argtypes = [vp, vp, vp, i32, i64, i64, vp, i32, vp, sz, vp]
+    L.aa_resample_embed_many.restype = i32
+    L.aa_resample_embed_many_bwd.argtypes = [vp, vp, vp, i32, vp, i32, vp, sz, vp]
+    L.aa_resample_embed_many_bwd.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "aa_box.h"
+#include "aa_embed_many.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_maps.h"
@@ -587,6 +588,28 @@ int aa_resample_many_maps(const void *desc_host, const void *desc_dev, void *out
                           aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_many_maps(desc_host, desc_dev, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- ragged position grids ---------------------------------------------------------------------------------------------------------------
+size_t aa_embed_many_desc_bytes(int64_t n) { return aa_embed_desc_size(n); }
+
+int aa_embed_many_plan(int filter, int64_t n, int64_t D, int64_t H0, int64_t W0, const int64_t *grids, int64_t pad_to, void *desc_host,
+                       size_t desc_bytes, size_t *workspace_bytes, int64_t *out_rows) {
+  return aa_embed_plan_host(filter, n, D, H0, W0, grids, pad_to, desc_host, desc_bytes, workspace_bytes, out_rows);
+}
+
+int aa_resample_embed_many(const void *desc_host, const void *desc_dev, const void *embed_dev, int in_dtype, int64_t stride_row, int64_t stride_px,
+                           void *out_dev, int out_dtype, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_embed_many(desc_host, desc_dev, embed_dev, in_dtype, stride_row, stride_px, out_dev, out_dtype, workspace_dev, workspace_bytes,
+                              (hipStream_t)stream);
+}
+
+int aa_resample_embed_many_bwd(const void *desc_host, const void *desc_dev, const void *grad_tokens_dev, int grad_dtype, void *grad_embed_dev,
+                               int out_dtype, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_embed_many_bwd(desc_host, desc_dev, grad_tokens_dev, grad_dtype, grad_embed_dev, out_dtype, workspace_dev, workspace_bytes,
+                                  (hipStream_t)stream);
 }
 
 size_t aa_many_desc_bytes_ycbcr(int64_t n) { return aa_ycc_desc_size(n); }

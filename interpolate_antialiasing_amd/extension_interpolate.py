@@ -43,6 +43,9 @@ Differences, all additive:
   * ``resize_many_to_patches(images, patch, mode, sizes=, patch_format=, pad_to=, ...)``: the same list, every item resized to its own
     multiple of the patch, converted and cut into ViT patch tokens: one packed [sum T_i, C * ph * pw] matrix (or a zero-padded
     [N, L, C * ph * pw] one) from the same three launches;
+  * ``resize_embed_to_tokens(embed, grids, mode, pad_to=, out_dtype=)``: the model's learned position grid [H0, W0, D] resampled to every
+    item's token grid in the reference's fp32 arithmetic and packed in those tokens' row order, two launches whatever N; differentiable,
+    and ``resize_embed_to_tokens_backward`` is its deterministic backward, the ordered fp32 sum of the items' gather-form adjoints;
   * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -62,7 +65,8 @@ import torch
 
 from . import _lib, boxmath, tables
 
-__all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+__all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -1239,6 +1243,159 @@ def resize_many_to_patches(images, patch: Sequence[int], mode: str = "bicubic", 
         name, dev, L.aa_many_desc_bytes_patches(n), plan, lambda: torch.empty(shape, dtype=out_dtype, device=dev),
         lambda desc_host, desc_dev, out, ws, stream: L.aa_resample_many_u8_to_patches(desc_host, desc_dev, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                                                       ctypes.byref(cv), fmt, stream))[0]
+
+
+_EMBED_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _embed_grids(name: str, grids, pad_to):
+    """grids and pad_to of the position-grid calls, checked -> ([(gh, gw)], the int64 pairs for the planner, L or None)."""
+    try:
+        grids = list(grids)
+    except TypeError:
+        raise ValueError(f"{name}(): grids must be N pairs (gh, gw), got {grids!r}") from None
+    out = []
+    for i, g in enumerate(grids):
+        gh, gw = _many_int_pair(name, "grids", i, g)
+        if gh < 1 or gw < 1:
+            raise ValueError(f"{name}(): grids[{i}] = ({gh}, {gw}) must be positive")
+        if gh > _MANY_MAX or gw > _MANY_MAX or gh * gw > _MANY_MAX:
+            raise ValueError(f"{name}(): grids[{i}] = ({gh}, {gw}) is beyond the supported {_MANY_MAX}")
+        out.append((gh, gw))
+    if pad_to is not None:
+        if isinstance(pad_to, bool) or int(pad_to) != pad_to or pad_to < 1 or pad_to > 2 ** 31 - 1:
+            raise ValueError(f"{name}(): pad_to must be None or a positive integer, got {pad_to!r}")
+        pad_to = int(pad_to)
+        for i, (gh, gw) in enumerate(out):
+            if gh * gw > pad_to:
+                raise ValueError(f"{name}(): grids[{i}] = ({gh}, {gw}) is {gh * gw} tokens, more than pad_to = {pad_to}")
+    return out, (ctypes.c_int64 * max(2 * len(out), 1))(*[v for g in out for v in g]), pad_to
+
+
+def _embed_run(name: str, mode: str, dev, d: int, h0: int, w0: int, grids, flat, pad_to, alloc_out, launch):
+    """The plan of the position-grid calls and _many_run: ``launch(L, desc_host, desc_dev, out, ws, stream)``."""
+    L = _lib.load()
+    n = len(grids)
+    out_rows = ctypes.c_int64(0)
+    rows = boxmath.token_offsets(grids, (1, 1))[-1] if pad_to is None else n * pad_to
+
+    def plan(desc, nbytes, ws_bytes):
+        rc = L.aa_embed_many_plan(_lib.FILTER_IDS[mode], n, d, h0, w0, flat, pad_to or 0, desc, nbytes, ws_bytes, ctypes.byref(out_rows))
+        assert rc < 0 or out_rows.value == rows, (out_rows.value, rows, pad_to)
+        return rc
+
+    return _many_run(name, dev, L.aa_embed_many_desc_bytes(n), plan, alloc_out,
+                     lambda desc_host, desc_dev, out, ws, stream: launch(L, desc_host, desc_dev, out, ws, stream))[0]
+
+
+def _resize_embed_forward(embed: torch.Tensor, grids, flat, pad_to, mode: str, out_dtype) -> torch.Tensor:
+    name = "resize_embed_to_tokens"
+    h0, w0, d = embed.shape
+    n = len(grids)
+    rows = boxmath.token_offsets(grids, (1, 1))[-1]
+    shape = (rows, d) if pad_to is None else (n, pad_to, d)
+    if n == 0:
+        return torch.empty(shape, dtype=out_dtype, device=embed.device)
+    return _embed_run(name, mode, embed.device, d, h0, w0, grids, flat, pad_to, lambda: torch.empty(shape, dtype=out_dtype, device=embed.device),
+                      lambda L, desc_host, desc_dev, out, ws, stream: L.aa_resample_embed_many(
+                          desc_host, desc_dev, embed.data_ptr(), _DTYPE_IDS[embed.dtype], embed.stride(0), embed.stride(1), out.data_ptr(),
+                          _DTYPE_IDS[out_dtype], ws.data_ptr(), ws.numel(), stream))
+
+
+class _ResizeEmbedToTokens(torch.autograd.Function):
+    """resize_embed_to_tokens for an embedding that requires grad: the backward plans again from the saved grids."""
+
+    @staticmethod
+    def forward(ctx, embed, grids, flat, pad_to, mode, out_dtype):
+        ctx.embed_size, ctx.embed_dtype = tuple(embed.shape), embed.dtype
+        ctx.grids, ctx.pad_to, ctx.mode = grids, pad_to, mode
+        return _resize_embed_forward(embed, grids, flat, pad_to, mode, out_dtype)
+
+    @staticmethod
+    def backward(ctx, grad_tokens):
+        ge = resize_embed_to_tokens_backward(grad_tokens, ctx.embed_size, ctx.grids, ctx.mode, pad_to=ctx.pad_to, dtype=ctx.embed_dtype)
+        return ge, None, None, None, None, None
+
+
+def resize_embed_to_tokens(embed: torch.Tensor, grids, mode: str = "bicubic", *, pad_to: Optional[int] = None, out_dtype=None) -> torch.Tensor:
+    """A learned position grid resampled to every item's own token grid and packed in ``resize_many_to_patches``'s row order: what a
+    native-resolution vision transformer (NaViT, NaFlex, VLM towers) adds to those tokens.  ``embed`` is [H0, W0, D], float32, float16 or
+    bfloat16 on the GPU, read where it lies: ``stride(2) == 1``, any row and pixel stride, any element-aligned address — a view such as
+    ``pos_embed[0, 1:].view(H0, W0, D)``, which skips a class token, is not copied.  ``grids``: N pairs (gh_i, gw_i), height first, each
+    at least 1 — what ``boxmath.patch_grids(sizes, patch)`` returns.  With ``F`` the ``<mode>_forward`` of this module, item i is, bit
+    for bit,
+
+        F(embed.float().permute(2, 0, 1)[None], [gh_i, gw_i])[0].permute(1, 2, 0).reshape(gh_i * gw_i, D).to(out_dtype)
+
+    the reference's fp32 arithmetic (the horizontal pass first, an fp32 intermediate, product and sum rounded apart, antialiased where an
+    axis shrinks) with ONE rounding to nearest even at the store, and the result is the ``torch.cat`` of the items, [sum T_i, D], item i at
+    rows ``boxmath.token_offsets(grids, (1, 1))[i]`` on; or [N, L, D] with literal zeros (+0.0) beyond T_i (``pad_to=L``; an item of more
+    than L tokens raises ValueError).  ``mode``: any of the five filters' names; ``align_corners`` is always False.  ``out_dtype``: None
+    (``embed.dtype``), float32, float16 or bfloat16.  N == 0 gives [0, D] or [0, L, D].
+
+    Differentiable: when ``embed`` requires grad the result carries a backward, ``resize_embed_to_tokens_backward`` with
+    ``dtype=embed.dtype``.  Two launches and one non-blocking descriptor copy whatever N and whatever the grids; nothing is read back, no
+    table cache is touched, the call does not synchronise."""
+    name = "resize_embed_to_tokens"
+    if not isinstance(embed, torch.Tensor) or embed.dim() != 3:
+        raise ValueError(f"{name}(): embed must be a tensor [H0, W0, D]")
+    if embed.dtype not in _EMBED_DTYPES:
+        raise NotImplementedError(f"{name}(): embed of {embed.dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+    out_dtype = embed.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _EMBED_DTYPES:
+        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    h0, w0, d = embed.shape
+    if h0 < 1 or w0 < 1 or d < 1 or max(h0, w0, d) > _MANY_MAX:
+        raise ValueError(f"{name}(): embed of shape {tuple(embed.shape)}: every size must be in 1 .. {_MANY_MAX}")
+    if d > 1 and embed.stride(2) != 1:
+        raise ValueError(f"{name}(): embed must have stride(2) == 1 (channels last), got strides {embed.stride()}")
+    grids, flat, pad_to = _embed_grids(name, grids, pad_to)
+    _require_gpu(embed, name)
+    if embed.requires_grad and torch.is_grad_enabled():
+        return _ResizeEmbedToTokens.apply(embed, grids, flat, pad_to, mode, out_dtype)
+    return _resize_embed_forward(embed.detach(), grids, flat, pad_to, mode, out_dtype)
+
+
+def resize_embed_to_tokens_backward(grad_tokens: torch.Tensor, embed_size: Sequence[int], grids, mode: str = "bicubic", *,
+                                    pad_to: Optional[int] = None, dtype=torch.float32) -> torch.Tensor:
+    """The backward of ``resize_embed_to_tokens``: the gradient of the [H0, W0, D] position grid from the tokens' gradient,
+    [sum T_i, D] or [N, L, D] (``pad_to=L``; rows beyond T_i are not read), float32, float16 or bfloat16.  With ``b_i`` the existing
+    gather-form backward of item i's rows in fp32, ``<mode>_backward(G_i.float() as [1, D, gh_i, gw_i], [gh_i, gw_i], [1, D, H0, W0])``,
+    the result is, bit for bit, ``acc = b_0``, then ``acc = acc + b_i`` in fp32 for i = 1 .. N - 1 in ascending order, then
+    ``acc.to(dtype)`` as [H0, W0, D], contiguous.  No atomics: deterministic, whatever the launch shape.  N == 0 gives zeros.
+    Two launches whatever N; nothing is read back, the call does not synchronise."""
+    name = "resize_embed_to_tokens_backward"
+    if not isinstance(grad_tokens, torch.Tensor):
+        raise ValueError(f"{name}(): grad_tokens must be a tensor")
+    if grad_tokens.dtype not in _EMBED_DTYPES:
+        raise NotImplementedError(f"{name}(): grad_tokens of {grad_tokens.dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+    if dtype not in _EMBED_DTYPES:
+        raise NotImplementedError(f"{name}(): dtype {dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    try:
+        h0, w0, d = (int(v) for v in embed_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}(): embed_size must be (H0, W0, D), got {embed_size!r}") from None
+    if h0 < 1 or w0 < 1 or d < 1 or max(h0, w0, d) > _MANY_MAX:
+        raise ValueError(f"{name}(): embed_size = ({h0}, {w0}, {d}): every size must be in 1 .. {_MANY_MAX}")
+    grids, flat, pad_to = _embed_grids(name, grids, pad_to)
+    n = len(grids)
+    rows = boxmath.token_offsets(grids, (1, 1))[-1]
+    shape = (rows, d) if pad_to is None else (n, pad_to, d)
+    if tuple(grad_tokens.shape) != shape:
+        raise ValueError(f"{name}(): grad_tokens of shape {tuple(grad_tokens.shape)}, expected {shape}")
+    _require_gpu(grad_tokens, name)
+    dev = grad_tokens.device
+    if n == 0:
+        return torch.zeros((h0, w0, d), dtype=dtype, device=dev)
+    g = grad_tokens.detach().contiguous()
+    return _embed_run(name, mode, dev, d, h0, w0, grids, flat, pad_to, lambda: torch.empty((h0, w0, d), dtype=dtype, device=dev),
+                      lambda L, desc_host, desc_dev, out, ws, stream: L.aa_resample_embed_many_bwd(
+                          desc_host, desc_dev, g.data_ptr(), _DTYPE_IDS[g.dtype], out.data_ptr(), _DTYPE_IDS[dtype], ws.data_ptr(), ws.numel(),
+                          stream))
 
 
 def _reduce_many_factors(name: str, factors, n: int):

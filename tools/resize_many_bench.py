@@ -73,6 +73,17 @@ half the items flipped.  No other GPU code produces these bits, so the contestan
 launches) and the one call (3 launches); resize_many_nearest on the same geometry (the maps viewed as int16) is the copy-only floor.
 No bar is set; what is required is three launches whatever N, and that the numbers are written down.
 
+--embed: what follows the patch tokens in such a tower — its learned position grid, 16 x 16 x 768 float32, resampled to the token grids
+of 64 camera-sized images (patch 16, fit_patch_sizes(max_tokens=256)), bicubic, bfloat16 tokens, forward alone and forward + backward
+(bfloat16 gradients, a float32 gradient of the grid) — two ways:
+
+  loop  timm's NaFlexVit method with the existing calls: one cubic_forward per DISTINCT grid, to(bfloat16), cat in the items' order; for
+        the backward the gradients of the items of a grid are summed, one cubic_backward per distinct grid, and the results added up;
+  call  resize_embed_to_tokens / resize_embed_to_tokens_backward: two launches each, whatever N.
+
+The forward gives the same bits; the loop's backward sums equal grids first, so its last bits differ.  The call must take less time than
+the loop by more than the two spreads together; launches are counted with torch's profiler.  With --trace K: K calls of each for a kernel trace.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
@@ -89,6 +100,7 @@ results into one tensor; (c) writes the batch.
   python tools/resize_many_bench.py --nearest > out.txt  # only Pillow's NEAREST for a list (above); profiles/resize_many_nearest.txt
   python tools/resize_many_bench.py --maps > out.txt     # only Pillow's I;16 resize for a list (below); profiles/resize_many_maps.txt
   python tools/resize_many_bench.py --ycbcr > out.txt    # only 4:2:0 planes to the batch (above); profiles/resize_many_ycbcr.txt
+  python tools/resize_many_bench.py --embed > out.txt    # only the position grid to the token grids (above); profiles/resize_embed_many.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -724,6 +736,81 @@ def reduce_rate(args, torch, aa, timed):
             print(f"  {m} against {d}: {stat[m][0] / stat[d][0]:.3f} x the kernel time; the ranges {'do not overlap' if apart else 'overlap'}")
 
 
+def embed(args, torch, aa, timed):
+    """resize_embed_to_tokens and its backward against timm's method with the existing calls: one forward (one backward) per distinct grid."""
+    from interpolate_antialiasing_amd import boxmath
+
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)]
+    patch, h0, w0, d = (16, 16), 16, 16, 768
+    grids = boxmath.patch_grids(boxmath.fit_patch_sizes(shapes, patch, max_tokens=256), patch)
+    offs = boxmath.token_offsets(grids, (1, 1))
+    distinct = sorted(set(grids))
+    members = {g: [i for i, q in enumerate(grids) if q == g] for g in distinct}
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    pos = torch.randn((h0, w0, d), device="cuda", generator=gen)  # the fp32 parameter
+    grad = torch.randn((offs[-1], d), device="cuda", generator=gen).to(torch.bfloat16)  # what the AMP model hands back
+    if args.trace:  # (under a profiler's kernel trace: the one call, both ways)
+        for _ in range(WARM_CALLS + args.trace):
+            aa.resize_embed_to_tokens(pos, grids, "bicubic", out_dtype=torch.bfloat16)
+            aa.resize_embed_to_tokens_backward(grad, (h0, w0, d), grids, "bicubic")
+        torch.cuda.synchronize()
+        return
+    img = pos.permute(2, 0, 1)[None]  # [1, D, H0, W0] over the same memory (channels_last)
+
+    def loop_forward():
+        per = {g: aa.cubic_forward(img, list(g))[0].permute(1, 2, 0).reshape(g[0] * g[1], d).to(torch.bfloat16) for g in distinct}
+        return torch.cat([per[g] for g in grids])
+
+    def loop_backward(g_tokens):
+        acc = None
+        for (gh, gw), idx in members.items():
+            gsum = torch.stack([g_tokens[offs[i]:offs[i + 1]] for i in idx]).float().sum(0)
+            b = aa.cubic_backward(gsum.view(gh, gw, d).permute(2, 0, 1)[None], [gh, gw], [1, d, h0, w0])
+            acc = b if acc is None else acc + b
+        return acc[0].permute(1, 2, 0).contiguous()
+
+    def call_forward():
+        return aa.resize_embed_to_tokens(pos, grids, "bicubic", out_dtype=torch.bfloat16)
+
+    def call_backward(g_tokens):
+        return aa.resize_embed_to_tokens_backward(g_tokens, (h0, w0, d), grids, "bicubic")
+
+    print(f"resize_many_bench --embed: a {h0} x {w0} x {d} float32 position grid to the token grids of N = {N} camera-sized images, H in [1080, 3000], "
+          f"W in [1440, 4000] (seed {SEED}); library: {os.path.basename(_lib_path())}")
+    print(f"patch {patch[0]} x {patch[1]}, fit_patch_sizes(max_tokens=256): {offs[-1]} tokens, {len(distinct)} distinct grids, "
+          f"{min(b - a for a, b in zip(offs, offs[1:]))} .. {max(b - a for a, b in zip(offs, offs[1:]))} tokens per item; bicubic, bfloat16 tokens and gradients")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]")
+    a, b = loop_forward(), call_forward()
+    assert a.shape == b.shape and torch.equal(a.view(torch.int16), b.view(torch.int16)), "resize_embed_to_tokens differs from the loop"
+    ga, gb = loop_backward(grad), call_backward(grad)
+    # (the loop adds the gradients of equal grids first: another order of the same sum, so the last bits differ)
+    err = float((ga - gb).abs().max() / ga.abs().max())
+    assert err < 1e-5, f"the backward differs from the loop: {err}"
+    print(f"forward: the same bits; backward: max |difference| / max |gradient| = {err:.2e} (the loop sums equal grids first)")
+    for title, loop_fn, call_fn in (("forward", loop_forward, call_forward),
+                                    ("forward + backward", lambda: (loop_forward(), loop_backward(grad)), lambda: (call_forward(), call_backward(grad)))):
+        contestants = {"loop: one call per distinct grid, to(bf16), cat": loop_fn, "call: resize_embed_to_tokens": call_fn}
+        for fn in contestants.values():
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in contestants}
+        for _ in range(args.rounds):
+            for k, fn in contestants.items():
+                times[k].append(timed(fn))
+        print(f"\n{title}")
+        stat = {}
+        for k, v in times.items():
+            stat[k] = (statistics.median(v), min(v), max(v))
+            launches = count_launches(torch, contestants[k])
+            print(f"  {k:50s} {stat[k][0]:8.3f} [{stat[k][1]:8.3f} .. {stat[k][2]:8.3f}]   kernel launches per batch: "
+                  f"{launches if launches is not None else 'not measured'}")
+        (ml, ll, hl), (mc, lc, hc) = stat.values()
+        verdict = "the one call is faster" if ml - mc > (hl - ll) + (hc - lc) else "THE ONE CALL IS NOT FASTER by more than the spreads"
+        print(f"  call against loop: {ml / mc:.2f} x; median gain {ml - mc:.3f} ms, the two spreads together {(hl - ll) + (hc - lc):.3f} ms: {verdict}")
+
+
 def _lib_path():
     from interpolate_antialiasing_amd import _lib
 
@@ -746,6 +833,8 @@ def main():
     ap.add_argument("--maps", action="store_true", help="only Pillow's I;16 resize for measured maps: resize_many_maps against the call per item")
     ap.add_argument("--ycbcr", action="store_true", help="only resize_many_ycbcr (4:2:0 planes in) against resize_many_to_float on interleaved RGB "
                     "and against the torch conversion a user writes today; with --trace K: K calls of the planar form for a kernel trace")
+    ap.add_argument("--embed", action="store_true", help="only resize_embed_to_tokens and its backward against one existing call per distinct grid; "
+                    "with --trace K: K calls of each for a kernel trace")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -788,6 +877,9 @@ def main():
 
     if args.trace and args.ycbcr:
         ycbcr(args, torch, aa, None)
+        return
+    if args.trace and args.embed:
+        embed(args, torch, aa, None)
         return
     if args.trace:
         for _ in range(WARM_CALLS + args.trace):
@@ -843,6 +935,9 @@ def main():
         return
     if args.ycbcr:
         ycbcr(args, torch, aa, timed)
+        return
+    if args.embed:
+        embed(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
