@@ -27,7 +27,9 @@ extern "C" {
 #endif
 
 #define AA_INTERP_ABI_VERSION 3 /* 3: aa_resample_fwd_ex (flags), aa_resample_fwd_strided, aa_set_store_form, aa_convert.flags; every other
-                                   v2 entry point unchanged */
+                                   v2 entry point unchanged.  Added since without a version change (additive; a caller looks the
+                                   symbol up): aa_back_many_desc_bytes, aa_back_many_plan, aa_resample_back_many, with aa_back_item
+                                   and the aa_dtype values AA_I16 .. AA_BOOL that only they take */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -54,7 +56,9 @@ enum aa_status {
 enum aa_filter { AA_FILTER_LINEAR = 0, AA_FILTER_CUBIC = 1, AA_FILTER_BOX = 2, AA_FILTER_HAMMING = 3, AA_FILTER_LANCZOS = 4 };
 
 /* Element type of the image tensors. */
-enum aa_dtype { AA_U8 = 0, AA_F32 = 1, AA_F64 = 2, AA_F16 = 3, AA_BF16 = 4 };
+enum aa_dtype { AA_U8 = 0, AA_F32 = 1, AA_F64 = 2, AA_F16 = 3, AA_BF16 = 4,
+                /* what aa_back_many_plan stores besides: labels and masks, never an image's element (AA_ERR_BAD_DTYPE everywhere else) */
+                AA_I16 = 5, AA_I32 = 6, AA_I64 = 7, AA_BOOL = 8 };
 /* AA_F16 / AA_BF16 (the reference dispatches float and double only): AA_TABLE_F32 tables, fp32
  * arithmetic in the reference's order, fp32 intermediate between the passes, ONE round-to-nearest-even at the store —
  * i.e. exactly  half(reference_fp32(float(x))). */
@@ -587,6 +591,57 @@ int aa_resample_embed_many(const void *desc_host, const void *desc_dev, const vo
                            int64_t stride_px, void *out_dev, int out_dtype, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 int aa_resample_embed_many_bwd(const void *desc_host, const void *desc_dev, const void *grad_tokens_dev, int grad_dtype, void *grad_embed_dev,
                                int out_dtype, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back: N float sources [K, h_i, w_i] to N outputs of N sizes, reduced over K before the store -----------------
+ * The return path of the ragged calls above.  A segmentation, depth or mask head answers [N, K, H, W] on the canvas; item i is the
+ * rectangle of it that image i occupied, and what is wanted is that rectangle at the image's own [oh_i, ow_i], mostly only its argmax
+ * over the K classes or its sign.  The arithmetic is aa_resample_fwd's for float images with AA_TABLE_F32 tables: with R_i, bit for
+ * bit, what that call gives float(item i) as a [1, K, h_i, w_i] float32 image at size [oh_i, ow_i] (the horizontal pass first, an fp32
+ * intermediate, tap 0 unconditionally and the others in order, product and sum rounded apart), item i of the arena is
+ *   reduce 0 (values)   [K, oh_i, ow_i] of out_dtype AA_F32 / AA_F16 / AA_BF16: R_i rounded to nearest even ONCE;
+ *   reduce 1 (argmax)   [oh_i, ow_i] of out_dtype AA_U8 (K <= 256) / AA_I16 (K <= 32768) / AA_I32 / AA_I64: the lowest k at which R_i is
+ *                       greatest, a NaN counting as greater than every number and the first NaN winning (numpy.argmax over axis 0);
+ *                       the K values of a pixel are never stored;
+ *   reduce 2 (greater)  [K, oh_i, ow_i] bytes, out_dtype AA_BOOL or AA_U8: 1 where R_i > threshold (compared as floats; a NaN gives 0),
+ * dense, at byte out_offsets[i] of the arena, a multiple of 16; the bytes between items are not written.  An item with AA_MANY_FLIP_X
+ * holds column ow_i - 1 - x of that result at column x.
+ * aa_back_item: data_dev is the rectangle's corner, class k, row y, pixel x of it at data_dev + k * stride_ch + y * stride_row +
+ * x * stride_px ELEMENTS; non-negative strides in one of two classes, ONE per call (`layout`) — AA_NCHW: planes, stride_px = 1, any
+ * stride_ch and stride_row; AA_NHWC: interleaved classes, stride_ch = 1, stride_px = K, any stride_row (AA_ERR_STRIDES otherwise; the
+ * stride of an axis of one element is not looked at).  Nothing outside the rectangle is read.
+ * aa_back_many_plan is host arithmetic only (no HIP call: works without a device).  It writes one packed descriptor block — per item
+ * its pointer and strides, sizes and flags, the ksize and scale of its two tables (aa_table_ksize(filter, AA_TABLE_F32, in, out, 0, 0.0);
+ * (float)in / (float)out), their offsets in the workspace (header, xmin, xsize and weight rows each, no gather section, one table after
+ * the other) and its arena
+ * offset, then the int64 running count of work units (an output row times 256 columns) — into desc_host, desc_bytes >=
+ * aa_back_many_desc_bytes(n), and reports the workspace, the arena and the items' offsets.  Errors, in this order: AA_ERR_BAD_FILTER;
+ * AA_ERR_BAD_LAYOUT; AA_ERR_BAD_SHAPE for n outside 0 .. INT32_MAX / 4, K outside 1 .. INT32_MAX / 4, an unknown reduce, K beyond what an
+ * AA_U8 / AA_I16 label holds; AA_ERR_NULL; AA_ERR_WORKSPACE for a short block; then per item AA_ERR_NULL for a null pointer, AA_ERR_BAD_SHAPE for a
+ * size outside 1 .. INT32_MAX / 4, K * oh_i * ow_i beyond 2^40, an unknown flag bit, an arena beyond 2^43 bytes or more work units than
+ * one grid holds, AA_ERR_STRIDES, AA_ERR_KSIZE; last AA_ERR_BAD_DTYPE for an out_dtype the reduction does not store.
+ * aa_resample_back_many enqueues TWO launches whatever n and whatever the sizes: a table kernel (one workgroup per item and axis, the
+ * device function of aa_table_build) and the resample, one workgroup per work unit and a lane per output column, which computes every
+ * class's vertical sum of horizontal sums in registers and hands it to the reduction; there is no intermediate in memory.  in_dtype:
+ * AA_F32, AA_F16 or AA_BF16 (AA_ERR_BAD_DTYPE otherwise), every data_dev aligned to it (AA_ERR_STRIDES).  threshold: finite
+ * (AA_ERR_BAD_SHAPE; looked at for reduce 2 only).  arena_dev: arena_bytes >= the plan's (AA_ERR_WORKSPACE), aligned to out_dtype's
+ * element (AA_ERR_BAD_SHAPE); desc_dev (8-byte aligned) and workspace_dev (16-byte aligned, at least the plan's size) as
+ * aa_resample_many_u8; a block that is not this planner's AA_ERR_BAD_SHAPE.  Every check comes before the first launch; nothing is
+ * allocated, synchronised or read back, and no table cache is touched.  Not built: fractional rectangles, a dense padded output, a
+ * backward, softmax.  Added without an ABI version change (additive). */
+typedef struct aa_back_item {
+  const void *data_dev;                      /* the rectangle's first element of class 0 */
+  int64_t stride_ch, stride_row, stride_px;  /* in ELEMENTS */
+  int64_t h, w;                              /* the rectangle */
+  int64_t oh, ow;                            /* the size it is resampled to */
+  int32_t flags;                             /* 0 or AA_MANY_FLIP_X */
+  int32_t reserved;
+} aa_back_item;
+size_t aa_back_many_desc_bytes(int64_t n);
+int aa_back_many_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce /* 0 values, 1 argmax, 2 greater */,
+                      int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
+                      int64_t *out_offsets /* n, bytes */);
+int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
+                          void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged Image.reduce: N uint8 images of N sizes, each with its own integer box and factors, into one arena ------------------------
  * Pillow's first step of Image.resize(reducing_gap=...) for a list: every large item is read ONCE by an integer box mean, and the ragged

@@ -34,6 +34,7 @@ def by_filter_name(value) -> dict:
 
 FILTER_IDS = by_filter_name(lambda f: f.id)
 U8, F32, F64, F16, BF16 = 0, 1, 2, 3, 4
+I16, I32, I64, BOOL = 5, 6, 7, 8  # aa_dtype: what only aa_back_many_plan stores (labels, masks)
 NCHW, NHWC = 0, 1
 TABLE_PIL, TABLE_F32, TABLE_F64 = 0, 1, 2
 ERR_BAD_DTYPE = -2
@@ -59,6 +60,7 @@ EXPORTS = (
     "aa_many_desc_bytes_ycbcr", "aa_many_plan_ycbcr", "aa_resample_many_ycbcr", "aa_ycbcr_to_rgb_u8",
     "aa_set_launch_shape", "aa_last_launch_shape",
     "aa_embed_many_desc_bytes", "aa_embed_many_plan", "aa_resample_embed_many", "aa_resample_embed_many_bwd",
+    "aa_back_many_desc_bytes", "aa_back_many_plan", "aa_resample_back_many",
 )
 
 
@@ -215,6 +217,29 @@ class EmbedItem(ctypes.Structure):
                 ("trk_h", ctypes.c_int32), ("trk_w", ctypes.c_int32), ("scale_h", ctypes.c_float), ("scale_w", ctypes.c_float)]
 
 
+class BackItemIn(ctypes.Structure):
+    """aa_back_item: one item of the ragged return path (strides in ELEMENTS; data_dev at the region's corner)."""
+    _fields_ = [("data_dev", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("stride_px", ctypes.c_int64),
+                ("h", ctypes.c_int64), ("w", ctypes.c_int64), ("oh", ctypes.c_int64), ("ow", ctypes.c_int64), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class BackHeader(ctypes.Structure):
+    """Head of the block aa_back_many_plan writes (csrc/aa_many_back.h AABackHeader; opaque to C callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("K", ctypes.c_int32), ("filter", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("reduce", ctypes.c_int32), ("out_dtype", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64)]
+
+
+class BackItem(ctypes.Structure):
+    """One item of that block (csrc/aa_many_back.h AABackItem): the region's corner and element strides, the workspace offsets of its two
+    tables, its arena offset in bytes, sizes, the tables' row lengths, the two float scales, flags and its column tiles."""
+    _fields_ = [("src", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("stride_px", ctypes.c_int64),
+                ("tab_h", ctypes.c_int64), ("tab_w", ctypes.c_int64), ("out_off", ctypes.c_int64), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("oh", ctypes.c_int32), ("ow", ctypes.c_int32), ("ksize_h", ctypes.c_int32), ("ksize_w", ctypes.c_int32),
+                ("scale_h", ctypes.c_float), ("scale_w", ctypes.c_float), ("flags", ctypes.c_int32), ("xtiles", ctypes.c_int32)]
+
+
 class LaunchShapeIn(ctypes.Structure):
     """aa_launch_shape_in: what a fused family's launch shape is chosen from (csrc/aa_launch_shape.h); occupancy[s] for s = 1..8 strips."""
     _fields_ = [("family", ctypes.c_int32), ("nstrips", ctypes.c_int32), ("strips_per_block", ctypes.c_int32), ("spb_forced", ctypes.c_int32),
@@ -243,6 +268,8 @@ MAPS_HROWS = 16     # hull rows per work unit of the maps call's horizontal pass
 MAPS_VCOLS = 256    # canvas columns per work unit of the maps call's vertical pass (csrc/aa_many_maps.h AA_MAPS_VCOLS)
 YCC_SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "440": 3}  # aa_ycbcr_image.subsampling (AA_YCC_*)
 YCC_VROWS, YCC_VCOLS = 4, 256  # canvas rows and columns per work unit of the YCbCr call's vertical pass (csrc/aa_many_ycbcr.h)
+BACK_VALUES, BACK_ARGMAX, BACK_GREATER = 0, 1, 2  # aa_back_many_plan reduce (csrc/aa_many_back.h AA_BACK_*)
+BACK_TILE = 256     # output columns per work unit of the return path's resample (csrc/aa_many_back.h AA_BACK_TILE)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
 
@@ -272,6 +299,10 @@ def maps_desc_view(buf, n: int):
 
 def embed_desc_view(buf, n: int):
     return desc_view(buf, n, EmbedHeader, EmbedItem)
+
+
+def back_desc_view(buf, n: int):
+    return desc_view(buf, n, BackHeader, BackItem)
 
 
 def many_placed_view(buf, n: int):
@@ -429,6 +460,13 @@ def load() -> ctypes.CDLL:
     L.aa_resample_embed_many.restype = i32
     L.aa_resample_embed_many_bwd.argtypes = [vp, vp, vp, i32, vp, i32, vp, sz, vp]
     L.aa_resample_embed_many_bwd.restype = i32
+    L.aa_back_many_desc_bytes.argtypes = [i64]
+    L.aa_back_many_desc_bytes.restype = sz
+    L.aa_back_many_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),
+                                    ctypes.POINTER(i64)]
+    L.aa_back_many_plan.restype = i32
+    L.aa_resample_back_many.argtypes = [vp, vp, i32, ctypes.c_float, vp, sz, vp, sz, vp]
+    L.aa_resample_back_many.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

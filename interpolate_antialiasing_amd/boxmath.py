@@ -304,6 +304,36 @@ def center_offset(v: int, o: int) -> int:
     return -int(round((v - o) / 2.0)) if v >= o else (o - v) // 2
 
 
+def placed_regions(sizes, offsets, output_size):
+    """[(y0, x0, h, w)]: the rectangle of the [oh, ow] canvas that ``resize_many(..., sizes=, offsets=)`` gave each item — height first,
+    like ``output_size``; what ``resize_many_back(regions=)`` takes to bring a prediction on that canvas back to the images.  ``sizes``:
+    N pairs (vh_i, vw_i), or None per entry for the whole canvas; ``offsets``: None (every corner at (0, 0)), "center"
+    (``center_offset`` per axis) or N pairs (py_i, px_i), None per entry for (0, 0).  An item that does not lie wholly on the canvas
+    raises ValueError naming it: a cropped item has no way back to its whole image."""
+    oh, ow = (int(v) for v in output_size)
+    center = isinstance(offsets, str)
+    if center and offsets != "center":
+        raise ValueError(f"placed_regions: offsets must be None, 'center' or one entry per item, got {offsets!r}")
+    if offsets is not None and not center and len(offsets) != len(sizes):
+        raise ValueError(f"placed_regions: offsets must hold one entry per item ({len(sizes)}), got {len(offsets)}")
+    out = []
+    for i, s in enumerate(sizes):
+        vh, vw = (oh, ow) if s is None else (int(s[0]), int(s[1]))
+        if vh <= 0 or vw <= 0:
+            raise ValueError(f"placed_regions: sizes[{i}] = ({vh}, {vw}) must be positive")
+        if center:
+            py, px = center_offset(vh, oh), center_offset(vw, ow)
+        elif offsets is None or offsets[i] is None:
+            py, px = 0, 0
+        else:
+            py, px = int(offsets[i][0]), int(offsets[i][1])
+        if py < 0 or px < 0 or py + vh > oh or px + vw > ow:
+            raise ValueError(f"placed_regions: item {i} of size ({vh}, {vw}) at ({py}, {px}) does not lie wholly on the ({oh}, {ow}) canvas: "
+                             "a cropped item has no way back to its whole image")
+        out.append((py, px, vh, vw))
+    return out
+
+
 def axis_is_full(in_size: int, in0: float, in1: float) -> bool:
     return in0 == 0 and in1 == in_size
 

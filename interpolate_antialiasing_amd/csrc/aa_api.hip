@@ -8,6 +8,7 @@
 
 #include "aa_box.h"
 #include "aa_embed_many.h"
+#include "aa_many_back.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_maps.h"
@@ -610,6 +611,20 @@ int aa_resample_embed_many_bwd(const void *desc_host, const void *desc_dev, cons
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_embed_many_bwd(desc_host, desc_dev, grad_tokens_dev, grad_dtype, grad_embed_dev, out_dtype, workspace_dev, workspace_bytes,
                                   (hipStream_t)stream);
+}
+
+// ---- ragged predictions back ---------------------------------------------------------------------------------------------------------------
+size_t aa_back_many_desc_bytes(int64_t n) { return aa_back_desc_size(n); }
+
+int aa_back_many_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce, int out_dtype, void *desc_host,
+                      size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
+  return aa_back_plan_host(filter, layout, n, K, items, reduce, out_dtype, desc_host, desc_bytes, workspace_bytes, arena_bytes, out_offsets);
+}
+
+int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
+                          void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_back_many(desc_host, desc_dev, in_dtype, threshold, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t aa_many_desc_bytes_ycbcr(int64_t n) { return aa_ycc_desc_size(n); }

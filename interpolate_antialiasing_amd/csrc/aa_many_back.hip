@@ -1,0 +1,315 @@
+// aa_many_back.hip — canvas predictions back to each image's own size: N float sources [K, h_i, w_i] resampled to N outputs of N sizes,
+// and reduced over the K classes before anything is stored.  The arithmetic is the reference's fp32 passes as aa_embed_many.hip states
+// them (aa_generic.hip's contract): AA_TABLE_F32 tables, the horizontal pass first, an fp32 intermediate, tap 0 unconditionally and taps
+// 1 .. xsize - 1 in order, product and sum rounded apart (-ffp-contract=off), one round-to-nearest-even at the store.  Two launches
+// whatever N and whatever the sizes:
+//   1. back_tables    one workgroup per (item, axis): the rows of the item's table (table_build_f32_one, aa_table_rows.h — the device
+//                     function aa_tables.hip runs, so item i's tables are the bits aa_table_build gives its shape);
+//   2. back_resample  one workgroup per work unit, an output row of an item times AA_BACK_TILE consecutive output columns, a lane per
+//                     column: the row's vertical window is the workgroup's, the lane's horizontal window its own, both read once; then
+//                     the classes, AA_BACK_UNROLL at a time, each the vertical sum of horizontal sums.  No intermediate is staged: a lane
+//                     recomputes the horizontal sum of each tap row, the same operations in the same order as the two-pass form, so the
+//                     same bits.  What happens to a class's value is the epilogue, a template parameter: stored to its plane (Values),
+//                     compared with the running best (Argmax: the K values of a pixel never leave registers), or compared with the
+//                     threshold (Greater).  A flipped item's column x is stored at ow - 1 - x.
+// Sources are read where they lie: planes (classes stride_ch apart, pixels consecutive) or interleaved pixels (classes consecutive, pixels
+// K apart), the same code with the strides as arguments; interleaved sources whose K and addresses allow it load AA_BACK_UNROLL classes
+// as one vector.  Every element offset is 64-bit.  Stores are one element a lane, consecutive along the wave, so an arena on any
+// element boundary is served and the 16-byte gaps between items are never written.
+// Shared with the other ragged calls: aa_many_dev.h (the item of a unit, the element types), aa_many_host.h (the block, the launch checks).
+
+#include <string.h>
+
+#include "aa_many_back.h"
+#include "aa_many_dev.h"
+#include "aa_many_host.h"
+#include "aa_table_rows.h"
+
+namespace {
+
+// ---- 1. tables ---------------------------------------------------------------------------------------------------------------------------
+// Workgroup 2 i builds item i's H axis, 2 i + 1 its W axis, as embed_tables does without adjoints.  A table's header is zeroed first: the
+// row function keeps max_taps there, and nobody reads that field back.
+__global__ void __launch_bounds__(AA_BACK_THREADS) back_tables(const AABackItem *items, char *ws, int filter) {
+  const AABackItem &it = items[blockIdx.x >> 1];
+  const bool horiz = blockIdx.x & 1;
+  const int in_size = horiz ? it.w : it.h, out_size = horiz ? it.ow : it.oh;
+  const int ksize = horiz ? it.ksize_w : it.ksize_h;
+  const float scale = horiz ? it.scale_w : it.scale_h;
+  char *tab = ws + (horiz ? it.tab_w : it.tab_h);
+  if (threadIdx.x < sizeof(aa_table_header) / 4) ((int32_t *)tab)[threadIdx.x] = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < out_size; i += AA_BACK_THREADS) table_build_f32_one(i, filter, in_size, out_size, ksize, scale, tab);
+}
+
+// ---- the sums ------------------------------------------------------------------------------------------------------------------------------
+__device__ inline float to_f32(float x) { return x; }
+__device__ inline float to_f32(f16_t x) { return (float)x.v; }
+__device__ inline float to_f32(bf16_t x) { return __uint_as_float((unsigned)x.v << 16); }
+
+template <typename T, int V> struct alignas(sizeof(T) * V) Vec { T v[V]; };
+
+// A table row, as aa_embed_many.hip's table_row reads it: the window [x0, x0 + n) and its weights.  n is max(xsize, 1) (tap 0 is read
+// unconditionally; a row without taps has weight 0 there), never more than a weight row holds, and the window is kept inside
+// [0, in_size): nothing outside an item's region is read.
+struct Row { int x0, n; const float *w; };
+__device__ inline Row table_row(const char *tab, int in_size, int out_size, int ksize, int i) {
+  const TableView<float> tv = make_table_view<float>(tab, out_size, ksize);
+  int n = tv.xsize[i];
+  n = n > 1 ? (n < ksize ? n : ksize) : 1;
+  int x0 = tv.xmin[i];
+  if (x0 > in_size - n) x0 = in_size - n;
+  if (x0 < 0) x0 = 0;
+  return {x0, n, tv.w + (size_t)i * ksize};
+}
+
+// V classes of one pixel from p: one vector (VEC: consecutive classes at an address that allows it) or V loads `sch` elements apart.
+template <typename T, int V, bool VEC> __device__ inline void load_classes(const T *p, int64_t sch, float (&e)[V]) {
+  if constexpr (VEC) {
+    const Vec<T, V> r = *(const Vec<T, V> *)p;
+#pragma unroll
+    for (int c = 0; c < V; c++) e[c] = to_f32(r.v[c]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < V; c++) e[c] = to_f32(p[c * sch]);
+  }
+}
+
+// acc = the vertical sum over ry's window of the horizontal sums over rx's window, for V classes from p = element (the lane's first
+// class, row ry.x0, pixel rx.x0); classes `sch`, rows `prow` and pixels `ppx` elements apart.  hs is the fp32 intermediate of the
+// two-pass form; the operations and their order are aa_embed_many.hip's window_sums.  A weight is read once for the V classes.
+template <typename T, int V, bool VEC>
+__device__ inline void class_sums(const T *p, int64_t sch, int64_t prow, int64_t ppx, const Row &ry, const Row &rx, float (&acc)[V]) {
+  for (int j = 0; j < ry.n; j++) {
+    const T *rp = p + j * prow;
+    float hs[V], e[V];
+    load_classes<T, V, VEC>(rp, sch, e);
+    const float w0 = rx.w[0];
+#pragma unroll
+    for (int c = 0; c < V; c++) hs[c] = e[c] * w0;
+    for (int k = 1; k < rx.n; k++) {
+      load_classes<T, V, VEC>(rp + k * ppx, sch, e);
+      const float wk = rx.w[k];
+#pragma unroll
+      for (int c = 0; c < V; c++) hs[c] = hs[c] + e[c] * wk;
+    }
+    const float wj = ry.w[j];
+#pragma unroll
+    for (int c = 0; c < V; c++) acc[c] = j == 0 ? hs[c] * wj : acc[c] + hs[c] * wj;
+  }
+}
+
+// ---- the epilogues -------------------------------------------------------------------------------------------------------------------------
+// put(k, v): class k's fp32 value of the lane's pixel, k ascending; done(): after the last class.  `at` is the lane's element of plane 0
+// of the item's output (the flip already in it), `plane` the elements of a plane.
+template <typename TOut> struct Values {
+  TOut *at;
+  int64_t plane;
+  __device__ Values(void *out, int64_t at_, int64_t plane_, float) : at((TOut *)out + at_), plane(plane_) {}
+  __device__ void put(int k, float v) { at[k * plane] = to_elem<TOut>(v); }
+  __device__ void done() {}
+};
+// The lowest k of the greatest value, a NaN greater than every number and the first NaN kept: numpy.argmax.
+template <typename TLabel> struct Argmax {
+  TLabel *at;
+  float best;
+  int idx;
+  __device__ Argmax(void *out, int64_t at_, int64_t, float) : at((TLabel *)out + at_), best(0.0f), idx(0) {}
+  __device__ void put(int k, float v) {
+    if (k == 0 || (best == best && (v > best || v != v))) {
+      best = v;
+      idx = k;
+    }
+  }
+  __device__ void done() { *at = (TLabel)idx; }
+};
+struct Greater {  // (a NaN is not greater: 0)
+  uint8_t *at;
+  int64_t plane;
+  float thr;
+  __device__ Greater(void *out, int64_t at_, int64_t plane_, float thr_) : at((uint8_t *)out + at_), plane(plane_), thr(thr_) {}
+  __device__ void put(int k, float v) { at[k * plane] = v > thr ? 1 : 0; }
+  __device__ void done() {}
+};
+
+struct BackArgs {
+  const AABackItem *items;
+  const int64_t *unit0;
+  const char *ws;
+  char *arena;
+  float threshold;
+  int n, K;
+};
+
+// ---- 2. the resample -----------------------------------------------------------------------------------------------------------------------
+template <typename TIn, bool VEC, typename Epi>
+__global__ void __launch_bounds__(AA_BACK_TILE) back_resample(BackArgs a) {
+  constexpr int U = AA_BACK_UNROLL;
+  const int64_t unit = blockIdx.x;
+  const int item = aa_unit_item(a.unit0, a.n, unit);
+  const AABackItem &it = a.items[item];
+  const int64_t u = unit - a.unit0[item];
+  const int y = (int)(u / it.xtiles);
+  const int x = (int)(u - (int64_t)y * it.xtiles) * AA_BACK_TILE + (int)threadIdx.x;
+  if (x >= it.ow) return;  // (no barrier below)
+  const Row ry = table_row(a.ws + it.tab_h, it.h, it.oh, it.ksize_h, y), rx = table_row(a.ws + it.tab_w, it.w, it.ow, it.ksize_w, x);
+  const int64_t sch = it.stride_ch, prow = it.stride_row, ppx = it.stride_px;
+  const TIn *p = (const TIn *)it.src + ry.x0 * prow + rx.x0 * ppx;
+  const int xs = (it.flags & AA_MANY_FLIP_X) ? it.ow - 1 - x : x;
+  Epi epi(a.arena + it.out_off, (int64_t)y * it.ow + xs, (int64_t)it.oh * it.ow, a.threshold);
+  int k = 0;
+  for (; k + U <= a.K; k += U) {
+    float acc[U];
+    class_sums<TIn, U, VEC>(p + k * sch, sch, prow, ppx, ry, rx, acc);
+#pragma unroll
+    for (int c = 0; c < U; c++) epi.put(k + c, acc[c]);
+  }
+  for (; k < a.K; k++) {
+    float acc[1];
+    class_sums<TIn, 1, false>(p + k * sch, sch, prow, ppx, ry, rx, acc);
+    epi.put(k, acc[0]);
+  }
+  epi.done();
+}
+
+template <typename TIn, bool VEC, typename Epi> void launch_as(const BackArgs &a, unsigned units, hipStream_t stream) {
+  hipLaunchKernelGGL((back_resample<TIn, VEC, Epi>), dim3(units), dim3(AA_BACK_TILE), 0, stream, a);
+}
+template <typename TIn, bool VEC> void launch_epi(int reduce, int out_dtype, const BackArgs &a, unsigned units, hipStream_t stream) {
+  if (reduce == AA_BACK_GREATER) launch_as<TIn, VEC, Greater>(a, units, stream);
+  else if (reduce == AA_BACK_ARGMAX) {
+    if (out_dtype == AA_U8) launch_as<TIn, VEC, Argmax<uint8_t>>(a, units, stream);
+    else if (out_dtype == AA_I16) launch_as<TIn, VEC, Argmax<int16_t>>(a, units, stream);
+    else if (out_dtype == AA_I32) launch_as<TIn, VEC, Argmax<int32_t>>(a, units, stream);
+    else launch_as<TIn, VEC, Argmax<int64_t>>(a, units, stream);
+  } else if (out_dtype == AA_F32) launch_as<TIn, VEC, Values<float>>(a, units, stream);
+  else if (out_dtype == AA_F16) launch_as<TIn, VEC, Values<f16_t>>(a, units, stream);
+  else launch_as<TIn, VEC, Values<bf16_t>>(a, units, stream);
+}
+template <bool VEC> void launch_in(int in_dtype, int reduce, int out_dtype, const BackArgs &a, unsigned units, hipStream_t stream) {
+  if (in_dtype == AA_F32) launch_epi<float, VEC>(reduce, out_dtype, a, units, stream);
+  else if (in_dtype == AA_F16) launch_epi<f16_t, VEC>(reduce, out_dtype, a, units, stream);
+  else launch_epi<bf16_t, VEC>(reduce, out_dtype, a, units, stream);
+}
+
+inline bool float_dtype(int dt) { return dt == AA_F32 || dt == AA_F16 || dt == AA_BF16; }
+inline size_t elem_bytes(int dt) {
+  switch (dt) {
+    case AA_U8: case AA_BOOL: return 1;
+    case AA_F16: case AA_BF16: case AA_I16: return 2;
+    case AA_I64: return 8;
+    default: return 4;
+  }
+}
+// What a reduction stores: values a float, argmax a label, greater a byte of 0 or 1.
+inline bool out_dtype_ok(int reduce, int dt) {
+  if (reduce == AA_BACK_VALUES) return float_dtype(dt);
+  if (reduce == AA_BACK_ARGMAX) return dt == AA_U8 || dt == AA_I16 || dt == AA_I32 || dt == AA_I64;
+  return dt == AA_BOOL || dt == AA_U8;
+}
+
+}  // namespace
+
+// ---- host: the planner -------------------------------------------------------------------------------------------------------------------
+size_t aa_back_desc_size(int64_t n) { return aa_desc_size(sizeof(AABackHeader), sizeof(AABackItem), n); }
+
+int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *in, int reduce, int out_dtype, void *desc_host,
+                      size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
+  if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (n < 0 || n > kAAManyMax || K < 1 || K > kAAManyMax || reduce < AA_BACK_VALUES || reduce > AA_BACK_GREATER) return AA_ERR_BAD_SHAPE;
+  // (a label type that cannot hold K - 1)
+  if (reduce == AA_BACK_ARGMAX && ((out_dtype == AA_U8 && K > 256) || (out_dtype == AA_I16 && K > 32768))) return AA_ERR_BAD_SHAPE;
+  if (!desc_host || !workspace_bytes || !arena_bytes || (n > 0 && (!in || !out_offsets))) return AA_ERR_NULL;
+  if (desc_bytes < aa_back_desc_size(n)) return AA_ERR_WORKSPACE;
+  const size_t eb = elem_bytes(out_dtype);
+  AABackHeader *hd = (AABackHeader *)desc_host;
+  AABackItem *items = (AABackItem *)(hd + 1);
+  int64_t *unit0 = (int64_t *)(items + n);
+  size_t ws = 0, arena = 0;
+  int64_t units = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const aa_back_item &im = in[i];
+    if (!im.data_dev) return AA_ERR_NULL;
+    if (im.h <= 0 || im.w <= 0 || im.h > kAAManyMax || im.w > kAAManyMax || im.oh <= 0 || im.ow <= 0 || im.oh > kAAManyMax || im.ow > kAAManyMax ||
+        (im.flags & ~AA_MANY_FLIP_X))
+      return AA_ERR_BAD_SHAPE;
+    if (im.oh * im.ow > AA_BACK_MAX_ELEMS / K) return AA_ERR_BAD_SHAPE;
+    // (the stride of an axis of one element never matters)
+    if ((K > 1 && im.stride_ch < 0) || (im.h > 1 && im.stride_row < 0) || (im.w > 1 && im.stride_px < 0)) return AA_ERR_STRIDES;
+    if (layout == AA_NHWC ? ((K > 1 && im.stride_ch != 1) || (im.w > 1 && im.stride_px != K)) : (im.w > 1 && im.stride_px != 1)) return AA_ERR_STRIDES;
+    AABackItem it;
+    memset(&it, 0, sizeof(it));
+    it.src = im.data_dev;
+    it.stride_ch = K > 1 ? im.stride_ch : 0;
+    it.stride_row = im.h > 1 ? im.stride_row : 0;
+    it.stride_px = im.w > 1 ? im.stride_px : 0;
+    it.h = (int32_t)im.h; it.w = (int32_t)im.w; it.oh = (int32_t)im.oh; it.ow = (int32_t)im.ow;
+    const int kh = aa_table_ksize(filter, AA_TABLE_F32, im.h, im.oh, 0, 0.0), kw = aa_table_ksize(filter, AA_TABLE_F32, im.w, im.ow, 0, 0.0);
+    if (kh < 0) return kh;
+    if (kw < 0) return kw;
+    it.ksize_h = kh; it.ksize_w = kw;
+    it.scale_h = (float)im.h / (float)im.oh;
+    it.scale_w = (float)im.w / (float)im.ow;
+    it.tab_h = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.oh, kh);
+    it.tab_w = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.ow, kw);
+    it.flags = im.flags;
+    it.xtiles = (int32_t)((im.ow + AA_BACK_TILE - 1) / AA_BACK_TILE);
+    arena = aa_align16(arena);
+    it.out_off = (int64_t)arena;
+    out_offsets[i] = (int64_t)arena;
+    arena += (size_t)(reduce == AA_BACK_ARGMAX ? 1 : K) * (size_t)im.oh * (size_t)im.ow * eb;
+    if (arena > (size_t)AA_BACK_MAX_ELEMS * 8) return AA_ERR_BAD_SHAPE;
+    unit0[i] = units;
+    units += im.oh * (int64_t)it.xtiles;
+    if (units > INT32_MAX) return AA_ERR_BAD_SHAPE;  // (one grid)
+    items[i] = it;
+  }
+  unit0[n] = units;
+  if (!out_dtype_ok(reduce, out_dtype)) return AA_ERR_BAD_DTYPE;
+  memset(hd, 0, sizeof(*hd));
+  hd->magic = AA_BACK_MAGIC;
+  hd->n = (int32_t)n; hd->K = (int32_t)K; hd->filter = filter; hd->layout = layout;
+  hd->reduce = reduce; hd->out_dtype = out_dtype;
+  hd->units = units;
+  hd->ws_bytes = (int64_t)ws;
+  hd->arena_bytes = (int64_t)arena;
+  *workspace_bytes = ws;
+  *arena_bytes = arena;
+  return AA_OK;
+}
+
+// ---- host: the two launches ----------------------------------------------------------------------------------------------------------------
+// Every check comes before the first launch.  desc_host is the planned block, so the items' pointers are looked at here: against the
+// element of in_dtype, which the planner did not know, and for whether every address of an interleaved list allows the vector loads.
+int aa_launch_back_many(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
+                        void *workspace_dev, size_t workspace_bytes, hipStream_t stream) {
+  const AABackHeader *hd = (const AABackHeader *)desc_host;
+  if (hd->magic != AA_BACK_MAGIC || !aa_filter_valid(hd->filter) || hd->n < 0 || hd->K < 1 || hd->units < 0 || hd->units > INT32_MAX ||
+      hd->reduce < AA_BACK_VALUES || hd->reduce > AA_BACK_GREATER || (hd->layout != AA_NCHW && hd->layout != AA_NHWC))
+    return AA_ERR_BAD_SHAPE;
+  if (!float_dtype(in_dtype) || !out_dtype_ok(hd->reduce, hd->out_dtype)) return AA_ERR_BAD_DTYPE;
+  if (hd->reduce == AA_BACK_GREATER && !(threshold - threshold == 0.0f)) return AA_ERR_BAD_SHAPE;  // (not finite)
+  const int rc = aa_many_check_launch(hd->n, desc_dev, arena_dev, workspace_dev, workspace_bytes, hd->ws_bytes, elem_bytes(hd->out_dtype));
+  if (rc != AA_OK || hd->n == 0) return rc;
+  if (arena_bytes < (size_t)hd->arena_bytes) return AA_ERR_WORKSPACE;
+  const AABackItem *host_items = (const AABackItem *)(hd + 1);
+  const size_t ei = elem_bytes(in_dtype);
+  bool vec = hd->layout == AA_NHWC && hd->K % AA_BACK_UNROLL == 0;
+  for (int64_t i = 0; i < hd->n; i++) {
+    const AABackItem &it = host_items[i];
+    if ((uintptr_t)it.src % ei) return AA_ERR_STRIDES;
+    vec = vec && (uintptr_t)it.src % (AA_BACK_UNROLL * ei) == 0 && it.stride_row % AA_BACK_UNROLL == 0;  // (stride_px is K or unused)
+  }
+  const AADescView<AABackItem> v = aa_desc_view<AABackHeader, AABackItem>(desc_dev, hd->n);
+  hipLaunchKernelGGL(back_tables, dim3(2u * (unsigned)hd->n), dim3(AA_BACK_THREADS), 0, stream, v.items, (char *)workspace_dev, (int)hd->filter);
+  AA_HIP_CHECK_LAUNCH();
+  BackArgs a;
+  a.items = v.items; a.unit0 = v.prefix; a.ws = (const char *)workspace_dev; a.arena = (char *)arena_dev;
+  a.threshold = threshold;
+  a.n = hd->n; a.K = hd->K;
+  if (vec) launch_in<true>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
+  else launch_in<false>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
+  AA_HIP_CHECK_LAUNCH();
+  return AA_OK;
+}

@@ -46,6 +46,9 @@ Differences, all additive:
   * ``resize_embed_to_tokens(embed, grids, mode, pad_to=, out_dtype=)``: the model's learned position grid [H0, W0, D] resampled to every
     item's token grid in the reference's fp32 arithmetic and packed in those tokens' row order, two launches whatever N; differentiable,
     and ``resize_embed_to_tokens_backward`` is its deterministic backward, the ordered fp32 sum of the items' gather-form adjoints;
+  * ``resize_many_back(pred, sizes, mode, regions=, flips=, reduce=, threshold=, out_dtype=)``: the way back — a model's [N, K, H, W] float
+    answer on the canvas resampled to every image's own size in the reference's fp32 arithmetic, as values, as the argmax over K or as
+    ``> threshold``, two launches whatever N; with ``reduce="argmax"`` the K values of a pixel are never stored;
   * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -66,7 +69,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -1396,6 +1399,193 @@ def resize_embed_to_tokens_backward(grad_tokens: torch.Tensor, embed_size: Seque
                       lambda L, desc_host, desc_dev, out, ws, stream: L.aa_resample_embed_many_bwd(
                           desc_host, desc_dev, g.data_ptr(), _DTYPE_IDS[g.dtype], out.data_ptr(), _DTYPE_IDS[dtype], ws.data_ptr(), ws.numel(),
                           stream))
+
+
+_BACK_MAX_ELEMS = 2 ** 40  # the library's bound on K * oh_i * ow_i (csrc/aa_many_back.h AA_BACK_MAX_ELEMS)
+# reduce -> (the planner's id, the default out_dtype, {out_dtype: (aa_dtype, the most classes it holds or None)})
+_BACK_REDUCE = {
+    None: (_lib.BACK_VALUES, None, {torch.float32: (_lib.F32, None), torch.float16: (_lib.F16, None), torch.bfloat16: (_lib.BF16, None)}),
+    "argmax": (_lib.BACK_ARGMAX, torch.int64, {torch.int64: (_lib.I64, None), torch.int32: (_lib.I32, None), torch.int16: (_lib.I16, 32768),
+                                               torch.uint8: (_lib.U8, 256)}),
+    "greater": (_lib.BACK_GREATER, torch.bool, {torch.bool: (_lib.BOOL, None), torch.uint8: (_lib.U8, None)}),
+}
+
+
+def _back_items(name: str, pred, channels: Optional[int]):
+    """pred of resize_many_back -> ([K, H_i, W_i] items, the device of a batch tensor or None, N, K), dtype, K, sizes and devices checked."""
+    if isinstance(pred, torch.Tensor):
+        if pred.dim() != 4:
+            raise ValueError(f"{name}(): one tensor must be [N, K, H, W], got {list(pred.shape)}")
+        if channels is None:
+            channels = int(pred.shape[1])
+        items, dev0 = list(pred.unbind(0)), pred.device
+    else:
+        items, dev0 = [], None
+        for i, t in enumerate(pred):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}(): pred[{i}] must be Tensor")
+            if t.dim() == 4 and t.shape[0] == 1:
+                t = t[0]
+            if t.dim() != 3:
+                raise ValueError(f"{name}(): pred[{i}] must be [K, H, W] or [1, K, H, W], got {list(t.shape)}")
+            items.append(t)
+    n = len(items)
+    if n == 0 and channels is None:
+        raise ValueError(f"{name}(): an empty list needs channels= (the K of the items)")
+    k = int(channels) if channels is not None else int(items[0].shape[0])
+    if not (1 <= k <= _MANY_MAX):
+        raise ValueError(f"{name}(): K must be in 1 .. {_MANY_MAX}, got K = {k}")
+    for i, t in enumerate(items):
+        if t.dtype not in _EMBED_DTYPES:
+            raise NotImplementedError(f"{name}(): pred[{i}] of {t.dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+        if t.dtype != items[0].dtype:
+            raise ValueError(f"{name}(): every item must have the same dtype: pred[{i}] is {t.dtype}, pred[0] {items[0].dtype}")
+        if int(t.shape[0]) != k:
+            raise ValueError(f"{name}(): every item must have the same K: pred[{i}] has {int(t.shape[0])}, expected {k}")
+        if not (int(t.shape[1]) > 0 and int(t.shape[2]) > 0):
+            raise ValueError(f"{name}(): pred[{i}] is empty: {list(t.shape)}")
+        if t.device != items[0].device:
+            raise ValueError(f"{name}(): every item must be on the same device: pred[{i}] is on {t.device}, pred[0] on {items[0].device}")
+    return items, dev0, n, k
+
+
+def _back_sizes(name: str, sizes, n: int, k: int):
+    try:
+        sizes = list(sizes)
+    except TypeError:
+        raise ValueError(f"{name}(): sizes must be N pairs (oh, ow), got {sizes!r}") from None
+    if len(sizes) != n:
+        raise ValueError(f"{name}(): sizes must hold one entry per item ({n}), got {len(sizes)}")
+    out = []
+    for i, s in enumerate(sizes):
+        oh, ow = _many_int_pair(name, "sizes", i, s)
+        if oh < 1 or ow < 1:
+            raise ValueError(f"{name}(): sizes[{i}] = ({oh}, {ow}) must be positive")
+        if oh > _MANY_MAX or ow > _MANY_MAX or oh * ow * k > _BACK_MAX_ELEMS:
+            raise ValueError(f"{name}(): sizes[{i}] = ({oh}, {ow}) with K = {k} is beyond the supported {_MANY_MAX} a side and "
+                             f"{_BACK_MAX_ELEMS} elements")
+        out.append((oh, ow))
+    return out
+
+
+def _back_regions(name: str, regions, items):
+    """regions of resize_many_back, checked -> [(y0, x0, h, w)], the whole item for None."""
+    n = len(items)
+    if regions is not None and len(regions) != n:
+        raise ValueError(f"{name}(): regions must hold one entry per item ({n}), got {len(regions)}")
+    out = []
+    for i, t in enumerate(items):
+        hh, ww = int(t.shape[1]), int(t.shape[2])
+        r = regions[i] if regions is not None else None
+        if r is None:
+            out.append((0, 0, hh, ww))
+            continue
+        try:
+            y0, x0, h, w = r
+            if any(isinstance(v, bool) or int(v) != v for v in (y0, x0, h, w)):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}(): regions[{i}] must be None or four integers (y0, x0, h, w), got {r!r}") from None
+        y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+        if h < 1 or w < 1:
+            raise ValueError(f"{name}(): regions[{i}] = ({y0}, {x0}, {h}, {w}) is empty")
+        if y0 < 0 or x0 < 0 or y0 + h > hh or x0 + w > ww:
+            raise ValueError(f"{name}(): regions[{i}] = ({y0}, {x0}, {h}, {w}) does not lie inside its item of size ({hh}, {ww})")
+        out.append((y0, x0, h, w))
+    return out
+
+
+def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips=None, reduce: Optional[str] = None, threshold: float = 0.0,
+                     out_dtype=None, channels: Optional[int] = None):
+    """A model's answer on the canvas, back at every image's own size: the return path of ``resize_many`` and its kin, for segmentation,
+    depth and mask heads.  ``pred``: one float32 / float16 / bfloat16 GPU tensor [N, K, H, W], or a sequence of N tensors [K, H_i, W_i]
+    (or [1, K, H_i, W_i]); the same K (1 .. 2^29 - 1), dtype and device for all.  Items are read where they lie, in one of two classes:
+    planes (``stride(2) == 1``, any plane and row stride) or interleaved classes (``stride(0) == 1``, ``stride(2) == K``: a channels_last
+    batch).  One class per call, the majority's; an item in neither, or in the other, is copied into it first.
+    ``regions``: None, or N entries, each None (the whole item) or integers (y0, x0, h, w) — HEIGHT FIRST, like ``output_size`` — the
+    rectangle of the item that image i occupied; exactly the view ``pred_i[:, y0:y0 + h, x0:x0 + w]``, and nothing outside it is read.
+    ``boxmath.placed_regions(sizes, offsets, output_size)`` gives the rectangles ``resize_many(..., sizes=, offsets=)`` placed the images
+    at.  ``sizes``: N pairs (oh_i, ow_i), the images' own sizes.  ``flips``: None or N booleans; a flipped item's column x holds column
+    ``ow_i - 1 - x`` of the unflipped result (the undo of a flipped test-time pass).  ``mode``: any of the five filters' names;
+    ``align_corners`` is always False.
+
+    With ``F`` the ``<mode>_forward`` of this module and ``R_i = F(view_i.float()[None], [oh_i, ow_i])[0]`` — the reference's fp32
+    arithmetic: the horizontal pass first, an fp32 intermediate, product and sum rounded apart, antialiased where an axis shrinks — the
+    result is a list of N tensors, bit for bit:
+
+      * ``reduce=None``: ``R_i.to(out_dtype)`` [K, oh_i, ow_i], ONE rounding to nearest even; ``out_dtype`` None (``pred``'s), float32,
+        float16 or bfloat16;
+      * ``reduce="argmax"``: [oh_i, ow_i], the lowest k at which ``R_i`` is greatest, taken on the fp32 value before any rounding to 16
+        bits; a NaN counts as greater than every number and the first NaN wins (``numpy.argmax`` over axis 0).  ``out_dtype`` None
+        (int64, what ``torch.argmax`` gives), uint8 (K <= 256), int16 (K <= 32768) or int32.  The K values of a pixel are never stored;
+      * ``reduce="greater"``: ``R_i > threshold`` [K, oh_i, ow_i] on the fp32 value; ``threshold`` a finite float, compared as float32; a
+        NaN gives False.  ``out_dtype`` None (bool) or uint8.
+
+    The tensors are contiguous views of ONE arena, each starting on a 16-byte boundary of it, as ``reduce_many`` returns its images.
+    N == 0 gives [] (a list then states K with ``channels=``).  Two launches whatever N and whatever the sizes — one builds every item's two
+    fp32 weight tables, one resamples and reduces — and one non-blocking copy of a packed descriptor; nothing is read back, no table cache
+    is touched, the call does not synchronise.  Not built: fractional regions, a dense padded output, a backward, softmax."""
+    name = "resize_many_back"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if reduce not in _BACK_REDUCE:
+        raise ValueError(f"{name}(): reduce must be None, 'argmax' or 'greater', got {reduce!r}")
+    reduce_id, default_dtype, out_dtypes = _BACK_REDUCE[reduce]
+    items, dev0, n, k = _back_items(name, pred, channels)
+    sizes = _back_sizes(name, sizes, n, k)
+    rects = _back_regions(name, regions, items)
+    flips = _many_flips(name, flips, n)
+    if out_dtype is None:
+        out_dtype = default_dtype if default_dtype is not None else (items[0].dtype if n else torch.float32)
+    if out_dtype not in out_dtypes:
+        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built for reduce={reduce!r}; {', '.join(str(d) for d in out_dtypes)}")
+    out_id, most = out_dtypes[out_dtype]
+    if most is not None and k > most:
+        raise ValueError(f"{name}(): out_dtype {out_dtype} holds labels below {most}, got K = {k}")
+    try:
+        threshold = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}(): threshold must be a finite float, got {threshold!r}") from None
+    if not math.isfinite(threshold) or not math.isfinite(ctypes.c_float(threshold).value):
+        raise ValueError(f"{name}(): threshold must be a finite float (as float32), got {threshold!r}")
+    if n == 0:
+        return []
+    for t in items:
+        _require_gpu(t, name)
+    dev = items[0].device
+    views = [t[:, y0:y0 + h, x0:x0 + w] for t, (y0, x0, h, w) in zip(items, rects)]
+    classes, interleaved = _many_layout(views, k)
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    recs, keep = (_lib.BackItemIn * n)(), []  # (keep: the copies of items outside the class, alive until the launches are enqueued)
+    for i, t in enumerate(views):
+        if not classes[i][0 if interleaved else 1]:
+            t = t.permute(1, 2, 0).contiguous().permute(2, 0, 1) if interleaved else t.contiguous()
+            keep.append(t)
+        r = recs[i]
+        r.data_dev = t.data_ptr()
+        r.h, r.w = int(t.shape[1]), int(t.shape[2])
+        r.oh, r.ow = sizes[i]
+        # (the stride of an axis of one element is arbitrary: hand over the class's own)
+        r.stride_ch = 1 if interleaved else (t.stride(0) if k > 1 else 0)
+        r.stride_row = t.stride(1) if r.h > 1 else 0
+        r.stride_px = k if interleaved else 1
+        r.flags = _lib.MANY_FLIP_X if flips is not None and flips[i] else 0
+    offs = (ctypes.c_int64 * n)()
+    arena_bytes = ctypes.c_size_t(0)
+    es = torch.empty((), dtype=out_dtype).element_size()
+    arena = _many_run(
+        name, dev, L.aa_back_many_desc_bytes(n),
+        lambda desc, nbytes, ws_bytes: L.aa_back_many_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, reduce_id, out_id, desc, nbytes, ws_bytes,
+                                                           ctypes.byref(arena_bytes), offs),
+        lambda: torch.empty((arena_bytes.value // es,), dtype=out_dtype, device=dev),
+        lambda desc_host, desc_dev, out, ws, stream: L.aa_resample_back_many(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], threshold, out.data_ptr(),
+                                                                            out.numel() * es, ws.data_ptr(), ws.numel(), stream))[0]
+    outs = []
+    for i, (oh, ow) in enumerate(sizes):
+        shape = (oh, ow) if reduce == "argmax" else (k, oh, ow)
+        outs.append(arena[offs[i] // es:offs[i] // es + math.prod(shape)].view(shape))
+    return outs
 
 
 def _reduce_many_factors(name: str, factors, n: int):

@@ -84,6 +84,17 @@ of 64 camera-sized images (patch 16, fit_patch_sizes(max_tokens=256)), bicubic, 
 The forward gives the same bits; the loop's backward sums equal grids first, so its last bits differ.  The call must take less time than
 the loop by more than the two spreads together; launches are counted with torch's profiler.  With --trace K: K calls of each for a kernel trace.
 
+--logits: the way back — [16, K, 512, 512] logits on a letterbox canvas (fit_sizes(longer=512), "center") to the 16 camera-sized images'
+own sizes and their argmax over K, bilinear, K = 19 and 150, float32 and bfloat16 logits — three ways:
+
+  a  the per-item loop of existing calls: linear_forward(crop.float()[None], size), then argmax(1);
+  b  resize_many_back(reduce=None), then argmax per item;
+  c  resize_many_back(reduce="argmax"): two launches whatever N.
+
+(c) gives (a)'s labels.  Per contestant: kernel launches (torch's profiler), ms per batch, and the growth of
+torch.cuda.max_memory_allocated over one call.  No ratio is a bar; the loop (a) is the yardstick, and the numbers are written down.
+(b)'s arena at K = 150 is 56 GB: --rounds 5 --batches 5 keeps the run short.
+
 Timing: device events around `--batches` batches that end in a synchronise; every contestant is warmed up first; the median and the
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
@@ -101,6 +112,8 @@ results into one tensor; (c) writes the batch.
   python tools/resize_many_bench.py --maps > out.txt     # only Pillow's I;16 resize for a list (below); profiles/resize_many_maps.txt
   python tools/resize_many_bench.py --ycbcr > out.txt    # only 4:2:0 planes to the batch (above); profiles/resize_many_ycbcr.txt
   python tools/resize_many_bench.py --embed > out.txt    # only the position grid to the token grids (above); profiles/resize_embed_many.txt
+  python tools/resize_many_bench.py --logits > out.txt   # only the way back: canvas logits to the images' own sizes, argmax (below);
+                                                         # profiles/resize_many_back.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -811,6 +824,76 @@ def embed(args, torch, aa, timed):
         print(f"  call against loop: {ml / mc:.2f} x; median gain {ml - mc:.3f} ms, the two spreads together {(hl - ll) + (hc - lc):.3f} ms: {verdict}")
 
 
+def logits(args, torch, aa, timed):
+    """resize_many_back against the per-item loop of existing calls: logits on a 512 x 512 letterbox canvas back to 16 camera-sized images,
+    argmax over K.  Per contestant: kernel launches, ms per batch, and the growth of torch.cuda.max_memory_allocated over one call."""
+    from interpolate_antialiasing_amd import boxmath
+
+    n, canvas = 16, (512, 512)
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    placed_sizes = boxmath.fit_sizes(shapes, longer=canvas[0])
+    regions = boxmath.placed_regions(placed_sizes, "center", canvas)
+    pixels = sum(h * w for h, w in shapes)
+    print(f"resize_many_bench --logits: [N, K, {canvas[0]}, {canvas[1]}] logits on a letterbox canvas (fit_sizes(longer={canvas[0]}), 'center') back to "
+          f"N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), {pixels / 1e6:.1f} M output pixels; bilinear; "
+          f"library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for k in (19, 150):
+        for dtype in (torch.float32, torch.bfloat16):
+            x = torch.randn((n, k) + canvas, device="cuda", generator=gen).to(dtype)
+
+            def loop():
+                out = []
+                for i, (y0, x0, h, w) in enumerate(regions):
+                    out.append(aa.linear_forward(x[i, :, y0:y0 + h, x0:x0 + w].float()[None], list(shapes[i])).argmax(1)[0])
+                return out
+
+            def values_then_argmax():
+                return [v.argmax(0) for v in aa.resize_many_back(x, shapes, regions=regions)]
+
+            def fused():
+                return aa.resize_many_back(x, shapes, regions=regions, reduce="argmax")
+
+            contestants = {"a: loop: linear_forward(crop.float()), argmax(1) per item": loop,
+                           "b: resize_many_back(reduce=None), argmax per item": values_then_argmax,
+                           "c: resize_many_back(reduce='argmax')": fused}
+            results = {}
+            for key, fn in contestants.items():
+                results[key] = fn()
+                fn()
+            torch.cuda.synchronize()
+            # (the 16-bit values of (b) are rounded before its argmax: only the float32 logits must agree everywhere)
+            same_a = all(torch.equal(p, q) for p, q in zip(results["a: loop: linear_forward(crop.float()), argmax(1) per item"], results["c: resize_many_back(reduce='argmax')"]))
+            assert same_a, "reduce='argmax' differs from the loop"
+            del results
+            times = {key: [] for key in contestants}
+            for _ in range(args.rounds):
+                for key, fn in contestants.items():
+                    times[key].append(timed(fn))
+            print(f"\nK = {k}, {str(dtype).replace('torch.', '')}: (c) gives the loop's labels")
+            stat = {}
+            for key, v in times.items():
+                stat[key] = (statistics.median(v), min(v), max(v))
+                launches = count_launches(torch, contestants[key])
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.max_memory_allocated()
+                r = contestants[key]()
+                torch.cuda.synchronize()
+                peak = torch.cuda.max_memory_allocated() - before
+                del r
+                print(f"  {key:62s} {stat[key][0]:9.3f} [{stat[key][1]:9.3f} .. {stat[key][2]:9.3f}]   launches {launches if launches is not None else 'not measured'}"
+                      f"   peak {peak / 1e6:10.1f} MB")
+            (ma, la, ha), (mb, lb, hb), (mc, lc, hc) = stat.values()
+            verdict = "(c) is faster" if ma - mc > (ha - la) + (hc - lc) else "(c) IS NOT FASTER than the loop by more than the spreads"
+            print(f"  (c) against (a): {ma / mc:.2f} x; (c) against (b): {mb / mc:.2f} x; median gain over (a) {ma - mc:.3f} ms, the two spreads together "
+                  f"{(ha - la) + (hc - lc):.3f} ms: {verdict}")
+            del x
+
+
 def _lib_path():
     from interpolate_antialiasing_amd import _lib
 
@@ -835,6 +918,8 @@ def main():
                     "and against the torch conversion a user writes today; with --trace K: K calls of the planar form for a kernel trace")
     ap.add_argument("--embed", action="store_true", help="only resize_embed_to_tokens and its backward against one existing call per distinct grid; "
                     "with --trace K: K calls of each for a kernel trace")
+    ap.add_argument("--logits", action="store_true", help="only resize_many_back: canvas logits back to the images' sizes and argmax, against the "
+                    "per-item loop of existing calls and against reduce=None followed by argmax")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -938,6 +1023,9 @@ def main():
         return
     if args.embed:
         embed(args, torch, aa, timed)
+        return
+    if args.logits:
+        logits(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
