@@ -29,7 +29,8 @@ extern "C" {
 #define AA_INTERP_ABI_VERSION 3 /* 3: aa_resample_fwd_ex (flags), aa_resample_fwd_strided, aa_set_store_form, aa_convert.flags; every other
                                    v2 entry point unchanged.  Added since without a version change (additive; a caller looks the
                                    symbol up): aa_back_many_desc_bytes, aa_back_many_plan, aa_resample_back_many, with aa_back_item
-                                   and the aa_dtype values AA_I16 .. AA_BOOL that only they take */
+                                   and the aa_dtype values AA_I16 .. AA_BOOL that only they take; aa_back_many_bwd_desc_bytes,
+                                   aa_back_many_bwd_plan, aa_resample_back_many_bwd, with aa_back_bwd_item */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -626,8 +627,8 @@ int aa_resample_embed_many_bwd(const void *desc_host, const void *desc_dev, cons
  * (AA_ERR_BAD_SHAPE; looked at for reduce 2 only).  arena_dev: arena_bytes >= the plan's (AA_ERR_WORKSPACE), aligned to out_dtype's
  * element (AA_ERR_BAD_SHAPE); desc_dev (8-byte aligned) and workspace_dev (16-byte aligned, at least the plan's size) as
  * aa_resample_many_u8; a block that is not this planner's AA_ERR_BAD_SHAPE.  Every check comes before the first launch; nothing is
- * allocated, synchronised or read back, and no table cache is touched.  Not built: fractional rectangles, a dense padded output, a
- * backward, softmax.  Added without an ABI version change (additive). */
+ * allocated, synchronised or read back, and no table cache is touched.  Not built: fractional rectangles, a dense padded output,
+ * softmax (the backward of reduce 0 is below).  Added without an ABI version change (additive). */
 typedef struct aa_back_item {
   const void *data_dev;                      /* the rectangle's first element of class 0 */
   int64_t stride_ch, stride_row, stride_px;  /* in ELEMENTS */
@@ -642,6 +643,54 @@ int aa_back_many_plan(int filter, int layout, int64_t n, int64_t K, const aa_bac
                       int64_t *out_offsets /* n, bytes */);
 int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
                           void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back, backward: N gradients [K, oh_i, ow_i] to N canvases [K, H_i, W_i] ---------------------------------------
+ * The backward of aa_resample_back_many's reduce 0, for losses taken at every image's own size.  Item i has a canvas [H_i, W_i], the
+ * rectangle (y0, x0, h, w) of it that the forward read, and the gradient G_i [K, oh_i, ow_i] of what the forward made of it.  With
+ * U_i = G_i, or G_i mirrored left to right for an item with AA_MANY_FLIP_X, and B_i, bit for bit, what aa_resample_bwd (the gather
+ * form) gives float(U_i) as a [1, K, oh_i, ow_i] float32 image for the input [1, K, h, w] with AA_TABLE_F32 tables (the horizontal
+ * adjoint pass first, an fp32 intermediate, tap 0 unconditionally and the others in ascending order, product and sum rounded apart),
+ * item i of the output is [K, H_i, W_i] (out_layout AA_NCHW) or [H_i, W_i, K] (AA_NHWC) of out_dtype AA_F32 / AA_F16 / AA_BF16: B_i
+ * rounded to nearest even ONCE inside the rectangle, +0.0 outside it.  An item whose grad_dev is null has no gradient: all +0.0, and
+ * nothing but its H and W is looked at.  No atomics: the bits do not depend on n, on the launch shape or on the run.  Item i lies at byte
+ * out_offsets[i] of the output: dense = 1 packs the items one after the other (equal canvases: one [n, K, H, W] tensor), dense = 0 puts
+ * each on a multiple of 16 and never writes the bytes between them.
+ * aa_back_bwd_item: class k, row r, column c of the gradient at grad_dev + k * stride_ch + r * stride_row + c ELEMENTS (columns are
+ * consecutive); non-negative strides, the stride of an axis of one element not looked at.  Nothing outside the gradient is read.
+ * aa_back_many_bwd_plan is host arithmetic only (no HIP call: works without a device).  It writes one packed descriptor block — a
+ * 64-byte header, per item its pointer and strides, sizes and flags, the ksize and scale of its two forward tables (as
+ * aa_back_many_plan), the row capacity of their adjoints (aa_table_transposed_ksize) and the four offsets into one table arena (none
+ * for an item without a gradient), its output offset, then the int64 running count of work units (4 canvas rows times 64 canvas
+ * columns of the WHOLE canvas) — into desc_host, desc_bytes >= aa_back_many_bwd_desc_bytes(n), and reports the workspace, the output's
+ * bytes and the items' offsets.  Errors, in this order: AA_ERR_BAD_FILTER; AA_ERR_BAD_LAYOUT; AA_ERR_BAD_SHAPE for n outside
+ * 0 .. INT32_MAX / 4, K outside 1 .. INT32_MAX / 4 or dense outside 0 .. 1; AA_ERR_NULL; AA_ERR_WORKSPACE for a short block; then per
+ * item AA_ERR_BAD_SHAPE for a canvas side outside 1 .. INT32_MAX / 4, K * H_i * W_i beyond 2^40 or an unknown flag bit, and for an item
+ * with a gradient a gradient side outside 1 .. INT32_MAX / 4, K * oh_i * ow_i beyond 2^40 or a rectangle that is empty or not inside the
+ * canvas, AA_ERR_STRIDES for a negative stride, AA_ERR_KSIZE, AA_ERR_BAD_SHAPE for an output beyond 2^43 bytes or more work units
+ * than one grid holds; last AA_ERR_BAD_DTYPE for an out_dtype that is not AA_F32, AA_F16 or AA_BF16.
+ * aa_resample_back_many_bwd enqueues TWO launches whatever n and whatever the sizes: a table kernel (one workgroup per item and axis:
+ * the forward table by the device function of aa_table_build, a barrier, its adjoint by that of aa_table_transpose) and the gather, one
+ * workgroup per work unit and a lane per canvas cell, which stores every element of the output — the zeros too; there is no memset —
+ * and keeps the fp32 intermediate in registers.  grad_dtype: AA_F32, AA_F16 or AA_BF16 (AA_ERR_BAD_DTYPE otherwise), every grad_dev
+ * aligned to it (AA_ERR_STRIDES).  out_dev: out_bytes >= the plan's (AA_ERR_WORKSPACE), aligned to out_dtype's element
+ * (AA_ERR_BAD_SHAPE); desc_dev (8-byte aligned) and workspace_dev (16-byte aligned, at least the plan's size) as aa_resample_many_u8;
+ * a block that is not this planner's AA_ERR_BAD_SHAPE.  Every check comes before the first launch; nothing is allocated, synchronised
+ * or read back, and no table cache is touched.  n == 0 launches nothing.  Added without an ABI version change (additive). */
+typedef struct aa_back_bwd_item {
+  const void *grad_dev;           /* the gradient's first element of class 0; NULL: this item has no gradient */
+  int64_t stride_ch, stride_row;  /* in ELEMENTS */
+  int64_t H, W;                   /* the item's canvas */
+  int64_t y0, x0, h, w;           /* the rectangle of it the forward read */
+  int64_t oh, ow;                 /* the gradient's size */
+  int32_t flags;                  /* 0 or AA_MANY_FLIP_X */
+  int32_t reserved;
+} aa_back_bwd_item;
+size_t aa_back_many_bwd_desc_bytes(int64_t n);
+int aa_back_many_bwd_plan(int filter, int out_layout, int64_t n, int64_t K, const aa_back_bwd_item *items, int out_dtype,
+                          int dense /* 0: items on 16-byte boundaries, 1: packed */, void *desc_host, size_t desc_bytes,
+                          size_t *workspace_bytes, size_t *out_bytes, int64_t *out_offsets /* n, bytes */);
+int aa_resample_back_many_bwd(const void *desc_host, const void *desc_dev, int grad_dtype, void *out_dev, size_t out_bytes,
+                              void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged Image.reduce: N uint8 images of N sizes, each with its own integer box and factors, into one arena ------------------------
  * Pillow's first step of Image.resize(reducing_gap=...) for a list: every large item is read ONCE by an integer box mean, and the ragged

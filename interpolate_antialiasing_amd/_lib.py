@@ -61,6 +61,7 @@ EXPORTS = (
     "aa_set_launch_shape", "aa_last_launch_shape",
     "aa_embed_many_desc_bytes", "aa_embed_many_plan", "aa_resample_embed_many", "aa_resample_embed_many_bwd",
     "aa_back_many_desc_bytes", "aa_back_many_plan", "aa_resample_back_many",
+    "aa_back_many_bwd_desc_bytes", "aa_back_many_bwd_plan", "aa_resample_back_many_bwd",
 )
 
 
@@ -240,6 +241,32 @@ class BackItem(ctypes.Structure):
                 ("scale_h", ctypes.c_float), ("scale_w", ctypes.c_float), ("flags", ctypes.c_int32), ("xtiles", ctypes.c_int32)]
 
 
+class BackBwdItemIn(ctypes.Structure):
+    """aa_back_bwd_item: one item of the ragged return path's backward (strides in ELEMENTS; grad_dev None: the item has no gradient)."""
+    _fields_ = [("grad_dev", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("H", ctypes.c_int64),
+                ("W", ctypes.c_int64), ("y0", ctypes.c_int64), ("x0", ctypes.c_int64), ("h", ctypes.c_int64), ("w", ctypes.c_int64),
+                ("oh", ctypes.c_int64), ("ow", ctypes.c_int64), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class BackBwdHeader(ctypes.Structure):
+    """Head of the block aa_back_many_bwd_plan writes (csrc/aa_many_back_bwd.h AABackBwdHeader; opaque to C callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("K", ctypes.c_int32), ("filter", ctypes.c_int32), ("out_layout", ctypes.c_int32),
+                ("out_dtype", ctypes.c_int32), ("dense", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("out_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64)]
+
+
+class BackBwdItem(ctypes.Structure):
+    """One item of that block (csrc/aa_many_back_bwd.h AABackBwdItem): the gradient and its element strides, the workspace offsets of its
+    two forward tables and their adjoints, its output offset in bytes, the canvas, the region, the gradient's size, the tables' row
+    lengths, the two float scales, flags and its column tiles."""
+    _fields_ = [("grad", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("tab_h", ctypes.c_int64),
+                ("tab_w", ctypes.c_int64), ("tr_h", ctypes.c_int64), ("tr_w", ctypes.c_int64), ("out_off", ctypes.c_int64),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("y0", ctypes.c_int32), ("x0", ctypes.c_int32), ("h", ctypes.c_int32),
+                ("w", ctypes.c_int32), ("oh", ctypes.c_int32), ("ow", ctypes.c_int32), ("ksize_h", ctypes.c_int32), ("ksize_w", ctypes.c_int32),
+                ("trk_h", ctypes.c_int32), ("trk_w", ctypes.c_int32), ("scale_h", ctypes.c_float), ("scale_w", ctypes.c_float),
+                ("flags", ctypes.c_int32), ("xtiles", ctypes.c_int32)]
+
+
 class LaunchShapeIn(ctypes.Structure):
     """aa_launch_shape_in: what a fused family's launch shape is chosen from (csrc/aa_launch_shape.h); occupancy[s] for s = 1..8 strips."""
     _fields_ = [("family", ctypes.c_int32), ("nstrips", ctypes.c_int32), ("strips_per_block", ctypes.c_int32), ("spb_forced", ctypes.c_int32),
@@ -270,6 +297,7 @@ YCC_SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "440": 3}  # aa_ycbcr_image.sub
 YCC_VROWS, YCC_VCOLS = 4, 256  # canvas rows and columns per work unit of the YCbCr call's vertical pass (csrc/aa_many_ycbcr.h)
 BACK_VALUES, BACK_ARGMAX, BACK_GREATER = 0, 1, 2  # aa_back_many_plan reduce (csrc/aa_many_back.h AA_BACK_*)
 BACK_TILE = 256     # output columns per work unit of the return path's resample (csrc/aa_many_back.h AA_BACK_TILE)
+BACK_BWD_ROWS, BACK_BWD_COLS = 4, 64  # canvas rows and columns per work unit of the return path's backward (csrc/aa_many_back_bwd.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
 
@@ -303,6 +331,10 @@ def embed_desc_view(buf, n: int):
 
 def back_desc_view(buf, n: int):
     return desc_view(buf, n, BackHeader, BackItem)
+
+
+def back_bwd_desc_view(buf, n: int):
+    return desc_view(buf, n, BackBwdHeader, BackBwdItem)
 
 
 def many_placed_view(buf, n: int):
@@ -467,6 +499,13 @@ def load() -> ctypes.CDLL:
     L.aa_back_many_plan.restype = i32
     L.aa_resample_back_many.argtypes = [vp, vp, i32, ctypes.c_float, vp, sz, vp, sz, vp]
     L.aa_resample_back_many.restype = i32
+    L.aa_back_many_bwd_desc_bytes.argtypes = [i64]
+    L.aa_back_many_bwd_desc_bytes.restype = sz
+    L.aa_back_many_bwd_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackBwdItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),
+                                        ctypes.POINTER(i64)]
+    L.aa_back_many_bwd_plan.restype = i32
+    L.aa_resample_back_many_bwd.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp]
+    L.aa_resample_back_many_bwd.restype = i32
     L.aa_set_fused.argtypes = [i32]
     L.aa_set_fused.restype = i32
     L.aa_set_store_form.argtypes = [i32]

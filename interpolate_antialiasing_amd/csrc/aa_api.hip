@@ -9,6 +9,7 @@
 #include "aa_box.h"
 #include "aa_embed_many.h"
 #include "aa_many_back.h"
+#include "aa_many_back_bwd.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_maps.h"
@@ -625,6 +626,20 @@ int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dt
                           void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_back_many(desc_host, desc_dev, in_dtype, threshold, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- ragged predictions back, backward -----------------------------------------------------------------------------------------------------
+size_t aa_back_many_bwd_desc_bytes(int64_t n) { return aa_back_bwd_desc_size(n); }
+
+int aa_back_many_bwd_plan(int filter, int out_layout, int64_t n, int64_t K, const aa_back_bwd_item *items, int out_dtype, int dense, void *desc_host,
+                          size_t desc_bytes, size_t *workspace_bytes, size_t *out_bytes, int64_t *out_offsets) {
+  return aa_back_bwd_plan_host(filter, out_layout, n, K, items, out_dtype, dense, desc_host, desc_bytes, workspace_bytes, out_bytes, out_offsets);
+}
+
+int aa_resample_back_many_bwd(const void *desc_host, const void *desc_dev, int grad_dtype, void *out_dev, size_t out_bytes, void *workspace_dev,
+                              size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_back_many_bwd(desc_host, desc_dev, grad_dtype, out_dev, out_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t aa_many_desc_bytes_ycbcr(int64_t n) { return aa_ycc_desc_size(n); }

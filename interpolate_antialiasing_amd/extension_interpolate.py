@@ -69,7 +69,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -1524,7 +1524,14 @@ def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips
     The tensors are contiguous views of ONE arena, each starting on a 16-byte boundary of it, as ``reduce_many`` returns its images.
     N == 0 gives [] (a list then states K with ``channels=``).  Two launches whatever N and whatever the sizes — one builds every item's two
     fp32 weight tables, one resamples and reduces — and one non-blocking copy of a packed descriptor; nothing is read back, no table cache
-    is touched, the call does not synchronise.  Not built: fractional regions, a dense padded output, a backward, softmax."""
+    is touched, the call does not synchronise.
+
+    Differentiable for ``reduce=None``: when gradients are enabled and ``pred`` (or any item of a list) requires grad, the results carry
+    a backward, ``resize_many_back_backward`` with ``dtype=pred``'s dtype and the layout class ``pred`` was read in: one gradient for a
+    batch tensor, one per list item, +0.0 outside the regions and for items the loss did not use (two launches for the whole list,
+    whatever the loss uses).  The values, the arena and the launch count are the same with and without it.  The results are views of
+    one arena and outputs of one autograd node: under autograd they must not be modified in place.  ``reduce="argmax"`` and
+    ``"greater"`` are not differentiable and never carry a ``grad_fn``.  Not built: fractional regions, a dense padded output, softmax."""
     name = "resize_many_back"
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
@@ -1552,6 +1559,20 @@ def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips
         return []
     for t in items:
         _require_gpu(t, name)
+    plan = (name, mode, n, k, sizes, rects, flips, reduce, reduce_id, out_dtype, out_id, threshold)
+    if reduce is None and torch.is_grad_enabled():
+        if isinstance(pred, torch.Tensor):
+            if pred.requires_grad:
+                return list(_ResizeManyBack.apply(plan, True, pred))
+        elif any(t.requires_grad for t in items):
+            return list(_ResizeManyBack.apply(plan, False, *items))
+    return _resize_many_back_run(plan, [t.detach() for t in items])[0]
+
+
+def _resize_many_back_run(plan, items):
+    """The layout class, the plan and the two launches of resize_many_back on checked GPU items -> (N views of one arena, whether the
+    items were read as interleaved classes)."""
+    name, mode, n, k, sizes, rects, flips, reduce, reduce_id, out_dtype, out_id, threshold = plan
     dev = items[0].device
     views = [t[:, y0:y0 + h, x0:x0 + w] for t, (y0, x0, h, w) in zip(items, rects)]
     classes, interleaved = _many_layout(views, k)
@@ -1585,6 +1606,184 @@ def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips
     for i, (oh, ow) in enumerate(sizes):
         shape = (oh, ow) if reduce == "argmax" else (k, oh, ow)
         outs.append(arena[offs[i] // es:offs[i] // es + math.prod(shape)].view(shape))
+    return outs, interleaved
+
+
+class _ResizeManyBack(torch.autograd.Function):
+    """resize_many_back(reduce=None) for predictions that require grad: the backward is resize_many_back_backward on the saved geometry,
+    in pred's dtype and in the layout class the forward read pred in.  One input (a batch tensor) or N (a list's items); N outputs,
+    views of one arena.  Outputs the loss did not use arrive as None and stay None items."""
+
+    @staticmethod
+    def forward(ctx, plan, is_batch, *inputs):
+        items = list(inputs[0].unbind(0)) if is_batch else [t[0] if t.dim() == 4 else t for t in inputs]
+        outs, interleaved = _resize_many_back_run(plan, items)
+        ctx.plan, ctx.is_batch, ctx.interleaved = plan, is_batch, interleaved
+        ctx.shapes, ctx.in_dtype, ctx.dev = [tuple(t.shape) for t in inputs], inputs[0].dtype, inputs[0].device
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        _, mode, n, k, _, rects, flips, *_ = ctx.plan
+        kw = dict(regions=rects, flips=flips, channels=k, dtype=ctx.in_dtype, out_format="nhwc" if ctx.interleaved else "nchw", device=ctx.dev)
+        if ctx.is_batch:
+            return None, None, resize_many_back_backward(grads, ctx.shapes[0][2:], mode, **kw)
+        gs = resize_many_back_backward(grads, [s[-2:] for s in ctx.shapes], mode, **kw)
+        return (None, None) + tuple(g.view(s) if ctx.needs_input_grad[2 + i] else None for i, (g, s) in enumerate(zip(gs, ctx.shapes)))
+
+
+def _back_canvas(name: str, canvas, n: int, k: int):
+    """canvas of resize_many_back_backward -> (whether it is ONE (H, W), [(H_i, W_i)] per item), checked."""
+    try:
+        canvas = list(canvas)
+    except TypeError:
+        raise ValueError(f"{name}(): canvas must be (H, W) or N pairs (H_i, W_i), got {canvas!r}") from None
+    one = len(canvas) == 2 and not any(isinstance(v, (tuple, list, torch.Size)) for v in canvas)
+    pairs = [canvas] if one else canvas
+    if not one and len(pairs) != n:
+        raise ValueError(f"{name}(): canvas must be (H, W) or hold one pair per item ({n}), got {len(pairs)}")
+    out = []
+    for i, c in enumerate(pairs):
+        hh, ww = _many_int_pair(name, "canvas", i, c)
+        if hh < 1 or ww < 1:
+            raise ValueError(f"{name}(): canvas[{i}] = ({hh}, {ww}) must be positive")
+        if hh > _MANY_MAX or ww > _MANY_MAX or hh * ww * k > _BACK_MAX_ELEMS:
+            raise ValueError(f"{name}(): canvas[{i}] = ({hh}, {ww}) with K = {k} is beyond the supported {_MANY_MAX} a side and "
+                             f"{_BACK_MAX_ELEMS} elements")
+        out.append((hh, ww))
+    return one, out * max(n, 1) if one else out
+
+
+class _CanvasShape:
+    """What _back_regions looks at of an item: its shape."""
+
+    def __init__(self, k, hh, ww):
+        self.shape = (k, hh, ww)
+
+
+def resize_many_back_backward(grads, canvas, mode: str = "bilinear", *, regions=None, flips=None, channels: Optional[int] = None, dtype=None,
+                              out_format: str = "nchw", device=None):
+    """The backward of ``resize_many_back(..., reduce=None)``: the gradients of the resampled items, each at its image's own size, back
+    to the canvas — for depth, mask and distillation losses taken at full resolution.  ``grads``: a sequence of N entries, each None
+    (autograd's "this output was not used") or a float32 / float16 / bfloat16 GPU tensor [K, oh_i, ow_i]; one dtype, one device and one
+    K for all tensors; the items' sizes are the tensors'.  A gradient with ``stride(2) == 1`` is read where it lies, at any plane
+    stride, row stride and element-aligned address (a crop of a larger tensor is not copied); any other is copied first.
+    ``canvas``: (H, W), the size of the batch the forward read — the result is ONE tensor [N, K, H, W], contiguous
+    (``out_format="nchw"``) or channels_last (``"nhwc"``), [0, K, H, W] for N == 0; or a list of N pairs (H_i, W_i), the sizes of a
+    list's items — the result is a list of N tensors [K, H_i, W_i], views of one arena, each starting on a 16-byte boundary of it, each
+    contiguous (``"nchw"``) or with interleaved classes, strides (1, W_i * K, K) (``"nhwc"``); [] for N == 0.
+    ``regions``, ``flips``, ``mode``: exactly what the forward was given (a region lies inside its item's canvas).  ``dtype``: None (the
+    gradients' dtype), float32, float16 or bfloat16.  If every entry of ``grads`` is None there is no tensor to take K, the dtype and the
+    device from: state them, ``channels=K, dtype=..., device=...`` (otherwise ``channels`` and ``device``, where given, must agree with
+    the tensors).
+
+    With ``U_i = G_i``, or ``G_i.flip(-1)`` for a flipped item, and ``B`` the ``<mode>_backward`` of this module in its gather form,
+    ``B_i = B(U_i.float()[None], [oh_i, ow_i], [1, K, h, w])[0]``, item i of the result is, bit for bit, ``B_i.to(dtype)`` at
+    ``[:, y0:y0 + h, x0:x0 + w]`` — fp32 arithmetic, the horizontal adjoint pass first, an fp32 intermediate, taps in ascending order,
+    product and sum rounded apart, ONE rounding to nearest even at the store — and literal +0.0 everywhere else; an item whose gradient is
+    None is all +0.0.  No atomics: the bits do not depend on N, on the launch shape or on the run.
+
+    Two launches whatever N and whatever the sizes — one builds every item's two fp32 weight tables and their adjoints, one gathers and
+    writes the WHOLE result, the zeros too (there is no memset) — and one non-blocking copy of a packed descriptor; nothing is read back,
+    no table cache is touched, the call does not synchronise.  Not built: fractional regions, an atomics form."""
+    name = "resize_many_back_backward"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if out_format not in ("nchw", "nhwc"):
+        raise ValueError(f"{name}(): out_format must be 'nchw' or 'nhwc', got {out_format!r}")
+    if isinstance(grads, torch.Tensor):
+        raise ValueError(f"{name}(): grads must be a sequence of N entries, each None or a tensor [K, oh, ow]")
+    try:
+        grads = list(grads)
+    except TypeError:
+        raise ValueError(f"{name}(): grads must be a sequence of N entries, each None or a tensor [K, oh, ow]") from None
+    n = len(grads)
+    live = [i for i, g in enumerate(grads) if g is not None]
+    for i in live:
+        g = grads[i]
+        if not isinstance(g, torch.Tensor):
+            raise TypeError(f"{name}(): grads[{i}] must be None or Tensor")
+        if g.dim() != 3:
+            raise ValueError(f"{name}(): grads[{i}] must be [K, oh, ow], got {list(g.shape)}")
+        if g.dtype not in _EMBED_DTYPES:
+            raise NotImplementedError(f"{name}(): grads[{i}] of {g.dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+    first = grads[live[0]] if live else None
+    if first is None and (channels is None or dtype is None or (device is None and n > 0)):
+        raise ValueError(f"{name}(): no entry of grads is a tensor: state channels=, dtype= and device= (an empty list: channels= and dtype=)")
+    k = int(channels) if channels is not None else int(first.shape[0])
+    if not (1 <= k <= _MANY_MAX):
+        raise ValueError(f"{name}(): K must be in 1 .. {_MANY_MAX}, got K = {k}")
+    dev = torch.device(device) if device is not None else (first.device if first is not None else _many_empty_device(None))
+    for i in live:
+        g = grads[i]
+        if g.dtype != first.dtype:
+            raise ValueError(f"{name}(): every gradient must have the same dtype: grads[{i}] is {g.dtype}, grads[{live[0]}] {first.dtype}")
+        if int(g.shape[0]) != k:
+            raise ValueError(f"{name}(): every gradient must have the same K: grads[{i}] has {int(g.shape[0])}, expected {k}")
+        if not (int(g.shape[1]) > 0 and int(g.shape[2]) > 0):
+            raise ValueError(f"{name}(): grads[{i}] is empty: {list(g.shape)}")
+        if g.device != dev:
+            raise ValueError(f"{name}(): every gradient must be on the same device: grads[{i}] is on {g.device}, expected {dev}")
+    dtype = first.dtype if dtype is None else dtype
+    if dtype not in _EMBED_DTYPES:
+        raise NotImplementedError(f"{name}(): dtype {dtype} is not built; torch.float32, torch.float16 or torch.bfloat16")
+    one, canvases = _back_canvas(name, canvas, n, k)
+    # (an item without a gradient has no size: any will do for the check, and the planner does not look at it)
+    sizes = _back_sizes(name, [(1, 1) if g is None else (int(g.shape[1]), int(g.shape[2])) for g in grads], n, k)
+    rects = _back_regions(name, regions, [_CanvasShape(k, hh, ww) for hh, ww in canvases[:n]])
+    flips = _many_flips(name, flips, n)
+    nhwc = out_format == "nhwc"
+    if n == 0:
+        if not one:
+            return []
+        hh, ww = canvases[0]
+        return torch.empty((0, k, hh, ww), dtype=dtype, device=dev, memory_format=torch.channels_last if nhwc else torch.contiguous_format)
+    if first is None and dev.type != "cuda":
+        raise _lib.AAInterpError(f"{name}: expected device= a ROCm GPU, got '{dev}'. interpolate_antialiasing_amd is the MI355X HIP path "
+                                 "only and has no CPU implementation.")
+    for i in live:
+        _require_gpu(grads[i], name)
+    L = _lib.load()
+    recs, keep = (_lib.BackBwdItemIn * n)(), []  # (keep: the copies of gradients whose columns are not consecutive, alive until the launches are enqueued)
+    for i, g in enumerate(grads):
+        r = recs[i]
+        r.H, r.W = canvases[i]
+        if g is None:
+            continue
+        g = g.detach()
+        if g.shape[2] > 1 and g.stride(2) != 1:
+            g = g.contiguous()
+            keep.append(g)
+        r.grad_dev = g.data_ptr()
+        r.stride_ch = g.stride(0) if k > 1 else 0
+        r.stride_row = g.stride(1) if g.shape[1] > 1 else 0
+        r.y0, r.x0, r.h, r.w = rects[i]
+        r.oh, r.ow = sizes[i]
+        r.flags = _lib.MANY_FLIP_X if flips is not None and flips[i] else 0
+    offs = (ctypes.c_int64 * n)()
+    out_bytes = ctypes.c_size_t(0)
+    es = torch.empty((), dtype=dtype).element_size()
+    grad_id = _DTYPE_IDS[first.dtype if first is not None else dtype]
+
+    def alloc_out():
+        if one:
+            return torch.empty((n, k) + canvases[0], dtype=dtype, device=dev, memory_format=torch.channels_last if nhwc else torch.contiguous_format)
+        return torch.empty((out_bytes.value // es,), dtype=dtype, device=dev)
+
+    out = _many_run(
+        name, dev, L.aa_back_many_bwd_desc_bytes(n),
+        lambda desc, nbytes, ws_bytes: L.aa_back_many_bwd_plan(_lib.FILTER_IDS[mode], _lib.NHWC if nhwc else _lib.NCHW, n, k, recs, _DTYPE_IDS[dtype],
+                                                               1 if one else 0, desc, nbytes, ws_bytes, ctypes.byref(out_bytes), offs),
+        alloc_out,
+        lambda desc_host, desc_dev, o, ws, stream: L.aa_resample_back_many_bwd(desc_host, desc_dev, grad_id, o.data_ptr(), o.numel() * es,
+                                                                               ws.data_ptr(), ws.numel(), stream))[0]
+    if one:
+        return out
+    outs = []
+    for i, (hh, ww) in enumerate(canvases):
+        flat = out[offs[i] // es:offs[i] // es + k * hh * ww]
+        outs.append(flat.view(hh, ww, k).permute(2, 0, 1) if nhwc else flat.view(k, hh, ww))
     return outs
 
 

@@ -99,6 +99,14 @@ Timing: device events around `--batches` batches that end in a synchronise; ever
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
 
+--logits-backward: the gradient's way — gradients [K, oh_i, ow_i] at the images' own sizes back to the canvas, bilinear, odd items
+flipped, float32 and bfloat16, resize_many_back_backward (two launches) against the loop a user writes today: linear_backward per item
+(its table cache warm), the gradient flipped where needed, copied into a zeroed canvas.  Two workloads: "small", N = 64, K = 21, image
+sides from 240 .. 640 (seed 7), a 128 x 128 letterbox canvas, where the loop is launch-bound and the call MUST be faster by more than
+the two spreads together; and "large", --logits' 16 camera-sized images from a 512 x 512 canvas at K = 1, 19 and 150 (a fifth of
+`--batches` a round; the K = 150 float32 gradients are 53 GB), whose figures are recorded without a requirement.  The two sides give
+the same bits.  The kernel's fetched bytes come from a counter run of its own: tools/pmc_any.sh TAG back_bwd:small:21:f32 back_bwd_gather.
+
   python tools/resize_many_bench.py                      # the timing table
   python tools/resize_many_bench.py --float-only         # only the (d) / (e) table
   python tools/resize_many_bench.py --placed > out.txt   # only the placed call against the per-image loop (below);
@@ -114,6 +122,8 @@ results into one tensor; (c) writes the batch.
   python tools/resize_many_bench.py --embed > out.txt    # only the position grid to the token grids (above); profiles/resize_embed_many.txt
   python tools/resize_many_bench.py --logits > out.txt   # only the way back: canvas logits to the images' own sizes, argmax (below);
                                                          # profiles/resize_many_back.txt
+  python tools/resize_many_bench.py --logits-backward > out.txt   # only the gradients' way back to the canvas (above);
+                                                         # profiles/resize_many_back_bwd.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
                                                          # kernel trace; every input reaches the GPU in ONE host-to-device copy)
   python tools/resize_many_bench.py --trace 20 --trace-float   # the same with resize_many_to_float calls
@@ -894,6 +904,87 @@ def logits(args, torch, aa, timed):
             del x
 
 
+def back_bwd_workload(which, torch, k, dtype):
+    """The two geometries of --logits-backward -> (canvas, regions, flips, gradients [K, oh_i, ow_i] on the GPU, their bytes): "large",
+    --logits' 16 camera-sized images from a 512 x 512 letterbox canvas; "small", 64 images with sides drawn from 240 .. 640 from a
+    128 x 128 letterbox canvas.  Odd items are flipped.  (tools/workload.py back_bwd:... runs the same for the counter passes.)"""
+    from interpolate_antialiasing_amd import boxmath
+
+    rng = np.random.default_rng(SEED)
+    if which == "large":
+        canvas = (512, 512)
+        shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:16]
+    else:
+        canvas = (128, 128)
+        shapes = [(int(rng.integers(240, 641)), int(rng.integers(240, 641))) for _ in range(64)]
+    regions = boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=canvas[0]), "center", canvas)
+    flips = [i % 2 == 1 for i in range(len(shapes))]
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    grads = [torch.randn((k, h, w), device="cuda", generator=gen).to(dtype) for h, w in shapes]
+    return canvas, regions, flips, grads, sum(g.numel() * g.element_size() for g in grads)
+
+
+def logits_backward(args, torch, aa, timed):
+    """resize_many_back_backward against the per-item loop a user writes today, on --logits' geometry and on many small items.  Per
+    contestant: kernel launches, ms per batch (median and minimum over the rounds), and the growth of torch.cuda.max_memory_allocated."""
+    print(f"resize_many_bench --logits-backward: gradients at the images' own sizes back to a letterbox canvas, bilinear, odd items flipped (seed {SEED}); "
+          f"library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds per contestant, alternating, every contestant warmed up first (the loop's table cache is warm); ms per batch: "
+          "median, minimum [min .. max]; peak: the growth of torch.cuda.max_memory_allocated over one call")
+    for which, ks, batches in (("small", (21,), args.batches), ("large", (1, 19, 150), max(2, args.batches // 5))):
+        for k in ks:
+            for dtype in (torch.float32, torch.bfloat16):
+                canvas, regions, flips, grads, gbytes = back_bwd_workload(which, torch, k, dtype)
+                n = len(grads)
+
+                def loop():
+                    out = torch.zeros((n, k) + canvas, dtype=dtype, device="cuda")
+                    for i, (y0, x0, h, w) in enumerate(regions):
+                        g = grads[i].flip(-1) if flips[i] else grads[i]
+                        out[i, :, y0:y0 + h, x0:x0 + w] = aa.linear_backward(g[None], list(g.shape[1:]), [1, k, h, w])[0]
+                    return out
+
+                def call():
+                    return aa.resize_many_back_backward(grads, canvas, regions=regions, flips=flips)
+
+                contestants = {"loop: linear_backward per item, flipped, into a zeroed canvas": loop, "call: resize_many_back_backward": call}
+                a, b = loop(), call()
+                same = a.dtype == b.dtype and torch.equal(a.view(torch.int32 if dtype == torch.float32 else torch.int16),
+                                                           b.view(torch.int32 if dtype == torch.float32 else torch.int16))
+                assert same, "resize_many_back_backward differs from the loop"
+                del a, b
+                for fn in contestants.values():
+                    fn()
+                torch.cuda.synchronize()
+                args_batches, args.batches = args.batches, batches
+                times = {key: [] for key in contestants}
+                for _ in range(args.rounds):
+                    for key, fn in contestants.items():
+                        times[key].append(timed(fn))
+                args.batches = args_batches
+                out_mb = n * k * canvas[0] * canvas[1] * grads[0].element_size() / 1e6
+                print(f"\n{which}: N = {n}, K = {k}, canvas {canvas[0]} x {canvas[1]}, {str(dtype).replace('torch.', '')}; gradients {gbytes / 1e6:.1f} MB, "
+                      f"result {out_mb:.1f} MB; {batches} batches a round; the same bits")
+                stat = {}
+                for key, v in times.items():
+                    stat[key] = (statistics.median(v), min(v), max(v))
+                    launches = count_launches(torch, contestants[key])
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    before = torch.cuda.max_memory_allocated()
+                    r = contestants[key]()
+                    torch.cuda.synchronize()
+                    peak = torch.cuda.max_memory_allocated() - before
+                    del r
+                    print(f"  {key:66s} median {stat[key][0]:9.3f}  min {stat[key][1]:9.3f} [{stat[key][1]:9.3f} .. {stat[key][2]:9.3f}]   launches "
+                          f"{launches if launches is not None else 'not measured'}   peak {peak / 1e6:10.1f} MB")
+                (ml, ll, hl), (mc, lc, hc) = stat.values()
+                verdict = "the one call is faster" if ml - mc > (hl - ll) + (hc - lc) else "THE ONE CALL IS NOT FASTER by more than the spreads"
+                print(f"  call against loop: {ml / mc:.2f} x; median gain {ml - mc:.3f} ms, the two spreads together {(hl - ll) + (hc - lc):.3f} ms: {verdict}"
+                      + ("" if which == "small" else "  (recorded, not a requirement)"))
+                del grads
+
+
 def _lib_path():
     from interpolate_antialiasing_amd import _lib
 
@@ -920,6 +1011,8 @@ def main():
                     "with --trace K: K calls of each for a kernel trace")
     ap.add_argument("--logits", action="store_true", help="only resize_many_back: canvas logits back to the images' sizes and argmax, against the "
                     "per-item loop of existing calls and against reduce=None followed by argmax")
+    ap.add_argument("--logits-backward", action="store_true", help="only resize_many_back_backward: gradients at the images' sizes back to the "
+                    "canvas, against the per-item loop of linear_backward into a zeroed canvas; --logits' geometry and 64 small items")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -1026,6 +1119,9 @@ def main():
         return
     if args.logits:
         logits(args, torch, aa, timed)
+        return
+    if args.logits_backward:
+        logits_backward(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")

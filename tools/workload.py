@@ -67,6 +67,13 @@ elif name.startswith("bwdw:"):  # bwdw:<W> : the backward of config A with W inp
     wcols = int(name.split(":")[1])
     x = torch.randn(256, 3, 196, 320, device=dev)
     fn = lambda: aa.linear_backward(x, [196, 320], [256, 3, 438, wcols])
+elif name.startswith("back_bwd:"):  # back_bwd:<small|large>:<K>:<f32|bf16> : resize_many_back_backward on resize_many_bench's geometry
+    import resize_many_bench
+
+    _, which, k, dt = name.split(":")
+    canvas, regions, flips, grads, gbytes = resize_many_bench.back_bwd_workload(which, torch, int(k), torch.float32 if dt == "f32" else torch.bfloat16)
+    print(f"{name}: gradients {gbytes} bytes, result {len(grads) * int(k) * canvas[0] * canvas[1] * grads[0].element_size()} bytes", flush=True)
+    fn = lambda: aa.resize_many_back_backward(grads, canvas, regions=regions, flips=flips)
 elif name.startswith("planar:"):  # planar:<H>:<W>:<oH>:<oW>:<linear|cubic>:<B>:<plane groups 0|1>   (uint8 NCHW, Pillow arithmetic)
     _, h, w, oh, ow, filt, b, grp = name.split(":")
     _lib.set_plane_groups(int(grp))
