@@ -30,7 +30,8 @@ extern "C" {
                                    v2 entry point unchanged.  Added since without a version change (additive; a caller looks the
                                    symbol up): aa_back_many_desc_bytes, aa_back_many_plan, aa_resample_back_many, with aa_back_item
                                    and the aa_dtype values AA_I16 .. AA_BOOL that only they take; aa_back_many_bwd_desc_bytes,
-                                   aa_back_many_bwd_plan, aa_resample_back_many_bwd, with aa_back_bwd_item */
+                                   aa_back_many_bwd_plan, aa_resample_back_many_bwd, with aa_back_bwd_item; aa_back_merged_desc_bytes,
+                                   aa_back_merged_plan, aa_resample_back_merged */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -643,6 +644,40 @@ int aa_back_many_plan(int filter, int layout, int64_t n, int64_t K, const aa_bac
                       int64_t *out_offsets /* n, bytes */);
 int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
                           void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back, merged: the n items are members of G groups, summed per group before the reduction over K --------------
+ * Test-time augmentation: a model answers every image several times, at several scales and mirrored, and the passes are resampled to
+ * the image's size, un-mirrored and SUMMED before the label is taken.  Here item i is a member of group group_of[i] in 0 .. G - 1 (any
+ * order; every group has at least one member, and its members all have the group's oh, ow), and a group is one output.  With R_i the
+ * fp32 value aa_back_many_plan's section defines for item i — mirrored left to right for AA_MANY_FLIP_X, before any rounding to
+ * out_dtype — and i_0 < i_1 < ... < i_{M-1} the members of group g in ascending item index,
+ *   S_g = R_{i_0}, then S_g = S_g + R_{i_j} for j = 1 .. M - 1: one fp32 round-to-nearest add per element, in that order, never fused
+ *   and never reassociated; merge 1 (mean) then divides, S_g / (float)M, correctly rounded (merge 0, sum, does not);
+ * and group g of the arena is reduce 0, 1 or 2 of S_g exactly as that section states them for R_i, at byte out_offsets[g].  So a NaN in
+ * any member is a NaN in the sum, +inf and -inf in two members give NaN, and a group of one member is aa_resample_back_many's item.
+ * aa_back_merged_plan is host arithmetic only.  Its block — header, the n item records of aa_back_many_plan (oh, ow and arena offset
+ * their group's), G group records (first member slot, member count, oh, ow, column tiles, arena offset), the int32 list of the n item
+ * indices grouped by group and ascending within a group, then the int64 running count of work units per GROUP (an output row times 256
+ * columns) — goes into desc_host, desc_bytes >= aa_back_merged_desc_bytes(n, G); the workspace is aa_back_many_plan's for the same
+ * items.  Errors, in aa_back_many_plan's order with these added: AA_ERR_BAD_SHAPE beside n, K and reduce for G outside 0 .. n, G == 0
+ * with n > 0 or an unknown merge; group_of beside the pointers (AA_ERR_NULL, n > 0); after the short block AA_ERR_BAD_SHAPE for a
+ * group_of entry outside 0 .. G - 1, then for an empty group; per item, after its own checks, AA_ERR_BAD_SHAPE for an (oh, ow) that is
+ * not that of its group's first member; then per group AA_ERR_BAD_SHAPE for an arena beyond 2^43 bytes or more work units than one grid
+ * holds; last AA_ERR_BAD_DTYPE.
+ * aa_resample_back_merged enqueues TWO launches whatever n, G and the sizes: aa_resample_back_many's table kernel over the members, and
+ * a resample with one workgroup per work unit of a group and a lane per output column: for AA_BACK_UNROLL classes at a time the lane
+ * walks the group's members in order, each one's vertical sum of horizontal sums added to the group's in registers, and hands the
+ * complete sums to the reduction.  A mirrored member is mirrored where it is read.  Neither a member's values nor, for reduce 1, the K
+ * sums are ever stored.  Parameters, checks and their order as aa_resample_back_many; every check comes before the first launch;
+ * nothing is allocated, synchronised or read back, and no table cache is touched.  n == 0 launches nothing.  Not built: softmax before
+ * the sum, per-member weights, a maximum instead of the sum, members placed at different positions of the output.  Added without an
+ * ABI version change (additive). */
+size_t aa_back_merged_desc_bytes(int64_t n, int64_t g);
+int aa_back_merged_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of /* n */,
+                        int merge /* 0 sum, 1 mean */, int reduce /* 0 values, 1 argmax, 2 greater */, int out_dtype, void *desc_host,
+                        size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets /* G, bytes */);
+int aa_resample_back_merged(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
+                            void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged predictions back, backward: N gradients [K, oh_i, ow_i] to N canvases [K, H_i, W_i] ---------------------------------------
  * The backward of aa_resample_back_many's reduce 0, for losses taken at every image's own size.  Item i has a canvas [H_i, W_i], the

@@ -62,6 +62,7 @@ EXPORTS = (
     "aa_embed_many_desc_bytes", "aa_embed_many_plan", "aa_resample_embed_many", "aa_resample_embed_many_bwd",
     "aa_back_many_desc_bytes", "aa_back_many_plan", "aa_resample_back_many",
     "aa_back_many_bwd_desc_bytes", "aa_back_many_bwd_plan", "aa_resample_back_many_bwd",
+    "aa_back_merged_desc_bytes", "aa_back_merged_plan", "aa_resample_back_merged",
 )
 
 
@@ -241,6 +242,20 @@ class BackItem(ctypes.Structure):
                 ("scale_h", ctypes.c_float), ("scale_w", ctypes.c_float), ("flags", ctypes.c_int32), ("xtiles", ctypes.c_int32)]
 
 
+class BackMergedHeader(ctypes.Structure):
+    """Head of the block aa_back_merged_plan writes (csrc/aa_many_back.h AABackMergedHeader; opaque to C callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("K", ctypes.c_int32), ("filter", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("reduce", ctypes.c_int32), ("out_dtype", ctypes.c_int32), ("merge", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("G", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class BackGroup(ctypes.Structure):
+    """One group of that block (csrc/aa_many_back.h AABackGroup): its arena offset in bytes, its first slot of the member list, its
+    members, its size and its column tiles."""
+    _fields_ = [("out_off", ctypes.c_int64), ("first", ctypes.c_int32), ("count", ctypes.c_int32), ("oh", ctypes.c_int32), ("ow", ctypes.c_int32),
+                ("xtiles", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class BackBwdItemIn(ctypes.Structure):
     """aa_back_bwd_item: one item of the ragged return path's backward (strides in ELEMENTS; grad_dev None: the item has no gradient)."""
     _fields_ = [("grad_dev", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("H", ctypes.c_int64),
@@ -296,6 +311,7 @@ MAPS_VCOLS = 256    # canvas columns per work unit of the maps call's vertical p
 YCC_SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "440": 3}  # aa_ycbcr_image.subsampling (AA_YCC_*)
 YCC_VROWS, YCC_VCOLS = 4, 256  # canvas rows and columns per work unit of the YCbCr call's vertical pass (csrc/aa_many_ycbcr.h)
 BACK_VALUES, BACK_ARGMAX, BACK_GREATER = 0, 1, 2  # aa_back_many_plan reduce (csrc/aa_many_back.h AA_BACK_*)
+BACK_MERGE = {"sum": 0, "mean": 1}  # aa_back_merged_plan merge (csrc/aa_many_back.h AA_BACK_MERGE_*)
 BACK_TILE = 256     # output columns per work unit of the return path's resample (csrc/aa_many_back.h AA_BACK_TILE)
 BACK_BWD_ROWS, BACK_BWD_COLS = 4, 64  # canvas rows and columns per work unit of the return path's backward (csrc/aa_many_back_bwd.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
@@ -331,6 +347,20 @@ def embed_desc_view(buf, n: int):
 
 def back_desc_view(buf, n: int):
     return desc_view(buf, n, BackHeader, BackItem)
+
+
+def back_merged_desc_view(buf, n: int, g: int):
+    """(header, items, groups, members, unit0) of aa_back_merged_plan's block held in a ctypes buffer:
+    [BackMergedHeader][n BackItems][g BackGroups][int32 member[n], padded to 8 bytes][int64 unit0[g + 1]]."""
+    hd = BackMergedHeader.from_buffer(buf, 0)
+    at = ctypes.sizeof(BackMergedHeader)
+    items = (BackItem * n).from_buffer(buf, at)
+    at += n * ctypes.sizeof(BackItem)
+    groups = (BackGroup * g).from_buffer(buf, at)
+    at += g * ctypes.sizeof(BackGroup)
+    members = (ctypes.c_int32 * n).from_buffer(buf, at)
+    at += (4 * n + 7) & ~7
+    return hd, items, groups, members, (ctypes.c_int64 * (g + 1)).from_buffer(buf, at)
 
 
 def back_bwd_desc_view(buf, n: int):
@@ -499,6 +529,13 @@ def load() -> ctypes.CDLL:
     L.aa_back_many_plan.restype = i32
     L.aa_resample_back_many.argtypes = [vp, vp, i32, ctypes.c_float, vp, sz, vp, sz, vp]
     L.aa_resample_back_many.restype = i32
+    L.aa_back_merged_desc_bytes.argtypes = [i64, i64]
+    L.aa_back_merged_desc_bytes.restype = sz
+    L.aa_back_merged_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), i64, ctypes.POINTER(i64), i32, i32, i32, vp, sz,
+                                      ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_back_merged_plan.restype = i32
+    L.aa_resample_back_merged.argtypes = [vp, vp, i32, ctypes.c_float, vp, sz, vp, sz, vp]
+    L.aa_resample_back_merged.restype = i32
     L.aa_back_many_bwd_desc_bytes.argtypes = [i64]
     L.aa_back_many_bwd_desc_bytes.restype = sz
     L.aa_back_many_bwd_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackBwdItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),

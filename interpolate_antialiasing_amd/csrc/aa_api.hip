@@ -628,6 +628,22 @@ int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dt
   return aa_launch_back_many(desc_host, desc_dev, in_dtype, threshold, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
+// ---- ragged predictions back, merged: the members of a group summed before the reduction ------------------------------------------------
+size_t aa_back_merged_desc_bytes(int64_t n, int64_t g) { return aa_back_merged_desc_size(n, g); }
+
+int aa_back_merged_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of, int merge,
+                        int reduce, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
+                        int64_t *out_offsets) {
+  return aa_back_merged_plan_host(filter, layout, n, K, items, G, group_of, merge, reduce, out_dtype, desc_host, desc_bytes, workspace_bytes,
+                                  arena_bytes, out_offsets);
+}
+
+int aa_resample_back_merged(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
+                            void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_back_merged(desc_host, desc_dev, in_dtype, threshold, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
 // ---- ragged predictions back, backward -----------------------------------------------------------------------------------------------------
 size_t aa_back_many_bwd_desc_bytes(int64_t n) { return aa_back_bwd_desc_size(n); }
 

@@ -44,6 +44,45 @@ struct AABackItem {
 };
 static_assert(sizeof(AABackItem) == 96, "descriptor item is 96 bytes");
 
+// ---- merged (aa_back_merged_plan): the n items are MEMBERS of G groups, a group one output: its members, each resampled to the group's
+// [oh, ow], are summed in fp32 in ascending item order (and divided by their count for the mean) before the reduction over K.  The block:
+//   [ AABackMergedHeader : 64 B ][ AABackItem x n ][ AABackGroup x G ][ int32 member[n], padded to 8 B ][ int64 unit0[G + 1] ]
+// A member is an ordinary AABackItem whose oh, ow and out_off are its group's, so back_tables builds its tables unchanged.  member[] is
+// the item indices grouped by group, ascending within a group; group g's are member[first .. first + count).  unit0[g] is the first work
+// unit of group g; a unit is one output row of a GROUP times AA_BACK_TILE consecutive output columns.
+#define AA_BACK_MERGED_MAGIC 0x4B43424D  // 'MBCK'
+enum { AA_BACK_MERGE_SUM = 0, AA_BACK_MERGE_MEAN = 1 };
+
+struct AABackMergedHeader {
+  int32_t magic, n, K, filter, layout;
+  int32_t reduce;     // AA_BACK_*
+  int32_t out_dtype;  // aa_dtype of an arena element
+  int32_t merge;      // AA_BACK_MERGE_*
+  int64_t units;      // unit0[G]: the workgroups of the resample
+  int64_t ws_bytes;   // the table arena: per member its H table, then its W table (aa_back_many_plan's for the same items)
+  int64_t arena_bytes;
+  int32_t G;
+  int32_t reserved;
+};
+static_assert(sizeof(AABackMergedHeader) == 64, "descriptor header is 64 bytes");
+
+struct AABackGroup {
+  int64_t out_off;  // bytes from the arena's start, a multiple of 16
+  int32_t first;    // the group's first slot of member[]
+  int32_t count;    // its members, at least 1
+  int32_t oh, ow;
+  int32_t xtiles;   // ceil(ow / AA_BACK_TILE)
+  int32_t reserved;
+};
+static_assert(sizeof(AABackGroup) == 32, "descriptor group is 32 bytes");
+
+size_t aa_back_merged_desc_size(int64_t n, int64_t g);
+int aa_back_merged_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of, int merge,
+                             int reduce, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
+                             int64_t *out_offsets);
+int aa_launch_back_merged(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
+                          void *workspace_dev, size_t workspace_bytes, hipStream_t stream);
+
 size_t aa_back_desc_size(int64_t n);
 int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce, int out_dtype, void *desc_host,
                       size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets);

@@ -16,6 +16,9 @@
 // K apart), the same code with the strides as arguments; interleaved sources whose K and addresses allow it load AA_BACK_UNROLL classes
 // as one vector.  Every element offset is 64-bit.  Stores are one element a lane, consecutive along the wave, so an arena on any
 // element boundary is served and the 16-byte gaps between items are never written.
+// The merged call (aa_back_merged_plan) runs the same two launches with back_resample_merged in place of back_resample: the items are
+// members of groups, a work unit is an output row of a GROUP, and a class's value is the members' values added in order before the
+// epilogue sees it (at "2'." below).
 // Shared with the other ragged calls: aa_many_dev.h (the item of a unit, the element types), aa_many_host.h (the block, the launch checks).
 
 #include <string.h>
@@ -172,10 +175,80 @@ __global__ void __launch_bounds__(AA_BACK_TILE) back_resample(BackArgs a) {
   epi.done();
 }
 
+// ---- 2'. the merged resample ---------------------------------------------------------------------------------------------------------------
+// A work unit is an output row of a GROUP times AA_BACK_TILE columns.  The class chunk is the outer loop and the group's members the
+// inner one, so the epilogue sees a class's complete sum: the first member's value, then one fp32 add per further member, in ascending
+// item order (member[] is in that order), then for the mean one correctly rounded division by the count.  A flipped member is mirrored
+// where it is READ: lane x walks that member's horizontal window of column ow - 1 - x, and the store is never mirrored.  A member's two
+// table rows are looked up again per class chunk (a few cached words; the member index is uniform over the workgroup) rather than
+// kept per member, so there is no limit on the members of a group and nothing is indexed dynamically in registers.
+struct MergedArgs {
+  const AABackItem *items;
+  const AABackGroup *groups;
+  const int32_t *member;
+  const int64_t *unit0;
+  const char *ws;
+  char *arena;
+  float threshold;
+  int G, K, mean;
+};
+
+// sum = the merged value of V classes from class k on of the lane's pixel (y, x) of group gr.
+template <typename TIn, int V, bool VEC>
+__device__ inline void member_sums(const MergedArgs &a, const AABackGroup &gr, int y, int x, int k, float (&sum)[V]) {
+  const int32_t *member = a.member + gr.first;
+  for (int m = 0; m < gr.count; m++) {
+    const AABackItem &it = a.items[member[m]];
+    const int xr = (it.flags & AA_MANY_FLIP_X) ? gr.ow - 1 - x : x;
+    const Row ry = table_row(a.ws + it.tab_h, it.h, gr.oh, it.ksize_h, y), rx = table_row(a.ws + it.tab_w, it.w, gr.ow, it.ksize_w, xr);
+    const int64_t sch = it.stride_ch, prow = it.stride_row, ppx = it.stride_px;
+    float acc[V];
+    class_sums<TIn, V, VEC>((const TIn *)it.src + ry.x0 * prow + rx.x0 * ppx + k * sch, sch, prow, ppx, ry, rx, acc);
+#pragma unroll
+    for (int c = 0; c < V; c++) sum[c] = m == 0 ? acc[c] : sum[c] + acc[c];
+  }
+  if (a.mean) {
+    const float count = (float)gr.count;
+#pragma unroll
+    for (int c = 0; c < V; c++) sum[c] = sum[c] / count;
+  }
+}
+
+template <typename TIn, bool VEC, typename Epi>
+__global__ void __launch_bounds__(AA_BACK_TILE) back_resample_merged(MergedArgs a) {
+  constexpr int U = AA_BACK_UNROLL;
+  const int64_t unit = blockIdx.x;
+  const int g = aa_unit_item(a.unit0, a.G, unit);
+  const AABackGroup &gr = a.groups[g];
+  const int64_t u = unit - a.unit0[g];
+  const int y = (int)(u / gr.xtiles);
+  const int x = (int)(u - (int64_t)y * gr.xtiles) * AA_BACK_TILE + (int)threadIdx.x;
+  if (x >= gr.ow) return;  // (no barrier below)
+  Epi epi(a.arena + gr.out_off, (int64_t)y * gr.ow + x, (int64_t)gr.oh * gr.ow, a.threshold);
+  int k = 0;
+  for (; k + U <= a.K; k += U) {
+    float sum[U];
+    member_sums<TIn, U, VEC>(a, gr, y, x, k, sum);
+#pragma unroll
+    for (int c = 0; c < U; c++) epi.put(k + c, sum[c]);
+  }
+  for (; k < a.K; k++) {
+    float sum[1];
+    member_sums<TIn, 1, false>(a, gr, y, x, k, sum);
+    epi.put(k, sum[0]);
+  }
+  epi.done();
+}
+
+// The kernel of an argument block: back_resample for the items of aa_back_many_plan, back_resample_merged for the groups of
+// aa_back_merged_plan; the same epilogues and element types for both.
 template <typename TIn, bool VEC, typename Epi> void launch_as(const BackArgs &a, unsigned units, hipStream_t stream) {
   hipLaunchKernelGGL((back_resample<TIn, VEC, Epi>), dim3(units), dim3(AA_BACK_TILE), 0, stream, a);
 }
-template <typename TIn, bool VEC> void launch_epi(int reduce, int out_dtype, const BackArgs &a, unsigned units, hipStream_t stream) {
+template <typename TIn, bool VEC, typename Epi> void launch_as(const MergedArgs &a, unsigned units, hipStream_t stream) {
+  hipLaunchKernelGGL((back_resample_merged<TIn, VEC, Epi>), dim3(units), dim3(AA_BACK_TILE), 0, stream, a);
+}
+template <typename TIn, bool VEC, typename Args> void launch_epi(int reduce, int out_dtype, const Args &a, unsigned units, hipStream_t stream) {
   if (reduce == AA_BACK_GREATER) launch_as<TIn, VEC, Greater>(a, units, stream);
   else if (reduce == AA_BACK_ARGMAX) {
     if (out_dtype == AA_U8) launch_as<TIn, VEC, Argmax<uint8_t>>(a, units, stream);
@@ -186,7 +259,7 @@ template <typename TIn, bool VEC> void launch_epi(int reduce, int out_dtype, con
   else if (out_dtype == AA_F16) launch_as<TIn, VEC, Values<f16_t>>(a, units, stream);
   else launch_as<TIn, VEC, Values<bf16_t>>(a, units, stream);
 }
-template <bool VEC> void launch_in(int in_dtype, int reduce, int out_dtype, const BackArgs &a, unsigned units, hipStream_t stream) {
+template <bool VEC, typename Args> void launch_in(int in_dtype, int reduce, int out_dtype, const Args &a, unsigned units, hipStream_t stream) {
   if (in_dtype == AA_F32) launch_epi<float, VEC>(reduce, out_dtype, a, units, stream);
   else if (in_dtype == AA_F16) launch_epi<f16_t, VEC>(reduce, out_dtype, a, units, stream);
   else launch_epi<bf16_t, VEC>(reduce, out_dtype, a, units, stream);
@@ -208,6 +281,72 @@ inline bool out_dtype_ok(int reduce, int dt) {
   return dt == AA_BOOL || dt == AA_U8;
 }
 
+// What both planners check first, in this order: the filter; the layout; n, K and reduce (own_ok: what the caller adds to them); a label
+// type that cannot hold K - 1.
+inline int plan_prologue(int filter, int layout, int64_t n, int64_t K, int reduce, int out_dtype, bool own_ok) {
+  if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
+  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
+  if (n < 0 || n > kAAManyMax || K < 1 || K > kAAManyMax || reduce < AA_BACK_VALUES || reduce > AA_BACK_GREATER || !own_ok) return AA_ERR_BAD_SHAPE;
+  if (reduce == AA_BACK_ARGMAX && ((out_dtype == AA_U8 && K > 256) || (out_dtype == AA_I16 && K > 32768))) return AA_ERR_BAD_SHAPE;
+  return AA_OK;
+}
+
+// One aa_back_item checked and written as its record, its two tables appended to the table arena at ws: everything of an item but its
+// place in the arena and among the work units, which are the planner's (an item's own, or its group's).
+inline int plan_item(int filter, int layout, int64_t K, const aa_back_item &im, AABackItem &it, size_t &ws) {
+  if (!im.data_dev) return AA_ERR_NULL;
+  if (im.h <= 0 || im.w <= 0 || im.h > kAAManyMax || im.w > kAAManyMax || im.oh <= 0 || im.ow <= 0 || im.oh > kAAManyMax || im.ow > kAAManyMax ||
+      (im.flags & ~AA_MANY_FLIP_X))
+    return AA_ERR_BAD_SHAPE;
+  if (im.oh * im.ow > AA_BACK_MAX_ELEMS / K) return AA_ERR_BAD_SHAPE;
+  // (the stride of an axis of one element never matters)
+  if ((K > 1 && im.stride_ch < 0) || (im.h > 1 && im.stride_row < 0) || (im.w > 1 && im.stride_px < 0)) return AA_ERR_STRIDES;
+  if (layout == AA_NHWC ? ((K > 1 && im.stride_ch != 1) || (im.w > 1 && im.stride_px != K)) : (im.w > 1 && im.stride_px != 1)) return AA_ERR_STRIDES;
+  memset(&it, 0, sizeof(it));
+  it.src = im.data_dev;
+  it.stride_ch = K > 1 ? im.stride_ch : 0;
+  it.stride_row = im.h > 1 ? im.stride_row : 0;
+  it.stride_px = im.w > 1 ? im.stride_px : 0;
+  it.h = (int32_t)im.h; it.w = (int32_t)im.w; it.oh = (int32_t)im.oh; it.ow = (int32_t)im.ow;
+  const int kh = aa_table_ksize(filter, AA_TABLE_F32, im.h, im.oh, 0, 0.0), kw = aa_table_ksize(filter, AA_TABLE_F32, im.w, im.ow, 0, 0.0);
+  if (kh < 0) return kh;
+  if (kw < 0) return kw;
+  it.ksize_h = kh; it.ksize_w = kw;
+  it.scale_h = (float)im.h / (float)im.oh;
+  it.scale_w = (float)im.w / (float)im.ow;
+  it.tab_h = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.oh, kh);
+  it.tab_w = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.ow, kw);
+  it.flags = im.flags;
+  it.xtiles = (int32_t)((im.ow + AA_BACK_TILE - 1) / AA_BACK_TILE);
+  return AA_OK;
+}
+
+// An output [K or 1, oh, ow] appended to the arena on a 16-byte boundary, its rows of tiles to the work units; -> its offset in *off.
+inline int plan_output(int64_t K, int reduce, size_t eb, int64_t oh, int64_t ow, int64_t xtiles, size_t &arena, int64_t &units, int64_t *off) {
+  arena = aa_align16(arena);
+  *off = (int64_t)arena;
+  arena += (size_t)(reduce == AA_BACK_ARGMAX ? 1 : K) * (size_t)oh * (size_t)ow * eb;
+  if (arena > (size_t)AA_BACK_MAX_ELEMS * 8) return AA_ERR_BAD_SHAPE;
+  units += oh * xtiles;
+  if (units > INT32_MAX) return AA_ERR_BAD_SHAPE;  // (one grid)
+  return AA_OK;
+}
+
+// What both launches check of the planned items' pointers, which the planner could not: against the element of in_dtype, and for
+// whether every address of an interleaved list allows the vector loads (*vec).
+inline int check_sources(const AABackItem *host_items, int64_t n, int in_dtype, int layout, int K, bool *vec) {
+  const size_t ei = elem_bytes(in_dtype);
+  *vec = layout == AA_NHWC && K % AA_BACK_UNROLL == 0;
+  for (int64_t i = 0; i < n; i++) {
+    const AABackItem &it = host_items[i];
+    if ((uintptr_t)it.src % ei) return AA_ERR_STRIDES;
+    *vec = *vec && (uintptr_t)it.src % (AA_BACK_UNROLL * ei) == 0 && it.stride_row % AA_BACK_UNROLL == 0;  // (stride_px is K or unused)
+  }
+  return AA_OK;
+}
+
+inline size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
+
 }  // namespace
 
 // ---- host: the planner -------------------------------------------------------------------------------------------------------------------
@@ -215,11 +354,8 @@ size_t aa_back_desc_size(int64_t n) { return aa_desc_size(sizeof(AABackHeader), 
 
 int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *in, int reduce, int out_dtype, void *desc_host,
                       size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
-  if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
-  if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
-  if (n < 0 || n > kAAManyMax || K < 1 || K > kAAManyMax || reduce < AA_BACK_VALUES || reduce > AA_BACK_GREATER) return AA_ERR_BAD_SHAPE;
-  // (a label type that cannot hold K - 1)
-  if (reduce == AA_BACK_ARGMAX && ((out_dtype == AA_U8 && K > 256) || (out_dtype == AA_I16 && K > 32768))) return AA_ERR_BAD_SHAPE;
+  int rc = plan_prologue(filter, layout, n, K, reduce, out_dtype, true);
+  if (rc != AA_OK) return rc;
   if (!desc_host || !workspace_bytes || !arena_bytes || (n > 0 && (!in || !out_offsets))) return AA_ERR_NULL;
   if (desc_bytes < aa_back_desc_size(n)) return AA_ERR_WORKSPACE;
   const size_t eb = elem_bytes(out_dtype);
@@ -229,40 +365,11 @@ int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_bac
   size_t ws = 0, arena = 0;
   int64_t units = 0;
   for (int64_t i = 0; i < n; i++) {
-    const aa_back_item &im = in[i];
-    if (!im.data_dev) return AA_ERR_NULL;
-    if (im.h <= 0 || im.w <= 0 || im.h > kAAManyMax || im.w > kAAManyMax || im.oh <= 0 || im.ow <= 0 || im.oh > kAAManyMax || im.ow > kAAManyMax ||
-        (im.flags & ~AA_MANY_FLIP_X))
-      return AA_ERR_BAD_SHAPE;
-    if (im.oh * im.ow > AA_BACK_MAX_ELEMS / K) return AA_ERR_BAD_SHAPE;
-    // (the stride of an axis of one element never matters)
-    if ((K > 1 && im.stride_ch < 0) || (im.h > 1 && im.stride_row < 0) || (im.w > 1 && im.stride_px < 0)) return AA_ERR_STRIDES;
-    if (layout == AA_NHWC ? ((K > 1 && im.stride_ch != 1) || (im.w > 1 && im.stride_px != K)) : (im.w > 1 && im.stride_px != 1)) return AA_ERR_STRIDES;
     AABackItem it;
-    memset(&it, 0, sizeof(it));
-    it.src = im.data_dev;
-    it.stride_ch = K > 1 ? im.stride_ch : 0;
-    it.stride_row = im.h > 1 ? im.stride_row : 0;
-    it.stride_px = im.w > 1 ? im.stride_px : 0;
-    it.h = (int32_t)im.h; it.w = (int32_t)im.w; it.oh = (int32_t)im.oh; it.ow = (int32_t)im.ow;
-    const int kh = aa_table_ksize(filter, AA_TABLE_F32, im.h, im.oh, 0, 0.0), kw = aa_table_ksize(filter, AA_TABLE_F32, im.w, im.ow, 0, 0.0);
-    if (kh < 0) return kh;
-    if (kw < 0) return kw;
-    it.ksize_h = kh; it.ksize_w = kw;
-    it.scale_h = (float)im.h / (float)im.oh;
-    it.scale_w = (float)im.w / (float)im.ow;
-    it.tab_h = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.oh, kh);
-    it.tab_w = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.ow, kw);
-    it.flags = im.flags;
-    it.xtiles = (int32_t)((im.ow + AA_BACK_TILE - 1) / AA_BACK_TILE);
-    arena = aa_align16(arena);
-    it.out_off = (int64_t)arena;
-    out_offsets[i] = (int64_t)arena;
-    arena += (size_t)(reduce == AA_BACK_ARGMAX ? 1 : K) * (size_t)im.oh * (size_t)im.ow * eb;
-    if (arena > (size_t)AA_BACK_MAX_ELEMS * 8) return AA_ERR_BAD_SHAPE;
+    if ((rc = plan_item(filter, layout, K, in[i], it, ws)) != AA_OK) return rc;
     unit0[i] = units;
-    units += im.oh * (int64_t)it.xtiles;
-    if (units > INT32_MAX) return AA_ERR_BAD_SHAPE;  // (one grid)
+    if ((rc = plan_output(K, reduce, eb, it.oh, it.ow, it.xtiles, arena, units, &it.out_off)) != AA_OK) return rc;
+    out_offsets[i] = it.out_off;
     items[i] = it;
   }
   unit0[n] = units;
@@ -293,14 +400,9 @@ int aa_launch_back_many(const void *desc_host, const void *desc_dev, int in_dtyp
   const int rc = aa_many_check_launch(hd->n, desc_dev, arena_dev, workspace_dev, workspace_bytes, hd->ws_bytes, elem_bytes(hd->out_dtype));
   if (rc != AA_OK || hd->n == 0) return rc;
   if (arena_bytes < (size_t)hd->arena_bytes) return AA_ERR_WORKSPACE;
-  const AABackItem *host_items = (const AABackItem *)(hd + 1);
-  const size_t ei = elem_bytes(in_dtype);
-  bool vec = hd->layout == AA_NHWC && hd->K % AA_BACK_UNROLL == 0;
-  for (int64_t i = 0; i < hd->n; i++) {
-    const AABackItem &it = host_items[i];
-    if ((uintptr_t)it.src % ei) return AA_ERR_STRIDES;
-    vec = vec && (uintptr_t)it.src % (AA_BACK_UNROLL * ei) == 0 && it.stride_row % AA_BACK_UNROLL == 0;  // (stride_px is K or unused)
-  }
+  bool vec;
+  const int rs = check_sources((const AABackItem *)(hd + 1), hd->n, in_dtype, hd->layout, hd->K, &vec);
+  if (rs != AA_OK) return rs;
   const AADescView<AABackItem> v = aa_desc_view<AABackHeader, AABackItem>(desc_dev, hd->n);
   hipLaunchKernelGGL(back_tables, dim3(2u * (unsigned)hd->n), dim3(AA_BACK_THREADS), 0, stream, v.items, (char *)workspace_dev, (int)hd->filter);
   AA_HIP_CHECK_LAUNCH();
@@ -308,6 +410,111 @@ int aa_launch_back_many(const void *desc_host, const void *desc_dev, int in_dtyp
   a.items = v.items; a.unit0 = v.prefix; a.ws = (const char *)workspace_dev; a.arena = (char *)arena_dev;
   a.threshold = threshold;
   a.n = hd->n; a.K = hd->K;
+  if (vec) launch_in<true>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
+  else launch_in<false>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
+  AA_HIP_CHECK_LAUNCH();
+  return AA_OK;
+}
+
+// ---- host: the merged planner --------------------------------------------------------------------------------------------------------------
+size_t aa_back_merged_desc_size(int64_t n, int64_t g) {
+  if (n < 0 || g < 0) return 0;
+  return sizeof(AABackMergedHeader) + (size_t)n * sizeof(AABackItem) + (size_t)g * sizeof(AABackGroup) + align8((size_t)n * sizeof(int32_t)) +
+         ((size_t)g + 1) * sizeof(int64_t);
+}
+
+// aa_back_plan_host's checks in its order, with G and merge beside n, K and reduce; the groups' membership after the block's size and
+// before the items; a member's size against its group's after the member's own checks; the arena and the work units per GROUP.
+int aa_back_merged_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *in, int64_t G, const int64_t *group_of, int merge,
+                             int reduce, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
+                             int64_t *out_offsets) {
+  const bool own_ok = G >= 0 && G <= n && (G > 0 || n == 0) && (merge == AA_BACK_MERGE_SUM || merge == AA_BACK_MERGE_MEAN);
+  int rc = plan_prologue(filter, layout, n, K, reduce, out_dtype, own_ok);
+  if (rc != AA_OK) return rc;
+  if (!desc_host || !workspace_bytes || !arena_bytes || (n > 0 && (!in || !group_of || !out_offsets))) return AA_ERR_NULL;
+  if (desc_bytes < aa_back_merged_desc_size(n, G)) return AA_ERR_WORKSPACE;
+  const size_t eb = elem_bytes(out_dtype);
+  AABackMergedHeader *hd = (AABackMergedHeader *)desc_host;
+  AABackItem *items = (AABackItem *)(hd + 1);
+  AABackGroup *groups = (AABackGroup *)(items + n);
+  int32_t *member = (int32_t *)(groups + G);
+  int64_t *unit0 = (int64_t *)((char *)member + align8((size_t)n * sizeof(int32_t)));
+  // the groups' members: counted, then the slots handed out in item order, so a group's members ascend
+  memset(groups, 0, (size_t)G * sizeof(AABackGroup));
+  for (int64_t i = 0; i < n; i++) {
+    if (group_of[i] < 0 || group_of[i] >= G) return AA_ERR_BAD_SHAPE;
+    groups[group_of[i]].count++;
+  }
+  int32_t slot = 0;
+  for (int64_t g = 0; g < G; g++) {
+    if (groups[g].count == 0) return AA_ERR_BAD_SHAPE;  // (an empty group)
+    groups[g].first = slot;
+    slot += groups[g].count;
+    groups[g].count = 0;  // (counted up again as the slots are filled)
+  }
+  size_t ws = 0, arena = 0;
+  int64_t units = 0;
+  for (int64_t i = 0; i < n; i++) {
+    AABackItem &it = items[i];
+    if ((rc = plan_item(filter, layout, K, in[i], it, ws)) != AA_OK) return rc;
+    AABackGroup &gr = groups[group_of[i]];
+    if (gr.count == 0) {
+      gr.oh = it.oh; gr.ow = it.ow; gr.xtiles = it.xtiles;
+    } else if (gr.oh != it.oh || gr.ow != it.ow) {
+      return AA_ERR_BAD_SHAPE;  // (the members of a group have one size)
+    }
+    member[gr.first + gr.count++] = (int32_t)i;
+  }
+  for (int64_t g = 0; g < G; g++) {
+    AABackGroup &gr = groups[g];
+    unit0[g] = units;
+    if ((rc = plan_output(K, reduce, eb, gr.oh, gr.ow, gr.xtiles, arena, units, &gr.out_off)) != AA_OK) return rc;
+    out_offsets[g] = gr.out_off;
+  }
+  unit0[G] = units;
+  for (int64_t i = 0; i < n; i++) items[i].out_off = groups[group_of[i]].out_off;
+  if (n % 2) member[n] = 0;  // (the padding)
+  if (!out_dtype_ok(reduce, out_dtype)) return AA_ERR_BAD_DTYPE;
+  memset(hd, 0, sizeof(*hd));
+  hd->magic = AA_BACK_MERGED_MAGIC;
+  hd->n = (int32_t)n; hd->K = (int32_t)K; hd->filter = filter; hd->layout = layout;
+  hd->reduce = reduce; hd->out_dtype = out_dtype; hd->merge = merge;
+  hd->units = units;
+  hd->ws_bytes = (int64_t)ws;
+  hd->arena_bytes = (int64_t)arena;
+  hd->G = (int32_t)G;
+  *workspace_bytes = ws;
+  *arena_bytes = arena;
+  return AA_OK;
+}
+
+// ---- host: the merged call's two launches --------------------------------------------------------------------------------------------------
+// aa_launch_back_many's checks, every one before the first launch; the table kernel is its own, over the members.
+int aa_launch_back_merged(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
+                          void *workspace_dev, size_t workspace_bytes, hipStream_t stream) {
+  const AABackMergedHeader *hd = (const AABackMergedHeader *)desc_host;
+  if (hd->magic != AA_BACK_MERGED_MAGIC || !aa_filter_valid(hd->filter) || hd->n < 0 || hd->K < 1 || hd->units < 0 || hd->units > INT32_MAX ||
+      hd->reduce < AA_BACK_VALUES || hd->reduce > AA_BACK_GREATER || (hd->layout != AA_NCHW && hd->layout != AA_NHWC) || hd->G < 0 ||
+      hd->G > hd->n || (hd->G == 0 && hd->n > 0) || (hd->merge != AA_BACK_MERGE_SUM && hd->merge != AA_BACK_MERGE_MEAN))
+    return AA_ERR_BAD_SHAPE;
+  if (!float_dtype(in_dtype) || !out_dtype_ok(hd->reduce, hd->out_dtype)) return AA_ERR_BAD_DTYPE;
+  if (hd->reduce == AA_BACK_GREATER && !(threshold - threshold == 0.0f)) return AA_ERR_BAD_SHAPE;  // (not finite)
+  const int rc = aa_many_check_launch(hd->n, desc_dev, arena_dev, workspace_dev, workspace_bytes, hd->ws_bytes, elem_bytes(hd->out_dtype));
+  if (rc != AA_OK || hd->n == 0) return rc;
+  if (arena_bytes < (size_t)hd->arena_bytes) return AA_ERR_WORKSPACE;
+  bool vec;
+  const int rs = check_sources((const AABackItem *)(hd + 1), hd->n, in_dtype, hd->layout, hd->K, &vec);
+  if (rs != AA_OK) return rs;
+  MergedArgs a;
+  a.items = (const AABackItem *)((const char *)desc_dev + sizeof(AABackMergedHeader));
+  a.groups = (const AABackGroup *)(a.items + hd->n);
+  a.member = (const int32_t *)(a.groups + hd->G);
+  a.unit0 = (const int64_t *)((const char *)a.member + align8((size_t)hd->n * sizeof(int32_t)));
+  a.ws = (const char *)workspace_dev; a.arena = (char *)arena_dev;
+  a.threshold = threshold;
+  a.G = hd->G; a.K = hd->K; a.mean = hd->merge == AA_BACK_MERGE_MEAN;
+  hipLaunchKernelGGL(back_tables, dim3(2u * (unsigned)hd->n), dim3(AA_BACK_THREADS), 0, stream, a.items, (char *)workspace_dev, (int)hd->filter);
+  AA_HIP_CHECK_LAUNCH();
   if (vec) launch_in<true>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
   else launch_in<false>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
   AA_HIP_CHECK_LAUNCH();

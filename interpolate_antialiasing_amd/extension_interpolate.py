@@ -69,7 +69,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -1495,6 +1495,26 @@ def _back_regions(name: str, regions, items):
     return out
 
 
+def _back_out(name: str, reduce, out_dtype, threshold, items, k: int):
+    """out_dtype and threshold of resize_many_back and its kin, checked for ``reduce`` (a key of _BACK_REDUCE) ->
+    (the planner's reduce id, out_dtype, its aa_dtype, threshold as a float)."""
+    reduce_id, default_dtype, out_dtypes = _BACK_REDUCE[reduce]
+    if out_dtype is None:
+        out_dtype = default_dtype if default_dtype is not None else (items[0].dtype if items else torch.float32)
+    if out_dtype not in out_dtypes:
+        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built for reduce={reduce!r}; {', '.join(str(d) for d in out_dtypes)}")
+    out_id, most = out_dtypes[out_dtype]
+    if most is not None and k > most:
+        raise ValueError(f"{name}(): out_dtype {out_dtype} holds labels below {most}, got K = {k}")
+    try:
+        threshold = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}(): threshold must be a finite float, got {threshold!r}") from None
+    if not math.isfinite(threshold) or not math.isfinite(ctypes.c_float(threshold).value):
+        raise ValueError(f"{name}(): threshold must be a finite float (as float32), got {threshold!r}")
+    return reduce_id, out_dtype, out_id, threshold
+
+
 def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips=None, reduce: Optional[str] = None, threshold: float = 0.0,
                      out_dtype=None, channels: Optional[int] = None):
     """A model's answer on the canvas, back at every image's own size: the return path of ``resize_many`` and its kin, for segmentation,
@@ -1531,30 +1551,18 @@ def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips
     batch tensor, one per list item, +0.0 outside the regions and for items the loss did not use (two launches for the whole list,
     whatever the loss uses).  The values, the arena and the launch count are the same with and without it.  The results are views of
     one arena and outputs of one autograd node: under autograd they must not be modified in place.  ``reduce="argmax"`` and
-    ``"greater"`` are not differentiable and never carry a ``grad_fn``.  Not built: fractional regions, a dense padded output, softmax."""
+    ``"greater"`` are not differentiable and never carry a ``grad_fn``.  Not built: fractional regions, a dense padded output, softmax
+    (several passes per image summed before the reduction: ``resize_many_back_merged``)."""
     name = "resize_many_back"
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
     if reduce not in _BACK_REDUCE:
         raise ValueError(f"{name}(): reduce must be None, 'argmax' or 'greater', got {reduce!r}")
-    reduce_id, default_dtype, out_dtypes = _BACK_REDUCE[reduce]
     items, dev0, n, k = _back_items(name, pred, channels)
     sizes = _back_sizes(name, sizes, n, k)
     rects = _back_regions(name, regions, items)
     flips = _many_flips(name, flips, n)
-    if out_dtype is None:
-        out_dtype = default_dtype if default_dtype is not None else (items[0].dtype if n else torch.float32)
-    if out_dtype not in out_dtypes:
-        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built for reduce={reduce!r}; {', '.join(str(d) for d in out_dtypes)}")
-    out_id, most = out_dtypes[out_dtype]
-    if most is not None and k > most:
-        raise ValueError(f"{name}(): out_dtype {out_dtype} holds labels below {most}, got K = {k}")
-    try:
-        threshold = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name}(): threshold must be a finite float, got {threshold!r}") from None
-    if not math.isfinite(threshold) or not math.isfinite(ctypes.c_float(threshold).value):
-        raise ValueError(f"{name}(): threshold must be a finite float (as float32), got {threshold!r}")
+    reduce_id, out_dtype, out_id, threshold = _back_out(name, reduce, out_dtype, threshold, items, k)
     if n == 0:
         return []
     for t in items:
@@ -1569,16 +1577,14 @@ def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips
     return _resize_many_back_run(plan, [t.detach() for t in items])[0]
 
 
-def _resize_many_back_run(plan, items):
-    """The layout class, the plan and the two launches of resize_many_back on checked GPU items -> (N views of one arena, whether the
-    items were read as interleaved classes)."""
-    name, mode, n, k, sizes, rects, flips, reduce, reduce_id, out_dtype, out_id, threshold = plan
-    dev = items[0].device
+def _back_records(items, rects, sizes, flips, k: int):
+    """The aa_back_item records of checked GPU items: each one's region, read where it lies in the call's layout class and resampled to
+    sizes[i] -> (records, the copies of items outside the class, which must stay alive until the launches are enqueued; whether the
+    class is interleaved)."""
+    n = len(items)
     views = [t[:, y0:y0 + h, x0:x0 + w] for t, (y0, x0, h, w) in zip(items, rects)]
     classes, interleaved = _many_layout(views, k)
-    layout = _lib.NHWC if interleaved else _lib.NCHW
-    L = _lib.load()
-    recs, keep = (_lib.BackItemIn * n)(), []  # (keep: the copies of items outside the class, alive until the launches are enqueued)
+    recs, keep = (_lib.BackItemIn * n)(), []
     for i, t in enumerate(views):
         if not classes[i][0 if interleaved else 1]:
             t = t.permute(1, 2, 0).contiguous().permute(2, 0, 1) if interleaved else t.contiguous()
@@ -1592,21 +1598,60 @@ def _resize_many_back_run(plan, items):
         r.stride_row = t.stride(1) if r.h > 1 else 0
         r.stride_px = k if interleaved else 1
         r.flags = _lib.MANY_FLIP_X if flips is not None and flips[i] else 0
-    offs = (ctypes.c_int64 * n)()
-    arena_bytes = ctypes.c_size_t(0)
-    es = torch.empty((), dtype=out_dtype).element_size()
-    arena = _many_run(
-        name, dev, L.aa_back_many_desc_bytes(n),
-        lambda desc, nbytes, ws_bytes: L.aa_back_many_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, reduce_id, out_id, desc, nbytes, ws_bytes,
-                                                           ctypes.byref(arena_bytes), offs),
-        lambda: torch.empty((arena_bytes.value // es,), dtype=out_dtype, device=dev),
-        lambda desc_host, desc_dev, out, ws, stream: L.aa_resample_back_many(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], threshold, out.data_ptr(),
-                                                                            out.numel() * es, ws.data_ptr(), ws.numel(), stream))[0]
-    outs = []
+    return recs, keep, interleaved
+
+
+def _back_views(arena, offs, sizes, reduce, k: int):
+    """The outputs of a return-path call as views of its arena: [oh, ow] at byte offs[i] for argmax, else [K, oh, ow]."""
+    es, outs = arena.element_size(), []
     for i, (oh, ow) in enumerate(sizes):
         shape = (oh, ow) if reduce == "argmax" else (k, oh, ow)
         outs.append(arena[offs[i] // es:offs[i] // es + math.prod(shape)].view(shape))
-    return outs, interleaved
+    return outs
+
+
+def _resize_many_back_run(plan, items, merged=None):
+    """The layout class, the plan and the two launches of resize_many_back on checked GPU items -> (N views of one arena, whether the
+    items were read as interleaved classes).  merged: None, or (groups, the G groups' sizes, merge) of resize_many_back_merged, whose
+    plan's sizes are the members' (each its group's): the merged planner and launch, and G views."""
+    name, mode, n, k, sizes, rects, flips, reduce, reduce_id, out_dtype, out_id, threshold = plan
+    dev = items[0].device
+    recs, keep, interleaved = _back_records(items, rects, sizes, flips, k)  # (keep: alive until the launches are enqueued)
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    arena_bytes = ctypes.c_size_t(0)
+    es = torch.empty((), dtype=out_dtype).element_size()
+    if merged is None:
+        out_sizes, offs = sizes, (ctypes.c_int64 * n)()
+        desc_bytes, resample = L.aa_back_many_desc_bytes(n), L.aa_resample_back_many
+
+        def planner(desc, nbytes, ws_bytes):
+            return L.aa_back_many_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, reduce_id, out_id, desc, nbytes, ws_bytes, ctypes.byref(arena_bytes), offs)
+    else:
+        groups, out_sizes, merge = merged
+        g = len(out_sizes)
+        offs, group_of = (ctypes.c_int64 * g)(), (ctypes.c_int64 * n)(*groups)
+        desc_bytes, resample = L.aa_back_merged_desc_bytes(n, g), L.aa_resample_back_merged
+
+        def planner(desc, nbytes, ws_bytes):
+            return L.aa_back_merged_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, g, group_of, _lib.BACK_MERGE[merge], reduce_id, out_id, desc, nbytes,
+                                         ws_bytes, ctypes.byref(arena_bytes), offs)
+    arena = _many_run(
+        name, dev, desc_bytes, planner, lambda: torch.empty((arena_bytes.value // es,), dtype=out_dtype, device=dev),
+        lambda desc_host, desc_dev, out, ws, stream: resample(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], threshold, out.data_ptr(),
+                                                              out.numel() * es, ws.data_ptr(), ws.numel(), stream))[0]
+    return _back_views(arena, offs, out_sizes, reduce, k), interleaved
+
+
+def _back_input_grads(ctx, grads, first: int = 2):
+    """What the backward of a return-path autograd node returns for its inputs from number ``first`` on, the batch tensor or the list's
+    items: resize_many_back_backward of the N items' gradients (None: not used) on the geometry ctx saved."""
+    _, mode, n, k, _, rects, flips, *_ = ctx.plan
+    kw = dict(regions=rects, flips=flips, channels=k, dtype=ctx.in_dtype, out_format="nhwc" if ctx.interleaved else "nchw", device=ctx.dev)
+    if ctx.is_batch:
+        return (resize_many_back_backward(grads, ctx.shapes[0][2:], mode, **kw),)
+    gs = resize_many_back_backward(grads, [s[-2:] for s in ctx.shapes], mode, **kw)
+    return tuple(g.view(s) if ctx.needs_input_grad[first + i] else None for i, (g, s) in enumerate(zip(gs, ctx.shapes)))
 
 
 class _ResizeManyBack(torch.autograd.Function):
@@ -1625,12 +1670,118 @@ class _ResizeManyBack(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        _, mode, n, k, _, rects, flips, *_ = ctx.plan
-        kw = dict(regions=rects, flips=flips, channels=k, dtype=ctx.in_dtype, out_format="nhwc" if ctx.interleaved else "nchw", device=ctx.dev)
-        if ctx.is_batch:
-            return None, None, resize_many_back_backward(grads, ctx.shapes[0][2:], mode, **kw)
-        gs = resize_many_back_backward(grads, [s[-2:] for s in ctx.shapes], mode, **kw)
-        return (None, None) + tuple(g.view(s) if ctx.needs_input_grad[2 + i] else None for i, (g, s) in enumerate(zip(gs, ctx.shapes)))
+        return (None, None) + _back_input_grads(ctx, grads)
+
+
+def _back_groups(name: str, groups, n: int, g: int):
+    """groups of resize_many_back_merged, checked -> (N ints in 0 .. G - 1, the members of every group, each at least 1)."""
+    try:
+        groups = list(groups)
+    except TypeError:
+        raise ValueError(f"{name}(): groups must be N integers, got {groups!r}") from None
+    if len(groups) != n:
+        raise ValueError(f"{name}(): groups must hold one entry per item ({n}), got {len(groups)}")
+    counts = [0] * g
+    for i, v in enumerate(groups):
+        try:
+            if isinstance(v, bool) or int(v) != v:
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}(): groups[{i}] must be an integer, got {v!r}") from None
+        if not (0 <= int(v) < g):
+            raise ValueError(f"{name}(): groups[{i}] = {int(v)} is outside 0 .. {g - 1}, the groups that sizes states ({g})")
+        groups[i] = int(v)
+        counts[groups[i]] += 1
+    for j, c in enumerate(counts):
+        if c == 0:
+            raise ValueError(f"{name}(): group {j} (sizes[{j}]) has no member: every group needs at least one entry of groups")
+    return groups, counts
+
+
+def resize_many_back_merged(pred, groups, sizes, mode: str = "bilinear", *, regions=None, flips=None, merge: str = "sum",
+                            reduce: Optional[str] = None, threshold: float = 0.0, out_dtype=None, channels: Optional[int] = None):
+    """Test-time augmentation's merge: several passes per image — scales, mirrored or not — each brought back to the image's own size as
+    ``resize_many_back`` does, un-mirrored, SUMMED per image, and only then reduced to a label, a mask or values.  ``pred``, ``regions``,
+    ``flips``, ``mode``, ``reduce``, ``threshold``, ``out_dtype`` and ``channels`` are ``resize_many_back``'s, with its checks: N items, one
+    batch tensor [N, K, H, W] or a list of [K, H_i, W_i], float32 / float16 / bfloat16, read where they lie in one layout class.
+    ``groups``: N integers, ``groups[i]`` in 0 .. G - 1 the output that item i contributes to, in any order (a batch laid out pass by pass
+    interleaves them); every group has at least one member.  ``sizes``: G pairs (oh_g, ow_g), one per GROUP: every member of group g is
+    resampled to that size.  ``merge``: "sum" or "mean".
+
+    With ``R_i`` the fp32 value ``resize_many_back`` defines for item i at size ``sizes[groups[i]]`` — mirrored left to right where
+    ``flips[i]``, BEFORE any rounding to ``out_dtype`` — and ``i_0 < i_1 < ... < i_{M-1}`` the members of group g in ascending item index,
+    ``S_g = R_{i_0}``, then ``S_g = S_g + R_{i_j}`` for j = 1 .. M - 1: one fp32 round-to-nearest add per element, in that order, no fused
+    multiply-add, no reassociation.  ``merge="mean"`` then divides once, ``S_g / float32(M)``, correctly rounded (not a multiplication by a
+    reciprocal).  The result is a list of G tensors, bit for bit ``resize_many_back``'s reductions of ``S_g``: ``reduce=None`` gives
+    ``S_g.to(out_dtype)`` [K, oh_g, ow_g], ONE rounding; ``"argmax"`` gives ``numpy.argmax`` of the fp32 ``S_g`` over K [oh_g, ow_g];
+    ``"greater"`` gives ``S_g > float32(threshold)``.  So a NaN in any member makes the sum NaN; +inf in one member and -inf in another
+    at the same pixel and class give NaN, which wins the argmax; and a group of one member is exactly ``resize_many_back``'s item, for
+    both merges.
+
+    The tensors are contiguous views of ONE arena, each on a 16-byte boundary of it; G == 0 with N == 0 gives [].  Two launches
+    whatever N, G and the sizes — the members' tables, then one resample that walks a group's members per chunk of four classes and adds
+    them in registers — and one non-blocking copy of a packed descriptor; nothing is read back, no table cache is touched, the call does
+    not synchronise.  With ``"argmax"`` neither the K sums nor any member's values are ever stored.
+
+    Differentiable for ``reduce=None`` like ``resize_many_back``: when gradients are enabled and ``pred`` (or any item of a list) requires
+    grad, the results carry a backward, ONE ``resize_many_back_backward`` over all members with member i's gradient that of its group's
+    output — for "sum" the same tensor for every member, read where it lies; for "mean" ``G_g.float() / M_g``, one division per used
+    group; None for the members of a group the loss did not use.  ``"argmax"`` and ``"greater"`` never carry a ``grad_fn``.
+
+    Not built: softmax before the sum (``exp`` has no bit-exact definition here), per-member weights, a maximum instead of the sum,
+    sliding-window overlap-add (members placed at different positions of the output), a dense padded output."""
+    name = "resize_many_back_merged"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if reduce not in _BACK_REDUCE:
+        raise ValueError(f"{name}(): reduce must be None, 'argmax' or 'greater', got {reduce!r}")
+    if merge not in _lib.BACK_MERGE:
+        raise ValueError(f"{name}(): merge must be 'sum' or 'mean', got {merge!r}")
+    items, dev0, n, k = _back_items(name, pred, channels)
+    try:
+        sizes = list(sizes)
+    except TypeError:
+        raise ValueError(f"{name}(): sizes must be G pairs (oh, ow), got {sizes!r}") from None
+    sizes = _back_sizes(name, sizes, len(sizes), k)
+    groups, counts = _back_groups(name, groups, n, len(sizes))
+    rects = _back_regions(name, regions, items)
+    flips = _many_flips(name, flips, n)
+    reduce_id, out_dtype, out_id, threshold = _back_out(name, reduce, out_dtype, threshold, items, k)
+    if n == 0:
+        return []
+    for t in items:
+        _require_gpu(t, name)
+    plan = (name, mode, n, k, [sizes[g] for g in groups], rects, flips, reduce, reduce_id, out_dtype, out_id, threshold)
+    merged = (groups, sizes, merge)
+    if reduce is None and torch.is_grad_enabled():
+        if isinstance(pred, torch.Tensor):
+            if pred.requires_grad:
+                return list(_ResizeManyBackMerged.apply(plan, True, merged, counts, pred))
+        elif any(t.requires_grad for t in items):
+            return list(_ResizeManyBackMerged.apply(plan, False, merged, counts, *items))
+    return _resize_many_back_run(plan, [t.detach() for t in items], merged)[0]
+
+
+class _ResizeManyBackMerged(torch.autograd.Function):
+    """resize_many_back_merged(reduce=None) for predictions that require grad.  A member's gradient is its group's: the backward is
+    _ResizeManyBack's, resize_many_back_backward once over the N members, given per member the group's gradient (sum) or the group's
+    gradient in float32 divided by the members' count (mean), None where the loss did not use the group."""
+
+    @staticmethod
+    def forward(ctx, plan, is_batch, merged, counts, *inputs):
+        items = list(inputs[0].unbind(0)) if is_batch else [t[0] if t.dim() == 4 else t for t in inputs]
+        outs, interleaved = _resize_many_back_run(plan, items, merged)
+        ctx.plan, ctx.is_batch, ctx.interleaved, ctx.merged, ctx.counts = plan, is_batch, interleaved, merged, counts
+        ctx.shapes, ctx.in_dtype, ctx.dev = [tuple(t.shape) for t in inputs], inputs[0].dtype, inputs[0].device
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        groups, _, merge = ctx.merged
+        if merge == "mean":
+            grads = [None if g is None else g.float() / m for g, m in zip(grads, ctx.counts)]
+        return (None,) * 4 + _back_input_grads(ctx, [grads[g] for g in groups], first=4)
 
 
 def _back_canvas(name: str, canvas, n: int, k: int):

@@ -99,6 +99,19 @@ Timing: device events around `--batches` batches that end in a synchronise; ever
 min-to-max spread of `--rounds` rounds.  (c) must beat (a) by more than the two spreads together.  The loops do not assemble their N
 results into one tensor; (c) writes the batch.
 
+--tta: the way back for test-time augmentation — --logits' 16 camera-sized images, each answered M = 6 times: [16, K, c, c] logits on
+letterbox canvases c = 384, 512 and 640, plain and mirrored; every pass resampled to the image's own size, un-mirrored, summed in pass
+order in fp32 and reduced to the argmax over K; bilinear, K = 19 and 150, float32 and bfloat16 logits — three ways:
+
+  a  the per-member loop of existing calls: linear_forward(crop.float()[None], size), flip(-1) where mirrored, added in place; argmax;
+  b  resize_many_back(reduce=None, out_dtype=float32) of all 96 members, then torch's adds in order and argmax per image;
+  c  resize_many_back_merged(reduce="argmax"): two launches whatever N and M.
+
+The labels of (a) and (b) are compared with (c)'s and the differing ones counted (torch.argmax promises no order among equal sums).
+Per contestant: kernel launches, ms per batch, the growth of torch.cuda.max_memory_allocated over one call; a contestant that does not
+fit the device's memory — (b) at K = 150 needs 96 float32 [K, oh, ow] tensors, 334 GB — is reported as such and not timed.  No number
+is a bar: the output is written down as measured, profiles/resize_many_back_merged.txt (--rounds 5 --batches 3 keeps the run short).
+
 --logits-backward: the gradient's way — gradients [K, oh_i, ow_i] at the images' own sizes back to the canvas, bilinear, odd items
 flipped, float32 and bfloat16, resize_many_back_backward (two launches) against the loop a user writes today: linear_backward per item
 (its table cache warm), the gradient flipped where needed, copied into a zeroed canvas.  Two workloads: "small", N = 64, K = 21, image
@@ -122,6 +135,8 @@ the same bits.  The kernel's fetched bytes come from a counter run of its own: t
   python tools/resize_many_bench.py --embed > out.txt    # only the position grid to the token grids (above); profiles/resize_embed_many.txt
   python tools/resize_many_bench.py --logits > out.txt   # only the way back: canvas logits to the images' own sizes, argmax (below);
                                                          # profiles/resize_many_back.txt
+  python tools/resize_many_bench.py --tta --rounds 5 --batches 3 > out.txt   # only the merged way back: 6 passes per image summed, argmax (above);
+                                                         # profiles/resize_many_back_merged.txt is this output
   python tools/resize_many_bench.py --logits-backward > out.txt   # only the gradients' way back to the canvas (above);
                                                          # profiles/resize_many_back_bwd.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
@@ -904,6 +919,115 @@ def logits(args, torch, aa, timed):
             del x
 
 
+def tta(args, torch, aa, timed):
+    """resize_many_back_merged on test-time augmentation: --logits' 16 camera-sized images, each answered M = 6 times (letterbox canvases
+    of 384, 512 and 640, plain and mirrored), the passes resampled to the image's size, un-mirrored, summed in order and reduced to the
+    argmax.  Three ways; per contestant: kernel launches, ms per batch, and the growth of torch.cuda.max_memory_allocated over one call.
+    A contestant that does not fit the device's memory is reported as such and not timed."""
+    from interpolate_antialiasing_amd import boxmath
+
+    n, canvases = 16, (384, 512, 640)
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    passes = [(c, flip) for c in canvases for flip in (False, True)]
+    regions, flips, groups = [], [], []
+    for c, flip in passes:  # (a batch is laid out pass by pass: the groups interleave)
+        regions += boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=c), "center", (c, c))
+        flips += [flip] * n
+        groups += list(range(n))
+    pixels = sum(h * w for h, w in shapes)
+    print(f"resize_many_bench --tta: N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), {pixels / 1e6:.1f} M output "
+          f"pixels, each from M = {len(passes)} passes: [N, K, c, c] logits on letterbox canvases c = {', '.join(map(str, canvases))} "
+          f"(fit_sizes(longer=c), 'center'), plain and mirrored; bilinear; summed in pass order, argmax over K; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for k in (19, 150):
+        for dtype in (torch.float32, torch.bfloat16):
+            batches = [torch.randn((n, k, c, c), device="cuda", generator=gen).to(dtype) for c, _ in passes]
+            items = [b[i] for b in batches for i in range(n)]
+            members = [[p * n + i for p in range(len(passes))] for i in range(n)]
+
+            def loop():
+                out = []
+                for i in range(n):
+                    s = None
+                    for j in members[i]:
+                        y0, x0, h, w = regions[j]
+                        r = aa.linear_forward(items[j][:, y0:y0 + h, x0:x0 + w].float()[None], list(shapes[i]))[0]
+                        r = r.flip(-1) if flips[j] else r
+                        s = r if s is None else s.add_(r)
+                    out.append(s.argmax(0))
+                return out
+
+            def values_then_sum():
+                vals = aa.resize_many_back(items, [shapes[g] for g in groups], regions=regions, flips=flips, out_dtype=torch.float32)
+                out = []
+                for i in range(n):
+                    s = vals[members[i][0]]
+                    for j in members[i][1:]:
+                        s = s + vals[j]
+                    out.append(s.argmax(0))
+                return out
+
+            def merged():
+                return aa.resize_many_back_merged(items, groups, shapes, regions=regions, flips=flips, reduce="argmax")
+
+            contestants = {"a: loop: linear_forward, flip, add per member; argmax per image": loop,
+                           "b: resize_many_back(reduce=None) of all members; add, argmax": values_then_sum,
+                           "c: resize_many_back_merged(reduce='argmax')": merged}
+            results, fits = {}, {}
+            for key, fn in contestants.items():
+                try:
+                    results[key] = fn()
+                    fn()
+                    torch.cuda.synchronize()
+                    fits[key] = True
+                except torch.cuda.OutOfMemoryError:
+                    results[key], fits[key] = None, False
+                    torch.cuda.empty_cache()
+            want = results["c: resize_many_back_merged(reduce='argmax')"]
+            agree = []
+            for key in list(contestants)[:2]:  # (torch.argmax promises no order among equal sums: the differing labels are counted)
+                if fits[key]:
+                    agree.append(f"({key[0]}) differs from (c) at {sum(int((p != q).sum()) for p, q in zip(results[key], want))} of {pixels} labels")
+                    assert sum(int((p != q).sum()) for p, q in zip(results[key], want)) <= pixels // 10 ** 6, f"({key[0]}) differs from the merged call"
+            del results, want
+            torch.cuda.empty_cache()
+            times = {key: [] for key in contestants if fits[key]}
+            for _ in range(args.rounds):
+                for key in times:
+                    times[key].append(timed(contestants[key]))
+            print(f"\nK = {k}, {str(dtype).replace('torch.', '')}: " + "; ".join(agree))
+            stat = {}
+            for key in contestants:
+                if not fits[key]:
+                    print(f"  {key:64s} does not fit the device's memory: not timed")
+                    continue
+                v = times[key]
+                stat[key[0]] = (statistics.median(v), min(v), max(v))
+                launches = count_launches(torch, contestants[key])
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.max_memory_allocated()
+                r = contestants[key]()
+                torch.cuda.synchronize()
+                peak = torch.cuda.max_memory_allocated() - before
+                del r
+                m, lo, hi = stat[key[0]]
+                print(f"  {key:64s} {m:9.3f} [{lo:9.3f} .. {hi:9.3f}]   launches {launches if launches is not None else 'not measured'}"
+                      f"   peak {peak / 1e6:10.1f} MB")
+            mc, lc, hc = stat["c"]
+            for other in ("a", "b"):
+                if other in stat:
+                    mo, lo, ho = stat[other]
+                    verdict = "(c) is faster" if mo - mc > (ho - lo) + (hc - lc) else f"(c) IS NOT FASTER than ({other}) by more than the spreads"
+                    print(f"  (c) against ({other}): {mo / mc:.2f} x; median gain {mo - mc:.3f} ms, the two spreads together {(ho - lo) + (hc - lc):.3f} ms: {verdict}")
+            del batches, items
+            torch.cuda.empty_cache()
+
+
 def back_bwd_workload(which, torch, k, dtype):
     """The two geometries of --logits-backward -> (canvas, regions, flips, gradients [K, oh_i, ow_i] on the GPU, their bytes): "large",
     --logits' 16 camera-sized images from a 512 x 512 letterbox canvas; "small", 64 images with sides drawn from 240 .. 640 from a
@@ -1013,6 +1137,8 @@ def main():
                     "per-item loop of existing calls and against reduce=None followed by argmax")
     ap.add_argument("--logits-backward", action="store_true", help="only resize_many_back_backward: gradients at the images' sizes back to the "
                     "canvas, against the per-item loop of linear_backward into a zeroed canvas; --logits' geometry and 64 small items")
+    ap.add_argument("--tta", action="store_true", help="only resize_many_back_merged: 6 test-time passes per image summed and reduced to the argmax, "
+                    "against resize_many_back(reduce=None) plus torch adds and against the per-member loop of linear_forward")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -1122,6 +1248,9 @@ def main():
         return
     if args.logits_backward:
         logits_backward(args, torch, aa, timed)
+        return
+    if args.tta:
+        tta(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
