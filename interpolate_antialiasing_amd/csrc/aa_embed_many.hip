@@ -13,64 +13,31 @@
 //                    gradient's token columns, then its vertical pass — and the first wave adds them in ascending order into a
 //                    register, acc = b_0, acc = acc + b_i; one store, no atomics, so the result does not depend on the launch shape.
 // A lane owns AA_EMBED_VEC consecutive channels when D and every address allow vector accesses, one channel otherwise.
-// Shared with the other ragged calls: aa_many_dev.h (the item of a row, the element types), aa_many_host.h (the block, the launch checks).
+// Shared with the other ragged calls: aa_many_dev.h (the item of a row, the element types), aa_many_host.h (the block, the launch checks);
+// with the other float ragged calls: aa_float_many_dev.h (the table kernels' body, table_row, the element helpers), aa_float_many_host.h
+// (the float types, the tables of an item in a plan).
 
 #include <string.h>
 
 #include "aa_embed_many.h"
-#include "aa_many_dev.h"
-#include "aa_many_host.h"
-#include "aa_table_rows.h"
+#include "aa_float_many_dev.h"
+#include "aa_float_many_host.h"
 
 namespace {
 
 // ---- 1. tables ---------------------------------------------------------------------------------------------------------------------------
-// Workgroup 2 i builds item i's H axis, 2 i + 1 its W axis.  A table's header is zeroed first: the row functions keep max_taps there.
-// Nobody reads that field back (the call reads nothing back); the adjoint rows hold aa_table_transposed_ksize's estimate of entries,
-// which the single-shape backward checks against the measured count and has never seen exceeded.
+// Workgroup 2 i builds item i's H axis, 2 i + 1 its W axis: the shared body, with adjoints for the backward.
 __global__ void __launch_bounds__(AA_EMBED_THREADS) embed_tables(const AAEmbedItem *items, char *ws, int H0, int W0, int filter, int adjoints) {
   const AAEmbedItem &it = items[blockIdx.x >> 1];
   const bool horiz = blockIdx.x & 1;
-  const int in_size = horiz ? W0 : H0, out_size = horiz ? it.gw : it.gh;
-  const int ksize = horiz ? it.ksize_w : it.ksize_h, trk = horiz ? it.trk_w : it.trk_h;
-  const float scale = horiz ? it.scale_w : it.scale_h;
-  char *tab = ws + (horiz ? it.tab_w : it.tab_h), *tr = ws + (horiz ? it.tr_w : it.tr_h);
-  if (threadIdx.x < sizeof(aa_table_header) / 4) {
-    ((int32_t *)tab)[threadIdx.x] = 0;
-    if (adjoints) ((int32_t *)tr)[threadIdx.x] = 0;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < out_size; i += AA_EMBED_THREADS) table_build_f32_one(i, filter, in_size, out_size, ksize, scale, tab);
-  if (!adjoints) return;
-  __threadfence();
-  __syncthreads();
-  int32_t *tmin = (int32_t *)(tr + aa_table_xmin_off()), *tsize = (int32_t *)(tr + aa_table_xsize_off(in_size));
-  float *tw = (float *)(tr + aa_table_w_off(in_size));
-  for (int x = threadIdx.x; x < in_size; x += AA_EMBED_THREADS)
-    table_transpose_one<float>(x, tab, tmin, tsize, tw, &((aa_table_header *)tr)->max_taps, out_size, ksize, trk);
+  const TableAxis ax = {horiz ? W0 : H0, horiz ? it.gw : it.gh, horiz ? it.ksize_w : it.ksize_h, horiz ? it.trk_w : it.trk_h,
+                        horiz ? it.scale_w : it.scale_h, ws + (horiz ? it.tab_w : it.tab_h), ws + (horiz ? it.tr_w : it.tr_h)};
+  table_axis_build<AA_EMBED_THREADS>(ax, filter, adjoints);
 }
 
 // ---- the sum both directions share ---------------------------------------------------------------------------------------------------------
-__device__ inline float to_f32(float x) { return x; }
-__device__ inline float to_f32(f16_t x) { return (float)x.v; }
-__device__ inline float to_f32(bf16_t x) { return __uint_as_float((unsigned)x.v << 16); }
-
-template <typename T, int V> struct alignas(sizeof(T) * V) Vec { T v[V]; };
-
-// A table row: the window [x0, x0 + n) and its weights.  n is max(xsize, 1), as in aa_generic.hip (tap 0 is read unconditionally; a
-// row without taps has weight 0 there), never more than a weight row holds, and the window is kept inside [0, in_size) (never moved:
-// the tables clip their windows to the axis).
-struct Row { int x0, n; const float *w; };
-__device__ inline Row table_row(const char *tab, int in_size, int out_size, int ksize, int i) {
-  const TableView<float> tv = make_table_view<float>(tab, out_size, ksize);
-  int n = tv.xsize[i];
-  n = n > 1 ? (n < ksize ? n : ksize) : 1;
-  int x0 = tv.xmin[i];
-  if (x0 > in_size - n) x0 = in_size - n;
-  if (x0 < 0) x0 = 0;
-  return {x0, n, tv.w + (size_t)i * ksize};
-}
-
+// (aa_float_many_dev.h's class_sums<T, V, true> is this sum, but through it the float16-input kernels compile to other code, embed_bwd
+// 62 -> 53 VGPRs and embed_fwd 40 -> 33: profiles/float_ragged_shared_refactor.txt.  So this file keeps its own.)
 // acc = the vertical sum over ry's window of the horizontal sums over rx's window, for V channels from p = element (row ry.x0, pixel
 // rx.x0, the lane's first channel); rows `prow` and pixels `ppx` elements apart.  hs is the fp32 intermediate of the two-pass form.
 template <typename T, int V>
@@ -187,19 +154,11 @@ template <typename TIn, typename TOut, int V> void launch_as(bool bwd, const Emb
   if (bwd) hipLaunchKernelGGL((embed_bwd<TIn, TOut, V>), dim3((unsigned)((a.jobs + kBwdLanes - 1) / kBwdLanes)), dim3(kBwdLanes * kBwdSlots), 0, stream, a);
   else hipLaunchKernelGGL((embed_fwd<TIn, TOut, V>), dim3((unsigned)((a.jobs + AA_EMBED_THREADS - 1) / AA_EMBED_THREADS)), dim3(AA_EMBED_THREADS), 0, stream, a);
 }
-template <typename TIn, int V> void launch_out(int out_dtype, bool bwd, const EmbedArgs &a, hipStream_t stream) {
-  if (out_dtype == AA_F32) launch_as<TIn, float, V>(bwd, a, stream);
-  else if (out_dtype == AA_F16) launch_as<TIn, f16_t, V>(bwd, a, stream);
-  else launch_as<TIn, bf16_t, V>(bwd, a, stream);
-}
 template <int V> void launch_in(int in_dtype, int out_dtype, bool bwd, const EmbedArgs &a, hipStream_t stream) {
-  if (in_dtype == AA_F32) launch_out<float, V>(out_dtype, bwd, a, stream);
-  else if (in_dtype == AA_F16) launch_out<f16_t, V>(out_dtype, bwd, a, stream);
-  else launch_out<bf16_t, V>(out_dtype, bwd, a, stream);
+  with_float_type(in_dtype, [&](auto in) {
+    with_float_type(out_dtype, [&](auto out) { launch_as<tag_t<decltype(in)>, tag_t<decltype(out)>, V>(bwd, a, stream); });
+  });
 }
-
-inline bool float_dtype(int dt) { return dt == AA_F32 || dt == AA_F16 || dt == AA_BF16; }
-inline size_t elem_bytes(int dt) { return dt == AA_F32 ? 4 : 2; }
 
 }  // namespace
 
@@ -226,19 +185,9 @@ int aa_embed_plan_host(int filter, int64_t n, int64_t D, int64_t H0, int64_t W0,
     AAEmbedItem it;
     memset(&it, 0, sizeof(it));
     it.gh = (int32_t)gh; it.gw = (int32_t)gw;
-    const int kh = aa_table_ksize(filter, AA_TABLE_F32, H0, gh, 0, 0.0), kw = aa_table_ksize(filter, AA_TABLE_F32, W0, gw, 0, 0.0);
-    if (kh < 0) return kh;
-    if (kw < 0) return kw;
-    const int th = aa_table_transposed_ksize(filter, AA_TABLE_F32, H0, gh, 0, 0.0), tw = aa_table_transposed_ksize(filter, AA_TABLE_F32, W0, gw, 0, 0.0);
-    if (th < 0) return th;
-    if (tw < 0) return tw;
-    it.ksize_h = kh; it.ksize_w = kw; it.trk_h = th; it.trk_w = tw;
-    it.scale_h = (float)H0 / (float)gh;
-    it.scale_w = (float)W0 / (float)gw;
-    it.tab_h = (int64_t)off; off += aa_table_weights_end(AA_TABLE_F32, gh, kh);
-    it.tab_w = (int64_t)off; off += aa_table_weights_end(AA_TABLE_F32, gw, kw);
-    it.tr_h = (int64_t)off; off += aa_table_weights_end(AA_TABLE_F32, H0, th);
-    it.tr_w = (int64_t)off; off += aa_table_weights_end(AA_TABLE_F32, W0, tw);
+    int rc = plan_forward_tables(filter, H0, W0, gh, gw, it, off);
+    if (rc == AA_OK) rc = plan_adjoint_tables(filter, H0, W0, gh, gw, it, off);
+    if (rc != AA_OK) return rc;
     items[i] = it;
     tok0[i] = rows;
     rows += gh * gw;

@@ -19,87 +19,26 @@
 // The merged call (aa_back_merged_plan) runs the same two launches with back_resample_merged in place of back_resample: the items are
 // members of groups, a work unit is an output row of a GROUP, and a class's value is the members' values added in order before the
 // epilogue sees it (at "2'." below).
-// Shared with the other ragged calls: aa_many_dev.h (the item of a unit, the element types), aa_many_host.h (the block, the launch checks).
+// Shared with the other ragged calls: aa_many_dev.h (the item of a unit, the element types), aa_many_host.h (the block, the launch checks);
+// with the other float ragged calls: aa_float_many_dev.h (the table kernels' body, table_row, class_sums), aa_float_many_host.h (the
+// float types, the tables of an item in a plan).
 
 #include <string.h>
 
 #include "aa_many_back.h"
-#include "aa_many_dev.h"
-#include "aa_many_host.h"
-#include "aa_table_rows.h"
+#include "aa_float_many_dev.h"
+#include "aa_float_many_host.h"
 
 namespace {
 
 // ---- 1. tables ---------------------------------------------------------------------------------------------------------------------------
-// Workgroup 2 i builds item i's H axis, 2 i + 1 its W axis, as embed_tables does without adjoints.  A table's header is zeroed first: the
-// row function keeps max_taps there, and nobody reads that field back.
+// Workgroup 2 i builds item i's H axis, 2 i + 1 its W axis: the shared body without adjoints (the record has none).
 __global__ void __launch_bounds__(AA_BACK_THREADS) back_tables(const AABackItem *items, char *ws, int filter) {
   const AABackItem &it = items[blockIdx.x >> 1];
   const bool horiz = blockIdx.x & 1;
-  const int in_size = horiz ? it.w : it.h, out_size = horiz ? it.ow : it.oh;
-  const int ksize = horiz ? it.ksize_w : it.ksize_h;
-  const float scale = horiz ? it.scale_w : it.scale_h;
-  char *tab = ws + (horiz ? it.tab_w : it.tab_h);
-  if (threadIdx.x < sizeof(aa_table_header) / 4) ((int32_t *)tab)[threadIdx.x] = 0;
-  __syncthreads();
-  for (int i = threadIdx.x; i < out_size; i += AA_BACK_THREADS) table_build_f32_one(i, filter, in_size, out_size, ksize, scale, tab);
-}
-
-// ---- the sums ------------------------------------------------------------------------------------------------------------------------------
-__device__ inline float to_f32(float x) { return x; }
-__device__ inline float to_f32(f16_t x) { return (float)x.v; }
-__device__ inline float to_f32(bf16_t x) { return __uint_as_float((unsigned)x.v << 16); }
-
-template <typename T, int V> struct alignas(sizeof(T) * V) Vec { T v[V]; };
-
-// A table row, as aa_embed_many.hip's table_row reads it: the window [x0, x0 + n) and its weights.  n is max(xsize, 1) (tap 0 is read
-// unconditionally; a row without taps has weight 0 there), never more than a weight row holds, and the window is kept inside
-// [0, in_size): nothing outside an item's region is read.
-struct Row { int x0, n; const float *w; };
-__device__ inline Row table_row(const char *tab, int in_size, int out_size, int ksize, int i) {
-  const TableView<float> tv = make_table_view<float>(tab, out_size, ksize);
-  int n = tv.xsize[i];
-  n = n > 1 ? (n < ksize ? n : ksize) : 1;
-  int x0 = tv.xmin[i];
-  if (x0 > in_size - n) x0 = in_size - n;
-  if (x0 < 0) x0 = 0;
-  return {x0, n, tv.w + (size_t)i * ksize};
-}
-
-// V classes of one pixel from p: one vector (VEC: consecutive classes at an address that allows it) or V loads `sch` elements apart.
-template <typename T, int V, bool VEC> __device__ inline void load_classes(const T *p, int64_t sch, float (&e)[V]) {
-  if constexpr (VEC) {
-    const Vec<T, V> r = *(const Vec<T, V> *)p;
-#pragma unroll
-    for (int c = 0; c < V; c++) e[c] = to_f32(r.v[c]);
-  } else {
-#pragma unroll
-    for (int c = 0; c < V; c++) e[c] = to_f32(p[c * sch]);
-  }
-}
-
-// acc = the vertical sum over ry's window of the horizontal sums over rx's window, for V classes from p = element (the lane's first
-// class, row ry.x0, pixel rx.x0); classes `sch`, rows `prow` and pixels `ppx` elements apart.  hs is the fp32 intermediate of the
-// two-pass form; the operations and their order are aa_embed_many.hip's window_sums.  A weight is read once for the V classes.
-template <typename T, int V, bool VEC>
-__device__ inline void class_sums(const T *p, int64_t sch, int64_t prow, int64_t ppx, const Row &ry, const Row &rx, float (&acc)[V]) {
-  for (int j = 0; j < ry.n; j++) {
-    const T *rp = p + j * prow;
-    float hs[V], e[V];
-    load_classes<T, V, VEC>(rp, sch, e);
-    const float w0 = rx.w[0];
-#pragma unroll
-    for (int c = 0; c < V; c++) hs[c] = e[c] * w0;
-    for (int k = 1; k < rx.n; k++) {
-      load_classes<T, V, VEC>(rp + k * ppx, sch, e);
-      const float wk = rx.w[k];
-#pragma unroll
-      for (int c = 0; c < V; c++) hs[c] = hs[c] + e[c] * wk;
-    }
-    const float wj = ry.w[j];
-#pragma unroll
-    for (int c = 0; c < V; c++) acc[c] = j == 0 ? hs[c] * wj : acc[c] + hs[c] * wj;
-  }
+  const TableAxis ax = {horiz ? it.w : it.h, horiz ? it.ow : it.oh, horiz ? it.ksize_w : it.ksize_h, 0, horiz ? it.scale_w : it.scale_h,
+                        ws + (horiz ? it.tab_w : it.tab_h), nullptr};
+  table_axis_build<AA_BACK_THREADS>(ax, filter, 0);
 }
 
 // ---- the epilogues -------------------------------------------------------------------------------------------------------------------------
@@ -255,25 +194,12 @@ template <typename TIn, bool VEC, typename Args> void launch_epi(int reduce, int
     else if (out_dtype == AA_I16) launch_as<TIn, VEC, Argmax<int16_t>>(a, units, stream);
     else if (out_dtype == AA_I32) launch_as<TIn, VEC, Argmax<int32_t>>(a, units, stream);
     else launch_as<TIn, VEC, Argmax<int64_t>>(a, units, stream);
-  } else if (out_dtype == AA_F32) launch_as<TIn, VEC, Values<float>>(a, units, stream);
-  else if (out_dtype == AA_F16) launch_as<TIn, VEC, Values<f16_t>>(a, units, stream);
-  else launch_as<TIn, VEC, Values<bf16_t>>(a, units, stream);
+  } else with_float_type(out_dtype, [&](auto out) { launch_as<TIn, VEC, Values<tag_t<decltype(out)>>>(a, units, stream); });
 }
 template <bool VEC, typename Args> void launch_in(int in_dtype, int reduce, int out_dtype, const Args &a, unsigned units, hipStream_t stream) {
-  if (in_dtype == AA_F32) launch_epi<float, VEC>(reduce, out_dtype, a, units, stream);
-  else if (in_dtype == AA_F16) launch_epi<f16_t, VEC>(reduce, out_dtype, a, units, stream);
-  else launch_epi<bf16_t, VEC>(reduce, out_dtype, a, units, stream);
+  with_float_type(in_dtype, [&](auto in) { launch_epi<tag_t<decltype(in)>, VEC>(reduce, out_dtype, a, units, stream); });
 }
 
-inline bool float_dtype(int dt) { return dt == AA_F32 || dt == AA_F16 || dt == AA_BF16; }
-inline size_t elem_bytes(int dt) {
-  switch (dt) {
-    case AA_U8: case AA_BOOL: return 1;
-    case AA_F16: case AA_BF16: case AA_I16: return 2;
-    case AA_I64: return 8;
-    default: return 4;
-  }
-}
 // What a reduction stores: values a float, argmax a label, greater a byte of 0 or 1.
 inline bool out_dtype_ok(int reduce, int dt) {
   if (reduce == AA_BACK_VALUES) return float_dtype(dt);
@@ -308,14 +234,8 @@ inline int plan_item(int filter, int layout, int64_t K, const aa_back_item &im, 
   it.stride_row = im.h > 1 ? im.stride_row : 0;
   it.stride_px = im.w > 1 ? im.stride_px : 0;
   it.h = (int32_t)im.h; it.w = (int32_t)im.w; it.oh = (int32_t)im.oh; it.ow = (int32_t)im.ow;
-  const int kh = aa_table_ksize(filter, AA_TABLE_F32, im.h, im.oh, 0, 0.0), kw = aa_table_ksize(filter, AA_TABLE_F32, im.w, im.ow, 0, 0.0);
-  if (kh < 0) return kh;
-  if (kw < 0) return kw;
-  it.ksize_h = kh; it.ksize_w = kw;
-  it.scale_h = (float)im.h / (float)im.oh;
-  it.scale_w = (float)im.w / (float)im.ow;
-  it.tab_h = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.oh, kh);
-  it.tab_w = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.ow, kw);
+  const int rc = plan_forward_tables(filter, im.h, im.w, im.oh, im.ow, it, ws);
+  if (rc != AA_OK) return rc;
   it.flags = im.flags;
   it.xtiles = (int32_t)((im.ow + AA_BACK_TILE - 1) / AA_BACK_TILE);
   return AA_OK;

@@ -5,9 +5,9 @@
 // round-to-nearest-even at the store; outside it, and for an item without a gradient, +0.0.  No atomics.  Two launches whatever N and
 // whatever the sizes:
 //   1. back_bwd_tables  one workgroup per (item, axis): the rows of the item's forward table (table_build_f32_one), a barrier, the rows
-//                       of its adjoint (table_transpose_one) — embed_tables' body with the source size per item (aa_table_rows.h's
-//                       device functions, so the tables are the bits aa_table_build and aa_table_transpose give the shape).  An item
-//                       without a gradient has no tables: its two workgroups leave at once;
+//                       of its adjoint (table_transpose_one) — the body embed_tables runs, with the source size per item
+//                       (aa_table_rows.h's device functions, so the tables are the bits aa_table_build and aa_table_transpose give the
+//                       shape).  An item without a gradient has no tables: its two workgroups leave at once;
 //   2. back_bwd_gather  one workgroup per work unit, AA_BACK_BWD_ROWS x AA_BACK_BWD_COLS cells of an item's CANVAS, a lane per cell, a
 //                       wave per canvas row.  The units of an item tile its whole canvas, so this one kernel writes every element of
 //                       the output: a cell outside the region stores K zeros, a cell inside it the K sums.  A cell's sums are the
@@ -22,86 +22,27 @@
 // chunk loop of its own; that form was not built, and the strided scalar loads are what bounds this kernel.
 // A flipped item reads gradient column ow - 1 - c for column c.  Every element offset is 64-bit.  Stores are one element a lane, so an
 // output on any element boundary is served and the 16-byte gaps between the items of an arena are never written.
-// Shared with the other ragged calls: aa_many_dev.h (the item of a unit, the element types), aa_many_host.h (the block, the launch checks).
+// Shared with the other ragged calls: aa_many_dev.h (the item of a unit, the element types), aa_many_host.h (the block, the launch checks);
+// with the other float ragged calls: aa_float_many_dev.h (the table kernels' body, table_row, class_sums), aa_float_many_host.h (the
+// float types, the tables of an item in a plan).
 
 #include <string.h>
 
 #include "aa_many_back_bwd.h"
-#include "aa_many_dev.h"
-#include "aa_many_host.h"
-#include "aa_table_rows.h"
+#include "aa_float_many_dev.h"
+#include "aa_float_many_host.h"
 
 namespace {
 
 // ---- 1. tables ---------------------------------------------------------------------------------------------------------------------------
-// Workgroup 2 i builds item i's H axis, 2 i + 1 its W axis.  A table's header is zeroed first: the row functions keep max_taps there.
-// Nobody reads that field back; the adjoint rows hold aa_table_transposed_ksize's estimate of entries, as in aa_embed_many.hip.
-// (Like embed_tables, whose body this is, the kernel keeps a few scalar registers in vector lanes across the two loops — 6 here, 8
-// there; nothing goes to scratch memory.  The body is repeated, not shared: moving it into a header would recompile embed_tables.)
+// Workgroup 2 i builds item i's H axis, 2 i + 1 its W axis: the shared body with adjoints, the source size per item.
 __global__ void __launch_bounds__(AA_BACK_BWD_THREADS) back_bwd_tables(const AABackBwdItem *items, char *ws, int filter) {
   const AABackBwdItem &it = items[blockIdx.x >> 1];
   if (!it.grad) return;  // (uniform per workgroup: before every barrier)
   const bool horiz = blockIdx.x & 1;
-  const int in_size = horiz ? it.w : it.h, out_size = horiz ? it.ow : it.oh;
-  const int ksize = horiz ? it.ksize_w : it.ksize_h, trk = horiz ? it.trk_w : it.trk_h;
-  const float scale = horiz ? it.scale_w : it.scale_h;
-  char *tab = ws + (horiz ? it.tab_w : it.tab_h), *tr = ws + (horiz ? it.tr_w : it.tr_h);
-  if (threadIdx.x < sizeof(aa_table_header) / 4) {
-    ((int32_t *)tab)[threadIdx.x] = 0;
-    ((int32_t *)tr)[threadIdx.x] = 0;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < out_size; i += AA_BACK_BWD_THREADS) table_build_f32_one(i, filter, in_size, out_size, ksize, scale, tab);
-  __threadfence();
-  __syncthreads();
-  int32_t *tmin = (int32_t *)(tr + aa_table_xmin_off()), *tsize = (int32_t *)(tr + aa_table_xsize_off(in_size));
-  float *tw = (float *)(tr + aa_table_w_off(in_size));
-  for (int x = threadIdx.x; x < in_size; x += AA_BACK_BWD_THREADS)
-    table_transpose_one<float>(x, tab, tmin, tsize, tw, &((aa_table_header *)tr)->max_taps, out_size, ksize, trk);
-}
-
-// ---- the sums ------------------------------------------------------------------------------------------------------------------------------
-__device__ inline float to_f32(float x) { return x; }
-__device__ inline float to_f32(f16_t x) { return (float)x.v; }
-__device__ inline float to_f32(bf16_t x) { return __uint_as_float((unsigned)x.v << 16); }
-
-// A table row, as aa_embed_many.hip's table_row reads it: the window [x0, x0 + n) and its weights.  n is max(xsize, 1) (tap 0 is read
-// unconditionally; a row without taps has weight 0 there), never more than a weight row holds, and the window is kept inside
-// [0, in_size): nothing outside a gradient is read.  For an adjoint table in_size is the gradient's side and out_size the region's.
-struct Row { int x0, n; const float *w; };
-__device__ inline Row table_row(const char *tab, int in_size, int out_size, int ksize, int i) {
-  const TableView<float> tv = make_table_view<float>(tab, out_size, ksize);
-  int n = tv.xsize[i];
-  n = n > 1 ? (n < ksize ? n : ksize) : 1;
-  int x0 = tv.xmin[i];
-  if (x0 > in_size - n) x0 = in_size - n;
-  if (x0 < 0) x0 = 0;
-  return {x0, n, tv.w + (size_t)i * ksize};
-}
-
-// acc = the vertical sum over ry's window of the horizontal sums over rx's window, for V classes from p = element (the lane's first
-// class, gradient row ry.x0, the column of tap 0 of rx); classes `sch` and rows `prow` elements apart, the column of tap k at k * ppx
-// (1, or -1 for a flipped item).  hs is the fp32 intermediate of the two-pass form; the operations and their order are
-// aa_embed_many.hip's window_sums.  The loops run over the taps: no array is sized by a longest row.  A weight is read once for the V
-// classes.
-template <typename T, int V>
-__device__ inline void class_sums(const T *p, int64_t sch, int64_t prow, int64_t ppx, const Row &ry, const Row &rx, float (&acc)[V]) {
-  for (int j = 0; j < ry.n; j++) {
-    const T *rp = p + j * prow;
-    float hs[V];
-    const float w0 = rx.w[0];
-#pragma unroll
-    for (int c = 0; c < V; c++) hs[c] = to_f32(rp[c * sch]) * w0;
-    for (int k = 1; k < rx.n; k++) {
-      const T *cp = rp + k * ppx;
-      const float wk = rx.w[k];
-#pragma unroll
-      for (int c = 0; c < V; c++) hs[c] = hs[c] + to_f32(cp[c * sch]) * wk;
-    }
-    const float wj = ry.w[j];
-#pragma unroll
-    for (int c = 0; c < V; c++) acc[c] = j == 0 ? hs[c] * wj : acc[c] + hs[c] * wj;
-  }
+  const TableAxis ax = {horiz ? it.w : it.h, horiz ? it.ow : it.oh, horiz ? it.ksize_w : it.ksize_h, horiz ? it.trk_w : it.trk_h,
+                        horiz ? it.scale_w : it.scale_h, ws + (horiz ? it.tab_w : it.tab_h), ws + (horiz ? it.tr_w : it.tr_h)};
+  table_axis_build<AA_BACK_BWD_THREADS>(ax, filter, 1);
 }
 
 struct BwdArgs {
@@ -140,13 +81,13 @@ __global__ void __launch_bounds__(AA_BACK_BWD_THREADS) back_bwd_gather(BwdArgs a
   int k = 0;
   for (; k + U <= a.K; k += U) {
     float acc[U];
-    class_sums<TG, U>(p + k * sch, sch, prow, ppx, ry, rx, acc);
+    class_sums<TG, U, false>(p + k * sch, sch, prow, ppx, ry, rx, acc);
 #pragma unroll
     for (int c = 0; c < U; c++) o[(k + c) * kstep] = to_elem<TOut>(acc[c]);
   }
   for (; k < a.K; k++) {
     float acc[1];
-    class_sums<TG, 1>(p + k * sch, sch, prow, ppx, ry, rx, acc);
+    class_sums<TG, 1, false>(p + k * sch, sch, prow, ppx, ry, rx, acc);
     o[k * kstep] = to_elem<TOut>(acc[0]);
   }
 }
@@ -155,14 +96,6 @@ template <typename TG, typename TOut> void launch_as(bool nhwc, const BwdArgs &a
   if (nhwc) hipLaunchKernelGGL((back_bwd_gather<TG, TOut, true>), dim3(units), dim3(AA_BACK_BWD_THREADS), 0, stream, a);
   else hipLaunchKernelGGL((back_bwd_gather<TG, TOut, false>), dim3(units), dim3(AA_BACK_BWD_THREADS), 0, stream, a);
 }
-template <typename TG> void launch_out(int out_dtype, bool nhwc, const BwdArgs &a, unsigned units, hipStream_t stream) {
-  if (out_dtype == AA_F32) launch_as<TG, float>(nhwc, a, units, stream);
-  else if (out_dtype == AA_F16) launch_as<TG, f16_t>(nhwc, a, units, stream);
-  else launch_as<TG, bf16_t>(nhwc, a, units, stream);
-}
-
-inline bool float_dtype(int dt) { return dt == AA_F32 || dt == AA_F16 || dt == AA_BF16; }
-inline size_t elem_bytes(int dt) { return dt == AA_F32 ? 4 : 2; }
 
 }  // namespace
 
@@ -201,19 +134,9 @@ int aa_back_bwd_plan_host(int filter, int out_layout, int64_t n, int64_t K, cons
       it.y0 = (int32_t)im.y0; it.x0 = (int32_t)im.x0; it.h = (int32_t)im.h; it.w = (int32_t)im.w;
       it.oh = (int32_t)im.oh; it.ow = (int32_t)im.ow;
       it.flags = im.flags;
-      const int kh = aa_table_ksize(filter, AA_TABLE_F32, im.h, im.oh, 0, 0.0), kw = aa_table_ksize(filter, AA_TABLE_F32, im.w, im.ow, 0, 0.0);
-      if (kh < 0) return kh;
-      if (kw < 0) return kw;
-      const int th = aa_table_transposed_ksize(filter, AA_TABLE_F32, im.h, im.oh, 0, 0.0), tw = aa_table_transposed_ksize(filter, AA_TABLE_F32, im.w, im.ow, 0, 0.0);
-      if (th < 0) return th;
-      if (tw < 0) return tw;
-      it.ksize_h = kh; it.ksize_w = kw; it.trk_h = th; it.trk_w = tw;
-      it.scale_h = (float)im.h / (float)im.oh;
-      it.scale_w = (float)im.w / (float)im.ow;
-      it.tab_h = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.oh, kh);
-      it.tab_w = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.ow, kw);
-      it.tr_h = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.h, th);
-      it.tr_w = (int64_t)ws; ws += aa_table_weights_end(AA_TABLE_F32, im.w, tw);
+      int rc = plan_forward_tables(filter, im.h, im.w, im.oh, im.ow, it, ws);
+      if (rc == AA_OK) rc = plan_adjoint_tables(filter, im.h, im.w, im.oh, im.ow, it, ws);
+      if (rc != AA_OK) return rc;
     }
     it.xtiles = (int32_t)((im.W + AA_BACK_BWD_COLS - 1) / AA_BACK_BWD_COLS);
     if (!dense) out = aa_align16(out);
@@ -264,9 +187,9 @@ int aa_launch_back_many_bwd(const void *desc_host, const void *desc_dev, int gra
   a.items = v.items; a.unit0 = v.prefix; a.ws = (const char *)workspace_dev; a.out = (char *)out_dev;
   a.n = hd->n; a.K = hd->K;
   const bool nhwc = hd->out_layout == AA_NHWC;
-  if (grad_dtype == AA_F32) launch_out<float>(hd->out_dtype, nhwc, a, (unsigned)hd->units, stream);
-  else if (grad_dtype == AA_F16) launch_out<f16_t>(hd->out_dtype, nhwc, a, (unsigned)hd->units, stream);
-  else launch_out<bf16_t>(hd->out_dtype, nhwc, a, (unsigned)hd->units, stream);
+  with_float_type(grad_dtype, [&](auto g) {
+    with_float_type(hd->out_dtype, [&](auto o) { launch_as<tag_t<decltype(g)>, tag_t<decltype(o)>>(nhwc, a, (unsigned)hd->units, stream); });
+  });
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }

@@ -10,8 +10,11 @@ Run by hand, with that commit's library (no GPU, no Pillow):
 The committed file was made with the library built from commit 467775f ("Add resize_many_nearest"), the parent of the change that
 moved the planners' shared checks into csrc/aa_many_host.h; the groups maps, ycbcr, err/maps and err/ycbcr were added with the library
 built from commit b3940fe ("Add resize_many_ycbcr"), the parent of the change that gave the ragged kernels one device header
-(csrc/aa_many_dev.h), and every older key came out of that library byte-equal to what was committed.  main() enumerates twice and asserts that both runs agree: the blocks are
-zero-initialised and the planners memset their records, so the bytes do not depend on what the memory held."""
+(csrc/aa_many_dev.h), and every older key came out of that library byte-equal to what was committed; the groups embed, back, merged,
+back_bwd and their err/ groups were added with the library built from commit b51284d ("Add resize_many_back_merged"), the parent of
+the change that gave the float ragged calls their shared headers (csrc/aa_float_many_dev.h, csrc/aa_float_many_host.h), again with
+every older key byte-equal.  main() enumerates twice and asserts that both runs agree: the blocks are zero-initialised and the planners
+memset their records, so the bytes do not depend on what the memory held."""
 import hashlib
 import json
 import os

@@ -1,6 +1,7 @@
 """Shared by the frozen-plan test and its generator (tests/golden/make_golden_many_plans.py): every plan the host planners of the ragged
 calls write for the cases of the ragged fixtures, through the C-ABI with fake device pointers (a plan is host arithmetic: the pointers
-are never dereferenced), and a handful of literal error inputs per planner.  plans() yields (key, rc, workspace bytes, descriptor
+are never dereferenced), for the float ragged calls (embed, back, merged, back_bwd) the cases of their CPU restatements
+(resize_embed_ref.py, resize_many_back*_ref.py), and literal error inputs per planner.  plans() yields (key, rc, workspace bytes, descriptor
 bytes); the block is a zero-initialised buffer and the planners memset their records, so the bytes are deterministic.  Nothing here
 says what a plan should hold: tests/golden/many_plans.json records what the planners wrote before they were restructured.  Not a test
 module."""
@@ -147,6 +148,167 @@ def plan_reduce(layout, c, recs, n, nbytes=None):
     offs = (ctypes.c_int64 * max(n, 1))()
     return _planned(L.aa_reduce_many_desc_bytes(n) if nbytes is None else nbytes,
                     lambda b, nb, ws: L.aa_reduce_many_plan(layout, n, c, recs, b, nb, ws, offs), lambda: bytes(offs))
+
+
+# ---- the float ragged calls: one position grid to N token grids, canvas predictions back to N sizes (merged or not), its backward ------
+FILTERS5 = ("linear", "cubic", "box", "hamming", "lanczos")
+# (reduce, out_dtype) as aa_back_many_plan takes them: values a float, argmax a label, greater a byte
+BACK_OUT = ([("values", _lib.BACK_VALUES, n, d) for n, d in (("f32", _lib.F32), ("f16", _lib.F16), ("bf16", _lib.BF16))] +
+            [("argmax", _lib.BACK_ARGMAX, n, d) for n, d in (("u8", _lib.U8), ("i16", _lib.I16), ("i32", _lib.I32), ("i64", _lib.I64))] +
+            [("greater", _lib.BACK_GREATER, n, d) for n, d in (("bool", _lib.BOOL), ("u8", _lib.U8))])
+
+
+def _fid(f):
+    return _lib.FILTER_IDS[f] if isinstance(f, str) else f
+
+
+def _or_null(null, **named):
+    """The named arguments, None for those listed in `null`."""
+    return [None if k in null else v for k, v in named.items()]
+
+
+def plan_embed(f, d, h0, w0, grids, pad_to=0, n=None, nbytes=None, null=()):
+    """aa_embed_many_plan; the rows it reports follow the block."""
+    L = _lib.load()
+    n = len(grids) if n is None else n
+    flat = (ctypes.c_int64 * max(2 * len(grids), 1))(*[v for g in grids for v in g])
+    rows = ctypes.c_int64(-1)
+
+    def call(b, nb, ws):
+        flat_, b_, ws_, rows_ = _or_null(null, grids=flat, desc=b, ws=ws, rows=ctypes.byref(rows))
+        return L.aa_embed_many_plan(_fid(f), n, d, h0, w0, flat_, pad_to, b_, nb, ws_, rows_)
+    return _planned(L.aa_embed_many_desc_bytes(max(n, 0)) if nbytes is None else nbytes, call, lambda: struct.pack("<q", rows.value))
+
+
+def back_items(layout, k, geo, ptr=1 << 20):
+    """geo [((H, W) of the source, (y0, x0, h, w) or None, (oh, ow), flip)] -> aa_back_item records of dense [K, H, W] sources in
+    `layout`'s class, data_dev at the region's corner."""
+    recs = (_lib.BackItemIn * max(len(geo), 1))()
+    for i, ((hh, ww), region, (oh, ow), flip) in enumerate(geo):
+        y0, x0, h, w = (0, 0, hh, ww) if region is None else region
+        r = recs[i]
+        r.stride_ch, r.stride_row, r.stride_px = (1, ww * k, k) if layout == _lib.NHWC else (hh * ww, ww, 1)
+        r.data_dev = ptr + 65536 * i + 4 * (y0 * r.stride_row + x0 * r.stride_px)
+        r.h, r.w, r.oh, r.ow, r.flags = h, w, oh, ow, FLIP if flip else 0
+    return recs
+
+
+def _two_sizes(call, nbytes, n_offs):
+    """A planner that reports a second size and n_offs offsets besides the block: both follow the block."""
+    second = ctypes.c_size_t(0)
+    offs = (ctypes.c_int64 * max(n_offs, 1))()
+    return _planned(nbytes, lambda b, nb, ws: call(b, nb, ws, second, offs), lambda: struct.pack("<Q", second.value) + bytes(offs))
+
+
+def plan_back(f, layout, k, recs, n, reduce=_lib.BACK_VALUES, out_dtype=_lib.F32, nbytes=None, null=()):
+    """aa_back_many_plan; the arena's bytes and the items' offsets into it follow the block."""
+    L = _lib.load()
+
+    def call(b, nb, ws, arena, offs):
+        recs_, b_, ws_, arena_, offs_ = _or_null(null, items=recs, desc=b, ws=ws, arena=ctypes.byref(arena), offs=offs)
+        return L.aa_back_many_plan(_fid(f), layout, n, k, recs_, reduce, out_dtype, b_, nb, ws_, arena_, offs_)
+    return _two_sizes(call, L.aa_back_many_desc_bytes(max(n, 0)) if nbytes is None else nbytes, n)
+
+
+def plan_merged(f, layout, k, recs, n, groups, g, merge=0, reduce=_lib.BACK_VALUES, out_dtype=_lib.F32, nbytes=None, null=()):
+    """aa_back_merged_plan; the arena's bytes and the groups' offsets into it follow the block."""
+    L = _lib.load()
+    group_of = (ctypes.c_int64 * max(len(groups), 1))(*groups)
+
+    def call(b, nb, ws, arena, offs):
+        recs_, group_, b_, ws_, arena_, offs_ = _or_null(null, items=recs, groups=group_of, desc=b, ws=ws, arena=ctypes.byref(arena), offs=offs)
+        return L.aa_back_merged_plan(_fid(f), layout, n, k, recs_, g, group_, merge, reduce, out_dtype, b_, nb, ws_, arena_, offs_)
+    return _two_sizes(call, L.aa_back_merged_desc_bytes(max(n, 0), max(g, 0)) if nbytes is None else nbytes, g)
+
+
+def back_bwd_items(k, geo, ptr=1 << 20):
+    """geo [((H, W) of the canvas, (y0, x0, h, w) or None, (oh, ow), flip, has a gradient)] -> aa_back_bwd_item records of dense
+    [K, oh, ow] gradients; an item without one has grad_dev None and nothing but its canvas."""
+    recs = (_lib.BackBwdItemIn * max(len(geo), 1))()
+    for i, ((hh, ww), region, (oh, ow), flip, has) in enumerate(geo):
+        r = recs[i]
+        r.H, r.W = hh, ww
+        if has:
+            r.grad_dev = ptr + 65536 * i
+            r.stride_ch, r.stride_row = oh * ow, ow
+            r.y0, r.x0, r.h, r.w = (0, 0, hh, ww) if region is None else region
+            r.oh, r.ow, r.flags = oh, ow, FLIP if flip else 0
+    return recs
+
+
+def plan_back_bwd(f, layout, k, recs, n, out_dtype=_lib.F32, dense=0, nbytes=None, null=()):
+    """aa_back_many_bwd_plan; the output's bytes and the items' offsets into it follow the block."""
+    L = _lib.load()
+
+    def call(b, nb, ws, out, offs):
+        recs_, b_, ws_, out_, offs_ = _or_null(null, items=recs, desc=b, ws=ws, out=ctypes.byref(out), offs=offs)
+        return L.aa_back_many_bwd_plan(_fid(f), layout, n, k, recs_, out_dtype, dense, b_, nb, ws_, out_, offs_)
+    return _two_sizes(call, L.aa_back_many_bwd_desc_bytes(max(n, 0)) if nbytes is None else nbytes, n)
+
+
+def _float_case_plans():
+    import resize_embed_ref as embed_ref
+    import resize_many_back_bwd_ref as bwd_ref
+    import resize_many_back_merged_ref as merged_ref
+    import resize_many_back_ref as back_ref
+
+    for name, (h0, w0), grids in [("base", embed_ref.BASE_SOURCE, embed_ref.BASE_GRIDS)] + [(k,) + v for k, v in embed_ref.FURTHER.items()]:
+        longest = max(gh * gw for gh, gw in grids)
+        for f in FILTERS5:
+            for pad_to in (0, longest + 3):
+                for d in (8, 523):
+                    yield f"embed/{name}/{f}/{'pad' if pad_to else 'packed'}/d{d}", plan_embed(f, d, h0, w0, grids, pad_to)
+
+    def batch(canvas, regions, sizes):  # every item a region of its own slice of one [N, K, H, W] batch
+        return canvas.shape[1], [(tuple(canvas.shape[2:]), r, s, i % 2 == 1) for i, (r, s) in enumerate(zip(regions, sizes))]
+
+    srcs, regions, sizes = back_ref.list_case()
+    back_cases = {"base": batch(back_ref.BASE_CANVAS, back_ref.BASE_REGIONS, back_ref.BASE_SIZES), "k300": batch(*back_ref.k300_case()),
+                  "seventy": batch(*back_ref.seventy_case()),
+                  "list": (3, [(tuple(s.shape[1:]), r, z, i % 2 == 1) for i, (s, r, z) in enumerate(zip(srcs, regions, sizes))])}
+    for name, (k, geo) in back_cases.items():
+        for f in FILTERS5:
+            for ln, layout in LAYOUTS:
+                for rn, reduce, dn, dt in BACK_OUT:
+                    if reduce == _lib.BACK_ARGMAX and k > {_lib.U8: 256, _lib.I16: 32768}.get(dt, k):
+                        continue  # (a label type that cannot hold K - 1: not a pair the planner accepts)
+                    yield f"back/{name}/{f}/{ln}/{rn}/{dn}", plan_back(f, layout, k, back_items(layout, k, geo), len(geo), reduce, dt)
+
+    def members(canvas, regions, groups, sizes, flips):  # every member at its GROUP's size
+        shapes = [tuple(s.shape[1:]) for s in canvas] if isinstance(canvas, list) else [tuple(canvas.shape[2:])] * len(groups)
+        k = canvas[0].shape[0] if isinstance(canvas, list) else canvas.shape[1]
+        return k, [(shapes[i], regions[i], sizes[g], flips[i]) for i, g in enumerate(groups)], groups, len(sizes)
+
+    c, regions, groups, sizes = merged_ref.k300_case()
+    merged_cases = {"base": members(merged_ref.BASE_CANVAS, merged_ref.BASE_REGIONS, merged_ref.BASE_GROUPS, merged_ref.BASE_SIZES,
+                                    merged_ref.BASE_FLIPS),
+                    "k300": members(c, regions, groups, sizes, [False, True]), "seventy": members(*merged_ref.seventy_case()),
+                    "list": members(*merged_ref.list_case())}
+    for name, (k, geo, groups, g) in merged_cases.items():
+        for f in FILTERS5:
+            for ln, layout in LAYOUTS:
+                for mn, merge in sorted(_lib.BACK_MERGE.items()):
+                    for rn, reduce, dt in (("values", _lib.BACK_VALUES, _lib.F32), ("argmax", _lib.BACK_ARGMAX, _lib.I64),
+                                           ("greater", _lib.BACK_GREATER, _lib.BOOL)):
+                        yield (f"merged/{name}/{f}/{ln}/{mn}/{rn}",
+                               plan_merged(f, layout, k, back_items(layout, k, geo), len(geo), groups, g, merge, reduce, dt))
+
+    def canvases(canvas, regions, sizes, flips=None):
+        cv = bwd_ref.canvases_of(canvas, len(sizes))
+        return [(cv[i], regions[i], sizes[i], flips[i] if flips is not None else i % 2 == 1) for i in range(len(sizes))]
+
+    bwd_cases = {"base": (bwd_ref.BASE_K, canvases(bwd_ref.BASE_HW, bwd_ref.BASE_REGIONS, bwd_ref.BASE_SIZES, bwd_ref.BASE_FLIPS)),
+                 "list": (3, canvases(*bwd_ref.list_case())), "seventy": (3, canvases(*bwd_ref.seventy_case())),
+                 "long_rows": (2, canvases(*bwd_ref.long_rows_case())), "seams": (5, canvases(*bwd_ref.seams_case()))}
+    for name, (k, geo) in bwd_cases.items():
+        for nn, none in (("all", ()), ("none3", range(0, len(geo), 3))):  # every item with a gradient; every third without
+            recs = back_bwd_items(k, [q + (i not in none,) for i, q in enumerate(geo)])
+            for f in FILTERS5:
+                for ln, layout in LAYOUTS:
+                    for dn, dt in (("f32", _lib.F32), ("f16", _lib.F16), ("bf16", _lib.BF16)):
+                        for dense in (0, 1):
+                            yield (f"back_bwd/{name}/{nn}/{f}/{ln}/{dn}/{'dense' if dense else 'aligned'}",
+                                   plan_back_bwd(f, layout, k, recs, len(geo), dt, dense))
 
 
 def _case_plans():
@@ -318,10 +480,176 @@ def _error_plans():
     yield "err/ycbcr/short_block", ycc(nbytes=_lib.load().aa_many_desc_bytes_ycbcr(2) - 1)
     yield "err/ycbcr/flag_alpha", ycc(recs=ycc_images(yok, False, [FLIP, ALPHA]))
 
+    # the float ragged calls: the inputs of their planners' own error tests, and inputs that break two rules at once where the two
+    # rules are written in different places, so what comes back says which is looked at first
+    L = _lib.load()
+    emb = lambda **kw: plan_embed(**{**dict(f="cubic", d=8, h0=5, w0=7, grids=[(2, 3)]), **kw})  # noqa: E731
+    yield "err/embed/ok", emb()
+    yield "err/embed/n_negative", emb(n=-1)
+    yield "err/embed/d_zero", emb(d=0)
+    yield "err/embed/h0_zero", emb(h0=0)
+    yield "err/embed/w0_beyond", emb(w0=KMAX + 1)
+    yield "err/embed/filter", emb(f=5)
+    yield "err/embed/filter_before_shape", emb(f=5, d=0)
+    yield "err/embed/null_block", emb(null=("desc",))
+    yield "err/embed/null_grids", emb(null=("grids",))
+    yield "err/embed/null_ws", emb(null=("ws",))
+    yield "err/embed/null_rows", emb(null=("rows",))
+    yield "err/embed/short_block", emb(nbytes=L.aa_embed_many_desc_bytes(1) - 1)
+    yield "err/embed/pad_to_short", emb(pad_to=5)
+    yield "err/embed/pad_to_negative", emb(pad_to=-1)
+    for i, grids in enumerate([[(0, 3)], [(3, 0)], [(2, 2), (-1, 2)], [(KMAX + 1, 1)], [(1, KMAX + 1)], [(65536, 65536)]]):
+        yield f"err/embed/grid_{i}", emb(grids=grids)
+    yield "err/embed/ksize_h", emb(f="lanczos", h0=20000, grids=[(2, 3), (1, 3)])
+    yield "err/embed/ksize_w", emb(f="lanczos", w0=20000, grids=[(2, 3), (2, 1)])
+    yield "err/embed/ksize_h_and_w", emb(f="lanczos", h0=20000, w0=20000, grids=[(2, 3), (1, 1)])
+    yield "err/embed/trk_h", emb(h0=1, grids=[(2, 3), (100000, 3)])
+    yield "err/embed/ksize_w_and_trk_h", emb(f="lanczos", h0=1, w0=20000, grids=[(100000, 1)])
+    yield "err/embed/pad_to_before_ksize", emb(f="lanczos", h0=20000, grids=[(1, 3)], pad_to=2)
+    yield "err/embed/rows_beyond_a_grid", emb(d=KMAX, grids=[(1024, 1024)] * 4)
+
+    P = _lib.NCHW
+    bgeo = [((12, 16), (1, 2, 6, 9), (3, 4), False), ((12, 16), (0, 0, 12, 16), (5, 7), True)]
+
+    def changed(recs, at=1, **kw):
+        for k, v in kw.items():
+            setattr(recs[at], k, v)
+        return recs
+
+    back = lambda **kw: plan_back(**{**dict(f="linear", layout=P, k=7, recs=back_items(P, 7, bgeo), n=2), **kw})  # noqa: E731
+    yield "err/back/ok", back()
+    yield "err/back/filter_first", back(f=5, layout=7, n=-1, null=("desc",))
+    yield "err/back/layout", back(layout=7, n=-1, null=("desc",))
+    yield "err/back/n_negative", back(n=-1, null=("desc",))
+    yield "err/back/k_zero", back(k=0, null=("desc",))
+    yield "err/back/k_beyond", back(k=KMAX + 1)
+    yield "err/back/reduce", back(reduce=3, null=("desc",))
+    yield "err/back/reduce_negative", back(reduce=-1)
+    yield "err/back/k257_u8", back(k=257, reduce=_lib.BACK_ARGMAX, out_dtype=_lib.U8, null=("desc",))
+    yield "err/back/k256_u8", back(k=256, recs=back_items(P, 256, bgeo), reduce=_lib.BACK_ARGMAX, out_dtype=_lib.U8)
+    yield "err/back/k32769_i16", back(k=32769, reduce=_lib.BACK_ARGMAX, out_dtype=_lib.I16)
+    yield "err/back/k32769_i32", back(k=32769, recs=back_items(P, 32769, bgeo), reduce=_lib.BACK_ARGMAX, out_dtype=_lib.I32)
+    for what in ("items", "ws", "arena", "offs", "desc"):
+        yield f"err/back/null_{what}", back(recs=changed(back_items(P, 7, bgeo), h=0), null=(what,), nbytes=L.aa_back_many_desc_bytes(2) - 1)
+    yield "err/back/short_block", back(recs=changed(back_items(P, 7, bgeo), h=0), nbytes=L.aa_back_many_desc_bytes(2) - 1)
+    yield "err/back/null_source", back(recs=changed(back_items(P, 7, bgeo), data_dev=None))
+    for name, kw in (("h_zero", {"h": 0}), ("w_negative", {"w": -1}), ("oh_zero", {"oh": 0}), ("ow_zero", {"ow": 0}), ("h_beyond", {"h": KMAX + 1}),
+                     ("ow_beyond", {"ow": KMAX + 1}), ("flag_bit", {"flags": 2}), ("flag_bits", {"flags": 3})):
+        yield f"err/back/{name}_before_strides_and_dtype", back(recs=changed(back_items(P, 7, bgeo), stride_row=-9, **kw), out_dtype=_lib.F64)
+    yield "err/back/elems_beyond", back(k=2, recs=changed(back_items(P, 2, bgeo), oh=1 << 20, ow=1 << 20))
+    yield "err/back/elems_beyond_before_strides", back(k=2, recs=changed(back_items(P, 2, bgeo), oh=1 << 20, ow=1 << 20, stride_row=-9))
+    yield "err/back/units_beyond", back(k=2, recs=changed(back_items(P, 2, bgeo), oh=1 << 20, ow=1 << 19))
+    yield "err/back/units_beyond_sum", plan_back("linear", P, 1, back_items(P, 1, [((6, 9), None, (KMAX, 8), False)] * 5), 5)
+    yield "err/back/strides_before_dtype", back(recs=changed(back_items(P, 7, bgeo), stride_row=-9), out_dtype=_lib.F64)
+    yield "err/back/stride_class_nchw", back(recs=back_items(N, 7, bgeo))
+    yield "err/back/stride_class_nhwc", back(layout=N)
+    yield "err/back/stride_px_nhwc", back(layout=N, recs=changed(back_items(N, 7, bgeo), stride_px=8))
+    yield "err/back/one_element_axes", back(k=1, recs=changed(changed(back_items(P, 1, [((1, 9), None, (3, 4), False), ((6, 1), None, (3, 4), False)]),
+                                                                     0, stride_ch=-3, stride_row=-5), 1, stride_px=77))
+    yield "err/back/ksize_h", back(f="lanczos", recs=changed(back_items(P, 7, bgeo), h=20000, oh=1))
+    yield "err/back/ksize_w", back(f="lanczos", recs=changed(back_items(P, 7, bgeo), w=20000, ow=1))
+    yield "err/back/ksize_h_and_w", back(f="lanczos", recs=changed(back_items(P, 7, bgeo), h=20000, oh=1, w=20000, ow=1))
+    yield "err/back/strides_before_ksize", back(f="lanczos", recs=changed(back_items(P, 7, bgeo), h=20000, oh=1, stride_ch=-1))
+    yield "err/back/ksize_before_dtype", back(f="lanczos", recs=changed(back_items(P, 7, bgeo), h=20000, oh=1), out_dtype=_lib.F64)
+    for rn, reduce, bad in (("values", _lib.BACK_VALUES, (_lib.U8, _lib.F64, _lib.I32, _lib.BOOL, 9, -1)),
+                            ("argmax", _lib.BACK_ARGMAX, (_lib.F32, _lib.BOOL, _lib.F64)), ("greater", _lib.BACK_GREATER, (_lib.F32, _lib.I16, _lib.I64))):
+        for dt in bad:
+            yield f"err/back/dtype_{rn}_{dt}", back(reduce=reduce, out_dtype=dt)
+
+    mgeo = [((12, 16), (1, 2, 6, 9), (3, 4), False), ((12, 16), (0, 0, 12, 16), (3, 4), True)]
+    mrg = lambda **kw: plan_merged(**{**dict(f="linear", layout=P, k=7, recs=back_items(P, 7, mgeo), n=2, groups=[0, 0], g=1), **kw})  # noqa: E731
+    bad_shape = lambda: changed(back_items(P, 7, mgeo), 0, h=0)  # noqa: E731
+    yield "err/merged/ok", mrg()
+    yield "err/merged/ok_mean", mrg(merge=1)
+    yield "err/merged/filter_first", mrg(f=5, layout=7, n=-1, g=-1, merge=2, groups=[0, 5], null=("desc",))
+    yield "err/merged/layout", mrg(layout=7, n=-1, g=-1, merge=2, groups=[0, 5], null=("desc",))
+    yield "err/merged/n_negative", mrg(n=-1, null=("desc",))
+    yield "err/merged/k_zero", mrg(k=0, null=("desc",))
+    yield "err/merged/k_beyond", mrg(k=KMAX + 1)
+    yield "err/merged/reduce", mrg(reduce=3, null=("desc",))
+    for g in (-1, 3, 0):
+        yield f"err/merged/g_{g}", mrg(g=g, null=("desc",))
+    for merge in (-1, 2):
+        yield f"err/merged/merge_{merge}", mrg(merge=merge, null=("desc",))
+    yield "err/merged/k257_u8", mrg(k=257, reduce=_lib.BACK_ARGMAX, out_dtype=_lib.U8, null=("desc",))
+    yield "err/merged/k256_u8", mrg(k=256, recs=back_items(P, 256, mgeo), reduce=_lib.BACK_ARGMAX, out_dtype=_lib.U8)
+    for what in ("items", "groups", "ws", "arena", "offs", "desc"):
+        yield f"err/merged/null_{what}", mrg(recs=bad_shape(), groups=[0, 5], g=2, null=(what,), nbytes=L.aa_back_merged_desc_bytes(2, 2) - 1)
+    yield "err/merged/short_block", mrg(recs=bad_shape(), groups=[0, 5], g=2, nbytes=L.aa_back_merged_desc_bytes(2, 2) - 1)
+    for i, bad in enumerate([[0, 2], [-1, 0], [0, 1 << 40]]):
+        yield f"err/merged/group_of_{i}_before_items", mrg(recs=bad_shape(), groups=bad, g=2)
+    yield "err/merged/empty_group_before_null_source", mrg(recs=changed(back_items(P, 7, mgeo), 0, data_dev=None), groups=[1, 1], g=2)
+    yield "err/merged/null_source", mrg(recs=changed(back_items(P, 7, mgeo), 0, data_dev=None), groups=[1, 0], g=2)
+    for name, kw in (("h_zero", {"h": 0}), ("ow_zero", {"ow": 0}), ("h_beyond", {"h": KMAX + 1}), ("flag_bit", {"flags": 2})):
+        yield f"err/merged/{name}_before_strides_and_dtype", mrg(recs=changed(back_items(P, 7, mgeo), stride_row=-9, **kw), out_dtype=_lib.F64)
+    yield "err/merged/strides_before_dtype", mrg(recs=changed(back_items(P, 7, mgeo), stride_row=-9), out_dtype=_lib.F64)
+    for name, kw in (("oh", {"oh": 4}), ("ow", {"ow": 5}), ("oh_ow", {"oh": 4, "ow": 3})):
+        yield f"err/merged/member_size_{name}_before_dtype", mrg(recs=changed(back_items(P, 7, mgeo), **kw), out_dtype=_lib.F64)
+        yield f"err/merged/member_size_{name}_two_groups", mrg(recs=changed(back_items(P, 7, mgeo), **kw), groups=[0, 1], g=2)
+        yield f"err/merged/strides_before_member_size_{name}", mrg(recs=changed(back_items(P, 7, mgeo), stride_row=-9, **kw))
+    big = [((6, 9), None, (KMAX, 8), False)]
+    yield "err/merged/units_one_group", plan_merged("linear", P, 1, back_items(P, 1, big * 4), 4, [0, 0, 0, 0], 1)
+    yield "err/merged/units_four_groups", plan_merged("linear", P, 1, back_items(P, 1, big * 5), 5, [0, 1, 2, 3, 3], 4)
+    yield "err/merged/units_beyond", plan_merged("linear", P, 1, back_items(P, 1, big * 5), 5, [0, 1, 2, 3, 4], 5)
+    yield "err/merged/elems_beyond", plan_merged("linear", P, 2, back_items(P, 2, [((6, 9), None, (1 << 20, 1 << 20), False)]), 1, [0], 1)
+    yield "err/merged/elems_beyond_before_strides", mrg(k=2, recs=changed(back_items(P, 2, mgeo), oh=1 << 20, ow=1 << 20, stride_row=-9))
+    yield "err/merged/ksize_h", mrg(f="lanczos", recs=changed(back_items(P, 7, mgeo), h=20000, oh=1))
+    yield "err/merged/ksize_h_and_w", mrg(f="lanczos", recs=changed(back_items(P, 7, mgeo), h=20000, oh=1, w=20000, ow=1))
+    yield "err/merged/strides_before_ksize", mrg(f="lanczos", recs=changed(back_items(P, 7, mgeo), h=20000, oh=1, stride_ch=-1))
+    yield "err/merged/ksize_before_member_size", mrg(f="lanczos", recs=changed(back_items(P, 7, mgeo), h=20000, oh=1, ow=5))
+    for rn, reduce, bad in (("values", _lib.BACK_VALUES, (_lib.U8, _lib.F64, _lib.BOOL, 9)), ("argmax", _lib.BACK_ARGMAX, (_lib.F32, _lib.BOOL)),
+                            ("greater", _lib.BACK_GREATER, (_lib.F32, _lib.I64))):
+        for dt in bad:
+            yield f"err/merged/dtype_{rn}_{dt}", mrg(reduce=reduce, out_dtype=dt)
+
+    wgeo = [((12, 16), (1, 2, 6, 9), (3, 4), False, True), ((12, 16), (2, 3, 5, 7), (5, 7), True, True)]
+    bwd = lambda **kw: plan_back_bwd(**{**dict(f="linear", layout=P, k=7, recs=back_bwd_items(7, wgeo), n=2), **kw})  # noqa: E731
+    bad_canvas = lambda: changed(back_bwd_items(7, wgeo), H=0)  # noqa: E731
+    yield "err/back_bwd/ok", bwd()
+    yield "err/back_bwd/filter_first", bwd(f=5, layout=7, n=-1, recs=bad_canvas(), null=("desc",))
+    yield "err/back_bwd/layout", bwd(layout=7, n=-1, recs=bad_canvas(), null=("desc",))
+    yield "err/back_bwd/n_negative", bwd(n=-1, null=("desc",))
+    yield "err/back_bwd/k_zero", bwd(k=0, null=("desc",))
+    yield "err/back_bwd/k_beyond", bwd(k=KMAX + 1)
+    yield "err/back_bwd/dense_2", bwd(dense=2, null=("desc",))
+    yield "err/back_bwd/dense_negative", bwd(dense=-1)
+    for what in ("items", "ws", "out", "offs", "desc"):
+        yield f"err/back_bwd/null_{what}", bwd(recs=bad_canvas(), null=(what,), nbytes=L.aa_back_many_bwd_desc_bytes(2) - 1)
+    yield "err/back_bwd/short_block", bwd(recs=bad_canvas(), nbytes=L.aa_back_many_bwd_desc_bytes(2) - 1)
+    for name, kw in (("H_zero", {"H": 0}), ("W_negative", {"W": -1}), ("H_beyond", {"H": KMAX + 1}), ("flag_bit", {"flags": 2}), ("oh_zero", {"oh": 0}),
+                     ("ow_beyond", {"ow": KMAX + 1}), ("h_zero", {"h": 0}), ("y0_negative", {"y0": -1}), ("y0_beyond", {"y0": 8}),
+                     ("x0_beyond", {"x0": 10}), ("region_beyond", {"y0": 0, "x0": 0, "h": 13, "w": 16})):
+        yield f"err/back_bwd/{name}_before_strides_and_dtype", bwd(recs=changed(back_bwd_items(7, wgeo), stride_row=-4, **kw), out_dtype=_lib.F64)
+    yield "err/back_bwd/canvas_elems_beyond", bwd(k=2, recs=changed(back_bwd_items(2, wgeo), H=1 << 20, W=1 << 20))
+    yield "err/back_bwd/grad_elems_beyond", bwd(k=2, recs=changed(back_bwd_items(2, wgeo), oh=1 << 20, ow=1 << 20))
+    yield "err/back_bwd/grad_elems_beyond_before_strides", bwd(k=2, recs=changed(back_bwd_items(2, wgeo), oh=1 << 20, ow=1 << 20, stride_row=-4))
+    yield "err/back_bwd/no_gradient_nothing_else_looked_at", bwd(recs=changed(back_bwd_items(7, wgeo), grad_dev=None, y0=-5, x0=99, h=0, w=0, oh=0, ow=-3,
+                                                                                stride_ch=-1, stride_row=-1))
+    yield "err/back_bwd/no_gradient_bad_canvas", bwd(recs=changed(bad_canvas(), grad_dev=None))
+    yield "err/back_bwd/strides_before_dtype", bwd(recs=changed(back_bwd_items(7, wgeo), stride_row=-4), out_dtype=_lib.F64)
+    yield "err/back_bwd/stride_ch", bwd(recs=changed(back_bwd_items(7, wgeo), stride_ch=-12))
+    yield "err/back_bwd/one_row_stride_unused", bwd(recs=changed(back_bwd_items(7, wgeo), oh=1, stride_row=-4))
+    yield "err/back_bwd/one_class_stride_unused", bwd(k=1, recs=changed(back_bwd_items(1, wgeo), stride_ch=-3))
+    wide = [((KMAX, 64), (0, 0, 2, 2), (3, 4), False, True)]
+    yield "err/back_bwd/units_15", plan_back_bwd("linear", P, 1, back_bwd_items(1, wide * 15), 15)
+    yield "err/back_bwd/units_beyond", plan_back_bwd("linear", P, 1, back_bwd_items(1, wide * 16), 16)
+    yield "err/back_bwd/ksize_h", bwd(f="lanczos", recs=changed(back_bwd_items(7, [((20000, 16), None, (1, 4), False, True)] * 2), x0=2, w=9))
+    yield "err/back_bwd/ksize_w", bwd(f="lanczos", recs=changed(back_bwd_items(7, [((12, 20000), None, (3, 1), False, True)] * 2), y0=1, h=6))
+    yield "err/back_bwd/ksize_h_and_w", bwd(f="lanczos", recs=back_bwd_items(7, [((20000, 20000), None, (1, 1), False, True)] * 2))
+    yield "err/back_bwd/trk_h", bwd(recs=changed(back_bwd_items(7, wgeo), h=1, oh=100000))
+    yield "err/back_bwd/ksize_w_and_trk_h", bwd(f="lanczos", recs=back_bwd_items(7, [((1, 20000), None, (100000, 1), False, True)] * 2))
+    yield "err/back_bwd/strides_before_ksize", bwd(f="lanczos", recs=changed(back_bwd_items(7, [((20000, 16), None, (1, 4), False, True)] * 2), 0,
+                                                                             stride_ch=-1))
+    yield "err/back_bwd/ksize_before_dtype", bwd(f="lanczos", recs=back_bwd_items(7, [((20000, 16), None, (1, 4), False, True)] * 2), out_dtype=_lib.F64)
+    for dt in (_lib.U8, _lib.F64, _lib.I32, _lib.BOOL, 9, -1):
+        yield f"err/back_bwd/dtype_{dt}", bwd(out_dtype=dt)
+
 
 def plans():
     """-> (key, rc, workspace bytes, descriptor bytes) of every plan."""
     for key, (rc, ws, block) in _case_plans():
+        yield key, rc, ws, block
+    for key, (rc, ws, block) in _float_case_plans():
         yield key, rc, ws, block
     for key, (rc, ws, block) in _error_plans():
         yield key, rc, ws, block

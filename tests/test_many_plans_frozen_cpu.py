@@ -25,8 +25,9 @@ def planned():
 
 def test_the_key_set_is_complete(planned):
     assert sorted(planned) == sorted(FROZEN)
-    assert GROUPS == ["alpha", "err", "many", "maps", "nearest", "patches", "placed", "reduce", "ycbcr"]
-    assert {k.split("/")[1] for k in FROZEN if k.startswith("err/")} == {"many", "patches", "nearest", "reduce", "maps", "ycbcr"}
+    assert GROUPS == ["alpha", "back", "back_bwd", "embed", "err", "many", "maps", "merged", "nearest", "patches", "placed", "reduce", "ycbcr"]
+    assert {k.split("/")[1] for k in FROZEN if k.startswith("err/")} == {"many", "patches", "nearest", "reduce", "maps", "ycbcr", "embed", "back",
+                                                                         "merged", "back_bwd"}
 
 
 @pytest.mark.parametrize("group", GROUPS)
