@@ -6,6 +6,7 @@ A request is honoured by what the plan knows alone (strips, LDS per strip, oH) â
 and tests/test_launch_shape_gpu.py relies on it when it requires every shape it asks for to have run."""
 import ctypes
 import itertools
+import threading
 
 import pytest
 
@@ -60,7 +61,13 @@ def test_the_setter_returns_the_previous_setting():
     assert _lib.set_launch_shape(-3, -1) == (0, 0)
     assert _lib.set_launch_shape(1000, 1 << 20) == (0, 0)
     assert _lib.set_launch_shape(0, 0) == (255, 0xFFFF)
-    assert _lib.last_launch_shape() is None  # no fused launch on this thread
+    # no fused launch on a thread: asked on a thread of its own, since the record is per thread and in a whole-suite run on a GPU the
+    # tests before this one (test_launch_shape_gpu.py) have launched fused kernels on pytest's
+    seen = []
+    asker = threading.Thread(target=lambda: seen.append(_lib.last_launch_shape()))
+    asker.start()
+    asker.join()
+    assert seen == [None]
 
 
 # oH -> min(max_yb, 64) with 8 rows per band, with the up kernel's 16
