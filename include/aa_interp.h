@@ -31,7 +31,8 @@ extern "C" {
                                    symbol up): aa_back_many_desc_bytes, aa_back_many_plan, aa_resample_back_many, with aa_back_item
                                    and the aa_dtype values AA_I16 .. AA_BOOL that only they take; aa_back_many_bwd_desc_bytes,
                                    aa_back_many_bwd_plan, aa_resample_back_many_bwd, with aa_back_bwd_item; aa_back_merged_desc_bytes,
-                                   aa_back_merged_plan, aa_resample_back_merged */
+                                   aa_back_merged_plan, aa_resample_back_merged; aa_back_many_plan_act, aa_back_merged_plan_act
+                                   (a softmax or sigmoid before the reduction), with AA_BACK_ACT_* */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -628,8 +629,22 @@ int aa_resample_embed_many_bwd(const void *desc_host, const void *desc_dev, cons
  * (AA_ERR_BAD_SHAPE; looked at for reduce 2 only).  arena_dev: arena_bytes >= the plan's (AA_ERR_WORKSPACE), aligned to out_dtype's
  * element (AA_ERR_BAD_SHAPE); desc_dev (8-byte aligned) and workspace_dev (16-byte aligned, at least the plan's size) as
  * aa_resample_many_u8; a block that is not this planner's AA_ERR_BAD_SHAPE.  Every check comes before the first launch; nothing is
- * allocated, synchronised or read back, and no table cache is touched.  Not built: fractional rectangles, a dense padded output,
- * softmax (the backward of reduce 0 is below).  Added without an ABI version change (additive). */
+ * allocated, synchronised or read back, and no table cache is touched.  Not built: fractional rectangles, a dense padded output
+ * (the backward of reduce 0 is below).  Added without an ABI version change (additive).
+ * aa_back_many_plan_act is aa_back_many_plan with an activation between R_i and everything after it: AA_BACK_ACT_NONE (0; the block is
+ * aa_back_many_plan's byte for byte), AA_BACK_ACT_SOFTMAX (1, over the K classes of a pixel) or AA_BACK_ACT_SIGMOID (2, per element);
+ * anything else is AA_ERR_BAD_SHAPE, beside the unknown reduce.  The block keeps the activation, and aa_resample_back_many reads it
+ * there: the same two launches, no workspace beyond the tables.  P replaces R_i in reduce 0, 1 and 2 as they are stated above, computed
+ * in fp32 with every product and sum rounded on its own (never fused), bit for bit tests/activation_ref.py's numpy restatement:
+ *   aa_exp(x), x <= 0 or NaN:  NaN -> x + x;  x < -86.0f -> +0;  else n = rintf(x * 1.44269504f) (ties to even),
+ *       r = x - n * 0.693359375f, r = r - n * -2.12194440e-4f,  p = 1.9875691500e-4f, p = p * r + c for c = 1.3981999507e-3f,
+ *       8.3334519073e-3f, 4.1665795894e-2f, 1.6666665459e-1f, 5.0000001201e-1f,  y = ((p * r) * r + r) + 1.0f,  y * 2^n (exact; 2^n is a
+ *       normal number).  At most 0.9916 ulp from exp over every float32 of [-86, 0]; aa_exp(0) = 1; no non-zero subnormal result.
+ *   sigmoid:  e = aa_exp(-|v|), q = 1.0f + e, P = (v >= 0 ? 1.0f : e) / q, one correctly rounded division.  NaN -> NaN, +inf -> 1, -inf -> +0.
+ *   softmax:  pass one over k ascending, m = v_0, d = 1.0f; v_k > m: d = d * aa_exp(m - v_k) + 1.0f, m = v_k; else d = d + aa_exp(v_k - m).
+ *       rcp = 1.0f / d, one correctly rounded division, NaN where m is +inf.  Pass two: P_k = aa_exp(v_k - m) * rcp, subnormal products
+ *       kept.  A -inf value gets +0; a pixel with a NaN or a +inf value, or with nothing but -inf, is NaN in every class.
+ * A NaN's sign and payload are not defined.  The kernel resamples a softmax pixel's classes twice (nothing is staged). */
 typedef struct aa_back_item {
   const void *data_dev;                      /* the rectangle's first element of class 0 */
   int64_t stride_ch, stride_row, stride_px;  /* in ELEMENTS */
@@ -642,6 +657,10 @@ size_t aa_back_many_desc_bytes(int64_t n);
 int aa_back_many_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce /* 0 values, 1 argmax, 2 greater */,
                       int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
                       int64_t *out_offsets /* n, bytes */);
+enum { AA_BACK_ACT_NONE = 0, AA_BACK_ACT_SOFTMAX = 1, AA_BACK_ACT_SIGMOID = 2 };
+int aa_back_many_plan_act(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce /* 0 values, 1 argmax, 2 greater */,
+                          int activation /* AA_BACK_ACT_* */, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes,
+                          size_t *arena_bytes, int64_t *out_offsets /* n, bytes */);
 int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
                           void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 
@@ -669,13 +688,28 @@ int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dt
  * walks the group's members in order, each one's vertical sum of horizontal sums added to the group's in registers, and hands the
  * complete sums to the reduction.  A mirrored member is mirrored where it is read.  Neither a member's values nor, for reduce 1, the K
  * sums are ever stored.  Parameters, checks and their order as aa_resample_back_many; every check comes before the first launch;
- * nothing is allocated, synchronised or read back, and no table cache is touched.  n == 0 launches nothing.  Not built: softmax before
- * the sum, per-member weights, a maximum instead of the sum, members placed at different positions of the output.  Added without an
- * ABI version change (additive). */
+ * nothing is allocated, synchronised or read back, and no table cache is touched.  n == 0 launches nothing.  Not built: per-member
+ * weights, a maximum instead of the sum, members placed at different positions of the output.  Added without an ABI version change
+ * (additive).
+ * aa_back_merged_plan_act is aa_back_merged_plan with an activation (AA_BACK_ACT_*, defined at aa_back_many_plan_act) applied to every
+ * member's R_i BEFORE the sum: S_g adds the members' P in the same order, and the mean and the reductions follow unchanged, so a group
+ * of one member is aa_back_many_plan_act's item.  Activation 0 writes aa_back_merged_plan's block byte for byte.  Errors as
+ * aa_back_merged_plan, with these added: AA_ERR_BAD_SHAPE beside the unknown reduce for an unknown activation; for AA_BACK_ACT_SOFTMAX,
+ * after the empty group, AA_ERR_BAD_SHAPE for a group of more than 16 members (a lane keeps every member's maximum and reciprocal
+ * denominator in LDS between its two passes, 2 KiB a member and workgroup; the sigmoid and activation 0 have no limit).  The block
+ * keeps the activation and aa_resample_back_merged reads it there: the same two launches, no workspace beyond the tables.  Its checks
+ * as before, with a block whose activation is unknown, or whose softmax plan holds a group of more than 16 members, no plan's block
+ * (AA_ERR_BAD_SHAPE, with the header, before in_dtype is looked at); then for a softmax, last before the first launch, the limit on a
+ * workgroup's LDS of the device the launches go to — the stream's device, for the null stream the current one — against 2 KiB times the
+ * plan's largest group (AA_ERR_BAD_SHAPE; AA_ERR_HIP where the device cannot be asked). */
 size_t aa_back_merged_desc_bytes(int64_t n, int64_t g);
 int aa_back_merged_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of /* n */,
                         int merge /* 0 sum, 1 mean */, int reduce /* 0 values, 1 argmax, 2 greater */, int out_dtype, void *desc_host,
                         size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets /* G, bytes */);
+int aa_back_merged_plan_act(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of /* n */,
+                            int merge /* 0 sum, 1 mean */, int reduce /* 0 values, 1 argmax, 2 greater */, int activation /* AA_BACK_ACT_* */,
+                            int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
+                            int64_t *out_offsets /* G, bytes */);
 int aa_resample_back_merged(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
                             void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 

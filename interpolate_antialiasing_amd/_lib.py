@@ -63,6 +63,7 @@ EXPORTS = (
     "aa_back_many_desc_bytes", "aa_back_many_plan", "aa_resample_back_many",
     "aa_back_many_bwd_desc_bytes", "aa_back_many_bwd_plan", "aa_resample_back_many_bwd",
     "aa_back_merged_desc_bytes", "aa_back_merged_plan", "aa_resample_back_merged",
+    "aa_back_many_plan_act", "aa_back_merged_plan_act",
 )
 
 
@@ -312,6 +313,8 @@ YCC_SUBSAMPLING = {"444": 0, "422": 1, "420": 2, "440": 3}  # aa_ycbcr_image.sub
 YCC_VROWS, YCC_VCOLS = 4, 256  # canvas rows and columns per work unit of the YCbCr call's vertical pass (csrc/aa_many_ycbcr.h)
 BACK_VALUES, BACK_ARGMAX, BACK_GREATER = 0, 1, 2  # aa_back_many_plan reduce (csrc/aa_many_back.h AA_BACK_*)
 BACK_MERGE = {"sum": 0, "mean": 1}  # aa_back_merged_plan merge (csrc/aa_many_back.h AA_BACK_MERGE_*)
+BACK_ACT = {None: 0, "softmax": 1, "sigmoid": 2}  # aa_back_many_plan_act activation (include/aa_interp.h AA_BACK_ACT_*)
+BACK_ACT_MEMBERS = 16  # the most members of a group of a merged softmax plan (csrc/aa_many_back.h AA_BACK_ACT_MEMBERS)
 BACK_TILE = 256     # output columns per work unit of the return path's resample (csrc/aa_many_back.h AA_BACK_TILE)
 BACK_BWD_ROWS, BACK_BWD_COLS = 4, 64  # canvas rows and columns per work unit of the return path's backward (csrc/aa_many_back_bwd.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
@@ -536,6 +539,12 @@ def load() -> ctypes.CDLL:
     L.aa_back_merged_plan.restype = i32
     L.aa_resample_back_merged.argtypes = [vp, vp, i32, ctypes.c_float, vp, sz, vp, sz, vp]
     L.aa_resample_back_merged.restype = i32
+    L.aa_back_many_plan_act.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), i32, i32, i32, vp, sz, ctypes.POINTER(sz),
+                                        ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_back_many_plan_act.restype = i32
+    L.aa_back_merged_plan_act.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), i64, ctypes.POINTER(i64), i32, i32, i32, i32, vp, sz,
+                                          ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_back_merged_plan_act.restype = i32
     L.aa_back_many_bwd_desc_bytes.argtypes = [i64]
     L.aa_back_many_bwd_desc_bytes.restype = sz
     L.aa_back_many_bwd_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackBwdItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),

@@ -619,7 +619,14 @@ size_t aa_back_many_desc_bytes(int64_t n) { return aa_back_desc_size(n); }
 
 int aa_back_many_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce, int out_dtype, void *desc_host,
                       size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
-  return aa_back_plan_host(filter, layout, n, K, items, reduce, out_dtype, desc_host, desc_bytes, workspace_bytes, arena_bytes, out_offsets);
+  return aa_back_plan_host(filter, layout, n, K, items, reduce, AA_BACK_ACT_NONE, out_dtype, desc_host, desc_bytes, workspace_bytes, arena_bytes,
+                           out_offsets);
+}
+
+int aa_back_many_plan_act(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce, int activation, int out_dtype,
+                          void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
+  return aa_back_plan_host(filter, layout, n, K, items, reduce, activation, out_dtype, desc_host, desc_bytes, workspace_bytes, arena_bytes,
+                           out_offsets);
 }
 
 int aa_resample_back_many(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
@@ -634,8 +641,15 @@ size_t aa_back_merged_desc_bytes(int64_t n, int64_t g) { return aa_back_merged_d
 int aa_back_merged_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of, int merge,
                         int reduce, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
                         int64_t *out_offsets) {
-  return aa_back_merged_plan_host(filter, layout, n, K, items, G, group_of, merge, reduce, out_dtype, desc_host, desc_bytes, workspace_bytes,
-                                  arena_bytes, out_offsets);
+  return aa_back_merged_plan_host(filter, layout, n, K, items, G, group_of, merge, reduce, AA_BACK_ACT_NONE, out_dtype, desc_host, desc_bytes,
+                                  workspace_bytes, arena_bytes, out_offsets);
+}
+
+int aa_back_merged_plan_act(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of, int merge,
+                            int reduce, int activation, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes,
+                            size_t *arena_bytes, int64_t *out_offsets) {
+  return aa_back_merged_plan_host(filter, layout, n, K, items, G, group_of, merge, reduce, activation, out_dtype, desc_host, desc_bytes,
+                                  workspace_bytes, arena_bytes, out_offsets);
 }
 
 int aa_resample_back_merged(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,

@@ -16,12 +16,15 @@
 #define AA_BACK_MAX_ELEMS ((int64_t)1 << 40)  // the bound on K * oh_i * ow_i, and on the elements of the arena
 
 enum { AA_BACK_VALUES = 0, AA_BACK_ARGMAX = 1, AA_BACK_GREATER = 2 };
+// The activation an item's (a member's) fp32 value goes through before the reduction (and before the merged call's sum) is one of
+// include/aa_interp.h's AA_BACK_ACT_NONE / _SOFTMAX / _SIGMOID; the device code is aa_activation.h.
+#define AA_BACK_ACT_MEMBERS 16  // the most members of a group of a merged SOFTMAX plan: a lane keeps (max, 1 / denominator) per member in LDS
 
 struct AABackHeader {
   int32_t magic, n, K, filter, layout;
   int32_t reduce;     // AA_BACK_*
   int32_t out_dtype;  // aa_dtype of an arena element
-  int32_t reserved0;
+  int32_t reserved0;  // AA_BACK_ACT_* (0, none: what the field held before there were activations)
   int64_t units;      // unit0[n]: the workgroups of the resample
   int64_t ws_bytes;   // the table arena: per item its H table, then its W table
   int64_t arena_bytes;
@@ -62,7 +65,7 @@ struct AABackMergedHeader {
   int64_t ws_bytes;   // the table arena: per member its H table, then its W table (aa_back_many_plan's for the same items)
   int64_t arena_bytes;
   int32_t G;
-  int32_t reserved;
+  int32_t reserved;   // AA_BACK_ACT_* (0, none: what the field held before there were activations)
 };
 static_assert(sizeof(AABackMergedHeader) == 64, "descriptor header is 64 bytes");
 
@@ -78,13 +81,13 @@ static_assert(sizeof(AABackGroup) == 32, "descriptor group is 32 bytes");
 
 size_t aa_back_merged_desc_size(int64_t n, int64_t g);
 int aa_back_merged_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of, int merge,
-                             int reduce, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
+                             int reduce, int activation, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
                              int64_t *out_offsets);
 int aa_launch_back_merged(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
                           void *workspace_dev, size_t workspace_bytes, hipStream_t stream);
 
 size_t aa_back_desc_size(int64_t n);
-int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce, int out_dtype, void *desc_host,
+int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int reduce, int activation, int out_dtype, void *desc_host,
                       size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets);
 int aa_launch_back_many(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
                         void *workspace_dev, size_t workspace_bytes, hipStream_t stream);

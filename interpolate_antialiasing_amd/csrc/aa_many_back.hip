@@ -19,6 +19,14 @@
 // The merged call (aa_back_merged_plan) runs the same two launches with back_resample_merged in place of back_resample: the items are
 // members of groups, a work unit is an output row of a GROUP, and a class's value is the members' values added in order before the
 // epilogue sees it (at "2'." below).
+// An activation (the plan's AA_BACK_ACT_*, aa_activation.h) stands between a value and what follows it, inside the same two launches and
+// without a workspace: the kernels with ACT, one instantiation for both activations (which one is uniform over the launch), so that the
+// instantiations double rather than triple and the kernels without an activation stay the code they were.  A sigmoid is applied to a
+// class's value where it leaves class_sums.  A softmax makes the lane walk the classes twice: once for the pixel's maximum and
+// denominator, once more — the resample recomputed, not staged, this kernel's bargain — for the probabilities, which then go where the
+// values went.  In the merged kernel a lane needs that pair of every member before the class-outer loop can add probabilities: a first
+// phase walks the members and keeps the pairs in LDS, [member][lane], 8 bytes a lane, so consecutive lanes touch consecutive slots
+// and a lane reads only what it wrote (no barrier; the early return stays).  That is 2 KiB a member, AA_BACK_ACT_MEMBERS of them at most.
 // Shared with the other ragged calls: aa_many_dev.h (the item of a unit, the element types), aa_many_host.h (the block, the launch checks);
 // with the other float ragged calls: aa_float_many_dev.h (the table kernels' body, table_row, class_sums), aa_float_many_host.h (the
 // float types, the tables of an item in a plan).
@@ -26,6 +34,7 @@
 #include <string.h>
 
 #include "aa_many_back.h"
+#include "aa_activation.h"
 #include "aa_float_many_dev.h"
 #include "aa_float_many_host.h"
 
@@ -81,12 +90,32 @@ struct BackArgs {
   char *arena;
   float threshold;
   int n, K;
+  int act;  // AA_BACK_ACT_*: looked at by the kernels with ACT only
 };
 
-// ---- 2. the resample -----------------------------------------------------------------------------------------------------------------------
-template <typename TIn, bool VEC, typename Epi>
-__global__ void __launch_bounds__(AA_BACK_TILE) back_resample(BackArgs a) {
+// The classes of one pixel in ascending k, AA_BACK_UNROLL at a time and then the tail one by one: put(k, class k's fp32 value).
+template <typename TIn, bool VEC, typename Put>
+__device__ inline void each_class(const TIn *p, int64_t sch, int64_t prow, int64_t ppx, const Row &ry, const Row &rx, int K, Put put) {
   constexpr int U = AA_BACK_UNROLL;
+  int k = 0;
+  for (; k + U <= K; k += U) {
+    float acc[U];
+    class_sums<TIn, U, VEC>(p + k * sch, sch, prow, ppx, ry, rx, acc);
+#pragma unroll
+    for (int c = 0; c < U; c++) put(k + c, acc[c]);
+  }
+  for (; k < K; k++) {
+    float acc[1];
+    class_sums<TIn, 1, false>(p + k * sch, sch, prow, ppx, ry, rx, acc);
+    put(k, acc[0]);
+  }
+}
+
+// ---- 2. the resample -----------------------------------------------------------------------------------------------------------------------
+// With ACT the value an epilogue sees is the activation's: the sigmoid of the class's value, or — after a first walk over the classes
+// for the pixel's maximum and denominator — its softmax term.  Both K loops of each walk are each_class's.
+template <typename TIn, bool VEC, bool ACT, typename Epi>
+__global__ void __launch_bounds__(AA_BACK_TILE) back_resample(BackArgs a) {
   const int64_t unit = blockIdx.x;
   const int item = aa_unit_item(a.unit0, a.n, unit);
   const AABackItem &it = a.items[item];
@@ -99,17 +128,15 @@ __global__ void __launch_bounds__(AA_BACK_TILE) back_resample(BackArgs a) {
   const TIn *p = (const TIn *)it.src + ry.x0 * prow + rx.x0 * ppx;
   const int xs = (it.flags & AA_MANY_FLIP_X) ? it.ow - 1 - x : x;
   Epi epi(a.arena + it.out_off, (int64_t)y * it.ow + xs, (int64_t)it.oh * it.ow, a.threshold);
-  int k = 0;
-  for (; k + U <= a.K; k += U) {
-    float acc[U];
-    class_sums<TIn, U, VEC>(p + k * sch, sch, prow, ppx, ry, rx, acc);
-#pragma unroll
-    for (int c = 0; c < U; c++) epi.put(k + c, acc[c]);
-  }
-  for (; k < a.K; k++) {
-    float acc[1];
-    class_sums<TIn, 1, false>(p + k * sch, sch, prow, ppx, ry, rx, acc);
-    epi.put(k, acc[0]);
+  if constexpr (!ACT) {
+    each_class<TIn, VEC>(p, sch, prow, ppx, ry, rx, a.K, [&](int k, float v) { epi.put(k, v); });
+  } else if (a.act == AA_BACK_ACT_SOFTMAX) {
+    SoftmaxPass one;
+    each_class<TIn, VEC>(p, sch, prow, ppx, ry, rx, a.K, [&](int k, float v) { one.put(k, v); });
+    const float m = one.m, rcp = one.rcp();
+    each_class<TIn, VEC>(p, sch, prow, ppx, ry, rx, a.K, [&](int k, float v) { epi.put(k, aa_softmax_term(v, m, rcp)); });
+  } else {
+    each_class<TIn, VEC>(p, sch, prow, ppx, ry, rx, a.K, [&](int k, float v) { epi.put(k, aa_sigmoid(v)); });
   }
   epi.done();
 }
@@ -130,11 +157,20 @@ struct MergedArgs {
   char *arena;
   float threshold;
   int G, K, mean;
+  int act;  // AA_BACK_ACT_*: looked at by the kernels with ACT only
 };
 
-// sum = the merged value of V classes from class k on of the lane's pixel (y, x) of group gr.
-template <typename TIn, int V, bool VEC>
-__device__ inline void member_sums(const MergedArgs &a, const AABackGroup &gr, int y, int x, int k, float (&sum)[V]) {
+// A softmax member's pair for the lane's pixel, in LDS: the maximum and 1 / denominator of its pass one.  Member m's slot of lane t is
+// element m * AA_BACK_TILE + t: the lanes of a wave write and read consecutive 8-byte slots.
+struct alignas(8) SoftmaxPair { float m, rcp; };
+
+// sum = the merged value of V classes from class k on of the lane's pixel (y, x) of group gr.  With ACT a member's value is first its
+// sigmoid, or its softmax term with the pair the lane left at pairs[m * AA_BACK_TILE].
+// (A float16 store may follow `sum[c] + acc[c]`, the mean's division or the sigmoid's directly.  Each must reach it as a rounded fp32
+// value: today's compiler folds only a PRODUCT into the conversion (aa_softmax_term keeps that apart).  Nothing in the source keeps a
+// later compiler from folding an add or a division the same way; the GPU bit tests with float16 outputs are what would show it.)
+template <typename TIn, int V, bool VEC, bool ACT>
+__device__ inline void member_sums(const MergedArgs &a, const AABackGroup &gr, int y, int x, int k, const SoftmaxPair *pairs, float (&sum)[V]) {
   const int32_t *member = a.member + gr.first;
   for (int m = 0; m < gr.count; m++) {
     const AABackItem &it = a.items[member[m]];
@@ -143,6 +179,16 @@ __device__ inline void member_sums(const MergedArgs &a, const AABackGroup &gr, i
     const int64_t sch = it.stride_ch, prow = it.stride_row, ppx = it.stride_px;
     float acc[V];
     class_sums<TIn, V, VEC>((const TIn *)it.src + ry.x0 * prow + rx.x0 * ppx + k * sch, sch, prow, ppx, ry, rx, acc);
+    if constexpr (ACT) {
+      if (a.act == AA_BACK_ACT_SOFTMAX) {
+        const SoftmaxPair s = pairs[m * AA_BACK_TILE];
+#pragma unroll
+        for (int c = 0; c < V; c++) acc[c] = aa_softmax_term(acc[c], s.m, s.rcp);
+      } else {
+#pragma unroll
+        for (int c = 0; c < V; c++) acc[c] = aa_sigmoid(acc[c]);
+      }
+    }
 #pragma unroll
     for (int c = 0; c < V; c++) sum[c] = m == 0 ? acc[c] : sum[c] + acc[c];
   }
@@ -153,7 +199,10 @@ __device__ inline void member_sums(const MergedArgs &a, const AABackGroup &gr, i
   }
 }
 
-template <typename TIn, bool VEC, typename Epi>
+// With ACT and a softmax, phase one: per member of the group, in order, the lane walks the member's classes once (each_class over the
+// member's own windows, mirrored where it is read like phase two) and leaves the pair in its LDS slot.  The launch sizes the dynamic LDS
+// for the plan's largest group (AA_BACK_TILE pairs a member; nothing for a sigmoid), and the planner bounds that group.
+template <typename TIn, bool VEC, bool ACT, typename Epi>
 __global__ void __launch_bounds__(AA_BACK_TILE) back_resample_merged(MergedArgs a) {
   constexpr int U = AA_BACK_UNROLL;
   const int64_t unit = blockIdx.x;
@@ -163,17 +212,34 @@ __global__ void __launch_bounds__(AA_BACK_TILE) back_resample_merged(MergedArgs 
   const int y = (int)(u / gr.xtiles);
   const int x = (int)(u - (int64_t)y * gr.xtiles) * AA_BACK_TILE + (int)threadIdx.x;
   if (x >= gr.ow) return;  // (no barrier below)
+  const SoftmaxPair *pairs = nullptr;
+  if constexpr (ACT) {
+    extern __shared__ __attribute__((aligned(8))) SoftmaxPair act_pairs[];
+    pairs = act_pairs + threadIdx.x;
+    if (a.act == AA_BACK_ACT_SOFTMAX) {
+      const int32_t *member = a.member + gr.first;
+      for (int m = 0; m < gr.count; m++) {
+        const AABackItem &it = a.items[member[m]];
+        const int xr = (it.flags & AA_MANY_FLIP_X) ? gr.ow - 1 - x : x;
+        const Row ry = table_row(a.ws + it.tab_h, it.h, gr.oh, it.ksize_h, y), rx = table_row(a.ws + it.tab_w, it.w, gr.ow, it.ksize_w, xr);
+        const int64_t sch = it.stride_ch, prow = it.stride_row, ppx = it.stride_px;
+        SoftmaxPass one;
+        each_class<TIn, VEC>((const TIn *)it.src + ry.x0 * prow + rx.x0 * ppx, sch, prow, ppx, ry, rx, a.K, [&](int k, float v) { one.put(k, v); });
+        act_pairs[m * AA_BACK_TILE + threadIdx.x] = {one.m, one.rcp()};
+      }
+    }
+  }
   Epi epi(a.arena + gr.out_off, (int64_t)y * gr.ow + x, (int64_t)gr.oh * gr.ow, a.threshold);
   int k = 0;
   for (; k + U <= a.K; k += U) {
     float sum[U];
-    member_sums<TIn, U, VEC>(a, gr, y, x, k, sum);
+    member_sums<TIn, U, VEC, ACT>(a, gr, y, x, k, pairs, sum);
 #pragma unroll
     for (int c = 0; c < U; c++) epi.put(k + c, sum[c]);
   }
   for (; k < a.K; k++) {
     float sum[1];
-    member_sums<TIn, 1, false>(a, gr, y, x, k, sum);
+    member_sums<TIn, 1, false, ACT>(a, gr, y, x, k, pairs, sum);
     epi.put(k, sum[0]);
   }
   epi.done();
@@ -181,24 +247,39 @@ __global__ void __launch_bounds__(AA_BACK_TILE) back_resample_merged(MergedArgs 
 
 // The kernel of an argument block: back_resample for the items of aa_back_many_plan, back_resample_merged for the groups of
 // aa_back_merged_plan; the same epilogues and element types for both.
-template <typename TIn, bool VEC, typename Epi> void launch_as(const BackArgs &a, unsigned units, hipStream_t stream) {
-  hipLaunchKernelGGL((back_resample<TIn, VEC, Epi>), dim3(units), dim3(AA_BACK_TILE), 0, stream, a);
+// What is launched: the work units, the bytes of dynamic LDS (the merged softmax's pairs; 0 otherwise), the stream.
+struct BackLaunch {
+  unsigned units, lds;
+  hipStream_t stream;
+};
+template <typename TIn, bool VEC, bool ACT, typename Epi> void launch_as(const BackArgs &a, const BackLaunch &l) {
+  hipLaunchKernelGGL((back_resample<TIn, VEC, ACT, Epi>), dim3(l.units), dim3(AA_BACK_TILE), 0, l.stream, a);
 }
-template <typename TIn, bool VEC, typename Epi> void launch_as(const MergedArgs &a, unsigned units, hipStream_t stream) {
-  hipLaunchKernelGGL((back_resample_merged<TIn, VEC, Epi>), dim3(units), dim3(AA_BACK_TILE), 0, stream, a);
+template <typename TIn, bool VEC, bool ACT, typename Epi> void launch_as(const MergedArgs &a, const BackLaunch &l) {
+  hipLaunchKernelGGL((back_resample_merged<TIn, VEC, ACT, Epi>), dim3(l.units), dim3(AA_BACK_TILE), ACT ? l.lds : 0, l.stream, a);
 }
-template <typename TIn, bool VEC, typename Args> void launch_epi(int reduce, int out_dtype, const Args &a, unsigned units, hipStream_t stream) {
-  if (reduce == AA_BACK_GREATER) launch_as<TIn, VEC, Greater>(a, units, stream);
+template <typename TIn, bool VEC, bool ACT, typename Args> void launch_epi(int reduce, int out_dtype, const Args &a, const BackLaunch &l) {
+  if (reduce == AA_BACK_GREATER) launch_as<TIn, VEC, ACT, Greater>(a, l);
   else if (reduce == AA_BACK_ARGMAX) {
-    if (out_dtype == AA_U8) launch_as<TIn, VEC, Argmax<uint8_t>>(a, units, stream);
-    else if (out_dtype == AA_I16) launch_as<TIn, VEC, Argmax<int16_t>>(a, units, stream);
-    else if (out_dtype == AA_I32) launch_as<TIn, VEC, Argmax<int32_t>>(a, units, stream);
-    else launch_as<TIn, VEC, Argmax<int64_t>>(a, units, stream);
-  } else with_float_type(out_dtype, [&](auto out) { launch_as<TIn, VEC, Values<tag_t<decltype(out)>>>(a, units, stream); });
+    if (out_dtype == AA_U8) launch_as<TIn, VEC, ACT, Argmax<uint8_t>>(a, l);
+    else if (out_dtype == AA_I16) launch_as<TIn, VEC, ACT, Argmax<int16_t>>(a, l);
+    else if (out_dtype == AA_I32) launch_as<TIn, VEC, ACT, Argmax<int32_t>>(a, l);
+    else launch_as<TIn, VEC, ACT, Argmax<int64_t>>(a, l);
+  } else with_float_type(out_dtype, [&](auto out) { launch_as<TIn, VEC, ACT, Values<tag_t<decltype(out)>>>(a, l); });
 }
-template <bool VEC, typename Args> void launch_in(int in_dtype, int reduce, int out_dtype, const Args &a, unsigned units, hipStream_t stream) {
-  with_float_type(in_dtype, [&](auto in) { launch_epi<tag_t<decltype(in)>, VEC>(reduce, out_dtype, a, units, stream); });
+template <bool VEC, bool ACT, typename Args> void launch_in(int in_dtype, int reduce, int out_dtype, const Args &a, const BackLaunch &l) {
+  with_float_type(in_dtype, [&](auto in) { launch_epi<tag_t<decltype(in)>, VEC, ACT>(reduce, out_dtype, a, l); });
 }
+// The kernel of (vector loads or not, an activation or not): a.act says which.
+template <typename Args> void launch_resample(bool vec, int in_dtype, int reduce, int out_dtype, const Args &a, const BackLaunch &l) {
+  if (a.act != AA_BACK_ACT_NONE) {
+    if (vec) launch_in<true, true>(in_dtype, reduce, out_dtype, a, l);
+    else launch_in<false, true>(in_dtype, reduce, out_dtype, a, l);
+  } else if (vec) launch_in<true, false>(in_dtype, reduce, out_dtype, a, l);
+  else launch_in<false, false>(in_dtype, reduce, out_dtype, a, l);
+}
+
+inline bool act_ok(int activation) { return activation >= AA_BACK_ACT_NONE && activation <= AA_BACK_ACT_SIGMOID; }
 
 // What a reduction stores: values a float, argmax a label, greater a byte of 0 or 1.
 inline bool out_dtype_ok(int reduce, int dt) {
@@ -207,12 +288,14 @@ inline bool out_dtype_ok(int reduce, int dt) {
   return dt == AA_BOOL || dt == AA_U8;
 }
 
-// What both planners check first, in this order: the filter; the layout; n, K and reduce (own_ok: what the caller adds to them); a label
-// type that cannot hold K - 1.
-inline int plan_prologue(int filter, int layout, int64_t n, int64_t K, int reduce, int out_dtype, bool own_ok) {
+// What both planners check first, in this order: the filter; the layout; n, K, reduce and the activation (own_ok: what the caller adds to
+// them); a label type that cannot hold K - 1.
+inline int plan_prologue(int filter, int layout, int64_t n, int64_t K, int reduce, int activation, int out_dtype, bool own_ok) {
   if (!aa_filter_valid(filter)) return AA_ERR_BAD_FILTER;
   if (layout != AA_NCHW && layout != AA_NHWC) return AA_ERR_BAD_LAYOUT;
-  if (n < 0 || n > kAAManyMax || K < 1 || K > kAAManyMax || reduce < AA_BACK_VALUES || reduce > AA_BACK_GREATER || !own_ok) return AA_ERR_BAD_SHAPE;
+  if (n < 0 || n > kAAManyMax || K < 1 || K > kAAManyMax || reduce < AA_BACK_VALUES || reduce > AA_BACK_GREATER || !act_ok(activation) ||
+      !own_ok)
+    return AA_ERR_BAD_SHAPE;
   if (reduce == AA_BACK_ARGMAX && ((out_dtype == AA_U8 && K > 256) || (out_dtype == AA_I16 && K > 32768))) return AA_ERR_BAD_SHAPE;
   return AA_OK;
 }
@@ -272,9 +355,9 @@ inline size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
 // ---- host: the planner -------------------------------------------------------------------------------------------------------------------
 size_t aa_back_desc_size(int64_t n) { return aa_desc_size(sizeof(AABackHeader), sizeof(AABackItem), n); }
 
-int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *in, int reduce, int out_dtype, void *desc_host,
-                      size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
-  int rc = plan_prologue(filter, layout, n, K, reduce, out_dtype, true);
+int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *in, int reduce, int activation, int out_dtype,
+                      void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
+  int rc = plan_prologue(filter, layout, n, K, reduce, activation, out_dtype, true);
   if (rc != AA_OK) return rc;
   if (!desc_host || !workspace_bytes || !arena_bytes || (n > 0 && (!in || !out_offsets))) return AA_ERR_NULL;
   if (desc_bytes < aa_back_desc_size(n)) return AA_ERR_WORKSPACE;
@@ -298,6 +381,7 @@ int aa_back_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_bac
   hd->magic = AA_BACK_MAGIC;
   hd->n = (int32_t)n; hd->K = (int32_t)K; hd->filter = filter; hd->layout = layout;
   hd->reduce = reduce; hd->out_dtype = out_dtype;
+  hd->reserved0 = activation;
   hd->units = units;
   hd->ws_bytes = (int64_t)ws;
   hd->arena_bytes = (int64_t)arena;
@@ -313,7 +397,7 @@ int aa_launch_back_many(const void *desc_host, const void *desc_dev, int in_dtyp
                         void *workspace_dev, size_t workspace_bytes, hipStream_t stream) {
   const AABackHeader *hd = (const AABackHeader *)desc_host;
   if (hd->magic != AA_BACK_MAGIC || !aa_filter_valid(hd->filter) || hd->n < 0 || hd->K < 1 || hd->units < 0 || hd->units > INT32_MAX ||
-      hd->reduce < AA_BACK_VALUES || hd->reduce > AA_BACK_GREATER || (hd->layout != AA_NCHW && hd->layout != AA_NHWC))
+      hd->reduce < AA_BACK_VALUES || hd->reduce > AA_BACK_GREATER || (hd->layout != AA_NCHW && hd->layout != AA_NHWC) || !act_ok(hd->reserved0))
     return AA_ERR_BAD_SHAPE;
   if (!float_dtype(in_dtype) || !out_dtype_ok(hd->reduce, hd->out_dtype)) return AA_ERR_BAD_DTYPE;
   if (hd->reduce == AA_BACK_GREATER && !(threshold - threshold == 0.0f)) return AA_ERR_BAD_SHAPE;  // (not finite)
@@ -330,8 +414,8 @@ int aa_launch_back_many(const void *desc_host, const void *desc_dev, int in_dtyp
   a.items = v.items; a.unit0 = v.prefix; a.ws = (const char *)workspace_dev; a.arena = (char *)arena_dev;
   a.threshold = threshold;
   a.n = hd->n; a.K = hd->K;
-  if (vec) launch_in<true>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
-  else launch_in<false>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
+  a.act = hd->reserved0;
+  launch_resample(vec, in_dtype, hd->reduce, hd->out_dtype, a, BackLaunch{(unsigned)hd->units, 0u, stream});
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }
@@ -346,10 +430,10 @@ size_t aa_back_merged_desc_size(int64_t n, int64_t g) {
 // aa_back_plan_host's checks in its order, with G and merge beside n, K and reduce; the groups' membership after the block's size and
 // before the items; a member's size against its group's after the member's own checks; the arena and the work units per GROUP.
 int aa_back_merged_plan_host(int filter, int layout, int64_t n, int64_t K, const aa_back_item *in, int64_t G, const int64_t *group_of, int merge,
-                             int reduce, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
+                             int reduce, int activation, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes,
                              int64_t *out_offsets) {
   const bool own_ok = G >= 0 && G <= n && (G > 0 || n == 0) && (merge == AA_BACK_MERGE_SUM || merge == AA_BACK_MERGE_MEAN);
-  int rc = plan_prologue(filter, layout, n, K, reduce, out_dtype, own_ok);
+  int rc = plan_prologue(filter, layout, n, K, reduce, activation, out_dtype, own_ok);
   if (rc != AA_OK) return rc;
   if (!desc_host || !workspace_bytes || !arena_bytes || (n > 0 && (!in || !group_of || !out_offsets))) return AA_ERR_NULL;
   if (desc_bytes < aa_back_merged_desc_size(n, G)) return AA_ERR_WORKSPACE;
@@ -368,6 +452,7 @@ int aa_back_merged_plan_host(int filter, int layout, int64_t n, int64_t K, const
   int32_t slot = 0;
   for (int64_t g = 0; g < G; g++) {
     if (groups[g].count == 0) return AA_ERR_BAD_SHAPE;  // (an empty group)
+    if (activation == AA_BACK_ACT_SOFTMAX && groups[g].count > AA_BACK_ACT_MEMBERS) return AA_ERR_BAD_SHAPE;  // (the pairs of a lane: LDS)
     groups[g].first = slot;
     slot += groups[g].count;
     groups[g].count = 0;  // (counted up again as the slots are filled)
@@ -403,6 +488,7 @@ int aa_back_merged_plan_host(int filter, int layout, int64_t n, int64_t K, const
   hd->ws_bytes = (int64_t)ws;
   hd->arena_bytes = (int64_t)arena;
   hd->G = (int32_t)G;
+  hd->reserved = activation;
   *workspace_bytes = ws;
   *arena_bytes = arena;
   return AA_OK;
@@ -415,8 +501,15 @@ int aa_launch_back_merged(const void *desc_host, const void *desc_dev, int in_dt
   const AABackMergedHeader *hd = (const AABackMergedHeader *)desc_host;
   if (hd->magic != AA_BACK_MERGED_MAGIC || !aa_filter_valid(hd->filter) || hd->n < 0 || hd->K < 1 || hd->units < 0 || hd->units > INT32_MAX ||
       hd->reduce < AA_BACK_VALUES || hd->reduce > AA_BACK_GREATER || (hd->layout != AA_NCHW && hd->layout != AA_NHWC) || hd->G < 0 ||
-      hd->G > hd->n || (hd->G == 0 && hd->n > 0) || (hd->merge != AA_BACK_MERGE_SUM && hd->merge != AA_BACK_MERGE_MEAN))
+      hd->G > hd->n || (hd->G == 0 && hd->n > 0) || (hd->merge != AA_BACK_MERGE_SUM && hd->merge != AA_BACK_MERGE_MEAN) || !act_ok(hd->reserved))
     return AA_ERR_BAD_SHAPE;
+  // a softmax plan's largest group, which the planner bounded: part of what makes the block a plan's, so looked at with the header
+  int most = 0;
+  if (hd->reserved == AA_BACK_ACT_SOFTMAX) {
+    const AABackGroup *host_groups = (const AABackGroup *)((const AABackItem *)(hd + 1) + hd->n);
+    for (int32_t g = 0; g < hd->G; g++) most = host_groups[g].count > most ? host_groups[g].count : most;
+    if (most > AA_BACK_ACT_MEMBERS) return AA_ERR_BAD_SHAPE;
+  }
   if (!float_dtype(in_dtype) || !out_dtype_ok(hd->reduce, hd->out_dtype)) return AA_ERR_BAD_DTYPE;
   if (hd->reduce == AA_BACK_GREATER && !(threshold - threshold == 0.0f)) return AA_ERR_BAD_SHAPE;  // (not finite)
   const int rc = aa_many_check_launch(hd->n, desc_dev, arena_dev, workspace_dev, workspace_bytes, hd->ws_bytes, elem_bytes(hd->out_dtype));
@@ -433,10 +526,23 @@ int aa_launch_back_merged(const void *desc_host, const void *desc_dev, int in_dt
   a.ws = (const char *)workspace_dev; a.arena = (char *)arena_dev;
   a.threshold = threshold;
   a.G = hd->G; a.K = hd->K; a.mean = hd->merge == AA_BACK_MERGE_MEAN;
+  a.act = hd->reserved;
+  // a softmax's pairs: AA_BACK_TILE of them per member of the plan's largest group; the device the launches go to — the stream's, for
+  // the null stream the current one — must admit that much LDS a workgroup
+  unsigned lds = 0;
+  if (a.act == AA_BACK_ACT_SOFTMAX) {
+    lds = (unsigned)most * AA_BACK_TILE * (unsigned)sizeof(SoftmaxPair);
+    hipDevice_t dev = 0;
+    int limit = 0;
+    if (hipStreamGetDevice(stream, &dev) != hipSuccess || hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      return AA_ERR_HIP;
+    }
+    if ((int64_t)lds > (int64_t)limit) return AA_ERR_BAD_SHAPE;
+  }
   hipLaunchKernelGGL(back_tables, dim3(2u * (unsigned)hd->n), dim3(AA_BACK_THREADS), 0, stream, a.items, (char *)workspace_dev, (int)hd->filter);
   AA_HIP_CHECK_LAUNCH();
-  if (vec) launch_in<true>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
-  else launch_in<false>(in_dtype, hd->reduce, hd->out_dtype, a, (unsigned)hd->units, stream);
+  launch_resample(vec, in_dtype, hd->reduce, hd->out_dtype, a, BackLaunch{(unsigned)hd->units, lds, stream});
   AA_HIP_CHECK_LAUNCH();
   return AA_OK;
 }

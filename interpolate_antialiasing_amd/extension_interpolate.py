@@ -48,7 +48,9 @@ Differences, all additive:
     and ``resize_embed_to_tokens_backward`` is its deterministic backward, the ordered fp32 sum of the items' gather-form adjoints;
   * ``resize_many_back(pred, sizes, mode, regions=, flips=, reduce=, threshold=, out_dtype=)``: the way back — a model's [N, K, H, W] float
     answer on the canvas resampled to every image's own size in the reference's fp32 arithmetic, as values, as the argmax over K or as
-    ``> threshold``, two launches whatever N; with ``reduce="argmax"`` the K values of a pixel are never stored;
+    ``> threshold``, two launches whatever N; with ``reduce="argmax"`` the K values of a pixel are never stored; ``activation="softmax"``
+    or ``"sigmoid"`` puts bit-exactly defined probabilities in the values' place, here and in ``resize_many_back_merged``, which sums
+    several test-time passes per image before the reduction;
   * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -1515,8 +1517,24 @@ def _back_out(name: str, reduce, out_dtype, threshold, items, k: int):
     return reduce_id, out_dtype, out_id, threshold
 
 
+def _back_activation_name(name: str, activation):
+    """activation of resize_many_back and its kin: None, "softmax" or "sigmoid"."""
+    if not (activation is None or isinstance(activation, str)) or activation not in _lib.BACK_ACT:
+        raise ValueError(f"{name}(): activation must be None, 'softmax' or 'sigmoid', got {activation!r}")
+
+
+def _back_activation(name: str, activation, reduce, pred, items) -> int:
+    """-> the planner's id of a checked activation name.  The activations have no backward: values that would carry a grad_fn are refused
+    rather than handed out detached."""
+    if activation is not None and reduce is None and torch.is_grad_enabled():
+        if pred.requires_grad if isinstance(pred, torch.Tensor) else any(t.requires_grad for t in items):
+            raise NotImplementedError(f"{name}(): activation={activation!r} is not differentiable: with reduce=None and a pred that requires "
+                                      f"grad, call it under torch.no_grad() or pass pred.detach()")
+    return _lib.BACK_ACT[activation]
+
+
 def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips=None, reduce: Optional[str] = None, threshold: float = 0.0,
-                     out_dtype=None, channels: Optional[int] = None):
+                     out_dtype=None, channels: Optional[int] = None, activation: Optional[str] = None):
     """A model's answer on the canvas, back at every image's own size: the return path of ``resize_many`` and its kin, for segmentation,
     depth and mask heads.  ``pred``: one float32 / float16 / bfloat16 GPU tensor [N, K, H, W], or a sequence of N tensors [K, H_i, W_i]
     (or [1, K, H_i, W_i]); the same K (1 .. 2^29 - 1), dtype and device for all.  Items are read where they lie, in one of two classes:
@@ -1551,23 +1569,39 @@ def resize_many_back(pred, sizes, mode: str = "bilinear", *, regions=None, flips
     batch tensor, one per list item, +0.0 outside the regions and for items the loss did not use (two launches for the whole list,
     whatever the loss uses).  The values, the arena and the launch count are the same with and without it.  The results are views of
     one arena and outputs of one autograd node: under autograd they must not be modified in place.  ``reduce="argmax"`` and
-    ``"greater"`` are not differentiable and never carry a ``grad_fn``.  Not built: fractional regions, a dense padded output, softmax
-    (several passes per image summed before the reduction: ``resize_many_back_merged``)."""
+    ``"greater"`` are not differentiable and never carry a ``grad_fn``.
+
+    ``activation``: None (everything above as it stands), ``"softmax"`` (over the K classes of a pixel) or ``"sigmoid"`` (per element),
+    applied in fp32 to ``R_i`` — before any rounding to 16 bits — inside the same two launches; the probabilities ``P_i`` then stand where
+    ``R_i`` stood: ``reduce=None`` rounds ``P_i`` once to ``out_dtype``, ``"argmax"`` and ``"greater"`` look at the fp32 ``P_i``.  ``P_i`` is
+    defined bit for bit (``tests/activation_ref.py`` restates it in numpy; ``include/aa_interp.h`` spells it out): ``aa_exp``, an fp32
+    exponential for arguments <= 0, at most 0.9916 ulp from ``exp`` over all of [-86, 0] and +0 below -86, every product and sum rounded
+    on its own; the sigmoid ``(v >= 0 ? 1 : e) / (1 + e)`` with ``e = aa_exp(-|v|)``, one correctly rounded division; the softmax in two
+    passes over ascending k — an online maximum ``m`` and denominator ``d``, then ``aa_exp(v_k - m) * (1 / d)`` — so a ``-inf`` (masked)
+    class gets +0, and a pixel with a NaN, a ``+inf`` or nothing but ``-inf`` is NaN in every class (which class the argmax then names
+    is ``numpy.argmax``'s answer: 0).  A softmax pixel's classes are resampled twice; nothing more is stored than without it.  The
+    activation is NOT differentiable: with ``reduce=None``, gradients enabled and a ``pred`` that requires grad the call raises
+    ``NotImplementedError`` rather than hand out detached probabilities — call it under ``torch.no_grad()`` or pass ``pred.detach()``.
+
+    Not built: fractional regions, a dense padded output, a backward through the activation, ``log_softmax`` (several passes per image
+    summed before the reduction: ``resize_many_back_merged``)."""
     name = "resize_many_back"
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
     if reduce not in _BACK_REDUCE:
         raise ValueError(f"{name}(): reduce must be None, 'argmax' or 'greater', got {reduce!r}")
+    _back_activation_name(name, activation)
     items, dev0, n, k = _back_items(name, pred, channels)
     sizes = _back_sizes(name, sizes, n, k)
     rects = _back_regions(name, regions, items)
     flips = _many_flips(name, flips, n)
     reduce_id, out_dtype, out_id, threshold = _back_out(name, reduce, out_dtype, threshold, items, k)
+    act_id = _back_activation(name, activation, reduce, pred, items)
     if n == 0:
         return []
     for t in items:
         _require_gpu(t, name)
-    plan = (name, mode, n, k, sizes, rects, flips, reduce, reduce_id, out_dtype, out_id, threshold)
+    plan = (name, mode, n, k, sizes, rects, flips, reduce, reduce_id, out_dtype, out_id, threshold, act_id)
     if reduce is None and torch.is_grad_enabled():
         if isinstance(pred, torch.Tensor):
             if pred.requires_grad:
@@ -1614,7 +1648,7 @@ def _resize_many_back_run(plan, items, merged=None):
     """The layout class, the plan and the two launches of resize_many_back on checked GPU items -> (N views of one arena, whether the
     items were read as interleaved classes).  merged: None, or (groups, the G groups' sizes, merge) of resize_many_back_merged, whose
     plan's sizes are the members' (each its group's): the merged planner and launch, and G views."""
-    name, mode, n, k, sizes, rects, flips, reduce, reduce_id, out_dtype, out_id, threshold = plan
+    name, mode, n, k, sizes, rects, flips, reduce, reduce_id, out_dtype, out_id, threshold, act_id = plan
     dev = items[0].device
     recs, keep, interleaved = _back_records(items, rects, sizes, flips, k)  # (keep: alive until the launches are enqueued)
     layout = _lib.NHWC if interleaved else _lib.NCHW
@@ -1626,7 +1660,8 @@ def _resize_many_back_run(plan, items, merged=None):
         desc_bytes, resample = L.aa_back_many_desc_bytes(n), L.aa_resample_back_many
 
         def planner(desc, nbytes, ws_bytes):
-            return L.aa_back_many_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, reduce_id, out_id, desc, nbytes, ws_bytes, ctypes.byref(arena_bytes), offs)
+            return L.aa_back_many_plan_act(_lib.FILTER_IDS[mode], layout, n, k, recs, reduce_id, act_id, out_id, desc, nbytes, ws_bytes,
+                                           ctypes.byref(arena_bytes), offs)
     else:
         groups, out_sizes, merge = merged
         g = len(out_sizes)
@@ -1634,8 +1669,8 @@ def _resize_many_back_run(plan, items, merged=None):
         desc_bytes, resample = L.aa_back_merged_desc_bytes(n, g), L.aa_resample_back_merged
 
         def planner(desc, nbytes, ws_bytes):
-            return L.aa_back_merged_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, g, group_of, _lib.BACK_MERGE[merge], reduce_id, out_id, desc, nbytes,
-                                         ws_bytes, ctypes.byref(arena_bytes), offs)
+            return L.aa_back_merged_plan_act(_lib.FILTER_IDS[mode], layout, n, k, recs, g, group_of, _lib.BACK_MERGE[merge], reduce_id, act_id, out_id,
+                                             desc, nbytes, ws_bytes, ctypes.byref(arena_bytes), offs)
     arena = _many_run(
         name, dev, desc_bytes, planner, lambda: torch.empty((arena_bytes.value // es,), dtype=out_dtype, device=dev),
         lambda desc_host, desc_dev, out, ws, stream: resample(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], threshold, out.data_ptr(),
@@ -1699,7 +1734,8 @@ def _back_groups(name: str, groups, n: int, g: int):
 
 
 def resize_many_back_merged(pred, groups, sizes, mode: str = "bilinear", *, regions=None, flips=None, merge: str = "sum",
-                            reduce: Optional[str] = None, threshold: float = 0.0, out_dtype=None, channels: Optional[int] = None):
+                            reduce: Optional[str] = None, threshold: float = 0.0, out_dtype=None, channels: Optional[int] = None,
+                            activation: Optional[str] = None):
     """Test-time augmentation's merge: several passes per image — scales, mirrored or not — each brought back to the image's own size as
     ``resize_many_back`` does, un-mirrored, SUMMED per image, and only then reduced to a label, a mask or values.  ``pred``, ``regions``,
     ``flips``, ``mode``, ``reduce``, ``threshold``, ``out_dtype`` and ``channels`` are ``resize_many_back``'s, with its checks: N items, one
@@ -1728,7 +1764,17 @@ def resize_many_back_merged(pred, groups, sizes, mode: str = "bilinear", *, regi
     output — for "sum" the same tensor for every member, read where it lies; for "mean" ``G_g.float() / M_g``, one division per used
     group; None for the members of a group the loss did not use.  ``"argmax"`` and ``"greater"`` never carry a ``grad_fn``.
 
-    Not built: softmax before the sum (``exp`` has no bit-exact definition here), per-member weights, a maximum instead of the sum,
+    ``activation``: None, ``"softmax"`` or ``"sigmoid"``, ``resize_many_back``'s, applied to every member's ``R_i`` BEFORE the sum: with
+    ``P_i`` as that call defines it, ``S_g`` adds the members' ``P_i`` in the same order, and the mean and the reductions follow
+    unchanged — the standard test-time augmentation, softmax per pass, probabilities summed, then the argmax; or sigmoid, ``merge="mean"``
+    and ``reduce="greater", threshold=0.5`` for mask heads.  A group of one member is ``resize_many_back``'s item with the same
+    activation, bit for bit.  Still two launches and no workspace beyond the tables: for a softmax a lane first walks every member's
+    classes once for its maximum and denominator, keeps the pairs in LDS, and then adds probabilities class by class; that bounds a
+    softmax group to 16 members (``ValueError`` naming the group; the sigmoid and None have no limit).  Not differentiable: with
+    ``reduce=None``, gradients enabled and a ``pred`` that requires grad the call raises ``NotImplementedError`` — call it under
+    ``torch.no_grad()`` or pass ``pred.detach()``.
+
+    Not built: per-member weights, a maximum instead of the sum, a backward through the activation, ``log_softmax``,
     sliding-window overlap-add (members placed at different positions of the output), a dense padded output."""
     name = "resize_many_back_merged"
     if mode not in _lib.FILTER_IDS:
@@ -1737,6 +1783,7 @@ def resize_many_back_merged(pred, groups, sizes, mode: str = "bilinear", *, regi
         raise ValueError(f"{name}(): reduce must be None, 'argmax' or 'greater', got {reduce!r}")
     if merge not in _lib.BACK_MERGE:
         raise ValueError(f"{name}(): merge must be 'sum' or 'mean', got {merge!r}")
+    _back_activation_name(name, activation)
     items, dev0, n, k = _back_items(name, pred, channels)
     try:
         sizes = list(sizes)
@@ -1744,14 +1791,20 @@ def resize_many_back_merged(pred, groups, sizes, mode: str = "bilinear", *, regi
         raise ValueError(f"{name}(): sizes must be G pairs (oh, ow), got {sizes!r}") from None
     sizes = _back_sizes(name, sizes, len(sizes), k)
     groups, counts = _back_groups(name, groups, n, len(sizes))
+    if activation == "softmax":
+        for j, c in enumerate(counts):
+            if c > _lib.BACK_ACT_MEMBERS:
+                raise ValueError(f"{name}(): group {j} (sizes[{j}]) has {c} members: activation='softmax' takes at most "
+                                 f"{_lib.BACK_ACT_MEMBERS} per group")
     rects = _back_regions(name, regions, items)
     flips = _many_flips(name, flips, n)
     reduce_id, out_dtype, out_id, threshold = _back_out(name, reduce, out_dtype, threshold, items, k)
+    act_id = _back_activation(name, activation, reduce, pred, items)
     if n == 0:
         return []
     for t in items:
         _require_gpu(t, name)
-    plan = (name, mode, n, k, [sizes[g] for g in groups], rects, flips, reduce, reduce_id, out_dtype, out_id, threshold)
+    plan = (name, mode, n, k, [sizes[g] for g in groups], rects, flips, reduce, reduce_id, out_dtype, out_id, threshold, act_id)
     merged = (groups, sizes, merge)
     if reduce is None and torch.is_grad_enabled():
         if isinstance(pred, torch.Tensor):

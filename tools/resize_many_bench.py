@@ -112,6 +112,14 @@ Per contestant: kernel launches, ms per batch, the growth of torch.cuda.max_memo
 fit the device's memory — (b) at K = 150 needs 96 float32 [K, oh, ow] tensors, 334 GB — is reported as such and not timed.  No number
 is a bar: the output is written down as measured, profiles/resize_many_back_merged.txt (--rounds 5 --batches 3 keeps the run short).
 
+--tta --activation softmax|sigmoid: the same geometry with the activation per pass and the PROBABILITIES summed — (a) the loop a user
+writes today, linear_forward, softmax(0) (or sigmoid), flip, add per member, argmax per image; (c) resize_many_back_merged(activation=,
+reduce="argmax"); (d) the same call with activation=None, so that (c) against (d) is what the activation costs.  --logits --activation
+softmax|sigmoid: probabilities at the images' sizes, reduce=None — (a) linear_forward and softmax per item, (c) resize_many_back(
+activation=), (d) the call with activation=None.  Launches, ms per batch with the spread rule and peak memory as above; the share of
+labels (the largest difference of the probabilities) by which (a) and (c) differ is reported, never asserted: torch's exp is not this
+library's aa_exp.  Nothing is promised to be faster; where the loop wins the line says so.  profiles/resize_many_back_activation.txt.
+
 --logits-backward: the gradient's way — gradients [K, oh_i, ow_i] at the images' own sizes back to the canvas, bilinear, odd items
 flipped, float32 and bfloat16, resize_many_back_backward (two launches) against the loop a user writes today: linear_backward per item
 (its table cache warm), the gradient flipped where needed, copied into a zeroed canvas.  Two workloads: "small", N = 64, K = 21, image
@@ -1028,6 +1036,189 @@ def tta(args, torch, aa, timed):
             torch.cuda.empty_cache()
 
 
+def _run_contestants(args, torch, timed, contestants):
+    """A generator of two steps.  First every contestant is warmed (one that does not fit the device's memory is reported and not timed)
+    -> {key: the warm-up's result, kept for the first two; None otherwise}.  Then they are timed, alternating, and printed: ms per batch
+    as median [min .. max], the kernel launches and the growth of torch.cuda.max_memory_allocated over one call
+    -> {a key's first letter: (median, min, max)}."""
+    results, fits = {}, {}
+    for key, fn in contestants.items():
+        try:
+            r = fn()
+            results[key] = r if len(results) < 2 else None  # (the first two are compared; a third set of outputs need not stay)
+            del r
+            fn()
+            torch.cuda.synchronize()
+            fits[key] = True
+        except torch.cuda.OutOfMemoryError:
+            results[key], fits[key] = None, False
+            torch.cuda.empty_cache()
+    yield results
+    results.clear()
+    torch.cuda.empty_cache()
+    times = {key: [] for key in contestants if fits[key]}
+    for _ in range(args.rounds):
+        for key in times:
+            times[key].append(timed(contestants[key]))
+    stat = {}
+    for key in contestants:
+        if not fits[key]:
+            print(f"  {key:76s} does not fit the device's memory: not timed")
+            continue
+        v = times[key]
+        stat[key[0]] = (statistics.median(v), min(v), max(v))
+        launches = count_launches(torch, contestants[key])
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.max_memory_allocated()
+        r = contestants[key]()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - before
+        del r
+        m, lo, hi = stat[key[0]]
+        print(f"  {key:76s} {m:9.3f} [{lo:9.3f} .. {hi:9.3f}]   launches {launches if launches is not None else 'not measured'}"
+              f"   peak {peak / 1e6:10.1f} MB")
+    yield stat
+
+
+def _against(stat, c, other, what):
+    """One line: contestant c against `other`, with the bench's spread rule (a median gain counts when it exceeds the two spreads)."""
+    if c not in stat or other not in stat:
+        return
+    (mc, lc, hc), (mo, lo, ho) = stat[c], stat[other]
+    spreads = (ho - lo) + (hc - lc)
+    if mo - mc > spreads:
+        verdict = f"({c}) is faster"
+    elif mc - mo > spreads:
+        verdict = f"({other}) WINS: ({c}) is slower by more than the spreads"
+    else:
+        verdict = f"({c}) and ({other}) are NOT APART by more than the spreads"
+    print(f"  ({c}) against ({other}), {what}: {mo / mc:.2f} x; median gain {mo - mc:.3f} ms, the two spreads together {spreads:.3f} ms: {verdict}")
+
+
+def tta_activation(args, torch, aa, timed):
+    """--tta --activation: the standard test-time augmentation — per pass the resized logits through a softmax (or sigmoid), un-mirrored,
+    the PROBABILITIES summed, then the argmax — on --tta's geometry.  (a) is the loop a user writes today; (c) is
+    resize_many_back_merged(activation=..., reduce='argmax'); (d) is the same call with activation=None, so (c) - (d) is what the
+    activation costs.  torch's exp is not this library's, so near-ties may fall the other way: the share of differing labels is
+    reported, not asserted."""
+    from interpolate_antialiasing_amd import boxmath
+
+    act = args.activation
+    n, canvases = 16, (384, 512, 640)
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    passes = [(c, flip) for c in canvases for flip in (False, True)]
+    regions, flips, groups = [], [], []
+    for c, flip in passes:  # (a batch is laid out pass by pass: the groups interleave)
+        regions += boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=c), "center", (c, c))
+        flips += [flip] * n
+        groups += list(range(n))
+    pixels = sum(h * w for h, w in shapes)
+    print(f"resize_many_bench --tta --activation {act}: N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), "
+          f"{pixels / 1e6:.1f} M output pixels, each from M = {len(passes)} passes: [N, K, c, c] logits on letterbox canvases c = "
+          f"{', '.join(map(str, canvases))} (fit_sizes(longer=c), 'center'), plain and mirrored; bilinear; {act} per pass, probabilities summed in "
+          f"pass order, argmax over K; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for k in (19, 150):
+        for dtype in (torch.float32, torch.bfloat16):
+            batches = [torch.randn((n, k, c, c), device="cuda", generator=gen).to(dtype) for c, _ in passes]
+            items = [b[i] for b in batches for i in range(n)]
+            members = [[p * n + i for p in range(len(passes))] for i in range(n)]
+
+            def loop():
+                out = []
+                for i in range(n):
+                    s = None
+                    for j in members[i]:
+                        y0, x0, h, w = regions[j]
+                        r = aa.linear_forward(items[j][:, y0:y0 + h, x0:x0 + w].float()[None], list(shapes[i]))[0]
+                        r = r.softmax(0) if act == "softmax" else r.sigmoid_()
+                        r = r.flip(-1) if flips[j] else r
+                        s = r if s is None else s.add_(r)
+                    out.append(s.argmax(0))
+                return out
+
+            def merged():
+                return aa.resize_many_back_merged(items, groups, shapes, regions=regions, flips=flips, reduce="argmax", activation=act)
+
+            def merged_none():
+                return aa.resize_many_back_merged(items, groups, shapes, regions=regions, flips=flips, reduce="argmax")
+
+            a_key = f"a: loop: linear_forward, {act}, flip, add per member; argmax per image"
+            c_key = f"c: resize_many_back_merged(activation='{act}', reduce='argmax')"
+            contestants = {a_key: loop, c_key: merged, "d: resize_many_back_merged(activation=None, reduce='argmax'): summed logits": merged_none}
+            run = _run_contestants(args, torch, timed, contestants)
+            results = next(run)
+            note = "(a) does not fit"
+            if results[a_key] is not None:
+                differ = sum(int((p != q).sum()) for p, q in zip(results[a_key], results[c_key]))
+                note = f"(a) differs from (c) at {differ} of {pixels} labels ({100.0 * differ / pixels:.5f} %)"
+            del results
+            print(f"\nK = {k}, {str(dtype).replace('torch.', '')}: {note}")
+            stat = next(run)
+            _against(stat, "c", "a", "the call against the loop")
+            _against(stat, "d", "c", "what the activation costs")
+            del batches, items
+            torch.cuda.empty_cache()
+
+
+def logits_activation(args, torch, aa, timed):
+    """--logits --activation: probabilities at the images' own sizes, reduce=None, on --logits' geometry.  (a) is the loop a user writes
+    today, linear_forward and softmax (or sigmoid) per item; (c) is resize_many_back(activation=...); (d) the same call with
+    activation=None.  The largest difference between (a) and (c) is reported, not asserted (torch's exp is not this library's)."""
+    from interpolate_antialiasing_amd import boxmath
+
+    act = args.activation
+    n, canvas = 16, (512, 512)
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    regions = boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=canvas[0]), "center", canvas)
+    pixels = sum(h * w for h, w in shapes)
+    print(f"resize_many_bench --logits --activation {act}: [N, K, {canvas[0]}, {canvas[1]}] logits on a letterbox canvas (fit_sizes(longer="
+          f"{canvas[0]}), 'center') back to N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), {pixels / 1e6:.1f} M "
+          f"output pixels; bilinear; {act} over K, probabilities in the logits' dtype; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for k in (19, 150):
+        for dtype in (torch.float32, torch.bfloat16):
+            x = torch.randn((n, k) + canvas, device="cuda", generator=gen).to(dtype)
+
+            def loop():
+                out = []
+                for i, (y0, x0, h, w) in enumerate(regions):
+                    r = aa.linear_forward(x[i, :, y0:y0 + h, x0:x0 + w].float()[None], list(shapes[i]))[0]
+                    out.append((r.softmax(0) if act == "softmax" else r.sigmoid_()).to(dtype))
+                return out
+
+            def call():
+                return aa.resize_many_back(x, shapes, regions=regions, activation=act)
+
+            def call_none():
+                return aa.resize_many_back(x, shapes, regions=regions)
+
+            a_key = f"a: loop: linear_forward(crop.float()), {act}, .to(dtype) per item"
+            c_key = f"c: resize_many_back(activation='{act}', reduce=None)"
+            contestants = {a_key: loop, c_key: call, "d: resize_many_back(activation=None, reduce=None): logits": call_none}
+            run = _run_contestants(args, torch, timed, contestants)
+            results = next(run)
+            note = "a contestant does not fit"
+            if results[a_key] is not None and results[c_key] is not None:
+                worst = max(float((p.float() - q.float()).abs().max()) for p, q in zip(results[a_key], results[c_key]))
+                note = f"(a) and (c) differ by at most {worst:.3e}"
+            del results
+            print(f"\nK = {k}, {str(dtype).replace('torch.', '')}: {note}")
+            stat = next(run)
+            _against(stat, "c", "a", "the call against the loop")
+            _against(stat, "d", "c", "what the activation costs")
+            del x
+            torch.cuda.empty_cache()
+
+
 def back_bwd_workload(which, torch, k, dtype):
     """The two geometries of --logits-backward -> (canvas, regions, flips, gradients [K, oh_i, ow_i] on the GPU, their bytes): "large",
     --logits' 16 camera-sized images from a 512 x 512 letterbox canvas; "small", 64 images with sides drawn from 240 .. 640 from a
@@ -1139,6 +1330,9 @@ def main():
                     "canvas, against the per-item loop of linear_backward into a zeroed canvas; --logits' geometry and 64 small items")
     ap.add_argument("--tta", action="store_true", help="only resize_many_back_merged: 6 test-time passes per image summed and reduced to the argmax, "
                     "against resize_many_back(reduce=None) plus torch adds and against the per-member loop of linear_forward")
+    ap.add_argument("--activation", choices=("softmax", "sigmoid"), default=None,
+                    help="with --tta or --logits: the activation before the sum / the store, against the loop with torch's softmax / sigmoid "
+                    "and against the same call with activation=None")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -1244,13 +1438,13 @@ def main():
         embed(args, torch, aa, timed)
         return
     if args.logits:
-        logits(args, torch, aa, timed)
+        (logits_activation if args.activation else logits)(args, torch, aa, timed)
         return
     if args.logits_backward:
         logits_backward(args, torch, aa, timed)
         return
     if args.tta:
-        tta(args, torch, aa, timed)
+        (tta_activation if args.activation else tta)(args, torch, aa, timed)
         return
 
     print(f"resize_many_bench: N = {N} interleaved uint8 images, H and W in [256, 1024] (seed {SEED}), one RandomResizedCrop box each -> {OUT}")
