@@ -32,7 +32,9 @@ extern "C" {
                                    and the aa_dtype values AA_I16 .. AA_BOOL that only they take; aa_back_many_bwd_desc_bytes,
                                    aa_back_many_bwd_plan, aa_resample_back_many_bwd, with aa_back_bwd_item; aa_back_merged_desc_bytes,
                                    aa_back_merged_plan, aa_resample_back_merged; aa_back_many_plan_act, aa_back_merged_plan_act
-                                   (a softmax or sigmoid before the reduction), with AA_BACK_ACT_* */
+                                   (a softmax or sigmoid before the reduction), with AA_BACK_ACT_*; aa_back_confusion_desc_bytes,
+                                   aa_back_merged_confusion_desc_bytes, aa_back_confusion_plan, aa_back_merged_confusion_plan,
+                                   aa_resample_back_confusion, with aa_back_target */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -712,6 +714,49 @@ int aa_back_merged_plan_act(int filter, int layout, int64_t n, int64_t K, const 
                             int64_t *out_offsets /* G, bytes */);
 int aa_resample_back_merged(const void *desc_host, const void *desc_dev, int in_dtype, float threshold, void *arena_dev, size_t arena_bytes,
                             void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back, confusion matrices: the label map compared with a target where it is computed --------------------------
+ * Evaluation: the label map of an image is compared at once with its ground truth and dropped.  With L_i, bit for bit, the [oh_i, ow_i]
+ * label map aa_back_many_plan_act's reduce 1 gives item i — for the merged form aa_back_merged_plan_act's reduce 1 gives group i — the
+ * lowest-index and NaN rules, the flip, the activations and the softmax group bound included, and T_i the output's target, an integer
+ * [oh_i, ow_i] image, output i of the result is the K x K int64 block
+ *   conf[i, t, p] = the number of (y, x) with T_i[y, x] == t and L_i[y, x] == p, for 0 <= t < K;
+ * a pixel whose target lies outside 0 .. K - 1 (255, -1, -100) is not counted.  The result is dense, [outputs, K, K]; every element is
+ * written, an output whose pixels are all ignored is zeros.  The adds are integer, so the bits do not depend on n, on the launch shape
+ * or on the run.  No label map is stored.
+ * aa_back_target: row y, column x of the target at data_dev + (y * stride_row + x) ELEMENTS of target_dtype — AA_U8, AA_I16, AA_I32 or
+ * AA_I64, one type per call — stride_row non-negative (not looked at for one row); its size is the item's (the group's) oh, ow.
+ * aa_back_confusion_plan and aa_back_merged_confusion_plan are host arithmetic only.  The block is the sections of aa_back_many_plan's
+ * (aa_back_merged_plan's) after a header of its own, then one record per output: the target's pointer and row stride, the element
+ * offset i * K * K of its block and its count of row tiles; a work unit is 8 consecutive output rows times 256 columns.  desc_bytes >=
+ * aa_back_confusion_desc_bytes(n) (aa_back_merged_confusion_desc_bytes(n, G)); the workspace is aa_back_many_plan's for the same items;
+ * *conf_elems is outputs * K * K.  Errors in aa_back_many_plan's (aa_back_merged_plan_act's) order with these added: AA_ERR_BAD_SHAPE
+ * beside n and K for K * K * outputs beyond 2^40; `targets` beside the pointers (AA_ERR_NULL, n > 0); per output, after its item's (after
+ * all the members') checks, AA_ERR_NULL for a null target, AA_ERR_STRIDES for a negative row stride, AA_ERR_BAD_SHAPE for more work
+ * units than one grid holds; last AA_ERR_BAD_DTYPE for a target_dtype that is none of the four.
+ * aa_resample_back_confusion serves both blocks and enqueues TWO launches whatever n and the sizes: the table kernel, whose further
+ * workgroups zero conf_dev (no memset), and a resample whose lanes walk down the 8 rows of their unit, compute each pixel's label in
+ * registers, and count (target, label) pairs per wave — ballots over equal keys, then 64 (key, count) slots of LDS per wave — so that
+ * the only global writes are 64-bit integer atomic adds of evicted or flushed counts.  Checks as aa_resample_back_many's
+ * (aa_resample_back_merged's), in their order: conf_dev 8-byte aligned (AA_ERR_BAD_SHAPE), conf_elems >= the plan's
+ * (AA_ERR_WORKSPACE), every target aligned to its element beside the sources (AA_ERR_STRIDES).  Every check comes before the first
+ * launch; nothing is allocated, synchronised or read back.  n == 0 launches nothing.  Not built: one summed K x K block (the sum of the
+ * result over its outputs), per-pixel weights, top-k.  Added without an ABI version change (additive). */
+typedef struct aa_back_target {
+  const void *data_dev; /* the target's first element */
+  int64_t stride_row;   /* in ELEMENTS */
+} aa_back_target;
+size_t aa_back_confusion_desc_bytes(int64_t n);
+size_t aa_back_merged_confusion_desc_bytes(int64_t n, int64_t g);
+int aa_back_confusion_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, const aa_back_target *targets /* n */,
+                           int target_dtype, int activation /* AA_BACK_ACT_* */, void *desc_host, size_t desc_bytes, size_t *workspace_bytes,
+                           int64_t *conf_elems);
+int aa_back_merged_confusion_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G,
+                                  const int64_t *group_of /* n */, int merge /* 0 sum, 1 mean */, const aa_back_target *targets /* G */,
+                                  int target_dtype, int activation /* AA_BACK_ACT_* */, void *desc_host, size_t desc_bytes,
+                                  size_t *workspace_bytes, int64_t *conf_elems);
+int aa_resample_back_confusion(const void *desc_host, const void *desc_dev, int in_dtype, void *conf_dev, size_t conf_elems, void *workspace_dev,
+                               size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged predictions back, backward: N gradients [K, oh_i, ow_i] to N canvases [K, H_i, W_i] ---------------------------------------
  * The backward of aa_resample_back_many's reduce 0, for losses taken at every image's own size.  Item i has a canvas [H_i, W_i], the

@@ -64,6 +64,8 @@ EXPORTS = (
     "aa_back_many_bwd_desc_bytes", "aa_back_many_bwd_plan", "aa_resample_back_many_bwd",
     "aa_back_merged_desc_bytes", "aa_back_merged_plan", "aa_resample_back_merged",
     "aa_back_many_plan_act", "aa_back_merged_plan_act",
+    "aa_back_confusion_desc_bytes", "aa_back_merged_confusion_desc_bytes", "aa_back_confusion_plan", "aa_back_merged_confusion_plan",
+    "aa_resample_back_confusion",
 )
 
 
@@ -257,6 +259,26 @@ class BackGroup(ctypes.Structure):
                 ("xtiles", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class BackTargetIn(ctypes.Structure):
+    """aa_back_target: one output's integer target of the confusion call (stride_row in ELEMENTS)."""
+    _fields_ = [("data_dev", ctypes.c_void_p), ("stride_row", ctypes.c_int64)]
+
+
+class BackConfHeader(ctypes.Structure):
+    """Head of the block aa_back_confusion_plan and aa_back_merged_confusion_plan write (csrc/aa_many_back_confusion.h AABackConfHeader;
+    opaque to C callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("K", ctypes.c_int32), ("filter", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("activation", ctypes.c_int32), ("target_dtype", ctypes.c_int32), ("merge", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("conf_elems", ctypes.c_int64), ("G", ctypes.c_int32), ("merged", ctypes.c_int32)]
+
+
+class BackConfTarget(ctypes.Structure):
+    """One output of that block (csrc/aa_many_back_confusion.h AABackConfTarget): its target and row stride in elements, the element
+    offset of its K x K block, its row tiles."""
+    _fields_ = [("tgt", ctypes.c_void_p), ("stride_row", ctypes.c_int64), ("conf_off", ctypes.c_int64), ("ytiles", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class BackBwdItemIn(ctypes.Structure):
     """aa_back_bwd_item: one item of the ragged return path's backward (strides in ELEMENTS; grad_dev None: the item has no gradient)."""
     _fields_ = [("grad_dev", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("H", ctypes.c_int64),
@@ -316,6 +338,7 @@ BACK_MERGE = {"sum": 0, "mean": 1}  # aa_back_merged_plan merge (csrc/aa_many_ba
 BACK_ACT = {None: 0, "softmax": 1, "sigmoid": 2}  # aa_back_many_plan_act activation (include/aa_interp.h AA_BACK_ACT_*)
 BACK_ACT_MEMBERS = 16  # the most members of a group of a merged softmax plan (csrc/aa_many_back.h AA_BACK_ACT_MEMBERS)
 BACK_TILE = 256     # output columns per work unit of the return path's resample (csrc/aa_many_back.h AA_BACK_TILE)
+BACK_CONF_ROWS = 8  # output rows per work unit of the confusion call's resample (csrc/aa_many_back_confusion.h AA_BACK_CONF_ROWS)
 BACK_BWD_ROWS, BACK_BWD_COLS = 4, 64  # canvas rows and columns per work unit of the return path's backward (csrc/aa_many_back_bwd.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
@@ -364,6 +387,24 @@ def back_merged_desc_view(buf, n: int, g: int):
     members = (ctypes.c_int32 * n).from_buffer(buf, at)
     at += (4 * n + 7) & ~7
     return hd, items, groups, members, (ctypes.c_int64 * (g + 1)).from_buffer(buf, at)
+
+
+def back_conf_desc_view(buf, n: int, g=None):
+    """(header, items, groups, members, unit0, targets) of a confusion plan's block held in a ctypes buffer: the sections of
+    back_desc_view (g None: no groups, no members) or back_merged_desc_view after a BackConfHeader, then one BackConfTarget per output."""
+    hd = BackConfHeader.from_buffer(buf, 0)
+    at = ctypes.sizeof(BackConfHeader)
+    items = (BackItem * n).from_buffer(buf, at)
+    at += n * ctypes.sizeof(BackItem)
+    groups = members = None
+    if g is not None:
+        groups = (BackGroup * g).from_buffer(buf, at)
+        at += g * ctypes.sizeof(BackGroup)
+        members = (ctypes.c_int32 * n).from_buffer(buf, at)
+        at += (4 * n + 7) & ~7
+    outs = n if g is None else g
+    unit0 = (ctypes.c_int64 * (outs + 1)).from_buffer(buf, at)
+    return hd, items, groups, members, unit0, (BackConfTarget * outs).from_buffer(buf, at + 8 * (outs + 1))
 
 
 def back_bwd_desc_view(buf, n: int):
@@ -545,6 +586,18 @@ def load() -> ctypes.CDLL:
     L.aa_back_merged_plan_act.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), i64, ctypes.POINTER(i64), i32, i32, i32, i32, vp, sz,
                                           ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(i64)]
     L.aa_back_merged_plan_act.restype = i32
+    L.aa_back_confusion_desc_bytes.argtypes = [i64]
+    L.aa_back_confusion_desc_bytes.restype = sz
+    L.aa_back_merged_confusion_desc_bytes.argtypes = [i64, i64]
+    L.aa_back_merged_confusion_desc_bytes.restype = sz
+    L.aa_back_confusion_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), ctypes.POINTER(BackTargetIn), i32, i32, vp, sz,
+                                         ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_back_confusion_plan.restype = i32
+    L.aa_back_merged_confusion_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), i64, ctypes.POINTER(i64), i32,
+                                                ctypes.POINTER(BackTargetIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_back_merged_confusion_plan.restype = i32
+    L.aa_resample_back_confusion.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp]
+    L.aa_resample_back_confusion.restype = i32
     L.aa_back_many_bwd_desc_bytes.argtypes = [i64]
     L.aa_back_many_bwd_desc_bytes.restype = sz
     L.aa_back_many_bwd_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackBwdItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),

@@ -10,6 +10,7 @@
 #include "aa_embed_many.h"
 #include "aa_many_back.h"
 #include "aa_many_back_bwd.h"
+#include "aa_many_back_confusion.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_maps.h"
@@ -656,6 +657,29 @@ int aa_resample_back_merged(const void *desc_host, const void *desc_dev, int in_
                             void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_back_merged(desc_host, desc_dev, in_dtype, threshold, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- ragged predictions back, confusion matrices: the labels counted against a target, never stored ----------------------------------------
+size_t aa_back_confusion_desc_bytes(int64_t n) { return aa_back_conf_desc_size(n, 0, 0); }
+size_t aa_back_merged_confusion_desc_bytes(int64_t n, int64_t g) { return aa_back_conf_desc_size(n, g, 1); }
+
+int aa_back_confusion_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, const aa_back_target *targets, int target_dtype,
+                           int activation, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, int64_t *conf_elems) {
+  return aa_back_conf_plan_host(filter, layout, n, K, items, 0, 0, nullptr, 0, targets, target_dtype, activation, desc_host, desc_bytes,
+                                workspace_bytes, conf_elems);
+}
+
+int aa_back_merged_confusion_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, int64_t G, const int64_t *group_of,
+                                  int merge, const aa_back_target *targets, int target_dtype, int activation, void *desc_host, size_t desc_bytes,
+                                  size_t *workspace_bytes, int64_t *conf_elems) {
+  return aa_back_conf_plan_host(filter, layout, n, K, items, 1, G, group_of, merge, targets, target_dtype, activation, desc_host, desc_bytes,
+                                workspace_bytes, conf_elems);
+}
+
+int aa_resample_back_confusion(const void *desc_host, const void *desc_dev, int in_dtype, void *conf_dev, size_t conf_elems, void *workspace_dev,
+                               size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_back_confusion(desc_host, desc_dev, in_dtype, conf_dev, conf_elems, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- ragged predictions back, backward -----------------------------------------------------------------------------------------------------

@@ -71,7 +71,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -1835,6 +1835,125 @@ class _ResizeManyBackMerged(torch.autograd.Function):
         if merge == "mean":
             grads = [None if g is None else g.float() / m for g, m in zip(grads, ctx.counts)]
         return (None,) * 4 + _back_input_grads(ctx, [grads[g] for g in groups], first=4)
+
+
+_BACK_TARGET_DTYPES = {torch.uint8: _lib.U8, torch.int16: _lib.I16, torch.int32: _lib.I32, torch.int64: _lib.I64}
+
+
+def _back_targets(name: str, targets, outs: int, what: str):
+    """targets of resize_many_back_confusion, checked -> (the tensors, their sizes (oh, ow), the aa_dtype of their one integer type)."""
+    try:
+        targets = list(targets)
+    except TypeError:
+        raise ValueError(f"{name}(): targets must be a sequence of integer tensors [oh, ow], got {targets!r}") from None
+    if outs is not None and len(targets) != outs:
+        raise ValueError(f"{name}(): targets must hold one entry per {what} ({outs}), got {len(targets)}")
+    for i, t in enumerate(targets):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}(): targets[{i}] must be Tensor")
+        if t.dtype not in _BACK_TARGET_DTYPES:
+            raise TypeError(f"{name}(): targets[{i}] of {t.dtype} is not an integer target; torch.uint8, torch.int16, torch.int32 or torch.int64")
+        if t.dtype != targets[0].dtype:
+            raise ValueError(f"{name}(): every target must have the same dtype: targets[{i}] is {t.dtype}, targets[0] {targets[0].dtype}")
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name}(): targets[{i}] must be a non-empty [oh, ow], got {list(t.shape)}")
+    return targets, [(int(t.shape[0]), int(t.shape[1])) for t in targets], _BACK_TARGET_DTYPES[targets[0].dtype] if targets else _lib.I64
+
+
+def resize_many_back_confusion(pred, targets, mode: str = "bilinear", *, regions=None, flips=None, groups=None, merge: str = "sum",
+                               activation: Optional[str] = None, channels: Optional[int] = None) -> torch.Tensor:
+    """Evaluation's last step fused into the return path: the per-image confusion matrices of the resampled prediction against the
+    ground truth — ``fast_hist`` — without the label maps ever reaching memory.  ``pred``, ``regions``, ``flips``, ``mode``,
+    ``activation`` and ``channels`` are ``resize_many_back``'s, with its checks; with ``groups=`` (N integers) and ``merge`` the N items
+    are members of G groups exactly as in ``resize_many_back_merged``, with its checks (every group has a member; a softmax group at most
+    16).  ``targets``: a sequence of N GPU tensors — G of them with ``groups`` — each an integer ``[oh_i, ow_i]`` ground truth on
+    ``pred``'s device, all uint8, int16, int32 or int64.  The sizes of the call are the targets' shapes: what ``sizes=`` is to the
+    other two calls.  Targets are read where they lie, whatever their row stride; one whose column stride is not 1 is copied first.
+
+    With ``L_i``, bit for bit, the label map ``resize_many_back(pred, sizes, mode, regions=, flips=, reduce="argmax", activation=)``
+    gives item i — with ``groups`` the one ``resize_many_back_merged(..., merge=, activation=, reduce="argmax")`` gives group i: the
+    lowest index of the greatest fp32 value, a NaN greater than every number — and ``T_i = targets[i]``, the result is ONE int64 tensor
+    ``[N, K, K]`` (``[G, K, K]``):
+
+        ``conf[i, t, p]`` = the number of pixels (y, x) with ``T_i[y, x] == t`` and ``L_i[y, x] == p``, for ``0 <= t < K``.
+
+    A pixel whose target lies outside 0 .. K - 1 is not counted — 255, -1 and -100 alike, so there is no ``ignore_index`` — which is
+    ``k = (t >= 0) & (t < K); bincount(K * t[k] + p[k], minlength=K * K)``.  Every element is written; an image whose pixels are all
+    ignored gives zeros; ``conf[i].sum()`` is the number of its counted pixels.  mIoU, per-class accuracy and Dice follow from it.
+    Everything is integers: the bits do not depend on N, on the launch shape or on the run.  ``K * K * N`` is at most 2^40.
+
+    Two launches whatever N and the sizes, and one non-blocking copy of a packed descriptor: the table kernel, whose further workgroups
+    zero the result (no memset), and a resample whose lanes walk down 8 rows of 256 columns, compute each pixel's label in registers
+    as the argmax calls do, and count (target, label) pairs per wave: lanes holding the same pair are balloted and counted, the counts
+    kept in 64 slots of LDS per wave, and only evicted or flushed counts reach memory, as 64-bit integer atomic adds.  Nothing of the
+    size of a label map is allocated.  Never differentiable: the result carries no ``grad_fn`` and a ``pred`` that requires grad is
+    taken as it is.  N == 0 gives an empty ``[0, K, K]``.
+
+    Not built: one summed ``[K, K]`` matrix (``conf.sum(0)``), per-pixel weights, top-k."""
+    name = "resize_many_back_confusion"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if merge not in _lib.BACK_MERGE:
+        raise ValueError(f"{name}(): merge must be 'sum' or 'mean', got {merge!r}")
+    _back_activation_name(name, activation)
+    items, dev0, n, k = _back_items(name, pred, channels)
+    if groups is None:
+        targets, sizes, target_id = _back_targets(name, targets, n, "item")
+        item_sizes = sizes = _back_sizes(name, sizes, n, k)
+    else:
+        targets, sizes, target_id = _back_targets(name, targets, None, "group")  # (G is their count: what groups is checked against)
+        sizes = _back_sizes(name, sizes, len(sizes), k)
+        groups, counts = _back_groups(name, groups, n, len(sizes))
+        if activation == "softmax":
+            for j, c in enumerate(counts):
+                if c > _lib.BACK_ACT_MEMBERS:
+                    raise ValueError(f"{name}(): group {j} (targets[{j}]) has {c} members: activation='softmax' takes at most "
+                                     f"{_lib.BACK_ACT_MEMBERS} per group")
+        item_sizes = [sizes[g] for g in groups]
+    outs = len(sizes)
+    rects = _back_regions(name, regions, items)
+    flips = _many_flips(name, flips, n)
+    if k * k * outs > _BACK_MAX_ELEMS:
+        raise ValueError(f"{name}(): K * K * {outs} = {k * k * outs} counts are beyond the supported {_BACK_MAX_ELEMS}")
+    if n == 0:
+        return torch.zeros((0, k, k), dtype=torch.int64, device=_many_empty_device(dev0))
+    for t in items:
+        _require_gpu(t, name)
+    dev = items[0].device
+    for i, t in enumerate(targets):
+        if t.device != dev:
+            raise ValueError(f"{name}(): targets[{i}] is on {t.device}, pred on {dev}")
+    items = [t.detach() for t in items]
+    recs, keep, interleaved = _back_records(items, rects, item_sizes, flips, k)  # (keep: alive until the launches are enqueued)
+    trecs = (_lib.BackTargetIn * outs)()
+    for i, t in enumerate(targets):
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            t = t.contiguous()
+            keep.append(t)
+        trecs[i].data_dev = t.data_ptr()
+        trecs[i].stride_row = t.stride(0) if t.shape[0] > 1 else 0
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    conf_elems = ctypes.c_int64(0)
+    if groups is None:
+        desc_bytes = L.aa_back_confusion_desc_bytes(n)
+
+        def planner(desc, nbytes, ws_bytes):
+            return L.aa_back_confusion_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, trecs, target_id, _lib.BACK_ACT[activation], desc, nbytes,
+                                            ws_bytes, ctypes.byref(conf_elems))
+    else:
+        group_of = (ctypes.c_int64 * n)(*groups)
+        desc_bytes = L.aa_back_merged_confusion_desc_bytes(n, outs)
+
+        def planner(desc, nbytes, ws_bytes):
+            return L.aa_back_merged_confusion_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, outs, group_of, _lib.BACK_MERGE[merge], trecs,
+                                                   target_id, _lib.BACK_ACT[activation], desc, nbytes, ws_bytes, ctypes.byref(conf_elems))
+    conf = _many_run(
+        name, dev, desc_bytes, planner, lambda: torch.empty((outs, k, k), dtype=torch.int64, device=dev),
+        lambda desc_host, desc_dev, out, ws, stream: L.aa_resample_back_confusion(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], out.data_ptr(),
+                                                                                  out.numel(), ws.data_ptr(), ws.numel(), stream))[0]
+    del keep
+    return conf
 
 
 def _back_canvas(name: str, canvas, n: int, k: int):

@@ -1219,6 +1219,90 @@ def logits_activation(args, torch, aa, timed):
             torch.cuda.empty_cache()
 
 
+def fast_hist(torch, t, p, k):
+    """The classic evaluation step in torch: the K x K counts of (target, prediction) over the pixels whose target is a class."""
+    keep = (t >= 0) & (t < k)
+    return torch.bincount(k * t[keep] + p[keep], minlength=k * k).view(k, k)
+
+
+def confusion(args, torch, aa, timed):
+    """--confusion: per-image confusion matrices on --logits' geometry (one pass) and on --tta's (6 passes summed), int64 targets of 64 x 64
+    blocks of one class (--noise-targets: a class per pixel) with 5 % of the pixels 255.  (a) the loop a user writes today, linear_forward, argmax, fast_hist per item; (b) the argmax call of the return
+    path, then fast_hist per item; (c) resize_many_back_confusion; (d) the argmax call alone: (c) - (d) is what counting costs over
+    storing the labels.  --quick: K = 19, bfloat16 only."""
+    from interpolate_antialiasing_amd import boxmath
+
+    n, canvases = 16, (384, 512, 640)
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    pixels = sum(h * w for h, w in shapes)
+    passes = {"logits": [(512, False)], "tta": [(c, flip) for c in canvases for flip in (False, True)]}
+    print(f"resize_many_bench --confusion: N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), {pixels / 1e6:.1f} M "
+          f"output pixels; bilinear; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for geometry, ps in passes.items():
+        regions, flips, groups = [], [], []
+        for c, flip in ps:
+            regions += boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=c), "center", (c, c))
+            flips += [flip] * n
+            groups += list(range(n))
+        merged = len(ps) > 1
+        for k in (19,) if args.quick else (19, 150):
+            for dtype in (torch.bfloat16,) if args.quick else (torch.float32, torch.bfloat16):
+                batches = [torch.randn((n, k, c, c), device="cuda", generator=gen).to(dtype) for c, _ in ps]
+                items = [b[i] for b in batches for i in range(n)]
+                targets = []
+                for s in shapes:  # (ground truth is piecewise constant: 64 x 64 blocks of one class; --noise-targets: every pixel its own)
+                    b = 1 if args.noise_targets else 64
+                    t = torch.randint(0, k, (-(-s[0] // b), -(-s[1] // b)), device="cuda", generator=gen)
+                    t = t.repeat_interleave(b, 0).repeat_interleave(b, 1)[:s[0], :s[1]].contiguous()
+                    t[torch.rand(s, device="cuda", generator=gen) < 0.05] = 255
+                    targets.append(t)
+
+                def loop():
+                    out = []
+                    for i in range(n):
+                        s = None
+                        for j in range(i, len(items), n):
+                            y0, x0, h, w = regions[j]
+                            r = aa.linear_forward(items[j][:, y0:y0 + h, x0:x0 + w].float()[None], list(shapes[i]))[0]
+                            r = r.flip(-1) if flips[j] else r
+                            s = r if s is None else s.add_(r)
+                        out.append(fast_hist(torch, targets[i], s.argmax(0), k))
+                    return torch.stack(out)
+
+                def labels():
+                    if merged:
+                        return aa.resize_many_back_merged(items, groups, shapes, regions=regions, flips=flips, reduce="argmax")
+                    return aa.resize_many_back(items, shapes, regions=regions, reduce="argmax")
+
+                def labels_then_hist():
+                    return torch.stack([fast_hist(torch, t, p, k) for t, p in zip(targets, labels())])
+
+                def fused():
+                    return aa.resize_many_back_confusion(items, targets, regions=regions, flips=flips if merged else None, groups=groups if merged else None)
+
+                call = "resize_many_back_merged" if merged else "resize_many_back"
+                a_key, b_key = "a: loop: linear_forward, (flip, add,) argmax, fast_hist per item", f"b: {call}(reduce='argmax'), fast_hist per item"
+                contestants = {a_key: loop, b_key: labels_then_hist, "c: resize_many_back_confusion": fused, f"d: {call}(reduce='argmax') alone": labels}
+                run = _run_contestants(args, torch, timed, contestants)
+                results = next(run)
+                want = fused()
+                note = "; ".join(f"({key[0]}) differs from (c) in {int((results[key] != want).sum())} counts" for key in (a_key, b_key)
+                                 if results[key] is not None)
+                assert results[b_key] is None or torch.equal(results[b_key], want), "(c) differs from fast_hist of the call's labels"
+                del results, want
+                print(f"\n{geometry}, K = {k}, {str(dtype).replace('torch.', '')}: {note}")
+                stat = next(run)
+                _against(stat, "c", "a", "the call against the loop")
+                _against(stat, "c", "b", "the call against labels + fast_hist")
+                _against(stat, "d", "c", "what counting costs over storing labels")
+                del batches, items, targets
+                torch.cuda.empty_cache()
+
+
 def back_bwd_workload(which, torch, k, dtype):
     """The two geometries of --logits-backward -> (canvas, regions, flips, gradients [K, oh_i, ow_i] on the GPU, their bytes): "large",
     --logits' 16 camera-sized images from a 512 x 512 letterbox canvas; "small", 64 images with sides drawn from 240 .. 640 from a
@@ -1333,6 +1417,11 @@ def main():
     ap.add_argument("--activation", choices=("softmax", "sigmoid"), default=None,
                     help="with --tta or --logits: the activation before the sum / the store, against the loop with torch's softmax / sigmoid "
                     "and against the same call with activation=None")
+    ap.add_argument("--confusion", action="store_true", help="only resize_many_back_confusion: per-image confusion matrices on --logits' and --tta's "
+                    "geometries against the loop, against the argmax call followed by fast_hist, and against the argmax call alone")
+    ap.add_argument("--quick", action="store_true", help="with --confusion: K = 19 and bfloat16 only (the sweep of the kernel's tunables)")
+    ap.add_argument("--noise-targets", action="store_true", help="with --confusion: targets uniform per pixel, the counting's worst case, "
+                    "instead of 64 x 64 blocks of one class")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
     ap.add_argument("--trace-patches", action="store_true", help="with --trace: the calls are resize_many_to_patches (the --patches workload); "
                     "with --summarise: kernel times only")
@@ -1436,6 +1525,9 @@ def main():
         return
     if args.embed:
         embed(args, torch, aa, timed)
+        return
+    if args.confusion:
+        confusion(args, torch, aa, timed)
         return
     if args.logits:
         (logits_activation if args.activation else logits)(args, torch, aa, timed)
