@@ -34,7 +34,8 @@ extern "C" {
                                    aa_back_merged_plan, aa_resample_back_merged; aa_back_many_plan_act, aa_back_merged_plan_act
                                    (a softmax or sigmoid before the reduction), with AA_BACK_ACT_*; aa_back_confusion_desc_bytes,
                                    aa_back_merged_confusion_desc_bytes, aa_back_confusion_plan, aa_back_merged_confusion_plan,
-                                   aa_resample_back_confusion, with aa_back_target */
+                                   aa_resample_back_confusion, with aa_back_target; aa_back_queries_desc_bytes,
+                                   aa_back_queries_plan, aa_resample_back_queries, with aa_back_weights */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -757,6 +758,50 @@ int aa_back_merged_confusion_plan(int filter, int layout, int64_t n, int64_t K, 
                                   size_t *workspace_bytes, int64_t *conf_elems);
 int aa_resample_back_confusion(const void *desc_host, const void *desc_dev, int in_dtype, void *conf_dev, size_t conf_elems, void *workspace_dev,
                                size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back, mask classification: Q resampled masks times [Q, C] class weights, reduced over C ------------------------
+ * MaskFormer-style heads answer Q mask logits [Q, H, W] and Q class distributions [Q, C] per image; their semantic inference is the
+ * sigmoid of the resampled masks, einsum("qc,qhw->chw") with the class probabilities, and the argmax over C.  Item i is an
+ * aa_back_item with K = Q (1 .. 256) and a weight matrix.  With R_i the fp32 value aa_back_many_plan's section defines for item i
+ * (bit for bit; for AA_MANY_FLIP_X mirrored left to right) and fl16 one round-to-nearest-even to IEEE float16,
+ *   P[q, y, x] = fl16(sigmoid(R_i[q, y, x]))      the sigmoid of aa_back_many_plan_act, bit for bit
+ *   Wh[q, c]   = fl16(weights_i[q, c])            beyond +-65504: +-inf
+ *   S[c, y, x] = sum over q of Wh[q, c] * P[q, y, x]
+ * every product exact in fp32 and the sum taken in fp32 on the matrix unit (v_mfma_f32_32x32x16_f16) in an order that is the
+ * kernel's own: P and Wh are defined bit for bit, S within Q * 2^-23 * sum |Wh * P| of the exact sum.  The matrix unit may take an
+ * operand below 2^-14 in magnitude (a float16 subnormal) as zero.  A NaN in P makes S NaN in every class of that pixel and of no other.
+ * Item i of the arena is
+ *   reduce 0 (values)   [C, oh_i, ow_i] of out_dtype AA_F32 / AA_F16 / AA_BF16: S rounded to nearest even ONCE;
+ *   reduce 1 (argmax)   [oh_i, ow_i] of out_dtype AA_U8 (C <= 256) / AA_I16 (C <= 32768) / AA_I32 / AA_I64: the lowest c at which S is
+ *                       greatest, a NaN counting as greater than every number and the lowest NaN winning; neither the Q values of P
+ *                       nor the C scores of a pixel are stored;
+ * at byte out_offsets[i], a multiple of 16; the bytes between items are not written.
+ * aa_back_weights: weight (q, c) at data_dev + q * stride_q + c * stride_c float32 ELEMENTS, any non-negative strides (the stride of
+ * an axis of one element is not looked at), read where it lies.
+ * aa_back_queries_plan is host arithmetic only.  Its block is aa_back_many_plan's sections after a header of its own, then one record
+ * per item: the weights' pointer and two strides.  desc_bytes >= aa_back_queries_desc_bytes(n); the workspace is aa_back_many_plan's
+ * for the same items (the tables; nothing else).  Errors in aa_back_many_plan's order with K = Q and these added: AA_ERR_BAD_SHAPE
+ * beside n and K for Q > 256, C outside 1 .. INT32_MAX / 4 or a reduce other than 0 and 1, then for a label type that cannot hold
+ * C - 1; `weights` beside the pointers (AA_ERR_NULL, n > 0); per item, after its own checks, AA_ERR_NULL for null weights,
+ * AA_ERR_STRIDES for a negative stride or a pointer that is not 4-byte aligned, AA_ERR_BAD_SHAPE for C * oh_i * ow_i beyond 2^40; last
+ * AA_ERR_BAD_DTYPE.
+ * aa_resample_back_queries enqueues TWO launches whatever n and the sizes: the table kernel, and a resample with one workgroup per
+ * work unit (an output row times 256 columns), each of whose waves resamples the Q masks of its 64 pixels into LDS as float16 and
+ * multiplies them there by the weights, 32 classes at a time.  Parameters and checks as aa_resample_back_many's, in their order; last
+ * before the first launch the LDS of a workgroup, 512 bytes times Q rounded up to 16, against the limit of the device the launches go
+ * to (AA_ERR_BAD_SHAPE; AA_ERR_HIP where the device cannot be asked).  Nothing is allocated, synchronised or read back, and no table
+ * cache is touched.  n == 0 launches nothing.  Not built: groups (the merged form), confusion matrices, a backward, Mask2Former's
+ * panoptic and instance inference.  Added without an ABI version change (additive). */
+typedef struct aa_back_weights {
+  const void *data_dev;        /* weight (0, 0), float32 */
+  int64_t stride_q, stride_c;  /* in ELEMENTS */
+} aa_back_weights;
+size_t aa_back_queries_desc_bytes(int64_t n);
+int aa_back_queries_plan(int filter, int layout, int64_t n, int64_t Q, int64_t C, const aa_back_item *items, const aa_back_weights *weights /* n */,
+                         int reduce /* 0 values, 1 argmax */, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes,
+                         size_t *arena_bytes, int64_t *out_offsets /* n, bytes */);
+int aa_resample_back_queries(const void *desc_host, const void *desc_dev, int in_dtype, void *arena_dev, size_t arena_bytes, void *workspace_dev,
+                             size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged predictions back, backward: N gradients [K, oh_i, ow_i] to N canvases [K, H_i, W_i] ---------------------------------------
  * The backward of aa_resample_back_many's reduce 0, for losses taken at every image's own size.  Item i has a canvas [H_i, W_i], the

@@ -66,6 +66,7 @@ EXPORTS = (
     "aa_back_many_plan_act", "aa_back_merged_plan_act",
     "aa_back_confusion_desc_bytes", "aa_back_merged_confusion_desc_bytes", "aa_back_confusion_plan", "aa_back_merged_confusion_plan",
     "aa_resample_back_confusion",
+    "aa_back_queries_desc_bytes", "aa_back_queries_plan", "aa_resample_back_queries",
 )
 
 
@@ -279,6 +280,24 @@ class BackConfTarget(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class BackWeightsIn(ctypes.Structure):
+    """aa_back_weights: one item's [Q, C] float32 class weights of the mask-classification call (strides in ELEMENTS)."""
+    _fields_ = [("data_dev", ctypes.c_void_p), ("stride_q", ctypes.c_int64), ("stride_c", ctypes.c_int64)]
+
+
+class BackQueriesHeader(ctypes.Structure):
+    """Head of the block aa_back_queries_plan writes (csrc/aa_many_back_queries.h AABackQueriesHeader; opaque to C callers, mirrored for
+    the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("Q", ctypes.c_int32), ("filter", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("reduce", ctypes.c_int32), ("out_dtype", ctypes.c_int32), ("C", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64)]
+
+
+class BackQueryWeights(ctypes.Structure):
+    """One item's weights in that block (csrc/aa_many_back_queries.h AABackQueryWeights), after the items and unit0."""
+    _fields_ = [("w", ctypes.c_void_p), ("stride_q", ctypes.c_int64), ("stride_c", ctypes.c_int64), ("reserved", ctypes.c_int64)]
+
+
 class BackBwdItemIn(ctypes.Structure):
     """aa_back_bwd_item: one item of the ragged return path's backward (strides in ELEMENTS; grad_dev None: the item has no gradient)."""
     _fields_ = [("grad_dev", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("H", ctypes.c_int64),
@@ -339,6 +358,7 @@ BACK_ACT = {None: 0, "softmax": 1, "sigmoid": 2}  # aa_back_many_plan_act activa
 BACK_ACT_MEMBERS = 16  # the most members of a group of a merged softmax plan (csrc/aa_many_back.h AA_BACK_ACT_MEMBERS)
 BACK_TILE = 256     # output columns per work unit of the return path's resample (csrc/aa_many_back.h AA_BACK_TILE)
 BACK_CONF_ROWS = 8  # output rows per work unit of the confusion call's resample (csrc/aa_many_back_confusion.h AA_BACK_CONF_ROWS)
+BACK_QUERIES_MAX = 256  # the most queries of the mask-classification call (csrc/aa_many_back_queries.h AA_BACK_QUERIES_MAX_Q)
 BACK_BWD_ROWS, BACK_BWD_COLS = 4, 64  # canvas rows and columns per work unit of the return path's backward (csrc/aa_many_back_bwd.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
 
@@ -598,6 +618,13 @@ def load() -> ctypes.CDLL:
     L.aa_back_merged_confusion_plan.restype = i32
     L.aa_resample_back_confusion.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp]
     L.aa_resample_back_confusion.restype = i32
+    L.aa_back_queries_desc_bytes.argtypes = [i64]
+    L.aa_back_queries_desc_bytes.restype = sz
+    L.aa_back_queries_plan.argtypes = [i32, i32, i64, i64, i64, ctypes.POINTER(BackItemIn), ctypes.POINTER(BackWeightsIn), i32, i32, vp, sz,
+                                       ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_back_queries_plan.restype = i32
+    L.aa_resample_back_queries.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp]
+    L.aa_resample_back_queries.restype = i32
     L.aa_back_many_bwd_desc_bytes.argtypes = [i64]
     L.aa_back_many_bwd_desc_bytes.restype = sz
     L.aa_back_many_bwd_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackBwdItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),

@@ -11,6 +11,7 @@
 #include "aa_many_back.h"
 #include "aa_many_back_bwd.h"
 #include "aa_many_back_confusion.h"
+#include "aa_many_back_queries.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_maps.h"
@@ -680,6 +681,21 @@ int aa_resample_back_confusion(const void *desc_host, const void *desc_dev, int 
                                size_t workspace_bytes, aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_back_confusion(desc_host, desc_dev, in_dtype, conf_dev, conf_elems, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- ragged predictions back, mask classification: resampled masks times class weights on the matrix unit --------------------------------
+size_t aa_back_queries_desc_bytes(int64_t n) { return aa_back_queries_desc_size(n); }
+
+int aa_back_queries_plan(int filter, int layout, int64_t n, int64_t Q, int64_t C, const aa_back_item *items, const aa_back_weights *weights, int reduce,
+                         int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
+  return aa_back_queries_plan_host(filter, layout, n, Q, C, items, weights, reduce, out_dtype, desc_host, desc_bytes, workspace_bytes, arena_bytes,
+                                   out_offsets);
+}
+
+int aa_resample_back_queries(const void *desc_host, const void *desc_dev, int in_dtype, void *arena_dev, size_t arena_bytes, void *workspace_dev,
+                             size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_back_queries(desc_host, desc_dev, in_dtype, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- ragged predictions back, backward -----------------------------------------------------------------------------------------------------

@@ -50,7 +50,9 @@ Differences, all additive:
     answer on the canvas resampled to every image's own size in the reference's fp32 arithmetic, as values, as the argmax over K or as
     ``> threshold``, two launches whatever N; with ``reduce="argmax"`` the K values of a pixel are never stored; ``activation="softmax"``
     or ``"sigmoid"`` puts bit-exactly defined probabilities in the values' place, here and in ``resize_many_back_merged``, which sums
-    several test-time passes per image before the reduction;
+    several test-time passes per image before the reduction; ``resize_many_back_queries(masks, class_weights, sizes, ...)`` is the same
+    way back for mask-classification heads (MaskFormer's semantic inference): Q resampled masks, their sigmoid, the product with the
+    [Q, C] class weights on the matrix unit and the argmax over C, in the same two launches;
   * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -71,7 +73,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -1954,6 +1956,117 @@ def resize_many_back_confusion(pred, targets, mode: str = "bilinear", *, regions
                                                                                   out.numel(), ws.data_ptr(), ws.numel(), stream))[0]
     del keep
     return conf
+
+
+def _back_class_weights(name: str, class_weights, n: int, q: int, dev):
+    """class_weights of resize_many_back_queries, checked -> ([Q, C] float32 tensors, one per item, read where they lie; C)."""
+    if isinstance(class_weights, torch.Tensor):
+        if class_weights.dim() != 3:
+            raise ValueError(f"{name}(): one class_weights tensor must be [N, Q, C], got {list(class_weights.shape)}")
+        ws = list(class_weights.unbind(0))
+    else:
+        try:
+            ws = list(class_weights)
+        except TypeError:
+            raise ValueError(f"{name}(): class_weights must be a [N, Q, C] tensor or N tensors [Q, C], got {class_weights!r}") from None
+    if len(ws) != n:
+        raise ValueError(f"{name}(): class_weights must hold one entry per item ({n}), got {len(ws)}")
+    for i, w in enumerate(ws):
+        if not isinstance(w, torch.Tensor):
+            raise TypeError(f"{name}(): class_weights[{i}] must be Tensor")
+        if w.dim() != 2:
+            raise ValueError(f"{name}(): class_weights[{i}] must be [Q, C], got {list(w.shape)}")
+        if w.dtype != torch.float32:
+            raise ValueError(f"{name}(): class_weights[{i}] must be torch.float32, got {w.dtype}")
+        if int(w.shape[0]) != q:
+            raise ValueError(f"{name}(): class_weights[{i}] has {int(w.shape[0])} queries, masks have Q = {q}")
+        if int(w.shape[1]) != int(ws[0].shape[1]):
+            raise ValueError(f"{name}(): every item must have the same C: class_weights[{i}] has {int(w.shape[1])}, expected {int(ws[0].shape[1])}")
+        if dev is not None and w.device != dev:
+            raise ValueError(f"{name}(): class_weights[{i}] is on {w.device}, masks on {dev}")
+    c = int(ws[0].shape[1]) if ws else 1
+    if not (1 <= c <= _MANY_MAX):
+        raise ValueError(f"{name}(): C must be in 1 .. {_MANY_MAX}, got C = {c}")
+    return ws, c
+
+
+def resize_many_back_queries(masks, class_weights, sizes, mode: str = "bilinear", *, regions=None, flips=None, reduce: Optional[str] = "argmax",
+                             out_dtype=None):
+    """The way back for mask-classification heads — MaskFormer, Mask2Former, OneFormer and the semantic heads on SAM-style decoders —
+    whose semantic inference at every image's own size is: resample the Q mask logits, take the sigmoid,
+    ``einsum("qc,qhw->chw", class_probs, mask_probs)``, argmax over C.  ``masks``, ``sizes``, ``mode``, ``regions`` and ``flips`` are
+    ``resize_many_back``'s ``pred`` and its arguments with K = Q, with its checks: one float32 / float16 / bfloat16 GPU tensor
+    [N, Q, H, W] or a list of [Q, H_i, W_i], planar or channels_last, read where they lie; 1 <= Q <= 256.  ``class_weights``: one
+    float32 tensor [N, Q, C] or N tensors [Q, C] on the same device, any strides, read where they lie — typically
+    ``softmax(class_logits, -1)[..., :-1]``.
+
+    With ``R_i`` the fp32 resample ``resize_many_back`` defines (bit for bit) and ``fl16`` one round-to-nearest-even to float16:
+
+        ``P[q] = fl16(sigmoid(R_i[q]))`` (``activation="sigmoid"``'s value), ``Wh[q, c] = fl16(class_weights[i][q, c])``,
+        ``S[c, y, x] = sum_q Wh[q, c] * P[q, y, x]``, exact products summed in fp32 on the matrix unit.
+
+    ``P`` and ``Wh`` are defined bit for bit; the order of the sum is the kernel's own, and ``S`` lies within
+    ``Q * 2^-23 * sum_q |Wh * P|`` of the exact sum.  What float16 operands mean: a weight beyond +-65504 becomes +-inf, and an operand
+    below 2^-14 in magnitude (a float16 subnormal) may be taken as zero by the matrix unit — the call is for probabilities and similar
+    weights, not for logits of arbitrary range.  A NaN logit makes the scores of its pixel NaN in every class, and of no other pixel.
+
+      * ``reduce="argmax"``: label maps [oh_i, ow_i], the lowest c at which ``S`` is greatest, a NaN greater than every number;
+        ``out_dtype`` None (int64), uint8 (C <= 256), int16 (C <= 32768) or int32.  Neither the Q probabilities nor the C scores of a
+        pixel reach memory;
+      * ``reduce=None``: ``S`` as [C, oh_i, ow_i], rounded ONCE to ``out_dtype``: None (``masks``' dtype), float32, float16 or bfloat16.
+
+    The results are contiguous views of ONE arena, each on a 16-byte boundary.  N == 0 gives [].  Two launches whatever N and the
+    sizes — the table kernel, and a resample whose waves keep the float16 probabilities of their 64 pixels in LDS and multiply them
+    there by the weights, 32 classes at a time — no workspace beyond the tables, nothing read back, no synchronisation.
+
+    Not differentiable: with ``reduce=None``, gradients enabled and a ``masks`` or ``class_weights`` that requires grad the call raises
+    ``NotImplementedError`` — call it under ``torch.no_grad()`` or pass ``.detach()``.  Not built: ``groups=`` (merged test-time
+    passes), confusion matrices, Mask2Former's panoptic and instance inference."""
+    name = "resize_many_back_queries"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if reduce not in (None, "argmax"):
+        raise ValueError(f"{name}(): reduce must be 'argmax' or None, got {reduce!r}")
+    if not isinstance(masks, torch.Tensor) and len(masks) == 0:
+        return []
+    items, _, n, q = _back_items(name, masks, None)
+    if q > _lib.BACK_QUERIES_MAX:
+        raise ValueError(f"{name}(): Q must be in 1 .. {_lib.BACK_QUERIES_MAX}, got Q = {q}")
+    ws, c = _back_class_weights(name, class_weights, n, q, items[0].device if items else None)
+    sizes = _back_sizes(name, sizes, n, max(q, c))
+    rects = _back_regions(name, regions, items)
+    flips = _many_flips(name, flips, n)
+    reduce_id, out_dtype, out_id, _ = _back_out(name, reduce, out_dtype, 0.0, items, c)
+    if reduce is None and torch.is_grad_enabled() and any(t.requires_grad for t in [masks] + items + [class_weights] + ws
+                                                          if isinstance(t, torch.Tensor)):
+        raise NotImplementedError(f"{name}() is not differentiable: with reduce=None and masks or class_weights that require grad, call it "
+                                  f"under torch.no_grad() or pass .detach()")
+    if n == 0:
+        return []
+    for t in items:
+        _require_gpu(t, name)
+    dev = items[0].device
+    items, ws = [t.detach() for t in items], [w.detach() for w in ws]
+    recs, keep, interleaved = _back_records(items, rects, sizes, flips, q)  # (keep: alive until the launches are enqueued)
+    wrecs = (_lib.BackWeightsIn * n)()
+    for i, w in enumerate(ws):
+        wrecs[i].data_dev = w.data_ptr()
+        wrecs[i].stride_q = w.stride(0) if q > 1 else 0
+        wrecs[i].stride_c = w.stride(1) if c > 1 else 0
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    arena_bytes, offs = ctypes.c_size_t(0), (ctypes.c_int64 * n)()
+    es = torch.empty((), dtype=out_dtype).element_size()
+
+    def planner(desc, nbytes, ws_bytes):
+        return L.aa_back_queries_plan(_lib.FILTER_IDS[mode], layout, n, q, c, recs, wrecs, reduce_id, out_id, desc, nbytes, ws_bytes,
+                                      ctypes.byref(arena_bytes), offs)
+    arena = _many_run(
+        name, dev, L.aa_back_queries_desc_bytes(n), planner, lambda: torch.empty((arena_bytes.value // es,), dtype=out_dtype, device=dev),
+        lambda desc_host, desc_dev, out, wsp, stream: L.aa_resample_back_queries(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], out.data_ptr(),
+                                                                                 out.numel() * es, wsp.data_ptr(), wsp.numel(), stream))[0]
+    del keep
+    return _back_views(arena, offs, sizes, reduce, c)
 
 
 def _back_canvas(name: str, canvas, n: int, k: int):

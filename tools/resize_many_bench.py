@@ -145,6 +145,8 @@ the same bits.  The kernel's fetched bytes come from a counter run of its own: t
                                                          # profiles/resize_many_back.txt
   python tools/resize_many_bench.py --tta --rounds 5 --batches 3 > out.txt   # only the merged way back: 6 passes per image summed, argmax (above);
                                                          # profiles/resize_many_back_merged.txt is this output
+  python tools/resize_many_bench.py --queries --rounds 5 --batches 3 > out.txt   # only resize_many_back_queries: Q = 100 masks, sigmoid,
+                                                         # class weights, argmax (at queries()); profiles/resize_many_back_queries.txt
   python tools/resize_many_bench.py --logits-backward > out.txt   # only the gradients' way back to the canvas (above);
                                                          # profiles/resize_many_back_bwd.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
@@ -1219,6 +1221,63 @@ def logits_activation(args, torch, aa, timed):
             torch.cuda.empty_cache()
 
 
+def queries(args, torch, aa, timed):
+    """--queries: mask-classification semantic inference on --logits' geometry, Q = 100 queries, C = 19 and 150 classes, float32 and
+    bfloat16 masks, int64 labels.  (a) is the loop a user writes today, per item linear_forward, sigmoid, einsum, argmax, in fp32;
+    (b) the same loop under bfloat16 autocast (the einsum in bfloat16); (c) resize_many_back(activation="sigmoid", reduce=None), which
+    writes Q floats a pixel, then einsum and argmax per item; (d) resize_many_back_queries.  The labels of (a) and (d) are compared and
+    the share that differs reported, not asserted (float16 operands and another summation order move near-ties)."""
+    from interpolate_antialiasing_amd import boxmath
+
+    n, canvas, q = 16, (512, 512), 100
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    regions = boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=canvas[0]), "center", canvas)
+    pixels = sum(h * w for h, w in shapes)
+    print(f"resize_many_bench --queries: [N, Q = {q}, {canvas[0]}, {canvas[1]}] mask logits on a letterbox canvas (fit_sizes(longer={canvas[0]}), "
+          f"'center') back to N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), {pixels / 1e6:.1f} M output pixels; "
+          f"bilinear; sigmoid, einsum with [Q, C] class probabilities, argmax over C, int64 labels; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for c in (19, 150):
+        for dtype in (torch.float32, torch.bfloat16):
+            x = torch.randn((n, q) + canvas, device="cuda", generator=gen).to(dtype)
+            w = torch.randn((n, q, c + 1), device="cuda", generator=gen).softmax(-1)[..., :c]
+
+            def loop(autocast=False):
+                out = []
+                for i, (y0, x0, h, ww) in enumerate(regions):
+                    p = aa.linear_forward(x[i, :, y0:y0 + h, x0:x0 + ww].float()[None], list(shapes[i]))[0].sigmoid_()
+                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+                        out.append(torch.einsum("qc,qhw->chw", w[i], p).argmax(0))
+                return out
+
+            def values_then_einsum():
+                ps = aa.resize_many_back(x, shapes, regions=regions, activation="sigmoid")
+                return [torch.einsum("qc,qhw->chw", w[i].to(p.dtype), p).argmax(0) for i, p in enumerate(ps)]
+
+            def fused():
+                return aa.resize_many_back_queries(x, w, shapes, regions=regions)
+
+            a_key, d_key = "a: loop: linear_forward, sigmoid, einsum, argmax per item, fp32", "d: resize_many_back_queries(reduce='argmax')"
+            contestants = {a_key: loop, d_key: fused, "b: the loop with the einsum under bfloat16 autocast": lambda: loop(True),
+                           "c: resize_many_back(activation='sigmoid', reduce=None), then einsum, argmax per item": values_then_einsum}
+            run = _run_contestants(args, torch, timed, contestants)
+            results = next(run)
+            note = "a contestant does not fit"
+            if results[a_key] is not None and results[d_key] is not None:
+                differ = sum(int((p != r).sum()) for p, r in zip(results[a_key], results[d_key]))
+                note = f"the labels of (a) and (d) differ at {differ} of {pixels} pixels ({100.0 * differ / pixels:.4f} %)"
+            del results
+            print(f"\nQ = {q}, C = {c}, {str(dtype).replace('torch.', '')} masks: {note}")
+            stat = next(run)
+            for other, what in (("a", "the fp32 loop"), ("b", "the autocast loop"), ("c", "values, then einsum")):
+                _against(stat, "d", other, f"the call against {what}")
+            del x, w
+            torch.cuda.empty_cache()
+
+
 def fast_hist(torch, t, p, k):
     """The classic evaluation step in torch: the K x K counts of (target, prediction) over the pixels whose target is a class."""
     keep = (t >= 0) & (t < k)
@@ -1419,6 +1478,8 @@ def main():
                     "and against the same call with activation=None")
     ap.add_argument("--confusion", action="store_true", help="only resize_many_back_confusion: per-image confusion matrices on --logits' and --tta's "
                     "geometries against the loop, against the argmax call followed by fast_hist, and against the argmax call alone")
+    ap.add_argument("--queries", action="store_true", help="only resize_many_back_queries: mask-classification semantic inference on --logits' "
+                    "geometry, Q = 100, C = 19 and 150, against the per-item loops and against resize_many_back + einsum")
     ap.add_argument("--quick", action="store_true", help="with --confusion: K = 19 and bfloat16 only (the sweep of the kernel's tunables)")
     ap.add_argument("--noise-targets", action="store_true", help="with --confusion: targets uniform per pixel, the counting's worst case, "
                     "instead of 64 x 64 blocks of one class")
@@ -1528,6 +1589,9 @@ def main():
         return
     if args.confusion:
         confusion(args, torch, aa, timed)
+        return
+    if args.queries:
+        queries(args, torch, aa, timed)
         return
     if args.logits:
         (logits_activation if args.activation else logits)(args, torch, aa, timed)
