@@ -35,7 +35,9 @@ extern "C" {
                                    (a softmax or sigmoid before the reduction), with AA_BACK_ACT_*; aa_back_confusion_desc_bytes,
                                    aa_back_merged_confusion_desc_bytes, aa_back_confusion_plan, aa_back_merged_confusion_plan,
                                    aa_resample_back_confusion, with aa_back_target; aa_back_queries_desc_bytes,
-                                   aa_back_queries_plan, aa_resample_back_queries, with aa_back_weights */
+                                   aa_back_queries_plan, aa_resample_back_queries, with aa_back_weights;
+                                   aa_back_panoptic_desc_bytes, aa_back_panoptic_plan, aa_resample_back_panoptic, with
+                                   aa_back_panoptic_io */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -790,8 +792,8 @@ int aa_resample_back_confusion(const void *desc_host, const void *desc_dev, int 
  * multiplies them there by the weights, 32 classes at a time.  Parameters and checks as aa_resample_back_many's, in their order; last
  * before the first launch the LDS of a workgroup, 512 bytes times Q rounded up to 16, against the limit of the device the launches go
  * to (AA_ERR_BAD_SHAPE; AA_ERR_HIP where the device cannot be asked).  Nothing is allocated, synchronised or read back, and no table
- * cache is touched.  n == 0 launches nothing.  Not built: groups (the merged form), confusion matrices, a backward, Mask2Former's
- * panoptic and instance inference.  Added without an ABI version change (additive). */
+ * cache is touched.  n == 0 launches nothing.  Not built: groups (the merged form), confusion matrices, a backward, instance
+ * inference (panoptic inference: aa_back_panoptic_plan).  Added without an ABI version change (additive). */
 typedef struct aa_back_weights {
   const void *data_dev;        /* weight (0, 0), float32 */
   int64_t stride_q, stride_c;  /* in ELEMENTS */
@@ -802,6 +804,52 @@ int aa_back_queries_plan(int filter, int layout, int64_t n, int64_t Q, int64_t C
                          size_t *arena_bytes, int64_t *out_offsets /* n, bytes */);
 int aa_resample_back_queries(const void *desc_host, const void *desc_dev, int in_dtype, void *arena_dev, size_t arena_bytes, void *workspace_dev,
                              size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back, panoptic inference: Q resampled masks and Q scores to a segment map and per-query areas ------------------
+ * Panoptic inference of MaskFormer-style heads, per image: the sigmoid of the resampled masks times the query scores, the argmax over
+ * the queries, and per query the overlap test of its won area against its own mask.  Item i is an aa_back_item with K = Q (1 .. 256).
+ * With R_i the fp32 value aa_back_many_plan's section defines for item i (bit for bit; for AA_MANY_FLIP_X mirrored left to right):
+ *   p[q]   = sigmoid(R_i[q])                      the sigmoid of aa_back_many_plan_act, bit for bit
+ *   v[q]   = scores[i, q] * p[q]                  one rounded fp32 product
+ *   query q is KEPT iff scores[i, q] > 0 (a NaN is not); the winner of a pixel is the lowest kept q of the greatest v, a NaN counting
+ *   as greater than every number and the lowest NaN winning; a pixel of an item without kept queries has no winner;
+ *   inside = p[winner] >= 0.5 (false for a NaN)
+ *   counts[i, q] = (area: the pixels whose winner is q; original: the pixels with p[q] >= 0.5, 0 for a query that is not kept; inter:
+ *                  the pixels whose winner is q and that are inside), int64
+ *   q survives iff area > 0, original > 0, inter > 0 and (double)area / (double)original >= overlap_threshold (one fp64 division)
+ *   map[y, x] = (out_dtype)ids[i, winner] where the pixel has a winner that survives and is inside, else (out_dtype)void_value; ids
+ *               int32, converted as a C cast converts (no range check); ids_dev NULL: the query's index.
+ * Everything is integers or single correctly rounded operations: the same bits on every run.  out_dtype is AA_U8 (Q <= 255), AA_I16,
+ * AA_I32 or AA_I64.  The arena holds item i's [oh_i, ow_i] map at byte out_offsets[i], then counts [n, Q, 3] int64 at *counts_offset and
+ * survives [n, Q] uint8 at *survives_offset, every offset a multiple of 16; the bytes between are not written.
+ * aa_back_panoptic_plan is host arithmetic only.  desc_bytes >= aa_back_panoptic_desc_bytes(n); the workspace is aa_back_many_plan's
+ * for the same items and after it one list of kept queries per item, 4 (Q + 1) bytes rounded up to 16.  Errors in
+ * aa_back_queries_plan's order with K = Q: AA_ERR_BAD_SHAPE beside n and K for Q > 256, then for AA_U8 with Q = 256; the pointers
+ * (AA_ERR_NULL); per item its own checks, then AA_ERR_BAD_SHAPE for an arena beyond 2^43 bytes or more work units than one grid holds;
+ * last AA_ERR_BAD_DTYPE.
+ * aa_resample_back_panoptic enqueues THREE launches whatever n and the sizes: the table kernel, which also compacts every item's kept
+ * queries from the scores on the device and zeroes the counts; the resample, one workgroup per 16 output rows times 256 columns, which
+ * walks only the kept queries, stores a provisional map and adds the counts with 64-bit integer atomics; and a streaming pass that
+ * applies the overlap test and rewrites the map in place.  Parameters and checks as aa_resample_back_queries', in their order, the arena
+ * on an 8-byte boundary; after the sources AA_ERR_NULL for a null io or scores, AA_ERR_STRIDES for a negative stride or a pointer that
+ * is not 4-byte aligned, AA_ERR_BAD_SHAPE for a void_value that out_dtype does not hold or a NaN threshold; last the LDS of a workgroup
+ * against the device's limit.  Nothing is allocated, synchronised or read back, and no table cache is touched.  n == 0 launches nothing.
+ * Not built: groups (the merged form), a backward, instance inference (the top-k over Q x C).  Added without an ABI version change
+ * (additive). */
+typedef struct aa_back_panoptic_io {
+  const void *scores_dev;                    /* score (0, 0), float32 */
+  int64_t scores_stride_n, scores_stride_q;  /* in ELEMENTS */
+  const void *ids_dev;                       /* id (0, 0), int32, or NULL */
+  int64_t ids_stride_n, ids_stride_q;        /* in ELEMENTS */
+  int64_t void_value;
+  double overlap_threshold;
+} aa_back_panoptic_io;
+size_t aa_back_panoptic_desc_bytes(int64_t n);
+int aa_back_panoptic_plan(int filter, int layout, int64_t n, int64_t Q, const aa_back_item *items, int out_dtype, void *desc_host, size_t desc_bytes,
+                          size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets /* n, bytes */, int64_t *counts_offset,
+                          int64_t *survives_offset);
+int aa_resample_back_panoptic(const void *desc_host, const void *desc_dev, int in_dtype, const aa_back_panoptic_io *io, void *arena_dev,
+                              size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged predictions back, backward: N gradients [K, oh_i, ow_i] to N canvases [K, H_i, W_i] ---------------------------------------
  * The backward of aa_resample_back_many's reduce 0, for losses taken at every image's own size.  Item i has a canvas [H_i, W_i], the

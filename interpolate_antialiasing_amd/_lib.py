@@ -67,6 +67,7 @@ EXPORTS = (
     "aa_back_confusion_desc_bytes", "aa_back_merged_confusion_desc_bytes", "aa_back_confusion_plan", "aa_back_merged_confusion_plan",
     "aa_resample_back_confusion",
     "aa_back_queries_desc_bytes", "aa_back_queries_plan", "aa_resample_back_queries",
+    "aa_back_panoptic_desc_bytes", "aa_back_panoptic_plan", "aa_resample_back_panoptic",
 )
 
 
@@ -298,6 +299,22 @@ class BackQueryWeights(ctypes.Structure):
     _fields_ = [("w", ctypes.c_void_p), ("stride_q", ctypes.c_int64), ("stride_c", ctypes.c_int64), ("reserved", ctypes.c_int64)]
 
 
+class BackPanopticIO(ctypes.Structure):
+    """aa_back_panoptic_io: the scores, ids, void and threshold of the panoptic call (strides in ELEMENTS; ids_dev None: the query's index)."""
+    _fields_ = [("scores_dev", ctypes.c_void_p), ("scores_stride_n", ctypes.c_int64), ("scores_stride_q", ctypes.c_int64),
+                ("ids_dev", ctypes.c_void_p), ("ids_stride_n", ctypes.c_int64), ("ids_stride_q", ctypes.c_int64),
+                ("void_value", ctypes.c_int64), ("overlap_threshold", ctypes.c_double)]
+
+
+class BackPanopticHeader(ctypes.Structure):
+    """Head of the block aa_back_panoptic_plan writes (csrc/aa_many_back_panoptic.h AABackPanopticHeader; opaque to C callers, mirrored
+    for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("Q", ctypes.c_int32), ("filter", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("out_dtype", ctypes.c_int32), ("kept_words", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("fin_units", ctypes.c_int64), ("ws_bytes", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("tables_bytes", ctypes.c_int64),
+                ("kept_off", ctypes.c_int64), ("counts_off", ctypes.c_int64), ("survives_off", ctypes.c_int64)]
+
+
 class BackBwdItemIn(ctypes.Structure):
     """aa_back_bwd_item: one item of the ragged return path's backward (strides in ELEMENTS; grad_dev None: the item has no gradient)."""
     _fields_ = [("grad_dev", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("H", ctypes.c_int64),
@@ -358,6 +375,8 @@ BACK_ACT = {None: 0, "softmax": 1, "sigmoid": 2}  # aa_back_many_plan_act activa
 BACK_ACT_MEMBERS = 16  # the most members of a group of a merged softmax plan (csrc/aa_many_back.h AA_BACK_ACT_MEMBERS)
 BACK_TILE = 256     # output columns per work unit of the return path's resample (csrc/aa_many_back.h AA_BACK_TILE)
 BACK_CONF_ROWS = 8  # output rows per work unit of the confusion call's resample (csrc/aa_many_back_confusion.h AA_BACK_CONF_ROWS)
+BACK_PANOPTIC_ROWS = 16  # output rows per work unit of the panoptic call's resample (csrc/aa_many_back_panoptic.h AA_BACK_PANOPTIC_ROWS)
+BACK_PANOPTIC_FIN_BYTES = 16384  # bytes of a map per work unit of its finalise (csrc/aa_many_back_panoptic.h AA_BACK_PANOPTIC_FIN_BYTES)
 BACK_QUERIES_MAX = 256  # the most queries of the mask-classification call (csrc/aa_many_back_queries.h AA_BACK_QUERIES_MAX_Q)
 BACK_BWD_ROWS, BACK_BWD_COLS = 4, 64  # canvas rows and columns per work unit of the return path's backward (csrc/aa_many_back_bwd.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
@@ -625,6 +644,13 @@ def load() -> ctypes.CDLL:
     L.aa_back_queries_plan.restype = i32
     L.aa_resample_back_queries.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp]
     L.aa_resample_back_queries.restype = i32
+    L.aa_back_panoptic_desc_bytes.argtypes = [i64]
+    L.aa_back_panoptic_desc_bytes.restype = sz
+    L.aa_back_panoptic_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),
+                                        ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.aa_back_panoptic_plan.restype = i32
+    L.aa_resample_back_panoptic.argtypes = [vp, vp, i32, ctypes.POINTER(BackPanopticIO), vp, sz, vp, sz, vp]
+    L.aa_resample_back_panoptic.restype = i32
     L.aa_back_many_bwd_desc_bytes.argtypes = [i64]
     L.aa_back_many_bwd_desc_bytes.restype = sz
     L.aa_back_many_bwd_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackBwdItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),

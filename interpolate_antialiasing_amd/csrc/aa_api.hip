@@ -12,6 +12,7 @@
 #include "aa_many_back_bwd.h"
 #include "aa_many_back_confusion.h"
 #include "aa_many_back_queries.h"
+#include "aa_many_back_panoptic.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_maps.h"
@@ -696,6 +697,21 @@ int aa_resample_back_queries(const void *desc_host, const void *desc_dev, int in
                              size_t workspace_bytes, aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_back_queries(desc_host, desc_dev, in_dtype, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- ragged predictions back, panoptic inference: the winner among the kept queries, per-query areas, the overlap test ------------------
+size_t aa_back_panoptic_desc_bytes(int64_t n) { return aa_back_panoptic_desc_size(n); }
+
+int aa_back_panoptic_plan(int filter, int layout, int64_t n, int64_t Q, const aa_back_item *items, int out_dtype, void *desc_host, size_t desc_bytes,
+                          size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets, int64_t *counts_offset, int64_t *survives_offset) {
+  return aa_back_panoptic_plan_host(filter, layout, n, Q, items, out_dtype, desc_host, desc_bytes, workspace_bytes, arena_bytes, out_offsets,
+                                    counts_offset, survives_offset);
+}
+
+int aa_resample_back_panoptic(const void *desc_host, const void *desc_dev, int in_dtype, const aa_back_panoptic_io *io, void *arena_dev,
+                              size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_back_panoptic(desc_host, desc_dev, in_dtype, io, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- ragged predictions back, backward -----------------------------------------------------------------------------------------------------

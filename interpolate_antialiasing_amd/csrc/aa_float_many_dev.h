@@ -104,4 +104,29 @@ __device__ inline void class_sums(const T *p, int64_t sch, int64_t prow, int64_t
   }
 }
 
+// The same sums for V classes that are not evenly spaced: class c at p + off[c] elements (the kept queries of a panoptic item).  The
+// arithmetic of a class is class_sums' to the bit: the same products and adds in the same order.
+template <typename T, int V>
+__device__ inline void class_sums_at(const T *p, const int64_t (&off)[V], int64_t prow, int64_t ppx, const Row &ry, const Row &rx, float (&acc)[V]) {
+  for (int j = 0; j < ry.n; j++) {
+    const T *rp = p + j * prow;
+    float hs[V], e[V];
+#pragma unroll
+    for (int c = 0; c < V; c++) e[c] = to_f32(rp[off[c]]);
+    const float w0 = rx.w[0];
+#pragma unroll
+    for (int c = 0; c < V; c++) hs[c] = e[c] * w0;
+    for (int k = 1; k < rx.n; k++) {
+#pragma unroll
+      for (int c = 0; c < V; c++) e[c] = to_f32(rp[k * ppx + off[c]]);
+      const float wk = rx.w[k];
+#pragma unroll
+      for (int c = 0; c < V; c++) hs[c] = hs[c] + e[c] * wk;
+    }
+    const float wj = ry.w[j];
+#pragma unroll
+    for (int c = 0; c < V; c++) acc[c] = j == 0 ? hs[c] * wj : acc[c] + hs[c] * wj;
+  }
+}
+
 }  // namespace

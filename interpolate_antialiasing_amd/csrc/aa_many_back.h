@@ -15,6 +15,11 @@
 #define AA_BACK_UNROLL 4          // classes a lane carries through its windows at a time
 #define AA_BACK_MAX_ELEMS ((int64_t)1 << 40)  // the bound on K * oh_i * ow_i, and on the elements of the arena
 
+// The counting calls (confusion matrices, panoptic areas): a wave keeps (key, count) pairs in LDS between the rows of its tile.
+#define AA_BACK_CONF_SLOTS 64       // (key, count) slots of a wave: a lane flushes one
+#define AA_BACK_CONF_COUNT_BITS 16  // a slot is key << 16 | count; a wave counts at most 64 pixels times the rows of its tile
+#define AA_BACK_CONF_ZERO 4096      // elements of the result a workgroup of the table kernel zeroes at a time
+
 enum { AA_BACK_VALUES = 0, AA_BACK_ARGMAX = 1, AA_BACK_GREATER = 2 };
 // The activation an item's (a member's) fp32 value goes through before the reduction (and before the merged call's sum) is one of
 // include/aa_interp.h's AA_BACK_ACT_NONE / _SOFTMAX / _SIGMOID; the device code is aa_activation.h.

@@ -14,9 +14,7 @@
 #ifndef AA_BACK_CONF_ROWS
 #define AA_BACK_CONF_ROWS 8   // output rows a workgroup walks, its counts kept in LDS between them (profiles/resize_many_back_confusion.txt)
 #endif
-#define AA_BACK_CONF_SLOTS 64       // (key, count) slots of a wave: a lane flushes one
-#define AA_BACK_CONF_COUNT_BITS 16  // a slot is key << 16 | count; a wave counts at most 64 * AA_BACK_CONF_ROWS pixels
-#define AA_BACK_CONF_ZERO 4096      // elements of the result a workgroup of the table kernel zeroes at a time
+// (the slots of a wave, AA_BACK_CONF_SLOTS of key << AA_BACK_CONF_COUNT_BITS | count: aa_many_back.h)
 static_assert(AA_BACK_CONF_ROWS >= 1 && 64 * AA_BACK_CONF_ROWS < (1 << AA_BACK_CONF_COUNT_BITS), "a slot's count holds a wave's pixels");
 
 struct AABackConfHeader {

@@ -35,14 +35,10 @@ __global__ void __launch_bounds__(AA_BACK_THREADS) conf_tables(const AABackItem 
     table_axis_build<AA_BACK_THREADS>(ax, filter, 0);
     return;
   }
-  const int64_t step = ((int64_t)gridDim.x - 2 * (int64_t)n) * AA_BACK_CONF_ZERO;
-  for (int64_t base = b * AA_BACK_CONF_ZERO; base < conf_elems; base += step) {
-    const int64_t end = base + AA_BACK_CONF_ZERO < conf_elems ? base + AA_BACK_CONF_ZERO : conf_elems;
-    for (int64_t e = base + threadIdx.x; e < end; e += AA_BACK_THREADS) conf[e] = 0;
-  }
+  zero_counts(conf, conf_elems, b, (int64_t)gridDim.x - 2 * (int64_t)n);
 }
 
-// ---- the counts of a wave ------------------------------------------------------------------------------------------------------------------
+// ---- what a lane counts (the wave's table, WaveCounts, and the tile's geometry: aa_many_back_shared.h) -------------------------------------
 struct ConfArgs {
   const AABackConfTarget *targets;
   int64_t *conf;
@@ -55,69 +51,6 @@ __device__ inline int64_t load_target(const void *p, int64_t e, int dt) {
   if (dt == AA_I16) return ((const int16_t *)p)[e];
   if (dt == AA_I32) return ((const int32_t *)p)[e];
   return ((const int64_t *)p)[e];
-}
-
-constexpr unsigned long long kCountMask = (1ull << AA_BACK_CONF_COUNT_BITS) - 1;
-
-// slots: the wave's AA_BACK_CONF_SLOTS words of LDS, each key << AA_BACK_CONF_COUNT_BITS | count, 0 an empty slot (a count is never 0
-// otherwise).  conf: the output's K x K block.  Every method is called by all 64 lanes of the wave together.  Lane 0 writes what lane
-// s reads back: the accesses are relaxed atomics of wavefront scope with a fence of that scope where lanes meet, so that the compiler
-// keeps them in program order and in LDS; a wave's LDS operations complete in the order it issued them, so none of this costs a wait.
-struct WaveCounts {
-  unsigned long long *slots;
-  unsigned long long *conf;
-  int lane;
-
-  __device__ static unsigned long long get(const unsigned long long *s) { return __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-  __device__ static void set(unsigned long long *s, unsigned long long v) { __hip_atomic_store(s, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-  __device__ static void lanes_meet() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-
-  __device__ void clear() {
-    set(slots + lane, 0);
-    lanes_meet();
-  }
-
-  // `count` pixels of `key` (both uniform over the wave) into the key's slot; what another key left there goes to conf first.
-  __device__ void add(int64_t key, unsigned count) {
-    if (lane != 0) return;
-    unsigned long long *s = slots + (key % AA_BACK_CONF_SLOTS);
-    unsigned long long held = get(s);
-    if (held != 0 && (int64_t)(held >> AA_BACK_CONF_COUNT_BITS) != key) {
-      atomicAdd(conf + (held >> AA_BACK_CONF_COUNT_BITS), held & kCountMask);
-      held = 0;
-    }
-    set(s, (held != 0 ? held : (unsigned long long)key << AA_BACK_CONF_COUNT_BITS) + count);
-  }
-
-  // One row: the lanes with `active` hold `key`.  The first live lane's key, the ballot of the lanes that hold it, their count to the
-  // table, and they retire; until none is live.
-  __device__ void count_row(bool active, int64_t key) {
-    unsigned long long live = __ballot(active);
-    while (live != 0) {  // (uniform)
-      const int first = __builtin_ctzll(live);
-      const int64_t k0 = ((int64_t)__builtin_amdgcn_readlane((int)(key >> 32), first) << 32) | (unsigned)__builtin_amdgcn_readlane((int)key, first);
-      const unsigned long long same = __ballot(active && key == k0);
-      add(k0, (unsigned)__popcll(same));
-      live &= ~same;
-    }
-  }
-
-  // After the last row: lane s adds slot s to conf.
-  __device__ void flush() {
-    lanes_meet();
-    const unsigned long long held = get(slots + lane);
-    if (held != 0) atomicAdd(conf + (held >> AA_BACK_CONF_COUNT_BITS), held & kCountMask);
-  }
-};
-
-// The rows [y0, y1) of a unit's row tile and the lane's column; false for a wave wholly beyond ow, which leaves.
-struct ConfTile { int y0, y1, x; };
-__device__ inline bool conf_tile(int64_t u, int xtiles, int oh, int ow, ConfTile &t) {
-  const int ty = (int)(u / xtiles);
-  t.x = (int)(u - (int64_t)ty * xtiles) * AA_BACK_TILE + (int)threadIdx.x;
-  t.y0 = ty * AA_BACK_CONF_ROWS;
-  t.y1 = t.y0 + AA_BACK_CONF_ROWS < oh ? t.y0 + AA_BACK_CONF_ROWS : oh;
-  return t.x - (int)(threadIdx.x & 63) < ow;
 }
 
 // The lane's key of target element e with label p, and whether it counts.
@@ -137,9 +70,9 @@ __global__ void __launch_bounds__(AA_BACK_TILE) conf_resample(BackArgs a, ConfAr
   const int item = aa_unit_item(a.unit0, a.n, unit);
   const AABackItem &it = a.items[item];
   const AABackConfTarget &tg = c.targets[item];
-  ConfTile t;
-  if (!conf_tile(unit - a.unit0[item], it.xtiles, it.oh, it.ow, t)) return;  // (no barrier below)
-  WaveCounts wc = {slots + (threadIdx.x >> 6) * AA_BACK_CONF_SLOTS, (unsigned long long *)c.conf + tg.conf_off, (int)(threadIdx.x & 63)};
+  RowTile t;
+  if (!row_tile<AA_BACK_CONF_ROWS>(unit - a.unit0[item], it.xtiles, it.oh, it.ow, t)) return;  // (no barrier below)
+  WaveCounts<ConfSink> wc = {slots + (threadIdx.x >> 6) * AA_BACK_CONF_SLOTS, {(unsigned long long *)c.conf + tg.conf_off}, (int)(threadIdx.x & 63)};
   wc.clear();
   const bool inside = t.x < it.ow;
   const int xs = (it.flags & AA_MANY_FLIP_X) ? it.ow - 1 - t.x : t.x;
@@ -164,9 +97,9 @@ __global__ void __launch_bounds__(AA_BACK_TILE) conf_resample_merged(MergedArgs 
   const int g = aa_unit_item(a.unit0, a.G, unit);
   const AABackGroup &gr = a.groups[g];
   const AABackConfTarget &tg = c.targets[g];
-  ConfTile t;
-  if (!conf_tile(unit - a.unit0[g], gr.xtiles, gr.oh, gr.ow, t)) return;  // (no barrier below)
-  WaveCounts wc = {slots + (threadIdx.x >> 6) * AA_BACK_CONF_SLOTS, (unsigned long long *)c.conf + tg.conf_off, (int)(threadIdx.x & 63)};
+  RowTile t;
+  if (!row_tile<AA_BACK_CONF_ROWS>(unit - a.unit0[g], gr.xtiles, gr.oh, gr.ow, t)) return;  // (no barrier below)
+  WaveCounts<ConfSink> wc = {slots + (threadIdx.x >> 6) * AA_BACK_CONF_SLOTS, {(unsigned long long *)c.conf + tg.conf_off}, (int)(threadIdx.x & 63)};
   wc.clear();
   const bool inside = t.x < gr.ow;
   const SoftmaxPair *pairs = nullptr;
@@ -235,12 +168,6 @@ inline ConfSections conf_sections(const void *block, int64_t n, int64_t G, int m
   }
   s.targets = (const AABackConfTarget *)(s.unit0 + (merged ? G : n) + 1);
   return s;
-}
-
-// The workgroups of launch 1 that zero: one per AA_BACK_CONF_ZERO elements, 65536 at most (they stride).
-inline unsigned zero_blocks(int64_t conf_elems) {
-  const int64_t b = (conf_elems + AA_BACK_CONF_ZERO - 1) / AA_BACK_CONF_ZERO;
-  return (unsigned)(b < 65536 ? b : 65536);
 }
 
 }  // namespace

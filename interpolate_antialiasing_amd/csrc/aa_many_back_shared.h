@@ -1,5 +1,6 @@
 // aa_many_back_shared.h — what the files of the ragged return path share (aa_many_back.hip: values, labels and masks;
-// aa_many_back_confusion.hip: confusion matrices): the argument blocks of the resamples, the classes of one pixel of an item and of a
+// aa_many_back_confusion.hip: confusion matrices; aa_many_back_queries.hip and aa_many_back_panoptic.hip: mask-classification heads):
+// the counts of a wave and the geometry of a row tile for the files that count, the argument blocks of the resamples, the classes of one pixel of an item and of a
 // group as an epilogue sees them (each_class, the activation's walks, the merged member loop), the argmax rule, and on the host what the
 // planners check first, the record of an item, the slots of a merged plan's groups and what a launch checks of the sources.  Each is
 // written here once.  In the unnamed namespace like the kernels that use it; only for files built with -ffp-contract=off -fno-fast-math
@@ -172,7 +173,94 @@ __device__ inline void group_classes(const MergedArgs &a, const AABackGroup &gr,
   }
 }
 
+// ---- the counts of a wave ------------------------------------------------------------------------------------------------------------------
+// (aa_many_back_confusion.hip: key = target * K + label; aa_many_back_panoptic.hip: key = 2 * winner + inside)
+constexpr unsigned long long kCountMask = (1ull << AA_BACK_CONF_COUNT_BITS) - 1;
+
+// Where a confusion matrix's (key, count) goes: element `key` of the output's K x K block.
+struct ConfSink {
+  unsigned long long *conf;
+  __device__ void operator()(unsigned long long key, unsigned long long count) const { atomicAdd(conf + key, count); }
+};
+
+// slots: the wave's AA_BACK_CONF_SLOTS words of LDS, each key << AA_BACK_CONF_COUNT_BITS | count, 0 an empty slot (a count is never 0
+// otherwise).  sink(key, count): what leaves a slot goes to the result, by 64-bit integer atomic adds.  Every method is called by all 64
+// lanes of the wave together.  Lane 0 writes what lane
+// s reads back: the accesses are relaxed atomics of wavefront scope with a fence of that scope where lanes meet, so that the compiler
+// keeps them in program order and in LDS; a wave's LDS operations complete in the order it issued them, so none of this costs a wait.
+template <typename Sink> struct WaveCounts {
+  unsigned long long *slots;
+  Sink sink;
+  int lane;
+
+  __device__ static unsigned long long get(const unsigned long long *s) { return __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+  __device__ static void set(unsigned long long *s, unsigned long long v) { __hip_atomic_store(s, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+  __device__ static void lanes_meet() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+  __device__ void clear() {
+    set(slots + lane, 0);
+    lanes_meet();
+  }
+
+  // `count` pixels of `key` (both uniform over the wave) into the key's slot; what another key left there goes to the sink first.
+  __device__ void add(int64_t key, unsigned count) {
+    if (lane != 0) return;
+    unsigned long long *s = slots + (key % AA_BACK_CONF_SLOTS);
+    unsigned long long held = get(s);
+    if (held != 0 && (int64_t)(held >> AA_BACK_CONF_COUNT_BITS) != key) {
+      sink(held >> AA_BACK_CONF_COUNT_BITS, held & kCountMask);
+      held = 0;
+    }
+    set(s, (held != 0 ? held : (unsigned long long)key << AA_BACK_CONF_COUNT_BITS) + count);
+  }
+
+  // One row: the lanes with `active` hold `key`.  The first live lane's key, the ballot of the lanes that hold it, their count to the
+  // table, and they retire; until none is live.
+  __device__ void count_row(bool active, int64_t key) {
+    unsigned long long live = __ballot(active);
+    while (live != 0) {  // (uniform)
+      const int first = __builtin_ctzll(live);
+      const int64_t k0 = ((int64_t)__builtin_amdgcn_readlane((int)(key >> 32), first) << 32) | (unsigned)__builtin_amdgcn_readlane((int)key, first);
+      const unsigned long long same = __ballot(active && key == k0);
+      add(k0, (unsigned)__popcll(same));
+      live &= ~same;
+    }
+  }
+
+  // After the last row: lane s hands slot s to the sink.
+  __device__ void flush() {
+    lanes_meet();
+    const unsigned long long held = get(slots + lane);
+    if (held != 0) sink(held >> AA_BACK_CONF_COUNT_BITS, held & kCountMask);
+  }
+};
+
+// The rows [y0, y1) of a unit's tile of ROWS rows and the lane's column; false for a wave wholly beyond ow, which leaves.
+struct RowTile { int y0, y1, x; };
+template <int ROWS> __device__ inline bool row_tile(int64_t u, int xtiles, int oh, int ow, RowTile &t) {
+  const int ty = (int)(u / xtiles);
+  t.x = (int)(u - (int64_t)ty * xtiles) * AA_BACK_TILE + (int)threadIdx.x;
+  t.y0 = ty * ROWS;
+  t.y1 = t.y0 + ROWS < oh ? t.y0 + ROWS : oh;
+  return t.x - (int)(threadIdx.x & 63) < ow;
+}
+
+// The workgroups of a table launch that zero a result of int64 counts, AA_BACK_CONF_ZERO elements at a time: workgroup b of `blocks`.
+__device__ inline void zero_counts(int64_t *counts, int64_t elems, int64_t b, int64_t blocks) {
+  const int64_t step = blocks * AA_BACK_CONF_ZERO;
+  for (int64_t base = b * AA_BACK_CONF_ZERO; base < elems; base += step) {
+    const int64_t end = base + AA_BACK_CONF_ZERO < elems ? base + AA_BACK_CONF_ZERO : elems;
+    for (int64_t e = base + threadIdx.x; e < end; e += AA_BACK_THREADS) counts[e] = 0;
+  }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------
+// The workgroups that zero: one per AA_BACK_CONF_ZERO elements, 65536 at most (they stride).
+inline unsigned zero_blocks(int64_t elems) {
+  const int64_t b = (elems + AA_BACK_CONF_ZERO - 1) / AA_BACK_CONF_ZERO;
+  return (unsigned)(b < 65536 ? b : 65536);
+}
+
 inline bool act_ok(int activation) { return activation >= AA_BACK_ACT_NONE && activation <= AA_BACK_ACT_SIGMOID; }
 
 // What the planners check first, in this order: the filter; the layout; n, K, reduce and the activation (own_ok: what the caller adds to

@@ -52,7 +52,8 @@ Differences, all additive:
     or ``"sigmoid"`` puts bit-exactly defined probabilities in the values' place, here and in ``resize_many_back_merged``, which sums
     several test-time passes per image before the reduction; ``resize_many_back_queries(masks, class_weights, sizes, ...)`` is the same
     way back for mask-classification heads (MaskFormer's semantic inference): Q resampled masks, their sigmoid, the product with the
-    [Q, C] class weights on the matrix unit and the argmax over C, in the same two launches;
+    [Q, C] class weights on the matrix unit and the argmax over C, in the same two launches; ``resize_many_back_panoptic(masks, scores,
+    sizes, ...)`` is their panoptic inference: the winner among the kept queries, per-query areas and the overlap test, in three;
   * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -73,7 +74,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "resize_many_back_panoptic", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -2021,7 +2022,7 @@ def resize_many_back_queries(masks, class_weights, sizes, mode: str = "bilinear"
 
     Not differentiable: with ``reduce=None``, gradients enabled and a ``masks`` or ``class_weights`` that requires grad the call raises
     ``NotImplementedError`` — call it under ``torch.no_grad()`` or pass ``.detach()``.  Not built: ``groups=`` (merged test-time
-    passes), confusion matrices, Mask2Former's panoptic and instance inference."""
+    passes), confusion matrices, instance inference (panoptic inference: ``resize_many_back_panoptic``)."""
     name = "resize_many_back_queries"
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
@@ -2067,6 +2068,118 @@ def resize_many_back_queries(masks, class_weights, sizes, mode: str = "bilinear"
                                                                                  out.numel() * es, wsp.data_ptr(), wsp.numel(), stream))[0]
     del keep
     return _back_views(arena, offs, sizes, reduce, c)
+
+
+_PANOPTIC_DTYPES = {torch.uint8: (_lib.U8, 0, 255), torch.int16: (_lib.I16, -2 ** 15, 2 ** 15 - 1), torch.int32: (_lib.I32, -2 ** 31, 2 ** 31 - 1),
+                    torch.int64: (_lib.I64, -2 ** 63, 2 ** 63 - 1)}
+
+
+def _back_per_query(name: str, what: str, t, dtype, n: int, q: int, dev):
+    """scores or ids of resize_many_back_panoptic, checked: one [N, Q] tensor of `dtype` on the masks' device, any strides."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}(): {what} must be Tensor")
+    if t.dim() != 2 or tuple(t.shape) != (n, q):
+        raise ValueError(f"{name}(): {what} must be [N, Q] = [{n}, {q}], got {list(t.shape)}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}(): {what} must be {dtype}, got {t.dtype}")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name}(): {what} is on {t.device}, masks on {dev}")
+    return t.detach()
+
+
+def resize_many_back_panoptic(masks, scores, sizes, mode: str = "bilinear", *, regions=None, flips=None, ids=None, void: int = -1,
+                              overlap_threshold: float = 0.8, out_dtype=torch.int32):
+    """Panoptic inference of mask-classification heads (MaskFormer, Mask2Former, OneFormer) at every image's own size: resample the Q
+    mask logits, take the sigmoid, scale by the query scores, argmax over the queries, and keep a query's segment only if the area it
+    won is at least ``overlap_threshold`` of its own mask.  ``masks``, ``sizes``, ``mode``, ``regions`` and ``flips`` are
+    ``resize_many_back_queries``' with its checks; 1 <= Q <= 256.  ``scores``: one float32 tensor [N, Q] on the masks' device, any
+    strides, read where it lies and never read back.  Query q of item i is KEPT iff ``scores[i, q] > 0`` (a NaN is not): fold "the label
+    is not void and the score exceeds object_mask_threshold" into the scores by zeroing the others.  ``ids``: optional int32 [N, Q], the
+    segment id a surviving query writes (the query index by default; give the stuff queries of one class one id to merge them); an id is
+    stored with a plain conversion to ``out_dtype`` (as ``Tensor.to`` converts: no range check).  ``void``: a Python int that
+    ``out_dtype`` holds.  ``out_dtype``: uint8 (Q <= 255), int16, int32 or int64.
+
+    Per item, with ``R`` the fp32 resample ``resize_many_back`` defines (bit for bit) — nothing below has a tolerance:
+
+      1. ``p[q] = sigmoid(R[q])`` (``activation="sigmoid"``'s value) and ``v[q] = scores[q] * p[q]``, one rounded fp32 product;
+      2. the winner of a pixel is the lowest kept q of the greatest ``v``, a NaN greater than every number and the first NaN kept; with
+         no kept query there is no winner; the pixel is inside iff ``p[winner] >= 0.5``;
+      3. ``counts[i, q] = (area, original, inter)``: the pixels whose winner is q; the pixels with ``p[q] >= 0.5`` whoever wins (0 for
+         a query that is not kept); the pixels whose winner is q and that are inside;
+      4. q survives iff area, original and inter are positive and ``area / original >= overlap_threshold`` in float64 (Python's
+         ``int / int``);
+      5. a pixel of the map is ``ids[i, winner]`` if it has a winner that survives and is inside, else ``void``.
+
+    Returns ``(maps, counts, survives)``: N maps [oh_i, ow_i] of ``out_dtype``, counts [N, Q, 3] int64 and survives [N, Q] bool, all
+    views of ONE arena, each on a 16-byte boundary.  N == 0 gives ([], empty counts, empty survives).  Three launches whatever N and the
+    sizes — the table kernel, which also compacts every item's kept queries on the device and zeroes the counts; a resample that walks
+    only the kept queries, stores a provisional map and counts per wave with ballots and 64-bit integer atomics; a streaming pass that
+    applies the overlap test to the map in place — no workspace beyond the tables and the kept lists, nothing read back, no
+    synchronisation.  Not differentiable: with gradients enabled and a ``masks`` or ``scores`` that requires grad the call raises
+    ``NotImplementedError`` — call it under ``torch.no_grad()`` or pass ``.detach()``.  Not built: ``groups=`` (merged test-time
+    passes), instance inference (the top-k over Q x C)."""
+    name = "resize_many_back_panoptic"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if out_dtype not in _PANOPTIC_DTYPES:
+        raise NotImplementedError(f"{name}(): out_dtype {out_dtype} is not built; {', '.join(str(d) for d in _PANOPTIC_DTYPES)}")
+    out_id, lowest, highest = _PANOPTIC_DTYPES[out_dtype]
+    if isinstance(void, bool) or not isinstance(void, int) or not (lowest <= void <= highest):
+        raise ValueError(f"{name}(): void must be an int that {out_dtype} holds ({lowest} .. {highest}), got {void!r}")
+    try:
+        overlap_threshold = float(overlap_threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}(): overlap_threshold must be a float, got {overlap_threshold!r}") from None
+    if math.isnan(overlap_threshold):
+        raise ValueError(f"{name}(): overlap_threshold must not be NaN")
+    empty = not isinstance(masks, torch.Tensor) and len(masks) == 0
+    items, dev0, n, q = ([], None, 0, int(scores.shape[1]) if isinstance(scores, torch.Tensor) and scores.dim() == 2 else 1) if empty else \
+        _back_items(name, masks, None)
+    if not (1 <= q <= _lib.BACK_QUERIES_MAX):
+        raise ValueError(f"{name}(): Q must be in 1 .. {_lib.BACK_QUERIES_MAX}, got Q = {q}")
+    if out_dtype == torch.uint8 and q > 255:
+        raise ValueError(f"{name}(): out_dtype torch.uint8 holds query indices below 255 beside its void code, got Q = {q}")
+    dev = items[0].device if items else None
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in [masks] + items + [scores] if isinstance(t, torch.Tensor))
+    scores = _back_per_query(name, "scores", scores, torch.float32, n, q, dev)
+    if ids is not None:
+        ids = _back_per_query(name, "ids", ids, torch.int32, n, q, dev)
+    sizes = _back_sizes(name, sizes, n, q)
+    rects = _back_regions(name, regions, items)
+    flips = _many_flips(name, flips, n)
+    if needs_grad:
+        raise NotImplementedError(f"{name}() is not differentiable: with masks or scores that require grad, call it under torch.no_grad() "
+                                  f"or pass .detach()")
+    if n == 0:
+        return [], torch.zeros((0, q, 3), dtype=torch.int64, device=scores.device), torch.zeros((0, q), dtype=torch.bool, device=scores.device)
+    for t in items:
+        _require_gpu(t, name)
+    items = [t.detach() for t in items]
+    recs, keep, interleaved = _back_records(items, rects, sizes, flips, q)  # (keep: alive until the launches are enqueued)
+    io = _lib.BackPanopticIO()
+    io.scores_dev, io.scores_stride_n, io.scores_stride_q = scores.data_ptr(), scores.stride(0) if n > 1 else 0, scores.stride(1) if q > 1 else 0
+    if ids is not None:
+        io.ids_dev, io.ids_stride_n, io.ids_stride_q = ids.data_ptr(), ids.stride(0) if n > 1 else 0, ids.stride(1) if q > 1 else 0
+    io.void_value, io.overlap_threshold = void, overlap_threshold
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    arena_bytes, offs = ctypes.c_size_t(0), (ctypes.c_int64 * n)()
+    counts_off, survives_off = ctypes.c_int64(0), ctypes.c_int64(0)
+
+    def planner(desc, nbytes, ws_bytes):
+        return L.aa_back_panoptic_plan(_lib.FILTER_IDS[mode], layout, n, q, recs, out_id, desc, nbytes, ws_bytes, ctypes.byref(arena_bytes), offs,
+                                       ctypes.byref(counts_off), ctypes.byref(survives_off))
+    # (the arena is int64 words, the counts' alignment; the maps and survives are views of its bytes)
+    arena = _many_run(
+        name, dev, L.aa_back_panoptic_desc_bytes(n), planner, lambda: torch.empty(((arena_bytes.value + 7) // 8,), dtype=torch.int64, device=dev),
+        lambda desc_host, desc_dev, out, wsp, stream: L.aa_resample_back_panoptic(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], ctypes.byref(io),
+                                                                                  out.data_ptr(), out.numel() * 8, wsp.data_ptr(), wsp.numel(), stream))[0]
+    del keep
+    raw = arena.view(torch.uint8)
+    maps = _back_views(raw.view(out_dtype), offs, sizes, "argmax", q)
+    counts = arena[counts_off.value // 8:counts_off.value // 8 + n * q * 3].view(n, q, 3)
+    survives = raw[survives_off.value:survives_off.value + n * q].view(torch.bool).view(n, q)
+    return maps, counts, survives
 
 
 def _back_canvas(name: str, canvas, n: int, k: int):

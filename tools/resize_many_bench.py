@@ -145,6 +145,8 @@ the same bits.  The kernel's fetched bytes come from a counter run of its own: t
                                                          # profiles/resize_many_back.txt
   python tools/resize_many_bench.py --tta --rounds 5 --batches 3 > out.txt   # only the merged way back: 6 passes per image summed, argmax (above);
                                                          # profiles/resize_many_back_merged.txt is this output
+  python tools/resize_many_bench.py --panoptic --rounds 5 --batches 3 > out.txt  # only resize_many_back_panoptic: Q = 100 masks, 10 and 100
+                                                         # kept (at panoptic()); profiles/resize_many_back_panoptic.txt
   python tools/resize_many_bench.py --queries --rounds 5 --batches 3 > out.txt   # only resize_many_back_queries: Q = 100 masks, sigmoid,
                                                          # class weights, argmax (at queries()); profiles/resize_many_back_queries.txt
   python tools/resize_many_bench.py --logits-backward > out.txt   # only the gradients' way back to the canvas (above);
@@ -1278,6 +1280,85 @@ def queries(args, torch, aa, timed):
             torch.cuda.empty_cache()
 
 
+def panoptic(args, torch, aa, timed):
+    """--panoptic: panoptic inference on --queries' geometry, Q = 100 queries, float32 and bfloat16 masks, 10 and 100 kept queries an
+    item, int32 maps, overlap_threshold 0.8.  (a) is the loop a user writes today: per item linear_forward, sigmoid, scale by the
+    scores, argmax, then the per-query area loop with three full-image reductions each (its results stay on the device: no read-back is
+    charged to it); (b) resize_many_back(activation="sigmoid"), which writes Q floats a pixel, then the same torch steps; (c)
+    resize_many_back_panoptic.  With 100 kept queries (d) resize_many_back_queries at C = 19 is timed beside them as a plausibility
+    check: both are dominated by the resample of 100 masks.  The maps of (a) and (c) are compared and the pixels that differ reported
+    (torch's sigmoid is not the package's: a near-tie may move)."""
+    from interpolate_antialiasing_amd import boxmath
+
+    n, canvas, q = 16, (512, 512), 100
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    regions = boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=canvas[0]), "center", canvas)
+    pixels = sum(h * w for h, w in shapes)
+    print(f"resize_many_bench --panoptic: [N, Q = {q}, {canvas[0]}, {canvas[1]}] mask logits on a letterbox canvas (fit_sizes(longer={canvas[0]}), "
+          f"'center') back to N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), {pixels / 1e6:.1f} M output pixels; "
+          f"bilinear; sigmoid, scores, argmax over the kept queries, areas, overlap 0.8, int32 maps; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for kept in (10, 100):
+        for dtype in (torch.float32, torch.bfloat16):
+            # smooth masks (a coarse grid upsampled) so that segments are regions, as a head's are, and some pass the overlap test
+            x = torch.nn.functional.interpolate(4.0 * torch.randn((n, q, 16, 16), device="cuda", generator=gen), size=canvas, mode="bicubic").to(dtype)
+            scores = torch.rand((n, q), device="cuda", generator=gen) * 0.7 + 0.3
+            order = torch.rand((n, q), device="cuda", generator=gen).argsort(1)
+            scores = torch.where(order < kept, scores, torch.zeros_like(scores))
+            w = torch.randn((n, q, 20), device="cuda", generator=gen).softmax(-1)[..., :19]
+
+            def torch_steps(p, s):
+                """The steps after the probabilities, as detectron2's panoptic_inference does them, on the device."""
+                keep = (s > 0).nonzero().flatten()
+                seg = torch.full(p.shape[1:], -1, dtype=torch.int32, device=p.device)
+                if keep.numel() == 0:
+                    return seg
+                pk = p[keep]
+                ids = (s[keep].view(-1, 1, 1) * pk).argmax(0)
+                for k in range(keep.numel()):
+                    won, own = ids == k, pk[k] >= 0.5
+                    area, original, mask = won.sum(), own.sum(), won & own
+                    ok = (area > 0) & (original > 0) & (mask.sum() > 0) & (area.double() / original.double().clamp(min=1) >= 0.8)
+                    seg = torch.where(mask & ok, keep[k].to(torch.int32), seg)
+                return seg
+
+            def loop():
+                out = []
+                for i, (y0, x0, h, ww) in enumerate(regions):
+                    p = aa.linear_forward(x[i, :, y0:y0 + h, x0:x0 + ww].float()[None], list(shapes[i]))[0].sigmoid_()
+                    out.append(torch_steps(p, scores[i]))
+                return out
+
+            def values_then_torch():
+                return [torch_steps(p, scores[i]) for i, p in enumerate(aa.resize_many_back(x, shapes, regions=regions, activation="sigmoid"))]
+
+            def fused():
+                return aa.resize_many_back_panoptic(x, scores, shapes, regions=regions)[0]
+
+            a_key, c_key = "a: loop: linear_forward, sigmoid, scores, argmax, per-query areas per item", "c: resize_many_back_panoptic"
+            contestants = {a_key: loop, c_key: fused, "b: resize_many_back(activation='sigmoid'), then the torch steps per item": values_then_torch}
+            if kept == q:
+                contestants["d: resize_many_back_queries(C = 19, reduce='argmax'), another call of the same resample"] = \
+                    lambda: aa.resize_many_back_queries(x, w, shapes, regions=regions, out_dtype=torch.int32)
+            run = _run_contestants(args, torch, timed, contestants)
+            results = next(run)
+            note = "a contestant does not fit"
+            if results[a_key] is not None and results[c_key] is not None:
+                differ = sum(int((p != r).sum()) for p, r in zip(results[a_key], results[c_key]))
+                segs = sum(int(r.unique().numel()) - 1 for r in results[c_key])
+                note = f"the maps of (a) and (c) differ at {differ} of {pixels} pixels ({100.0 * differ / pixels:.4f} %); {segs} segments"
+            del results
+            print(f"\nQ = {q}, {kept} kept an item, {str(dtype).replace('torch.', '')} masks: {note}")
+            stat = next(run)
+            for other, what in (("a", "the loop"), ("b", "values, then the torch steps")) + ((("d", "the queries call at C = 19"),) if kept == q else ()):
+                _against(stat, "c", other, f"the call against {what}")
+            del x, w, scores
+            torch.cuda.empty_cache()
+
+
 def fast_hist(torch, t, p, k):
     """The classic evaluation step in torch: the K x K counts of (target, prediction) over the pixels whose target is a class."""
     keep = (t >= 0) & (t < k)
@@ -1480,6 +1561,8 @@ def main():
                     "geometries against the loop, against the argmax call followed by fast_hist, and against the argmax call alone")
     ap.add_argument("--queries", action="store_true", help="only resize_many_back_queries: mask-classification semantic inference on --logits' "
                     "geometry, Q = 100, C = 19 and 150, against the per-item loops and against resize_many_back + einsum")
+    ap.add_argument("--panoptic", action="store_true", help="only resize_many_back_panoptic: panoptic inference on --queries' geometry, 10 and "
+                    "100 kept queries of 100, against the per-item torch loop and against resize_many_back plus the torch steps")
     ap.add_argument("--quick", action="store_true", help="with --confusion: K = 19 and bfloat16 only (the sweep of the kernel's tunables)")
     ap.add_argument("--noise-targets", action="store_true", help="with --confusion: targets uniform per pixel, the counting's worst case, "
                     "instead of 64 x 64 blocks of one class")
@@ -1592,6 +1675,9 @@ def main():
         return
     if args.queries:
         queries(args, torch, aa, timed)
+        return
+    if args.panoptic:
+        panoptic(args, torch, aa, timed)
         return
     if args.logits:
         (logits_activation if args.activation else logits)(args, torch, aa, timed)
