@@ -37,7 +37,8 @@ extern "C" {
                                    aa_resample_back_confusion, with aa_back_target; aa_back_queries_desc_bytes,
                                    aa_back_queries_plan, aa_resample_back_queries, with aa_back_weights;
                                    aa_back_panoptic_desc_bytes, aa_back_panoptic_plan, aa_resample_back_panoptic, with
-                                   aa_back_panoptic_io */
+                                   aa_back_panoptic_io; aa_back_instances_desc_bytes, aa_back_instances_plan,
+                                   aa_resample_back_instances, with aa_back_instances_io */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -834,7 +835,7 @@ int aa_resample_back_queries(const void *desc_host, const void *desc_dev, int in
  * on an 8-byte boundary; after the sources AA_ERR_NULL for a null io or scores, AA_ERR_STRIDES for a negative stride or a pointer that
  * is not 4-byte aligned, AA_ERR_BAD_SHAPE for a void_value that out_dtype does not hold or a NaN threshold; last the LDS of a workgroup
  * against the device's limit.  Nothing is allocated, synchronised or read back, and no table cache is touched.  n == 0 launches nothing.
- * Not built: groups (the merged form), a backward, instance inference (the top-k over Q x C).  Added without an ABI version change
+ * Not built: groups (the merged form), a backward (instance inference: aa_back_instances_plan).  Added without an ABI version change
  * (additive). */
 typedef struct aa_back_panoptic_io {
   const void *scores_dev;                    /* score (0, 0), float32 */
@@ -850,6 +851,46 @@ int aa_back_panoptic_plan(int filter, int layout, int64_t n, int64_t Q, const aa
                           int64_t *survives_offset);
 int aa_resample_back_panoptic(const void *desc_host, const void *desc_dev, int in_dtype, const aa_back_panoptic_io *io, void *arena_dev,
                               size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back, instance inference: the asked masks thresholded and stored per slot, with area, score sum and box ---------
+ * Instance inference of MaskFormer-style heads, per image: M slots, slot m asking for query queries[i, m] (after a top-k over Q x C:
+ * the index // C, so entries repeat); an entry outside 0 .. Q - 1 is an empty slot.  Item i is an aa_back_item with K = Q (1 .. 256);
+ * 1 <= M <= 256.  With R_i the fp32 value aa_back_many_plan's section defines for item i (bit for bit; for AA_MANY_FLIP_X mirrored
+ * left to right) and q = queries[i, m]:
+ *   mask[m][y, x] = R_i[q][y, x] > 0 (false for a NaN); all zeros for an empty slot
+ *   stats[i, m]   = (area, psum, x0, y0, x1, y1), int64, over the pixels of mask[m]: their count; the sum of sigmoid(R_i[q]) * 2^24,
+ *                   the sigmoid of aa_back_many_plan_act — of a positive value it lies in [0.5, 1], where every float32 is a multiple
+ *                   of 2^-24, so each term is an exact integer and the mask score is psum / 2^24 / area; the tight half-open box in
+ *                   the output's own (un-mirrored) coordinates.  An empty mask has area = psum = 0 and the box (ow_i, oh_i, 0, 0).
+ * Everything is integers: the same bits on every run.  bits = 0 stores a mask as [oh_i, ow_i] bytes 0 / 1, bits = 1 as [oh_i,
+ * ceil(ow_i / 8)] bytes, column x in bit x & 7 of byte x >> 3 and the unused bits of a row's last byte 0.  The arena holds item i's
+ * [M, ...] masks at byte out_offsets[i], then stats [n, M, 6] at *stats_offset, every offset a multiple of 16; the bytes between are
+ * not written.
+ * aa_back_instances_plan is host arithmetic only.  desc_bytes >= aa_back_instances_desc_bytes(n); the workspace is aa_back_many_plan's
+ * for the same items and after it one work list per item, 4 (2 + 2 Q + M) bytes rounded up to 16.  Errors in aa_back_panoptic_plan's
+ * order with K = Q: AA_ERR_BAD_SHAPE beside n and K for Q > 256, M outside 1 .. 256 or bits outside 0 .. 1; the pointers (AA_ERR_NULL);
+ * per item its own checks, then AA_ERR_BAD_SHAPE for M * oh_i * ow_i beyond 2^40, an arena beyond 2^43 bytes or more work units than
+ * one grid holds.
+ * aa_resample_back_instances enqueues TWO launches whatever n, M and the sizes: the table kernel, which also sorts every item's slots by
+ * query on the device, lists its distinct asked queries and sets the stats to their identities; and the resample, one workgroup per 8
+ * output rows times 256 columns, which resamples every distinct asked query ONCE, stores its ballot word for each slot that asked and
+ * adds the stats with 64-bit integer atomics.  Parameters and checks as aa_resample_back_panoptic's, in their order; after the sources
+ * AA_ERR_NULL for a null io or queries, AA_ERR_BAD_DTYPE for queries_elem_bytes other than 4 and 8, AA_ERR_STRIDES for a negative stride
+ * or a pointer that is not aligned to its element; last the LDS of a workgroup against the device's limit.  Nothing is allocated,
+ * synchronised or read back, and no table cache is touched.  n == 0 launches nothing.  Not built: the top-k itself, run-length
+ * encoding, groups (the merged form), a backward.  Added without an ABI version change (additive). */
+typedef struct aa_back_instances_io {
+  const void *queries_dev;                     /* query (0, 0), int32 or int64 */
+  int64_t queries_stride_n, queries_stride_m;  /* in ELEMENTS */
+  int32_t queries_elem_bytes;                  /* 4 or 8 */
+  int32_t reserved;
+} aa_back_instances_io;
+size_t aa_back_instances_desc_bytes(int64_t n);
+int aa_back_instances_plan(int filter, int layout, int64_t n, int64_t Q, int64_t M, const aa_back_item *items, int bits, void *desc_host,
+                           size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets /* n, bytes */,
+                           int64_t *stats_offset);
+int aa_resample_back_instances(const void *desc_host, const void *desc_dev, int in_dtype, const aa_back_instances_io *io, void *arena_dev,
+                               size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged predictions back, backward: N gradients [K, oh_i, ow_i] to N canvases [K, H_i, W_i] ---------------------------------------
  * The backward of aa_resample_back_many's reduce 0, for losses taken at every image's own size.  Item i has a canvas [H_i, W_i], the

@@ -68,6 +68,7 @@ EXPORTS = (
     "aa_resample_back_confusion",
     "aa_back_queries_desc_bytes", "aa_back_queries_plan", "aa_resample_back_queries",
     "aa_back_panoptic_desc_bytes", "aa_back_panoptic_plan", "aa_resample_back_panoptic",
+    "aa_back_instances_desc_bytes", "aa_back_instances_plan", "aa_resample_back_instances",
 )
 
 
@@ -315,6 +316,21 @@ class BackPanopticHeader(ctypes.Structure):
                 ("kept_off", ctypes.c_int64), ("counts_off", ctypes.c_int64), ("survives_off", ctypes.c_int64)]
 
 
+class BackInstancesIO(ctypes.Structure):
+    """aa_back_instances_io: the queries of the instance call (strides in ELEMENTS of elem_bytes, 4 for int32 and 8 for int64)."""
+    _fields_ = [("queries_dev", ctypes.c_void_p), ("queries_stride_n", ctypes.c_int64), ("queries_stride_m", ctypes.c_int64),
+                ("queries_elem_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class BackInstancesHeader(ctypes.Structure):
+    """Head of the block aa_back_instances_plan writes (csrc/aa_many_back_instances.h AABackInstancesHeader; opaque to C callers,
+    mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("Q", ctypes.c_int32), ("M", ctypes.c_int32), ("filter", ctypes.c_int32),
+                ("layout", ctypes.c_int32), ("bits", ctypes.c_int32), ("list_words", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("tables_bytes", ctypes.c_int64), ("lists_off", ctypes.c_int64),
+                ("stats_off", ctypes.c_int64)]
+
+
 class BackBwdItemIn(ctypes.Structure):
     """aa_back_bwd_item: one item of the ragged return path's backward (strides in ELEMENTS; grad_dev None: the item has no gradient)."""
     _fields_ = [("grad_dev", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("H", ctypes.c_int64),
@@ -377,6 +393,8 @@ BACK_TILE = 256     # output columns per work unit of the return path's resample
 BACK_CONF_ROWS = 8  # output rows per work unit of the confusion call's resample (csrc/aa_many_back_confusion.h AA_BACK_CONF_ROWS)
 BACK_PANOPTIC_ROWS = 16  # output rows per work unit of the panoptic call's resample (csrc/aa_many_back_panoptic.h AA_BACK_PANOPTIC_ROWS)
 BACK_PANOPTIC_FIN_BYTES = 16384  # bytes of a map per work unit of its finalise (csrc/aa_many_back_panoptic.h AA_BACK_PANOPTIC_FIN_BYTES)
+BACK_INSTANCES_ROWS = 8  # output rows per work unit of the instance call's resample (csrc/aa_many_back_instances.h AA_BACK_INSTANCES_ROWS)
+BACK_INSTANCES_MAX_M = 256  # the most slots of an item of the instance call (csrc/aa_many_back_instances.h AA_BACK_INSTANCES_MAX_M)
 BACK_QUERIES_MAX = 256  # the most queries of the mask-classification call (csrc/aa_many_back_queries.h AA_BACK_QUERIES_MAX_Q)
 BACK_BWD_ROWS, BACK_BWD_COLS = 4, 64  # canvas rows and columns per work unit of the return path's backward (csrc/aa_many_back_bwd.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
@@ -651,6 +669,13 @@ def load() -> ctypes.CDLL:
     L.aa_back_panoptic_plan.restype = i32
     L.aa_resample_back_panoptic.argtypes = [vp, vp, i32, ctypes.POINTER(BackPanopticIO), vp, sz, vp, sz, vp]
     L.aa_resample_back_panoptic.restype = i32
+    L.aa_back_instances_desc_bytes.argtypes = [i64]
+    L.aa_back_instances_desc_bytes.restype = sz
+    L.aa_back_instances_plan.argtypes = [i32, i32, i64, i64, i64, ctypes.POINTER(BackItemIn), i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),
+                                         ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.aa_back_instances_plan.restype = i32
+    L.aa_resample_back_instances.argtypes = [vp, vp, i32, ctypes.POINTER(BackInstancesIO), vp, sz, vp, sz, vp]
+    L.aa_resample_back_instances.restype = i32
     L.aa_back_many_bwd_desc_bytes.argtypes = [i64]
     L.aa_back_many_bwd_desc_bytes.restype = sz
     L.aa_back_many_bwd_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackBwdItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),

@@ -377,3 +377,10 @@ def ycbcr_rgb_tables():
     truncates towards zero (Python's int() does too).  R = clip(Y + (R_Cr[Cr] >> 6)), G = clip(Y + ((G_Cb[Cb] + G_Cr[Cr]) >> 6)),
     B = clip(Y + (B_Cb[Cb] >> 6)), >> arithmetic.  The library computes the same entries in registers (csrc/aa_ycbcr.h)."""
     return tuple([int(c * 64 * (v - 128) + 0.5) for v in range(256)] for c in _YCC_COEFFS)
+
+
+def instance_scores(stats):
+    """Mask2Former's mask scores from ``resize_many_back_instances``' stats [N, M, 6]: ``psum / 2^24 / (area + 1e-6)`` as a float64
+    tensor [N, M] — the mean of the sigmoid over the mask's pixels, 0 for an empty mask or slot.  psum is exact, so the score is the
+    same bits on every run.  (Works on the tensor's own methods: this module does not import torch.)"""
+    return stats[..., 1].double() / float(1 << 24) / (stats[..., 0].double() + 1e-6)

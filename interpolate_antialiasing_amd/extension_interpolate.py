@@ -54,6 +54,8 @@ Differences, all additive:
     way back for mask-classification heads (MaskFormer's semantic inference): Q resampled masks, their sigmoid, the product with the
     [Q, C] class weights on the matrix unit and the argmax over C, in the same two launches; ``resize_many_back_panoptic(masks, scores,
     sizes, ...)`` is their panoptic inference: the winner among the kept queries, per-query areas and the overlap test, in three;
+    ``resize_many_back_instances(masks, queries, sizes, ...)`` is their instance inference: the asked masks thresholded and stored per
+    instance as bool or packed bits, with areas, exact mask-score sums and boxes, in two;
   * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -74,7 +76,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "resize_many_back_panoptic", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "resize_many_back_panoptic", "resize_many_back_instances", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -2022,7 +2024,8 @@ def resize_many_back_queries(masks, class_weights, sizes, mode: str = "bilinear"
 
     Not differentiable: with ``reduce=None``, gradients enabled and a ``masks`` or ``class_weights`` that requires grad the call raises
     ``NotImplementedError`` — call it under ``torch.no_grad()`` or pass ``.detach()``.  Not built: ``groups=`` (merged test-time
-    passes), confusion matrices, instance inference (panoptic inference: ``resize_many_back_panoptic``)."""
+    passes), confusion matrices (panoptic inference: ``resize_many_back_panoptic``; instance inference:
+    ``resize_many_back_instances``)."""
     name = "resize_many_back_queries"
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
@@ -2117,7 +2120,7 @@ def resize_many_back_panoptic(masks, scores, sizes, mode: str = "bilinear", *, r
     applies the overlap test to the map in place — no workspace beyond the tables and the kept lists, nothing read back, no
     synchronisation.  Not differentiable: with gradients enabled and a ``masks`` or ``scores`` that requires grad the call raises
     ``NotImplementedError`` — call it under ``torch.no_grad()`` or pass ``.detach()``.  Not built: ``groups=`` (merged test-time
-    passes), instance inference (the top-k over Q x C)."""
+    passes) (instance inference: ``resize_many_back_instances``)."""
     name = "resize_many_back_panoptic"
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
@@ -2180,6 +2183,92 @@ def resize_many_back_panoptic(masks, scores, sizes, mode: str = "bilinear", *, r
     counts = arena[counts_off.value // 8:counts_off.value // 8 + n * q * 3].view(n, q, 3)
     survives = raw[survives_off.value:survives_off.value + n * q].view(torch.bool).view(n, q)
     return maps, counts, survives
+
+
+def resize_many_back_instances(masks, queries, sizes, mode: str = "bilinear", *, regions=None, flips=None, mask_format: str = "bool"):
+    """Instance inference of mask-classification heads (MaskFormer, Mask2Former, OneFormer) at every image's own size: of the Q mask
+    logits resample only the asked ones, threshold at 0, and per instance store the mask and count its area, its mask-score sum and its
+    box.  ``masks``, ``sizes``, ``mode``, ``regions`` and ``flips`` are ``resize_many_back_panoptic``'s with its checks; 1 <= Q <= 256.
+    ``queries``: one int32 or int64 tensor [N, M] on the masks' device, 1 <= M <= 256, any non-negative strides, read where it lies
+    and never read back.  Slot m of item i asks for query ``queries[i, m]``; an entry outside 0 .. Q - 1 (such as -1) is an EMPTY slot,
+    for an item with fewer than M instances.  Entries may repeat — after ``topk`` over ``scores.flatten(1)`` and ``// C`` they do — and
+    a repeated query is resampled once.
+
+    Per item, with ``R`` the fp32 resample ``resize_many_back`` defines (bit for bit) — nothing below has a tolerance:
+
+      * slot m's mask is ``R[queries[i, m]] > 0`` (Mask2Former's ``mask_pred > 0``; a NaN is false), all zeros for an empty slot;
+      * ``mask_format="bool"``: a ``torch.bool`` [M, oh_i, ow_i]; ``"bits"``: a uint8 [M, oh_i, ceil(ow_i / 8)] equal to
+        ``numpy.packbits(mask, axis=-1, bitorder="little")``, the unused bits of a row's last byte 0;
+      * ``stats[i, m] = (area, psum, x0, y0, x1, y1)`` int64 over the mask's pixels: their count; the sum of ``p * 2^24`` with
+        ``p = sigmoid(R)`` (``activation="sigmoid"``'s value) — of a positive value ``p`` lies in [0.5, 1], where every float32 is a
+        multiple of 2^-24, so the sum is exact and the same bits on every run; the tight half-open box in the image's own
+        (un-mirrored) coordinates, detectron2's ``BitMasks.get_bounding_boxes``.  An empty mask, and an empty slot, has
+        ``area = psum = 0`` and the box ``(ow_i, oh_i, 0, 0)`` — the identities of the minimum and the maximum: test ``area``.
+        ``boxmath.instance_scores(stats)`` gives Mask2Former's mask scores ``psum / 2^24 / (area + 1e-6)``.
+
+    Returns ``(masks_out, stats)``: N views of ONE arena, each on a 16-byte boundary, and stats [N, M, 6] behind them.  N == 0 gives
+    ([], empty stats).  Two launches whatever N, M and the sizes — the table kernel, which also sorts every item's slots by query on
+    the device, lists its distinct queries and sets the stats to their identities; and a resample that takes ONE ballot word per
+    (distinct query, row, wave), stores it for every slot that asked, skips sigmoid and counting where it is 0 and adds the rest with
+    64-bit integer atomics — no workspace beyond the tables and the work lists, nothing read back, no synchronisation.  Not
+    differentiable: with gradients enabled and a ``masks`` that requires grad the call raises ``NotImplementedError`` — call it under
+    ``torch.no_grad()`` or pass ``.detach()``.  Not built: the top-k itself, run-length encoding, ``groups=`` (merged test-time
+    passes)."""
+    name = "resize_many_back_instances"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if mask_format not in ("bool", "bits"):
+        raise ValueError(f"{name}(): mask_format must be 'bool' or 'bits', got {mask_format!r}")
+    bits = mask_format == "bits"
+    if not isinstance(queries, torch.Tensor):
+        raise TypeError(f"{name}(): queries must be Tensor")
+    if queries.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}(): queries must be torch.int32 or torch.int64, got {queries.dtype}")
+    empty = not isinstance(masks, torch.Tensor) and len(masks) == 0
+    items, dev0, n, q = ([], None, 0, 1) if empty else _back_items(name, masks, None)
+    if not (1 <= q <= _lib.BACK_QUERIES_MAX):
+        raise ValueError(f"{name}(): Q must be in 1 .. {_lib.BACK_QUERIES_MAX}, got Q = {q}")
+    if queries.dim() != 2 or int(queries.shape[0]) != n:
+        raise ValueError(f"{name}(): queries must be [N, M] = [{n}, M], got {list(queries.shape)}")
+    m = int(queries.shape[1])
+    if not (1 <= m <= _lib.BACK_INSTANCES_MAX_M):
+        raise ValueError(f"{name}(): M must be in 1 .. {_lib.BACK_INSTANCES_MAX_M}, got M = {m}")
+    dev = items[0].device if items else None
+    if dev is not None and queries.device != dev:
+        raise ValueError(f"{name}(): queries is on {queries.device}, masks on {dev}")
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in [masks] + items if isinstance(t, torch.Tensor))
+    sizes = _back_sizes(name, sizes, n, max(q, m))
+    rects = _back_regions(name, regions, items)
+    flips = _many_flips(name, flips, n)
+    if needs_grad:
+        raise NotImplementedError(f"{name}() is not differentiable: with masks that require grad, call it under torch.no_grad() or pass .detach()")
+    if n == 0:
+        return [], torch.zeros((0, m, 6), dtype=torch.int64, device=queries.device)
+    for t in items:
+        _require_gpu(t, name)
+    items = [t.detach() for t in items]
+    recs, keep, interleaved = _back_records(items, rects, sizes, flips, q)  # (keep: alive until the launches are enqueued)
+    io = _lib.BackInstancesIO()
+    io.queries_dev, io.queries_elem_bytes = queries.data_ptr(), queries.element_size()
+    io.queries_stride_n, io.queries_stride_m = queries.stride(0) if n > 1 else 0, queries.stride(1) if m > 1 else 0
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    arena_bytes, offs, stats_off = ctypes.c_size_t(0), (ctypes.c_int64 * n)(), ctypes.c_int64(0)
+
+    def planner(desc, nbytes, ws_bytes):
+        return L.aa_back_instances_plan(_lib.FILTER_IDS[mode], layout, n, q, m, recs, int(bits), desc, nbytes, ws_bytes, ctypes.byref(arena_bytes),
+                                        offs, ctypes.byref(stats_off))
+    # (the arena is int64 words, the stats' alignment; the masks are views of its bytes)
+    arena = _many_run(
+        name, dev, L.aa_back_instances_desc_bytes(n), planner, lambda: torch.empty(((arena_bytes.value + 7) // 8,), dtype=torch.int64, device=dev),
+        lambda desc_host, desc_dev, out, wsp, stream: L.aa_resample_back_instances(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], ctypes.byref(io),
+                                                                                   out.data_ptr(), out.numel() * 8, wsp.data_ptr(), wsp.numel(), stream))[0]
+    del keep
+    raw = arena.view(torch.uint8)
+    outs = _back_views(raw, offs, [(oh, (ow + 7) // 8 if bits else ow) for oh, ow in sizes], None, m)
+    if not bits:
+        outs = [o.view(torch.bool) for o in outs]
+    return outs, arena[stats_off.value // 8:stats_off.value // 8 + n * m * 6].view(n, m, 6)
 
 
 def _back_canvas(name: str, canvas, n: int, k: int):

@@ -147,6 +147,8 @@ the same bits.  The kernel's fetched bytes come from a counter run of its own: t
                                                          # profiles/resize_many_back_merged.txt is this output
   python tools/resize_many_bench.py --panoptic --rounds 5 --batches 3 > out.txt  # only resize_many_back_panoptic: Q = 100 masks, 10 and 100
                                                          # kept (at panoptic()); profiles/resize_many_back_panoptic.txt
+  python tools/resize_many_bench.py --instances --rounds 5 --batches 3 > out.txt # only resize_many_back_instances: Q = 100 masks, M = 100
+                                                         # and 20 (at instances()); profiles/resize_many_back_instances.txt
   python tools/resize_many_bench.py --queries --rounds 5 --batches 3 > out.txt   # only resize_many_back_queries: Q = 100 masks, sigmoid,
                                                          # class weights, argmax (at queries()); profiles/resize_many_back_queries.txt
   python tools/resize_many_bench.py --logits-backward > out.txt   # only the gradients' way back to the canvas (above);
@@ -1359,6 +1361,73 @@ def panoptic(args, torch, aa, timed):
             torch.cuda.empty_cache()
 
 
+def instances(args, torch, aa, timed):
+    """--instances: instance inference on --panoptic's geometry, Q = 100 queries, float32 and bfloat16 masks; M = 100 slots an item drawn
+    as a top-k over Q x 80 random class scores (queries repeat) and M = 20.  (a) is the loop a user writes today: per item
+    linear_forward of the selected masks, > 0, sigmoid, a masked sum and a count per instance; (b) resize_many_back(reduce="greater"),
+    which resamples all Q queries and writes a byte a pixel, then the gather, and resize_many_back(activation="sigmoid") with torch
+    reductions for the scores; (c) resize_many_back_instances with bool masks; (d) with packed bits.  The areas of (a) and (c) are
+    compared and the slots that differ reported."""
+    from interpolate_antialiasing_amd import boxmath
+
+    n, canvas, q, classes = 16, (512, 512), 100, 80
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    regions = boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=canvas[0]), "center", canvas)
+    pixels = sum(h * w for h, w in shapes)
+    print(f"resize_many_bench --instances: [N, Q = {q}, {canvas[0]}, {canvas[1]}] mask logits on a letterbox canvas (fit_sizes(longer={canvas[0]}), "
+          f"'center') back to N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), {pixels / 1e6:.1f} M output pixels; "
+          f"bilinear; M masks > 0 an item with area, mask-score sum and box; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for m in (100, 20):
+        for dtype in (torch.float32, torch.bfloat16):
+            # smooth masks (a coarse grid upsampled), lowered so that an instance covers a small part of its image, as a head's do
+            x = (torch.nn.functional.interpolate(4.0 * torch.randn((n, q, 16, 16), device="cuda", generator=gen), size=canvas, mode="bicubic") - 6.0).to(dtype)
+            sel = torch.rand((n, q * classes), device="cuda", generator=gen).topk(m, dim=1).indices // classes
+
+            def loop():
+                out = []
+                for i, (y0, x0, h, ww) in enumerate(regions):
+                    r = aa.linear_forward(x[i, sel[i], y0:y0 + h, x0:x0 + ww].float()[None], list(shapes[i]))[0]
+                    mask = r > 0
+                    psum = (r.sigmoid_() * mask).flatten(1).sum(1)
+                    out.append((mask, mask.flatten(1).sum(1), psum))
+                return out
+
+            def two_calls():
+                masks = aa.resize_many_back(x, shapes, regions=regions, reduce="greater", threshold=0.0)
+                probs = aa.resize_many_back(x, shapes, regions=regions, activation="sigmoid")
+                out = []
+                for i in range(n):
+                    mask = masks[i][sel[i]]
+                    out.append((mask, mask.flatten(1).sum(1), (probs[i][sel[i]] * mask).flatten(1).sum(1)))
+                return out
+
+            a_key, c_key = "a: loop: linear_forward of the selected masks, > 0, sigmoid, sums per item", "c: resize_many_back_instances(mask_format='bool')"
+            contestants = {a_key: loop, c_key: lambda: aa.resize_many_back_instances(x, sel, shapes, regions=regions),
+                           "b: resize_many_back(reduce='greater') and (activation='sigmoid'), gather, sums per item": two_calls,
+                           "d: resize_many_back_instances(mask_format='bits')": lambda: aa.resize_many_back_instances(x, sel, shapes, regions=regions,
+                                                                                                                      mask_format="bits")}
+            run = _run_contestants(args, torch, timed, contestants)
+            results = next(run)
+            note = "a contestant does not fit"
+            if results[a_key] is not None and results[c_key] is not None:
+                areas = torch.stack([r[1] for r in results[a_key]])
+                differ, distinct = int((areas != results[c_key][1][:, :, 0]).sum()), sum(int(s.unique().numel()) for s in sel)
+                note = (f"the areas of (a) and (c) differ at {differ} of {n * m} slots; {distinct} distinct queries of {n * m} slots; "
+                        f"{100.0 * float(areas.sum()) / (m * pixels):.2f} % of the masks' pixels set")
+            del results
+            print(f"\nQ = {q}, M = {m}, {str(dtype).replace('torch.', '')} masks: {note}")
+            stat = next(run)
+            for mine in ("c", "d"):
+                for other, what in (("a", "the loop"), ("b", "two calls, gather and sums")):
+                    _against(stat, mine, other, f"({mine}) against {what}")
+            del x, sel
+            torch.cuda.empty_cache()
+
+
 def fast_hist(torch, t, p, k):
     """The classic evaluation step in torch: the K x K counts of (target, prediction) over the pixels whose target is a class."""
     keep = (t >= 0) & (t < k)
@@ -1563,6 +1632,8 @@ def main():
                     "geometry, Q = 100, C = 19 and 150, against the per-item loops and against resize_many_back + einsum")
     ap.add_argument("--panoptic", action="store_true", help="only resize_many_back_panoptic: panoptic inference on --queries' geometry, 10 and "
                     "100 kept queries of 100, against the per-item torch loop and against resize_many_back plus the torch steps")
+    ap.add_argument("--instances", action="store_true", help="only resize_many_back_instances: instance inference on --panoptic's geometry, 100 "
+                    "and 20 instances an item, against the per-item torch loop and against two resize_many_back calls plus torch reductions")
     ap.add_argument("--quick", action="store_true", help="with --confusion: K = 19 and bfloat16 only (the sweep of the kernel's tunables)")
     ap.add_argument("--noise-targets", action="store_true", help="with --confusion: targets uniform per pixel, the counting's worst case, "
                     "instead of 64 x 64 blocks of one class")
@@ -1678,6 +1749,9 @@ def main():
         return
     if args.panoptic:
         panoptic(args, torch, aa, timed)
+        return
+    if args.instances:
+        instances(args, torch, aa, timed)
         return
     if args.logits:
         (logits_activation if args.activation else logits)(args, torch, aa, timed)
