@@ -38,7 +38,8 @@ extern "C" {
                                    aa_back_queries_plan, aa_resample_back_queries, with aa_back_weights;
                                    aa_back_panoptic_desc_bytes, aa_back_panoptic_plan, aa_resample_back_panoptic, with
                                    aa_back_panoptic_io; aa_back_instances_desc_bytes, aa_back_instances_plan,
-                                   aa_resample_back_instances, with aa_back_instances_io */
+                                   aa_resample_back_instances, with aa_back_instances_io; aa_back_instances_rle_desc_bytes,
+                                   aa_back_instances_rle_plan, aa_launch_back_instances_rle */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -891,6 +892,33 @@ int aa_back_instances_plan(int filter, int layout, int64_t n, int64_t Q, int64_t
                            int64_t *stats_offset);
 int aa_resample_back_instances(const void *desc_host, const void *desc_dev, int in_dtype, const aa_back_instances_io *io, void *arena_dev,
                                size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back, instance inference with COCO's run-length encoding as the mask output -------------------------------------
+ * The section above with another mask output.  Items, Q, M, the queries (aa_back_instances_io) and stats are aa_back_instances_plan's,
+ * stats bit for bit.  With B = mask[m] of that section, [oh_i, ow_i], and v = B read column by column, y fastest (COCO's Fortran order),
+ * counts is COCO's uncompressed RLE of v: counts[0] the leading zeros (0 where v[0] is set), then the lengths of the runs of ones and
+ * zeros in turn, summing to oh_i ow_i; a run that reaches the bottom of column x goes on at the top of column x + 1; an all-zero mask
+ * (and an empty slot) is [oh_i ow_i], an all-one mask [0, oh_i ow_i].
+ *   nruns[i, m]   = len(counts), int32, always the true length
+ *   runs[i, m, r] = counts[r] for r < min(nruns[i, m], max_runs), int32, and 0 behind them: nruns[i, m] > max_runs tells the overflow
+ * The arena holds runs [n, M, max_runs] at byte 0, nruns [n, M] at *nruns_offset and stats [n, M, 6] at *stats_offset, multiples of 16;
+ * every element of the three is written and the bytes between are not.  Everything is integers: the same bits on every run.
+ * aa_back_instances_rle_plan is host arithmetic only.  desc_bytes >= aa_back_instances_rle_desc_bytes(n); the workspace is
+ * aa_back_instances_plan's and after it, per item, min(Q, M) bit planes [oh_i][ceil(ow_i / 64)] of 8-byte words, one per distinct
+ * asked query.  Errors in aa_back_instances_plan's order: max_runs outside 1 .. 2^20 in the place of bits; per item after its own
+ * checks AA_ERR_BAD_SHAPE for ow_i > 4096 (the encode's scan keeps two int32 per column in LDS; no spill is built) or oh_i ow_i >=
+ * 2^31 - 1, then for planes beyond 2^43 bytes, more work units than one grid holds, n M beyond one grid or n M max_runs beyond 2^40.
+ * aa_launch_back_instances_rle enqueues THREE launches whatever n, Q, M and the sizes: the table kernel of aa_resample_back_instances;
+ * its resample, storing the ballot word of (distinct query, row, 64 columns) as one 8-byte word of the query's plane instead of per
+ * slot; and the encode, one workgroup per (item, slot place), which turns a distinct query's plane into run lengths in two passes
+ * around a scan over the columns and stores them for every slot that asked.  Parameters and checks as aa_resample_back_instances',
+ * in their order.  Nothing is allocated, synchronised or read back.  n == 0 launches nothing.  Not built: COCO's compressed string
+ * form, polygons, groups (the merged form), a backward.  Added without an ABI version change (additive). */
+size_t aa_back_instances_rle_desc_bytes(int64_t n);
+int aa_back_instances_rle_plan(int filter, int layout, int64_t n, int64_t Q, int64_t M, const aa_back_item *items, int64_t max_runs, void *desc_host,
+                               size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *nruns_offset, int64_t *stats_offset);
+int aa_launch_back_instances_rle(const void *desc_host, const void *desc_dev, int in_dtype, const aa_back_instances_io *io, void *arena_dev,
+                                 size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged predictions back, backward: N gradients [K, oh_i, ow_i] to N canvases [K, H_i, W_i] ---------------------------------------
  * The backward of aa_resample_back_many's reduce 0, for losses taken at every image's own size.  Item i has a canvas [H_i, W_i], the

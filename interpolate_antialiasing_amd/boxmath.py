@@ -384,3 +384,20 @@ def instance_scores(stats):
     tensor [N, M] — the mean of the sigmoid over the mask's pixels, 0 for an empty mask or slot.  psum is exact, so the score is the
     same bits on every run.  (Works on the tensor's own methods: this module does not import torch.)"""
     return stats[..., 1].double() / float(1 << 24) / (stats[..., 0].double() + 1e-6)
+
+
+def coco_rles(runs, nruns, sizes):
+    """``resize_many_back_instances_rle``'s runs [N, M, max_runs] and nruns [N, M] with the call's sizes -> N lists of M dicts
+    ``{"size": [oh_i, ow_i], "counts": [...]}``, COCO's uncompressed RLE as ``pycocotools.mask.frPyObjects`` takes it.  Copies both
+    tensors to the host.  A slot whose nruns exceeds max_runs holds only its first max_runs counts: ``ValueError`` naming it — call
+    again with a larger ``max_runs``, or take that image's masks from ``resize_many_back_instances(mask_format="bits")``."""
+    rows, lens = runs.tolist(), nruns.tolist()
+    if len(sizes) != len(rows):
+        raise ValueError(f"coco_rles(): {len(sizes)} sizes for runs of {len(rows)} items")
+    out = []
+    for i, (oh, ow) in enumerate(sizes):
+        for m, k in enumerate(lens[i]):
+            if k > len(rows[i][m]):
+                raise ValueError(f"coco_rles(): item {i} slot {m} has {k} runs, max_runs = {len(rows[i][m])} holds only the first of them")
+        out.append([{"size": [int(oh), int(ow)], "counts": rows[i][m][:k]} for m, k in enumerate(lens[i])])
+    return out

@@ -14,6 +14,7 @@
 #include "aa_many_back_queries.h"
 #include "aa_many_back_panoptic.h"
 #include "aa_many_back_instances.h"
+#include "aa_many_back_instances_rle.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_maps.h"
@@ -727,6 +728,21 @@ int aa_resample_back_instances(const void *desc_host, const void *desc_dev, int 
                                size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_back_instances(desc_host, desc_dev, in_dtype, io, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- ragged predictions back, instance inference with COCO's run-length encoding as the mask output -------------------------------------
+size_t aa_back_instances_rle_desc_bytes(int64_t n) { return aa_back_instances_rle_desc_size(n); }
+
+int aa_back_instances_rle_plan(int filter, int layout, int64_t n, int64_t Q, int64_t M, const aa_back_item *items, int64_t max_runs, void *desc_host,
+                               size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *nruns_offset, int64_t *stats_offset) {
+  return aa_back_instances_rle_plan_host(filter, layout, n, Q, M, items, max_runs, desc_host, desc_bytes, workspace_bytes, arena_bytes, nruns_offset,
+                                         stats_offset);
+}
+
+int aa_launch_back_instances_rle(const void *desc_host, const void *desc_dev, int in_dtype, const aa_back_instances_io *io, void *arena_dev,
+                                 size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_back_instances_rle_launch(desc_host, desc_dev, in_dtype, io, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- ragged predictions back, backward -----------------------------------------------------------------------------------------------------

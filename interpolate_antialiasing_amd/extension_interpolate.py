@@ -55,7 +55,8 @@ Differences, all additive:
     [Q, C] class weights on the matrix unit and the argmax over C, in the same two launches; ``resize_many_back_panoptic(masks, scores,
     sizes, ...)`` is their panoptic inference: the winner among the kept queries, per-query areas and the overlap test, in three;
     ``resize_many_back_instances(masks, queries, sizes, ...)`` is their instance inference: the asked masks thresholded and stored per
-    instance as bool or packed bits, with areas, exact mask-score sums and boxes, in two;
+    instance as bool or packed bits, with areas, exact mask-score sums and boxes, in two; ``resize_many_back_instances_rle(masks,
+    queries, sizes, ..., max_runs=...)`` gives the same instances as COCO's uncompressed run lengths, encoded on the device, in three;
   * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -76,7 +77,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "resize_many_back_panoptic", "resize_many_back_instances", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "resize_many_back_panoptic", "resize_many_back_instances", "resize_many_back_instances_rle", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -2212,14 +2213,41 @@ def resize_many_back_instances(masks, queries, sizes, mode: str = "bilinear", *,
     (distinct query, row, wave), stores it for every slot that asked, skips sigmoid and counting where it is 0 and adds the rest with
     64-bit integer atomics — no workspace beyond the tables and the work lists, nothing read back, no synchronisation.  Not
     differentiable: with gradients enabled and a ``masks`` that requires grad the call raises ``NotImplementedError`` — call it under
-    ``torch.no_grad()`` or pass ``.detach()``.  Not built: the top-k itself, run-length encoding, ``groups=`` (merged test-time
-    passes)."""
+    ``torch.no_grad()`` or pass ``.detach()``.  Not built: the top-k itself, ``groups=`` (merged test-time passes); run-length
+    encoding is ``resize_many_back_instances_rle``."""
     name = "resize_many_back_instances"
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
     if mask_format not in ("bool", "bits"):
         raise ValueError(f"{name}(): mask_format must be 'bool' or 'bits', got {mask_format!r}")
     bits = mask_format == "bits"
+    n, q, m, sizes, call = _back_instances_inputs(name, masks, queries, sizes, regions, flips)
+    if n == 0:
+        return [], torch.zeros((0, m, 6), dtype=torch.int64, device=queries.device)
+    items, recs, keep, io, layout, dev = call
+    L = _lib.load()
+    arena_bytes, offs, stats_off = ctypes.c_size_t(0), (ctypes.c_int64 * n)(), ctypes.c_int64(0)
+
+    def planner(desc, nbytes, ws_bytes):
+        return L.aa_back_instances_plan(_lib.FILTER_IDS[mode], layout, n, q, m, recs, int(bits), desc, nbytes, ws_bytes, ctypes.byref(arena_bytes),
+                                        offs, ctypes.byref(stats_off))
+    # (the arena is int64 words, the stats' alignment; the masks are views of its bytes)
+    arena = _many_run(
+        name, dev, L.aa_back_instances_desc_bytes(n), planner, lambda: torch.empty(((arena_bytes.value + 7) // 8,), dtype=torch.int64, device=dev),
+        lambda desc_host, desc_dev, out, wsp, stream: L.aa_resample_back_instances(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], ctypes.byref(io),
+                                                                                   out.data_ptr(), out.numel() * 8, wsp.data_ptr(), wsp.numel(), stream))[0]
+    del keep
+    raw = arena.view(torch.uint8)
+    outs = _back_views(raw, offs, [(oh, (ow + 7) // 8 if bits else ow) for oh, ow in sizes], None, m)
+    if not bits:
+        outs = [o.view(torch.bool) for o in outs]
+    return outs, arena[stats_off.value // 8:stats_off.value // 8 + n * m * 6].view(n, m, 6)
+
+
+def _back_instances_inputs(name: str, masks, queries, sizes, regions, flips):
+    """What the instance calls check of masks, queries, sizes, regions and flips, in their order -> (N, Q, M, sizes, None) for N == 0,
+    else (N, Q, M, sizes, (the detached items, their records, what the records keep alive, the queries' aa_back_instances_io, the
+    layout, the device))."""
     if not isinstance(queries, torch.Tensor):
         raise TypeError(f"{name}(): queries must be Tensor")
     if queries.dtype not in (torch.int32, torch.int64):
@@ -2243,7 +2271,7 @@ def resize_many_back_instances(masks, queries, sizes, mode: str = "bilinear", *,
     if needs_grad:
         raise NotImplementedError(f"{name}() is not differentiable: with masks that require grad, call it under torch.no_grad() or pass .detach()")
     if n == 0:
-        return [], torch.zeros((0, m, 6), dtype=torch.int64, device=queries.device)
+        return n, q, m, sizes, None
     for t in items:
         _require_gpu(t, name)
     items = [t.detach() for t in items]
@@ -2251,24 +2279,59 @@ def resize_many_back_instances(masks, queries, sizes, mode: str = "bilinear", *,
     io = _lib.BackInstancesIO()
     io.queries_dev, io.queries_elem_bytes = queries.data_ptr(), queries.element_size()
     io.queries_stride_n, io.queries_stride_m = queries.stride(0) if n > 1 else 0, queries.stride(1) if m > 1 else 0
-    layout = _lib.NHWC if interleaved else _lib.NCHW
+    return n, q, m, sizes, (items, recs, keep, io, _lib.NHWC if interleaved else _lib.NCHW, dev)
+
+
+def resize_many_back_instances_rle(masks, queries, sizes, mode: str = "bilinear", *, regions=None, flips=None, max_runs):
+    """``resize_many_back_instances`` with COCO's uncompressed run-length encoding as its mask output, for COCO and Cityscapes instance
+    evaluation: the masks never exist as bytes, on the device or the host.  ``masks``, ``queries``, ``sizes``, ``mode``, ``regions`` and
+    ``flips`` are that call's, with its checks and refusals (1 <= Q, M <= 256; int32 or int64 queries of any non-negative strides, never
+    read back; an entry outside 0 .. Q - 1 is an empty slot; not differentiable).  Nothing below has a tolerance.
+
+    Slot m's mask ``B`` [oh_i, ow_i] is the one ``mask_format="bool"`` gives (``R[q] > 0``, a NaN false, an empty slot all zeros), and
+    ``counts`` is COCO's uncompressed RLE of ``v = B.T.ravel()`` — column by column, y fastest, what
+    ``pycocotools.mask.encode(np.asfortranarray(B))`` walks: ``counts[0]`` the leading zeros (0 when ``v[0]`` is set), then the lengths
+    of the runs of ones and zeros in turn, summing to ``oh_i * ow_i``; a run that reaches the bottom of column x goes on at the top of
+    column x + 1; an all-zero mask is ``[oh_i * ow_i]``, an all-one mask ``[0, oh_i * ow_i]``.
+
+    Returns ``(runs, nruns, stats)``, three views of ONE arena: ``nruns`` int32 [N, M] is ``len(counts)``, always the true length;
+    ``runs`` int32 [N, M, max_runs] holds ``counts[r]`` for ``r < min(nruns, max_runs)`` and 0 behind them, so a slot with ``nruns >
+    max_runs`` holds the first ``max_runs`` counts — compare ``nruns`` with ``max_runs``; ``stats`` int64 [N, M, 6] is
+    ``resize_many_back_instances``' bit for bit (``boxmath.instance_scores`` applies).  Slots that ask for the same query get the same
+    row.  ``boxmath.coco_rles(runs, nruns, sizes)`` gives the dicts ``pycocotools.mask.frPyObjects`` takes.
+
+    ``max_runs``: required, an int in 1 .. 2^20.  ``ow_i`` <= 4096 (the encode's scan keeps two int32 per column in LDS; no spill is
+    built) and ``oh_i * ow_i`` < 2^31 - 1, else the planner refuses the call.  Three launches whatever N, Q, M and the sizes: the
+    table kernel of the instance call; its resample, which stores the ballot word of (distinct query, row, 64 columns) as one 8-byte
+    word of a bit plane [oh_i][ceil(ow_i / 64)] in the workspace (min(Q, M) planes per item); and an encode, one workgroup per (item,
+    slot place), two passes over a distinct query's plane around a scan over its columns, every asking slot's row written in the
+    second.  Nothing is read back or synchronised.  Not built: ``groups=``, COCO's compressed string form, polygons."""
+    name = "resize_many_back_instances_rle"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    if isinstance(max_runs, bool) or not isinstance(max_runs, int) or not (1 <= max_runs <= _lib.BACK_INSTANCES_RLE_MAX_RUNS):
+        raise ValueError(f"{name}(): max_runs must be an int in 1 .. {_lib.BACK_INSTANCES_RLE_MAX_RUNS}, got {max_runs!r}")
+    n, q, m, sizes, call = _back_instances_inputs(name, masks, queries, sizes, regions, flips)
+    if n == 0:
+        z = lambda *shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=queries.device)
+        return z(0, m, max_runs), z(0, m), z(0, m, 6, dtype=torch.int64)
+    items, recs, keep, io, layout, dev = call
     L = _lib.load()
-    arena_bytes, offs, stats_off = ctypes.c_size_t(0), (ctypes.c_int64 * n)(), ctypes.c_int64(0)
+    arena_bytes, nruns_off, stats_off = ctypes.c_size_t(0), ctypes.c_int64(0), ctypes.c_int64(0)
 
     def planner(desc, nbytes, ws_bytes):
-        return L.aa_back_instances_plan(_lib.FILTER_IDS[mode], layout, n, q, m, recs, int(bits), desc, nbytes, ws_bytes, ctypes.byref(arena_bytes),
-                                        offs, ctypes.byref(stats_off))
-    # (the arena is int64 words, the stats' alignment; the masks are views of its bytes)
+        return L.aa_back_instances_rle_plan(_lib.FILTER_IDS[mode], layout, n, q, m, recs, max_runs, desc, nbytes, ws_bytes, ctypes.byref(arena_bytes),
+                                            ctypes.byref(nruns_off), ctypes.byref(stats_off))
+    # (the arena is int64 words, the stats' alignment; runs and nruns are views of its int32 halves)
     arena = _many_run(
-        name, dev, L.aa_back_instances_desc_bytes(n), planner, lambda: torch.empty(((arena_bytes.value + 7) // 8,), dtype=torch.int64, device=dev),
-        lambda desc_host, desc_dev, out, wsp, stream: L.aa_resample_back_instances(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], ctypes.byref(io),
-                                                                                   out.data_ptr(), out.numel() * 8, wsp.data_ptr(), wsp.numel(), stream))[0]
+        name, dev, L.aa_back_instances_rle_desc_bytes(n), planner, lambda: torch.empty(((arena_bytes.value + 7) // 8,), dtype=torch.int64, device=dev),
+        lambda desc_host, desc_dev, out, wsp, stream: L.aa_launch_back_instances_rle(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], ctypes.byref(io),
+                                                                                     out.data_ptr(), out.numel() * 8, wsp.data_ptr(), wsp.numel(), stream))[0]
     del keep
-    raw = arena.view(torch.uint8)
-    outs = _back_views(raw, offs, [(oh, (ow + 7) // 8 if bits else ow) for oh, ow in sizes], None, m)
-    if not bits:
-        outs = [o.view(torch.bool) for o in outs]
-    return outs, arena[stats_off.value // 8:stats_off.value // 8 + n * m * 6].view(n, m, 6)
+    words = arena.view(torch.int32)
+    runs = words[:n * m * max_runs].view(n, m, max_runs)
+    nruns = words[nruns_off.value // 4:nruns_off.value // 4 + n * m].view(n, m)
+    return runs, nruns, arena[stats_off.value // 8:stats_off.value // 8 + n * m * 6].view(n, m, 6)
 
 
 def _back_canvas(name: str, canvas, n: int, k: int):

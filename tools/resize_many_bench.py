@@ -149,6 +149,8 @@ the same bits.  The kernel's fetched bytes come from a counter run of its own: t
                                                          # kept (at panoptic()); profiles/resize_many_back_panoptic.txt
   python tools/resize_many_bench.py --instances --rounds 5 --batches 3 > out.txt # only resize_many_back_instances: Q = 100 masks, M = 100
                                                          # and 20 (at instances()); profiles/resize_many_back_instances.txt
+  python tools/resize_many_bench.py --instances-rle --rounds 5 --batches 3 > out.txt # only resize_many_back_instances_rle on the same
+                                                         # masks (at instances_rle()); profiles/resize_many_back_instances_rle.txt
   python tools/resize_many_bench.py --queries --rounds 5 --batches 3 > out.txt   # only resize_many_back_queries: Q = 100 masks, sigmoid,
                                                          # class weights, argmax (at queries()); profiles/resize_many_back_queries.txt
   python tools/resize_many_bench.py --logits-backward > out.txt   # only the gradients' way back to the canvas (above);
@@ -1428,6 +1430,71 @@ def instances(args, torch, aa, timed):
             torch.cuda.empty_cache()
 
 
+def instances_rle(args, torch, aa, timed):
+    """--instances-rle: resize_many_back_instances_rle on --instances' geometry and masks.  (a) the run-length call, max_runs the power
+    of two at or above the largest nruns of the configuration; (b), (c) resize_many_back_instances with bool masks and with packed bits
+    alone; (d), (e) the same calls plus the copy of their masks to pinned host memory, the least any host encoder pays before it
+    encodes (the host encode itself is not timed: pycocotools is not a dependency).  The distribution of nruns is printed first."""
+    from interpolate_antialiasing_amd import boxmath
+
+    n, canvas, q, classes = 16, (512, 512), 100, 80
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    regions = boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=canvas[0]), "center", canvas)
+    pixels = sum(h * w for h, w in shapes)
+    print(f"resize_many_bench --instances-rle: --instances' geometry and masks: [N, Q = {q}, {canvas[0]}, {canvas[1]}] mask logits back to N = {n} "
+          f"camera-sized images (seed {SEED}), {pixels / 1e6:.1f} M output pixels; bilinear; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for m in (100, 20):
+        for dtype in (torch.float32, torch.bfloat16):
+            x = (torch.nn.functional.interpolate(4.0 * torch.randn((n, q, 16, 16), device="cuda", generator=gen), size=canvas, mode="bicubic") - 6.0).to(dtype)
+            sel = torch.rand((n, q * classes), device="cuda", generator=gen).topk(m, dim=1).indices // classes
+            _, nruns, stats = aa.resize_many_back_instances_rle(x, sel, shapes, regions=regions, max_runs=1)
+            k = nruns.flatten().sort().values.cpu()
+            max_runs = 1 << max(int(k[-1]) - 1, 1).bit_length()
+            pick = lambda f: int(k[min(int(f * k.numel()), k.numel() - 1)])
+            byte_sizes = {"bool": m * pixels, "bits": m * sum(h * ((w + 7) // 8) for h, w in shapes)}
+            pinned = {}
+            try:
+                pinned = {fmt: torch.empty(size, dtype=torch.uint8, pin_memory=True) for fmt, size in byte_sizes.items()}
+            except RuntimeError as e:
+                print(f"  (pinned host memory for the masks could not be allocated: (d), (e) are not timed: {str(e).splitlines()[0]})")
+
+            def with_copy(fmt):
+                masks, st = aa.resize_many_back_instances(x, sel, shapes, regions=regions, mask_format=fmt)
+                at = 0
+                for t in masks:  # (one arena, but its items start on 16-byte boundaries: item by item)
+                    pinned[fmt][at:at + t.numel()].copy_(t.flatten().view(torch.uint8), non_blocking=True)
+                    at += t.numel()
+                return st
+
+            contestants = {f"a: resize_many_back_instances_rle(max_runs={max_runs})": lambda: aa.resize_many_back_instances_rle(
+                               x, sel, shapes, regions=regions, max_runs=max_runs),
+                           "b: resize_many_back_instances(mask_format='bool') alone": lambda: aa.resize_many_back_instances(x, sel, shapes, regions=regions),
+                           "c: resize_many_back_instances(mask_format='bits') alone": lambda: aa.resize_many_back_instances(
+                               x, sel, shapes, regions=regions, mask_format="bits")}
+            if pinned:
+                contestants["d: (b) and its masks copied to pinned host memory"] = lambda: with_copy("bool")
+                contestants["e: (c) and its masks copied to pinned host memory"] = lambda: with_copy("bits")
+            print(f"\nQ = {q}, M = {m}, {str(dtype).replace('torch.', '')} masks: {100.0 * float(stats[:, :, 0].sum()) / (m * pixels):.2f} % of the masks' "
+                  f"pixels set; nruns over the {k.numel()} slots: min {int(k[0])}, median {pick(0.5)}, 90 % {pick(0.9)}, 99 % {pick(0.99)}, max {int(k[-1])}, "
+                  f"sum {int(k.sum())}")
+            print(f"  bytes that leave the device: (a) runs + nruns + stats {n * m * (4 * max_runs + 4 + 48)} B, of which {4 * int(k.sum())} B are counts; "
+                  f"(d) {byte_sizes['bool']} B + stats; (e) {byte_sizes['bits']} B + stats")
+            del stats, nruns
+            run = _run_contestants(args, torch, timed, contestants)
+            results = next(run)
+            del results
+            stat = next(run)
+            for other, what in (("b", "bool masks alone"), ("c", "packed bits alone"), ("d", "bool masks and their copy to the host"),
+                                ("e", "packed bits and their copy to the host")):
+                _against(stat, "a", other, what)
+            del x, sel, pinned
+            torch.cuda.empty_cache()
+
+
 def fast_hist(torch, t, p, k):
     """The classic evaluation step in torch: the K x K counts of (target, prediction) over the pixels whose target is a class."""
     keep = (t >= 0) & (t < k)
@@ -1634,6 +1701,8 @@ def main():
                     "100 kept queries of 100, against the per-item torch loop and against resize_many_back plus the torch steps")
     ap.add_argument("--instances", action="store_true", help="only resize_many_back_instances: instance inference on --panoptic's geometry, 100 "
                     "and 20 instances an item, against the per-item torch loop and against two resize_many_back calls plus torch reductions")
+    ap.add_argument("--instances-rle", action="store_true", help="only resize_many_back_instances_rle on --instances' geometry: against "
+                    "resize_many_back_instances alone and with its masks copied to pinned host memory; the distribution of nruns")
     ap.add_argument("--quick", action="store_true", help="with --confusion: K = 19 and bfloat16 only (the sweep of the kernel's tunables)")
     ap.add_argument("--noise-targets", action="store_true", help="with --confusion: targets uniform per pixel, the counting's worst case, "
                     "instead of 64 x 64 blocks of one class")
@@ -1752,6 +1821,9 @@ def main():
         return
     if args.instances:
         instances(args, torch, aa, timed)
+        return
+    if args.instances_rle:
+        instances_rle(args, torch, aa, timed)
         return
     if args.logits:
         (logits_activation if args.activation else logits)(args, torch, aa, timed)
