@@ -39,7 +39,8 @@ extern "C" {
                                    aa_back_panoptic_desc_bytes, aa_back_panoptic_plan, aa_resample_back_panoptic, with
                                    aa_back_panoptic_io; aa_back_instances_desc_bytes, aa_back_instances_plan,
                                    aa_resample_back_instances, with aa_back_instances_io; aa_back_instances_rle_desc_bytes,
-                                   aa_back_instances_rle_plan, aa_launch_back_instances_rle */
+                                   aa_back_instances_rle_plan, aa_launch_back_instances_rle; aa_back_peaks_desc_bytes,
+                                   aa_back_peaks_plan, aa_resample_back_peaks */
 
 typedef void *aa_stream_t; /* hipStream_t */
 
@@ -919,6 +920,37 @@ int aa_back_instances_rle_plan(int filter, int layout, int64_t n, int64_t Q, int
                                size_t desc_bytes, size_t *workspace_bytes, size_t *arena_bytes, int64_t *nruns_offset, int64_t *stats_offset);
 int aa_launch_back_instances_rle(const void *desc_host, const void *desc_dev, int in_dtype, const aa_back_instances_io *io, void *arena_dev,
                                  size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ragged predictions back, reduced over space: per channel the peak of its heatmap and the five values around it ---------------------
+ * Keypoint and landmark heads: item i is an aa_back_item of K heatmaps, 1 <= K <= 2^29 - 1.  With R_i [K, oh_i, ow_i] the fp32 value
+ * aa_back_many_plan's section defines for item i (bit for bit; for AA_MANY_FLIP_X mirrored left to right, so everything below is in the
+ * output's own, un-mirrored coordinates):
+ *   peaks[i, k]  = (x, y), int32: the lowest flat index y * ow_i + x at which R_i[k] is greatest, a NaN greater than every number and
+ *                  the first NaN kept, -0.0 and +0.0 equal (numpy.argmax of the flattened channel)
+ *   values[i, k] = R_i[k] at (x, y), (x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1), float32, the bits of R_i (the sign of a zero and
+ *                  a NaN as aa_resample_back_many stores them); a neighbour outside the image is the peak's own value
+ * The arena holds peaks [n, K, 2] at byte 0 and values [n, K, 5] at *values_offset, a multiple of 16; every element of both is
+ * written and the bytes between are not.  The resampled values never reach memory.  The reduction is the maximum of 64-bit keys
+ * (ord(value) << 32 | 0xFFFFFFFF - flat index) over a total order, which is associative and commutative: the same bits on every run
+ * and for every launch shape.
+ * aa_back_peaks_plan is host arithmetic only.  desc_bytes >= aa_back_peaks_desc_bytes(n); the workspace is aa_back_many_plan's for the
+ * same items and after it, on a multiple of 16, n K keys of 8 bytes.  Errors in aa_back_many_plan's order: AA_ERR_BAD_SHAPE beside n
+ * and K for n K beyond 2^31 - 1 (one grid of the decode); the pointers (AA_ERR_NULL); the block's size (AA_ERR_WORKSPACE); per item its
+ * own checks (K oh_i ow_i <= 2^40 among them), then AA_ERR_BAD_SHAPE for oh_i ow_i > 2^31 - 1 (a flat index is 32 bits of the key) or
+ * more work units than one grid holds.
+ * aa_resample_back_peaks enqueues THREE launches whatever n, K and the sizes: the table kernel, whose further workgroups set the keys
+ * to 0 (no memset); the resample, one workgroup per 16 output rows times 256 columns, which walks the classes four at a time, keeps a
+ * lane's greatest key per class in registers and combines the keys across the wave (DPP), the workgroup (LDS) and the grid (one 64-bit
+ * atomic maximum per work unit and class); and a decode, one lane per (item, channel), which resamples R again at the five places.
+ * Parameters and checks as aa_resample_back_many's, in their order; the arena on a 4-byte boundary.  Nothing is allocated, synchronised
+ * or read back, and no table cache is touched.  n == 0 launches nothing.  Not built: groups (the merged form), an activation, the
+ * top-k peaks of a channel or a non-maximum suppression, a backward; the swap of left and right channel pairs after a flipped pass is
+ * the caller's.  Added without an ABI version change (additive). */
+size_t aa_back_peaks_desc_bytes(int64_t n);
+int aa_back_peaks_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, void *desc_host, size_t desc_bytes,
+                       size_t *workspace_bytes, size_t *arena_bytes, int64_t *values_offset);
+int aa_resample_back_peaks(const void *desc_host, const void *desc_dev, int in_dtype, void *arena_dev, size_t arena_bytes, void *workspace_dev,
+                           size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged predictions back, backward: N gradients [K, oh_i, ow_i] to N canvases [K, H_i, W_i] ---------------------------------------
  * The backward of aa_resample_back_many's reduce 0, for losses taken at every image's own size.  Item i has a canvas [H_i, W_i], the

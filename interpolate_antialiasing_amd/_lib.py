@@ -70,6 +70,7 @@ EXPORTS = (
     "aa_back_panoptic_desc_bytes", "aa_back_panoptic_plan", "aa_resample_back_panoptic",
     "aa_back_instances_desc_bytes", "aa_back_instances_plan", "aa_resample_back_instances",
     "aa_back_instances_rle_desc_bytes", "aa_back_instances_rle_plan", "aa_launch_back_instances_rle",
+    "aa_back_peaks_desc_bytes", "aa_back_peaks_plan", "aa_resample_back_peaks",
 )
 
 
@@ -341,6 +342,15 @@ class BackInstancesRleHeader(ctypes.Structure):
                 ("planes_off", ctypes.c_int64), ("nruns_off", ctypes.c_int64), ("stats_off", ctypes.c_int64), ("max_ow", ctypes.c_int64)]
 
 
+class BackPeaksHeader(ctypes.Structure):
+    """Head of the block aa_back_peaks_plan writes (csrc/aa_many_back_peaks.h AABackPeaksHeader; opaque to C callers, mirrored for the
+    tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("K", ctypes.c_int32), ("filter", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("rows", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("reserved1", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("tables_bytes", ctypes.c_int64), ("keys_off", ctypes.c_int64),
+                ("values_off", ctypes.c_int64)]
+
+
 class BackBwdItemIn(ctypes.Structure):
     """aa_back_bwd_item: one item of the ragged return path's backward (strides in ELEMENTS; grad_dev None: the item has no gradient)."""
     _fields_ = [("grad_dev", ctypes.c_void_p), ("stride_ch", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("H", ctypes.c_int64),
@@ -407,6 +417,7 @@ BACK_INSTANCES_ROWS = 8  # output rows per work unit of the instance call's resa
 BACK_INSTANCES_MAX_M = 256  # the most slots of an item of the instance call (csrc/aa_many_back_instances.h AA_BACK_INSTANCES_MAX_M)
 BACK_INSTANCES_RLE_MAX_RUNS = 1 << 20  # the most runs a slot's row of the run-length call holds (csrc/aa_many_back_instances_rle.h)
 BACK_INSTANCES_RLE_MAX_OW = 4096  # the widest item of the run-length call: its scan's LDS (csrc/aa_many_back_instances_rle.h)
+BACK_PEAKS_ROWS = 16  # output rows per work unit of the peak call's resample (csrc/aa_many_back_peaks.h AA_BACK_PEAKS_ROWS)
 BACK_QUERIES_MAX = 256  # the most queries of the mask-classification call (csrc/aa_many_back_queries.h AA_BACK_QUERIES_MAX_Q)
 BACK_BWD_ROWS, BACK_BWD_COLS = 4, 64  # canvas rows and columns per work unit of the return path's backward (csrc/aa_many_back_bwd.h)
 MANY_STRIP = 64     # output columns per work unit of the ragged call's horizontal pass (csrc/aa_many.h AA_MANY_STRIP)
@@ -695,6 +706,12 @@ def load() -> ctypes.CDLL:
     L.aa_back_instances_rle_plan.restype = i32
     L.aa_launch_back_instances_rle.argtypes = [vp, vp, i32, ctypes.POINTER(BackInstancesIO), vp, sz, vp, sz, vp]
     L.aa_launch_back_instances_rle.restype = i32
+    L.aa_back_peaks_desc_bytes.argtypes = [i64]
+    L.aa_back_peaks_desc_bytes.restype = sz
+    L.aa_back_peaks_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_back_peaks_plan.restype = i32
+    L.aa_resample_back_peaks.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp]
+    L.aa_resample_back_peaks.restype = i32
     L.aa_back_many_bwd_desc_bytes.argtypes = [i64]
     L.aa_back_many_bwd_desc_bytes.restype = sz
     L.aa_back_many_bwd_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackBwdItemIn), i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),

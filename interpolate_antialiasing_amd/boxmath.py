@@ -401,3 +401,26 @@ def coco_rles(runs, nruns, sizes):
                 raise ValueError(f"coco_rles(): item {i} slot {m} has {k} runs, max_runs = {len(rows[i][m])} holds only the first of them")
         out.append([{"size": [int(oh), int(ow)], "counts": rows[i][m][:k]} for m, k in enumerate(lens[i])])
     return out
+
+
+def peak_points(peaks, values, sizes, boxes=None, refine: Optional[str] = None):
+    """``resize_many_back_peaks``' peaks [N, K, 2] and values [N, K, 5] with the call's sizes -> float32 points [N, K, 2], (x, y), on
+    the tensors' device, in float32 arithmetic and without a read-back.  The base point is the pixel's centre, ``(x + 0.5, y + 0.5)``.
+    ``refine="quarter"`` adds HRNet's shift, ``0.25 * sign(right - left)`` and ``0.25 * sign(down - up)``: 0 where the two are equal,
+    and so at a border, where the missing neighbour is the peak's own value (a NaN difference gives NaN).  ``boxes``: None (the
+    points stay in the item's own pixels) or N boxes ``(x0, y0, x1, y1)``: every coordinate is multiplied by ``(x1 - x0) / ow_i``
+    (``(y1 - y0) / oh_i``) and the box's corner added, ``heatmaps_to_keypoints``' mapping.  (Works on the tensors' own methods: this
+    module does not import torch.)"""
+    if refine not in (None, "quarter"):
+        raise ValueError(f"peak_points(): refine must be None or 'quarter', got {refine!r}")
+    n = int(peaks.shape[0])
+    if len(sizes) != n or (boxes is not None and len(boxes) != n):
+        raise ValueError(f"peak_points(): sizes (and boxes) must hold one entry per item ({n})")
+    pts = peaks.to(values.dtype) + 0.5
+    if refine == "quarter":
+        pts = pts + 0.25 * (values[..., [2, 4]] - values[..., [1, 3]]).sign()
+    if boxes is not None and n > 0:
+        b = values.new_tensor([[float(v) for v in bx] for bx in boxes])
+        wh = values.new_tensor([[float(ow), float(oh)] for oh, ow in sizes])
+        pts = pts * ((b[:, 2:] - b[:, :2]) / wh)[:, None, :] + b[:, None, :2]
+    return pts

@@ -15,6 +15,7 @@
 #include "aa_many_back_panoptic.h"
 #include "aa_many_back_instances.h"
 #include "aa_many_back_instances_rle.h"
+#include "aa_many_back_peaks.h"
 #include "aa_launch_shape.h"
 #include "aa_many.h"
 #include "aa_many_maps.h"
@@ -743,6 +744,20 @@ int aa_launch_back_instances_rle(const void *desc_host, const void *desc_dev, in
                                  size_t arena_bytes, void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_back_instances_rle_launch(desc_host, desc_dev, in_dtype, io, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- ragged predictions back, reduced over space: per channel the peak of its heatmap and the five values around it --------------------------
+size_t aa_back_peaks_desc_bytes(int64_t n) { return aa_back_peaks_desc_size(n); }
+
+int aa_back_peaks_plan(int filter, int layout, int64_t n, int64_t K, const aa_back_item *items, void *desc_host, size_t desc_bytes,
+                       size_t *workspace_bytes, size_t *arena_bytes, int64_t *values_offset) {
+  return aa_back_peaks_plan_host(filter, layout, n, K, items, desc_host, desc_bytes, workspace_bytes, arena_bytes, values_offset);
+}
+
+int aa_resample_back_peaks(const void *desc_host, const void *desc_dev, int in_dtype, void *arena_dev, size_t arena_bytes, void *workspace_dev,
+                           size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_back_peaks(desc_host, desc_dev, in_dtype, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- ragged predictions back, backward -----------------------------------------------------------------------------------------------------

@@ -57,6 +57,8 @@ Differences, all additive:
     ``resize_many_back_instances(masks, queries, sizes, ...)`` is their instance inference: the asked masks thresholded and stored per
     instance as bool or packed bits, with areas, exact mask-score sums and boxes, in two; ``resize_many_back_instances_rle(masks,
     queries, sizes, ..., max_runs=...)`` gives the same instances as COCO's uncompressed run lengths, encoded on the device, in three;
+    ``resize_many_back_peaks(pred, sizes, ...)`` reduces over SPACE, for keypoint and landmark heads: per channel the place of its
+    heatmap's maximum at the item's own size and the five values around it, in three, the resampled heatmaps never stored;
   * ``resize_many(images, output_size, mode, boxes=None, alpha=False)``: a LIST of uint8 images of different sizes, each with its own box, into one
     dense [N, C, oH, oW] batch, bit-exact with the single-image call per item: three launches and one small host-to-device copy
     whatever N, no table cache traffic, no synchronisation.  ``sizes=``, ``offsets=``, ``fill=`` on both calls give every item its own
@@ -77,7 +79,7 @@ import torch
 from . import _lib, boxmath, tables
 
 __all__ = ["reduce", "reduce_many", "reduce_many_for_resize", "resize_many", "resize_many_to_float", "resize_many_to_patches",
-           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "resize_many_back_panoptic", "resize_many_back_instances", "resize_many_back_instances_rle", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
+           "resize_embed_to_tokens", "resize_embed_to_tokens_backward", "resize_many_back", "resize_many_back_backward", "resize_many_back_merged", "resize_many_back_confusion", "resize_many_back_queries", "resize_many_back_panoptic", "resize_many_back_instances", "resize_many_back_instances_rle", "resize_many_back_peaks", "linear_forward", "nearest_forward", "cubic_forward", "linear_backward", "cubic_backward",
            "nearest_backward", "forward", "linear_forward_nd", "cubic_forward_nd", "nearest_forward_nd", "linear_backward_nd",
            "cubic_backward_nd", "lanczos_forward", "hamming_forward", "lanczos_backward", "hamming_backward", "lanczos_forward_nd",
            "hamming_forward_nd", "lanczos_backward_nd", "hamming_backward_nd", "set_uint8_mode",
@@ -2334,6 +2336,78 @@ def resize_many_back_instances_rle(masks, queries, sizes, mode: str = "bilinear"
     return runs, nruns, arena[stats_off.value // 8:stats_off.value // 8 + n * m * 6].view(n, m, 6)
 
 
+def resize_many_back_peaks(pred, sizes, mode: str = "bilinear", *, regions=None, flips=None):
+    """The way back for keypoint and landmark heads (Keypoint R-CNN's ``heatmaps_to_keypoints``, HRNet's and ViTPose's per-crop decode):
+    every item's K heatmaps resampled to the item's own box or image size, and per channel only the place of the maximum and the
+    values around it kept — a reduction over SPACE, where the other calls of the return path reduce over the channels of a pixel.
+    ``pred``, ``sizes``, ``mode``, ``regions`` and ``flips`` are ``resize_many_back``'s, with its checks: one float32 / float16 /
+    bfloat16 GPU tensor [N, K, H, W] or a list of [K, H_i, W_i], planar or channels_last, read where they lie.
+
+    With ``R_i`` [K, oh_i, ow_i] the fp32 values ``resize_many_back(..., reduce=None, out_dtype=torch.float32)`` gives item i, bit for
+    bit and un-mirrored for a flipped item — nothing below has a tolerance — the call returns ``(peaks, values)``:
+
+      * ``peaks`` int32 [N, K, 2]: ``(x, y)`` with ``y, x = divmod(numpy.argmax(R_i[k].ravel()), ow_i)`` — the lowest flat index of the
+        greatest value; a NaN beats every number and the first NaN wins; ``-0.0`` and ``+0.0`` are equal, so the lower index wins;
+      * ``values`` float32 [N, K, 5]: ``R_i[k]`` at the peak and at its left, right, upper and lower neighbour, the bits of ``R_i``
+        (the peak's sign of zero and its NaN included); a neighbour outside the image is the peak's own value, so a difference across
+        the border is 0.  ``boxmath.peak_points(peaks, values, sizes, boxes=, refine=)`` turns both into coordinates.
+
+    Both are views of ONE arena; every element is written; N == 0 gives empty tensors of those shapes.  Three launches whatever N, K
+    and the sizes, no memset, nothing read back, no synchronisation: the table kernel, which also empties N * K 64-bit keys in the
+    workspace; a resample whose lanes walk down 16 rows of 256 columns per chunk of four channels, keep ``ord(value) << 32 |
+    0xFFFFFFFF - flat index`` of their best pixel per channel in registers and combine the keys across the wave (DPP), the workgroup
+    (LDS) and the grid (one 64-bit atomic maximum per tile and channel); and a decode, one lane per (item, channel), that resamples
+    ``R`` again at the five places.  The maximum over a total order is associative and commutative, so the bits are the same on every
+    run.  The ``[K, oh_i, ow_i]`` floats never reach memory.  ``oh_i * ow_i`` <= 2^31 - 1 and ``N * K`` <= 2^31 - 1.
+
+    ``mode="bicubic"`` is this package's cubic (``cubic_forward``: Keys' kernel with a = -0.5, Pillow's BICUBIC, antialiased where an
+    axis shrinks), not ``torch.nn.functional.interpolate(mode="bicubic")``'s (a = -0.75, four taps, never antialiased), which
+    ``heatmaps_to_keypoints`` uses: peaks of the two may differ by a pixel where a heatmap is flat.
+
+    Not differentiable: with gradients enabled and a ``pred`` that requires grad the call raises ``NotImplementedError`` — call it
+    under ``torch.no_grad()`` or pass ``.detach()``.  Not built: ``groups=`` (merged test-time passes), an activation, the top-k peaks
+    of a channel or a non-maximum suppression; after a flipped pass the swap of left and right channel pairs is the caller's."""
+    name = "resize_many_back_peaks"
+    if mode not in _lib.FILTER_IDS:
+        raise ValueError(mode)
+    empty = not isinstance(pred, torch.Tensor) and len(pred) == 0
+    items, dev0, n, k = ([], None, 0, 1) if empty else _back_items(name, pred, None)
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in [pred] + items if isinstance(t, torch.Tensor))
+    sizes = _back_sizes(name, sizes, n, k)
+    for i, (oh, ow) in enumerate(sizes):
+        if oh * ow > 2 ** 31 - 1:
+            raise ValueError(f"{name}(): sizes[{i}] = ({oh}, {ow}) has more than 2^31 - 1 pixels: a flat index is 32 bits of the key")
+    if n * k > 2 ** 31 - 1:
+        raise ValueError(f"{name}(): N * K = {n * k} keys are beyond the supported 2^31 - 1")
+    rects = _back_regions(name, regions, items)
+    flips = _many_flips(name, flips, n)
+    if needs_grad:
+        raise NotImplementedError(f"{name}() is not differentiable: with a pred that requires grad, call it under torch.no_grad() or pass .detach()")
+    if n == 0:
+        dev = _many_empty_device(dev0)
+        return torch.zeros((0, k, 2), dtype=torch.int32, device=dev), torch.zeros((0, k, 5), dtype=torch.float32, device=dev)
+    for t in items:
+        _require_gpu(t, name)
+    dev = items[0].device
+    items = [t.detach() for t in items]
+    recs, keep, interleaved = _back_records(items, rects, sizes, flips, k)  # (keep: alive until the launches are enqueued)
+    layout = _lib.NHWC if interleaved else _lib.NCHW
+    L = _lib.load()
+    arena_bytes, values_off = ctypes.c_size_t(0), ctypes.c_int64(0)
+
+    def planner(desc, nbytes, ws_bytes):
+        return L.aa_back_peaks_plan(_lib.FILTER_IDS[mode], layout, n, k, recs, desc, nbytes, ws_bytes, ctypes.byref(arena_bytes),
+                                    ctypes.byref(values_off))
+    # (the arena is int32 words; the values are a view of its bytes)
+    arena = _many_run(
+        name, dev, L.aa_back_peaks_desc_bytes(n), planner, lambda: torch.empty(((arena_bytes.value + 3) // 4,), dtype=torch.int32, device=dev),
+        lambda desc_host, desc_dev, out, wsp, stream: L.aa_resample_back_peaks(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], out.data_ptr(),
+                                                                               out.numel() * 4, wsp.data_ptr(), wsp.numel(), stream))[0]
+    del keep
+    first = values_off.value // 4
+    return arena[:n * k * 2].view(n, k, 2), arena[first:first + n * k * 5].view(torch.float32).view(n, k, 5)
+
+
 def _back_canvas(name: str, canvas, n: int, k: int):
     """canvas of resize_many_back_backward -> (whether it is ONE (H, W), [(H_i, W_i)] per item), checked."""
     try:
@@ -3217,6 +3291,31 @@ def _register_torch_ops() -> None:
 
     lib.impl("reduce_many", _reduce_many_cuda, "CUDA")
     lib.impl("reduce_many", _reduce_many_meta, "Meta")
+
+    # per channel the peak of its heatmap: sizes flattened to 2 N ints (height first), regions to 4 N ints (y0, x0, h, w), the whole
+    # item standing for None; the Meta shapes follow from N and K alone
+    lib.define('resize_many_back_peaks(Tensor[] pred, int[] sizes, str mode="bilinear", int[]? regions=None, bool[]? flips=None) -> (Tensor, Tensor)')
+
+    def _peaks_args(pred, sizes, regions):
+        n = len(pred)
+        if len(sizes) != 2 * n:
+            raise ValueError(f"resize_many_back_peaks(): sizes must hold 2 values per item ({2 * n}), got {len(sizes)}")
+        if regions is not None and len(regions) != 4 * n:
+            raise ValueError(f"resize_many_back_peaks(): regions must hold 4 values per item ({4 * n}), got {len(regions)}")
+        return ([tuple(sizes[2 * i:2 * i + 2]) for i in range(n)],
+                None if regions is None else [tuple(int(v) for v in regions[4 * i:4 * i + 4]) for i in range(n)])
+
+    def _peaks_meta(pred, sizes, mode="bilinear", regions=None, flips=None):
+        _peaks_args(pred, sizes, regions)
+        n, k = len(pred), (int(pred[0].shape[-3]) if pred else 1)
+        return torch.empty((n, k, 2), dtype=torch.int32, device="meta"), torch.empty((n, k, 5), dtype=torch.float32, device="meta")
+
+    def _peaks_cuda(pred, sizes, mode="bilinear", regions=None, flips=None):
+        pairs, rects = _peaks_args(pred, sizes, regions)
+        return resize_many_back_peaks(list(pred), pairs, mode, regions=rects, flips=flips)
+
+    lib.impl("resize_many_back_peaks", _peaks_cuda, "CUDA")
+    lib.impl("resize_many_back_peaks", _peaks_meta, "Meta")
 
     for name, fn in bwds.items():
         lib.impl(name, (lambda f: lambda grad_output, output_size, input_size, align_corners=False:

@@ -1430,6 +1430,76 @@ def instances(args, torch, aa, timed):
             torch.cuda.empty_cache()
 
 
+def peaks(args, torch, aa, timed):
+    """--peaks: resize_many_back_peaks, K = 17 heatmaps an item, float32 and bfloat16 sources, on two geometries.  (1) Keypoint R-CNN's:
+    one [256, 17, 56, 56] tensor, every item to its own box size with sides in 40 .. 400, bicubic.  (2) --logits' 16 camera-sized
+    images from the 512 x 512 letterbox canvas, bilinear.  (a) is the loop a user writes today: per item <mode>_forward,
+    flatten(1).argmax(1) and the gather of the five values; (b) resize_many_back(reduce=None, out_dtype=float32) and the same torch
+    steps per item; (c) the call.  The peaks of (a) and (c) are compared and the channels that differ reported.  --quick: only (c) (the
+    sweep of AA_BACK_PEAKS_ROWS, one library each)."""
+    from interpolate_antialiasing_amd import boxmath
+
+    k = 17
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:16]
+    canvas = (512, 512)
+    boxes = [(int(rng.integers(40, 401)), int(rng.integers(40, 401))) for _ in range(256)]
+    geometries = (("1: Keypoint R-CNN's: [256, 17, 56, 56] to box sizes with sides in 40 .. 400", "bicubic", aa.cubic_forward, (256, k, 56, 56), boxes, None),
+                  ("2: --logits': [16, 17, 512, 512] on a letterbox canvas to camera-sized images", "bilinear", aa.linear_forward, (16, k) + canvas, shapes,
+                   boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=canvas[0]), "center", canvas)))
+    print(f"resize_many_bench --peaks: K = {k} heatmaps an item to the item's own size, per channel the argmax over space and five values "
+          f"(seed {SEED}); library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+
+    def torch_steps(r):
+        """r [K, oh, ow] float32 -> (peaks [K, 2], values [K, 5]) by torch: what a user writes after the resample."""
+        kk, oh, ow = r.shape
+        idx = r.flatten(1).argmax(1)
+        y, x = idx // ow, idx % ow
+        ch = torch.arange(kk, device=r.device)
+        own = r[ch, y, x]
+
+        def at(yy, xx):
+            inside = (yy >= 0) & (yy < oh) & (xx >= 0) & (xx < ow)
+            return torch.where(inside, r[ch, yy.clamp(0, oh - 1), xx.clamp(0, ow - 1)], own)
+        return torch.stack([x, y], 1), torch.stack([own, at(y, x - 1), at(y, x + 1), at(y - 1, x), at(y + 1, x)], 1)
+
+    for title, mode, forward, shape, out_sizes, regions in geometries:
+        rects = regions if regions is not None else [(0, 0) + shape[2:]] * shape[0]
+        pixels = sum(h * w for h, w in out_sizes)
+        for dtype in (torch.float32, torch.bfloat16):
+            # smooth heatmaps (a coarse grid upsampled), as a head's are
+            x = torch.nn.functional.interpolate(torch.randn(shape[:2] + (8, 8), device="cuda", generator=gen), size=shape[2:], mode="bicubic").to(dtype)
+
+            def loop():
+                return [torch_steps(forward(x[i, :, y0:y0 + h, x0:x0 + w].float()[None], list(out_sizes[i]))[0]) for i, (y0, x0, h, w) in enumerate(rects)]
+
+            def values_then_torch():
+                return [torch_steps(r) for r in aa.resize_many_back(x, out_sizes, mode, regions=regions, out_dtype=torch.float32)]
+
+            a_key, c_key = f"a: loop: {forward.__name__}, flatten(1).argmax(1), gather per item", "c: resize_many_back_peaks"
+            contestants = {a_key: loop, c_key: lambda: aa.resize_many_back_peaks(x, out_sizes, mode, regions=regions),
+                           "b: resize_many_back(reduce=None, out_dtype=float32), the same torch steps per item": values_then_torch}
+            if args.quick:
+                contestants = {c_key: contestants[c_key]}
+            run = _run_contestants(args, torch, timed, contestants)
+            results = next(run)
+            note = "(c) alone"
+            if results.get(a_key) is not None and results[c_key] is not None:
+                differ = int((torch.stack([p for p, _ in results[a_key]]) != results[c_key][0]).any(-1).sum())
+                same = all(torch.equal(v.view(torch.int32), results[c_key][1][i].view(torch.int32)) for i, (_, v) in enumerate(results[a_key]))
+                note = f"the peaks of (a) and (c) differ at {differ} of {shape[0] * k} channels; the values' bits are {'the same' if same else 'NOT the same'}"
+            del results
+            print(f"\ngeometry {title}, {mode}, {pixels / 1e6:.1f} M output pixels a channel, {str(dtype).replace('torch.', '')}: {note}")
+            stat = next(run)
+            for other, what in (("a", "the loop"), ("b", "values, then torch")):
+                _against(stat, "c", other, f"(c) against {what}")
+            del x
+            torch.cuda.empty_cache()
+
+
 def instances_rle(args, torch, aa, timed):
     """--instances-rle: resize_many_back_instances_rle on --instances' geometry and masks.  (a) the run-length call, max_runs the power
     of two at or above the largest nruns of the configuration; (b), (c) resize_many_back_instances with bool masks and with packed bits
@@ -1703,7 +1773,10 @@ def main():
                     "and 20 instances an item, against the per-item torch loop and against two resize_many_back calls plus torch reductions")
     ap.add_argument("--instances-rle", action="store_true", help="only resize_many_back_instances_rle on --instances' geometry: against "
                     "resize_many_back_instances alone and with its masks copied to pinned host memory; the distribution of nruns")
-    ap.add_argument("--quick", action="store_true", help="with --confusion: K = 19 and bfloat16 only (the sweep of the kernel's tunables)")
+    ap.add_argument("--peaks", action="store_true", help="only resize_many_back_peaks: per channel the argmax over space and five values, on "
+                    "Keypoint R-CNN's geometry and on --logits', against the per-item loop and against resize_many_back plus torch")
+    ap.add_argument("--quick", action="store_true", help="with --confusion: K = 19 and bfloat16 only (the sweep of the kernel's tunables); "
+                    "with --peaks: the call alone")
     ap.add_argument("--noise-targets", action="store_true", help="with --confusion: targets uniform per pixel, the counting's worst case, "
                     "instead of 64 x 64 blocks of one class")
     ap.add_argument("--rate-only", action="store_true", help="with --gap: only the reduce kernels' own rate (dense against ragged)")
@@ -1824,6 +1897,9 @@ def main():
         return
     if args.instances_rle:
         instances_rle(args, torch, aa, timed)
+        return
+    if args.peaks:
+        peaks(args, torch, aa, timed)
         return
     if args.logits:
         (logits_activation if args.activation else logits)(args, torch, aa, timed)
