@@ -36,6 +36,7 @@ extern "C" {
                                    aa_back_merged_confusion_desc_bytes, aa_back_confusion_plan, aa_back_merged_confusion_plan,
                                    aa_resample_back_confusion, with aa_back_target; aa_back_queries_desc_bytes,
                                    aa_back_queries_plan, aa_resample_back_queries, with aa_back_weights;
+                                   aa_back_queries_merged_desc_bytes, aa_back_queries_merged_plan, aa_resample_back_queries_merged;
                                    aa_back_panoptic_desc_bytes, aa_back_panoptic_plan, aa_resample_back_panoptic, with
                                    aa_back_panoptic_io; aa_back_instances_desc_bytes, aa_back_instances_plan,
                                    aa_resample_back_instances, with aa_back_instances_io; aa_back_instances_rle_desc_bytes,
@@ -807,6 +808,41 @@ int aa_back_queries_plan(int filter, int layout, int64_t n, int64_t Q, int64_t C
                          size_t *arena_bytes, int64_t *out_offsets /* n, bytes */);
 int aa_resample_back_queries(const void *desc_host, const void *desc_dev, int in_dtype, void *arena_dev, size_t arena_bytes, void *workspace_dev,
                              size_t workspace_bytes, aa_stream_t stream);
+
+/* ---- ... merged: the n items are members of G groups, each with its own weights, summed per group on the matrix unit -------------------
+ * Test-time augmentation for mask-classification heads: every pass answers Q masks and its own [Q, C] class distribution, and the
+ * passes' scores are added before the one argmax.  Item i is a member of group group_of[i] as in aa_back_merged_plan (any order, no
+ * empty group, every member with its group's oh, ow), with P_i and Wh_i exactly the section above's operands of item i at that size,
+ * and with i_0 < ... < i_{M-1} the members of group g
+ *   S_g[c, y, x] = sum over j, sum over q, of Wh_{i_j}[q, c] * P_{i_j}[q, y, x]
+ * every product exact and the whole sum taken in fp32 on the matrix unit in an order that is the kernel's own: S_g lies within
+ * M * Q * 2^-23 * sum |Wh * P| of the exact sum of the rounded operands.  merge 1 (mean) divides every fp32 S_g once by (float)M,
+ * correctly rounded, before the store and before the argmax; merge 0 (sum) does not.  Group g of the arena is reduce 0 or 1 of S_g as
+ * the section above states them, at byte out_offsets[g].  A NaN in any member makes S_g NaN in every class of that pixel and of no
+ * other.  A group of one member is aa_resample_back_queries' item bit for bit, for both merges.
+ * aa_back_queries_merged_plan is host arithmetic only.  Its block is aa_back_merged_plan's sections after a header of its own, then
+ * one weight record per member; desc_bytes >= aa_back_queries_merged_desc_bytes(n, G).  The workspace is aa_back_many_plan's tables for
+ * the same items, rounded up to 16 bytes, then per member its weights as float16 in the matrix instruction's operand order,
+ * [member][class block of 32][query step of 16][64 lanes][8 halves], 2 bytes times C rounded up to 32 times Q rounded up to 16 a
+ * member, classes >= C and queries >= Q as +0.  Errors in aa_back_merged_plan's order with K = Q and aa_back_queries_plan's additions
+ * in their places: AA_ERR_BAD_SHAPE beside n, G and merge for Q, C or the reduce, then for the label type, then for weights whose
+ * packing takes more workgroups than one grid holds; `weights` beside the pointers; per member, after its own checks and its size
+ * against its group's, AA_ERR_NULL and AA_ERR_STRIDES for its weights; per group AA_ERR_BAD_SHAPE for C * oh * ow beyond 2^40, the arena
+ * and the work units; last AA_ERR_BAD_DTYPE.
+ * aa_resample_back_queries_merged enqueues TWO launches whatever n, G, M and the sizes: the table kernel, whose further workgroups pack
+ * the weights, and a resample with one workgroup per work unit of a group (an output row times 256 columns): a wave resamples member
+ * after member into the same LDS tile and multiplies each there into accumulators that stay in registers across the members, for 1, 3
+ * or 6 blocks of 32 classes at a time (C beyond 192 walks the members once per 192 classes).  Parameters and checks as
+ * aa_resample_back_queries', in their order.  Nothing is allocated, synchronised or read back, and no table cache is touched.  n == 0
+ * launches nothing.  Not built: an activation other than the sigmoid, confusion matrices, per-member scalar weights, a maximum instead
+ * of the sum, a backward.  Added without an ABI version change (additive). */
+size_t aa_back_queries_merged_desc_bytes(int64_t n, int64_t g);
+int aa_back_queries_merged_plan(int filter, int layout, int64_t n, int64_t Q, int64_t C, const aa_back_item *items,
+                                const aa_back_weights *weights /* n */, int64_t G, const int64_t *group_of /* n */, int merge /* 0 sum, 1 mean */,
+                                int reduce /* 0 values, 1 argmax */, int out_dtype, void *desc_host, size_t desc_bytes, size_t *workspace_bytes,
+                                size_t *arena_bytes, int64_t *out_offsets /* G, bytes */);
+int aa_resample_back_queries_merged(const void *desc_host, const void *desc_dev, int in_dtype, void *arena_dev, size_t arena_bytes,
+                                    void *workspace_dev, size_t workspace_bytes, aa_stream_t stream);
 
 /* ---- ragged predictions back, panoptic inference: Q resampled masks and Q scores to a segment map and per-query areas ------------------
  * Panoptic inference of MaskFormer-style heads, per image: the sigmoid of the resampled masks times the query scores, the argmax over

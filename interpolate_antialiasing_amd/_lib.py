@@ -67,6 +67,7 @@ EXPORTS = (
     "aa_back_confusion_desc_bytes", "aa_back_merged_confusion_desc_bytes", "aa_back_confusion_plan", "aa_back_merged_confusion_plan",
     "aa_resample_back_confusion",
     "aa_back_queries_desc_bytes", "aa_back_queries_plan", "aa_resample_back_queries",
+    "aa_back_queries_merged_desc_bytes", "aa_back_queries_merged_plan", "aa_resample_back_queries_merged",
     "aa_back_panoptic_desc_bytes", "aa_back_panoptic_plan", "aa_resample_back_panoptic",
     "aa_back_instances_desc_bytes", "aa_back_instances_plan", "aa_resample_back_instances",
     "aa_back_instances_rle_desc_bytes", "aa_back_instances_rle_plan", "aa_launch_back_instances_rle",
@@ -302,6 +303,14 @@ class BackQueryWeights(ctypes.Structure):
     _fields_ = [("w", ctypes.c_void_p), ("stride_q", ctypes.c_int64), ("stride_c", ctypes.c_int64), ("reserved", ctypes.c_int64)]
 
 
+class BackQueriesMergedHeader(ctypes.Structure):
+    """Head of the block aa_back_queries_merged_plan writes (csrc/aa_many_back_queries_merged.h AABackQueriesMergedHeader; opaque to C
+    callers, mirrored for the tests)."""
+    _fields_ = [("magic", ctypes.c_int32), ("n", ctypes.c_int32), ("Q", ctypes.c_int32), ("filter", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("reduce", ctypes.c_int32), ("out_dtype", ctypes.c_int32), ("C", ctypes.c_int32), ("units", ctypes.c_int64),
+                ("ws_bytes", ctypes.c_int64), ("arena_bytes", ctypes.c_int64), ("G", ctypes.c_int32), ("merge", ctypes.c_int32)]
+
+
 class BackPanopticIO(ctypes.Structure):
     """aa_back_panoptic_io: the scores, ids, void and threshold of the panoptic call (strides in ELEMENTS; ids_dev None: the query's index)."""
     _fields_ = [("scores_dev", ctypes.c_void_p), ("scores_stride_n", ctypes.c_int64), ("scores_stride_q", ctypes.c_int64),
@@ -467,6 +476,14 @@ def back_merged_desc_view(buf, n: int, g: int):
     members = (ctypes.c_int32 * n).from_buffer(buf, at)
     at += (4 * n + 7) & ~7
     return hd, items, groups, members, (ctypes.c_int64 * (g + 1)).from_buffer(buf, at)
+
+
+def back_queries_merged_desc_view(buf, n: int, g: int):
+    """(header, items, groups, members, unit0, weights) of aa_back_queries_merged_plan's block held in a ctypes buffer:
+    back_merged_desc_view's sections after a BackQueriesMergedHeader (the same 64 bytes), then one BackQueryWeights per member."""
+    _, items, groups, members, unit0 = back_merged_desc_view(buf, n, g)
+    at = ctypes.sizeof(BackMergedHeader) + n * ctypes.sizeof(BackItem) + g * ctypes.sizeof(BackGroup) + ((4 * n + 7) & ~7) + 8 * (g + 1)
+    return BackQueriesMergedHeader.from_buffer(buf, 0), items, groups, members, unit0, (BackQueryWeights * n).from_buffer(buf, at)
 
 
 def back_conf_desc_view(buf, n: int, g=None):
@@ -685,6 +702,13 @@ def load() -> ctypes.CDLL:
     L.aa_back_queries_plan.restype = i32
     L.aa_resample_back_queries.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp]
     L.aa_resample_back_queries.restype = i32
+    L.aa_back_queries_merged_desc_bytes.argtypes = [i64, i64]
+    L.aa_back_queries_merged_desc_bytes.restype = sz
+    L.aa_back_queries_merged_plan.argtypes = [i32, i32, i64, i64, i64, ctypes.POINTER(BackItemIn), ctypes.POINTER(BackWeightsIn), i64,
+                                              ctypes.POINTER(i64), i32, i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(i64)]
+    L.aa_back_queries_merged_plan.restype = i32
+    L.aa_resample_back_queries_merged.argtypes = [vp, vp, i32, vp, sz, vp, sz, vp]
+    L.aa_resample_back_queries_merged.restype = i32
     L.aa_back_panoptic_desc_bytes.argtypes = [i64]
     L.aa_back_panoptic_desc_bytes.restype = sz
     L.aa_back_panoptic_plan.argtypes = [i32, i32, i64, i64, ctypes.POINTER(BackItemIn), i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz),

@@ -12,6 +12,7 @@
 #include "aa_many_back_bwd.h"
 #include "aa_many_back_confusion.h"
 #include "aa_many_back_queries.h"
+#include "aa_many_back_queries_merged.h"
 #include "aa_many_back_panoptic.h"
 #include "aa_many_back_instances.h"
 #include "aa_many_back_instances_rle.h"
@@ -700,6 +701,22 @@ int aa_resample_back_queries(const void *desc_host, const void *desc_dev, int in
                              size_t workspace_bytes, aa_stream_t stream) {
   if (!desc_host) return AA_ERR_NULL;
   return aa_launch_back_queries(desc_host, desc_dev, in_dtype, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- ... merged: the members of a group (test-time passes, each with its own weights) summed in the matrix unit's accumulators ----------
+size_t aa_back_queries_merged_desc_bytes(int64_t n, int64_t g) { return aa_back_queries_merged_desc_size(n, g); }
+
+int aa_back_queries_merged_plan(int filter, int layout, int64_t n, int64_t Q, int64_t C, const aa_back_item *items, const aa_back_weights *weights,
+                                int64_t G, const int64_t *group_of, int merge, int reduce, int out_dtype, void *desc_host, size_t desc_bytes,
+                                size_t *workspace_bytes, size_t *arena_bytes, int64_t *out_offsets) {
+  return aa_back_queries_merged_plan_host(filter, layout, n, Q, C, items, weights, G, group_of, merge, reduce, out_dtype, desc_host, desc_bytes,
+                                          workspace_bytes, arena_bytes, out_offsets);
+}
+
+int aa_resample_back_queries_merged(const void *desc_host, const void *desc_dev, int in_dtype, void *arena_dev, size_t arena_bytes,
+                                    void *workspace_dev, size_t workspace_bytes, aa_stream_t stream) {
+  if (!desc_host) return AA_ERR_NULL;
+  return aa_launch_back_queries_merged(desc_host, desc_dev, in_dtype, arena_dev, arena_bytes, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- ragged predictions back, panoptic inference: the winner among the kept queries, per-query areas, the overlap test ------------------

@@ -1997,7 +1997,7 @@ def _back_class_weights(name: str, class_weights, n: int, q: int, dev):
 
 
 def resize_many_back_queries(masks, class_weights, sizes, mode: str = "bilinear", *, regions=None, flips=None, reduce: Optional[str] = "argmax",
-                             out_dtype=None):
+                             out_dtype=None, groups=None, merge: str = "sum"):
     """The way back for mask-classification heads — MaskFormer, Mask2Former, OneFormer and the semantic heads on SAM-style decoders —
     whose semantic inference at every image's own size is: resample the Q mask logits, take the sigmoid,
     ``einsum("qc,qhw->chw", class_probs, mask_probs)``, argmax over C.  ``masks``, ``sizes``, ``mode``, ``regions`` and ``flips`` are
@@ -2025,22 +2025,52 @@ def resize_many_back_queries(masks, class_weights, sizes, mode: str = "bilinear"
     sizes — the table kernel, and a resample whose waves keep the float16 probabilities of their 64 pixels in LDS and multiply them
     there by the weights, 32 classes at a time — no workspace beyond the tables, nothing read back, no synchronisation.
 
+    ``groups``: None, or N integers in 0 .. G - 1 as ``resize_many_back_merged`` takes them — test-time augmentation, item i one pass
+    (a scale, mirrored or not) over image ``groups[i]``.  ``sizes`` then holds one pair per GROUP, every member of group g is resampled
+    to ``sizes[g]`` and un-mirrored where ``flips[i]``, ``class_weights`` stays per item (every pass has its own class distribution),
+    and with ``i_0 < ... < i_{M-1}`` the members of g
+
+        ``S_g[c, y, x] = sum_j sum_q Wh_{i_j}[q, c] * P_{i_j}[q, y, x]``
+
+    — the same float16 operands, the sum over (member, query) ONE inner dimension of the matrix unit's fp32 accumulation, within
+    ``M * Q * 2^-23 * sum |Wh * P|`` of the exact sum.  ``merge="mean"`` divides every fp32 ``S_g`` once by ``float32(M)``, correctly
+    rounded, before the store and before the argmax; ``merge`` other than ``"sum"`` without ``groups`` is a ``ValueError``.  The result
+    is G tensors, ``reduce`` and ``out_dtype`` as above.  A NaN logit in any member makes its pixel NaN in every class (label 0) and
+    touches no other pixel; a group of one member is the un-grouped call's item bit for bit, for both merges.  Still two launches: the
+    table kernel also packs every member's weights once as float16 in the matrix instruction's operand order (2 bytes x C rounded up
+    to 32 x Q rounded up to 16 a member, behind the tables of the workspace), and a wave of the resample rewrites its LDS tile member
+    after member while the accumulators of 1, 3 or 6 blocks of 32 classes stay in registers — C <= 192 is resampled once, a larger C
+    once per 192 classes; LDS does not grow with M, a group may have any number of members, and no member's scores are ever stored.
+
     Not differentiable: with ``reduce=None``, gradients enabled and a ``masks`` or ``class_weights`` that requires grad the call raises
-    ``NotImplementedError`` — call it under ``torch.no_grad()`` or pass ``.detach()``.  Not built: ``groups=`` (merged test-time
-    passes), confusion matrices (panoptic inference: ``resize_many_back_panoptic``; instance inference:
-    ``resize_many_back_instances``)."""
+    ``NotImplementedError`` — call it under ``torch.no_grad()`` or pass ``.detach()``.  Not built: an ``activation=`` option (the
+    sigmoid is the call's), confusion matrices — for ``groups`` as without — per-member scalar weights, a maximum instead of the sum
+    (panoptic inference: ``resize_many_back_panoptic``; instance inference: ``resize_many_back_instances``)."""
     name = "resize_many_back_queries"
     if mode not in _lib.FILTER_IDS:
         raise ValueError(mode)
     if reduce not in (None, "argmax"):
         raise ValueError(f"{name}(): reduce must be 'argmax' or None, got {reduce!r}")
+    if merge not in _lib.BACK_MERGE:
+        raise ValueError(f"{name}(): merge must be 'sum' or 'mean', got {merge!r}")
+    if groups is None and merge != "sum":
+        raise ValueError(f"{name}(): merge={merge!r} needs groups: without groups there is nothing to merge")
     if not isinstance(masks, torch.Tensor) and len(masks) == 0:
         return []
     items, _, n, q = _back_items(name, masks, None)
     if q > _lib.BACK_QUERIES_MAX:
         raise ValueError(f"{name}(): Q must be in 1 .. {_lib.BACK_QUERIES_MAX}, got Q = {q}")
     ws, c = _back_class_weights(name, class_weights, n, q, items[0].device if items else None)
-    sizes = _back_sizes(name, sizes, n, max(q, c))
+    if groups is not None:
+        try:
+            sizes = list(sizes)
+        except TypeError:
+            raise ValueError(f"{name}(): sizes must be G pairs (oh, ow), got {sizes!r}") from None
+        out_sizes = _back_sizes(name, sizes, len(sizes), max(q, c))
+        groups, _ = _back_groups(name, groups, n, len(out_sizes))
+        sizes = [out_sizes[g] for g in groups]  # (every member at its group's size)
+    else:
+        sizes = _back_sizes(name, sizes, n, max(q, c))
     rects = _back_regions(name, regions, items)
     flips = _many_flips(name, flips, n)
     reduce_id, out_dtype, out_id, _ = _back_out(name, reduce, out_dtype, 0.0, items, c)
@@ -2062,18 +2092,29 @@ def resize_many_back_queries(masks, class_weights, sizes, mode: str = "bilinear"
         wrecs[i].stride_c = w.stride(1) if c > 1 else 0
     layout = _lib.NHWC if interleaved else _lib.NCHW
     L = _lib.load()
-    arena_bytes, offs = ctypes.c_size_t(0), (ctypes.c_int64 * n)()
+    arena_bytes = ctypes.c_size_t(0)
     es = torch.empty((), dtype=out_dtype).element_size()
+    if groups is None:
+        out_sizes, offs = sizes, (ctypes.c_int64 * n)()
+        desc_bytes, resample = L.aa_back_queries_desc_bytes(n), L.aa_resample_back_queries
 
-    def planner(desc, nbytes, ws_bytes):
-        return L.aa_back_queries_plan(_lib.FILTER_IDS[mode], layout, n, q, c, recs, wrecs, reduce_id, out_id, desc, nbytes, ws_bytes,
-                                      ctypes.byref(arena_bytes), offs)
+        def planner(desc, nbytes, ws_bytes):
+            return L.aa_back_queries_plan(_lib.FILTER_IDS[mode], layout, n, q, c, recs, wrecs, reduce_id, out_id, desc, nbytes, ws_bytes,
+                                          ctypes.byref(arena_bytes), offs)
+    else:
+        g = len(out_sizes)
+        offs, group_of = (ctypes.c_int64 * g)(), (ctypes.c_int64 * n)(*groups)
+        desc_bytes, resample = L.aa_back_queries_merged_desc_bytes(n, g), L.aa_resample_back_queries_merged
+
+        def planner(desc, nbytes, ws_bytes):
+            return L.aa_back_queries_merged_plan(_lib.FILTER_IDS[mode], layout, n, q, c, recs, wrecs, g, group_of, _lib.BACK_MERGE[merge], reduce_id,
+                                                 out_id, desc, nbytes, ws_bytes, ctypes.byref(arena_bytes), offs)
     arena = _many_run(
-        name, dev, L.aa_back_queries_desc_bytes(n), planner, lambda: torch.empty((arena_bytes.value // es,), dtype=out_dtype, device=dev),
-        lambda desc_host, desc_dev, out, wsp, stream: L.aa_resample_back_queries(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], out.data_ptr(),
-                                                                                 out.numel() * es, wsp.data_ptr(), wsp.numel(), stream))[0]
+        name, dev, desc_bytes, planner, lambda: torch.empty((arena_bytes.value // es,), dtype=out_dtype, device=dev),
+        lambda desc_host, desc_dev, out, wsp, stream: resample(desc_host, desc_dev, _DTYPE_IDS[items[0].dtype], out.data_ptr(), out.numel() * es,
+                                                               wsp.data_ptr(), wsp.numel(), stream))[0]
     del keep
-    return _back_views(arena, offs, sizes, reduce, c)
+    return _back_views(arena, offs, out_sizes, reduce, c)
 
 
 _PANOPTIC_DTYPES = {torch.uint8: (_lib.U8, 0, 255), torch.int16: (_lib.I16, -2 ** 15, 2 ** 15 - 1), torch.int32: (_lib.I32, -2 ** 31, 2 ** 31 - 1),

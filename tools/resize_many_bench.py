@@ -153,6 +153,8 @@ the same bits.  The kernel's fetched bytes come from a counter run of its own: t
                                                          # masks (at instances_rle()); profiles/resize_many_back_instances_rle.txt
   python tools/resize_many_bench.py --queries --rounds 5 --batches 3 > out.txt   # only resize_many_back_queries: Q = 100 masks, sigmoid,
                                                          # class weights, argmax (at queries()); profiles/resize_many_back_queries.txt
+  python tools/resize_many_bench.py --queries --tta --rounds 5 --batches 3 > out.txt   # only resize_many_back_queries(groups=...): 6 passes
+                                                         # per image (at queries_tta()); profiles/resize_many_back_queries_merged.txt
   python tools/resize_many_bench.py --logits-backward > out.txt   # only the gradients' way back to the canvas (above);
                                                          # profiles/resize_many_back_bwd.txt
   python tools/resize_many_bench.py --trace 20           # only resize_many, 20 calls after 3 warm-up calls (run it under a profiler's
@@ -1284,6 +1286,83 @@ def queries(args, torch, aa, timed):
             torch.cuda.empty_cache()
 
 
+def queries_tta(args, torch, aa, timed):
+    """--queries --tta: mask-classification semantic inference with test-time augmentation on --tta's geometry (16 camera-sized images,
+    6 passes each: three canvases, plain and mirrored), Q = 100, C = 19 and 150, float32 and bfloat16 masks, int64 labels, every pass
+    with class weights of its own.  (a) is the loop a user writes: per member linear_forward, sigmoid, einsum, flip, add; argmax per
+    image.  (b) is this package without groups=: M un-grouped calls with reduce=None, torch adds, argmax.  (c) is
+    resize_many_back_queries(groups=...).  (d), the yardstick, is ONE un-grouped call over the first pass (a sixth of the resampling).
+    The labels of (a) and (c) are compared and the share that differs reported, not asserted."""
+    from interpolate_antialiasing_amd import boxmath
+
+    n, canvases, q = 16, (384, 512, 640), 100
+    rng = np.random.default_rng(SEED)
+    shapes = [(int(rng.integers(1080, 3001)), int(rng.integers(1440, 4001))) for _ in range(N)][:n]
+    passes = [(c, flip) for c in canvases for flip in (False, True)]
+    regions, flips, groups = [], [], []
+    for c, flip in passes:  # (a batch is laid out pass by pass: the groups interleave)
+        regions += boxmath.placed_regions(boxmath.fit_sizes(shapes, longer=c), "center", (c, c))
+        flips += [flip] * n
+        groups += list(range(n))
+    pixels, m = sum(h * w for h, w in shapes), len(passes)
+    print(f"resize_many_bench --queries --tta: N = {n} camera-sized images, H in [1080, 3000], W in [1440, 4000] (seed {SEED}), {pixels / 1e6:.1f} M "
+          f"output pixels, each from M = {m} passes: [N, Q = {q}, c, c] mask logits on letterbox canvases c = {', '.join(map(str, canvases))} "
+          f"(fit_sizes(longer=c), 'center'), plain and mirrored; bilinear; per pass sigmoid and einsum with its own [Q, C] class probabilities, "
+          f"summed, argmax over C, int64 labels; library: {os.path.basename(_lib_path())}")
+    print(f"{args.rounds} rounds of {args.batches} batches per contestant, alternating; ms per batch: median [min .. max]; peak: the growth of "
+          "torch.cuda.max_memory_allocated over one call")
+    gen = torch.Generator(device="cuda").manual_seed(SEED)
+    for c in (19, 150):
+        for dtype in (torch.float32, torch.bfloat16):
+            batches = [torch.randn((n, q, cv, cv), device="cuda", generator=gen).to(dtype) for cv, _ in passes]
+            items = [b[i] for b in batches for i in range(n)]
+            w = torch.randn((m * n, q, c + 1), device="cuda", generator=gen).softmax(-1)[..., :c]
+
+            def loop():
+                out = []
+                for i in range(n):
+                    s = None
+                    for j in range(i, m * n, n):
+                        y0, x0, h, ww = regions[j]
+                        p = aa.linear_forward(items[j][:, y0:y0 + h, x0:x0 + ww].float()[None], list(shapes[i]))[0].sigmoid_()
+                        r = torch.einsum("qc,qhw->chw", w[j], p)
+                        r = r.flip(-1) if flips[j] else r
+                        s = r if s is None else s.add_(r)
+                    out.append(s.argmax(0))
+                return out
+
+            def ungrouped_calls():
+                s = None
+                for p in range(m):
+                    sl = slice(p * n, (p + 1) * n)
+                    r = aa.resize_many_back_queries(batches[p], w[sl], shapes, regions=regions[sl], flips=flips[sl], reduce=None, out_dtype=torch.float32)
+                    s = r if s is None else [a.add_(b) for a, b in zip(s, r)]
+                return [a.argmax(0) for a in s]
+
+            def merged():
+                return aa.resize_many_back_queries(items, w, shapes, regions=regions, flips=flips, groups=groups)
+
+            def one_pass():
+                return aa.resize_many_back_queries(batches[0], w[:n], shapes, regions=regions[:n])
+
+            a_key, c_key = "a: loop: linear_forward, sigmoid, einsum, flip, add per member; argmax per image", "c: resize_many_back_queries(groups=...)"
+            contestants = {a_key: loop, c_key: merged, "b: M un-grouped calls with reduce=None, torch adds, argmax": ungrouped_calls,
+                           "d: ONE un-grouped call over the first pass (the yardstick: a sixth of the resampling)": one_pass}
+            run = _run_contestants(args, torch, timed, contestants)
+            results = next(run)
+            note = "a contestant does not fit"
+            if results[a_key] is not None and results[c_key] is not None:
+                differ = sum(int((p != r).sum()) for p, r in zip(results[a_key], results[c_key]))
+                note = f"the labels of (a) and (c) differ at {differ} of {pixels} pixels ({100.0 * differ / pixels:.4f} %)"
+            del results
+            print(f"\nQ = {q}, C = {c}, {str(dtype).replace('torch.', '')} masks: {note}")
+            stat = next(run)
+            for other, what in (("a", "the loop"), ("b", "M un-grouped calls"), ("d", "one un-grouped pass")):
+                _against(stat, "c", other, f"the call against {what}")
+            del batches, items, w
+            torch.cuda.empty_cache()
+
+
 def panoptic(args, torch, aa, timed):
     """--panoptic: panoptic inference on --queries' geometry, Q = 100 queries, float32 and bfloat16 masks, 10 and 100 kept queries an
     item, int32 maps, overlap_threshold 0.8.  (a) is the loop a user writes today: per item linear_forward, sigmoid, scale by the
@@ -1887,7 +1966,7 @@ def main():
         confusion(args, torch, aa, timed)
         return
     if args.queries:
-        queries(args, torch, aa, timed)
+        (queries_tta if args.tta else queries)(args, torch, aa, timed)
         return
     if args.panoptic:
         panoptic(args, torch, aa, timed)
